@@ -214,8 +214,13 @@ int tsf_fit_ragged_dev(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, const int6
 /* ---- predict --------------------------------------------------------------------------
  * yhat[n][h] = trend*(1+multiplicative)+additive in original units (float64).  If
  * yhat_int != NULL also the reference's post-step: (int) truncation toward zero, then
- * values below floor[n] replaced by floor[n] (prophet_scorer.py:73-84).
+ * values below floor[n] replaced by (int32_t)floor[n] (prophet_scorer.py:73-84).  A truncated
+ * value outside int32 saturates to INT32_MIN / INT32_MAX (NaN: INT32_MIN) before the floor
+ * clamp; the reference would instead fail the IntegerType cast of its output column there.
  * n_grids = 1 (aligned fit) or N.  ds_future: [H] if shared_future else [N][H].
+ * Every grid must satisfy 0 <= S <= min(spec->n_changepoints, TSF_MAX_S) and t_scale_ns > 0,
+ * its t_change[0 .. S) ascending: tsf_predict and tsf_predict_intervals reject other grids
+ * before any launch; the _dev entries cannot read device-resident grids and require it.
  * extra_future: [n_extra][H] (shared) or [N][n_extra][H]; NULL if n_extra == 0.
  * floor/cap: the values the caller puts in the future frame (prophet_scorer.py:67-68). */
 int tsf_predict(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H, const double *theta,

@@ -1284,6 +1284,28 @@ extern "C" int tsf_eval_quadratic(tsf_ctx *ctx, const tsf_spec *spec, int64_t N,
 
 // ---- predict ----------------------------------------------------------------------------------
 
+// The grids a host-memory predict entry is handed are caller data (model blobs read back from storage):
+// checked before anything is copied or launched.  S beyond the spec's n_changepoints would read beta as
+// delta; beyond TSF_MAX_S the kernel's LDS segment tables overflow.
+static int check_grids(tsf_ctx *ctx, const tsf_spec *spec, const tsf_grid_info *grid, int32_t n_grids)
+{
+    for (int32_t g = 0; g < n_grids; ++g) {
+        const tsf_grid_info &gi = grid[g];
+        const char *why = nullptr;
+        if (gi.S < 0) why = "S < 0";
+        else if (gi.S > spec->n_changepoints) why = "S > the spec's n_changepoints";
+        else if (gi.S > TSF_MAX_S) why = "S > TSF_MAX_S";
+        else if (gi.t_scale_ns <= 0) why = "t_scale_ns <= 0";
+        if (why) {
+            char msg[160];
+            snprintf(msg, sizeof(msg), "grid[%d]: %s (S = %d, t_scale_ns = %lld)", (int)g, why, (int)gi.S,
+                     (long long)gi.t_scale_ns);
+            return fail(ctx, msg);
+        }
+    }
+    return 0;
+}
+
 // predict_kernel on the series [n0, n0 + n) of the caller's arrays.  A shared future grid gets its
 // design table built first (once per call: tab_ready), in the context's own buffer.
 static int launch_predict(tsf_ctx *ctx, const DevSpec &hs, PredictArgs a, int64_t n0, int64_t n, bool *tab_ready,
@@ -1362,6 +1384,7 @@ extern "C" int tsf_predict(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_
     if (N <= 0 || H <= 0) return fail(ctx, "N and H must be > 0");
     if (!spec || !theta || !y_scale || !grid || !ds_future || !yhat) return fail(ctx, "NULL input");
     if (n_grids != 1 && n_grids != N) return fail(ctx, "n_grids must be 1 or N");
+    if (int rc = check_grids(ctx, spec, grid, n_grids)) return rc;
     const int stride = tsf_theta_stride(spec);
     const size_t nfut = shared_future ? (size_t)H : (size_t)N * H;
     DevBuf d_th, d_ys, d_grid, d_ds, d_fl, d_cap, d_ex, d_yh, d_yi;
@@ -1504,6 +1527,7 @@ extern "C" int tsf_predict_intervals(tsf_ctx *ctx, const tsf_spec *spec, int64_t
     if (N <= 0 || H <= 0) return fail(ctx, "N and H must be > 0");
     if (!spec || !theta || !y_scale || !grid || !ds_future || !yhat || !yhat_lower || !yhat_upper) return fail(ctx, "NULL input");
     if (n_grids != 1 && n_grids != N) return fail(ctx, "n_grids must be 1 or N");
+    if (int rc = check_grids(ctx, spec, grid, n_grids)) return rc;
     const int stride = tsf_theta_stride(spec);
     const size_t nfut = shared_future ? (size_t)H : (size_t)N * H;
     DevBuf d_th, d_ys, d_grid, d_ds, d_fl, d_cap, d_ex, d_key, d_yh, d_lo, d_hi;

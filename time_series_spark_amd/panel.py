@@ -376,6 +376,7 @@ def load_models(blobs):
         rec = np.frombuffer(b''.join(bodies), dtype=dt)
         if (rec['n_theta'] != nth).any() or (rec['n_tchange'] != ntc).any():
             raise ValueError('inconsistent model blobs')
+        _check_grids(rec)
         spec = json.loads(pre[12:].decode())
         out.append((spec, np.asarray(pos, dtype=np.int64), rec))
     return out
@@ -397,7 +398,16 @@ def _load_uniform(arr):
     rec = np.ascontiguousarray(arr[:, pl:]).view(dt).reshape(n)
     if (rec['n_theta'] != nth).any() or (rec['n_tchange'] != ntc).any():
         raise ValueError('inconsistent model blobs')
+    _check_grids(rec)
     return [(json.loads(pre[12:].decode()), np.arange(n, dtype=np.int64), rec)]
+
+
+def _check_grids(rec):
+    """A record's changepoint count must fit the t_change it carries: predict would otherwise read
+    coefficients as changepoint deltas, or past its tables (the predict entries check the rest of a grid)."""
+    S = rec['S']
+    if (S < 0).any() or (S > rec['n_tchange']).any() or (S > _lib.MAX_S).any():
+        raise ValueError('model blob: changepoint count S out of range (S must be in [0, n_tchange])')
 
 
 def model_column_arrow(buf):
