@@ -259,6 +259,85 @@ int tsf_predict_intervals_dev(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int
                               uint64_t seed, double *yhat, double *yhat_lower, double *yhat_upper,
                               void *stream);
 
+/* ---- cross-validation ---------------------------------------------------------------------
+ * fbprophet 0.5 diagnostics.cross_validation + performance_metrics for a whole panel: every series is refitted at
+ * several cutoffs and each fold's forecast is scored against the rows held out after its cutoff.  The semantics are
+ * restated from recall of fbprophet 0.5's diagnostics.py; parity with the real package is not pinned by any test.
+ *
+ * Cutoffs, per series (generate_cutoffs; times int64 ns):
+ *   the first is max(ds) - horizon (before min(ds): status TSF_CV_LESS_THAN_HORIZON); step back by period while the
+ *   last cutoff is >= min(ds) + initial; where (cutoff, cutoff + horizon] holds no row, jump to (the last ds <= cutoff)
+ *   - horizon; drop the last cutoff appended (none left: TSF_CV_NO_CUTOFF); ascending order.
+ * Fold c of a series fits rows ds <= cutoff_c (fewer than 2: TSF_CV_TOO_FEW, the series gets no fold at all) with the
+ * call's tsf_spec -- prophet_copy keeps the seasonalities of the full-history model; its scales and changepoints come
+ * from the shorter history -- and predicts the rows in (cutoff_c, cutoff_c + horizon] with their own extra columns and
+ * the series' floor / cap.  Since ds is sorted, those are rows [hist_rows, hist_rows + hold_rows) of the series.
+ *
+ * Optimiser: spec->algorithm = TSF_ALGO_AUTO is fbprophet's rule PER FOLD -- Newton for a fold history of fewer than
+ * TSF_NEWTON_BELOW_T rows, L-BFGS otherwise, and Newton once more for a fold whose L-BFGS fit ended in TSF_ST_LSFAIL,
+ * TSF_ST_INIT_NONFINITE or TSF_ST_EVAL_LIMIT (models of at most TSF_MAX_P parameters; wider models stay on L-BFGS).
+ * TSF_ALGO_LBFGS / TSF_ALGO_NEWTON run every fold on that optimiser and retry nothing.  A fold's fit outputs are those
+ * of tsf_fit_ragged on the explicitly cut prefix panel, bit for bit.
+ *
+ * Intervals (n_samples > 0): tsf_predict_intervals with series_key of fold c of series n =
+ *   (int64_t)((uint64_t)key_n * 0x9E3779B97F4A7C15 + (uint64_t)c),   key_n = series_key[n] (NULL: n)
+ * -- independent of how series are batched; passing that key to tsf_predict_intervals reproduces the fold's interval.
+ *
+ * Metrics, per series over all its holdout rows (n of them), horizon = ds - cutoff:
+ *   w = clamp((int64_t)(rolling_window * n), 1, n); rows are grouped by distinct horizon into sums and counts, and
+ *   every distinct horizon h whose cumulative count (horizons ascending) reaches w gets one metric row: the mean over
+ *   the w rows of the window ending with h's group, the leftmost group of the window weighted partially (Prophet's
+ *   rolling_mean_by_h).  mse, rmse = sqrt(windowed mse), mae, mape (NaN for the whole series if min |y| < 1e-8),
+ *   coverage (fraction of rows with lower <= y <= upper; only with intervals).
+ *   DELIBERATE DEVIATION: fbprophet 0.5 itself takes a row-wise rolling mean of w rows after an unstable sort by
+ *   horizon, so on an aligned panel (C rows at every horizon) its result depends on how those ties happen to be
+ *   ordered; the grouped form here does not.  The metric row count depends on the timestamps only (tsf_cv_plan).
+ *
+ * tsf_cv_plan (host only, no tsf_ctx, no device): aligned input (offsets NULL, ds [T], T >= 1) or ragged (T = 0,
+ * offsets [N+1], ds [offsets[N]]).  Fills per series n_folds / status (TSF_CV_*) / n_holdout (holdout rows over all
+ * folds) / n_metric (metric rows); cutoff / hist_rows / hold_rows are per fold, series by series (fold c of series n
+ * at index sum(n_folds[0 .. n)) + c), and may be NULL -- call once without them to size them.  Returns 0, -1 bad
+ * arguments.  args->period_ns <= 0 = horizon / 2, args->initial_ns < 0 = 3 * horizon (fbprophet's defaults);
+ * horizon_ns > 0, rolling_window in [0, 1] (performance_metrics' default 0.1).
+ *
+ * tsf_cross_validate: the whole cross-validation on this context's GPU; input as tsf_fit_aligned (T > 0, offsets
+ * NULL, y [N][T], extra [n_extra][T]) or tsf_fit_ragged (T = 0, offsets [N+1]); floor / cap [N] as there.  Outputs
+ * (host pointers, sized from tsf_cv_plan: F = sum n_folds, R = sum n_holdout, M = sum n_metric):
+ *   fit                 every member [F] (grid [F]), folds in plan order
+ *   yhat                [R] holdout rows fold by fold; yhat_lower / yhat_upper [R] with intervals, else unused
+ *   horizon_ns .. mape  [M] metric rows series by series, horizons ascending; coverage [M] with intervals
+ *   series_status       [N] TSF_CV_* of the plan, or TSF_CV_FIT_FAILED if a fold's final fit status is < 0 (its
+ *                       metric rows are then NaN)
+ * Pending cost hints (tsf_set_cost_hints) are discarded.  Returns 0, < 0 as every entry point.
+ * Reference interface replaced: none (the reference's jobs never cross-validate). */
+enum {
+    TSF_CV_OK = 0,
+    TSF_CV_LESS_THAN_HORIZON = -20,   /* max(ds) - horizon < min(ds) ("Less data than horizon.") */
+    TSF_CV_NO_CUTOFF = -21,           /* no cutoff after the initial window */
+    TSF_CV_TOO_FEW = -22,             /* fewer than 2 rows before a cutoff */
+    TSF_CV_FIT_FAILED = -23           /* a fold's fit failed (status < 0): Prophet would raise */
+};
+typedef struct {
+    int64_t horizon_ns;
+    int64_t period_ns;          /* <= 0: horizon / 2 */
+    int64_t initial_ns;         /* < 0: 3 * horizon */
+    double rolling_window;      /* 0.1 */
+} tsf_cv_args;
+typedef struct {
+    tsf_fit_out fit;
+    double *yhat, *yhat_lower, *yhat_upper;
+    int64_t *horizon_ns;
+    double *mse, *rmse, *mae, *mape, *coverage;
+    int32_t *series_status;
+} tsf_cv_out;
+int tsf_cv_plan(int64_t N, int32_t T, const int64_t *offsets, const int64_t *ds, const tsf_cv_args *args,
+                int32_t *n_folds, int32_t *status, int64_t *n_holdout, int64_t *n_metric, int64_t *cutoff,
+                int32_t *hist_rows, int32_t *hold_rows);
+int tsf_cross_validate(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t T, const int64_t *offsets,
+                       const int64_t *ds, const void *y, int32_t y_dtype, const double *floor, const double *cap,
+                       const double *extra, const tsf_cv_args *args, const int64_t *series_key, int32_t n_samples,
+                       double interval_width, uint64_t seed, tsf_cv_out *out);
+
 /* ---- scheduling hints ---------------------------------------------------------------------
  * A launch ends with its longest fits (cfg2: 1 582 evaluations against a mean of 454), and nothing
  * cheap about a series predicts how long its fit takes -- except an earlier fit of the same

@@ -91,6 +91,10 @@ int tsf_last_fit_kernel_ms(tsf_ctx *ctx, float *ms_out);
  * *sparse_columns = 1 if a wide model's indicator columns ran in sparse form (every grid qualified), 0 if the dense
  * kernels ran or the call was not a candidate.  Waits for the device; valid until the next fit call. */
 int tsf_last_fit_route(tsf_ctx *ctx, int32_t *sparse_columns);
+/* The last tsf_cross_validate call of this context: *n_grids = grid tables its fit launches built (sum over its
+ * launches: one per calendar class where folds share timestamp vectors, else one per fold), *n_launches = fit
+ * launches (Newton group, L-BFGS group, Newton retry). */
+int tsf_last_cv_grids(const tsf_ctx *ctx, int64_t *n_grids, int32_t *n_launches);
 
 #ifdef __cplusplus
 }

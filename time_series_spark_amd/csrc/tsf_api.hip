@@ -24,6 +24,8 @@
 #include "tsf_quad_kernels.h"
 #include "tsf_mfma_tabs.h"
 #include "tsf_launch.h"
+#include "tsf_cv_kernels.h"
+#include "tsf_cv_plan.h"
 
 using namespace tsf;
 
@@ -54,6 +56,9 @@ struct tsf_ctx {
     hipEvent_t ev0[TSF_PROFILE_RING], ev1[TSF_PROFILE_RING];
     int ev_created;
     long ev_count;          // profiled calls since profiling was enabled
+    int64_t last_n_grids;   // grid tables the last run_fit call built
+    int64_t cv_grids;       // tsf_last_cv_grids: grid tables / fit launches of the last tsf_cross_validate call
+    int32_t cv_launches;
 };
 
 #define HIP_TRY(ctx, expr)                                                                   \
@@ -94,6 +99,7 @@ extern "C" int tsf_create(int device_id, tsf_ctx **out)
     c->order_ev[0] = c->order_ev[1] = nullptr; c->order_busy[0] = c->order_busy[1] = 0;
     c->profiling = 0; c->ev_created = 0; c->ev_count = 0;
     c->last_sp_flag = nullptr;
+    c->last_n_grids = 0; c->cv_grids = 0; c->cv_launches = 0;
     for (int i = 0; i < TSF_OPT_COUNT; ++i) c->opt[i] = -1;
     if (hipMalloc((void **)&c->d_spec, sizeof(DevSpec)) != hipSuccess) { delete c; return -2; }
     {
@@ -427,6 +433,7 @@ static int run_fit(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int aligned, i
     // per distinct vector
     if (aligned || !grid_of || !grid_rows || n_distinct <= 0 || n_distinct >= N) { grid_of = nullptr; grid_rows = nullptr; n_distinct = 0; }
     const int64_t n_grids = aligned ? 1 : (grid_of ? n_distinct : N);
+    ctx->last_n_grids = n_grids;
     // quadratic (Gram) form of the data term: see tsf_quad_kernels.h
     // Stan's Newton optimiser (tsf_newton_kernels.h): explicitly, or by fbprophet's rule on the
     // longest series of the call
@@ -911,6 +918,92 @@ struct DevBuf {
 size_t ysize(int dt) { return dt == TSF_Y_F64 ? 8 : 4; }
 }  // namespace
 
+// Which of N timestamp vectors -- vector n = ds[start[n] .. start[n] + len[n]) -- are IDENTICAL (hash of the bytes, then
+// memcmp against the class's first member): gof[n] = class of vector n, classes numbered in order of their first member,
+// reps[k] = the first member of class k.  The one producer of the calendar classes of a ragged fit (fit_host_one) and of
+// the folds of a ragged cross-validation (tsf_cross_validate, where the vectors are prefixes of the caller's series).
+static void calendar_classes(const int64_t *ds, const int64_t *start, const int64_t *len, int64_t N,
+                             std::vector<int32_t> *gof_out, std::vector<int64_t> *reps_out)
+{
+    struct Key { int64_t len; uint64_t h; int64_t n; };
+    std::vector<Key> keys((size_t)N);
+    {
+        int hw = (int)std::thread::hardware_concurrency();
+        const int nt = hw < 1 ? 1 : (hw > 16 ? 16 : hw);
+        std::atomic<int64_t> next(0);
+        auto work = [&]() {
+            for (;;) {
+                const int64_t b = next.fetch_add(256);
+                if (b >= N) break;
+                for (int64_t n = b; n < N && n < b + 256; ++n) {
+                    const int64_t l = len[n];
+                    const uint64_t *p = (const uint64_t *)(ds + start[n]);
+                    uint64_t h = 0x9e3779b97f4a7c15ull ^ (uint64_t)l;
+                    for (int64_t i = 0; i < l; ++i) { h ^= p[i]; h *= 0xff51afd7ed558ccdull; h ^= h >> 32; }
+                    keys[(size_t)n] = Key{l, h, n};
+                }
+            }
+        };
+        if (nt <= 1 || N < 1024) work();
+        else {
+            std::vector<std::thread> th;
+            for (int i = 0; i < nt; ++i) th.emplace_back(work);
+            for (auto &x : th) x.join();
+        }
+    }
+    std::sort(keys.begin(), keys.end(), [](const Key &a, const Key &b) {
+        return a.len != b.len ? a.len < b.len : (a.h != b.h ? a.h < b.h : a.n < b.n);
+    });
+    std::vector<int64_t> rep((size_t)N);            // first member of the class of vector n
+    for (size_t i = 0; i < keys.size();) {
+        size_t j = i;
+        while (j < keys.size() && keys[j].len == keys[i].len && keys[j].h == keys[i].h) ++j;
+        // members of one (length, hash) run: classes by memcmp against the representatives found so far
+        std::vector<int64_t> reps;
+        for (size_t k = i; k < j; ++k) {
+            const int64_t n = keys[k].n;
+            int64_t r = -1;
+            for (int64_t c : reps)
+                if (memcmp(ds + start[c], ds + start[n], (size_t)keys[k].len * 8) == 0) { r = c; break; }
+            if (r < 0) { reps.push_back(n); r = n; }
+            rep[(size_t)n] = r;
+        }
+        i = j;
+    }
+    std::vector<int32_t> &gof = *gof_out, id_of((size_t)N, -1);
+    gof.assign((size_t)N, 0);
+    reps_out->clear();
+    for (int64_t n = 0; n < N; ++n) {
+        const int64_t r = rep[(size_t)n];
+        if (id_of[(size_t)r] < 0) {
+            id_of[(size_t)r] = (int32_t)reps_out->size();
+            reps_out->push_back(r);
+        }
+        gof[(size_t)n] = id_of[(size_t)r];
+    }
+}
+
+// The order in which a launch over calendar classes starts its series: grouped by grid, and the grouped list cut into 8
+// segments dealt out one position each in turn -- block b of a one-wave launch runs on XCD b % 8 (observed,
+// MI355X_MICROARCH: for speed only), so every XCD works its way through ITS segment and its 4 MB of L2 hold the two or
+// three grids its resident blocks are on, instead of a share of all of them (10 000 series on 91 grids, the reference's
+// model: 205 -> 172 ms, tools/bench_ragged.py).  Used when the caller gave no cost hints; results do not depend on the
+// order.
+static void calendar_start_order(const std::vector<int32_t> &gof, int64_t n_distinct, std::vector<int32_t> *ord_out)
+{
+    const int64_t N = (int64_t)gof.size();
+    std::vector<int32_t> byg((size_t)N), &ord = *ord_out;
+    ord.assign((size_t)N, 0);
+    std::vector<int64_t> start((size_t)n_distinct + 1, 0);
+    for (int64_t n = 0; n < N; ++n) start[(size_t)gof[(size_t)n] + 1]++;
+    for (int64_t g = 0; g < n_distinct; ++g) start[(size_t)g + 1] += start[(size_t)g];
+    for (int64_t n = 0; n < N; ++n) byg[(size_t)start[(size_t)gof[(size_t)n]]++] = (int32_t)n;
+    const int64_t seg = (N + 7) / 8;
+    int64_t q = 0;
+    for (int64_t i = 0; i < seg; ++i)
+        for (int x = 0; x < 8; ++x) { const int64_t k = (int64_t)x * seg + i; if (k < N) ord[(size_t)q++] = byg[(size_t)k]; }
+}
+
 static int fit_host_one(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int aligned, int32_t T,
                         const int64_t *offsets, const int64_t *ds, const void *y, int32_t y_dtype,
                         const double *floor_, const double *cap, const double *extra,
@@ -1010,85 +1103,21 @@ static int fit_host_one(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int align
     int64_t n_distinct = 0;
     {
         if (!aligned && !theta_in && spec->n_extra == 0 && N >= 2 && ctx->opt[TSF_OPT_GRID_SHARE] != 0) {
-            struct Key { int64_t len; uint64_t h; int64_t n; };
-            std::vector<Key> keys((size_t)N);
-            {
-                int hw = (int)std::thread::hardware_concurrency();
-                const int nt = hw < 1 ? 1 : (hw > 16 ? 16 : hw);
-                std::atomic<int64_t> next(0);
-                auto work = [&]() {
-                    for (;;) {
-                        const int64_t b = next.fetch_add(256);
-                        if (b >= N) break;
-                        for (int64_t n = b; n < N && n < b + 256; ++n) {
-                            const int64_t len = offsets[n + 1] - offsets[n];
-                            const uint64_t *p = (const uint64_t *)(ds + offsets[n]);
-                            uint64_t h = 0x9e3779b97f4a7c15ull ^ (uint64_t)len;
-                            for (int64_t i = 0; i < len; ++i) { h ^= p[i]; h *= 0xff51afd7ed558ccdull; h ^= h >> 32; }
-                            keys[(size_t)n] = Key{len, h, n};
-                        }
-                    }
-                };
-                if (nt <= 1 || N < 1024) work();
-                else {
-                    std::vector<std::thread> th;
-                    for (int i = 0; i < nt; ++i) th.emplace_back(work);
-                    for (auto &x : th) x.join();
-                }
-            }
-            std::sort(keys.begin(), keys.end(), [](const Key &a, const Key &b) {
-                return a.len != b.len ? a.len < b.len : (a.h != b.h ? a.h < b.h : a.n < b.n);
-            });
-            std::vector<int64_t> rep((size_t)N);            // first member of the class of series n
-            for (size_t i = 0; i < keys.size();) {
-                size_t j = i;
-                while (j < keys.size() && keys[j].len == keys[i].len && keys[j].h == keys[i].h) ++j;
-                // members of one (length, hash) run: classes by memcmp against the representatives found so far
-                std::vector<int64_t> reps;
-                for (size_t k = i; k < j; ++k) {
-                    const int64_t n = keys[k].n;
-                    int64_t r = -1;
-                    for (int64_t c : reps)
-                        if (memcmp(ds + offsets[c], ds + offsets[n], (size_t)keys[k].len * 8) == 0) { r = c; break; }
-                    if (r < 0) { reps.push_back(n); r = n; }
-                    rep[(size_t)n] = r;
-                }
-                i = j;
-            }
-            std::vector<int32_t> gof((size_t)N), id_of((size_t)N, -1);
+            std::vector<int64_t> vstart((size_t)N), vlen((size_t)N), reps;
+            for (int64_t n = 0; n < N; ++n) { vstart[(size_t)n] = offsets[n]; vlen[(size_t)n] = offsets[n + 1] - offsets[n]; }
+            std::vector<int32_t> gof;
+            calendar_classes(ds, vstart.data(), vlen.data(), N, &gof, &reps);
             std::vector<int64_t> grows;
-            for (int64_t n = 0; n < N; ++n) {
-                const int64_t r = rep[(size_t)n];
-                if (id_of[(size_t)r] < 0) {
-                    id_of[(size_t)r] = (int32_t)(grows.size() / 2);
-                    grows.push_back(offsets[r]);
-                    grows.push_back(offsets[r + 1] - offsets[r]);
-                }
-                gof[(size_t)n] = id_of[(size_t)r];
-            }
+            for (int64_t r : reps) { grows.push_back(offsets[r]); grows.push_back(offsets[r + 1] - offsets[r]); }
             n_distinct = (int64_t)(grows.size() / 2);
             if (n_distinct < N) {
                 HIP_TRY(ctx, d_gof.alloc(4 * (size_t)N));
                 HIP_TRY(ctx, d_grows.alloc(8 * grows.size()));
                 HIP_TRY(ctx, hipMemcpy(d_gof.p, gof.data(), 4 * (size_t)N, hipMemcpyHostToDevice));
                 HIP_TRY(ctx, hipMemcpy(d_grows.p, grows.data(), 8 * grows.size(), hipMemcpyHostToDevice));
-                // The order in which the launch starts the series: grouped by grid, and the grouped list cut into 8
-                // segments dealt out one position each in turn -- block b of a one-wave launch runs on XCD b % 8
-                // (observed, MI355X_MICROARCH: for speed only), so every XCD works its way through ITS segment and its
-                // 4 MB of L2 hold the two or three grids its resident blocks are on, instead of a share of all of them
-                // (10 000 series on 91 grids, the reference's model: 205 -> 172 ms, tools/bench_ragged.py).  Used
-                // when the caller gave no cost hints; results do not depend on the order.
-                std::vector<int32_t> byg((size_t)N), ord((size_t)N);
-                {
-                    std::vector<int64_t> start((size_t)n_distinct + 1, 0);
-                    for (int64_t n = 0; n < N; ++n) start[(size_t)gof[(size_t)n] + 1]++;
-                    for (int64_t g = 0; g < n_distinct; ++g) start[(size_t)g + 1] += start[(size_t)g];
-                    for (int64_t n = 0; n < N; ++n) byg[(size_t)start[(size_t)gof[(size_t)n]]++] = (int32_t)n;
-                    const int64_t seg = (N + 7) / 8;
-                    int64_t q = 0;
-                    for (int64_t i = 0; i < seg; ++i)
-                        for (int x = 0; x < 8; ++x) { const int64_t k = (int64_t)x * seg + i; if (k < N) ord[(size_t)q++] = byg[(size_t)k]; }
-                }
+                // the order in which the launch starts the series (calendar_start_order)
+                std::vector<int32_t> ord;
+                calendar_start_order(gof, n_distinct, &ord);
                 HIP_TRY(ctx, d_gord.alloc(4 * (size_t)N));
                 HIP_TRY(ctx, hipMemcpy(d_gord.p, ord.data(), 4 * (size_t)N, hipMemcpyHostToDevice));
             } else {
@@ -1718,5 +1747,300 @@ extern "C" int tsf_last_fit_kernel_ms(tsf_ctx *ctx, float *ms_out)
     int rc = tsf_profile_read(ctx, tmp, TSF_PROFILE_RING, &n);
     if (rc) return rc;
     *ms_out = tmp[n - 1];
+    return 0;
+}
+
+// ---- cross-validation (include/tsf.h) ---------------------------------------------------------------
+// The caller's panel crosses to the device once; every fit launch gets its fold panel from cv_expand_kernel (history
+// rows of its folds, cut on the device) and runs through run_fit like a ragged fit, its calendar classes handed in
+// (aligned input: fold c of every series is one calendar, known from the construction; ragged input: the prefixes of
+// the caller's series through calendar_classes, reading the caller's rows in place).  The fold results are scattered to
+// plan order, the holdout rows predicted by the predict (and interval) kernels in one call over every fold, and
+// cv_metrics_kernel reduces them per series.
+
+extern "C" int tsf_last_cv_grids(const tsf_ctx *ctx, int64_t *n_grids, int32_t *n_launches)
+{
+    if (!ctx || !n_grids || !n_launches) return -1;
+    *n_grids = ctx->cv_grids;
+    *n_launches = ctx->cv_launches;
+    return 0;
+}
+
+extern "C" int tsf_cross_validate(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t T, const int64_t *offsets,
+                                  const int64_t *ds, const void *y, int32_t y_dtype, const double *floor_,
+                                  const double *cap, const double *extra, const tsf_cv_args *args,
+                                  const int64_t *series_key, int32_t n_samples, double interval_width, uint64_t seed,
+                                  tsf_cv_out *out)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!spec || !ds || !y || !out || !out->series_status) return fail(ctx, "NULL input");
+    if (y_dtype < TSF_Y_F64 || y_dtype > TSF_Y_I32) return fail(ctx, "bad y_dtype");
+    tsf_cv_args a;
+    if (tsf_cv::resolve_args(args, &a)) return fail(ctx, "bad cross-validation arguments (horizon_ns > 0, rolling_window in [0, 1])");
+    if (tsf_cv::check_panel(N, T, offsets, ds))
+        return fail(ctx, "bad panel (aligned: offsets NULL, 1 <= T <= TSF_MAX_T; ragged: T = 0, offsets[0] = 0, ascending)");
+    if (spec->n_extra > 0 && !extra) return fail(ctx, "extra columns declared but extra is NULL");
+    if (spec->growth == TSF_GROWTH_LOGISTIC && !cap) return fail(ctx, "logistic growth needs cap");
+    const bool iv = n_samples > 0;
+    if (iv && (n_samples < 2 || n_samples > 4096)) return fail(ctx, "n_samples must be 0 or in [2, 4096]");
+    if (iv && !(interval_width > 0.0 && interval_width < 1.0)) return fail(ctx, "interval_width must be in (0, 1)");
+    ctx->order_n = 0;                   // (pending cost hints were meant for a fit call)
+    ctx->cv_grids = 0;
+    ctx->cv_launches = 0;
+    const bool aligned = offsets == nullptr;
+    std::vector<std::vector<tsf_cv::Fold>> plan;
+    std::vector<int32_t> pst;
+    std::vector<int64_t> pnh, pnm;
+    tsf_cv::panel_plan(N, T, offsets, ds, a, &plan, &pst, &pnh, &pnm);
+    std::vector<int64_t> fold_off((size_t)N + 1, 0), rows_off((size_t)N + 1, 0), m_off((size_t)N + 1, 0);
+    for (int64_t n = 0; n < N; ++n) {
+        fold_off[(size_t)n + 1] = fold_off[(size_t)n] + (int64_t)plan[(size_t)n].size();
+        rows_off[(size_t)n + 1] = rows_off[(size_t)n] + pnh[(size_t)n];
+        m_off[(size_t)n + 1] = m_off[(size_t)n] + pnm[(size_t)n];
+    }
+    const int64_t F = fold_off[(size_t)N], R = rows_off[(size_t)N], M = m_off[(size_t)N];
+    memcpy(out->series_status, pst.data(), sizeof(int32_t) * (size_t)N);
+    if (F == 0) return 0;
+    const tsf_fit_out &fo = out->fit;
+    if (!fo.theta || !fo.y_scale || !fo.fval || !fo.status || !fo.n_iter || !fo.n_eval || !fo.grid)
+        return fail(ctx, "tsf_cv_out.fit has NULL members");
+    if (!out->yhat || !out->horizon_ns || !out->mse || !out->rmse || !out->mae || !out->mape ||
+        (iv && (!out->yhat_lower || !out->yhat_upper || !out->coverage)))
+        return fail(ctx, "tsf_cv_out has NULL members");
+    std::vector<int32_t> f_series((size_t)F), f_c((size_t)F);
+    std::vector<int64_t> f_cut((size_t)F), f_hist((size_t)F), f_hold((size_t)F), f_row0((size_t)F);
+    std::vector<double> f_floor(floor_ ? (size_t)F : 0), f_cap(cap ? (size_t)F : 0);
+    int32_t Hmax = 1, C = 0;
+    for (int64_t n = 0; n < N; ++n) {
+        int64_t r = rows_off[(size_t)n];
+        for (size_t c = 0; c < plan[(size_t)n].size(); ++c) {
+            const int64_t f = fold_off[(size_t)n] + (int64_t)c;
+            const tsf_cv::Fold &x = plan[(size_t)n][c];
+            f_series[(size_t)f] = (int32_t)n; f_c[(size_t)f] = (int32_t)c;
+            f_cut[(size_t)f] = x.cutoff; f_hist[(size_t)f] = x.hist; f_hold[(size_t)f] = x.hold; f_row0[(size_t)f] = r;
+            if (floor_) f_floor[(size_t)f] = floor_[n];
+            if (cap) f_cap[(size_t)f] = cap[n];
+            r += x.hold;
+            if (x.hold > Hmax) Hmax = (int32_t)x.hold;
+        }
+        if ((int32_t)plan[(size_t)n].size() > C) C = (int32_t)plan[(size_t)n].size();
+    }
+    const int stride = tsf_theta_stride(spec);
+    const size_t ysz = ysize(y_dtype);
+    const int64_t n_ds = aligned ? (int64_t)T : offsets[N];
+    const int64_t n_y = aligned ? N * (int64_t)T : offsets[N];
+    // the caller's panel, once
+    DevBuf d_ds, d_y, d_off, d_ex, d_fl, d_cap, d_key, d_fser, d_fc, d_fhist, d_fhold;
+    HIP_TRY(ctx, d_ds.alloc(8 * (size_t)n_ds));
+    HIP_TRY(ctx, hipMemcpy(d_ds.p, ds, 8 * (size_t)n_ds, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_y.alloc(ysz * (size_t)n_y));
+    HIP_TRY(ctx, hipMemcpy(d_y.p, y, ysz * (size_t)n_y, hipMemcpyHostToDevice));
+    if (!aligned) {
+        HIP_TRY(ctx, d_off.alloc(8 * ((size_t)N + 1)));
+        HIP_TRY(ctx, hipMemcpy(d_off.p, offsets, 8 * ((size_t)N + 1), hipMemcpyHostToDevice));
+    }
+    if (spec->n_extra > 0) {
+        HIP_TRY(ctx, d_ex.alloc(8 * (size_t)spec->n_extra * n_ds));
+        HIP_TRY(ctx, hipMemcpy(d_ex.p, extra, 8 * (size_t)spec->n_extra * n_ds, hipMemcpyHostToDevice));
+    }
+    if (floor_) { HIP_TRY(ctx, d_fl.alloc(8 * (size_t)N)); HIP_TRY(ctx, hipMemcpy(d_fl.p, floor_, 8 * (size_t)N, hipMemcpyHostToDevice)); }
+    if (cap) { HIP_TRY(ctx, d_cap.alloc(8 * (size_t)N)); HIP_TRY(ctx, hipMemcpy(d_cap.p, cap, 8 * (size_t)N, hipMemcpyHostToDevice)); }
+    if (series_key) { HIP_TRY(ctx, d_key.alloc(8 * (size_t)N)); HIP_TRY(ctx, hipMemcpy(d_key.p, series_key, 8 * (size_t)N, hipMemcpyHostToDevice)); }
+    HIP_TRY(ctx, d_fser.alloc(4 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(d_fser.p, f_series.data(), 4 * (size_t)F, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_fc.alloc(4 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(d_fc.p, f_c.data(), 4 * (size_t)F, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_fhist.alloc(8 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(d_fhist.p, f_hist.data(), 8 * (size_t)F, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_fhold.alloc(8 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(d_fhold.p, f_hold.data(), 8 * (size_t)F, hipMemcpyHostToDevice));
+    CvPanel pn;
+    pn.ds = d_ds.as<int64_t>(); pn.y = d_y.p; pn.extra = spec->n_extra > 0 ? d_ex.as<double>() : nullptr;
+    pn.src_off = aligned ? nullptr : d_off.as<int64_t>(); pn.T = aligned ? T : 0; pn.src_total = aligned ? 0 : offsets[N];
+    pn.ysz = (int)ysz; pn.n_extra = spec->n_extra;
+    // fit outputs in plan order
+    DevBuf d_th, d_ys, d_fv, d_st, d_it, d_ev, d_gr;
+    HIP_TRY(ctx, d_th.alloc(8 * (size_t)F * stride)); HIP_TRY(ctx, d_ys.alloc(8 * (size_t)F));
+    HIP_TRY(ctx, d_fv.alloc(8 * (size_t)F)); HIP_TRY(ctx, d_st.alloc(4 * (size_t)F));
+    HIP_TRY(ctx, d_it.alloc(4 * (size_t)F)); HIP_TRY(ctx, d_ev.alloc(4 * (size_t)F));
+    HIP_TRY(ctx, d_gr.alloc(sizeof(tsf_grid_info) * (size_t)F));
+    tsf_fit_out dfo;
+    dfo.theta = d_th.as<double>(); dfo.y_scale = d_ys.as<double>(); dfo.fval = d_fv.as<double>();
+    dfo.status = d_st.as<int32_t>(); dfo.n_iter = d_it.as<int32_t>(); dfo.n_eval = d_ev.as<int32_t>();
+    dfo.grid = d_gr.as<tsf_grid_info>();
+    // one fit launch over the folds gf (plan indices)
+    auto fit_group = [&](const tsf_spec &gs, const std::vector<int32_t> &gf) -> int {
+        const int64_t G = (int64_t)gf.size();
+        if (G == 0) return 0;
+        std::vector<int64_t> goff((size_t)G + 1, 0);
+        int32_t maxT = 0;
+        for (int64_t g = 0; g < G; ++g) {
+            const int64_t h = f_hist[(size_t)gf[(size_t)g]];
+            goff[(size_t)g + 1] = goff[(size_t)g] + h;
+            if (h > maxT) maxT = (int32_t)h;
+        }
+        const int64_t rows = goff[(size_t)G];
+        DevBuf d_gf, d_goff, d_gds, d_gy, d_gex, d_gfl, d_gcap, g_th, g_ys, g_fv, g_st, g_it, g_ev, g_gr, d_gof, d_grows, d_gord;
+        HIP_TRY(ctx, d_gf.alloc(4 * (size_t)G)); HIP_TRY(ctx, hipMemcpy(d_gf.p, gf.data(), 4 * (size_t)G, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, d_goff.alloc(8 * ((size_t)G + 1))); HIP_TRY(ctx, hipMemcpy(d_goff.p, goff.data(), 8 * ((size_t)G + 1), hipMemcpyHostToDevice));
+        HIP_TRY(ctx, d_gds.alloc(8 * (size_t)rows)); HIP_TRY(ctx, d_gy.alloc(ysz * (size_t)rows));
+        if (spec->n_extra > 0) HIP_TRY(ctx, d_gex.alloc(8 * (size_t)spec->n_extra * rows));
+        if (floor_) HIP_TRY(ctx, d_gfl.alloc(8 * (size_t)G));
+        if (cap) HIP_TRY(ctx, d_gcap.alloc(8 * (size_t)G));
+        hipLaunchKernelGGL(cv_expand_kernel, dim3((unsigned)(G < 65535 ? G : 65535)), dim3(256), 0, nullptr, pn, G,
+                           d_gf.as<int32_t>(), d_fser.as<int32_t>(), d_goff.as<int64_t>(), rows,
+                           floor_ ? d_fl.as<double>() : nullptr, cap ? d_cap.as<double>() : nullptr, d_gds.as<int64_t>(),
+                           d_gy.p, spec->n_extra > 0 ? d_gex.as<double>() : nullptr,
+                           floor_ ? d_gfl.as<double>() : nullptr, cap ? d_gcap.as<double>() : nullptr);
+        HIP_TRY(ctx, hipGetLastError());
+        // calendar classes (same rule as fit_host_one: ragged, no explicit columns, two series or more)
+        int64_t n_distinct = 0;
+        if (gs.n_extra == 0 && G >= 2 && ctx->opt[TSF_OPT_GRID_SHARE] != 0) {
+            std::vector<int32_t> gof((size_t)G);
+            std::vector<int64_t> reps;
+            if (aligned) {
+                std::vector<int32_t> id_of((size_t)C, -1);
+                for (int64_t g = 0; g < G; ++g) {
+                    const int32_t c = f_c[(size_t)gf[(size_t)g]];
+                    if (id_of[(size_t)c] < 0) { id_of[(size_t)c] = (int32_t)reps.size(); reps.push_back(g); }
+                    gof[(size_t)g] = id_of[(size_t)c];
+                }
+            } else {
+                std::vector<int64_t> vstart((size_t)G), vlen((size_t)G);
+                for (int64_t g = 0; g < G; ++g) {
+                    vstart[(size_t)g] = offsets[f_series[(size_t)gf[(size_t)g]]];
+                    vlen[(size_t)g] = f_hist[(size_t)gf[(size_t)g]];
+                }
+                calendar_classes(ds, vstart.data(), vlen.data(), G, &gof, &reps);
+            }
+            n_distinct = (int64_t)reps.size();
+            if (n_distinct < G) {
+                std::vector<int64_t> grows;
+                for (int64_t r : reps) { grows.push_back(goff[(size_t)r]); grows.push_back(goff[(size_t)r + 1] - goff[(size_t)r]); }
+                std::vector<int32_t> ord;
+                calendar_start_order(gof, n_distinct, &ord);
+                HIP_TRY(ctx, d_gof.alloc(4 * (size_t)G)); HIP_TRY(ctx, hipMemcpy(d_gof.p, gof.data(), 4 * (size_t)G, hipMemcpyHostToDevice));
+                HIP_TRY(ctx, d_grows.alloc(8 * grows.size())); HIP_TRY(ctx, hipMemcpy(d_grows.p, grows.data(), 8 * grows.size(), hipMemcpyHostToDevice));
+                HIP_TRY(ctx, d_gord.alloc(4 * (size_t)G)); HIP_TRY(ctx, hipMemcpy(d_gord.p, ord.data(), 4 * (size_t)G, hipMemcpyHostToDevice));
+            } else {
+                n_distinct = 0;
+            }
+        }
+        HIP_TRY(ctx, g_th.alloc(8 * (size_t)G * stride)); HIP_TRY(ctx, g_ys.alloc(8 * (size_t)G)); HIP_TRY(ctx, g_fv.alloc(8 * (size_t)G));
+        HIP_TRY(ctx, g_st.alloc(4 * (size_t)G)); HIP_TRY(ctx, g_it.alloc(4 * (size_t)G)); HIP_TRY(ctx, g_ev.alloc(4 * (size_t)G));
+        HIP_TRY(ctx, g_gr.alloc(sizeof(tsf_grid_info) * (size_t)G));
+        HIP_TRY(ctx, hipMemset(g_st.p, 0, 4 * (size_t)G)); HIP_TRY(ctx, hipMemset(g_it.p, 0, 4 * (size_t)G));
+        HIP_TRY(ctx, hipMemset(g_ev.p, 0, 4 * (size_t)G)); HIP_TRY(ctx, hipMemset(g_gr.p, 0, sizeof(tsf_grid_info) * (size_t)G));
+        tsf_fit_out go;
+        go.theta = g_th.as<double>(); go.y_scale = g_ys.as<double>(); go.fval = g_fv.as<double>();
+        go.status = g_st.as<int32_t>(); go.n_iter = g_it.as<int32_t>(); go.n_eval = g_ev.as<int32_t>();
+        go.grid = g_gr.as<tsf_grid_info>();
+        int rc = run_fit(ctx, &gs, G, 0, 0, d_goff.as<int64_t>(), rows, maxT, d_gds.as<int64_t>(), d_gy.p, y_dtype,
+                         floor_ ? d_gfl.as<double>() : nullptr, cap ? d_gcap.as<double>() : nullptr,
+                         spec->n_extra > 0 ? d_gex.as<double>() : nullptr, &go, nullptr, nullptr, nullptr, 0, 0, 0, nullptr,
+                         n_distinct > 0 ? d_gof.as<int32_t>() : nullptr, n_distinct > 0 ? d_grows.as<int64_t>() : nullptr,
+                         n_distinct, n_distinct > 0 ? d_gord.as<int32_t>() : nullptr);
+        if (rc) return rc;
+        ctx->cv_grids += ctx->last_n_grids;
+        ctx->cv_launches += 1;
+        hipLaunchKernelGGL(cv_scatter_kernel, dim3((unsigned)G), dim3(64), 0, nullptr, G, d_gf.as<int32_t>(), stride, go, dfo);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipDeviceSynchronize());       // (this launch's buffers go back to the pool)
+        return 0;
+    };
+    // fbprophet's optimiser choice per fold (include/tsf.h)
+    tsf_spec sp_l = *spec, sp_n = *spec;
+    sp_l.algorithm = TSF_ALGO_LBFGS;
+    sp_n.algorithm = TSF_ALGO_NEWTON;
+    const bool auto_algo = spec->algorithm == TSF_ALGO_AUTO;
+    const bool newton_ok = 3 + spec->n_changepoints + tsf_spec_K(spec) <= TSF_MAX_P;
+    std::vector<int32_t> g_newton, g_lbfgs;
+    for (int64_t f = 0; f < F; ++f) {
+        const bool nw = auto_algo ? (newton_ok && f_hist[(size_t)f] < TSF_NEWTON_BELOW_T) : spec->algorithm == TSF_ALGO_NEWTON;
+        (nw ? g_newton : g_lbfgs).push_back((int32_t)f);
+    }
+    if (int rc = fit_group(sp_l, g_lbfgs)) return rc;
+    if (auto_algo && newton_ok && !g_lbfgs.empty()) {
+        std::vector<int32_t> st((size_t)F), retry;
+        HIP_TRY(ctx, hipMemcpy(st.data(), d_st.p, 4 * (size_t)F, hipMemcpyDeviceToHost));
+        for (int32_t f : g_lbfgs) {
+            const int32_t s = st[(size_t)f];
+            if (s == TSF_ST_LSFAIL || s == TSF_ST_INIT_NONFINITE || s == TSF_ST_EVAL_LIMIT) retry.push_back(f);
+        }
+        if (int rc = fit_group(sp_n, retry)) return rc;
+    }
+    if (int rc = fit_group(sp_n, g_newton)) return rc;
+    // the holdout rows of every fold, predicted in one call
+    DevBuf d_fds, d_fex, d_fkey, d_ffl, d_fcap, d_yh, d_lo, d_hi;
+    HIP_TRY(ctx, d_fds.alloc(8 * (size_t)F * Hmax));
+    if (spec->n_extra > 0) HIP_TRY(ctx, d_fex.alloc(8 * (size_t)F * spec->n_extra * Hmax));
+    HIP_TRY(ctx, d_fkey.alloc(8 * (size_t)F));
+    if (floor_) { HIP_TRY(ctx, d_ffl.alloc(8 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(d_ffl.p, f_floor.data(), 8 * (size_t)F, hipMemcpyHostToDevice)); }
+    if (cap) { HIP_TRY(ctx, d_fcap.alloc(8 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(d_fcap.p, f_cap.data(), 8 * (size_t)F, hipMemcpyHostToDevice)); }
+    HIP_TRY(ctx, d_yh.alloc(8 * (size_t)F * Hmax));
+    if (iv) { HIP_TRY(ctx, d_lo.alloc(8 * (size_t)F * Hmax)); HIP_TRY(ctx, d_hi.alloc(8 * (size_t)F * Hmax)); }
+    hipLaunchKernelGGL(cv_holdout_kernel, dim3((unsigned)(F < 65535 ? F : 65535)), dim3(128), 0, nullptr, pn, F, Hmax,
+                       d_fser.as<int32_t>(), d_fc.as<int32_t>(), d_fhist.as<int64_t>(), d_fhold.as<int64_t>(),
+                       series_key ? d_key.as<int64_t>() : nullptr, d_fds.as<int64_t>(),
+                       spec->n_extra > 0 ? d_fex.as<double>() : nullptr, d_fkey.as<int64_t>());
+    HIP_TRY(ctx, hipGetLastError());
+    {
+        const double *pfl = floor_ ? d_ffl.as<double>() : nullptr, *pcap = cap ? d_fcap.as<double>() : nullptr;
+        const double *pex = spec->n_extra > 0 ? d_fex.as<double>() : nullptr;
+        const int rc = iv ? tsf_predict_intervals_dev(ctx, spec, F, Hmax, dfo.theta, dfo.y_scale, dfo.grid, (int32_t)F,
+                                                      d_fds.as<int64_t>(), 0, pfl, pcap, pex, d_fkey.as<int64_t>(), n_samples,
+                                                      interval_width, seed, d_yh.as<double>(), d_lo.as<double>(),
+                                                      d_hi.as<double>(), nullptr)
+                          : tsf_predict_dev(ctx, spec, F, Hmax, dfo.theta, dfo.y_scale, dfo.grid, (int32_t)F, d_fds.as<int64_t>(),
+                                            0, pfl, pcap, pex, d_yh.as<double>(), nullptr, nullptr);
+        if (rc) return rc;
+    }
+    // metrics per series
+    DevBuf d_foff, d_roff, d_moff, d_fcut, d_frow0, d_hs, d_ts, d_pre, d_yo, d_loo, d_hio, d_mh, d_mm, d_sst;
+    HIP_TRY(ctx, d_foff.alloc(8 * ((size_t)N + 1))); HIP_TRY(ctx, hipMemcpy(d_foff.p, fold_off.data(), 8 * ((size_t)N + 1), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_roff.alloc(8 * ((size_t)N + 1))); HIP_TRY(ctx, hipMemcpy(d_roff.p, rows_off.data(), 8 * ((size_t)N + 1), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_moff.alloc(8 * ((size_t)N + 1))); HIP_TRY(ctx, hipMemcpy(d_moff.p, m_off.data(), 8 * ((size_t)N + 1), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_fcut.alloc(8 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(d_fcut.p, f_cut.data(), 8 * (size_t)F, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_frow0.alloc(8 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(d_frow0.p, f_row0.data(), 8 * (size_t)F, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_hs.alloc(8 * (size_t)R)); HIP_TRY(ctx, d_ts.alloc(8 * 4 * (size_t)R)); HIP_TRY(ctx, d_pre.alloc(8 * 4 * (size_t)(R + N)));
+    HIP_TRY(ctx, d_yo.alloc(8 * (size_t)R));
+    if (iv) { HIP_TRY(ctx, d_loo.alloc(8 * (size_t)R)); HIP_TRY(ctx, d_hio.alloc(8 * (size_t)R)); }
+    HIP_TRY(ctx, d_mh.alloc(8 * (size_t)M)); HIP_TRY(ctx, d_mm.alloc(8 * 5 * (size_t)M));
+    HIP_TRY(ctx, d_sst.alloc(4 * (size_t)N)); HIP_TRY(ctx, hipMemcpy(d_sst.p, pst.data(), 4 * (size_t)N, hipMemcpyHostToDevice));
+    CvMetricArgs ma;
+    memset(&ma, 0, sizeof(ma));
+    ma.p = pn; ma.y_dtype = y_dtype; ma.N = N; ma.Hmax = Hmax;
+    ma.fold_off = d_foff.as<int64_t>(); ma.rows_off = d_roff.as<int64_t>(); ma.m_off = d_moff.as<int64_t>();
+    ma.cutoff = d_fcut.as<int64_t>(); ma.fold_hist = d_fhist.as<int64_t>(); ma.fold_hold = d_fhold.as<int64_t>();
+    ma.fold_row0 = d_frow0.as<int64_t>(); ma.fit_status = dfo.status;
+    ma.yhat = d_yh.as<double>(); ma.lo = iv ? d_lo.as<double>() : nullptr; ma.hi = iv ? d_hi.as<double>() : nullptr;
+    ma.rolling_window = a.rolling_window;
+    ma.h_s = d_hs.as<int64_t>(); ma.t_s = d_ts.as<double>(); ma.pre = d_pre.as<double>(); ma.R = R;
+    ma.yhat_out = d_yo.as<double>(); ma.lo_out = iv ? d_loo.as<double>() : nullptr; ma.hi_out = iv ? d_hio.as<double>() : nullptr;
+    double *mm = d_mm.as<double>();
+    ma.horizon = d_mh.as<int64_t>(); ma.mse = mm; ma.rmse = mm + M; ma.mae = mm + 2 * M; ma.mape = mm + 3 * M;
+    ma.coverage = mm + 4 * M; ma.series_status = d_sst.as<int32_t>();
+    hipLaunchKernelGGL(cv_metrics_kernel, dim3((unsigned)N), dim3(64), 0, nullptr, ma);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    // outputs
+    HIP_TRY(ctx, hipMemcpy(fo.theta, d_th.p, 8 * (size_t)F * stride, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(fo.y_scale, d_ys.p, 8 * (size_t)F, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(fo.fval, d_fv.p, 8 * (size_t)F, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(fo.status, d_st.p, 4 * (size_t)F, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(fo.n_iter, d_it.p, 4 * (size_t)F, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(fo.n_eval, d_ev.p, 4 * (size_t)F, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(fo.grid, d_gr.p, sizeof(tsf_grid_info) * (size_t)F, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(out->yhat, d_yo.p, 8 * (size_t)R, hipMemcpyDeviceToHost));
+    if (iv) {
+        HIP_TRY(ctx, hipMemcpy(out->yhat_lower, d_loo.p, 8 * (size_t)R, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out->yhat_upper, d_hio.p, 8 * (size_t)R, hipMemcpyDeviceToHost));
+    }
+    if (M > 0) {
+        HIP_TRY(ctx, hipMemcpy(out->horizon_ns, d_mh.p, 8 * (size_t)M, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out->mse, mm, 8 * (size_t)M, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out->rmse, mm + M, 8 * (size_t)M, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out->mae, mm + 2 * M, 8 * (size_t)M, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out->mape, mm + 3 * M, 8 * (size_t)M, hipMemcpyDeviceToHost));
+        if (iv) HIP_TRY(ctx, hipMemcpy(out->coverage, mm + 4 * M, 8 * (size_t)M, hipMemcpyDeviceToHost));
+    }
+    HIP_TRY(ctx, hipMemcpy(out->series_status, d_sst.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
     return 0;
 }

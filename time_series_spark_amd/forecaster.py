@@ -550,3 +550,193 @@ def selftest_math(op, a, b=None, ctx=None):
                              out.ctypes.data)
     ctx.check(rc)
     return out
+
+
+# ---- cross-validation ---------------------------------------------------------------------------
+
+class CVResult(object):
+    """What cross_validate returns (include/tsf.h tsf_cross_validate).
+
+    Per series [N]: status (TSF_CV_*), n_folds, n_holdout, n_metric.
+    Per fold [F] (series by series, cutoffs ascending): fold_series, cutoff, hist_rows, hold_rows, and `fit`, the
+    FitResult of every fold (grid [F]).
+    Per holdout row [R] (fold by fold): row_fold, ds, y, yhat, yhat_lower / yhat_upper (None without intervals).
+    Per metric row [M] (series by series, horizons ascending): metric_series, horizon, mse, rmse, mae, mape,
+    coverage (None without intervals)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    @property
+    def fold_offsets(self):
+        return np.concatenate([[0], np.cumsum(self.n_folds)]).astype(np.int64)
+
+    @property
+    def row_offsets(self):
+        return np.concatenate([[0], np.cumsum(self.n_holdout)]).astype(np.int64)
+
+    @property
+    def metric_offsets(self):
+        return np.concatenate([[0], np.cumsum(self.n_metric)]).astype(np.int64)
+
+
+def _cv_args(horizon, period, initial, rolling_window):
+    a = _lib.TsfCvArgs()
+    a.horizon_ns = int(horizon)
+    a.period_ns = -1 if period is None else int(period)
+    a.initial_ns = -1 if initial is None else int(initial)
+    a.rolling_window = float(rolling_window)
+    return a
+
+
+def _cv_panel(ds_ns, y, offsets):
+    ds_ns = np.ascontiguousarray(ds_ns, dtype=np.int64)
+    y = np.ascontiguousarray(y)
+    if offsets is None:
+        if y.ndim != 2 or y.shape[1] != ds_ns.shape[0]:
+            raise ValueError('aligned panel: y must be [N][T] with T == len(ds)')
+        return ds_ns, y, None, y.shape[0], ds_ns.shape[0]
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    if y.ndim != 1 or y.shape[0] != ds_ns.shape[0] or offsets[-1] != y.shape[0]:
+        raise ValueError('ragged panel: ds / y must be 1-D with offsets[-1] rows')
+    return ds_ns, y, offsets, len(offsets) - 1, 0
+
+
+def cv_plan(ds_ns, horizon, period=None, initial=None, rolling_window=0.1, offsets=None, N=1):
+    """tsf_cv_plan (host only, no GPU): fbprophet's cutoffs and row masks per series.  Aligned input: ds_ns [T] shared
+    by N series; ragged: offsets [N+1] into ds_ns.  Times in ns; period None = horizon / 2, initial None = 3 * horizon.
+    Returns dict: n_folds, status, n_holdout, n_metric [N]; cutoff, hist_rows, hold_rows [F]."""
+    L = _lib.load()
+    ds_ns = np.ascontiguousarray(ds_ns, dtype=np.int64)
+    if offsets is not None:
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        N, T = len(offsets) - 1, 0
+    else:
+        T = len(ds_ns)
+    a = _cv_args(horizon, period, initial, rolling_window)
+    nf, st = np.zeros(N, np.int32), np.zeros(N, np.int32)
+    nh, nm = np.zeros(N, np.int64), np.zeros(N, np.int64)
+    args = (N, T, _lib._ptr(offsets), ds_ns.ctypes.data, ctypes.byref(a), nf.ctypes.data, st.ctypes.data,
+            nh.ctypes.data, nm.ctypes.data)
+    if L.tsf_cv_plan(*args, None, None, None) != 0:
+        raise ValueError('tsf_cv_plan: bad arguments (horizon > 0, rolling_window in [0, 1], sorted panel)')
+    F = int(nf.sum())
+    cut, hist, hold = np.zeros(F, np.int64), np.zeros(F, np.int32), np.zeros(F, np.int32)
+    if L.tsf_cv_plan(*args, cut.ctypes.data, hist.ctypes.data, hold.ctypes.data) != 0:
+        raise ValueError('tsf_cv_plan failed')
+    return {'n_folds': nf, 'status': st, 'n_holdout': nh, 'n_metric': nm, 'cutoff': cut, 'hist_rows': hist,
+            'hold_rows': hold}
+
+
+def cross_validate(spec, ds_ns, y, horizon, period=None, initial=None, offsets=None, floor=None, cap=None, extra=None,
+                   rolling_window=0.1, intervals=False, uncertainty_samples=1000, interval_width=0.8, seed=0,
+                   series_key=None, ctx=None, devices=None):
+    """fbprophet's diagnostics.cross_validation + performance_metrics for a whole panel, on the GPU
+    (include/tsf.h tsf_cross_validate).  Input as fit_aligned (ds_ns [T], y [N][T], extra [n_extra][T]) or, with
+    offsets [N+1], as fit_ragged.  horizon / period / initial: int64 ns (period None = horizon / 2, initial None =
+    3 * horizon).  spec: the full-history model's spec (ModelSpec); algorithm=ALGO_AUTO gives fbprophet's optimiser
+    rule per fold, with its Newton retry.  series_key [N] keys the interval streams (default: the series index in
+    this call).  devices: several GPUs, all folds of a series on one of them.  Returns a CVResult."""
+    ds_ns, y, offsets, N, T = _cv_panel(ds_ns, y, offsets)
+    fl = _opt_f64(floor, N, 'floor')
+    cp = _opt_f64(cap, N, 'cap')
+    key = None if series_key is None else np.ascontiguousarray(series_key, dtype=np.int64)
+    if key is not None and key.shape != (N,):
+        raise ValueError('series_key must be [N]')
+    devs = None if ctx is not None else resolve_devices(devices)
+    kw = dict(rolling_window=rolling_window, intervals=intervals, uncertainty_samples=uncertainty_samples,
+              interval_width=interval_width, seed=seed)
+    if devs and N >= 2 * MIN_SERIES_PER_DEVICE:
+        parts = min(len(devs), N // MIN_SERIES_PER_DEVICE)
+        lens = np.full(N, T, np.int64) if offsets is None else np.diff(offsets)
+        cuts = _cuts(lens, parts)
+        key = np.arange(N, dtype=np.int64) if key is None else key       # (the same streams whatever the split)
+        ex = None if extra is None else np.asarray(extra)
+
+        def one(c, a, b):
+            if offsets is None:
+                return cross_validate(spec, ds_ns, y[a:b], horizon, period, initial, None,
+                                      None if fl is None else fl[a:b], None if cp is None else cp[a:b], extra,
+                                      series_key=key[a:b], ctx=c, **kw)
+            r0, r1 = int(offsets[a]), int(offsets[b])
+            return cross_validate(spec, ds_ns[r0:r1], y[r0:r1], horizon, period, initial, offsets[a:b + 1] - r0,
+                                  None if fl is None else fl[a:b], None if cp is None else cp[a:b],
+                                  None if ex is None else ex[:, r0:r1], series_key=key[a:b], ctx=c, **kw)
+        blocks = [(c, int(a), int(b)) for c, a, b in zip(_contexts(devs[:parts]), cuts[:-1], cuts[1:]) if b > a]
+        parts_res = _run_blocks(one, blocks)
+        return _merge_cv(spec, parts_res, [a for _, a, _ in blocks], intervals)
+    ctx = ctx or get_context()
+    L = _lib.load()
+    cs = spec.to_c()
+    ex = None
+    if spec.extra:
+        ex = np.ascontiguousarray(extra, dtype=np.float64)
+        if ex.shape != (len(spec.extra), len(ds_ns)):
+            raise ValueError('extra must be [n_extra][len(ds)]')
+    plan = cv_plan(ds_ns, horizon, period, initial, rolling_window, offsets=offsets, N=N)
+    F, R, M = int(plan['n_folds'].sum()), int(plan['n_holdout'].sum()), int(plan['n_metric'].sum())
+    fout, farrs = _alloc_out(F, spec.theta_stride, F)
+    yhat = np.zeros(R)
+    lo = np.zeros(R) if intervals else None
+    hi = np.zeros(R) if intervals else None
+    hz = np.zeros(M, np.int64)
+    mse, rmse, mae, mape = np.zeros(M), np.zeros(M), np.zeros(M), np.zeros(M)
+    cov = np.zeros(M) if intervals else None
+    sst = np.zeros(N, np.int32)
+    out = _lib.TsfCvOut(fout, yhat.ctypes.data, _lib._ptr(lo), _lib._ptr(hi), hz.ctypes.data, mse.ctypes.data,
+                        rmse.ctypes.data, mae.ctypes.data, mape.ctypes.data, _lib._ptr(cov), sst.ctypes.data)
+    a = _cv_args(horizon, period, initial, rolling_window)
+    rc = L.tsf_cross_validate(ctx.handle, ctypes.byref(cs), N, T, _lib._ptr(offsets), ds_ns.ctypes.data, y.ctypes.data,
+                              _lib.y_dtype_code(y), _lib._ptr(fl), _lib._ptr(cp), _lib._ptr(ex), ctypes.byref(a),
+                              _lib._ptr(key), int(uncertainty_samples) if intervals else 0, float(interval_width),
+                              int(seed), ctypes.byref(out))
+    ctx.check(rc)
+    fold_series = np.repeat(np.arange(N, dtype=np.int64), plan['n_folds'])
+    # holdout rows: ds / y of the caller's rows [hist, hist + hold) of each fold's series
+    start = (np.zeros(N, np.int64) if offsets is None else offsets[:-1])[fold_series] + plan['hist_rows']
+    ridx = np.repeat(start - np.concatenate([[0], np.cumsum(plan['hold_rows'])[:-1]]), plan['hold_rows']) + np.arange(R)
+    row_fold = np.repeat(np.arange(F, dtype=np.int64), plan['hold_rows'])
+    if offsets is None:
+        y_rows = y[fold_series[row_fold], ridx].astype(np.float64)
+    else:
+        y_rows = y[ridx].astype(np.float64)
+    return CVResult(spec=spec, status=sst, n_folds=plan['n_folds'], n_holdout=plan['n_holdout'], n_metric=plan['n_metric'],
+                    fold_series=fold_series, cutoff=plan['cutoff'], hist_rows=plan['hist_rows'], hold_rows=plan['hold_rows'],
+                    fit=FitResult(spec, *farrs), row_fold=row_fold, ds=ds_ns[ridx], y=y_rows, yhat=yhat,
+                    yhat_lower=lo, yhat_upper=hi,
+                    metric_series=np.repeat(np.arange(N, dtype=np.int64), plan['n_metric']), horizon=hz, mse=mse,
+                    rmse=rmse, mae=mae, mape=mape, coverage=cov)
+
+
+def _merge_cv(spec, parts, firsts, intervals):
+    cat = lambda k, p=parts: np.concatenate([getattr(x, k) for x in p])     # noqa: E731
+    f_first = np.cumsum([0] + [len(p.cutoff) for p in parts])
+    shifted = lambda k, base: np.concatenate([getattr(p, k) + b for p, b in zip(parts, base)])   # noqa: E731
+    return CVResult(spec=spec, status=cat('status'), n_folds=cat('n_folds'), n_holdout=cat('n_holdout'),
+                    n_metric=cat('n_metric'), fold_series=shifted('fold_series', firsts), cutoff=cat('cutoff'),
+                    hist_rows=cat('hist_rows'), hold_rows=cat('hold_rows'),
+                    fit=_merge_fits(spec, [p.fit for p in parts], shared_grid=False),
+                    row_fold=shifted('row_fold', f_first[:-1]), ds=cat('ds'), y=cat('y'), yhat=cat('yhat'),
+                    yhat_lower=cat('yhat_lower') if intervals else None, yhat_upper=cat('yhat_upper') if intervals else None,
+                    metric_series=shifted('metric_series', firsts), horizon=cat('horizon'), mse=cat('mse'),
+                    rmse=cat('rmse'), mae=cat('mae'), mape=cat('mape'), coverage=cat('coverage') if intervals else None)
+
+
+def performance_metrics(cv):
+    """fbprophet's performance_metrics frame of a cross_validate result: one row per series and distinct horizon
+    (series, horizon [ns], mse, rmse, mae, mape[, coverage]); the rolling window is the one cross_validate was given."""
+    import pandas as pd
+    d = {'series': cv.metric_series, 'horizon': cv.horizon, 'mse': cv.mse, 'rmse': cv.rmse, 'mae': cv.mae,
+         'mape': cv.mape}
+    if cv.coverage is not None:
+        d['coverage'] = cv.coverage
+    return pd.DataFrame(d)
+
+
+def last_cv_grids(ctx=None):
+    """tsf_last_cv_grids (include/tsf_dev.h): (grid tables built, fit launches) of the context's last
+    cross_validate call."""
+    ctx = ctx or get_context()
+    g, n = ctypes.c_int64(), ctypes.c_int32()
+    ctx.check(_lib.load().tsf_last_cv_grids(ctx.handle, ctypes.byref(g), ctypes.byref(n)))
+    return int(g.value), int(n.value)

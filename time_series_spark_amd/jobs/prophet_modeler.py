@@ -146,20 +146,13 @@ def _empty_models():
     return pd.DataFrame(columns=MODEL_OUTPUT_COLUMNS)
 
 
-def fit_packed(panel, floor, cap, kw, devices=None, cost=None, lap=None):
-    """Fit every series of a PackedPanel.  Series are bucketed by the seasonality set
-    fbprophet's 'auto' rules give their own history (each Prophet object decides alone), one
-    kernel launch per bucket.  Returns (pieces, status, n_iter): pieces = [(members, buffer)] -- the blobs of one fit
-    call, uint8 [len(members)][stride] (panel.dump_models_buffer), row i the model of series members[i]; a series whose
-    status is negative has no model, and a later piece (fbprophet's Newton retry) supersedes an earlier one.
-    cost: optional [N] expected relative cost per series (the iteration counts of the previous run's models):
-    scheduling hints for the launches (tsf_set_cost_hints); results do not depend on them."""
-    N = panel.N
-    lap = lap or (lambda name: None)
-    hint = (lambda mem: None) if cost is None else (lambda mem: np.asarray(cost)[mem])
+def bucket_models(panel, kw):
+    """The models fbprophet would build for the series of a PackedPanel: series are bucketed by the seasonality set
+    fbprophet's 'auto' rules give their own history (each Prophet object decides alone).  Returns (buckets, holidays,
+    holiday days, holiday columns); buckets = [(seasonalities, members (sorted), model dict for ModelSpec)]."""
     span, min_dt, _ = pk.per_series_stats(panel)
-    growth = kw.get('growth', 'linear')
     mode = kw.get('seasonality_mode', 'additive')
+    growth = kw.get('growth', 'linear')
     sps = float(kw.get('seasonality_prior_scale', 10.0))
     # the auto rules depend on the series only through three booleans
     sig = ((span < 730 * fc.DAY_NS).astype(np.int8)
@@ -184,6 +177,34 @@ def fit_packed(panel, floor, cap, kw, devices=None, cost=None, lap=None):
     hol = features.normalize_holidays(kw.get('holidays'), float(kw.get('holidays_prior_scale', 10.0)))
     hol_names, hol_scales, hol_days = features.holiday_columns(hol)
     hol_extra = [{'name': n, 'prior_scale': p, 'mode': mode} for n, p in zip(hol_names, hol_scales)]
+    buckets = []
+    for key, (seas, members) in specs.items():
+        members = np.sort(np.asarray(members))
+        if hol_extra:
+            model = dict(growth=growth, seasonality_mode=mode, seasonalities=seas, extra=hol_extra, holidays=hol)
+        elif not seas:
+            # fbprophet adds a zero column when there is no seasonality at all
+            model = dict(growth=growth, seasonality_mode=mode, seasonalities=[],
+                         extra=[{'name': 'zeros', 'prior_scale': 1.0, 'mode': 'additive'}])
+        else:
+            model = dict(growth=growth, seasonality_mode=mode, seasonalities=seas)
+        buckets.append((seas, members, model))
+    return buckets, hol, hol_days, hol_extra
+
+
+def fit_packed(panel, floor, cap, kw, devices=None, cost=None, lap=None):
+    """Fit every series of a PackedPanel.  Series are bucketed by the seasonality set
+    fbprophet's 'auto' rules give their own history (each Prophet object decides alone), one
+    kernel launch per bucket.  Returns (pieces, status, n_iter): pieces = [(members, buffer)] -- the blobs of one fit
+    call, uint8 [len(members)][stride] (panel.dump_models_buffer), row i the model of series members[i]; a series whose
+    status is negative has no model, and a later piece (fbprophet's Newton retry) supersedes an earlier one.
+    cost: optional [N] expected relative cost per series (the iteration counts of the previous run's models):
+    scheduling hints for the launches (tsf_set_cost_hints); results do not depend on them."""
+    N = panel.N
+    lap = lap or (lambda name: None)
+    hint = (lambda mem: None) if cost is None else (lambda mem: np.asarray(cost)[mem])
+    mode = kw.get('seasonality_mode', 'additive')
+    buckets, _, hol_days, hol_extra = bucket_models(panel, kw)
     pieces = []
     status = np.zeros(N, dtype=np.int32)
     n_iter = np.zeros(N, dtype=np.int32)
@@ -246,16 +267,7 @@ def fit_packed(panel, floor, cap, kw, devices=None, cost=None, lap=None):
             pieces.append((mem, pk.dump_models_buffer(sd, res.theta, res.y_scale, res.grid, last_ds[mem], st, res.n_iter)))
             lap('blobs')
 
-    for key, (seas, members) in specs.items():
-        members = np.sort(np.asarray(members))
-        if hol_extra:
-            model = dict(growth=growth, seasonality_mode=mode, seasonalities=seas, extra=hol_extra, holidays=hol)
-        elif not seas:
-            # fbprophet adds a zero column when there is no seasonality at all
-            model = dict(growth=growth, seasonality_mode=mode, seasonalities=[],
-                         extra=[{'name': 'zeros', 'prior_scale': 1.0, 'mode': 'additive'}])
-        else:
-            model = dict(growth=growth, seasonality_mode=mode, seasonalities=seas)
+    for seas, members, model in buckets:
         lbfgs = fc.ModelSpec(algorithm=_lib.ALGO_LBFGS, **model, **opts)
         newton = fc.ModelSpec(algorithm=_lib.ALGO_NEWTON, **model, **opts)
         sd = fc.ModelSpec(**model, **opts).to_dict()      # what predict needs: no optimiser choice
