@@ -1,15 +1,19 @@
 """GPU tests of batched cross-validation (run with `-m gpu` on an MI355X): tsf_cross_validate against the library's own
 fit_ragged / predict / predict_intervals on the explicitly cut prefix panels (bit for bit), a sample of folds against
-the canonical CPU oracle, and the metrics against Prophet's rolling_mean_by_h restated in numpy
-(tests/test_cv_plan.py)."""
+the canonical CPU oracle, and the metrics against Prophet's rolling_mean_by_h in exact arithmetic
+(oracle/cv_metrics_ref.py) within its tolerance -- on benign panels and at the call's edges: outliers, mape's NaN
+threshold, 4-byte y, row counts around the wave width, one-row groups, many folds, failed fits and zero-fold series
+among OK ones, ragged explicit columns, and more folds than one launch grid holds."""
 import os
 import subprocess
+import types
 
 import numpy as np
 import pytest
 
+from oracle import cv_metrics_ref as cref
 from tests import helpers
-from tests.test_cv_plan import rolling_mean_by_h, window_rows
+from tests.test_cv_plan import window_rows
 
 pytestmark = pytest.mark.gpu
 DAY = 86400 * 10 ** 9
@@ -98,42 +102,76 @@ def _by_hand(fc, _lib, spec, cv, ds, y, offsets=None, floor=None, cap=None, extr
     return res, flat(yh), flat(lo), flat(hi)
 
 
-def _assert_same_folds(cv, res, yh, lo, hi):
+def _assert_same_folds(cv, res, yh, lo, hi, folds=None, rows=None):
+    """cv's folds (all, or the plan indices `folds` with their holdout rows `rows`) are the by-hand ones, bit for bit."""
+    fsel = slice(None) if folds is None else folds
+    rsel = slice(None) if rows is None else rows
     for k in ('theta', 'y_scale', 'fval', 'status', 'n_iter', 'n_eval'):
-        assert helpers.n_bit_diff(getattr(cv.fit, k), res[k]) == 0 if k in ('theta', 'y_scale', 'fval') else \
-            np.array_equal(getattr(cv.fit, k), res[k]), k
-    assert cv.fit.grid.tobytes() == res['grid'].tobytes()
-    assert helpers.n_bit_diff(cv.yhat, yh) == 0
+        got = getattr(cv.fit, k)[fsel]
+        assert helpers.n_bit_diff(got, res[k]) == 0 if k in ('theta', 'y_scale', 'fval') else \
+            np.array_equal(got, res[k]), k
+    assert cv.fit.grid[fsel].tobytes() == res['grid'].tobytes()
+    assert helpers.n_bit_diff(cv.yhat[rsel], yh) == 0
     if lo is not None:
-        assert helpers.n_bit_diff(cv.yhat_lower, lo) == 0 and helpers.n_bit_diff(cv.yhat_upper, hi) == 0
+        assert helpers.n_bit_diff(cv.yhat_lower[rsel], lo) == 0 and helpers.n_bit_diff(cv.yhat_upper[rsel], hi) == 0
 
 
-def _assert_metrics(_lib, cv, rolling_window):
-    """Metrics against the numpy restatement, per series, within a sum-of-|terms| tolerance (every term is >= 0)."""
+def _assert_metrics(_lib, cv, rolling_window, series=None):
+    """Metrics against the exact reference (oracle/cv_metrics_ref.py), per series (all, or those in `series`) and metric
+    row, within its tolerance TOL_C u (E - gb + 2) M_win; rmse is the square root of the returned mse, bit for bit;
+    the metric rows of a series whose fit failed are NaN.  Returns the largest err / tol."""
     ro, mo = cv.row_offsets, cv.metric_offsets
-    for n in range(len(cv.status)):
+    worst = 0.0
+    for n in range(len(cv.status)) if series is None else series:
         a, b = int(ro[n]), int(ro[n + 1])
+        m0, m1 = int(mo[n]), int(mo[n + 1])
         if b == a:
-            assert mo[n + 1] == mo[n]
+            assert m1 == m0 and cv.n_folds[n] == 0
             continue
         f = cv.row_fold[a:b]
         h = cv.ds[a:b] - cv.cutoff[f]
         y, yh = cv.y[a:b], cv.yhat[a:b]
         w = window_rows(rolling_window, b - a)
-        m0, m1 = int(mo[n]), int(mo[n + 1])
-        terms = {'mse': (y - yh) ** 2, 'mae': np.abs(y - yh), 'mape': np.abs((y - yh) / y)}
-        if cv.coverage is not None:
-            terms['coverage'] = ((y >= cv.yhat_lower[a:b]) & (y <= cv.yhat_upper[a:b])).astype(np.float64)
-        for name, x in terms.items():
-            hs, want = rolling_mean_by_h(x, h, w)
-            assert np.array_equal(cv.horizon[m0:m1], hs), name
-            got = getattr(cv, name)[m0:m1]
-            if name == 'mape' and np.min(np.abs(y)) < 1e-8:
-                assert np.all(np.isnan(got))
+        if cv.status[n] == _lib.CV_FIT_FAILED:
+            for k in ('mse', 'rmse', 'mae', 'mape') + (('coverage',) if cv.coverage is not None else ()):
+                assert np.all(np.isnan(getattr(cv, k)[m0:m1])), (n, k)
+            continue
+        assert cv.status[n] == _lib.CV_OK
+        lo = None if cv.coverage is None else cv.yhat_lower[a:b]
+        hi = None if cv.coverage is None else cv.yhat_upper[a:b]
+        r = cref.cv_metrics(y, yh, h, w, lo, hi)
+        assert np.array_equal(cv.horizon[m0:m1], r['horizon']), n
+        for name in cref.METRICS:
+            got = getattr(cv, name)
+            if got is None:
                 continue
-            assert np.allclose(got, want, rtol=1e-10, atol=1e-300), (n, name)
-            if name == 'mse':
-                assert np.allclose(cv.rmse[m0:m1], np.sqrt(want), rtol=1e-10, atol=1e-300)
+            got = got[m0:m1]
+            if r[name] is None:
+                assert np.all(np.isnan(got)), (n, name)
+                continue
+            q = r[name].err_over_tol(got)
+            assert q.max() <= 1.0, (n, name, int(np.argmax(q)), float(q.max()), got[np.argmax(q)],
+                                    r[name].value()[np.argmax(q)])
+            worst = max(worst, float(q.max()))
+        assert helpers.n_bit_diff(cv.rmse[m0:m1], np.sqrt(cv.mse[m0:m1])) == 0, n
+    return worst
+
+
+def _sub_plan(cv, idx):
+    """The plan of series idx of a call, as _by_hand takes it, with their fold and holdout-row indices in the call."""
+    fo, ro = cv.fold_offsets, cv.row_offsets
+    folds = np.concatenate([np.arange(fo[n], fo[n + 1]) for n in idx]).astype(np.int64)
+    rows = np.concatenate([np.arange(ro[n], ro[n + 1]) for n in idx]).astype(np.int64)
+    sub = types.SimpleNamespace(cutoff=cv.cutoff[folds], status=cv.status[idx], hist_rows=cv.hist_rows[folds],
+                                hold_rows=cv.hold_rows[folds], n_folds=cv.n_folds[idx],
+                                fold_series=np.repeat(np.arange(len(idx), dtype=np.int64), cv.n_folds[idx]))
+    return sub, folds, rows
+
+
+def _ragged(parts):
+    """(offsets, ds, y) of a ragged panel from per-series (ds, y) pairs."""
+    off = np.concatenate([[0], np.cumsum([len(d) for d, _ in parts])]).astype(np.int64)
+    return off, np.concatenate([d for d, _ in parts]).astype(np.int64), np.concatenate([v for _, v in parts])
 
 
 def test_cfg2_like_aligned_quadratic_route(env):
@@ -287,3 +325,290 @@ def test_validator_driver_on_reference_fixture(env, tmp_path):
     assert np.array_equal(f['ds'].to_numpy().astype(np.int64), cv.ds)
     assert helpers.n_bit_diff(f['yhat'].to_numpy(), cv.yhat) == 0
     assert helpers.n_bit_diff(f['yhat_upper'].to_numpy(), cv.yhat_upper) == 0
+
+
+# ---- the call at its edges -----------------------------------------------------------------------------------------
+
+# w = 81 is 9 whole groups of the 9-fold aligned panel (E - w on a group boundary), 80 and 82 are not; 0 -> w = 1,
+# 1 -> w = n (one metric row)
+CFG2_WINDOWS = (0.1, 80.5 / 810, 82.5 / 810, 0.0, 1.0)
+
+
+def test_spike_after_last_cutoff(env):
+    """Outliers on the row one day after the last cutoff -- in no fold's history, in the holdout of the last two folds
+    (horizons 1 d and 46 d): y scaled by 1e6 and by 1e12 in two series, a large negative value in a third.  Every fit
+    and forecast is the spike-free panel's, bit for bit; the metrics of every window after the spike's horizon must not
+    cancel, and those of the untouched series are unchanged."""
+    fc, _lib = env
+    N = 8
+    from time_series_spark_amd import synth
+    ds, y = synth.make_panel(N, 730, 'linear', seed=21)
+    spec = fc.ModelSpec(growth='linear', seasonalities=SEAS)
+    T0 = 730 - 90
+    ys = y.copy()
+    ys[1, T0] *= 1e6
+    ys[2, T0] *= 1e12
+    ys[3, T0] = -3e13
+    clean = fc.cross_validate(spec, ds, y, 90 * DAY, intervals=True, uncertainty_samples=200, seed=5)
+    for rw in CFG2_WINDOWS:
+        cv = fc.cross_validate(spec, ds, ys, 90 * DAY, rolling_window=rw, intervals=True, uncertainty_samples=200,
+                               seed=5)
+        assert (cv.status == 0).all() and list(cv.n_folds) == [9] * N
+        for k in ('theta', 'y_scale', 'fval'):
+            assert helpers.n_bit_diff(getattr(cv.fit, k), getattr(clean.fit, k)) == 0, k
+        for k in ('status', 'n_iter', 'n_eval'):
+            assert np.array_equal(getattr(cv.fit, k), getattr(clean.fit, k)), k
+        for k in ('yhat', 'yhat_lower', 'yhat_upper'):
+            assert helpers.n_bit_diff(getattr(cv, k), getattr(clean, k)) == 0, k
+        assert np.sum(cv.y != clean.y) == 6                     # 3 series x 2 folds
+        _assert_metrics(_lib, cv, rw)
+        if rw == 0.1:
+            mo = cv.metric_offsets
+            for n in (0, 4, 5, 6, 7):
+                for k in ('mse', 'mae', 'mape', 'coverage'):
+                    assert helpers.n_bit_diff(getattr(cv, k)[mo[n]:mo[n + 1]], getattr(clean, k)[mo[n]:mo[n + 1]]) == 0
+            assert np.all(cv.mse > 0) and np.all(np.isfinite(cv.rmse))
+    res, yh, lo, hi = _by_hand(fc, _lib, spec, cv, ds, ys, intervals=True, n_samples=200, seed=5)
+    _assert_same_folds(cv, res, yh, lo, hi)
+
+
+def test_mape_threshold(env):
+    """min |y| of exactly 0, 0.99e-8, 1e-8, 1.01e-8 and -0.99e-8 (on a holdout-only row), and a finite tiny |y| at
+    horizon 1 d: mape is NaN for the whole series exactly when min |y| < 1e-8; the other metrics are unaffected."""
+    fc, _lib = env
+    from time_series_spark_amd import synth
+    N, T = 7, 400
+    ds, y = synth.make_panel(N, T, 'linear', seed=4)
+    spec = fc.ModelSpec(growth='linear', seasonalities=SEAS[1:])
+    r = T - 30                                                  # the row one day after the last cutoff
+    for n, v in enumerate((0.0, 0.99e-8, 1e-8, 1.01e-8, -0.99e-8, 3e-8)):
+        y[n, r] = v
+    y[5, r - 15] = -2e-8                                        # (another fold's horizon 1 d as well)
+    cv = fc.cross_validate(spec, ds, y, 30 * DAY, intervals=True, uncertainty_samples=100)
+    assert (cv.status == 0).all()
+    mo = cv.metric_offsets
+    nan = [bool(np.all(np.isnan(cv.mape[mo[n]:mo[n + 1]]))) for n in range(N)]
+    assert nan == [True, True, False, False, True, False, False]
+    assert np.isfinite(cv.mse).all() and np.isfinite(cv.mae).all()
+    _assert_metrics(_lib, cv, 0.1)
+    cv0 = fc.cross_validate(spec, ds, y, 30 * DAY, rolling_window=0.0)
+    _assert_metrics(_lib, cv0, 0.0)
+    res, yh, lo, hi = _by_hand(fc, _lib, spec, cv0, ds, y)
+    _assert_same_folds(cv0, res, yh, lo, hi)
+
+
+def test_y_dtypes(env):
+    """The same panel as float64, float32 and int32 y (aligned and ragged): the 4-byte copy of the fold panel and the
+    holdout y conversion give fits, forecasts and metrics bit-identical to the float64 call on the converted values."""
+    fc, _lib = env
+    from time_series_spark_amd import synth
+    N, T = 6, 500
+    ds, y = synth.make_panel(N, T, 'linear', seed=8)
+    spec = fc.ModelSpec(growth='linear', seasonalities=SEAS)
+    keys = ('mse', 'rmse', 'mae', 'mape', 'coverage', 'yhat', 'yhat_lower', 'yhat_upper')
+    lens = [500, 430, 470, 380, 500, 455]
+    for yt in (((y + 0.37) * 1.3).astype(np.float32), y.astype(np.int32), (y - 2e4).astype(np.int32)):
+        for ragged in (False, True):
+            if ragged:
+                off, dsr, yr = _ragged([(ds[-k:], yt[n, -k:]) for n, k in enumerate(lens)])
+                args, kw = (dsr, yr), dict(offsets=off)
+                args64 = (dsr, yr.astype(np.float64))
+            else:
+                args, kw, args64 = (ds, yt), {}, (ds, yt.astype(np.float64))
+            cv = fc.cross_validate(spec, *args, 60 * DAY, intervals=True, uncertainty_samples=100, **kw)
+            ref = fc.cross_validate(spec, *args64, 60 * DAY, intervals=True, uncertainty_samples=100, **kw)
+            assert (cv.status == 0).all()
+            for k in ('theta', 'y_scale', 'fval', 'status', 'n_iter', 'n_eval'):
+                assert helpers.n_bit_diff(getattr(cv.fit, k), getattr(ref.fit, k)) == 0, (yt.dtype, ragged, k)
+            assert cv.fit.grid.tobytes() == ref.fit.grid.tobytes()
+            for k in keys:
+                assert helpers.n_bit_diff(getattr(cv, k), getattr(ref, k)) == 0, (yt.dtype, ragged, k)
+            assert helpers.n_bit_diff(cv.y, ref.y) == 0
+            _assert_metrics(_lib, cv, 0.1)
+    res, yh, lo, hi = _by_hand(fc, _lib, spec, cv, *args, offsets=off, intervals=True, n_samples=100)
+    _assert_same_folds(cv, res, yh, lo, hi)
+
+
+WAVE_ROWS = (1, 63, 64, 65, 127, 128, 129, 4100)
+
+
+def _one_fold_panel(rows, seed, horizon=30 * DAY, hist=200):
+    """A ragged panel of one fold per series: `hist` daily rows, then rows[n] holdout rows spread over
+    (cutoff, cutoff + horizon], every one at its own horizon.  period = horizon, initial = hist - 10 days."""
+    from time_series_spark_amd import synth
+    ds_h, y_h = synth.make_panel(len(rows), hist + 1, 'linear', seed=seed)
+    rng = np.random.default_rng(seed)
+    cut = int(ds_h[hist - 1])
+    parts = []
+    for n, k in enumerate(rows):
+        step = horizon // k
+        d = np.concatenate([ds_h[:hist], cut + horizon - step * np.arange(k - 1, -1, -1, dtype=np.int64)])
+        v = np.concatenate([y_h[n, :hist], y_h[n, hist] * (1 + 0.1 * rng.standard_normal(k))])
+        parts.append((d, v))
+    return _ragged(parts) + (horizon, horizon, (hist - 10) * DAY)
+
+
+def test_wave_boundaries(env):
+    """Holdout rows per series of 1, 63, 64, 65, 127, 128, 129 and 4 100 (one fold each, distinct horizons): with
+    w = 1 as many metric rows, across the 64-row steps of the output loop; w = n (one row); w = 10 %; windows that
+    leave the 4 100-row series 64 and 128 metric rows."""
+    fc, _lib = env
+    spec = fc.ModelSpec(growth='linear', seasonalities=SEAS[1:])
+    off, ds, y, horizon, period, initial = _one_fold_panel(WAVE_ROWS, 12)
+    # w = 4 100 - 64 + 1 and - 128 + 1 leave the long series 64 and 128 metric rows
+    for rw in (0.0, 1.0, 0.1, 4037.5 / 4100, 3973.5 / 4100):
+        cv = fc.cross_validate(spec, ds, y, horizon, period, initial, offsets=off, rolling_window=rw,
+                               intervals=True, uncertainty_samples=50)
+        assert (cv.status == 0).all() and list(cv.n_folds) == [1] * len(WAVE_ROWS)
+        assert list(cv.n_holdout) == list(WAVE_ROWS)
+        want = {0.0: list(WAVE_ROWS), 1.0: [1] * len(WAVE_ROWS)}.get(rw, [k - window_rows(rw, k) + 1 for k in WAVE_ROWS])
+        assert list(cv.n_metric) == want
+        assert rw in (0.0, 0.1, 1.0) or want[-1] in (64, 128)
+        _assert_metrics(_lib, cv, rw)
+    res, yh, lo, hi = _by_hand(fc, _lib, spec, cv, ds, y, off, intervals=True, n_samples=50)
+    _assert_same_folds(cv, res, yh, lo, hi)
+
+
+def test_group_shapes(env):
+    """Groups of one row (irregular timestamps at ns resolution: every holdout row its own horizon), many folds per
+    series (period 1 d: 90 folds, groups of 90 rows, w = 90 and 45), and folds of a single holdout row (horizon 1 d:
+    one group of every fold's row)."""
+    fc, _lib = env
+    from time_series_spark_amd import synth
+    rng = np.random.default_rng(17)
+    spec = fc.ModelSpec(growth='linear', seasonalities=SEAS[1:])
+    # one-row groups
+    parts = []
+    for n, T in enumerate((300, 260, 330)):
+        d0, v = synth.make_panel(1, T, 'linear', seed=40 + n)
+        parts.append((d0 + rng.integers(0, DAY, T), v[0]))
+    off, ds, y = _ragged(parts)
+    cv = fc.cross_validate(spec, ds, y, 20 * DAY, 10 * DAY, 100 * DAY, offsets=off, rolling_window=0.1)
+    assert (cv.status == 0).all() and cv.n_folds.min() >= 10
+    ro = cv.row_offsets
+    for n in range(3):
+        h = cv.ds[ro[n]:ro[n + 1]] - cv.cutoff[cv.row_fold[ro[n]:ro[n + 1]]]
+        assert len(np.unique(h)) == len(h)
+    _assert_metrics(_lib, cv, 0.1)
+    res, yh, lo, hi = _by_hand(fc, _lib, spec, cv, ds, y, off)
+    _assert_same_folds(cv, res, yh, lo, hi)
+    # many folds
+    ds, y = synth.make_panel(4, 200, 'linear', seed=41)
+    for rw in (0.1, 0.05):
+        cv = fc.cross_validate(spec, ds, y, 10 * DAY, DAY, 100 * DAY, rolling_window=rw)
+        assert (cv.status == 0).all() and list(cv.n_folds) == [90] * 4 and list(cv.n_metric) == [10] * 4
+        _assert_metrics(_lib, cv, rw)
+    res, yh, lo, hi = _by_hand(fc, _lib, spec, cv, ds, y)
+    _assert_same_folds(cv, res, yh, lo, hi)
+    # one holdout row per fold
+    cv = fc.cross_validate(spec, ds, y, DAY, DAY, 150 * DAY, rolling_window=0.1, intervals=True, uncertainty_samples=50)
+    assert (cv.status == 0).all() and (cv.hold_rows == 1).all() and cv.n_folds.min() >= 49
+    assert list(cv.n_metric) == [1] * 4
+    _assert_metrics(_lib, cv, 0.1)
+    res, yh, lo, hi = _by_hand(fc, _lib, spec, cv, ds, y, intervals=True, n_samples=50)
+    _assert_same_folds(cv, res, yh, lo, hi)
+
+
+def _status_panel():
+    """A ragged panel whose zero-fold series (LESS_THAN_HORIZON, NO_CUTOFF, TOO_FEW) sit between OK ones, for horizon
+    30 d, period 30 d and the default initial (90 d)."""
+    from time_series_spark_amd import synth
+    d, v = synth.make_panel(4, 400, 'linear', seed=50)
+    lone = np.array([d[0] - 400 * DAY])
+    parts = [(d[:300], v[0, :300]), (d[:20], v[1, :20]), (d[:250], v[1, :250]), (d[:100], v[2, :100]),
+             (d[:280], v[2, :280]), (np.concatenate([lone, d[:200]]), np.concatenate([[5e3], v[3, :200]])),
+             (d[:320], v[3, :320])]
+    return _ragged(parts)
+
+
+def test_statuses_between_ok_series(env):
+    """Zero-fold series placed between OK series have no fold, holdout or metric row and leave their neighbours'
+    results as the panel without them gives them; a logistic series with cap <= floor has every fold fail with
+    TSF_ST_CAP, comes back TSF_CV_FIT_FAILED with NaN metric rows, and its neighbours are unaffected."""
+    fc, _lib = env
+    from time_series_spark_amd import synth
+    spec = fc.ModelSpec(growth='linear', seasonalities=SEAS[1:])
+    off, ds, y = _status_panel()
+    cv = fc.cross_validate(spec, ds, y, 30 * DAY, 30 * DAY, offsets=off, intervals=True, uncertainty_samples=50)
+    assert list(cv.status) == [0, _lib.CV_LESS_THAN_HORIZON, 0, _lib.CV_NO_CUTOFF, 0, _lib.CV_TOO_FEW, 0]
+    assert list(cv.n_folds[[1, 3, 5]]) == [0, 0, 0] and list(cv.n_metric[[1, 3, 5]]) == [0, 0, 0]
+    _assert_metrics(_lib, cv, 0.1)
+    ok = [0, 2, 4, 6]
+    parts = [(ds[off[n]:off[n + 1]], y[off[n]:off[n + 1]]) for n in ok]
+    off2, ds2, y2 = _ragged(parts)
+    cv2 = fc.cross_validate(spec, ds2, y2, 30 * DAY, 30 * DAY, offsets=off2, series_key=ok, intervals=True,
+                            uncertainty_samples=50)
+    for k in ('theta', 'fval', 'status', 'n_iter'):
+        assert helpers.n_bit_diff(getattr(cv.fit, k), getattr(cv2.fit, k)) == 0, k
+    for k in ('yhat', 'yhat_lower', 'yhat_upper', 'horizon', 'mse', 'rmse', 'mae', 'mape', 'coverage'):
+        assert helpers.n_bit_diff(getattr(cv, k), getattr(cv2, k)) == 0, k
+    res, yh, lo, hi = _by_hand(fc, _lib, spec, cv, ds, y, off, intervals=True, n_samples=50)
+    _assert_same_folds(cv, res, yh, lo, hi)
+    # logistic, per-series floor / cap on an aligned panel; series 2 has cap == floor
+    N = 5
+    ds, y = synth.make_panel(N, 400, 'logistic', seed=51)
+    floor = np.array([0.0, 100.0, 200.0, -50.0, 10.0])
+    cap = y.max(axis=1) * 1.2
+    cap[2] = floor[2]
+    lspec = fc.ModelSpec(growth='logistic', seasonality_mode='multiplicative', seasonalities=SEAS[1:])
+    cv = fc.cross_validate(lspec, ds, y, 40 * DAY, floor=floor, cap=cap, intervals=True, uncertainty_samples=50)
+    fo = cv.fold_offsets
+    assert list(cv.status) == [0, 0, _lib.CV_FIT_FAILED, 0, 0]
+    assert (cv.fit.status[fo[2]:fo[3]] == _lib.ST_CAP).all() and cv.n_metric[2] > 0
+    _assert_metrics(_lib, cv, 0.1)
+    keep = [0, 1, 3, 4]
+    cv2 = fc.cross_validate(lspec, ds, y[keep], 40 * DAY, floor=floor[keep], cap=cap[keep], series_key=keep,
+                            intervals=True, uncertainty_samples=50)
+    _, fk, rk = _sub_plan(cv, keep)
+    mk = np.concatenate([np.arange(cv.metric_offsets[n], cv.metric_offsets[n + 1]) for n in keep])
+    for k in ('theta', 'fval', 'status', 'n_iter'):
+        assert helpers.n_bit_diff(getattr(cv.fit, k)[fk], getattr(cv2.fit, k)) == 0, k
+    for k in ('yhat', 'yhat_lower', 'yhat_upper'):
+        assert helpers.n_bit_diff(getattr(cv, k)[rk], getattr(cv2, k)) == 0, k
+    for k in ('horizon', 'mse', 'rmse', 'mae', 'mape', 'coverage'):
+        assert helpers.n_bit_diff(getattr(cv, k)[mk], getattr(cv2, k)) == 0, k
+    res, yh, lo, hi = _by_hand(fc, _lib, lspec, cv, ds, y, floor=floor, cap=cap, intervals=True, n_samples=50)
+    _assert_same_folds(cv, res, yh, lo, hi)
+
+
+def test_ragged_holidays(env):
+    """Explicit (holiday) columns on a ragged panel: each fold's columns are its own series' rows, cut on the device
+    for the fit and read at the holdout rows for the forecast."""
+    fc, _lib = env
+    from time_series_spark_amd import synth
+    ds_all = synth.daily_grid(520)
+    ex_all, names = synth.holiday_matrix(ds_all, 6)
+    _, y_all = synth.make_panel(5, 520, 'linear', seed=55, holidays=ex_all)
+    spans = [(0, 520), (40, 500), (100, 520), (0, 360), (20, 470)]
+    off, ds, y = _ragged([(ds_all[a:b], y_all[n, a:b]) for n, (a, b) in enumerate(spans)])
+    ex = np.concatenate([ex_all[:, a:b] for a, b in spans], axis=1)
+    spec = fc.ModelSpec(growth='linear', seasonalities=SEAS[1:], extra=[{'name': n} for n in names])
+    cv = fc.cross_validate(spec, ds, y, 45 * DAY, 40 * DAY, offsets=off, extra=ex, intervals=True,
+                           uncertainty_samples=50)
+    assert (cv.status == 0).all() and cv.n_folds.min() >= 3
+    _assert_metrics(_lib, cv, 0.1)
+    res, yh, lo, hi = _by_hand(fc, _lib, spec, cv, ds, y, off, extra=ex, intervals=True, n_samples=50)
+    _assert_same_folds(cv, res, yh, lo, hi)
+
+
+def test_more_folds_than_one_launch_grid(env):
+    """8 000 short series x 9 folds = 72 000 folds: the expand and holdout kernels loop past their 65 535-block grid.
+    Folds above index 65 535 are checked bit for bit against the folds done by hand on their series alone."""
+    fc, _lib = env
+    from time_series_spark_amd import synth
+    N = 8000
+    ds, y = synth.make_panel(N, 80, 'linear', seed=60)
+    spec = fc.ModelSpec(growth='linear', seasonalities=SEAS[1:])
+    cv = fc.cross_validate(spec, ds, y, 4 * DAY, 4 * DAY, 40 * DAY, intervals=True, uncertainty_samples=50,
+                           ctx=fc.get_context())
+    assert list(set(cv.n_folds)) == [9] and len(cv.cutoff) == 72000
+    # (a short history's L-BFGS fit may fail; such a series is TSF_CV_FIT_FAILED, its metric rows NaN)
+    assert set(cv.status) <= {_lib.CV_OK, _lib.CV_FIT_FAILED} and np.mean(cv.status == 0) > 0.9, \
+        np.unique(cv.fit.status, return_counts=True)
+    idx = [7281, 7282, 7500, 7777, 7999]            # (series 7281 holds folds 65 529 .. 65 537)
+    sub, folds, rows = _sub_plan(cv, idx)
+    assert folds.min() < 65535 < folds[9] and folds.max() == 71999
+    res, yh, lo, hi = _by_hand(fc, _lib, spec, sub, ds, y[idx], intervals=True, n_samples=50, series_key=idx)
+    _assert_same_folds(cv, res, yh, lo, hi, folds=folds, rows=rows)
+    rng = np.random.default_rng(0)
+    _assert_metrics(_lib, cv, 0.1, series=sorted(set(idx) | set(rng.choice(N, 200, replace=False).tolist())))

@@ -1999,7 +1999,7 @@ extern "C" int tsf_cross_validate(tsf_ctx *ctx, const tsf_spec *spec, int64_t N,
     HIP_TRY(ctx, d_moff.alloc(8 * ((size_t)N + 1))); HIP_TRY(ctx, hipMemcpy(d_moff.p, m_off.data(), 8 * ((size_t)N + 1), hipMemcpyHostToDevice));
     HIP_TRY(ctx, d_fcut.alloc(8 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(d_fcut.p, f_cut.data(), 8 * (size_t)F, hipMemcpyHostToDevice));
     HIP_TRY(ctx, d_frow0.alloc(8 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(d_frow0.p, f_row0.data(), 8 * (size_t)F, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_hs.alloc(8 * (size_t)R)); HIP_TRY(ctx, d_ts.alloc(8 * 4 * (size_t)R)); HIP_TRY(ctx, d_pre.alloc(8 * 4 * (size_t)(R + N)));
+    HIP_TRY(ctx, d_hs.alloc(8 * (size_t)R)); HIP_TRY(ctx, d_ts.alloc(8 * 4 * (size_t)R)); HIP_TRY(ctx, d_pre.alloc(8 * 4 * (size_t)(R + 64 * N)));
     HIP_TRY(ctx, d_yo.alloc(8 * (size_t)R));
     if (iv) { HIP_TRY(ctx, d_loo.alloc(8 * (size_t)R)); HIP_TRY(ctx, d_hio.alloc(8 * (size_t)R)); }
     HIP_TRY(ctx, d_mh.alloc(8 * (size_t)M)); HIP_TRY(ctx, d_mm.alloc(8 * 5 * (size_t)M));

@@ -115,10 +115,11 @@ struct CvMetricArgs {
     const int32_t *fit_status;  // [F]
     const double *yhat, *lo, *hi;                       // [F][Hmax] (lo / hi nullptr without intervals)
     double rolling_window;
-    // scratch [R]: the rows sorted by horizon, and per quantity the exclusive prefix sums [R + N] (series n at rows_off[n] + n)
+    // scratch [R]: the rows sorted by horizon, and per quantity the levels of a tree of block sums [R + 64 N] (series n
+    // at rows_off[n] + 64 n; its levels 1, 2, .. take fewer than its rows + 64 slots)
     int64_t *h_s;
     double *t_s;                // [4][R]: squared error, absolute error, absolute percentage error, covered
-    double *pre;                // [4][R + N]
+    double *pre;                // [4][R + 64 N]
     int64_t R;
     // outputs
     double *yhat_out, *lo_out, *hi_out;                 // [R]
@@ -144,20 +145,31 @@ __device__ __forceinline__ int64_t cv_count(const CvMetricArgs &a, int64_t s0, i
     return lo;
 }
 
-__device__ __forceinline__ double cv_wave_scan(double v, int lane)
+// Sum of the terms t[lo, hi) of one series from its tree (level 0: t [len0], level k >= 1: node i = the sum of nodes 2i
+// and 2i + 1 of level k - 1, stored level after level from `tree`): the O(log) nodes that tile [lo, hi) exactly.
+__device__ __forceinline__ double cv_tree_sum(const double *t, const double *tree, int64_t len0, int64_t lo, int64_t hi)
 {
-    for (int d = 1; d < 64; d <<= 1) {
-        const double u = __shfl_up(v, d, 64);
-        if (lane >= d) v = v + u;
+    const double *lev = t;
+    int64_t len = len0, off = 0;
+    double s = 0.0;
+    while (lo < hi) {
+        if (lo & 1) s += lev[lo++];
+        if (hi & 1) s += lev[--hi];
+        lo >>= 1; hi >>= 1;
+        const int64_t nl = (len + 1) >> 1;
+        lev = tree + off; off += nl; len = nl;
     }
-    return v;
+    return s;
 }
 
 // performance_metrics of one series per wave (include/tsf.h): its C holdout runs (each sorted by horizon) are merged
 // by rank -- every row counts, by binary search in each run, the rows that precede it (smaller horizon, or equal
-// horizon in an earlier fold / earlier in its own) -- so all lanes place rows at once; then prefix sums of the terms
-// in merged order, and for every distinct horizon h whose window of w rows exists, the window's left end: the group
-// holding merged row E - w (E = rows up to and including h's group), found by binary search for its bounds.
+// horizon in an earlier fold / earlier in its own) -- so all lanes place rows at once; then a tree of pairwise block
+// sums of the terms in merged order, and for every distinct horizon h whose window of w rows exists, the window's left
+// end: the group [gb, ge) holding merged row E - w (E = rows up to and including h's group), found by binary search.
+// The window is S[ge, E) + (ge - E + w) / (ge - gb) * S[gb, ge), each S from tree nodes inside it: every term is >= 0
+// and no row outside [gb, E) enters, so one large term cannot cancel the windows that do not hold it (as differences
+// of prefix sums over all rows would).
 __global__ __launch_bounds__(64) void cv_metrics_kernel(CvMetricArgs a)
 {
     const int64_t n = blockIdx.x;
@@ -207,21 +219,20 @@ __global__ __launch_bounds__(64) void cv_metrics_kernel(CvMetricArgs a)
     }
     bad = __any(bad) ? 1 : 0;
     __syncthreads();
-    // 2) exclusive prefix sums of the four terms in merged order
-    const int64_t p0 = r0 + n;
-    for (int qn = 0; qn < 4; ++qn) {
-        const double *t = a.t_s + (size_t)qn * a.R + r0;
-        double *P = a.pre + (size_t)qn * (a.R + a.N) + p0;
-        double carry = 0.0;
-        if (lane == 0) P[0] = 0.0;
-        for (int64_t b = 0; b < nr; b += 64) {
-            const double v = (b + lane < nr) ? t[b + lane] : 0.0;
-            const double s = cv_wave_scan(v, lane);
-            if (b + lane < nr) P[b + lane + 1] = carry + s;
-            carry = carry + __shfl(s, 63, 64);
+    // 2) the tree of block sums of the four terms in merged order, level by level
+    const int64_t p0 = r0 + 64 * n;
+    const size_t qs = (size_t)(a.R + 64 * a.N);
+    for (int64_t len = nr, src = -1, dst = 0; len > 1;) {
+        const int64_t nl = (len + 1) >> 1;
+        for (int qn = 0; qn < 4; ++qn) {
+            double *tree = a.pre + qn * qs + p0;
+            const double *x = src < 0 ? a.t_s + (size_t)qn * a.R + r0 : tree + src;
+            for (int64_t i = lane; i < nl; i += 64)
+                tree[dst + i] = 2 * i + 1 < len ? x[2 * i] + x[2 * i + 1] : x[2 * i];
         }
+        __syncthreads();
+        src = dst; dst += nl; len = nl;
     }
-    __syncthreads();
     // 3) one metric row per distinct horizon whose cumulative count reaches w
     const int64_t w = [&] { int64_t x = (int64_t)(a.rolling_window * (double)nr); return x < 1 ? 1 : (x > nr ? nr : x); }();
     const int64_t *hs = a.h_s + r0;
@@ -245,10 +256,10 @@ __global__ __launch_bounds__(64) void cv_metrics_kernel(CvMetricArgs a)
             const int64_t ge = lo;
             double v[4];
             for (int qn = 0; qn < 4; ++qn) {
-                const double *P = a.pre + (size_t)qn * (a.R + a.N) + p0;
-                const double xs = P[ge] - P[gb];
-                const double excess = (double)(E - gb - w) * xs / (double)(ge - gb);
-                v[qn] = (P[E] - P[gb] - excess) / (double)w;
+                const double *t = a.t_s + (size_t)qn * a.R + r0, *tree = a.pre + qn * qs + p0;
+                const double whole = cv_tree_sum(t, tree, nr, ge, E);
+                const double left = cv_tree_sum(t, tree, nr, gb, ge);
+                v[qn] = (whole + (double)(ge - E + w) * left / (double)(ge - gb)) / (double)w;
             }
             a.horizon[o] = hs[i];
             a.mse[o] = bad ? NaN : v[0];
