@@ -16,7 +16,7 @@
  *       `model.predict(future_df)` + the int cast + floor clamp of
  *       /root/reference/src/jobs/prophet_scorer.py:64-84 (future frame :64-68, predict :70,
  *       astype(int) :73, clamp :76-84).  Only `yhat` is produced: the reference keeps
- *       nothing else (:86).
+ *       nothing else (:86).  (tsf_predict_components adds the trend and the components.)
  *   (tests and measurements -- per-evaluation hooks, route switches, kernel timers -- are NOT here: include/tsf_dev.h)
  *
  * Conventions
@@ -258,6 +258,52 @@ int tsf_predict_intervals_dev(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int
                               const int64_t *series_key, int32_t n_samples, double interval_width,
                               uint64_t seed, double *yhat, double *yhat_lower, double *yhat_upper,
                               void *stream);
+
+/* ---- forecast components ------------------------------------------------------------------------
+ * The decomposition fbprophet 0.5's Prophet.predict returns beside yhat (predict_trend, predict_seasonal_components,
+ * predict_uncertainty): the trend and any set of components -- seasonalities, holidays, regressors, their additive /
+ * multiplicative totals -- for a whole panel.  Semantics restated from recall of fbprophet 0.5: parity unpinned (no test
+ * compares with the real package; what is pinned is the contract below, against tsf_predict / tsf_predict_intervals).
+ * Reference interface replaced: none (the reference keeps yhat alone, prophet_scorer.py:86).
+ *
+ * Arguments shared with tsf_predict / tsf_predict_intervals mean what they mean there; the same grid check runs first.
+ * Component c is a set of design columns: bit j of comp_cols[c] = original column j (the theta layout's beta order:
+ * seasonalities in spec order [sin1, cos1, ...], then the extra columns).  comp_scaled[c] = 1 multiplies the component
+ * by the series' y_scale (fbprophet does so for additive components; multiplicative ones are relative).  The table
+ * (n_comp in [0, TSF_MAX_COMP], every bit below K) is HOST memory in both variants, like spec, and is checked before any
+ * launch.
+ *
+ * Outputs: yhat [N][H], bit-identical to tsf_predict's; trend [N][H] in original units (gtr * y_scale + floor, the value
+ * tsf_predict combines with the terms); comp [N][n_comp][H] (NULL if n_comp = 0).
+ * Order-of-operations contract: component c is an fma chain over its set columns in ascending original column order
+ * starting from 0.0, then multiplied by y_scale if comp_scaled[c]; the design values are the ones tsf_predict uses
+ * (the first harmonic from the deterministic sincos, the others by the harmonic recurrence; the caller's extra
+ * columns).  So the mask of every additive column with comp_scaled = 1 is tsf_predict's additive term times y_scale,
+ * the mask of every multiplicative column (scaled 0) its multiplicative term, and
+ *   yhat = trend * (1 + multiplicative_terms) + additive_terms     up to the rounding of that last expression.
+ * An empty mask gives 0.0.
+ *
+ * Intervals: n_samples = 0 computes none (the four interval pointers may be NULL).  Otherwise n_samples in [2, 4096],
+ * interval_width in (0, 1) and all four pointers non-NULL: yhat_lower / yhat_upper are tsf_predict_intervals' with the
+ * same series_key, seed, width and samples, bit for bit; trend_lower / trend_upper are the same percentiles of the
+ * sampled trend of the same draws, before the observation noise (fbprophet's sample_model takes trend and yhat from
+ * one trend simulation).  With a MAP fit beta is one point, so a component's own interval is the component itself. */
+#define TSF_MAX_COMP 128
+int tsf_predict_components(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H, const double *theta,
+                           const double *y_scale, const tsf_grid_info *grid, int32_t n_grids,
+                           const int64_t *ds_future, int32_t shared_future, const double *floor, const double *cap,
+                           const double *extra_future, int32_t n_comp, const uint64_t *comp_cols,
+                           const int32_t *comp_scaled, const int64_t *series_key, int32_t n_samples,
+                           double interval_width, uint64_t seed, double *yhat, double *trend, double *comp,
+                           double *yhat_lower, double *yhat_upper, double *trend_lower, double *trend_upper);
+int tsf_predict_components_dev(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H, const double *theta,
+                               const double *y_scale, const tsf_grid_info *grid, int32_t n_grids,
+                               const int64_t *ds_future, int32_t shared_future, const double *floor,
+                               const double *cap, const double *extra_future, int32_t n_comp,
+                               const uint64_t *comp_cols, const int32_t *comp_scaled, const int64_t *series_key,
+                               int32_t n_samples, double interval_width, uint64_t seed, double *yhat, double *trend,
+                               double *comp, double *yhat_lower, double *yhat_upper, double *trend_lower,
+                               double *trend_upper, void *stream);
 
 /* ---- cross-validation ---------------------------------------------------------------------
  * fbprophet 0.5 diagnostics.cross_validation + performance_metrics for a whole panel: every series is refitted at

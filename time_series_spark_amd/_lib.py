@@ -17,6 +17,7 @@ MAX_EXTRA = 64
 MAX_S = 60
 MAX_K = 64
 MAX_P = 128
+MAX_COMP = 128
 
 GROWTH_LINEAR, GROWTH_LOGISTIC = 0, 1
 MODE_ADDITIVE, MODE_MULTIPLICATIVE = 0, 1
@@ -97,7 +98,7 @@ class TsfCvOut(ctypes.Structure):
 EXPORTS = ['tsf_create', 'tsf_destroy', 'tsf_last_error', 'tsf_device_count', 'tsf_spec_default',
            'tsf_spec_size', 'tsf_grid_info_size', 'tsf_spec_K', 'tsf_theta_stride',
            'tsf_fit_aligned', 'tsf_fit_aligned_dev', 'tsf_fit_ragged', 'tsf_fit_ragged_dev',
-           'tsf_predict', 'tsf_predict_dev', 'tsf_predict_intervals', 'tsf_predict_intervals_dev', 'tsf_eval', 'tsf_eval_quadratic', 'tsf_design', 'tsf_selftest_math',
+           'tsf_predict', 'tsf_predict_dev', 'tsf_predict_intervals', 'tsf_predict_intervals_dev', 'tsf_predict_components', 'tsf_predict_components_dev', 'tsf_eval', 'tsf_eval_quadratic', 'tsf_design', 'tsf_selftest_math',
            'tsf_set_option', 'tsf_get_option', 'tsf_set_cost_hints', 'tsf_set_profiling', 'tsf_profile_read', 'tsf_last_fit_kernel_ms', 'tsf_last_fit_route',
            'tsf_cv_plan', 'tsf_cross_validate', 'tsf_last_cv_grids',
            'tsf_pack_rows', 'tsf_pack_rows_typed', 'tsf_pack_fetch', 'tsf_pack_flags', 'tsf_pack_free', 'tsf_model_blobs',
@@ -156,6 +157,9 @@ def load():
     L.tsf_predict_intervals.argtypes = [vp, psp, i64, i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, i32, f64,
                                         u64, vp, vp, vp]
     L.tsf_predict_intervals_dev.argtypes = L.tsf_predict_intervals.argtypes + [vp]
+    L.tsf_predict_components.argtypes = [vp, psp, i64, i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32,
+                                         f64, u64, vp, vp, vp, vp, vp, vp, vp]
+    L.tsf_predict_components_dev.argtypes = L.tsf_predict_components.argtypes + [vp]
     L.tsf_eval.argtypes = [vp, psp, i64, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     L.tsf_eval_quadratic.argtypes = [vp, psp, i64, i32, vp, vp, i32, vp, vp, vp, vp, vp]
     L.tsf_design.argtypes = [vp, psp, i32, vp, vp, vp, vp, vp]

@@ -20,6 +20,7 @@
 
 #include "tsf_aux_kernels.h"
 #include "tsf_interval_kernels.h"
+#include "tsf_component_kernels.h"
 #include "tsf_fit_kernels.h"
 #include "tsf_quad_kernels.h"
 #include "tsf_mfma_tabs.h"
@@ -42,6 +43,7 @@ struct tsf_ctx {
     size_t fut_tab_bytes;
     void *iv_ws;            // scratch of tsf_predict_intervals_dev (per-row pieces + samples of one chunk; grown on demand, <= ~0.5 GB)
     size_t iv_ws_bytes;
+    void *comp_tab;         // tsf_predict_components: the component table ([TSF_MAX_COMP] masks, then [TSF_MAX_COMP] flags)
     int32_t *order_dev[2];  // tsf_set_cost_hints: series in order of decreasing expected cost (two buffers, used in
     size_t order_cap[2];    // turn: a fit that is still running on its stream keeps reading the one it was given)
     int order_next;
@@ -95,6 +97,7 @@ extern "C" int tsf_create(int device_id, tsf_ctx **out)
     c->fut_tab = nullptr; c->fut_tab_bytes = 0;
     c->nb_ws = nullptr; c->nb_ws_bytes = 0;
     c->iv_ws = nullptr; c->iv_ws_bytes = 0;
+    c->comp_tab = nullptr;
     c->order_dev[0] = c->order_dev[1] = nullptr; c->order_cap[0] = c->order_cap[1] = 0; c->order_next = 0; c->order_n = 0;
     c->order_ev[0] = c->order_ev[1] = nullptr; c->order_busy[0] = c->order_busy[1] = 0;
     c->profiling = 0; c->ev_created = 0; c->ev_count = 0;
@@ -125,6 +128,7 @@ extern "C" void tsf_destroy(tsf_ctx *ctx)
     if (ctx->fut_tab) hipFree(ctx->fut_tab);
     if (ctx->nb_ws) hipFree(ctx->nb_ws);
     if (ctx->iv_ws) hipFree(ctx->iv_ws);
+    if (ctx->comp_tab) hipFree(ctx->comp_tab);
     for (int b = 0; b < 2; ++b) { if (ctx->order_dev[b]) hipFree(ctx->order_dev[b]); if (ctx->order_ev[b]) hipEventDestroy(ctx->order_ev[b]); }
     if (ctx->ev_created)
         for (int i = 0; i < TSF_PROFILE_RING; ++i) { hipEventDestroy(ctx->ev0[i]); hipEventDestroy(ctx->ev1[i]); }
@@ -1366,6 +1370,7 @@ static int launch_predict(tsf_ctx *ctx, const DevSpec &hs, PredictArgs a, int64_
     if (a.cap) a.cap += n0;
     if (a.extra_future && !a.shared_future) a.extra_future += (size_t)n0 * hs.n_extra * a.H;
     a.yhat += (size_t)n0 * a.H;
+    if (a.trend_out) a.trend_out += (size_t)n0 * a.H;
     if (a.yhat_int) a.yhat_int += (size_t)n0 * a.H;
     hipLaunchKernelGGL(predict_kernel, dim3((unsigned)((n + PREDICT_WAVES - 1) / PREDICT_WAVES)), dim3(PREDICT_WAVES * 64), 0, st, a);
     HIP_TRY(ctx, hipGetLastError());
@@ -1590,6 +1595,200 @@ extern "C" int tsf_predict_intervals(tsf_ctx *ctx, const tsf_spec *spec, int64_t
     HIP_TRY(ctx, hipMemcpy(yhat, d_yh.p, nh, hipMemcpyDeviceToHost));
     HIP_TRY(ctx, hipMemcpy(yhat_lower, d_lo.p, nh, hipMemcpyDeviceToHost));
     HIP_TRY(ctx, hipMemcpy(yhat_upper, d_hi.p, nh, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- forecast components ------------------------------------------------------------------------------
+
+// What both component entries check before anything is launched: the component table (host data in both, like the
+// spec) against the spec's K, and the interval arguments.
+static int check_component_args(tsf_ctx *ctx, const tsf_spec *spec, int32_t n_comp, const uint64_t *comp_cols,
+                                const int32_t *comp_scaled, double *comp, int32_t n_samples, double interval_width,
+                                double *yhat_lower, double *yhat_upper, double *trend_lower, double *trend_upper)
+{
+    if (n_comp < 0 || n_comp > TSF_MAX_COMP) return fail(ctx, "n_comp must be in [0, TSF_MAX_COMP]");
+    if (n_comp > 0 && (!comp_cols || !comp_scaled || !comp)) return fail(ctx, "NULL component table or output");
+    const int K = tsf_spec_K(spec);
+    for (int32_t c = 0; c < n_comp; ++c)
+        if (K < 64 && (comp_cols[c] >> (K > 0 ? K : 0)) != 0) {
+            char msg[120];
+            snprintf(msg, sizeof(msg), "comp_cols[%d]: a column at or above K = %d", (int)c, K);
+            return fail(ctx, msg);
+        }
+    if (n_samples != 0) {
+        if (n_samples < 2 || n_samples > 4096) return fail(ctx, "n_samples must be 0 or in [2, 4096]");
+        if (!(interval_width > 0.0 && interval_width < 1.0)) return fail(ctx, "interval_width must be in (0, 1)");
+        if (!yhat_lower || !yhat_upper || !trend_lower || !trend_upper) return fail(ctx, "NULL interval output");
+    }
+    return 0;
+}
+
+extern "C" int tsf_predict_components_dev(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H,
+                                          const double *theta, const double *y_scale, const tsf_grid_info *grid,
+                                          int32_t n_grids, const int64_t *ds_future, int32_t shared_future,
+                                          const double *floor_, const double *cap, const double *extra_future,
+                                          int32_t n_comp, const uint64_t *comp_cols, const int32_t *comp_scaled,
+                                          const int64_t *series_key, int32_t n_samples, double interval_width,
+                                          uint64_t seed, double *yhat, double *trend, double *comp,
+                                          double *yhat_lower, double *yhat_upper, double *trend_lower,
+                                          double *trend_upper, void *stream)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (N <= 0 || H <= 0) return fail(ctx, "N and H must be > 0");
+    if (!spec || !theta || !y_scale || !grid || !ds_future || !yhat || !trend) return fail(ctx, "NULL input");
+    if (n_grids != 1 && n_grids != N) return fail(ctx, "n_grids must be 1 or N");
+    if (int rc = check_component_args(ctx, spec, n_comp, comp_cols, comp_scaled, comp, n_samples, interval_width,
+                                      yhat_lower, yhat_upper, trend_lower, trend_upper))
+        return rc;
+    DevSpec hs;
+    int mode = 0;
+    int rc = build_devspec(ctx, spec, &hs, &mode);
+    if (rc) return rc;
+    if (hs.n_extra > 0 && !extra_future) return fail(ctx, "extra_future is NULL");
+    if (hs.growth == TSF_GROWTH_LOGISTIC && !cap) return fail(ctx, "logistic growth needs cap");
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_spec, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
+    const size_t tab_flags = sizeof(uint64_t) * TSF_MAX_COMP;
+    if (n_comp > 0) {
+        if (!ctx->comp_tab) HIP_TRY(ctx, hipMalloc(&ctx->comp_tab, tab_flags + sizeof(int32_t) * TSF_MAX_COMP));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->comp_tab, comp_cols, sizeof(uint64_t) * n_comp, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync((char *)ctx->comp_tab + tab_flags, comp_scaled, sizeof(int32_t) * n_comp,
+                                    hipMemcpyHostToDevice, st));
+    }
+    PredictArgs p;
+    memset(&p, 0, sizeof(p));
+    p.sp = ctx->d_spec; p.N = N; p.H = H; p.theta_stride = tsf_theta_stride(spec);
+    p.n_grids = n_grids; p.shared_future = shared_future; p.theta = theta; p.y_scale = y_scale;
+    p.grid = grid; p.ds_future = ds_future; p.floor_ = floor_; p.cap = cap;
+    p.extra_future = extra_future; p.yhat = yhat; p.yhat_int = nullptr; p.trend_out = trend;
+    bool tab_ready = false;
+    if (n_samples == 0) {
+        if (int prc = launch_predict(ctx, hs, p, 0, N, &tab_ready, st)) return prc;
+    } else {
+        // tsf_predict_intervals_dev's scheme with a second sample buffer (the sampled trend): a chunk's scratch,
+        // 3 + 2 n_samples values per row, stays within 512 MB of the same cached block
+        const size_t per_series = (size_t)H * 8 * (3 + 2 * (size_t)n_samples);
+        int64_t chunk = (int64_t)(((size_t)512 << 20) / per_series);
+        if (chunk < 1) chunk = 1;
+        if (chunk > N) chunk = N;
+        const size_t nh = (size_t)chunk * H;
+        const size_t need = 8 * nh * (3 + 2 * (size_t)n_samples);
+        if (ctx->iv_ws_bytes < need) {
+            if (ctx->iv_ws) { HIP_TRY(ctx, hipFree(ctx->iv_ws)); ctx->iv_ws = nullptr; ctx->iv_ws_bytes = 0; }
+            HIP_TRY(ctx, hipMalloc(&ctx->iv_ws, need));
+            ctx->iv_ws_bytes = need;
+        }
+        double *d_t = (double *)ctx->iv_ws, *d_xa = d_t + nh, *d_opm = d_xa + nh, *d_samp = d_opm + nh;
+        double *d_tsamp = d_samp + nh * n_samples;
+        p.t_out = d_t; p.xa_out = d_xa; p.opm_out = d_opm;
+        int NSP = 2;
+        while (NSP < n_samples) NSP <<= 1;
+        IntervalArgs a;
+        memset(&a, 0, sizeof(a));
+        a.sp = ctx->d_spec; a.H = H; a.theta_stride = tsf_theta_stride(spec); a.n_grids = n_grids; a.NS = n_samples;
+        a.theta = theta; a.y_scale = y_scale; a.grid = grid; a.floor_ = floor_; a.cap = cap;
+        a.series_key = series_key; a.seed = seed;
+        a.lo_frac = (1.0 - interval_width) / 2.0; a.hi_frac = (1.0 + interval_width) / 2.0;
+        a.samples = d_samp; a.trend_samples = d_tsamp; a.lower = yhat_lower; a.upper = yhat_upper;
+        IntervalArgs b = a;                 // the percentiles of the sampled trend
+        b.samples = d_tsamp; b.trend_samples = nullptr; b.lower = trend_lower; b.upper = trend_upper;
+        for (int64_t n0 = 0; n0 < N; n0 += chunk) {
+            const int64_t nc = (N - n0 < chunk) ? N - n0 : chunk;
+            if (int prc = launch_predict(ctx, hs, p, n0, nc, &tab_ready, st)) return prc;
+            a.n0 = b.n0 = n0; a.n_chunk = b.n_chunk = nc;
+            a.t = d_t - (size_t)n0 * H; a.xa = d_xa - (size_t)n0 * H; a.opm = d_opm - (size_t)n0 * H;
+            hipLaunchKernelGGL(interval_sample_kernel, dim3((unsigned)nc, (unsigned)((n_samples + 255) / 256)),
+                               dim3(256), 0, st, a);
+            HIP_TRY(ctx, hipGetLastError());
+            hipLaunchKernelGGL(interval_percentile_kernel, dim3((unsigned)(nc * H)), dim3(256),
+                               sizeof(double) * NSP, st, a, NSP);
+            HIP_TRY(ctx, hipGetLastError());
+            hipLaunchKernelGGL(interval_percentile_kernel, dim3((unsigned)(nc * H)), dim3(256),
+                               sizeof(double) * NSP, st, b, NSP);
+            HIP_TRY(ctx, hipGetLastError());
+        }
+    }
+    if (n_comp > 0) {
+        // behind the predict launches: a shared future grid's design table is built
+        ComponentArgs c;
+        memset(&c, 0, sizeof(c));
+        c.sp = ctx->d_spec; c.N = N; c.H = H; c.theta_stride = tsf_theta_stride(spec);
+        c.shared_future = shared_future; c.n_comp = n_comp; c.theta = theta; c.y_scale = y_scale;
+        c.ds_future = ds_future; c.extra_future = extra_future; c.Xf = shared_future ? ctx->fut_tab : nullptr;
+        c.cols = (const uint64_t *)ctx->comp_tab;
+        c.scaled = (const int32_t *)((const char *)ctx->comp_tab + tab_flags);
+        c.comp = comp;
+        hipLaunchKernelGGL(component_kernel, dim3((unsigned)((N + COMP_WAVES - 1) / COMP_WAVES)), dim3(COMP_WAVES * 64),
+                           0, st, c);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" int tsf_predict_components(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H,
+                                      const double *theta, const double *y_scale, const tsf_grid_info *grid,
+                                      int32_t n_grids, const int64_t *ds_future, int32_t shared_future,
+                                      const double *floor_, const double *cap, const double *extra_future,
+                                      int32_t n_comp, const uint64_t *comp_cols, const int32_t *comp_scaled,
+                                      const int64_t *series_key, int32_t n_samples, double interval_width,
+                                      uint64_t seed, double *yhat, double *trend, double *comp,
+                                      double *yhat_lower, double *yhat_upper, double *trend_lower, double *trend_upper)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (N <= 0 || H <= 0) return fail(ctx, "N and H must be > 0");
+    if (!spec || !theta || !y_scale || !grid || !ds_future || !yhat || !trend) return fail(ctx, "NULL input");
+    if (n_grids != 1 && n_grids != N) return fail(ctx, "n_grids must be 1 or N");
+    if (int rc = check_grids(ctx, spec, grid, n_grids)) return rc;
+    if (int rc = check_component_args(ctx, spec, n_comp, comp_cols, comp_scaled, comp, n_samples, interval_width,
+                                      yhat_lower, yhat_upper, trend_lower, trend_upper))
+        return rc;
+    const bool iv = n_samples != 0;
+    const int stride = tsf_theta_stride(spec);
+    const size_t nfut = shared_future ? (size_t)H : (size_t)N * H;
+    DevBuf d_th, d_ys, d_grid, d_ds, d_fl, d_cap, d_ex, d_key, d_yh, d_tr, d_co, d_lo, d_hi, d_tlo, d_thi;
+    HIP_TRY(ctx, d_th.alloc(8 * (size_t)N * stride));
+    HIP_TRY(ctx, hipMemcpy(d_th.p, theta, 8 * (size_t)N * stride, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_ys.alloc(8 * N));
+    HIP_TRY(ctx, hipMemcpy(d_ys.p, y_scale, 8 * N, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_grid.alloc(sizeof(tsf_grid_info) * n_grids));
+    HIP_TRY(ctx, hipMemcpy(d_grid.p, grid, sizeof(tsf_grid_info) * n_grids, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_ds.alloc(8 * nfut));
+    HIP_TRY(ctx, hipMemcpy(d_ds.p, ds_future, 8 * nfut, hipMemcpyHostToDevice));
+    if (floor_) { HIP_TRY(ctx, d_fl.alloc(8 * N)); HIP_TRY(ctx, hipMemcpy(d_fl.p, floor_, 8 * N, hipMemcpyHostToDevice)); }
+    if (cap) { HIP_TRY(ctx, d_cap.alloc(8 * N)); HIP_TRY(ctx, hipMemcpy(d_cap.p, cap, 8 * N, hipMemcpyHostToDevice)); }
+    if (iv && series_key) { HIP_TRY(ctx, d_key.alloc(8 * N)); HIP_TRY(ctx, hipMemcpy(d_key.p, series_key, 8 * N, hipMemcpyHostToDevice)); }
+    if (spec->n_extra > 0) {
+        if (!extra_future) return fail(ctx, "extra_future is NULL");
+        const size_t nb = 8 * (size_t)spec->n_extra * nfut;
+        HIP_TRY(ctx, d_ex.alloc(nb));
+        HIP_TRY(ctx, hipMemcpy(d_ex.p, extra_future, nb, hipMemcpyHostToDevice));
+    }
+    const size_t nh = 8 * (size_t)N * H;
+    HIP_TRY(ctx, d_yh.alloc(nh)); HIP_TRY(ctx, d_tr.alloc(nh));
+    if (n_comp > 0) HIP_TRY(ctx, d_co.alloc(nh * n_comp));
+    if (iv) { HIP_TRY(ctx, d_lo.alloc(nh)); HIP_TRY(ctx, d_hi.alloc(nh)); HIP_TRY(ctx, d_tlo.alloc(nh)); HIP_TRY(ctx, d_thi.alloc(nh)); }
+    int rc = tsf_predict_components_dev(ctx, spec, N, H, d_th.as<double>(), d_ys.as<double>(),
+                                        d_grid.as<tsf_grid_info>(), n_grids, d_ds.as<int64_t>(), shared_future,
+                                        floor_ ? d_fl.as<double>() : nullptr, cap ? d_cap.as<double>() : nullptr,
+                                        spec->n_extra > 0 ? d_ex.as<double>() : nullptr, n_comp, comp_cols, comp_scaled,
+                                        (iv && series_key) ? d_key.as<int64_t>() : nullptr, n_samples, interval_width,
+                                        seed, d_yh.as<double>(), d_tr.as<double>(),
+                                        n_comp > 0 ? d_co.as<double>() : nullptr,
+                                        iv ? d_lo.as<double>() : nullptr, iv ? d_hi.as<double>() : nullptr,
+                                        iv ? d_tlo.as<double>() : nullptr, iv ? d_thi.as<double>() : nullptr, nullptr);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    HIP_TRY(ctx, hipMemcpy(yhat, d_yh.p, nh, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(trend, d_tr.p, nh, hipMemcpyDeviceToHost));
+    if (n_comp > 0) HIP_TRY(ctx, hipMemcpy(comp, d_co.p, nh * n_comp, hipMemcpyDeviceToHost));
+    if (iv) {
+        HIP_TRY(ctx, hipMemcpy(yhat_lower, d_lo.p, nh, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(yhat_upper, d_hi.p, nh, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(trend_lower, d_tlo.p, nh, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(trend_upper, d_thi.p, nh, hipMemcpyDeviceToHost));
+    }
     return 0;
 }
 

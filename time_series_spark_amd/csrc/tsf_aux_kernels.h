@@ -373,6 +373,7 @@ struct PredictArgs {
     // optional per-row pieces for the interval kernels (tsf_interval_kernels.h): scaled time,
     // additive term * y_scale, 1 + multiplicative term
     double *t_out, *xa_out, *opm_out;
+    double *trend_out;          // optional [N][H]: the trend in original units (tsf_predict_components)
     const double *Xf;           // shared future grid: [K][H] design values in ORIGINAL column order
 };
 
@@ -511,6 +512,7 @@ __global__ __launch_bounds__(PREDICT_WAVES * 64) void predict_kernel(PredictArgs
         const double trend = gtr * ys + fl;
         const double yh = trend * (1.0 + xm) + xa * ys;
         a.yhat[gid] = yh;
+        if (a.trend_out) a.trend_out[gid] = trend;
         if (a.t_out) { a.t_out[gid] = t; a.xa_out[gid] = xa * ys; a.opm_out[gid] = 1.0 + xm; }
         if (a.yhat_int) {
             // prophet_scorer.py:73 astype(int) truncates toward zero; :76-84 clamp to floor

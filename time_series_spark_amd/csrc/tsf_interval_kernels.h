@@ -7,7 +7,7 @@
 // sample, stream), deterministic transcendentals, the sampled changepoint times generated already
 // sorted.  These kernels consume the same streams in the same order: bit-identical to the oracle.
 //   interval_sample_kernel      one thread per (series, sample): sweeps the future rows, writes
-//                               samples[series][row][sample]
+//                               samples[series][row][sample] (and, where asked, the sampled trend alike)
 //   interval_percentile_kernel  one workgroup per (series, row): bitonic sort of the samples in LDS,
 //                               the two percentiles by linear interpolation (np.nanpercentile)
 // Non-template __global__ functions: include from exactly one translation unit (tsf_api.hip).
@@ -60,6 +60,7 @@ struct IntervalArgs {
     uint64_t seed;
     double lo_frac, hi_frac;    // (1 - width) / 2, (1 + width) / 2
     double *samples;            // [n_chunk][H][NS]
+    double *trend_samples;      // optional [n_chunk][H][NS]: each sample's trend before noise (tsf_predict_components)
     double *lower, *upper;      // [N][H]
 };
 
@@ -132,6 +133,7 @@ __global__ __launch_bounds__(256) void interval_sample_kernel(IntervalArgs a)
         dm_sincos(6.283185307179586 * u2, sn, cs);
         const double z = __builtin_sqrt(-2.0 * dm_log(u1)) * cs;
         out[(size_t)h * a.NS] = trend * opm[h] + xa[h] + (z * sigma) * ys;
+        if (a.trend_samples) a.trend_samples[(size_t)nl * H * a.NS + s + (size_t)h * a.NS] = trend;
     }
 }
 

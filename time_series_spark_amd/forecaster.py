@@ -476,6 +476,179 @@ def predict_intervals(spec, theta, y_scale, grid, ds_future_ns, floor=None, cap=
     return yhat, lo, hi
 
 
+# ---- forecast components ----------------------------------------------------------------------------
+# fbprophet 0.5's Prophet.predict returns the decomposition beside yhat: trend, one column per seasonality /
+# holiday / regressor, the group totals, each with _lower / _upper (regressor_column_matrix, add_group_component,
+# predict_seasonal_components, predict_uncertainty; restated from recall, parity with the real package not pinned).
+# The library computes any set of components given as design-column masks (include/tsf.h tsf_predict_components);
+# component_columns names the sets fbprophet forms for a model.
+
+def component_columns(spec):
+    """[(name, mask, scaled)] of the components fbprophet 0.5 forms for `spec`, in its column order: the columns of
+    pandas.crosstab over (design column, component), i.e. sorted by name, then 'additive_terms' / 'multiplicative_terms'
+    appended if they have no column (regressor_column_matrix adds them empty, behind the others).  mask: bit j =
+    original design column j; scaled: the component is additive (times y_scale).  Components: one per seasonality; one
+    per holiday (the name before '_delim_' of the leading extra columns features.holiday_columns(spec.holidays) names)
+    and 'holidays'; one per other extra column (a regressor) except the 'zeros' placeholder, and
+    'extra_regressors_additive' / '_multiplicative' where non-empty; 'additive_terms' and 'multiplicative_terms'."""
+    from . import features
+    ADD, MUL = 'additive', 'multiplicative'
+    masks, modes = {}, {}
+    total = {ADD: 0, MUL: 0}
+    reg = {ADD: 0, MUL: 0}
+
+    def put(name, bits, mode):
+        masks[name] = masks.get(name, 0) | bits
+        modes[name] = mode
+        total[mode] |= bits
+
+    col = 0
+    for se in spec.seasonalities:
+        w = 2 * int(se['fourier_order'])
+        if w:
+            put(se['name'], ((1 << w) - 1) << col, se.get('mode', spec.seasonality_mode))
+        col += w
+    n_hol = len(features.holiday_columns(features.normalize_holidays(spec.holidays))[0]) if spec.holidays else 0
+    hol = 0
+    for e, ex in enumerate(spec.extra):
+        bit, mode = 1 << (col + e), ex.get('mode', spec.seasonality_mode)
+        if e < n_hol:
+            put(ex['name'].split('_delim_')[0], bit, mode)
+            hol |= bit
+        elif ex['name'] == 'zeros':           # fbprophet's placeholder column: in its mode's total, no component of its own
+            total[mode] |= bit
+        else:
+            put(ex['name'], bit, mode)
+            reg[mode] |= bit
+    if hol:
+        masks['holidays'], modes['holidays'] = hol, spec.seasonality_mode
+    for mode in (ADD, MUL):
+        if reg[mode]:
+            masks['extra_regressors_' + mode], modes['extra_regressors_' + mode] = reg[mode], mode
+        if total[mode]:
+            masks[mode + '_terms'], modes[mode + '_terms'] = total[mode], mode
+    names = sorted(masks)
+    for mode in (ADD, MUL):
+        if not total[mode]:
+            names.append(mode + '_terms')
+            masks[mode + '_terms'], modes[mode + '_terms'] = 0, mode
+    return [(n, masks[n], int(modes[n] == ADD)) for n in names]
+
+
+class Components(object):
+    """What predict_components returns: names [C]; yhat, trend [N][H]; comp [N][C][H] and terms (name -> its [N][H]
+    view of comp); trend_lower / trend_upper / yhat_lower / yhat_upper [N][H] with intervals, else None."""
+
+    def __init__(self, spec, names, yhat, trend, comp, yhat_lower=None, yhat_upper=None, trend_lower=None,
+                 trend_upper=None, floor=None, cap=None):
+        self.spec, self.names = spec, list(names)
+        self.yhat, self.trend, self.comp = yhat, trend, comp
+        self.terms = {name: comp[:, i, :] for i, name in enumerate(self.names)}
+        self.yhat_lower, self.yhat_upper = yhat_lower, yhat_upper
+        self.trend_lower, self.trend_upper = trend_lower, trend_upper
+        self.floor, self.cap = floor, cap
+
+    @property
+    def intervals(self):
+        return self.yhat_lower is not None
+
+    def frame(self, n, ds, cap=None, floor=None):
+        """Series n as a DataFrame in fbprophet 0.5's predict() layout: ds, trend, cap and floor (logistic growth; default:
+        the values predict_components was given), yhat_lower, yhat_upper, trend_lower, trend_upper (with intervals), then
+        per component c: c, c_lower, c_upper (a MAP fit has one beta: all three equal), yhat last."""
+        import pandas as pd
+        ds = np.asarray(ds)
+        if ds.dtype.kind != 'M':
+            ds = ds.astype(np.int64).view('datetime64[ns]')
+        cols = {'ds': ds, 'trend': self.trend[n]}
+        if self.spec.growth == 'logistic':
+            cap = self.cap[n] if cap is None and self.cap is not None else cap
+            if cap is None:
+                raise ValueError('logistic growth: cap is needed')
+            floor = (self.floor[n] if self.floor is not None else 0.0) if floor is None else floor
+            cols['cap'] = np.broadcast_to(np.asarray(cap, dtype=np.float64), ds.shape)
+            cols['floor'] = np.broadcast_to(np.asarray(floor, dtype=np.float64), ds.shape)
+        if self.intervals:
+            for k in ('yhat_lower', 'yhat_upper', 'trend_lower', 'trend_upper'):
+                cols[k] = getattr(self, k)[n]
+        for name in self.names:
+            v = self.terms[name][n]
+            cols[name], cols[name + '_lower'], cols[name + '_upper'] = v, v, v
+        cols['yhat'] = self.yhat[n]
+        return pd.DataFrame(cols, columns=list(cols))
+
+
+def predict_components(spec, theta, y_scale, grid, ds_future_ns, floor=None, cap=None, extra_future=None,
+                       intervals=False, series_key=None, uncertainty_samples=1000, interval_width=0.8, seed=0,
+                       ctx=None, devices=None, columns=None):
+    """Trend, yhat and the components of component_columns(spec) (or `columns`: [(name, mask, scaled)]) for every
+    series (include/tsf.h tsf_predict_components) -> Components.  yhat is predict's bit for bit; with intervals,
+    yhat_lower / yhat_upper are predict_intervals' (same series_key, samples, width, seed) and trend_lower /
+    trend_upper the same percentiles of the sampled trend.  devices: as predict."""
+    cols = component_columns(spec) if columns is None else [tuple(c) for c in columns]
+    devs = None if ctx is not None else resolve_devices(devices)
+    if devs and len(theta) >= 2 * MIN_SERIES_PER_DEVICE:
+        N = len(theta)
+        parts = min(len(devs), N // MIN_SERIES_PER_DEVICE)
+        cuts = _cuts(np.ones(N, np.int64), parts)
+        fl = _opt_f64(floor, N, 'floor')
+        cp = _opt_f64(cap, N, 'cap')
+        fut = np.asarray(ds_future_ns)
+        exf = None if extra_future is None else np.asarray(extra_future)
+        key = None if series_key is None else np.asarray(series_key, dtype=np.int64)
+        blocks = [(c, int(a), int(b)) for c, a, b in zip(_contexts(devs[:parts]), cuts[:-1], cuts[1:])]
+
+        def one(c, a, b):
+            return predict_components(spec, theta[a:b], np.asarray(y_scale)[a:b],
+                                      grid if len(grid) == 1 else grid[a:b], fut if fut.ndim == 1 else fut[a:b],
+                                      None if fl is None else fl[a:b], None if cp is None else cp[a:b],
+                                      exf if (exf is None or fut.ndim == 1) else exf[a:b], intervals=intervals,
+                                      # (the default key is the series' index in the whole call)
+                                      series_key=np.arange(a, b, dtype=np.int64) if key is None else key[a:b],
+                                      uncertainty_samples=uncertainty_samples, interval_width=interval_width,
+                                      seed=seed, ctx=c, columns=cols)
+        res = _run_blocks(one, blocks)
+        cat = lambda k: None if getattr(res[0], k) is None else np.concatenate([getattr(r, k) for r in res])  # noqa: E731
+        return Components(spec, res[0].names, cat('yhat'), cat('trend'), cat('comp'), cat('yhat_lower'),
+                          cat('yhat_upper'), cat('trend_lower'), cat('trend_upper'), fl, cp)
+    ctx = ctx or get_context()
+    L = _lib.load()
+    theta = np.ascontiguousarray(theta, dtype=np.float64)
+    N = theta.shape[0]
+    y_scale = np.ascontiguousarray(y_scale, dtype=np.float64)
+    grid = np.ascontiguousarray(grid, dtype=_lib.GRID_DTYPE)
+    ds_future_ns = np.ascontiguousarray(ds_future_ns, dtype=np.int64)
+    shared = ds_future_ns.ndim == 1
+    H = ds_future_ns.shape[-1]
+    if not shared and ds_future_ns.shape != (N, H):
+        raise ValueError('ds_future must be [H] or [N][H]')
+    cs = spec.to_c()
+    floor = _opt_f64(floor, N, 'floor')
+    cap = _opt_f64(cap, N, 'cap')
+    ex = None
+    if spec.extra:
+        ex = np.ascontiguousarray(extra_future, dtype=np.float64)
+        want = (len(spec.extra), H) if shared else (N, len(spec.extra), H)
+        if ex.shape != want:
+            raise ValueError('extra_future must be %r' % (want,))
+    key = None if series_key is None else np.ascontiguousarray(series_key, dtype=np.int64)
+    if key is not None and key.shape != (N,):
+        raise ValueError('series_key must be [N]')
+    C = len(cols)
+    masks = np.array([int(m) for _, m, _ in cols], dtype=np.uint64)
+    scaled = np.array([int(s) for _, _, s in cols], dtype=np.int32)
+    yhat, trend, comp = np.zeros((N, H)), np.zeros((N, H)), np.zeros((N, C, H))
+    iv = [np.zeros((N, H)) for _ in range(4)] if intervals else [None] * 4
+    rc = L.tsf_predict_components(ctx.handle, ctypes.byref(cs), N, H, theta.ctypes.data, y_scale.ctypes.data,
+                                  grid.ctypes.data, len(grid), ds_future_ns.ctypes.data, int(shared),
+                                  _lib._ptr(floor), _lib._ptr(cap), _lib._ptr(ex), C, masks.ctypes.data,
+                                  scaled.ctypes.data, _lib._ptr(key), int(uncertainty_samples) if intervals else 0,
+                                  float(interval_width), int(seed), yhat.ctypes.data, trend.ctypes.data,
+                                  comp.ctypes.data, *[_lib._ptr(a) for a in iv])
+    ctx.check(rc)
+    return Components(spec, [c[0] for c in cols], yhat, trend, comp, *iv, floor=floor, cap=cap)
+
+
 # ---- diagnostics used by the parity tests -----------------------------------------------------
 
 def eval_aligned(spec, ds_ns, y, theta, floor=None, cap=None, extra=None, ctx=None):

@@ -31,7 +31,8 @@ def _empty_forecasts():
 def forecast_arrays(config):
     """The predict UDF on columns that never were a DataFrame: (series_id, dim_id, floor, cap, models) -> dict of the
     forecast frame's columns (series_id, dim_id int32; ds int64 ns; yhat int32; yhat_lower / yhat_upper when
-    forecast.intervals), `periods` rows per series, or None when there is nothing to forecast.  models: a list of blobs
+    forecast.intervals; trend, trend_lower / trend_upper and the components' float64 columns when forecast.components),
+    `periods` rows per series, or None when there is nothing to forecast.  models: a list of blobs
     (None = no model) or the uint8 [n][L] buffer of a model column whose blobs share one length
     (panel.model_column_buffer: a parquet column as it lies in memory, no Python object per series)."""
 
@@ -87,25 +88,33 @@ def forecast_arrays(config):
                                     want_int=True,      # :70-84
                                     devices=config.get('devices'))
             lap('predict')
-            iv = None
-            if (config.get('forecast') or {}).get('intervals'):
-                # not in the reference's output (it drops yhat_lower / yhat_upper, :86): opt-in extra
-                # columns; the random streams are keyed by (series_id, dim_id), so a series gets the
+            iv = comps = None
+            fcfg = config.get('forecast') or {}
+            if fcfg.get('intervals') or fcfg.get('components'):
+                # not in the reference's output (it drops yhat_lower / yhat_upper and the components, :86): opt-in
+                # extra columns; the random streams are keyed by (series_id, dim_id), so a series gets the
                 # same interval whatever frame it arrives in
-                fcfg = config['forecast']
                 key = (sids[idx].astype(np.int64) << 32) ^ (dids[idx].astype(np.int64) & 0xffffffff)
-                _, lo, hi = fc.predict_intervals(
-                    spec, theta, rec['y_scale'], grid, fut, floor=floor, cap=cap,
-                    extra_future=ex if (ex is None or fut.ndim == 2) else np.ascontiguousarray(ex[0]),
-                    series_key=key, uncertainty_samples=int(fcfg.get('uncertainty_samples', 1000)),
-                    interval_width=float(fcfg.get('interval_width', 0.8)), seed=int(fcfg.get('seed', 0)))
-                iv = (lo, hi)
+                kw = dict(floor=floor, cap=cap,
+                          extra_future=ex if (ex is None or fut.ndim == 2) else np.ascontiguousarray(ex[0]),
+                          series_key=key, uncertainty_samples=int(fcfg.get('uncertainty_samples', 1000)),
+                          interval_width=float(fcfg.get('interval_width', 0.8)), seed=int(fcfg.get('seed', 0)))
+                if fcfg.get('components'):
+                    # (its yhat_lower / yhat_upper are predict_intervals' bit for bit: include/tsf.h)
+                    comps = fc.predict_components(spec, theta, rec['y_scale'], grid, fut,
+                                                  intervals=bool(fcfg.get('intervals')),
+                                                  devices=config.get('devices'), **kw)
+                    if fcfg.get('intervals'):
+                        iv = (comps.yhat_lower, comps.yhat_upper)
+                else:
+                    _, lo, hi = fc.predict_intervals(spec, theta, rec['y_scale'], grid, fut, **kw)
+                    iv = (lo, hi)
             for j in np.flatnonzero((np.trunc(yhat) < floor[:, None]).any(axis=1)):
                 print(f"Negative forecast values found for series_id: {int(sids[idx[j]])}, "
                       f"dim_id: {int(dids[idx[j]])}")                    # :77-79
             if fut.ndim == 1:
                 fut = np.broadcast_to(fut, (len(idx), periods))
-            pieces.append((idx, fut, yint, iv))
+            pieces.append((idx, fut, yint, iv, comps))
             lap('negative check')
         if not pieces:
             return None
@@ -121,6 +130,16 @@ def forecast_arrays(config):
         if pieces[0][3] is not None:
             res['yhat_lower'] = np.concatenate([p[3][0].reshape(-1) for p in pieces])
             res['yhat_upper'] = np.concatenate([p[3][1].reshape(-1) for p in pieces])
+        if pieces[0][4] is not None:
+            # forecast.components: trend (+ trend_lower / trend_upper with intervals) and one column per component name of
+            # any bucket, 0.0 where a bucket's model has no such component (what an absent term contributes)
+            res['trend'] = np.concatenate([p[4].trend.reshape(-1) for p in pieces])
+            if pieces[0][4].intervals:
+                res['trend_lower'] = np.concatenate([p[4].trend_lower.reshape(-1) for p in pieces])
+                res['trend_upper'] = np.concatenate([p[4].trend_upper.reshape(-1) for p in pieces])
+            for name in sorted(set().union(*[p[4].names for p in pieces])):
+                res[name] = np.concatenate([p[4].terms[name].reshape(-1) if name in p[4].terms
+                                            else np.zeros(len(p[0]) * periods) for p in pieces])
         lap('columns')
         lap.__exit__()
         return res
@@ -142,7 +161,7 @@ def forecast_panel(config):
             return _empty_forecasts()
         cols['ds'] = cols['ds'].view('datetime64[ns]')
         # (copy=True stacks the three int32 columns into one block: a copy of 900 000 x 3)
-        return pd.DataFrame(cols, columns=FORECAST_COLUMNS + [c for c in ('yhat_lower', 'yhat_upper') if c in cols], copy=False)
+        return pd.DataFrame(cols, columns=FORECAST_COLUMNS + [c for c in cols if c not in FORECAST_COLUMNS], copy=False)
 
     return forecast_panel_fn
 
