@@ -7,15 +7,21 @@ points span 729 d < fbprophet's 730 d auto threshold) additive Fourier seasonali
 Stan-style L-BFGS (Stan's default tolerances), then a 90-step forecast.  A "step" is ONE PASS
 of that fit + predict over the whole panel with the panel already resident in HBM.
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, runs the W warm-up and K timed steps, writes --dump-outputs and prints the line:
+`value`, `ms_per_step` and the figures derived from those steps alone (`config`, `optimizer`, `roofline`
+from the library's kernel timers and the committed PMC profile).  Everything else -- the legs below, the
+scaling model and checks, the device-copy peak, cost hints, the host-pointer entry, parity context, CPU
+baselines and the boundary legs -- runs only with --full (and its --no-* / --timed-only switches).
 
 Multi-GPU: series are sharded by id, one rank per GPU, no data-path collective;
 torch.distributed (RCCL) only brackets the timed regions and gathers the evaluation counts.
 `value` is the BASELINE metric read literally for every N: ONE 10 000-series panel, split over the
 ranks for N > 1 (series i on rank i mod N: parallel.shard_indices) -- STRONG scaling.  A launch cannot
 end before its longest fit, so this panel stops scaling early (`strong_scaling_expectation` states the
-ceiling next to the measurement).  Beside it, timed the same way:
+ceiling next to the measurement).  Beside it, timed the same way (--full):
   * `weak_scaling` (N > 1): every rank its own 10 000-series panel;
   * `cfg3_sharded` (every N): BASELINE config 3 -- 100 000 series x 1 095 points as 8 blocks of 12 500,
     block b on rank b mod N -- the configuration that has enough work per GPU to scale;
@@ -310,6 +316,26 @@ def simulate_strong_scaling(n_eval, fit_ms, n_cu, waves_per_cu=12):
         out['gpus'][str(g)] = {'fit_kernel_ms': ms, 'series_per_s_kernel_only': len(n_eval) / (ms * 1e-3)}
     out['longest_series_ms'] = float(n_eval.max()) * tau_ms
     return out
+
+
+def device_copy_gbps(dev):
+    """Measured HBM ceiling on this device beside the 8 TB/s spec figure: device-to-device copy of
+    1 GiB (reads + writes counted), outside the timed region (torch only moves memory here)."""
+    import torch
+    try:
+        src = torch.empty(1 << 28, dtype=torch.float32, device=dev).normal_()
+        dst = torch.empty_like(src)
+        dst.copy_(src)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(5):
+            dst.copy_(src)
+        e1.record()
+        torch.cuda.synchronize()
+        return 5 * 2 * src.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9
+    except Exception:
+        return None
 
 
 def pmc_traffic(kernel):
@@ -694,13 +720,18 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=2)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-cfg3', action='store_true', help='skip the cfg3_sharded leg (100 000 x 1 095 over the ranks)')
-    ap.add_argument('--no-other-configs', action='store_true', help='skip the other_baseline_configs leg (cfg1, cfg4, reference settings)')
-    ap.add_argument('--no-boundary', action='store_true', help='skip the files_to_files / dataframe_boundary legs')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline steps, run every other leg: scaling, other configurations, boundary, '
+                         'parity context, CPU baselines (the switches below drop some of them)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines and vs_true_map')
+    ap.add_argument('--no-cfg3', action='store_true', help='with --full: skip the cfg3_sharded leg (100 000 x 1 095 over the ranks)')
+    ap.add_argument('--no-other-configs', action='store_true',
+                    help='with --full: skip the other_baseline_configs leg (cfg1, cfg4, reference settings)')
+    ap.add_argument('--no-boundary', action='store_true', help='with --full: skip the files_to_files / dataframe_boundary legs')
     ap.add_argument('--timed-only', action='store_true',
-                    help='only warm-up + the K timed steps (for rocprofv3 runs: every dispatch of the fit '
-                         'kernel is then a full-panel launch, so per-kernel means are per launch)')
+                    help='with --full: only warm-up + the K timed steps, the weak_scaling leg of N > 1 and the '
+                         'device-copy peak (for rocprofv3 runs: every dispatch of the fit kernel is then a full-panel '
+                         'launch, so per-kernel means are per launch); a plain run is leaner still')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='write what the last timed step computed (fit outputs and forecasts of the panel) '
                          'as DIR/<name>.npy, float64, at most 64 MB in all')
@@ -763,10 +794,10 @@ def main():
 
     dt, kernel_ms, out, yhat, yhat_int = timed_leg(y)
     dumped = dump_outputs(args.dump_outputs, out, yhat, yhat_int, dev, rank) if args.dump_outputs else None
-    seen = ranks_seen(dev, local)        # (a collective: every rank)
+    seen = ranks_seen(dev, local) if args.full else None       # (a collective: every rank)
 
     weak = None
-    if world > 1:
+    if world > 1 and args.full:
         _, yw_np = synth.make_panel(N_SERIES, T_POINTS, 'linear', seed=751 + rank)
         dtw, kmsw, _, _, _ = timed_leg(torch.from_numpy(yw_np).to(dev))
         weak = {'value': world * N_SERIES * args.steps / dtw, 'unit': 'series/s', 'ms_per_step': 1e3 * dtw / args.steps,
@@ -778,7 +809,7 @@ def main():
     # GPU to scale -- 8 blocks of 12 500 series (block b = make_panel(12 500, 1 095, seed 3000 + b)), block b on
     # rank b mod N, no collective; same step (fit + 90-step forecast), same bracketing, MAX over ranks
     cfg3 = None
-    if not args.timed_only and not args.no_cfg3 and 8 % world == 0:
+    if args.full and not args.timed_only and not args.no_cfg3 and 8 % world == 0:
         try:
             C3_BLOCKS, C3_N, C3_T = 8, int(os.environ.get('BENCH_C3_BLOCK', '12500')), 1095
             mine = [b for b in range(C3_BLOCKS) if b % world == rank]
@@ -820,26 +851,10 @@ def main():
             cfg3 = {'error': str(e)}
 
     # the evaluation counts of the whole cfg2 panel on every rank, in series order (rank r holds the series i mod world == r)
-    n_eval_all = parallel.gather_rows(out.n_eval.cpu().numpy().astype(np.float64).reshape(-1, 1), N_SERIES, dev)[:, 0]
+    if args.full:
+        n_eval_all = parallel.gather_rows(out.n_eval.cpu().numpy().astype(np.float64).reshape(-1, 1), N_SERIES, dev)[:, 0]
     if rank != 0:
         return
-    # measured HBM ceiling on this device beside the 8 TB/s spec figure: device-to-device copy of
-    # 1 GiB (reads + writes counted), outside the timed region (torch only moves memory here)
-    try:
-        src = torch.empty(1 << 28, dtype=torch.float32, device=dev).normal_()
-        dst = torch.empty_like(src)
-        dst.copy_(src)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(5):
-            dst.copy_(src)
-        e1.record()
-        torch.cuda.synchronize()
-        copy_gbps = 5 * 2 * src.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9
-        del src, dst
-    except Exception:
-        copy_gbps = None
     n_eval = out.n_eval.cpu().numpy().astype(np.int64)
     n_iter = out.n_iter.cpu().numpy()
     status = out.status.cpu().numpy()
@@ -867,9 +882,8 @@ def main():
         # N > 1 -- total work fixed as N grows = STRONG scaling, also at N = 1 (rounds 1-3 reported per-GPU panels for
         # N > 1, i.e. weak scaling: those numbers are `weak_scaling.value` now)
         'scaling': 'strong',
-        'value_scaling': 'strong: one %d-series panel whatever N (weak-scaling figure beside it in weak_scaling for N > 1)' % N_SERIES,
+        'value_scaling': 'strong: one %d-series panel whatever N (with --full, the weak-scaling figure beside it in weak_scaling for N > 1)' % N_SERIES,
         'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
-        'ranks_seen': seen,
         'config': {'workload': 'cfg2: ONE panel of %d series x %d daily points%s, linear trend + 25 '
                                'changepoints, weekly(3)+yearly(10) additive Fourier, MAP L-BFGS '
                                '(Stan default tolerances) + %d-step forecast'
@@ -882,7 +896,7 @@ def main():
                    'parallelism': 'shard-by-id x%d' % world},
         'roofline': {'bound': 'hbm', 'kernel': kernel, 'achieved': achieved,
                      'peak': HBM_PEAK_GBPS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBPS,
-                     'peak_measured_device_copy': copy_gbps,
+                     'peak_measured_device_copy': None,     # (--full measures it)
                      'traffic': traffic, 'traffic_kernel': kernel + ' (the dominant kernel only; step_traffic = all kernels of the step)',
                      'traffic_source': traffic_src,
                      'fetch_size_factor': '2 x FETCH_SIZE: calibrated on 4 GiB streamed once with each load shape of the library '
@@ -917,6 +931,11 @@ def main():
             res['roofline']['step_traffic_over_algorithmic'] = stt['bytes'] / float(bytes_per_series * n_local)
     if dumped is not None:
         res['dump_outputs'] = dumped
+    if not args.full:
+        print(json.dumps(res))
+        return
+    res['ranks_seen'] = seen
+    res['roofline']['peak_measured_device_copy'] = device_copy_gbps(dev)
     if weak is not None:
         res['weak_scaling'] = weak
     if cfg3 is not None:

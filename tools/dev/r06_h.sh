@@ -1,6 +1,6 @@
 #!/bin/bash
 OUT=$PWD/gpurun_out/r06_h; mkdir -p $OUT; export TMPDIR=/tmp
-python bench.py --no-cfg3 --no-other-configs --no-boundary --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -3 $OUT/bench.err
+python bench.py --full --no-cfg3 --no-other-configs --no-boundary --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -3 $OUT/bench.err
 python - <<PY
 import json
 d=json.load(open('$OUT/bench.json'))

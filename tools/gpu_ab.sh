@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 for V in default "$@"; do
   if [ "$V" = default ]; then unset TSF_LIB_PATH; else export TSF_LIB_PATH=$PWD/tools/variants/libtsf_amd_$V.so; fi
   for i in 1 2 3; do
-    timeout 600 python bench.py --steps 5 --warmup 2 --no-cfg3 --no-cpu-baseline > $OUT/bench_${V}_$i.json 2> $OUT/bench_${V}_$i.err
+    timeout 600 python bench.py --full --steps 5 --warmup 2 --no-cfg3 --no-cpu-baseline > $OUT/bench_${V}_$i.json 2> $OUT/bench_${V}_$i.err
     python - <<PY | tee -a $OUT/summary.txt
 import json
 d=json.load(open('$OUT/bench_${V}_$i.json'))

@@ -28,7 +28,7 @@ for leg in $LEGS; do
 done
 fi
 echo "== bench" | tee -a $OUT/summary.txt
-timeout 600 python bench.py --steps 5 --warmup 1 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?" | tee -a $OUT/summary.txt
+timeout 600 python bench.py --full --steps 5 --warmup 1 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?" | tee -a $OUT/summary.txt
 python -c "
 import json; d = json.load(open('$OUT/bench.json')); print('value', d['value'], 'ms_per_step', d['ms_per_step'], 'kernel_ms', d['roofline']['kernel_ms_avg'], 'oracle err', d.get('forecast_max_rel_err_vs_oracle'))" | tee -a $OUT/summary.txt
 if [ -z "$SKIP_PROF" ]; then

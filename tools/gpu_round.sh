@@ -13,7 +13,7 @@ timeout 1500 python -m pytest tests -m gpu -x -q --durations=12 > $OUT/pytest_gp
 tail -5 $OUT/pytest_gpu.log | tee -a $OUT/summary.txt
 fi
 echo "== bench" | tee -a $OUT/summary.txt
-timeout 600 python bench.py --steps $STEPS --warmup 1 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?" | tee -a $OUT/summary.txt
+timeout 600 python bench.py --full --steps $STEPS --warmup 1 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?" | tee -a $OUT/summary.txt
 cat $OUT/bench.json | tee -a $OUT/summary.txt
 if [ -z "$SKIP_PROF" ]; then
 echo "== rocprofv3 kernel stats" | tee -a $OUT/summary.txt

@@ -24,7 +24,7 @@ cp $OUT/pmc_latest.json profiles/pmc_latest.json 2>/dev/null
 python tools/irregular_pmc_summary.py $OUT/prof_irregular $OUT/irregular_pmc_latest.json | tee -a $OUT/summary.txt
 cp $OUT/irregular_pmc_latest.json profiles/irregular_pmc_latest.json 2>/dev/null
 echo "== bench (with the profiles of THIS call in place)" | tee -a $OUT/summary.txt
-timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?" | tee -a $OUT/summary.txt
+timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?" | tee -a $OUT/summary.txt
 cut -c1-1500 $OUT/bench.json | tee -a $OUT/summary.txt
 echo "== configurations" | tee -a $OUT/summary.txt
 timeout 900 python tools/bench_configs.py ${CFGS:-cfg1 cfg3 cfg3_full cfg4 cfg5 cfg2_resid ref10k ref100k cfg2x4 cfg2x16 lin_hol} > $OUT/configs.jsonl 2> $OUT/configs.err

@@ -25,7 +25,7 @@ cp $OUT/pmc_latest.json profiles/pmc_latest.json 2>/dev/null
 python tools/irregular_pmc_summary.py $OUT/prof_irregular $OUT/irregular_pmc_latest.json | tee -a $OUT/summary.txt
 cp $OUT/irregular_pmc_latest.json profiles/irregular_pmc_latest.json 2>/dev/null
 echo "== bench (with the profiles of THIS call in place)" | tee -a $OUT/summary.txt
-( time timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err ) 2> $OUT/bench_time.txt; echo "bench rc=$?" | tee -a $OUT/summary.txt
+( time timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err ) 2> $OUT/bench_time.txt; echo "bench rc=$?" | tee -a $OUT/summary.txt
 tail -3 $OUT/bench_time.txt | tee -a $OUT/summary.txt
 cut -c1-1500 $OUT/bench.json | tee -a $OUT/summary.txt
 echo "== configurations" | tee -a $OUT/summary.txt
