@@ -1067,6 +1067,7 @@ done:
  * j >= 64 term fma'd onto the j - 64 term, then the 64-slot butterfly.  The round-robin Jacobi cross-check keeps
  * its 64 (CN_JACOBI_MAX_P). */
 #define CN_NEWTON_MAX_P 128
+#define CN_NEWTON_QGUARD 0x1p-20   /* halving trial in residual form when the quadratic form's SSE cancels (cn_newton) */
 #define CN_JACOBI_MAX_P 64
 enum { TERM_NEWTON_CONVERGED = 60, CN_NEWTON_FAIL = -4, CN_NEWTON_TOO_WIDE = -13 };
 
@@ -1396,11 +1397,19 @@ static int cn_newton(cn_series *se, const cn_spec *o, const double *theta0, doub
             if (se->gram) {
                 double zero[CN_MAX_P];
                 for (int p = 0; p < CN_MAX_P; ++p) zero[p] = 0.0;
-                se->n_eval++;
                 const double q2 = (size * size) * sw;
                 const double cd = -(size * cs);
                 const double sse = fma(-2.0, cd, se->s0) + q2;
-                f1 = cn_assemble_q(se, x, sse, zero, &fn, tg) ? -1e100 : -fn;
+                /* CN_NEWTON_QGUARD: the three terms cancel to less than 2^-20 of their sum (a step that would cut the SSE a
+                 * million-fold, or one whose SSE rounds to <= 0: a history the model interpolates, sigma -> 0, where
+                 * -SSE / (2 sigma^2) turns the form's rounding into lp = +1e189 for a point whose lp is -1e188) -- the
+                 * quadratic form cannot tell that trial's SSE; it is evaluated in residual form, as Stan would. */
+                if (sse < CN_NEWTON_QGUARD * ((se->s0 + fabs(2.0 * cd)) + q2)) {
+                    f1 = cn_resid_q(se, x, &fn, tg) ? -1e100 : -fn;
+                } else {
+                    se->n_eval++;
+                    f1 = cn_assemble_q(se, x, sse, zero, &fn, tg) ? -1e100 : -fn;
+                }
             } else {
                 f1 = CN_NEWTON_EVAL(x, &fn, tg) ? -1e100 : -fn;
             }

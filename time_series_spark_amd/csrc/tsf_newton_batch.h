@@ -326,8 +326,16 @@ __global__ __launch_bounds__(64, (KP <= 16 ? TSF_NEWTON_QUAD_WPS : 1)) void newt
                     const double q2l = (size * size) * sw;
                     const double cdl = -(size * cs);
                     const double ssel = __builtin_fma(-2.0, cdl, s0) + q2l;
-                    const double zero[PPL] = {0.0};
-                    const bool bad = assemble_q<PPL>(sv, lk, x, ssel, zero, fx, gx);
+                    bool bad;
+                    if (ssel < TSF_NEWTON_QGUARD * ((s0 + __builtin_fabs(2.0 * cdl)) + q2l)) {
+                        // the three terms cancel (oracle cn_newton, CN_NEWTON_QGUARD): this trial in residual form
+                        double sse_e, ztr_e[PPL];
+                        wl.th[W + lane] = 0.0;
+                        bad = resid_eval_q<KP, PPL>(sv, wl, lk, rb, x, fx, gx, sse_e, ztr_e);
+                    } else {
+                        const double zero[PPL] = {0.0};
+                        bad = assemble_q<PPL>(sv, lk, x, ssel, zero, fx, gx);
+                    }
                     f1 = bad ? -1e100 : -fx;
                 }
                 NBT_LAP(4);

@@ -14,6 +14,7 @@
 
 namespace tsf {
 
+#define TSF_NEWTON_QGUARD 0x1p-20    // halving trial in residual form when the quadratic form's SSE cancels (oracle cn_newton)
 #ifndef TSF_NEWTON_QUAD_WPS
 #define TSF_NEWTON_QUAD_WPS 3        // waves per SIMD the compiler budgets registers for (KP <= 16: 162 VGPRs, no scratch)
 #endif
@@ -115,8 +116,15 @@ __device__ __forceinline__ void newton_one_quad(const QuadArgs &qa, NewtonQuadLd
             const double q2l = (size * size) * sw;
             const double cdl = -(size * cs);
             const double ssel = __builtin_fma(-2.0, cdl, s0) + q2l;
-            const double zero[PPL] = {0.0};
-            bad = assemble_q<PPL>(sv, lk, x, ssel, zero, fx, gx);
+            if (ssel < TSF_NEWTON_QGUARD * ((s0 + __builtin_fabs(2.0 * cdl)) + q2l)) {
+                // the three terms cancel (oracle cn_newton, CN_NEWTON_QGUARD): this trial in residual form
+                double sse_e, ztr_e[PPL];
+                wl.th[W + lane] = 0.0;
+                bad = resid_eval_q<KP, PPL>(sv, wl, lk, rb, x, fx, gx, sse_e, ztr_e);
+            } else {
+                const double zero[PPL] = {0.0};
+                bad = assemble_q<PPL>(sv, lk, x, ssel, zero, fx, gx);
+            }
             QT_LAP(5);
         }
         bool finish_iter = false, moved = false;
