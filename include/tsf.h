@@ -384,6 +384,54 @@ int tsf_cross_validate(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t T,
                        const double *extra, const tsf_cv_args *args, const int64_t *series_key, int32_t n_samples,
                        double interval_width, uint64_t seed, tsf_cv_out *out);
 
+/* ---- prior-scale tuning by cross-validation ------------------------------------------------------
+ * The documented Prophet recipe for choosing hyperparameters -- cross_validation for every combination of a grid of
+ * prior scales, performance_metrics(..., rolling_window=1), keep the argmin -- for every series of a panel at once.
+ * fbprophet 0.5 has no tuner of its own; parity with the real package is not pinned.
+ *
+ * Candidates: cand[0 .. C) are tsf_specs structurally identical to base; only changepoint_prior_scale,
+ *   seas_prior_scale[0 .. n_seas) and extra_prior_scale[0 .. n_extra) may differ (every other field -- growth,
+ *   changepoints, columns, modes, optimiser options, converge -- must be equal; the call rejects anything else before
+ *   any launch).  So every candidate has one theta layout, one set of grids, one predict spec: the predict, interval
+ *   and cross-validation kernels read no prior scale.  1 <= C <= TSF_TUNE_MAX_CAND; every prior scale of base and of
+ *   the candidates finite and > 0.
+ * Score: score[n][c] = the cross-validation metric of series n under candidate c over all its holdout rows -- the single
+ *   metric row tsf_cross_validate returns with rolling_window = 1 (w = n rows), bit for bit.  metric: TSF_TUNE_MSE ..
+ *   TSF_TUNE_MAPE.  Cutoffs from cv->horizon_ns / period_ns / initial_ns exactly as there; cv->rolling_window is
+ *   ignored; no intervals.  The folds' optimiser (including algorithm = TSF_ALGO_AUTO's rule and Newton retry per fold)
+ *   is tsf_cross_validate's, with the candidate's spec.
+ * cand_status[n][c]: TSF_CV_* as tsf_cross_validate's series_status under candidate c: the plan's status (then a NaN
+ *   score), TSF_CV_FIT_FAILED (a fold's fit failed: NaN score), or TSF_CV_OK.
+ * Choice: best[n] = the lowest c among the candidates with a finite score that attain the minimum (np.nanargmin's
+ *   first minimum).  series_status[n]: the plan's status where it is not TSF_CV_OK (best -1); TSF_TUNE_NO_SCORE where
+ *   no candidate has a finite score (e.g. mape with min |y| < 1e-8, or every candidate's fold fit failed; best -1);
+ *   else TSF_CV_OK.
+ * Refit (refit = 1): each series fitted on its full history with cand[best[n]], or with base where best[n] = -1; out->fit
+ *   as tsf_fit_aligned (aligned input: grid [1]) or tsf_fit_ragged (ragged: grid [N]) would return it for that series.
+ *   algorithm = TSF_ALGO_AUTO applies fbprophet's rule PER SERIES as cross-validation applies it per fold: Newton below
+ *   TSF_NEWTON_BELOW_T rows, L-BFGS otherwise, Newton once more after TSF_ST_LSFAIL / TSF_ST_INIT_NONFINITE /
+ *   TSF_ST_EVAL_LIMIT (models of at most TSF_MAX_P parameters).  refit = 0: out->fit is not touched.
+ * Input as tsf_cross_validate (host pointers; T > 0 aligned, T = 0 with offsets [N+1] ragged).  Outputs (host):
+ *   score / cand_status [N][C], best / series_status [N], fit (refit = 1) [N].  Pending cost hints are discarded.
+ * Work shared by the candidates: the panel crosses to the device once, the plan, the holdout panel, the fold panel of
+ * each optimiser group (cv_expand_kernel) and its calendar classes are made once; per candidate one fit launch per
+ * optimiser group (plus its own Newton retry group), one predict over every fold and one metrics pass.
+ * Reference interface replaced: none. */
+#define TSF_TUNE_MAX_CAND 256
+enum { TSF_TUNE_MSE = 0, TSF_TUNE_RMSE = 1, TSF_TUNE_MAE = 2, TSF_TUNE_MAPE = 3 };
+enum { TSF_TUNE_NO_SCORE = -24 };     /* series_status: no candidate has a finite score */
+typedef struct {
+    double *score;              /* [N][C] */
+    int32_t *cand_status;       /* [N][C] */
+    int32_t *best;              /* [N] */
+    int32_t *series_status;     /* [N] */
+    tsf_fit_out fit;            /* refit: [N], grid [1] aligned / [N] ragged */
+} tsf_tune_out;
+int tsf_tune(tsf_ctx *ctx, const tsf_spec *base, const tsf_spec *cand, int32_t C, int64_t N, int32_t T,
+             const int64_t *offsets, const int64_t *ds, const void *y, int32_t y_dtype, const double *floor,
+             const double *cap, const double *extra, const tsf_cv_args *cv, int32_t metric, int32_t refit,
+             tsf_tune_out *out);
+
 /* ---- scheduling hints ---------------------------------------------------------------------
  * A launch ends with its longest fits (cfg2: 1 582 evaluations against a mean of 454), and nothing
  * cheap about a series predicts how long its fit takes -- except an earlier fit of the same

@@ -95,6 +95,10 @@ int tsf_last_fit_route(tsf_ctx *ctx, int32_t *sparse_columns);
  * launches: one per calendar class where folds share timestamp vectors, else one per fold), *n_launches = fit
  * launches (Newton group, L-BFGS group, Newton retry). */
 int tsf_last_cv_grids(const tsf_ctx *ctx, int64_t *n_grids, int32_t *n_launches);
+/* The last tsf_tune call of this context: *expand_launches = fold panels cut by cv_expand_kernel (one per optimiser
+ * group, shared by every candidate, plus each candidate's Newton retry group; the refit's full-history views are not
+ * counted), *fit_launches = fit launches (folds of every candidate, and the refit groups). */
+int tsf_last_tune_counts(const tsf_ctx *ctx, int32_t *expand_launches, int32_t *fit_launches);
 
 #ifdef __cplusplus
 }

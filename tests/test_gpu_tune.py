@@ -1,0 +1,315 @@
+"""GPU tests of prior-scale tuning (run with `-m gpu` on an MI355X): tsf_tune against the library's own cross_validate
+(rolling_window=1) per candidate and fit_aligned / fit_ragged per refit group, bit for bit; the choice against the
+numpy rule (tests/tune_rule.py) -- on a cfg2-like aligned panel, the reference's model on its ragged fixture with
+fbprophet's optimiser rule, edge series in one panel, a holidays axis, MAP fits, a split over two contexts, a plain-C
+caller and the validator job."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import helpers
+from tests import tune_rule
+
+pytestmark = pytest.mark.gpu
+DAY = 86400 * 10 ** 9
+SEAS = [{'name': 'yearly', 'period': 365.25, 'fourier_order': 10}, {'name': 'weekly', 'period': 7, 'fourier_order': 3}]
+FIT_KEYS = ('theta', 'y_scale', 'fval', 'status', 'n_iter', 'n_eval')
+
+
+@pytest.fixture(scope='module')
+def env(built):
+    from time_series_spark_amd import _lib, forecaster as fc
+    if _lib.load().tsf_device_count() < 1:
+        pytest.fail('no GPU visible: GPU tests cannot run (product has no CPU fallback)')
+    return fc, _lib
+
+
+def _same_fit(got, want, rows, grid_rows=None):
+    """rows `rows` of FitResult got are FitResult want, bit for bit (grid: got.grid[grid_rows] against want.grid)."""
+    for k in FIT_KEYS:
+        g, w = getattr(got, k)[rows], getattr(want, k)
+        assert (helpers.n_bit_diff(g, w) == 0) if k in ('theta', 'y_scale', 'fval') else np.array_equal(g, w), k
+    gr = got.grid if grid_rows is None else got.grid[grid_rows]
+    assert gr.tobytes() == want.grid.tobytes()
+
+
+def _assert_scores_are_cv(fc, r, cvs, metrics):
+    """score[:, c] and cand_status[:, c] are cross_validate(candidates[c], rolling_window=1)'s single metric row and
+    series status (NaN where a series has no metric row)."""
+    for c, cv in enumerate(cvs):
+        assert np.array_equal(r.cand_status[:, c], cv.status), c
+        mo = cv.metric_offsets
+        assert (np.diff(mo) <= 1).all()
+        for m, rr in metrics.items():
+            want = np.full(len(cv.status), np.nan)
+            has = np.diff(mo) == 1
+            want[has] = getattr(cv, m)[mo[:-1][has]]
+            assert helpers.n_bit_diff(rr.score[:, c], want) == 0, (c, m)
+
+
+def _refit_by_hand(fc, _lib, r, ds, y, offsets=None, floor=None, cap=None, extra=None):
+    """The refit done by hand, one series at a time with fit_ragged (ragged) -- fbprophet's rule for algorithm AUTO:
+    Newton below 100 rows, L-BFGS and a Newton retry otherwise."""
+    N = len(r.best)
+    for n in range(N):
+        sp = r.spec_of(n)
+        a, b = int(offsets[n]), int(offsets[n + 1])
+        kw = dict(floor=None if floor is None else floor[n:n + 1], cap=None if cap is None else cap[n:n + 1],
+                  extra=None if extra is None else extra[:, a:b])
+        off = np.array([0, b - a], np.int64)
+        algo = sp.lbfgs.get('algorithm', _lib.ALGO_LBFGS)
+        if algo == _lib.ALGO_AUTO:
+            d = {k: v for k, v in sp.to_dict().items() if k != 'lbfgs'}
+            opts = {k: v for k, v in sp.lbfgs.items() if k != 'algorithm'}
+            nw = fc.ModelSpec(algorithm=_lib.ALGO_NEWTON, **d, **opts)
+            if b - a < 100:
+                f = fc.fit_ragged(nw, off, ds[a:b], y[a:b], **kw)
+            else:
+                f = fc.fit_ragged(fc.ModelSpec(algorithm=_lib.ALGO_LBFGS, **d, **opts), off, ds[a:b], y[a:b], **kw)
+                if f.status[0] in (_lib.ST_LSFAIL, _lib.ST_INIT_NONFINITE, _lib.ST_EVAL_LIMIT):
+                    f = fc.fit_ragged(nw, off, ds[a:b], y[a:b], **kw)
+        else:
+            f = fc.fit_ragged(sp, off, ds[a:b], y[a:b], **kw)
+        _same_fit(r.fit, f, slice(n, n + 1), slice(n, n + 1))
+
+
+def test_cfg2_like_aligned_grid(env):
+    """BASELINE cfg2's model and shape (linear / additive yearly + weekly, 730 daily rows, horizon 90 d: 9 cutoffs) on a
+    few hundred series, a 4 x 3 grid: every score column is cross_validate's, for all four metrics; the choice is the
+    numpy rule; each refit group is fit_aligned of its candidate on its series; the fold panel is cut once."""
+    fc, _lib = env
+    from time_series_spark_amd import synth
+    N = 256
+    ds, y = synth.make_panel(N, 730, 'linear', seed=23)
+    spec = fc.ModelSpec(growth='linear', seasonalities=SEAS)
+    grid = {'changepoint_prior_scale': [0.001, 0.01, 0.1, 0.5], 'seasonality_prior_scale': [0.1, 1.0, 10.0]}
+    r = fc.tune(spec, ds, y, 90 * DAY, grid=grid)
+    C = len(r.candidates)
+    assert C == 12 and r.score.shape == (N, C) and (r.status == 0).all()
+    assert np.array_equal(r.params['changepoint_prior_scale'], np.repeat([0.001, 0.01, 0.1, 0.5], 3))
+    exp, fits = fc.last_tune_counts()
+    choices = np.unique(r.best)
+    assert exp == 1 and fits == C + len(choices)
+    cvs = [fc.cross_validate(c, ds, y, 90 * DAY, rolling_window=1.0) for c in r.candidates]
+    rs = {'rmse': r}
+    for m in ('mse', 'mae', 'mape'):
+        rs[m] = fc.tune(spec, ds, y, 90 * DAY, grid=grid, metric=m, refit=False)
+        assert rs[m].fit is None and np.array_equal(rs[m].cand_status, r.cand_status)
+    _assert_scores_are_cv(fc, r, cvs, rs)
+    plan = fc.cv_plan(ds, 90 * DAY, N=N)['status']
+    for m, rr in rs.items():
+        best, st = tune_rule.choose(rr.score, plan)
+        assert np.array_equal(rr.best, best) and np.array_equal(rr.status, st), m
+    assert len(choices) >= 2                    # the series do not all choose alike
+    assert len(r.fit.grid) == 1
+    for c in choices:
+        sel = np.flatnonzero(r.best == c)
+        f = fc.fit_aligned(r.candidates[c], ds, y[sel])
+        _same_fit(r.fit, f, sel)
+    fr = r.frame()
+    assert list(fr.columns) == ['series', 'candidate', 'status'] + list(fc.TUNE_AXES) + ['metric', 'score']
+    assert np.array_equal(fr['changepoint_prior_scale'].to_numpy(), r.params['changepoint_prior_scale'][r.best])
+    assert helpers.n_bit_diff(fr['score'].to_numpy(), r.score[np.arange(N), r.best]) == 0
+
+
+def test_reference_model_ragged_auto(env):
+    """The reference's model (logistic growth, multiplicative seasonality) on its irregular ragged fixture with algorithm
+    AUTO: folds on both sides of 100 rows (Newton and L-BFGS groups in one call); the refit is fbprophet's rule per
+    series done by hand with fit_ragged."""
+    fc, _lib = env
+    g = np.load(helpers.GOLDEN + '/fixture_751.npz')
+    off, ds, y = g['offsets'], g['raw_ds_ns'], g['raw_y'].astype(np.float64)
+    seas = fc.ModelSpec.auto_seasonalities(ds[off[0]:off[1]], seasonality_mode='multiplicative')
+    spec = fc.ModelSpec(growth='logistic', seasonality_mode='multiplicative', seasonalities=seas,
+                        algorithm=_lib.ALGO_AUTO)
+    cap = np.array([y[off[n]:off[n + 1]].max() * 1.1 for n in range(2)])
+    floor = np.zeros(2)
+    kw = dict(offsets=off, floor=floor, cap=cap, period=60 * DAY, initial=60 * DAY)
+    plan = fc.cv_plan(ds, 40 * DAY, 60 * DAY, 60 * DAY, 1.0, offsets=off)
+    assert (plan['hist_rows'] < 100).any() and (plan['hist_rows'] >= 100).any()
+    grid = {'changepoint_prior_scale': [0.01, 0.5], 'seasonality_prior_scale': [0.1, 10.0]}
+    r = fc.tune(spec, ds, y, 40 * DAY, grid=grid, **kw)
+    assert (r.status == 0).all() and (r.best >= 0).all()
+    cvs = [fc.cross_validate(c, ds, y, 40 * DAY, rolling_window=1.0, **kw) for c in r.candidates]
+    _assert_scores_are_cv(fc, r, cvs, {'rmse': r})
+    best, st = tune_rule.choose(r.score, plan['status'])
+    assert np.array_equal(r.best, best) and np.array_equal(r.status, st)
+    assert len(r.fit.grid) == 2
+    _refit_by_hand(fc, _lib, r, ds, y, off, floor, cap)
+
+
+def test_edge_series_in_one_panel(env):
+    """Among OK series: one with less data than the horizon (plan status for every candidate, base refit), a constant one
+    (every candidate ties: candidate 0), and one with zeros in its holdout rows under mape (no score: TSF_TUNE_NO_SCORE,
+    base refit).  C = 1 is cross_validate plus fit."""
+    fc, _lib = env
+    from time_series_spark_amd import synth
+    ds0, y0 = synth.make_panel(6, 400, 'linear', seed=31)
+    parts = [(ds0, y0[0]), (ds0, y0[1]), (ds0[:20], y0[2][:20]), (ds0, np.full(400, 5.0)), (ds0, y0[4].copy()),
+             (ds0[50:], y0[5][50:])]
+    parts[4][1][-10:] = 0.0
+    off = np.concatenate([[0], np.cumsum([len(d) for d, _ in parts])]).astype(np.int64)
+    ds = np.concatenate([d for d, _ in parts]).astype(np.int64)
+    y = np.concatenate([v for _, v in parts])
+    spec = fc.ModelSpec(growth='linear', seasonalities=SEAS[1:])
+    grid = {'changepoint_prior_scale': [0.01, 0.5, 0.05]}
+    r = fc.tune(spec, ds, y, 30 * DAY, offsets=off, grid=grid, metric='mape')
+    assert r.status[2] == _lib.CV_LESS_THAN_HORIZON and r.best[2] == -1
+    assert (r.cand_status[2] == _lib.CV_LESS_THAN_HORIZON).all() and np.isnan(r.score[2]).all()
+    assert r.status[4] == _lib.TUNE_NO_SCORE and r.best[4] == -1 and np.isnan(r.score[4]).all()
+    assert (r.cand_status[4] == _lib.CV_OK).all()
+    assert r.status[3] == 0 and r.best[3] == 0 and (r.score[3] == r.score[3, 0]).all()
+    assert (r.status[[0, 1, 5]] == 0).all()
+    cvs = [fc.cross_validate(c, ds, y, 30 * DAY, offsets=off, rolling_window=1.0) for c in r.candidates]
+    _assert_scores_are_cv(fc, r, cvs, {'mape': r})
+    plan = fc.cv_plan(ds, 30 * DAY, offsets=off)['status']
+    assert plan[2] == _lib.CV_LESS_THAN_HORIZON
+    best, st = tune_rule.choose(r.score, plan)
+    assert np.array_equal(r.best, best) and np.array_equal(r.status, st)
+    assert r.spec_of(2) is spec and r.spec_of(4) is spec
+    _refit_by_hand(fc, _lib, r, ds, y, off)
+    # one candidate: cross_validate + fit_ragged
+    r1 = fc.tune(spec, ds, y, 30 * DAY, offsets=off, candidates=[spec])
+    cv = fc.cross_validate(spec, ds, y, 30 * DAY, offsets=off, rolling_window=1.0)
+    _assert_scores_are_cv(fc, r1, [cv], {'rmse': r1})
+    f = fc.fit_ragged(spec, off, ds, y)
+    _same_fit(r1.fit, f, slice(None))
+    assert np.array_equal(r1.best, np.where(cv.status == 0, 0, -1))
+
+
+def test_holidays_axis(env):
+    """A holidays axis replaces the holiday columns' scales only (a regressor keeps its own); the fold panel and the refit
+    carry the explicit columns."""
+    fc, _lib = env
+    from time_series_spark_amd import features, synth
+    ds = synth.daily_grid(500)
+    hol = features.normalize_holidays([{'holiday': 'h%d' % i, 'ds': [int(ds[40 + 61 * i + 7 * k]) for k in range(3)],
+                                        'lower_window': 0, 'upper_window': 1} for i in range(3)])
+    names, scales, days = features.holiday_columns(hol)
+    hx = features.holiday_matrix(ds, days)
+    reg = np.sin(np.arange(500) / 17.0)[None, :]
+    ex = np.concatenate([hx, reg])
+    _, y = synth.make_panel(8, 500, 'linear', seed=5, holidays=hx)
+    extra = [{'name': n, 'prior_scale': s} for n, s in zip(names, scales)] + [{'name': 'reg', 'prior_scale': 3.0}]
+    spec = fc.ModelSpec(growth='linear', seasonalities=SEAS[1:], extra=extra, holidays=hol)
+    r = fc.tune(spec, ds, y, 60 * DAY, extra=ex, period=60 * DAY,
+                grid={'holidays_prior_scale': [0.05, 5.0], 'changepoint_prior_scale': [0.01, 0.5]})
+    assert len(r.candidates) == 4 and (r.status == 0).all()
+    for c in r.candidates:
+        cs = c.to_c()
+        assert [cs.extra_prior_scale[i] for i in range(len(names))] == [c.holidays_prior_scale] * len(names)
+        assert cs.extra_prior_scale[len(names)] == 3.0
+    cvs = [fc.cross_validate(c, ds, y, 60 * DAY, extra=ex, period=60 * DAY, rolling_window=1.0) for c in r.candidates]
+    _assert_scores_are_cv(fc, r, cvs, {'rmse': r})
+    for c in np.unique(r.best):
+        sel = np.flatnonzero(r.best == c)
+        _same_fit(r.fit, fc.fit_aligned(r.candidates[c], ds, y[sel], extra=ex), sel)
+
+
+def test_map_direct_solver(env):
+    """converge = MAP on a linear / additive model (the direct solver) through tuning."""
+    fc, _lib = env
+    from time_series_spark_amd import synth
+    ds, y = synth.make_panel(24, 400, 'linear', seed=41)
+    spec = fc.ModelSpec(growth='linear', seasonalities=SEAS[1:], converge=_lib.CONVERGE_MAP)
+    r = fc.tune(spec, ds, y, 30 * DAY, grid={'changepoint_prior_scale': [0.005, 0.5]}, metric='mae')
+    assert set(np.unique(r.fit.status)) <= {_lib.ST_MAP_KKT, _lib.ST_MAP_FTOL, _lib.ST_MAP_LS}
+    cvs = [fc.cross_validate(c, ds, y, 30 * DAY, rolling_window=1.0) for c in r.candidates]
+    _assert_scores_are_cv(fc, r, cvs, {'mae': r})
+    for c in np.unique(r.best):
+        sel = np.flatnonzero(r.best == c)
+        _same_fit(r.fit, fc.fit_aligned(r.candidates[c], ds, y[sel]), sel)
+
+
+def test_split_over_two_contexts(env):
+    """devices=[0, 0]: the panel split by series over two contexts gives the single call's result."""
+    fc, _lib = env
+    from time_series_spark_amd import synth
+    N = 2 * fc.MIN_SERIES_PER_DEVICE
+    ds, y = synth.make_panel(N, 160, 'linear', seed=8)
+    spec = fc.ModelSpec(growth='linear', seasonalities=SEAS[1:])
+    kw = dict(grid={'changepoint_prior_scale': [0.01, 0.5]}, period=14 * DAY)
+    one = fc.tune(spec, ds, y, 14 * DAY, **kw)
+    two = fc.tune(spec, ds, y, 14 * DAY, devices=[0, 0], **kw)
+    assert helpers.n_bit_diff(one.score, two.score) == 0
+    for k in ('cand_status', 'best', 'status'):
+        assert np.array_equal(getattr(one, k), getattr(two, k)), k
+    _same_fit(two.fit, one.fit, slice(None))
+
+
+def test_bad_arguments(env):
+    """The call rejects candidates that differ in more than their prior scales, and bad counts, before any launch."""
+    fc, _lib = env
+    from time_series_spark_amd import synth
+    ds, y = synth.make_panel(2, 200, 'linear', seed=1)
+    spec = fc.ModelSpec(growth='linear', seasonalities=SEAS[1:])
+    other = fc.ModelSpec(growth='linear', seasonalities=SEAS[1:], n_changepoints=10)
+    with pytest.raises(_lib.TsfError):
+        fc.tune(spec, ds, y, 30 * DAY, candidates=[spec, other])
+    with pytest.raises(_lib.TsfError):
+        fc.tune(spec, ds, y, 30 * DAY, candidates=[fc.ModelSpec(growth='linear', seasonalities=SEAS[1:],
+                                                                changepoint_prior_scale=0.0)])
+    with pytest.raises(ValueError):
+        fc.tune(spec, ds, y, 30 * DAY, candidates=[spec] * (_lib.TUNE_MAX_CAND + 1))
+
+
+def test_abi_tune_plain_c(env, tmp_path):
+    """tests/c/abi_tune.c drives tsf_tune from plain C99 and writes what the binding returns."""
+    fc, _lib = env
+    from time_series_spark_amd import synth
+    root = helpers.ROOT
+    N, T = 4, 400
+    ds, y = synth.make_panel(N, T, 'linear', seed=2)
+    ds.astype(np.int64).tofile(str(tmp_path / 'ds.i64'))
+    np.ascontiguousarray(y, np.float64).tofile(str(tmp_path / 'y.f64'))
+    exe = str(tmp_path / 'abi_tune')
+    lib_dir = os.path.dirname(_lib.LIB_PATH)
+    subprocess.check_call(['gcc', '-std=c99', '-pedantic', '-Wall', '-Wextra', '-Werror', '-I', os.path.join(root, 'include'),
+                           os.path.join(root, 'tests', 'c', 'abi_tune.c'), '-o', exe, '-L', lib_dir, '-ltsf_amd',
+                           '-Wl,-rpath,' + lib_dir])
+    subprocess.check_call([exe, str(N), str(T), str(tmp_path / 'ds.i64'), str(tmp_path / 'y.f64'), str(tmp_path / 'out.f64')])
+    got = np.fromfile(str(tmp_path / 'out.f64'))
+    spec = fc.ModelSpec(growth='linear', seasonalities=SEAS[1:])
+    r = fc.tune(spec, ds, y, 30 * DAY, grid={'changepoint_prior_scale': [0.01, 0.5]})
+    want = np.concatenate([r.score.ravel(), r.best.astype(np.float64), r.fit.theta.ravel()])
+    assert helpers.n_bit_diff(got, want) == 0
+
+
+def test_validator_tune_on_reference_fixture(env, tmp_path):
+    """The validator job with a `tune:` section writes io.tuning: the choice and score fc.tune gives for the same series
+    and settings."""
+    fc, _lib = env
+    import pandas as pd
+    import yaml
+    from time_series_spark_amd import validator_driver
+    g = np.load(helpers.GOLDEN + '/fixture_751.npz')
+    d = tmp_path / 'in' / 'series_id=751'
+    d.mkdir(parents=True)
+    stamps = pd.DatetimeIndex(g['raw_ds_ns'].astype('datetime64[ns]')).strftime('%Y-%m-%d %H:%M:%S').values
+    with open(str(d / 'part-0.csv'), 'w') as fh:
+        fh.write(''.join('%d,%s,%d\n' % (k, s, v) for k, s, v in zip(g['raw_dim_id'], stamps, g['raw_y'])))
+    cfg = {'model': {'floor': 0, 'cap_multiplier': 1.1},
+           'io': {'input': str(tmp_path / 'in'), 'metrics': str(tmp_path / 'm'), 'tuning': str(tmp_path / 't')},
+           'cv': {'horizon': '40 days', 'period': '40 days', 'initial': '300 days'},
+           'tune': {'changepoint_prior_scale': [0.01, 0.5], 'seasonality_prior_scale': [0.1, 10.0], 'metric': 'mae'}}
+    with open(str(tmp_path / 'cfg.yaml'), 'w') as fh:
+        yaml.safe_dump(cfg, fh)
+    assert validator_driver.main(['x', str(tmp_path / 'cfg.yaml')]) == 0
+    t = pd.read_parquet(str(tmp_path / 't'))
+    off, ds, y = g['offsets'], g['raw_ds_ns'], g['raw_y'].astype(np.float64)
+    seas = fc.ModelSpec.auto_seasonalities(ds[off[0]:off[1]], seasonality_mode='multiplicative')
+    spec = fc.ModelSpec(growth='logistic', seasonality_mode='multiplicative', seasonalities=seas, algorithm=_lib.ALGO_AUTO)
+    cap = np.array([y[off[n]:off[n + 1]].max() * 1.1 for n in range(2)])
+    r = fc.tune(spec, ds, y, 40 * DAY, 40 * DAY, 300 * DAY, offsets=off, floor=np.zeros(2), cap=cap,
+                grid={'changepoint_prior_scale': [0.01, 0.5], 'seasonality_prior_scale': [0.1, 10.0]}, metric='mae',
+                refit=False)
+    assert list(t.columns) == ['series_id', 'dim_id', 'changepoint_prior_scale', 'seasonality_prior_scale',
+                               'holidays_prior_scale', 'metric', 'score']
+    assert (t['series_id'] == 751).all() and np.array_equal(t['dim_id'].to_numpy(), g['dim_ids'])
+    assert (r.best >= 0).all() and (t['metric'] == 'mae').all()
+    assert np.array_equal(t['changepoint_prior_scale'].to_numpy(), r.params['changepoint_prior_scale'][r.best])
+    assert np.array_equal(t['seasonality_prior_scale'].to_numpy(), r.params['seasonality_prior_scale'][r.best])
+    assert t['holidays_prior_scale'].isna().all()
+    assert helpers.n_bit_diff(t['score'].to_numpy(), r.score[np.arange(2), r.best]) == 0

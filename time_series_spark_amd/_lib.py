@@ -94,13 +94,19 @@ class TsfCvOut(ctypes.Structure):
                 ('coverage', ctypes.c_void_p), ('series_status', ctypes.c_void_p)]
 
 
+class TsfTuneOut(ctypes.Structure):
+    """tsf_tune_out (include/tsf.h)."""
+    _fields_ = [('score', ctypes.c_void_p), ('cand_status', ctypes.c_void_p), ('best', ctypes.c_void_p),
+                ('series_status', ctypes.c_void_p), ('fit', TsfFitOut)]
+
+
 # every symbol include/tsf.h declares; tests check the library exports all of them
 EXPORTS = ['tsf_create', 'tsf_destroy', 'tsf_last_error', 'tsf_device_count', 'tsf_spec_default',
            'tsf_spec_size', 'tsf_grid_info_size', 'tsf_spec_K', 'tsf_theta_stride',
            'tsf_fit_aligned', 'tsf_fit_aligned_dev', 'tsf_fit_ragged', 'tsf_fit_ragged_dev',
            'tsf_predict', 'tsf_predict_dev', 'tsf_predict_intervals', 'tsf_predict_intervals_dev', 'tsf_predict_components', 'tsf_predict_components_dev', 'tsf_eval', 'tsf_eval_quadratic', 'tsf_design', 'tsf_selftest_math',
            'tsf_set_option', 'tsf_get_option', 'tsf_set_cost_hints', 'tsf_set_profiling', 'tsf_profile_read', 'tsf_last_fit_kernel_ms', 'tsf_last_fit_route',
-           'tsf_cv_plan', 'tsf_cross_validate', 'tsf_last_cv_grids',
+           'tsf_cv_plan', 'tsf_cross_validate', 'tsf_last_cv_grids', 'tsf_tune', 'tsf_last_tune_counts',
            'tsf_pack_rows', 'tsf_pack_rows_typed', 'tsf_pack_fetch', 'tsf_pack_flags', 'tsf_pack_free', 'tsf_model_blobs',
            'tsf_csv_read', 'tsf_csv_fetch', 'tsf_csv_columns', 'tsf_csv_malformed', 'tsf_csv_free', 'tsf_csv_write_forecasts', 'tsf_csv_write_forecasts_i32',
            'tsf_csv_discover', 'tsf_csv_discover_load', 'tsf_csv_root_open', 'tsf_csv_root_load', 'tsf_csv_root_free', 'tsf_csv_read_loaded', 'tsf_csv_dir_paths', 'tsf_csv_dir_series_id', 'tsf_csv_dir_error_path', 'tsf_csv_dir_free']
@@ -108,6 +114,11 @@ EXPORTS = ['tsf_create', 'tsf_destroy', 'tsf_last_error', 'tsf_device_count', 't
 CSV_E_OPEN, CSV_E_PARSE, CSV_E_CODEC = -10, -11, -12          # TSF_CSV_E_* (include/tsf.h)
 # TSF_CV_* (include/tsf.h): per-series outcome of a cross-validation plan / call
 CV_OK, CV_LESS_THAN_HORIZON, CV_NO_CUTOFF, CV_TOO_FEW, CV_FIT_FAILED = 0, -20, -21, -22, -23
+# TSF_TUNE_* (include/tsf.h): tsf_tune's metrics, its series status where no candidate scored, its candidate limit
+TUNE_MSE, TUNE_RMSE, TUNE_MAE, TUNE_MAPE = 0, 1, 2, 3
+TUNE_METRICS = {'mse': TUNE_MSE, 'rmse': TUNE_RMSE, 'mae': TUNE_MAE, 'mape': TUNE_MAPE}
+TUNE_NO_SCORE = -24
+TUNE_MAX_CAND = 256
 
 # TSF_OPT_* (include/tsf.h): route switches of one context
 OPTIONS = ['harm', 'lattice', 'sparse_extra', 'fit_grouped', 'gram_share', 'grid_order', 'grid_share', 'ragged_split',
@@ -175,6 +186,9 @@ def load():
     L.tsf_cross_validate.argtypes = [vp, psp, i64, i32, vp, vp, vp, i32, vp, vp, vp, ctypes.POINTER(TsfCvArgs), vp, i32,
                                      ctypes.c_double, ctypes.c_uint64, ctypes.POINTER(TsfCvOut)]
     L.tsf_last_cv_grids.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i32)]
+    L.tsf_tune.argtypes = [vp, psp, psp, i32, i64, i32, vp, vp, vp, i32, vp, vp, vp, ctypes.POINTER(TsfCvArgs), i32, i32,
+                           ctypes.POINTER(TsfTuneOut)]
+    L.tsf_last_tune_counts.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.tsf_pack_rows.argtypes = [i64, vp, vp, vp, vp, i32, ctypes.POINTER(vp), ctypes.POINTER(i64),
                                 ctypes.POINTER(i64), ctypes.POINTER(i32)]
     L.tsf_pack_fetch.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]

@@ -26,6 +26,7 @@
 #include "tsf_mfma_tabs.h"
 #include "tsf_launch.h"
 #include "tsf_cv_kernels.h"
+#include "tsf_tune_kernels.h"
 #include "tsf_cv_plan.h"
 
 using namespace tsf;
@@ -61,6 +62,8 @@ struct tsf_ctx {
     int64_t last_n_grids;   // grid tables the last run_fit call built
     int64_t cv_grids;       // tsf_last_cv_grids: grid tables / fit launches of the last tsf_cross_validate call
     int32_t cv_launches;
+    int32_t tune_expand;    // tsf_last_tune_counts: fold panels cut / fit launches of the last tsf_tune call
+    int32_t tune_fits;
 };
 
 #define HIP_TRY(ctx, expr)                                                                   \
@@ -102,7 +105,7 @@ extern "C" int tsf_create(int device_id, tsf_ctx **out)
     c->order_ev[0] = c->order_ev[1] = nullptr; c->order_busy[0] = c->order_busy[1] = 0;
     c->profiling = 0; c->ev_created = 0; c->ev_count = 0;
     c->last_sp_flag = nullptr;
-    c->last_n_grids = 0; c->cv_grids = 0; c->cv_launches = 0;
+    c->last_n_grids = 0; c->cv_grids = 0; c->cv_launches = 0; c->tune_expand = 0; c->tune_fits = 0;
     for (int i = 0; i < TSF_OPT_COUNT; ++i) c->opt[i] = -1;
     if (hipMalloc((void **)&c->d_spec, sizeof(DevSpec)) != hipSuccess) { delete c; return -2; }
     {
@@ -1955,13 +1958,323 @@ extern "C" int tsf_last_fit_kernel_ms(tsf_ctx *ctx, float *ms_out)
 // (aligned input: fold c of every series is one calendar, known from the construction; ragged input: the prefixes of
 // the caller's series through calendar_classes, reading the caller's rows in place).  The fold results are scattered to
 // plan order, the holdout rows predicted by the predict (and interval) kernels in one call over every fold, and
-// cv_metrics_kernel reduces them per series.
+// cv_metrics_kernel reduces them per series.  tsf_tune runs the same pieces: the plan, the panel, the holdout rows and
+// the fold panel of each optimiser group once, the fits, predict and metrics once per candidate.
 
 extern "C" int tsf_last_cv_grids(const tsf_ctx *ctx, int64_t *n_grids, int32_t *n_launches)
 {
     if (!ctx || !n_grids || !n_launches) return -1;
     *n_grids = ctx->cv_grids;
     *n_launches = ctx->cv_launches;
+    return 0;
+}
+
+namespace {
+// What a cross-validation call derives once from its arguments: the plan, the fold tables, the caller's panel on the
+// device (cv_upload) and the fold fit outputs in plan order.
+struct CvCall {
+    bool aligned = false;
+    int64_t N = 0;
+    int32_t T = 0;
+    const int64_t *offsets = nullptr, *ds = nullptr;      // the caller's (host)
+    int32_t y_dtype = 0;
+    size_t ysz = 8;
+    int n_extra = 0, stride = 0;
+    bool has_floor = false, has_cap = false;
+    std::vector<std::vector<tsf_cv::Fold>> plan;
+    std::vector<int32_t> pst;
+    std::vector<int64_t> pnh, pnm, fold_off, rows_off, m_off;
+    int64_t F = 0, R = 0, M = 0;
+    std::vector<int32_t> f_series, f_c;
+    std::vector<int64_t> f_cut, f_hist, f_hold, f_row0;
+    std::vector<double> f_floor, f_cap;
+    int32_t Hmax = 1, C = 0;
+    DevBuf d_ds, d_y, d_off, d_ex, d_fl, d_cap, d_key, d_fser, d_fc, d_fhist, d_fhold;
+    CvPanel pn;
+    DevBuf d_th, d_ys, d_fv, d_st, d_it, d_ev, d_gr;
+    tsf_fit_out dfo;
+};
+
+// Views of the caller's series that cv_expand_kernel cuts: view v = rows [0, hist[v]) of series series[v].  The folds
+// of a call (on an aligned panel every cutoff is one calendar: cls = the cutoff index), or whole series (tsf_tune's
+// ragged refit).
+struct CvViews {
+    const int32_t *d_series;    // device [V]
+    const int32_t *series;      // host [V]
+    const int64_t *hist;        // host [V]
+    const int32_t *cls;         // host [V]: calendar class known from the construction, or null (classes by hashing)
+    int32_t n_cls;
+};
+
+// The panel of one fit launch: views gf[0 .. G), cut on the device, and their calendar classes.
+struct CvGroup {
+    std::vector<int32_t> gf;
+    int64_t G = 0, rows = 0, n_distinct = 0;
+    int32_t maxT = 0;
+    DevBuf d_gf, d_goff, d_gds, d_gy, d_gex, d_gfl, d_gcap, d_gof, d_grows, d_gord;
+};
+
+struct CvHoldout {              // the holdout rows of every fold as one padded future panel [F][Hmax]
+    DevBuf d_fds, d_fex, d_fkey, d_ffl, d_fcap;
+};
+
+struct CvMetrics {              // cv_metrics_kernel's tables, scratch and outputs
+    DevBuf d_foff, d_roff, d_moff, d_fcut, d_frow0, d_hs, d_ts, d_pre, d_yo, d_loo, d_hio, d_mh, d_mm, d_sst;
+    CvMetricArgs ma;
+};
+}  // namespace
+
+// the plan and the fold tables (host only)
+static void cv_plan_call(int64_t N, int32_t T, const int64_t *offsets, const int64_t *ds, const tsf_cv_args &a,
+                         const tsf_spec *spec, int32_t y_dtype, const double *floor_, const double *cap, CvCall *S)
+{
+    S->aligned = offsets == nullptr;
+    S->N = N; S->T = T; S->offsets = offsets; S->ds = ds; S->y_dtype = y_dtype; S->ysz = ysize(y_dtype);
+    S->n_extra = spec->n_extra; S->stride = tsf_theta_stride(spec);
+    S->has_floor = floor_ != nullptr; S->has_cap = cap != nullptr;
+    tsf_cv::panel_plan(N, T, offsets, ds, a, &S->plan, &S->pst, &S->pnh, &S->pnm);
+    S->fold_off.assign((size_t)N + 1, 0); S->rows_off.assign((size_t)N + 1, 0); S->m_off.assign((size_t)N + 1, 0);
+    for (int64_t n = 0; n < N; ++n) {
+        S->fold_off[(size_t)n + 1] = S->fold_off[(size_t)n] + (int64_t)S->plan[(size_t)n].size();
+        S->rows_off[(size_t)n + 1] = S->rows_off[(size_t)n] + S->pnh[(size_t)n];
+        S->m_off[(size_t)n + 1] = S->m_off[(size_t)n] + S->pnm[(size_t)n];
+    }
+    const int64_t F = S->F = S->fold_off[(size_t)N];
+    S->R = S->rows_off[(size_t)N]; S->M = S->m_off[(size_t)N];
+    S->f_series.resize((size_t)F); S->f_c.resize((size_t)F);
+    S->f_cut.resize((size_t)F); S->f_hist.resize((size_t)F); S->f_hold.resize((size_t)F); S->f_row0.resize((size_t)F);
+    S->f_floor.resize(floor_ ? (size_t)F : 0); S->f_cap.resize(cap ? (size_t)F : 0);
+    for (int64_t n = 0; n < N; ++n) {
+        int64_t r = S->rows_off[(size_t)n];
+        for (size_t c = 0; c < S->plan[(size_t)n].size(); ++c) {
+            const int64_t f = S->fold_off[(size_t)n] + (int64_t)c;
+            const tsf_cv::Fold &x = S->plan[(size_t)n][c];
+            S->f_series[(size_t)f] = (int32_t)n; S->f_c[(size_t)f] = (int32_t)c;
+            S->f_cut[(size_t)f] = x.cutoff; S->f_hist[(size_t)f] = x.hist; S->f_hold[(size_t)f] = x.hold; S->f_row0[(size_t)f] = r;
+            if (floor_) S->f_floor[(size_t)f] = floor_[n];
+            if (cap) S->f_cap[(size_t)f] = cap[n];
+            r += x.hold;
+            if (x.hold > S->Hmax) S->Hmax = (int32_t)x.hold;
+        }
+        if ((int32_t)S->plan[(size_t)n].size() > S->C) S->C = (int32_t)S->plan[(size_t)n].size();
+    }
+}
+
+// the caller's panel, once; the fold tables; the fold outputs in plan order
+static int cv_upload(tsf_ctx *ctx, const void *y, const double *floor_, const double *cap, const double *extra,
+                     const int64_t *series_key, CvCall *S)
+{
+    const int64_t N = S->N, F = S->F, T = S->T;
+    const int64_t n_ds = S->aligned ? T : S->offsets[N];
+    const int64_t n_y = S->aligned ? N * T : S->offsets[N];
+    HIP_TRY(ctx, S->d_ds.alloc(8 * (size_t)n_ds));
+    HIP_TRY(ctx, hipMemcpy(S->d_ds.p, S->ds, 8 * (size_t)n_ds, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, S->d_y.alloc(S->ysz * (size_t)n_y));
+    HIP_TRY(ctx, hipMemcpy(S->d_y.p, y, S->ysz * (size_t)n_y, hipMemcpyHostToDevice));
+    if (!S->aligned) {
+        HIP_TRY(ctx, S->d_off.alloc(8 * ((size_t)N + 1)));
+        HIP_TRY(ctx, hipMemcpy(S->d_off.p, S->offsets, 8 * ((size_t)N + 1), hipMemcpyHostToDevice));
+    }
+    if (S->n_extra > 0) {
+        HIP_TRY(ctx, S->d_ex.alloc(8 * (size_t)S->n_extra * n_ds));
+        HIP_TRY(ctx, hipMemcpy(S->d_ex.p, extra, 8 * (size_t)S->n_extra * n_ds, hipMemcpyHostToDevice));
+    }
+    if (floor_) { HIP_TRY(ctx, S->d_fl.alloc(8 * (size_t)N)); HIP_TRY(ctx, hipMemcpy(S->d_fl.p, floor_, 8 * (size_t)N, hipMemcpyHostToDevice)); }
+    if (cap) { HIP_TRY(ctx, S->d_cap.alloc(8 * (size_t)N)); HIP_TRY(ctx, hipMemcpy(S->d_cap.p, cap, 8 * (size_t)N, hipMemcpyHostToDevice)); }
+    if (series_key) { HIP_TRY(ctx, S->d_key.alloc(8 * (size_t)N)); HIP_TRY(ctx, hipMemcpy(S->d_key.p, series_key, 8 * (size_t)N, hipMemcpyHostToDevice)); }
+    if (F > 0) {                        // (tsf_tune uploads a panel without folds for its refit)
+        HIP_TRY(ctx, S->d_fser.alloc(4 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(S->d_fser.p, S->f_series.data(), 4 * (size_t)F, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, S->d_fc.alloc(4 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(S->d_fc.p, S->f_c.data(), 4 * (size_t)F, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, S->d_fhist.alloc(8 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(S->d_fhist.p, S->f_hist.data(), 8 * (size_t)F, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, S->d_fhold.alloc(8 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(S->d_fhold.p, S->f_hold.data(), 8 * (size_t)F, hipMemcpyHostToDevice));
+    }
+    CvPanel &pn = S->pn;
+    pn.ds = S->d_ds.as<int64_t>(); pn.y = S->d_y.p; pn.extra = S->n_extra > 0 ? S->d_ex.as<double>() : nullptr;
+    pn.src_off = S->aligned ? nullptr : S->d_off.as<int64_t>(); pn.T = S->aligned ? T : 0;
+    pn.src_total = S->aligned ? 0 : S->offsets[N];
+    pn.ysz = (int)S->ysz; pn.n_extra = S->n_extra;
+    const int stride = S->stride;
+    HIP_TRY(ctx, S->d_th.alloc(8 * (size_t)F * stride)); HIP_TRY(ctx, S->d_ys.alloc(8 * (size_t)F));
+    HIP_TRY(ctx, S->d_fv.alloc(8 * (size_t)F)); HIP_TRY(ctx, S->d_st.alloc(4 * (size_t)F));
+    HIP_TRY(ctx, S->d_it.alloc(4 * (size_t)F)); HIP_TRY(ctx, S->d_ev.alloc(4 * (size_t)F));
+    HIP_TRY(ctx, S->d_gr.alloc(sizeof(tsf_grid_info) * (size_t)F));
+    tsf_fit_out &dfo = S->dfo;
+    dfo.theta = S->d_th.as<double>(); dfo.y_scale = S->d_ys.as<double>(); dfo.fval = S->d_fv.as<double>();
+    dfo.status = S->d_st.as<int32_t>(); dfo.n_iter = S->d_it.as<int32_t>(); dfo.n_eval = S->d_ev.as<int32_t>();
+    dfo.grid = S->d_gr.as<tsf_grid_info>();
+    return 0;
+}
+
+static CvViews cv_fold_views(CvCall &S)
+{
+    return CvViews{S.d_fser.as<int32_t>(), S.f_series.data(), S.f_hist.data(), S.aligned ? S.f_c.data() : nullptr, S.C};
+}
+
+// the panel of one fit launch over the views gf (cv_expand_kernel) and its calendar classes (same rule as
+// fit_host_one: ragged, no explicit columns, two views or more)
+static int cv_expand(tsf_ctx *ctx, CvCall &S, const CvViews &V, const std::vector<int32_t> &gf, CvGroup *E)
+{
+    const int64_t G = E->G = (int64_t)gf.size();
+    E->gf = gf;
+    if (G == 0) return 0;
+    std::vector<int64_t> goff((size_t)G + 1, 0);
+    int32_t maxT = 0;
+    for (int64_t g = 0; g < G; ++g) {
+        const int64_t h = V.hist[(size_t)gf[(size_t)g]];
+        goff[(size_t)g + 1] = goff[(size_t)g] + h;
+        if (h > maxT) maxT = (int32_t)h;
+    }
+    const int64_t rows = E->rows = goff[(size_t)G];
+    E->maxT = maxT;
+    HIP_TRY(ctx, E->d_gf.alloc(4 * (size_t)G)); HIP_TRY(ctx, hipMemcpy(E->d_gf.p, gf.data(), 4 * (size_t)G, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, E->d_goff.alloc(8 * ((size_t)G + 1))); HIP_TRY(ctx, hipMemcpy(E->d_goff.p, goff.data(), 8 * ((size_t)G + 1), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, E->d_gds.alloc(8 * (size_t)rows)); HIP_TRY(ctx, E->d_gy.alloc(S.ysz * (size_t)rows));
+    if (S.n_extra > 0) HIP_TRY(ctx, E->d_gex.alloc(8 * (size_t)S.n_extra * rows));
+    if (S.has_floor) HIP_TRY(ctx, E->d_gfl.alloc(8 * (size_t)G));
+    if (S.has_cap) HIP_TRY(ctx, E->d_gcap.alloc(8 * (size_t)G));
+    hipLaunchKernelGGL(cv_expand_kernel, dim3((unsigned)(G < 65535 ? G : 65535)), dim3(256), 0, nullptr, S.pn, G,
+                       E->d_gf.as<int32_t>(), V.d_series, E->d_goff.as<int64_t>(), rows,
+                       S.has_floor ? S.d_fl.as<double>() : nullptr, S.has_cap ? S.d_cap.as<double>() : nullptr,
+                       E->d_gds.as<int64_t>(), E->d_gy.p, S.n_extra > 0 ? E->d_gex.as<double>() : nullptr,
+                       S.has_floor ? E->d_gfl.as<double>() : nullptr, S.has_cap ? E->d_gcap.as<double>() : nullptr);
+    HIP_TRY(ctx, hipGetLastError());
+    int64_t n_distinct = 0;
+    if (S.n_extra == 0 && G >= 2 && ctx->opt[TSF_OPT_GRID_SHARE] != 0) {
+        std::vector<int32_t> gof((size_t)G);
+        std::vector<int64_t> reps;
+        if (V.cls) {
+            std::vector<int32_t> id_of((size_t)V.n_cls, -1);
+            for (int64_t g = 0; g < G; ++g) {
+                const int32_t c = V.cls[(size_t)gf[(size_t)g]];
+                if (id_of[(size_t)c] < 0) { id_of[(size_t)c] = (int32_t)reps.size(); reps.push_back(g); }
+                gof[(size_t)g] = id_of[(size_t)c];
+            }
+        } else {
+            std::vector<int64_t> vstart((size_t)G), vlen((size_t)G);
+            for (int64_t g = 0; g < G; ++g) {
+                vstart[(size_t)g] = S.offsets[V.series[(size_t)gf[(size_t)g]]];
+                vlen[(size_t)g] = V.hist[(size_t)gf[(size_t)g]];
+            }
+            calendar_classes(S.ds, vstart.data(), vlen.data(), G, &gof, &reps);
+        }
+        n_distinct = (int64_t)reps.size();
+        if (n_distinct < G) {
+            std::vector<int64_t> grows;
+            for (int64_t r : reps) { grows.push_back(goff[(size_t)r]); grows.push_back(goff[(size_t)r + 1] - goff[(size_t)r]); }
+            std::vector<int32_t> ord;
+            calendar_start_order(gof, n_distinct, &ord);
+            HIP_TRY(ctx, E->d_gof.alloc(4 * (size_t)G)); HIP_TRY(ctx, hipMemcpy(E->d_gof.p, gof.data(), 4 * (size_t)G, hipMemcpyHostToDevice));
+            HIP_TRY(ctx, E->d_grows.alloc(8 * grows.size())); HIP_TRY(ctx, hipMemcpy(E->d_grows.p, grows.data(), 8 * grows.size(), hipMemcpyHostToDevice));
+            HIP_TRY(ctx, E->d_gord.alloc(4 * (size_t)G)); HIP_TRY(ctx, hipMemcpy(E->d_gord.p, ord.data(), 4 * (size_t)G, hipMemcpyHostToDevice));
+        } else {
+            n_distinct = 0;
+        }
+    }
+    E->n_distinct = n_distinct;
+    return 0;
+}
+
+// one fit launch over an expanded group with spec gs, its outputs scattered to dst at the views' indices
+static int cv_fit(tsf_ctx *ctx, CvCall &S, CvGroup &E, const tsf_spec &gs, const tsf_fit_out &dst, int64_t *n_grids,
+                  int32_t *n_launches)
+{
+    const int64_t G = E.G;
+    if (G == 0) return 0;
+    const int stride = S.stride;
+    DevBuf g_th, g_ys, g_fv, g_st, g_it, g_ev, g_gr;
+    HIP_TRY(ctx, g_th.alloc(8 * (size_t)G * stride)); HIP_TRY(ctx, g_ys.alloc(8 * (size_t)G)); HIP_TRY(ctx, g_fv.alloc(8 * (size_t)G));
+    HIP_TRY(ctx, g_st.alloc(4 * (size_t)G)); HIP_TRY(ctx, g_it.alloc(4 * (size_t)G)); HIP_TRY(ctx, g_ev.alloc(4 * (size_t)G));
+    HIP_TRY(ctx, g_gr.alloc(sizeof(tsf_grid_info) * (size_t)G));
+    HIP_TRY(ctx, hipMemset(g_st.p, 0, 4 * (size_t)G)); HIP_TRY(ctx, hipMemset(g_it.p, 0, 4 * (size_t)G));
+    HIP_TRY(ctx, hipMemset(g_ev.p, 0, 4 * (size_t)G)); HIP_TRY(ctx, hipMemset(g_gr.p, 0, sizeof(tsf_grid_info) * (size_t)G));
+    tsf_fit_out go;
+    go.theta = g_th.as<double>(); go.y_scale = g_ys.as<double>(); go.fval = g_fv.as<double>();
+    go.status = g_st.as<int32_t>(); go.n_iter = g_it.as<int32_t>(); go.n_eval = g_ev.as<int32_t>();
+    go.grid = g_gr.as<tsf_grid_info>();
+    const int64_t nd = E.n_distinct;
+    int rc = run_fit(ctx, &gs, G, 0, 0, E.d_goff.as<int64_t>(), E.rows, E.maxT, E.d_gds.as<int64_t>(), E.d_gy.p, S.y_dtype,
+                     S.has_floor ? E.d_gfl.as<double>() : nullptr, S.has_cap ? E.d_gcap.as<double>() : nullptr,
+                     S.n_extra > 0 ? E.d_gex.as<double>() : nullptr, &go, nullptr, nullptr, nullptr, 0, 0, 0, nullptr,
+                     nd > 0 ? E.d_gof.as<int32_t>() : nullptr, nd > 0 ? E.d_grows.as<int64_t>() : nullptr, nd,
+                     nd > 0 ? E.d_gord.as<int32_t>() : nullptr);
+    if (rc) return rc;
+    *n_grids += ctx->last_n_grids;
+    *n_launches += 1;
+    hipLaunchKernelGGL(cv_scatter_kernel, dim3((unsigned)G), dim3(64), 0, nullptr, G, E.d_gf.as<int32_t>(), stride, go, dst);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipDeviceSynchronize());       // (this launch's buffers go back to the pool)
+    return 0;
+}
+
+// the folds with history below fbprophet's Newton threshold (algorithm AUTO), or all folds on the spec's optimiser
+static void cv_optimiser_groups(const CvCall &S, const tsf_spec *spec, std::vector<int32_t> *g_lbfgs,
+                                std::vector<int32_t> *g_newton)
+{
+    const bool auto_algo = spec->algorithm == TSF_ALGO_AUTO;
+    const bool newton_ok = 3 + spec->n_changepoints + tsf_spec_K(spec) <= TSF_MAX_P;
+    for (int64_t f = 0; f < S.F; ++f) {
+        const bool nw = auto_algo ? (newton_ok && S.f_hist[(size_t)f] < TSF_NEWTON_BELOW_T) : spec->algorithm == TSF_ALGO_NEWTON;
+        (nw ? *g_newton : *g_lbfgs).push_back((int32_t)f);
+    }
+}
+
+// the views of `sel` whose L-BFGS fit (status in `st`, indexed by view) ended the way pystan raises RuntimeError on
+static std::vector<int32_t> newton_retry(const std::vector<int32_t> &sel, const std::vector<int32_t> &st)
+{
+    std::vector<int32_t> retry;
+    for (int32_t f : sel) {
+        const int32_t s = st[(size_t)f];
+        if (s == TSF_ST_LSFAIL || s == TSF_ST_INIT_NONFINITE || s == TSF_ST_EVAL_LIMIT) retry.push_back(f);
+    }
+    return retry;
+}
+
+static int cv_holdout(tsf_ctx *ctx, CvCall &S, const int64_t *series_key, CvHoldout *H)
+{
+    const int64_t F = S.F;
+    const int32_t Hmax = S.Hmax;
+    HIP_TRY(ctx, H->d_fds.alloc(8 * (size_t)F * Hmax));
+    if (S.n_extra > 0) HIP_TRY(ctx, H->d_fex.alloc(8 * (size_t)F * S.n_extra * Hmax));
+    HIP_TRY(ctx, H->d_fkey.alloc(8 * (size_t)F));
+    if (S.has_floor) { HIP_TRY(ctx, H->d_ffl.alloc(8 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(H->d_ffl.p, S.f_floor.data(), 8 * (size_t)F, hipMemcpyHostToDevice)); }
+    if (S.has_cap) { HIP_TRY(ctx, H->d_fcap.alloc(8 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(H->d_fcap.p, S.f_cap.data(), 8 * (size_t)F, hipMemcpyHostToDevice)); }
+    hipLaunchKernelGGL(cv_holdout_kernel, dim3((unsigned)(F < 65535 ? F : 65535)), dim3(128), 0, nullptr, S.pn, F, Hmax,
+                       S.d_fser.as<int32_t>(), S.d_fc.as<int32_t>(), S.d_fhist.as<int64_t>(), S.d_fhold.as<int64_t>(),
+                       series_key ? S.d_key.as<int64_t>() : nullptr, H->d_fds.as<int64_t>(),
+                       S.n_extra > 0 ? H->d_fex.as<double>() : nullptr, H->d_fkey.as<int64_t>());
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+// cv_metrics_kernel's arguments over the holdout forecasts yhat (and lo / hi: intervals) [F][Hmax]
+static int cv_metrics_setup(tsf_ctx *ctx, CvCall &S, const double *yhat, const double *lo, const double *hi,
+                            double rolling_window, CvMetrics *X)
+{
+    const int64_t N = S.N, F = S.F, R = S.R, M = S.M;
+    const bool iv = lo != nullptr;
+    HIP_TRY(ctx, X->d_foff.alloc(8 * ((size_t)N + 1))); HIP_TRY(ctx, hipMemcpy(X->d_foff.p, S.fold_off.data(), 8 * ((size_t)N + 1), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, X->d_roff.alloc(8 * ((size_t)N + 1))); HIP_TRY(ctx, hipMemcpy(X->d_roff.p, S.rows_off.data(), 8 * ((size_t)N + 1), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, X->d_moff.alloc(8 * ((size_t)N + 1))); HIP_TRY(ctx, hipMemcpy(X->d_moff.p, S.m_off.data(), 8 * ((size_t)N + 1), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, X->d_fcut.alloc(8 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(X->d_fcut.p, S.f_cut.data(), 8 * (size_t)F, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, X->d_frow0.alloc(8 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(X->d_frow0.p, S.f_row0.data(), 8 * (size_t)F, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, X->d_hs.alloc(8 * (size_t)R)); HIP_TRY(ctx, X->d_ts.alloc(8 * 4 * (size_t)R)); HIP_TRY(ctx, X->d_pre.alloc(8 * 4 * (size_t)(R + 64 * N)));
+    HIP_TRY(ctx, X->d_yo.alloc(8 * (size_t)R));
+    if (iv) { HIP_TRY(ctx, X->d_loo.alloc(8 * (size_t)R)); HIP_TRY(ctx, X->d_hio.alloc(8 * (size_t)R)); }
+    HIP_TRY(ctx, X->d_mh.alloc(8 * (size_t)M)); HIP_TRY(ctx, X->d_mm.alloc(8 * 5 * (size_t)M));
+    HIP_TRY(ctx, X->d_sst.alloc(4 * (size_t)N)); HIP_TRY(ctx, hipMemcpy(X->d_sst.p, S.pst.data(), 4 * (size_t)N, hipMemcpyHostToDevice));
+    CvMetricArgs &ma = X->ma;
+    memset(&ma, 0, sizeof(ma));
+    ma.p = S.pn; ma.y_dtype = S.y_dtype; ma.N = N; ma.Hmax = S.Hmax;
+    ma.fold_off = X->d_foff.as<int64_t>(); ma.rows_off = X->d_roff.as<int64_t>(); ma.m_off = X->d_moff.as<int64_t>();
+    ma.cutoff = X->d_fcut.as<int64_t>(); ma.fold_hist = S.d_fhist.as<int64_t>(); ma.fold_hold = S.d_fhold.as<int64_t>();
+    ma.fold_row0 = X->d_frow0.as<int64_t>(); ma.fit_status = S.dfo.status;
+    ma.yhat = yhat; ma.lo = lo; ma.hi = hi;
+    ma.rolling_window = rolling_window;
+    ma.h_s = X->d_hs.as<int64_t>(); ma.t_s = X->d_ts.as<double>(); ma.pre = X->d_pre.as<double>(); ma.R = R;
+    ma.yhat_out = X->d_yo.as<double>(); ma.lo_out = iv ? X->d_loo.as<double>() : nullptr; ma.hi_out = iv ? X->d_hio.as<double>() : nullptr;
+    double *mm = X->d_mm.as<double>();
+    ma.horizon = X->d_mh.as<int64_t>(); ma.mse = mm; ma.rmse = mm + M; ma.mae = mm + 2 * M; ma.mape = mm + 3 * M;
+    ma.coverage = mm + 4 * M; ma.series_status = X->d_sst.as<int32_t>();
     return 0;
 }
 
@@ -1987,19 +2300,10 @@ extern "C" int tsf_cross_validate(tsf_ctx *ctx, const tsf_spec *spec, int64_t N,
     ctx->order_n = 0;                   // (pending cost hints were meant for a fit call)
     ctx->cv_grids = 0;
     ctx->cv_launches = 0;
-    const bool aligned = offsets == nullptr;
-    std::vector<std::vector<tsf_cv::Fold>> plan;
-    std::vector<int32_t> pst;
-    std::vector<int64_t> pnh, pnm;
-    tsf_cv::panel_plan(N, T, offsets, ds, a, &plan, &pst, &pnh, &pnm);
-    std::vector<int64_t> fold_off((size_t)N + 1, 0), rows_off((size_t)N + 1, 0), m_off((size_t)N + 1, 0);
-    for (int64_t n = 0; n < N; ++n) {
-        fold_off[(size_t)n + 1] = fold_off[(size_t)n] + (int64_t)plan[(size_t)n].size();
-        rows_off[(size_t)n + 1] = rows_off[(size_t)n] + pnh[(size_t)n];
-        m_off[(size_t)n + 1] = m_off[(size_t)n] + pnm[(size_t)n];
-    }
-    const int64_t F = fold_off[(size_t)N], R = rows_off[(size_t)N], M = m_off[(size_t)N];
-    memcpy(out->series_status, pst.data(), sizeof(int32_t) * (size_t)N);
+    CvCall S;
+    cv_plan_call(N, T, offsets, ds, a, spec, y_dtype, floor_, cap, &S);
+    const int64_t F = S.F, R = S.R, M = S.M;
+    memcpy(out->series_status, S.pst.data(), sizeof(int32_t) * (size_t)N);
     if (F == 0) return 0;
     const tsf_fit_out &fo = out->fit;
     if (!fo.theta || !fo.y_scale || !fo.fval || !fo.status || !fo.n_iter || !fo.n_eval || !fo.grid)
@@ -2007,142 +2311,16 @@ extern "C" int tsf_cross_validate(tsf_ctx *ctx, const tsf_spec *spec, int64_t N,
     if (!out->yhat || !out->horizon_ns || !out->mse || !out->rmse || !out->mae || !out->mape ||
         (iv && (!out->yhat_lower || !out->yhat_upper || !out->coverage)))
         return fail(ctx, "tsf_cv_out has NULL members");
-    std::vector<int32_t> f_series((size_t)F), f_c((size_t)F);
-    std::vector<int64_t> f_cut((size_t)F), f_hist((size_t)F), f_hold((size_t)F), f_row0((size_t)F);
-    std::vector<double> f_floor(floor_ ? (size_t)F : 0), f_cap(cap ? (size_t)F : 0);
-    int32_t Hmax = 1, C = 0;
-    for (int64_t n = 0; n < N; ++n) {
-        int64_t r = rows_off[(size_t)n];
-        for (size_t c = 0; c < plan[(size_t)n].size(); ++c) {
-            const int64_t f = fold_off[(size_t)n] + (int64_t)c;
-            const tsf_cv::Fold &x = plan[(size_t)n][c];
-            f_series[(size_t)f] = (int32_t)n; f_c[(size_t)f] = (int32_t)c;
-            f_cut[(size_t)f] = x.cutoff; f_hist[(size_t)f] = x.hist; f_hold[(size_t)f] = x.hold; f_row0[(size_t)f] = r;
-            if (floor_) f_floor[(size_t)f] = floor_[n];
-            if (cap) f_cap[(size_t)f] = cap[n];
-            r += x.hold;
-            if (x.hold > Hmax) Hmax = (int32_t)x.hold;
-        }
-        if ((int32_t)plan[(size_t)n].size() > C) C = (int32_t)plan[(size_t)n].size();
-    }
-    const int stride = tsf_theta_stride(spec);
-    const size_t ysz = ysize(y_dtype);
-    const int64_t n_ds = aligned ? (int64_t)T : offsets[N];
-    const int64_t n_y = aligned ? N * (int64_t)T : offsets[N];
-    // the caller's panel, once
-    DevBuf d_ds, d_y, d_off, d_ex, d_fl, d_cap, d_key, d_fser, d_fc, d_fhist, d_fhold;
-    HIP_TRY(ctx, d_ds.alloc(8 * (size_t)n_ds));
-    HIP_TRY(ctx, hipMemcpy(d_ds.p, ds, 8 * (size_t)n_ds, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_y.alloc(ysz * (size_t)n_y));
-    HIP_TRY(ctx, hipMemcpy(d_y.p, y, ysz * (size_t)n_y, hipMemcpyHostToDevice));
-    if (!aligned) {
-        HIP_TRY(ctx, d_off.alloc(8 * ((size_t)N + 1)));
-        HIP_TRY(ctx, hipMemcpy(d_off.p, offsets, 8 * ((size_t)N + 1), hipMemcpyHostToDevice));
-    }
-    if (spec->n_extra > 0) {
-        HIP_TRY(ctx, d_ex.alloc(8 * (size_t)spec->n_extra * n_ds));
-        HIP_TRY(ctx, hipMemcpy(d_ex.p, extra, 8 * (size_t)spec->n_extra * n_ds, hipMemcpyHostToDevice));
-    }
-    if (floor_) { HIP_TRY(ctx, d_fl.alloc(8 * (size_t)N)); HIP_TRY(ctx, hipMemcpy(d_fl.p, floor_, 8 * (size_t)N, hipMemcpyHostToDevice)); }
-    if (cap) { HIP_TRY(ctx, d_cap.alloc(8 * (size_t)N)); HIP_TRY(ctx, hipMemcpy(d_cap.p, cap, 8 * (size_t)N, hipMemcpyHostToDevice)); }
-    if (series_key) { HIP_TRY(ctx, d_key.alloc(8 * (size_t)N)); HIP_TRY(ctx, hipMemcpy(d_key.p, series_key, 8 * (size_t)N, hipMemcpyHostToDevice)); }
-    HIP_TRY(ctx, d_fser.alloc(4 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(d_fser.p, f_series.data(), 4 * (size_t)F, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_fc.alloc(4 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(d_fc.p, f_c.data(), 4 * (size_t)F, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_fhist.alloc(8 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(d_fhist.p, f_hist.data(), 8 * (size_t)F, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_fhold.alloc(8 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(d_fhold.p, f_hold.data(), 8 * (size_t)F, hipMemcpyHostToDevice));
-    CvPanel pn;
-    pn.ds = d_ds.as<int64_t>(); pn.y = d_y.p; pn.extra = spec->n_extra > 0 ? d_ex.as<double>() : nullptr;
-    pn.src_off = aligned ? nullptr : d_off.as<int64_t>(); pn.T = aligned ? T : 0; pn.src_total = aligned ? 0 : offsets[N];
-    pn.ysz = (int)ysz; pn.n_extra = spec->n_extra;
-    // fit outputs in plan order
-    DevBuf d_th, d_ys, d_fv, d_st, d_it, d_ev, d_gr;
-    HIP_TRY(ctx, d_th.alloc(8 * (size_t)F * stride)); HIP_TRY(ctx, d_ys.alloc(8 * (size_t)F));
-    HIP_TRY(ctx, d_fv.alloc(8 * (size_t)F)); HIP_TRY(ctx, d_st.alloc(4 * (size_t)F));
-    HIP_TRY(ctx, d_it.alloc(4 * (size_t)F)); HIP_TRY(ctx, d_ev.alloc(4 * (size_t)F));
-    HIP_TRY(ctx, d_gr.alloc(sizeof(tsf_grid_info) * (size_t)F));
-    tsf_fit_out dfo;
-    dfo.theta = d_th.as<double>(); dfo.y_scale = d_ys.as<double>(); dfo.fval = d_fv.as<double>();
-    dfo.status = d_st.as<int32_t>(); dfo.n_iter = d_it.as<int32_t>(); dfo.n_eval = d_ev.as<int32_t>();
-    dfo.grid = d_gr.as<tsf_grid_info>();
+    if (int rc = cv_upload(ctx, y, floor_, cap, extra, series_key, &S)) return rc;
+    const int stride = S.stride;
+    const int32_t Hmax = S.Hmax;
+    const tsf_fit_out &dfo = S.dfo;
+    const CvViews folds = cv_fold_views(S);
     // one fit launch over the folds gf (plan indices)
     auto fit_group = [&](const tsf_spec &gs, const std::vector<int32_t> &gf) -> int {
-        const int64_t G = (int64_t)gf.size();
-        if (G == 0) return 0;
-        std::vector<int64_t> goff((size_t)G + 1, 0);
-        int32_t maxT = 0;
-        for (int64_t g = 0; g < G; ++g) {
-            const int64_t h = f_hist[(size_t)gf[(size_t)g]];
-            goff[(size_t)g + 1] = goff[(size_t)g] + h;
-            if (h > maxT) maxT = (int32_t)h;
-        }
-        const int64_t rows = goff[(size_t)G];
-        DevBuf d_gf, d_goff, d_gds, d_gy, d_gex, d_gfl, d_gcap, g_th, g_ys, g_fv, g_st, g_it, g_ev, g_gr, d_gof, d_grows, d_gord;
-        HIP_TRY(ctx, d_gf.alloc(4 * (size_t)G)); HIP_TRY(ctx, hipMemcpy(d_gf.p, gf.data(), 4 * (size_t)G, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, d_goff.alloc(8 * ((size_t)G + 1))); HIP_TRY(ctx, hipMemcpy(d_goff.p, goff.data(), 8 * ((size_t)G + 1), hipMemcpyHostToDevice));
-        HIP_TRY(ctx, d_gds.alloc(8 * (size_t)rows)); HIP_TRY(ctx, d_gy.alloc(ysz * (size_t)rows));
-        if (spec->n_extra > 0) HIP_TRY(ctx, d_gex.alloc(8 * (size_t)spec->n_extra * rows));
-        if (floor_) HIP_TRY(ctx, d_gfl.alloc(8 * (size_t)G));
-        if (cap) HIP_TRY(ctx, d_gcap.alloc(8 * (size_t)G));
-        hipLaunchKernelGGL(cv_expand_kernel, dim3((unsigned)(G < 65535 ? G : 65535)), dim3(256), 0, nullptr, pn, G,
-                           d_gf.as<int32_t>(), d_fser.as<int32_t>(), d_goff.as<int64_t>(), rows,
-                           floor_ ? d_fl.as<double>() : nullptr, cap ? d_cap.as<double>() : nullptr, d_gds.as<int64_t>(),
-                           d_gy.p, spec->n_extra > 0 ? d_gex.as<double>() : nullptr,
-                           floor_ ? d_gfl.as<double>() : nullptr, cap ? d_gcap.as<double>() : nullptr);
-        HIP_TRY(ctx, hipGetLastError());
-        // calendar classes (same rule as fit_host_one: ragged, no explicit columns, two series or more)
-        int64_t n_distinct = 0;
-        if (gs.n_extra == 0 && G >= 2 && ctx->opt[TSF_OPT_GRID_SHARE] != 0) {
-            std::vector<int32_t> gof((size_t)G);
-            std::vector<int64_t> reps;
-            if (aligned) {
-                std::vector<int32_t> id_of((size_t)C, -1);
-                for (int64_t g = 0; g < G; ++g) {
-                    const int32_t c = f_c[(size_t)gf[(size_t)g]];
-                    if (id_of[(size_t)c] < 0) { id_of[(size_t)c] = (int32_t)reps.size(); reps.push_back(g); }
-                    gof[(size_t)g] = id_of[(size_t)c];
-                }
-            } else {
-                std::vector<int64_t> vstart((size_t)G), vlen((size_t)G);
-                for (int64_t g = 0; g < G; ++g) {
-                    vstart[(size_t)g] = offsets[f_series[(size_t)gf[(size_t)g]]];
-                    vlen[(size_t)g] = f_hist[(size_t)gf[(size_t)g]];
-                }
-                calendar_classes(ds, vstart.data(), vlen.data(), G, &gof, &reps);
-            }
-            n_distinct = (int64_t)reps.size();
-            if (n_distinct < G) {
-                std::vector<int64_t> grows;
-                for (int64_t r : reps) { grows.push_back(goff[(size_t)r]); grows.push_back(goff[(size_t)r + 1] - goff[(size_t)r]); }
-                std::vector<int32_t> ord;
-                calendar_start_order(gof, n_distinct, &ord);
-                HIP_TRY(ctx, d_gof.alloc(4 * (size_t)G)); HIP_TRY(ctx, hipMemcpy(d_gof.p, gof.data(), 4 * (size_t)G, hipMemcpyHostToDevice));
-                HIP_TRY(ctx, d_grows.alloc(8 * grows.size())); HIP_TRY(ctx, hipMemcpy(d_grows.p, grows.data(), 8 * grows.size(), hipMemcpyHostToDevice));
-                HIP_TRY(ctx, d_gord.alloc(4 * (size_t)G)); HIP_TRY(ctx, hipMemcpy(d_gord.p, ord.data(), 4 * (size_t)G, hipMemcpyHostToDevice));
-            } else {
-                n_distinct = 0;
-            }
-        }
-        HIP_TRY(ctx, g_th.alloc(8 * (size_t)G * stride)); HIP_TRY(ctx, g_ys.alloc(8 * (size_t)G)); HIP_TRY(ctx, g_fv.alloc(8 * (size_t)G));
-        HIP_TRY(ctx, g_st.alloc(4 * (size_t)G)); HIP_TRY(ctx, g_it.alloc(4 * (size_t)G)); HIP_TRY(ctx, g_ev.alloc(4 * (size_t)G));
-        HIP_TRY(ctx, g_gr.alloc(sizeof(tsf_grid_info) * (size_t)G));
-        HIP_TRY(ctx, hipMemset(g_st.p, 0, 4 * (size_t)G)); HIP_TRY(ctx, hipMemset(g_it.p, 0, 4 * (size_t)G));
-        HIP_TRY(ctx, hipMemset(g_ev.p, 0, 4 * (size_t)G)); HIP_TRY(ctx, hipMemset(g_gr.p, 0, sizeof(tsf_grid_info) * (size_t)G));
-        tsf_fit_out go;
-        go.theta = g_th.as<double>(); go.y_scale = g_ys.as<double>(); go.fval = g_fv.as<double>();
-        go.status = g_st.as<int32_t>(); go.n_iter = g_it.as<int32_t>(); go.n_eval = g_ev.as<int32_t>();
-        go.grid = g_gr.as<tsf_grid_info>();
-        int rc = run_fit(ctx, &gs, G, 0, 0, d_goff.as<int64_t>(), rows, maxT, d_gds.as<int64_t>(), d_gy.p, y_dtype,
-                         floor_ ? d_gfl.as<double>() : nullptr, cap ? d_gcap.as<double>() : nullptr,
-                         spec->n_extra > 0 ? d_gex.as<double>() : nullptr, &go, nullptr, nullptr, nullptr, 0, 0, 0, nullptr,
-                         n_distinct > 0 ? d_gof.as<int32_t>() : nullptr, n_distinct > 0 ? d_grows.as<int64_t>() : nullptr,
-                         n_distinct, n_distinct > 0 ? d_gord.as<int32_t>() : nullptr);
-        if (rc) return rc;
-        ctx->cv_grids += ctx->last_n_grids;
-        ctx->cv_launches += 1;
-        hipLaunchKernelGGL(cv_scatter_kernel, dim3((unsigned)G), dim3(64), 0, nullptr, G, d_gf.as<int32_t>(), stride, go, dfo);
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipDeviceSynchronize());       // (this launch's buffers go back to the pool)
-        return 0;
+        CvGroup E;
+        if (int rc = cv_expand(ctx, S, folds, gf, &E)) return rc;
+        return cv_fit(ctx, S, E, gs, dfo, &ctx->cv_grids, &ctx->cv_launches);
     };
     // fbprophet's optimiser choice per fold (include/tsf.h)
     tsf_spec sp_l = *spec, sp_n = *spec;
@@ -2151,95 +2329,300 @@ extern "C" int tsf_cross_validate(tsf_ctx *ctx, const tsf_spec *spec, int64_t N,
     const bool auto_algo = spec->algorithm == TSF_ALGO_AUTO;
     const bool newton_ok = 3 + spec->n_changepoints + tsf_spec_K(spec) <= TSF_MAX_P;
     std::vector<int32_t> g_newton, g_lbfgs;
-    for (int64_t f = 0; f < F; ++f) {
-        const bool nw = auto_algo ? (newton_ok && f_hist[(size_t)f] < TSF_NEWTON_BELOW_T) : spec->algorithm == TSF_ALGO_NEWTON;
-        (nw ? g_newton : g_lbfgs).push_back((int32_t)f);
-    }
+    cv_optimiser_groups(S, spec, &g_lbfgs, &g_newton);
     if (int rc = fit_group(sp_l, g_lbfgs)) return rc;
     if (auto_algo && newton_ok && !g_lbfgs.empty()) {
-        std::vector<int32_t> st((size_t)F), retry;
-        HIP_TRY(ctx, hipMemcpy(st.data(), d_st.p, 4 * (size_t)F, hipMemcpyDeviceToHost));
-        for (int32_t f : g_lbfgs) {
-            const int32_t s = st[(size_t)f];
-            if (s == TSF_ST_LSFAIL || s == TSF_ST_INIT_NONFINITE || s == TSF_ST_EVAL_LIMIT) retry.push_back(f);
-        }
-        if (int rc = fit_group(sp_n, retry)) return rc;
+        std::vector<int32_t> st((size_t)F);
+        HIP_TRY(ctx, hipMemcpy(st.data(), S.d_st.p, 4 * (size_t)F, hipMemcpyDeviceToHost));
+        if (int rc = fit_group(sp_n, newton_retry(g_lbfgs, st))) return rc;
     }
     if (int rc = fit_group(sp_n, g_newton)) return rc;
     // the holdout rows of every fold, predicted in one call
-    DevBuf d_fds, d_fex, d_fkey, d_ffl, d_fcap, d_yh, d_lo, d_hi;
-    HIP_TRY(ctx, d_fds.alloc(8 * (size_t)F * Hmax));
-    if (spec->n_extra > 0) HIP_TRY(ctx, d_fex.alloc(8 * (size_t)F * spec->n_extra * Hmax));
-    HIP_TRY(ctx, d_fkey.alloc(8 * (size_t)F));
-    if (floor_) { HIP_TRY(ctx, d_ffl.alloc(8 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(d_ffl.p, f_floor.data(), 8 * (size_t)F, hipMemcpyHostToDevice)); }
-    if (cap) { HIP_TRY(ctx, d_fcap.alloc(8 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(d_fcap.p, f_cap.data(), 8 * (size_t)F, hipMemcpyHostToDevice)); }
+    CvHoldout H;
+    DevBuf d_yh, d_lo, d_hi;
     HIP_TRY(ctx, d_yh.alloc(8 * (size_t)F * Hmax));
     if (iv) { HIP_TRY(ctx, d_lo.alloc(8 * (size_t)F * Hmax)); HIP_TRY(ctx, d_hi.alloc(8 * (size_t)F * Hmax)); }
-    hipLaunchKernelGGL(cv_holdout_kernel, dim3((unsigned)(F < 65535 ? F : 65535)), dim3(128), 0, nullptr, pn, F, Hmax,
-                       d_fser.as<int32_t>(), d_fc.as<int32_t>(), d_fhist.as<int64_t>(), d_fhold.as<int64_t>(),
-                       series_key ? d_key.as<int64_t>() : nullptr, d_fds.as<int64_t>(),
-                       spec->n_extra > 0 ? d_fex.as<double>() : nullptr, d_fkey.as<int64_t>());
-    HIP_TRY(ctx, hipGetLastError());
+    if (int rc = cv_holdout(ctx, S, series_key, &H)) return rc;
     {
-        const double *pfl = floor_ ? d_ffl.as<double>() : nullptr, *pcap = cap ? d_fcap.as<double>() : nullptr;
-        const double *pex = spec->n_extra > 0 ? d_fex.as<double>() : nullptr;
+        const double *pfl = floor_ ? H.d_ffl.as<double>() : nullptr, *pcap = cap ? H.d_fcap.as<double>() : nullptr;
+        const double *pex = spec->n_extra > 0 ? H.d_fex.as<double>() : nullptr;
         const int rc = iv ? tsf_predict_intervals_dev(ctx, spec, F, Hmax, dfo.theta, dfo.y_scale, dfo.grid, (int32_t)F,
-                                                      d_fds.as<int64_t>(), 0, pfl, pcap, pex, d_fkey.as<int64_t>(), n_samples,
+                                                      H.d_fds.as<int64_t>(), 0, pfl, pcap, pex, H.d_fkey.as<int64_t>(), n_samples,
                                                       interval_width, seed, d_yh.as<double>(), d_lo.as<double>(),
                                                       d_hi.as<double>(), nullptr)
-                          : tsf_predict_dev(ctx, spec, F, Hmax, dfo.theta, dfo.y_scale, dfo.grid, (int32_t)F, d_fds.as<int64_t>(),
+                          : tsf_predict_dev(ctx, spec, F, Hmax, dfo.theta, dfo.y_scale, dfo.grid, (int32_t)F, H.d_fds.as<int64_t>(),
                                             0, pfl, pcap, pex, d_yh.as<double>(), nullptr, nullptr);
         if (rc) return rc;
     }
     // metrics per series
-    DevBuf d_foff, d_roff, d_moff, d_fcut, d_frow0, d_hs, d_ts, d_pre, d_yo, d_loo, d_hio, d_mh, d_mm, d_sst;
-    HIP_TRY(ctx, d_foff.alloc(8 * ((size_t)N + 1))); HIP_TRY(ctx, hipMemcpy(d_foff.p, fold_off.data(), 8 * ((size_t)N + 1), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_roff.alloc(8 * ((size_t)N + 1))); HIP_TRY(ctx, hipMemcpy(d_roff.p, rows_off.data(), 8 * ((size_t)N + 1), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_moff.alloc(8 * ((size_t)N + 1))); HIP_TRY(ctx, hipMemcpy(d_moff.p, m_off.data(), 8 * ((size_t)N + 1), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_fcut.alloc(8 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(d_fcut.p, f_cut.data(), 8 * (size_t)F, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_frow0.alloc(8 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(d_frow0.p, f_row0.data(), 8 * (size_t)F, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_hs.alloc(8 * (size_t)R)); HIP_TRY(ctx, d_ts.alloc(8 * 4 * (size_t)R)); HIP_TRY(ctx, d_pre.alloc(8 * 4 * (size_t)(R + 64 * N)));
-    HIP_TRY(ctx, d_yo.alloc(8 * (size_t)R));
-    if (iv) { HIP_TRY(ctx, d_loo.alloc(8 * (size_t)R)); HIP_TRY(ctx, d_hio.alloc(8 * (size_t)R)); }
-    HIP_TRY(ctx, d_mh.alloc(8 * (size_t)M)); HIP_TRY(ctx, d_mm.alloc(8 * 5 * (size_t)M));
-    HIP_TRY(ctx, d_sst.alloc(4 * (size_t)N)); HIP_TRY(ctx, hipMemcpy(d_sst.p, pst.data(), 4 * (size_t)N, hipMemcpyHostToDevice));
-    CvMetricArgs ma;
-    memset(&ma, 0, sizeof(ma));
-    ma.p = pn; ma.y_dtype = y_dtype; ma.N = N; ma.Hmax = Hmax;
-    ma.fold_off = d_foff.as<int64_t>(); ma.rows_off = d_roff.as<int64_t>(); ma.m_off = d_moff.as<int64_t>();
-    ma.cutoff = d_fcut.as<int64_t>(); ma.fold_hist = d_fhist.as<int64_t>(); ma.fold_hold = d_fhold.as<int64_t>();
-    ma.fold_row0 = d_frow0.as<int64_t>(); ma.fit_status = dfo.status;
-    ma.yhat = d_yh.as<double>(); ma.lo = iv ? d_lo.as<double>() : nullptr; ma.hi = iv ? d_hi.as<double>() : nullptr;
-    ma.rolling_window = a.rolling_window;
-    ma.h_s = d_hs.as<int64_t>(); ma.t_s = d_ts.as<double>(); ma.pre = d_pre.as<double>(); ma.R = R;
-    ma.yhat_out = d_yo.as<double>(); ma.lo_out = iv ? d_loo.as<double>() : nullptr; ma.hi_out = iv ? d_hio.as<double>() : nullptr;
-    double *mm = d_mm.as<double>();
-    ma.horizon = d_mh.as<int64_t>(); ma.mse = mm; ma.rmse = mm + M; ma.mae = mm + 2 * M; ma.mape = mm + 3 * M;
-    ma.coverage = mm + 4 * M; ma.series_status = d_sst.as<int32_t>();
-    hipLaunchKernelGGL(cv_metrics_kernel, dim3((unsigned)N), dim3(64), 0, nullptr, ma);
+    CvMetrics X;
+    if (int rc = cv_metrics_setup(ctx, S, d_yh.as<double>(), iv ? d_lo.as<double>() : nullptr, iv ? d_hi.as<double>() : nullptr,
+                                  a.rolling_window, &X))
+        return rc;
+    hipLaunchKernelGGL(cv_metrics_kernel, dim3((unsigned)N), dim3(64), 0, nullptr, X.ma);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipDeviceSynchronize());
     // outputs
-    HIP_TRY(ctx, hipMemcpy(fo.theta, d_th.p, 8 * (size_t)F * stride, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(fo.y_scale, d_ys.p, 8 * (size_t)F, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(fo.fval, d_fv.p, 8 * (size_t)F, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(fo.status, d_st.p, 4 * (size_t)F, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(fo.n_iter, d_it.p, 4 * (size_t)F, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(fo.n_eval, d_ev.p, 4 * (size_t)F, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(fo.grid, d_gr.p, sizeof(tsf_grid_info) * (size_t)F, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(out->yhat, d_yo.p, 8 * (size_t)R, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(fo.theta, S.d_th.p, 8 * (size_t)F * stride, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(fo.y_scale, S.d_ys.p, 8 * (size_t)F, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(fo.fval, S.d_fv.p, 8 * (size_t)F, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(fo.status, S.d_st.p, 4 * (size_t)F, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(fo.n_iter, S.d_it.p, 4 * (size_t)F, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(fo.n_eval, S.d_ev.p, 4 * (size_t)F, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(fo.grid, S.d_gr.p, sizeof(tsf_grid_info) * (size_t)F, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(out->yhat, X.d_yo.p, 8 * (size_t)R, hipMemcpyDeviceToHost));
     if (iv) {
-        HIP_TRY(ctx, hipMemcpy(out->yhat_lower, d_loo.p, 8 * (size_t)R, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(out->yhat_upper, d_hio.p, 8 * (size_t)R, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out->yhat_lower, X.d_loo.p, 8 * (size_t)R, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out->yhat_upper, X.d_hio.p, 8 * (size_t)R, hipMemcpyDeviceToHost));
     }
     if (M > 0) {
-        HIP_TRY(ctx, hipMemcpy(out->horizon_ns, d_mh.p, 8 * (size_t)M, hipMemcpyDeviceToHost));
+        const double *mm = X.d_mm.as<double>();
+        HIP_TRY(ctx, hipMemcpy(out->horizon_ns, X.d_mh.p, 8 * (size_t)M, hipMemcpyDeviceToHost));
         HIP_TRY(ctx, hipMemcpy(out->mse, mm, 8 * (size_t)M, hipMemcpyDeviceToHost));
         HIP_TRY(ctx, hipMemcpy(out->rmse, mm + M, 8 * (size_t)M, hipMemcpyDeviceToHost));
         HIP_TRY(ctx, hipMemcpy(out->mae, mm + 2 * M, 8 * (size_t)M, hipMemcpyDeviceToHost));
         HIP_TRY(ctx, hipMemcpy(out->mape, mm + 3 * M, 8 * (size_t)M, hipMemcpyDeviceToHost));
         if (iv) HIP_TRY(ctx, hipMemcpy(out->coverage, mm + 4 * M, 8 * (size_t)M, hipMemcpyDeviceToHost));
     }
-    HIP_TRY(ctx, hipMemcpy(out->series_status, d_sst.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(out->series_status, X.d_sst.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- prior-scale tuning (include/tsf.h) ---------------------------------------------------------------
+
+extern "C" int tsf_last_tune_counts(const tsf_ctx *ctx, int32_t *expand_launches, int32_t *fit_launches)
+{
+    if (!ctx || !expand_launches || !fit_launches) return -1;
+    *expand_launches = ctx->tune_expand;
+    *fit_launches = ctx->tune_fits;
+    return 0;
+}
+
+// every field of a and b equal except the prior scales (the columns' entries only)
+static bool same_but_prior_scales(const tsf_spec &a, const tsf_spec &b)
+{
+    if (a.growth != b.growth || a.n_changepoints != b.n_changepoints || a.changepoint_range != b.changepoint_range ||
+        a.n_seas != b.n_seas || a.n_extra != b.n_extra)
+        return false;
+    if (a.n_seas < 0 || a.n_seas > TSF_MAX_SEAS || a.n_extra < 0 || a.n_extra > TSF_MAX_EXTRA) return false;
+    for (int i = 0; i < a.n_seas; ++i)
+        if (a.seas_period[i] != b.seas_period[i] || a.seas_order[i] != b.seas_order[i] || a.seas_mode[i] != b.seas_mode[i])
+            return false;
+    for (int i = 0; i < a.n_extra; ++i)
+        if (a.extra_mode[i] != b.extra_mode[i]) return false;
+    return a.max_iter == b.max_iter && a.history == b.history && a.init_alpha == b.init_alpha && a.tol_obj == b.tol_obj &&
+           a.tol_rel_obj == b.tol_rel_obj && a.tol_grad == b.tol_grad && a.tol_rel_grad == b.tol_rel_grad &&
+           a.tol_param == b.tol_param && a.eval_form == b.eval_form && a.recenter_every == b.recenter_every &&
+           a.recenter_ratio == b.recenter_ratio && a.algorithm == b.algorithm && a.residual_kernel == b.residual_kernel &&
+           a.coop_after == b.coop_after && a.converge == b.converge && a.map_max_iter == b.map_max_iter &&
+           a.map_tol == b.map_tol;
+}
+
+static bool prior_scales_ok(const tsf_spec &s)
+{
+    auto ok = [](double v) { return std::isfinite(v) && v > 0.0; };
+    if (!ok(s.changepoint_prior_scale)) return false;
+    for (int i = 0; i < s.n_seas; ++i) if (!ok(s.seas_prior_scale[i])) return false;
+    for (int i = 0; i < s.n_extra; ++i) if (!ok(s.extra_prior_scale[i])) return false;
+    return true;
+}
+
+extern "C" int tsf_tune(tsf_ctx *ctx, const tsf_spec *base, const tsf_spec *cand, int32_t C, int64_t N, int32_t T,
+                        const int64_t *offsets, const int64_t *ds, const void *y, int32_t y_dtype, const double *floor_,
+                        const double *cap, const double *extra, const tsf_cv_args *cv, int32_t metric, int32_t refit,
+                        tsf_tune_out *out)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!base || !cand || !ds || !y || !out || !out->score || !out->cand_status || !out->best || !out->series_status)
+        return fail(ctx, "NULL input");
+    if (C < 1 || C > TSF_TUNE_MAX_CAND) return fail(ctx, "C must be in [1, TSF_TUNE_MAX_CAND]");
+    if (metric < TSF_TUNE_MSE || metric > TSF_TUNE_MAPE) return fail(ctx, "bad metric (TSF_TUNE_MSE .. TSF_TUNE_MAPE)");
+    if (refit != 0 && refit != 1) return fail(ctx, "refit must be 0 or 1");
+    if (y_dtype < TSF_Y_F64 || y_dtype > TSF_Y_I32) return fail(ctx, "bad y_dtype");
+    tsf_cv_args a;
+    if (!cv) return fail(ctx, "cv is NULL");
+    tsf_cv_args cv1 = *cv;
+    cv1.rolling_window = 1.0;           // one metric row per series, over all its holdout rows
+    if (tsf_cv::resolve_args(&cv1, &a)) return fail(ctx, "bad cross-validation arguments (horizon_ns > 0)");
+    if (tsf_cv::check_panel(N, T, offsets, ds))
+        return fail(ctx, "bad panel (aligned: offsets NULL, 1 <= T <= TSF_MAX_T; ragged: T = 0, offsets[0] = 0, ascending)");
+    if (base->n_extra > 0 && !extra) return fail(ctx, "extra columns declared but extra is NULL");
+    if (base->growth == TSF_GROWTH_LOGISTIC && !cap) return fail(ctx, "logistic growth needs cap");
+    if (!prior_scales_ok(*base)) return fail(ctx, "base: prior scales must be finite and > 0");
+    for (int32_t c = 0; c < C; ++c) {
+        if (!same_but_prior_scales(*base, cand[c]))
+            return fail(ctx, "a candidate differs from base in more than its prior scales");
+        if (!prior_scales_ok(cand[c])) return fail(ctx, "a candidate's prior scales must be finite and > 0");
+    }
+    const tsf_fit_out &fo = out->fit;
+    if (refit && (!fo.theta || !fo.y_scale || !fo.fval || !fo.status || !fo.n_iter || !fo.n_eval || !fo.grid))
+        return fail(ctx, "tsf_tune_out.fit has NULL members");
+    ctx->order_n = 0;                   // (pending cost hints were meant for a fit call)
+    ctx->tune_expand = 0;
+    ctx->tune_fits = 0;
+    CvCall S;
+    cv_plan_call(N, T, offsets, ds, a, base, y_dtype, floor_, cap, &S);
+    const int64_t F = S.F, M = S.M, NC = N * (int64_t)C;
+    if (int rc = cv_upload(ctx, y, floor_, cap, extra, nullptr, &S)) return rc;
+    const int stride = S.stride;
+    int64_t grids = 0;                  // (not reported)
+    DevBuf d_score, d_cst, d_pst, d_best, d_sstat;
+    HIP_TRY(ctx, d_score.alloc(8 * (size_t)NC)); HIP_TRY(ctx, d_cst.alloc(4 * (size_t)NC));
+    HIP_TRY(ctx, d_pst.alloc(4 * (size_t)N)); HIP_TRY(ctx, hipMemcpy(d_pst.p, S.pst.data(), 4 * (size_t)N, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_best.alloc(4 * (size_t)N)); HIP_TRY(ctx, d_sstat.alloc(4 * (size_t)N));
+    if (F == 0) {                       // no series has a fold: every score NaN, every status the plan's
+        std::vector<double> sc((size_t)NC, std::nan(""));
+        std::vector<int32_t> cs((size_t)NC);
+        for (int64_t i = 0; i < NC; ++i) cs[(size_t)i] = S.pst[(size_t)(i / C)];
+        HIP_TRY(ctx, hipMemcpy(d_score.p, sc.data(), 8 * (size_t)NC, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(d_cst.p, cs.data(), 4 * (size_t)NC, hipMemcpyHostToDevice));
+    } else {
+        // shared by every candidate: the holdout rows, the metric tables, the fold panel of each optimiser group
+        CvHoldout H;
+        DevBuf d_yh;
+        HIP_TRY(ctx, d_yh.alloc(8 * (size_t)F * S.Hmax));
+        if (int rc = cv_holdout(ctx, S, nullptr, &H)) return rc;
+        CvMetrics X;
+        if (int rc = cv_metrics_setup(ctx, S, d_yh.as<double>(), nullptr, nullptr, a.rolling_window, &X)) return rc;
+        const double *mval = X.d_mm.as<double>() + (size_t)metric * M;
+        const CvViews folds = cv_fold_views(S);
+        std::vector<int32_t> g_newton, g_lbfgs;
+        cv_optimiser_groups(S, base, &g_lbfgs, &g_newton);
+        CvGroup E_l, E_n;
+        if (int rc = cv_expand(ctx, S, folds, g_lbfgs, &E_l)) return rc;
+        if (int rc = cv_expand(ctx, S, folds, g_newton, &E_n)) return rc;
+        ctx->tune_expand += (E_l.G > 0) + (E_n.G > 0);
+        const bool auto_algo = base->algorithm == TSF_ALGO_AUTO;
+        const bool newton_ok = 3 + base->n_changepoints + tsf_spec_K(base) <= TSF_MAX_P;
+        std::vector<int32_t> st((size_t)F);
+        for (int32_t c = 0; c < C; ++c) {
+            tsf_spec sp_l = cand[c], sp_n = cand[c];
+            sp_l.algorithm = TSF_ALGO_LBFGS;
+            sp_n.algorithm = TSF_ALGO_NEWTON;
+            if (int rc = cv_fit(ctx, S, E_l, sp_l, S.dfo, &grids, &ctx->tune_fits)) return rc;
+            if (auto_algo && newton_ok && E_l.G > 0) {
+                HIP_TRY(ctx, hipMemcpy(st.data(), S.d_st.p, 4 * (size_t)F, hipMemcpyDeviceToHost));
+                CvGroup E_r;
+                if (int rc = cv_expand(ctx, S, folds, newton_retry(g_lbfgs, st), &E_r)) return rc;
+                ctx->tune_expand += E_r.G > 0;
+                if (int rc = cv_fit(ctx, S, E_r, sp_n, S.dfo, &grids, &ctx->tune_fits)) return rc;
+            }
+            if (int rc = cv_fit(ctx, S, E_n, sp_n, S.dfo, &grids, &ctx->tune_fits)) return rc;
+            const double *pfl = floor_ ? H.d_ffl.as<double>() : nullptr, *pcap = cap ? H.d_fcap.as<double>() : nullptr;
+            const double *pex = base->n_extra > 0 ? H.d_fex.as<double>() : nullptr;
+            if (int rc = tsf_predict_dev(ctx, &cand[c], F, S.Hmax, S.dfo.theta, S.dfo.y_scale, S.dfo.grid, (int32_t)F,
+                                         H.d_fds.as<int64_t>(), 0, pfl, pcap, pex, d_yh.as<double>(), nullptr, nullptr))
+                return rc;
+            HIP_TRY(ctx, hipMemcpy(X.d_sst.p, S.pst.data(), 4 * (size_t)N, hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(cv_metrics_kernel, dim3((unsigned)N), dim3(64), 0, nullptr, X.ma);
+            HIP_TRY(ctx, hipGetLastError());
+            hipLaunchKernelGGL(tune_score_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, nullptr, N, C, c, mval,
+                               X.d_moff.as<int64_t>(), X.d_sst.as<int32_t>(), d_score.as<double>(), d_cst.as<int32_t>());
+            HIP_TRY(ctx, hipGetLastError());
+        }
+    }
+    hipLaunchKernelGGL(tune_select_kernel, dim3((unsigned)((N + TUNE_SELECT_WAVES - 1) / TUNE_SELECT_WAVES)),
+                       dim3(TUNE_SELECT_WAVES * 64), 0, nullptr, N, C, d_score.as<double>(), d_pst.as<int32_t>(),
+                       d_best.as<int32_t>(), d_sstat.as<int32_t>());
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    HIP_TRY(ctx, hipMemcpy(out->score, d_score.p, 8 * (size_t)NC, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(out->cand_status, d_cst.p, 4 * (size_t)NC, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(out->best, d_best.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(out->series_status, d_sstat.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+    if (!refit) return 0;
+    // ---- refit: one group per distinct choice (base for best = -1), per optimiser
+    const bool aligned = S.aligned;
+    const int64_t n_grids = aligned ? 1 : N;
+    DevBuf r_th, r_ys, r_fv, r_st, r_it, r_ev, r_gr;
+    HIP_TRY(ctx, r_th.alloc(8 * (size_t)N * stride)); HIP_TRY(ctx, r_ys.alloc(8 * (size_t)N)); HIP_TRY(ctx, r_fv.alloc(8 * (size_t)N));
+    HIP_TRY(ctx, r_st.alloc(4 * (size_t)N)); HIP_TRY(ctx, r_it.alloc(4 * (size_t)N)); HIP_TRY(ctx, r_ev.alloc(4 * (size_t)N));
+    HIP_TRY(ctx, r_gr.alloc(sizeof(tsf_grid_info) * (size_t)n_grids));
+    HIP_TRY(ctx, hipMemset(r_th.p, 0, 8 * (size_t)N * stride)); HIP_TRY(ctx, hipMemset(r_ys.p, 0, 8 * (size_t)N));
+    HIP_TRY(ctx, hipMemset(r_fv.p, 0, 8 * (size_t)N)); HIP_TRY(ctx, hipMemset(r_it.p, 0, 4 * (size_t)N));
+    HIP_TRY(ctx, hipMemset(r_ev.p, 0, 4 * (size_t)N)); HIP_TRY(ctx, hipMemset(r_gr.p, 0, sizeof(tsf_grid_info) * (size_t)n_grids));
+    std::vector<int32_t> rst((size_t)N, TSF_ST_TOO_FEW);      // (a ragged series without rows is not fitted)
+    HIP_TRY(ctx, hipMemcpy(r_st.p, rst.data(), 4 * (size_t)N, hipMemcpyHostToDevice));
+    tsf_fit_out rfo;
+    rfo.theta = r_th.as<double>(); rfo.y_scale = r_ys.as<double>(); rfo.fval = r_fv.as<double>();
+    rfo.status = r_st.as<int32_t>(); rfo.n_iter = r_it.as<int32_t>(); rfo.n_eval = r_ev.as<int32_t>();
+    rfo.grid = r_gr.as<tsf_grid_info>();
+    std::vector<int32_t> ident((size_t)N);
+    std::vector<int64_t> len((size_t)N);
+    for (int64_t n = 0; n < N; ++n) { ident[(size_t)n] = (int32_t)n; len[(size_t)n] = aligned ? T : offsets[n + 1] - offsets[n]; }
+    DevBuf d_ident;
+    if (!aligned) { HIP_TRY(ctx, d_ident.alloc(4 * (size_t)N)); HIP_TRY(ctx, hipMemcpy(d_ident.p, ident.data(), 4 * (size_t)N, hipMemcpyHostToDevice)); }
+    const CvViews whole{d_ident.as<int32_t>(), ident.data(), len.data(), nullptr, 0};
+    // one fit launch over the series sel with spec gs: aligned, the series' rows gathered into a [G][T] panel
+    // (tune_gather_kernel); ragged, their full histories as views (cv_expand_kernel)
+    auto refit_group = [&](const tsf_spec &gs, const std::vector<int32_t> &sel) -> int {
+        const int64_t G = (int64_t)sel.size();
+        if (G == 0) return 0;
+        if (!aligned) {
+            CvGroup E;
+            if (int rc = cv_expand(ctx, S, whole, sel, &E)) return rc;
+            return cv_fit(ctx, S, E, gs, rfo, &grids, &ctx->tune_fits);
+        }
+        DevBuf d_sel, d_gy, d_gfl, d_gcap, g_th, g_ys, g_fv, g_st, g_it, g_ev, g_gr;
+        HIP_TRY(ctx, d_sel.alloc(4 * (size_t)G)); HIP_TRY(ctx, hipMemcpy(d_sel.p, sel.data(), 4 * (size_t)G, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, d_gy.alloc(S.ysz * (size_t)G * T));
+        if (floor_) HIP_TRY(ctx, d_gfl.alloc(8 * (size_t)G));
+        if (cap) HIP_TRY(ctx, d_gcap.alloc(8 * (size_t)G));
+        hipLaunchKernelGGL(tune_gather_kernel, dim3((unsigned)(G < 65535 ? G : 65535)), dim3(256), 0, nullptr, S.pn, G,
+                           d_sel.as<int32_t>(), floor_ ? S.d_fl.as<double>() : nullptr, cap ? S.d_cap.as<double>() : nullptr,
+                           d_gy.p, floor_ ? d_gfl.as<double>() : nullptr, cap ? d_gcap.as<double>() : nullptr);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, g_th.alloc(8 * (size_t)G * stride)); HIP_TRY(ctx, g_ys.alloc(8 * (size_t)G)); HIP_TRY(ctx, g_fv.alloc(8 * (size_t)G));
+        HIP_TRY(ctx, g_st.alloc(4 * (size_t)G)); HIP_TRY(ctx, g_it.alloc(4 * (size_t)G)); HIP_TRY(ctx, g_ev.alloc(4 * (size_t)G));
+        HIP_TRY(ctx, g_gr.alloc(sizeof(tsf_grid_info)));
+        HIP_TRY(ctx, hipMemset(g_st.p, 0, 4 * (size_t)G)); HIP_TRY(ctx, hipMemset(g_it.p, 0, 4 * (size_t)G));
+        HIP_TRY(ctx, hipMemset(g_ev.p, 0, 4 * (size_t)G)); HIP_TRY(ctx, hipMemset(g_gr.p, 0, sizeof(tsf_grid_info)));
+        tsf_fit_out go;
+        go.theta = g_th.as<double>(); go.y_scale = g_ys.as<double>(); go.fval = g_fv.as<double>();
+        go.status = g_st.as<int32_t>(); go.n_iter = g_it.as<int32_t>(); go.n_eval = g_ev.as<int32_t>();
+        go.grid = g_gr.as<tsf_grid_info>();
+        int rc = run_fit(ctx, &gs, G, 1, T, nullptr, 0, T, S.d_ds.as<int64_t>(), d_gy.p, y_dtype,
+                         floor_ ? d_gfl.as<double>() : nullptr, cap ? d_gcap.as<double>() : nullptr,
+                         base->n_extra > 0 ? S.d_ex.as<double>() : nullptr, &go, nullptr, nullptr, nullptr);
+        if (rc) return rc;
+        ctx->tune_fits += 1;
+        hipLaunchKernelGGL(tune_scatter_kernel, dim3((unsigned)G), dim3(64), 0, nullptr, G, d_sel.as<int32_t>(), stride, go, rfo);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipDeviceSynchronize());
+        return 0;
+    };
+    std::vector<int32_t> rstat((size_t)N);
+    for (int32_t b = -1; b < C; ++b) {
+        const tsf_spec &gs = b < 0 ? *base : cand[b];
+        const bool auto_g = gs.algorithm == TSF_ALGO_AUTO;
+        const bool newton_ok = 3 + gs.n_changepoints + tsf_spec_K(&gs) <= TSF_MAX_P;
+        std::vector<int32_t> g_lb, g_nw;      // (not AUTO: every series of the choice in g_lb, on gs's own optimiser)
+        for (int64_t n = 0; n < N; ++n) {
+            if (out->best[n] != b || len[(size_t)n] == 0) continue;
+            (auto_g && newton_ok && len[(size_t)n] < TSF_NEWTON_BELOW_T ? g_nw : g_lb).push_back((int32_t)n);
+        }
+        if (!auto_g) {
+            if (int rc = refit_group(gs, g_lb)) return rc;
+            continue;
+        }
+        tsf_spec sp_l = gs, sp_n = gs;
+        sp_l.algorithm = TSF_ALGO_LBFGS;
+        sp_n.algorithm = TSF_ALGO_NEWTON;
+        if (int rc = refit_group(sp_l, g_lb)) return rc;
+        if (newton_ok && !g_lb.empty()) {
+            HIP_TRY(ctx, hipMemcpy(rstat.data(), r_st.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+            if (int rc = refit_group(sp_n, newton_retry(g_lb, rstat))) return rc;
+        }
+        if (int rc = refit_group(sp_n, g_nw)) return rc;
+    }
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    HIP_TRY(ctx, hipMemcpy(fo.theta, r_th.p, 8 * (size_t)N * stride, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(fo.y_scale, r_ys.p, 8 * (size_t)N, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(fo.fval, r_fv.p, 8 * (size_t)N, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(fo.status, r_st.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(fo.n_iter, r_it.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(fo.n_eval, r_ev.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(fo.grid, r_gr.p, sizeof(tsf_grid_info) * (size_t)n_grids, hipMemcpyDeviceToHost));
     return 0;
 }

@@ -913,3 +913,181 @@ def last_cv_grids(ctx=None):
     g, n = ctypes.c_int64(), ctypes.c_int32()
     ctx.check(_lib.load().tsf_last_cv_grids(ctx.handle, ctypes.byref(g), ctypes.byref(n)))
     return int(g.value), int(n.value)
+
+
+# ---- prior-scale tuning ----------------------------------------------------------------------------
+
+TUNE_AXES = ('changepoint_prior_scale', 'seasonality_prior_scale', 'holidays_prior_scale')
+
+
+def _n_holiday_columns(spec):
+    from . import features
+    return len(features.holiday_columns(spec.holidays)[0]) if spec.holidays else 0
+
+
+def tune_candidates(spec, grid):
+    """The candidates of a grid over TUNE_AXES (dict axis -> list of scales): itertools.product of the axes in
+    TUNE_AXES order, the first varying slowest.  seasonality_prior_scale replaces the prior scale of every seasonality;
+    holidays_prior_scale that of the holiday columns of `extra` (the first len(features.holiday_columns(spec.holidays)
+    [0]) entries) -- regressors keep their own scale.  -> (candidates [ModelSpec], params {axis: float64 [C]})."""
+    import itertools
+    if not isinstance(grid, dict) or not grid:
+        raise ValueError('grid must be a non-empty dict over %s' % (TUNE_AXES,))
+    unknown = sorted(set(grid) - set(TUNE_AXES))
+    if unknown:
+        raise ValueError('unknown grid axes %s (tunable: %s)' % (unknown, TUNE_AXES))
+    n_hol = _n_holiday_columns(spec)
+    if 'seasonality_prior_scale' in grid and not spec.seasonalities:
+        raise ValueError('grid over seasonality_prior_scale, but the model has no seasonality')
+    if 'holidays_prior_scale' in grid and n_hol == 0:
+        raise ValueError('grid over holidays_prior_scale, but the model has no holidays')
+    axes = [k for k in TUNE_AXES if k in grid]
+    values = []
+    for k in axes:
+        v = np.asarray(grid[k], dtype=np.float64).ravel()
+        if v.size == 0:
+            raise ValueError('grid axis %s is empty' % k)
+        if not (np.isfinite(v).all() and (v > 0).all()):
+            raise ValueError('grid axis %s: prior scales must be finite and > 0' % k)
+        values.append(v)
+    cands, params = [], {k: [] for k in axes}
+    for combo in itertools.product(*values):
+        d = spec.to_dict()
+        d['seasonalities'] = [dict(s) for s in spec.seasonalities]
+        d['extra'] = [dict(e) for e in spec.extra]
+        for e in d['extra'][n_hol:]:          # (a regressor without its own scale would follow holidays_prior_scale)
+            e.setdefault('prior_scale', spec.holidays_prior_scale)
+        for k, v in zip(axes, combo):
+            v = float(v)
+            d[k] = v
+            params[k].append(v)
+            if k == 'seasonality_prior_scale':
+                for s in d['seasonalities']:
+                    s['prior_scale'] = v
+            elif k == 'holidays_prior_scale':
+                for e in d['extra'][:n_hol]:
+                    e['prior_scale'] = v
+        cands.append(ModelSpec.from_dict(d))
+    return cands, {k: np.array(v) for k, v in params.items()}
+
+
+def _effective_scales(spec, cands):
+    """{axis: [C]} the scale each candidate gives the axis's columns (the first such column; NaN where it has none)."""
+    n_hol = _n_holiday_columns(spec)
+    cs = [c.to_c() for c in cands]
+    return {'changepoint_prior_scale': np.array([c.changepoint_prior_scale for c in cs]),
+            'seasonality_prior_scale': np.array([c.seas_prior_scale[0] if c.n_seas else np.nan for c in cs]),
+            'holidays_prior_scale': np.array([c.extra_prior_scale[0] if n_hol else np.nan for c in cs])}
+
+
+class TuneResult(object):
+    """What tune returns (include/tsf.h tsf_tune).
+
+    candidates [C] (ModelSpec), params {axis: [C]} (the grid value of each axis per candidate; with explicit candidates
+    the scale each gives the axis's columns), metric; score / cand_status [N][C]; best / status [N] (best -1: no
+    choice, status the plan's TSF_CV_* or TUNE_NO_SCORE); fit: FitResult of the refit (None without)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def spec_of(self, n):
+        """The ModelSpec series n is refitted with: its choice, or the base spec where it has none."""
+        b = int(self.best[n])
+        return self.candidates[b] if b >= 0 else self.spec
+
+    def frame(self):
+        """One row per series: series, candidate (-1: none), status, the scales in effect (TUNE_AXES) and the score of
+        the choice (NaN without one)."""
+        import pandas as pd
+        N = len(self.best)
+        ok = self.best >= 0
+        eff = _effective_scales(self.spec, list(self.candidates) + [self.spec])
+        pick = np.where(ok, self.best, len(self.candidates))
+        d = {'series': np.arange(N, dtype=np.int64), 'candidate': self.best.astype(np.int64),
+             'status': self.status.astype(np.int64)}
+        for k in TUNE_AXES:
+            d[k] = eff[k][pick]
+        d['metric'] = np.full(N, self.metric, dtype=object)
+        d['score'] = np.where(ok, self.score[np.arange(N), np.maximum(self.best, 0)], np.nan)
+        return pd.DataFrame(d)
+
+
+def tune(spec, ds_ns, y, horizon, period=None, initial=None, offsets=None, floor=None, cap=None, extra=None,
+         grid=None, candidates=None, metric='rmse', refit=True, ctx=None, devices=None):
+    """Prophet's hyperparameter recipe for every series at once (include/tsf.h tsf_tune): cross_validate with each
+    candidate's prior scales, score each series by `metric` over all its holdout rows (performance_metrics with
+    rolling_window=1), keep the first minimum, and (refit) fit every series on its full history with its choice (the
+    base spec where it has none).  Input as cross_validate.  grid: {axis: [scales]} over TUNE_AXES (tune_candidates),
+    or candidates: explicit ModelSpecs that differ from spec in their prior scales only.  metric: mse / rmse / mae /
+    mape.  devices: several GPUs, split by series.  Returns a TuneResult."""
+    if (grid is None) == (candidates is None):
+        raise ValueError('give exactly one of grid and candidates')
+    if grid is not None:
+        cands, params = tune_candidates(spec, grid)
+    else:
+        cands = list(candidates)
+        if not cands:
+            raise ValueError('candidates is empty')
+        params = _effective_scales(spec, cands)
+    if len(cands) > _lib.TUNE_MAX_CAND:
+        raise ValueError('at most %d candidates' % _lib.TUNE_MAX_CAND)
+    if metric not in _lib.TUNE_METRICS:
+        raise ValueError('metric must be one of %s' % sorted(_lib.TUNE_METRICS))
+    ds_ns, y, offsets, N, T = _cv_panel(ds_ns, y, offsets)
+    fl = _opt_f64(floor, N, 'floor')
+    cp = _opt_f64(cap, N, 'cap')
+    C = len(cands)
+
+    def result(score, cst, best, sst, fit):
+        return TuneResult(spec=spec, candidates=cands, params=params, metric=metric, score=score, cand_status=cst,
+                          best=best, status=sst, fit=fit)
+    devs = None if ctx is not None else resolve_devices(devices)
+    if devs and N >= 2 * MIN_SERIES_PER_DEVICE:
+        parts = min(len(devs), N // MIN_SERIES_PER_DEVICE)
+        lens = np.full(N, T, np.int64) if offsets is None else np.diff(offsets)
+        cuts = _cuts(lens, parts)
+        ex = None if extra is None else np.asarray(extra)
+
+        def one(c, a, b):
+            kw = dict(candidates=cands, metric=metric, refit=refit, ctx=c)
+            if offsets is None:
+                return tune(spec, ds_ns, y[a:b], horizon, period, initial, None, None if fl is None else fl[a:b],
+                            None if cp is None else cp[a:b], extra, **kw)
+            r0, r1 = int(offsets[a]), int(offsets[b])
+            return tune(spec, ds_ns[r0:r1], y[r0:r1], horizon, period, initial, offsets[a:b + 1] - r0,
+                        None if fl is None else fl[a:b], None if cp is None else cp[a:b],
+                        None if ex is None else ex[:, r0:r1], **kw)
+        blocks = [(c, int(a), int(b)) for c, a, b in zip(_contexts(devs[:parts]), cuts[:-1], cuts[1:]) if b > a]
+        pr = _run_blocks(one, blocks)
+        cat = lambda k: np.concatenate([getattr(p, k) for p in pr])     # noqa: E731
+        fit = _merge_fits(spec, [p.fit for p in pr], shared_grid=offsets is None) if refit else None
+        return result(cat('score'), cat('cand_status'), cat('best'), cat('status'), fit)
+    ctx = ctx or get_context()
+    L = _lib.load()
+    ex = None
+    if spec.extra:
+        ex = np.ascontiguousarray(extra, dtype=np.float64)
+        if ex.shape != (len(spec.extra), len(ds_ns)):
+            raise ValueError('extra must be [n_extra][len(ds)]')
+    base = spec.to_c()
+    carr = (_lib.TsfSpec * C)(*[c.to_c() for c in cands])
+    score = np.zeros((N, C))
+    cst = np.zeros((N, C), np.int32)
+    best = np.zeros(N, np.int32)
+    sst = np.zeros(N, np.int32)
+    fout, farrs = _alloc_out(N, spec.theta_stride, 1 if offsets is None else N) if refit else (_lib.TsfFitOut(), None)
+    out = _lib.TsfTuneOut(score.ctypes.data, cst.ctypes.data, best.ctypes.data, sst.ctypes.data, fout)
+    a = _cv_args(horizon, period, initial, 1.0)
+    rc = L.tsf_tune(ctx.handle, ctypes.byref(base), carr, C, N, T, _lib._ptr(offsets), ds_ns.ctypes.data, y.ctypes.data,
+                    _lib.y_dtype_code(y), _lib._ptr(fl), _lib._ptr(cp), _lib._ptr(ex), ctypes.byref(a),
+                    _lib.TUNE_METRICS[metric], int(bool(refit)), ctypes.byref(out))
+    ctx.check(rc)
+    return result(score, cst, best, sst, FitResult(spec, *farrs) if refit else None)
+
+
+def last_tune_counts(ctx=None):
+    """tsf_last_tune_counts (include/tsf_dev.h): (fold panels cut, fit launches) of the context's last tune call."""
+    ctx = ctx or get_context()
+    e, f = ctypes.c_int32(), ctypes.c_int32()
+    ctx.check(_lib.load().tsf_last_tune_counts(ctx.handle, ctypes.byref(e), ctypes.byref(f)))
+    return int(e.value), int(f.value)

@@ -12,7 +12,16 @@ writes one parquet of metric rows
 
 Settings under `cv` (durations as pandas Timedelta strings): horizon (required), period (default horizon / 2),
 initial (default 3 * horizon), rolling_window (0.1), intervals (false), uncertainty_samples (1000), interval_width
-(0.8), seed (0).  A series the plan or a fit fails (include/tsf.h TSF_CV_*) has no rows and is reported on stdout."""
+(0.8), seed (0).  A series the plan or a fit fails (include/tsf.h TSF_CV_*) has no rows and is reported on stdout.
+
+An optional `tune` section chooses every series' prior scales by cross-validation (include/tsf.h tsf_tune, with the
+`cv` cutoffs): axes changepoint_prior_scale / seasonality_prior_scale / holidays_prior_scale as lists, metric (rmse).
+An axis a model bucket has no columns for (no seasonality, no holidays) is left out of that bucket's grid and reported
+as null.  It writes io.tuning, one row per series with a choice:
+
+    series_id, dim_id, changepoint_prior_scale, seasonality_prior_scale, holidays_prior_scale, metric, score
+
+Series without a choice are reported on stdout.  Without `tune` the job does what it did before."""
 import os
 import time
 
@@ -42,11 +51,34 @@ def cv_settings(config):
                 interval_width=float(c.get('interval_width', 0.8)), seed=int(c.get('seed', 0)))
 
 
-def validate_panel(config, panel):
-    """-> (metrics frame, fold frame) for a PackedPanel."""
-    cvs = cv_settings(config)
+def tune_settings(config):
+    """The `tune` section -> (grid {axis: [scales]}, metric), or None without one."""
+    t = config.get('tune')
+    if t is None:
+        return None
+    t = dict(t)
+    metric = str(t.pop('metric', 'rmse')).lower()
+    if metric not in _lib.TUNE_METRICS:
+        raise ValueError('tune.metric must be one of %s' % sorted(_lib.TUNE_METRICS))
+    unknown = sorted(set(t) - set(fc.TUNE_AXES))
+    if unknown:
+        raise ValueError('unknown tune keys %s (axes: %s, metric)' % (unknown, fc.TUNE_AXES))
+    grid = {}
+    for k in fc.TUNE_AXES:
+        if k in t:
+            v = t[k] if isinstance(t[k], (list, tuple)) else [t[k]]
+            if not v:
+                raise ValueError('tune.%s is empty' % k)
+            grid[k] = [float(x) for x in v]
+    if not grid:
+        raise ValueError('tune needs at least one of %s' % (fc.TUNE_AXES,))
+    return grid, metric
+
+
+def _buckets(config, panel):
+    """Per model bucket of the modeler: (spec, members, offsets, ds, y, extra, cap of the members) -- the bucket's
+    series as one ragged panel."""
     kw = pm._prophet_kwargs(config)
-    floor = float(config['model']['floor'])
     cap = pk.per_series_stats(panel)[2] * config['model']['cap_multiplier']
     algo = str(kw.get('algorithm', 'auto')).lower()
     algos = {'auto': _lib.ALGO_AUTO, 'lbfgs': _lib.ALGO_LBFGS, 'newton': _lib.ALGO_NEWTON}
@@ -54,11 +86,6 @@ def validate_panel(config, panel):
         raise ValueError("algorithm must be 'auto', 'lbfgs' or 'newton'")
     opts = pm._spec_opts(kw)
     buckets, _, hol_days, hol_extra = pm.bucket_models(panel, kw)
-    sids = panel.keys['series_id'].to_numpy().astype(np.int64)
-    dids = panel.keys['dim_id'].to_numpy().astype(np.int64)
-    # the interval streams of a series are keyed by (series_id, dim_id): the same intervals whatever else is in the run
-    key = (sids << 32) | (dids & 0xffffffff)
-    metrics, folds = [], []
     for seas, members, model in buckets:
         spec = fc.ModelSpec(algorithm=algos[algo], **model, **opts)
         lens = panel.lengths[members]
@@ -66,7 +93,25 @@ def validate_panel(config, panel):
         idx = np.repeat(panel.offsets[members] - off[:-1], lens) + np.arange(off[-1], dtype=np.int64)
         ds_r, y_r = panel.ds_ns[idx], panel.y[idx]
         ex = features.holiday_matrix(ds_r, hol_days) if hol_extra else (np.zeros((1, len(ds_r))) if not seas else None)
-        cv = fc.cross_validate(spec, ds_r, y_r, offsets=off, floor=np.full(len(members), floor), cap=cap[members],
+        yield spec, members, off, ds_r, y_r, ex, cap[members]
+
+
+def _series_keys(panel):
+    sids = panel.keys['series_id'].to_numpy().astype(np.int64)
+    dids = panel.keys['dim_id'].to_numpy().astype(np.int64)
+    return sids, dids
+
+
+def validate_panel(config, panel):
+    """-> (metrics frame, fold frame) for a PackedPanel."""
+    cvs = cv_settings(config)
+    floor = float(config['model']['floor'])
+    sids, dids = _series_keys(panel)
+    # the interval streams of a series are keyed by (series_id, dim_id): the same intervals whatever else is in the run
+    key = (sids << 32) | (dids & 0xffffffff)
+    metrics, folds = [], []
+    for spec, members, off, ds_r, y_r, ex, cap_m in _buckets(config, panel):
+        cv = fc.cross_validate(spec, ds_r, y_r, offsets=off, floor=np.full(len(members), floor), cap=cap_m,
                                extra=ex, series_key=key[members], devices=config.get('devices'), **cvs)
         for i in np.flatnonzero(cv.status != 0):
             n = members[i]
@@ -92,6 +137,40 @@ def validate_panel(config, panel):
     return m.reset_index(drop=True), f.reset_index(drop=True)
 
 
+def tune_panel(config, panel):
+    """-> the tuning frame (one row per series with a choice) for a PackedPanel; series without one on stdout."""
+    grid, metric = tune_settings(config)
+    cvs = cv_settings(config)
+    floor = float(config['model']['floor'])
+    sids, dids = _series_keys(panel)
+    out = []
+    for spec, members, off, ds_r, y_r, ex, cap_m in _buckets(config, panel):
+        g = dict(grid)
+        if not spec.seasonalities:
+            g.pop('seasonality_prior_scale', None)
+        if not spec.holidays:
+            g.pop('holidays_prior_scale', None)
+        # (no axis left for this bucket: its own spec is the one candidate)
+        r = fc.tune(spec, ds_r, y_r, cvs['horizon'], cvs['period'], cvs['initial'], offsets=off,
+                    floor=np.full(len(members), floor), cap=cap_m, extra=ex, grid=g or None,
+                    candidates=None if g else [spec], metric=metric, refit=False, devices=config.get('devices'))
+        for i in np.flatnonzero(r.best < 0):
+            n = members[i]
+            why = 'no candidate scored' if r.status[i] == _lib.TUNE_NO_SCORE else \
+                CV_STATUS_NAMES.get(int(r.status[i]), r.status[i])
+            print(f"Tuning skipped for series_id: {sids[n]}, dim_id: {dids[n]}: {why}")
+        ok = np.flatnonzero(r.best >= 0)
+        b = r.best[ok]
+        fr = {'series_id': sids[members[ok]].astype('int32'), 'dim_id': dids[members[ok]].astype('int32')}
+        for k in fc.TUNE_AXES:
+            fr[k] = r.params[k][b] if k in g else np.full(len(ok), np.nan)
+        fr['metric'] = np.full(len(ok), metric, dtype=object)
+        fr['score'] = r.score[ok, b]
+        out.append(pd.DataFrame(fr))
+    t = pd.concat(out, ignore_index=True).sort_values(['series_id', 'dim_id'], kind='stable')
+    return t.reset_index(drop=True)
+
+
 class ProphetValidator(object):
     """Cross-validate the models the modeler would fit (config: the modeler's keys + `cv` + io.metrics [+ io.folds])."""
 
@@ -107,11 +186,16 @@ class ProphetValidator(object):
         if (panel.lengths < 2).any() or panel.dropped_keys:
             raise ValueError('Dataframe has less than 2 non-NaN rows.')
         metrics, folds = validate_panel(config, panel)
+        tuning = tune_panel(config, panel) if config.get('tune') is not None else None
         os.makedirs(config['io']['metrics'], exist_ok=True)
         metrics.to_parquet(os.path.join(config['io']['metrics'], 'part-00000.parquet'), index=False)
         if config['io'].get('folds'):
             os.makedirs(config['io']['folds'], exist_ok=True)
             folds.to_parquet(os.path.join(config['io']['folds'], 'part-00000.parquet'), index=False)
+        if tuning is not None:
+            os.makedirs(config['io']['tuning'], exist_ok=True)
+            tuning.to_parquet(os.path.join(config['io']['tuning'], 'part-00000.parquet'), index=False)
+            print(f"Tuned {len(tuning)} of {panel.N} series")
         print(f"Cross-validated {panel.N} series ({len(folds)} holdout rows, {len(metrics)} metric rows) in "
               f"{time.time() - t0}")
         return (metrics, folds) if return_frame else None
