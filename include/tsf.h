@@ -99,7 +99,9 @@ enum {
     TSF_ST_EVAL_LIMIT = -3,    /* > 64*max_iter+1024 evaluations: the line search never settled
                                   (guard; treated like LSFAIL) */
     TSF_ST_TOO_FEW = -10,      /* < 2 rows (fbprophet raises ValueError) */
-    TSF_ST_CAP = -11           /* cap <= floor (fbprophet raises ValueError) */
+    TSF_ST_CAP = -11,          /* cap <= floor (fbprophet raises ValueError) */
+    TSF_ST_CHANGEPOINT = -12   /* a specified changepoint outside [min ds, max ds] of the series (fbprophet raises
+                                  ValueError('Changepoints must fall within training data.')) */
 };
 
 /* Model + optimiser settings shared by every series of a call.  Defaults = fbprophet 0.5
@@ -151,7 +153,36 @@ typedef struct {
     int32_t converge;                       /* TSF_CONVERGE_STAN */
     int32_t map_max_iter;                   /* 10000: iterations of the continuation (converge = MAP) */
     double map_tol;                         /* 1e-7: its KKT tolerance */
+    /* Specified changepoints: see "changepoints at given dates" below. */
+    int32_t changepoints_specified;         /* 0 (default): the automatic rule */
+    int64_t changepoint_ns[TSF_MAX_S];      /* n_changepoints dates, ns since the epoch, strictly ascending */
 } tsf_spec;
+
+/* ---- changepoints at given dates ----------------------------------------------------------------
+ * Replaces the `changepoints=[...]` argument of fbprophet's constructor (`Prophet(changepoints=...)`, set_changepoints'
+ * `self.specified_changepoints` branch): the trend may change slope at dates the caller knows -- a price change, a
+ * migration -- instead of at n_changepoints row timestamps spread over the first changepoint_range of the history.
+ * The reference job never passes the argument (prophet_modeler.py:65 uses the default); it is here because users of
+ * the model expect it.
+ *
+ * changepoints_specified = 1: n_changepoints is the number of dates, in [0, TSF_MAX_S], and changepoint_range is
+ * ignored, as in fbprophet.  Per grid t_change[j] = (double)(changepoint_ns[j] - start_ns) / (double)t_scale_ns -- the
+ * expression that scales a row's timestamp --, S = n_changepoints, and a row belongs to the segments of the dates at or
+ * before it; dates may fall between rows.  No dates: the dummy changepoint at t = 0, as for the automatic rule with
+ * n_changepoints = 0.  The theta layout does not change.  Every fit, evaluation, prediction, interval and component
+ * entry point reads changepoints from the grid alone, so all of them follow.
+ *   - A series with a date < min ds or > max ds gets status TSF_ST_CHANGEPOINT: theta is its initial value and no
+ *     optimiser runs (as TSF_ST_CAP / TSF_ST_TOO_FEW).  On an aligned panel the one grid decides for every series.  A
+ *     date equal to min ds (t_change = 0) or max ds is legal.
+ *   - tsf_cross_validate / tsf_tune: fold c of a series fits with the leading dates <= its cutoff -- what fbprophet's
+ *     diagnostics.prophet_copy(m, cutoff) keeps --, the deltas of the others are 0; a kept date after the fold's last
+ *     history row (irregular timestamps only) makes the fold TSF_ST_CHANGEPOINT and the series TSF_CV_FIT_FAILED.
+ *     tsf_tune's candidates must carry base's dates.
+ * Deviations, on purpose: dates that are not strictly ascending are API misuse (return < 0 before any launch) where
+ * fbprophet sorts them and tolerates duplicates, which give two identical trend columns; TSF_RK_MFMA is rejected
+ * with specified dates (its launch plan bounds the changepoint rows per chunk by the automatic spacing).
+ * These semantics are restated from recall of fbprophet 0.5; parity with fbprophet itself is unpinned, as everywhere
+ * in this library (the tests compare with oracle/fbprophet_restated.py). */
 
 /* What setup derives from one timestamp vector ("grid").  One per call for aligned panels,
  * one per series for ragged panels. */

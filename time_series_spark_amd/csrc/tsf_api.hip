@@ -12,9 +12,11 @@
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <mutex>
 #include <string>
 #include <thread>
+#include <utility>
 #include <atomic>
 #include <vector>
 
@@ -203,7 +205,12 @@ static int build_devspec(tsf_ctx *ctx, const tsf_spec *s, DevSpec *d, int *mode_
     if (s->n_seas < 0 || s->n_seas > TSF_MAX_SEAS || s->n_extra < 0 || s->n_extra > TSF_MAX_EXTRA)
         return fail(ctx, "too many seasonalities / extra columns");
     if (s->n_changepoints < 0 || s->n_changepoints > TSF_MAX_S) return fail(ctx, "n_changepoints out of range");
-    if (!(s->changepoint_range >= 0.0 && s->changepoint_range <= 1.0)) return fail(ctx, "changepoint_range must be in [0,1]");
+    if (s->changepoints_specified != 0 && s->changepoints_specified != 1) return fail(ctx, "changepoints_specified must be 0 or 1");
+    // (fbprophet ignores changepoint_range when the dates are given)
+    if (!s->changepoints_specified && !(s->changepoint_range >= 0.0 && s->changepoint_range <= 1.0)) return fail(ctx, "changepoint_range must be in [0,1]");
+    if (s->changepoints_specified)
+        for (int j = 1; j < s->n_changepoints; ++j)
+            if (s->changepoint_ns[j] <= s->changepoint_ns[j - 1]) return fail(ctx, "changepoint_ns must be strictly ascending");
     if (!(s->changepoint_prior_scale > 0.0)) return fail(ctx, "changepoint_prior_scale must be > 0");
     if (s->history < 1 || s->history > MAXH) return fail(ctx, "history must be in [1,8]");
     if (s->eval_form < TSF_EVAL_AUTO || s->eval_form > TSF_EVAL_QUADRATIC) return fail(ctx, "bad eval_form");
@@ -254,6 +261,11 @@ static int build_devspec(tsf_ctx *ctx, const tsf_spec *s, DevSpec *d, int *mode_
         if (ok) d->harm = harm_code(s->seas_order[0], s->n_seas > 1 ? s->seas_order[1] : 0, s->n_seas > 2 ? s->seas_order[2] : 0);
     }
     d->cp_range = s->changepoint_range; d->tau = s->changepoint_prior_scale;
+    d->cp_spec = s->changepoints_specified;
+    if (d->cp_spec) {
+        d->cp_range = 0.0;
+        for (int j = 0; j < s->n_changepoints; ++j) d->cp_ns[j] = s->changepoint_ns[j];
+    }
     d->init_alpha = s->init_alpha; d->tol_obj = s->tol_obj; d->tol_rel_obj = s->tol_rel_obj;
     d->tol_grad = s->tol_grad; d->tol_rel_grad = s->tol_rel_grad; d->tol_param = s->tol_param;
     *mode_out = m;
@@ -419,7 +431,7 @@ static int run_fit(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int aligned, i
                    double *grad_out, hipStream_t st, int64_t lat_base = 0, int64_t lat_step = 0,
                    int64_t lat_U = 0, const double *theta_ref = nullptr,
                    const int32_t *grid_of = nullptr, const int64_t *grid_rows = nullptr, int64_t n_distinct = 0,
-                   const int32_t *grid_order = nullptr)
+                   const int32_t *grid_order = nullptr, const int32_t *grid_keep = nullptr)
 {
     if (!ctx) return -1;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -528,6 +540,10 @@ static int run_fit(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int aligned, i
     // which has no rounds to synchronise, is ahead on every panel measured (100 000 x 730, iteration
     // cap 150: 271 vs 326 ms; reference settings with their stragglers: 1.27 vs 1.62 s).  The
     // matrix-core kernel stays available (TSF_RK_MFMA), bit-identical.
+    // Specified changepoints: rejected -- per_chunk below bounds the changepoint rows of a chunk by the automatic rule's
+    // spacing, which dates at arbitrary places do not have.
+    if (spec->residual_kernel == TSF_RK_MFMA && hs.cp_spec && theta_in == nullptr)
+        return fail(ctx, "residual_kernel MFMA does not take specified changepoints (changepoints_specified = 1)");
     const bool want_mfma = spec->residual_kernel == TSF_RK_MFMA;
     if (aligned && !quad && !newton && theta_in == nullptr && hs.KP <= 28 && want_mfma) {
         const int hist_rows = (int)floor((double)Tm * hs.cp_range);
@@ -651,7 +667,7 @@ static int run_fit(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int aligned, i
                        (int)n_grids, aligned ? nullptr : offsets, T, ds, extra,
                        aligned ? (int64_t)T : total_rows, NTmax, gtab, tw, cw, Xw,
                        (int32_t *)(ws + l.uw), lat_base, lat_U > 0 ? lat_step : (int64_t)0, grid_rows,
-                       (bw_ns && lat_U == 0) ? (double *)(ws + l.Bw) : (double *)nullptr);
+                       (bw_ns && lat_U == 0) ? (double *)(ws + l.Bw) : (double *)nullptr, grid_keep);
     HIP_TRY(ctx, hipGetLastError());
     if (sparse_try) {
         int *sp_bad = (int *)(ws + l.counter) + 8;
@@ -1988,6 +2004,7 @@ struct CvCall {
     std::vector<int32_t> f_series, f_c;
     std::vector<int64_t> f_cut, f_hist, f_hold, f_row0;
     std::vector<double> f_floor, f_cap;
+    std::vector<int32_t> f_keep;        // specified changepoints: the leading dates <= the fold's cutoff (else empty)
     int32_t Hmax = 1, C = 0;
     DevBuf d_ds, d_y, d_off, d_ex, d_fl, d_cap, d_key, d_fser, d_fc, d_fhist, d_fhold;
     CvPanel pn;
@@ -2004,6 +2021,7 @@ struct CvViews {
     const int64_t *hist;        // host [V]
     const int32_t *cls;         // host [V]: calendar class known from the construction, or null (classes by hashing)
     int32_t n_cls;
+    const int32_t *keep;        // host [V]: specified changepoints the view's fit keeps (CvCall::f_keep), or null (all)
 };
 
 // The panel of one fit launch: views gf[0 .. G), cut on the device, and their calendar classes.
@@ -2012,6 +2030,7 @@ struct CvGroup {
     int64_t G = 0, rows = 0, n_distinct = 0;
     int32_t maxT = 0;
     DevBuf d_gf, d_goff, d_gds, d_gy, d_gex, d_gfl, d_gcap, d_gof, d_grows, d_gord;
+    DevBuf d_gkeep;             // [grids of the launch] CvViews::keep per grid (setup_grid_kernel grid_keep), where given
 };
 
 struct CvHoldout {              // the holdout rows of every fold as one padded future panel [F][Hmax]
@@ -2044,6 +2063,8 @@ static void cv_plan_call(int64_t N, int32_t T, const int64_t *offsets, const int
     S->f_series.resize((size_t)F); S->f_c.resize((size_t)F);
     S->f_cut.resize((size_t)F); S->f_hist.resize((size_t)F); S->f_hold.resize((size_t)F); S->f_row0.resize((size_t)F);
     S->f_floor.resize(floor_ ? (size_t)F : 0); S->f_cap.resize(cap ? (size_t)F : 0);
+    const bool cp_spec = spec->changepoints_specified == 1 && spec->n_changepoints >= 0 && spec->n_changepoints <= TSF_MAX_S;
+    S->f_keep.resize(cp_spec ? (size_t)F : 0);
     for (int64_t n = 0; n < N; ++n) {
         int64_t r = S->rows_off[(size_t)n];
         for (size_t c = 0; c < S->plan[(size_t)n].size(); ++c) {
@@ -2053,6 +2074,12 @@ static void cv_plan_call(int64_t N, int32_t T, const int64_t *offsets, const int
             S->f_cut[(size_t)f] = x.cutoff; S->f_hist[(size_t)f] = x.hist; S->f_hold[(size_t)f] = x.hold; S->f_row0[(size_t)f] = r;
             if (floor_) S->f_floor[(size_t)f] = floor_[n];
             if (cap) S->f_cap[(size_t)f] = cap[n];
+            if (cp_spec) {
+                // what prophet_copy(m, cutoff) keeps: changepoints[changepoints <= cutoff], a prefix of the sorted list
+                int32_t k = 0;
+                while (k < spec->n_changepoints && spec->changepoint_ns[k] <= x.cutoff) ++k;
+                S->f_keep[(size_t)f] = k;
+            }
             r += x.hold;
             if (x.hold > S->Hmax) S->Hmax = (int32_t)x.hold;
         }
@@ -2107,7 +2134,8 @@ static int cv_upload(tsf_ctx *ctx, const void *y, const double *floor_, const do
 
 static CvViews cv_fold_views(CvCall &S)
 {
-    return CvViews{S.d_fser.as<int32_t>(), S.f_series.data(), S.f_hist.data(), S.aligned ? S.f_c.data() : nullptr, S.C};
+    return CvViews{S.d_fser.as<int32_t>(), S.f_series.data(), S.f_hist.data(), S.aligned ? S.f_c.data() : nullptr, S.C,
+                   S.f_keep.empty() ? nullptr : S.f_keep.data()};
 }
 
 // the panel of one fit launch over the views gf (cv_expand_kernel) and its calendar classes (same rule as
@@ -2157,6 +2185,19 @@ static int cv_expand(tsf_ctx *ctx, CvCall &S, const CvViews &V, const std::vecto
             }
             calendar_classes(S.ds, vstart.data(), vlen.data(), G, &gof, &reps);
         }
+        if (V.keep) {
+            // views that share a timestamp vector share a grid only where they keep the same number of dates (two series
+            // of one calendar whose cutoffs differ): split the classes that do not
+            std::map<std::pair<int32_t, int32_t>, int32_t> ids;
+            std::vector<int64_t> reps2;
+            for (int64_t g = 0; g < G; ++g) {
+                const auto key = std::make_pair(gof[(size_t)g], V.keep[(size_t)gf[(size_t)g]]);
+                auto it = ids.find(key);
+                if (it == ids.end()) { it = ids.emplace(key, (int32_t)reps2.size()).first; reps2.push_back(g); }
+                gof[(size_t)g] = it->second;
+            }
+            reps.swap(reps2);
+        }
         n_distinct = (int64_t)reps.size();
         if (n_distinct < G) {
             std::vector<int64_t> grows;
@@ -2166,9 +2207,19 @@ static int cv_expand(tsf_ctx *ctx, CvCall &S, const CvViews &V, const std::vecto
             HIP_TRY(ctx, E->d_gof.alloc(4 * (size_t)G)); HIP_TRY(ctx, hipMemcpy(E->d_gof.p, gof.data(), 4 * (size_t)G, hipMemcpyHostToDevice));
             HIP_TRY(ctx, E->d_grows.alloc(8 * grows.size())); HIP_TRY(ctx, hipMemcpy(E->d_grows.p, grows.data(), 8 * grows.size(), hipMemcpyHostToDevice));
             HIP_TRY(ctx, E->d_gord.alloc(4 * (size_t)G)); HIP_TRY(ctx, hipMemcpy(E->d_gord.p, ord.data(), 4 * (size_t)G, hipMemcpyHostToDevice));
+            if (V.keep) {
+                std::vector<int32_t> kp;
+                for (int64_t r : reps) kp.push_back(V.keep[(size_t)gf[(size_t)r]]);
+                HIP_TRY(ctx, E->d_gkeep.alloc(4 * kp.size())); HIP_TRY(ctx, hipMemcpy(E->d_gkeep.p, kp.data(), 4 * kp.size(), hipMemcpyHostToDevice));
+            }
         } else {
             n_distinct = 0;
         }
+    }
+    if (V.keep && n_distinct == 0) {        // a grid per view
+        std::vector<int32_t> kp((size_t)G);
+        for (int64_t g = 0; g < G; ++g) kp[(size_t)g] = V.keep[(size_t)gf[(size_t)g]];
+        HIP_TRY(ctx, E->d_gkeep.alloc(4 * (size_t)G)); HIP_TRY(ctx, hipMemcpy(E->d_gkeep.p, kp.data(), 4 * (size_t)G, hipMemcpyHostToDevice));
     }
     E->n_distinct = n_distinct;
     return 0;
@@ -2196,7 +2247,7 @@ static int cv_fit(tsf_ctx *ctx, CvCall &S, CvGroup &E, const tsf_spec &gs, const
                      S.has_floor ? E.d_gfl.as<double>() : nullptr, S.has_cap ? E.d_gcap.as<double>() : nullptr,
                      S.n_extra > 0 ? E.d_gex.as<double>() : nullptr, &go, nullptr, nullptr, nullptr, 0, 0, 0, nullptr,
                      nd > 0 ? E.d_gof.as<int32_t>() : nullptr, nd > 0 ? E.d_grows.as<int64_t>() : nullptr, nd,
-                     nd > 0 ? E.d_gord.as<int32_t>() : nullptr);
+                     nd > 0 ? E.d_gord.as<int32_t>() : nullptr, E.d_gkeep.p ? E.d_gkeep.as<int32_t>() : nullptr);
     if (rc) return rc;
     *n_grids += ctx->last_n_grids;
     *n_launches += 1;
@@ -2402,8 +2453,11 @@ extern "C" int tsf_last_tune_counts(const tsf_ctx *ctx, int32_t *expand_launches
 static bool same_but_prior_scales(const tsf_spec &a, const tsf_spec &b)
 {
     if (a.growth != b.growth || a.n_changepoints != b.n_changepoints || a.changepoint_range != b.changepoint_range ||
-        a.n_seas != b.n_seas || a.n_extra != b.n_extra)
+        a.n_seas != b.n_seas || a.n_extra != b.n_extra || a.changepoints_specified != b.changepoints_specified)
         return false;
+    if (a.changepoints_specified && a.n_changepoints >= 0 && a.n_changepoints <= TSF_MAX_S)
+        for (int j = 0; j < a.n_changepoints; ++j)
+            if (a.changepoint_ns[j] != b.changepoint_ns[j]) return false;
     if (a.n_seas < 0 || a.n_seas > TSF_MAX_SEAS || a.n_extra < 0 || a.n_extra > TSF_MAX_EXTRA) return false;
     for (int i = 0; i < a.n_seas; ++i)
         if (a.seas_period[i] != b.seas_period[i] || a.seas_order[i] != b.seas_order[i] || a.seas_mode[i] != b.seas_mode[i])
@@ -2553,7 +2607,7 @@ extern "C" int tsf_tune(tsf_ctx *ctx, const tsf_spec *base, const tsf_spec *cand
     for (int64_t n = 0; n < N; ++n) { ident[(size_t)n] = (int32_t)n; len[(size_t)n] = aligned ? T : offsets[n + 1] - offsets[n]; }
     DevBuf d_ident;
     if (!aligned) { HIP_TRY(ctx, d_ident.alloc(4 * (size_t)N)); HIP_TRY(ctx, hipMemcpy(d_ident.p, ident.data(), 4 * (size_t)N, hipMemcpyHostToDevice)); }
-    const CvViews whole{d_ident.as<int32_t>(), ident.data(), len.data(), nullptr, 0};
+    const CvViews whole{d_ident.as<int32_t>(), ident.data(), len.data(), nullptr, 0, nullptr};
     // one fit launch over the series sel with spec gs: aligned, the series' rows gathered into a [G][T] panel
     // (tune_gather_kernel); ragged, their full histories as views (cv_expand_kernel)
     auto refit_group = [&](const tsf_spec &gs, const std::vector<int32_t> &sel) -> int {

@@ -114,7 +114,8 @@ __global__ void setup_grid_kernel(const DevSpec *__restrict__ sp, int n_grids,
                                   double *__restrict__ Xw_all, int32_t *__restrict__ uw_all,
                                   int64_t lat_base, int64_t lat_step,
                                   const int64_t *__restrict__ grid_rows = nullptr,
-                                  double *__restrict__ Bw_all = nullptr)
+                                  double *__restrict__ Bw_all = nullptr,
+                                  const int32_t *__restrict__ grid_keep = nullptr)
 {
     const int g = blockIdx.x;
     if (g >= n_grids) return;
@@ -141,9 +142,18 @@ __global__ void setup_grid_kernel(const DevSpec *__restrict__ sp, int n_grids,
     }
     const int64_t start = ds[0];
     const double tsc = (double)(ds[T - 1] - ds[0]);
+    // Changepoints.  The automatic rule (fbprophet set_changepoints without `changepoints`): n_cp row timestamps spread
+    // over the first cp_range of the rows.  Specified dates (DevSpec::cp_spec, `Prophet(changepoints=...)`): the leading
+    // `keep` of the n_cp dates (all of them; a cross-validation fold keeps those <= its cutoff, grid_keep), scaled by the
+    // same expression as a row's time; a date outside [ds[0], ds[T - 1]] marks the grid (GridTab::cp_bad).
+    const bool cp_spec = sp->cp_spec != 0;
     int hist = (int)__builtin_floor((double)T * sp->cp_range);
     int S = sp->n_cp;
-    if (S + 1 > hist) S = hist - 1;
+    if (cp_spec) {
+        if (grid_keep && grid_keep[g] < S) S = grid_keep[g];
+    } else if (S + 1 > hist) {
+        S = hist - 1;
+    }
     if (S < 0) S = 0;
     const int S_out = S;
     if (threadIdx.x == 0) S_sh = S;
@@ -153,14 +163,32 @@ __global__ void setup_grid_kernel(const DevSpec *__restrict__ sp, int n_grids,
         S = 1;
         if (threadIdx.x == 0) { tch[0] = 0.0; gt.Lj[0] = 0; gt.info.t_change[0] = 0.0; }
     }
-    for (int j = threadIdx.x; j < S_out; j += blockDim.x) {
-        const double v = (j + 1 == S) ? (double)(hist - 1) : (double)(j + 1) * step;
-        const int idx = (int)__builtin_rint(v);
-        tch[j] = (double)(ds[idx] - start) / tsc;
-        int fj = idx;
-        while (fj > 0 && ds[fj - 1] == ds[idx]) --fj;
-        gt.Lj[j] = fj / NT;
-        gt.info.t_change[j] = tch[j];
+    if (cp_spec) {
+        for (int j = threadIdx.x; j < S_out; j += blockDim.x) {
+            const int64_t cp = sp->cp_ns[j];
+            const double tc = (double)(cp - start) / tsc;
+            if (cp < start || cp > ds[T - 1]) gt.cp_bad = 1;
+            // first row at or after the changepoint, by the comparison the row loop below makes (rows ascend, and so do
+            // their scaled times); no such row (a date after the last row: cp_bad) -> the last row
+            int lo = 0, hi = T - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if ((double)(ds[mid] - start) / tsc >= tc) hi = mid; else lo = mid + 1;
+            }
+            tch[j] = tc;
+            gt.Lj[j] = lo / NT;
+            gt.info.t_change[j] = tc;
+        }
+    } else {
+        for (int j = threadIdx.x; j < S_out; j += blockDim.x) {
+            const double v = (j + 1 == S) ? (double)(hist - 1) : (double)(j + 1) * step;
+            const int idx = (int)__builtin_rint(v);
+            tch[j] = (double)(ds[idx] - start) / tsc;
+            int fj = idx;
+            while (fj > 0 && ds[fj - 1] == ds[idx]) --fj;
+            gt.Lj[j] = fj / NT;
+            gt.info.t_change[j] = tch[j];
+        }
     }
     if (threadIdx.x == 0) {
         int i1 = T - 1;
@@ -324,7 +352,9 @@ __global__ __launch_bounds__(64) void setup_series_kernel(
             k0 = (y1 - y0) / Td;
             m0 = y0 - k0 * t0;
             if (ymin == ymax) status0 = TSF_ST_CONSTANT;
+            if (gt.cp_bad) status0 = TSF_ST_CHANGEPOINT;
         } else {
+            if (gt.cp_bad) status0 = TSF_ST_CHANGEPOINT;
             if (capv <= fl) {
                 status0 = TSF_ST_CAP;
             } else {

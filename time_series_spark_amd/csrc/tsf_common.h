@@ -74,7 +74,8 @@ struct DevSpec {
     int32_t seas_order[TSF_MAX_SEAS];   // Fourier order,
     int32_t seas_col[TSF_MAX_SEAS];     // original column of sin(1 theta) (columns: sin 1, cos 1, sin 2, cos 2, ...)
     int32_t harm;                       // harmonic structure the residual-form kernel is compiled for (HARM_*), 0 = none
-    int32_t pad_;
+    int32_t cp_spec;                    // 1: the changepoints are the n_cp dates cp_ns (tsf_spec.changepoints_specified), cp_range unused
+    int64_t cp_ns[TSF_MAX_S];           // strictly ascending (build_devspec checks)
 };
 
 // Canonical design values (round 5; oracle fourier_row): the FIRST harmonic of a seasonality from dm_sincos at
@@ -120,7 +121,9 @@ struct GridTab {
     // model on a dummy changepoint at t = 0 (set_changepoints: `changepoints_t = np.array([0.])`)
     // and folds its delta into k afterwards (store_theta); the caller never sees it
     int32_t S_fit;
-    int32_t pad_;
+    // specified changepoints: a date before the first or after the last row of the grid (fbprophet raises
+    // 'Changepoints must fall within training data.'): every series of the grid gets TSF_ST_CHANGEPOINT
+    int32_t cp_bad;
 };
 
 // one value of the caller's y column (f64, f32 or the reference schema's int32: prophet_modeler.py:16)
@@ -133,7 +136,7 @@ __device__ __forceinline__ double load_y(const void *y, int dtype, int64_t i)
 
 struct SeriesTab {
     double y_scale, cap, k0, m0, floor_;
-    int32_t status0;                    // 0 ok, TSF_ST_TOO_FEW / TSF_ST_CAP / TSF_ST_CONSTANT
+    int32_t status0;                    // 0 ok, TSF_ST_TOO_FEW / TSF_ST_CAP / TSF_ST_CHANGEPOINT / TSF_ST_CONSTANT
     int32_t pad_;
 };
 

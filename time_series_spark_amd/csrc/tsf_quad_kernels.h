@@ -1048,6 +1048,7 @@ __device__ __forceinline__ SeriesTab series_tab_wave(const SeriesView &sv, const
     st.k0 = (y1 - y0) / Td;
     st.m0 = y0 - st.k0 * t0;
     if (ymin == ymax) st.status0 = TSF_ST_CONSTANT;
+    if (gt.cp_bad) st.status0 = TSF_ST_CHANGEPOINT;        // (as setup_series_kernel)
     st.y_scale = ys;
     return st;
 }

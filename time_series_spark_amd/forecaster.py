@@ -22,12 +22,18 @@ class ModelSpec(object):
     seasonalities: list of dicts {name, period (days), fourier_order, prior_scale, mode}.
     extra: list of dicts {name, prior_scale, mode} for explicit design columns (holiday
     indicators, regressors) whose values the caller supplies.
+    changepoints: fbprophet's ``Prophet(changepoints=[...])`` -- the dates at which the trend may change slope, instead
+    of ``n_changepoints`` row timestamps spread over the first ``changepoint_range`` of the history.  Anything
+    ``numpy.asarray(..., 'datetime64[ns]')`` accepts, or int64 ns since the epoch.  The list is sorted, a date given twice
+    is a ValueError (fbprophet would fit two identical trend columns), ``n_changepoints`` becomes its length and
+    ``changepoint_range`` is ignored.  A series whose history does not span every date comes back with status
+    ST_CHANGEPOINT.  (Semantics restated from recall of fbprophet 0.5: include/tsf.h.)
     """
 
     def __init__(self, growth='linear', seasonality_mode='additive', n_changepoints=25,
                  changepoint_range=0.8, changepoint_prior_scale=0.05,
                  seasonality_prior_scale=10.0, holidays_prior_scale=10.0,
-                 seasonalities=None, extra=None, holidays=None, **lbfgs):
+                 seasonalities=None, extra=None, holidays=None, changepoints=None, **lbfgs):
         if growth not in ('linear', 'logistic'):
             raise ValueError("Parameter 'growth' should be 'linear' or 'logistic'.")
         if seasonality_mode not in ('additive', 'multiplicative'):
@@ -36,7 +42,8 @@ class ModelSpec(object):
             raise ValueError("Parameter 'changepoint_range' must be in [0, 1]")
         self.growth = growth
         self.seasonality_mode = seasonality_mode
-        self.n_changepoints = int(n_changepoints)
+        self.changepoints = None if changepoints is None else changepoints_ns(changepoints)
+        self.n_changepoints = int(n_changepoints) if self.changepoints is None else len(self.changepoints)
         self.changepoint_range = float(changepoint_range)
         self.changepoint_prior_scale = float(changepoint_prior_scale)
         self.seasonality_prior_scale = float(seasonality_prior_scale)
@@ -107,6 +114,11 @@ class ModelSpec(object):
         return out
 
     @property
+    def specified_changepoints(self):
+        """fbprophet's attribute of the same name: were the changepoint dates given?"""
+        return self.changepoints is not None
+
+    @property
     def K(self):
         return sum(2 * int(s['fourier_order']) for s in self.seasonalities) + len(self.extra)
 
@@ -120,6 +132,10 @@ class ModelSpec(object):
         s.n_changepoints = self.n_changepoints
         s.changepoint_range = self.changepoint_range
         s.changepoint_prior_scale = self.changepoint_prior_scale
+        if self.changepoints is not None:
+            s.changepoints_specified = 1
+            for j, v in enumerate(self.changepoints):
+                s.changepoint_ns[j] = int(v)
         if len(self.seasonalities) > _lib.MAX_SEAS or len(self.extra) > _lib.MAX_EXTRA:
             raise ValueError('too many seasonalities (max %d) or extra columns (max %d)'
                              % (_lib.MAX_SEAS, _lib.MAX_EXTRA))
@@ -144,13 +160,45 @@ class ModelSpec(object):
                 'seasonality_prior_scale': self.seasonality_prior_scale,
                 'holidays_prior_scale': self.holidays_prior_scale,
                 'seasonalities': self.seasonalities, 'extra': self.extra, 'lbfgs': self.lbfgs,
-                **({'holidays': self.holidays} if self.holidays else {})}
+                **({'holidays': self.holidays} if self.holidays else {}),
+                # ISO strings with nanoseconds: JSON (the model blobs' prefix) and YAML keep them exactly
+                **({'changepoints': [str(np.datetime64(int(v), 'ns')) for v in self.changepoints]}
+                   if self.changepoints is not None else {})}
 
     @classmethod
     def from_dict(cls, d):
         d = dict(d)
         lb = d.pop('lbfgs', {})
         return cls(**d, **lb)
+
+
+def changepoints_ns(changepoints):
+    """Changepoint dates as sorted int64 ns since the epoch (ModelSpec(changepoints=...))."""
+    a = np.asarray(changepoints)
+    if a.size == 0:
+        a = np.zeros(0, dtype=np.int64)
+    elif a.dtype.kind in 'iu':
+        a = a.astype(np.int64)
+    else:
+        a = a.astype('datetime64[ns]').astype(np.int64)
+    a = np.sort(a.reshape(-1))
+    if a.size > _lib.MAX_S:
+        raise ValueError('at most %d changepoints (got %d)' % (_lib.MAX_S, a.size))
+    if a.size > 1 and (np.diff(a) == 0).any():
+        raise ValueError('changepoints must be distinct dates')
+    return a
+
+
+def changepoint_dates(fit, n=0):
+    """The changepoint dates of series n of a fit as int64 ns -- what fbprophet's add_changepoints_to_plot reads from
+    ``m.changepoints``.  Specified dates: the spec's own list (integer ns are not exactly recoverable from the scaled
+    double); the automatic rule: start_ns + t_change * t_scale_ns of the series' grid, rounded to the nearest ns."""
+    g = fit.grid_of(n)
+    S = int(g['S'])
+    if fit.spec.specified_changepoints:
+        return fit.spec.changepoints[:S].copy()
+    t = np.asarray(g['t_change'][:S], dtype=np.float64)
+    return int(g['start_ns']) + np.rint(t * float(g['t_scale_ns'])).astype(np.int64)
 
 
 class FitResult(object):

@@ -376,6 +376,11 @@ def _spec_opts(kw):
               'init_alpha', 'tol_obj', 'tol_rel_obj', 'tol_grad', 'tol_rel_grad', 'tol_param'):
         if k in kw:
             out[k] = kw[k]
+    # changepoints: a list of dates, fbprophet's Prophet(changepoints=[...]) -- the trend changes slope at these dates
+    # instead of at n_changepoints automatic ones (ModelSpec); the reference job has no such key (it constructs Prophet
+    # with the default, prophet_modeler.py:65)
+    if kw.get('changepoints') is not None:
+        out['changepoints'] = fc.changepoints_ns(kw['changepoints'])
     # converge: 'stan' (default: where Stan's termination tests stop the optimiser -- what Prophet.fit returns) or 'map'
     # (on to the maximum a posteriori estimate itself: include/tsf.h TSF_CONVERGE_MAP); not in the reference
     if 'converge' in kw:
@@ -387,6 +392,19 @@ def _spec_opts(kw):
             if k in kw:
                 out[k] = kw[k]
     return out
+
+
+def check_changepoints(kw, panel):
+    """fbprophet's set_changepoints raises for a model whose specified changepoints do not all lie inside its history;
+    the fit reports such a series as ST_CHANGEPOINT, the jobs raise what fbprophet raises."""
+    if kw.get('changepoints') is None or panel.N == 0:
+        return
+    cp = fc.changepoints_ns(kw['changepoints'])
+    if len(cp) == 0:
+        return
+    first, last = panel.ds_ns[panel.offsets[:-1]], panel.ds_ns[panel.offsets[1:] - 1]
+    if (cp[0] < first).any() or (cp[-1] > last).any():
+        raise ValueError('Changepoints must fall within training data.')
 
 
 def _model_packed(config, panel, n_rows, execution_time, previous=None, lap=None):
@@ -405,6 +423,7 @@ def _model_packed(config, panel, n_rows, execution_time, previous=None, lap=None
         raise ValueError('Dataframe has less than 2 non-NaN rows.')
     if kw['growth'] == 'logistic' and (cap <= floors).any():
         raise ValueError('cap must be greater than floor (which defaults to 0).')
+    check_changepoints(kw, panel)
     # config['devices'] (not in the reference): GPUs to spread the series over, e.g. [0, 1, 2, 3]
     # or 'all'; default: TSF_DEVICES, else one GPU
     cost = None

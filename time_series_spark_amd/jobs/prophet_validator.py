@@ -185,6 +185,7 @@ class ProphetValidator(object):
         panel = pk.pack_rows(sid, did, ds_ns, y, key_dtypes=(np.int32, np.int32))
         if (panel.lengths < 2).any() or panel.dropped_keys:
             raise ValueError('Dataframe has less than 2 non-NaN rows.')
+        pm.check_changepoints(pm._prophet_kwargs(config), panel)
         metrics, folds = validate_panel(config, panel)
         tuning = tune_panel(config, panel) if config.get('tune') is not None else None
         os.makedirs(config['io']['metrics'], exist_ok=True)
