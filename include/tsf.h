@@ -336,6 +336,59 @@ int tsf_predict_components_dev(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, in
                                double *comp, double *yhat_lower, double *yhat_upper, double *trend_lower,
                                double *trend_upper, void *stream);
 
+/* ---- forecast quantiles, cumulative quantiles, predictive samples ----------------------------------
+ * The predictive distribution behind tsf_predict_intervals' one symmetric pair: any set of quantiles of the sampled yhat
+ * per future row, the same quantiles of each sample's running sum over the future rows ("P90 of the total of the next 14
+ * days": quantiles of sums are not sums of quantiles), the quantiles of the sampled trend, and the raw draws themselves
+ * (fbprophet 0.5's Prophet.predictive_samples: {'yhat', 'trend'}, each (H, n_samples) per series).  Semantics restated
+ * from recall of fbprophet 0.5: parity unpinned (no test compares with the real package; what is pinned is the contract
+ * below, against tsf_predict / tsf_predict_intervals / tsf_predict_components).
+ * Reference interface replaced: none (the reference keeps yhat alone, prophet_scorer.py:86).
+ *
+ * Arguments shared with tsf_predict_intervals mean what they mean there; the same grid check runs first.  n_samples in
+ * [2, 4096].  quantiles [n_q] and the tsf_quantile_out struct are HOST memory in both variants, like spec; the pointers
+ * inside the struct are host pointers in the host variant and device pointers in _dev.  n_q in [0, TSF_MAX_QUANT], every
+ * level finite and in [0, 1] (0: the minimum, 1: the maximum); their order and duplicates are the caller's business.
+ * n_q = 0 is legal only where a sample output is wanted; a call that wants none of q / cum_q / trend_q / samples /
+ * trend_samples is refused.  Every refusal returns < 0 with a message, before any launch; the context stays usable.
+ *
+ * Contract:
+ *   The draws are tsf_predict_intervals' draws: the same generator, keys (seed, series_key[n], sample, stream) and
+ *   counters.  Sample s of a series depends neither on n_samples, nor on the batch, nor on which outputs are requested.
+ *   A quantile at level p is taken over the ascending sorted values v[0 .. n_samples): with
+ *     pos = p * (double)(n_samples - 1), lo = floor(pos), hi = min(lo + 1, n_samples - 1)
+ *   it is v[lo] + (v[hi] - v[lo]) * (pos - lo), the expression and rounding of tsf_predict_intervals.  So the levels
+ *   (1 - w) / 2 and (1 + w) / 2, formed in double exactly so, give tsf_predict_intervals' yhat_lower / yhat_upper at
+ *   width w bit for bit, and trend_q gives tsf_predict_components' trend_lower / trend_upper the same way.
+ *   The running sum of sample s is c[s][0] = sample[s][0], c[s][h] = c[s][h-1] + sample[s][h]: plain double adds in the
+ *   row order the caller gave (it does not restart where unsorted futures restart the trend sweep).  cum_q[n][i][h] is
+ *   the quantile of c[.][h]; cum_q[n][i][0] == q[n][i][0] bit for bit.
+ *   No int truncation or floor clamp is applied (tsf_predict_intervals applies none either).
+ *
+ * Scratch: series are processed in chunks whose sample buffers (yhat; the running sums if cum_q; the trend if trend_q or
+ * trend_samples) stay within 512 MB; results do not depend on the chunking.  Requested raw samples are copied out of the
+ * scratch chunk by chunk in stream order: the host variant never holds N * H * n_samples values on the device. */
+#define TSF_MAX_QUANT 64
+typedef struct {
+    double *yhat;           /* [N][H]        required: tsf_predict's, bit for bit */
+    double *q;              /* [N][n_q][H]   per-row quantiles of the sampled yhat; NULL: not wanted */
+    double *cum_q;          /* [N][n_q][H]   quantiles of each sample's running sum over rows 0..h; NULL: not wanted */
+    double *trend_q;        /* [N][n_q][H]   per-row quantiles of the sampled trend (before noise); NULL: not wanted */
+    double *samples;        /* [N][H][n_samples] raw yhat draws, sample s at index s; NULL: not wanted */
+    double *trend_samples;  /* [N][H][n_samples] raw trend draws; NULL: not wanted */
+} tsf_quantile_out;
+int tsf_predict_quantiles(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H, const double *theta,
+                          const double *y_scale, const tsf_grid_info *grid, int32_t n_grids,
+                          const int64_t *ds_future, int32_t shared_future, const double *floor, const double *cap,
+                          const double *extra_future, const int64_t *series_key, int32_t n_samples, uint64_t seed,
+                          int32_t n_q, const double *quantiles, tsf_quantile_out *out);
+int tsf_predict_quantiles_dev(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H, const double *theta,
+                              const double *y_scale, const tsf_grid_info *grid, int32_t n_grids,
+                              const int64_t *ds_future, int32_t shared_future, const double *floor,
+                              const double *cap, const double *extra_future, const int64_t *series_key,
+                              int32_t n_samples, uint64_t seed, int32_t n_q, const double *quantiles,
+                              tsf_quantile_out *out, void *stream);
+
 /* ---- cross-validation ---------------------------------------------------------------------
  * fbprophet 0.5 diagnostics.cross_validation + performance_metrics for a whole panel: every series is refitted at
  * several cutoffs and each fold's forecast is scored against the rows held out after its cutoff.  The semantics are

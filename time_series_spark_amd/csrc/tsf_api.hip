@@ -1811,6 +1811,188 @@ extern "C" int tsf_predict_components(tsf_ctx *ctx, const tsf_spec *spec, int64_
     return 0;
 }
 
+// ---- forecast quantiles, cumulative quantiles, predictive samples ----------------------------------------
+
+// What both quantile entries check before anything is launched: the sample count, the levels (host data in both, like
+// the spec) and that the call asks for something.
+static int check_quantile_args(tsf_ctx *ctx, int32_t n_samples, int32_t n_q, const double *quantiles,
+                               const tsf_quantile_out *out)
+{
+    if (!out || !out->yhat) return fail(ctx, "NULL output (tsf_quantile_out and its yhat are required)");
+    if (n_samples < 2 || n_samples > 4096) return fail(ctx, "n_samples must be in [2, 4096]");
+    if (n_q < 0 || n_q > TSF_MAX_QUANT) return fail(ctx, "n_q must be in [0, TSF_MAX_QUANT]");
+    if (n_q > 0 && !quantiles) return fail(ctx, "NULL quantiles");
+    for (int32_t i = 0; i < n_q; ++i)
+        if (!(quantiles[i] >= 0.0 && quantiles[i] <= 1.0)) {       // (NaN fails both comparisons)
+            char msg[120];
+            snprintf(msg, sizeof(msg), "quantiles[%d] = %g: a level must be finite and in [0, 1]", (int)i, quantiles[i]);
+            return fail(ctx, msg);
+        }
+    const bool want_q = out->q || out->cum_q || out->trend_q, want_s = out->samples || out->trend_samples;
+    if (!want_q && !want_s) return fail(ctx, "nothing requested: q, cum_q, trend_q, samples and trend_samples are all NULL");
+    if (n_q == 0 && want_q) return fail(ctx, "n_q = 0 with a quantile output requested");
+    if (n_q == 0 && !want_s) return fail(ctx, "n_q = 0 is legal only with a sample output");
+    return 0;
+}
+
+// The work of both entries on device-resident inputs.  The quantile outputs of `o` are device pointers; its two sample
+// outputs are copied out of the chunk's scratch in stream order with `kind` (device to device for the _dev entry,
+// device to host for the host entry, which therefore never holds N * H * n_samples values on the device).
+static int predict_quantiles_run(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H, const double *theta,
+                                 const double *y_scale, const tsf_grid_info *grid, int32_t n_grids,
+                                 const int64_t *ds_future, int32_t shared_future, const double *floor_,
+                                 const double *cap, const double *extra_future, const int64_t *series_key,
+                                 int32_t n_samples, uint64_t seed, int32_t n_q, const double *quantiles,
+                                 const tsf_quantile_out &o, hipMemcpyKind kind, hipStream_t st)
+{
+    DevSpec hs;
+    int mode = 0;
+    int rc = build_devspec(ctx, spec, &hs, &mode);
+    if (rc) return rc;
+    if (hs.n_extra > 0 && !extra_future) return fail(ctx, "extra_future is NULL");
+    if (hs.growth == TSF_GROWTH_LOGISTIC && !cap) return fail(ctx, "logistic growth needs cap");
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_spec, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
+    // tsf_predict_intervals_dev's scheme: a chunk's scratch -- the three per-row pieces and every sample buffer the
+    // call needs (yhat always; the running sums for cum_q; the trend for trend_q / trend_samples) -- stays within
+    // 512 MB of the same cached block
+    const bool want_cum = o.cum_q != nullptr, want_trend = o.trend_q || o.trend_samples;
+    const size_t n_buf = 1 + (size_t)want_cum + (size_t)want_trend;
+    const size_t per_series = (size_t)H * 8 * (3 + n_buf * (size_t)n_samples);
+    int64_t chunk = (int64_t)(((size_t)512 << 20) / per_series);
+    if (chunk < 1) chunk = 1;
+    if (chunk > N) chunk = N;
+    const size_t nh = (size_t)chunk * H;
+    const size_t need = 8 * nh * (3 + n_buf * (size_t)n_samples);
+    if (ctx->iv_ws_bytes < need) {
+        if (ctx->iv_ws) { HIP_TRY(ctx, hipFree(ctx->iv_ws)); ctx->iv_ws = nullptr; ctx->iv_ws_bytes = 0; }
+        HIP_TRY(ctx, hipMalloc(&ctx->iv_ws, need));
+        ctx->iv_ws_bytes = need;
+    }
+    double *d_t = (double *)ctx->iv_ws, *d_xa = d_t + nh, *d_opm = d_xa + nh, *d_samp = d_opm + nh;
+    double *d_next = d_samp + nh * n_samples;
+    double *d_cum = nullptr, *d_tsamp = nullptr;
+    if (want_cum) { d_cum = d_next; d_next += nh * n_samples; }
+    if (want_trend) d_tsamp = d_next;
+    PredictArgs p;
+    memset(&p, 0, sizeof(p));
+    p.sp = ctx->d_spec; p.N = N; p.H = H; p.theta_stride = tsf_theta_stride(spec);
+    p.n_grids = n_grids; p.shared_future = shared_future; p.theta = theta; p.y_scale = y_scale;
+    p.grid = grid; p.ds_future = ds_future; p.floor_ = floor_; p.cap = cap;
+    p.extra_future = extra_future; p.yhat = o.yhat; p.yhat_int = nullptr;
+    p.t_out = d_t; p.xa_out = d_xa; p.opm_out = d_opm;
+    int NSP = 2;
+    while (NSP < n_samples) NSP <<= 1;
+    IntervalArgs a;
+    memset(&a, 0, sizeof(a));
+    a.sp = ctx->d_spec; a.H = H; a.theta_stride = tsf_theta_stride(spec); a.n_grids = n_grids; a.NS = n_samples;
+    a.theta = theta; a.y_scale = y_scale; a.grid = grid; a.floor_ = floor_; a.cap = cap;
+    a.series_key = series_key; a.seed = seed;
+    a.samples = d_samp; a.trend_samples = d_tsamp; a.cum_samples = d_cum;
+    QuantileArgs q;
+    memset(&q, 0, sizeof(q));
+    q.H = H; q.NS = n_samples; q.n_q = n_q;
+    for (int32_t i = 0; i < n_q; ++i) q.level[i] = quantiles[i];
+    const struct { const double *src; double *dst; } sorts[3] = {{d_samp, o.q}, {d_cum, o.cum_q}, {d_tsamp, o.trend_q}};
+    bool tab_ready = false;
+    for (int64_t n0 = 0; n0 < N; n0 += chunk) {
+        const int64_t nc = (N - n0 < chunk) ? N - n0 : chunk;
+        if (int prc = launch_predict(ctx, hs, p, n0, nc, &tab_ready, st)) return prc;
+        a.n0 = n0; a.n_chunk = nc;
+        a.t = d_t - (size_t)n0 * H; a.xa = d_xa - (size_t)n0 * H; a.opm = d_opm - (size_t)n0 * H;
+        hipLaunchKernelGGL(interval_sample_kernel, dim3((unsigned)nc, (unsigned)((n_samples + 255) / 256)),
+                           dim3(256), 0, st, a);
+        HIP_TRY(ctx, hipGetLastError());
+        for (const auto &so : sorts) {
+            if (!so.dst) continue;
+            q.src = so.src; q.dst = so.dst; q.n0 = n0;
+            hipLaunchKernelGGL(quantile_kernel, dim3((unsigned)(nc * H)), dim3(256), sizeof(double) * NSP, st, q, NSP);
+            HIP_TRY(ctx, hipGetLastError());
+        }
+        // the raw draws leave the scratch before the next chunk overwrites it (stream order)
+        const size_t off = (size_t)n0 * H * n_samples, nb = 8 * (size_t)nc * H * n_samples;
+        if (o.samples) HIP_TRY(ctx, hipMemcpyAsync(o.samples + off, d_samp, nb, kind, st));
+        if (o.trend_samples) HIP_TRY(ctx, hipMemcpyAsync(o.trend_samples + off, d_tsamp, nb, kind, st));
+    }
+    return 0;
+}
+
+extern "C" int tsf_predict_quantiles_dev(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H,
+                                         const double *theta, const double *y_scale, const tsf_grid_info *grid,
+                                         int32_t n_grids, const int64_t *ds_future, int32_t shared_future,
+                                         const double *floor_, const double *cap, const double *extra_future,
+                                         const int64_t *series_key, int32_t n_samples, uint64_t seed, int32_t n_q,
+                                         const double *quantiles, tsf_quantile_out *out, void *stream)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (N <= 0 || H <= 0) return fail(ctx, "N and H must be > 0");
+    if (!spec || !theta || !y_scale || !grid || !ds_future) return fail(ctx, "NULL input");
+    if (n_grids != 1 && n_grids != N) return fail(ctx, "n_grids must be 1 or N");
+    if (int rc = check_quantile_args(ctx, n_samples, n_q, quantiles, out)) return rc;
+    return predict_quantiles_run(ctx, spec, N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap,
+                                 extra_future, series_key, n_samples, seed, n_q, quantiles, *out,
+                                 hipMemcpyDeviceToDevice, (hipStream_t)stream);
+}
+
+extern "C" int tsf_predict_quantiles(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H,
+                                     const double *theta, const double *y_scale, const tsf_grid_info *grid,
+                                     int32_t n_grids, const int64_t *ds_future, int32_t shared_future,
+                                     const double *floor_, const double *cap, const double *extra_future,
+                                     const int64_t *series_key, int32_t n_samples, uint64_t seed, int32_t n_q,
+                                     const double *quantiles, tsf_quantile_out *out)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (N <= 0 || H <= 0) return fail(ctx, "N and H must be > 0");
+    if (!spec || !theta || !y_scale || !grid || !ds_future) return fail(ctx, "NULL input");
+    if (n_grids != 1 && n_grids != N) return fail(ctx, "n_grids must be 1 or N");
+    if (int rc = check_grids(ctx, spec, grid, n_grids)) return rc;
+    if (int rc = check_quantile_args(ctx, n_samples, n_q, quantiles, out)) return rc;
+    if (spec->n_extra > 0 && !extra_future) return fail(ctx, "extra_future is NULL");
+    const int stride = tsf_theta_stride(spec);
+    const size_t nfut = shared_future ? (size_t)H : (size_t)N * H;
+    DevBuf d_th, d_ys, d_grid, d_ds, d_fl, d_cap, d_ex, d_key, d_yh, d_q, d_cq, d_tq;
+    HIP_TRY(ctx, d_th.alloc(8 * (size_t)N * stride));
+    HIP_TRY(ctx, hipMemcpy(d_th.p, theta, 8 * (size_t)N * stride, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_ys.alloc(8 * N));
+    HIP_TRY(ctx, hipMemcpy(d_ys.p, y_scale, 8 * N, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_grid.alloc(sizeof(tsf_grid_info) * n_grids));
+    HIP_TRY(ctx, hipMemcpy(d_grid.p, grid, sizeof(tsf_grid_info) * n_grids, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_ds.alloc(8 * nfut));
+    HIP_TRY(ctx, hipMemcpy(d_ds.p, ds_future, 8 * nfut, hipMemcpyHostToDevice));
+    if (floor_) { HIP_TRY(ctx, d_fl.alloc(8 * N)); HIP_TRY(ctx, hipMemcpy(d_fl.p, floor_, 8 * N, hipMemcpyHostToDevice)); }
+    if (cap) { HIP_TRY(ctx, d_cap.alloc(8 * N)); HIP_TRY(ctx, hipMemcpy(d_cap.p, cap, 8 * N, hipMemcpyHostToDevice)); }
+    if (series_key) { HIP_TRY(ctx, d_key.alloc(8 * N)); HIP_TRY(ctx, hipMemcpy(d_key.p, series_key, 8 * N, hipMemcpyHostToDevice)); }
+    if (spec->n_extra > 0) {
+        const size_t nb = 8 * (size_t)spec->n_extra * nfut;
+        HIP_TRY(ctx, d_ex.alloc(nb));
+        HIP_TRY(ctx, hipMemcpy(d_ex.p, extra_future, nb, hipMemcpyHostToDevice));
+    }
+    const size_t nh = 8 * (size_t)N * H, nqh = nh * (size_t)n_q;
+    HIP_TRY(ctx, d_yh.alloc(nh));
+    if (out->q) HIP_TRY(ctx, d_q.alloc(nqh));
+    if (out->cum_q) HIP_TRY(ctx, d_cq.alloc(nqh));
+    if (out->trend_q) HIP_TRY(ctx, d_tq.alloc(nqh));
+    tsf_quantile_out o;
+    o.yhat = d_yh.as<double>();
+    o.q = out->q ? d_q.as<double>() : nullptr;
+    o.cum_q = out->cum_q ? d_cq.as<double>() : nullptr;
+    o.trend_q = out->trend_q ? d_tq.as<double>() : nullptr;
+    o.samples = out->samples; o.trend_samples = out->trend_samples;      // host: filled chunk by chunk
+    int rc = predict_quantiles_run(ctx, spec, N, H, d_th.as<double>(), d_ys.as<double>(), d_grid.as<tsf_grid_info>(),
+                                   n_grids, d_ds.as<int64_t>(), shared_future, floor_ ? d_fl.as<double>() : nullptr,
+                                   cap ? d_cap.as<double>() : nullptr, spec->n_extra > 0 ? d_ex.as<double>() : nullptr,
+                                   series_key ? d_key.as<int64_t>() : nullptr, n_samples, seed, n_q, quantiles, o,
+                                   hipMemcpyDeviceToHost, nullptr);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    HIP_TRY(ctx, hipMemcpy(out->yhat, d_yh.p, nh, hipMemcpyDeviceToHost));
+    if (out->q) HIP_TRY(ctx, hipMemcpy(out->q, d_q.p, nqh, hipMemcpyDeviceToHost));
+    if (out->cum_q) HIP_TRY(ctx, hipMemcpy(out->cum_q, d_cq.p, nqh, hipMemcpyDeviceToHost));
+    if (out->trend_q) HIP_TRY(ctx, hipMemcpy(out->trend_q, d_tq.p, nqh, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // ---- diagnostics --------------------------------------------------------------------------------
 
 extern "C" int tsf_design(tsf_ctx *ctx, const tsf_spec *spec, int32_t T, const int64_t *ds,

@@ -10,6 +10,8 @@
 //                               samples[series][row][sample] (and, where asked, the sampled trend alike)
 //   interval_percentile_kernel  one workgroup per (series, row): bitonic sort of the samples in LDS,
 //                               the two percentiles by linear interpolation (np.nanpercentile)
+//   quantile_kernel             the same sort once per (series, row), then any number of levels from the sorted
+//                               row (tsf_predict_quantiles: one launch per sample buffer -- yhat, running sum, trend)
 // Non-template __global__ functions: include from exactly one translation unit (tsf_api.hip).
 #pragma once
 #include "tsf_common.h"
@@ -62,6 +64,7 @@ struct IntervalArgs {
     double *samples;            // [n_chunk][H][NS]
     double *trend_samples;      // optional [n_chunk][H][NS]: each sample's trend before noise (tsf_predict_components)
     double *lower, *upper;      // [N][H]
+    double *cum_samples;        // optional [n_chunk][H][NS]: each sample's running sum over rows 0..h (tsf_predict_quantiles)
 };
 
 __global__ __launch_bounds__(256) void interval_sample_kernel(IntervalArgs a)
@@ -94,6 +97,7 @@ __global__ __launch_bounds__(256) void interval_sample_kernel(IntervalArgs a)
     int ih = 0, inew = 0, n_new = 0;
     uint64_t ctr = 0;
     double *out = a.samples + (size_t)nl * H * a.NS + s;
+    double csum = 0.0;          // the running sum of this sample's rows, in the caller's row order (never restarted)
     for (int h = 0; h < H; ++h) {
         const double th_ = t[h];
         if (h == 0 || th_ < t_last) {       // (re)start the sweep: the stream is replayed from 0
@@ -132,7 +136,12 @@ __global__ __launch_bounds__(256) void interval_sample_kernel(IntervalArgs a)
         double sn, cs;
         dm_sincos(6.283185307179586 * u2, sn, cs);
         const double z = __builtin_sqrt(-2.0 * dm_log(u1)) * cs;
-        out[(size_t)h * a.NS] = trend * opm[h] + xa[h] + (z * sigma) * ys;
+        const double val = trend * opm[h] + xa[h] + (z * sigma) * ys;
+        out[(size_t)h * a.NS] = val;
+        if (a.cum_samples) {
+            csum = (h == 0) ? val : csum + val;
+            a.cum_samples[(size_t)nl * H * a.NS + s + (size_t)h * a.NS] = csum;
+        }
         if (a.trend_samples) a.trend_samples[(size_t)nl * H * a.NS + s + (size_t)h * a.NS] = trend;
     }
 }
@@ -167,6 +176,49 @@ __global__ __launch_bounds__(256) void interval_percentile_kernel(IntervalArgs a
         const double val = v[lo] + (v[hi] - v[lo]) * (pos - (double)lo);
         double *dst = threadIdx.x ? a.upper : a.lower;
         dst[(size_t)(a.n0 + nl) * a.H + h] = val;
+    }
+}
+
+// tsf_predict_quantiles: one (series, row) of a chunk's sample buffer sorted once, every level read from the sorted
+// row.  The sort and the interpolation are interval_percentile_kernel's, expression for expression, so a level formed
+// as that kernel's lo_frac / hi_frac gives its bits.  The levels travel by value (TSF_MAX_QUANT doubles of kernel
+// arguments); LDS: NSP doubles (<= 32 KB), as there.
+struct QuantileArgs {
+    const double *src;          // [n_chunk][H][NS] of the chunk
+    double *dst;                // [N][n_q][H] of the call
+    int64_t n0;                 // first series of the chunk
+    int H, NS, n_q;
+    double level[TSF_MAX_QUANT];
+};
+
+__global__ __launch_bounds__(256) void quantile_kernel(QuantileArgs a, int NSP)
+{
+    extern __shared__ __align__(16) unsigned char iv_smem[];
+    double *v = reinterpret_cast<double *>(iv_smem);
+    const int64_t nl = blockIdx.x / a.H;
+    const int h = (int)(blockIdx.x - nl * a.H);
+    const double *src = a.src + ((size_t)nl * a.H + h) * a.NS;
+    for (int i = threadIdx.x; i < NSP; i += blockDim.x) v[i] = (i < a.NS) ? src[i] : __builtin_huge_val();
+    __syncthreads();
+    for (int k = 2; k <= NSP; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = threadIdx.x; i < NSP; i += blockDim.x) {
+                const int ixj = i ^ j;
+                if (ixj > i) {
+                    const bool asc = (i & k) == 0;
+                    const double x = v[i], y = v[ixj];
+                    if ((x > y) == asc) { v[i] = y; v[ixj] = x; }
+                }
+            }
+            __syncthreads();
+        }
+    for (int q = threadIdx.x; q < a.n_q; q += blockDim.x) {
+        const double pos = a.level[q] * (double)(a.NS - 1);
+        int lo = (int)__builtin_floor(pos);
+        if (lo > a.NS - 1) lo = a.NS - 1;
+        const int hi = lo + 1 < a.NS ? lo + 1 : a.NS - 1;
+        const double val = v[lo] + (v[hi] - v[lo]) * (pos - (double)lo);
+        a.dst[((size_t)(a.n0 + nl) * a.n_q + q) * a.H + h] = val;
     }
 }
 

@@ -697,6 +697,121 @@ def predict_components(spec, theta, y_scale, grid, ds_future_ns, floor=None, cap
     return Components(spec, [c[0] for c in cols], yhat, trend, comp, *iv, floor=floor, cap=cap)
 
 
+# ---- forecast quantiles, cumulative quantiles, predictive samples ----------------------------------
+# The predictive distribution behind predict_intervals' one symmetric pair (include/tsf.h tsf_predict_quantiles): any
+# set of levels from one draw and one sort per row, the same levels of each sample's running sum over the future rows,
+# and the raw draws (fbprophet 0.5's Prophet.predictive_samples; restated from recall, parity not pinned).
+
+def quantile_columns(quantiles, prefix='yhat_q'):
+    """Column names of quantile levels: 0.1 -> 'yhat_q10', 0.975 -> 'yhat_q97.5' ('%s%s' % (prefix, format(100 * p,
+    'g'))).  ValueError for a level that is not finite or outside [0, 1], for two levels with the same name and for
+    more than MAX_QUANT levels."""
+    levels = [float(p) for p in np.asarray(quantiles, dtype=np.float64).reshape(-1)]
+    if len(levels) > _lib.MAX_QUANT:
+        raise ValueError('at most %d quantile levels (got %d)' % (_lib.MAX_QUANT, len(levels)))
+    names = []
+    for p in levels:
+        if not (np.isfinite(p) and 0.0 <= p <= 1.0):
+            raise ValueError('quantile level %r: must be finite and in [0, 1]' % (p,))
+        name = '%s%s' % (prefix, format(100 * p, 'g'))
+        if name in names:
+            raise ValueError('quantile levels: two levels are named %s' % name)
+        names.append(name)
+    return names
+
+
+class Quantiles(object):
+    """What predict_quantiles returns: yhat [N][H]; quantiles [Q] (the levels as given); q [N][Q][H]; cum_q and
+    trend_q [N][Q][H] or None."""
+
+    def __init__(self, yhat, quantiles, q, cum_q=None, trend_q=None):
+        self.yhat, self.quantiles, self.q, self.cum_q, self.trend_q = yhat, quantiles, q, cum_q, trend_q
+
+    def frame(self, n, ds):
+        """Series n as a DataFrame: ds, yhat, yhat_q<..> per level, then yhat_cum_q<..> and trend_q<..> where computed
+        (names: quantile_columns)."""
+        import pandas as pd
+        ds = np.asarray(ds)
+        if ds.dtype.kind != 'M':
+            ds = ds.astype(np.int64).view('datetime64[ns]')
+        cols = {'ds': ds, 'yhat': self.yhat[n]}
+        for prefix, arr in (('yhat_q', self.q), ('yhat_cum_q', self.cum_q), ('trend_q', self.trend_q)):
+            if arr is not None:
+                for i, name in enumerate(quantile_columns(self.quantiles, prefix)):
+                    cols[name] = arr[n, i]
+        return pd.DataFrame(cols, columns=list(cols))
+
+
+def _predict_quantiles_call(spec, theta, y_scale, grid, ds_future_ns, floor, cap, extra_future, series_key,
+                            uncertainty_samples, seed, levels, want, ctx):
+    """One tsf_predict_quantiles call -> dict of the outputs named in `want` (and yhat)."""
+    ctx = ctx or get_context()
+    L = _lib.load()
+    theta = np.ascontiguousarray(theta, dtype=np.float64)
+    N = theta.shape[0]
+    y_scale = np.ascontiguousarray(y_scale, dtype=np.float64)
+    grid = np.ascontiguousarray(grid, dtype=_lib.GRID_DTYPE)
+    ds_future_ns = np.ascontiguousarray(ds_future_ns, dtype=np.int64)
+    shared = ds_future_ns.ndim == 1
+    H = ds_future_ns.shape[-1]
+    if not shared and ds_future_ns.shape != (N, H):
+        raise ValueError('ds_future must be [H] or [N][H]')
+    cs = spec.to_c()
+    floor = _opt_f64(floor, N, 'floor')
+    cap = _opt_f64(cap, N, 'cap')
+    ex = None
+    if spec.extra:
+        ex = np.ascontiguousarray(extra_future, dtype=np.float64)
+        shape = (len(spec.extra), H) if shared else (N, len(spec.extra), H)
+        if ex.shape != shape:
+            raise ValueError('extra_future must be %r' % (shape,))
+    key = None if series_key is None else np.ascontiguousarray(series_key, dtype=np.int64)
+    if key is not None and key.shape != (N,):
+        raise ValueError('series_key must be [N]')
+    levels = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
+    Q, S = len(levels), int(uncertainty_samples)
+    res = {'yhat': np.zeros((N, H))}
+    for k in ('q', 'cum_q', 'trend_q'):
+        if k in want:
+            res[k] = np.zeros((N, Q, H))
+    for k in ('samples', 'trend_samples'):
+        if k in want:
+            if not 2 <= S <= 4096:          # (the library refuses it too; here before an array is sized by it)
+                raise ValueError('uncertainty_samples must be in [2, 4096]')
+            res[k] = np.zeros((N, H, S))
+    out = _lib.TsfQuantileOut(**{k: v.ctypes.data for k, v in res.items()})
+    rc = L.tsf_predict_quantiles(ctx.handle, ctypes.byref(cs), N, H, theta.ctypes.data, y_scale.ctypes.data,
+                                 grid.ctypes.data, len(grid), ds_future_ns.ctypes.data, int(shared),
+                                 _lib._ptr(floor), _lib._ptr(cap), _lib._ptr(ex), _lib._ptr(key), S, int(seed),
+                                 Q, levels.ctypes.data if Q else None, ctypes.byref(out))
+    ctx.check(rc)
+    return res
+
+
+def predict_quantiles(spec, theta, y_scale, grid, ds_future_ns, quantiles, floor=None, cap=None, extra_future=None,
+                      series_key=None, uncertainty_samples=1000, seed=0, cumulative=False, trend=False, ctx=None):
+    """Quantiles of the simulated futures of every series -> Quantiles (include/tsf.h tsf_predict_quantiles): q [N][Q][H]
+    per future row at the levels `quantiles` (in [0, 1]; 0.5 the median); with cumulative, cum_q: the same levels of each
+    sample's running sum over the future rows (row h: the total of rows 0..h, e.g. demand over a lead time); with trend,
+    trend_q: of the sampled trend.  The draws are predict_intervals' (same series_key, samples, seed): levels
+    (1 - w) / 2, (1 + w) / 2 give its yhat_lower / yhat_upper at width w bit for bit; yhat is predict's."""
+    want = ['q'] + (['cum_q'] if cumulative else []) + (['trend_q'] if trend else [])
+    levels = np.array(quantiles, dtype=np.float64).reshape(-1)
+    r = _predict_quantiles_call(spec, theta, y_scale, grid, ds_future_ns, floor, cap, extra_future, series_key,
+                                uncertainty_samples, seed, levels, want, ctx)
+    return Quantiles(r['yhat'], levels, r['q'], r.get('cum_q'), r.get('trend_q'))
+
+
+def predictive_samples(spec, theta, y_scale, grid, ds_future_ns, floor=None, cap=None, extra_future=None,
+                       series_key=None, uncertainty_samples=1000, seed=0, ctx=None):
+    """fbprophet 0.5's Prophet.predictive_samples for a panel: {'yhat': [N][H][S], 'trend': [N][H][S]}, the raw draws
+    behind predict_intervals / predict_quantiles (sample s at index s, whatever S is; the trend before the observation
+    noise).  For one series [n] is fbprophet's (H, S) layout.  N * H * S * 16 bytes of host memory."""
+    r = _predict_quantiles_call(spec, theta, y_scale, grid, ds_future_ns, floor, cap, extra_future, series_key,
+                                uncertainty_samples, seed, [], ['samples', 'trend_samples'], ctx)
+    return {'yhat': r['samples'], 'trend': r['trend_samples']}
+
+
 # ---- diagnostics used by the parity tests -----------------------------------------------------
 
 def eval_aligned(spec, ds_ns, y, theta, floor=None, cap=None, extra=None, ctx=None):

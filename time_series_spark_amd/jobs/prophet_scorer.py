@@ -31,7 +31,8 @@ def _empty_forecasts():
 def forecast_arrays(config):
     """The predict UDF on columns that never were a DataFrame: (series_id, dim_id, floor, cap, models) -> dict of the
     forecast frame's columns (series_id, dim_id int32; ds int64 ns; yhat int32; yhat_lower / yhat_upper when
-    forecast.intervals; trend, trend_lower / trend_upper and the components' float64 columns when forecast.components),
+    forecast.intervals; trend, trend_lower / trend_upper and the components' float64 columns when forecast.components;
+    yhat_q<..> per level of forecast.quantiles and yhat_cum_q<..> with forecast.cumulative, named by fc.quantile_columns),
     `periods` rows per series, or None when there is nothing to forecast.  models: a list of blobs
     (None = no model) or the uint8 [n][L] buffer of a model column whose blobs share one length
     (panel.model_column_buffer: a parquet column as it lies in memory, no Python object per series)."""
@@ -88,8 +89,19 @@ def forecast_arrays(config):
                                     want_int=True,      # :70-84
                                     devices=config.get('devices'))
             lap('predict')
-            iv = comps = None
+            iv = comps = quant = None
             fcfg = config.get('forecast') or {}
+            if fcfg.get('quantiles'):
+                # opt-in like the intervals below, from the same draws (same key, samples and seed: a level (1 -+ w) / 2
+                # is the interval bound at width w, include/tsf.h); forecast.cumulative adds the levels of the running
+                # total over the forecast rows
+                fc.quantile_columns(fcfg['quantiles'])              # (a bad level list fails before any launch)
+                quant = fc.predict_quantiles(
+                    spec, theta, rec['y_scale'], grid, fut, fcfg['quantiles'], floor=floor, cap=cap,
+                    extra_future=ex if (ex is None or fut.ndim == 2) else np.ascontiguousarray(ex[0]),
+                    series_key=(sids[idx].astype(np.int64) << 32) ^ (dids[idx].astype(np.int64) & 0xffffffff),
+                    uncertainty_samples=int(fcfg.get('uncertainty_samples', 1000)), seed=int(fcfg.get('seed', 0)),
+                    cumulative=bool(fcfg.get('cumulative')))
             if fcfg.get('intervals') or fcfg.get('components'):
                 # not in the reference's output (it drops yhat_lower / yhat_upper and the components, :86): opt-in
                 # extra columns; the random streams are keyed by (series_id, dim_id), so a series gets the
@@ -114,7 +126,7 @@ def forecast_arrays(config):
                       f"dim_id: {int(dids[idx[j]])}")                    # :77-79
             if fut.ndim == 1:
                 fut = np.broadcast_to(fut, (len(idx), periods))
-            pieces.append((idx, fut, yint, iv, comps))
+            pieces.append((idx, fut, yint, iv, comps, quant))
             lap('negative check')
         if not pieces:
             return None
@@ -140,6 +152,12 @@ def forecast_arrays(config):
             for name in sorted(set().union(*[p[4].names for p in pieces])):
                 res[name] = np.concatenate([p[4].terms[name].reshape(-1) if name in p[4].terms
                                             else np.zeros(len(p[0]) * periods) for p in pieces])
+        if pieces[0][5] is not None:
+            # forecast.quantiles (+ forecast.cumulative): one column per level, the same levels in every bucket
+            for prefix, attr in (('yhat_q', 'q'), ('yhat_cum_q', 'cum_q')):
+                if getattr(pieces[0][5], attr) is not None:
+                    for i, name in enumerate(fc.quantile_columns(pieces[0][5].quantiles, prefix)):
+                        res[name] = np.concatenate([getattr(p[5], attr)[:, i, :].reshape(-1) for p in pieces])
         lap('columns')
         lap.__exit__()
         return res
