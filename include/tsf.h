@@ -389,6 +389,63 @@ int tsf_predict_quantiles_dev(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int
                               int32_t n_samples, uint64_t seed, int32_t n_q, const double *quantiles,
                               tsf_quantile_out *out, void *stream);
 
+/* ---- group roll-ups: predictive quantiles of sums over series ---------------------------------------
+ * The predictive distribution of a TOTAL over several series -- P90 of a series_id over its dim_ids, of a region, of the
+ * whole panel -- and of its running sum over the future rows.  The point forecast of a total is a sum of yhat columns;
+ * its quantiles are not sums of quantiles, so the draws of the members are summed sample by sample on the device and
+ * the sums are sorted.  A group's members need not share a tsf_spec nor fit one call, so a roll-up is an accumulator
+ * that lives across calls: create, add (once per spec, as often as needed), read quantiles (any time), free.
+ * Reference interface replaced: none (neither the reference nor fbprophet has such a function); parity unpinned (what is
+ * pinned is the contract below, against tsf_predict_quantiles' draws).  Host pointers only, like tsf_cross_validate.
+ * Timing: tools/bench_rollup.py; the first MI355X run is in DESIGN.md 5f.
+ *
+ * Meaning: the members are taken as independent given their fits (each series is fitted alone and draws from its own
+ * stream); where the members' errors are positively correlated in reality, the roll-up's spread is too narrow.
+ *
+ * Rows: every member is forecast on the roll-up's own ds_future[H], one shared calendar; row h of a group is the sum
+ * over its members at row index h.  extra_future is [n_extra][H] with shared_extra set, else [N][n_extra][H].  A
+ * member's forecast is tsf_predict's with shared_future = 1 where the spec has no extra column or shared_extra is
+ * set, and with shared_future = 0 and the calendar repeated per series otherwise.
+ *
+ * Draws: tsf_predict_quantiles' draws for the same (seed, series_key[n], sample); sample s of a member depends on
+ * nothing else.  series_key is required: the "index in this call" default would give series 0 of two add calls the
+ * same stream and a perfectly correlated sum.  Keys that are distinct across calls are the caller's business.
+ *
+ * Accumulation: acc[g][h][s] ([G][H][n_samples]), ysum[g][h] and count[g] belong to the handle and start at +0.0 / 0.
+ * An add performs acc = acc + sample and ysum = ysum + yhat (tsf_predict's float64 value: no int truncation, no floor
+ * clamp), plain double adds, the members of a group one at a time in ascending order of their index in that call; add
+ * calls apply in call order.  The result depends neither on how a call is cut into scratch chunks (512 MB, one sample
+ * buffer) nor on what else the call contains.  No floating-point atomics.
+ *
+ * Quantiles: q[g][i][h] is tsf_predict_quantiles' expression (same pos / lo / hi, same rounding) over the ascending
+ * sort of acc[g][h][0 .. n_samples); cum_q[g][i][h] the same over c[g][h][s], c[g][0][s] = acc[g][0][s],
+ * c[g][h][s] = c[g][h-1][s] + acc[g][h][s], so cum_q[.][.][0] == q[.][.][0] bit for bit.  tsf_rollup_quantiles does
+ * not modify the accumulators: it may be called repeatedly and between adds.  A group nobody was added to has count 0
+ * and 0.0 everywhere.  n_q and the levels as in tsf_predict_quantiles; n_q = 0 is legal only with samples.
+ *
+ * Refusals (< 0 with a message in the context's tsf_last_error, before any launch; the accumulators are untouched and
+ * the context stays usable) -- create: G < 1, H < 1, n_samples outside [2, 4096], NULL ds_future; add: a group value
+ * outside [0, G), NULL series_key, tsf_predict's grid checks, n_extra > 0 with NULL extra_future, logistic growth
+ * without cap, n_grids not 1 or N; quantiles: a bad n_q or level, an output set that wants none of q / cum_q / samples.
+ * N == 0 is a legal no-op.  A failed device allocation in create returns < 0 and leaves nothing behind.  A HIP failure
+ * in the middle of an add poisons the handle: every later call on it returns < 0. */
+typedef struct tsf_rollup tsf_rollup;
+int tsf_rollup_create(tsf_ctx *ctx, int64_t G, int32_t H, const int64_t *ds_future /* [H] */, int32_t n_samples,
+                      uint64_t seed, tsf_rollup **out);
+int tsf_rollup_add(tsf_rollup *r, const tsf_spec *spec, int64_t N, const double *theta, const double *y_scale,
+                   const tsf_grid_info *grid, int32_t n_grids, const double *floor, const double *cap,
+                   const double *extra_future, int32_t shared_extra, const int64_t *series_key /* [N], required */,
+                   const int64_t *group /* [N], each in [0, G) */);
+typedef struct {
+    double *yhat;           /* [G][H]        required: the sum of the members' yhat */
+    int64_t *count;         /* [G]           members added so far; NULL: not wanted */
+    double *q;              /* [G][n_q][H]   per-row quantiles of the summed draws; NULL: not wanted */
+    double *cum_q;          /* [G][n_q][H]   quantiles of each summed sample's running sum over rows 0..h; NULL: not wanted */
+    double *samples;        /* [G][H][n_samples] the summed draws themselves; NULL: not wanted */
+} tsf_rollup_out;
+int tsf_rollup_quantiles(tsf_rollup *r, int32_t n_q, const double *quantiles, tsf_rollup_out *out);
+void tsf_rollup_free(tsf_rollup *r);        /* before tsf_destroy of its context */
+
 /* ---- cross-validation ---------------------------------------------------------------------
  * fbprophet 0.5 diagnostics.cross_validation + performance_metrics for a whole panel: every series is refitted at
  * several cutoffs and each fold's forecast is scored against the rows held out after its cutoff.  The semantics are

@@ -103,6 +103,12 @@ class TsfQuantileOut(ctypes.Structure):
                 ('trend_q', ctypes.c_void_p), ('samples', ctypes.c_void_p), ('trend_samples', ctypes.c_void_p)]
 
 
+class TsfRollupOut(ctypes.Structure):
+    """tsf_rollup_out (include/tsf.h)."""
+    _fields_ = [('yhat', ctypes.c_void_p), ('count', ctypes.c_void_p), ('q', ctypes.c_void_p), ('cum_q', ctypes.c_void_p),
+                ('samples', ctypes.c_void_p)]
+
+
 class TsfTuneOut(ctypes.Structure):
     """tsf_tune_out (include/tsf.h)."""
     _fields_ = [('score', ctypes.c_void_p), ('cand_status', ctypes.c_void_p), ('best', ctypes.c_void_p),
@@ -114,7 +120,8 @@ EXPORTS = ['tsf_create', 'tsf_destroy', 'tsf_last_error', 'tsf_device_count', 't
            'tsf_spec_size', 'tsf_grid_info_size', 'tsf_spec_K', 'tsf_theta_stride',
            'tsf_fit_aligned', 'tsf_fit_aligned_dev', 'tsf_fit_ragged', 'tsf_fit_ragged_dev',
            'tsf_predict', 'tsf_predict_dev', 'tsf_predict_intervals', 'tsf_predict_intervals_dev', 'tsf_predict_components', 'tsf_predict_components_dev',
-           'tsf_predict_quantiles', 'tsf_predict_quantiles_dev', 'tsf_eval', 'tsf_eval_quadratic', 'tsf_design', 'tsf_selftest_math',
+           'tsf_predict_quantiles', 'tsf_predict_quantiles_dev',
+           'tsf_rollup_create', 'tsf_rollup_add', 'tsf_rollup_quantiles', 'tsf_rollup_free', 'tsf_eval', 'tsf_eval_quadratic', 'tsf_design', 'tsf_selftest_math',
            'tsf_set_option', 'tsf_get_option', 'tsf_set_cost_hints', 'tsf_set_profiling', 'tsf_profile_read', 'tsf_last_fit_kernel_ms', 'tsf_last_fit_route',
            'tsf_cv_plan', 'tsf_cross_validate', 'tsf_last_cv_grids', 'tsf_tune', 'tsf_last_tune_counts',
            'tsf_pack_rows', 'tsf_pack_rows_typed', 'tsf_pack_fetch', 'tsf_pack_flags', 'tsf_pack_free', 'tsf_model_blobs',
@@ -184,6 +191,11 @@ def load():
     L.tsf_predict_quantiles.argtypes = [vp, psp, i64, i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, i32, u64, i32, vp,
                                         ctypes.POINTER(TsfQuantileOut)]
     L.tsf_predict_quantiles_dev.argtypes = L.tsf_predict_quantiles.argtypes + [vp]
+    L.tsf_rollup_create.argtypes = [vp, i64, i32, vp, i32, u64, ctypes.POINTER(vp)]
+    L.tsf_rollup_add.argtypes = [vp, psp, i64, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp]
+    L.tsf_rollup_quantiles.argtypes = [vp, i32, vp, ctypes.POINTER(TsfRollupOut)]
+    L.tsf_rollup_free.argtypes = [vp]
+    L.tsf_rollup_free.restype = None
     L.tsf_eval.argtypes = [vp, psp, i64, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     L.tsf_eval_quadratic.argtypes = [vp, psp, i64, i32, vp, vp, i32, vp, vp, vp, vp, vp]
     L.tsf_design.argtypes = [vp, psp, i32, vp, vp, vp, vp, vp]

@@ -22,6 +22,7 @@
 
 #include "tsf_aux_kernels.h"
 #include "tsf_interval_kernels.h"
+#include "tsf_rollup_kernels.h"
 #include "tsf_component_kernels.h"
 #include "tsf_fit_kernels.h"
 #include "tsf_quad_kernels.h"
@@ -1835,15 +1836,32 @@ static int check_quantile_args(tsf_ctx *ctx, int32_t n_samples, int32_t n_q, con
     return 0;
 }
 
-// The work of both entries on device-resident inputs.  The quantile outputs of `o` are device pointers; its two sample
-// outputs are copied out of the chunk's scratch in stream order with `kind` (device to device for the _dev entry,
-// device to host for the host entry, which therefore never holds N * H * n_samples values on the device).
-static int predict_quantiles_run(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H, const double *theta,
-                                 const double *y_scale, const tsf_grid_info *grid, int32_t n_grids,
-                                 const int64_t *ds_future, int32_t shared_future, const double *floor_,
-                                 const double *cap, const double *extra_future, const int64_t *series_key,
-                                 int32_t n_samples, uint64_t seed, int32_t n_q, const double *quantiles,
-                                 const tsf_quantile_out &o, hipMemcpyKind kind, hipStream_t st)
+// The draw loop of tsf_predict_quantiles and tsf_rollup_add on device-resident inputs: per chunk of series
+// launch_predict (yhat and the three per-row pieces), then interval_sample_kernel, then `after(n0, nc, bufs)` on the
+// same stream -- what the caller does with the chunk's draws before the next chunk overwrites them.
+// tsf_predict_intervals_dev's scheme: a chunk's scratch -- the three per-row pieces and every sample buffer the call
+// needs (yhat always; the running sums with want_cum; the trend with want_trend) -- stays within 512 MB of the same
+// cached block.
+struct DrawBufs {
+    double *samp, *cum, *trend;     // [n_chunk][H][n_samples] each; cum / trend null where not asked for
+};
+
+// series per chunk: n_buf sample buffers and the three per-row pieces of a chunk within 512 MB
+static int64_t draw_chunk_series(int64_t N, int32_t H, int32_t n_samples, size_t n_buf)
+{
+    const size_t per_series = (size_t)H * 8 * (3 + n_buf * (size_t)n_samples);
+    int64_t chunk = (int64_t)(((size_t)512 << 20) / per_series);
+    if (chunk < 1) chunk = 1;
+    if (chunk > N) chunk = N;
+    return chunk;
+}
+
+template <class After>
+static int draw_chunks(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H, const double *theta,
+                       const double *y_scale, const tsf_grid_info *grid, int32_t n_grids, const int64_t *ds_future,
+                       int32_t shared_future, const double *floor_, const double *cap, const double *extra_future,
+                       const int64_t *series_key, int32_t n_samples, uint64_t seed, bool want_cum, bool want_trend,
+                       double *yhat, hipStream_t st, After &&after)
 {
     DevSpec hs;
     int mode = 0;
@@ -1852,15 +1870,8 @@ static int predict_quantiles_run(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, 
     if (hs.n_extra > 0 && !extra_future) return fail(ctx, "extra_future is NULL");
     if (hs.growth == TSF_GROWTH_LOGISTIC && !cap) return fail(ctx, "logistic growth needs cap");
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_spec, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
-    // tsf_predict_intervals_dev's scheme: a chunk's scratch -- the three per-row pieces and every sample buffer the
-    // call needs (yhat always; the running sums for cum_q; the trend for trend_q / trend_samples) -- stays within
-    // 512 MB of the same cached block
-    const bool want_cum = o.cum_q != nullptr, want_trend = o.trend_q || o.trend_samples;
     const size_t n_buf = 1 + (size_t)want_cum + (size_t)want_trend;
-    const size_t per_series = (size_t)H * 8 * (3 + n_buf * (size_t)n_samples);
-    int64_t chunk = (int64_t)(((size_t)512 << 20) / per_series);
-    if (chunk < 1) chunk = 1;
-    if (chunk > N) chunk = N;
+    const int64_t chunk = draw_chunk_series(N, H, n_samples, n_buf);
     const size_t nh = (size_t)chunk * H;
     const size_t need = 8 * nh * (3 + n_buf * (size_t)n_samples);
     if (ctx->iv_ws_bytes < need) {
@@ -1878,21 +1889,15 @@ static int predict_quantiles_run(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, 
     p.sp = ctx->d_spec; p.N = N; p.H = H; p.theta_stride = tsf_theta_stride(spec);
     p.n_grids = n_grids; p.shared_future = shared_future; p.theta = theta; p.y_scale = y_scale;
     p.grid = grid; p.ds_future = ds_future; p.floor_ = floor_; p.cap = cap;
-    p.extra_future = extra_future; p.yhat = o.yhat; p.yhat_int = nullptr;
+    p.extra_future = extra_future; p.yhat = yhat; p.yhat_int = nullptr;
     p.t_out = d_t; p.xa_out = d_xa; p.opm_out = d_opm;
-    int NSP = 2;
-    while (NSP < n_samples) NSP <<= 1;
     IntervalArgs a;
     memset(&a, 0, sizeof(a));
     a.sp = ctx->d_spec; a.H = H; a.theta_stride = tsf_theta_stride(spec); a.n_grids = n_grids; a.NS = n_samples;
     a.theta = theta; a.y_scale = y_scale; a.grid = grid; a.floor_ = floor_; a.cap = cap;
     a.series_key = series_key; a.seed = seed;
     a.samples = d_samp; a.trend_samples = d_tsamp; a.cum_samples = d_cum;
-    QuantileArgs q;
-    memset(&q, 0, sizeof(q));
-    q.H = H; q.NS = n_samples; q.n_q = n_q;
-    for (int32_t i = 0; i < n_q; ++i) q.level[i] = quantiles[i];
-    const struct { const double *src; double *dst; } sorts[3] = {{d_samp, o.q}, {d_cum, o.cum_q}, {d_tsamp, o.trend_q}};
+    const DrawBufs bufs = {d_samp, d_cum, d_tsamp};
     bool tab_ready = false;
     for (int64_t n0 = 0; n0 < N; n0 += chunk) {
         const int64_t nc = (N - n0 < chunk) ? N - n0 : chunk;
@@ -1902,6 +1907,29 @@ static int predict_quantiles_run(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, 
         hipLaunchKernelGGL(interval_sample_kernel, dim3((unsigned)nc, (unsigned)((n_samples + 255) / 256)),
                            dim3(256), 0, st, a);
         HIP_TRY(ctx, hipGetLastError());
+        if (int arc = after(n0, nc, bufs)) return arc;
+    }
+    return 0;
+}
+
+// The work of both quantile entries on device-resident inputs.  The quantile outputs of `o` are device pointers; its
+// two sample outputs are copied out of the chunk's scratch in stream order with `kind` (device to device for the _dev
+// entry, device to host for the host entry, which therefore never holds N * H * n_samples values on the device).
+static int predict_quantiles_run(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H, const double *theta,
+                                 const double *y_scale, const tsf_grid_info *grid, int32_t n_grids,
+                                 const int64_t *ds_future, int32_t shared_future, const double *floor_,
+                                 const double *cap, const double *extra_future, const int64_t *series_key,
+                                 int32_t n_samples, uint64_t seed, int32_t n_q, const double *quantiles,
+                                 const tsf_quantile_out &o, hipMemcpyKind kind, hipStream_t st)
+{
+    int NSP = 2;
+    while (NSP < n_samples) NSP <<= 1;
+    QuantileArgs q;
+    memset(&q, 0, sizeof(q));
+    q.H = H; q.NS = n_samples; q.n_q = n_q;
+    for (int32_t i = 0; i < n_q; ++i) q.level[i] = quantiles[i];
+    auto after = [&](int64_t n0, int64_t nc, const DrawBufs &b) -> int {
+        const struct { const double *src; double *dst; } sorts[3] = {{b.samp, o.q}, {b.cum, o.cum_q}, {b.trend, o.trend_q}};
         for (const auto &so : sorts) {
             if (!so.dst) continue;
             q.src = so.src; q.dst = so.dst; q.n0 = n0;
@@ -1910,10 +1938,13 @@ static int predict_quantiles_run(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, 
         }
         // the raw draws leave the scratch before the next chunk overwrites it (stream order)
         const size_t off = (size_t)n0 * H * n_samples, nb = 8 * (size_t)nc * H * n_samples;
-        if (o.samples) HIP_TRY(ctx, hipMemcpyAsync(o.samples + off, d_samp, nb, kind, st));
-        if (o.trend_samples) HIP_TRY(ctx, hipMemcpyAsync(o.trend_samples + off, d_tsamp, nb, kind, st));
-    }
-    return 0;
+        if (o.samples) HIP_TRY(ctx, hipMemcpyAsync(o.samples + off, b.samp, nb, kind, st));
+        if (o.trend_samples) HIP_TRY(ctx, hipMemcpyAsync(o.trend_samples + off, b.trend, nb, kind, st));
+        return 0;
+    };
+    return draw_chunks(ctx, spec, N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap,
+                       extra_future, series_key, n_samples, seed, o.cum_q != nullptr, o.trend_q || o.trend_samples,
+                       o.yhat, st, after);
 }
 
 extern "C" int tsf_predict_quantiles_dev(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H,
@@ -1990,6 +2021,271 @@ extern "C" int tsf_predict_quantiles(tsf_ctx *ctx, const tsf_spec *spec, int64_t
     if (out->q) HIP_TRY(ctx, hipMemcpy(out->q, d_q.p, nqh, hipMemcpyDeviceToHost));
     if (out->cum_q) HIP_TRY(ctx, hipMemcpy(out->cum_q, d_cq.p, nqh, hipMemcpyDeviceToHost));
     if (out->trend_q) HIP_TRY(ctx, hipMemcpy(out->trend_q, d_tq.p, nqh, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- group roll-ups: predictive quantiles of sums over series ---------------------------------------------
+
+// The accumulators of one roll-up (include/tsf.h): owned by the handle, not carved from the context's scratch.
+struct tsf_rollup {
+    tsf_ctx *ctx;
+    int64_t G;
+    int32_t H, S;
+    uint64_t seed;
+    int64_t *d_ds;                  // [H] the roll-up's calendar
+    double *acc;                    // [G][H][S]
+    double *ysum;                   // [G][H]
+    std::vector<int64_t> count;     // [G] members added so far (host)
+    bool poisoned;                  // a HIP failure in the middle of an add: the accumulators may be half-added
+};
+
+static void rollup_release(tsf_rollup *r)
+{
+    if (r->d_ds) (void)hipFree(r->d_ds);
+    if (r->acc) (void)hipFree(r->acc);
+    if (r->ysum) (void)hipFree(r->ysum);
+    delete r;
+}
+
+extern "C" int tsf_rollup_create(tsf_ctx *ctx, int64_t G, int32_t H, const int64_t *ds_future, int32_t n_samples,
+                                 uint64_t seed, tsf_rollup **out)
+{
+    if (!ctx) return -1;
+    if (!out) return fail(ctx, "NULL out");
+    *out = nullptr;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (G < 1 || G > 2147483647) return fail(ctx, "G must be in [1, 2^31 - 1]");
+    if (H < 1) return fail(ctx, "H must be >= 1");
+    if (n_samples < 2 || n_samples > 4096) return fail(ctx, "n_samples must be in [2, 4096]");
+    if (!ds_future) return fail(ctx, "NULL ds_future");
+    tsf_rollup *r = new tsf_rollup();
+    r->ctx = ctx; r->G = G; r->H = H; r->S = n_samples; r->seed = seed;
+    r->d_ds = nullptr; r->acc = nullptr; r->ysum = nullptr; r->poisoned = false;
+    const size_t gh = (size_t)G * H;
+    hipError_t e = hipMalloc((void **)&r->d_ds, 8 * (size_t)H);
+    if (e == hipSuccess) e = hipMalloc((void **)&r->acc, 8 * gh * n_samples);
+    if (e == hipSuccess) e = hipMalloc((void **)&r->ysum, 8 * gh);
+    if (e == hipSuccess) e = hipMemcpy(r->d_ds, ds_future, 8 * (size_t)H, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(r->acc, 0, 8 * gh * n_samples);       // +0.0
+    if (e == hipSuccess) e = hipMemset(r->ysum, 0, 8 * gh);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        ctx->err = std::string("tsf_rollup_create: ") + hipGetErrorString(e);
+        (void)hipGetLastError();        // (an allocation failure is not sticky once read: the context stays usable)
+        rollup_release(r);
+        return -2;
+    }
+    try {
+        r->count.assign((size_t)G, 0);
+    } catch (const std::bad_alloc &) {
+        rollup_release(r);
+        return fail(ctx, "tsf_rollup_create: out of host memory");
+    }
+    *out = r;
+    return 0;
+}
+
+extern "C" void tsf_rollup_free(tsf_rollup *r)
+{
+    if (!r) return;
+    hipSetDevice(r->ctx->device);
+    rollup_release(r);
+}
+
+// The small CSR of one add call, per scratch chunk [n0, n0 + nc): the groups the chunk touches (ascending) and, per
+// such group, its chunk-local members in ascending order.  One int32 buffer: touched | first | member.
+struct RollupPlan {
+    std::vector<int32_t> touched, first, member;            // all chunks, one after another
+    std::vector<size_t> t0, f0;                             // per chunk: where its touched / first entries start
+};
+
+static void rollup_plan(const int64_t *group, int64_t N, int64_t chunk, RollupPlan *P)
+{
+    P->member.resize((size_t)N);
+    std::vector<std::pair<int64_t, int32_t>> order;
+    for (int64_t n0 = 0; n0 < N; n0 += chunk) {
+        const int64_t nc = (N - n0 < chunk) ? N - n0 : chunk;
+        order.clear();
+        for (int64_t i = 0; i < nc; ++i) order.push_back({group[n0 + i], (int32_t)i});
+        std::sort(order.begin(), order.end());              // by group, then by index in the call
+        P->t0.push_back(P->touched.size());
+        P->f0.push_back(P->first.size());
+        for (int64_t i = 0; i < nc; ++i) {
+            if (i == 0 || order[i].first != order[i - 1].first) {
+                P->touched.push_back((int32_t)order[i].first);
+                P->first.push_back((int32_t)i);
+            }
+            P->member[(size_t)(n0 + i)] = order[i].second;
+        }
+        P->first.push_back((int32_t)nc);
+    }
+}
+
+extern "C" int tsf_rollup_add(tsf_rollup *r, const tsf_spec *spec, int64_t N, const double *theta, const double *y_scale,
+                              const tsf_grid_info *grid, int32_t n_grids, const double *floor_, const double *cap,
+                              const double *extra_future, int32_t shared_extra, const int64_t *series_key,
+                              const int64_t *group)
+{
+    if (!r) return -1;
+    tsf_ctx *ctx = r->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (r->poisoned) return fail(ctx, "the roll-up is poisoned: an earlier tsf_rollup_add failed in the middle");
+    if (N < 0) return fail(ctx, "N must be >= 0");
+    if (N == 0) return 0;
+    if (N > 2147483647) return fail(ctx, "N must be < 2^31 per call");
+    if (!spec || !theta || !y_scale || !grid) return fail(ctx, "NULL input");
+    if (!series_key)
+        return fail(ctx, "series_key is required: the index-in-call default would give two calls the same streams");
+    if (!group) return fail(ctx, "NULL group");
+    if (n_grids != 1 && n_grids != N) return fail(ctx, "n_grids must be 1 or N");
+    for (int64_t n = 0; n < N; ++n)
+        if (group[n] < 0 || group[n] >= r->G) {
+            char msg[120];
+            snprintf(msg, sizeof(msg), "group[%lld] = %lld: outside [0, G = %lld)", (long long)n, (long long)group[n],
+                     (long long)r->G);
+            return fail(ctx, msg);
+        }
+    if (int rc = check_grids(ctx, spec, grid, n_grids)) return rc;
+    {
+        DevSpec hs;
+        int mode = 0;
+        if (int rc = build_devspec(ctx, spec, &hs, &mode)) return rc;
+    }
+    if (spec->n_extra > 0 && !extra_future) return fail(ctx, "extra_future is NULL");
+    if (spec->growth == TSF_GROWTH_LOGISTIC && !cap) return fail(ctx, "logistic growth needs cap");
+    // shared extra columns (or none): tsf_predict on the shared calendar; per-series columns: tsf_predict with the
+    // calendar repeated per series (shared_future = 0), which is what their layout [N][n_extra][H] belongs to
+    const int32_t H = r->H, S = r->S;
+    const int shared = (spec->n_extra == 0 || shared_extra) ? 1 : 0;
+    const int stride = tsf_theta_stride(spec);
+    const int64_t chunk = draw_chunk_series(N, H, S, 1);       // draw_chunks' chunks: one sample buffer
+    RollupPlan P;
+    std::vector<int64_t> ds_rep;
+    try {
+        rollup_plan(group, N, chunk, &P);
+        if (!shared) ds_rep.resize((size_t)N * H);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, "tsf_rollup_add: out of host memory");
+    }
+    DevBuf d_th, d_ys, d_grid, d_ds, d_fl, d_cap, d_ex, d_key, d_yh, d_csr;
+    HIP_TRY(ctx, d_th.alloc(8 * (size_t)N * stride));
+    HIP_TRY(ctx, hipMemcpy(d_th.p, theta, 8 * (size_t)N * stride, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_ys.alloc(8 * N));
+    HIP_TRY(ctx, hipMemcpy(d_ys.p, y_scale, 8 * N, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_grid.alloc(sizeof(tsf_grid_info) * n_grids));
+    HIP_TRY(ctx, hipMemcpy(d_grid.p, grid, sizeof(tsf_grid_info) * n_grids, hipMemcpyHostToDevice));
+    if (floor_) { HIP_TRY(ctx, d_fl.alloc(8 * N)); HIP_TRY(ctx, hipMemcpy(d_fl.p, floor_, 8 * N, hipMemcpyHostToDevice)); }
+    if (cap) { HIP_TRY(ctx, d_cap.alloc(8 * N)); HIP_TRY(ctx, hipMemcpy(d_cap.p, cap, 8 * N, hipMemcpyHostToDevice)); }
+    HIP_TRY(ctx, d_key.alloc(8 * N));
+    HIP_TRY(ctx, hipMemcpy(d_key.p, series_key, 8 * N, hipMemcpyHostToDevice));
+    if (spec->n_extra > 0) {
+        const size_t nb = 8 * (size_t)spec->n_extra * H * (shared ? 1 : (size_t)N);
+        HIP_TRY(ctx, d_ex.alloc(nb));
+        HIP_TRY(ctx, hipMemcpy(d_ex.p, extra_future, nb, hipMemcpyHostToDevice));
+    }
+    const int64_t *ds_dev = r->d_ds;
+    if (!shared) {
+        HIP_TRY(ctx, hipMemcpy(ds_rep.data(), r->d_ds, 8 * (size_t)H, hipMemcpyDeviceToHost));
+        for (int64_t n = 1; n < N; ++n) memcpy(&ds_rep[(size_t)n * H], ds_rep.data(), 8 * (size_t)H);
+        HIP_TRY(ctx, d_ds.alloc(8 * (size_t)N * H));
+        HIP_TRY(ctx, hipMemcpy(d_ds.p, ds_rep.data(), 8 * (size_t)N * H, hipMemcpyHostToDevice));
+        ds_dev = d_ds.as<int64_t>();
+    }
+    HIP_TRY(ctx, d_yh.alloc(8 * (size_t)N * H));
+    const size_t n_t = P.touched.size(), n_f = P.first.size();
+    HIP_TRY(ctx, d_csr.alloc(4 * (n_t + n_f + (size_t)N)));
+    int32_t *d_touched = d_csr.as<int32_t>(), *d_first = d_touched + n_t, *d_member = d_first + n_f;
+    HIP_TRY(ctx, hipMemcpy(d_touched, P.touched.data(), 4 * n_t, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(d_first, P.first.data(), 4 * n_f, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(d_member, P.member.data(), 4 * (size_t)N, hipMemcpyHostToDevice));
+    // from here on the accumulators are written: any failure leaves them half-added, so the handle is poisoned
+    r->poisoned = true;
+    RollupAddArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    ra.acc = r->acc; ra.ysum = r->ysum; ra.H = H; ra.NS = S;
+    auto after = [&](int64_t n0, int64_t nc, const DrawBufs &b) -> int {
+        const size_t c = (size_t)(n0 / chunk);
+        const size_t n_touched = (c + 1 < P.t0.size() ? P.t0[c + 1] : n_t) - P.t0[c];
+        ra.samples = b.samp; ra.yhat = d_yh.as<double>() + (size_t)n0 * H;
+        ra.touched = d_touched + P.t0[c]; ra.first = d_first + P.f0[c]; ra.member = d_member + n0;
+        (void)nc;
+        hipLaunchKernelGGL(rollup_add_kernel, dim3((unsigned)(n_touched * (size_t)H), (unsigned)((S + 255) / 256)), dim3(256), 0,
+                           nullptr, ra);
+        HIP_TRY(ctx, hipGetLastError());
+        return 0;
+    };
+    int rc = draw_chunks(ctx, spec, N, H, d_th.as<double>(), d_ys.as<double>(), d_grid.as<tsf_grid_info>(), n_grids,
+                         ds_dev, shared, floor_ ? d_fl.as<double>() : nullptr, cap ? d_cap.as<double>() : nullptr,
+                         spec->n_extra > 0 ? d_ex.as<double>() : nullptr, d_key.as<int64_t>(), S, r->seed, false, false,
+                         d_yh.as<double>(), nullptr, after);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    r->poisoned = false;
+    for (int64_t n = 0; n < N; ++n) r->count[(size_t)group[n]] += 1;
+    return 0;
+}
+
+extern "C" int tsf_rollup_quantiles(tsf_rollup *r, int32_t n_q, const double *quantiles, tsf_rollup_out *out)
+{
+    if (!r) return -1;
+    tsf_ctx *ctx = r->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (r->poisoned) return fail(ctx, "the roll-up is poisoned: an earlier tsf_rollup_add failed in the middle");
+    if (!out) return fail(ctx, "NULL output (tsf_rollup_out and its yhat are required)");
+    {
+        tsf_quantile_out chk;
+        memset(&chk, 0, sizeof(chk));
+        chk.yhat = out->yhat; chk.q = out->q; chk.cum_q = out->cum_q; chk.samples = out->samples;
+        if (int rc = check_quantile_args(ctx, r->S, n_q, quantiles, &chk)) return rc;
+    }
+    const int32_t H = r->H, S = r->S;
+    const int64_t G = r->G;
+    const size_t hs = (size_t)H * S, gh = (size_t)G * H, nqh = 8 * gh * (size_t)n_q;
+    int NSP = 2;
+    while (NSP < S) NSP <<= 1;
+    QuantileArgs q;
+    memset(&q, 0, sizeof(q));
+    q.H = H; q.NS = S; q.n_q = n_q;
+    for (int32_t i = 0; i < n_q; ++i) q.level[i] = quantiles[i];
+    DevBuf d_q, d_cq;
+    if (out->q) {
+        // quantile_kernel reads the accumulator in place, a range of groups per launch (its grid is groups * H)
+        HIP_TRY(ctx, d_q.alloc(nqh));
+        const int64_t range = std::max<int64_t>(1, ((int64_t)1 << 30) / H);
+        for (int64_t g0 = 0; g0 < G; g0 += range) {
+            const int64_t gc = std::min(range, G - g0);
+            q.src = r->acc + (size_t)g0 * hs; q.dst = d_q.as<double>(); q.n0 = g0;
+            hipLaunchKernelGGL(quantile_kernel, dim3((unsigned)(gc * H)), dim3(256), sizeof(double) * NSP, nullptr, q, NSP);
+            HIP_TRY(ctx, hipGetLastError());
+        }
+    }
+    if (out->cum_q) {
+        // the running sums of a range of groups in the context's scratch (within its 512 MB), sorted from there
+        HIP_TRY(ctx, d_cq.alloc(nqh));
+        const int64_t range = std::max<int64_t>(1, std::min<int64_t>(G, (int64_t)(((size_t)512 << 20) / (8 * hs))));
+        const size_t need = 8 * (size_t)range * hs;
+        if (ctx->iv_ws_bytes < need) {
+            if (ctx->iv_ws) { HIP_TRY(ctx, hipFree(ctx->iv_ws)); ctx->iv_ws = nullptr; ctx->iv_ws_bytes = 0; }
+            HIP_TRY(ctx, hipMalloc(&ctx->iv_ws, need));
+            ctx->iv_ws_bytes = need;
+        }
+        double *d_c = (double *)ctx->iv_ws;
+        for (int64_t g0 = 0; g0 < G; g0 += range) {
+            const int64_t gc = std::min(range, G - g0);
+            hipLaunchKernelGGL(rollup_cumsum_kernel, dim3((unsigned)((gc * S + 255) / 256)), dim3(256), 0, nullptr,
+                               r->acc + (size_t)g0 * hs, d_c, gc, H, S);
+            HIP_TRY(ctx, hipGetLastError());
+            q.src = d_c; q.dst = d_cq.as<double>(); q.n0 = g0;
+            hipLaunchKernelGGL(quantile_kernel, dim3((unsigned)(gc * H)), dim3(256), sizeof(double) * NSP, nullptr, q, NSP);
+            HIP_TRY(ctx, hipGetLastError());
+        }
+    }
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    HIP_TRY(ctx, hipMemcpy(out->yhat, r->ysum, 8 * gh, hipMemcpyDeviceToHost));
+    if (out->count) memcpy(out->count, r->count.data(), 8 * (size_t)G);
+    if (out->q) HIP_TRY(ctx, hipMemcpy(out->q, d_q.p, nqh, hipMemcpyDeviceToHost));
+    if (out->cum_q) HIP_TRY(ctx, hipMemcpy(out->cum_q, d_cq.p, nqh, hipMemcpyDeviceToHost));
+    if (out->samples) HIP_TRY(ctx, hipMemcpy(out->samples, r->acc, 8 * gh * S, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -1,0 +1,69 @@
+// Group roll-ups (include/tsf.h "group roll-ups"): the draws of interval_sample_kernel summed across the series
+// of a group, sample by sample, into accumulators that live across calls (tsf_rollup).
+//   rollup_add_kernel     one thread per (touched group, row, sample): it adds the group's members of this chunk one
+//                         at a time in list order -- a streaming pass with a fixed order of double adds per
+//                         accumulator cell (no atomics, no LDS, no cross-lane traffic)
+//   rollup_cumsum_kernel  one thread per (group, sample): the running sum of the accumulator over the rows, for the
+//                         cumulative quantiles (quantile_kernel sorts it, as it sorts the accumulator itself)
+// Non-template __global__ functions: include from exactly one translation unit (tsf_api.hip).
+#pragma once
+#include "tsf_common.h"
+
+namespace tsf {
+
+struct RollupAddArgs {
+    const double *samples;      // [n_chunk][H][NS] of the chunk (interval_sample_kernel's output)
+    const double *yhat;         // [n_chunk][H] of the chunk (predict_kernel's output)
+    double *acc;                // [G][H][NS]
+    double *ysum;               // [G][H]
+    const int32_t *touched;     // [n_touched] groups this chunk has members of
+    const int32_t *first;       // [n_touched + 1] offsets into `member`
+    const int32_t *member;      // chunk-local series indices, ascending within a group
+    int H, NS;
+};
+
+// grid (n_touched * H, ceil(NS / 256)), 256 threads: thread t of block (x, y) owns sample 256 y + t of one (touched
+// group, row).  Lanes are contiguous in the sample index: every load and store is a coalesced 8-byte-per-lane stream.
+// A cell's adds happen in one thread, in the order of `member`; the loads of the next members do not wait for them.
+__global__ __launch_bounds__(256) void rollup_add_kernel(RollupAddArgs a)
+{
+    const int k = (int)(blockIdx.x / (unsigned)a.H);
+    const int h = (int)(blockIdx.x - (unsigned)k * (unsigned)a.H);
+    const int64_t g = a.touched[k];
+    const int m0 = a.first[k], m1 = a.first[k + 1];
+    const int s = (int)(blockIdx.y * 256 + threadIdx.x);
+    if (s < a.NS) {
+        double *acc = a.acc + ((size_t)g * a.H + h) * a.NS + s;
+        const double *src = a.samples + (size_t)h * a.NS + s;
+        const size_t stride = (size_t)a.H * a.NS;
+        double v = *acc;
+#pragma unroll 4
+        for (int i = m0; i < m1; ++i) v = v + src[(size_t)a.member[i] * stride];
+        *acc = v;
+    }
+    if (blockIdx.y == 0 && threadIdx.x == 0) {
+        double y = a.ysum[(size_t)g * a.H + h];
+        for (int i = m0; i < m1; ++i) y = y + a.yhat[(size_t)a.member[i] * a.H + h];
+        a.ysum[(size_t)g * a.H + h] = y;
+    }
+}
+
+// c[g][0][s] = acc[g][0][s], c[g][h][s] = c[g][h-1][s] + acc[g][h][s] for n_groups groups (acc and c point at the
+// first of them).  One thread per (group, sample), consecutive threads on consecutive samples.
+__global__ __launch_bounds__(256) void rollup_cumsum_kernel(const double *acc, double *c, int64_t n_groups, int H, int NS)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_groups * NS) return;
+    const int64_t g = i / NS;
+    const int s = (int)(i - g * NS);
+    const double *src = acc + (size_t)g * H * NS + s;
+    double *dst = c + (size_t)g * H * NS + s;
+    double run = 0.0;
+    for (int h = 0; h < H; ++h) {
+        const double v = src[(size_t)h * NS];
+        run = (h == 0) ? v : run + v;
+        dst[(size_t)h * NS] = run;
+    }
+}
+
+}  // namespace tsf

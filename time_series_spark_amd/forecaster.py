@@ -812,6 +812,195 @@ def predictive_samples(spec, theta, y_scale, grid, ds_future_ns, floor=None, cap
     return {'yhat': r['samples'], 'trend': r['trend_samples']}
 
 
+# ---- group roll-ups: predictive quantiles of sums over series --------------------------------------
+# The distribution of a total over several series (include/tsf.h "group roll-ups"): the members' draws summed sample by
+# sample on the device, across specs and calls, then sorted.  Members are taken as independent given their fits: where
+# their errors are positively correlated in reality the spread is too narrow.
+
+def rollup_groups(labels):
+    """Group labels -> (unique_sorted_labels, dense_index int64 [N]): the `group` argument of Rollup.add.  labels: one
+    integer array [N], or a tuple of them (a group per distinct combination; the unique labels are then [G][len(tuple)],
+    sorted by the first array, then the second, ...).  Pure numpy."""
+    if isinstance(labels, tuple):
+        cols = [np.asarray(a) for a in labels]
+        if not cols or any(c.ndim != 1 or c.shape != cols[0].shape for c in cols):
+            raise ValueError('labels: a tuple of equally long 1-d integer arrays')
+        lab = np.stack(cols, axis=1)
+    else:
+        lab = np.asarray(labels)
+        if lab.ndim != 1:
+            raise ValueError('labels: a 1-d integer array or a tuple of them')
+    if lab.size and lab.dtype.kind not in 'iu':
+        raise ValueError('labels must be integers')
+    if lab.shape[0] == 0:
+        return lab.astype(np.int64), np.zeros(0, dtype=np.int64)
+    uniq, inv = np.unique(lab, axis=0, return_inverse=True)
+    return uniq, np.ascontiguousarray(inv, dtype=np.int64).reshape(-1)
+
+
+class RollupQuantiles(object):
+    """What Rollup.quantiles returns: yhat [G][H] (the sum of the members' yhat); count [G] (members added); quantiles [Q]
+    (the levels as given); q [G][Q][H]; cum_q [G][Q][H] or None."""
+
+    def __init__(self, yhat, count, quantiles, q, cum_q=None):
+        self.yhat, self.count, self.quantiles, self.q, self.cum_q = yhat, count, quantiles, q, cum_q
+
+    def frame(self, g, ds):
+        """Group g as a DataFrame: ds, yhat, yhat_q<..> per level, then yhat_cum_q<..> where computed (names:
+        quantile_columns)."""
+        import pandas as pd
+        ds = np.asarray(ds)
+        if ds.dtype.kind != 'M':
+            ds = ds.astype(np.int64).view('datetime64[ns]')
+        cols = {'ds': ds, 'yhat': self.yhat[g]}
+        for prefix, arr in (('yhat_q', self.q), ('yhat_cum_q', self.cum_q)):
+            if arr is not None:
+                for i, name in enumerate(quantile_columns(self.quantiles, prefix)):
+                    cols[name] = arr[g, i]
+        return pd.DataFrame(cols, columns=list(cols))
+
+
+def _rollup_add_args(spec, theta, y_scale, grid, group, series_key, floor, cap, extra_future, G, H):
+    """The arguments of one Rollup.add as the library takes them; every shape error is a ValueError raised here, before
+    the library is touched."""
+    theta = np.ascontiguousarray(theta, dtype=np.float64)
+    if theta.ndim != 2:
+        raise ValueError('theta must be [N][stride]')
+    N = theta.shape[0]
+    if series_key is None:
+        raise ValueError('series_key is required: the index-in-call default would give two add calls the same streams')
+    key = np.ascontiguousarray(series_key, dtype=np.int64)
+    if key.shape != (N,):
+        raise ValueError('series_key must be [N]')
+    group = np.ascontiguousarray(group, dtype=np.int64)
+    if group.shape != (N,):
+        raise ValueError('group must be [N]')
+    if N and (group.min() < 0 or group.max() >= G):
+        raise ValueError('group values must be in [0, %d)' % G)
+    y_scale = np.ascontiguousarray(y_scale, dtype=np.float64)
+    if y_scale.shape != (N,):
+        raise ValueError('y_scale must be [N]')
+    grid = np.ascontiguousarray(grid, dtype=_lib.GRID_DTYPE)
+    floor = _opt_f64(floor, N, 'floor')
+    cap = _opt_f64(cap, N, 'cap')
+    ex, shared = None, 1
+    if spec.extra:
+        if extra_future is None:
+            raise ValueError('extra_future is required: the spec has extra columns')
+        ex = np.ascontiguousarray(extra_future, dtype=np.float64)
+        shared = int(ex.ndim == 2)
+        shape = (len(spec.extra), H) if shared else (N, len(spec.extra), H)
+        if ex.shape != shape:
+            raise ValueError('extra_future must be [n_extra][H] or [N][n_extra][H]')
+    return N, theta, y_scale, grid, group, key, floor, cap, ex, shared
+
+
+class Rollup(object):
+    """One tsf_rollup: n_groups accumulators of uncertainty_samples summed draws per row of ds_future_ns [H], filled by
+    add (once per spec, any number of calls) and read by quantiles / samples at any time.  A context manager; close()
+    frees the device memory (before its context is closed).  Shape and level errors raise ValueError before the library
+    is touched."""
+
+    def __init__(self, ds_future_ns, n_groups, uncertainty_samples=1000, seed=0, ctx=None):
+        self._h = None
+        ds = np.ascontiguousarray(ds_future_ns, dtype=np.int64)
+        if ds.ndim != 1 or ds.shape[0] < 1:
+            raise ValueError('ds_future must be [H], H >= 1: a roll-up has one calendar')
+        if int(n_groups) < 1:
+            raise ValueError('n_groups must be >= 1')
+        if not 2 <= int(uncertainty_samples) <= 4096:
+            raise ValueError('uncertainty_samples must be in [2, 4096]')
+        self.ds_future_ns, self.G, self.H, self.S = ds, int(n_groups), ds.shape[0], int(uncertainty_samples)
+        self.seed = int(seed)
+        self._ctx = ctx or get_context()
+        h = ctypes.c_void_p()
+        self._ctx.check(_lib.load().tsf_rollup_create(self._ctx.handle, self.G, self.H, ds.ctypes.data, self.S, self.seed,
+                                                      ctypes.byref(h)))
+        self._h = h
+
+    def _handle(self):
+        if not self._h:
+            raise ValueError('the roll-up is closed')
+        return self._h
+
+    def close(self):
+        if getattr(self, '_h', None):
+            _lib.load().tsf_rollup_free(self._h)
+        self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, spec, theta, y_scale, grid, group, series_key, floor=None, cap=None, extra_future=None):
+        """Adds N series of one spec: group [N] (dense indices in [0, n_groups): rollup_groups), series_key [N]
+        (required: the streams of two add calls must differ; the scorer's is (series_id << 32) ^ dim_id).  extra_future:
+        [n_extra][H] shared by the series, or [N][n_extra][H]."""
+        h = self._handle()
+        N, theta, y_scale, grid, group, key, floor, cap, ex, shared = _rollup_add_args(
+            spec, theta, y_scale, grid, group, series_key, floor, cap, extra_future, self.G, self.H)
+        cs = spec.to_c()
+        self._ctx.check(_lib.load().tsf_rollup_add(h, ctypes.byref(cs), N, theta.ctypes.data, y_scale.ctypes.data,
+                                                   grid.ctypes.data, len(grid), _lib._ptr(floor), _lib._ptr(cap),
+                                                   _lib._ptr(ex), shared, key.ctypes.data, group.ctypes.data))
+
+    def _read(self, levels, want):
+        h = self._handle()
+        levels = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
+        Q = len(levels)
+        res = {'yhat': np.zeros((self.G, self.H)), 'count': np.zeros(self.G, dtype=np.int64)}
+        for k in ('q', 'cum_q'):
+            if k in want:
+                res[k] = np.zeros((self.G, Q, self.H))
+        if 'samples' in want:
+            res['samples'] = np.zeros((self.G, self.H, self.S))
+        out = _lib.TsfRollupOut(**{k: v.ctypes.data for k, v in res.items()})
+        self._ctx.check(_lib.load().tsf_rollup_quantiles(h, Q, levels.ctypes.data if Q else None, ctypes.byref(out)))
+        return res
+
+    def quantiles(self, levels, cumulative=False):
+        """-> RollupQuantiles at the levels (in [0, 1]) of what has been added so far; with cumulative, cum_q: the same
+        levels of each summed sample's running sum over the rows.  The accumulators are not modified."""
+        self._handle()
+        quantile_columns(levels)                # (a bad level list: ValueError before the library is touched)
+        levels = np.array(levels, dtype=np.float64).reshape(-1)
+        if len(levels) == 0:
+            raise ValueError('at least one quantile level')
+        r = self._read(levels, ['q'] + (['cum_q'] if cumulative else []))
+        return RollupQuantiles(r['yhat'], r['count'], levels, r['q'], r.get('cum_q'))
+
+    def samples(self):
+        """-> [G][H][S]: the summed draws themselves (sample s of a group: the sum of sample s of its members)."""
+        return self._read([], ['samples'])['samples']
+
+
+def predict_rollup(spec, theta, y_scale, grid, ds_future_ns, labels, quantiles, series_key, floor=None, cap=None,
+                   extra_future=None, uncertainty_samples=1000, seed=0, cumulative=False, ctx=None):
+    """The one-spec convenience: rollup_groups(labels), one Rollup.add, quantiles, close ->
+    (unique_labels, RollupQuantiles)."""
+    quantile_columns(quantiles)
+    if len(np.asarray(quantiles).reshape(-1)) == 0:
+        raise ValueError('at least one quantile level')
+    uniq, group = rollup_groups(labels)
+    if len(group) == 0:
+        raise ValueError('nothing to roll up: no series')
+    ds = np.asarray(ds_future_ns)
+    if ds.ndim != 1 or ds.shape[0] < 1:
+        raise ValueError('ds_future must be [H], H >= 1: a roll-up has one calendar')
+    _rollup_add_args(spec, theta, y_scale, grid, group, series_key, floor, cap, extra_future, len(uniq), ds.shape[0])
+    with Rollup(ds_future_ns, len(uniq), uncertainty_samples=uncertainty_samples, seed=seed, ctx=ctx) as r:
+        r.add(spec, theta, y_scale, grid, group, series_key, floor=floor, cap=cap, extra_future=extra_future)
+        return uniq, r.quantiles(quantiles, cumulative=cumulative)
+
+
 # ---- diagnostics used by the parity tests -----------------------------------------------------
 
 def eval_aligned(spec, ds_ns, y, theta, floor=None, cap=None, extra=None, ctx=None):

@@ -28,6 +28,25 @@ def _empty_forecasts():
     return pd.DataFrame(columns=FORECAST_COLUMNS)
 
 
+def _future_extra(spec, fut):
+    """The extra columns of a bucket's future rows fut [n][periods] -> [n][n_extra][periods], or None without any."""
+    if not spec.extra:
+        return None
+    # holiday columns for the future dates (fbprophet rebuilds them from the holidays
+    # frame it keeps in the model); any other explicit column has no future values in
+    # the reference's scorer (its future frame holds ds, floor, cap only): zeros
+    ex = np.zeros((fut.shape[0], len(spec.extra), fut.shape[1]))
+    if spec.holidays:
+        names, _scales, days = features.holiday_columns(features.normalize_holidays(spec.holidays))
+        if [e['name'] for e in spec.extra[:len(names)]] != names:
+            # (not an assert: it is the only guard between a blob whose `holidays` and
+            # `extra` disagree and holiday indicators multiplied into the wrong coefficients)
+            raise ValueError('model blob: the holiday columns rebuilt from `holidays` do not match '
+                             'the leading entries of `extra`')
+        ex[:, :len(names), :] = np.moveaxis(features.holiday_matrix(fut, days), 0, 1)
+    return ex
+
+
 def forecast_arrays(config):
     """The predict UDF on columns that never were a DataFrame: (series_id, dim_id, floor, cap, models) -> dict of the
     forecast frame's columns (series_id, dim_id int32; ds int64 ns; yhat int32; yhat_lower / yhat_upper when
@@ -68,20 +87,7 @@ def forecast_arrays(config):
             fut = pk.future_dates(rec['last_ds_ns'], periods, frequency)  # :64-66
             lap('future_dates')
             floor, cap = floors[idx], caps[idx]                          # :67-68
-            ex = None
-            if spec.extra:
-                # holiday columns for the future dates (fbprophet rebuilds them from the holidays
-                # frame it keeps in the model); any other explicit column has no future values in
-                # the reference's scorer (its future frame holds ds, floor, cap only): zeros
-                ex = np.zeros((len(idx), len(spec.extra), periods))
-                if spec.holidays:
-                    names, _scales, days = features.holiday_columns(features.normalize_holidays(spec.holidays))
-                    if [e['name'] for e in spec.extra[:len(names)]] != names:
-                        # (not an assert: it is the only guard between a blob whose `holidays` and
-                        # `extra` disagree and holiday indicators multiplied into the wrong coefficients)
-                        raise ValueError('model blob: the holiday columns rebuilt from `holidays` do not match '
-                                         'the leading entries of `extra`')
-                    ex[:, :len(names), :] = np.moveaxis(features.holiday_matrix(fut, days), 0, 1)
+            ex = _future_extra(spec, fut)
             if len(fut) and (fut == fut[0]).all():
                 fut = np.ascontiguousarray(fut[0])           # one future grid for the batch: one shared design table on the device
             yhat, yint = fc.predict(spec, theta, rec['y_scale'], grid, fut, floor=floor, cap=cap,
@@ -184,6 +190,76 @@ def forecast_panel(config):
     return forecast_panel_fn
 
 
+def rollup_panel(config):
+    """forecast.rollup: {by: series_id, quantiles: [...], cumulative: bool} -- the predictive distribution of the TOTAL of
+    every series_id over its dim_ids (fc.Rollup, include/tsf.h "group roll-ups"): the model frame -> one frame of
+    `periods` rows per distinct series_id with columns series_id int32, ds, yhat float64 (the sum of the members' yhat, not
+    truncated), count int64 (models summed), then yhat_q<..> per level and, with cumulative, yhat_cum_q<..> (the levels
+    of the running total over the forecast rows).  Same uncertainty_samples, seed and series key (series_id << 32) ^ dim_id
+    as forecast.quantiles, so a group of one model has that model's quantile columns.  One Rollup for the frame, one add
+    per spec bucket of pk.load_models in its order.  The members are taken as independent given their fits.  All models
+    must share one forecast calendar: a total over different dates is a decision the job does not take silently."""
+
+    def rollup_panel_fn(pdf):
+        fcfg = config['forecast']
+        ro = fcfg['rollup']
+        if ro.get('by', 'series_id') != 'series_id':
+            raise ValueError('forecast.rollup.by: only series_id is supported')
+        levels = list(ro['quantiles'])
+        names = fc.quantile_columns(levels)                      # (a bad level list fails before any launch)
+        if not names:
+            raise ValueError('forecast.rollup.quantiles: at least one level')
+        cumulative = bool(ro.get('cumulative'))
+        cum_names = fc.quantile_columns(levels, 'yhat_cum_q') if cumulative else []
+        frequency = fcfg['frequency']
+        if frequency == 'W':
+            frequency = pd.offsets.Week()
+        periods = int(fcfg['periods'])
+        sids, dids = pdf['series_id'].to_numpy(), pdf['dim_id'].to_numpy()
+        floors, caps = pdf['floor'].to_numpy(dtype=np.float64), pdf['cap'].to_numpy(dtype=np.float64)
+        blobs = [None if (b is None or isinstance(b, float)) else b for b in pdf['model'].tolist()]
+        uniq, group = fc.rollup_groups(sids.astype(np.int64))
+        roll = cal = None
+        try:
+            for spec_dict, idx, rec in pk.load_models(blobs):
+                spec = fc.ModelSpec.from_dict(spec_dict)
+                theta = np.zeros((len(idx), spec.theta_stride))
+                theta[:, :rec['theta'].shape[1]] = rec['theta']
+                fut = pk.future_dates(rec['last_ds_ns'], periods, frequency)
+                if cal is None:
+                    cal = np.ascontiguousarray(fut[0])
+                other = np.flatnonzero((fut != cal).any(axis=1))
+                if len(other):
+                    d = fut[other[0]]
+                    raise ValueError('forecast.rollup needs one forecast calendar for all models: %s and %s differ '
+                                     '(series_id %d, dim_id %d)'
+                                     % (cal[cal != d][0].view('datetime64[ns]'), d[cal != d][0].view('datetime64[ns]'),
+                                        int(sids[idx[other[0]]]), int(dids[idx[other[0]]])))
+                if roll is None:
+                    roll = fc.Rollup(cal, len(uniq), uncertainty_samples=int(fcfg.get('uncertainty_samples', 1000)),
+                                     seed=int(fcfg.get('seed', 0)))
+                ex = _future_extra(spec, fut[:1])                # (one calendar: one set of columns for the bucket)
+                roll.add(spec, theta, rec['y_scale'], pk.grid_from_records(rec), group[idx],
+                         (sids[idx].astype(np.int64) << 32) ^ (dids[idx].astype(np.int64) & 0xffffffff),
+                         floor=floors[idx], cap=caps[idx], extra_future=None if ex is None else ex[0])
+            if roll is None:
+                return pd.DataFrame(columns=['series_id', 'ds', 'yhat', 'count'] + names + cum_names)
+            r = roll.quantiles(levels, cumulative=cumulative)
+        finally:
+            if roll is not None:
+                roll.close()
+        cols = {'series_id': np.repeat(uniq.astype('int32'), periods),
+                'ds': np.tile(cal, len(uniq)).view('datetime64[ns]'),
+                'yhat': r.yhat.reshape(-1), 'count': np.repeat(r.count, periods)}
+        for i, name in enumerate(names):
+            cols[name] = r.q[:, i, :].reshape(-1)
+        for i, name in enumerate(cum_names):
+            cols[name] = r.cum_q[:, i, :].reshape(-1)
+        return pd.DataFrame(cols, columns=list(cols))
+
+    return rollup_panel_fn
+
+
 def forecast_time_series(config):
     """Forecast using trained time series model (series_id, dim_id) -- prophet_scorer.py:18."""
     batched = forecast_panel(config)
@@ -258,6 +334,18 @@ class ProphetScorer:
             pacsv.write_csv(pa.table(cols), f,
                             write_options=pacsv.WriteOptions(include_header=False, quoting_style='none'))
 
+    def write_rollup(self, rollup_df):
+        """The roll-up frame as one CSV with a header under io.rollup_forecasts (timestamps as write_forecasts writes
+        them; the float64 columns with repr's digits, so they read back bit for bit)."""
+        import shutil
+        path = self.config['io']['rollup_forecasts']
+        if os.path.isdir(path):
+            shutil.rmtree(path)
+        os.makedirs(path, exist_ok=True)
+        out = rollup_df.copy()
+        out['ds'] = [t + 'Z' for t in np.datetime_as_string(out['ds'].values.astype('datetime64[ns]'), unit='ms')]
+        out.to_csv(os.path.join(path, 'part-00000.csv'), index=False)
+
     def _clear_forecasts(self):
         """-> function that waits until the previous run's files are gone (pipeline.clear_directory)"""
         from ..pipeline import clear_directory
@@ -327,7 +415,9 @@ class ProphetScorer:
         the write; here the native sink formats the converted rows straight from the forecast columns
         (_write_converted_part: the same rows write_forecasts(convert_forecasts(forecast_df)) gives, test_host.py), so
         the converted frame -- 900 000 rows of Python date strings for 10 000 series -- is never built.  Returns None, as
-        the reference does."""
+        the reference does.
+        With forecast.rollup and io.rollup_forecasts both set, the roll-up frame (rollup_panel) is written as CSV there
+        after the forecasts: a second pass over the whole model frame, not pipelined with the first."""
         from .. import pipeline
         scorer = ProphetScorer(config)
         created = datetime.now(timezone.utc).replace(microsecond=0).isoformat()
@@ -358,3 +448,5 @@ class ProphetScorer:
         if not n_parts:             # no model at all: the header alone, as an empty frame's CSV has
             scorer._write_converted_part(0, {'series_id': np.zeros(0, np.int32), 'dim_id': np.zeros(0, np.int32),
                                              'ds': np.zeros(0, np.int64), 'yhat': np.zeros(0, np.int32)}, created)
+        if (scorer.config.get('forecast') or {}).get('rollup') and scorer.config['io'].get('rollup_forecasts'):
+            scorer.write_rollup(rollup_panel(scorer.config)(scorer.read_model_dataframe()))
