@@ -389,6 +389,79 @@ int tsf_predict_quantiles_dev(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int
                               int32_t n_samples, uint64_t seed, int32_t n_q, const double *quantiles,
                               tsf_quantile_out *out, void *stream);
 
+/* ---- scoring observed values against the predictive distribution (PIT, CRPS, pinball) ----------------
+ * The other half of tsf_predict_quantiles: given fitted models and the values observed on the forecast rows, how good
+ * is the predictive distribution, and how surprising is each observation under it?  Per row, from the same draws and
+ * the same single sort per row: the probability integral transform (PIT: uniform on [0, 1] over many rows where the
+ * distribution is calibrated; a value in a far tail flags an anomaly), the sample CRPS (a proper score in the units of
+ * y: lower is better), the quantiles at any set of levels and their pinball losses.  Per series: the means over the
+ * observed rows, the empirical coverage of every level (the share of observed rows with y <= q: near the level where
+ * the quantile is calibrated) and the row count.  Only [N][H]-sized answers leave the device; doing the same from
+ * tsf_predict_quantiles' raw samples needs N * H * n_samples values on the host.
+ * Reference interface replaced: none (neither the reference nor fbprophet has such a function); parity unpinned (what
+ * is pinned is the contract below, against tsf_predict_quantiles' draws and quantiles).
+ * Timing: tools/bench_scores.py; DESIGN.md 5g.
+ *
+ * Arguments shared with tsf_predict_quantiles mean what they mean there; the same grid check runs first, then its
+ * checks of n_samples ([2, 4096]), n_q ([0, TSF_MAX_QUANT]) and the levels.  quantiles [n_q] and the tsf_score_out
+ * struct are HOST memory in both variants; y_obs and the pointers inside the struct are host pointers in the host
+ * variant and device pointers in _dev.  y_obs [N][H]: the observed value of every forecast row, NaN = not observed.
+ *
+ * Contract:
+ *   The draws are tsf_predict_quantiles' draws (same generator, keys and counters); v[0 .. n_samples) below is a row's
+ *   draws sorted ascending and y its observed value.
+ *   q[n][i][h] is tsf_predict_quantiles' expression at level p = quantiles[i] (same pos, lo, hi, same three
+ *   roundings): bit for bit its q.  pinball[n][i][h]: with e = y - q, e >= 0 ? p * e : (p - 1.0) * e.
+ *   pit = ((double)lt + 0.5 * (double)eq) / (double)n_samples, lt = #{v < y}, eq = #{v == y} (exact counts): the
+ *   mid-distribution transform, in steps of 0.5 / n_samples; 0 below every draw, 1 above every draw.
+ *   crps is the sample CRPS mean_i |v[i] - y| - (1/2) mean_{i,j} |v[i] - v[j]|, regrouped over the sorted row into
+ *   non-negative terms so that nothing cancels:
+ *     d = v[i] - y;  w = (double)(2 * i - (n_samples - 1)) / (double)n_samples;  c[i] = fabs(d) - w * d
+ *   (plain operations: multiply, round, subtract; |w| < 1 so c[i] >= 0), c[i] = +0.0 for n_samples <= i < NSP (NSP:
+ *   n_samples rounded up to a power of two, at least 2), then the fixed tree
+ *     for (s = NSP / 2; s >= 1; s /= 2) c[i] = c[i] + c[i + s] for every i < s
+ *   and crps = c[0] / (double)n_samples.  With the exact value x of the sample CRPS of the same draws,
+ *     |crps - x| <= 2^-53 * (4 * mean_i |v[i] - y| + (log2(NSP) + 2) * x).
+ *   A row whose y is NaN gets NaN in pit, crps and pinball; its q is still written.
+ *   Per series, over its rows in the caller's row order with plain double adds from +0.0: n_obs = the number of rows
+ *   with a non-NaN y; mean_crps and mean_pinball[n][i] = the sum over the observed rows / (double)n_obs;
+ *   coverage[n][i] = (double)#{observed rows with y <= q[n][i][h]} / (double)n_obs.  n_obs = 0: NaN means and coverage.
+ *   No floating-point atomics.  Every output depends neither on how the call is cut into scratch chunks (512 MB, one
+ *   sample buffer), nor on what else is in the batch, nor on which other outputs are requested.  Per-row arrays the
+ *   requested aggregates need and the caller did not ask for live in the context's scratch.
+ *   Behaviour for non-finite draws is unspecified (as for the quantiles).
+ *
+ * Refusals (< 0 with a message, before any launch; the context stays usable): a NULL out, out->yhat or y_obs;
+ * n_samples outside [2, 4096]; a bad n_q or level; n_q = 0 with q, pinball, mean_pinball or coverage requested; a call
+ * that wants nothing beyond yhat; in the host variant an infinite y_obs value (the _dev variant cannot look: there it
+ * is the caller's business).  N == 0 is a legal no-op.
+ *
+ * Out of scope: scoring running totals against cum_q; scoring roll-ups (tsf_rollup_*); a split over several GPUs (the
+ * call is per context, like tsf_predict_quantiles). */
+typedef struct {
+    double *yhat;           /* [N][H]        required: tsf_predict's, bit for bit */
+    double *pit;            /* [N][H]        NULL: not wanted (all below likewise) */
+    double *crps;           /* [N][H] */
+    double *q;              /* [N][n_q][H]   tsf_predict_quantiles' q, bit for bit */
+    double *pinball;        /* [N][n_q][H] */
+    int32_t *n_obs;         /* [N] */
+    double *mean_crps;      /* [N] */
+    double *mean_pinball;   /* [N][n_q] */
+    double *coverage;       /* [N][n_q] */
+} tsf_score_out;
+int tsf_score_out_size(void);       /* sizeof(tsf_score_out): the self-check of a binding */
+int tsf_score_actuals(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H, const double *theta,
+                      const double *y_scale, const tsf_grid_info *grid, int32_t n_grids, const int64_t *ds_future,
+                      int32_t shared_future, const double *floor, const double *cap, const double *extra_future,
+                      const int64_t *series_key, int32_t n_samples, uint64_t seed,
+                      const double *y_obs /* [N][H], NaN = not observed */, int32_t n_q, const double *quantiles,
+                      tsf_score_out *out);
+int tsf_score_actuals_dev(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H, const double *theta,
+                          const double *y_scale, const tsf_grid_info *grid, int32_t n_grids,
+                          const int64_t *ds_future, int32_t shared_future, const double *floor, const double *cap,
+                          const double *extra_future, const int64_t *series_key, int32_t n_samples, uint64_t seed,
+                          const double *y_obs, int32_t n_q, const double *quantiles, tsf_score_out *out, void *stream);
+
 /* ---- group roll-ups: predictive quantiles of sums over series ---------------------------------------
  * The predictive distribution of a TOTAL over several series -- P90 of a series_id over its dim_ids, of a region, of the
  * whole panel -- and of its running sum over the future rows.  The point forecast of a total is a sum of yhat columns;

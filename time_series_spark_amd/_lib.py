@@ -103,6 +103,13 @@ class TsfQuantileOut(ctypes.Structure):
                 ('trend_q', ctypes.c_void_p), ('samples', ctypes.c_void_p), ('trend_samples', ctypes.c_void_p)]
 
 
+class TsfScoreOut(ctypes.Structure):
+    """tsf_score_out (include/tsf.h)."""
+    _fields_ = [('yhat', ctypes.c_void_p), ('pit', ctypes.c_void_p), ('crps', ctypes.c_void_p), ('q', ctypes.c_void_p),
+                ('pinball', ctypes.c_void_p), ('n_obs', ctypes.c_void_p), ('mean_crps', ctypes.c_void_p),
+                ('mean_pinball', ctypes.c_void_p), ('coverage', ctypes.c_void_p)]
+
+
 class TsfRollupOut(ctypes.Structure):
     """tsf_rollup_out (include/tsf.h)."""
     _fields_ = [('yhat', ctypes.c_void_p), ('count', ctypes.c_void_p), ('q', ctypes.c_void_p), ('cum_q', ctypes.c_void_p),
@@ -121,6 +128,7 @@ EXPORTS = ['tsf_create', 'tsf_destroy', 'tsf_last_error', 'tsf_device_count', 't
            'tsf_fit_aligned', 'tsf_fit_aligned_dev', 'tsf_fit_ragged', 'tsf_fit_ragged_dev',
            'tsf_predict', 'tsf_predict_dev', 'tsf_predict_intervals', 'tsf_predict_intervals_dev', 'tsf_predict_components', 'tsf_predict_components_dev',
            'tsf_predict_quantiles', 'tsf_predict_quantiles_dev',
+           'tsf_score_out_size', 'tsf_score_actuals', 'tsf_score_actuals_dev',
            'tsf_rollup_create', 'tsf_rollup_add', 'tsf_rollup_quantiles', 'tsf_rollup_free', 'tsf_eval', 'tsf_eval_quadratic', 'tsf_design', 'tsf_selftest_math',
            'tsf_set_option', 'tsf_get_option', 'tsf_set_cost_hints', 'tsf_set_profiling', 'tsf_profile_read', 'tsf_last_fit_kernel_ms', 'tsf_last_fit_route',
            'tsf_cv_plan', 'tsf_cross_validate', 'tsf_last_cv_grids', 'tsf_tune', 'tsf_last_tune_counts',
@@ -191,6 +199,9 @@ def load():
     L.tsf_predict_quantiles.argtypes = [vp, psp, i64, i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, i32, u64, i32, vp,
                                         ctypes.POINTER(TsfQuantileOut)]
     L.tsf_predict_quantiles_dev.argtypes = L.tsf_predict_quantiles.argtypes + [vp]
+    L.tsf_score_actuals.argtypes = [vp, psp, i64, i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, i32, u64, vp, i32, vp,
+                                    ctypes.POINTER(TsfScoreOut)]
+    L.tsf_score_actuals_dev.argtypes = L.tsf_score_actuals.argtypes + [vp]
     L.tsf_rollup_create.argtypes = [vp, i64, i32, vp, i32, u64, ctypes.POINTER(vp)]
     L.tsf_rollup_add.argtypes = [vp, psp, i64, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp]
     L.tsf_rollup_quantiles.argtypes = [vp, i32, vp, ctypes.POINTER(TsfRollupOut)]
@@ -255,6 +266,8 @@ def load():
         raise TsfError('tsf_spec layout mismatch between _lib.py and libtsf_amd.so')
     if L.tsf_grid_info_size() != ctypes.sizeof(TsfGridInfo) or GRID_DTYPE.itemsize != ctypes.sizeof(TsfGridInfo):
         raise TsfError('tsf_grid_info layout mismatch between _lib.py and libtsf_amd.so')
+    if L.tsf_score_out_size() != ctypes.sizeof(TsfScoreOut):
+        raise TsfError('tsf_score_out layout mismatch between _lib.py and libtsf_amd.so')
     _lib = L
     return L
 

@@ -22,6 +22,7 @@
 
 #include "tsf_aux_kernels.h"
 #include "tsf_interval_kernels.h"
+#include "tsf_score_kernels.h"
 #include "tsf_rollup_kernels.h"
 #include "tsf_component_kernels.h"
 #include "tsf_fit_kernels.h"
@@ -1856,6 +1857,12 @@ static int64_t draw_chunk_series(int64_t N, int32_t H, int32_t n_samples, size_t
     return chunk;
 }
 
+// bytes of scratch draw_chunks carves for chunks of `chunk` series
+static size_t draw_scratch_bytes(int64_t chunk, int32_t H, int32_t n_samples, size_t n_buf)
+{
+    return 8 * (size_t)chunk * H * (3 + n_buf * (size_t)n_samples);
+}
+
 template <class After>
 static int draw_chunks(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H, const double *theta,
                        const double *y_scale, const tsf_grid_info *grid, int32_t n_grids, const int64_t *ds_future,
@@ -1873,7 +1880,7 @@ static int draw_chunks(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H,
     const size_t n_buf = 1 + (size_t)want_cum + (size_t)want_trend;
     const int64_t chunk = draw_chunk_series(N, H, n_samples, n_buf);
     const size_t nh = (size_t)chunk * H;
-    const size_t need = 8 * nh * (3 + n_buf * (size_t)n_samples);
+    const size_t need = draw_scratch_bytes(chunk, H, n_samples, n_buf);
     if (ctx->iv_ws_bytes < need) {
         if (ctx->iv_ws) { HIP_TRY(ctx, hipFree(ctx->iv_ws)); ctx->iv_ws = nullptr; ctx->iv_ws_bytes = 0; }
         HIP_TRY(ctx, hipMalloc(&ctx->iv_ws, need));
@@ -2021,6 +2028,191 @@ extern "C" int tsf_predict_quantiles(tsf_ctx *ctx, const tsf_spec *spec, int64_t
     if (out->q) HIP_TRY(ctx, hipMemcpy(out->q, d_q.p, nqh, hipMemcpyDeviceToHost));
     if (out->cum_q) HIP_TRY(ctx, hipMemcpy(out->cum_q, d_cq.p, nqh, hipMemcpyDeviceToHost));
     if (out->trend_q) HIP_TRY(ctx, hipMemcpy(out->trend_q, d_tq.p, nqh, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- scoring observed values against the predictive distribution -------------------------------------------
+
+extern "C" int tsf_score_out_size(void) { return (int)sizeof(tsf_score_out); }
+
+// What both score entries check before anything is launched (after the grid check): tsf_predict_quantiles' checks of the
+// sample count and the levels, then what the outputs need.
+static int check_score_args(tsf_ctx *ctx, int32_t n_samples, int32_t n_q, const double *quantiles, const double *y_obs,
+                            const tsf_score_out *out)
+{
+    if (!out || !out->yhat) return fail(ctx, "NULL output (tsf_score_out and its yhat are required)");
+    if (!y_obs) return fail(ctx, "NULL y_obs");
+    if (n_samples < 2 || n_samples > 4096) return fail(ctx, "n_samples must be in [2, 4096]");
+    if (n_q < 0 || n_q > TSF_MAX_QUANT) return fail(ctx, "n_q must be in [0, TSF_MAX_QUANT]");
+    if (n_q > 0 && !quantiles) return fail(ctx, "NULL quantiles");
+    for (int32_t i = 0; i < n_q; ++i)
+        if (!(quantiles[i] >= 0.0 && quantiles[i] <= 1.0)) {       // (NaN fails both comparisons)
+            char msg[120];
+            snprintf(msg, sizeof(msg), "quantiles[%d] = %g: a level must be finite and in [0, 1]", (int)i, quantiles[i]);
+            return fail(ctx, msg);
+        }
+    const bool want_q = out->q || out->pinball || out->mean_pinball || out->coverage;
+    if (!want_q && !out->pit && !out->crps && !out->n_obs && !out->mean_crps)
+        return fail(ctx, "nothing requested: every output of tsf_score_out beyond yhat is NULL");
+    if (n_q == 0 && want_q) return fail(ctx, "n_q = 0 with q, pinball, mean_pinball or coverage requested");
+    return 0;
+}
+
+// The work of both score entries on device-resident inputs; every pointer of `o` and y_obs are device pointers.  The
+// per-row arrays the aggregates read (crps for mean_crps, pinball for mean_pinball, q for coverage) are the caller's
+// where given and otherwise lie in the context's sample scratch behind the chunk draw_chunks carves from it.
+static int score_actuals_run(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H, const double *theta,
+                             const double *y_scale, const tsf_grid_info *grid, int32_t n_grids,
+                             const int64_t *ds_future, int32_t shared_future, const double *floor_, const double *cap,
+                             const double *extra_future, const int64_t *series_key, int32_t n_samples, uint64_t seed,
+                             const double *y_obs, int32_t n_q, const double *quantiles, const tsf_score_out &o,
+                             hipStream_t st)
+{
+    int NSP = 2;
+    while (NSP < n_samples) NSP <<= 1;
+    const size_t nh = (size_t)N * H, nqh = nh * (size_t)n_q;
+    ScoreArgs a;
+    memset(&a, 0, sizeof(a));
+    a.y = y_obs; a.pit = o.pit; a.crps = o.crps; a.q = o.q; a.pinball = o.pinball;
+    a.H = H; a.NS = n_samples; a.n_q = n_q;
+    for (int32_t i = 0; i < n_q; ++i) a.level[i] = quantiles[i];
+    const size_t extra = (o.mean_crps && !o.crps ? nh : 0) + (o.mean_pinball && !o.pinball ? nqh : 0) +
+                         (o.coverage && !o.q ? nqh : 0);
+    if (extra) {
+        const size_t draw = draw_scratch_bytes(draw_chunk_series(N, H, n_samples, 1), H, n_samples, 1);
+        const size_t need = draw + 8 * extra;
+        if (ctx->iv_ws_bytes < need) {
+            if (ctx->iv_ws) { HIP_TRY(ctx, hipFree(ctx->iv_ws)); ctx->iv_ws = nullptr; ctx->iv_ws_bytes = 0; }
+            HIP_TRY(ctx, hipMalloc(&ctx->iv_ws, need));
+            ctx->iv_ws_bytes = need;
+        }
+        double *d_next = (double *)((char *)ctx->iv_ws + draw);
+        if (o.mean_crps && !o.crps) { a.crps = d_next; d_next += nh; }
+        if (o.mean_pinball && !o.pinball) { a.pinball = d_next; d_next += nqh; }
+        if (o.coverage && !o.q) a.q = d_next;
+    }
+    if (a.pit || a.crps || a.q || a.pinball) {
+        auto after = [&](int64_t n0, int64_t nc, const DrawBufs &b) -> int {
+            a.src = b.samp; a.n0 = n0;
+            hipLaunchKernelGGL(score_kernel, dim3((unsigned)(nc * H)), dim3(256), sizeof(double) * NSP, st, a, NSP);
+            HIP_TRY(ctx, hipGetLastError());
+            return 0;
+        };
+        if (int rc = draw_chunks(ctx, spec, N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap,
+                                 extra_future, series_key, n_samples, seed, false, false, o.yhat, st, after))
+            return rc;
+    } else {
+        // n_obs alone: no draw is needed, only yhat
+        if (int rc = tsf_predict_dev(ctx, spec, N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_,
+                                     cap, extra_future, o.yhat, nullptr, st))
+            return rc;
+    }
+    if (o.n_obs || o.mean_crps || o.mean_pinball || o.coverage) {
+        ScoreSeriesArgs s;
+        memset(&s, 0, sizeof(s));
+        s.y = y_obs; s.crps = a.crps; s.q = a.q; s.pinball = a.pinball;
+        s.n_obs = o.n_obs; s.mean_crps = o.mean_crps; s.mean_pinball = o.mean_pinball; s.coverage = o.coverage;
+        s.N = N; s.H = H; s.n_q = n_q;
+        const int64_t threads = N * (1 + n_q);
+        hipLaunchKernelGGL(score_series_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, s);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" int tsf_score_actuals_dev(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H, const double *theta,
+                                     const double *y_scale, const tsf_grid_info *grid, int32_t n_grids,
+                                     const int64_t *ds_future, int32_t shared_future, const double *floor_,
+                                     const double *cap, const double *extra_future, const int64_t *series_key,
+                                     int32_t n_samples, uint64_t seed, const double *y_obs, int32_t n_q,
+                                     const double *quantiles, tsf_score_out *out, void *stream)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (N < 0 || H <= 0) return fail(ctx, "N must be >= 0 and H > 0");
+    if (int rc = check_score_args(ctx, n_samples, n_q, quantiles, y_obs, out)) return rc;
+    if (N == 0) return 0;
+    if (!spec || !theta || !y_scale || !grid || !ds_future) return fail(ctx, "NULL input");
+    if (n_grids != 1 && n_grids != N) return fail(ctx, "n_grids must be 1 or N");
+    return score_actuals_run(ctx, spec, N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap,
+                             extra_future, series_key, n_samples, seed, y_obs, n_q, quantiles, *out, (hipStream_t)stream);
+}
+
+extern "C" int tsf_score_actuals(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H, const double *theta,
+                                 const double *y_scale, const tsf_grid_info *grid, int32_t n_grids,
+                                 const int64_t *ds_future, int32_t shared_future, const double *floor_, const double *cap,
+                                 const double *extra_future, const int64_t *series_key, int32_t n_samples, uint64_t seed,
+                                 const double *y_obs, int32_t n_q, const double *quantiles, tsf_score_out *out)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (N < 0 || H <= 0) return fail(ctx, "N must be >= 0 and H > 0");
+    if (N > 0) {
+        if (!spec || !theta || !y_scale || !grid || !ds_future) return fail(ctx, "NULL input");
+        if (n_grids != 1 && n_grids != N) return fail(ctx, "n_grids must be 1 or N");
+        if (int rc = check_grids(ctx, spec, grid, n_grids)) return rc;
+    }
+    if (int rc = check_score_args(ctx, n_samples, n_q, quantiles, y_obs, out)) return rc;
+    if (N == 0) return 0;
+    if (spec->n_extra > 0 && !extra_future) return fail(ctx, "extra_future is NULL");
+    const size_t nhn = (size_t)N * H;
+    for (size_t i = 0; i < nhn; ++i)
+        if (std::isinf(y_obs[i])) {
+            char msg[120];
+            snprintf(msg, sizeof(msg), "y_obs[%lld][%d] is infinite: an observed value must be finite (NaN = not observed)",
+                     (long long)(i / H), (int)(i % H));
+            return fail(ctx, msg);
+        }
+    const int stride = tsf_theta_stride(spec);
+    const size_t nfut = shared_future ? (size_t)H : (size_t)N * H;
+    DevBuf d_th, d_ys, d_grid, d_ds, d_fl, d_cap, d_ex, d_key, d_y, d_yh, d_pit, d_crps, d_q, d_pb, d_no, d_mc, d_mp, d_cv;
+    HIP_TRY(ctx, d_th.alloc(8 * (size_t)N * stride));
+    HIP_TRY(ctx, hipMemcpy(d_th.p, theta, 8 * (size_t)N * stride, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_ys.alloc(8 * N));
+    HIP_TRY(ctx, hipMemcpy(d_ys.p, y_scale, 8 * N, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_grid.alloc(sizeof(tsf_grid_info) * n_grids));
+    HIP_TRY(ctx, hipMemcpy(d_grid.p, grid, sizeof(tsf_grid_info) * n_grids, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_ds.alloc(8 * nfut));
+    HIP_TRY(ctx, hipMemcpy(d_ds.p, ds_future, 8 * nfut, hipMemcpyHostToDevice));
+    if (floor_) { HIP_TRY(ctx, d_fl.alloc(8 * N)); HIP_TRY(ctx, hipMemcpy(d_fl.p, floor_, 8 * N, hipMemcpyHostToDevice)); }
+    if (cap) { HIP_TRY(ctx, d_cap.alloc(8 * N)); HIP_TRY(ctx, hipMemcpy(d_cap.p, cap, 8 * N, hipMemcpyHostToDevice)); }
+    if (series_key) { HIP_TRY(ctx, d_key.alloc(8 * N)); HIP_TRY(ctx, hipMemcpy(d_key.p, series_key, 8 * N, hipMemcpyHostToDevice)); }
+    if (spec->n_extra > 0) {
+        const size_t nb = 8 * (size_t)spec->n_extra * nfut;
+        HIP_TRY(ctx, d_ex.alloc(nb));
+        HIP_TRY(ctx, hipMemcpy(d_ex.p, extra_future, nb, hipMemcpyHostToDevice));
+    }
+    const size_t nh = 8 * nhn, nqh = nh * (size_t)n_q, nq = 8 * (size_t)N * n_q;
+    HIP_TRY(ctx, d_y.alloc(nh));
+    HIP_TRY(ctx, hipMemcpy(d_y.p, y_obs, nh, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_yh.alloc(nh));
+    tsf_score_out o;
+    memset(&o, 0, sizeof(o));
+    o.yhat = d_yh.as<double>();
+    if (out->pit) { HIP_TRY(ctx, d_pit.alloc(nh)); o.pit = d_pit.as<double>(); }
+    if (out->crps) { HIP_TRY(ctx, d_crps.alloc(nh)); o.crps = d_crps.as<double>(); }
+    if (out->q) { HIP_TRY(ctx, d_q.alloc(nqh)); o.q = d_q.as<double>(); }
+    if (out->pinball) { HIP_TRY(ctx, d_pb.alloc(nqh)); o.pinball = d_pb.as<double>(); }
+    if (out->n_obs) { HIP_TRY(ctx, d_no.alloc(4 * (size_t)N)); o.n_obs = d_no.as<int32_t>(); }
+    if (out->mean_crps) { HIP_TRY(ctx, d_mc.alloc(8 * (size_t)N)); o.mean_crps = d_mc.as<double>(); }
+    if (out->mean_pinball) { HIP_TRY(ctx, d_mp.alloc(nq)); o.mean_pinball = d_mp.as<double>(); }
+    if (out->coverage) { HIP_TRY(ctx, d_cv.alloc(nq)); o.coverage = d_cv.as<double>(); }
+    int rc = score_actuals_run(ctx, spec, N, H, d_th.as<double>(), d_ys.as<double>(), d_grid.as<tsf_grid_info>(), n_grids,
+                               d_ds.as<int64_t>(), shared_future, floor_ ? d_fl.as<double>() : nullptr,
+                               cap ? d_cap.as<double>() : nullptr, spec->n_extra > 0 ? d_ex.as<double>() : nullptr,
+                               series_key ? d_key.as<int64_t>() : nullptr, n_samples, seed, d_y.as<double>(), n_q,
+                               quantiles, o, nullptr);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    HIP_TRY(ctx, hipMemcpy(out->yhat, d_yh.p, nh, hipMemcpyDeviceToHost));
+    if (out->pit) HIP_TRY(ctx, hipMemcpy(out->pit, d_pit.p, nh, hipMemcpyDeviceToHost));
+    if (out->crps) HIP_TRY(ctx, hipMemcpy(out->crps, d_crps.p, nh, hipMemcpyDeviceToHost));
+    if (out->q) HIP_TRY(ctx, hipMemcpy(out->q, d_q.p, nqh, hipMemcpyDeviceToHost));
+    if (out->pinball) HIP_TRY(ctx, hipMemcpy(out->pinball, d_pb.p, nqh, hipMemcpyDeviceToHost));
+    if (out->n_obs) HIP_TRY(ctx, hipMemcpy(out->n_obs, d_no.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+    if (out->mean_crps) HIP_TRY(ctx, hipMemcpy(out->mean_crps, d_mc.p, 8 * (size_t)N, hipMemcpyDeviceToHost));
+    if (out->mean_pinball) HIP_TRY(ctx, hipMemcpy(out->mean_pinball, d_mp.p, nq, hipMemcpyDeviceToHost));
+    if (out->coverage) HIP_TRY(ctx, hipMemcpy(out->coverage, d_cv.p, nq, hipMemcpyDeviceToHost));
     return 0;
 }
 

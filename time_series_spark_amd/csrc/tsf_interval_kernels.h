@@ -146,15 +146,12 @@ __global__ __launch_bounds__(256) void interval_sample_kernel(IntervalArgs a)
     }
 }
 
-// NSP: NS rounded up to a power of two (<= 4096), the padding sorts to the end as +inf
-__global__ __launch_bounds__(256) void interval_percentile_kernel(IntervalArgs a, int NSP)
+// The sort of the three per-row kernels (here and tsf_score_kernels.h): the NS values of one row into LDS, padded to
+// NSP (a power of two) with +inf, then a bitonic network of compare-exchanges, ascending; ends behind a barrier.
+// Exchanges move values and round nothing, so the sorted row is a function of the row's multiset alone.
+__device__ __forceinline__ void iv_load_sort(double *v, const double *src, int NS, int NSP)
 {
-    extern __shared__ __align__(16) unsigned char iv_smem[];
-    double *v = reinterpret_cast<double *>(iv_smem);
-    const int64_t nl = blockIdx.x / a.H;
-    const int h = (int)(blockIdx.x - nl * a.H);
-    const double *src = a.samples + ((size_t)nl * a.H + h) * a.NS;
-    for (int i = threadIdx.x; i < NSP; i += blockDim.x) v[i] = (i < a.NS) ? src[i] : __builtin_huge_val();
+    for (int i = threadIdx.x; i < NSP; i += blockDim.x) v[i] = (i < NS) ? src[i] : __builtin_huge_val();
     __syncthreads();
     for (int k = 2; k <= NSP; k <<= 1)
         for (int j = k >> 1; j > 0; j >>= 1) {
@@ -168,6 +165,17 @@ __global__ __launch_bounds__(256) void interval_percentile_kernel(IntervalArgs a
             }
             __syncthreads();
         }
+}
+
+// NSP: NS rounded up to a power of two (<= 4096), the padding sorts to the end as +inf
+__global__ __launch_bounds__(256) void interval_percentile_kernel(IntervalArgs a, int NSP)
+{
+    extern __shared__ __align__(16) unsigned char iv_smem[];
+    double *v = reinterpret_cast<double *>(iv_smem);
+    const int64_t nl = blockIdx.x / a.H;
+    const int h = (int)(blockIdx.x - nl * a.H);
+    const double *src = a.samples + ((size_t)nl * a.H + h) * a.NS;
+    iv_load_sort(v, src, a.NS, NSP);
     if (threadIdx.x < 2) {
         const double pos = (threadIdx.x ? a.hi_frac : a.lo_frac) * (double)(a.NS - 1);
         int lo = (int)__builtin_floor(pos);
@@ -198,20 +206,7 @@ __global__ __launch_bounds__(256) void quantile_kernel(QuantileArgs a, int NSP)
     const int64_t nl = blockIdx.x / a.H;
     const int h = (int)(blockIdx.x - nl * a.H);
     const double *src = a.src + ((size_t)nl * a.H + h) * a.NS;
-    for (int i = threadIdx.x; i < NSP; i += blockDim.x) v[i] = (i < a.NS) ? src[i] : __builtin_huge_val();
-    __syncthreads();
-    for (int k = 2; k <= NSP; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < NSP; i += blockDim.x) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const bool asc = (i & k) == 0;
-                    const double x = v[i], y = v[ixj];
-                    if ((x > y) == asc) { v[i] = y; v[ixj] = x; }
-                }
-            }
-            __syncthreads();
-        }
+    iv_load_sort(v, src, a.NS, NSP);
     for (int q = threadIdx.x; q < a.n_q; q += blockDim.x) {
         const double pos = a.level[q] * (double)(a.NS - 1);
         int lo = (int)__builtin_floor(pos);

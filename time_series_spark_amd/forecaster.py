@@ -812,6 +812,139 @@ def predictive_samples(spec, theta, y_scale, grid, ds_future_ns, floor=None, cap
     return {'yhat': r['samples'], 'trend': r['trend_samples']}
 
 
+# ---- scoring observed values against the predictive distribution -----------------------------------
+# The other half of predict_quantiles (include/tsf.h tsf_score_actuals): given the values observed on the forecast
+# rows, the PIT, the sample CRPS and the pinball losses per row, their means and the coverage of every level per series,
+# from the same draws and the same sort per row; only [N][H]-sized answers leave the device.
+
+SCORE_ROW_FIELDS = ('pit', 'crps', 'q', 'pinball')
+SCORE_SERIES_FIELDS = ('n_obs', 'mean_crps', 'mean_pinball', 'coverage')
+_SCORE_LEVEL_FIELDS = ('q', 'pinball', 'mean_pinball', 'coverage')
+
+
+class Scores(object):
+    """What score_actuals returns (include/tsf.h tsf_score_out): y and yhat [N][H]; quantiles [Q] (the levels as
+    given); per row pit, crps [N][H] and q, pinball [N][Q][H]; per series n_obs [N] (int32), mean_crps [N],
+    mean_pinball, coverage [N][Q].  q, pinball, mean_pinball and coverage are None without levels.  Rows whose y is NaN
+    (not observed) have NaN in pit, crps and pinball and count in no mean."""
+
+    def __init__(self, y, yhat, quantiles, pit=None, crps=None, q=None, pinball=None, n_obs=None, mean_crps=None,
+                 mean_pinball=None, coverage=None):
+        self.y, self.yhat, self.quantiles = y, yhat, quantiles
+        self.pit, self.crps, self.q, self.pinball = pit, crps, q, pinball
+        self.n_obs, self.mean_crps, self.mean_pinball, self.coverage = n_obs, mean_crps, mean_pinball, coverage
+
+    def frame(self, n, ds):
+        """Series n as a DataFrame: ds, y, yhat, pit, crps, then yhat_q<..> and pinball_q<..> per level (names:
+        quantile_columns)."""
+        import pandas as pd
+        ds = np.asarray(ds)
+        if ds.dtype.kind != 'M':
+            ds = ds.astype(np.int64).view('datetime64[ns]')
+        cols = {'ds': ds, 'y': self.y[n], 'yhat': self.yhat[n]}
+        for k in ('pit', 'crps'):
+            if getattr(self, k) is not None:
+                cols[k] = getattr(self, k)[n]
+        if self.q is not None or self.pinball is not None:
+            for i, (qn, pn) in enumerate(zip(quantile_columns(self.quantiles), quantile_columns(self.quantiles, 'pinball_q'))):
+                if self.q is not None:
+                    cols[qn] = self.q[n, i]
+                if self.pinball is not None:
+                    cols[pn] = self.pinball[n, i]
+        return pd.DataFrame(cols, columns=list(cols))
+
+    def anomalies(self, alpha):
+        """Boolean mask [N][H]: rows whose observed value lies in the two-sided alpha tail of their predictive
+        distribution, pit < alpha / 2 or pit > 1 - alpha / 2; False on rows that were not observed.  The PIT comes from
+        uncertainty_samples draws, so its resolution is 0.5 / uncertainty_samples: an alpha below 1 / uncertainty_samples
+        flags only values outside every draw, and none finer than that can be told apart."""
+        alpha = float(alpha)
+        if not 0.0 < alpha < 1.0:
+            raise ValueError('alpha must be in (0, 1)')
+        if self.pit is None:
+            raise ValueError('anomalies needs the pit output')
+        with np.errstate(invalid='ignore'):
+            return (self.pit < alpha / 2.0) | (self.pit > 1.0 - alpha / 2.0)
+
+
+def _score_actuals_call(spec, theta, y_scale, grid, ds_ns, y_obs, floor, cap, extra_future, series_key,
+                        uncertainty_samples, seed, levels, want, ctx):
+    """One tsf_score_actuals call -> dict of the outputs named in `want` (and yhat).  Every argument-shape error is
+    raised before the library is loaded."""
+    theta = np.ascontiguousarray(theta, dtype=np.float64)
+    if theta.ndim != 2 or theta.shape[1] != spec.theta_stride:
+        raise ValueError('theta must be [N][%d]' % spec.theta_stride)
+    N = theta.shape[0]
+    y_scale = np.ascontiguousarray(y_scale, dtype=np.float64)
+    if y_scale.shape != (N,):
+        raise ValueError('y_scale must be [N]')
+    grid = np.ascontiguousarray(grid, dtype=_lib.GRID_DTYPE)
+    if grid.ndim != 1 or len(grid) not in (1, N):
+        raise ValueError('grid must hold 1 or N records')
+    ds_ns = np.ascontiguousarray(ds_ns, dtype=np.int64)
+    shared = ds_ns.ndim == 1
+    H = ds_ns.shape[-1]
+    if ds_ns.ndim not in (1, 2) or H < 1 or (not shared and ds_ns.shape != (N, H)):
+        raise ValueError('ds must be [H] or [N][H], H >= 1')
+    y_obs = np.ascontiguousarray(y_obs, dtype=np.float64)
+    if y_obs.shape != (N, H):
+        raise ValueError('y_obs must be [N][H] = %r (got %r)' % ((N, H), y_obs.shape))
+    if np.isinf(y_obs).any():
+        raise ValueError('y_obs holds an infinite value: an observed value must be finite (NaN = not observed)')
+    floor = _opt_f64(floor, N, 'floor')
+    cap = _opt_f64(cap, N, 'cap')
+    ex = None
+    if spec.extra:
+        if extra_future is None:
+            raise ValueError('extra_future is required: the spec has extra columns')
+        ex = np.ascontiguousarray(extra_future, dtype=np.float64)
+        shape = (len(spec.extra), H) if shared else (N, len(spec.extra), H)
+        if ex.shape != shape:
+            raise ValueError('extra_future must be %r' % (shape,))
+    key = None if series_key is None else np.ascontiguousarray(series_key, dtype=np.int64)
+    if key is not None and key.shape != (N,):
+        raise ValueError('series_key must be [N]')
+    levels = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
+    quantile_columns(levels)            # (ValueError for a bad level, two levels of one name, too many)
+    Q, S = len(levels), int(uncertainty_samples)
+    unknown = set(want) - set(SCORE_ROW_FIELDS + SCORE_SERIES_FIELDS)
+    if unknown:
+        raise ValueError('unknown outputs %s' % sorted(unknown))
+    if not Q and set(want) & set(_SCORE_LEVEL_FIELDS):
+        raise ValueError('q, pinball, mean_pinball and coverage need quantile levels')
+    shapes = {'pit': (N, H), 'crps': (N, H), 'q': (N, Q, H), 'pinball': (N, Q, H), 'mean_crps': (N,),
+              'mean_pinball': (N, Q), 'coverage': (N, Q)}
+    res = {'yhat': np.zeros((N, H))}
+    for k in want:
+        res[k] = np.zeros(N, np.int32) if k == 'n_obs' else np.zeros(shapes[k])
+    ctx = ctx or get_context()
+    L = _lib.load()
+    cs = spec.to_c()
+    out = _lib.TsfScoreOut(**{k: v.ctypes.data for k, v in res.items()})
+    rc = L.tsf_score_actuals(ctx.handle, ctypes.byref(cs), N, H, theta.ctypes.data, y_scale.ctypes.data,
+                             grid.ctypes.data, len(grid), ds_ns.ctypes.data, int(shared), _lib._ptr(floor),
+                             _lib._ptr(cap), _lib._ptr(ex), _lib._ptr(key), S, int(seed), y_obs.ctypes.data, Q,
+                             levels.ctypes.data if Q else None, ctypes.byref(out))
+    ctx.check(rc)
+    res['y'] = y_obs
+    return res
+
+
+def score_actuals(spec, theta, y_scale, grid, ds_ns, y_obs, quantiles=(), floor=None, cap=None, extra_future=None,
+                  series_key=None, uncertainty_samples=1000, seed=0, ctx=None):
+    """Observed values scored against the predictive distribution of every series -> Scores (include/tsf.h
+    tsf_score_actuals).  ds_ns [H] or [N][H]: the rows that were forecast; y_obs [N][H]: what was observed on them, NaN =
+    not observed.  Per row: pit (the probability integral transform: uniform where the distribution is calibrated, in
+    steps of 0.5 / uncertainty_samples), crps (the sample CRPS, in the units of y, lower is better) and, with levels
+    `quantiles`, q and pinball; per series: n_obs, mean_crps, mean_pinball, coverage (the share of observed rows at or
+    below each quantile).  The draws are predict_quantiles' (same series_key, samples, seed): q is its q bit for bit."""
+    levels = np.array(quantiles, dtype=np.float64).reshape(-1)
+    want = ['pit', 'crps', 'n_obs', 'mean_crps'] + (list(_SCORE_LEVEL_FIELDS) if len(levels) else [])
+    r = _score_actuals_call(spec, theta, y_scale, grid, ds_ns, y_obs, floor, cap, extra_future, series_key,
+                            uncertainty_samples, seed, levels, want, ctx)
+    return Scores(r.pop('y'), r.pop('yhat'), levels, **r)
+
+
 # ---- group roll-ups: predictive quantiles of sums over series --------------------------------------
 # The distribution of a total over several series (include/tsf.h "group roll-ups"): the members' draws summed sample by
 # sample on the device, across specs and calls, then sorted.  Members are taken as independent given their fits: where
@@ -1085,7 +1218,9 @@ class CVResult(object):
     Per series [N]: status (TSF_CV_*), n_folds, n_holdout, n_metric.
     Per fold [F] (series by series, cutoffs ascending): fold_series, cutoff, hist_rows, hold_rows, and `fit`, the
     FitResult of every fold (grid [F]).
-    Per holdout row [R] (fold by fold): row_fold, ds, y, yhat, yhat_lower / yhat_upper (None without intervals).
+    Per holdout row [R] (fold by fold): row_fold, row_index (the row's index in the caller's ds: into [T] for an
+    aligned panel, into the ragged panel's rows otherwise), ds, y, yhat, yhat_lower / yhat_upper (None without
+    intervals).
     Per metric row [M] (series by series, horizons ascending): metric_series, horizon, mse, rmse, mae, mape,
     coverage (None without intervals)."""
 
@@ -1189,7 +1324,8 @@ def cross_validate(spec, ds_ns, y, horizon, period=None, initial=None, offsets=N
                                   None if ex is None else ex[:, r0:r1], series_key=key[a:b], ctx=c, **kw)
         blocks = [(c, int(a), int(b)) for c, a, b in zip(_contexts(devs[:parts]), cuts[:-1], cuts[1:]) if b > a]
         parts_res = _run_blocks(one, blocks)
-        return _merge_cv(spec, parts_res, [a for _, a, _ in blocks], intervals)
+        row_first = [0 if offsets is None else int(offsets[a]) for _, a, _ in blocks]
+        return _merge_cv(spec, parts_res, [a for _, a, _ in blocks], intervals, row_first)
     ctx = ctx or get_context()
     L = _lib.load()
     cs = spec.to_c()
@@ -1227,13 +1363,13 @@ def cross_validate(spec, ds_ns, y, horizon, period=None, initial=None, offsets=N
         y_rows = y[ridx].astype(np.float64)
     return CVResult(spec=spec, status=sst, n_folds=plan['n_folds'], n_holdout=plan['n_holdout'], n_metric=plan['n_metric'],
                     fold_series=fold_series, cutoff=plan['cutoff'], hist_rows=plan['hist_rows'], hold_rows=plan['hold_rows'],
-                    fit=FitResult(spec, *farrs), row_fold=row_fold, ds=ds_ns[ridx], y=y_rows, yhat=yhat,
+                    fit=FitResult(spec, *farrs), row_fold=row_fold, row_index=ridx, ds=ds_ns[ridx], y=y_rows, yhat=yhat,
                     yhat_lower=lo, yhat_upper=hi,
                     metric_series=np.repeat(np.arange(N, dtype=np.int64), plan['n_metric']), horizon=hz, mse=mse,
                     rmse=rmse, mae=mae, mape=mape, coverage=cov)
 
 
-def _merge_cv(spec, parts, firsts, intervals):
+def _merge_cv(spec, parts, firsts, intervals, row_first):
     cat = lambda k, p=parts: np.concatenate([getattr(x, k) for x in p])     # noqa: E731
     f_first = np.cumsum([0] + [len(p.cutoff) for p in parts])
     shifted = lambda k, base: np.concatenate([getattr(p, k) + b for p, b in zip(parts, base)])   # noqa: E731
@@ -1241,7 +1377,7 @@ def _merge_cv(spec, parts, firsts, intervals):
                     n_metric=cat('n_metric'), fold_series=shifted('fold_series', firsts), cutoff=cat('cutoff'),
                     hist_rows=cat('hist_rows'), hold_rows=cat('hold_rows'),
                     fit=_merge_fits(spec, [p.fit for p in parts], shared_grid=False),
-                    row_fold=shifted('row_fold', f_first[:-1]), ds=cat('ds'), y=cat('y'), yhat=cat('yhat'),
+                    row_fold=shifted('row_fold', f_first[:-1]), row_index=shifted('row_index', row_first), ds=cat('ds'), y=cat('y'), yhat=cat('yhat'),
                     yhat_lower=cat('yhat_lower') if intervals else None, yhat_upper=cat('yhat_upper') if intervals else None,
                     metric_series=shifted('metric_series', firsts), horizon=cat('horizon'), mse=cat('mse'),
                     rmse=cat('rmse'), mae=cat('mae'), mape=cat('mape'), coverage=cat('coverage') if intervals else None)
@@ -1256,6 +1392,102 @@ def performance_metrics(cv):
     if cv.coverage is not None:
         d['coverage'] = cv.coverage
     return pd.DataFrame(d)
+
+
+class CVScores(object):
+    """What score_cv returns.  quantiles [Q].  Per holdout row [R], in the CVResult's row order: pit, crps [R] and q,
+    pinball [Q][R] (None without levels).  Per fold [F], the library's aggregates over the fold's holdout rows:
+    fold_n_obs, fold_mean_crps [F], fold_mean_pinball, fold_coverage [F][Q].  Per series [N], over all its holdout rows in
+    row order: n_obs (int64), mean_crps [N], mean_pinball, coverage [N][Q]; NaN (n_obs 0) for a series whose
+    CVResult.status is not 0."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def cv_fold_keys(cv, series_key=None):
+    """The interval stream key of every fold of a CVResult (include/tsf.h, cross-validation):
+    (int64)((uint64)key_n * 0x9E3779B97F4A7C15 + (uint64)c) for fold c of series n; key_n = series_key[n] (None: n)."""
+    N = len(cv.status)
+    key = np.arange(N, dtype=np.int64) if series_key is None else np.ascontiguousarray(series_key, dtype=np.int64)
+    if key.shape != (N,):
+        raise ValueError('series_key must be [N]')
+    F = len(cv.cutoff)
+    c = (np.arange(F, dtype=np.int64) - cv.fold_offsets[:-1][cv.fold_series]).astype(np.uint64)
+    with np.errstate(over='ignore'):
+        return (key[cv.fold_series].view(np.uint64) * np.uint64(0x9E3779B97F4A7C15) + c).view(np.int64)
+
+
+def cv_fold_futures(cv, extra=None):
+    """The holdout rows of a CVResult as one padded batch over its F folds -> (ds [F][Hmax], pad [F][Hmax] bool, row
+    [F][Hmax] index into the [R] holdout rows, extra_future [F][n_extra][Hmax] or None): every fold's holdout dates,
+    padded to the longest holdout by repeating its last one.  extra: the caller's [n_extra][len(ds)] columns."""
+    F = len(cv.cutoff)
+    hold = cv.hold_rows.astype(np.int64)
+    Hm = int(hold.max()) if F else 0
+    first = np.concatenate([[0], np.cumsum(hold)[:-1]]).astype(np.int64) if F else np.zeros(0, np.int64)
+    j = np.arange(Hm, dtype=np.int64)[None, :]
+    pad = j >= hold[:, None]
+    row = first[:, None] + np.minimum(j, hold[:, None] - 1)
+    exf = None
+    if extra is not None:
+        ex = np.asarray(extra, dtype=np.float64)
+        exf = np.ascontiguousarray(np.moveaxis(ex[:, cv.row_index[row]], 0, 1))      # [n_extra][F][Hm] -> [F][n_extra][Hm]
+    return cv.ds[row], pad, row, exf
+
+
+def score_cv(cv, quantiles=(), floor=None, cap=None, extra=None, series_key=None, uncertainty_samples=1000, seed=0,
+             ctx=None):
+    """Every holdout row of a cross_validate result scored against its fold's predictive distribution -> CVScores: one
+    score_actuals call over the F folds (fold f's model from cv.fit, its holdout dates padded to the longest holdout by
+    repeating the last one, y NaN on the padding, the fold's stream key as in cross_validate).  floor / cap / extra /
+    series_key: what cross_validate was given.  With the same uncertainty_samples and seed, the levels (1 - w) / 2 and
+    (1 + w) / 2 give cross_validate's yhat_lower / yhat_upper at width w bit for bit."""
+    levels = np.array(quantiles, dtype=np.float64).reshape(-1)
+    Q = len(levels)
+    N, F, R = len(cv.status), len(cv.cutoff), len(cv.y)
+    spec = cv.spec
+    if spec.extra and extra is None:
+        raise ValueError('extra is required: the spec has extra columns')
+    fs = cv.fold_series
+    fl = _opt_f64(floor, N, 'floor')
+    cp = _opt_f64(cap, N, 'cap')
+    nanv = lambda *shape: np.full(shape, np.nan)      # noqa: E731
+    out = dict(quantiles=levels, pit=nanv(R), crps=nanv(R), q=nanv(Q, R) if Q else None,
+               pinball=nanv(Q, R) if Q else None, fold_n_obs=np.zeros(F, np.int32), fold_mean_crps=nanv(F),
+               fold_mean_pinball=nanv(F, Q) if Q else None, fold_coverage=nanv(F, Q) if Q else None,
+               n_obs=np.zeros(N, np.int64), mean_crps=nanv(N), mean_pinball=nanv(N, Q) if Q else None,
+               coverage=nanv(N, Q) if Q else None)
+    if F == 0 or R == 0:
+        return CVScores(**out)
+    fut, pad, row, exf = cv_fold_futures(cv, extra if spec.extra else None)
+    y_obs = np.where(pad, np.nan, cv.y[row])
+    s = score_actuals(spec, cv.fit.theta, cv.fit.y_scale, cv.fit.grid, fut, y_obs, levels,
+                      floor=None if fl is None else fl[fs], cap=None if cp is None else cp[fs], extra_future=exf,
+                      series_key=cv_fold_keys(cv, series_key), uncertainty_samples=uncertainty_samples, seed=seed, ctx=ctx)
+    real = ~pad
+    out['pit'], out['crps'] = s.pit[real], s.crps[real]               # (row-major over [F][Hmax]: cv's row order)
+    out['fold_n_obs'], out['fold_mean_crps'] = s.n_obs, s.mean_crps
+    if Q:
+        out['q'] = np.ascontiguousarray(np.moveaxis(s.q, 1, 0)[:, real])
+        out['pinball'] = np.ascontiguousarray(np.moveaxis(s.pinball, 1, 0)[:, real])
+        out['fold_mean_pinball'], out['fold_coverage'] = s.mean_pinball, s.coverage
+    # per series: tsf_score_actuals' per-series rule on the host -- a left-to-right sum from +0.0 over its observed
+    # holdout rows (np.cumsum of a 1-D array adds in index order)
+    seq = lambda x: np.cumsum(np.concatenate([[0.0], x]))[-1]      # noqa: E731
+    ro = cv.row_offsets
+    for n in np.flatnonzero(np.asarray(cv.status) == 0):
+        rows = np.arange(int(ro[n]), int(ro[n + 1]))
+        obs = rows[~np.isnan(cv.y[rows])]
+        out['n_obs'][n] = len(obs)
+        if not len(obs):
+            continue
+        cnt = np.float64(len(obs))
+        out['mean_crps'][n] = seq(out['crps'][obs]) / cnt
+        for i in range(Q):
+            out['mean_pinball'][n, i] = seq(out['pinball'][i, obs]) / cnt
+            out['coverage'][n, i] = np.float64(np.count_nonzero(cv.y[obs] <= out['q'][i, obs])) / cnt
+    return CVScores(**out)
 
 
 def last_cv_grids(ctx=None):

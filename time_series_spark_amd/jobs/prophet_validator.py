@@ -21,7 +21,17 @@ as null.  It writes io.tuning, one row per series with a choice:
 
     series_id, dim_id, changepoint_prior_scale, seasonality_prior_scale, holidays_prior_scale, metric, score
 
-Series without a choice are reported on stdout.  Without `tune` the job does what it did before."""
+Series without a choice are reported on stdout.  Without `tune` the job does what it did before.
+
+An optional `scores` section scores every holdout row against its fold's predictive distribution (include/tsf.h
+tsf_score_actuals, forecaster.score_cv): quantiles (a list of levels in [0, 1], may be empty), uncertainty_samples
+(1000), seed (0).  It writes io.scores, one row per series that was cross-validated:
+
+    series_id, dim_id, n_obs, crps, pinball_q<..> per level, coverage_q<..> per level
+
+(crps and pinball_q*: the means over the series' holdout rows; coverage_q*: the share of them at or below the quantile;
+names as forecaster.quantile_columns), and the fold frame gains pit and crps.  Without `scores` every output is what it
+was before."""
 import os
 import time
 
@@ -75,6 +85,31 @@ def tune_settings(config):
     return grid, metric
 
 
+def score_settings(config):
+    """The `scores` section -> dict(quantiles, uncertainty_samples, seed), or None without one."""
+    sc = config.get('scores')
+    if sc is None:
+        return None
+    sc = dict(sc)
+    unknown = sorted(set(sc) - {'quantiles', 'uncertainty_samples', 'seed'})
+    if unknown:
+        raise ValueError('unknown scores keys %s (quantiles, uncertainty_samples, seed)' % unknown)
+    q = sc.get('quantiles')
+    q = [] if q is None else (list(q) if isinstance(q, (list, tuple)) else [q])
+    levels = [float(x) for x in q]
+    fc.quantile_columns(levels)         # (ValueError for a bad level)
+    n = int(sc.get('uncertainty_samples', 1000))
+    if not 2 <= n <= 4096:
+        raise ValueError('scores.uncertainty_samples must be in [2, 4096]')
+    return dict(quantiles=levels, uncertainty_samples=n, seed=int(sc.get('seed', 0)))
+
+
+def score_columns(levels):
+    """Columns of the io.scores frame for the levels of the `scores` section."""
+    return (['series_id', 'dim_id', 'n_obs', 'crps'] + fc.quantile_columns(levels, 'pinball_q')
+            + fc.quantile_columns(levels, 'coverage_q'))
+
+
 def _buckets(config, panel):
     """Per model bucket of the modeler: (spec, members, offsets, ds, y, extra, cap of the members) -- the bucket's
     series as one ragged panel."""
@@ -104,7 +139,14 @@ def _series_keys(panel):
 
 def validate_panel(config, panel):
     """-> (metrics frame, fold frame) for a PackedPanel."""
+    return validate_scored(config, panel)[:2]
+
+
+def validate_scored(config, panel):
+    """-> (metrics frame, fold frame, scores frame or None without a `scores` section) for a PackedPanel."""
     cvs = cv_settings(config)
+    scs = score_settings(config)
+    scores = []
     floor = float(config['model']['floor'])
     sids, dids = _series_keys(panel)
     # the interval streams of a series are keyed by (series_id, dim_id): the same intervals whatever else is in the run
@@ -131,10 +173,25 @@ def validate_panel(config, panel):
               'y': cv.y[keep], 'yhat': cv.yhat[keep]}
         if cv.yhat_lower is not None:
             fr['yhat_lower'], fr['yhat_upper'] = cv.yhat_lower[keep], cv.yhat_upper[keep]
+        if scs is not None:
+            sc = fc.score_cv(cv, scs['quantiles'], floor=np.full(len(members), floor), cap=cap_m, extra=ex,
+                             series_key=key[members], uncertainty_samples=scs['uncertainty_samples'], seed=scs['seed'])
+            fr['pit'], fr['crps'] = sc.pit[keep], sc.crps[keep]
+            good = np.flatnonzero(cv.status == 0)
+            sf = {'series_id': sids[members[good]].astype('int32'), 'dim_id': dids[members[good]].astype('int32'),
+                  'n_obs': sc.n_obs[good], 'crps': sc.mean_crps[good]}
+            for arr, prefix in ((sc.mean_pinball, 'pinball_q'), (sc.coverage, 'coverage_q')):
+                for i, name in enumerate(fc.quantile_columns(scs['quantiles'], prefix)):
+                    sf[name] = arr[good, i]
+            scores.append(pd.DataFrame(sf, columns=score_columns(scs['quantiles'])))
         folds.append(pd.DataFrame(fr))
+    sc_frame = None
+    if scs is not None:
+        sc_frame = pd.concat(scores, ignore_index=True).sort_values(['series_id', 'dim_id'], kind='stable')
+        sc_frame = sc_frame.reset_index(drop=True)
     m = pd.concat(metrics, ignore_index=True).sort_values(['series_id', 'dim_id', 'horizon'], kind='stable')
     f = pd.concat(folds, ignore_index=True).sort_values(['series_id', 'dim_id', 'cutoff', 'ds'], kind='stable')
-    return m.reset_index(drop=True), f.reset_index(drop=True)
+    return m.reset_index(drop=True), f.reset_index(drop=True), sc_frame
 
 
 def tune_panel(config, panel):
@@ -172,7 +229,8 @@ def tune_panel(config, panel):
 
 
 class ProphetValidator(object):
-    """Cross-validate the models the modeler would fit (config: the modeler's keys + `cv` + io.metrics [+ io.folds])."""
+    """Cross-validate the models the modeler would fit (config: the modeler's keys + `cv` + io.metrics [+ io.folds]
+    [+ `scores` + io.scores])."""
 
     def __init__(self, config):
         self.config = config
@@ -186,13 +244,18 @@ class ProphetValidator(object):
         if (panel.lengths < 2).any() or panel.dropped_keys:
             raise ValueError('Dataframe has less than 2 non-NaN rows.')
         pm.check_changepoints(pm._prophet_kwargs(config), panel)
-        metrics, folds = validate_panel(config, panel)
+        if config.get('scores') is not None and not config['io'].get('scores'):
+            raise ValueError('the scores section needs io.scores')
+        metrics, folds, scores = validate_scored(config, panel)
         tuning = tune_panel(config, panel) if config.get('tune') is not None else None
         os.makedirs(config['io']['metrics'], exist_ok=True)
         metrics.to_parquet(os.path.join(config['io']['metrics'], 'part-00000.parquet'), index=False)
         if config['io'].get('folds'):
             os.makedirs(config['io']['folds'], exist_ok=True)
             folds.to_parquet(os.path.join(config['io']['folds'], 'part-00000.parquet'), index=False)
+        if scores is not None:
+            os.makedirs(config['io']['scores'], exist_ok=True)
+            scores.to_parquet(os.path.join(config['io']['scores'], 'part-00000.parquet'), index=False)
         if tuning is not None:
             os.makedirs(config['io']['tuning'], exist_ok=True)
             tuning.to_parquet(os.path.join(config['io']['tuning'], 'part-00000.parquet'), index=False)
