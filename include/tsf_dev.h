@@ -22,7 +22,11 @@ extern "C" {
 enum {
     TSF_OPT_HARM = 0,        /* 0: the residual-form kernel streams every design column from the table instead of
                                 expanding the Fourier columns from the rows' base pairs; 1 / 2: never / always the variant of
-                                that kernel that requests a row one step ahead (default: where the rows come from HBM) */
+                                that kernel that requests a row one step ahead (default: where the rows come from HBM).
+                                0 also keeps every quadratic-form kernel on the design table: the Gram build of a ragged
+                                call with a calendar per series, and the residual passes of an aligned call with
+                                3 + S + K <= 64, which otherwise go over base-pair rows in ONE sweep (no parked weights)
+                                for the compiled shapes yearly 10 + weekly 3, weekly 3 + daily 4, weekly 3 */
     TSF_OPT_LATTICE,         /* 0 / 1: never / always the shared lattice table of a ragged call on regular timestamps */
     TSF_OPT_SPARSE_EXTRA,    /* 0: holiday columns of a wide model as dense columns; 2: sparse fit kernel, but its stragglers on the
                                 64-column cooperative kernel instead of the sparse one (A/B runs, tests) */

@@ -625,6 +625,14 @@ static int run_fit(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int aligned, i
     int gram_harm = 0;
     if (quad && !aligned && !quad_pre && lat_U == 0 && hs.harm == HARM_Y10_W3 && hs.KP == 28 && ctx->opt[TSF_OPT_HARM] != 0)
         gram_harm = hs.harm;
+    // ... and for the residual passes of an ALIGNED quadratic-form call with one parameter per lane (the 12- and 16-wave
+    // kernels, the M-in-registers kernel, tsf_eval_quadratic): rows as base pairs, the column sums taken in the row sweep
+    // itself (ztr_sweep_harm, tsf_quad_kernels.h) -- every compiled shape, dense columns behind the Fourier block allowed.
+    // Two-slot kernels (P > 64), ragged calls and other models keep the two-sweep table route; TSF_OPT_HARM 0: every call.
+    int resid_harm = 0;
+    if ((quad || quad_eval) && aligned && qp.PPL == 1 && ctx->opt[TSF_OPT_HARM] != 0 &&
+        ((hs.harm == HARM_Y10_W3 && hs.KP == 28) || (hs.harm == HARM_W3_D4 && hs.KP == 16) || (hs.harm == HARM_W3 && hs.KP == 8)))
+        resid_harm = hs.harm;
     // ... and for the MAP continuation (tsf_map_kernels.h): its evaluator reads base-pair rows wherever the model has a
     // compiled expansion, whatever kernel ran the Stan-rule fit (the quadratic-form route builds the table for it)
     int map_harm = 0;
@@ -632,7 +640,7 @@ static int run_fit(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int aligned, i
         hs.K == harm_kf(hs.harm) &&
         ((hs.harm == HARM_Y10_W3 && hs.KP == 28) || (hs.harm == HARM_W3_D4 && hs.KP == 16) || (hs.harm == HARM_W3 && hs.KP == 8)))
         map_harm = hs.harm;
-    const int bw_ns = (harm || gram_harm || map_harm) ? hs.n_seas : 0;
+    const int bw_ns = (harm || gram_harm || resid_harm || map_harm) ? hs.n_seas : 0;
     // Quadratic-form L-BFGS fits read the caller's y rows themselves (FitArgs::y_raw) instead of a scaled step-major copy
     // that setup_series_kernel would write and they would read back -- a second f64 panel on the device and half of the
     // step's HBM bytes.  Not when the MAP continuation follows (its evaluator reads yw).
@@ -757,6 +765,7 @@ static int run_fit(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int aligned, i
         memset(&qa, 0, sizeof(qa));
         qa.f = a; qa.Mg = (const double *)(ws + l.Mg); qa.rbuf = (double *)(ws + l.rbuf);
         qa.counter = (int *)(ws + l.counter); qa.P4 = qp.P4;
+        qa.resid_harm = resid_harm;
         lrc = launch_eval_quad(hs.KP, qp, qa, (double *)(ws + l.Mg), theta_ref, st);
     } else if (quad) {
         QuadArgs qa;
@@ -767,7 +776,7 @@ static int run_fit(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int aligned, i
         qa.recenter_every = spec->recenter_every; qa.recenter_ratio = spec->recenter_ratio;
         qa.dbg = nullptr; qa.nb_buf = nullptr; qa.nb_bytes = 0;
         qa.Mpre = quad_pre ? qa.Mg : nullptr; qa.n_pre = quad_pre;
-        qa.gram_harm = gram_harm;
+        qa.gram_harm = gram_harm; qa.resid_harm = resid_harm;
         HIP_TRY(ctx, hipMemsetAsync(qa.counter, 0, sizeof(int), st));
         lrc = -1;
         if (spec->converge == TSF_CONVERGE_MAP && qp.PPL == 1 && ctx->opt[TSF_OPT_MAP_DIRECT] != 0) {

@@ -60,6 +60,8 @@ struct QuadArgs {
     size_t nb_bytes;
     int gram_harm;                      // ragged, a grid per series, M in registers: harm_code of the model when the build expands the
                                         // Fourier columns from the rows' base pairs (FitArgs::Bw; gram_columns_harm), else 0
+    int resid_harm;                     // aligned, one parameter per lane: harm_code of the model when the residual passes take
+                                        // the one-sweep route over base-pair rows (ztr_sweep_harm), else 0
 };
 
 template <int KP, int PPL>
@@ -201,6 +203,33 @@ __device__ __forceinline__ void column_group_harm(const SeriesView &sv, const do
     column_sums_g<G>(acc, accR + G0);
 }
 
+// the entries of Z^T r from the tables a residual pass leaves in wl (tot1 / tot2, tp1 / tp2, accR): ztr[s] is entry
+// p = lane + 64 s
+template <int KP, int PPL>
+__device__ __forceinline__ void ztr_entries(const SeriesView &sv, QuadLds<KP, PPL> &wl, double (&ztr)[PPL])
+{
+    const int lane = lane_id();
+    const int S = sv.S;
+    wave_sync();
+#pragma unroll
+    for (int s = 0; s < PPL; ++s) {
+        const int p = lane + s * W;
+        double v = 0.0;
+        if (p == 0) v = wl.tot1[0];
+        else if (p == 1) v = wl.tot2[0];
+        else if (p >= 3 && p < 3 + S) {
+            const int j = p - 3, Lj = sv.Ljp_l[s];
+            const double SA = wl.tp1[j] + wl.tot1[Lj + 1];
+            const double SB = wl.tp2[j] + wl.tot2[Lj + 1];
+            v = SA - sv.tcp_l[s] * SB;
+        } else if (p >= 3 + S && p < sv.P) {
+            v = wl.accR[p - 3 - S];
+        }
+        ztr[s] = v;
+    }
+    wave_sync();
+}
+
 // Z^T r and r.r, in the operation order of eval_fg<GROWTH 0, MODE 0> (cn_ztr).  The weight of
 // row lane*NT+q comes from gen(q, idx, c, ti) (called for valid rows only, q descending); it is
 // parked in rb[q*64+lane] for the per-column passes (0 for rows past the end of the series).
@@ -264,24 +293,132 @@ __device__ __forceinline__ void ztr_pass(const SeriesView &sv, QuadLds<KP, PPL> 
     for (int g0 = 0; g0 < G8; g0 += 8) column_group<KP, 8, NTR>(sv, rb, g0, wl.accR, rr);
     if (KP % 8 != 0) column_group<KP, 4, NTR>(sv, rb, G8, wl.accR, rr);
     }
-    wave_sync();
+    ztr_entries<KP, PPL>(sv, wl, ztr);
+}
+
+// ONE SWEEP over the rows of an aligned panel kept as base pairs (SeriesView::Bw), for the models with a compiled harmonic
+// shape: the row step that produced the weight r also accumulates the K column sums, acc_j = fma(x_j, r, acc_j), with the
+// Fourier columns expanded a second time from the same pairs (harm_row: the bits Xw holds) and any dense columns behind the
+// Fourier block read from Xw.  column_group runs q descending as row_step does, so every accumulator sees the operands of
+// the two-sweep form in the same order: the same bits, with no parked weights (no rr / rb, no NTR) and 3 + NS loads per
+// row step instead of 2 KP + 1.  Rows a lane does not have: weight 0 against pairs forced to (0, 0) -- every harmonic is
+// then +-0 and fma(+-0, 0, acc) leaves acc (which is never -0) as it is, as the zero padding of Xw does.
+// beta: the coefficients in column order (wl.th + 3 + S).
+// PF: the next step's inputs requested ahead; BB: coefficients per LDS round trip (below).  The kernels with registers to
+// spare take PF with BB = 4; the M-in-registers kernel (256 registers, 112 of them Z^T Z) PF with BB = 2 -- the forms that
+// compile without a scratch access inside the sweep.
+template <int KP, int PPL, int HARM, bool PF = true, int BB = 4>
+__device__ __forceinline__ void ztr_sweep_harm(const SeriesView &sv, QuadLds<KP, PPL> &wl, const double *beta,
+                                               double &sse_out, double (&ztr)[PPL])
+{
+    constexpr int KF = harm_kf(HARM), NS = harm_ns(HARM);
+    static_assert(BB == 2 || BB == 4 || BB == 8, "coefficient batches: a power of two");
+    static_assert(HARM != 0 && KF <= KP && KP % 4 == 0, "one-sweep residual pass: a compiled harmonic shape inside the column tile");
+    const int lane = lane_id();
+    const bool has_xd = sv.P - 3 - sv.S > KF;
+    double sse = 0.0, rt1 = 0.0, rt2 = 0.0;
+    double acc[KP];
 #pragma unroll
-    for (int s = 0; s < PPL; ++s) {
-        const int p = lane + s * W;
-        double v = 0.0;
-        if (p == 0) v = wl.tot1[0];
-        else if (p == 1) v = wl.tot2[0];
-        else if (p >= 3 && p < 3 + S) {
-            const int j = p - 3, Lj = sv.Ljp_l[s];
-            const double SA = wl.tp1[j] + wl.tot1[Lj + 1];
-            const double SB = wl.tp2[j] + wl.tot2[Lj + 1];
-            v = SA - sv.tcp_l[s] * SB;
-        } else if (p >= 3 + S && p < sv.P) {
-            v = wl.accR[p - 3 - S];
+    for (int j = 0; j < KP; ++j) acc[j] = 0.0;
+    // The inputs of a row step -- segment word, t, y, the base pairs: 3 + NS loads -- are requested one step AHEAD of their
+    // use and all at once: a wave of this kernel is bound by its dependent chains, and every load waited for where it is
+    // used is a round trip to L2 on the chain.  The table loads are unconditional (rows a lane does not have exist in the
+    // tables: NTmax x 64 entries per grid; their values are dropped below); y keeps its raw bits until the step that uses
+    // them, so that the conversion does not wait at the request.
+    struct RowIn { unsigned cwv, ylo, yhi; double ti; double2 bp[NS]; };
+    auto row_fetch = [&](int q, RowIn &ri) {
+        const int idx = q * W + lane;
+        ri.cwv = (unsigned)sv.cw[idx]; ri.ti = sv.tw[idx];
+        const double2 *bq = reinterpret_cast<const double2 *>(sv.Bw) + (size_t)q * NS * W + lane;
+#pragma unroll
+        for (int se = 0; se < NS; ++se) ri.bp[se] = bq[se * W];
+        ri.ylo = 0u; ri.yhi = 0u;
+        if (sv.y_raw) {
+            if (q < sv.cnt) {
+                const long long i = sv.y_base + (long long)lane * sv.NT + q;
+                if (sv.y_dtype == TSF_Y_F64) { const uint2 b = reinterpret_cast<const uint2 *>(sv.y_raw)[i]; ri.ylo = b.x; ri.yhi = b.y; }
+                else ri.ylo = reinterpret_cast<const unsigned *>(sv.y_raw)[i];
+            }
+        } else {
+            const uint2 b = reinterpret_cast<const uint2 *>(sv.yw)[idx]; ri.ylo = b.x; ri.yhi = b.y;
         }
-        ztr[s] = v;
+    };
+    RowIn rnext;
+    if (PF && sv.NT > 0) row_fetch(sv.NT - 1, rnext);
+#pragma unroll 1
+    for (int q = sv.NT - 1; q >= 0; --q) {
+        RowIn rc;
+        if (PF) { rc = rnext; if (q > 0) row_fetch(q - 1, rnext); }
+        else row_fetch(q, rc);
+        const bool valid = q < sv.cnt;
+        const unsigned cwv = valid ? rc.cwv : 0u;
+        const int c = (int)(cwv & 0xffu), cprev = (int)(cwv >> 8);
+        const double ti = valid ? rc.ti : 0.0;
+        double yi = __hiloint2double((int)rc.yhi, (int)rc.ylo);
+        if (sv.y_raw) {
+            // load_y's conversions, then setup_series_kernel's scaling (resid_eval_q's gen)
+            if (sv.y_dtype == TSF_Y_F32) yi = (double)__uint_as_float(rc.ylo);
+            else if (sv.y_dtype != TSF_Y_F64) yi = (double)(int)rc.ylo;
+            yi = yi / sv.y_scl;
+            if (!valid) yi = 0.0;
+        }
+        const double *xp = sv.Xw + (size_t)q * KP * W + lane;
+        double2 bp[NS];
+#pragma unroll
+        for (int se = 0; se < NS; ++se) { bp[se].x = valid ? rc.bp[se].x : 0.0; bp[se].y = valid ? rc.bp[se].y : 0.0; }
+        // X.beta, columns ascending.  The coefficients come from LDS BB at a time (the empty asm: one round trip per
+        // batch, not one per pair in the middle of the chain)
+        double xa = 0.0, bb[BB];
+        harm_row<HARM>(bp, [&](int j, double v) {
+            if ((j & (BB - 1)) == 0) {
+#pragma unroll
+                for (int u = 0; u < BB; ++u) bb[u] = beta[j + u];
+#pragma unroll
+                for (int u = 0; u < BB; ++u) asm volatile("" : "+v"(bb[u]));
+            }
+            xa = __builtin_fma(v, bb[j & (BB - 1)], xa);
+        });
+        if (KF < KP && has_xd) {
+#pragma unroll
+            for (int j = KF; j < KP; ++j) xa = __builtin_fma(xp[j * W], beta[j], xa);
+        }
+        const double gtr = __builtin_fma(wl.ks[c], ti, wl.mc[c]);
+        double r = yi - (gtr + xa);
+        if (!valid) r = 0.0;
+        sse = __builtin_fma(r, r, sse);
+        rt1 = __builtin_fma(r, ti, rt1);
+        rt2 = rt2 + r;
+        for (int j = cprev; j < c; ++j) { wl.tp1[j] = rt1; wl.tp2[j] = rt2; }
+        // (the empty asm: the second expansion is not recognised as the first, so the row's 2 x order values are not held
+        // across the trend arithmetic -- as in eval_fg HARM, tsf_fit_kernels.h)
+#pragma unroll
+        for (int se = 0; se < NS; ++se) { asm volatile("" : "+v"(bp[se].x)); asm volatile("" : "+v"(bp[se].y)); }
+        harm_row<HARM>(bp, [&](int j, double v) { acc[j] = __builtin_fma(v, r, acc[j]); });
+        if (KF < KP && has_xd) {
+#pragma unroll
+            for (int j = KF; j < KP; ++j) acc[j] = __builtin_fma(xp[j * W], r, acc[j]);
+        }
     }
-    wave_sync();
+    sse_out = bfly_sum(sse);
+    const double s1 = suffix_scan(rt1), s2v = suffix_scan(rt2);
+    wl.tot1[lane] = s1; wl.tot2[lane] = s2v;
+    if (lane == 0) { wl.tot1[W] = 0.0; wl.tot2[W] = 0.0; }
+    // the butterflies of column_group, over its groups: eights, then a four
+#pragma unroll
+    for (int g0 = 0; g0 < KP; g0 += 8) {
+        if (KP - g0 >= 8) {
+            double ga[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) ga[u] = acc[g0 + u < KP ? g0 + u : 0];
+            column_sums_g<8>(ga, wl.accR + g0);
+        } else {
+            double ga[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) ga[u] = acc[g0 + u < KP ? g0 + u : 0];
+            column_sums_g<4>(ga, wl.accR + g0);
+        }
+    }
+    ztr_entries<KP, PPL>(sv, wl, ztr);
 }
 
 // per-lane constants of cn_assemble_q
@@ -467,8 +604,18 @@ __device__ __forceinline__ bool assemble_q(const SeriesView &sv, const LaneConst
     return assemble_post<PPL>(sv, lk, ap, sabs, sb, th, sse, ztr, f_out, g);
 }
 
+// the compiled harmonic shape of a column tile (tsf_api.hip launches the one-sweep pass for exactly these): yearly 10 +
+// weekly 3 on 28 columns, weekly 3 + daily 4 on 16, weekly 3 on 8
+constexpr int quad_harm_of(int kp) { return kp == 28 ? HARM_Y10_W3 : (kp == 16 ? HARM_W3_D4 : (kp == 8 ? HARM_W3 : 0)); }
+
+// ... and whether the kernel variant has the registers for it: the 16-wave pooled kernel (128 registers) cannot hold the 28
+// accumulators of the 28-column tile beside the row in flight without scratch accesses inside the sweep, and keeps the
+// two-sweep table route there (launch_quad_mm sizes its pool slots by the same rule)
+constexpr bool quad_sweep_fits(int kp, bool pool) { return !(pool && kp > 16); }
+
 // residual-form evaluation (cn_resid_q): r -> rb, then Z^T r, then assemble_q
-template <int KP, int PPL, int NTR = 0, int HARM = 0>
+// ONE (HARM != 0): rows as base pairs and the column sums in the row sweep itself (ztr_sweep_harm); rb is not used
+template <int KP, int PPL, int NTR = 0, int HARM = 0, bool ONE = false, bool PF = true, int BB = 4>
 __device__ __forceinline__ bool resid_eval_q(const SeriesView &sv, QuadLds<KP, PPL> &wl,
                                              const LaneConst<PPL> &lk, double *rb,
                                              const double (&th)[PPL], double &f_out,
@@ -492,6 +639,11 @@ __device__ __forceinline__ bool resid_eval_q(const SeriesView &sv, QuadLds<KP, P
     }
     wave_sync();
     const double *beta = wl.th + 3 + S;
+    if constexpr (ONE) {
+        static_assert(!ONE || (HARM != 0 && NTR == 0), "one-sweep pass: base-pair rows, no parked weights");
+        ztr_sweep_harm<KP, PPL, HARM, PF, BB>(sv, wl, beta, sse_out, ztr);
+        return assemble_q<PPL>(sv, lk, th, sse_out, ztr, f_out, g);
+    } else {
     auto gen = [&](int q, int idx, int c, double ti) -> double {
         // y of the row: from the scaled step-major copy, or (round 6) the caller's own row, scaled here with
         // setup_series_kernel's operation -- (y - 0) / y_scale: linear growth has no floor -- so the same bits, and no
@@ -530,6 +682,7 @@ __device__ __forceinline__ bool resid_eval_q(const SeriesView &sv, QuadLds<KP, P
     };
     ztr_pass<KP, PPL, NTR, HARM>(sv, wl, rb, gen, sse_out, ztr);
     return assemble_q<PPL>(sv, lk, th, sse_out, ztr, f_out, g);
+    }
 }
 
 // quadratic-form evaluation (cn_eval_gram).  Ml: [P4][PPL][64] in LDS (or global).
@@ -1228,13 +1381,22 @@ __device__ __forceinline__ bool fit_one_quad(const QuadArgs &qa, QuadLds<KP, PPL
         sv.n_eval++;
         QT_LAP(2);
         bool bad;
+        // aligned panel, one parameter per lane, a model with a compiled harmonic shape (QuadArgs::resid_harm): the
+        // one-sweep pass over base-pair rows
+        constexpr int HM1 = (!RAGGED && PPL == 1 && quad_sweep_fits(KP, POOL)) ? quad_harm_of(KP) : 0;
         if constexpr (POOL) {
             const int slot = pool_acquire(*pool);
             unsigned char *sl = pool->slots + (size_t)slot * pool->slot_bytes;
             // short series: the slot also holds the staging rows (slot_bytes says so); else the global scratch
             double *rbs = pool->slot_bytes > sizeof(QuadLds<KP, PPL>) ? reinterpret_cast<double *>(sl + sizeof(QuadLds<KP, PPL>)) : rb;
+            if (HM1 != 0 && qa.resid_harm == HM1)
+                bad = resid_eval_q<KP, PPL, 0, HM1, HM1 != 0>(sv, *reinterpret_cast<QuadLds<KP, PPL> *>(sl), lk, rbs, xe, fe, ge, sse_e, ztr_e);
+            else
             bad = resid_eval_q<KP, PPL, NTR>(sv, *reinterpret_cast<QuadLds<KP, PPL> *>(sl), lk, rbs, xe, fe, ge, sse_e, ztr_e);
             pool_release(*pool, slot);
+        } else if constexpr (HM1 != 0) {
+            if (qa.resid_harm == HM1) bad = resid_eval_q<KP, PPL, 0, HM1, true, true, MREG ? 2 : 4>(sv, *wlp, lk, rb, xe, fe, ge, sse_e, ztr_e);
+            else bad = resid_eval_q<KP, PPL, NTR>(sv, *wlp, lk, rb, xe, fe, ge, sse_e, ztr_e);
         } else if constexpr (RAGGED && MREG && PPL == 1 && KP == 28 && NTR == 0) {
             // a calendar per series: the rows as base pairs here too (QuadArgs::gram_harm)
             if (qa.gram_harm == HARM_Y10_W3) bad = resid_eval_q<KP, PPL, NTR, HARM_Y10_W3>(sv, *wlp, lk, rb, xe, fe, ge, sse_e, ztr_e);
@@ -1691,7 +1853,10 @@ __global__ __launch_bounds__(64) void eval_quad_kernel(QuadArgs qa, const double
         lk.ct = lanec + 3 * W;
         double xr[1], gr[1], fr, s0, ztr[1];
         load_theta<1>(a, sv, n, theta_ref, xr);
-        const bool bad_ref = resid_eval_q<KP, 1, NTR>(sv, wl, lk, rb, xr, fr, gr, s0, ztr);
+        constexpr int HM1 = quad_harm_of(KP);
+        bool bad_ref;
+        if (HM1 != 0 && qa.resid_harm == HM1) bad_ref = resid_eval_q<KP, 1, 0, HM1, HM1 != 0>(sv, wl, lk, rb, xr, fr, gr, s0, ztr);
+        else bad_ref = resid_eval_q<KP, 1, NTR>(sv, wl, lk, rb, xr, fr, gr, s0, ztr);
         wl.ref[lane] = (lane == 2) ? 0.0 : xr[0];
         wl.cvec[lane] = ztr[0];
         wave_sync();

@@ -126,8 +126,9 @@ static int launch_quad_mm(const QuadPlan &qp, const QuadArgs &qa, double *Mg, hi
         const size_t pbase = quad_pool_base_bytes<PPL>(qp.P4, TSF_QUAD_NW4);
         const size_t avail = pbase < 160 * 1024 ? 160 * 1024 - pbase : 0;
         // short series: the staging rows ride in the slot when that still leaves TSF_QUAD_POOL_RB_MIN copies
+        // (the one-sweep pass over base-pair rows -- QuadArgs::resid_harm -- parks no weights: tables only)
         size_t slot = sizeof(QuadLds<KP, PPL>) + sizeof(double) * (size_t)qa.f.NTmax * W;
-        if (avail / slot < TSF_QUAD_POOL_RB_MIN) slot = sizeof(QuadLds<KP, PPL>);
+        if (avail / slot < TSF_QUAD_POOL_RB_MIN || (qa.resid_harm != 0 && quad_sweep_fits(KP, true))) slot = sizeof(QuadLds<KP, PPL>);
         int ns = (int)(avail / slot);
         if (ns > TSF_QUAD_NW4) ns = TSF_QUAD_NW4;
         if (forced > 0 && forced < ns) ns = forced;
