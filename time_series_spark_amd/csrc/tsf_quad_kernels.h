@@ -1562,6 +1562,19 @@ __device__ __forceinline__ bool fit_one_quad(const QuadArgs &qa, QuadLds<KP, PPL
                 }
             }
             QT_LAP(6);                  // the two-loop recursion
+            // CT: the constants of the termination tests, read together and HERE -- the copies of the ring are dead, and
+            // the butterfly of g.p below runs while the eight loads are under way.  (Each read at its test, they were
+            // eight LDS round trips one after another, a branch behind each, in every iteration that goes on.)
+            // (Not the pooled kernel on the 28-column tile: at 128 registers the batch spills two more values per lane; it
+            // keeps the ladder below.)
+            constexpr bool TERM = CT && !(POOL && KP > 16);
+            double t_obj = 0, t_rel_obj = 0, g2_lo = 0, g2_hi = 0, rg_lo = 0, rg_hi = 0, p2_lo = 0, p2_hi = 0;
+            if constexpr (TERM) {
+                t_obj = qc(ct, QC_TOL_OBJ); t_rel_obj = qc(ct, QC_TOL_REL_OBJ);
+                g2_lo = qc(ct, QC_GRAD2_LO); g2_hi = qc(ct, QC_GRAD2_HI);
+                rg_lo = qc(ct, QC_RELGRAD_LO); rg_hi = qc(ct, QC_RELGRAD_HI);
+                p2_lo = qc(ct, QC_PARAM2_LO); p2_hi = qc(ct, QC_PARAM2_HI);
+            }
             const double dF = __builtin_fabs(fk1 - fk);
             const double fmaxv = __builtin_fmax(__builtin_fabs(fk1),
                                                 __builtin_fmax(__builtin_fabs(fk), 1.0));
@@ -1574,7 +1587,18 @@ __device__ __forceinline__ bool fit_one_quad(const QuadArgs &qa, QuadLds<KP, PPL
                 if (ngp > qc(ct, QC_RELGRAD_HI) * m) return false;
                 return ngp / m < qc(ct, QC_TOL_REL_GRAD);
             };
-            if constexpr (CT) {
+            if constexpr (TERM) {
+                // every outcome as a predicate of the values read above, then Stan's priority order.  The exact paths
+                // (operand inside a bracket) stay behind their branch and read their tolerance there.
+                const double m = __builtin_fmax(__builtin_fabs(fk), 1.0), ngp = -gp;
+                const bool absf = dF < t_obj, relf = dF < t_rel_obj * fmaxv;
+                bool absg = g2sum < g2_lo, relg = ngp < rg_lo * m, absx = s2sum < p2_lo;
+                if (!absg && !(g2sum >= g2_hi)) absg = __builtin_sqrt(g2sum) < qc(ct, QC_TOL_GRAD);
+                if (!relg && !(ngp > rg_hi * m)) relg = ngp / m < qc(ct, QC_TOL_REL_GRAD);
+                if (!absx && !(s2sum >= p2_hi)) absx = __builtin_sqrt(s2sum) < qc(ct, QC_TOL_PARAM);
+                ret = absf ? TSF_ST_ABSF : relf ? TSF_ST_RELF : absg ? TSF_ST_ABSGRAD : relg ? TSF_ST_RELGRAD
+                    : absx ? TSF_ST_ABSX : (itNum >= a.opt.max_iter) ? TSF_ST_MAXIT : 0;
+            } else if constexpr (CT) {
                 if (dF < qc(ct, QC_TOL_OBJ)) ret = TSF_ST_ABSF;
                 else if (dF < qc(ct, QC_TOL_REL_OBJ) * fmaxv) ret = TSF_ST_RELF;
                 else if (norm_below(g2sum, QC_GRAD2_LO, QC_TOL_GRAD)) ret = TSF_ST_ABSGRAD;
