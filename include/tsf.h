@@ -646,6 +646,91 @@ int tsf_tune(tsf_ctx *ctx, const tsf_spec *base, const tsf_spec *cand, int32_t C
              const double *cap, const double *extra, const tsf_cv_args *cv, int32_t metric, int32_t refit,
              tsf_tune_out *out);
 
+/* ---- outlier screening: robust residual flags and refit ------------------------------------------------
+ * One bad row -- a double-counted day, an outage, a unit mix-up -- bends the trend and the seasonality of its whole
+ * series, and Prophet's documented remedy is to remove the rows and fit again.  tsf_screen_rows is that decision for
+ * every series of a panel at once, as a pure function of (y, fitted, excluded) per series; tsf_fit_screened is the whole
+ * remedy in one call: fit, screen, cut, fit again.  Everything here is opt-in: no other entry point changes.
+ * Reference interface replaced: none (neither the reference nor fbprophet has such a function); parity unpinned (what is
+ * pinned is the contract below, bit for bit against a numpy restatement, and tsf_fit_screened against the composition of
+ * the public calls).  Timing: tools/bench_screen.py; DESIGN.md 5h.
+ *
+ * tsf_screen_rows.  Panel: aligned (offsets NULL: y, fitted, excluded, flag, resid are [N][T]) or ragged (T ignored;
+ * series n owns rows [offsets[n], offsets[n + 1]) of each).  y in y_dtype; fitted double; excluded uint8 (non-zero = the
+ * row was removed earlier and takes no part) or NULL; min_scale [N] (a floor under the robust scale) or NULL = 0.
+ * Host pointers in the host variant; device pointers in _dev (args and the tsf_screen_out struct itself are HOST memory
+ * in both; _dev on a ragged panel reads offsets back and synchronises the stream).
+ *
+ * Contract per series.  m0 = its row count; L = its rows with excluded == 0, m = |L|; x = m0 - m.  In plain double
+ * operations, one rounding each:
+ *   r_i = (double)y_i - fitted_i for every row;  a = {r_i : i in L} sorted ascending;
+ *   center = 0.5 * (a[(m-1)/2] + a[m/2]);  d_i = fabs(r_i - center);  b = {d_i : i in L} sorted ascending;
+ *   mad = 0.5 * (b[(m-1)/2] + b[m/2]);  scale = fmax(1.4826 * mad, min_scale[n]);
+ *   B = (int64)floor(max_share * (double)m0) - x  (the budget: at most a share max_share of the series' rows is ever
+ *   flagged, earlier exclusions included);  B <= 0: no new flag;  otherwise
+ *   cut = fmax(threshold * scale, b[m-1-B]),  and row i of L is flagged iff d_i > cut.
+ *   The comparison is strict, so at most B rows are flagged and ties at the budget's boundary flag nothing.  Sorting
+ *   moves values and rounds nothing: every output is a function of the series' multiset of residuals alone.
+ *   flag_i = (excluded_i != 0) | new_i;  resid_i = r_i (every row);  n_new = the new flags, n_flagged = all flags.
+ *   status[n]: TSF_SCREEN_OK, or -- each of these leaves flag = excluded, n_new = 0, center = scale = NaN (resid is
+ *   still written), the first that applies -- TSF_SCREEN_TOO_LONG (m0 > TSF_SCREEN_MAX_ROWS), TSF_SCREEN_TOO_FEW
+ *   (m < min_rows), TSF_SCREEN_NONFINITE (a non-finite r_i on a row of L: a NaN in fitted flags nothing).
+ *   No atomics; a series' results depend neither on the rest of the batch nor on how the call is cut into launches.
+ * Refusals (< 0 with a message, before any launch; the context stays usable): a NULL out, out->flag, out->status, y or
+ *   fitted; threshold not finite or not > 0; max_share outside [0, 0.5]; min_rows < 2; max_passes outside [1, 8] (read by
+ *   tsf_fit_screened only, checked by both); a bad y_dtype; a bad panel.  N == 0 is a legal no-op.
+ *
+ * tsf_fit_screened.  Input as tsf_cross_validate (host pointers; T > 0 aligned, T = 0 with offsets [N+1] ragged); the
+ * panel crosses to the device once.
+ *   Round 0: every series fitted on its full history as tsf_tune's refit fits base: with algorithm TSF_ALGO_LBFGS /
+ *   TSF_ALGO_NEWTON tsf_fit_aligned / tsf_fit_ragged bit for bit, with TSF_ALGO_AUTO fbprophet's rule PER SERIES with
+ *   the Newton retry (see tsf_tune).  out->first, where given, receives it (grid [1] aligned / [N] ragged).
+ *   Round p = 1 .. max_passes: fitted = tsf_predict of each series' current fit on its own history dates, every row,
+ *   the excluded ones too (aligned: shared_future = 1 over ds [T]; ragged: shared_future = 0 over [N][Tmax], Tmax = the
+ *   longest series, rows past a series' last repeating its last date); tsf_screen_rows with excluded = the flags so far
+ *   and min_scale[n] = scale_floor_rel * y_scale[n] of the current fit (fitted is NaN for a series whose current fit
+ *   failed: it is reported TSF_SCREEN_NONFINITE or TSF_SCREEN_TOO_FEW); the series with n_new > 0 are cut
+ *   (screen_compact_kernel: the rows without a flag, in order) into ragged panels and fitted again, the optimiser by the
+ *   same rule on the KEPT row count.  A series with n_new == 0 is finished and is not screened again; the loop ends when
+ *   no series has new flags or after max_passes rounds, the last round's flagged series fitted again too: no final fit
+ *   has seen a flagged row.
+ *   out->fit [N], grid [N] always: a never-flagged series has its first fit bit for bit (aligned: a copy of the one
+ *   grid); a flagged series has what tsf_fit_ragged returns on the explicitly cut panel, bit for bit, a failed refit's
+ *   status included.  out->screen: flag and n_flagged cumulative; resid, center, scale, status, n_new those of the last
+ *   round in which the series was screened.  rounds[n] = the rounds that gave series n new flags.
+ *   Pending cost hints are discarded.  scale_floor_rel finite and >= 0. */
+#define TSF_SCREEN_MAX_ROWS 16384
+enum { TSF_SCREEN_OK = 0, TSF_SCREEN_TOO_FEW = -30, TSF_SCREEN_TOO_LONG = -31, TSF_SCREEN_NONFINITE = -32 };
+typedef struct {
+    double threshold, max_share;
+    int32_t min_rows, max_passes;
+} tsf_screen_args;
+typedef struct {
+    uint8_t *flag;          /* [rows]  required: 1 = excluded on input or flagged now */
+    double *resid;          /* [rows]  NULL: not wanted (all below but status likewise) */
+    double *center, *scale; /* [N] */
+    int32_t *n_new, *n_flagged;     /* [N] */
+    int32_t *status;        /* [N]     required */
+} tsf_screen_out;
+typedef struct {
+    tsf_fit_out fit;        /* [N], grid [N] always */
+    tsf_fit_out *first;     /* NULL: not wanted; the first fit, grid [1] aligned / [N] ragged */
+    tsf_screen_out screen;
+    int32_t *rounds;        /* [N] or NULL */
+} tsf_fit_screened_out;
+int tsf_screen_args_size(void);     /* sizeof(tsf_screen_args), sizeof(tsf_screen_out): the self-checks of a binding */
+int tsf_screen_out_size(void);
+int tsf_fit_screened_out_size(void);
+int tsf_screen_rows(tsf_ctx *ctx, int64_t N, int32_t T, const int64_t *offsets /* NULL = aligned [N][T] */, const void *y,
+                    int32_t y_dtype, const double *fitted, const uint8_t *excluded, const double *min_scale,
+                    const tsf_screen_args *args, tsf_screen_out *out);
+int tsf_screen_rows_dev(tsf_ctx *ctx, int64_t N, int32_t T, const int64_t *offsets, const void *y, int32_t y_dtype,
+                        const double *fitted, const uint8_t *excluded, const double *min_scale,
+                        const tsf_screen_args *args, tsf_screen_out *out, void *stream);
+int tsf_fit_screened(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t T, const int64_t *offsets, const int64_t *ds,
+                     const void *y, int32_t y_dtype, const double *floor, const double *cap, const double *extra,
+                     double scale_floor_rel, const tsf_screen_args *args, tsf_fit_screened_out *out);
+
 /* ---- scheduling hints ---------------------------------------------------------------------
  * A launch ends with its longest fits (cfg2: 1 582 evaluations against a mean of 454), and nothing
  * cheap about a series predicts how long its fit takes -- except an earlier fit of the same

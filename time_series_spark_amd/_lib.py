@@ -122,6 +122,25 @@ class TsfTuneOut(ctypes.Structure):
                 ('series_status', ctypes.c_void_p), ('fit', TsfFitOut)]
 
 
+class TsfScreenArgs(ctypes.Structure):
+    """tsf_screen_args (include/tsf.h)."""
+    _fields_ = [('threshold', ctypes.c_double), ('max_share', ctypes.c_double), ('min_rows', ctypes.c_int32),
+                ('max_passes', ctypes.c_int32)]
+
+
+class TsfScreenOut(ctypes.Structure):
+    """tsf_screen_out (include/tsf.h)."""
+    _fields_ = [('flag', ctypes.c_void_p), ('resid', ctypes.c_void_p), ('center', ctypes.c_void_p),
+                ('scale', ctypes.c_void_p), ('n_new', ctypes.c_void_p), ('n_flagged', ctypes.c_void_p),
+                ('status', ctypes.c_void_p)]
+
+
+class TsfFitScreenedOut(ctypes.Structure):
+    """tsf_fit_screened_out (include/tsf.h)."""
+    _fields_ = [('fit', TsfFitOut), ('first', ctypes.POINTER(TsfFitOut)), ('screen', TsfScreenOut),
+                ('rounds', ctypes.c_void_p)]
+
+
 # every symbol include/tsf.h declares; tests check the library exports all of them
 EXPORTS = ['tsf_create', 'tsf_destroy', 'tsf_last_error', 'tsf_device_count', 'tsf_spec_default',
            'tsf_spec_size', 'tsf_grid_info_size', 'tsf_spec_K', 'tsf_theta_stride',
@@ -132,6 +151,8 @@ EXPORTS = ['tsf_create', 'tsf_destroy', 'tsf_last_error', 'tsf_device_count', 't
            'tsf_rollup_create', 'tsf_rollup_add', 'tsf_rollup_quantiles', 'tsf_rollup_free', 'tsf_eval', 'tsf_eval_quadratic', 'tsf_design', 'tsf_selftest_math',
            'tsf_set_option', 'tsf_get_option', 'tsf_set_cost_hints', 'tsf_set_profiling', 'tsf_profile_read', 'tsf_last_fit_kernel_ms', 'tsf_last_fit_route',
            'tsf_cv_plan', 'tsf_cross_validate', 'tsf_last_cv_grids', 'tsf_tune', 'tsf_last_tune_counts',
+           'tsf_screen_args_size', 'tsf_screen_out_size', 'tsf_fit_screened_out_size', 'tsf_screen_rows', 'tsf_screen_rows_dev',
+           'tsf_fit_screened',
            'tsf_pack_rows', 'tsf_pack_rows_typed', 'tsf_pack_fetch', 'tsf_pack_flags', 'tsf_pack_free', 'tsf_model_blobs',
            'tsf_csv_read', 'tsf_csv_fetch', 'tsf_csv_columns', 'tsf_csv_malformed', 'tsf_csv_free', 'tsf_csv_write_forecasts', 'tsf_csv_write_forecasts_i32',
            'tsf_csv_discover', 'tsf_csv_discover_load', 'tsf_csv_root_open', 'tsf_csv_root_load', 'tsf_csv_root_free', 'tsf_csv_read_loaded', 'tsf_csv_dir_paths', 'tsf_csv_dir_series_id', 'tsf_csv_dir_error_path', 'tsf_csv_dir_free']
@@ -144,6 +165,9 @@ TUNE_MSE, TUNE_RMSE, TUNE_MAE, TUNE_MAPE = 0, 1, 2, 3
 TUNE_METRICS = {'mse': TUNE_MSE, 'rmse': TUNE_RMSE, 'mae': TUNE_MAE, 'mape': TUNE_MAPE}
 TUNE_NO_SCORE = -24
 TUNE_MAX_CAND = 256
+# TSF_SCREEN_* (include/tsf.h): per-series outcome of the screening rule, its row limit
+SCREEN_OK, SCREEN_TOO_FEW, SCREEN_TOO_LONG, SCREEN_NONFINITE = 0, -30, -31, -32
+SCREEN_MAX_ROWS = 16384
 
 # TSF_OPT_* (include/tsf.h): route switches of one context
 OPTIONS = ['harm', 'lattice', 'sparse_extra', 'fit_grouped', 'gram_share', 'grid_order', 'grid_share', 'ragged_split',
@@ -225,6 +249,11 @@ def load():
     L.tsf_tune.argtypes = [vp, psp, psp, i32, i64, i32, vp, vp, vp, i32, vp, vp, vp, ctypes.POINTER(TsfCvArgs), i32, i32,
                            ctypes.POINTER(TsfTuneOut)]
     L.tsf_last_tune_counts.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.tsf_screen_rows.argtypes = [vp, i64, i32, vp, vp, i32, vp, vp, vp, ctypes.POINTER(TsfScreenArgs),
+                                  ctypes.POINTER(TsfScreenOut)]
+    L.tsf_screen_rows_dev.argtypes = L.tsf_screen_rows.argtypes + [vp]
+    L.tsf_fit_screened.argtypes = [vp, psp, i64, i32, vp, vp, vp, i32, vp, vp, vp, ctypes.c_double,
+                                   ctypes.POINTER(TsfScreenArgs), ctypes.POINTER(TsfFitScreenedOut)]
     L.tsf_pack_rows.argtypes = [i64, vp, vp, vp, vp, i32, ctypes.POINTER(vp), ctypes.POINTER(i64),
                                 ctypes.POINTER(i64), ctypes.POINTER(i32)]
     L.tsf_pack_fetch.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -268,6 +297,9 @@ def load():
         raise TsfError('tsf_grid_info layout mismatch between _lib.py and libtsf_amd.so')
     if L.tsf_score_out_size() != ctypes.sizeof(TsfScoreOut):
         raise TsfError('tsf_score_out layout mismatch between _lib.py and libtsf_amd.so')
+    if (L.tsf_screen_args_size() != ctypes.sizeof(TsfScreenArgs) or L.tsf_screen_out_size() != ctypes.sizeof(TsfScreenOut)
+            or L.tsf_fit_screened_out_size() != ctypes.sizeof(TsfFitScreenedOut)):
+        raise TsfError('tsf_screen_args / tsf_screen_out layout mismatch between _lib.py and libtsf_amd.so')
     _lib = L
     return L
 

@@ -31,6 +31,7 @@
 #include "tsf_launch.h"
 #include "tsf_cv_kernels.h"
 #include "tsf_tune_kernels.h"
+#include "tsf_screen_kernels.h"
 #include "tsf_cv_plan.h"
 
 using namespace tsf;
@@ -3118,6 +3119,51 @@ extern "C" int tsf_cross_validate(tsf_ctx *ctx, const tsf_spec *spec, int64_t N,
     return 0;
 }
 
+// One fit launch over the whole histories of the series sel of an uploaded panel with spec gs, its outputs put at the
+// series' positions of dst (tsf_tune's refit, tsf_fit_screened's first fit): aligned, the series' rows gathered into a
+// [G][T] panel (tune_gather_kernel; dst.grid[0] receives the one grid); ragged, their full histories as views
+// (cv_expand_kernel; dst.grid[n] per series).  whole: the identity views of the panel.
+static int fit_whole_group(tsf_ctx *ctx, CvCall &S, const CvViews &whole, const tsf_spec &gs, const std::vector<int32_t> &sel,
+                           const tsf_fit_out &dst, int64_t *n_grids, int32_t *n_launches)
+{
+    const int64_t G = (int64_t)sel.size();
+    if (G == 0) return 0;
+    if (!S.aligned) {
+        CvGroup E;
+        if (int rc = cv_expand(ctx, S, whole, sel, &E)) return rc;
+        return cv_fit(ctx, S, E, gs, dst, n_grids, n_launches);
+    }
+    const int32_t T = S.T;
+    const int stride = S.stride;
+    DevBuf d_sel, d_gy, d_gfl, d_gcap, g_th, g_ys, g_fv, g_st, g_it, g_ev, g_gr;
+    HIP_TRY(ctx, d_sel.alloc(4 * (size_t)G)); HIP_TRY(ctx, hipMemcpy(d_sel.p, sel.data(), 4 * (size_t)G, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_gy.alloc(S.ysz * (size_t)G * T));
+    if (S.has_floor) HIP_TRY(ctx, d_gfl.alloc(8 * (size_t)G));
+    if (S.has_cap) HIP_TRY(ctx, d_gcap.alloc(8 * (size_t)G));
+    hipLaunchKernelGGL(tune_gather_kernel, dim3((unsigned)(G < 65535 ? G : 65535)), dim3(256), 0, nullptr, S.pn, G,
+                       d_sel.as<int32_t>(), S.has_floor ? S.d_fl.as<double>() : nullptr, S.has_cap ? S.d_cap.as<double>() : nullptr,
+                       d_gy.p, S.has_floor ? d_gfl.as<double>() : nullptr, S.has_cap ? d_gcap.as<double>() : nullptr);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, g_th.alloc(8 * (size_t)G * stride)); HIP_TRY(ctx, g_ys.alloc(8 * (size_t)G)); HIP_TRY(ctx, g_fv.alloc(8 * (size_t)G));
+    HIP_TRY(ctx, g_st.alloc(4 * (size_t)G)); HIP_TRY(ctx, g_it.alloc(4 * (size_t)G)); HIP_TRY(ctx, g_ev.alloc(4 * (size_t)G));
+    HIP_TRY(ctx, g_gr.alloc(sizeof(tsf_grid_info)));
+    HIP_TRY(ctx, hipMemset(g_st.p, 0, 4 * (size_t)G)); HIP_TRY(ctx, hipMemset(g_it.p, 0, 4 * (size_t)G));
+    HIP_TRY(ctx, hipMemset(g_ev.p, 0, 4 * (size_t)G)); HIP_TRY(ctx, hipMemset(g_gr.p, 0, sizeof(tsf_grid_info)));
+    tsf_fit_out go;
+    go.theta = g_th.as<double>(); go.y_scale = g_ys.as<double>(); go.fval = g_fv.as<double>();
+    go.status = g_st.as<int32_t>(); go.n_iter = g_it.as<int32_t>(); go.n_eval = g_ev.as<int32_t>();
+    go.grid = g_gr.as<tsf_grid_info>();
+    int rc = run_fit(ctx, &gs, G, 1, T, nullptr, 0, T, S.d_ds.as<int64_t>(), d_gy.p, S.y_dtype,
+                     S.has_floor ? d_gfl.as<double>() : nullptr, S.has_cap ? d_gcap.as<double>() : nullptr,
+                     S.n_extra > 0 ? S.d_ex.as<double>() : nullptr, &go, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    *n_launches += 1;
+    hipLaunchKernelGGL(tune_scatter_kernel, dim3((unsigned)G), dim3(64), 0, nullptr, G, d_sel.as<int32_t>(), stride, go, dst);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    return 0;
+}
+
 // ---- prior-scale tuning (include/tsf.h) ---------------------------------------------------------------
 
 extern "C" int tsf_last_tune_counts(const tsf_ctx *ctx, int32_t *expand_launches, int32_t *fit_launches)
@@ -3287,43 +3333,8 @@ extern "C" int tsf_tune(tsf_ctx *ctx, const tsf_spec *base, const tsf_spec *cand
     DevBuf d_ident;
     if (!aligned) { HIP_TRY(ctx, d_ident.alloc(4 * (size_t)N)); HIP_TRY(ctx, hipMemcpy(d_ident.p, ident.data(), 4 * (size_t)N, hipMemcpyHostToDevice)); }
     const CvViews whole{d_ident.as<int32_t>(), ident.data(), len.data(), nullptr, 0, nullptr};
-    // one fit launch over the series sel with spec gs: aligned, the series' rows gathered into a [G][T] panel
-    // (tune_gather_kernel); ragged, their full histories as views (cv_expand_kernel)
     auto refit_group = [&](const tsf_spec &gs, const std::vector<int32_t> &sel) -> int {
-        const int64_t G = (int64_t)sel.size();
-        if (G == 0) return 0;
-        if (!aligned) {
-            CvGroup E;
-            if (int rc = cv_expand(ctx, S, whole, sel, &E)) return rc;
-            return cv_fit(ctx, S, E, gs, rfo, &grids, &ctx->tune_fits);
-        }
-        DevBuf d_sel, d_gy, d_gfl, d_gcap, g_th, g_ys, g_fv, g_st, g_it, g_ev, g_gr;
-        HIP_TRY(ctx, d_sel.alloc(4 * (size_t)G)); HIP_TRY(ctx, hipMemcpy(d_sel.p, sel.data(), 4 * (size_t)G, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, d_gy.alloc(S.ysz * (size_t)G * T));
-        if (floor_) HIP_TRY(ctx, d_gfl.alloc(8 * (size_t)G));
-        if (cap) HIP_TRY(ctx, d_gcap.alloc(8 * (size_t)G));
-        hipLaunchKernelGGL(tune_gather_kernel, dim3((unsigned)(G < 65535 ? G : 65535)), dim3(256), 0, nullptr, S.pn, G,
-                           d_sel.as<int32_t>(), floor_ ? S.d_fl.as<double>() : nullptr, cap ? S.d_cap.as<double>() : nullptr,
-                           d_gy.p, floor_ ? d_gfl.as<double>() : nullptr, cap ? d_gcap.as<double>() : nullptr);
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, g_th.alloc(8 * (size_t)G * stride)); HIP_TRY(ctx, g_ys.alloc(8 * (size_t)G)); HIP_TRY(ctx, g_fv.alloc(8 * (size_t)G));
-        HIP_TRY(ctx, g_st.alloc(4 * (size_t)G)); HIP_TRY(ctx, g_it.alloc(4 * (size_t)G)); HIP_TRY(ctx, g_ev.alloc(4 * (size_t)G));
-        HIP_TRY(ctx, g_gr.alloc(sizeof(tsf_grid_info)));
-        HIP_TRY(ctx, hipMemset(g_st.p, 0, 4 * (size_t)G)); HIP_TRY(ctx, hipMemset(g_it.p, 0, 4 * (size_t)G));
-        HIP_TRY(ctx, hipMemset(g_ev.p, 0, 4 * (size_t)G)); HIP_TRY(ctx, hipMemset(g_gr.p, 0, sizeof(tsf_grid_info)));
-        tsf_fit_out go;
-        go.theta = g_th.as<double>(); go.y_scale = g_ys.as<double>(); go.fval = g_fv.as<double>();
-        go.status = g_st.as<int32_t>(); go.n_iter = g_it.as<int32_t>(); go.n_eval = g_ev.as<int32_t>();
-        go.grid = g_gr.as<tsf_grid_info>();
-        int rc = run_fit(ctx, &gs, G, 1, T, nullptr, 0, T, S.d_ds.as<int64_t>(), d_gy.p, y_dtype,
-                         floor_ ? d_gfl.as<double>() : nullptr, cap ? d_gcap.as<double>() : nullptr,
-                         base->n_extra > 0 ? S.d_ex.as<double>() : nullptr, &go, nullptr, nullptr, nullptr);
-        if (rc) return rc;
-        ctx->tune_fits += 1;
-        hipLaunchKernelGGL(tune_scatter_kernel, dim3((unsigned)G), dim3(64), 0, nullptr, G, d_sel.as<int32_t>(), stride, go, rfo);
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipDeviceSynchronize());
-        return 0;
+        return fit_whole_group(ctx, S, whole, gs, sel, rfo, &grids, &ctx->tune_fits);
     };
     std::vector<int32_t> rstat((size_t)N);
     for (int32_t b = -1; b < C; ++b) {
@@ -3357,5 +3368,372 @@ extern "C" int tsf_tune(tsf_ctx *ctx, const tsf_spec *base, const tsf_spec *cand
     HIP_TRY(ctx, hipMemcpy(fo.n_iter, r_it.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
     HIP_TRY(ctx, hipMemcpy(fo.n_eval, r_ev.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
     HIP_TRY(ctx, hipMemcpy(fo.grid, r_gr.p, sizeof(tsf_grid_info) * (size_t)n_grids, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- outlier screening (include/tsf.h) ----------------------------------------------------------------------
+// tsf_screen_rows: the rule, one workgroup per series, one launch per power-of-two class of row counts (the LDS of a
+// launch is its class's NSP doubles: a panel of 730-row series does not pay for a 16384-row one).  tsf_fit_screened runs
+// tsf_tune's pieces -- the panel once on the device, whole-history fit groups per optimiser -- then per round one
+// predict over the history, one screening pass, the flag counts back to the host (the destination offsets of the cut,
+// as the cross-validation plan stays on the host), one cut and one fit launch per optimiser group.
+
+extern "C" int tsf_screen_args_size(void) { return (int)sizeof(tsf_screen_args); }
+extern "C" int tsf_screen_out_size(void) { return (int)sizeof(tsf_screen_out); }
+extern "C" int tsf_fit_screened_out_size(void) { return (int)sizeof(tsf_fit_screened_out); }
+
+static int check_screen_args(tsf_ctx *ctx, const tsf_screen_args *a, const tsf_screen_out *out)
+{
+    if (!out || !out->flag || !out->status) return fail(ctx, "NULL output (tsf_screen_out, its flag and its status are required)");
+    if (!a) return fail(ctx, "NULL tsf_screen_args");
+    if (!(a->threshold > 0.0) || !std::isfinite(a->threshold)) return fail(ctx, "threshold must be finite and > 0");
+    if (!(a->max_share >= 0.0 && a->max_share <= 0.5)) return fail(ctx, "max_share must be in [0, 0.5]");
+    if (a->min_rows < 2) return fail(ctx, "min_rows must be >= 2");
+    if (a->max_passes < 1 || a->max_passes > 8) return fail(ctx, "max_passes must be in [1, 8]");
+    return 0;
+}
+
+// what a screening call needs of its panel's shape: aligned 1 <= T, ragged offsets from 0, ascending; N within int32
+static int check_screen_panel(tsf_ctx *ctx, int64_t N, int32_t T, const int64_t *h_off)
+{
+    if (N > (int64_t)INT32_MAX) return fail(ctx, "N too large");
+    if (!h_off) return T >= 1 ? 0 : fail(ctx, "bad panel (aligned: T >= 1)");
+    if (h_off[0] != 0) return fail(ctx, "bad panel (ragged: offsets[0] = 0)");
+    for (int64_t n = 0; n < N; ++n)
+        if (h_off[n + 1] < h_off[n]) return fail(ctx, "bad panel (ragged: offsets ascending)");
+    return 0;
+}
+
+// The rule on device-resident inputs.  h_off: the ragged panel's offsets on the host (the launch classes), null aligned;
+// fit_ld: ScreenArgs::fit_ld; active: the series to screen (host, ascending) or null = all N; o: device pointers.
+static int screen_run(tsf_ctx *ctx, int64_t N, int32_t T, const int64_t *d_off, const int64_t *h_off, const void *d_y,
+                      int32_t y_dtype, const double *d_fit, int64_t fit_ld, const uint8_t *d_excl, const double *d_ms,
+                      const tsf_screen_args &a, const tsf_screen_out &o, const int32_t *active, int64_t n_active,
+                      hipStream_t st)
+{
+    ScreenArgs k;
+    memset(&k, 0, sizeof(k));
+    k.y = d_y; k.fitted = d_fit; k.excluded = d_excl; k.min_scale = d_ms; k.offsets = h_off ? d_off : nullptr;
+    k.T = T; k.fit_ld = fit_ld; k.y_dtype = y_dtype; k.min_rows = a.min_rows; k.threshold = a.threshold; k.max_share = a.max_share;
+    k.flag = o.flag; k.resid = o.resid; k.center = o.center; k.scale = o.scale; k.n_new = o.n_new; k.n_flagged = o.n_flagged;
+    k.status = o.status;
+    // class c: NSP = 2^c rows of LDS; a series beyond TSF_SCREEN_MAX_ROWS only reports its status (class 1)
+    auto class_of = [](int64_t len) {
+        if (len > (int64_t)TSF_SCREEN_MAX_ROWS) return 1;
+        int c = 1;
+        while (((int64_t)1 << c) < len) ++c;
+        return c;
+    };
+    auto launch = [&](const int32_t *d_sel, int64_t blocks, int c) -> int {
+        const int NSP = 1 << c;
+        k.sel = d_sel;
+        const size_t lds = sizeof(double) * (size_t)NSP + SCREEN_PART_BYTES;
+        // beyond the 64 KiB a kernel gets unasked (series of more than 8184 rows); per launch: the attribute is per
+        // device, and a process may drive several GPUs
+        if (lds > 64 * 1024)
+            HIP_TRY(ctx, hipFuncSetAttribute((const void *)screen_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        hipLaunchKernelGGL(screen_rows_kernel, dim3((unsigned)blocks), dim3(256), lds, st, k, NSP);
+        HIP_TRY(ctx, hipGetLastError());
+        return 0;
+    };
+    if (!active) n_active = N;
+    if (n_active == 0) return 0;
+    if (!h_off && !active) return launch(nullptr, N, class_of(T));
+    constexpr int NC = 16;
+    int64_t count[NC] = {0}, start[NC + 1] = {0};
+    std::vector<int8_t> cls((size_t)n_active);
+    for (int64_t i = 0; i < n_active; ++i) {
+        const int64_t n = active ? active[i] : i;
+        cls[(size_t)i] = (int8_t)class_of(h_off ? h_off[n + 1] - h_off[n] : (int64_t)T);
+        count[cls[(size_t)i]]++;
+    }
+    for (int c = 0; c < NC; ++c) start[c + 1] = start[c] + count[c];
+    if (!active)
+        for (int c = 0; c < NC; ++c)
+            if (count[c] == N) return launch(nullptr, N, c);        // one class: no list
+    std::vector<int32_t> sel((size_t)n_active);
+    {
+        int64_t at[NC];
+        for (int c = 0; c < NC; ++c) at[c] = start[c];
+        for (int64_t i = 0; i < n_active; ++i) sel[(size_t)at[cls[(size_t)i]]++] = (int32_t)(active ? active[i] : i);
+    }
+    DevBuf d_sel;
+    HIP_TRY(ctx, d_sel.alloc(4 * (size_t)n_active));
+    HIP_TRY(ctx, hipMemcpy(d_sel.p, sel.data(), 4 * (size_t)n_active, hipMemcpyHostToDevice));
+    for (int c = 0; c < NC; ++c)
+        if (count[c] > 0)
+            if (int rc = launch(d_sel.as<int32_t>() + start[c], count[c], c)) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(st));         // (the list goes back to the pool)
+    return 0;
+}
+
+extern "C" int tsf_screen_rows_dev(tsf_ctx *ctx, int64_t N, int32_t T, const int64_t *offsets, const void *y, int32_t y_dtype,
+                                   const double *fitted, const uint8_t *excluded, const double *min_scale,
+                                   const tsf_screen_args *args, tsf_screen_out *out, void *stream)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (N < 0) return fail(ctx, "N must be >= 0");
+    if (int rc = check_screen_args(ctx, args, out)) return rc;
+    if (!y || !fitted) return fail(ctx, "NULL input (y and fitted are required)");
+    if (y_dtype < TSF_Y_F64 || y_dtype > TSF_Y_I32) return fail(ctx, "bad y_dtype");
+    if (N == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<int64_t> h_off;
+    if (offsets) {
+        h_off.resize((size_t)N + 1);
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        HIP_TRY(ctx, hipMemcpy(h_off.data(), offsets, 8 * ((size_t)N + 1), hipMemcpyDeviceToHost));
+    }
+    if (int rc = check_screen_panel(ctx, N, T, offsets ? h_off.data() : nullptr)) return rc;
+    return screen_run(ctx, N, T, offsets, offsets ? h_off.data() : nullptr, y, y_dtype, fitted, 0, excluded, min_scale, *args,
+                      *out, nullptr, 0, st);
+}
+
+extern "C" int tsf_screen_rows(tsf_ctx *ctx, int64_t N, int32_t T, const int64_t *offsets, const void *y, int32_t y_dtype,
+                               const double *fitted, const uint8_t *excluded, const double *min_scale,
+                               const tsf_screen_args *args, tsf_screen_out *out)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (N < 0) return fail(ctx, "N must be >= 0");
+    if (int rc = check_screen_args(ctx, args, out)) return rc;
+    if (!y || !fitted) return fail(ctx, "NULL input (y and fitted are required)");
+    if (y_dtype < TSF_Y_F64 || y_dtype > TSF_Y_I32) return fail(ctx, "bad y_dtype");
+    if (N == 0) return 0;
+    if (int rc = check_screen_panel(ctx, N, T, offsets)) return rc;
+    const size_t rows = offsets ? (size_t)offsets[N] : (size_t)N * T, ysz = ysize(y_dtype);
+    DevBuf d_off, d_y, d_fit, d_ex, d_ms, d_flag, d_res, d_cen, d_sc, d_nn, d_nf, d_st;
+    if (offsets) {
+        HIP_TRY(ctx, d_off.alloc(8 * ((size_t)N + 1)));
+        HIP_TRY(ctx, hipMemcpy(d_off.p, offsets, 8 * ((size_t)N + 1), hipMemcpyHostToDevice));
+    }
+    HIP_TRY(ctx, d_y.alloc(ysz * rows)); HIP_TRY(ctx, hipMemcpy(d_y.p, y, ysz * rows, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_fit.alloc(8 * rows)); HIP_TRY(ctx, hipMemcpy(d_fit.p, fitted, 8 * rows, hipMemcpyHostToDevice));
+    if (excluded) { HIP_TRY(ctx, d_ex.alloc(rows)); HIP_TRY(ctx, hipMemcpy(d_ex.p, excluded, rows, hipMemcpyHostToDevice)); }
+    if (min_scale) { HIP_TRY(ctx, d_ms.alloc(8 * (size_t)N)); HIP_TRY(ctx, hipMemcpy(d_ms.p, min_scale, 8 * (size_t)N, hipMemcpyHostToDevice)); }
+    tsf_screen_out o;
+    memset(&o, 0, sizeof(o));
+    HIP_TRY(ctx, d_flag.alloc(rows)); o.flag = d_flag.as<uint8_t>();
+    HIP_TRY(ctx, d_st.alloc(4 * (size_t)N)); o.status = d_st.as<int32_t>();
+    if (out->resid) { HIP_TRY(ctx, d_res.alloc(8 * rows)); o.resid = d_res.as<double>(); }
+    if (out->center) { HIP_TRY(ctx, d_cen.alloc(8 * (size_t)N)); o.center = d_cen.as<double>(); }
+    if (out->scale) { HIP_TRY(ctx, d_sc.alloc(8 * (size_t)N)); o.scale = d_sc.as<double>(); }
+    if (out->n_new) { HIP_TRY(ctx, d_nn.alloc(4 * (size_t)N)); o.n_new = d_nn.as<int32_t>(); }
+    if (out->n_flagged) { HIP_TRY(ctx, d_nf.alloc(4 * (size_t)N)); o.n_flagged = d_nf.as<int32_t>(); }
+    if (int rc = screen_run(ctx, N, T, d_off.as<int64_t>(), offsets, d_y.p, y_dtype, d_fit.as<double>(), 0,
+                            excluded ? d_ex.as<uint8_t>() : nullptr, min_scale ? d_ms.as<double>() : nullptr, *args, o,
+                            nullptr, 0, nullptr))
+        return rc;
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    if (rows) HIP_TRY(ctx, hipMemcpy(out->flag, d_flag.p, rows, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(out->status, d_st.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+    if (out->resid && rows) HIP_TRY(ctx, hipMemcpy(out->resid, d_res.p, 8 * rows, hipMemcpyDeviceToHost));
+    if (out->center) HIP_TRY(ctx, hipMemcpy(out->center, d_cen.p, 8 * (size_t)N, hipMemcpyDeviceToHost));
+    if (out->scale) HIP_TRY(ctx, hipMemcpy(out->scale, d_sc.p, 8 * (size_t)N, hipMemcpyDeviceToHost));
+    if (out->n_new) HIP_TRY(ctx, hipMemcpy(out->n_new, d_nn.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+    if (out->n_flagged) HIP_TRY(ctx, hipMemcpy(out->n_flagged, d_nf.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+static bool fit_out_complete(const tsf_fit_out &f)
+{
+    return f.theta && f.y_scale && f.fval && f.status && f.n_iter && f.n_eval && f.grid;
+}
+
+extern "C" int tsf_fit_screened(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t T, const int64_t *offsets,
+                                const int64_t *ds, const void *y, int32_t y_dtype, const double *floor_, const double *cap,
+                                const double *extra, double scale_floor_rel, const tsf_screen_args *args,
+                                tsf_fit_screened_out *out)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!spec || !ds || !y || !out) return fail(ctx, "NULL input");
+    if (int rc = check_screen_args(ctx, args, &out->screen)) return rc;
+    if (y_dtype < TSF_Y_F64 || y_dtype > TSF_Y_I32) return fail(ctx, "bad y_dtype");
+    if (N > (int64_t)INT32_MAX || tsf_cv::check_panel(N, T, offsets, ds))
+        return fail(ctx, "bad panel (aligned: offsets NULL, 1 <= T <= TSF_MAX_T; ragged: T = 0, offsets[0] = 0, ascending)");
+    if (spec->n_extra > 0 && !extra) return fail(ctx, "extra columns declared but extra is NULL");
+    if (spec->growth == TSF_GROWTH_LOGISTIC && !cap) return fail(ctx, "logistic growth needs cap");
+    if (!(scale_floor_rel >= 0.0) || !std::isfinite(scale_floor_rel)) return fail(ctx, "scale_floor_rel must be finite and >= 0");
+    if (!fit_out_complete(out->fit)) return fail(ctx, "tsf_fit_screened_out.fit has NULL members");
+    if (out->first && !fit_out_complete(*out->first)) return fail(ctx, "tsf_fit_screened_out.first has NULL members");
+    ctx->order_n = 0;                   // (pending cost hints were meant for a fit call)
+    const bool aligned = offsets == nullptr;
+    CvCall S;
+    S.aligned = aligned; S.N = N; S.T = T; S.offsets = offsets; S.ds = ds; S.y_dtype = y_dtype; S.ysz = ysize(y_dtype);
+    S.n_extra = spec->n_extra; S.stride = tsf_theta_stride(spec);
+    S.has_floor = floor_ != nullptr; S.has_cap = cap != nullptr;
+    std::vector<int32_t> ident((size_t)N);
+    std::vector<int64_t> len((size_t)N);
+    int64_t Tmax = 0;
+    for (int64_t n = 0; n < N; ++n) {
+        ident[(size_t)n] = (int32_t)n;
+        len[(size_t)n] = aligned ? T : offsets[n + 1] - offsets[n];
+        if (len[(size_t)n] > Tmax) Tmax = len[(size_t)n];
+    }
+    if (Tmax < 1) return fail(ctx, "no rows");
+    if (int rc = cv_upload(ctx, y, floor_, cap, extra, nullptr, &S)) return rc;
+    const int stride = S.stride;
+    const size_t rows = aligned ? (size_t)N * T : (size_t)offsets[N];
+    int64_t grids = 0;                  // (not reported)
+    int32_t launches = 0;
+    // ---- round 0: the first fit, as tsf_tune's refit of base
+    DevBuf r_th, r_ys, r_fv, r_st, r_it, r_ev, r_gr;
+    HIP_TRY(ctx, r_th.alloc(8 * (size_t)N * stride)); HIP_TRY(ctx, r_ys.alloc(8 * (size_t)N)); HIP_TRY(ctx, r_fv.alloc(8 * (size_t)N));
+    HIP_TRY(ctx, r_st.alloc(4 * (size_t)N)); HIP_TRY(ctx, r_it.alloc(4 * (size_t)N)); HIP_TRY(ctx, r_ev.alloc(4 * (size_t)N));
+    HIP_TRY(ctx, r_gr.alloc(sizeof(tsf_grid_info) * (size_t)N));
+    HIP_TRY(ctx, hipMemset(r_th.p, 0, 8 * (size_t)N * stride)); HIP_TRY(ctx, hipMemset(r_ys.p, 0, 8 * (size_t)N));
+    HIP_TRY(ctx, hipMemset(r_fv.p, 0, 8 * (size_t)N)); HIP_TRY(ctx, hipMemset(r_it.p, 0, 4 * (size_t)N));
+    HIP_TRY(ctx, hipMemset(r_ev.p, 0, 4 * (size_t)N)); HIP_TRY(ctx, hipMemset(r_gr.p, 0, sizeof(tsf_grid_info) * (size_t)N));
+    std::vector<int32_t> rstat((size_t)N, TSF_ST_TOO_FEW);    // (a ragged series without rows is not fitted)
+    HIP_TRY(ctx, hipMemcpy(r_st.p, rstat.data(), 4 * (size_t)N, hipMemcpyHostToDevice));
+    tsf_fit_out rfo;
+    rfo.theta = r_th.as<double>(); rfo.y_scale = r_ys.as<double>(); rfo.fval = r_fv.as<double>();
+    rfo.status = r_st.as<int32_t>(); rfo.n_iter = r_it.as<int32_t>(); rfo.n_eval = r_ev.as<int32_t>();
+    rfo.grid = r_gr.as<tsf_grid_info>();
+    DevBuf d_ident;
+    if (!aligned) { HIP_TRY(ctx, d_ident.alloc(4 * (size_t)N)); HIP_TRY(ctx, hipMemcpy(d_ident.p, ident.data(), 4 * (size_t)N, hipMemcpyHostToDevice)); }
+    const CvViews whole{d_ident.as<int32_t>(), ident.data(), len.data(), nullptr, 0, nullptr};
+    // fbprophet's optimiser rule per series of `members` on its row count n_rows[series] (tsf_tune's refit): one launch
+    // per optimiser, Newton once more where L-BFGS ended the way pystan raises on
+    const bool auto_g = spec->algorithm == TSF_ALGO_AUTO;
+    const bool newton_ok = 3 + spec->n_changepoints + tsf_spec_K(spec) <= TSF_MAX_P;
+    tsf_spec sp_l = *spec, sp_n = *spec;
+    sp_l.algorithm = TSF_ALGO_LBFGS;
+    sp_n.algorithm = TSF_ALGO_NEWTON;
+    auto by_rule = [&](const std::vector<int32_t> &members, const std::vector<int64_t> &n_rows, auto fit_group) -> int {
+        if (!auto_g) return fit_group(*spec, members);
+        std::vector<int32_t> g_lb, g_nw;
+        for (int32_t n : members) (newton_ok && n_rows[(size_t)n] < TSF_NEWTON_BELOW_T ? g_nw : g_lb).push_back(n);
+        if (int rc = fit_group(sp_l, g_lb)) return rc;
+        if (newton_ok && !g_lb.empty()) {
+            HIP_TRY(ctx, hipMemcpy(rstat.data(), r_st.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+            if (int rc = fit_group(sp_n, newton_retry(g_lb, rstat))) return rc;
+        }
+        return fit_group(sp_n, g_nw);
+    };
+    {
+        std::vector<int32_t> members;
+        for (int64_t n = 0; n < N; ++n) if (len[(size_t)n] > 0) members.push_back((int32_t)n);
+        if (int rc = by_rule(members, len, [&](const tsf_spec &gs, const std::vector<int32_t> &sel) -> int {
+                return fit_whole_group(ctx, S, whole, gs, sel, rfo, &grids, &launches);
+            }))
+            return rc;
+    }
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    if (out->first) {
+        const tsf_fit_out &f1 = *out->first;
+        HIP_TRY(ctx, hipMemcpy(f1.theta, r_th.p, 8 * (size_t)N * stride, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(f1.y_scale, r_ys.p, 8 * (size_t)N, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(f1.fval, r_fv.p, 8 * (size_t)N, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(f1.status, r_st.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(f1.n_iter, r_it.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(f1.n_eval, r_ev.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(f1.grid, r_gr.p, sizeof(tsf_grid_info) * (size_t)(aligned ? 1 : N), hipMemcpyDeviceToHost));
+    }
+    if (aligned && N > 1) {             // from here on a grid per series
+        const int64_t words = (N - 1) * (int64_t)(sizeof(tsf_grid_info) / 8);
+        hipLaunchKernelGGL(screen_grid_fill_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, nullptr, N, rfo.grid);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    // ---- the rounds
+    const int32_t H = aligned ? T : (int32_t)Tmax;
+    DevBuf d_hds, d_hex, d_fit, d_ms, d_flag, d_res, d_cen, d_sc, d_nn, d_nf, d_sst;
+    if (!aligned) {
+        HIP_TRY(ctx, d_hds.alloc(8 * (size_t)N * H));
+        if (S.n_extra > 0) HIP_TRY(ctx, d_hex.alloc(8 * (size_t)N * S.n_extra * H));
+        hipLaunchKernelGGL(screen_history_kernel, dim3((unsigned)(N < 65535 ? N : 65535)), dim3(256), 0, nullptr, S.pn, N, H,
+                           d_hds.as<int64_t>(), S.n_extra > 0 ? d_hex.as<double>() : nullptr);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, d_fit.alloc(8 * (size_t)N * H)); HIP_TRY(ctx, d_ms.alloc(8 * (size_t)N));
+    HIP_TRY(ctx, d_flag.alloc(rows)); HIP_TRY(ctx, hipMemset(d_flag.p, 0, rows ? rows : 1));
+    HIP_TRY(ctx, d_nn.alloc(4 * (size_t)N)); HIP_TRY(ctx, d_nf.alloc(4 * (size_t)N)); HIP_TRY(ctx, d_sst.alloc(4 * (size_t)N));
+    tsf_screen_out so;
+    memset(&so, 0, sizeof(so));
+    so.flag = d_flag.as<uint8_t>(); so.n_new = d_nn.as<int32_t>(); so.n_flagged = d_nf.as<int32_t>(); so.status = d_sst.as<int32_t>();
+    if (out->screen.resid) { HIP_TRY(ctx, d_res.alloc(8 * rows)); so.resid = d_res.as<double>(); }
+    if (out->screen.center) { HIP_TRY(ctx, d_cen.alloc(8 * (size_t)N)); so.center = d_cen.as<double>(); }
+    if (out->screen.scale) { HIP_TRY(ctx, d_sc.alloc(8 * (size_t)N)); so.scale = d_sc.as<double>(); }
+    std::vector<int32_t> h_new((size_t)N), h_flagged((size_t)N), rounds((size_t)N, 0), active;
+    std::vector<int64_t> kept((size_t)N);
+    // the rows without a flag of the series sel as one ragged panel, fitted with gs, the results at the series' positions
+    auto refit_cut = [&](const tsf_spec &gs, const std::vector<int32_t> &sel) -> int {
+        CvGroup E;
+        const int64_t G = E.G = (int64_t)sel.size();
+        if (G == 0) return 0;
+        E.gf = sel;
+        std::vector<int64_t> goff((size_t)G + 1, 0);
+        for (int64_t g = 0; g < G; ++g) {
+            const int64_t h = kept[(size_t)sel[(size_t)g]];
+            goff[(size_t)g + 1] = goff[(size_t)g] + h;
+            if (h > E.maxT) E.maxT = (int32_t)h;
+        }
+        const int64_t total = E.rows = goff[(size_t)G];
+        HIP_TRY(ctx, E.d_gf.alloc(4 * (size_t)G)); HIP_TRY(ctx, hipMemcpy(E.d_gf.p, sel.data(), 4 * (size_t)G, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, E.d_goff.alloc(8 * ((size_t)G + 1))); HIP_TRY(ctx, hipMemcpy(E.d_goff.p, goff.data(), 8 * ((size_t)G + 1), hipMemcpyHostToDevice));
+        HIP_TRY(ctx, E.d_gds.alloc(8 * (size_t)total)); HIP_TRY(ctx, E.d_gy.alloc(S.ysz * (size_t)total));
+        if (S.n_extra > 0) HIP_TRY(ctx, E.d_gex.alloc(8 * (size_t)S.n_extra * total));
+        if (S.has_floor) HIP_TRY(ctx, E.d_gfl.alloc(8 * (size_t)G));
+        if (S.has_cap) HIP_TRY(ctx, E.d_gcap.alloc(8 * (size_t)G));
+        hipLaunchKernelGGL(screen_compact_kernel, dim3((unsigned)(G < 65535 ? G : 65535)), dim3(256), 0, nullptr, S.pn, G,
+                           E.d_gf.as<int32_t>(), d_flag.as<uint8_t>(), E.d_goff.as<int64_t>(), total,
+                           S.has_floor ? S.d_fl.as<double>() : nullptr, S.has_cap ? S.d_cap.as<double>() : nullptr,
+                           E.d_gds.as<int64_t>(), E.d_gy.p, S.n_extra > 0 ? E.d_gex.as<double>() : nullptr,
+                           S.has_floor ? E.d_gfl.as<double>() : nullptr, S.has_cap ? E.d_gcap.as<double>() : nullptr);
+        HIP_TRY(ctx, hipGetLastError());
+        return cv_fit(ctx, S, E, gs, rfo, &grids, &launches);
+    };
+    for (int32_t p = 1; p <= args->max_passes; ++p) {
+        if (int rc = tsf_predict_dev(ctx, spec, N, H, rfo.theta, rfo.y_scale, rfo.grid, (int32_t)N,
+                                     aligned ? S.d_ds.as<int64_t>() : d_hds.as<int64_t>(), aligned ? 1 : 0,
+                                     floor_ ? S.d_fl.as<double>() : nullptr, cap ? S.d_cap.as<double>() : nullptr,
+                                     S.n_extra > 0 ? (aligned ? S.d_ex.as<double>() : d_hex.as<double>()) : nullptr,
+                                     d_fit.as<double>(), nullptr, nullptr))
+            return rc;
+        hipLaunchKernelGGL(screen_mask_failed_kernel, dim3((unsigned)(N < 65535 ? N : 65535)), dim3(256), 0, nullptr, N,
+                           (int64_t)H, rfo.status, d_fit.as<double>());
+        HIP_TRY(ctx, hipGetLastError());
+        hipLaunchKernelGGL(screen_scale_floor_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, nullptr, N,
+                           scale_floor_rel, rfo.y_scale, d_ms.as<double>());
+        HIP_TRY(ctx, hipGetLastError());
+        // (excluded and flag are one array: a thread reads a row's byte before it writes it, and no other thread does)
+        if (int rc = screen_run(ctx, N, T, S.d_off.as<int64_t>(), offsets, S.d_y.p, y_dtype, d_fit.as<double>(), H,
+                                d_flag.as<uint8_t>(), d_ms.as<double>(), *args, so, p == 1 ? nullptr : active.data(),
+                                (int64_t)active.size(), nullptr))
+            return rc;
+        HIP_TRY(ctx, hipMemcpy(h_new.data(), d_nn.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(h_flagged.data(), d_nf.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+        std::vector<int32_t> cutl;
+        for (int64_t i = 0; i < (p == 1 ? N : (int64_t)active.size()); ++i) {
+            const int32_t n = p == 1 ? (int32_t)i : active[(size_t)i];
+            if (h_new[(size_t)n] <= 0) continue;
+            cutl.push_back(n);
+            rounds[(size_t)n] += 1;
+            kept[(size_t)n] = len[(size_t)n] - h_flagged[(size_t)n];
+        }
+        if (cutl.empty()) break;
+        if (int rc = by_rule(cutl, kept, refit_cut)) return rc;
+        active.swap(cutl);
+    }
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    const tsf_fit_out &fo = out->fit;
+    HIP_TRY(ctx, hipMemcpy(fo.theta, r_th.p, 8 * (size_t)N * stride, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(fo.y_scale, r_ys.p, 8 * (size_t)N, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(fo.fval, r_fv.p, 8 * (size_t)N, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(fo.status, r_st.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(fo.n_iter, r_it.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(fo.n_eval, r_ev.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(fo.grid, r_gr.p, sizeof(tsf_grid_info) * (size_t)N, hipMemcpyDeviceToHost));
+    const tsf_screen_out &ho = out->screen;
+    if (rows) HIP_TRY(ctx, hipMemcpy(ho.flag, d_flag.p, rows, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(ho.status, d_sst.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+    if (ho.resid && rows) HIP_TRY(ctx, hipMemcpy(ho.resid, d_res.p, 8 * rows, hipMemcpyDeviceToHost));
+    if (ho.center) HIP_TRY(ctx, hipMemcpy(ho.center, d_cen.p, 8 * (size_t)N, hipMemcpyDeviceToHost));
+    if (ho.scale) HIP_TRY(ctx, hipMemcpy(ho.scale, d_sc.p, 8 * (size_t)N, hipMemcpyDeviceToHost));
+    if (ho.n_new) HIP_TRY(ctx, hipMemcpy(ho.n_new, d_nn.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+    if (ho.n_flagged) HIP_TRY(ctx, hipMemcpy(ho.n_flagged, d_nf.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+    if (out->rounds) memcpy(out->rounds, rounds.data(), 4 * (size_t)N);
     return 0;
 }

@@ -1675,3 +1675,182 @@ def last_tune_counts(ctx=None):
     e, f = ctypes.c_int32(), ctypes.c_int32()
     ctx.check(_lib.load().tsf_last_tune_counts(ctx.handle, ctypes.byref(e), ctypes.byref(f)))
     return int(e.value), int(f.value)
+
+
+# ---- outlier screening: robust residual flags and refit (include/tsf.h) --------------------------------------
+
+class Screen(object):
+    """What the screening rule returns: flag (uint8, y's shape: 1 = excluded on input or flagged now), resid (y's shape),
+    center / scale / n_new / n_flagged / status [N] (status: _lib.SCREEN_*); fitted (y's shape) where fc.screen made it."""
+
+    def __init__(self, flag, resid, center, scale, n_new, n_flagged, status, fitted=None):
+        self.flag, self.resid, self.center, self.scale = flag, resid, center, scale
+        self.n_new, self.n_flagged, self.status, self.fitted = n_new, n_flagged, status, fitted
+
+
+class ScreenedFit(object):
+    """fit_screened's result: fit (FitResult, grid [N]: no fit has seen a flagged row), first (the first fit, as
+    fit_aligned / fit_ragged return it), screen (Screen, flags cumulative), rounds [N] (rounds that gave new flags)."""
+
+    def __init__(self, fit, first, screen, rounds):
+        self.fit, self.first, self.screen, self.rounds = fit, first, screen, rounds
+
+
+def _screen_args(threshold, max_share, min_rows, passes=1):
+    """tsf_screen_args, refused here as the library refuses them (before it is loaded)."""
+    if not (np.isfinite(threshold) and threshold > 0):
+        raise ValueError('threshold must be finite and > 0')
+    if not 0.0 <= max_share <= 0.5:
+        raise ValueError('max_share must be in [0, 0.5]')
+    if int(min_rows) != min_rows or min_rows < 2:
+        raise ValueError('min_rows must be an integer >= 2')
+    if int(passes) != passes or not 1 <= passes <= 8:
+        raise ValueError('passes must be an integer in [1, 8]')
+    a = _lib.TsfScreenArgs()
+    a.threshold, a.max_share, a.min_rows, a.max_passes = float(threshold), float(max_share), int(min_rows), int(passes)
+    return a
+
+
+def _screen_panel(y, offsets, other, what):
+    """y (and arrays of y's layout) of a screening call: aligned [N][T], or 1-D with offsets [N+1]."""
+    y = np.ascontiguousarray(y)
+    if offsets is None:
+        if y.ndim != 2:
+            raise ValueError('aligned panel: y must be [N][T]')
+        N, T = y.shape
+    else:
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if y.ndim != 1 or offsets.ndim != 1 or len(offsets) < 1 or offsets[-1] != y.shape[0]:
+            raise ValueError('ragged panel: y must be 1-D with offsets[-1] rows')
+        N, T = len(offsets) - 1, 0
+    for name, a in zip(what, other):
+        if a is not None and a.shape != y.shape:
+            raise ValueError('%s must have the shape of y' % name)
+    return y, offsets, N, T
+
+
+def _alloc_screen(y, N):
+    flag = np.zeros(y.shape, np.uint8)
+    resid = np.zeros(y.shape)
+    center, scale = np.zeros(N), np.zeros(N)
+    n_new, n_flagged, status = np.zeros(N, np.int32), np.zeros(N, np.int32), np.zeros(N, np.int32)
+    out = _lib.TsfScreenOut(flag.ctypes.data, resid.ctypes.data, center.ctypes.data, scale.ctypes.data,
+                            n_new.ctypes.data, n_flagged.ctypes.data, status.ctypes.data)
+    return out, (flag, resid, center, scale, n_new, n_flagged, status)
+
+
+def screen_rows(y, fitted, offsets=None, excluded=None, min_scale=None, threshold=5.0, max_share=0.05, min_rows=10,
+                ctx=None):
+    """The screening rule (include/tsf.h tsf_screen_rows) on any (y, fitted): per series the median and the MAD of the
+    residuals of the rows not excluded, a row flagged where |resid - center| exceeds both threshold * 1.4826 * MAD
+    (at least min_scale[n]) and the budget's order statistic, so that at most max_share of a series' rows is ever
+    flagged, `excluded` included.  y: [N][T], or 1-D with offsets [N+1] (float64 / float32 / int32); fitted, excluded:
+    y's shape.  Returns a Screen."""
+    fitted = np.ascontiguousarray(fitted, dtype=np.float64)
+    ex = None if excluded is None else np.ascontiguousarray(np.asarray(excluded) != 0, dtype=np.uint8)
+    y, offsets, N, T = _screen_panel(y, offsets, (fitted, ex), ('fitted', 'excluded'))
+    ms = None if min_scale is None else np.ascontiguousarray(np.broadcast_to(np.asarray(min_scale, np.float64), (N,)))
+    code = _lib.y_dtype_code(y)
+    a = _screen_args(threshold, max_share, min_rows)
+    ctx = ctx or get_context()
+    L = _lib.load()
+    out, arrs = _alloc_screen(y, N)
+    ctx.check(L.tsf_screen_rows(ctx.handle, N, T, _lib._ptr(offsets), y.ctypes.data, code, fitted.ctypes.data,
+                                _lib._ptr(ex), _lib._ptr(ms), ctypes.byref(a), ctypes.byref(out)))
+    return Screen(*arrs)
+
+
+def history_future(ds_ns, offsets):
+    """A ragged panel's own dates as the padded future panel [N][Tmax] predict reads (rows past a series' last repeat
+    its last date), and the row index [N][Tmax] into the panel that made it (for extra columns)."""
+    offsets = np.asarray(offsets, dtype=np.int64)
+    lens = np.diff(offsets)
+    Tmax = int(lens.max())
+    idx = offsets[:-1, None] + np.minimum(np.arange(Tmax)[None, :], np.maximum(lens - 1, 0)[:, None])
+    return np.asarray(ds_ns, dtype=np.int64)[idx], idx
+
+
+def fitted_history(spec, fit, ds_ns, offsets=None, floor=None, cap=None, extra=None, ctx=None):
+    """predict on the history's own dates, every row, in y's layout: what fit_screened screens against (aligned:
+    shared dates ds [T]; ragged: per-series dates [N][Tmax], padded by the last date)."""
+    if offsets is None:
+        return predict(spec, fit.theta, fit.y_scale, fit.grid, ds_ns, floor=floor, cap=cap, extra_future=extra, ctx=ctx)
+    offsets = np.asarray(offsets, dtype=np.int64)
+    fut, idx = history_future(ds_ns, offsets)
+    exf = None
+    if spec.extra:
+        exf = np.ascontiguousarray(np.asarray(extra, dtype=np.float64)[:, idx].transpose(1, 0, 2))
+    yh = predict(spec, fit.theta, fit.y_scale, fit.grid, fut, floor=floor, cap=cap, extra_future=exf, ctx=ctx)
+    lens = np.diff(offsets)
+    return yh[np.arange(fut.shape[1])[None, :] < lens[:, None]]
+
+
+def screen(spec, fit, ds_ns, y, offsets=None, floor=None, cap=None, extra=None, excluded=None, scale_floor=1e-8,
+           threshold=5.0, max_share=0.05, min_rows=10, ctx=None):
+    """One screening round of fit_screened by hand: fitted_history of `fit` (a FitResult of this panel), then screen_rows
+    with min_scale = scale_floor * fit.y_scale.  Returns a Screen with .fitted."""
+    y = np.ascontiguousarray(y)
+    fitted = fitted_history(spec, fit, ds_ns, offsets, floor, cap, extra, ctx=ctx)
+    s = screen_rows(y, fitted.reshape(y.shape), offsets=offsets, excluded=excluded,
+                    min_scale=float(scale_floor) * np.asarray(fit.y_scale, dtype=np.float64), threshold=threshold,
+                    max_share=max_share, min_rows=min_rows, ctx=ctx)
+    s.fitted = fitted.reshape(y.shape)
+    return s
+
+
+def _merge_screens(parts, aligned):
+    cat = lambda k: np.concatenate([getattr(p, k) for p in parts])     # noqa: E731
+    return Screen(cat('flag'), cat('resid'), cat('center'), cat('scale'), cat('n_new'), cat('n_flagged'), cat('status'))
+
+
+def fit_screened(spec, ds_ns, y, offsets=None, floor=None, cap=None, extra=None, threshold=5.0, max_share=0.05,
+                 min_rows=10, scale_floor=1e-8, passes=1, ctx=None, devices=None):
+    """Fit, screen, cut, refit in one call (include/tsf.h tsf_fit_screened): every series fitted on its full history,
+    `passes` rounds of (predict on the history, screening rule, the flagged rows cut, the cut series fitted again).
+    Input as fit_aligned (ds_ns [T], y [N][T], extra [n_extra][T]) or, with offsets [N+1], as fit_ragged.
+    devices: several GPUs, split by series.  Returns a ScreenedFit."""
+    ds_ns, y, offsets, N, T = _cv_panel(ds_ns, y, offsets)
+    fl = _opt_f64(floor, N, 'floor')
+    cp = _opt_f64(cap, N, 'cap')
+    a = _screen_args(threshold, max_share, min_rows, passes)
+    if not (np.isfinite(scale_floor) and scale_floor >= 0):
+        raise ValueError('scale_floor must be finite and >= 0')
+    kw = dict(threshold=threshold, max_share=max_share, min_rows=min_rows, scale_floor=scale_floor, passes=passes)
+    devs = None if ctx is not None else resolve_devices(devices)
+    if devs and N >= 2 * MIN_SERIES_PER_DEVICE:
+        parts = min(len(devs), N // MIN_SERIES_PER_DEVICE)
+        lens = np.full(N, T, np.int64) if offsets is None else np.diff(offsets)
+        cuts = _cuts(lens, parts)
+        ex = None if extra is None else np.asarray(extra)
+
+        def one(c, a, b):
+            if offsets is None:
+                return fit_screened(spec, ds_ns, y[a:b], None, None if fl is None else fl[a:b],
+                                    None if cp is None else cp[a:b], extra, ctx=c, **kw)
+            r0, r1 = int(offsets[a]), int(offsets[b])
+            return fit_screened(spec, ds_ns[r0:r1], y[r0:r1], offsets[a:b + 1] - r0, None if fl is None else fl[a:b],
+                                None if cp is None else cp[a:b], None if ex is None else ex[:, r0:r1], ctx=c, **kw)
+        blocks = [(c, int(a), int(b)) for c, a, b in zip(_contexts(devs[:parts]), cuts[:-1], cuts[1:]) if b > a]
+        pr = _run_blocks(one, blocks)
+        return ScreenedFit(_merge_fits(spec, [p.fit for p in pr], shared_grid=False),
+                           _merge_fits(spec, [p.first for p in pr], shared_grid=offsets is None),
+                           _merge_screens([p.screen for p in pr], offsets is None),
+                           np.concatenate([p.rounds for p in pr]))
+    ctx = ctx or get_context()
+    L = _lib.load()
+    ex = None
+    if spec.extra:
+        ex = np.ascontiguousarray(extra, dtype=np.float64)
+        if ex.shape != (len(spec.extra), len(ds_ns)):
+            raise ValueError('extra must be [n_extra][len(ds)]')
+    cs = spec.to_c()
+    fout, farrs = _alloc_out(N, spec.theta_stride, N)
+    first, first_arrs = _alloc_out(N, spec.theta_stride, 1 if offsets is None else N)
+    sout, sarrs = _alloc_screen(y, N)
+    rounds = np.zeros(N, np.int32)
+    out = _lib.TsfFitScreenedOut(fout, ctypes.pointer(first), sout, rounds.ctypes.data)
+    rc = L.tsf_fit_screened(ctx.handle, ctypes.byref(cs), N, T, _lib._ptr(offsets), ds_ns.ctypes.data, y.ctypes.data,
+                            _lib.y_dtype_code(y), _lib._ptr(fl), _lib._ptr(cp), _lib._ptr(ex), float(scale_floor),
+                            ctypes.byref(a), ctypes.byref(out))
+    ctx.check(rc)
+    return ScreenedFit(FitResult(spec, *farrs), FitResult(spec, *first_arrs), Screen(*sarrs), rounds)

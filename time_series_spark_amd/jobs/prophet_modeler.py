@@ -192,14 +192,47 @@ def bucket_models(panel, kw):
     return buckets, hol, hol_days, hol_extra
 
 
-def fit_packed(panel, floor, cap, kw, devices=None, cost=None, lap=None):
+SCREEN_DEFAULTS = {'threshold': 5.0, 'max_share': 0.05, 'min_rows': 10, 'passes': 1}
+SCREENED_COLUMNS = ['series_id', 'dim_id', 'ds', 'y', 'resid', 'center', 'scale']
+
+
+def screen_settings(config):
+    """config['model']['screen'] (optional, not in the reference): outlier screening of every fit (fc.fit_screened:
+    fit, flag the rows whose residual lies beyond threshold robust scales -- at most max_share of a series' rows --,
+    cut them, fit again, `passes` rounds).  None without the section; else the keywords of fc.fit_screened, defaults
+    filled in.  An unknown key or a value the library would refuse raises ValueError."""
+    sec = (config.get('model') or {}).get('screen')
+    if sec is None:
+        return None
+    if not isinstance(sec, dict):
+        raise ValueError('model.screen must be a mapping (threshold, max_share, min_rows, passes)')
+    unknown = sorted(set(sec) - set(SCREEN_DEFAULTS))
+    if unknown:
+        raise ValueError('model.screen: unknown key(s) %s (known: %s)' % (unknown, sorted(SCREEN_DEFAULTS)))
+    out = dict(SCREEN_DEFAULTS, **sec)
+    out['threshold'], out['max_share'] = float(out['threshold']), float(out['max_share'])
+    fc._screen_args(out['threshold'], out['max_share'], out['min_rows'], out['passes'])     # (ValueError)
+    out['min_rows'], out['passes'] = int(out['min_rows']), int(out['passes'])
+    return out
+
+
+def _empty_screened():
+    return pd.DataFrame({'series_id': np.zeros(0, np.int32), 'dim_id': np.zeros(0, np.int32),
+                         'ds': np.zeros(0, 'datetime64[ns]'), 'y': np.zeros(0), 'resid': np.zeros(0),
+                         'center': np.zeros(0), 'scale': np.zeros(0)}, columns=SCREENED_COLUMNS)
+
+
+def fit_packed(panel, floor, cap, kw, devices=None, cost=None, lap=None, screen=None, removed=None):
     """Fit every series of a PackedPanel.  Series are bucketed by the seasonality set
     fbprophet's 'auto' rules give their own history (each Prophet object decides alone), one
     kernel launch per bucket.  Returns (pieces, status, n_iter): pieces = [(members, buffer)] -- the blobs of one fit
     call, uint8 [len(members)][stride] (panel.dump_models_buffer), row i the model of series members[i]; a series whose
     status is negative has no model, and a later piece (fbprophet's Newton retry) supersedes an earlier one.
     cost: optional [N] expected relative cost per series (the iteration counts of the previous run's models):
-    scheduling hints for the launches (tsf_set_cost_hints); results do not depend on them."""
+    scheduling hints for the launches (tsf_set_cost_hints); results do not depend on them.
+    screen: screen_settings(config) or None -- every fit call becomes fc.fit_screened with these keywords (same spec,
+    same groups, same Newton retry on top); removed: a dict that then receives, per series with flagged rows,
+    (ds, y, resid, center, scale) of those rows (a later fit of the series supersedes an earlier one)."""
     N = panel.N
     lap = lap or (lambda name: None)
     hint = (lambda mem: None) if cost is None else (lambda mem: np.asarray(cost)[mem])
@@ -218,6 +251,27 @@ def fit_packed(panel, floor, cap, kw, devices=None, cost=None, lap=None):
     min_group = int(kw.get('min_aligned_group', MIN_ALIGNED_GROUP))
     lap('specs')
 
+    def fit_call(spec, mem, ds, y, off, fl, cp, ex):
+        """fit_aligned (off None: y [G][T]) / fit_ragged of the series mem -- or, with `screen`, fit_screened"""
+        if screen is None:
+            if off is None:
+                return fc.fit_aligned(spec, ds, y, floor=fl, cap=cp, extra=ex, devices=devices, **_hint_kw(hint(mem)))
+            return fc.fit_ragged(spec, off, ds, y, floor=fl, cap=cp, extra=ex, devices=devices, **_hint_kw(hint(mem)))
+        sf = fc.fit_screened(spec, ds, y, offsets=off, floor=fl, cap=cp, extra=ex, devices=devices, **screen)
+        if removed is not None:
+            sc = sf.screen
+            for g in range(len(mem)):
+                removed.pop(int(mem[g]), None)
+            for g in np.flatnonzero(sc.n_flagged > 0):
+                if off is None:
+                    rows = np.flatnonzero(sc.flag[g])
+                    rec = (ds[rows], y[g][rows], sc.resid[g][rows])
+                else:
+                    rows = int(off[g]) + np.flatnonzero(sc.flag[int(off[g]):int(off[g + 1])])
+                    rec = (ds[rows], y[rows], sc.resid[rows])
+                removed[int(mem[g])] = rec + (float(sc.center[g]), float(sc.scale[g]))
+        return sf.fit
+
     def run(spec, sd, seas, members):
         """One optimiser over `members`: series that share a timestamp vector are fitted
         together through the aligned entry point (one set of design tables for the group), the
@@ -235,10 +289,10 @@ def fit_packed(panel, floor, cap, kw, devices=None, cost=None, lap=None):
             y2d = pk.rows_2d(panel.y, panel.offsets, gm, T)
             ex = features.holiday_matrix(panel.ds_ns[a0:a0 + T], hol_days) if hol_extra else (
                 np.zeros((1, T)) if not seas else None)
-            calls.append((gm, fc.fit_aligned(
-                spec, panel.ds_ns[a0:a0 + T], y2d,
-                floor=None if floor is None else np.asarray(floor)[gm],
-                cap=None if cap is None else np.asarray(cap)[gm], extra=ex, devices=devices, **_hint_kw(hint(gm)))))
+            calls.append((gm, fit_call(
+                spec, gm, panel.ds_ns[a0:a0 + T], y2d, None,
+                None if floor is None else np.asarray(floor)[gm],
+                None if cap is None else np.asarray(cap)[gm], ex)))
             lap('fit_aligned %d' % len(gm))
         if len(rest):
             lens = panel.lengths[rest]
@@ -254,10 +308,10 @@ def fit_packed(panel, floor, cap, kw, devices=None, cost=None, lap=None):
                 ds_r, y_r = panel.ds_ns[idx], panel.y[idx]
             ex = features.holiday_matrix(ds_r, hol_days) if hol_extra else (
                 np.zeros((1, len(ds_r))) if not seas else None)
-            calls.append((rest, fc.fit_ragged(
-                spec, off, ds_r, y_r,
-                floor=None if floor is None else np.asarray(floor)[rest],
-                cap=None if cap is None else np.asarray(cap)[rest], extra=ex, devices=devices, **_hint_kw(hint(rest)))))
+            calls.append((rest, fit_call(
+                spec, rest, ds_r, y_r, off,
+                None if floor is None else np.asarray(floor)[rest],
+                None if cap is None else np.asarray(cap)[rest], ex)))
             lap('fit_ragged %d' % len(rest))
         for mem, res in calls:
             st = np.asarray(res.status)
@@ -440,17 +494,36 @@ def _model_packed(config, panel, n_rows, execution_time, previous=None, lap=None
         at = np.minimum(np.searchsorted(pkey, k), len(pkey) - 1)
         cost = np.where(pkey[at] == k, pcost[at], int(np.median(pcost))).astype(np.int32)
     lap('checks + hints')
-    pieces, status, n_iter = fit_packed(panel, floors, cap, kw, devices=config.get('devices'), cost=cost, lap=lap)
+    screen = screen_settings(config)
+    removed = {} if screen is not None else None
+    pieces, status, n_iter = fit_packed(panel, floors, cap, kw, devices=config.get('devices'), cost=cost, lap=lap,
+                                        **({} if screen is None else {'screen': screen, 'removed': removed}))
     lap('fit_packed tail')
     sids = panel.keys['series_id'].to_numpy()
     dids = panel.keys['dim_id'].to_numpy()
     out = ModelBatch(sids, dids, floor, cap, pieces, status, n_iter)
+    if removed is not None:
+        out.screened = _screened_frame(sids, dids, removed)
     for n in np.flatnonzero(out.piece_of < 0):
         # pystan RuntimeError -> the reference prints and drops the series (:81-85)
         print(f"Runtime error {_lib.STATUS_NAMES.get(int(status[n]), status[n])} for "
               f"series_id: {int(sids[n])}, dim_id: {int(dids[n])}")
     print(f"Modeled {panel.N} series ({n_rows} rows) in {time.time() - execution_time}")
     return out
+
+
+def _screened_frame(sids, dids, removed):
+    """The rows model.screen removed, one per row (SCREENED_COLUMNS), series in panel order, rows in time order."""
+    if not removed:
+        return _empty_screened()
+    order = sorted(removed)
+    n_rows = [len(removed[n][0]) for n in order]
+    cat = lambda k: np.concatenate([np.asarray(removed[n][k]) for n in order])     # noqa: E731
+    rep = lambda v: np.repeat(np.asarray(v), n_rows)                                # noqa: E731
+    return pd.DataFrame({'series_id': rep(sids[order]).astype(np.int32), 'dim_id': rep(dids[order]).astype(np.int32),
+                         'ds': cat(0).astype('datetime64[ns]'), 'y': cat(1).astype(np.float64), 'resid': cat(2),
+                         'center': rep([removed[n][3] for n in order]), 'scale': rep([removed[n][4] for n in order])},
+                        columns=SCREENED_COLUMNS)
 
 
 def model_panel(config):
@@ -824,6 +897,22 @@ class ProphetModeler:
             _write_cost_sidecar(self.config['io']['models'], [part], model_df['series_id'].to_numpy(),
                                 model_df['dim_id'].to_numpy(), model_df.attrs.get('tsf_cost'))
 
+    def persist_screened(self, batches):
+        """config['io']['screened'] (optional, with model.screen): the rows the screening removed, as one parquet part
+        in that directory (SCREENED_COLUMNS), mode='overwrite' like the models."""
+        path = self.config['io'].get('screened')
+        if not path:
+            return
+        if screen_settings(self.config) is None:
+            raise ValueError('io.screened needs model.screen')
+        frames = [b.screened for b in batches if b is not None and getattr(b, 'screened', None) is not None]
+        out = pd.concat(frames, ignore_index=True) if frames else _empty_screened()
+        os.makedirs(path, exist_ok=True)
+        for f in os.listdir(path):
+            if f.endswith('.parquet'):
+                os.remove(os.path.join(path, f))
+        out.to_parquet(os.path.join(path, 'part-00000.parquet'), index=False)
+
     def _clear_models(self):
         """-> function that waits until the previous run's files are gone (pipeline.clear_directory)"""
         from ..pipeline import clear_directory
@@ -909,6 +998,7 @@ class ProphetModeler:
         # the columns go from the reader to the packer as arrays; read_input_dataframe gives the
         # same rows as a frame for callers that want one
         batch = fit(*scorer.read_input_columns())
+        scorer.persist_screened([batch])
         if batch is None:
             scorer.persist_models(_empty_models())
             return _empty_models() if return_frame else None
@@ -942,6 +1032,7 @@ class ProphetModeler:
             self.logger.warning('%d malformed model-input records dropped (PERMISSIVE)', stats['malformed'])
         if not cleared:
             self._clear_models()()
+        self.persist_screened([b for _k, b, _part in done])
         live = [(b, part) for _k, b, part in done if part is not None]
         if live:
             _write_cost_sidecar(self.config['io']['models'], [part for _b, part in live],
