@@ -731,6 +731,100 @@ int tsf_fit_screened(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t T, c
                      const void *y, int32_t y_dtype, const double *floor, const double *cap, const double *extra,
                      double scale_floor_rel, const tsf_screen_args *args, tsf_fit_screened_out *out);
 
+/* ---- conformal interval calibration from cross-validation residuals ------------------------------------
+ * Prophet's intervals carry trend and observation noise only, so on real panels the coverage tsf_cross_validate reports
+ * comes back off interval_width.  Split-conformal calibration is the standard remedy: per series and per horizon bucket,
+ * the finite-sample-corrected empirical quantile of a conformity score over the cross-validation's out-of-sample rows,
+ * by which the forecast's interval is then widened or narrowed.  tsf_calibrate_rows is that rule for a whole panel at
+ * once, as a pure function of each series' multiset of (bucket, score); tsf_apply_calibration applies a table to a
+ * forecast; tsf_calibrate is cross-validation and rule in one call.  Everything here is opt-in: no other entry point
+ * changes.  Reference interface replaced: none (neither the reference nor fbprophet has such a function); parity
+ * unpinned (what is pinned is the contract below, bit for bit against a numpy restatement, and tsf_calibrate against the
+ * composition of the public calls).  Timing: tools/bench_calibrate.py; DESIGN.md 5i.
+ * Coverage after calibration is MARGINAL (over series' rows, not conditional on a date) and rests on the folds' errors
+ * being exchangeable with the forecast's own: DESIGN.md 5i.
+ *
+ * tsf_calibrate_rows.  A ragged set of holdout rows: series n owns rows [row_off[n], row_off[n + 1]) of horizon_ns
+ * (int64: ds - cutoff), y, yhat (double) [R], R = row_off[N]; lower / upper [L][R] (level l's bounds at l * R; read under
+ * TSF_CALIB_CQR only, NULL otherwise).  Host pointers in the host variant; device pointers in _dev (args and the
+ * tsf_calib_table struct itself are HOST memory in both; _dev reads row_off back and synchronises the stream).
+ * tsf_calib_args: mode; n_levels L in [1, TSF_CALIB_MAX_LEVELS]; levels[l] strictly inside (0, 1), the coverage
+ * targets; horizon_ns > 0; n_buckets B in [1, TSF_CALIB_MAX_BUCKETS]; min_scores >= 1.
+ *
+ * Contract per series.  Integer arithmetic is int64; every double operation is rounded once, in the order written.
+ *   w = (horizon_ns + B - 1) / B.  A row with horizon h is eligible iff 0 < h <= horizon_ns; its bucket is
+ *   min(B - 1, (h - 1) / w).  Its score at level l:
+ *     TSF_CALIB_ABS: s = fabs(y - yhat), the same for every l; the row is live iff it is eligible and s is finite.
+ *     TSF_CALIB_CQR: s = fmax(lower_l - y, y - upper_l); live iff eligible and y, lower_l, upper_l are all finite (the
+ *       three operands are tested, not s: fmax drops a NaN).
+ *   Cell (b, l), b < B, holds the live scores of bucket b; cell (B, l) all live scores of the series (the pooled cell).
+ *   With m its count and a its scores ascending:  n[n][b][l] = m;  m < min_scores: q[n][b][l] = NaN;  otherwise
+ *     k = (int64)ceil((double)(m + 1) * levels[l]),  q[n][b][l] = a[min(k, m) - 1] + 0.0
+ *   (a product that rounds just above an integer takes the next rank: conservative; k > m takes the maximum; the + 0.0
+ *   returns a zero as +0.0 whichever zero the sort left at the rank).  Sorting moves values and rounds nothing: the
+ *   table depends on the series' multiset of (bucket, score) only -- not on the row order, the rest of the batch or how
+ *   the call is cut into launches.  No atomics.
+ *   status[n]: TSF_CALIB_TOO_LONG (more than TSF_CALIB_MAX_ROWS rows: every q NaN, every n 0); TSF_CALIB_NO_SCORES (the
+ *   pooled cell of every level has m < min_scores); TSF_CALIB_OK otherwise.
+ * Refusals (< 0 with a message, before any launch; the context stays usable): a NULL row_off, horizon_ns, y, yhat,
+ *   args, table, table->q, table->n or table->status; a mode other than the two; n_levels, a level, n_buckets,
+ *   min_scores or horizon_ns outside the ranges above; TSF_CALIB_CQR without lower and upper; row_off not ascending from
+ *   0.  N == 0 is a legal no-op.
+ *
+ * tsf_apply_calibration.  yhat [N][H]; lower / upper [N][L][H] (read under TSF_CALIB_CQR only, NULL otherwise);
+ * ds_future [H] (shared_future = 1) or [N][H] as in tsf_predict; origin_ns [N], the model's last history timestamp
+ * (grid.start_ns + grid.t_scale_ns); q / n [N][B+1][L] and the tsf_calib_args that made them.  Per element (n, l, i):
+ *   h = ds - origin;  b = h <= 0 ? 0 : min(B - 1, (h - 1) / w).  A row inside the history takes the first bucket and a
+ *   row beyond the calibrated horizon the last one: both are EXTRAPOLATIONS of the table, no score was observed there.
+ *   The cell used is b if n[b][l] >= min_scores, else the pooled cell B if n[B][l] >= min_scores, else none.
+ *   ABS: lo = yhat - q, hi = yhat + q.  CQR: lo = fmin(lower_l - q, yhat), hi = fmax(upper_l + q, yhat) (a negative q
+ *   narrows the interval, down to yhat at most).  No cell, or yhat not finite: lo = hi = NaN.
+ * Outputs lo, hi [N][L][H]; cell int8 [N][L][H] (b, B or -1) or NULL.  _dev: device pointers (args in HOST memory).
+ *
+ * tsf_calibrate.  Input as tsf_cross_validate plus the tsf_calib_args; calib->horizon_ns must equal the
+ * cross-validation's horizon.  The call runs tsf_cross_validate's own steps, forms each holdout row's horizon and
+ * observed value on the device, and runs the rule on the device's yhat [R] with row_off = the series' holdout rows: the
+ * table equals tsf_cross_validate followed by tsf_calibrate_rows on its outputs bit for bit, except that a series whose
+ * series_status is not TSF_CV_OK gets no table (q NaN, n 0, TSF_CALIB_NO_SCORES).  cv_out, where not NULL, receives
+ * what tsf_cross_validate returns, bit for bit.  TSF_CALIB_ABS needs no intervals (n_samples may be 0); TSF_CALIB_CQR is
+ * accepted only with n_levels == 1, n_samples > 0 and levels[0] == interval_width, and reads the folds' own yhat_lower /
+ * yhat_upper.  Only the [N]-sized table crosses back to the host where cv_out is NULL. */
+#define TSF_CALIB_MAX_ROWS 16384
+#define TSF_CALIB_MAX_LEVELS 16
+#define TSF_CALIB_MAX_BUCKETS 64
+enum { TSF_CALIB_ABS = 0, TSF_CALIB_CQR = 1 };
+enum { TSF_CALIB_OK = 0, TSF_CALIB_NO_SCORES = -40, TSF_CALIB_TOO_LONG = -41 };
+typedef struct {
+    int32_t mode, n_levels;
+    double levels[TSF_CALIB_MAX_LEVELS];
+    int64_t horizon_ns;
+    int32_t n_buckets, min_scores;
+} tsf_calib_args;
+typedef struct {
+    double *q;              /* [N][B+1][L] required */
+    int32_t *n;             /* [N][B+1][L] required */
+    int32_t *status;        /* [N]         required */
+} tsf_calib_table;
+int tsf_calib_args_size(void);      /* sizeof(tsf_calib_args), sizeof(tsf_calib_table): the self-checks of a binding */
+int tsf_calib_table_size(void);
+int tsf_calibrate_rows(tsf_ctx *ctx, int64_t N, const int64_t *row_off, const int64_t *horizon_ns, const double *y,
+                       const double *yhat, const double *lower, const double *upper, const tsf_calib_args *args,
+                       tsf_calib_table *table);
+int tsf_calibrate_rows_dev(tsf_ctx *ctx, int64_t N, const int64_t *row_off, const int64_t *horizon_ns, const double *y,
+                           const double *yhat, const double *lower, const double *upper, const tsf_calib_args *args,
+                           tsf_calib_table *table, void *stream);
+int tsf_apply_calibration(tsf_ctx *ctx, int64_t N, int32_t H, const double *yhat, const double *lower, const double *upper,
+                          const int64_t *ds_future, int32_t shared_future, const int64_t *origin_ns, const double *q,
+                          const int32_t *n, const tsf_calib_args *args, double *lo, double *hi, int8_t *cell);
+int tsf_apply_calibration_dev(tsf_ctx *ctx, int64_t N, int32_t H, const double *yhat, const double *lower,
+                              const double *upper, const int64_t *ds_future, int32_t shared_future, const int64_t *origin_ns,
+                              const double *q, const int32_t *n, const tsf_calib_args *args, double *lo, double *hi,
+                              int8_t *cell, void *stream);
+int tsf_calibrate(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t T, const int64_t *offsets, const int64_t *ds,
+                  const void *y, int32_t y_dtype, const double *floor, const double *cap, const double *extra,
+                  const tsf_cv_args *args, const int64_t *series_key, int32_t n_samples, double interval_width,
+                  uint64_t seed, const tsf_calib_args *calib, tsf_calib_table *table, tsf_cv_out *cv_out);
+
 /* ---- scheduling hints ---------------------------------------------------------------------
  * A launch ends with its longest fits (cfg2: 1 582 evaluations against a mean of 454), and nothing
  * cheap about a series predicts how long its fit takes -- except an earlier fit of the same

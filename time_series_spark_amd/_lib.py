@@ -141,6 +141,17 @@ class TsfFitScreenedOut(ctypes.Structure):
                 ('rounds', ctypes.c_void_p)]
 
 
+class TsfCalibArgs(ctypes.Structure):
+    """tsf_calib_args (include/tsf.h)."""
+    _fields_ = [('mode', ctypes.c_int32), ('n_levels', ctypes.c_int32), ('levels', ctypes.c_double * 16),
+                ('horizon_ns', ctypes.c_int64), ('n_buckets', ctypes.c_int32), ('min_scores', ctypes.c_int32)]
+
+
+class TsfCalibTable(ctypes.Structure):
+    """tsf_calib_table (include/tsf.h)."""
+    _fields_ = [('q', ctypes.c_void_p), ('n', ctypes.c_void_p), ('status', ctypes.c_void_p)]
+
+
 # every symbol include/tsf.h declares; tests check the library exports all of them
 EXPORTS = ['tsf_create', 'tsf_destroy', 'tsf_last_error', 'tsf_device_count', 'tsf_spec_default',
            'tsf_spec_size', 'tsf_grid_info_size', 'tsf_spec_K', 'tsf_theta_stride',
@@ -153,6 +164,8 @@ EXPORTS = ['tsf_create', 'tsf_destroy', 'tsf_last_error', 'tsf_device_count', 't
            'tsf_cv_plan', 'tsf_cross_validate', 'tsf_last_cv_grids', 'tsf_tune', 'tsf_last_tune_counts',
            'tsf_screen_args_size', 'tsf_screen_out_size', 'tsf_fit_screened_out_size', 'tsf_screen_rows', 'tsf_screen_rows_dev',
            'tsf_fit_screened',
+           'tsf_calib_args_size', 'tsf_calib_table_size', 'tsf_calibrate_rows', 'tsf_calibrate_rows_dev',
+           'tsf_apply_calibration', 'tsf_apply_calibration_dev', 'tsf_calibrate',
            'tsf_pack_rows', 'tsf_pack_rows_typed', 'tsf_pack_fetch', 'tsf_pack_flags', 'tsf_pack_free', 'tsf_model_blobs',
            'tsf_csv_read', 'tsf_csv_fetch', 'tsf_csv_columns', 'tsf_csv_malformed', 'tsf_csv_free', 'tsf_csv_write_forecasts', 'tsf_csv_write_forecasts_i32',
            'tsf_csv_discover', 'tsf_csv_discover_load', 'tsf_csv_root_open', 'tsf_csv_root_load', 'tsf_csv_root_free', 'tsf_csv_read_loaded', 'tsf_csv_dir_paths', 'tsf_csv_dir_series_id', 'tsf_csv_dir_error_path', 'tsf_csv_dir_free']
@@ -168,6 +181,11 @@ TUNE_MAX_CAND = 256
 # TSF_SCREEN_* (include/tsf.h): per-series outcome of the screening rule, its row limit
 SCREEN_OK, SCREEN_TOO_FEW, SCREEN_TOO_LONG, SCREEN_NONFINITE = 0, -30, -31, -32
 SCREEN_MAX_ROWS = 16384
+# TSF_CALIB_* (include/tsf.h): the conformity scores, the per-series outcome of the calibration rule, its limits
+CALIB_ABS, CALIB_CQR = 0, 1
+CALIB_MODES = {'abs': CALIB_ABS, 'cqr': CALIB_CQR}
+CALIB_OK, CALIB_NO_SCORES, CALIB_TOO_LONG = 0, -40, -41
+CALIB_MAX_ROWS, CALIB_MAX_LEVELS, CALIB_MAX_BUCKETS = 16384, 16, 64
 
 # TSF_OPT_* (include/tsf.h): route switches of one context
 OPTIONS = ['harm', 'lattice', 'sparse_extra', 'fit_grouped', 'gram_share', 'grid_order', 'grid_share', 'ragged_split',
@@ -254,6 +272,13 @@ def load():
     L.tsf_screen_rows_dev.argtypes = L.tsf_screen_rows.argtypes + [vp]
     L.tsf_fit_screened.argtypes = [vp, psp, i64, i32, vp, vp, vp, i32, vp, vp, vp, ctypes.c_double,
                                    ctypes.POINTER(TsfScreenArgs), ctypes.POINTER(TsfFitScreenedOut)]
+    pca, pct = ctypes.POINTER(TsfCalibArgs), ctypes.POINTER(TsfCalibTable)
+    L.tsf_calibrate_rows.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, pca, pct]
+    L.tsf_calibrate_rows_dev.argtypes = L.tsf_calibrate_rows.argtypes + [vp]
+    L.tsf_apply_calibration.argtypes = [vp, i64, i32, vp, vp, vp, vp, i32, vp, vp, vp, pca, vp, vp, vp]
+    L.tsf_apply_calibration_dev.argtypes = L.tsf_apply_calibration.argtypes + [vp]
+    L.tsf_calibrate.argtypes = [vp, psp, i64, i32, vp, vp, vp, i32, vp, vp, vp, ctypes.POINTER(TsfCvArgs), vp, i32,
+                                ctypes.c_double, ctypes.c_uint64, pca, pct, ctypes.POINTER(TsfCvOut)]
     L.tsf_pack_rows.argtypes = [i64, vp, vp, vp, vp, i32, ctypes.POINTER(vp), ctypes.POINTER(i64),
                                 ctypes.POINTER(i64), ctypes.POINTER(i32)]
     L.tsf_pack_fetch.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -300,6 +325,8 @@ def load():
     if (L.tsf_screen_args_size() != ctypes.sizeof(TsfScreenArgs) or L.tsf_screen_out_size() != ctypes.sizeof(TsfScreenOut)
             or L.tsf_fit_screened_out_size() != ctypes.sizeof(TsfFitScreenedOut)):
         raise TsfError('tsf_screen_args / tsf_screen_out layout mismatch between _lib.py and libtsf_amd.so')
+    if L.tsf_calib_args_size() != ctypes.sizeof(TsfCalibArgs) or L.tsf_calib_table_size() != ctypes.sizeof(TsfCalibTable):
+        raise TsfError('tsf_calib_args / tsf_calib_table layout mismatch between _lib.py and libtsf_amd.so')
     _lib = L
     return L
 

@@ -32,6 +32,7 @@
 #include "tsf_cv_kernels.h"
 #include "tsf_tune_kernels.h"
 #include "tsf_screen_kernels.h"
+#include "tsf_calib_kernels.h"
 #include "tsf_cv_plan.h"
 
 using namespace tsf;
@@ -3009,15 +3010,20 @@ static int cv_metrics_setup(tsf_ctx *ctx, CvCall &S, const double *yhat, const d
     return 0;
 }
 
-extern "C" int tsf_cross_validate(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t T, const int64_t *offsets,
-                                  const int64_t *ds, const void *y, int32_t y_dtype, const double *floor_,
-                                  const double *cap, const double *extra, const tsf_cv_args *args,
-                                  const int64_t *series_key, int32_t n_samples, double interval_width, uint64_t seed,
-                                  tsf_cv_out *out)
+static int calib_run(tsf_ctx *ctx, int64_t N, const int64_t *d_off, const int64_t *h_off, const int64_t *d_h, const double *d_y,
+                     const double *d_yhat, const double *d_lower, const double *d_upper, const tsf_calib_args &a,
+                     const tsf_calib_table &o, hipStream_t st);
+static int calib_no_table(const tsf_calib_args &a, int64_t N, const tsf_calib_table &t);
+
+// tsf_cross_validate (cal == nullptr: out required) and tsf_calibrate (cal and tab given, checked by the caller: the rule
+// runs on the device's holdout rows behind the metrics, and out may be null: then only the table crosses back)
+static int cross_validate_run(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t T, const int64_t *offsets,
+                              const int64_t *ds, const void *y, int32_t y_dtype, const double *floor_,
+                              const double *cap, const double *extra, const tsf_cv_args *args,
+                              const int64_t *series_key, int32_t n_samples, double interval_width, uint64_t seed,
+                              tsf_cv_out *out, const tsf_calib_args *cal, const tsf_calib_table *tab)
 {
-    if (!ctx) return -1;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!spec || !ds || !y || !out || !out->series_status) return fail(ctx, "NULL input");
+    if (!spec || !ds || !y || (!cal && !out) || (out && !out->series_status)) return fail(ctx, "NULL input");
     if (y_dtype < TSF_Y_F64 || y_dtype > TSF_Y_I32) return fail(ctx, "bad y_dtype");
     tsf_cv_args a;
     if (tsf_cv::resolve_args(args, &a)) return fail(ctx, "bad cross-validation arguments (horizon_ns > 0, rolling_window in [0, 1])");
@@ -3028,20 +3034,27 @@ extern "C" int tsf_cross_validate(tsf_ctx *ctx, const tsf_spec *spec, int64_t N,
     const bool iv = n_samples > 0;
     if (iv && (n_samples < 2 || n_samples > 4096)) return fail(ctx, "n_samples must be 0 or in [2, 4096]");
     if (iv && !(interval_width > 0.0 && interval_width < 1.0)) return fail(ctx, "interval_width must be in (0, 1)");
+    if (cal) {
+        if (cal->horizon_ns != a.horizon_ns) return fail(ctx, "tsf_calib_args.horizon_ns must equal the cross-validation's horizon");
+        if (cal->mode == TSF_CALIB_CQR && !(cal->n_levels == 1 && iv && cal->levels[0] == interval_width))
+            return fail(ctx, "TSF_CALIB_CQR needs n_levels == 1, n_samples > 0 and levels[0] == interval_width");
+    }
     ctx->order_n = 0;                   // (pending cost hints were meant for a fit call)
     ctx->cv_grids = 0;
     ctx->cv_launches = 0;
     CvCall S;
     cv_plan_call(N, T, offsets, ds, a, spec, y_dtype, floor_, cap, &S);
     const int64_t F = S.F, R = S.R, M = S.M;
-    memcpy(out->series_status, S.pst.data(), sizeof(int32_t) * (size_t)N);
-    if (F == 0) return 0;
-    const tsf_fit_out &fo = out->fit;
-    if (!fo.theta || !fo.y_scale || !fo.fval || !fo.status || !fo.n_iter || !fo.n_eval || !fo.grid)
-        return fail(ctx, "tsf_cv_out.fit has NULL members");
-    if (!out->yhat || !out->horizon_ns || !out->mse || !out->rmse || !out->mae || !out->mape ||
-        (iv && (!out->yhat_lower || !out->yhat_upper || !out->coverage)))
-        return fail(ctx, "tsf_cv_out has NULL members");
+    if (out) memcpy(out->series_status, S.pst.data(), sizeof(int32_t) * (size_t)N);
+    if (F == 0) return cal ? calib_no_table(*cal, N, *tab) : 0;
+    if (out) {
+        const tsf_fit_out &fo = out->fit;
+        if (!fo.theta || !fo.y_scale || !fo.fval || !fo.status || !fo.n_iter || !fo.n_eval || !fo.grid)
+            return fail(ctx, "tsf_cv_out.fit has NULL members");
+        if (!out->yhat || !out->horizon_ns || !out->mse || !out->rmse || !out->mae || !out->mape ||
+            (iv && (!out->yhat_lower || !out->yhat_upper || !out->coverage)))
+            return fail(ctx, "tsf_cv_out has NULL members");
+    }
     if (int rc = cv_upload(ctx, y, floor_, cap, extra, series_key, &S)) return rc;
     const int stride = S.stride;
     const int32_t Hmax = S.Hmax;
@@ -3092,8 +3105,32 @@ extern "C" int tsf_cross_validate(tsf_ctx *ctx, const tsf_spec *spec, int64_t N,
         return rc;
     hipLaunchKernelGGL(cv_metrics_kernel, dim3((unsigned)N), dim3(64), 0, nullptr, X.ma);
     HIP_TRY(ctx, hipGetLastError());
+    if (cal) {
+        // the rule on the device's own holdout rows: horizon and y per row, then the table; only it crosses back
+        const int cells = (cal->n_buckets + 1) * cal->n_levels;
+        DevBuf d_rh, d_ry, d_q, d_n, d_cst;
+        HIP_TRY(ctx, d_rh.alloc(8 * (size_t)R)); HIP_TRY(ctx, d_ry.alloc(8 * (size_t)R));
+        HIP_TRY(ctx, d_q.alloc(8 * (size_t)N * cells)); HIP_TRY(ctx, d_n.alloc(4 * (size_t)N * cells)); HIP_TRY(ctx, d_cst.alloc(4 * (size_t)N));
+        hipLaunchKernelGGL(calib_cv_rows_kernel, dim3((unsigned)(N < 65535 ? N : 65535)), dim3(256), 0, nullptr, X.ma,
+                           d_rh.as<int64_t>(), d_ry.as<double>());
+        HIP_TRY(ctx, hipGetLastError());
+        const tsf_calib_table dt{d_q.as<double>(), d_n.as<int32_t>(), d_cst.as<int32_t>()};
+        if (int rc = calib_run(ctx, N, X.d_roff.as<int64_t>(), S.rows_off.data(), d_rh.as<int64_t>(), d_ry.as<double>(),
+                               X.d_yo.as<double>(), iv ? X.d_loo.as<double>() : nullptr, iv ? X.d_hio.as<double>() : nullptr,
+                               *cal, dt, nullptr))
+            return rc;
+        hipLaunchKernelGGL(calib_mask_kernel, dim3((unsigned)(N < 65535 ? N : 65535)), dim3(256), 0, nullptr, N, cells,
+                           X.d_sst.as<int32_t>(), dt.q, dt.n, dt.status);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipDeviceSynchronize());
+        HIP_TRY(ctx, hipMemcpy(tab->q, d_q.p, 8 * (size_t)N * cells, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(tab->n, d_n.p, 4 * (size_t)N * cells, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(tab->status, d_cst.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+        if (!out) return 0;
+    }
     HIP_TRY(ctx, hipDeviceSynchronize());
     // outputs
+    const tsf_fit_out &fo = out->fit;
     HIP_TRY(ctx, hipMemcpy(fo.theta, S.d_th.p, 8 * (size_t)F * stride, hipMemcpyDeviceToHost));
     HIP_TRY(ctx, hipMemcpy(fo.y_scale, S.d_ys.p, 8 * (size_t)F, hipMemcpyDeviceToHost));
     HIP_TRY(ctx, hipMemcpy(fo.fval, S.d_fv.p, 8 * (size_t)F, hipMemcpyDeviceToHost));
@@ -3117,6 +3154,18 @@ extern "C" int tsf_cross_validate(tsf_ctx *ctx, const tsf_spec *spec, int64_t N,
     }
     HIP_TRY(ctx, hipMemcpy(out->series_status, X.d_sst.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
     return 0;
+}
+
+extern "C" int tsf_cross_validate(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t T, const int64_t *offsets,
+                                  const int64_t *ds, const void *y, int32_t y_dtype, const double *floor_,
+                                  const double *cap, const double *extra, const tsf_cv_args *args,
+                                  const int64_t *series_key, int32_t n_samples, double interval_width, uint64_t seed,
+                                  tsf_cv_out *out)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return cross_validate_run(ctx, spec, N, T, offsets, ds, y, y_dtype, floor_, cap, extra, args, series_key, n_samples,
+                              interval_width, seed, out, nullptr, nullptr);
 }
 
 // One fit launch over the whole histories of the series sel of an uploaded panel with spec gs, its outputs put at the
@@ -3736,4 +3785,262 @@ extern "C" int tsf_fit_screened(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, i
     if (ho.n_flagged) HIP_TRY(ctx, hipMemcpy(ho.n_flagged, d_nf.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
     if (out->rounds) memcpy(out->rounds, rounds.data(), 4 * (size_t)N);
     return 0;
+}
+
+// ---- conformal interval calibration (include/tsf.h) ---------------------------------------------------------
+// tsf_calibrate_rows: the rule, one workgroup per series, one launch per power-of-two class of row counts, as the
+// screening rule is launched (the LDS of a launch is its class's: calib_lds_bytes).  tsf_apply_calibration: one
+// elementwise launch.  tsf_calibrate is cross_validate_run with the rule behind its metrics.
+
+extern "C" int tsf_calib_args_size(void) { return (int)sizeof(tsf_calib_args); }
+extern "C" int tsf_calib_table_size(void) { return (int)sizeof(tsf_calib_table); }
+
+static int check_calib_args(tsf_ctx *ctx, const tsf_calib_args *a)
+{
+    if (!a) return fail(ctx, "NULL tsf_calib_args");
+    if (a->mode != TSF_CALIB_ABS && a->mode != TSF_CALIB_CQR) return fail(ctx, "mode must be TSF_CALIB_ABS or TSF_CALIB_CQR");
+    if (a->n_levels < 1 || a->n_levels > TSF_CALIB_MAX_LEVELS) return fail(ctx, "n_levels must be in [1, TSF_CALIB_MAX_LEVELS]");
+    for (int l = 0; l < a->n_levels; ++l)
+        if (!(a->levels[l] > 0.0 && a->levels[l] < 1.0)) return fail(ctx, "every level must be strictly inside (0, 1)");
+    if (a->horizon_ns <= 0) return fail(ctx, "horizon_ns must be > 0");
+    if (a->n_buckets < 1 || a->n_buckets > TSF_CALIB_MAX_BUCKETS) return fail(ctx, "n_buckets must be in [1, TSF_CALIB_MAX_BUCKETS]");
+    if (a->min_scores < 1) return fail(ctx, "min_scores must be >= 1");
+    return 0;
+}
+
+static int check_calib_table(tsf_ctx *ctx, const tsf_calib_table *t)
+{
+    if (!t || !t->q || !t->n || !t->status) return fail(ctx, "NULL output (tsf_calib_table, its q, n and status are required)");
+    return 0;
+}
+
+static int check_calib_rows(tsf_ctx *ctx, int64_t N, const int64_t *h_off)
+{
+    if (N > (int64_t)INT32_MAX) return fail(ctx, "N too large");
+    if (h_off[0] != 0) return fail(ctx, "bad rows (row_off[0] = 0)");
+    for (int64_t n = 0; n < N; ++n)
+        if (h_off[n + 1] < h_off[n]) return fail(ctx, "bad rows (row_off ascending)");
+    return 0;
+}
+
+// the table of a call without a single holdout row (host)
+static int calib_no_table(const tsf_calib_args &a, int64_t N, const tsf_calib_table &t)
+{
+    const size_t cells = (size_t)(a.n_buckets + 1) * a.n_levels;
+    for (size_t i = 0; i < (size_t)N * cells; ++i) { t.q[i] = std::numeric_limits<double>::quiet_NaN(); t.n[i] = 0; }
+    for (int64_t n = 0; n < N; ++n) t.status[n] = TSF_CALIB_NO_SCORES;
+    return 0;
+}
+
+// The rule on device-resident rows.  h_off: row_off on the host (the launch classes); o: device pointers.
+static int calib_run(tsf_ctx *ctx, int64_t N, const int64_t *d_off, const int64_t *h_off, const int64_t *d_h, const double *d_y,
+                     const double *d_yhat, const double *d_lower, const double *d_upper, const tsf_calib_args &a,
+                     const tsf_calib_table &o, hipStream_t st)
+{
+    if (N == 0) return 0;
+    CalibRowsArgs k;
+    memset(&k, 0, sizeof(k));
+    k.row_off = d_off; k.h = d_h; k.y = d_y; k.yhat = d_yhat;
+    k.lower = a.mode == TSF_CALIB_CQR ? d_lower : nullptr; k.upper = a.mode == TSF_CALIB_CQR ? d_upper : nullptr;
+    k.R = h_off[N]; k.horizon = a.horizon_ns; k.w = (a.horizon_ns + a.n_buckets - 1) / a.n_buckets;
+    k.mode = a.mode; k.L = a.n_levels; k.B = a.n_buckets; k.min_scores = a.min_scores;
+    for (int l = 0; l < a.n_levels; ++l) k.levels[l] = a.levels[l];
+    k.q = o.q; k.n = o.n; k.status = o.status;
+    // class c: NSP = 2^c rows of LDS; a series beyond TSF_CALIB_MAX_ROWS only reports its status (class 1)
+    auto class_of = [](int64_t len) {
+        if (len > (int64_t)TSF_CALIB_MAX_ROWS) return 1;
+        int c = 1;
+        while (((int64_t)1 << c) < len) ++c;
+        return c;
+    };
+    auto launch = [&](const int32_t *d_sel, int64_t blocks, int c) -> int {
+        const int NSP = 1 << c;
+        k.sel = d_sel;
+        const size_t lds = calib_lds_bytes(NSP);
+        if (lds > 64 * 1024)        // (per launch: the attribute is per device, and a process may drive several GPUs)
+            HIP_TRY(ctx, hipFuncSetAttribute((const void *)calib_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        hipLaunchKernelGGL(calib_rows_kernel, dim3((unsigned)blocks), dim3(256), lds, st, k, NSP);
+        HIP_TRY(ctx, hipGetLastError());
+        return 0;
+    };
+    constexpr int NC = 16;
+    int64_t count[NC] = {0}, start[NC + 1] = {0};
+    std::vector<int8_t> cls((size_t)N);
+    for (int64_t n = 0; n < N; ++n) {
+        cls[(size_t)n] = (int8_t)class_of(h_off[n + 1] - h_off[n]);
+        count[cls[(size_t)n]]++;
+    }
+    for (int c = 0; c < NC; ++c) start[c + 1] = start[c] + count[c];
+    for (int c = 0; c < NC; ++c)
+        if (count[c] == N) return launch(nullptr, N, c);        // one class: no list
+    std::vector<int32_t> sel((size_t)N);
+    {
+        int64_t at[NC];
+        for (int c = 0; c < NC; ++c) at[c] = start[c];
+        for (int64_t n = 0; n < N; ++n) sel[(size_t)at[cls[(size_t)n]]++] = (int32_t)n;
+    }
+    DevBuf d_sel;
+    HIP_TRY(ctx, d_sel.alloc(4 * (size_t)N));
+    HIP_TRY(ctx, hipMemcpy(d_sel.p, sel.data(), 4 * (size_t)N, hipMemcpyHostToDevice));
+    for (int c = 0; c < NC; ++c)
+        if (count[c] > 0)
+            if (int rc = launch(d_sel.as<int32_t>() + start[c], count[c], c)) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(st));         // (the list goes back to the pool)
+    return 0;
+}
+
+static int check_calib_rows_call(tsf_ctx *ctx, int64_t N, const int64_t *row_off, const int64_t *h, const double *y,
+                                 const double *yhat, const double *lower, const double *upper, const tsf_calib_args *args,
+                                 const tsf_calib_table *table)
+{
+    if (N < 0) return fail(ctx, "N must be >= 0");
+    if (int rc = check_calib_args(ctx, args)) return rc;
+    if (int rc = check_calib_table(ctx, table)) return rc;
+    if (!row_off || !h || !y || !yhat) return fail(ctx, "NULL input (row_off, horizon_ns, y and yhat are required)");
+    if (args->mode == TSF_CALIB_CQR && (!lower || !upper)) return fail(ctx, "TSF_CALIB_CQR needs lower and upper");
+    return 0;
+}
+
+extern "C" int tsf_calibrate_rows_dev(tsf_ctx *ctx, int64_t N, const int64_t *row_off, const int64_t *horizon_ns,
+                                      const double *y, const double *yhat, const double *lower, const double *upper,
+                                      const tsf_calib_args *args, tsf_calib_table *table, void *stream)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rc = check_calib_rows_call(ctx, N, row_off, horizon_ns, y, yhat, lower, upper, args, table)) return rc;
+    if (N == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<int64_t> h_off((size_t)N + 1);
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    HIP_TRY(ctx, hipMemcpy(h_off.data(), row_off, 8 * ((size_t)N + 1), hipMemcpyDeviceToHost));
+    if (int rc = check_calib_rows(ctx, N, h_off.data())) return rc;
+    return calib_run(ctx, N, row_off, h_off.data(), horizon_ns, y, yhat, lower, upper, *args, *table, st);
+}
+
+extern "C" int tsf_calibrate_rows(tsf_ctx *ctx, int64_t N, const int64_t *row_off, const int64_t *horizon_ns, const double *y,
+                                  const double *yhat, const double *lower, const double *upper, const tsf_calib_args *args,
+                                  tsf_calib_table *table)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rc = check_calib_rows_call(ctx, N, row_off, horizon_ns, y, yhat, lower, upper, args, table)) return rc;
+    if (N == 0) return 0;
+    if (int rc = check_calib_rows(ctx, N, row_off)) return rc;
+    const size_t R = (size_t)row_off[N], L = (size_t)args->n_levels, cells = (size_t)(args->n_buckets + 1) * L;
+    const bool cqr = args->mode == TSF_CALIB_CQR;
+    DevBuf d_off, d_h, d_y, d_yh, d_lo, d_hi, d_q, d_n, d_st;
+    HIP_TRY(ctx, d_off.alloc(8 * ((size_t)N + 1))); HIP_TRY(ctx, hipMemcpy(d_off.p, row_off, 8 * ((size_t)N + 1), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_h.alloc(8 * R)); HIP_TRY(ctx, d_y.alloc(8 * R)); HIP_TRY(ctx, d_yh.alloc(8 * R));
+    if (R) {
+        HIP_TRY(ctx, hipMemcpy(d_h.p, horizon_ns, 8 * R, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(d_y.p, y, 8 * R, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(d_yh.p, yhat, 8 * R, hipMemcpyHostToDevice));
+    }
+    if (cqr) {
+        HIP_TRY(ctx, d_lo.alloc(8 * L * R)); HIP_TRY(ctx, d_hi.alloc(8 * L * R));
+        if (R) {
+            HIP_TRY(ctx, hipMemcpy(d_lo.p, lower, 8 * L * R, hipMemcpyHostToDevice));
+            HIP_TRY(ctx, hipMemcpy(d_hi.p, upper, 8 * L * R, hipMemcpyHostToDevice));
+        }
+    }
+    HIP_TRY(ctx, d_q.alloc(8 * (size_t)N * cells)); HIP_TRY(ctx, d_n.alloc(4 * (size_t)N * cells)); HIP_TRY(ctx, d_st.alloc(4 * (size_t)N));
+    const tsf_calib_table dt{d_q.as<double>(), d_n.as<int32_t>(), d_st.as<int32_t>()};
+    if (int rc = calib_run(ctx, N, d_off.as<int64_t>(), row_off, d_h.as<int64_t>(), d_y.as<double>(), d_yh.as<double>(),
+                           cqr ? d_lo.as<double>() : nullptr, cqr ? d_hi.as<double>() : nullptr, *args, dt, nullptr))
+        return rc;
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    HIP_TRY(ctx, hipMemcpy(table->q, d_q.p, 8 * (size_t)N * cells, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(table->n, d_n.p, 4 * (size_t)N * cells, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(table->status, d_st.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+static int check_calib_apply_call(tsf_ctx *ctx, int64_t N, int32_t H, const double *yhat, const double *lower,
+                                  const double *upper, const int64_t *ds_future, const int64_t *origin_ns, const double *q,
+                                  const int32_t *n, const tsf_calib_args *args, const double *lo, const double *hi)
+{
+    if (N < 0 || H < 0) return fail(ctx, "N and H must be >= 0");
+    if (int rc = check_calib_args(ctx, args)) return rc;
+    if (!yhat || !ds_future || !origin_ns || !q || !n || !lo || !hi)
+        return fail(ctx, "NULL input (yhat, ds_future, origin_ns, q, n, lo and hi are required)");
+    if (args->mode == TSF_CALIB_CQR && (!lower || !upper)) return fail(ctx, "TSF_CALIB_CQR needs lower and upper");
+    return 0;
+}
+
+static int calib_apply_run(tsf_ctx *ctx, int64_t N, int32_t H, const double *yhat, const double *lower, const double *upper,
+                           const int64_t *ds_future, int32_t shared_future, const int64_t *origin_ns, const double *q,
+                           const int32_t *n, const tsf_calib_args &a, double *lo, double *hi, int8_t *cell, hipStream_t st)
+{
+    CalibApplyArgs k;
+    memset(&k, 0, sizeof(k));
+    k.N = N; k.H = H; k.L = a.n_levels; k.B = a.n_buckets; k.mode = a.mode; k.min_scores = a.min_scores;
+    k.shared_future = shared_future ? 1 : 0; k.w = (a.horizon_ns + a.n_buckets - 1) / a.n_buckets;
+    k.yhat = yhat; k.lower = a.mode == TSF_CALIB_CQR ? lower : nullptr; k.upper = a.mode == TSF_CALIB_CQR ? upper : nullptr;
+    k.ds_future = ds_future; k.origin = origin_ns; k.q = q; k.n = n; k.lo = lo; k.hi = hi; k.cell = cell;
+    const int64_t total = N * (int64_t)a.n_levels * H, blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(calib_apply_kernel, dim3((unsigned)(blocks < 65535 ? blocks : 65535)), dim3(256), 0, st, k);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+extern "C" int tsf_apply_calibration_dev(tsf_ctx *ctx, int64_t N, int32_t H, const double *yhat, const double *lower,
+                                         const double *upper, const int64_t *ds_future, int32_t shared_future,
+                                         const int64_t *origin_ns, const double *q, const int32_t *n,
+                                         const tsf_calib_args *args, double *lo, double *hi, int8_t *cell, void *stream)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rc = check_calib_apply_call(ctx, N, H, yhat, lower, upper, ds_future, origin_ns, q, n, args, lo, hi)) return rc;
+    if (N == 0 || H == 0) return 0;
+    return calib_apply_run(ctx, N, H, yhat, lower, upper, ds_future, shared_future, origin_ns, q, n, *args, lo, hi, cell,
+                           (hipStream_t)stream);
+}
+
+extern "C" int tsf_apply_calibration(tsf_ctx *ctx, int64_t N, int32_t H, const double *yhat, const double *lower,
+                                     const double *upper, const int64_t *ds_future, int32_t shared_future,
+                                     const int64_t *origin_ns, const double *q, const int32_t *n, const tsf_calib_args *args,
+                                     double *lo, double *hi, int8_t *cell)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rc = check_calib_apply_call(ctx, N, H, yhat, lower, upper, ds_future, origin_ns, q, n, args, lo, hi)) return rc;
+    if (N == 0 || H == 0) return 0;
+    const size_t NH = (size_t)N * H, L = (size_t)args->n_levels, cells = (size_t)(args->n_buckets + 1) * L;
+    const size_t n_ds = shared_future ? (size_t)H : NH;
+    const bool cqr = args->mode == TSF_CALIB_CQR;
+    DevBuf d_yh, d_lw, d_up, d_ds, d_or, d_q, d_n, d_lo, d_hi, d_cell;
+    HIP_TRY(ctx, d_yh.alloc(8 * NH)); HIP_TRY(ctx, hipMemcpy(d_yh.p, yhat, 8 * NH, hipMemcpyHostToDevice));
+    if (cqr) {
+        HIP_TRY(ctx, d_lw.alloc(8 * L * NH)); HIP_TRY(ctx, hipMemcpy(d_lw.p, lower, 8 * L * NH, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, d_up.alloc(8 * L * NH)); HIP_TRY(ctx, hipMemcpy(d_up.p, upper, 8 * L * NH, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(ctx, d_ds.alloc(8 * n_ds)); HIP_TRY(ctx, hipMemcpy(d_ds.p, ds_future, 8 * n_ds, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_or.alloc(8 * (size_t)N)); HIP_TRY(ctx, hipMemcpy(d_or.p, origin_ns, 8 * (size_t)N, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_q.alloc(8 * (size_t)N * cells)); HIP_TRY(ctx, hipMemcpy(d_q.p, q, 8 * (size_t)N * cells, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_n.alloc(4 * (size_t)N * cells)); HIP_TRY(ctx, hipMemcpy(d_n.p, n, 4 * (size_t)N * cells, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_lo.alloc(8 * L * NH)); HIP_TRY(ctx, d_hi.alloc(8 * L * NH));
+    if (cell) HIP_TRY(ctx, d_cell.alloc(L * NH));
+    if (int rc = calib_apply_run(ctx, N, H, d_yh.as<double>(), cqr ? d_lw.as<double>() : nullptr, cqr ? d_up.as<double>() : nullptr,
+                                 d_ds.as<int64_t>(), shared_future, d_or.as<int64_t>(), d_q.as<double>(), d_n.as<int32_t>(), *args,
+                                 d_lo.as<double>(), d_hi.as<double>(), cell ? d_cell.as<int8_t>() : nullptr, nullptr))
+        return rc;
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    HIP_TRY(ctx, hipMemcpy(lo, d_lo.p, 8 * L * NH, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(hi, d_hi.p, 8 * L * NH, hipMemcpyDeviceToHost));
+    if (cell) HIP_TRY(ctx, hipMemcpy(cell, d_cell.p, L * NH, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int tsf_calibrate(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t T, const int64_t *offsets,
+                             const int64_t *ds, const void *y, int32_t y_dtype, const double *floor_, const double *cap,
+                             const double *extra, const tsf_cv_args *args, const int64_t *series_key, int32_t n_samples,
+                             double interval_width, uint64_t seed, const tsf_calib_args *calib, tsf_calib_table *table,
+                             tsf_cv_out *cv_out)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rc = check_calib_args(ctx, calib)) return rc;
+    if (int rc = check_calib_table(ctx, table)) return rc;
+    return cross_validate_run(ctx, spec, N, T, offsets, ds, y, y_dtype, floor_, cap, extra, args, series_key, n_samples,
+                              interval_width, seed, cv_out, calib, table);
 }

@@ -1854,3 +1854,361 @@ def fit_screened(spec, ds_ns, y, offsets=None, floor=None, cap=None, extra=None,
                             ctypes.byref(a), ctypes.byref(out))
     ctx.check(rc)
     return ScreenedFit(FitResult(spec, *farrs), FitResult(spec, *first_arrs), Screen(*sarrs), rounds)
+
+
+# ---- conformal interval calibration from cross-validation residuals (include/tsf.h) ---------------------------
+
+def calibrated_columns(levels, prefix='yhat_lower_c'):
+    """Column names of coverage levels: 0.8 -> 'yhat_lower_c80', 0.975 -> 'yhat_lower_c97.5' ('%s%s' % (prefix,
+    format(100 * p, 'g')), the style of quantile_columns).  ValueError for a level that is not strictly inside (0, 1),
+    for two levels with the same name and for more than CALIB_MAX_LEVELS levels."""
+    lv = [float(p) for p in np.asarray(levels, dtype=np.float64).reshape(-1)]
+    if not 1 <= len(lv) <= _lib.CALIB_MAX_LEVELS:
+        raise ValueError('between 1 and %d coverage levels (got %d)' % (_lib.CALIB_MAX_LEVELS, len(lv)))
+    names = []
+    for p in lv:
+        if not (np.isfinite(p) and 0.0 < p < 1.0):
+            raise ValueError('coverage level %r: must be strictly inside (0, 1)' % (p,))
+        name = '%s%s' % (prefix, format(100 * p, 'g'))
+        if name in names:
+            raise ValueError('coverage levels: two levels are named %s' % name)
+        names.append(name)
+    return names
+
+
+def _calib_args(levels, mode, horizon, n_buckets, min_scores):
+    """tsf_calib_args, refused here as the library refuses them (before it is loaded)."""
+    lv = np.asarray(levels, dtype=np.float64).reshape(-1)
+    calibrated_columns(lv)
+    if isinstance(mode, str):
+        if mode not in _lib.CALIB_MODES:
+            raise ValueError("mode must be 'abs' or 'cqr'")
+        mode = _lib.CALIB_MODES[mode]
+    if mode not in (_lib.CALIB_ABS, _lib.CALIB_CQR):
+        raise ValueError("mode must be 'abs' or 'cqr'")
+    if int(horizon) != horizon or horizon <= 0:
+        raise ValueError('horizon must be an integer number of ns > 0')
+    if int(n_buckets) != n_buckets or not 1 <= n_buckets <= _lib.CALIB_MAX_BUCKETS:
+        raise ValueError('n_buckets must be an integer in [1, %d]' % _lib.CALIB_MAX_BUCKETS)
+    if int(min_scores) != min_scores or min_scores < 1:
+        raise ValueError('min_scores must be an integer >= 1')
+    a = _lib.TsfCalibArgs()
+    a.mode, a.n_levels, a.horizon_ns, a.n_buckets, a.min_scores = int(mode), len(lv), int(horizon), int(n_buckets), int(min_scores)
+    for i, p in enumerate(lv):
+        a.levels[i] = float(p)
+    return a
+
+
+class Calibration(object):
+    """A calibration table (include/tsf.h tsf_calibrate_rows): q [N][B+1][L] (the conformity-score quantile per series,
+    table row -- horizon buckets 0 .. B-1, then the pooled row B -- and level; NaN where fewer than min_scores scores),
+    n [N][B+1][L] int32 (the scores behind each), status [N] (_lib.CALIB_*), levels [L] (coverage targets), mode
+    (_lib.CALIB_ABS / CALIB_CQR), horizon (ns), n_buckets, min_scores.  cv: the CVResult where fc.calibrate was asked
+    for it."""
+
+    def __init__(self, q, n, status, levels, mode, horizon, n_buckets, min_scores, cv=None):
+        self.q, self.n, self.status = q, n, status
+        self.levels = np.array(levels, dtype=np.float64).reshape(-1)
+        self.mode, self.horizon, self.n_buckets, self.min_scores = int(mode), int(horizon), int(n_buckets), int(min_scores)
+        self.cv = cv
+
+    def _args(self):
+        return _calib_args(self.levels, self.mode, self.horizon, self.n_buckets, self.min_scores)
+
+    @property
+    def bucket_width(self):
+        return (self.horizon + self.n_buckets - 1) // self.n_buckets
+
+    def apply(self, yhat, ds_future, origin_ns, lower=None, upper=None, want_cell=False, ctx=None):
+        """The table applied to a forecast (include/tsf.h tsf_apply_calibration): yhat [N][H], ds_future [H] or [N][H]
+        (ns), origin_ns [N] (each model's last history timestamp), lower / upper [N][L][H] (CQR: the model's own bounds at
+        each level) -> (lo, hi) [N][L][H], with want_cell also cell int8 [N][L][H] (the bucket used, n_buckets for the
+        pooled row, -1 for none).  Rows inside the history use the first bucket and rows beyond the calibrated horizon
+        the last one: extrapolations."""
+        yhat = np.ascontiguousarray(yhat, dtype=np.float64)
+        if yhat.ndim != 2:
+            raise ValueError('yhat must be [N][H]')
+        N, H = yhat.shape
+        L = len(self.levels)
+        if self.q.shape != (N, self.n_buckets + 1, L):
+            raise ValueError('the table has %d series, yhat %d' % (self.q.shape[0], N))
+        ds = np.ascontiguousarray(ds_future, dtype=np.int64)
+        shared = ds.ndim == 1
+        if ds.shape != ((H,) if shared else (N, H)):
+            raise ValueError('ds_future must be [H] or [N][H]')
+        origin = np.ascontiguousarray(np.broadcast_to(np.asarray(origin_ns, dtype=np.int64), (N,)))
+        lw = up = None
+        if self.mode == _lib.CALIB_CQR:
+            if lower is None or upper is None:
+                raise ValueError('a CQR table needs lower and upper')
+            lw = np.ascontiguousarray(lower, dtype=np.float64)
+            up = np.ascontiguousarray(upper, dtype=np.float64)
+            if lw.shape != (N, L, H) or up.shape != (N, L, H):
+                raise ValueError('lower / upper must be [N][L][H]')
+        q = np.ascontiguousarray(self.q, dtype=np.float64)
+        cnt = np.ascontiguousarray(self.n, dtype=np.int32)
+        lo, hi = np.zeros((N, L, H)), np.zeros((N, L, H))
+        cell = np.zeros((N, L, H), np.int8) if want_cell else None
+        a = self._args()
+        ctx = ctx or get_context()
+        ctx.check(_lib.load().tsf_apply_calibration(ctx.handle, N, H, yhat.ctypes.data, _lib._ptr(lw), _lib._ptr(up),
+                                                    ds.ctypes.data, int(shared), origin.ctypes.data, q.ctypes.data,
+                                                    cnt.ctypes.data, ctypes.byref(a), lo.ctypes.data, hi.ctypes.data,
+                                                    _lib._ptr(cell)))
+        return (lo, hi, cell) if want_cell else (lo, hi)
+
+    def frame(self, keys):
+        """One row per series and table row.  keys: a dict (or DataFrame) of [N] series-key columns.  Columns: the keys,
+        bucket (0 .. n_buckets, the last the pooled row), horizon_upto (ns: the bucket's largest horizon, the pooled
+        row's the whole horizon), then n_c<..> and q_c<..> per level (calibrated_columns); then what from_frame needs
+        to rebuild the table: calib_status per series and the settings calib_mode, calib_horizon, calib_min_scores."""
+        import pandas as pd
+        N, R = self.q.shape[0], self.n_buckets + 1
+        cols = {}
+        for k in (keys if isinstance(keys, dict) else {c: keys[c] for c in keys.columns}).items():
+            v = np.asarray(k[1])
+            if v.shape != (N,):
+                raise ValueError('key column %s must be [N]' % k[0])
+            cols[k[0]] = np.repeat(v, R)
+        b = np.tile(np.arange(R, dtype=np.int32), N)
+        cols['bucket'] = b
+        cols['horizon_upto'] = np.minimum((b.astype(np.int64) + 1) * self.bucket_width, self.horizon)
+        cols['horizon_upto'][b == self.n_buckets] = self.horizon
+        for i, name in enumerate(calibrated_columns(self.levels, 'n_c')):
+            cols[name] = self.n[:, :, i].reshape(-1)
+        for i, name in enumerate(calibrated_columns(self.levels, 'q_c')):
+            cols[name] = self.q[:, :, i].reshape(-1)
+        cols['calib_status'] = np.repeat(self.status, R)
+        cols['calib_mode'] = np.full(N * R, self.mode, np.int32)
+        cols['calib_horizon'] = np.full(N * R, self.horizon, np.int64)
+        cols['calib_min_scores'] = np.full(N * R, self.min_scores, np.int32)
+        return pd.DataFrame(cols, columns=list(cols))
+
+    @classmethod
+    def from_frame(cls, df):
+        """(Calibration, keys DataFrame [N]) of a frame made by .frame: the rows of a series are consecutive, buckets
+        ascending; the levels are read back from the q_c<..> column names."""
+        names = [c for c in df.columns if c.startswith('q_c')]
+        if not names or len(df) == 0:
+            raise ValueError('not a calibration frame')
+        levels = [float(c[3:]) / 100.0 for c in names]
+        for c, want in zip(names, calibrated_columns(levels, 'q_c')):
+            if c != want:
+                raise ValueError('calibration frame: column %s does not name a level' % c)
+        R = int(df['bucket'].max()) + 1
+        if len(df) % R or not np.array_equal(df['bucket'].values, np.tile(np.arange(R), len(df) // R)):
+            raise ValueError('calibration frame: every series needs its buckets 0 .. %d in order' % (R - 1))
+        N, L = len(df) // R, len(names)
+        q = np.stack([df[c].values.astype(np.float64).reshape(N, R) for c in names], axis=2)
+        n = np.stack([df['n_c' + c[3:]].values.astype(np.int32).reshape(N, R) for c in names], axis=2)
+        fixed = ['bucket', 'horizon_upto', 'calib_status', 'calib_mode', 'calib_horizon', 'calib_min_scores']
+        kcols = [c for c in df.columns if c not in fixed and not c.startswith('q_c') and not c.startswith('n_c')]
+        keys = df.iloc[::R][kcols].reset_index(drop=True)
+        cal = cls(np.ascontiguousarray(q), np.ascontiguousarray(n), df['calib_status'].values[::R].astype(np.int32), levels,
+                  int(df['calib_mode'].iloc[0]), int(df['calib_horizon'].iloc[0]), R - 1, int(df['calib_min_scores'].iloc[0]))
+        return cal, keys
+
+
+def _alloc_calib(N, B, L):
+    q, n, st = np.zeros((N, B + 1, L)), np.zeros((N, B + 1, L), np.int32), np.zeros(N, np.int32)
+    return _lib.TsfCalibTable(q.ctypes.data, n.ctypes.data, st.ctypes.data), (q, n, st)
+
+
+def calibrate_rows(row_offsets, horizon_ns, y, yhat, levels, lower=None, upper=None, mode='abs', horizon=None,
+                   n_buckets=10, min_scores=20, ctx=None):
+    """The calibration rule alone (include/tsf.h tsf_calibrate_rows) on a ragged set of out-of-sample rows: series n owns
+    rows [row_offsets[n], row_offsets[n + 1]) of horizon_ns (int64: ds - cutoff), y, yhat; lower / upper [L][R] under
+    'cqr'.  Per series, horizon bucket (n_buckets of them over (0, horizon], plus one pooled row) and level: the
+    ceil((m + 1) * level)-th smallest of the m conformity scores |y - yhat| ('abs') or max(lower - y, y - upper) ('cqr'),
+    NaN below min_scores.  horizon: ns (required).  Returns a Calibration."""
+    if horizon is None:
+        raise ValueError('horizon (ns) is required')
+    a = _calib_args(levels, mode, horizon, n_buckets, min_scores)
+    off = np.ascontiguousarray(row_offsets, dtype=np.int64)
+    if off.ndim != 1 or len(off) < 1:
+        raise ValueError('row_offsets must be [N+1]')
+    N, R, L = len(off) - 1, int(off[-1]), a.n_levels
+    h = np.ascontiguousarray(horizon_ns, dtype=np.int64)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    yhat = np.ascontiguousarray(yhat, dtype=np.float64)
+    if h.shape != (R,) or y.shape != (R,) or yhat.shape != (R,):
+        raise ValueError('horizon_ns, y and yhat must be [row_offsets[-1]]')
+    lw = up = None
+    if a.mode == _lib.CALIB_CQR:
+        if lower is None or upper is None:
+            raise ValueError("mode 'cqr' needs lower and upper")
+        lw = np.ascontiguousarray(lower, dtype=np.float64).reshape(-1, R) if R else np.zeros((L, 0))
+        up = np.ascontiguousarray(upper, dtype=np.float64).reshape(-1, R) if R else np.zeros((L, 0))
+        if lw.shape != (L, R) or up.shape != (L, R):
+            raise ValueError('lower / upper must be [L][R]')
+    ctx = ctx or get_context()
+    tab, (q, n, st) = _alloc_calib(N, a.n_buckets, L)
+    ctx.check(_lib.load().tsf_calibrate_rows(ctx.handle, N, off.ctypes.data, h.ctypes.data, y.ctypes.data, yhat.ctypes.data,
+                                             _lib._ptr(lw), _lib._ptr(up), ctypes.byref(a), ctypes.byref(tab)))
+    return Calibration(q, n, st, np.array(a.levels[:L]), a.mode, a.horizon_ns, a.n_buckets, a.min_scores)
+
+
+def _calib_mask(cal, cv_status):
+    """tsf_calibrate's rule for a series whose cross-validation did not end CV_OK: no table."""
+    bad = np.asarray(cv_status) != _lib.CV_OK
+    cal.q[bad], cal.n[bad], cal.status[bad] = np.nan, 0, _lib.CALIB_NO_SCORES
+    return cal
+
+
+def cv_interval_levels(levels):
+    """The tail pairs of coverage levels p as quantile levels: [(1 - p) / 2 ..., (1 + p) / 2 ...] (2 L of them)."""
+    lv = np.asarray(levels, dtype=np.float64).reshape(-1)
+    return np.concatenate([(1.0 - lv) / 2.0, (1.0 + lv) / 2.0])
+
+
+def calibrate_cv(cv, levels, mode='abs', n_buckets=10, min_scores=20, horizon=None, interval_width=None, floor=None,
+                 cap=None, extra=None, series_key=None, uncertainty_samples=1000, seed=0, ctx=None):
+    """The calibration rule on a cross_validate result -> Calibration: the rows are the CVResult's holdout rows, their
+    horizon ds - cutoff.  horizon: the cross-validation's (ns; None: the largest horizon of the result's metric rows).
+    'cqr': each level's bounds come from score_cv(cv, quantiles=cv_interval_levels(levels)).q -- floor / cap / extra /
+    series_key / uncertainty_samples / seed are score_cv's, what cross_validate was given -- except that ONE level equal
+    to interval_width (the width cross_validate was given, with intervals=True) uses the CVResult's own yhat_lower /
+    yhat_upper.
+    A series whose cv.status is not CV_OK gets no table (CALIB_NO_SCORES), as in fc.calibrate."""
+    lv = np.asarray(levels, dtype=np.float64).reshape(-1)
+    if horizon is None:
+        if len(cv.horizon) == 0:
+            raise ValueError('horizon is required: the CVResult has no metric row to read it from')
+        horizon = int(np.max(cv.horizon))
+    h = cv.ds - cv.cutoff[cv.row_fold]
+    lw = up = None
+    m = _lib.CALIB_MODES.get(mode, mode)
+    if m == _lib.CALIB_CQR:
+        if len(lv) == 1 and cv.yhat_lower is not None and interval_width is not None and lv[0] == float(interval_width):
+            lw, up = cv.yhat_lower[None, :], cv.yhat_upper[None, :]
+        else:
+            s = score_cv(cv, quantiles=cv_interval_levels(lv), floor=floor, cap=cap, extra=extra, series_key=series_key,
+                         uncertainty_samples=uncertainty_samples, seed=seed, ctx=ctx)
+            lw, up = s.q[:len(lv)], s.q[len(lv):]
+    cal = calibrate_rows(cv.row_offsets, h, cv.y, cv.yhat, lv, lower=lw, upper=up, mode=mode, horizon=horizon,
+                         n_buckets=n_buckets, min_scores=min_scores, ctx=ctx)
+    return _calib_mask(cal, cv.status)
+
+
+def _merge_calibrations(parts, cv):
+    p0 = parts[0]
+    cat = lambda k: np.concatenate([getattr(p, k) for p in parts])     # noqa: E731
+    return Calibration(cat('q'), cat('n'), cat('status'), p0.levels, p0.mode, p0.horizon, p0.n_buckets, p0.min_scores, cv)
+
+
+def calibrate(spec, ds_ns, y, horizon, levels, mode='abs', n_buckets=10, min_scores=20, period=None, initial=None,
+              offsets=None, floor=None, cap=None, extra=None, rolling_window=0.1, uncertainty_samples=1000,
+              interval_width=0.8, seed=0, series_key=None, want_cv=False, ctx=None, devices=None):
+    """Cross-validation and calibration rule in one call (include/tsf.h tsf_calibrate): input as cross_validate; the rule
+    runs on the device's own holdout forecasts and only the table comes back (with want_cv the CVResult too, as
+    Calibration.cv: cross_validate's bit for bit).  'abs' runs the folds without intervals; 'cqr' takes ONE level equal
+    to interval_width and reads the folds' own yhat_lower / yhat_upper (cross_validate with intervals=True).  devices:
+    several GPUs, split by series as cross_validate splits.  Returns a Calibration equal to
+    calibrate_cv(cross_validate(...), ...) bit for bit."""
+    ds_ns, y, offsets, N, T = _cv_panel(ds_ns, y, offsets)
+    a = _calib_args(levels, mode, horizon, n_buckets, min_scores)
+    cqr = a.mode == _lib.CALIB_CQR
+    if cqr and not (a.n_levels == 1 and a.levels[0] == float(interval_width)):
+        raise ValueError("mode 'cqr' in the one call takes one level equal to interval_width (several levels: "
+                         "cross_validate, then calibrate_cv)")
+    fl = _opt_f64(floor, N, 'floor')
+    cp = _opt_f64(cap, N, 'cap')
+    key = None if series_key is None else np.ascontiguousarray(series_key, dtype=np.int64)
+    if key is not None and key.shape != (N,):
+        raise ValueError('series_key must be [N]')
+    kw = dict(mode=mode, n_buckets=n_buckets, min_scores=min_scores, period=period, initial=initial,
+              rolling_window=rolling_window, uncertainty_samples=uncertainty_samples, interval_width=interval_width,
+              seed=seed, want_cv=want_cv)
+    devs = None if ctx is not None else resolve_devices(devices)
+    if devs and N >= 2 * MIN_SERIES_PER_DEVICE:
+        parts = min(len(devs), N // MIN_SERIES_PER_DEVICE)
+        lens = np.full(N, T, np.int64) if offsets is None else np.diff(offsets)
+        cuts = _cuts(lens, parts)
+        key = np.arange(N, dtype=np.int64) if key is None else key       # (the same streams whatever the split)
+        ex = None if extra is None else np.asarray(extra)
+
+        def one(c, a_, b_):
+            if offsets is None:
+                return calibrate(spec, ds_ns, y[a_:b_], horizon, levels, offsets=None, floor=None if fl is None else fl[a_:b_],
+                                 cap=None if cp is None else cp[a_:b_], extra=extra, series_key=key[a_:b_], ctx=c, **kw)
+            r0, r1 = int(offsets[a_]), int(offsets[b_])
+            return calibrate(spec, ds_ns[r0:r1], y[r0:r1], horizon, levels, offsets=offsets[a_:b_ + 1] - r0,
+                             floor=None if fl is None else fl[a_:b_], cap=None if cp is None else cp[a_:b_],
+                             extra=None if ex is None else ex[:, r0:r1], series_key=key[a_:b_], ctx=c, **kw)
+        blocks = [(c, int(a_), int(b_)) for c, a_, b_ in zip(_contexts(devs[:parts]), cuts[:-1], cuts[1:]) if b_ > a_]
+        pr = _run_blocks(one, blocks)
+        cv = None
+        if want_cv:
+            row_first = [0 if offsets is None else int(offsets[a_]) for _, a_, _ in blocks]
+            cv = _merge_cv(spec, [p.cv for p in pr], [a_ for _, a_, _ in blocks], cqr, row_first)
+        return _merge_calibrations(pr, cv)
+    ctx = ctx or get_context()
+    L = _lib.load()
+    cs = spec.to_c()
+    ex = None
+    if spec.extra:
+        ex = np.ascontiguousarray(extra, dtype=np.float64)
+        if ex.shape != (len(spec.extra), len(ds_ns)):
+            raise ValueError('extra must be [n_extra][len(ds)]')
+    tab, (q, n, st) = _alloc_calib(N, a.n_buckets, a.n_levels)
+    ca = _cv_args(horizon, period, initial, rolling_window)
+    out_p, cv = None, None
+    if want_cv:
+        plan = cv_plan(ds_ns, horizon, period, initial, rolling_window, offsets=offsets, N=N)
+        F, R, M = int(plan['n_folds'].sum()), int(plan['n_holdout'].sum()), int(plan['n_metric'].sum())
+        fout, farrs = _alloc_out(F, spec.theta_stride, F)
+        yhat = np.zeros(R)
+        lo = np.zeros(R) if cqr else None
+        hi = np.zeros(R) if cqr else None
+        hz = np.zeros(M, np.int64)
+        mse, rmse, mae, mape = np.zeros(M), np.zeros(M), np.zeros(M), np.zeros(M)
+        cov = np.zeros(M) if cqr else None
+        sst = np.zeros(N, np.int32)
+        out = _lib.TsfCvOut(fout, yhat.ctypes.data, _lib._ptr(lo), _lib._ptr(hi), hz.ctypes.data, mse.ctypes.data,
+                            rmse.ctypes.data, mae.ctypes.data, mape.ctypes.data, _lib._ptr(cov), sst.ctypes.data)
+        out_p = ctypes.byref(out)
+    rc = L.tsf_calibrate(ctx.handle, ctypes.byref(cs), N, T, _lib._ptr(offsets), ds_ns.ctypes.data, y.ctypes.data,
+                         _lib.y_dtype_code(y), _lib._ptr(fl), _lib._ptr(cp), _lib._ptr(ex), ctypes.byref(ca),
+                         _lib._ptr(key), int(uncertainty_samples) if cqr else 0, float(interval_width), int(seed),
+                         ctypes.byref(a), ctypes.byref(tab), out_p)
+    ctx.check(rc)
+    if want_cv:
+        fold_series = np.repeat(np.arange(N, dtype=np.int64), plan['n_folds'])
+        start = (np.zeros(N, np.int64) if offsets is None else offsets[:-1])[fold_series] + plan['hist_rows']
+        ridx = np.repeat(start - np.concatenate([[0], np.cumsum(plan['hold_rows'])[:-1]]), plan['hold_rows']) + np.arange(R)
+        row_fold = np.repeat(np.arange(F, dtype=np.int64), plan['hold_rows'])
+        y_rows = (y[fold_series[row_fold], ridx] if offsets is None else y[ridx]).astype(np.float64)
+        cv = CVResult(spec=spec, status=sst, n_folds=plan['n_folds'], n_holdout=plan['n_holdout'], n_metric=plan['n_metric'],
+                      fold_series=fold_series, cutoff=plan['cutoff'], hist_rows=plan['hist_rows'], hold_rows=plan['hold_rows'],
+                      fit=FitResult(spec, *farrs), row_fold=row_fold, row_index=ridx, ds=ds_ns[ridx], y=y_rows, yhat=yhat,
+                      yhat_lower=lo, yhat_upper=hi,
+                      metric_series=np.repeat(np.arange(N, dtype=np.int64), plan['n_metric']), horizon=hz, mse=mse,
+                      rmse=rmse, mae=mae, mape=mape, coverage=cov)
+    return Calibration(q, n, st, np.array(a.levels[:a.n_levels]), a.mode, a.horizon_ns, a.n_buckets, a.min_scores, cv)
+
+
+def model_origin_ns(grid, N=None):
+    """Each model's last history timestamp from its grid: start_ns + t_scale_ns ([N]; one shared grid repeats)."""
+    g = np.ascontiguousarray(grid, dtype=_lib.GRID_DTYPE)
+    o = g['start_ns'].astype(np.int64) + g['t_scale_ns'].astype(np.int64)
+    return np.ascontiguousarray(np.broadcast_to(o, (N,))) if N is not None and len(o) == 1 else o
+
+
+def predict_calibrated(spec, theta, y_scale, grid, ds_future_ns, cal, floor=None, cap=None, extra_future=None,
+                       series_key=None, uncertainty_samples=1000, seed=0, want_cell=False, ctx=None):
+    """predict, then the calibration table `cal` applied with each model's origin from its grid -> (yhat [N][H], lo, hi
+    [N][L][H][, cell]).  An 'abs' table needs the point forecast only; a 'cqr' table first takes the model's own bounds at
+    each level's tail pair from predict_quantiles (series_key / uncertainty_samples / seed: its arguments).  yhat is
+    predict's bit for bit."""
+    N = len(theta)
+    lw = up = None
+    if cal.mode == _lib.CALIB_CQR:
+        L = len(cal.levels)
+        pq = predict_quantiles(spec, theta, y_scale, grid, ds_future_ns, cv_interval_levels(cal.levels), floor=floor, cap=cap,
+                               extra_future=extra_future, series_key=series_key, uncertainty_samples=uncertainty_samples,
+                               seed=seed, ctx=ctx)
+        yhat, lw, up = pq.yhat, np.ascontiguousarray(pq.q[:, :L]), np.ascontiguousarray(pq.q[:, L:])
+    else:
+        yhat = predict(spec, theta, y_scale, grid, ds_future_ns, floor=floor, cap=cap, extra_future=extra_future, ctx=ctx)
+    res = cal.apply(yhat, ds_future_ns, model_origin_ns(grid, N), lower=lw, upper=up, want_cell=want_cell, ctx=ctx)
+    return (yhat,) + tuple(res)

@@ -15,7 +15,7 @@ from datetime import datetime, timezone
 import numpy as np
 import pandas as pd
 
-from .. import features, forecaster as fc, panel as pk
+from .. import _lib, features, forecaster as fc, panel as pk
 
 FORECAST_COLUMNS = ['series_id', 'dim_id', 'ds', 'yhat']          # prophet_scorer.py:27-32
 SINK_PART_ROWS = 1 << 17           # rows per forecast CSV part (ProphetScorer.score)
@@ -51,10 +51,28 @@ def forecast_arrays(config):
     """The predict UDF on columns that never were a DataFrame: (series_id, dim_id, floor, cap, models) -> dict of the
     forecast frame's columns (series_id, dim_id int32; ds int64 ns; yhat int32; yhat_lower / yhat_upper when
     forecast.intervals; trend, trend_lower / trend_upper and the components' float64 columns when forecast.components;
-    yhat_q<..> per level of forecast.quantiles and yhat_cum_q<..> with forecast.cumulative, named by fc.quantile_columns),
+    yhat_q<..> per level of forecast.quantiles and yhat_cum_q<..> with forecast.cumulative, named by fc.quantile_columns;
+    yhat_lower_c<..> / yhat_upper_c<..> per level of the table forecast.calibration names, float64 like the quantile
+    columns, named by fc.calibrated_columns: the validator's io.calibration applied to the float64 point forecast,
+    joined on (series_id, dim_id), NaN for a model without a table row),
     `periods` rows per series, or None when there is nothing to forecast.  models: a list of blobs
     (None = no model) or the uint8 [n][L] buffer of a model column whose blobs share one length
     (panel.model_column_buffer: a parquet column as it lies in memory, no Python object per series)."""
+
+    table = []          # forecast.calibration, read at the first frame: [Calibration, {(series_id, dim_id): row}]
+
+    def calibration_of(sid, did):
+        """the rows of the calibration table for these models as a Calibration of their own (no row: no cell)"""
+        if not table:
+            cal, keys = fc.Calibration.from_frame(pd.read_parquet(config['forecast']['calibration']))
+            table.extend([cal, {k: i for i, k in enumerate(zip(keys['series_id'].tolist(), keys['dim_id'].tolist()))}])
+        cal, where = table
+        at = np.array([where.get(k, -1) for k in zip(sid.tolist(), did.tolist())], dtype=np.int64)
+        have = at >= 0
+        q = np.where(have[:, None, None], cal.q[np.maximum(at, 0)], np.nan)
+        n = np.where(have[:, None, None], cal.n[np.maximum(at, 0)], 0).astype(np.int32)
+        st = np.where(have, cal.status[np.maximum(at, 0)], _lib.CALIB_NO_SCORES).astype(np.int32)
+        return fc.Calibration(q, n, st, cal.levels, cal.mode, cal.horizon, cal.n_buckets, cal.min_scores)
 
     def forecast_arrays_fn(sids, dids, floors, caps, blobs):
         if len(sids) == 0:
@@ -95,8 +113,23 @@ def forecast_arrays(config):
                                     want_int=True,      # :70-84
                                     devices=config.get('devices'))
             lap('predict')
-            iv = comps = quant = None
+            iv = comps = quant = calib = None
             fcfg = config.get('forecast') or {}
+            if fcfg.get('calibration'):
+                # opt-in: the conformal table of the validator (io.calibration) on the float64 point forecast; a CQR
+                # table first takes the model's own bounds at each level's tail pair, from the draws of the quantiles
+                cal = calibration_of(sids[idx], dids[idx])
+                exf = ex if (ex is None or fut.ndim == 2) else np.ascontiguousarray(ex[0])
+                lw = up = None
+                if cal.mode == _lib.CALIB_CQR:
+                    pq = fc.predict_quantiles(
+                        spec, theta, rec['y_scale'], grid, fut, fc.cv_interval_levels(cal.levels), floor=floor, cap=cap,
+                        extra_future=exf,
+                        series_key=(sids[idx].astype(np.int64) << 32) ^ (dids[idx].astype(np.int64) & 0xffffffff),
+                        uncertainty_samples=int(fcfg.get('uncertainty_samples', 1000)), seed=int(fcfg.get('seed', 0)))
+                    nl = len(cal.levels)
+                    lw, up = np.ascontiguousarray(pq.q[:, :nl]), np.ascontiguousarray(pq.q[:, nl:])
+                calib = (cal.levels,) + cal.apply(yhat, fut, fc.model_origin_ns(grid, len(idx)), lower=lw, upper=up)
             if fcfg.get('quantiles'):
                 # opt-in like the intervals below, from the same draws (same key, samples and seed: a level (1 -+ w) / 2
                 # is the interval bound at width w, include/tsf.h); forecast.cumulative adds the levels of the running
@@ -132,7 +165,7 @@ def forecast_arrays(config):
                       f"dim_id: {int(dids[idx[j]])}")                    # :77-79
             if fut.ndim == 1:
                 fut = np.broadcast_to(fut, (len(idx), periods))
-            pieces.append((idx, fut, yint, iv, comps, quant))
+            pieces.append((idx, fut, yint, iv, comps, quant, calib))
             lap('negative check')
         if not pieces:
             return None
@@ -164,6 +197,11 @@ def forecast_arrays(config):
                 if getattr(pieces[0][5], attr) is not None:
                     for i, name in enumerate(fc.quantile_columns(pieces[0][5].quantiles, prefix)):
                         res[name] = np.concatenate([getattr(p[5], attr)[:, i, :].reshape(-1) for p in pieces])
+        if pieces[0][6] is not None:
+            # forecast.calibration: one pair of columns per level of the table, the same table in every bucket
+            for k, prefix in ((1, 'yhat_lower_c'), (2, 'yhat_upper_c')):
+                for i, name in enumerate(fc.calibrated_columns(pieces[0][6][0], prefix)):
+                    res[name] = np.concatenate([p[6][k][:, i, :].reshape(-1) for p in pieces])
         lap('columns')
         lap.__exit__()
         return res

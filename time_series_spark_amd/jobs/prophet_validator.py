@@ -31,7 +31,15 @@ tsf_score_actuals, forecaster.score_cv): quantiles (a list of levels in [0, 1], 
 
 (crps and pinball_q*: the means over the series' holdout rows; coverage_q*: the share of them at or below the quantile;
 names as forecaster.quantile_columns), and the fold frame gains pit and crps.  Without `scores` every output is what it
-was before."""
+was before.
+
+An optional `calibrate` section turns the holdout errors into a conformal calibration table (include/tsf.h
+tsf_calibrate_rows, forecaster.calibrate_cv): levels (coverage targets strictly inside (0, 1), required), mode ('abs':
+|y - yhat|; 'cqr': max(lower - y, y - upper) around the model's own bounds at each level, from the draws cv.seed and
+cv.uncertainty_samples name), n_buckets (10 horizon buckets over cv.horizon), min_scores (20).  It writes io.calibration,
+Calibration.frame's rows for every series (series_id, dim_id, bucket, horizon_upto, n_c<..> and q_c<..> per level, the
+table's settings), which the scorer's forecast.calibration reads.  Without `calibrate` every output is what it was
+before."""
 import os
 import time
 
@@ -104,6 +112,25 @@ def score_settings(config):
     return dict(quantiles=levels, uncertainty_samples=n, seed=int(sc.get('seed', 0)))
 
 
+def calibrate_settings(config):
+    """The `calibrate` section -> dict(levels, mode, n_buckets, min_scores), or None without one."""
+    c = config.get('calibrate')
+    if c is None:
+        return None
+    c = dict(c)
+    unknown = sorted(set(c) - {'levels', 'mode', 'n_buckets', 'min_scores'})
+    if unknown:
+        raise ValueError('unknown calibrate keys %s (levels, mode, n_buckets, min_scores)' % unknown)
+    lv = c.get('levels')
+    if lv is None:
+        raise ValueError('calibrate.levels is required')
+    levels = [float(x) for x in (lv if isinstance(lv, (list, tuple)) else [lv])]
+    mode = str(c.get('mode', 'abs')).lower()
+    out = dict(levels=levels, mode=mode, n_buckets=int(c.get('n_buckets', 10)), min_scores=int(c.get('min_scores', 20)))
+    fc._calib_args(levels, mode, 1, out['n_buckets'], out['min_scores'])      # (ValueError for a bad setting)
+    return out
+
+
 def score_columns(levels):
     """Columns of the io.scores frame for the levels of the `scores` section."""
     return (['series_id', 'dim_id', 'n_obs', 'crps'] + fc.quantile_columns(levels, 'pinball_q')
@@ -144,9 +171,16 @@ def validate_panel(config, panel):
 
 def validate_scored(config, panel):
     """-> (metrics frame, fold frame, scores frame or None without a `scores` section) for a PackedPanel."""
+    return validate_calibrated(config, panel)[:3]
+
+
+def validate_calibrated(config, panel):
+    """-> (metrics frame, fold frame, scores frame or None, calibration frame or None without a `calibrate` section) for
+    a PackedPanel."""
     cvs = cv_settings(config)
     scs = score_settings(config)
-    scores = []
+    cas = calibrate_settings(config)
+    scores, tables = [], []
     floor = float(config['model']['floor'])
     sids, dids = _series_keys(panel)
     # the interval streams of a series are keyed by (series_id, dim_id): the same intervals whatever else is in the run
@@ -184,14 +218,24 @@ def validate_scored(config, panel):
                 for i, name in enumerate(fc.quantile_columns(scs['quantiles'], prefix)):
                     sf[name] = arr[good, i]
             scores.append(pd.DataFrame(sf, columns=score_columns(scs['quantiles'])))
+        if cas is not None:
+            cal = fc.calibrate_cv(cv, cas['levels'], mode=cas['mode'], n_buckets=cas['n_buckets'], min_scores=cas['min_scores'],
+                                  horizon=cvs['horizon'], interval_width=cvs['interval_width'] if cvs['intervals'] else None,
+                                  floor=np.full(len(members), floor), cap=cap_m, extra=ex, series_key=key[members],
+                                  uncertainty_samples=cvs['uncertainty_samples'], seed=cvs['seed'])
+            tables.append(cal.frame({'series_id': sids[members].astype('int32'), 'dim_id': dids[members].astype('int32')}))
         folds.append(pd.DataFrame(fr))
+    ca_frame = None
+    if cas is not None:
+        ca_frame = pd.concat(tables, ignore_index=True).sort_values(['series_id', 'dim_id', 'bucket'], kind='stable')
+        ca_frame = ca_frame.reset_index(drop=True)
     sc_frame = None
     if scs is not None:
         sc_frame = pd.concat(scores, ignore_index=True).sort_values(['series_id', 'dim_id'], kind='stable')
         sc_frame = sc_frame.reset_index(drop=True)
     m = pd.concat(metrics, ignore_index=True).sort_values(['series_id', 'dim_id', 'horizon'], kind='stable')
     f = pd.concat(folds, ignore_index=True).sort_values(['series_id', 'dim_id', 'cutoff', 'ds'], kind='stable')
-    return m.reset_index(drop=True), f.reset_index(drop=True), sc_frame
+    return m.reset_index(drop=True), f.reset_index(drop=True), sc_frame, ca_frame
 
 
 def tune_panel(config, panel):
@@ -230,14 +274,21 @@ def tune_panel(config, panel):
 
 class ProphetValidator(object):
     """Cross-validate the models the modeler would fit (config: the modeler's keys + `cv` + io.metrics [+ io.folds]
-    [+ `scores` + io.scores])."""
+    [+ `scores` + io.scores] [+ `calibrate` + io.calibration])."""
 
     def __init__(self, config):
         self.config = config
 
     @staticmethod
+    def check_outputs(config):
+        """The `calibrate` section's settings and its output path, refused before any input is read."""
+        if calibrate_settings(config) is not None and not config['io'].get('calibration'):
+            raise ValueError('the calibrate section needs io.calibration')
+
+    @staticmethod
     def validate(spark_session, config, return_frame=True):
         t0 = time.time()
+        ProphetValidator.check_outputs(config)
         mode = str(config['io'].get('input_mode', 'FAILFAST')).upper()
         sid, did, ds_ns, y = pm.read_model_input_dir(config['io']['input'], mode=mode)
         panel = pk.pack_rows(sid, did, ds_ns, y, key_dtypes=(np.int32, np.int32))
@@ -246,7 +297,7 @@ class ProphetValidator(object):
         pm.check_changepoints(pm._prophet_kwargs(config), panel)
         if config.get('scores') is not None and not config['io'].get('scores'):
             raise ValueError('the scores section needs io.scores')
-        metrics, folds, scores = validate_scored(config, panel)
+        metrics, folds, scores, calibration = validate_calibrated(config, panel)
         tuning = tune_panel(config, panel) if config.get('tune') is not None else None
         os.makedirs(config['io']['metrics'], exist_ok=True)
         metrics.to_parquet(os.path.join(config['io']['metrics'], 'part-00000.parquet'), index=False)
@@ -256,6 +307,9 @@ class ProphetValidator(object):
         if scores is not None:
             os.makedirs(config['io']['scores'], exist_ok=True)
             scores.to_parquet(os.path.join(config['io']['scores'], 'part-00000.parquet'), index=False)
+        if calibration is not None:
+            os.makedirs(config['io']['calibration'], exist_ok=True)
+            calibration.to_parquet(os.path.join(config['io']['calibration'], 'part-00000.parquet'), index=False)
         if tuning is not None:
             os.makedirs(config['io']['tuning'], exist_ok=True)
             tuning.to_parquet(os.path.join(config['io']['tuning'], 'part-00000.parquet'), index=False)
