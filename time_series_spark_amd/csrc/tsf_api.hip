@@ -48,7 +48,7 @@ struct tsf_ctx {
     size_t nb_ws_bytes;
     double *fut_tab;        // design table of a shared future grid (predict): [K][H]
     size_t fut_tab_bytes;
-    void *iv_ws;            // scratch of tsf_predict_intervals_dev (per-row pieces + samples of one chunk; grown on demand, <= ~0.5 GB)
+    void *iv_ws;            // sample scratch (ensure_iv_ws: per-row pieces + samples of one chunk of draw_chunks; grown on demand, <= ~0.5 GB)
     size_t iv_ws_bytes;
     void *comp_tab;         // tsf_predict_components: the component table ([TSF_MAX_COMP] masks, then [TSF_MAX_COMP] flags)
     int32_t *order_dev[2];  // tsf_set_cost_hints: series in order of decreasing expected cost (two buffers, used in
@@ -1371,6 +1371,105 @@ static int check_grids(tsf_ctx *ctx, const tsf_spec *spec, const tsf_grid_info *
     return 0;
 }
 
+// What a forecast is computed from: the arguments every predict entry shares.  Host pointers in a host entry, device
+// pointers behind it (ForecastUpload turns the first into the second) and in a `_dev` entry.
+struct ForecastIn {
+    int64_t N;
+    int32_t H;
+    const double *theta, *y_scale;
+    const tsf_grid_info *grid;
+    int32_t n_grids;
+    const int64_t *ds_future;
+    int32_t shared_future;
+    const double *floor_, *cap, *extra_future;
+    const int64_t *series_key;
+};
+
+// The opening checks of the predict entries.  outs_ok: the entry's other required pointers are there.  Nothing is
+// dereferenced: in a `_dev` entry the arrays are device memory (check_grids is for the host entries).
+static int check_forecast_in(tsf_ctx *ctx, const ForecastIn &f, bool outs_ok)
+{
+    if (f.N <= 0 || f.H <= 0) return fail(ctx, "N and H must be > 0");
+    if (!f.theta || !f.y_scale || !f.grid || !f.ds_future || !outs_ok) return fail(ctx, "NULL input");
+    if (f.n_grids != 1 && f.n_grids != f.N) return fail(ctx, "n_grids must be 1 or N");
+    return 0;
+}
+
+// A host entry's inputs in pooled device buffers.  It lives in the entry's scope: the buffers go back to the pool when
+// it does, after the entry has copied its results out.
+struct ForecastUpload {
+    DevBuf th, ys, grid, ds, fl, cap, ex, key;
+    ForecastIn dev;
+
+    // ds_on_device: h.ds_future is device memory already (the roll-up's calendar) and is used as it is
+    int upload(tsf_ctx *ctx, const tsf_spec *spec, const ForecastIn &h, bool ds_on_device = false)
+    {
+        if (spec->n_extra > 0 && !h.extra_future) return fail(ctx, "extra_future is NULL");
+        const size_t N = (size_t)h.N, nfut = h.shared_future ? (size_t)h.H : N * h.H;
+        dev = h;
+        if (int rc = put(ctx, &th, h.theta, 8 * N * tsf_theta_stride(spec), &dev.theta)) return rc;
+        if (int rc = put(ctx, &ys, h.y_scale, 8 * N, &dev.y_scale)) return rc;
+        if (int rc = put(ctx, &grid, h.grid, sizeof(tsf_grid_info) * h.n_grids, &dev.grid)) return rc;
+        if (!ds_on_device)
+            if (int rc = put(ctx, &ds, h.ds_future, 8 * nfut, &dev.ds_future)) return rc;
+        if (int rc = put(ctx, &fl, h.floor_, 8 * N, &dev.floor_)) return rc;
+        if (int rc = put(ctx, &cap, h.cap, 8 * N, &dev.cap)) return rc;
+        if (int rc = put(ctx, &key, h.series_key, 8 * N, &dev.series_key)) return rc;
+        if (spec->n_extra == 0) dev.extra_future = nullptr;
+        else if (int rc = put(ctx, &ex, h.extra_future, 8 * (size_t)spec->n_extra * nfut, &dev.extra_future)) return rc;
+        return 0;
+    }
+
+    // *d = the device copy of the `bytes` at src, or null where src is
+    template <class T>
+    static int put(tsf_ctx *ctx, DevBuf *b, const T *src, size_t bytes, const T **d)
+    {
+        *d = nullptr;
+        if (!src) return 0;
+        HIP_TRY(ctx, b->alloc(bytes));
+        HIP_TRY(ctx, hipMemcpy(b->p, src, bytes, hipMemcpyHostToDevice));
+        *d = b->as<T>();
+        return 0;
+    }
+};
+
+// What every forecast starts with on the device: the spec built and checked against the inputs, then sent to the
+// context's copy in stream order.
+static int forecast_prologue(tsf_ctx *ctx, const tsf_spec *spec, const ForecastIn &f, hipStream_t st, DevSpec *hs)
+{
+    int mode = 0;
+    if (int rc = build_devspec(ctx, spec, hs, &mode)) return rc;
+    if (hs->n_extra > 0 && !f.extra_future) return fail(ctx, "extra_future is NULL");
+    if (hs->growth == TSF_GROWTH_LOGISTIC && !f.cap) return fail(ctx, "logistic growth needs cap");
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_spec, hs, sizeof(*hs), hipMemcpyHostToDevice, st));
+    return 0;
+}
+
+// predict_kernel's arguments for the whole call (launch_predict narrows them to a chunk); the optional outputs
+// (yhat_int, trend_out, the per-row pieces) are the caller's to set.
+static PredictArgs predict_args(const tsf_ctx *ctx, const tsf_spec *spec, const ForecastIn &f, double *yhat)
+{
+    PredictArgs p;
+    memset(&p, 0, sizeof(p));
+    p.sp = ctx->d_spec; p.N = f.N; p.H = f.H; p.theta_stride = tsf_theta_stride(spec);
+    p.n_grids = f.n_grids; p.shared_future = f.shared_future; p.theta = f.theta; p.y_scale = f.y_scale;
+    p.grid = f.grid; p.ds_future = f.ds_future; p.floor_ = f.floor_; p.cap = f.cap;
+    p.extra_future = f.extra_future; p.yhat = yhat;
+    return p;
+}
+
+// The context's sample scratch (one cached block, like the fit workspace: grown on demand by a plain hipMalloc, which
+// waits for the device only on the call that grows it) is at least `need` bytes.
+static int ensure_iv_ws(tsf_ctx *ctx, size_t need)
+{
+    if (ctx->iv_ws_bytes < need) {
+        if (ctx->iv_ws) { HIP_TRY(ctx, hipFree(ctx->iv_ws)); ctx->iv_ws = nullptr; ctx->iv_ws_bytes = 0; }
+        HIP_TRY(ctx, hipMalloc(&ctx->iv_ws, need));
+        ctx->iv_ws_bytes = need;
+    }
+    return 0;
+}
+
 // predict_kernel on the series [n0, n0 + n) of the caller's arrays.  A shared future grid gets its
 // design table built first (once per call: tab_ready), in the context's own buffer.
 static int launch_predict(tsf_ctx *ctx, const DevSpec &hs, PredictArgs a, int64_t n0, int64_t n, bool *tab_ready,
@@ -1418,23 +1517,13 @@ extern "C" int tsf_predict_dev(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, in
 {
     if (!ctx) return -1;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (N <= 0 || H <= 0) return fail(ctx, "N and H must be > 0");
-    if (!theta || !y_scale || !grid || !ds_future || !yhat) return fail(ctx, "NULL input");
-    if (n_grids != 1 && n_grids != N) return fail(ctx, "n_grids must be 1 or N");
-    DevSpec hs;
-    int mode = 0;
-    int rc = build_devspec(ctx, spec, &hs, &mode);
-    if (rc) return rc;
-    if (hs.n_extra > 0 && !extra_future) return fail(ctx, "extra_future is NULL");
-    if (hs.growth == TSF_GROWTH_LOGISTIC && !cap) return fail(ctx, "logistic growth needs cap");
+    const ForecastIn f = {N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap, extra_future, nullptr};
+    if (int rc = check_forecast_in(ctx, f, yhat != nullptr)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_spec, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
-    PredictArgs a;
-    memset(&a, 0, sizeof(a));
-    a.sp = ctx->d_spec; a.N = N; a.H = H; a.theta_stride = tsf_theta_stride(spec);
-    a.n_grids = n_grids; a.shared_future = shared_future; a.theta = theta; a.y_scale = y_scale;
-    a.grid = grid; a.ds_future = ds_future; a.floor_ = floor_; a.cap = cap;
-    a.extra_future = extra_future; a.yhat = yhat; a.yhat_int = yhat_int;
+    DevSpec hs;
+    if (int rc = forecast_prologue(ctx, spec, f, st, &hs)) return rc;
+    PredictArgs a = predict_args(ctx, spec, f, yhat);
+    a.yhat_int = yhat_int;
     bool tab_ready = false;
     return launch_predict(ctx, hs, a, 0, N, &tab_ready, st);
 }
@@ -1447,42 +1536,135 @@ extern "C" int tsf_predict(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_
 {
     if (!ctx) return -1;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (N <= 0 || H <= 0) return fail(ctx, "N and H must be > 0");
-    if (!spec || !theta || !y_scale || !grid || !ds_future || !yhat) return fail(ctx, "NULL input");
-    if (n_grids != 1 && n_grids != N) return fail(ctx, "n_grids must be 1 or N");
+    const ForecastIn h = {N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap, extra_future, nullptr};
+    if (int rc = check_forecast_in(ctx, h, spec && yhat)) return rc;
     if (int rc = check_grids(ctx, spec, grid, n_grids)) return rc;
-    const int stride = tsf_theta_stride(spec);
-    const size_t nfut = shared_future ? (size_t)H : (size_t)N * H;
-    DevBuf d_th, d_ys, d_grid, d_ds, d_fl, d_cap, d_ex, d_yh, d_yi;
-    HIP_TRY(ctx, d_th.alloc(8 * (size_t)N * stride));
-    HIP_TRY(ctx, hipMemcpy(d_th.p, theta, 8 * (size_t)N * stride, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_ys.alloc(8 * N));
-    HIP_TRY(ctx, hipMemcpy(d_ys.p, y_scale, 8 * N, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_grid.alloc(sizeof(tsf_grid_info) * n_grids));
-    HIP_TRY(ctx, hipMemcpy(d_grid.p, grid, sizeof(tsf_grid_info) * n_grids, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_ds.alloc(8 * nfut));
-    HIP_TRY(ctx, hipMemcpy(d_ds.p, ds_future, 8 * nfut, hipMemcpyHostToDevice));
-    if (floor_) { HIP_TRY(ctx, d_fl.alloc(8 * N)); HIP_TRY(ctx, hipMemcpy(d_fl.p, floor_, 8 * N, hipMemcpyHostToDevice)); }
-    if (cap) { HIP_TRY(ctx, d_cap.alloc(8 * N)); HIP_TRY(ctx, hipMemcpy(d_cap.p, cap, 8 * N, hipMemcpyHostToDevice)); }
-    if (spec->n_extra > 0) {
-        if (!extra_future) return fail(ctx, "extra_future is NULL");
-        const size_t nb = 8 * (size_t)spec->n_extra * nfut;
-        HIP_TRY(ctx, d_ex.alloc(nb));
-        HIP_TRY(ctx, hipMemcpy(d_ex.p, extra_future, nb, hipMemcpyHostToDevice));
-    }
+    ForecastUpload up;
+    if (int rc = up.upload(ctx, spec, h)) return rc;
+    const ForecastIn &d = up.dev;
+    DevBuf d_yh, d_yi;
     HIP_TRY(ctx, d_yh.alloc(8 * (size_t)N * H));
     if (yhat_int) HIP_TRY(ctx, d_yi.alloc(4 * (size_t)N * H));
-    int rc = tsf_predict_dev(ctx, spec, N, H, d_th.as<double>(), d_ys.as<double>(),
-                             d_grid.as<tsf_grid_info>(), n_grids, d_ds.as<int64_t>(), shared_future,
-                             floor_ ? d_fl.as<double>() : nullptr, cap ? d_cap.as<double>() : nullptr,
-                             spec->n_extra > 0 ? d_ex.as<double>() : nullptr, d_yh.as<double>(),
-                             yhat_int ? d_yi.as<int32_t>() : nullptr, nullptr);
+    int rc = tsf_predict_dev(ctx, spec, N, H, d.theta, d.y_scale, d.grid, n_grids, d.ds_future, shared_future, d.floor_,
+                             d.cap, d.extra_future, d_yh.as<double>(), yhat_int ? d_yi.as<int32_t>() : nullptr, nullptr);
     if (rc) return rc;
     HIP_TRY(ctx, hipDeviceSynchronize());
     HIP_TRY(ctx, hipMemcpy(yhat, d_yh.p, 8 * (size_t)N * H, hipMemcpyDeviceToHost));
     if (yhat_int) HIP_TRY(ctx, hipMemcpy(yhat_int, d_yi.p, 4 * (size_t)N * H, hipMemcpyDeviceToHost));
     return 0;
 }
+
+// ---- the chunked draw -------------------------------------------------------------------------------
+
+// The one draw loop behind the intervals, the components' intervals, the quantiles, the scores and the roll-ups, on
+// device-resident inputs: per chunk of series launch_predict (yhat and the three per-row pieces), then
+// interval_sample_kernel, then `after(n0, nc, bufs)` on the same stream -- what the caller does with the chunk's draws
+// before the next chunk overwrites them.  Series are processed in chunks sized so that ALL scratch of a chunk -- the
+// per-row pieces of the point forecast (t, additive term, 1 + multiplicative term) and every sample buffer the call
+// needs (yhat always; the running sums with want_cum; the trend with want_trend) -- stays within 512 MB.  The scratch
+// is the context's cached block (ensure_iv_ws); the chunks of a call and successive calls reuse it in stream order, so
+// in the steady state nothing here waits for the device, as the `_dev` contract (include/tsf.h) promises.  (Round 3
+// used hipMallocAsync / hipFreeAsync here; see tsf_create.)  As with the workspace: one stream at a time per context.
+struct DrawBufs {
+    double *samp, *cum, *trend;     // [n_chunk][H][n_samples] each; cum / trend null where not asked for
+};
+
+// What a draw is asked for beyond the forecast's inputs.  yhat [N][H] is always written; trend_out [N][H] (the point
+// forecast's trend) where not null.
+struct DrawSpec {
+    int32_t n_samples;
+    uint64_t seed;
+    bool want_cum, want_trend;
+    double *yhat, *trend_out;
+};
+
+// series per chunk: n_buf sample buffers and the three per-row pieces of a chunk within 512 MB
+static int64_t draw_chunk_series(int64_t N, int32_t H, int32_t n_samples, size_t n_buf)
+{
+    const size_t per_series = (size_t)H * 8 * (3 + n_buf * (size_t)n_samples);
+    int64_t chunk = (int64_t)(((size_t)512 << 20) / per_series);
+    if (chunk < 1) chunk = 1;
+    if (chunk > N) chunk = N;
+    return chunk;
+}
+
+// bytes of scratch draw_chunks carves for chunks of `chunk` series
+static size_t draw_scratch_bytes(int64_t chunk, int32_t H, int32_t n_samples, size_t n_buf)
+{
+    return 8 * (size_t)chunk * H * (3 + n_buf * (size_t)n_samples);
+}
+
+// the sort width of the percentile / quantile / score kernels: the power of two at or above the sample count
+static int sort_width(int32_t n_samples)
+{
+    int NSP = 2;
+    while (NSP < n_samples) NSP <<= 1;
+    return NSP;
+}
+
+template <class After>
+static int draw_chunks(tsf_ctx *ctx, const tsf_spec *spec, const ForecastIn &f, const DrawSpec &d, hipStream_t st,
+                       After &&after)
+{
+    DevSpec hs;
+    if (int rc = forecast_prologue(ctx, spec, f, st, &hs)) return rc;
+    const int64_t N = f.N;
+    const int32_t H = f.H, n_samples = d.n_samples;
+    const size_t n_buf = 1 + (size_t)d.want_cum + (size_t)d.want_trend;
+    const int64_t chunk = draw_chunk_series(N, H, n_samples, n_buf);
+    const size_t nh = (size_t)chunk * H;
+    if (int rc = ensure_iv_ws(ctx, draw_scratch_bytes(chunk, H, n_samples, n_buf))) return rc;
+    double *d_t = (double *)ctx->iv_ws, *d_xa = d_t + nh, *d_opm = d_xa + nh, *d_samp = d_opm + nh;
+    double *d_next = d_samp + nh * n_samples;
+    double *d_cum = nullptr, *d_tsamp = nullptr;
+    if (d.want_cum) { d_cum = d_next; d_next += nh * n_samples; }
+    if (d.want_trend) d_tsamp = d_next;
+    PredictArgs p = predict_args(ctx, spec, f, d.yhat);
+    p.trend_out = d.trend_out;
+    p.t_out = d_t; p.xa_out = d_xa; p.opm_out = d_opm;
+    IntervalArgs a;
+    memset(&a, 0, sizeof(a));
+    a.sp = ctx->d_spec; a.H = H; a.theta_stride = tsf_theta_stride(spec); a.n_grids = f.n_grids; a.NS = n_samples;
+    a.theta = f.theta; a.y_scale = f.y_scale; a.grid = f.grid; a.floor_ = f.floor_; a.cap = f.cap;
+    a.series_key = f.series_key; a.seed = d.seed;
+    a.samples = d_samp; a.trend_samples = d_tsamp; a.cum_samples = d_cum;
+    const DrawBufs bufs = {d_samp, d_cum, d_tsamp};
+    bool tab_ready = false;
+    for (int64_t n0 = 0; n0 < N; n0 += chunk) {
+        const int64_t nc = (N - n0 < chunk) ? N - n0 : chunk;
+        // the point forecast of the chunk and its per-row pieces (chunk-local scratch: rows of series n0 + i at [i][H])
+        if (int prc = launch_predict(ctx, hs, p, n0, nc, &tab_ready, st)) return prc;
+        a.n0 = n0; a.n_chunk = nc;
+        a.t = d_t - (size_t)n0 * H; a.xa = d_xa - (size_t)n0 * H; a.opm = d_opm - (size_t)n0 * H;
+        hipLaunchKernelGGL(interval_sample_kernel, dim3((unsigned)nc, (unsigned)((n_samples + 255) / 256)),
+                           dim3(256), 0, st, a);
+        HIP_TRY(ctx, hipGetLastError());
+        if (int arc = after(n0, nc, bufs)) return arc;
+    }
+    return 0;
+}
+
+// interval_percentile_kernel on one sample buffer of a chunk: the two percentiles of `width` per row into lower / upper
+// [N][H].  (Of its IntervalArgs the kernel reads the buffer, H, NS, n0, the two fractions and the two outputs.)
+struct Percentiles {
+    int32_t H, n_samples;
+    double width;
+    hipStream_t st;
+
+    int launch(tsf_ctx *ctx, double *samples, int64_t n0, int64_t nc, double *lower, double *upper) const
+    {
+        const int NSP = sort_width(n_samples);
+        IntervalArgs a;
+        memset(&a, 0, sizeof(a));
+        a.samples = samples; a.H = H; a.NS = n_samples; a.n0 = n0; a.n_chunk = nc;
+        a.lo_frac = (1.0 - width) / 2.0; a.hi_frac = (1.0 + width) / 2.0;
+        a.lower = lower; a.upper = upper;
+        hipLaunchKernelGGL(interval_percentile_kernel, dim3((unsigned)(nc * H)), dim3(256), sizeof(double) * NSP, st, a,
+                           NSP);
+        HIP_TRY(ctx, hipGetLastError());
+        return 0;
+    }
+};
 
 // ---- uncertainty intervals ------------------------------------------------------------------------
 
@@ -1497,86 +1679,16 @@ extern "C" int tsf_predict_intervals_dev(tsf_ctx *ctx, const tsf_spec *spec, int
 {
     if (!ctx) return -1;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (N <= 0 || H <= 0) return fail(ctx, "N and H must be > 0");
-    if (!spec || !theta || !y_scale || !grid || !ds_future || !yhat || !yhat_lower || !yhat_upper) return fail(ctx, "NULL input");
-    if (n_grids != 1 && n_grids != N) return fail(ctx, "n_grids must be 1 or N");
+    const ForecastIn f = {N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap, extra_future, series_key};
+    if (int rc = check_forecast_in(ctx, f, spec && yhat && yhat_lower && yhat_upper)) return rc;
     if (n_samples < 2 || n_samples > 4096) return fail(ctx, "n_samples must be in [2, 4096]");
     if (!(interval_width > 0.0 && interval_width < 1.0)) return fail(ctx, "interval_width must be in (0, 1)");
-    DevSpec hs;
-    int mode = 0;
-    int rc = build_devspec(ctx, spec, &hs, &mode);
-    if (rc) return rc;
-    if (hs.n_extra > 0 && !extra_future) return fail(ctx, "extra_future is NULL");
-    if (hs.growth == TSF_GROWTH_LOGISTIC && !cap) return fail(ctx, "logistic growth needs cap");
     hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_spec, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
-    // Series are processed in chunks sized so that ALL scratch of a chunk -- the per-row pieces of the
-    // point forecast (t, additive term, 1 + multiplicative term) and the samples -- stays within
-    // 512 MB.  The scratch is ONE cached block of the context (like the fit workspace: grown on demand by a
-    // plain hipMalloc, which waits for the device only on the call that grows it); the chunks of a call and
-    // successive calls reuse it in stream order, so in the steady state nothing here waits for the device, as
-    // the `_dev` contract (include/tsf.h) promises.  (Round 3 used hipMallocAsync / hipFreeAsync here; see
-    // tsf_create.)  As with the workspace: one stream at a time per context.
-    const size_t per_series = (size_t)H * 8 * (3 + (size_t)n_samples);
-    int64_t chunk = (int64_t)(((size_t)512 << 20) / per_series);
-    if (chunk < 1) chunk = 1;
-    if (chunk > N) chunk = N;
-    const size_t nh = (size_t)chunk * H;
-    {
-        const size_t need = 8 * nh * (3 + (size_t)n_samples);
-        if (ctx->iv_ws_bytes < need) {
-            if (ctx->iv_ws) { HIP_TRY(ctx, hipFree(ctx->iv_ws)); ctx->iv_ws = nullptr; ctx->iv_ws_bytes = 0; }
-            HIP_TRY(ctx, hipMalloc(&ctx->iv_ws, need));
-            ctx->iv_ws_bytes = need;
-        }
-    }
-    double *d_t = (double *)ctx->iv_ws, *d_xa = d_t + nh, *d_opm = d_xa + nh, *d_samp = d_opm + nh;
-    auto release = [&]() {};
-#define HIP_TRY_REL(expr)                                                                     \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                               \
-            ctx->err = std::string(#expr) + ": " + hipGetErrorString(e_);                     \
-            release();                                                                        \
-            return -2;                                                                        \
-        }                                                                                     \
-    } while (0)
-    PredictArgs p;
-    memset(&p, 0, sizeof(p));
-    p.sp = ctx->d_spec; p.N = N; p.H = H; p.theta_stride = tsf_theta_stride(spec);
-    p.n_grids = n_grids; p.shared_future = shared_future; p.theta = theta; p.y_scale = y_scale;
-    p.grid = grid; p.ds_future = ds_future; p.floor_ = floor_; p.cap = cap;
-    p.extra_future = extra_future; p.yhat = yhat; p.yhat_int = nullptr;
-    p.t_out = d_t; p.xa_out = d_xa; p.opm_out = d_opm;
-    int NSP = 2;
-    while (NSP < n_samples) NSP <<= 1;
-    IntervalArgs a;
-    memset(&a, 0, sizeof(a));
-    a.sp = ctx->d_spec; a.H = H; a.theta_stride = tsf_theta_stride(spec); a.n_grids = n_grids; a.NS = n_samples;
-    a.theta = theta; a.y_scale = y_scale; a.grid = grid; a.floor_ = floor_; a.cap = cap;
-    a.series_key = series_key; a.seed = seed;
-    a.lo_frac = (1.0 - interval_width) / 2.0; a.hi_frac = (1.0 + interval_width) / 2.0;
-    a.samples = d_samp; a.lower = yhat_lower; a.upper = yhat_upper;
-    bool tab_ready = false;
-    for (int64_t n0 = 0; n0 < N; n0 += chunk) {
-        const int64_t nc = (N - n0 < chunk) ? N - n0 : chunk;
-        // the point forecast of the chunk and its per-row pieces (chunk-local scratch: rows of
-        // series n0 + i at [i][H])
-        {
-            const int prc = launch_predict(ctx, hs, p, n0, nc, &tab_ready, st);
-            if (prc) { release(); return prc; }
-        }
-        a.n0 = n0; a.n_chunk = nc;
-        a.t = d_t - (size_t)n0 * H; a.xa = d_xa - (size_t)n0 * H; a.opm = d_opm - (size_t)n0 * H;
-        hipLaunchKernelGGL(interval_sample_kernel, dim3((unsigned)a.n_chunk, (unsigned)((n_samples + 255) / 256)),
-                           dim3(256), 0, st, a);
-        HIP_TRY_REL(hipGetLastError());
-        hipLaunchKernelGGL(interval_percentile_kernel, dim3((unsigned)(a.n_chunk * H)), dim3(256),
-                           sizeof(double) * NSP, st, a, NSP);
-        HIP_TRY_REL(hipGetLastError());
-    }
-#undef HIP_TRY_REL
-    return 0;
+    const Percentiles pc = {H, n_samples, interval_width, st};
+    const DrawSpec d = {n_samples, seed, false, false, yhat, nullptr};
+    return draw_chunks(ctx, spec, f, d, st, [&](int64_t n0, int64_t nc, const DrawBufs &b) -> int {
+        return pc.launch(ctx, b.samp, n0, nc, yhat_lower, yhat_upper);
+    });
 }
 
 extern "C" int tsf_predict_intervals(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H,
@@ -1590,37 +1702,17 @@ extern "C" int tsf_predict_intervals(tsf_ctx *ctx, const tsf_spec *spec, int64_t
 {
     if (!ctx) return -1;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (N <= 0 || H <= 0) return fail(ctx, "N and H must be > 0");
-    if (!spec || !theta || !y_scale || !grid || !ds_future || !yhat || !yhat_lower || !yhat_upper) return fail(ctx, "NULL input");
-    if (n_grids != 1 && n_grids != N) return fail(ctx, "n_grids must be 1 or N");
+    const ForecastIn h = {N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap, extra_future, series_key};
+    if (int rc = check_forecast_in(ctx, h, spec && yhat && yhat_lower && yhat_upper)) return rc;
     if (int rc = check_grids(ctx, spec, grid, n_grids)) return rc;
-    const int stride = tsf_theta_stride(spec);
-    const size_t nfut = shared_future ? (size_t)H : (size_t)N * H;
-    DevBuf d_th, d_ys, d_grid, d_ds, d_fl, d_cap, d_ex, d_key, d_yh, d_lo, d_hi;
-    HIP_TRY(ctx, d_th.alloc(8 * (size_t)N * stride));
-    HIP_TRY(ctx, hipMemcpy(d_th.p, theta, 8 * (size_t)N * stride, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_ys.alloc(8 * N));
-    HIP_TRY(ctx, hipMemcpy(d_ys.p, y_scale, 8 * N, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_grid.alloc(sizeof(tsf_grid_info) * n_grids));
-    HIP_TRY(ctx, hipMemcpy(d_grid.p, grid, sizeof(tsf_grid_info) * n_grids, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_ds.alloc(8 * nfut));
-    HIP_TRY(ctx, hipMemcpy(d_ds.p, ds_future, 8 * nfut, hipMemcpyHostToDevice));
-    if (floor_) { HIP_TRY(ctx, d_fl.alloc(8 * N)); HIP_TRY(ctx, hipMemcpy(d_fl.p, floor_, 8 * N, hipMemcpyHostToDevice)); }
-    if (cap) { HIP_TRY(ctx, d_cap.alloc(8 * N)); HIP_TRY(ctx, hipMemcpy(d_cap.p, cap, 8 * N, hipMemcpyHostToDevice)); }
-    if (series_key) { HIP_TRY(ctx, d_key.alloc(8 * N)); HIP_TRY(ctx, hipMemcpy(d_key.p, series_key, 8 * N, hipMemcpyHostToDevice)); }
-    if (spec->n_extra > 0) {
-        if (!extra_future) return fail(ctx, "extra_future is NULL");
-        const size_t nb = 8 * (size_t)spec->n_extra * nfut;
-        HIP_TRY(ctx, d_ex.alloc(nb));
-        HIP_TRY(ctx, hipMemcpy(d_ex.p, extra_future, nb, hipMemcpyHostToDevice));
-    }
+    ForecastUpload up;
+    if (int rc = up.upload(ctx, spec, h)) return rc;
+    const ForecastIn &d = up.dev;
     const size_t nh = 8 * (size_t)N * H;
+    DevBuf d_yh, d_lo, d_hi;
     HIP_TRY(ctx, d_yh.alloc(nh)); HIP_TRY(ctx, d_lo.alloc(nh)); HIP_TRY(ctx, d_hi.alloc(nh));
-    int rc = tsf_predict_intervals_dev(ctx, spec, N, H, d_th.as<double>(), d_ys.as<double>(),
-                                       d_grid.as<tsf_grid_info>(), n_grids, d_ds.as<int64_t>(), shared_future,
-                                       floor_ ? d_fl.as<double>() : nullptr, cap ? d_cap.as<double>() : nullptr,
-                                       spec->n_extra > 0 ? d_ex.as<double>() : nullptr,
-                                       series_key ? d_key.as<int64_t>() : nullptr, n_samples, interval_width, seed,
+    int rc = tsf_predict_intervals_dev(ctx, spec, N, H, d.theta, d.y_scale, d.grid, n_grids, d.ds_future, shared_future,
+                                       d.floor_, d.cap, d.extra_future, d.series_key, n_samples, interval_width, seed,
                                        d_yh.as<double>(), d_lo.as<double>(), d_hi.as<double>(), nullptr);
     if (rc) return rc;
     HIP_TRY(ctx, hipDeviceSynchronize());
@@ -1633,10 +1725,10 @@ extern "C" int tsf_predict_intervals(tsf_ctx *ctx, const tsf_spec *spec, int64_t
 // ---- forecast components ------------------------------------------------------------------------------
 
 // What both component entries check before anything is launched: the component table (host data in both, like the
-// spec) against the spec's K, and the interval arguments.
+// spec) against the spec's K, and the interval arguments (iv_outs: the four interval outputs are all there).
 static int check_component_args(tsf_ctx *ctx, const tsf_spec *spec, int32_t n_comp, const uint64_t *comp_cols,
-                                const int32_t *comp_scaled, double *comp, int32_t n_samples, double interval_width,
-                                double *yhat_lower, double *yhat_upper, double *trend_lower, double *trend_upper)
+                                const int32_t *comp_scaled, const double *comp, int32_t n_samples,
+                                double interval_width, bool iv_outs)
 {
     if (n_comp < 0 || n_comp > TSF_MAX_COMP) return fail(ctx, "n_comp must be in [0, TSF_MAX_COMP]");
     if (n_comp > 0 && (!comp_cols || !comp_scaled || !comp)) return fail(ctx, "NULL component table or output");
@@ -1650,7 +1742,7 @@ static int check_component_args(tsf_ctx *ctx, const tsf_spec *spec, int32_t n_co
     if (n_samples != 0) {
         if (n_samples < 2 || n_samples > 4096) return fail(ctx, "n_samples must be 0 or in [2, 4096]");
         if (!(interval_width > 0.0 && interval_width < 1.0)) return fail(ctx, "interval_width must be in (0, 1)");
-        if (!yhat_lower || !yhat_upper || !trend_lower || !trend_upper) return fail(ctx, "NULL interval output");
+        if (!iv_outs) return fail(ctx, "NULL interval output");
     }
     return 0;
 }
@@ -1667,20 +1759,14 @@ extern "C" int tsf_predict_components_dev(tsf_ctx *ctx, const tsf_spec *spec, in
 {
     if (!ctx) return -1;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (N <= 0 || H <= 0) return fail(ctx, "N and H must be > 0");
-    if (!spec || !theta || !y_scale || !grid || !ds_future || !yhat || !trend) return fail(ctx, "NULL input");
-    if (n_grids != 1 && n_grids != N) return fail(ctx, "n_grids must be 1 or N");
+    const ForecastIn f = {N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap, extra_future, series_key};
+    if (int rc = check_forecast_in(ctx, f, spec && yhat && trend)) return rc;
     if (int rc = check_component_args(ctx, spec, n_comp, comp_cols, comp_scaled, comp, n_samples, interval_width,
-                                      yhat_lower, yhat_upper, trend_lower, trend_upper))
+                                      yhat_lower && yhat_upper && trend_lower && trend_upper))
         return rc;
-    DevSpec hs;
-    int mode = 0;
-    int rc = build_devspec(ctx, spec, &hs, &mode);
-    if (rc) return rc;
-    if (hs.n_extra > 0 && !extra_future) return fail(ctx, "extra_future is NULL");
-    if (hs.growth == TSF_GROWTH_LOGISTIC && !cap) return fail(ctx, "logistic growth needs cap");
     hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_spec, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
+    // the component table (host data): sent ahead of the predict launches, and so ahead of the prologue, which with
+    // samples is draw_chunks'; only a HIP error can come between
     const size_t tab_flags = sizeof(uint64_t) * TSF_MAX_COMP;
     if (n_comp > 0) {
         if (!ctx->comp_tab) HIP_TRY(ctx, hipMalloc(&ctx->comp_tab, tab_flags + sizeof(int32_t) * TSF_MAX_COMP));
@@ -1688,58 +1774,22 @@ extern "C" int tsf_predict_components_dev(tsf_ctx *ctx, const tsf_spec *spec, in
         HIP_TRY(ctx, hipMemcpyAsync((char *)ctx->comp_tab + tab_flags, comp_scaled, sizeof(int32_t) * n_comp,
                                     hipMemcpyHostToDevice, st));
     }
-    PredictArgs p;
-    memset(&p, 0, sizeof(p));
-    p.sp = ctx->d_spec; p.N = N; p.H = H; p.theta_stride = tsf_theta_stride(spec);
-    p.n_grids = n_grids; p.shared_future = shared_future; p.theta = theta; p.y_scale = y_scale;
-    p.grid = grid; p.ds_future = ds_future; p.floor_ = floor_; p.cap = cap;
-    p.extra_future = extra_future; p.yhat = yhat; p.yhat_int = nullptr; p.trend_out = trend;
-    bool tab_ready = false;
     if (n_samples == 0) {
+        DevSpec hs;
+        if (int rc = forecast_prologue(ctx, spec, f, st, &hs)) return rc;
+        PredictArgs p = predict_args(ctx, spec, f, yhat);
+        p.trend_out = trend;
+        bool tab_ready = false;
         if (int prc = launch_predict(ctx, hs, p, 0, N, &tab_ready, st)) return prc;
     } else {
-        // tsf_predict_intervals_dev's scheme with a second sample buffer (the sampled trend): a chunk's scratch,
-        // 3 + 2 n_samples values per row, stays within 512 MB of the same cached block
-        const size_t per_series = (size_t)H * 8 * (3 + 2 * (size_t)n_samples);
-        int64_t chunk = (int64_t)(((size_t)512 << 20) / per_series);
-        if (chunk < 1) chunk = 1;
-        if (chunk > N) chunk = N;
-        const size_t nh = (size_t)chunk * H;
-        const size_t need = 8 * nh * (3 + 2 * (size_t)n_samples);
-        if (ctx->iv_ws_bytes < need) {
-            if (ctx->iv_ws) { HIP_TRY(ctx, hipFree(ctx->iv_ws)); ctx->iv_ws = nullptr; ctx->iv_ws_bytes = 0; }
-            HIP_TRY(ctx, hipMalloc(&ctx->iv_ws, need));
-            ctx->iv_ws_bytes = need;
-        }
-        double *d_t = (double *)ctx->iv_ws, *d_xa = d_t + nh, *d_opm = d_xa + nh, *d_samp = d_opm + nh;
-        double *d_tsamp = d_samp + nh * n_samples;
-        p.t_out = d_t; p.xa_out = d_xa; p.opm_out = d_opm;
-        int NSP = 2;
-        while (NSP < n_samples) NSP <<= 1;
-        IntervalArgs a;
-        memset(&a, 0, sizeof(a));
-        a.sp = ctx->d_spec; a.H = H; a.theta_stride = tsf_theta_stride(spec); a.n_grids = n_grids; a.NS = n_samples;
-        a.theta = theta; a.y_scale = y_scale; a.grid = grid; a.floor_ = floor_; a.cap = cap;
-        a.series_key = series_key; a.seed = seed;
-        a.lo_frac = (1.0 - interval_width) / 2.0; a.hi_frac = (1.0 + interval_width) / 2.0;
-        a.samples = d_samp; a.trend_samples = d_tsamp; a.lower = yhat_lower; a.upper = yhat_upper;
-        IntervalArgs b = a;                 // the percentiles of the sampled trend
-        b.samples = d_tsamp; b.trend_samples = nullptr; b.lower = trend_lower; b.upper = trend_upper;
-        for (int64_t n0 = 0; n0 < N; n0 += chunk) {
-            const int64_t nc = (N - n0 < chunk) ? N - n0 : chunk;
-            if (int prc = launch_predict(ctx, hs, p, n0, nc, &tab_ready, st)) return prc;
-            a.n0 = b.n0 = n0; a.n_chunk = b.n_chunk = nc;
-            a.t = d_t - (size_t)n0 * H; a.xa = d_xa - (size_t)n0 * H; a.opm = d_opm - (size_t)n0 * H;
-            hipLaunchKernelGGL(interval_sample_kernel, dim3((unsigned)nc, (unsigned)((n_samples + 255) / 256)),
-                               dim3(256), 0, st, a);
-            HIP_TRY(ctx, hipGetLastError());
-            hipLaunchKernelGGL(interval_percentile_kernel, dim3((unsigned)(nc * H)), dim3(256),
-                               sizeof(double) * NSP, st, a, NSP);
-            HIP_TRY(ctx, hipGetLastError());
-            hipLaunchKernelGGL(interval_percentile_kernel, dim3((unsigned)(nc * H)), dim3(256),
-                               sizeof(double) * NSP, st, b, NSP);
-            HIP_TRY(ctx, hipGetLastError());
-        }
+        // a second sample buffer (the sampled trend), and the percentiles of both
+        const Percentiles pc = {H, n_samples, interval_width, st};
+        const DrawSpec d = {n_samples, seed, false, true, yhat, trend};
+        int rc = draw_chunks(ctx, spec, f, d, st, [&](int64_t n0, int64_t nc, const DrawBufs &b) -> int {
+            if (int prc = pc.launch(ctx, b.samp, n0, nc, yhat_lower, yhat_upper)) return prc;
+            return pc.launch(ctx, b.trend, n0, nc, trend_lower, trend_upper);
+        });
+        if (rc) return rc;
     }
     if (n_comp > 0) {
         // behind the predict launches: a shared future grid's design table is built
@@ -1769,44 +1819,26 @@ extern "C" int tsf_predict_components(tsf_ctx *ctx, const tsf_spec *spec, int64_
 {
     if (!ctx) return -1;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (N <= 0 || H <= 0) return fail(ctx, "N and H must be > 0");
-    if (!spec || !theta || !y_scale || !grid || !ds_future || !yhat || !trend) return fail(ctx, "NULL input");
-    if (n_grids != 1 && n_grids != N) return fail(ctx, "n_grids must be 1 or N");
+    const bool iv = n_samples != 0;
+    // (the keys matter to the draws only)
+    const ForecastIn h = {N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap, extra_future,
+                          iv ? series_key : nullptr};
+    if (int rc = check_forecast_in(ctx, h, spec && yhat && trend)) return rc;
     if (int rc = check_grids(ctx, spec, grid, n_grids)) return rc;
     if (int rc = check_component_args(ctx, spec, n_comp, comp_cols, comp_scaled, comp, n_samples, interval_width,
-                                      yhat_lower, yhat_upper, trend_lower, trend_upper))
+                                      yhat_lower && yhat_upper && trend_lower && trend_upper))
         return rc;
-    const bool iv = n_samples != 0;
-    const int stride = tsf_theta_stride(spec);
-    const size_t nfut = shared_future ? (size_t)H : (size_t)N * H;
-    DevBuf d_th, d_ys, d_grid, d_ds, d_fl, d_cap, d_ex, d_key, d_yh, d_tr, d_co, d_lo, d_hi, d_tlo, d_thi;
-    HIP_TRY(ctx, d_th.alloc(8 * (size_t)N * stride));
-    HIP_TRY(ctx, hipMemcpy(d_th.p, theta, 8 * (size_t)N * stride, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_ys.alloc(8 * N));
-    HIP_TRY(ctx, hipMemcpy(d_ys.p, y_scale, 8 * N, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_grid.alloc(sizeof(tsf_grid_info) * n_grids));
-    HIP_TRY(ctx, hipMemcpy(d_grid.p, grid, sizeof(tsf_grid_info) * n_grids, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_ds.alloc(8 * nfut));
-    HIP_TRY(ctx, hipMemcpy(d_ds.p, ds_future, 8 * nfut, hipMemcpyHostToDevice));
-    if (floor_) { HIP_TRY(ctx, d_fl.alloc(8 * N)); HIP_TRY(ctx, hipMemcpy(d_fl.p, floor_, 8 * N, hipMemcpyHostToDevice)); }
-    if (cap) { HIP_TRY(ctx, d_cap.alloc(8 * N)); HIP_TRY(ctx, hipMemcpy(d_cap.p, cap, 8 * N, hipMemcpyHostToDevice)); }
-    if (iv && series_key) { HIP_TRY(ctx, d_key.alloc(8 * N)); HIP_TRY(ctx, hipMemcpy(d_key.p, series_key, 8 * N, hipMemcpyHostToDevice)); }
-    if (spec->n_extra > 0) {
-        if (!extra_future) return fail(ctx, "extra_future is NULL");
-        const size_t nb = 8 * (size_t)spec->n_extra * nfut;
-        HIP_TRY(ctx, d_ex.alloc(nb));
-        HIP_TRY(ctx, hipMemcpy(d_ex.p, extra_future, nb, hipMemcpyHostToDevice));
-    }
+    ForecastUpload up;
+    if (int rc = up.upload(ctx, spec, h)) return rc;
+    const ForecastIn &d = up.dev;
+    DevBuf d_yh, d_tr, d_co, d_lo, d_hi, d_tlo, d_thi;
     const size_t nh = 8 * (size_t)N * H;
     HIP_TRY(ctx, d_yh.alloc(nh)); HIP_TRY(ctx, d_tr.alloc(nh));
     if (n_comp > 0) HIP_TRY(ctx, d_co.alloc(nh * n_comp));
     if (iv) { HIP_TRY(ctx, d_lo.alloc(nh)); HIP_TRY(ctx, d_hi.alloc(nh)); HIP_TRY(ctx, d_tlo.alloc(nh)); HIP_TRY(ctx, d_thi.alloc(nh)); }
-    int rc = tsf_predict_components_dev(ctx, spec, N, H, d_th.as<double>(), d_ys.as<double>(),
-                                        d_grid.as<tsf_grid_info>(), n_grids, d_ds.as<int64_t>(), shared_future,
-                                        floor_ ? d_fl.as<double>() : nullptr, cap ? d_cap.as<double>() : nullptr,
-                                        spec->n_extra > 0 ? d_ex.as<double>() : nullptr, n_comp, comp_cols, comp_scaled,
-                                        (iv && series_key) ? d_key.as<int64_t>() : nullptr, n_samples, interval_width,
-                                        seed, d_yh.as<double>(), d_tr.as<double>(),
+    int rc = tsf_predict_components_dev(ctx, spec, N, H, d.theta, d.y_scale, d.grid, n_grids, d.ds_future, shared_future,
+                                        d.floor_, d.cap, d.extra_future, n_comp, comp_cols, comp_scaled, d.series_key,
+                                        n_samples, interval_width, seed, d_yh.as<double>(), d_tr.as<double>(),
                                         n_comp > 0 ? d_co.as<double>() : nullptr,
                                         iv ? d_lo.as<double>() : nullptr, iv ? d_hi.as<double>() : nullptr,
                                         iv ? d_tlo.as<double>() : nullptr, iv ? d_thi.as<double>() : nullptr, nullptr);
@@ -1848,104 +1880,26 @@ static int check_quantile_args(tsf_ctx *ctx, int32_t n_samples, int32_t n_q, con
     return 0;
 }
 
-// The draw loop of tsf_predict_quantiles and tsf_rollup_add on device-resident inputs: per chunk of series
-// launch_predict (yhat and the three per-row pieces), then interval_sample_kernel, then `after(n0, nc, bufs)` on the
-// same stream -- what the caller does with the chunk's draws before the next chunk overwrites them.
-// tsf_predict_intervals_dev's scheme: a chunk's scratch -- the three per-row pieces and every sample buffer the call
-// needs (yhat always; the running sums with want_cum; the trend with want_trend) -- stays within 512 MB of the same
-// cached block.
-struct DrawBufs {
-    double *samp, *cum, *trend;     // [n_chunk][H][n_samples] each; cum / trend null where not asked for
+// What the quantile and score entries are asked for beyond the forecast's inputs: the draw and the levels (host data).
+struct QuantileCall {
+    int32_t n_samples;
+    uint64_t seed;
+    int32_t n_q;
+    const double *quantiles;
 };
-
-// series per chunk: n_buf sample buffers and the three per-row pieces of a chunk within 512 MB
-static int64_t draw_chunk_series(int64_t N, int32_t H, int32_t n_samples, size_t n_buf)
-{
-    const size_t per_series = (size_t)H * 8 * (3 + n_buf * (size_t)n_samples);
-    int64_t chunk = (int64_t)(((size_t)512 << 20) / per_series);
-    if (chunk < 1) chunk = 1;
-    if (chunk > N) chunk = N;
-    return chunk;
-}
-
-// bytes of scratch draw_chunks carves for chunks of `chunk` series
-static size_t draw_scratch_bytes(int64_t chunk, int32_t H, int32_t n_samples, size_t n_buf)
-{
-    return 8 * (size_t)chunk * H * (3 + n_buf * (size_t)n_samples);
-}
-
-template <class After>
-static int draw_chunks(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H, const double *theta,
-                       const double *y_scale, const tsf_grid_info *grid, int32_t n_grids, const int64_t *ds_future,
-                       int32_t shared_future, const double *floor_, const double *cap, const double *extra_future,
-                       const int64_t *series_key, int32_t n_samples, uint64_t seed, bool want_cum, bool want_trend,
-                       double *yhat, hipStream_t st, After &&after)
-{
-    DevSpec hs;
-    int mode = 0;
-    int rc = build_devspec(ctx, spec, &hs, &mode);
-    if (rc) return rc;
-    if (hs.n_extra > 0 && !extra_future) return fail(ctx, "extra_future is NULL");
-    if (hs.growth == TSF_GROWTH_LOGISTIC && !cap) return fail(ctx, "logistic growth needs cap");
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_spec, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
-    const size_t n_buf = 1 + (size_t)want_cum + (size_t)want_trend;
-    const int64_t chunk = draw_chunk_series(N, H, n_samples, n_buf);
-    const size_t nh = (size_t)chunk * H;
-    const size_t need = draw_scratch_bytes(chunk, H, n_samples, n_buf);
-    if (ctx->iv_ws_bytes < need) {
-        if (ctx->iv_ws) { HIP_TRY(ctx, hipFree(ctx->iv_ws)); ctx->iv_ws = nullptr; ctx->iv_ws_bytes = 0; }
-        HIP_TRY(ctx, hipMalloc(&ctx->iv_ws, need));
-        ctx->iv_ws_bytes = need;
-    }
-    double *d_t = (double *)ctx->iv_ws, *d_xa = d_t + nh, *d_opm = d_xa + nh, *d_samp = d_opm + nh;
-    double *d_next = d_samp + nh * n_samples;
-    double *d_cum = nullptr, *d_tsamp = nullptr;
-    if (want_cum) { d_cum = d_next; d_next += nh * n_samples; }
-    if (want_trend) d_tsamp = d_next;
-    PredictArgs p;
-    memset(&p, 0, sizeof(p));
-    p.sp = ctx->d_spec; p.N = N; p.H = H; p.theta_stride = tsf_theta_stride(spec);
-    p.n_grids = n_grids; p.shared_future = shared_future; p.theta = theta; p.y_scale = y_scale;
-    p.grid = grid; p.ds_future = ds_future; p.floor_ = floor_; p.cap = cap;
-    p.extra_future = extra_future; p.yhat = yhat; p.yhat_int = nullptr;
-    p.t_out = d_t; p.xa_out = d_xa; p.opm_out = d_opm;
-    IntervalArgs a;
-    memset(&a, 0, sizeof(a));
-    a.sp = ctx->d_spec; a.H = H; a.theta_stride = tsf_theta_stride(spec); a.n_grids = n_grids; a.NS = n_samples;
-    a.theta = theta; a.y_scale = y_scale; a.grid = grid; a.floor_ = floor_; a.cap = cap;
-    a.series_key = series_key; a.seed = seed;
-    a.samples = d_samp; a.trend_samples = d_tsamp; a.cum_samples = d_cum;
-    const DrawBufs bufs = {d_samp, d_cum, d_tsamp};
-    bool tab_ready = false;
-    for (int64_t n0 = 0; n0 < N; n0 += chunk) {
-        const int64_t nc = (N - n0 < chunk) ? N - n0 : chunk;
-        if (int prc = launch_predict(ctx, hs, p, n0, nc, &tab_ready, st)) return prc;
-        a.n0 = n0; a.n_chunk = nc;
-        a.t = d_t - (size_t)n0 * H; a.xa = d_xa - (size_t)n0 * H; a.opm = d_opm - (size_t)n0 * H;
-        hipLaunchKernelGGL(interval_sample_kernel, dim3((unsigned)nc, (unsigned)((n_samples + 255) / 256)),
-                           dim3(256), 0, st, a);
-        HIP_TRY(ctx, hipGetLastError());
-        if (int arc = after(n0, nc, bufs)) return arc;
-    }
-    return 0;
-}
 
 // The work of both quantile entries on device-resident inputs.  The quantile outputs of `o` are device pointers; its
 // two sample outputs are copied out of the chunk's scratch in stream order with `kind` (device to device for the _dev
 // entry, device to host for the host entry, which therefore never holds N * H * n_samples values on the device).
-static int predict_quantiles_run(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H, const double *theta,
-                                 const double *y_scale, const tsf_grid_info *grid, int32_t n_grids,
-                                 const int64_t *ds_future, int32_t shared_future, const double *floor_,
-                                 const double *cap, const double *extra_future, const int64_t *series_key,
-                                 int32_t n_samples, uint64_t seed, int32_t n_q, const double *quantiles,
+static int predict_quantiles_run(tsf_ctx *ctx, const tsf_spec *spec, const ForecastIn &f, const QuantileCall &c,
                                  const tsf_quantile_out &o, hipMemcpyKind kind, hipStream_t st)
 {
-    int NSP = 2;
-    while (NSP < n_samples) NSP <<= 1;
+    const int32_t H = f.H, n_samples = c.n_samples;
+    const int NSP = sort_width(n_samples);
     QuantileArgs q;
     memset(&q, 0, sizeof(q));
-    q.H = H; q.NS = n_samples; q.n_q = n_q;
-    for (int32_t i = 0; i < n_q; ++i) q.level[i] = quantiles[i];
+    q.H = H; q.NS = n_samples; q.n_q = c.n_q;
+    for (int32_t i = 0; i < c.n_q; ++i) q.level[i] = c.quantiles[i];
     auto after = [&](int64_t n0, int64_t nc, const DrawBufs &b) -> int {
         const struct { const double *src; double *dst; } sorts[3] = {{b.samp, o.q}, {b.cum, o.cum_q}, {b.trend, o.trend_q}};
         for (const auto &so : sorts) {
@@ -1960,9 +1914,8 @@ static int predict_quantiles_run(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, 
         if (o.trend_samples) HIP_TRY(ctx, hipMemcpyAsync(o.trend_samples + off, b.trend, nb, kind, st));
         return 0;
     };
-    return draw_chunks(ctx, spec, N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap,
-                       extra_future, series_key, n_samples, seed, o.cum_q != nullptr, o.trend_q || o.trend_samples,
-                       o.yhat, st, after);
+    const DrawSpec d = {n_samples, c.seed, o.cum_q != nullptr, o.trend_q || o.trend_samples, o.yhat, nullptr};
+    return draw_chunks(ctx, spec, f, d, st, after);
 }
 
 extern "C" int tsf_predict_quantiles_dev(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H,
@@ -1974,13 +1927,11 @@ extern "C" int tsf_predict_quantiles_dev(tsf_ctx *ctx, const tsf_spec *spec, int
 {
     if (!ctx) return -1;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (N <= 0 || H <= 0) return fail(ctx, "N and H must be > 0");
-    if (!spec || !theta || !y_scale || !grid || !ds_future) return fail(ctx, "NULL input");
-    if (n_grids != 1 && n_grids != N) return fail(ctx, "n_grids must be 1 or N");
+    const ForecastIn f = {N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap, extra_future, series_key};
+    if (int rc = check_forecast_in(ctx, f, spec != nullptr)) return rc;
     if (int rc = check_quantile_args(ctx, n_samples, n_q, quantiles, out)) return rc;
-    return predict_quantiles_run(ctx, spec, N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap,
-                                 extra_future, series_key, n_samples, seed, n_q, quantiles, *out,
-                                 hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    return predict_quantiles_run(ctx, spec, f, {n_samples, seed, n_q, quantiles}, *out, hipMemcpyDeviceToDevice,
+                                 (hipStream_t)stream);
 }
 
 extern "C" int tsf_predict_quantiles(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H,
@@ -1992,31 +1943,13 @@ extern "C" int tsf_predict_quantiles(tsf_ctx *ctx, const tsf_spec *spec, int64_t
 {
     if (!ctx) return -1;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (N <= 0 || H <= 0) return fail(ctx, "N and H must be > 0");
-    if (!spec || !theta || !y_scale || !grid || !ds_future) return fail(ctx, "NULL input");
-    if (n_grids != 1 && n_grids != N) return fail(ctx, "n_grids must be 1 or N");
+    const ForecastIn h = {N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap, extra_future, series_key};
+    if (int rc = check_forecast_in(ctx, h, spec != nullptr)) return rc;
     if (int rc = check_grids(ctx, spec, grid, n_grids)) return rc;
     if (int rc = check_quantile_args(ctx, n_samples, n_q, quantiles, out)) return rc;
-    if (spec->n_extra > 0 && !extra_future) return fail(ctx, "extra_future is NULL");
-    const int stride = tsf_theta_stride(spec);
-    const size_t nfut = shared_future ? (size_t)H : (size_t)N * H;
-    DevBuf d_th, d_ys, d_grid, d_ds, d_fl, d_cap, d_ex, d_key, d_yh, d_q, d_cq, d_tq;
-    HIP_TRY(ctx, d_th.alloc(8 * (size_t)N * stride));
-    HIP_TRY(ctx, hipMemcpy(d_th.p, theta, 8 * (size_t)N * stride, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_ys.alloc(8 * N));
-    HIP_TRY(ctx, hipMemcpy(d_ys.p, y_scale, 8 * N, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_grid.alloc(sizeof(tsf_grid_info) * n_grids));
-    HIP_TRY(ctx, hipMemcpy(d_grid.p, grid, sizeof(tsf_grid_info) * n_grids, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_ds.alloc(8 * nfut));
-    HIP_TRY(ctx, hipMemcpy(d_ds.p, ds_future, 8 * nfut, hipMemcpyHostToDevice));
-    if (floor_) { HIP_TRY(ctx, d_fl.alloc(8 * N)); HIP_TRY(ctx, hipMemcpy(d_fl.p, floor_, 8 * N, hipMemcpyHostToDevice)); }
-    if (cap) { HIP_TRY(ctx, d_cap.alloc(8 * N)); HIP_TRY(ctx, hipMemcpy(d_cap.p, cap, 8 * N, hipMemcpyHostToDevice)); }
-    if (series_key) { HIP_TRY(ctx, d_key.alloc(8 * N)); HIP_TRY(ctx, hipMemcpy(d_key.p, series_key, 8 * N, hipMemcpyHostToDevice)); }
-    if (spec->n_extra > 0) {
-        const size_t nb = 8 * (size_t)spec->n_extra * nfut;
-        HIP_TRY(ctx, d_ex.alloc(nb));
-        HIP_TRY(ctx, hipMemcpy(d_ex.p, extra_future, nb, hipMemcpyHostToDevice));
-    }
+    ForecastUpload up;
+    if (int rc = up.upload(ctx, spec, h)) return rc;
+    DevBuf d_yh, d_q, d_cq, d_tq;
     const size_t nh = 8 * (size_t)N * H, nqh = nh * (size_t)n_q;
     HIP_TRY(ctx, d_yh.alloc(nh));
     if (out->q) HIP_TRY(ctx, d_q.alloc(nqh));
@@ -2028,11 +1961,7 @@ extern "C" int tsf_predict_quantiles(tsf_ctx *ctx, const tsf_spec *spec, int64_t
     o.cum_q = out->cum_q ? d_cq.as<double>() : nullptr;
     o.trend_q = out->trend_q ? d_tq.as<double>() : nullptr;
     o.samples = out->samples; o.trend_samples = out->trend_samples;      // host: filled chunk by chunk
-    int rc = predict_quantiles_run(ctx, spec, N, H, d_th.as<double>(), d_ys.as<double>(), d_grid.as<tsf_grid_info>(),
-                                   n_grids, d_ds.as<int64_t>(), shared_future, floor_ ? d_fl.as<double>() : nullptr,
-                                   cap ? d_cap.as<double>() : nullptr, spec->n_extra > 0 ? d_ex.as<double>() : nullptr,
-                                   series_key ? d_key.as<int64_t>() : nullptr, n_samples, seed, n_q, quantiles, o,
-                                   hipMemcpyDeviceToHost, nullptr);
+    int rc = predict_quantiles_run(ctx, spec, up.dev, {n_samples, seed, n_q, quantiles}, o, hipMemcpyDeviceToHost, nullptr);
     if (rc) return rc;
     HIP_TRY(ctx, hipDeviceSynchronize());
     HIP_TRY(ctx, hipMemcpy(out->yhat, d_yh.p, nh, hipMemcpyDeviceToHost));
@@ -2071,32 +2000,25 @@ static int check_score_args(tsf_ctx *ctx, int32_t n_samples, int32_t n_q, const 
 
 // The work of both score entries on device-resident inputs; every pointer of `o` and y_obs are device pointers.  The
 // per-row arrays the aggregates read (crps for mean_crps, pinball for mean_pinball, q for coverage) are the caller's
-// where given and otherwise lie in the context's sample scratch behind the chunk draw_chunks carves from it.
-static int score_actuals_run(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H, const double *theta,
-                             const double *y_scale, const tsf_grid_info *grid, int32_t n_grids,
-                             const int64_t *ds_future, int32_t shared_future, const double *floor_, const double *cap,
-                             const double *extra_future, const int64_t *series_key, int32_t n_samples, uint64_t seed,
-                             const double *y_obs, int32_t n_q, const double *quantiles, const tsf_score_out &o,
-                             hipStream_t st)
+// where given and otherwise lie in the context's sample scratch behind the chunk draw_chunks carves from it: the block
+// is sized for both here, so draw_chunks never reallocates under them.
+static int score_actuals_run(tsf_ctx *ctx, const tsf_spec *spec, const ForecastIn &f, const QuantileCall &c,
+                             const double *y_obs, const tsf_score_out &o, hipStream_t st)
 {
-    int NSP = 2;
-    while (NSP < n_samples) NSP <<= 1;
+    const int64_t N = f.N;
+    const int32_t H = f.H, n_samples = c.n_samples, n_q = c.n_q;
+    const int NSP = sort_width(n_samples);
     const size_t nh = (size_t)N * H, nqh = nh * (size_t)n_q;
     ScoreArgs a;
     memset(&a, 0, sizeof(a));
     a.y = y_obs; a.pit = o.pit; a.crps = o.crps; a.q = o.q; a.pinball = o.pinball;
     a.H = H; a.NS = n_samples; a.n_q = n_q;
-    for (int32_t i = 0; i < n_q; ++i) a.level[i] = quantiles[i];
+    for (int32_t i = 0; i < n_q; ++i) a.level[i] = c.quantiles[i];
     const size_t extra = (o.mean_crps && !o.crps ? nh : 0) + (o.mean_pinball && !o.pinball ? nqh : 0) +
                          (o.coverage && !o.q ? nqh : 0);
     if (extra) {
         const size_t draw = draw_scratch_bytes(draw_chunk_series(N, H, n_samples, 1), H, n_samples, 1);
-        const size_t need = draw + 8 * extra;
-        if (ctx->iv_ws_bytes < need) {
-            if (ctx->iv_ws) { HIP_TRY(ctx, hipFree(ctx->iv_ws)); ctx->iv_ws = nullptr; ctx->iv_ws_bytes = 0; }
-            HIP_TRY(ctx, hipMalloc(&ctx->iv_ws, need));
-            ctx->iv_ws_bytes = need;
-        }
+        if (int rc = ensure_iv_ws(ctx, draw + 8 * extra)) return rc;
         double *d_next = (double *)((char *)ctx->iv_ws + draw);
         if (o.mean_crps && !o.crps) { a.crps = d_next; d_next += nh; }
         if (o.mean_pinball && !o.pinball) { a.pinball = d_next; d_next += nqh; }
@@ -2109,13 +2031,12 @@ static int score_actuals_run(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int3
             HIP_TRY(ctx, hipGetLastError());
             return 0;
         };
-        if (int rc = draw_chunks(ctx, spec, N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap,
-                                 extra_future, series_key, n_samples, seed, false, false, o.yhat, st, after))
-            return rc;
+        const DrawSpec d = {n_samples, c.seed, false, false, o.yhat, nullptr};
+        if (int rc = draw_chunks(ctx, spec, f, d, st, after)) return rc;
     } else {
         // n_obs alone: no draw is needed, only yhat
-        if (int rc = tsf_predict_dev(ctx, spec, N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_,
-                                     cap, extra_future, o.yhat, nullptr, st))
+        if (int rc = tsf_predict_dev(ctx, spec, N, H, f.theta, f.y_scale, f.grid, f.n_grids, f.ds_future, f.shared_future,
+                                     f.floor_, f.cap, f.extra_future, o.yhat, nullptr, st))
             return rc;
     }
     if (o.n_obs || o.mean_crps || o.mean_pinball || o.coverage) {
@@ -2143,10 +2064,9 @@ extern "C" int tsf_score_actuals_dev(tsf_ctx *ctx, const tsf_spec *spec, int64_t
     if (N < 0 || H <= 0) return fail(ctx, "N must be >= 0 and H > 0");
     if (int rc = check_score_args(ctx, n_samples, n_q, quantiles, y_obs, out)) return rc;
     if (N == 0) return 0;
-    if (!spec || !theta || !y_scale || !grid || !ds_future) return fail(ctx, "NULL input");
-    if (n_grids != 1 && n_grids != N) return fail(ctx, "n_grids must be 1 or N");
-    return score_actuals_run(ctx, spec, N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap,
-                             extra_future, series_key, n_samples, seed, y_obs, n_q, quantiles, *out, (hipStream_t)stream);
+    const ForecastIn f = {N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap, extra_future, series_key};
+    if (int rc = check_forecast_in(ctx, f, spec != nullptr)) return rc;
+    return score_actuals_run(ctx, spec, f, {n_samples, seed, n_q, quantiles}, y_obs, *out, (hipStream_t)stream);
 }
 
 extern "C" int tsf_score_actuals(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H, const double *theta,
@@ -2158,14 +2078,14 @@ extern "C" int tsf_score_actuals(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, 
     if (!ctx) return -1;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (N < 0 || H <= 0) return fail(ctx, "N must be >= 0 and H > 0");
+    const ForecastIn h = {N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap, extra_future, series_key};
     if (N > 0) {
-        if (!spec || !theta || !y_scale || !grid || !ds_future) return fail(ctx, "NULL input");
-        if (n_grids != 1 && n_grids != N) return fail(ctx, "n_grids must be 1 or N");
+        if (int rc = check_forecast_in(ctx, h, spec != nullptr)) return rc;
         if (int rc = check_grids(ctx, spec, grid, n_grids)) return rc;
     }
     if (int rc = check_score_args(ctx, n_samples, n_q, quantiles, y_obs, out)) return rc;
     if (N == 0) return 0;
-    if (spec->n_extra > 0 && !extra_future) return fail(ctx, "extra_future is NULL");
+    if (spec->n_extra > 0 && !extra_future) return fail(ctx, "extra_future is NULL");     // (ahead of the scan of y_obs)
     const size_t nhn = (size_t)N * H;
     for (size_t i = 0; i < nhn; ++i)
         if (std::isinf(y_obs[i])) {
@@ -2174,25 +2094,9 @@ extern "C" int tsf_score_actuals(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, 
                      (long long)(i / H), (int)(i % H));
             return fail(ctx, msg);
         }
-    const int stride = tsf_theta_stride(spec);
-    const size_t nfut = shared_future ? (size_t)H : (size_t)N * H;
-    DevBuf d_th, d_ys, d_grid, d_ds, d_fl, d_cap, d_ex, d_key, d_y, d_yh, d_pit, d_crps, d_q, d_pb, d_no, d_mc, d_mp, d_cv;
-    HIP_TRY(ctx, d_th.alloc(8 * (size_t)N * stride));
-    HIP_TRY(ctx, hipMemcpy(d_th.p, theta, 8 * (size_t)N * stride, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_ys.alloc(8 * N));
-    HIP_TRY(ctx, hipMemcpy(d_ys.p, y_scale, 8 * N, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_grid.alloc(sizeof(tsf_grid_info) * n_grids));
-    HIP_TRY(ctx, hipMemcpy(d_grid.p, grid, sizeof(tsf_grid_info) * n_grids, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_ds.alloc(8 * nfut));
-    HIP_TRY(ctx, hipMemcpy(d_ds.p, ds_future, 8 * nfut, hipMemcpyHostToDevice));
-    if (floor_) { HIP_TRY(ctx, d_fl.alloc(8 * N)); HIP_TRY(ctx, hipMemcpy(d_fl.p, floor_, 8 * N, hipMemcpyHostToDevice)); }
-    if (cap) { HIP_TRY(ctx, d_cap.alloc(8 * N)); HIP_TRY(ctx, hipMemcpy(d_cap.p, cap, 8 * N, hipMemcpyHostToDevice)); }
-    if (series_key) { HIP_TRY(ctx, d_key.alloc(8 * N)); HIP_TRY(ctx, hipMemcpy(d_key.p, series_key, 8 * N, hipMemcpyHostToDevice)); }
-    if (spec->n_extra > 0) {
-        const size_t nb = 8 * (size_t)spec->n_extra * nfut;
-        HIP_TRY(ctx, d_ex.alloc(nb));
-        HIP_TRY(ctx, hipMemcpy(d_ex.p, extra_future, nb, hipMemcpyHostToDevice));
-    }
+    ForecastUpload up;
+    if (int rc = up.upload(ctx, spec, h)) return rc;
+    DevBuf d_y, d_yh, d_pit, d_crps, d_q, d_pb, d_no, d_mc, d_mp, d_cv;
     const size_t nh = 8 * nhn, nqh = nh * (size_t)n_q, nq = 8 * (size_t)N * n_q;
     HIP_TRY(ctx, d_y.alloc(nh));
     HIP_TRY(ctx, hipMemcpy(d_y.p, y_obs, nh, hipMemcpyHostToDevice));
@@ -2208,11 +2112,7 @@ extern "C" int tsf_score_actuals(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, 
     if (out->mean_crps) { HIP_TRY(ctx, d_mc.alloc(8 * (size_t)N)); o.mean_crps = d_mc.as<double>(); }
     if (out->mean_pinball) { HIP_TRY(ctx, d_mp.alloc(nq)); o.mean_pinball = d_mp.as<double>(); }
     if (out->coverage) { HIP_TRY(ctx, d_cv.alloc(nq)); o.coverage = d_cv.as<double>(); }
-    int rc = score_actuals_run(ctx, spec, N, H, d_th.as<double>(), d_ys.as<double>(), d_grid.as<tsf_grid_info>(), n_grids,
-                               d_ds.as<int64_t>(), shared_future, floor_ ? d_fl.as<double>() : nullptr,
-                               cap ? d_cap.as<double>() : nullptr, spec->n_extra > 0 ? d_ex.as<double>() : nullptr,
-                               series_key ? d_key.as<int64_t>() : nullptr, n_samples, seed, d_y.as<double>(), n_q,
-                               quantiles, o, nullptr);
+    int rc = score_actuals_run(ctx, spec, up.dev, {n_samples, seed, n_q, quantiles}, d_y.as<double>(), o, nullptr);
     if (rc) return rc;
     HIP_TRY(ctx, hipDeviceSynchronize());
     HIP_TRY(ctx, hipMemcpy(out->yhat, d_yh.p, nh, hipMemcpyDeviceToHost));
@@ -2360,7 +2260,6 @@ extern "C" int tsf_rollup_add(tsf_rollup *r, const tsf_spec *spec, int64_t N, co
     // calendar repeated per series (shared_future = 0), which is what their layout [N][n_extra][H] belongs to
     const int32_t H = r->H, S = r->S;
     const int shared = (spec->n_extra == 0 || shared_extra) ? 1 : 0;
-    const int stride = tsf_theta_stride(spec);
     const int64_t chunk = draw_chunk_series(N, H, S, 1);       // draw_chunks' chunks: one sample buffer
     RollupPlan P;
     std::vector<int64_t> ds_rep;
@@ -2370,22 +2269,8 @@ extern "C" int tsf_rollup_add(tsf_rollup *r, const tsf_spec *spec, int64_t N, co
     } catch (const std::bad_alloc &) {
         return fail(ctx, "tsf_rollup_add: out of host memory");
     }
-    DevBuf d_th, d_ys, d_grid, d_ds, d_fl, d_cap, d_ex, d_key, d_yh, d_csr;
-    HIP_TRY(ctx, d_th.alloc(8 * (size_t)N * stride));
-    HIP_TRY(ctx, hipMemcpy(d_th.p, theta, 8 * (size_t)N * stride, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_ys.alloc(8 * N));
-    HIP_TRY(ctx, hipMemcpy(d_ys.p, y_scale, 8 * N, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_grid.alloc(sizeof(tsf_grid_info) * n_grids));
-    HIP_TRY(ctx, hipMemcpy(d_grid.p, grid, sizeof(tsf_grid_info) * n_grids, hipMemcpyHostToDevice));
-    if (floor_) { HIP_TRY(ctx, d_fl.alloc(8 * N)); HIP_TRY(ctx, hipMemcpy(d_fl.p, floor_, 8 * N, hipMemcpyHostToDevice)); }
-    if (cap) { HIP_TRY(ctx, d_cap.alloc(8 * N)); HIP_TRY(ctx, hipMemcpy(d_cap.p, cap, 8 * N, hipMemcpyHostToDevice)); }
-    HIP_TRY(ctx, d_key.alloc(8 * N));
-    HIP_TRY(ctx, hipMemcpy(d_key.p, series_key, 8 * N, hipMemcpyHostToDevice));
-    if (spec->n_extra > 0) {
-        const size_t nb = 8 * (size_t)spec->n_extra * H * (shared ? 1 : (size_t)N);
-        HIP_TRY(ctx, d_ex.alloc(nb));
-        HIP_TRY(ctx, hipMemcpy(d_ex.p, extra_future, nb, hipMemcpyHostToDevice));
-    }
+    // the calendar is the handle's, on the device already; the inputs beside it are uploaded
+    DevBuf d_ds, d_yh, d_csr;
     const int64_t *ds_dev = r->d_ds;
     if (!shared) {
         HIP_TRY(ctx, hipMemcpy(ds_rep.data(), r->d_ds, 8 * (size_t)H, hipMemcpyDeviceToHost));
@@ -2394,6 +2279,9 @@ extern "C" int tsf_rollup_add(tsf_rollup *r, const tsf_spec *spec, int64_t N, co
         HIP_TRY(ctx, hipMemcpy(d_ds.p, ds_rep.data(), 8 * (size_t)N * H, hipMemcpyHostToDevice));
         ds_dev = d_ds.as<int64_t>();
     }
+    const ForecastIn h = {N, H, theta, y_scale, grid, n_grids, ds_dev, shared, floor_, cap, extra_future, series_key};
+    ForecastUpload up;
+    if (int rc = up.upload(ctx, spec, h, true)) return rc;
     HIP_TRY(ctx, d_yh.alloc(8 * (size_t)N * H));
     const size_t n_t = P.touched.size(), n_f = P.first.size();
     HIP_TRY(ctx, d_csr.alloc(4 * (n_t + n_f + (size_t)N)));
@@ -2417,10 +2305,8 @@ extern "C" int tsf_rollup_add(tsf_rollup *r, const tsf_spec *spec, int64_t N, co
         HIP_TRY(ctx, hipGetLastError());
         return 0;
     };
-    int rc = draw_chunks(ctx, spec, N, H, d_th.as<double>(), d_ys.as<double>(), d_grid.as<tsf_grid_info>(), n_grids,
-                         ds_dev, shared, floor_ ? d_fl.as<double>() : nullptr, cap ? d_cap.as<double>() : nullptr,
-                         spec->n_extra > 0 ? d_ex.as<double>() : nullptr, d_key.as<int64_t>(), S, r->seed, false, false,
-                         d_yh.as<double>(), nullptr, after);
+    const DrawSpec d = {S, r->seed, false, false, d_yh.as<double>(), nullptr};
+    int rc = draw_chunks(ctx, spec, up.dev, d, nullptr, after);
     if (rc) return rc;
     HIP_TRY(ctx, hipDeviceSynchronize());
     r->poisoned = false;
@@ -2444,8 +2330,7 @@ extern "C" int tsf_rollup_quantiles(tsf_rollup *r, int32_t n_q, const double *qu
     const int32_t H = r->H, S = r->S;
     const int64_t G = r->G;
     const size_t hs = (size_t)H * S, gh = (size_t)G * H, nqh = 8 * gh * (size_t)n_q;
-    int NSP = 2;
-    while (NSP < S) NSP <<= 1;
+    const int NSP = sort_width(S);
     QuantileArgs q;
     memset(&q, 0, sizeof(q));
     q.H = H; q.NS = S; q.n_q = n_q;
@@ -2466,12 +2351,7 @@ extern "C" int tsf_rollup_quantiles(tsf_rollup *r, int32_t n_q, const double *qu
         // the running sums of a range of groups in the context's scratch (within its 512 MB), sorted from there
         HIP_TRY(ctx, d_cq.alloc(nqh));
         const int64_t range = std::max<int64_t>(1, std::min<int64_t>(G, (int64_t)(((size_t)512 << 20) / (8 * hs))));
-        const size_t need = 8 * (size_t)range * hs;
-        if (ctx->iv_ws_bytes < need) {
-            if (ctx->iv_ws) { HIP_TRY(ctx, hipFree(ctx->iv_ws)); ctx->iv_ws = nullptr; ctx->iv_ws_bytes = 0; }
-            HIP_TRY(ctx, hipMalloc(&ctx->iv_ws, need));
-            ctx->iv_ws_bytes = need;
-        }
+        if (int rc = ensure_iv_ws(ctx, 8 * (size_t)range * hs)) return rc;
         double *d_c = (double *)ctx->iv_ws;
         for (int64_t g0 = 0; g0 < G; g0 += range) {
             const int64_t gc = std::min(range, G - g0);

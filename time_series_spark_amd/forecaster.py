@@ -314,6 +314,35 @@ def _opt_f64(a, N, name):
     return a
 
 
+_DS_FUTURE_SHAPE = 'ds_future must be [H] or [N][H]'
+
+
+def _forecast_inputs(spec, theta, y_scale, grid, ds_future_ns, floor, cap, extra_future, series_key=None):
+    """What every predict entry is handed, marshalled for the library: (theta, N, y_scale, grid, ds_future, shared, H,
+    floor, cap, ex, key), each array contiguous in the library's type, the optional ones None where not given."""
+    theta = np.ascontiguousarray(theta, dtype=np.float64)
+    N = theta.shape[0]
+    y_scale = np.ascontiguousarray(y_scale, dtype=np.float64)
+    grid = np.ascontiguousarray(grid, dtype=_lib.GRID_DTYPE)
+    ds_future_ns = np.ascontiguousarray(ds_future_ns, dtype=np.int64)
+    shared = ds_future_ns.ndim == 1
+    H = ds_future_ns.shape[-1]
+    if not shared and ds_future_ns.shape != (N, H):
+        raise ValueError(_DS_FUTURE_SHAPE)
+    floor = _opt_f64(floor, N, 'floor')
+    cap = _opt_f64(cap, N, 'cap')
+    ex = None
+    if spec.extra:
+        ex = np.ascontiguousarray(extra_future, dtype=np.float64)
+        want = (len(spec.extra), H) if shared else (N, len(spec.extra), H)
+        if ex.shape != want:
+            raise ValueError('extra_future must be %r' % (want,))
+    key = None if series_key is None else np.ascontiguousarray(series_key, dtype=np.int64)
+    if key is not None and key.shape != (N,):
+        raise ValueError('series_key must be [N]')
+    return theta, N, y_scale, grid, ds_future_ns, shared, H, floor, cap, ex, key
+
+
 def _alloc_out(N, stride, n_grids):
     theta = np.zeros((N, stride))
     y_scale = np.zeros(N)
@@ -456,24 +485,9 @@ def predict(spec, theta, y_scale, grid, ds_future_ns, floor=None, cap=None, extr
         return np.concatenate(res)
     ctx = ctx or get_context()
     L = _lib.load()
-    theta = np.ascontiguousarray(theta, dtype=np.float64)
-    N = theta.shape[0]
-    y_scale = np.ascontiguousarray(y_scale, dtype=np.float64)
-    grid = np.ascontiguousarray(grid, dtype=_lib.GRID_DTYPE)
-    ds_future_ns = np.ascontiguousarray(ds_future_ns, dtype=np.int64)
-    shared = ds_future_ns.ndim == 1
-    H = ds_future_ns.shape[-1]
-    if not shared and ds_future_ns.shape != (N, H):
-        raise ValueError('ds_future must be [H] or [N][H]')
+    theta, N, y_scale, grid, ds_future_ns, shared, H, floor, cap, ex, _ = _forecast_inputs(
+        spec, theta, y_scale, grid, ds_future_ns, floor, cap, extra_future)
     cs = spec.to_c()
-    floor = _opt_f64(floor, N, 'floor')
-    cap = _opt_f64(cap, N, 'cap')
-    ex = None
-    if spec.extra:
-        ex = np.ascontiguousarray(extra_future, dtype=np.float64)
-        want = (len(spec.extra), H) if shared else (N, len(spec.extra), H)
-        if ex.shape != want:
-            raise ValueError('extra_future must be %r' % (want,))
     yhat = np.zeros((N, H))
     yint = np.zeros((N, H), dtype=np.int32) if want_int else None
     rc = L.tsf_predict(ctx.handle, ctypes.byref(cs), N, H, theta.ctypes.data, y_scale.ctypes.data,
@@ -493,27 +507,9 @@ def predict_intervals(spec, theta, y_scale, grid, ds_future_ns, floor=None, cap=
     interval whatever batch it is in; default: its index in this call."""
     ctx = ctx or get_context()
     L = _lib.load()
-    theta = np.ascontiguousarray(theta, dtype=np.float64)
-    N = theta.shape[0]
-    y_scale = np.ascontiguousarray(y_scale, dtype=np.float64)
-    grid = np.ascontiguousarray(grid, dtype=_lib.GRID_DTYPE)
-    ds_future_ns = np.ascontiguousarray(ds_future_ns, dtype=np.int64)
-    shared = ds_future_ns.ndim == 1
-    H = ds_future_ns.shape[-1]
-    if not shared and ds_future_ns.shape != (N, H):
-        raise ValueError('ds_future must be [H] or [N][H]')
+    theta, N, y_scale, grid, ds_future_ns, shared, H, floor, cap, ex, key = _forecast_inputs(
+        spec, theta, y_scale, grid, ds_future_ns, floor, cap, extra_future, series_key)
     cs = spec.to_c()
-    floor = _opt_f64(floor, N, 'floor')
-    cap = _opt_f64(cap, N, 'cap')
-    ex = None
-    if spec.extra:
-        ex = np.ascontiguousarray(extra_future, dtype=np.float64)
-        want = (len(spec.extra), H) if shared else (N, len(spec.extra), H)
-        if ex.shape != want:
-            raise ValueError('extra_future must be %r' % (want,))
-    key = None if series_key is None else np.ascontiguousarray(series_key, dtype=np.int64)
-    if key is not None and key.shape != (N,):
-        raise ValueError('series_key must be [N]')
     yhat, lo, hi = np.zeros((N, H)), np.zeros((N, H)), np.zeros((N, H))
     rc = L.tsf_predict_intervals(ctx.handle, ctypes.byref(cs), N, H, theta.ctypes.data, y_scale.ctypes.data,
                                  grid.ctypes.data, len(grid), ds_future_ns.ctypes.data, int(shared),
@@ -661,27 +657,9 @@ def predict_components(spec, theta, y_scale, grid, ds_future_ns, floor=None, cap
                           cat('yhat_upper'), cat('trend_lower'), cat('trend_upper'), fl, cp)
     ctx = ctx or get_context()
     L = _lib.load()
-    theta = np.ascontiguousarray(theta, dtype=np.float64)
-    N = theta.shape[0]
-    y_scale = np.ascontiguousarray(y_scale, dtype=np.float64)
-    grid = np.ascontiguousarray(grid, dtype=_lib.GRID_DTYPE)
-    ds_future_ns = np.ascontiguousarray(ds_future_ns, dtype=np.int64)
-    shared = ds_future_ns.ndim == 1
-    H = ds_future_ns.shape[-1]
-    if not shared and ds_future_ns.shape != (N, H):
-        raise ValueError('ds_future must be [H] or [N][H]')
+    theta, N, y_scale, grid, ds_future_ns, shared, H, floor, cap, ex, key = _forecast_inputs(
+        spec, theta, y_scale, grid, ds_future_ns, floor, cap, extra_future, series_key)
     cs = spec.to_c()
-    floor = _opt_f64(floor, N, 'floor')
-    cap = _opt_f64(cap, N, 'cap')
-    ex = None
-    if spec.extra:
-        ex = np.ascontiguousarray(extra_future, dtype=np.float64)
-        want = (len(spec.extra), H) if shared else (N, len(spec.extra), H)
-        if ex.shape != want:
-            raise ValueError('extra_future must be %r' % (want,))
-    key = None if series_key is None else np.ascontiguousarray(series_key, dtype=np.int64)
-    if key is not None and key.shape != (N,):
-        raise ValueError('series_key must be [N]')
     C = len(cols)
     masks = np.array([int(m) for _, m, _ in cols], dtype=np.uint64)
     scaled = np.array([int(s) for _, _, s in cols], dtype=np.int32)
@@ -747,27 +725,9 @@ def _predict_quantiles_call(spec, theta, y_scale, grid, ds_future_ns, floor, cap
     """One tsf_predict_quantiles call -> dict of the outputs named in `want` (and yhat)."""
     ctx = ctx or get_context()
     L = _lib.load()
-    theta = np.ascontiguousarray(theta, dtype=np.float64)
-    N = theta.shape[0]
-    y_scale = np.ascontiguousarray(y_scale, dtype=np.float64)
-    grid = np.ascontiguousarray(grid, dtype=_lib.GRID_DTYPE)
-    ds_future_ns = np.ascontiguousarray(ds_future_ns, dtype=np.int64)
-    shared = ds_future_ns.ndim == 1
-    H = ds_future_ns.shape[-1]
-    if not shared and ds_future_ns.shape != (N, H):
-        raise ValueError('ds_future must be [H] or [N][H]')
+    theta, N, y_scale, grid, ds_future_ns, shared, H, floor, cap, ex, key = _forecast_inputs(
+        spec, theta, y_scale, grid, ds_future_ns, floor, cap, extra_future, series_key)
     cs = spec.to_c()
-    floor = _opt_f64(floor, N, 'floor')
-    cap = _opt_f64(cap, N, 'cap')
-    ex = None
-    if spec.extra:
-        ex = np.ascontiguousarray(extra_future, dtype=np.float64)
-        shape = (len(spec.extra), H) if shared else (N, len(spec.extra), H)
-        if ex.shape != shape:
-            raise ValueError('extra_future must be %r' % (shape,))
-    key = None if series_key is None else np.ascontiguousarray(series_key, dtype=np.int64)
-    if key is not None and key.shape != (N,):
-        raise ValueError('series_key must be [N]')
     levels = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
     Q, S = len(levels), int(uncertainty_samples)
     res = {'yhat': np.zeros((N, H))}
@@ -1935,7 +1895,7 @@ class Calibration(object):
         ds = np.ascontiguousarray(ds_future, dtype=np.int64)
         shared = ds.ndim == 1
         if ds.shape != ((H,) if shared else (N, H)):
-            raise ValueError('ds_future must be [H] or [N][H]')
+            raise ValueError(_DS_FUTURE_SHAPE)
         origin = np.ascontiguousarray(np.broadcast_to(np.asarray(origin_ns, dtype=np.int64), (N,)))
         lw = up = None
         if self.mode == _lib.CALIB_CQR:
