@@ -1673,7 +1673,10 @@ static uint64_t cn_rng_key(uint64_t seed, uint64_t series_key, uint64_t sample, 
 {
     return cn_mix64(cn_mix64(cn_mix64(cn_mix64(seed) ^ series_key) ^ sample) ^ stream);
 }
-static double cn_u01(uint64_t key, uint64_t ctr)        /* in (0, 1) */
+/* In (0, 1], not (0, 1): above 2^52 the sum with 0.5 is a tie that rounds to even, so the top 53-bit value gives
+ * exactly 1.0 (probability 2^-53).  Every consumer stays finite there: det_log(2 (1 - u)) = det_log(0) = -1023 ln 2,
+ * det_log(u) / rem = 0, z = 0 (tests/test_sampler_ref.py).  Every seeded bit depends on this map: it is not to change. */
+static double cn_u01(uint64_t key, uint64_t ctr)
 {
     const uint64_t x = cn_mix64(key + 0x9E3779B97F4A7C15ULL * ctr);
     return ((double)(x >> 11) + 0.5) * 1.1102230246251565e-16;
