@@ -1206,6 +1206,60 @@ __device__ __forceinline__ SeriesTab series_tab_wave(const SeriesView &sv, const
     return st;
 }
 
+#ifndef TSF_QUAD_CIS
+#define TSF_QUAD_CIS 1      // those kernels interpolate a line search's first step by cubic_interp6s (below)
+#endif
+#ifndef TSF_QUAD_PEEL
+#define TSF_QUAD_PEEL 7     // which kernels run a line search's first trial as straight-line code (fit_one_quad PEEL)
+#endif
+
+// cubic_interp6 (tsf_fit_kernels.h) with two cases decided ahead of its chain of two divisions and a square root --
+// decided exactly: every call returns the bits cubic_interp6 returns.
+// x1 == 1 (the previous line search took the unit step: 72 % of the calls on the bench panel): the denominators x1^3, x1
+// and x1^2 are 1.0 and a / 1.0 is a for every a, so c3 and c2 are the numerators themselves.
+// c2^2 - 2 c1 c3 < 0 (66 % of the calls): the square root of a negative number is NaN, so are both roots, and
+// `loX < s && s < hiX` is false for a NaN: the minimiser is loX or hiX, by the polynomial's values at the two alone
+// (the same expression in two lanes; div3_rn gives RN(a / 3) whichever way it takes).  Neither the square root nor the
+// division for the roots is computed then.
+__device__ __forceinline__ double cubic_interp6s(double df0, double x1, double f1, double df1, double loX, double hiX)
+{
+    const double n3 = -12.0 * f1 + 6.0 * x1 * (df0 + df1), n2a = -(4.0 * df0 + 2.0 * df1), n2b = 6.0 * f1;
+    double c3, c2;
+    if (x1 == 1.0) {
+        c3 = n3; c2 = n2a + n2b;
+    } else {
+        const double x1sq = x1 * x1;
+        const double q = lanes4(n3, n2a, n2b, 1.0) / lanes4(x1sq * x1, x1, x1sq, 1.0);
+        c3 = readlane_f64(q, 0);
+        c2 = readlane_f64(q, 1) + readlane_f64(q, 2);
+    }
+    const double c1 = df0;
+    const double disc = UQ(c2 * c2 - 2.0 * c1 * c3);
+    if (disc < 0.0) {
+        const double xe = lane_id() == 0 ? loX : hiX;
+        const double pe = xe * (xe * (div3_rn(xe * c3) + c2) / 2.0 + c1);
+        return readlane_f64(pe, 1) < readlane_f64(pe, 0) ? hiX : loX;
+    }
+    const double t_s = __builtin_sqrt(disc);
+    const double sr = lanes4(-(c2 + t_s), -(c2 - t_s), 0.0, 0.0) / c3;
+    const double s1 = readlane_f64(sr, 0), s2 = readlane_f64(sr, 1);
+    const double xs = lanes4(loX, hiX, s1, s2);
+    const double pv = xs * (xs * (div3_rn(xs * c3) + c2) / 2.0 + c1);
+    double tmpF, minF, minX;
+    minF = readlane_f64(pv, 0);
+    minX = loX;
+    tmpF = readlane_f64(pv, 1);
+    if (tmpF < minF) { minF = tmpF; minX = hiX; }
+    if (loX < s1 && s1 < hiX) {
+        tmpF = readlane_f64(pv, 2);
+        if (tmpF < minF) { minF = tmpF; minX = s1; }
+    }
+    if (loX < s2 && s2 < hiX) {
+        tmpF = readlane_f64(pv, 3);
+        if (tmpF < minF) { minF = tmpF; minX = s2; }
+    }
+    return minX;
+}
 // POOL: wlp is null; a residual pass borrows a QuadLds of `pool` and the vectors that live across
 // evaluations (D, ref, c) sit in the wave's QuadWave `qw`.
 template <int KP, int PPL, int PQ, bool RAGGED, int MRS = W, bool HLDS = false, int MBATCH = 16, bool MREG = false, int NTR = 0, bool POOL = false,
@@ -1261,6 +1315,12 @@ __device__ __forceinline__ bool fit_one_quad(const QuadArgs &qa, QuadLds<KP, PPL
     // tools/dev one-kernel compiles, ragged panels 15.3 -> 18 ms); they keep reading the kernel arguments.
     constexpr bool CT = HLDS && !RAGGED && !MREG && PQ > 0 && PPL == 1;
     const double *const ct = lk.ct;
+    // The first trial of a line search peeled out of the loop of trials (below), on the aligned one-slot kernels the
+    // mask names: 1 the 12-wave shared-M kernel, 2 the 16-wave pooled kernel, 4 the M-in-registers kernel.  The
+    // ragged and two-slot kernels keep the one loop.
+    constexpr bool PEEL = !RAGGED && PQ > 0 && PPL == 1 &&
+                          (MREG ? (TSF_QUAD_PEEL & 4) != 0 : POOL ? (TSF_QUAD_PEEL & 2) != 0 : (HLDS && (TSF_QUAD_PEEL & 1) != 0));
+    constexpr bool CIS = PEEL && (TSF_QUAD_CIS != 0);      // the first step by cubic_interp6s
     QT_DECL;
     if (RAGGED && MRS == W && qa.Mpre) {
         // ragged panel whose series share timestamp vectors: gram_grids_kernel built the M of this series' grid
@@ -1634,18 +1694,76 @@ __device__ __forceinline__ bool fit_one_quad(const QuadArgs &qa, QuadLds<KP, PPL
                 // g_{k-1}.p_{k-1} is the slope `dfp` of the previous line search unless p_{k-1}
                 // has been rescaled since
                 const double gp1 = pk1_scaled ? gp1s : dfp;
-                const double ci = cubic_interp6(gp1, alpha, fk - fk1, gp, minAlpha, 1.0);
+                const double ci = CIS ? cubic_interp6s(gp1, alpha, fk - fk1, gp, minAlpha, 1.0)
+                                      : cubic_interp6(gp1, alpha, fk - fk1, gp, minAlpha, 1.0);
                 alpha = UQ(__builtin_fmin(1.0, 1.01 * ci));
             } else {
                 alpha = CT ? qc(ct, QC_INIT_ALPHA) : a.opt.init_alpha;
             }
             dfp = gp;
             c1dfp = UQ(c1 * dfp); c2dfp = UQ(c2 * dfp);
-            alpha0 = minAlpha; prevF = fk; prevDFp = dfp;
-            nits = 0; lsRestarts = 0; zoom = 0; zit = 0;
 
-            bool ls_fail = false, pre = true;
-            for (;;) {                                  // trial points
+            bool ls_fail = false, pre = true, trials = true;
+            if constexpr (PEEL) {
+                // The first trial as straight-line code: three line searches in four end at it (measured on the bench
+                // panel), and none of those reads a bracket or zoom variable.  The thirteen of them are assigned HERE, on
+                // the way into the loop of the later trials and on every such way, so none is live, initialised or merged
+                // at a join on the path that accepts, nor across the rest of the iteration.  The tests are those of the
+                // loop's first pass (zoom = 0, nits = 0, alpha0 = minAlpha, prevF = fk, prevDFp = dfp) in Stan's order:
+                // sufficient decrease, strong curvature, slope sign; same operations on the same operands.
+                trials = false;
+                if (sv.n_eval >= eval_limit) {
+                    ret = TSF_ST_EVAL_LIMIT;
+                } else {
+                    double xe[PPL], ge[PPL], fe;
+#pragma unroll
+                    for (int s = 0; s < PPL; ++s) { xk1[s] = __builtin_fma(alpha, pk[s], xk[s]); xe[s] = xk1[s]; }
+                    sv.n_eval++;
+                    QT_LAP(2);
+                    const bool bad = gram_eval_q<PPL, PQ, MRS, MBATCH, MREG, MPIPE, (TSF_QUAD_EXPTAB != 0)>(sv, lk, Mp, P4, xe, ref_w, cvec_w, s0, fe, ge, q2, dl_w, mreg);
+                    QT_LAP(4);
+#pragma unroll
+                    for (int s = 0; s < PPL; ++s) gk1[s] = ge[s];
+                    const double f1 = UQ(fe);
+                    if (bad) {
+                        // non-finite: the loop's restart at half the step (lsRestarts 0 -> 1), evaluated without its pre-step
+                        trials = true; pre = false;
+                        alpha0 = minAlpha; prevF = fk; prevDFp = dfp;
+                        alpha = UQ(0.5 * (alpha0 + alpha));
+                        nits = 0; lsRestarts = 1; zoom = 0; zit = 0;
+                        alo = 0; aloF = 0; aloDFp = 0; ahi = 0; ahiF = 0; ahiDFp = 0;
+                    } else {
+                        const double newDFp = pdot<PPL>(gk1, pk);
+                        QT_LAP(5);
+                        if (f1 > fk + alpha * c1dfp) {
+                            trials = true;
+                            alpha0 = minAlpha; prevF = fk; prevDFp = dfp;
+                            nits = 0; lsRestarts = 0; zoom = 1; zit = 0;
+                            alo = minAlpha; aloF = fk; aloDFp = dfp;
+                            ahi = alpha; ahiF = f1; ahiDFp = newDFp;
+                        } else if (__builtin_fabs(newDFp) <= -c2dfp) {
+                            fk1 = f1; accepted = true;
+                        } else if (newDFp >= 0) {
+                            trials = true;
+                            alpha0 = minAlpha; prevF = fk; prevDFp = dfp;
+                            nits = 0; lsRestarts = 0; zoom = 1; zit = 0;
+                            alo = alpha; aloF = f1; aloDFp = newDFp;
+                            ahi = minAlpha; ahiF = fk; ahiDFp = dfp;
+                        } else {
+                            trials = true;
+                            alpha0 = alpha; prevF = f1; prevDFp = newDFp;
+                            alpha = UQ(alpha * 10.0);
+                            nits = 1; lsRestarts = 0; zoom = 0; zit = 0;
+                            alo = 0; aloF = 0; aloDFp = 0; ahi = 0; ahiF = 0; ahiDFp = 0;
+                        }
+                    }
+                }
+            } else {
+                alpha0 = minAlpha; prevF = fk; prevDFp = dfp;
+                nits = 0; lsRestarts = 0; zoom = 0; zit = 0;
+            }
+
+            if (trials) for (;;) {                      // trial points (PEEL: from the second on)
                 if (pre) {
                     if (!zoom) {
                         if (nits >= maxLSIts) ls_fail = true;
