@@ -95,6 +95,54 @@ int tsf_last_fit_kernel_ms(tsf_ctx *ctx, float *ms_out);
  * *sparse_columns = 1 if a wide model's indicator columns ran in sparse form (every grid qualified), 0 if the dense
  * kernels ran or the call was not a candidate.  Waits for the device; valid until the next fit call. */
 int tsf_last_fit_route(tsf_ctx *ctx, int32_t *sparse_columns);
+
+/* ---- the fit route plan -----------------------------------------------------------------
+ * Which kernels a fit call runs, and on what workspace, is decided on the host before anything is launched, from the
+ * model, the shape of the call, the context's route switches and the device's size alone.  tsf_fit_plan is that
+ * decision as a function: host code, no context, no device (the same standing as tsf_cv_plan), so tests pin it on a
+ * machine without a GPU (tests/test_fit_plan.py, tests/golden/fit_plan_cases.npz).  tsf_last_fit_plan returns the
+ * plan the context's last fit launch used (every fold group of a cross-validation is one such launch).
+ * The plan is the HOST's choice only.  Not part of it: a launch function's own fallback where a shape has no
+ * instance of the planned kernel, and the routes chosen on the device (whether the sparse-column form ran --
+ * tsf_last_fit_route --, the matrix-core kernel's changepoint-row overflow). */
+enum {                       /* tsf_fit_plan_info.route: the optimiser / kernel family */
+    TSF_ROUTE_NEWTON = 0,    /* Stan's Newton, residual form */
+    TSF_ROUTE_NEWTON_QUAD,   /* Stan's Newton, quadratic-form trial evaluations */
+    TSF_ROUTE_QUAD_EVAL,     /* tsf_eval_quadratic */
+    TSF_ROUTE_QUAD_LBFGS,    /* L-BFGS on the quadratic form (the headline route) */
+    TSF_ROUTE_MFMA,          /* L-BFGS, residual form on the matrix cores */
+    TSF_ROUTE_WAVE,          /* L-BFGS (or tsf_eval), residual form, one wave per series, with its cooperative tail */
+    TSF_ROUTE_COUNT
+};
+enum { TSF_CALL_FIT = 0, TSF_CALL_EVAL = 1, TSF_CALL_EVAL_QUADRATIC = 2 };     /* tsf_fit_shape.call */
+enum {                       /* tsf_fit_plan_info.err: why a call has no plan (tsf_fit_plan_error: the message) */
+    TSF_PLAN_OK = 0, TSF_PLAN_NO_ROWS, TSF_PLAN_TOO_LONG, TSF_PLAN_NEWTON_WIDE, TSF_PLAN_QUAD_FORM, TSF_PLAN_QUAD_EVAL,
+    TSF_PLAN_MFMA_CHANGEPOINTS, TSF_PLAN_MFMA_SHAPE, TSF_PLAN_COOP_SHAPE, TSF_PLAN_ERR_COUNT
+};
+typedef struct {
+    int64_t N;               /* series of the call */
+    int64_t n_distinct;      /* calendar classes handed in (used when classes = 1 and 0 < n_distinct < N) */
+    int64_t lat_step, lat_U; /* timestamp lattice of a ragged call (lat_step <= 0: none), its points */
+    int32_t aligned;
+    int32_t Tm;              /* rows of the longest series */
+    int32_t call;            /* TSF_CALL_* */
+    int32_t classes;         /* 1: the caller handed in calendar classes */
+} tsf_fit_shape;
+typedef struct {
+    int64_t n_grids, lat_U, quad_pre;
+    int32_t err, route, NTmax, shared_grids;
+    int32_t quad_P4, quad_PPL, quad_NW, quad_blocks, quad_slots, quad_ragged;
+    int32_t mfma_on, mfma_NG, mfma_KF, mfma_NCB, mfma_rr0, mfma_blocks;
+    int32_t coop, coop_after, coop_slots, coop_stride;
+    int32_t sparse_try, harm, gram_harm, resid_harm, map_harm, bw_ns, raw_y, reserved_;
+} tsf_fit_plan_info;
+int tsf_fit_plan_info_size(void);
+/* opt: TSF_OPT_COUNT route switches (-1: default); n_cu: compute units; mem_avail: bytes the context could have (free
+ * memory + its own workspace), < 0: unknown.  Returns 0, or -1 with out->err set (a bad spec: -1 and err = 0). */
+int tsf_fit_plan(const tsf_spec *spec, const tsf_fit_shape *shape, const int *opt, int n_cu, int64_t mem_avail,
+                 tsf_fit_plan_info *out);
+const char *tsf_fit_plan_error(int32_t err);
+int tsf_last_fit_plan(const tsf_ctx *ctx, tsf_fit_plan_info *out);
 /* The last tsf_cross_validate call of this context: *n_grids = grid tables its fit launches built (sum over its
  * launches: one per calendar class where folds share timestamp vectors, else one per fold), *n_launches = fit
  * launches (Newton group, L-BFGS group, Newton retry). */

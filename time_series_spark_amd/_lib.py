@@ -152,6 +152,29 @@ class TsfCalibTable(ctypes.Structure):
     _fields_ = [('q', ctypes.c_void_p), ('n', ctypes.c_void_p), ('status', ctypes.c_void_p)]
 
 
+class TsfFitShape(ctypes.Structure):
+    """tsf_fit_shape (include/tsf_dev.h)."""
+    _fields_ = [('N', ctypes.c_int64), ('n_distinct', ctypes.c_int64), ('lat_step', ctypes.c_int64), ('lat_U', ctypes.c_int64),
+                ('aligned', ctypes.c_int32), ('Tm', ctypes.c_int32), ('call', ctypes.c_int32), ('classes', ctypes.c_int32)]
+
+
+# tsf_fit_plan_info (include/tsf_dev.h), field by field; PLAN_FIELDS: what a plan says (all but the padding)
+_PLAN_I64 = ['n_grids', 'lat_U', 'quad_pre']
+_PLAN_I32 = ['err', 'route', 'NTmax', 'shared_grids', 'quad_P4', 'quad_PPL', 'quad_NW', 'quad_blocks', 'quad_slots',
+             'quad_ragged', 'mfma_on', 'mfma_NG', 'mfma_KF', 'mfma_NCB', 'mfma_rr0', 'mfma_blocks', 'coop', 'coop_after',
+             'coop_slots', 'coop_stride', 'sparse_try', 'harm', 'gram_harm', 'resid_harm', 'map_harm', 'bw_ns', 'raw_y']
+PLAN_FIELDS = _PLAN_I64 + _PLAN_I32
+
+
+class TsfFitPlanInfo(ctypes.Structure):
+    """tsf_fit_plan_info (include/tsf_dev.h)."""
+    _fields_ = ([(f, ctypes.c_int64) for f in _PLAN_I64] + [(f, ctypes.c_int32) for f in _PLAN_I32]
+                + [('reserved_', ctypes.c_int32)])
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f in PLAN_FIELDS}
+
+
 # every symbol include/tsf.h declares; tests check the library exports all of them
 EXPORTS = ['tsf_create', 'tsf_destroy', 'tsf_last_error', 'tsf_device_count', 'tsf_spec_default',
            'tsf_spec_size', 'tsf_grid_info_size', 'tsf_spec_K', 'tsf_theta_stride',
@@ -161,6 +184,7 @@ EXPORTS = ['tsf_create', 'tsf_destroy', 'tsf_last_error', 'tsf_device_count', 't
            'tsf_score_out_size', 'tsf_score_actuals', 'tsf_score_actuals_dev',
            'tsf_rollup_create', 'tsf_rollup_add', 'tsf_rollup_quantiles', 'tsf_rollup_free', 'tsf_eval', 'tsf_eval_quadratic', 'tsf_design', 'tsf_selftest_math',
            'tsf_set_option', 'tsf_get_option', 'tsf_set_cost_hints', 'tsf_set_profiling', 'tsf_profile_read', 'tsf_last_fit_kernel_ms', 'tsf_last_fit_route',
+           'tsf_fit_plan', 'tsf_fit_plan_info_size', 'tsf_fit_plan_error', 'tsf_last_fit_plan',
            'tsf_cv_plan', 'tsf_cross_validate', 'tsf_last_cv_grids', 'tsf_tune', 'tsf_last_tune_counts',
            'tsf_screen_args_size', 'tsf_screen_out_size', 'tsf_fit_screened_out_size', 'tsf_screen_rows', 'tsf_screen_rows_dev',
            'tsf_fit_screened',
@@ -186,6 +210,12 @@ CALIB_ABS, CALIB_CQR = 0, 1
 CALIB_MODES = {'abs': CALIB_ABS, 'cqr': CALIB_CQR}
 CALIB_OK, CALIB_NO_SCORES, CALIB_TOO_LONG = 0, -40, -41
 CALIB_MAX_ROWS, CALIB_MAX_LEVELS, CALIB_MAX_BUCKETS = 16384, 16, 64
+
+# TSF_ROUTE_* / TSF_CALL_* / TSF_PLAN_* (include/tsf_dev.h): a fit plan's route, the kind of call, why a call has no plan
+ROUTE_NEWTON, ROUTE_NEWTON_QUAD, ROUTE_QUAD_EVAL, ROUTE_QUAD_LBFGS, ROUTE_MFMA, ROUTE_WAVE = range(6)
+CALL_FIT, CALL_EVAL, CALL_EVAL_QUADRATIC = 0, 1, 2
+(PLAN_OK, PLAN_NO_ROWS, PLAN_TOO_LONG, PLAN_NEWTON_WIDE, PLAN_QUAD_FORM, PLAN_QUAD_EVAL, PLAN_MFMA_CHANGEPOINTS, PLAN_MFMA_SHAPE,
+ PLAN_COOP_SHAPE) = range(9)
 
 # TSF_OPT_* (include/tsf.h): route switches of one context
 OPTIONS = ['harm', 'lattice', 'sparse_extra', 'fit_grouped', 'gram_share', 'grid_order', 'grid_share', 'ragged_split',
@@ -260,6 +290,11 @@ def load():
     L.tsf_profile_read.argtypes = [vp, ctypes.POINTER(ctypes.c_float), i32, ctypes.POINTER(i32)]
     L.tsf_last_fit_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     L.tsf_last_fit_route.argtypes = [vp, ctypes.POINTER(ctypes.c_int32)]
+    L.tsf_fit_plan.argtypes = [psp, ctypes.POINTER(TsfFitShape), ctypes.POINTER(ctypes.c_int), ctypes.c_int, i64,
+                               ctypes.POINTER(TsfFitPlanInfo)]
+    L.tsf_fit_plan_error.argtypes = [i32]
+    L.tsf_fit_plan_error.restype = ctypes.c_char_p
+    L.tsf_last_fit_plan.argtypes = [vp, ctypes.POINTER(TsfFitPlanInfo)]
     L.tsf_cv_plan.argtypes = [i64, i32, vp, vp, ctypes.POINTER(TsfCvArgs), vp, vp, vp, vp, vp, vp, vp]
     L.tsf_cross_validate.argtypes = [vp, psp, i64, i32, vp, vp, vp, i32, vp, vp, vp, ctypes.POINTER(TsfCvArgs), vp, i32,
                                      ctypes.c_double, ctypes.c_uint64, ctypes.POINTER(TsfCvOut)]
@@ -327,6 +362,8 @@ def load():
         raise TsfError('tsf_screen_args / tsf_screen_out layout mismatch between _lib.py and libtsf_amd.so')
     if L.tsf_calib_args_size() != ctypes.sizeof(TsfCalibArgs) or L.tsf_calib_table_size() != ctypes.sizeof(TsfCalibTable):
         raise TsfError('tsf_calib_args / tsf_calib_table layout mismatch between _lib.py and libtsf_amd.so')
+    if L.tsf_fit_plan_info_size() != ctypes.sizeof(TsfFitPlanInfo):
+        raise TsfError('tsf_fit_plan_info layout mismatch between _lib.py and libtsf_amd.so')
     _lib = L
     return L
 
@@ -388,6 +425,31 @@ class Context(object):
         finally:
             for k, v in old.items():
                 self.set_option(k, v)
+
+
+def fit_plan(spec, N, Tm, aligned=True, call=CALL_FIT, classes=False, n_distinct=0, lat_step=0, lat_U=0, opt=None, n_cu=256,
+             mem_avail=-1):
+    """tsf_fit_plan (include/tsf_dev.h): the route plan of one fit launch, on the host -- no context, no GPU.  spec: a
+    TsfSpec; opt: {option name: value} over the defaults, or a full list.  Returns (rc, {field: value})."""
+    sh = TsfFitShape(N=int(N), n_distinct=int(n_distinct), lat_step=int(lat_step), lat_U=int(lat_U), aligned=int(bool(aligned)),
+                     Tm=int(Tm), call=int(call), classes=int(bool(classes)))
+    if isinstance(opt, dict) or opt is None:
+        vals = [-1] * len(OPTIONS)
+        for k, v in (opt or {}).items():
+            vals[OPTIONS.index(k)] = int(v)
+    else:
+        vals = [int(v) for v in opt]
+    info = TsfFitPlanInfo()
+    rc = load().tsf_fit_plan(ctypes.byref(spec), ctypes.byref(sh), (ctypes.c_int * len(vals))(*vals), int(n_cu), int(mem_avail),
+                             ctypes.byref(info))
+    return int(rc), info.as_dict()
+
+
+def last_fit_plan(ctx):
+    """tsf_last_fit_plan (include/tsf_dev.h): the plan the context's last fit launch used, as fit_plan returns it."""
+    info = TsfFitPlanInfo()
+    ctx.check(load().tsf_last_fit_plan(ctx.handle, ctypes.byref(info)))
+    return info.as_dict()
 
 
 def default_spec():

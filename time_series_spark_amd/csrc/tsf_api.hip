@@ -34,6 +34,7 @@
 #include "tsf_screen_kernels.h"
 #include "tsf_calib_kernels.h"
 #include "tsf_cv_plan.h"
+#include "tsf_fit_plan.h"
 
 using namespace tsf;
 
@@ -65,7 +66,7 @@ struct tsf_ctx {
     hipEvent_t ev0[TSF_PROFILE_RING], ev1[TSF_PROFILE_RING];
     int ev_created;
     long ev_count;          // profiled calls since profiling was enabled
-    int64_t last_n_grids;   // grid tables the last run_fit call built
+    FitPlan last_plan;      // what the last run_fit call planned (tsf_last_fit_plan; its n_grids: the grid tables it built)
     int64_t cv_grids;       // tsf_last_cv_grids: grid tables / fit launches of the last tsf_cross_validate call
     int32_t cv_launches;
     int32_t tune_expand;    // tsf_last_tune_counts: fold panels cut / fit launches of the last tsf_tune call
@@ -111,7 +112,7 @@ extern "C" int tsf_create(int device_id, tsf_ctx **out)
     c->order_ev[0] = c->order_ev[1] = nullptr; c->order_busy[0] = c->order_busy[1] = 0;
     c->profiling = 0; c->ev_created = 0; c->ev_count = 0;
     c->last_sp_flag = nullptr;
-    c->last_n_grids = 0; c->cv_grids = 0; c->cv_launches = 0; c->tune_expand = 0; c->tune_fits = 0;
+    memset(&c->last_plan, 0, sizeof(c->last_plan)); c->cv_grids = 0; c->cv_launches = 0; c->tune_expand = 0; c->tune_fits = 0;
     for (int i = 0; i < TSF_OPT_COUNT; ++i) c->opt[i] = -1;
     if (hipMalloc((void **)&c->d_spec, sizeof(DevSpec)) != hipSuccess) { delete c; return -2; }
     {
@@ -187,10 +188,6 @@ extern "C" int tsf_spec_K(const tsf_spec *s)
 extern "C" int tsf_theta_stride(const tsf_spec *s) { return 3 + s->n_changepoints + tsf_spec_K(s); }
 
 // ---- spec validation + device form ---------------------------------------------------------
-
-// parameters of the FIT: with no changepoints the model is fitted on one dummy changepoint
-// (GridTab::S_fit), so there is always at least one delta
-static int fit_P(int n_cp, int K) { return 3 + (n_cp > 0 ? n_cp : 1) + K; }
 
 static int pick_KP(int K, int n_cp, int mixed)
 {
@@ -285,30 +282,15 @@ struct WsLayout {
     size_t total;
 };
 
-// checkpoint slots of the cooperative tail: one per fit that can be suspended at a time -- the blocks
-// resident when the launch runs dry (a few thousand), all series of a small call
+// bytes of cached Newton slot records (tsf_ctx::nb_ws) that may outlive a call that does not use them
 constexpr size_t TSF_NB_KEEP = (size_t)1 << 30;
-
-// (after: FitArgs::coop_after.  COOP_DIRECT suspends nothing; the tail rule (< 0) suspends at most the fits
-// still running when no more of them are left than there are CUs -- 2 n_cu covers the waves racing past the
-// test; an explicit hand-over point (>= 0: tests, latency mode) can suspend every running fit)
-static int coop_slots_for(int64_t N, int after, int n_cu)
-{
-    if (after == COOP_DIRECT) return 0;
-    const int64_t cap = after >= 0 ? 8192 : 8 * (int64_t)n_cu;      // (hand-over at up to ~4 fits per CU, twice that for the waves racing past the test)
-    return (int)(N < cap ? N : cap);
-}
-
-// launch plan of the matrix-core residual kernel
-struct MfmaPlan { int on, NG, KF, NCB, rr0, blocks; };
 
 static size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
-static WsLayout ws_layout(int64_t N, int64_t n_grids, int NTmax, int KP, int quad_P4 = 0,
-                          int quad_slots = 0, int quad_ragged = 0, int64_t lat_U = 0,
-                          const MfmaPlan *mp = nullptr, int coop_slots = 0, int coop_stride = 0, int64_t quad_pre = 0,
-                          bool sparse = false, int bw_ns = 0, bool no_yw = false)
+static WsLayout ws_layout(int64_t N, const FitPlan &p, int KP)
 {
+    const int64_t n_grids = p.n_grids, lat_U = p.lat_U;
+    const int NTmax = p.NTmax, bw_ns = p.bw_ns;
     WsLayout l;
     size_t off = 0;
     l.gtab = off; off = align_up(off + sizeof(GridTab) * (size_t)n_grids);
@@ -318,32 +300,32 @@ static WsLayout ws_layout(int64_t N, int64_t n_grids, int NTmax, int KP, int qua
     // lattice panels (lat_U > 0) keep one shared table Xu and a row index per series row
     // instead of a design matrix per grid
     l.Xw = off; off = align_up(off + (lat_U > 0 ? 0 : sizeof(double) * (size_t)n_grids * NTmax * KP * W));
-    l.yw = off; off = align_up(off + (no_yw ? 0 : sizeof(double) * (size_t)N * NTmax * W));
+    l.yw = off; off = align_up(off + (p.raw_y ? 0 : sizeof(double) * (size_t)N * NTmax * W));
     // one Gram matrix for an aligned panel; quad_pre of them for a ragged panel whose series share timestamp vectors
-    l.Mg = off; off = align_up(off + sizeof(double) * (size_t)quad_P4 * 2 * W * (size_t)(quad_pre > 0 ? quad_pre : 1));
-    l.Mslot = off; off = align_up(off + (quad_ragged ? sizeof(double) * (size_t)quad_slots * quad_P4 * 2 * W : 0));
-    l.rbuf = off; off = align_up(off + sizeof(double) * (size_t)quad_slots * NTmax * W);
+    l.Mg = off; off = align_up(off + sizeof(double) * (size_t)p.qp.P4 * 2 * W * (size_t)(p.quad_pre > 0 ? p.quad_pre : 1));
+    l.Mslot = off; off = align_up(off + (p.quad_ragged ? sizeof(double) * (size_t)p.qp.slots * p.qp.P4 * 2 * W : 0));
+    l.rbuf = off; off = align_up(off + sizeof(double) * (size_t)p.qp.slots * NTmax * W);
     l.counter = off; off = align_up(off + 256);
     // sparse indicator columns (SP_* in tsf_fit_kernels.h): the lanes' entries and the columns' fold programs per grid
-    l.spm = off; off = align_up(off + (sparse ? sizeof(uint32_t) * (size_t)n_grids * SP_M * W : 0));
-    l.spp = off; off = align_up(off + (sparse ? sizeof(unsigned long long) * (size_t)n_grids * SP_MAXC : 0));
+    l.spm = off; off = align_up(off + (p.sparse_try ? sizeof(uint32_t) * (size_t)n_grids * SP_M * W : 0));
+    l.spp = off; off = align_up(off + (p.sparse_try ? sizeof(unsigned long long) * (size_t)n_grids * SP_MAXC : 0));
     // base pairs of the Fourier columns (fit_kernel<..., HARM>): two doubles per seasonality and row
     // (a panel on a timestamp lattice: per lattice POINT, one table for every series -- FitArgs::Bu)
     l.Bw = off; off = align_up(off + sizeof(double) * (lat_U > 0 ? (size_t)lat_U * bw_ns * 2 : (size_t)n_grids * NTmax * bw_ns * 2 * W));
     l.uw = off; off = align_up(off + (lat_U > 0 ? sizeof(int32_t) * (size_t)n_grids * NTmax * W : 0));
     l.Xu = off; off = align_up(off + (lat_U > 0 ? sizeof(double) * (size_t)lat_U * KP : 0));
-    const bool mf = mp && mp->on;
-    const size_t tiles = mf ? (size_t)W * mp->NG : 0;
-    l.mXF = off; off = align_up(off + (mf ? sizeof(double) * tiles * mp->KF * W : 0));
-    l.mXB = off; off = align_up(off + (mf ? sizeof(double) * tiles * 4 * mp->NCB * W : 0));
-    l.mXT = off; off = align_up(off + (mf ? sizeof(double) * tiles * 4 * W : 0));
-    l.mtq = off; off = align_up(off + (mf ? sizeof(double) * tiles * 16 : 0));
-    l.mcq = off; off = align_up(off + (mf ? sizeof(uint16_t) * tiles * 16 : 0));
-    l.mcpof = off; off = align_up(off + (mf ? (size_t)W * 8 : 0));
-    l.myq = off; off = align_up(off + (mf ? sizeof(double) * (size_t)N * tiles * 16 : 0));
-    l.mhist = off; off = align_up(off + (mf ? sizeof(double) * (size_t)mp->blocks * MT_NS * 2 * MAXH * W : 0));
-    l.clist = off; off = align_up(off + sizeof(int32_t) * (size_t)coop_slots);
-    l.cslots = off; off = align_up(off + sizeof(double) * (size_t)coop_slots * coop_stride);
+    const MfmaPlan &mp = p.mp;
+    const size_t tiles = mp.on ? (size_t)W * mp.NG : 0;
+    l.mXF = off; off = align_up(off + (mp.on ? sizeof(double) * tiles * mp.KF * W : 0));
+    l.mXB = off; off = align_up(off + (mp.on ? sizeof(double) * tiles * 4 * mp.NCB * W : 0));
+    l.mXT = off; off = align_up(off + (mp.on ? sizeof(double) * tiles * 4 * W : 0));
+    l.mtq = off; off = align_up(off + (mp.on ? sizeof(double) * tiles * 16 : 0));
+    l.mcq = off; off = align_up(off + (mp.on ? sizeof(uint16_t) * tiles * 16 : 0));
+    l.mcpof = off; off = align_up(off + (mp.on ? (size_t)W * 8 : 0));
+    l.myq = off; off = align_up(off + (mp.on ? sizeof(double) * (size_t)N * tiles * 16 : 0));
+    l.mhist = off; off = align_up(off + (mp.on ? sizeof(double) * (size_t)mp.blocks * MT_NS * 2 * MAXH * W : 0));
+    l.clist = off; off = align_up(off + sizeof(int32_t) * (size_t)p.coop_slots);
+    l.cslots = off; off = align_up(off + sizeof(double) * (size_t)p.coop_slots * p.coop_stride);
     l.total = off;
     return l;
 }
@@ -378,31 +360,6 @@ static int ensure_ws(tsf_ctx *ctx, size_t bytes, int64_t N = 0, int NTmax = 0, i
     return 0;
 }
 
-// grid / LDS plan of the quadratic-form kernel for this device
-static int quad_plan(tsf_ctx *ctx, const DevSpec &hs, int64_t N, QuadPlan *qp)
-{
-    const int P = fit_P(hs.n_cp, hs.K);
-    qp->PPL = (hs.KP == 64) ? 2 : 1;
-    // rows of M the kernel walks: compile-time 40 / 56 / 64 for the one-slot kernels (zero rows
-    // beyond P are bit-neutral), P rounded up to 4 for the two-slot kernel
-    qp->P4 = (qp->PPL == 2) ? ((P + 3) & ~3) : (P <= 40 ? 40 : (P <= 56 ? 56 : 64));
-    qp->NW = quad_waves_per_block(qp->PPL);       // the most any variant launches: sizes the slots
-    qp->n_cu = ctx->n_cu;
-    qp->opt = ctx->opt;
-    int64_t blocks = ctx->n_cu;                     // persistent: LDS admits one workgroup per CU
-    const int64_t need = (N + qp->NW - 1) / qp->NW;
-    if (blocks > need) blocks = need;
-    if (blocks < 1) blocks = 1;
-    qp->blocks = (int)blocks;
-    // resident waves over all kernel variants (their workgroups hold 4, 8 or 12 waves; each launcher
-    // sizes its own grid): at most n_cu x NW, and no more than one per series rounded up to a workgroup
-    int64_t slots = (int64_t)ctx->n_cu * qp->NW;
-    if (slots > N + qp->NW) slots = N + qp->NW;
-    qp->slots = (int)slots;
-    if (qp->slots < qp->P4) qp->slots = qp->P4;
-    return 0;
-}
-
 typedef int (*launch_t)(int, const FitArgs &, int, hipStream_t);
 typedef int (*launch_newton_t)(int, const FitArgs &, int, hipStream_t);
 static launch_newton_t pick_newton_launch(int growth, int mode)
@@ -427,237 +384,99 @@ static launch_t pick_launch(int growth, int mode)
     return tab[growth][mode];
 }
 
-// Common driver: setup kernels + fit (or eval-only) kernel on device pointers.
-static int run_fit(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int aligned, int32_t T,
-                   const int64_t *offsets, int64_t total_rows, int32_t max_T, const int64_t *ds,
-                   const void *y, int32_t y_dtype, const double *floor_, const double *cap,
-                   const double *extra, tsf_fit_out *out, const double *theta_in,
-                   double *grad_out, hipStream_t st, int64_t lat_base = 0, int64_t lat_step = 0,
-                   int64_t lat_U = 0, const double *theta_ref = nullptr,
-                   const int32_t *grid_of = nullptr, const int64_t *grid_rows = nullptr, int64_t n_distinct = 0,
-                   const int32_t *grid_order = nullptr, const int32_t *grid_keep = nullptr)
-{
-    if (!ctx) return -1;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (N <= 0) return fail(ctx, "N must be > 0");
-    if (!ds || !y || !out) return fail(ctx, "NULL input");
-    if (y_dtype < TSF_Y_F64 || y_dtype > TSF_Y_I32) return fail(ctx, "bad y_dtype");
+// ---- the fit driver -------------------------------------------------------------------------
+
+// One fit (or evaluation) launch on device pointers: what an entry point hands to run_fit.
+struct FitCall {
+    // the panel: aligned [N][T] on one timestamp vector ds [T], or ragged rows [offsets[n], offsets[n + 1]) of
+    // ds / y [total_rows], the longest series max_T rows
+    int64_t N;
+    int aligned;
+    int32_t T;
+    const int64_t *offsets;
+    int64_t total_rows;
+    int32_t max_T;
+    const int64_t *ds;
+    const void *y;
+    int32_t y_dtype;
+    const double *floor, *cap, *extra;
+    // evaluation only (tsf_eval: theta_in, grad_out; tsf_eval_quadratic: around theta_ref too)
+    const double *theta_in;
+    double *grad_out;
+    const double *theta_ref;
+    // ragged panel on a timestamp lattice base + u * step, u < U (lat_step 0: none)
+    int64_t lat_base, lat_step, lat_U;
+    // ragged panel whose series share timestamp vectors: class of each series [N], (first row, rows) per class
+    // [n_distinct][2], the order in which the launch starts the series [N], rows of a class's tables to keep (CV)
+    const int32_t *grid_of;
+    const int64_t *grid_rows;
+    int64_t n_distinct;
+    const int32_t *grid_order, *grid_keep;
+    hipStream_t stream;
+};
+
+// what the steps of one run_fit call share
+struct FitRun {
+    tsf_ctx *ctx;
+    const tsf_spec *spec;
+    const FitCall *c;
     DevSpec hs;
-    int mode = 0;
-    int rc = build_devspec(ctx, spec, &hs, &mode);
+    int mode;
+    FitPlan p;
+    WsLayout l;
+    char *ws;
+    const int32_t *grid_of;     // the call's calendar classes where the plan uses them, else null
+    const int64_t *grid_rows;
+    int slot;                   // profiling ring slot of this call
+};
+
+static int fit_validate(tsf_ctx *ctx, const tsf_spec *spec, const FitCall &c, const tsf_fit_out *out, DevSpec *hs, int *mode)
+{
+    if (c.N <= 0) return fail(ctx, "N must be > 0");
+    if (!c.ds || !c.y || !out) return fail(ctx, "NULL input");
+    if (c.y_dtype < TSF_Y_F64 || c.y_dtype > TSF_Y_I32) return fail(ctx, "bad y_dtype");
+    int rc = build_devspec(ctx, spec, hs, mode);
     if (rc) return rc;
-    if (hs.n_extra > 0 && !extra) return fail(ctx, "extra columns declared but extra is NULL");
-    if (hs.growth == TSF_GROWTH_LOGISTIC && !cap) return fail(ctx, "logistic growth needs cap");
-    const int Tm = aligned ? T : max_T;
-    if (Tm < 1) return fail(ctx, "no rows");
-    if (Tm > TSF_MAX_T) return fail(ctx, "series too long (TSF_MAX_T rows per series)");
-    const int NTmax = (Tm + W - 1) / W;
-    // ragged panel whose series share timestamp vectors (fit_host found n_distinct < N of them): one set of grid tables
-    // per distinct vector
-    if (aligned || !grid_of || !grid_rows || n_distinct <= 0 || n_distinct >= N) { grid_of = nullptr; grid_rows = nullptr; n_distinct = 0; }
-    const int64_t n_grids = aligned ? 1 : (grid_of ? n_distinct : N);
-    ctx->last_n_grids = n_grids;
-    // quadratic (Gram) form of the data term: see tsf_quad_kernels.h
-    // Stan's Newton optimiser (tsf_newton_kernels.h): explicitly, or by fbprophet's rule on the
-    // longest series of the call
-    const bool newton = theta_in == nullptr &&
-                        (spec->algorithm == TSF_ALGO_NEWTON ||
-                         (spec->algorithm == TSF_ALGO_AUTO && Tm < TSF_NEWTON_BELOW_T));
-    // (more than 64 parameters, or mixed additive / multiplicative columns: newton_kernel2, two parameters per lane)
-    if (newton && fit_P(hs.n_cp, hs.K) > 2 * W)
-        return fail(ctx, "Newton needs 3 + n_changepoints + K <= 128");
-    const bool quad_ok = hs.growth == TSF_GROWTH_LINEAR && mode == 0 && hs.history == QH &&
-                         theta_in == nullptr && !newton;
-    if (spec->eval_form == TSF_EVAL_QUADRATIC && !quad_ok && theta_in == nullptr)
-        return fail(ctx, "eval_form QUADRATIC needs linear growth, additive columns only and history == 5");
-    const bool quad = quad_ok && spec->eval_form != TSF_EVAL_RESIDUAL;
-    // Newton on the same models: residual form at the accepted points, quadratic form for the
-    // finite-difference and halving evaluations (tsf_newton_quad.h); aligned panels
-    const bool newton_quad = newton && hs.growth == TSF_GROWTH_LINEAR && mode == 0 && hs.KP <= 28 &&
-                             spec->eval_form != TSF_EVAL_RESIDUAL && NTmax <= 16;
-    // tsf_eval_quadratic: one quadratic-form evaluation at theta_in around the reference point theta_ref
-    const bool quad_eval = theta_in != nullptr && theta_ref != nullptr;
-    if (quad_eval && !(aligned && hs.growth == TSF_GROWTH_LINEAR && mode == 0 && hs.KP != 64))
-        return fail(ctx, "the quadratic form needs an aligned panel, linear growth, additive columns only and 3 + n_changepoints + K <= 64");
-    // the slot records of the several-series-per-wave Newton kernel are cached between Newton calls, but at most
-    // TSF_NB_KEEP bytes of them outlive a call that does not use them
-    if (!(newton_quad && aligned) && ctx->nb_ws_bytes > TSF_NB_KEEP) {
-        HIP_TRY(ctx, hipFree(ctx->nb_ws));
-        ctx->nb_ws = nullptr; ctx->nb_ws_bytes = 0;
-    }
-    QuadPlan qp;
-    memset(&qp, 0, sizeof(qp));
-    if (quad || newton_quad || quad_eval) {
-        rc = quad_plan(ctx, hs, N, &qp);
-        if (rc) return rc;
-        if (newton_quad) {          // one-wave workgroups, up to 16 per CU: that many Z^T Z slots (ragged)
-            qp.slots = ctx->n_cu * 16;
-            if (qp.slots < qp.P4) qp.slots = qp.P4;
-        }
-    }
-    // shared lattice table: ragged panel, residual-form kernel, no explicit columns
-    if (aligned || quad || newton || theta_in != nullptr || hs.n_extra > 0 || lat_step <= 0) lat_U = 0;
-    {
-        // Series that share timestamp vectors (grid_of) have step-major tables per DISTINCT vector: where those fit the
-        // caches (<= 64 MB of design tables) every wave reads them coalesced, as on an aligned panel, and the lattice
-        // table with its gathered rows (64 cache lines per load instruction) is the slower of the two.
-        // tsf_set_option(TSF_OPT_LATTICE, 0): never the lattice table; 1: always where it applies.
-        // Round 5: a model whose Fourier columns have a compiled expansion reads 32-byte base pairs per row from its OWN
-        // tables (eval_fg HARM) -- faster than the gathered 224-byte rows of the lattice table in the one-wave kernel (ragged
-        // bench panel, a grid per series: 93 -> 60 ms) and, above all, in the cooperative tail (gathered rows stream: 11 us
-        // per evaluation against 5) -- wherever a table per series is affordable: <= 32 GB of design tables per call
-        // (~190 000 series of 730 rows) AND no more than two fifths of the memory this context can have (what is free
-        // now + its own cached workspace; the tables are ~4/5 of the layout): several contexts or ranks on one GPU, or
-        // a smaller part, keep the shared lattice table -- the route that needs no table per series -- instead of
-        // failing in ensure_ws (round-5 advice).
-        // Round 6: the base-pair kernels read a lattice panel too (rows of 22 bytes + the lattice POINTS' pairs from one
-        // shared table, FitArgs::Bu: as fast or faster than a table per series -- 10 000 / 2 000 series at their own subsets
-        // of a daily lattice: 75.9 -> 74.5 / 31.1 -> 27.0 ms -- for 0.44 of the traffic and none of the 2 GB of tables), so
-        // such a model keeps the lattice (its MAP continuation too).
-        const int el = ctx->opt[TSF_OPT_LATTICE];
-        const size_t tab = sizeof(double) * (size_t)n_grids * (size_t)NTmax * hs.KP * W;
-        const bool harm_model = ctx->opt[TSF_OPT_HARM] != 0 && mode != 2 &&
-                                ((hs.harm == HARM_Y10_W3 && hs.KP == 28) || (hs.harm == HARM_W3_D4 && hs.KP == 16) || (hs.harm == HARM_W3 && hs.KP == 8));
-        const bool lat_harm = harm_model && hs.K == harm_kf(hs.harm);
-        size_t harm_cap = (size_t)32 << 30;
-        if (lat_U > 0 && el < 0 && harm_model && !lat_harm && tab > ((size_t)256 << 20)) {
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-                const size_t mine = (free_b + ctx->ws_bytes) / 5 * 2;
-                if (mine < harm_cap) harm_cap = mine;
-            } else {
-                (void)hipGetLastError();
-            }
-        }
-        if (el >= 0 ? el == 0 : ((grid_of != nullptr && tab <= ((size_t)64 << 20)) || (harm_model && !lat_harm && tab <= harm_cap))) lat_U = 0;
-    }
-    // matrix-core residual kernel (tsf_mfma_kernels.h): aligned panel, L-BFGS, one parameter per lane
-    // (KP <= 28 implies one column mode and P <= 64), at most MT_SP changepoints, and an upper bound
-    // on the changepoint rows one chunk can hold (the exact count is checked on the device:
-    // MfmaTabs::overflow routes the call to the one-wave kernel)
-    MfmaPlan mp;
-    memset(&mp, 0, sizeof(mp));
-    // TSF_RK_AUTO = the one-wave kernel.  Measured (profiles/r02_mfma_vs_wave.txt): both kernels issue
-    // the same number of vector instructions per evaluation and are bound by them -- fp64 MFMA has
-    // the vector unit's rate, and the 672 multiply-adds it takes over are 16 % of an evaluation --
-    // so once the reductions of the optimiser were cut (uniform butterflies) the one-wave kernel,
-    // which has no rounds to synchronise, is ahead on every panel measured (100 000 x 730, iteration
-    // cap 150: 271 vs 326 ms; reference settings with their stragglers: 1.27 vs 1.62 s).  The
-    // matrix-core kernel stays available (TSF_RK_MFMA), bit-identical.
-    // Specified changepoints: rejected -- per_chunk below bounds the changepoint rows of a chunk by the automatic rule's
-    // spacing, which dates at arbitrary places do not have.
-    if (spec->residual_kernel == TSF_RK_MFMA && hs.cp_spec && theta_in == nullptr)
-        return fail(ctx, "residual_kernel MFMA does not take specified changepoints (changepoints_specified = 1)");
-    const bool want_mfma = spec->residual_kernel == TSF_RK_MFMA;
-    if (aligned && !quad && !newton && theta_in == nullptr && hs.KP <= 28 && want_mfma) {
-        const int hist_rows = (int)floor((double)Tm * hs.cp_range);
-        int S = hs.n_cp;
-        if (S + 1 > hist_rows) S = hist_rows - 1;
-        if (S < 1) S = 1;
-        const double step = (hs.n_cp > 0 && S > 0) ? (double)(hist_rows - 1) / (double)S : 1e30;
-        const int per_chunk = (int)ceil((double)NTmax / (step > 1.0 ? step : 1.0)) + 2;
-        if (S <= MT_SP && per_chunk <= MT_MAXCP && mfma_lds_bytes(hs.KP) <= 160 * 1024) {
-            mp.on = 1;
-            mp.NG = (NTmax + 15) / 16;
-            mp.KF = hs.KP / 4;
-            mp.NCB = (hs.KP + 15) / 16;
-            mp.rr0 = (16 * mp.NG - NTmax) / 4;
-            int64_t blocks = (N + MT_NS - 1) / MT_NS;
-            if (blocks > ctx->n_cu) blocks = ctx->n_cu;
-            mp.blocks = (int)blocks;
-        }
-    }
-    if (spec->residual_kernel == TSF_RK_MFMA && !mp.on && theta_in == nullptr && !quad && !newton)
-        return fail(ctx, "residual_kernel MFMA needs an aligned panel, K <= 28 columns of one mode, 3+S+K <= 64 and S <= 28");
-    // cooperative tail of the one-wave residual kernel: series of at most COOP_MAX_NT steps per chunk
-    // (the rows of one evaluation are staged in the workgroup's LDS)
-    const bool coop_ok = !quad && !newton && theta_in == nullptr && !mp.on && NTmax <= COOP_MAX_NT;
-    if (spec->residual_kernel == TSF_RK_COOP && !coop_ok && theta_in == nullptr)
-        return fail(ctx, "residual_kernel COOP needs a residual-form L-BFGS fit of series of at most 4096 rows");
-    const bool coop = coop_ok && spec->residual_kernel != TSF_RK_WAVE;
-    // where fits are handed over (FitArgs::coop_after).  TSF_RK_COOP: the cooperative kernel runs every fit from
-    // its first evaluation (no one-wave phase, no checkpoints).  AUTO does the same for the models whose one-wave
-    // kernel holds two parameters per lane (KP = 64) on series too long for the grouped column sums: that kernel
-    // needs > 256 registers (one wave per SIMD) and measures 9.6 M evaluations/s on 50 000 x 730 with 56 columns,
-    // the workgroup kernel 11.4+ M.
-    // Round 3: on series of <= 768 rows the one-wave kernel of these models takes its per-column sums in groups
-    // of 8 (eval_fg GNTR: 187 instead of 379 registers, two waves per SIMD) and allocates only the history pairs
-    // it uses (wave_lds_bytes: eight blocks per CU instead of six): 17.0 M evaluations/s on cfg4 against the
-    // workgroup kernel's 15.4 M (2.27 against 2.50 s) -- so AUTO runs it, with the workgroup kernel for the tail
-    // as for the narrower models.  tsf_set_option(TSF_OPT_FIT_GROUPED, 0): every series on the workgroup kernel, as before.
-    // Wide models (64-column tables) whose columns from the 29th on are explicit columns -- holidays: 0 / 1 indicators,
-    // almost all 0 -- are tried on the sparse-column form of the 28-column kernel (eval_fg<..., SPARSE>, tsf_fit_kernels.h):
-    // sparse_extra_kernel decides on the device whether every grid qualifies, the dense route is launched behind it
-    // with the opposite guard (series of <= 768 rows: the grouped one-wave kernel; up to 4 096 rows: the workgroup
-    // kernel from the first evaluation; longer: the ungrouped one-wave kernel).  tsf_set_option(TSF_OPT_SPARSE_EXTRA, 0): never.
-    const bool sparse_try = !quad && !newton && !mp.on && theta_in == nullptr && lat_U == 0 && hs.KP == 64 && mode != 2 &&
-                            spec->residual_kernel == TSF_RK_AUTO && hs.K > SP_DENSE && hs.K <= SP_DENSE + SP_MAXC &&
-                            hs.K - hs.n_extra <= SP_DENSE && NTmax <= SP_MAX_NT && ctx->opt[TSF_OPT_SPARSE_EXTRA] != 0;
-    int coop_after = spec->residual_kernel == TSF_RK_COOP ? COOP_DIRECT : spec->coop_after;
-    if (coop) {
-        const bool grouped = NTmax <= 12 && ctx->opt[TSF_OPT_FIT_GROUPED] != 0 && lat_U == 0;
-        // (with sparse_try the slots of the tail exist either way: the dense route of longer series is then launched
-        // in direct mode by the launch function itself)
-        if (spec->residual_kernel == TSF_RK_AUTO && spec->coop_after < 0 && hs.KP == 64 && !grouped && !sparse_try) coop_after = COOP_DIRECT;
-    }
-    const int coop_slots = coop ? coop_slots_for(N, coop_after, ctx->n_cu) : 0;
-    const int coop_stride = coop ? coop_slot_doubles(hs.KP == 64 ? 2 : 1) : 0;
-    // ragged panel, quadratic form, series sharing timestamp vectors: Z^T Z once per distinct vector (gram_grids_kernel)
-    // instead of once per series inside the fit kernel -- when that at least halves the builds (TSF_OPT_GRAM_SHARE 0: never)
-    const int64_t quad_pre = (quad && !aligned && grid_of && n_grids * 2 <= N && ctx->opt[TSF_OPT_GRAM_SHARE] != 0) ? n_grids : 0;
-    // Fourier columns expanded from the rows' base pairs (eval_fg HARM): the residual-form one-wave kernel of models
-    // whose harmonic structure has a compiled kernel -- yearly 10 + weekly 3 on the 28-column kernel and its
-    // sparse-column form, weekly 3 + daily 4 (16 columns), weekly 3 (8 columns); never with the lattice table or the
-    // matrix-core / workgroup-from-the-start routes.  tsf_set_option(TSF_OPT_HARM, 0): never.
-    // Round 6: WITH the lattice table where the model is exactly one of those (nothing behind the Fourier block): a row keeps t, y, its segment word and its lattice point (22 bytes instead of 50) and the base pairs
-    // are the point's, from one table of 32 bytes per point that every series shares (FitArgs::Bu) -- no table per series.
-    int harm = 0;
-    if (!quad && !newton && !mp.on && theta_in == nullptr && lat_U == 0 && ctx->opt[TSF_OPT_HARM] != 0) {
-        if ((hs.harm == HARM_Y10_W3 && (hs.KP == 28 || sparse_try)) || (hs.harm == HARM_W3_D4 && hs.KP == 16) ||
-            (hs.harm == HARM_W3 && hs.KP == 8))
-            harm = hs.harm;
-    } else if (!quad && !newton && !mp.on && theta_in == nullptr && lat_U > 0 && ctx->opt[TSF_OPT_HARM] != 0 && mode != 2 &&
-               hs.K == harm_kf(hs.harm) &&
-               ((hs.harm == HARM_Y10_W3 && hs.KP == 28) || (hs.harm == HARM_W3_D4 && hs.KP == 16) || (hs.harm == HARM_W3 && hs.KP == 8))) {
-        harm = hs.harm;
-    }
-    // The same base pairs for the Gram build of a ragged quadratic-form panel whose series have a calendar each (the M-in-
-    // registers kernel builds Z^T Z per series: gram_columns_harm, tsf_quad_kernels.h); shared calendars build once per
-    // calendar (quad_pre) and keep reading the tables.
-    int gram_harm = 0;
-    if (quad && !aligned && !quad_pre && lat_U == 0 && hs.harm == HARM_Y10_W3 && hs.KP == 28 && ctx->opt[TSF_OPT_HARM] != 0)
-        gram_harm = hs.harm;
-    // ... and for the residual passes of an ALIGNED quadratic-form call with one parameter per lane (the 12- and 16-wave
-    // kernels, the M-in-registers kernel, tsf_eval_quadratic): rows as base pairs, the column sums taken in the row sweep
-    // itself (ztr_sweep_harm, tsf_quad_kernels.h) -- every compiled shape, dense columns behind the Fourier block allowed.
-    // Two-slot kernels (P > 64), ragged calls and other models keep the two-sweep table route; TSF_OPT_HARM 0: every call.
-    int resid_harm = 0;
-    if ((quad || quad_eval) && aligned && qp.PPL == 1 && ctx->opt[TSF_OPT_HARM] != 0 &&
-        ((hs.harm == HARM_Y10_W3 && hs.KP == 28) || (hs.harm == HARM_W3_D4 && hs.KP == 16) || (hs.harm == HARM_W3 && hs.KP == 8)))
-        resid_harm = hs.harm;
-    // ... and for the MAP continuation (tsf_map_kernels.h): its evaluator reads base-pair rows wherever the model has a
-    // compiled expansion, whatever kernel ran the Stan-rule fit (the quadratic-form route builds the table for it)
-    int map_harm = 0;
-    if (spec->converge == TSF_CONVERGE_MAP && theta_in == nullptr && mode != 2 && ctx->opt[TSF_OPT_HARM] != 0 &&
-        hs.K == harm_kf(hs.harm) &&
-        ((hs.harm == HARM_Y10_W3 && hs.KP == 28) || (hs.harm == HARM_W3_D4 && hs.KP == 16) || (hs.harm == HARM_W3 && hs.KP == 8)))
-        map_harm = hs.harm;
-    const int bw_ns = (harm || gram_harm || resid_harm || map_harm) ? hs.n_seas : 0;
-    // Quadratic-form L-BFGS fits read the caller's y rows themselves (FitArgs::y_raw) instead of a scaled step-major copy
-    // that setup_series_kernel would write and they would read back -- a second f64 panel on the device and half of the
-    // step's HBM bytes.  Not when the MAP continuation follows (its evaluator reads yw).
-    const bool raw_y = quad && spec->converge != TSF_CONVERGE_MAP && ctx->opt[TSF_OPT_QUAD_RAW_Y] != 0;
-    const WsLayout l = ws_layout(N, n_grids, NTmax, hs.KP, qp.P4, qp.slots, (quad || newton_quad) && !aligned, lat_U, &mp,
-                                 coop_slots, coop_stride, quad_pre, sparse_try, bw_ns, raw_y);
-    rc = ensure_ws(ctx, l.total, N, NTmax, !aligned);
-    if (rc) return rc;
-    char *ws = (char *)ctx->ws;
+    if (hs->n_extra > 0 && !c.extra) return fail(ctx, "extra columns declared but extra is NULL");
+    if (hs->growth == TSF_GROWTH_LOGISTIC && !c.cap) return fail(ctx, "logistic growth needs cap");
+    return 0;
+}
+
+static tsf_fit_shape fit_shape(const FitCall &c)
+{
+    tsf_fit_shape sh;
+    memset(&sh, 0, sizeof(sh));
+    sh.N = c.N; sh.aligned = c.aligned; sh.Tm = c.aligned ? c.T : c.max_T;
+    sh.call = !c.theta_in ? TSF_CALL_FIT : (c.theta_ref ? TSF_CALL_EVAL_QUADRATIC : TSF_CALL_EVAL);
+    sh.classes = c.grid_of && c.grid_rows; sh.n_distinct = c.n_distinct;
+    sh.lat_step = c.lat_step; sh.lat_U = c.lat_U;
+    return sh;
+}
+
+// plan_fit's memory query: what is free now + the context's own cached workspace
+static int64_t ctx_mem_avail(void *arg)
+{
+    const tsf_ctx *ctx = (const tsf_ctx *)arg;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) return (int64_t)(free_b + ctx->ws_bytes);
+    (void)hipGetLastError();
+    return -1;
+}
+
+// the set-up launches: the spec, the grids' tables (lattice / per grid), the sparse-column programs, the series' rows
+static int fit_setup(const FitRun &r)
+{
+    tsf_ctx *ctx = r.ctx;
+    const FitCall &c = *r.c;
+    const FitPlan &p = r.p;
+    const WsLayout &l = r.l;
+    const DevSpec &hs = r.hs;
+    char *ws = r.ws;
+    hipStream_t st = c.stream;
+    const int64_t n_grids = p.n_grids, lat_U = p.lat_U;
+    const int NTmax = p.NTmax, bw_ns = p.bw_ns;
     GridTab *gtab = (GridTab *)(ws + l.gtab);
-    SeriesTab *stab = (SeriesTab *)(ws + l.stab);
-    double *tw = (double *)(ws + l.tw);
-    uint16_t *cw = (uint16_t *)(ws + l.cw);
     double *Xw = (double *)(ws + l.Xw);
-    double *yw = raw_y ? (double *)nullptr : (double *)(ws + l.yw);
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_spec, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
     if (lat_U > 0) {
         double *Xu = (double *)(ws + l.Xu);
@@ -666,7 +485,7 @@ static int run_fit(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int aligned, i
         HIP_TRY(ctx, hipMemsetAsync(ws + l.uw, 0, sizeof(int32_t) * (size_t)n_grids * NTmax * W, st));
         const int64_t work = lat_U * (hs.n_seas > 0 ? hs.n_seas : 1);
         hipLaunchKernelGGL(setup_lattice_kernel, dim3((unsigned)((work + 255) / 256 > 65535 ? 65535 : (work + 255) / 256)),
-                           dim3(256), 0, st, ctx->d_spec, lat_U, lat_base, lat_step, Xu, bw_ns ? (double *)(ws + l.Bw) : (double *)nullptr);
+                           dim3(256), 0, st, ctx->d_spec, lat_U, c.lat_base, c.lat_step, Xu, bw_ns ? (double *)(ws + l.Bw) : (double *)nullptr);
         HIP_TRY(ctx, hipGetLastError());
     } else {
         HIP_TRY(ctx, hipMemsetAsync(Xw, 0, sizeof(double) * (size_t)n_grids * NTmax * hs.KP * W, st));
@@ -676,12 +495,12 @@ static int run_fit(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int aligned, i
     }
     HIP_TRY(ctx, hipMemsetAsync(gtab, 0, sizeof(GridTab) * (size_t)n_grids, st));
     hipLaunchKernelGGL(setup_grid_kernel, dim3((unsigned)n_grids), dim3(256), 0, st, ctx->d_spec,
-                       (int)n_grids, aligned ? nullptr : offsets, T, ds, extra,
-                       aligned ? (int64_t)T : total_rows, NTmax, gtab, tw, cw, Xw,
-                       (int32_t *)(ws + l.uw), lat_base, lat_U > 0 ? lat_step : (int64_t)0, grid_rows,
-                       (bw_ns && lat_U == 0) ? (double *)(ws + l.Bw) : (double *)nullptr, grid_keep);
+                       (int)n_grids, c.aligned ? nullptr : c.offsets, c.T, c.ds, c.extra,
+                       c.aligned ? (int64_t)c.T : c.total_rows, NTmax, gtab, (double *)(ws + l.tw), (uint16_t *)(ws + l.cw), Xw,
+                       (int32_t *)(ws + l.uw), c.lat_base, lat_U > 0 ? c.lat_step : (int64_t)0, r.grid_rows,
+                       (bw_ns && lat_U == 0) ? (double *)(ws + l.Bw) : (double *)nullptr, c.grid_keep);
     HIP_TRY(ctx, hipGetLastError());
-    if (sparse_try) {
+    if (p.sparse_try) {
         int *sp_bad = (int *)(ws + l.counter) + 8;
         HIP_TRY(ctx, hipMemsetAsync(sp_bad, 0, sizeof(int), st));
         hipLaunchKernelGGL(sparse_extra_kernel, dim3((unsigned)n_grids), dim3(64), 0, st, ctx->d_spec, gtab, Xw, NTmax,
@@ -690,16 +509,30 @@ static int run_fit(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int aligned, i
     }
     // (raw_y: the quadratic-form fit kernel derives the scale and the initial values from the caller's rows itself --
     // series_tab_wave, tsf_quad_kernels.h -- and no kernel of that route reads SeriesTab or yw)
-    if (!raw_y) {
-        hipLaunchKernelGGL(setup_series_kernel, dim3((unsigned)N), dim3(64), 0, st, ctx->d_spec, N,
-                           aligned ? nullptr : offsets, T, ds, y, y_dtype, floor_, cap, NTmax, gtab,
-                           aligned, stab, yw, grid_of);
+    if (!p.raw_y) {
+        hipLaunchKernelGGL(setup_series_kernel, dim3((unsigned)c.N), dim3(64), 0, st, ctx->d_spec, c.N,
+                           c.aligned ? nullptr : c.offsets, c.T, c.ds, c.y, c.y_dtype, c.floor, c.cap, NTmax, gtab,
+                           c.aligned, (SeriesTab *)(ws + l.stab), (double *)(ws + l.yw), r.grid_of);
         HIP_TRY(ctx, hipGetLastError());
     }
+    return 0;
+}
+
+// the fit kernels' arguments (the route's own additions are its launch step's)
+static FitArgs fit_args(const FitRun &r, const tsf_fit_out *out)
+{
+    const tsf_ctx *ctx = r.ctx;
+    const FitCall &c = *r.c;
+    const FitPlan &p = r.p;
+    const WsLayout &l = r.l;
+    const DevSpec &hs = r.hs;
+    char *ws = r.ws;
+    const int64_t lat_U = p.lat_U;
+    const int bw_ns = p.bw_ns, harm = p.harm;
     FitArgs a;
     memset(&a, 0, sizeof(a));
-    a.sp = ctx->d_spec; a.N = N; a.aligned = aligned; a.NTmax = NTmax;
-    a.theta_stride = tsf_theta_stride(spec);
+    a.sp = ctx->d_spec; a.N = c.N; a.aligned = c.aligned; a.NTmax = p.NTmax;
+    a.theta_stride = tsf_theta_stride(r.spec);
     {
         const double eps = 2.220446049250313e-16;
         a.opt.init_alpha = hs.init_alpha; a.opt.tol_obj = hs.tol_obj;
@@ -707,146 +540,245 @@ static int run_fit(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int aligned, i
         a.opt.tol_rel_grad_eps = hs.tol_rel_grad * eps; a.opt.tol_param = hs.tol_param;
         a.opt.max_iter = hs.max_iter; a.opt.history = hs.history;
     }
-    a.gtab = gtab; a.stab = stab; a.tw = tw; a.yw = yw; a.Xw = Xw; a.cw = cw;
+    a.gtab = (GridTab *)(ws + l.gtab); a.stab = (SeriesTab *)(ws + l.stab); a.tw = (double *)(ws + l.tw);
+    a.yw = p.raw_y ? (double *)nullptr : (double *)(ws + l.yw); a.Xw = (double *)(ws + l.Xw); a.cw = (uint16_t *)(ws + l.cw);
     a.theta = out->theta; a.y_scale = out->y_scale; a.fval = out->fval; a.status = out->status;
     a.n_iter = out->n_iter; a.n_eval = out->n_eval; a.grid_out = out->grid;
-    a.theta_in = theta_in; a.grad_out = grad_out;
-    if (raw_y) { a.y_raw = y; a.y_raw_dtype = y_dtype; a.y_offsets = aligned ? nullptr : offsets; a.y_T = T; }
+    a.theta_in = c.theta_in; a.grad_out = c.grad_out;
+    if (p.raw_y) { a.y_raw = c.y; a.y_raw_dtype = c.y_dtype; a.y_offsets = c.aligned ? nullptr : c.offsets; a.y_T = c.T; }
     a.uw = (const int32_t *)(ws + l.uw); a.Xu = (const double *)(ws + l.Xu); a.xidx = lat_U > 0 ? 1 : 0;
-    a.grid_of = grid_of;
+    a.grid_of = r.grid_of;
     a.Bw = (bw_ns && lat_U == 0) ? (const double *)(ws + l.Bw) : nullptr; a.bw_ns = bw_ns; a.harm = harm;
     a.Bu = (bw_ns && lat_U > 0) ? (const double *)(ws + l.Bw) : nullptr;
-    a.coop_harm = (harm != 0 && hs.K == harm_kf(harm) && mode != 2) ? 1 : 0;
+    a.coop_harm = (harm != 0 && hs.K == harm_kf(harm) && r.mode != 2) ? 1 : 0;
     {
         // rows of the one-wave base-pair kernel from HBM?  (tables per grid: segment words, t, base pairs; y per series)
-        const size_t row_tabs = (size_t)n_grids * NTmax * W * (sizeof(double) + sizeof(uint16_t) + sizeof(double) * 2 * (size_t)bw_ns) +
-                                (size_t)N * NTmax * W * sizeof(double);
+        const size_t row_tabs = (size_t)p.n_grids * p.NTmax * W * (sizeof(double) + sizeof(uint16_t) + sizeof(double) * 2 * (size_t)bw_ns) +
+                                (size_t)c.N * p.NTmax * W * sizeof(double);
         const int oh = ctx->opt[TSF_OPT_HARM];
-        a.harm_pf = (harm != 0 && (oh == 2 || (oh != 1 && !aligned && row_tabs > ((size_t)256 << 20)))) ? 1 : 0;
+        a.harm_pf = (harm != 0 && (oh == 2 || (oh != 1 && !c.aligned && row_tabs > ((size_t)256 << 20)))) ? 1 : 0;
         if (harm != 0 && lat_U > 0) a.harm_pf = 1;         // (the lattice form exists with the row prefetch only)
     }
     a.opt_coop_sparse = ctx->opt[TSF_OPT_SPARSE_EXTRA] != 2 ? 1 : 0;     // (2: the sparse fit kernel with the 64-column tail, for A/B runs)
-    ctx->last_sp_flag = nullptr;
-    if (sparse_try) {
+    if (p.sparse_try) {
         a.sp_meta = (const uint32_t *)(ws + l.spm); a.sp_prog = (const unsigned long long *)(ws + l.spp);
         a.sp_flag = (int *)(ws + l.counter) + 8;
-        ctx->last_sp_flag = a.sp_flag;
     }
-    // scheduling hints of tsf_set_cost_hints: for this call if they were given for this many series; used once
-    const int order_buf = (ctx->order_n == N && !theta_in) ? (ctx->order_next ^ 1) : -1;
-    if (order_buf >= 0) a.order = ctx->order_dev[order_buf];
-    else if (grid_order && ctx->opt[TSF_OPT_GRID_ORDER] != 0) a.order = grid_order;       // series grouped by shared grid (fit_host_one)
+    return a;
+}
+
+// scheduling hints of tsf_set_cost_hints: for this call if they were given for this many series; used once.
+// Returns the hint buffer the launch reads, or -1.
+static int take_order_hints(tsf_ctx *ctx, const FitCall &c, FitArgs *a)
+{
+    const int order_buf = (ctx->order_n == c.N && !c.theta_in) ? (ctx->order_next ^ 1) : -1;
+    if (order_buf >= 0) a->order = ctx->order_dev[order_buf];
+    else if (c.grid_order && ctx->opt[TSF_OPT_GRID_ORDER] != 0) a->order = c.grid_order;       // series grouped by shared grid (fit_host_one)
     ctx->order_n = 0;
-    const int slot = (int)(ctx->ev_count % TSF_PROFILE_RING);
-    if (ctx->profiling) HIP_TRY(ctx, hipEventRecord(ctx->ev0[slot], st));
-    int lrc;
+    return order_buf;
+}
+
+// what every quadratic-form launch shares
+static QuadArgs quad_args(const FitRun &r, const FitArgs &a)
+{
+    QuadArgs qa;
+    memset(&qa, 0, sizeof(qa));
+    qa.f = a; qa.Mg = (const double *)(r.ws + r.l.Mg); qa.rbuf = (double *)(r.ws + r.l.rbuf);
+    qa.counter = (int *)(r.ws + r.l.counter); qa.P4 = r.p.qp.P4;
+    return qa;
+}
+
+static int launch_route_newton_quad(const FitRun &r, const FitArgs &a, int *lrc)
+{
+    tsf_ctx *ctx = r.ctx;
+    const DevSpec &hs = r.hs;
+    hipStream_t st = r.c->stream;
+    QuadArgs qa = quad_args(r, a);
+    qa.Mslot = (double *)(r.ws + r.l.Mslot);
+    if (r.c->aligned && !(ctx->opt[TSF_OPT_DEBUG_ASYNC_SCRATCH] > 0 && (ctx->opt[TSF_OPT_DEBUG_ASYNC_SCRATCH] & 1))) {
+        const size_t need = newton_batch_scratch_bytes(hs.KP, fit_P(hs.n_cp, hs.K) | 1, r.c->N, r.p.NTmax, ctx->n_cu, ctx->opt);
+        if (need > ctx->nb_ws_bytes) {
+            if (ctx->nb_ws) { HIP_TRY(ctx, hipFree(ctx->nb_ws)); ctx->nb_ws = nullptr; ctx->nb_ws_bytes = 0; }
+            if (hipMalloc(&ctx->nb_ws, need) == hipSuccess) ctx->nb_ws_bytes = need;
+            else { ctx->nb_ws = nullptr; (void)hipGetLastError(); }       // no room: the one-series-per-wave kernel
+        }
+        qa.nb_buf = ctx->nb_ws; qa.nb_bytes = ctx->nb_ws_bytes;
+    }
+    HIP_TRY(ctx, hipMemsetAsync(qa.counter, 0, sizeof(int), st));
+    *lrc = launch_newton_quad(hs.KP, r.p.qp, qa, (double *)(r.ws + r.l.Mg), fit_P(hs.n_cp, hs.K) | 1, ctx->n_cu, st);
+    // (-1: this shape does not fit the quadratic-form Newton kernel's LDS -- the residual-form kernel has no such limit)
+    if (*lrc == -1) *lrc = pick_newton_launch(hs.growth, r.mode)(hs.KP, a, fit_P(hs.n_cp, hs.K), st);
+    return 0;
+}
+
+static int launch_route_quad(const FitRun &r, const FitArgs &a, int *lrc, bool *map_done)
+{
+    tsf_ctx *ctx = r.ctx;
+    const tsf_spec *spec = r.spec;
+    const DevSpec &hs = r.hs;
+    const FitPlan &p = r.p;
+    hipStream_t st = r.c->stream;
+    QuadArgs qa = quad_args(r, a);
+    qa.Mslot = (double *)(r.ws + r.l.Mslot);
+    qa.recenter_every = spec->recenter_every; qa.recenter_ratio = spec->recenter_ratio;
+    qa.Mpre = p.quad_pre ? qa.Mg : nullptr; qa.n_pre = p.quad_pre;
+    qa.gram_harm = p.gram_harm; qa.resid_harm = p.resid_harm;
+    HIP_TRY(ctx, hipMemsetAsync(qa.counter, 0, sizeof(int), st));
+    *lrc = -1;
+    if (spec->converge == TSF_CONVERGE_MAP && p.qp.PPL == 1 && ctx->opt[TSF_OPT_MAP_DIRECT] != 0) {
+        // converge = MAP where the posterior is a quadratic form in everything but sigma: the estimate itself by
+        // alternating exact minimisations (tsf_map_quad.h) -- no L-BFGS trajectory, no continuation
+        qa.f.map_max_iter = spec->map_max_iter; qa.f.map_tol = spec->map_tol;
+        *lrc = launch_map_quad(hs.KP, p.qp, qa, (double *)(r.ws + r.l.Mg), fit_P(hs.n_cp, hs.K) | 1, st);
+        if (*lrc == 0) *map_done = true;
+    }
+    if (*lrc == -1) *lrc = launch_quad(hs.KP, p.qp, qa, (double *)(r.ws + r.l.Mg), st);
+    return 0;
+}
+
+static int launch_route_mfma(const FitRun &r, const FitArgs &a, int *lrc)
+{
+    tsf_ctx *ctx = r.ctx;
+    const DevSpec &hs = r.hs;
+    const MfmaPlan &mp = r.p.mp;
+    const WsLayout &l = r.l;
+    char *ws = r.ws;
+    hipStream_t st = r.c->stream;
+    MfmaTabs mt;
+    memset(&mt, 0, sizeof(mt));
+    int *flags = (int *)(ws + l.counter);        // [0] work queue head, [1] changepoint-row overflow
+    HIP_TRY(ctx, hipMemsetAsync(flags, 0, 2 * sizeof(int), st));
+    mt.XF = (const double *)(ws + l.mXF); mt.XB = (const double *)(ws + l.mXB);
+    mt.XT = (const double *)(ws + l.mXT); mt.tq = (const double *)(ws + l.mtq);
+    mt.cq = (const uint16_t *)(ws + l.mcq); mt.cpof = (const int8_t *)(ws + l.mcpof);
+    mt.yq = (const double *)(ws + l.myq); mt.hist = (double *)(ws + l.mhist);
+    mt.counter = flags; mt.overflow = flags + 1;
+    mt.NG = mp.NG; mt.KF = mp.KF; mt.NCB = mp.NCB; mt.rr0 = mp.rr0; mt.run_if_overflow = 0;
+    *lrc = launch_mfma_layout(a, hs.KP, mt, (double *)(ws + l.mXF), (double *)(ws + l.mXB),
+                              (double *)(ws + l.mXT), (double *)(ws + l.mtq), (uint16_t *)(ws + l.mcq),
+                              (int8_t *)(ws + l.mcpof), (double *)(ws + l.myq), flags + 1, st);
+    if (*lrc == 0) {
+        if (ctx->profiling) HIP_TRY(ctx, hipEventRecord(ctx->ev0[r.slot], st));   // the fit kernel proper
+        *lrc = launch_mfma(hs.KP, hs.growth, r.mode, a, mt, mp.blocks, st);
+    }
+    if (*lrc == 0) {
+        // fallback, decided on the device: runs only if the layout kernel found a chunk with more
+        // changepoint rows than the trend block holds (long runs of equal timestamps)
+        FitArgs fb = a;
+        fb.run_flag = flags + 1; fb.run_if = 1;
+        *lrc = pick_launch(hs.growth, r.mode)(hs.KP, fb, 0, st);
+    }
+    return 0;
+}
+
+// the one-wave residual kernel (a fit, or tsf_eval's single evaluation) with its cooperative tail
+static int launch_route_wave(const FitRun &r, FitArgs &a, int *lrc)
+{
+    tsf_ctx *ctx = r.ctx;
+    const FitPlan &p = r.p;
+    hipStream_t st = r.c->stream;
+    if (p.coop) {
+        a.coop_ctl = (int *)(r.ws + r.l.counter);
+        a.coop_list = (int32_t *)(r.ws + r.l.clist);
+        a.coop_slots = (double *)(r.ws + r.l.cslots);
+        a.coop_max = p.coop_slots; a.coop_stride = p.coop_stride;
+        a.coop_after = p.coop_after;
+        a.coop_blocks = ctx->n_cu;
+        {
+            // Hand-over point of the tail rule: the one-wave kernel's waves run alone on their SIMDs by then (13.6 us per
+            // evaluation) and a cooperative workgroup needs 5.05: up to ~2.7 fits per CU the cooperative kernel has
+            // the higher aggregate rate even though they queue for its workgroups.  Default 2 per CU.
+            const int pct = ctx->opt[TSF_OPT_COOP_TAIL] > 0 ? ctx->opt[TSF_OPT_COOP_TAIL] : 200;
+            a.coop_tail_at = (int)((int64_t)ctx->n_cu * (pct > 400 ? 400 : pct) / 100);
+            if (a.coop_tail_at < 1) a.coop_tail_at = 1;
+        }
+        HIP_TRY(ctx, hipMemsetAsync(a.coop_ctl, 0, 4 * sizeof(int), st));
+    }
+    *lrc = pick_launch(r.hs.growth, r.mode)(r.hs.KP, a, r.c->theta_in != nullptr, st);
+    return 0;
+}
+
+// the planned route's kernels; *lrc: the launch function's code, *map_done: the route computed the MAP estimate itself
+static int launch_route(const FitRun &r, FitArgs &a, int *lrc, bool *map_done)
+{
+    const DevSpec &hs = r.hs;
+    hipStream_t st = r.c->stream;
+    switch (r.p.route) {
+    case TSF_ROUTE_NEWTON_QUAD:
+        return launch_route_newton_quad(r, a, lrc);
+    case TSF_ROUTE_NEWTON:
+        *lrc = pick_newton_launch(hs.growth, r.mode)(hs.KP, a, fit_P(hs.n_cp, hs.K), st);
+        return 0;
+    case TSF_ROUTE_QUAD_EVAL: {
+        QuadArgs qa = quad_args(r, a);
+        qa.resid_harm = r.p.resid_harm;
+        *lrc = launch_eval_quad(hs.KP, r.p.qp, qa, (double *)(r.ws + r.l.Mg), r.c->theta_ref, st);
+        return 0;
+    }
+    case TSF_ROUTE_QUAD_LBFGS:
+        return launch_route_quad(r, a, lrc, map_done);
+    case TSF_ROUTE_MFMA:
+        return launch_route_mfma(r, a, lrc);
+    default:
+        return launch_route_wave(r, a, lrc);
+    }
+}
+
+// converge = MAP: from where the optimiser's own tests stopped every fit on to the maximum a posteriori estimate
+// (tsf_map_kernels.h), on the same stream behind whichever kernels ran the fit; inside the profiled interval
+static int launch_map_continuation(const FitRun &r, FitArgs &a)
+{
+    const FitPlan &p = r.p;
+    a.map_max_iter = r.spec->map_max_iter; a.map_tol = r.spec->map_tol; a.map_harm = p.map_harm;
+    if (p.map_harm && p.lat_U == 0) a.Bw = (const double *)(r.ws + r.l.Bw);
+    if (p.map_harm && p.lat_U > 0) a.Bu = (const double *)(r.ws + r.l.Bw);
+    a.order = nullptr; a.run_flag = nullptr;
+    return pick_map_launch(r.hs.growth, r.mode)(r.hs.KP, a, r.c->stream);
+}
+
+// Common driver: setup kernels + fit (or eval-only) kernel on device pointers.  plan_fit (tsf_fit_plan.h) decides
+// what runs; the steps below only carry it out.
+static int run_fit(tsf_ctx *ctx, const tsf_spec *spec, const FitCall &c, tsf_fit_out *out)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    FitRun r;
+    r.ctx = ctx; r.spec = spec; r.c = &c;
+    int rc = fit_validate(ctx, spec, c, out, &r.hs, &r.mode);
+    if (rc) return rc;
+    const MemQuery mem = {ctx_mem_avail, ctx};
+    r.p = plan_fit(r.hs, r.mode, spec, fit_shape(c), ctx->opt, ctx->n_cu, mem);
+    const FitPlan &p = r.p;
+    ctx->last_plan = p;
+    if (p.rc) return fail(ctx, fit_plan_message(p.err));
+    // the slot records of the several-series-per-wave Newton kernel are cached between Newton calls, but at most
+    // TSF_NB_KEEP bytes of them outlive a call that does not use them
+    if (!(p.route == TSF_ROUTE_NEWTON_QUAD && c.aligned) && ctx->nb_ws_bytes > TSF_NB_KEEP) {
+        HIP_TRY(ctx, hipFree(ctx->nb_ws));
+        ctx->nb_ws = nullptr; ctx->nb_ws_bytes = 0;
+    }
+    r.l = ws_layout(c.N, p, r.hs.KP);
+    rc = ensure_ws(ctx, r.l.total, c.N, p.NTmax, !c.aligned);
+    if (rc) return rc;
+    r.ws = (char *)ctx->ws;
+    r.grid_of = p.shared_grids ? c.grid_of : nullptr;
+    r.grid_rows = p.shared_grids ? c.grid_rows : nullptr;
+    rc = fit_setup(r);
+    if (rc) return rc;
+    FitArgs a = fit_args(r, out);
+    ctx->last_sp_flag = a.sp_flag;
+    const int order_buf = take_order_hints(ctx, c, &a);
+    r.slot = (int)(ctx->ev_count % TSF_PROFILE_RING);
+    if (ctx->profiling) HIP_TRY(ctx, hipEventRecord(ctx->ev0[r.slot], c.stream));
+    int lrc = 0;
     bool map_done = false;
-    if (newton_quad) {
-        QuadArgs qa;
-        memset(&qa, 0, sizeof(qa));
-        qa.f = a; qa.Mg = (const double *)(ws + l.Mg); qa.Mslot = (double *)(ws + l.Mslot);
-        qa.rbuf = (double *)(ws + l.rbuf);
-        qa.counter = (int *)(ws + l.counter); qa.P4 = qp.P4;
-        if (aligned && !(ctx->opt[TSF_OPT_DEBUG_ASYNC_SCRATCH] > 0 && (ctx->opt[TSF_OPT_DEBUG_ASYNC_SCRATCH] & 1))) {
-            const size_t need = newton_batch_scratch_bytes(hs.KP, fit_P(hs.n_cp, hs.K) | 1, N, NTmax, ctx->n_cu, ctx->opt);
-            if (need > ctx->nb_ws_bytes) {
-                if (ctx->nb_ws) { HIP_TRY(ctx, hipFree(ctx->nb_ws)); ctx->nb_ws = nullptr; ctx->nb_ws_bytes = 0; }
-                if (hipMalloc(&ctx->nb_ws, need) == hipSuccess) ctx->nb_ws_bytes = need;
-                else { ctx->nb_ws = nullptr; (void)hipGetLastError(); }       // no room: the one-series-per-wave kernel
-            }
-            qa.nb_buf = ctx->nb_ws; qa.nb_bytes = ctx->nb_ws_bytes;
-        }
-        HIP_TRY(ctx, hipMemsetAsync(qa.counter, 0, sizeof(int), st));
-        lrc = launch_newton_quad(hs.KP, qp, qa, (double *)(ws + l.Mg), fit_P(hs.n_cp, hs.K) | 1, ctx->n_cu, st);
-        // (-1: this shape does not fit the quadratic-form Newton kernel's LDS -- the residual-form kernel has no such limit)
-        if (lrc == -1) lrc = pick_newton_launch(hs.growth, mode)(hs.KP, a, fit_P(hs.n_cp, hs.K), st);
-    } else if (newton) {
-        lrc = pick_newton_launch(hs.growth, mode)(hs.KP, a, fit_P(hs.n_cp, hs.K), st);
-    } else if (quad_eval) {
-        QuadArgs qa;
-        memset(&qa, 0, sizeof(qa));
-        qa.f = a; qa.Mg = (const double *)(ws + l.Mg); qa.rbuf = (double *)(ws + l.rbuf);
-        qa.counter = (int *)(ws + l.counter); qa.P4 = qp.P4;
-        qa.resid_harm = resid_harm;
-        lrc = launch_eval_quad(hs.KP, qp, qa, (double *)(ws + l.Mg), theta_ref, st);
-    } else if (quad) {
-        QuadArgs qa;
-        memset(&qa, 0, sizeof(qa));
-        qa.f = a; qa.Mg = (const double *)(ws + l.Mg); qa.Mslot = (double *)(ws + l.Mslot);
-        qa.rbuf = (double *)(ws + l.rbuf);
-        qa.counter = (int *)(ws + l.counter); qa.P4 = qp.P4;
-        qa.recenter_every = spec->recenter_every; qa.recenter_ratio = spec->recenter_ratio;
-        qa.dbg = nullptr; qa.nb_buf = nullptr; qa.nb_bytes = 0;
-        qa.Mpre = quad_pre ? qa.Mg : nullptr; qa.n_pre = quad_pre;
-        qa.gram_harm = gram_harm; qa.resid_harm = resid_harm;
-        HIP_TRY(ctx, hipMemsetAsync(qa.counter, 0, sizeof(int), st));
-        lrc = -1;
-        if (spec->converge == TSF_CONVERGE_MAP && qp.PPL == 1 && ctx->opt[TSF_OPT_MAP_DIRECT] != 0) {
-            // converge = MAP where the posterior is a quadratic form in everything but sigma: the estimate itself by
-            // alternating exact minimisations (tsf_map_quad.h) -- no L-BFGS trajectory, no continuation
-            qa.f.map_max_iter = spec->map_max_iter; qa.f.map_tol = spec->map_tol;
-            lrc = launch_map_quad(hs.KP, qp, qa, (double *)(ws + l.Mg), fit_P(hs.n_cp, hs.K) | 1, st);
-            if (lrc == 0) map_done = true;
-        }
-        if (lrc == -1) lrc = launch_quad(hs.KP, qp, qa, (double *)(ws + l.Mg), st);
-    } else if (mp.on) {
-        MfmaTabs mt;
-        memset(&mt, 0, sizeof(mt));
-        int *flags = (int *)(ws + l.counter);        // [0] work queue head, [1] changepoint-row overflow
-        HIP_TRY(ctx, hipMemsetAsync(flags, 0, 2 * sizeof(int), st));
-        mt.XF = (const double *)(ws + l.mXF); mt.XB = (const double *)(ws + l.mXB);
-        mt.XT = (const double *)(ws + l.mXT); mt.tq = (const double *)(ws + l.mtq);
-        mt.cq = (const uint16_t *)(ws + l.mcq); mt.cpof = (const int8_t *)(ws + l.mcpof);
-        mt.yq = (const double *)(ws + l.myq); mt.hist = (double *)(ws + l.mhist);
-        mt.counter = flags; mt.overflow = flags + 1;
-        mt.NG = mp.NG; mt.KF = mp.KF; mt.NCB = mp.NCB; mt.rr0 = mp.rr0; mt.run_if_overflow = 0;
-        lrc = launch_mfma_layout(a, hs.KP, mt, (double *)(ws + l.mXF), (double *)(ws + l.mXB),
-                                 (double *)(ws + l.mXT), (double *)(ws + l.mtq), (uint16_t *)(ws + l.mcq),
-                                 (int8_t *)(ws + l.mcpof), (double *)(ws + l.myq), flags + 1, st);
-        if (lrc == 0) {
-            if (ctx->profiling) HIP_TRY(ctx, hipEventRecord(ctx->ev0[slot], st));   // the fit kernel proper
-            lrc = launch_mfma(hs.KP, hs.growth, mode, a, mt, mp.blocks, st);
-        }
-        if (lrc == 0) {
-            // fallback, decided on the device: runs only if the layout kernel found a chunk with more
-            // changepoint rows than the trend block holds (long runs of equal timestamps)
-            FitArgs fb = a;
-            fb.run_flag = flags + 1; fb.run_if = 1;
-            lrc = pick_launch(hs.growth, mode)(hs.KP, fb, 0, st);
-        }
-    } else {
-        if (coop) {
-            a.coop_ctl = (int *)(ws + l.counter);
-            a.coop_list = (int32_t *)(ws + l.clist);
-            a.coop_slots = (double *)(ws + l.cslots);
-            a.coop_max = coop_slots; a.coop_stride = coop_stride;
-            a.coop_after = coop_after;
-            a.coop_blocks = ctx->n_cu;
-            {
-                // Hand-over point of the tail rule: the one-wave kernel's waves run alone on their SIMDs by then (13.6 us per
-                // evaluation) and a cooperative workgroup needs 5.05: up to ~2.7 fits per CU the cooperative kernel has
-                // the higher aggregate rate even though they queue for its workgroups.  Default 2 per CU.
-                const int pct = ctx->opt[TSF_OPT_COOP_TAIL] > 0 ? ctx->opt[TSF_OPT_COOP_TAIL] : 200;
-                a.coop_tail_at = (int)((int64_t)ctx->n_cu * (pct > 400 ? 400 : pct) / 100);
-                if (a.coop_tail_at < 1) a.coop_tail_at = 1;
-            }
-            HIP_TRY(ctx, hipMemsetAsync(a.coop_ctl, 0, 4 * sizeof(int), st));
-        }
-        lrc = pick_launch(hs.growth, mode)(hs.KP, a, theta_in != nullptr, st);
-    }
-    // converge = MAP: from where the optimiser's own tests stopped every fit on to the maximum a posteriori estimate
-    // (tsf_map_kernels.h), on the same stream behind whichever kernels ran the fit; inside the profiled interval
-    if (lrc == 0 && spec->converge == TSF_CONVERGE_MAP && theta_in == nullptr && !map_done) {
-        a.map_max_iter = spec->map_max_iter; a.map_tol = spec->map_tol; a.map_harm = map_harm;
-        if (map_harm && lat_U == 0) a.Bw = (const double *)(ws + l.Bw);
-        if (map_harm && lat_U > 0) a.Bu = (const double *)(ws + l.Bw);
-        a.order = nullptr; a.run_flag = nullptr;
-        lrc = pick_map_launch(hs.growth, mode)(hs.KP, a, st);
-    }
-    if (ctx->profiling) { HIP_TRY(ctx, hipEventRecord(ctx->ev1[slot], st)); ctx->ev_count++; }
+    rc = launch_route(r, a, &lrc, &map_done);
+    if (rc) return rc;
+    if (lrc == 0 && spec->converge == TSF_CONVERGE_MAP && c.theta_in == nullptr && !map_done) lrc = launch_map_continuation(r, a);
+    if (ctx->profiling) { HIP_TRY(ctx, hipEventRecord(ctx->ev1[r.slot], c.stream)); ctx->ev_count++; }
     if (order_buf >= 0) {       // the launch above reads the hint buffer: tsf_set_cost_hints waits for this before rewriting it
         if (!ctx->order_ev[order_buf]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->order_ev[order_buf], hipEventDisableTiming));
-        HIP_TRY(ctx, hipEventRecord(ctx->order_ev[order_buf], st));
+        HIP_TRY(ctx, hipEventRecord(ctx->order_ev[order_buf], c.stream));
         ctx->order_busy[order_buf] = 1;
     }
     if (lrc != 0) {
@@ -856,17 +788,50 @@ static int run_fit(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int aligned, i
     return 0;
 }
 
+extern "C" int tsf_fit_plan_info_size(void) { return (int)sizeof(tsf_fit_plan_info); }
+extern "C" const char *tsf_fit_plan_error(int32_t err) { return fit_plan_message(err); }
+
+static int64_t given_mem_avail(void *arg) { return *(const int64_t *)arg; }
+
+extern "C" int tsf_fit_plan(const tsf_spec *spec, const tsf_fit_shape *shape, const int *opt, int n_cu, int64_t mem_avail,
+                            tsf_fit_plan_info *out)
+{
+    if (!spec || !shape || !opt || !out || shape->N <= 0 || n_cu < 1) return -1;
+    memset(out, 0, sizeof(*out));
+    DevSpec hs;
+    int mode = 0;
+    int rc = build_devspec(nullptr, spec, &hs, &mode);
+    if (rc) return rc;
+    const MemQuery mem = {given_mem_avail, &mem_avail};
+    const FitPlan p = plan_fit(hs, mode, spec, *shape, opt, n_cu, mem);
+    fit_plan_info(p, out);
+    return p.rc;
+}
+
+extern "C" int tsf_last_fit_plan(const tsf_ctx *ctx, tsf_fit_plan_info *out)
+{
+    if (!ctx || !out) return -1;
+    fit_plan_info(ctx->last_plan, out);
+    return 0;
+}
+
+static bool fit_out_complete(const tsf_fit_out &f)
+{
+    return f.theta && f.y_scale && f.fval && f.status && f.n_iter && f.n_eval && f.grid;
+}
+
 extern "C" int tsf_fit_aligned_dev(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t T,
                                    const int64_t *ds, const void *y, int32_t y_dtype,
                                    const double *floor_, const double *cap, const double *extra,
                                    tsf_fit_out *out, void *stream)
 {
     if (!ctx) return -1;
-    if (!out || !out->theta || !out->y_scale || !out->fval || !out->status || !out->n_iter ||
-        !out->n_eval || !out->grid)
-        return fail(ctx, "tsf_fit_out has NULL members");
-    return run_fit(ctx, spec, N, 1, T, nullptr, 0, T, ds, y, y_dtype, floor_, cap, extra, out,
-                   nullptr, nullptr, (hipStream_t)stream);
+    if (!out || !fit_out_complete(*out)) return fail(ctx, "tsf_fit_out has NULL members");
+    FitCall c = {};
+    c.N = N; c.aligned = 1; c.T = T; c.max_T = T;
+    c.ds = ds; c.y = y; c.y_dtype = y_dtype; c.floor = floor_; c.cap = cap; c.extra = extra;
+    c.stream = (hipStream_t)stream;
+    return run_fit(ctx, spec, c, out);
 }
 
 extern "C" int tsf_fit_ragged_dev(tsf_ctx *ctx, const tsf_spec *spec, int64_t N,
@@ -877,11 +842,12 @@ extern "C" int tsf_fit_ragged_dev(tsf_ctx *ctx, const tsf_spec *spec, int64_t N,
 {
     if (!ctx) return -1;
     if (!offsets) return fail(ctx, "offsets is NULL");
-    if (!out || !out->theta || !out->y_scale || !out->fval || !out->status || !out->n_iter ||
-        !out->n_eval || !out->grid)
-        return fail(ctx, "tsf_fit_out has NULL members");
-    return run_fit(ctx, spec, N, 0, 0, offsets, total_rows, max_T, ds, y, y_dtype, floor_, cap,
-                   extra, out, nullptr, nullptr, (hipStream_t)stream);
+    if (!out || !fit_out_complete(*out)) return fail(ctx, "tsf_fit_out has NULL members");
+    FitCall c = {};
+    c.N = N; c.offsets = offsets; c.total_rows = total_rows; c.max_T = max_T;
+    c.ds = ds; c.y = y; c.y_dtype = y_dtype; c.floor = floor_; c.cap = cap; c.extra = extra;
+    c.stream = (hipStream_t)stream;
+    return run_fit(ctx, spec, c, out);
 }
 
 // ---- host-pointer wrappers --------------------------------------------------------------------
@@ -1162,15 +1128,18 @@ static int fit_host_one(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int align
         }
     }
     if (host_timing) t_h2d = now();
-    int rc = run_fit(ctx, spec, N, aligned, T, d_off.as<int64_t>(), total, max_T, d_ds.as<int64_t>(),
-                     d_y.p, y_dtype, floor_ ? d_floor.as<double>() : nullptr,
-                     cap ? d_cap.as<double>() : nullptr,
-                     spec->n_extra > 0 ? d_extra.as<double>() : nullptr, &dout,
-                     theta_in ? d_thin.as<double>() : nullptr,
-                     theta_in ? d_grad.as<double>() : nullptr, nullptr, lat_base, lat_step, lat_U,
-                     (theta_in && theta_ref) ? d_thref.as<double>() : nullptr,
-                     n_distinct > 0 ? d_gof.as<int32_t>() : nullptr, n_distinct > 0 ? d_grows.as<int64_t>() : nullptr, n_distinct,
-                     n_distinct > 0 ? d_gord.as<int32_t>() : nullptr);
+    FitCall c = {};
+    c.N = N; c.aligned = aligned; c.T = T; c.offsets = d_off.as<int64_t>(); c.total_rows = total; c.max_T = max_T;
+    c.ds = d_ds.as<int64_t>(); c.y = d_y.p; c.y_dtype = y_dtype;
+    if (floor_) c.floor = d_floor.as<double>();
+    if (cap) c.cap = d_cap.as<double>();
+    if (spec->n_extra > 0) c.extra = d_extra.as<double>();
+    if (theta_in) { c.theta_in = d_thin.as<double>(); c.grad_out = d_grad.as<double>(); }
+    if (theta_in && theta_ref) c.theta_ref = d_thref.as<double>();
+    c.lat_base = lat_base; c.lat_step = lat_step; c.lat_U = lat_U;
+    if (n_distinct > 0) { c.grid_of = d_gof.as<int32_t>(); c.grid_rows = d_grows.as<int64_t>(); c.grid_order = d_gord.as<int32_t>(); }
+    c.n_distinct = n_distinct;
+    int rc = run_fit(ctx, spec, c, &dout);
     if (rc) return rc;
     HIP_TRY(ctx, hipDeviceSynchronize());
     if (host_timing) t_fit = now();
@@ -2387,7 +2356,9 @@ extern "C" int tsf_design(tsf_ctx *ctx, const tsf_spec *spec, int32_t T, const i
     if (rc) return rc;
     if (hs.n_extra > 0 && !extra) return fail(ctx, "extra is NULL");
     const int NT = (T + W - 1) / W;
-    const WsLayout l = ws_layout(1, 1, NT, hs.KP);
+    FitPlan one = {};               // one grid's tables, nothing else
+    one.n_grids = 1; one.NTmax = NT;
+    const WsLayout l = ws_layout(1, one, hs.KP);
     rc = ensure_ws(ctx, l.total);
     if (rc) return rc;
     char *ws = (char *)ctx->ws;
@@ -2804,13 +2775,18 @@ static int cv_fit(tsf_ctx *ctx, CvCall &S, CvGroup &E, const tsf_spec &gs, const
     go.status = g_st.as<int32_t>(); go.n_iter = g_it.as<int32_t>(); go.n_eval = g_ev.as<int32_t>();
     go.grid = g_gr.as<tsf_grid_info>();
     const int64_t nd = E.n_distinct;
-    int rc = run_fit(ctx, &gs, G, 0, 0, E.d_goff.as<int64_t>(), E.rows, E.maxT, E.d_gds.as<int64_t>(), E.d_gy.p, S.y_dtype,
-                     S.has_floor ? E.d_gfl.as<double>() : nullptr, S.has_cap ? E.d_gcap.as<double>() : nullptr,
-                     S.n_extra > 0 ? E.d_gex.as<double>() : nullptr, &go, nullptr, nullptr, nullptr, 0, 0, 0, nullptr,
-                     nd > 0 ? E.d_gof.as<int32_t>() : nullptr, nd > 0 ? E.d_grows.as<int64_t>() : nullptr, nd,
-                     nd > 0 ? E.d_gord.as<int32_t>() : nullptr, E.d_gkeep.p ? E.d_gkeep.as<int32_t>() : nullptr);
+    FitCall c = {};
+    c.N = G; c.offsets = E.d_goff.as<int64_t>(); c.total_rows = E.rows; c.max_T = E.maxT;
+    c.ds = E.d_gds.as<int64_t>(); c.y = E.d_gy.p; c.y_dtype = S.y_dtype;
+    if (S.has_floor) c.floor = E.d_gfl.as<double>();
+    if (S.has_cap) c.cap = E.d_gcap.as<double>();
+    if (S.n_extra > 0) c.extra = E.d_gex.as<double>();
+    if (nd > 0) { c.grid_of = E.d_gof.as<int32_t>(); c.grid_rows = E.d_grows.as<int64_t>(); c.grid_order = E.d_gord.as<int32_t>(); }
+    c.n_distinct = nd;
+    if (E.d_gkeep.p) c.grid_keep = E.d_gkeep.as<int32_t>();
+    int rc = run_fit(ctx, &gs, c, &go);
     if (rc) return rc;
-    *n_grids += ctx->last_n_grids;
+    *n_grids += ctx->last_plan.n_grids;
     *n_launches += 1;
     hipLaunchKernelGGL(cv_scatter_kernel, dim3((unsigned)G), dim3(64), 0, nullptr, G, E.d_gf.as<int32_t>(), stride, go, dst);
     HIP_TRY(ctx, hipGetLastError());
@@ -3082,9 +3058,13 @@ static int fit_whole_group(tsf_ctx *ctx, CvCall &S, const CvViews &whole, const 
     go.theta = g_th.as<double>(); go.y_scale = g_ys.as<double>(); go.fval = g_fv.as<double>();
     go.status = g_st.as<int32_t>(); go.n_iter = g_it.as<int32_t>(); go.n_eval = g_ev.as<int32_t>();
     go.grid = g_gr.as<tsf_grid_info>();
-    int rc = run_fit(ctx, &gs, G, 1, T, nullptr, 0, T, S.d_ds.as<int64_t>(), d_gy.p, S.y_dtype,
-                     S.has_floor ? d_gfl.as<double>() : nullptr, S.has_cap ? d_gcap.as<double>() : nullptr,
-                     S.n_extra > 0 ? S.d_ex.as<double>() : nullptr, &go, nullptr, nullptr, nullptr);
+    FitCall c = {};
+    c.N = G; c.aligned = 1; c.T = T; c.max_T = T;
+    c.ds = S.d_ds.as<int64_t>(); c.y = d_gy.p; c.y_dtype = S.y_dtype;
+    if (S.has_floor) c.floor = d_gfl.as<double>();
+    if (S.has_cap) c.cap = d_gcap.as<double>();
+    if (S.n_extra > 0) c.extra = S.d_ex.as<double>();
+    int rc = run_fit(ctx, &gs, c, &go);
     if (rc) return rc;
     *n_launches += 1;
     hipLaunchKernelGGL(tune_scatter_kernel, dim3((unsigned)G), dim3(64), 0, nullptr, G, d_sel.as<int32_t>(), stride, go, dst);
@@ -3463,11 +3443,6 @@ extern "C" int tsf_screen_rows(tsf_ctx *ctx, int64_t N, int32_t T, const int64_t
     if (out->n_new) HIP_TRY(ctx, hipMemcpy(out->n_new, d_nn.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
     if (out->n_flagged) HIP_TRY(ctx, hipMemcpy(out->n_flagged, d_nf.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
     return 0;
-}
-
-static bool fit_out_complete(const tsf_fit_out &f)
-{
-    return f.theta && f.y_scale && f.fval && f.status && f.n_iter && f.n_eval && f.grid;
 }
 
 extern "C" int tsf_fit_screened(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t T, const int64_t *offsets,
