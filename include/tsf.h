@@ -501,7 +501,7 @@ int tsf_score_actuals_dev(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t
  * outside [0, G), NULL series_key, tsf_predict's grid checks, n_extra > 0 with NULL extra_future, logistic growth
  * without cap, n_grids not 1 or N; quantiles: a bad n_q or level, an output set that wants none of q / cum_q / samples.
  * N == 0 is a legal no-op.  A failed device allocation in create returns < 0 and leaves nothing behind.  A HIP failure
- * in the middle of an add poisons the handle: every later call on it returns < 0. */
+ * in the middle of an add (or of tsf_rollup_set_totals, below) poisons the handle: every later call on it returns < 0. */
 typedef struct tsf_rollup tsf_rollup;
 int tsf_rollup_create(tsf_ctx *ctx, int64_t G, int32_t H, const int64_t *ds_future /* [H] */, int32_t n_samples,
                       uint64_t seed, tsf_rollup **out);
@@ -518,6 +518,97 @@ typedef struct {
 } tsf_rollup_out;
 int tsf_rollup_quantiles(tsf_rollup *r, int32_t n_q, const double *quantiles, tsf_rollup_out *out);
 void tsf_rollup_free(tsf_rollup *r);        /* before tsf_destroy of its context */
+
+/* ---- reconciliation: member forecasts and directly fitted totals made coherent -----------------------
+ * A roll-up's total is bottom-up: the sum of its members' draws.  Whoever forecasts such a hierarchy usually fits the
+ * total directly as well (the sum of twenty noisy histories has a far better signal than any one of them), and then the
+ * direct forecast of the total and the sum of the member forecasts disagree, and the members do not use what the total
+ * knows.  Reconciliation projects the incoherent pair (total, members) onto the coherent subspace by weighted least
+ * squares, sample by sample, so that the reconciled quantiles are quantiles of coherent draws -- on the device, where
+ * the draws already are (doing it by hand moves N * H * n_samples * 8 bytes to the host).
+ * Reference interface replaced: none (neither the reference nor fbprophet has such a function: none of this is
+ * Prophet's); parity unpinned (what is pinned is the contract below, against tsf_predict_quantiles' draws and
+ * tsf_rollup_quantiles' accumulators).  Host pointers only, like tsf_rollup_*.
+ * Timing: tools/bench_reconcile.py; DESIGN.md 5j.
+ *
+ * Method (two-level hierarchy, diagonal weights: the MinT / WLS solution with a diagonal covariance, applied to joint
+ * samples).  Group g has members i with draws x_i[h][s] and one directly fitted total with draws t_g[h][s]; w_i > 0 and
+ * v_g > 0 are the caller's estimates of the forecast error variance of each base forecast; W_g = sum of w_i over the
+ * group.  Minimising (t - sum b_i)^2 / v + sum (x_i - b_i)^2 / w_i gives, with d_g[h][s] = t_g[h][s] - acc[g][h][s]
+ * (the incoherence of sample s; acc is the roll-up's sum of member draws),
+ *   lambda_i = w_i / (v_g + W_g),  mu_g = W_g / (v_g + W_g),
+ *   reconciled member x_i + lambda_i * d_g,  reconciled total acc_g + mu_g * d_g.
+ * sum_i lambda_i = mu_g, so the reconciled members sum to the reconciled total (to rounding).  The total's stream and
+ * the members' streams are independent, so where the weights equal the true variances the reconciled member has variance
+ * w_i - w_i^2 / (v_g + W_g): never wider than before.  The independence caveat of the roll-ups applies unchanged:
+ * members (and the total) are taken as independent given their fits; where their errors are positively correlated in
+ * reality, the spreads are too narrow.
+ *
+ * tsf_reconcile_shares (host only: no context, no device) turns weights into shares.  group [N] in [0, G); w [N] (NULL:
+ * all 1.0); v [G] (NaN: the group has no total).  W_g is summed from +0.0 in ascending member index by plain double
+ * adds; share[i] = w_i / (v_g + W_g) and share_total[g] = W_g / (v_g + W_g), each one add and one divide.  A group whose
+ * v is NaN, or which has no member, gets +0.0 in both.  Returns -1 for a group value outside [0, G) and for a weight
+ * or v that is not finite and positive (NaN v excepted).  Weight policies ('ols': all 1; 'struct': members 1, the total
+ * its member count; residual variances; cross-validation mse) are the caller's, on top of this.
+ *
+ * tsf_rollup_set_totals forecasts Gt directly fitted total series on the roll-up's calendar exactly as tsf_rollup_add
+ * forecasts members (same arguments, checks, refusals and draws: (seed, series_key[n], sample)) and adds them to a second
+ * accumulator: top[G][H][n_samples] = +0.0 + draw, ytop[G][H] = +0.0 + yhat, series n into group[n].  The two buffers
+ * are allocated by the first call and not before: a roll-up that never reconciles costs what it did.  It may be called
+ * once per spec bucket; a group that has a total already, or that appears twice in one call, is refused before any
+ * launch.  Keys distinct from each other and from the members' keys are the caller's business: a total that shares a
+ * key with a member shares its stream, and the independence above is gone.  A HIP failure in the middle poisons the
+ * handle, as for add.
+ *
+ * tsf_rollup_reconcile is the second pass over the members: called after every add and set_totals, with the same
+ * members, keys (and the handle's seed and n_samples), so the draws are the ones that were added.  Arguments as in
+ * tsf_rollup_add, then share [N] (finite, in [0, 1]), the levels as in tsf_predict_quantiles and the outputs.
+ * Contract, in plain double operations (no fused multiply-add):
+ *   d = top[g][h][s] - acc[g][h][s] where group g has a total, +0.0 where it has none;
+ *   sample' = sample + share[n] * d                         (a subtract, a multiply, an add)
+ *   yhat'   = yhat + share[n] * (ytop[g][h] - ysum[g][h])   (the same three; +0.0 in place of the difference without a total)
+ *   q is tsf_predict_quantiles' expression over the ascending sort of sample'; cum_q the same over the running sums
+ *   c[0] = sample'[0], c[h] = c[h-1] + sample'[h] along the rows.
+ * So share = 0 everywhere gives tsf_predict_quantiles' yhat, q, cum_q and samples bit for bit (for every value the
+ * draws produce: -0.0 would become +0.0), and a group without a total leaves its members untouched.  The call modifies
+ * neither accumulator, may be repeated, and poisons nothing.  The result depends neither on how the call is cut into
+ * scratch chunks (512 MB; one sample buffer, two with cum_q) nor on what else is in the call, nor on which outputs are
+ * requested.  No floating-point atomics.  Members that were not added (or other keys) are not detected: d is then not
+ * their incoherence, and that is the caller's business.
+ *
+ * tsf_rollup_reconciled_totals reads the totals: per cell acc + share_total[g] * (top - acc) (the same three operations,
+ * +0.0 for the difference without a total), yhat the same from ysum and ytop; the outputs are tsf_rollup_quantiles'
+ * outputs over that quantity (count: the members added).  share_total [G], finite and in [0, 1].  Groups are processed
+ * in ranges through the context's scratch; neither accumulator is modified.
+ *
+ * Refusals (< 0 with a message, before any launch; the accumulators are untouched and the handle and the context stay
+ * usable): tsf_rollup_add's for set_totals and reconcile; a second total for a group; reconcile or reconciled_totals
+ * before any set_totals (not silent zeros); a share outside [0, 1] or NaN; a bad n_q or level; an output set that
+ * wants none of q / cum_q / samples.  N == 0 (Gt == 0) is a legal no-op.
+ *
+ * Out of scope: hierarchies deeper than two levels; non-diagonal covariance (MinT-shrink); per-row weights; the job
+ * configuration of the modeler and the scorer; _dev variants; more than one GPU. */
+int tsf_reconcile_shares(int64_t N, const int64_t *group, const double *w /* [N], NULL = all 1.0 */, int64_t G,
+                         const double *v /* [G]; NaN = the group has no total */, double *share /* [N] lambda */,
+                         double *share_total /* [G] mu */);
+int tsf_rollup_set_totals(tsf_rollup *r, const tsf_spec *spec, int64_t Gt, const double *theta, const double *y_scale,
+                          const tsf_grid_info *grid, int32_t n_grids, const double *floor, const double *cap,
+                          const double *extra_future, int32_t shared_extra, const int64_t *series_key /* [Gt], required */,
+                          const int64_t *group /* [Gt], the group each total series belongs to */);
+typedef struct {
+    double *yhat;           /* [N][H]        required: the reconciled point forecast */
+    double *q;              /* [N][n_q][H]   per-row quantiles of the reconciled draws; NULL: not wanted */
+    double *cum_q;          /* [N][n_q][H]   quantiles of each reconciled sample's running sum over rows 0..h; NULL: not wanted */
+    double *samples;        /* [N][H][n_samples] the reconciled draws themselves; NULL: not wanted */
+} tsf_reconcile_out;
+int tsf_reconcile_out_size(void);   /* sizeof(tsf_reconcile_out): the self-check of a binding */
+int tsf_rollup_reconcile(tsf_rollup *r, const tsf_spec *spec, int64_t N, const double *theta, const double *y_scale,
+                         const tsf_grid_info *grid, int32_t n_grids, const double *floor, const double *cap,
+                         const double *extra_future, int32_t shared_extra, const int64_t *series_key /* [N], required */,
+                         const int64_t *group /* [N] */, const double *share /* [N] */, int32_t n_q,
+                         const double *quantiles, tsf_reconcile_out *out);
+int tsf_rollup_reconciled_totals(tsf_rollup *r, const double *share_total /* [G] */, int32_t n_q, const double *quantiles,
+                                 tsf_rollup_out *out);
 
 /* ---- cross-validation ---------------------------------------------------------------------
  * fbprophet 0.5 diagnostics.cross_validation + performance_metrics for a whole panel: every series is refitted at

@@ -116,6 +116,11 @@ class TsfRollupOut(ctypes.Structure):
                 ('samples', ctypes.c_void_p)]
 
 
+class TsfReconcileOut(ctypes.Structure):
+    """tsf_reconcile_out (include/tsf.h)."""
+    _fields_ = [('yhat', ctypes.c_void_p), ('q', ctypes.c_void_p), ('cum_q', ctypes.c_void_p), ('samples', ctypes.c_void_p)]
+
+
 class TsfTuneOut(ctypes.Structure):
     """tsf_tune_out (include/tsf.h)."""
     _fields_ = [('score', ctypes.c_void_p), ('cand_status', ctypes.c_void_p), ('best', ctypes.c_void_p),
@@ -182,7 +187,9 @@ EXPORTS = ['tsf_create', 'tsf_destroy', 'tsf_last_error', 'tsf_device_count', 't
            'tsf_predict', 'tsf_predict_dev', 'tsf_predict_intervals', 'tsf_predict_intervals_dev', 'tsf_predict_components', 'tsf_predict_components_dev',
            'tsf_predict_quantiles', 'tsf_predict_quantiles_dev',
            'tsf_score_out_size', 'tsf_score_actuals', 'tsf_score_actuals_dev',
-           'tsf_rollup_create', 'tsf_rollup_add', 'tsf_rollup_quantiles', 'tsf_rollup_free', 'tsf_eval', 'tsf_eval_quadratic', 'tsf_design', 'tsf_selftest_math',
+           'tsf_rollup_create', 'tsf_rollup_add', 'tsf_rollup_quantiles', 'tsf_rollup_free',
+           'tsf_reconcile_shares', 'tsf_reconcile_out_size', 'tsf_rollup_set_totals', 'tsf_rollup_reconcile', 'tsf_rollup_reconciled_totals',
+           'tsf_eval', 'tsf_eval_quadratic', 'tsf_design', 'tsf_selftest_math',
            'tsf_set_option', 'tsf_get_option', 'tsf_set_cost_hints', 'tsf_set_profiling', 'tsf_profile_read', 'tsf_last_fit_kernel_ms', 'tsf_last_fit_route',
            'tsf_fit_plan', 'tsf_fit_plan_info_size', 'tsf_fit_plan_error', 'tsf_last_fit_plan',
            'tsf_cv_plan', 'tsf_cross_validate', 'tsf_last_cv_grids', 'tsf_tune', 'tsf_last_tune_counts',
@@ -279,6 +286,10 @@ def load():
     L.tsf_rollup_quantiles.argtypes = [vp, i32, vp, ctypes.POINTER(TsfRollupOut)]
     L.tsf_rollup_free.argtypes = [vp]
     L.tsf_rollup_free.restype = None
+    L.tsf_reconcile_shares.argtypes = [i64, vp, vp, i64, vp, vp, vp]
+    L.tsf_rollup_set_totals.argtypes = L.tsf_rollup_add.argtypes
+    L.tsf_rollup_reconcile.argtypes = L.tsf_rollup_add.argtypes + [vp, i32, vp, ctypes.POINTER(TsfReconcileOut)]
+    L.tsf_rollup_reconciled_totals.argtypes = [vp, vp, i32, vp, ctypes.POINTER(TsfRollupOut)]
     L.tsf_eval.argtypes = [vp, psp, i64, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     L.tsf_eval_quadratic.argtypes = [vp, psp, i64, i32, vp, vp, i32, vp, vp, vp, vp, vp]
     L.tsf_design.argtypes = [vp, psp, i32, vp, vp, vp, vp, vp]
@@ -357,6 +368,8 @@ def load():
         raise TsfError('tsf_grid_info layout mismatch between _lib.py and libtsf_amd.so')
     if L.tsf_score_out_size() != ctypes.sizeof(TsfScoreOut):
         raise TsfError('tsf_score_out layout mismatch between _lib.py and libtsf_amd.so')
+    if L.tsf_reconcile_out_size() != ctypes.sizeof(TsfReconcileOut):
+        raise TsfError('tsf_reconcile_out layout mismatch between _lib.py and libtsf_amd.so')
     if (L.tsf_screen_args_size() != ctypes.sizeof(TsfScreenArgs) or L.tsf_screen_out_size() != ctypes.sizeof(TsfScreenOut)
             or L.tsf_fit_screened_out_size() != ctypes.sizeof(TsfFitScreenedOut)):
         raise TsfError('tsf_screen_args / tsf_screen_out layout mismatch between _lib.py and libtsf_amd.so')

@@ -24,6 +24,7 @@
 #include "tsf_interval_kernels.h"
 #include "tsf_score_kernels.h"
 #include "tsf_rollup_kernels.h"
+#include "tsf_reconcile_kernels.h"
 #include "tsf_component_kernels.h"
 #include "tsf_fit_kernels.h"
 #include "tsf_quad_kernels.h"
@@ -2109,6 +2110,11 @@ struct tsf_rollup {
     double *ysum;                   // [G][H]
     std::vector<int64_t> count;     // [G] members added so far (host)
     bool poisoned;                  // a HIP failure in the middle of an add: the accumulators may be half-added
+    // reconciliation (tsf_rollup_set_totals): allocated by its first call and not before
+    double *top;                    // [G][H][S] the draws of the groups' directly fitted totals
+    double *ytop;                   // [G][H]
+    int32_t *d_has_top;             // [G] device copy of has_top
+    std::vector<int32_t> has_top;   // [G] the group has a total (host; empty until the first set_totals)
 };
 
 static void rollup_release(tsf_rollup *r)
@@ -2116,6 +2122,9 @@ static void rollup_release(tsf_rollup *r)
     if (r->d_ds) (void)hipFree(r->d_ds);
     if (r->acc) (void)hipFree(r->acc);
     if (r->ysum) (void)hipFree(r->ysum);
+    if (r->top) (void)hipFree(r->top);
+    if (r->ytop) (void)hipFree(r->ytop);
+    if (r->d_has_top) (void)hipFree(r->d_has_top);
     delete r;
 }
 
@@ -2133,6 +2142,7 @@ extern "C" int tsf_rollup_create(tsf_ctx *ctx, int64_t G, int32_t H, const int64
     tsf_rollup *r = new tsf_rollup();
     r->ctx = ctx; r->G = G; r->H = H; r->S = n_samples; r->seed = seed;
     r->d_ds = nullptr; r->acc = nullptr; r->ysum = nullptr; r->poisoned = false;
+    r->top = nullptr; r->ytop = nullptr; r->d_has_top = nullptr;
     const size_t gh = (size_t)G * H;
     hipError_t e = hipMalloc((void **)&r->d_ds, 8 * (size_t)H);
     if (e == hipSuccess) e = hipMalloc((void **)&r->acc, 8 * gh * n_samples);
@@ -2193,17 +2203,16 @@ static void rollup_plan(const int64_t *group, int64_t N, int64_t chunk, RollupPl
     }
 }
 
-extern "C" int tsf_rollup_add(tsf_rollup *r, const tsf_spec *spec, int64_t N, const double *theta, const double *y_scale,
-                              const tsf_grid_info *grid, int32_t n_grids, const double *floor_, const double *cap,
-                              const double *extra_future, int32_t shared_extra, const int64_t *series_key,
-                              const int64_t *group)
+static const char *const ROLLUP_POISONED =
+    "the roll-up is poisoned: an earlier tsf_rollup_add or tsf_rollup_set_totals failed in the middle";
+
+// What tsf_rollup_add, tsf_rollup_set_totals and tsf_rollup_reconcile check of their series before anything is copied
+// or launched (the handle is not poisoned, N > 0).
+static int rollup_check_series(tsf_rollup *r, const tsf_spec *spec, int64_t N, const double *theta, const double *y_scale,
+                               const tsf_grid_info *grid, int32_t n_grids, const double *cap, const double *extra_future,
+                               const int64_t *series_key, const int64_t *group)
 {
-    if (!r) return -1;
     tsf_ctx *ctx = r->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (r->poisoned) return fail(ctx, "the roll-up is poisoned: an earlier tsf_rollup_add failed in the middle");
-    if (N < 0) return fail(ctx, "N must be >= 0");
-    if (N == 0) return 0;
     if (N > 2147483647) return fail(ctx, "N must be < 2^31 per call");
     if (!spec || !theta || !y_scale || !grid) return fail(ctx, "NULL input");
     if (!series_key)
@@ -2225,32 +2234,63 @@ extern "C" int tsf_rollup_add(tsf_rollup *r, const tsf_spec *spec, int64_t N, co
     }
     if (spec->n_extra > 0 && !extra_future) return fail(ctx, "extra_future is NULL");
     if (spec->growth == TSF_GROWTH_LOGISTIC && !cap) return fail(ctx, "logistic growth needs cap");
-    // shared extra columns (or none): tsf_predict on the shared calendar; per-series columns: tsf_predict with the
-    // calendar repeated per series (shared_future = 0), which is what their layout [N][n_extra][H] belongs to
+    return 0;
+}
+
+// The series of one such call on the device, on the handle's calendar.  Shared extra columns (or none): tsf_predict on
+// the shared calendar; per-series columns: tsf_predict with the calendar repeated per series (shared_future = 0), which
+// is what their layout [N][n_extra][H] belongs to.
+struct RollupSeries {
+    DevBuf d_ds;
+    ForecastUpload up;
+
+    int upload(tsf_rollup *r, const tsf_spec *spec, int64_t N, const double *theta, const double *y_scale,
+               const tsf_grid_info *grid, int32_t n_grids, const double *floor_, const double *cap,
+               const double *extra_future, int32_t shared_extra, const int64_t *series_key)
+    {
+        tsf_ctx *ctx = r->ctx;
+        const int32_t H = r->H;
+        const int shared = (spec->n_extra == 0 || shared_extra) ? 1 : 0;
+        // the calendar is the handle's, on the device already; the inputs beside it are uploaded
+        const int64_t *ds_dev = r->d_ds;
+        if (!shared) {
+            std::vector<int64_t> ds_rep;
+            try {
+                ds_rep.resize((size_t)N * H);
+            } catch (const std::bad_alloc &) {
+                return fail(ctx, "tsf_rollup: out of host memory");
+            }
+            HIP_TRY(ctx, hipMemcpy(ds_rep.data(), r->d_ds, 8 * (size_t)H, hipMemcpyDeviceToHost));
+            for (int64_t n = 1; n < N; ++n) memcpy(&ds_rep[(size_t)n * H], ds_rep.data(), 8 * (size_t)H);
+            HIP_TRY(ctx, d_ds.alloc(8 * (size_t)N * H));
+            HIP_TRY(ctx, hipMemcpy(d_ds.p, ds_rep.data(), 8 * (size_t)N * H, hipMemcpyHostToDevice));
+            ds_dev = d_ds.as<int64_t>();
+        }
+        const ForecastIn h = {N, H, theta, y_scale, grid, n_grids, ds_dev, shared, floor_, cap, extra_future, series_key};
+        return up.upload(ctx, spec, h, true);
+    }
+};
+
+// The work of tsf_rollup_add (into acc / ysum) and of tsf_rollup_set_totals (into top / ytop) once the call is
+// checked: the series' draws added to the cells of their groups by rollup_add_kernel.
+static int rollup_accumulate(tsf_rollup *r, const tsf_spec *spec, int64_t N, const double *theta, const double *y_scale,
+                             const tsf_grid_info *grid, int32_t n_grids, const double *floor_, const double *cap,
+                             const double *extra_future, int32_t shared_extra, const int64_t *series_key,
+                             const int64_t *group, double *acc, double *ysum)
+{
+    tsf_ctx *ctx = r->ctx;
     const int32_t H = r->H, S = r->S;
-    const int shared = (spec->n_extra == 0 || shared_extra) ? 1 : 0;
     const int64_t chunk = draw_chunk_series(N, H, S, 1);       // draw_chunks' chunks: one sample buffer
     RollupPlan P;
-    std::vector<int64_t> ds_rep;
     try {
         rollup_plan(group, N, chunk, &P);
-        if (!shared) ds_rep.resize((size_t)N * H);
     } catch (const std::bad_alloc &) {
-        return fail(ctx, "tsf_rollup_add: out of host memory");
+        return fail(ctx, "tsf_rollup: out of host memory");
     }
-    // the calendar is the handle's, on the device already; the inputs beside it are uploaded
-    DevBuf d_ds, d_yh, d_csr;
-    const int64_t *ds_dev = r->d_ds;
-    if (!shared) {
-        HIP_TRY(ctx, hipMemcpy(ds_rep.data(), r->d_ds, 8 * (size_t)H, hipMemcpyDeviceToHost));
-        for (int64_t n = 1; n < N; ++n) memcpy(&ds_rep[(size_t)n * H], ds_rep.data(), 8 * (size_t)H);
-        HIP_TRY(ctx, d_ds.alloc(8 * (size_t)N * H));
-        HIP_TRY(ctx, hipMemcpy(d_ds.p, ds_rep.data(), 8 * (size_t)N * H, hipMemcpyHostToDevice));
-        ds_dev = d_ds.as<int64_t>();
-    }
-    const ForecastIn h = {N, H, theta, y_scale, grid, n_grids, ds_dev, shared, floor_, cap, extra_future, series_key};
-    ForecastUpload up;
-    if (int rc = up.upload(ctx, spec, h, true)) return rc;
+    RollupSeries in;
+    if (int rc = in.upload(r, spec, N, theta, y_scale, grid, n_grids, floor_, cap, extra_future, shared_extra, series_key))
+        return rc;
+    DevBuf d_yh, d_csr;
     HIP_TRY(ctx, d_yh.alloc(8 * (size_t)N * H));
     const size_t n_t = P.touched.size(), n_f = P.first.size();
     HIP_TRY(ctx, d_csr.alloc(4 * (n_t + n_f + (size_t)N)));
@@ -2262,7 +2302,7 @@ extern "C" int tsf_rollup_add(tsf_rollup *r, const tsf_spec *spec, int64_t N, co
     r->poisoned = true;
     RollupAddArgs ra;
     memset(&ra, 0, sizeof(ra));
-    ra.acc = r->acc; ra.ysum = r->ysum; ra.H = H; ra.NS = S;
+    ra.acc = acc; ra.ysum = ysum; ra.H = H; ra.NS = S;
     auto after = [&](int64_t n0, int64_t nc, const DrawBufs &b) -> int {
         const size_t c = (size_t)(n0 / chunk);
         const size_t n_touched = (c + 1 < P.t0.size() ? P.t0[c + 1] : n_t) - P.t0[c];
@@ -2275,10 +2315,29 @@ extern "C" int tsf_rollup_add(tsf_rollup *r, const tsf_spec *spec, int64_t N, co
         return 0;
     };
     const DrawSpec d = {S, r->seed, false, false, d_yh.as<double>(), nullptr};
-    int rc = draw_chunks(ctx, spec, up.dev, d, nullptr, after);
+    int rc = draw_chunks(ctx, spec, in.up.dev, d, nullptr, after);
     if (rc) return rc;
     HIP_TRY(ctx, hipDeviceSynchronize());
     r->poisoned = false;
+    return 0;
+}
+
+extern "C" int tsf_rollup_add(tsf_rollup *r, const tsf_spec *spec, int64_t N, const double *theta, const double *y_scale,
+                              const tsf_grid_info *grid, int32_t n_grids, const double *floor_, const double *cap,
+                              const double *extra_future, int32_t shared_extra, const int64_t *series_key,
+                              const int64_t *group)
+{
+    if (!r) return -1;
+    tsf_ctx *ctx = r->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (r->poisoned) return fail(ctx, ROLLUP_POISONED);
+    if (N < 0) return fail(ctx, "N must be >= 0");
+    if (N == 0) return 0;
+    if (int rc = rollup_check_series(r, spec, N, theta, y_scale, grid, n_grids, cap, extra_future, series_key, group))
+        return rc;
+    if (int rc = rollup_accumulate(r, spec, N, theta, y_scale, grid, n_grids, floor_, cap, extra_future, shared_extra,
+                                   series_key, group, r->acc, r->ysum))
+        return rc;
     for (int64_t n = 0; n < N; ++n) r->count[(size_t)group[n]] += 1;
     return 0;
 }
@@ -2288,7 +2347,7 @@ extern "C" int tsf_rollup_quantiles(tsf_rollup *r, int32_t n_q, const double *qu
     if (!r) return -1;
     tsf_ctx *ctx = r->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (r->poisoned) return fail(ctx, "the roll-up is poisoned: an earlier tsf_rollup_add failed in the middle");
+    if (r->poisoned) return fail(ctx, ROLLUP_POISONED);
     if (!out) return fail(ctx, "NULL output (tsf_rollup_out and its yhat are required)");
     {
         tsf_quantile_out chk;
@@ -2338,6 +2397,268 @@ extern "C" int tsf_rollup_quantiles(tsf_rollup *r, int32_t n_q, const double *qu
     if (out->q) HIP_TRY(ctx, hipMemcpy(out->q, d_q.p, nqh, hipMemcpyDeviceToHost));
     if (out->cum_q) HIP_TRY(ctx, hipMemcpy(out->cum_q, d_cq.p, nqh, hipMemcpyDeviceToHost));
     if (out->samples) HIP_TRY(ctx, hipMemcpy(out->samples, r->acc, 8 * gh * S, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- reconciliation: member forecasts and fitted totals made coherent ---------------------------------------
+
+extern "C" int tsf_reconcile_out_size(void) { return (int)sizeof(tsf_reconcile_out); }
+
+extern "C" int tsf_reconcile_shares(int64_t N, const int64_t *group, const double *w, int64_t G, const double *v,
+                                    double *share, double *share_total)
+{
+    if (N < 0 || G < 0 || (N > 0 && (!group || !share)) || (G > 0 && (!v || !share_total))) return -1;
+    for (int64_t n = 0; n < N; ++n) {
+        if (group[n] < 0 || group[n] >= G) return -1;
+        if (w && !(w[n] > 0.0 && std::isfinite(w[n]))) return -1;
+    }
+    for (int64_t g = 0; g < G; ++g)
+        if (!std::isnan(v[g]) && !(v[g] > 0.0 && std::isfinite(v[g]))) return -1;
+    // W_g in share_total, from +0.0 in ascending member index
+    for (int64_t g = 0; g < G; ++g) share_total[g] = 0.0;
+    for (int64_t n = 0; n < N; ++n) share_total[group[n]] = share_total[group[n]] + (w ? w[n] : 1.0);
+    for (int64_t n = 0; n < N; ++n) {
+        const int64_t g = group[n];
+        share[n] = std::isnan(v[g]) ? 0.0 : (w ? w[n] : 1.0) / (v[g] + share_total[g]);
+    }
+    for (int64_t g = 0; g < G; ++g) {
+        const double W = share_total[g];
+        share_total[g] = (std::isnan(v[g]) || W == 0.0) ? 0.0 : W / (v[g] + W);
+    }
+    return 0;
+}
+
+extern "C" int tsf_rollup_set_totals(tsf_rollup *r, const tsf_spec *spec, int64_t Gt, const double *theta,
+                                     const double *y_scale, const tsf_grid_info *grid, int32_t n_grids,
+                                     const double *floor_, const double *cap, const double *extra_future,
+                                     int32_t shared_extra, const int64_t *series_key, const int64_t *group)
+{
+    if (!r) return -1;
+    tsf_ctx *ctx = r->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (r->poisoned) return fail(ctx, ROLLUP_POISONED);
+    if (Gt < 0) return fail(ctx, "N must be >= 0");
+    if (Gt == 0) return 0;
+    if (int rc = rollup_check_series(r, spec, Gt, theta, y_scale, grid, n_grids, cap, extra_future, series_key, group))
+        return rc;
+    std::vector<int32_t> has;
+    try {
+        has = r->has_top;
+        has.resize((size_t)r->G, 0);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, "tsf_rollup_set_totals: out of host memory");
+    }
+    for (int64_t n = 0; n < Gt; ++n) {
+        if (has[(size_t)group[n]]) {
+            char msg[160];
+            snprintf(msg, sizeof(msg), "group[%lld] = %lld: the group has a total already (one total per group)",
+                     (long long)n, (long long)group[n]);
+            return fail(ctx, msg);
+        }
+        has[(size_t)group[n]] = 1;
+    }
+    const size_t gh = (size_t)r->G * r->H;
+    if (!r->top) {
+        // the second accumulator: +0.0 everywhere, so that the add below leaves the draws themselves in it
+        double *top = nullptr, *ytop = nullptr;
+        int32_t *d_has = nullptr;
+        hipError_t e = hipMalloc((void **)&top, 8 * gh * r->S);
+        if (e == hipSuccess) e = hipMalloc((void **)&ytop, 8 * gh);
+        if (e == hipSuccess) e = hipMalloc((void **)&d_has, 4 * (size_t)r->G);
+        if (e == hipSuccess) e = hipMemset(top, 0, 8 * gh * r->S);
+        if (e == hipSuccess) e = hipMemset(ytop, 0, 8 * gh);
+        if (e == hipSuccess) e = hipMemset(d_has, 0, 4 * (size_t)r->G);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) {
+            ctx->err = std::string("tsf_rollup_set_totals: ") + hipGetErrorString(e);
+            (void)hipGetLastError();
+            if (top) (void)hipFree(top);
+            if (ytop) (void)hipFree(ytop);
+            if (d_has) (void)hipFree(d_has);
+            return -2;
+        }
+        r->top = top; r->ytop = ytop; r->d_has_top = d_has;
+    }
+    if (int rc = rollup_accumulate(r, spec, Gt, theta, y_scale, grid, n_grids, floor_, cap, extra_future, shared_extra,
+                                   series_key, group, r->top, r->ytop))
+        return rc;
+    // (a failure of this copy leaves the device's flags behind the draws in `top`: poisoned like a failed add)
+    r->poisoned = true;
+    HIP_TRY(ctx, hipMemcpy(r->d_has_top, has.data(), 4 * (size_t)r->G, hipMemcpyHostToDevice));
+    r->poisoned = false;
+    r->has_top.swap(has);
+    return 0;
+}
+
+// share [n]: finite and in [0, 1]
+static int check_shares(tsf_ctx *ctx, const char *name, const double *share, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i)
+        if (!(share[i] >= 0.0 && share[i] <= 1.0)) {            // (NaN fails both comparisons)
+            char msg[120];
+            snprintf(msg, sizeof(msg), "%s[%lld] = %g: a share must be finite and in [0, 1]", name, (long long)i, share[i]);
+            return fail(ctx, msg);
+        }
+    return 0;
+}
+
+extern "C" int tsf_rollup_reconcile(tsf_rollup *r, const tsf_spec *spec, int64_t N, const double *theta,
+                                    const double *y_scale, const tsf_grid_info *grid, int32_t n_grids,
+                                    const double *floor_, const double *cap, const double *extra_future,
+                                    int32_t shared_extra, const int64_t *series_key, const int64_t *group,
+                                    const double *share, int32_t n_q, const double *quantiles, tsf_reconcile_out *out)
+{
+    if (!r) return -1;
+    tsf_ctx *ctx = r->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (r->poisoned) return fail(ctx, ROLLUP_POISONED);
+    if (N < 0) return fail(ctx, "N must be >= 0");
+    if (N == 0) return 0;
+    if (!r->top) return fail(ctx, "tsf_rollup_reconcile before any tsf_rollup_set_totals: the roll-up has no total");
+    if (int rc = rollup_check_series(r, spec, N, theta, y_scale, grid, n_grids, cap, extra_future, series_key, group))
+        return rc;
+    if (!share) return fail(ctx, "NULL share");
+    if (int rc = check_shares(ctx, "share", share, N)) return rc;
+    if (!out) return fail(ctx, "NULL output (tsf_reconcile_out and its yhat are required)");
+    {
+        tsf_quantile_out chk;
+        memset(&chk, 0, sizeof(chk));
+        chk.yhat = out->yhat; chk.q = out->q; chk.cum_q = out->cum_q; chk.samples = out->samples;
+        if (int rc = check_quantile_args(ctx, r->S, n_q, quantiles, &chk)) return rc;
+    }
+    const int32_t H = r->H, S = r->S;
+    const int NSP = sort_width(S);
+    std::vector<int32_t> g32;
+    try {
+        g32.resize((size_t)N);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, "tsf_rollup_reconcile: out of host memory");
+    }
+    for (int64_t n = 0; n < N; ++n) g32[(size_t)n] = (int32_t)group[n];
+    RollupSeries in;
+    if (int rc = in.upload(r, spec, N, theta, y_scale, grid, n_grids, floor_, cap, extra_future, shared_extra, series_key))
+        return rc;
+    // the shares and the groups of the whole call, sent once ahead of the first launch
+    const size_t nh = 8 * (size_t)N * H, nqh = nh * (size_t)n_q;
+    DevBuf d_yh, d_q, d_cq, d_share, d_group;
+    HIP_TRY(ctx, d_yh.alloc(nh));
+    if (out->q) HIP_TRY(ctx, d_q.alloc(nqh));
+    if (out->cum_q) HIP_TRY(ctx, d_cq.alloc(nqh));
+    HIP_TRY(ctx, d_share.alloc(8 * (size_t)N));
+    HIP_TRY(ctx, d_group.alloc(4 * (size_t)N));
+    HIP_TRY(ctx, hipMemcpy(d_share.p, share, 8 * (size_t)N, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(d_group.p, g32.data(), 4 * (size_t)N, hipMemcpyHostToDevice));
+    ReconcileMemberArgs m;
+    memset(&m, 0, sizeof(m));
+    m.acc = r->acc; m.top = r->top; m.ysum = r->ysum; m.ytop = r->ytop; m.has_top = r->d_has_top; m.H = H; m.NS = S;
+    QuantileArgs q;
+    memset(&q, 0, sizeof(q));
+    q.H = H; q.NS = S; q.n_q = n_q;
+    for (int32_t i = 0; i < n_q; ++i) q.level[i] = quantiles[i];
+    auto after = [&](int64_t n0, int64_t nc, const DrawBufs &b) -> int {
+        m.samp = b.samp; m.yhat = d_yh.as<double>() + (size_t)n0 * H;
+        m.group = d_group.as<int32_t>() + n0; m.share = d_share.as<double>() + n0;
+        hipLaunchKernelGGL(reconcile_member_kernel, dim3((unsigned)(nc * H), (unsigned)((S + 255) / 256)), dim3(256), 0,
+                           nullptr, m);
+        HIP_TRY(ctx, hipGetLastError());
+        if (out->cum_q) {
+            // the running sums of the reconciled draws over the ones interval_sample_kernel left in the second buffer
+            hipLaunchKernelGGL(rollup_cumsum_kernel, dim3((unsigned)((nc * S + 255) / 256)), dim3(256), 0, nullptr,
+                               b.samp, b.cum, nc, H, S);
+            HIP_TRY(ctx, hipGetLastError());
+        }
+        const struct { const double *src; double *dst; } sorts[2] = {{b.samp, d_q.as<double>()}, {b.cum, d_cq.as<double>()}};
+        for (const auto &so : sorts) {
+            if (!so.dst) continue;
+            q.src = so.src; q.dst = so.dst; q.n0 = n0;
+            hipLaunchKernelGGL(quantile_kernel, dim3((unsigned)(nc * H)), dim3(256), sizeof(double) * NSP, nullptr, q, NSP);
+            HIP_TRY(ctx, hipGetLastError());
+        }
+        // the reconciled draws leave the scratch before the next chunk overwrites it (stream order)
+        if (out->samples)
+            HIP_TRY(ctx, hipMemcpyAsync(out->samples + (size_t)n0 * H * S, b.samp, 8 * (size_t)nc * H * S,
+                                        hipMemcpyDeviceToHost, nullptr));
+        return 0;
+    };
+    const DrawSpec d = {S, r->seed, out->cum_q != nullptr, false, d_yh.as<double>(), nullptr};
+    if (int rc = draw_chunks(ctx, spec, in.up.dev, d, nullptr, after)) return rc;
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    HIP_TRY(ctx, hipMemcpy(out->yhat, d_yh.p, nh, hipMemcpyDeviceToHost));
+    if (out->q) HIP_TRY(ctx, hipMemcpy(out->q, d_q.p, nqh, hipMemcpyDeviceToHost));
+    if (out->cum_q) HIP_TRY(ctx, hipMemcpy(out->cum_q, d_cq.p, nqh, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int tsf_rollup_reconciled_totals(tsf_rollup *r, const double *share_total, int32_t n_q,
+                                            const double *quantiles, tsf_rollup_out *out)
+{
+    if (!r) return -1;
+    tsf_ctx *ctx = r->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (r->poisoned) return fail(ctx, ROLLUP_POISONED);
+    if (!r->top)
+        return fail(ctx, "tsf_rollup_reconciled_totals before any tsf_rollup_set_totals: the roll-up has no total");
+    if (!share_total) return fail(ctx, "NULL share_total");
+    if (int rc = check_shares(ctx, "share_total", share_total, r->G)) return rc;
+    if (!out) return fail(ctx, "NULL output (tsf_rollup_out and its yhat are required)");
+    {
+        tsf_quantile_out chk;
+        memset(&chk, 0, sizeof(chk));
+        chk.yhat = out->yhat; chk.q = out->q; chk.cum_q = out->cum_q; chk.samples = out->samples;
+        if (int rc = check_quantile_args(ctx, r->S, n_q, quantiles, &chk)) return rc;
+    }
+    const int32_t H = r->H, S = r->S;
+    const int64_t G = r->G;
+    const size_t hs = (size_t)H * S, gh = (size_t)G * H, nqh = 8 * gh * (size_t)n_q;
+    const int NSP = sort_width(S);
+    DevBuf d_share, d_yh, d_q, d_cq;
+    HIP_TRY(ctx, d_share.alloc(8 * (size_t)G));
+    HIP_TRY(ctx, d_yh.alloc(8 * gh));
+    if (out->q) HIP_TRY(ctx, d_q.alloc(nqh));
+    if (out->cum_q) HIP_TRY(ctx, d_cq.alloc(nqh));
+    HIP_TRY(ctx, hipMemcpy(d_share.p, share_total, 8 * (size_t)G, hipMemcpyHostToDevice));
+    // a range of groups at a time in the context's scratch (within its 512 MB): the reconciled cells, and behind them
+    // their running sums where wanted
+    const size_t n_buf = out->cum_q ? 2 : 1;
+    const int64_t range = std::max<int64_t>(1, std::min<int64_t>(G, (int64_t)(((size_t)512 << 20) / (8 * hs * n_buf))));
+    if (int rc = ensure_iv_ws(ctx, 8 * (size_t)range * hs * n_buf)) return rc;
+    double *d_x = (double *)ctx->iv_ws, *d_c = d_x + (size_t)range * hs;
+    ReconcileTotalArgs t;
+    memset(&t, 0, sizeof(t));
+    t.acc = r->acc; t.top = r->top; t.ysum = r->ysum; t.ytop = r->ytop; t.has_top = r->d_has_top;
+    t.share = d_share.as<double>(); t.out = d_x; t.yout = d_yh.as<double>(); t.H = H; t.NS = S;
+    QuantileArgs q;
+    memset(&q, 0, sizeof(q));
+    q.H = H; q.NS = S; q.n_q = n_q;
+    for (int32_t i = 0; i < n_q; ++i) q.level[i] = quantiles[i];
+    for (int64_t g0 = 0; g0 < G; g0 += range) {
+        const int64_t gc = std::min(range, G - g0);
+        t.g0 = g0;
+        hipLaunchKernelGGL(reconcile_total_kernel, dim3((unsigned)(gc * H), (unsigned)((S + 255) / 256)), dim3(256), 0,
+                           nullptr, t);
+        HIP_TRY(ctx, hipGetLastError());
+        if (out->q) {
+            q.src = d_x; q.dst = d_q.as<double>(); q.n0 = g0;
+            hipLaunchKernelGGL(quantile_kernel, dim3((unsigned)(gc * H)), dim3(256), sizeof(double) * NSP, nullptr, q, NSP);
+            HIP_TRY(ctx, hipGetLastError());
+        }
+        if (out->cum_q) {
+            hipLaunchKernelGGL(rollup_cumsum_kernel, dim3((unsigned)((gc * S + 255) / 256)), dim3(256), 0, nullptr,
+                               d_x, d_c, gc, H, S);
+            HIP_TRY(ctx, hipGetLastError());
+            q.src = d_c; q.dst = d_cq.as<double>(); q.n0 = g0;
+            hipLaunchKernelGGL(quantile_kernel, dim3((unsigned)(gc * H)), dim3(256), sizeof(double) * NSP, nullptr, q, NSP);
+            HIP_TRY(ctx, hipGetLastError());
+        }
+        if (out->samples)
+            HIP_TRY(ctx, hipMemcpyAsync(out->samples + (size_t)g0 * hs, d_x, 8 * (size_t)gc * hs, hipMemcpyDeviceToHost,
+                                        nullptr));
+    }
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    HIP_TRY(ctx, hipMemcpy(out->yhat, d_yh.p, 8 * gh, hipMemcpyDeviceToHost));
+    if (out->count) memcpy(out->count, r->count.data(), 8 * (size_t)G);
+    if (out->q) HIP_TRY(ctx, hipMemcpy(out->q, d_q.p, nqh, hipMemcpyDeviceToHost));
+    if (out->cum_q) HIP_TRY(ctx, hipMemcpy(out->cum_q, d_cq.p, nqh, hipMemcpyDeviceToHost));
     return 0;
 }
 

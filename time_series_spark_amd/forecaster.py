@@ -992,7 +992,8 @@ class Rollup(object):
     """One tsf_rollup: n_groups accumulators of uncertainty_samples summed draws per row of ds_future_ns [H], filled by
     add (once per spec, any number of calls) and read by quantiles / samples at any time.  A context manager; close()
     frees the device memory (before its context is closed).  Shape and level errors raise ValueError before the library
-    is touched."""
+    is touched.  Where the totals are fitted directly as well: set_totals, then reconcile (the members) and
+    reconciled_totals (include/tsf.h "reconciliation")."""
 
     def __init__(self, ds_future_ns, n_groups, uncertainty_samples=1000, seed=0, ctx=None):
         self._h = None
@@ -1073,6 +1074,190 @@ class Rollup(object):
     def samples(self):
         """-> [G][H][S]: the summed draws themselves (sample s of a group: the sum of sample s of its members)."""
         return self._read([], ['samples'])['samples']
+
+    # -- reconciliation (include/tsf.h "reconciliation") --
+
+    def set_totals(self, spec, theta, y_scale, grid, group, series_key, floor=None, cap=None, extra_future=None):
+        """The directly fitted totals of one spec: series n is the total of group[n] (at most one total per group, over
+        all calls).  Forecast on the roll-up's calendar like the members of add; series_key [Gt] is required and must
+        differ from every member's key (a shared key is a shared stream)."""
+        h = self._handle()
+        N, theta, y_scale, grid, group, key, floor, cap, ex, shared = _rollup_add_args(
+            spec, theta, y_scale, grid, group, series_key, floor, cap, extra_future, self.G, self.H)
+        if len(np.unique(group)) != N:
+            raise ValueError('group: a group appears twice (one total per group)')
+        cs = spec.to_c()
+        self._ctx.check(_lib.load().tsf_rollup_set_totals(h, ctypes.byref(cs), N, theta.ctypes.data, y_scale.ctypes.data,
+                                                          grid.ctypes.data, len(grid), _lib._ptr(floor), _lib._ptr(cap),
+                                                          _lib._ptr(ex), shared, key.ctypes.data, group.ctypes.data))
+
+    def reconcile(self, spec, theta, y_scale, grid, group, series_key, share, quantiles=(), cumulative=False,
+                  samples=False, floor=None, cap=None, extra_future=None):
+        """The second pass over members that were added (same arguments and keys as in add), after every add and
+        set_totals: draw' = draw + share[n] * (total's draw - sum of the group's member draws) -> Reconciled (a
+        Quantiles: yhat [N][H], q and cum_q [N][Q][H] at the levels `quantiles`; .samples [N][H][S] where asked for).
+        share [N] in [0, 1] (reconcile_shares); a group without a total leaves its members as they are."""
+        h = self._handle()
+        N, theta, y_scale, grid, group, key, floor, cap, ex, shared = _rollup_add_args(
+            spec, theta, y_scale, grid, group, series_key, floor, cap, extra_future, self.G, self.H)
+        share = np.ascontiguousarray(share, dtype=np.float64)
+        if share.shape != (N,):
+            raise ValueError('share must be [N]')
+        if N and not (np.isfinite(share).all() and share.min() >= 0.0 and share.max() <= 1.0):
+            raise ValueError('share values must be finite and in [0, 1]')
+        quantile_columns(quantiles)             # (a bad level list: ValueError before the library is touched)
+        levels = np.array(quantiles, dtype=np.float64).reshape(-1)
+        Q = len(levels)
+        if Q == 0 and (cumulative or not samples):
+            raise ValueError('nothing requested: give quantile levels or samples=True (cumulative needs levels)')
+        res = {'yhat': np.zeros((N, self.H))}
+        if Q:
+            res['q'] = np.zeros((N, Q, self.H))
+            if cumulative:
+                res['cum_q'] = np.zeros((N, Q, self.H))
+        if samples:
+            res['samples'] = np.zeros((N, self.H, self.S))
+        out = _lib.TsfReconcileOut(**{k: v.ctypes.data for k, v in res.items()})
+        cs = spec.to_c()
+        self._ctx.check(_lib.load().tsf_rollup_reconcile(
+            h, ctypes.byref(cs), N, theta.ctypes.data, y_scale.ctypes.data, grid.ctypes.data, len(grid), _lib._ptr(floor),
+            _lib._ptr(cap), _lib._ptr(ex), shared, key.ctypes.data, group.ctypes.data, share.ctypes.data, Q,
+            levels.ctypes.data if Q else None, ctypes.byref(out)))
+        return Reconciled(res['yhat'], levels, res.get('q'), res.get('cum_q'), res.get('samples'))
+
+    def reconciled_totals(self, share_total, levels, cumulative=False, samples=False):
+        """-> RollupQuantiles of acc + share_total[g] * (total's draws - acc) per group (share_total [G] in [0, 1]:
+        reconcile_shares); with samples, (RollupQuantiles, [G][H][S]).  The accumulators are not modified."""
+        h = self._handle()
+        mu = np.ascontiguousarray(share_total, dtype=np.float64)
+        if mu.shape != (self.G,):
+            raise ValueError('share_total must be [n_groups]')
+        if not (np.isfinite(mu).all() and mu.min() >= 0.0 and mu.max() <= 1.0):
+            raise ValueError('share_total values must be finite and in [0, 1]')
+        quantile_columns(levels)
+        levels = np.array(levels, dtype=np.float64).reshape(-1)
+        Q = len(levels)
+        if Q == 0:
+            raise ValueError('at least one quantile level')
+        res = {'yhat': np.zeros((self.G, self.H)), 'count': np.zeros(self.G, dtype=np.int64), 'q': np.zeros((self.G, Q, self.H))}
+        if cumulative:
+            res['cum_q'] = np.zeros((self.G, Q, self.H))
+        if samples:
+            res['samples'] = np.zeros((self.G, self.H, self.S))
+        out = _lib.TsfRollupOut(**{k: v.ctypes.data for k, v in res.items()})
+        self._ctx.check(_lib.load().tsf_rollup_reconciled_totals(h, mu.ctypes.data, Q, levels.ctypes.data, ctypes.byref(out)))
+        r = RollupQuantiles(res['yhat'], res['count'], levels, res['q'], res.get('cum_q'))
+        return (r, res['samples']) if samples else r
+
+
+class Reconciled(Quantiles):
+    """What Rollup.reconcile returns: a Quantiles (yhat [N][H]; quantiles [Q]; q, cum_q [N][Q][H] or None; frame(n, ds)
+    with predict_quantiles' column names) of the reconciled draws, and samples [N][H][S] or None."""
+
+    def __init__(self, yhat, quantiles, q, cum_q=None, samples=None):
+        Quantiles.__init__(self, yhat, quantiles, q, cum_q)
+        self.samples = samples
+
+
+def reconcile_shares(group, n_groups, weight=None, total_weight='struct'):
+    """Weights -> (share [N], share_total [G]) for Rollup.reconcile / reconciled_totals: a thin binding of
+    tsf_reconcile_shares (host only).  group [N]: dense indices in [0, n_groups).  weight [N]: the members' forecast error
+    variances (None: all 1).  total_weight: the totals' -- 'ols' (all 1), 'struct' (the group's member count: a total
+    is as uncertain as its members together; a group without members gets none) or an array [G] (NaN: the group has no
+    total).  share = w / (v + W), share_total = W / (v + W), W the group's sum of w."""
+    G = int(n_groups)
+    group = np.ascontiguousarray(group, dtype=np.int64)
+    if group.ndim != 1:
+        raise ValueError('group must be [N]')
+    N = group.shape[0]
+    if G < 1:
+        raise ValueError('n_groups must be >= 1')
+    if N and (group.min() < 0 or group.max() >= G):
+        raise ValueError('group values must be in [0, %d)' % G)
+    w = None
+    if weight is not None:
+        w = np.ascontiguousarray(weight, dtype=np.float64)
+        if w.shape != (N,):
+            raise ValueError('weight must be [N]')
+        if not (np.isfinite(w).all() and (w > 0).all()):
+            raise ValueError('weight values must be finite and positive')
+    if isinstance(total_weight, str):
+        if total_weight == 'ols':
+            v = np.ones(G)
+        elif total_weight == 'struct':
+            v = np.bincount(group, minlength=G).astype(np.float64)
+            v[v == 0] = np.nan
+        else:
+            raise ValueError("total_weight must be 'ols', 'struct' or an array [n_groups]")
+    else:
+        v = np.ascontiguousarray(total_weight, dtype=np.float64)
+        if v.shape != (G,):
+            raise ValueError('total_weight must be [n_groups]')
+        if not ((np.isfinite(v) & (v > 0)) | np.isnan(v)).all():
+            raise ValueError('total_weight values must be finite and positive (NaN: no total)')
+    share, share_total = np.zeros(N), np.zeros(G)
+    rc = _lib.load().tsf_reconcile_shares(N, group.ctypes.data if N else None, _lib._ptr(w) if N else None, G,
+                                          v.ctypes.data, share.ctypes.data if N else None, share_total.ctypes.data)
+    if rc != 0:
+        raise _lib.TsfError('tsf_reconcile_shares refused its arguments (%d)' % rc)
+    return share, share_total
+
+
+def aggregate_aligned(y, group, n_groups):
+    """The histories of the totals to fit: y [N][T] on one calendar, group [N] -> [G][T] float64.  A pure numpy loop of
+    tot[g] = tot[g] + y[n] in ascending n from zeros (so the order of the adds is fixed); NaN propagates.  Ragged panels
+    are out of scope."""
+    y = np.asarray(y, dtype=np.float64)
+    group = np.asarray(group, dtype=np.int64)
+    G = int(n_groups)
+    if y.ndim != 2:
+        raise ValueError('y must be [N][T]')
+    if group.shape != (y.shape[0],):
+        raise ValueError('group must be [N]')
+    if G < 1 or (len(group) and (group.min() < 0 or group.max() >= G)):
+        raise ValueError('group values must be in [0, n_groups), n_groups >= 1')
+    tot = np.zeros((G, y.shape[1]))
+    for n in range(y.shape[0]):
+        g = int(group[n])
+        tot[g] = tot[g] + y[n]
+    return tot
+
+
+def predict_reconciled(spec, theta, y_scale, grid, ds_future_ns, labels, quantiles, series_key, total_theta,
+                       total_y_scale, total_grid, total_key, total_spec=None, weight=None, total_weight='struct',
+                       floor=None, cap=None, extra_future=None, total_floor=None, total_cap=None,
+                       total_extra_future=None, uncertainty_samples=1000, seed=0, cumulative=False, ctx=None):
+    """The one-spec convenience, in the manner of predict_rollup: rollup_groups(labels), one Rollup.add of the members,
+    set_totals of the G directly fitted totals (total g belongs to the g-th unique label; total_spec: the members' spec
+    where None), reconcile_shares, reconcile, reconciled_totals, close -> (unique_labels, Reconciled of the members,
+    RollupQuantiles of the totals)."""
+    quantile_columns(quantiles)
+    if len(np.asarray(quantiles).reshape(-1)) == 0:
+        raise ValueError('at least one quantile level')
+    uniq, group = rollup_groups(labels)
+    if len(group) == 0:
+        raise ValueError('nothing to reconcile: no series')
+    ds = np.asarray(ds_future_ns)
+    if ds.ndim != 1 or ds.shape[0] < 1:
+        raise ValueError('ds_future must be [H], H >= 1: a roll-up has one calendar')
+    G, H = len(uniq), ds.shape[0]
+    tspec = total_spec or spec
+    tgroup = np.arange(G, dtype=np.int64)
+    _rollup_add_args(spec, theta, y_scale, grid, group, series_key, floor, cap, extra_future, G, H)
+    if np.asarray(total_theta).ndim != 2 or np.asarray(total_theta).shape[0] != G:
+        raise ValueError('total_theta must be [G][stride]: one total per unique label')
+    _rollup_add_args(tspec, total_theta, total_y_scale, total_grid, tgroup, total_key, total_floor, total_cap,
+                     total_extra_future, G, H)
+    if set(np.asarray(total_key, dtype=np.int64).tolist()) & set(np.asarray(series_key, dtype=np.int64).tolist()):
+        raise ValueError('total_key: a total shares a key (a stream) with a member')
+    share, share_total = reconcile_shares(group, G, weight=weight, total_weight=total_weight)
+    with Rollup(ds_future_ns, G, uncertainty_samples=uncertainty_samples, seed=seed, ctx=ctx) as r:
+        r.add(spec, theta, y_scale, grid, group, series_key, floor=floor, cap=cap, extra_future=extra_future)
+        r.set_totals(tspec, total_theta, total_y_scale, total_grid, tgroup, total_key, floor=total_floor, cap=total_cap,
+                     extra_future=total_extra_future)
+        members = r.reconcile(spec, theta, y_scale, grid, group, series_key, share, quantiles=quantiles,
+                              cumulative=cumulative, floor=floor, cap=cap, extra_future=extra_future)
+        return uniq, members, r.reconciled_totals(share_total, quantiles, cumulative=cumulative)
 
 
 def predict_rollup(spec, theta, y_scale, grid, ds_future_ns, labels, quantiles, series_key, floor=None, cap=None,
