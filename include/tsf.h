@@ -436,8 +436,9 @@ int tsf_predict_quantiles_dev(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int
  * that wants nothing beyond yhat; in the host variant an infinite y_obs value (the _dev variant cannot look: there it
  * is the caller's business).  N == 0 is a legal no-op.
  *
- * Out of scope: scoring running totals against cum_q; scoring roll-ups (tsf_rollup_*); a split over several GPUs (the
- * call is per context, like tsf_predict_quantiles). */
+ * Totals over several rows (running totals, weeks, months) and roll-ups are scored by tsf_predict_windows and
+ * tsf_rollup_windows ("totals over row windows", below).
+ * Out of scope: a split over several GPUs (the call is per context, like tsf_predict_quantiles). */
 typedef struct {
     double *yhat;           /* [N][H]        required: tsf_predict's, bit for bit */
     double *pit;            /* [N][H]        NULL: not wanted (all below likewise) */
@@ -609,6 +610,99 @@ int tsf_rollup_reconcile(tsf_rollup *r, const tsf_spec *spec, int64_t N, const d
                          const double *quantiles, tsf_reconcile_out *out);
 int tsf_rollup_reconciled_totals(tsf_rollup *r, const double *share_total /* [G] */, int32_t n_q, const double *quantiles,
                                  tsf_rollup_out *out);
+
+/* ---- totals over row windows: quantiles and scores of calendar-period totals ----------------------------
+ * "P10 / P50 / P90 of next week's total, of each calendar month, of every rolling 7-row block", for a series and for
+ * a roll-up's group total, and how an observed total scores against it.  cum_q answers this only for windows that start
+ * at row 0; a later window cannot be had by differencing two of its quantiles (quantiles of sums are not sums or
+ * differences of quantiles), and summing tsf_predict_quantiles' raw samples on the host moves N * H * n_samples values.
+ * Here every sample's rows are summed over each window [win_start[k], win_end[k]) on the device, on the way into the
+ * per-row kernels' sort, and only [N][K]-sized answers leave it.  No second sample buffer is taken (cum_q takes one).
+ * Which rows make a week or a month is the caller's business: the library sees row indices (the Python layer's
+ * period_windows forms them from a calendar).
+ * Reference interface replaced: none (neither the reference nor fbprophet has such a function); parity unpinned (what
+ * is pinned is the contract below, against tsf_predict_quantiles, tsf_score_actuals and tsf_rollup_quantiles).
+ * Timing: tools/bench_windows.py; DESIGN.md 5k.
+ *
+ * tsf_predict_windows: the arguments up to seed are tsf_predict_quantiles' and mean what they mean there (the same
+ * grid check runs first, N > 0, n_samples in [2, 4096]); n_q, the levels and their checks are its as well.
+ * K in [1, TSF_MAX_WINDOWS]; win_start, win_end [K] with 0 <= win_start[k] < win_end[k] <= H: row indices, end
+ * exclusive.  Windows may overlap, repeat and come in any order.  y_win [N][K]: the observed total of every window,
+ * NaN = not observed (the caller decides what a window with a missing row is worth; the Python layer's window_totals
+ * makes it NaN); NULL where nothing is scored.  quantiles, win_start, win_end and the tsf_window_out struct are HOST
+ * memory in both variants (the windows are checked before anything is launched); y_win and the pointers inside the
+ * struct are host pointers in the host variant and device pointers in _dev.
+ *
+ * Contract:
+ *   The draws are tsf_predict_quantiles' draws (same generator, keys and counters; the chunking budget counts one
+ *   sample buffer).  The window sum of sample s is
+ *     c = sample[s][a];  c = c + sample[s][h] for h = a + 1 .. b - 1      (a = win_start[k], b = win_end[k])
+ *   plain double adds in the row order the caller gave: the running sum of tsf_predict_quantiles started at row a.
+ *   v[0 .. n_samples) below is a window's sums sorted ascending, y its y_win.
+ *   q[n][i][k] is tsf_predict_quantiles' expression at level quantiles[i] over v (same pos, lo, hi, same roundings);
+ *   pit, crps [n][k] and pinball [n][i][k] are tsf_score_actuals' expressions over v and y, operation for operation
+ *   (the mid-distribution PIT from exact counts; the CRPS regrouped to non-negative terms and summed by the fixed
+ *   halving tree, with tsf_score_actuals' error bound; NaN where y is NaN, q still written).
+ *   n_obs, mean_crps, mean_pinball and coverage are tsf_score_actuals' per-series rule with the windows in the place
+ *   of the rows: over the windows in the order given, plain double adds from +0.0, NaN where n_obs = 0.  A window
+ *   given twice counts twice.
+ *   yhat is tsf_predict's, bit for bit.  total[n][k] = yhat[n][a] + ... + yhat[n][b - 1], added one row at a time in
+ *   row order from the first row's value: the sum of the point forecasts, not the mean of the draws.
+ *   Identities (bit for bit): with the windows [h, h + 1) for every h, q is tsf_predict_quantiles' q, total is yhat,
+ *   and pit / crps / pinball and the per-series means are tsf_score_actuals' on y_obs = y_win; with the windows
+ *   [0, h + 1) for every h, q is tsf_predict_quantiles' cum_q.
+ *   No floating-point atomics.  Every output depends neither on how the call is cut into scratch chunks, nor on what
+ *   else is in the batch, nor on the other windows of the call, nor on which other outputs are requested.  Per-window
+ *   arrays the requested aggregates need and the caller did not ask for live in the context's scratch.
+ *   Behaviour for non-finite draws is unspecified (as for the quantiles).
+ *
+ * tsf_rollup_windows: the same over the handle's accumulators acc[g][h][s], a group in the place of a series (N = G,
+ * y_win [G][K]); yhat is the handle's ysum and total its window sums.  With the windows [h, h + 1) q is
+ * tsf_rollup_quantiles' q and with [0, h + 1) its cum_q, bit for bit.  Like tsf_rollup_quantiles it may be called at
+ * any time, between adds as well, and does not modify the handle; a group nobody was added to gives 0.0 in yhat,
+ * total and q.  Host pointers only.
+ *
+ * Refusals (< 0 with a message, before any launch; the context and the handle stay usable): a NULL out; an output set
+ * that wants nothing; K outside [1, TSF_MAX_WINDOWS]; NULL win_start or win_end; a window with win_start < 0,
+ * win_start >= win_end or win_end > H; n_samples outside [2, 4096]; a bad n_q or level; n_q = 0 with q, pinball,
+ * mean_pinball or coverage requested; a score output (pit, crps, pinball, n_obs, mean_crps, mean_pinball, coverage)
+ * with a NULL y_win; in the host-pointer entries an infinite y_win value (the _dev variant cannot look: there it is
+ * the caller's business); tsf_predict_quantiles' refusals of the forecast's inputs; a poisoned roll-up.
+ *
+ * Out of scope: windows of the trend draws; windows of the reconciled draws (tsf_rollup_reconcile /
+ * _reconciled_totals); windows over cross-validation folds; a roll-up `periods` key in the job configuration;
+ * per-series calendars in the Python layer's period_windows (row windows themselves work on any rows, per-series and
+ * unsorted ones included: the sum follows the caller's row order). */
+#define TSF_MAX_WINDOWS 4096
+typedef struct {
+    double *yhat;           /* [N][H]        tsf_predict's, bit for bit; NULL: not wanted (all below likewise) */
+    double *total;          /* [N][K]        the sum of yhat over each window's rows */
+    double *q;              /* [N][n_q][K]   quantiles of the window sums of the draws */
+    double *pit;            /* [N][K] */
+    double *crps;           /* [N][K] */
+    double *pinball;        /* [N][n_q][K] */
+    int32_t *n_obs;         /* [N]           windows with a non-NaN y_win */
+    double *mean_crps;      /* [N] */
+    double *mean_pinball;   /* [N][n_q] */
+    double *coverage;       /* [N][n_q] */
+} tsf_window_out;
+int tsf_window_out_size(void);      /* sizeof(tsf_window_out): the self-check of a binding */
+int tsf_predict_windows(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H, const double *theta,
+                        const double *y_scale, const tsf_grid_info *grid, int32_t n_grids, const int64_t *ds_future,
+                        int32_t shared_future, const double *floor, const double *cap, const double *extra_future,
+                        const int64_t *series_key, int32_t n_samples, uint64_t seed, int32_t K,
+                        const int32_t *win_start /* [K] */, const int32_t *win_end /* [K], exclusive */,
+                        const double *y_win /* [N][K] or NULL, NaN = not observed */, int32_t n_q,
+                        const double *quantiles, tsf_window_out *out);
+int tsf_predict_windows_dev(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H, const double *theta,
+                            const double *y_scale, const tsf_grid_info *grid, int32_t n_grids,
+                            const int64_t *ds_future, int32_t shared_future, const double *floor, const double *cap,
+                            const double *extra_future, const int64_t *series_key, int32_t n_samples, uint64_t seed,
+                            int32_t K, const int32_t *win_start, const int32_t *win_end, const double *y_win,
+                            int32_t n_q, const double *quantiles, tsf_window_out *out, void *stream);
+int tsf_rollup_windows(tsf_rollup *r, int32_t K, const int32_t *win_start, const int32_t *win_end,
+                       const double *y_win /* [G][K] or NULL */, int32_t n_q, const double *quantiles,
+                       tsf_window_out *out);
 
 /* ---- cross-validation ---------------------------------------------------------------------
  * fbprophet 0.5 diagnostics.cross_validation + performance_metrics for a whole panel: every series is refitted at

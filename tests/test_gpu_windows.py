@@ -1,0 +1,697 @@
+"""GPU tests of the totals over row windows (tsf_predict_windows, tsf_predict_windows_dev, tsf_rollup_windows:
+window_score_kernel, window_total_kernel; forecaster.predict_windows / Rollup.windows; the scorer's
+forecast.period_totals).
+
+What pins them (include/tsf.h, the contract of "totals over row windows"), bit for bit throughout:
+  one-row windows against predict_quantiles' q and score_actuals' scores and means;
+  windows from row 0 against predict_quantiles' cum_q;
+  general windows against the numpy restatement (tests/window_ref.py) evaluated on the draws that predictive_samples
+  (for a roll-up: Rollup.samples) returns;
+  independence of the output selection, of the batch, of the scratch chunks and of the other windows.
+The one comparison that is not bit for bit is crps against the sample CRPS of the window sums in exact rational
+arithmetic, within the bound the header derives for tsf_score_actuals.
+NaN compares as NaN (score_ref.same): its payload is not part of the contract."""
+import ctypes
+import os
+import re
+import subprocess
+from datetime import datetime as real_datetime
+from fractions import Fraction
+
+import numpy as np
+import pandas as pd
+import pytest
+# at collection, before anything loads libtsf_amd.so (as in tests/test_gpu_dev_entries.py): the library binds to the HIP
+# runtime that is loaded first
+import torch
+
+from tests import forecast_cases as fcs, helpers, score_ref as sr, window_ref as wr
+
+pytestmark = pytest.mark.gpu
+
+SEED = 23
+LEVELS = np.array([0, 0.1, 0.5, 0.9, 0.975, 1])
+SAMPLES = [2, 3, 257, 1000, 4096]
+ROW = ('q', 'pit', 'crps', 'pinball')
+SER = ('n_obs', 'mean_crps', 'mean_pinball', 'coverage')
+ALL = ('total',) + ROW + SER
+
+
+@pytest.fixture(scope='module')
+def env(built):
+    from time_series_spark_amd import _lib, forecaster as fc
+    if _lib.load().tsf_device_count() < 1:
+        pytest.fail('no GPU visible: GPU window tests cannot run (product has no CPU fallback)')
+    return fc, _lib
+
+
+def _keys(c):
+    return np.arange(c.N, dtype=np.int64) * 6151 + 11
+
+
+def _args(c):
+    return c.spec, c.theta, c.y_scale, c.grid, c.fut
+
+
+def _kw(c, n_samples, keys=None):
+    return dict(floor=c.floor, cap=c.cap, extra_future=c.extra, series_key=_keys(c) if keys is None else keys, seed=SEED,
+                uncertainty_samples=n_samples)
+
+
+def _call(fc, c, w, y_win, want, n_samples, levels=LEVELS, sl=slice(None), keys=None):
+    """the binding's one call (forecaster._predict_windows_call) on series `sl` of the case with any set of outputs"""
+    keys = _keys(c) if keys is None else keys
+    return fc._predict_windows_call(c.spec, c.theta[sl], c.y_scale[sl], c.grid if len(c.grid) == 1 else c.grid[sl],
+                                    c.fut if c.shared else c.fut[sl], w, None if y_win is None else y_win[sl], c.floor[sl],
+                                    None if c.cap is None else c.cap[sl],
+                                    c.extra if (c.extra is None or c.shared) else c.extra[sl], keys[sl], n_samples, SEED,
+                                    levels, want, None)
+
+
+def _y_rows(draws, yhat, seed=0):
+    """observed rows: the point forecast plus noise, a value below every draw (row 1), above every draw (row 2), a tie
+    with a draw (row 3), NaN rows; the last series all NaN"""
+    N, H, S = draws.shape
+    rng = np.random.default_rng(seed)
+    y = yhat + rng.normal(0, 1, (N, H)) * draws.std(axis=-1)
+    y[:, 1] = draws[:, 1].min(axis=-1) - 1.0
+    y[:, 2] = draws[:, 2].max(axis=-1) + 1.0
+    y[:, 3] = draws[:, 3, min(7, S - 1)]
+    y[:, 4:6] = np.nan
+    y[0, 40:50] = np.nan
+    y[N - 1] = np.nan
+    return y
+
+
+def _general_windows(fc, H):
+    """overlapping and disjoint windows, the whole range, the last row alone, a window given twice, descending order"""
+    start = [0, 0, 7, 5, H - 1, 7, H - 9, 40, 20, 3, 2]
+    end = [H, 7, 14, 30, H, 14, H, 64, 21, 5, 4]
+    return fc.Windows(start, end)
+
+
+def _y_win(sums, seed=1):
+    """observed totals from the window sums [N][K][S]: inside the draws, below all of them (window 0), above all (1), a
+    tie with a draw (2), not observed (3, and the last window of series 0)"""
+    N, K, S = sums.shape
+    rng = np.random.default_rng(seed)
+    y = sums[:, :, 1] + rng.normal(0, 0.3, (N, K)) * sums.std(axis=-1)
+    y[:, 0] = sums[:, 0].min(axis=-1) - 1.0
+    y[:, 1] = sums[:, 1].max(axis=-1) + 1.0
+    y[:, 2] = sums[:, 2, min(7, S - 1)]
+    y[:, 3] = np.nan
+    y[0, K - 1] = np.nan
+    return y
+
+
+@pytest.fixture(scope='module')
+def drawn(env):
+    """per (case, sample count): the case, its draws and its point forecast -- computed once, read-only"""
+    fc, _lib = env
+    cache = {}
+
+    def get(name, n_samples):
+        if (name, n_samples) not in cache:
+            c = fcs.make(name)
+            draws = fc.predictive_samples(*_args(c), **_kw(c, n_samples))['yhat']
+            yhat = fc.predict(*_args(c), floor=c.floor, cap=c.cap, extra_future=c.extra)
+            draws.setflags(write=False)
+            yhat.setflags(write=False)
+            cache[(name, n_samples)] = (c, draws, yhat)
+        return cache[(name, n_samples)]
+    return get
+
+
+@pytest.fixture(scope='module')
+def general(env, drawn):
+    """per (case, sample count): the general windows, the observed totals and the call with every output"""
+    fc, _lib = env
+    cache = {}
+
+    def get(name, n_samples):
+        if (name, n_samples) not in cache:
+            c, draws, yhat = drawn(name, n_samples)
+            w = _general_windows(fc, c.H)
+            sums = wr.window_sums(draws, w.start, w.end)
+            y = _y_win(sums)
+            got = _call(fc, c, w, y, ('yhat',) + ALL, n_samples)
+            for a in [sums, y] + list(got.values()):
+                a.setflags(write=False)
+            cache[(name, n_samples)] = (c, w, sums, y, got)
+        return cache[(name, n_samples)]
+    return get
+
+
+# ---- 1. one-row windows are the rows ---------------------------------------------------------------------------------
+
+@pytest.mark.parametrize('name', ['iv65', 'iv129'])
+@pytest.mark.parametrize('n_samples', SAMPLES)
+def test_one_row_windows_are_the_rows(env, drawn, name, n_samples):
+    fc, _lib = env
+    c, draws, yhat = drawn(name, n_samples)
+    w = fc.row_windows(c.H, 1)
+    assert len(w) == c.H
+    pq = fc.predict_quantiles(*_args(c), LEVELS, **_kw(c, n_samples))
+    r = fc.predict_windows(*_args(c), w, LEVELS, **_kw(c, n_samples))
+    assert sr.same(r.q, pq.q) and sr.same(r.yhat, pq.yhat) and sr.same(r.total, r.yhat) and sr.same(r.yhat, yhat)
+    assert r.pit is None and r.crps is None and r.n_obs is None and r.y is None
+    y = _y_rows(draws, yhat)
+    s = fc.score_actuals(*_args(c), y, LEVELS, **_kw(c, n_samples))
+    r = fc.predict_windows(*_args(c), w, LEVELS, y_obs=y, **_kw(c, n_samples))
+    assert sr.same(r.y, y) and sr.same(r.q, pq.q) and sr.same(r.total, yhat)
+    for k in ('pit', 'crps', 'pinball') + SER:
+        assert sr.same(getattr(r, k), getattr(s, k)), k
+    assert r.n_obs.dtype == np.int32 and r.n_obs[-1] == 0 and np.isnan(r.mean_crps[-1])
+    assert (r.pit[:-1, 1] == 0.0).all() and (r.pit[:-1, 2] == 1.0).all()
+
+
+# ---- 2. windows from row 0 are the running sums ----------------------------------------------------------------------
+
+@pytest.mark.parametrize('name', ['iv65', 'iv129'])
+@pytest.mark.parametrize('n_samples', SAMPLES)
+def test_prefix_windows_are_the_cumulative_quantiles(env, drawn, name, n_samples):
+    fc, _lib = env
+    c, draws, yhat = drawn(name, n_samples)
+    rows = np.arange(c.H)
+    w = fc.Windows(0 * rows, rows + 1)
+    pq = fc.predict_quantiles(*_args(c), LEVELS, cumulative=True, **_kw(c, n_samples))
+    r = fc.predict_windows(*_args(c), w, LEVELS, **_kw(c, n_samples))
+    assert sr.same(r.q, pq.cum_q) and sr.same(r.q[:, :, 0], pq.q[:, :, 0])
+    assert sr.same(r.total, np.cumsum(yhat, axis=1))
+    assert name != 'iv65' or (np.diff(c.fut, axis=1) < 0).any()             # unsorted rows: the sum follows the row order
+
+
+# ---- 3. general windows against the restatement ----------------------------------------------------------------------
+
+@pytest.mark.parametrize('name', ['iv65', 'iv129'])
+@pytest.mark.parametrize('n_samples', SAMPLES)
+def test_general_windows_against_the_restatement(env, drawn, general, name, n_samples):
+    fc, _lib = env
+    c, draws, yhat = drawn(name, n_samples)
+    c, w, sums, y, got = general(name, n_samples)
+    want = wr.score(draws, y, LEVELS, w.start, w.end)
+    assert sr.same(got['yhat'], yhat) and sr.same(got['total'], wr.totals(yhat, w.start, w.end))
+    assert got['n_obs'].dtype == np.int32
+    for k in ROW + SER:
+        assert sr.same(got[k], want[k]), k
+    K = len(w)
+    assert got['n_obs'].tolist() == [K - 2] + [K - 1] * (c.N - 1)
+    # the edge windows are what they are meant to be
+    assert (got['pit'][:, 0] == 0.0).all() and (got['pit'][:, 1] == 1.0).all()
+    assert np.isnan(got['pit'][:, 3]).all() and np.isnan(got['crps'][0, K - 1]) and np.isnan(got['pinball'][:, :, 3]).all()
+    assert not np.isnan(got['q']).any() and (got['crps'][~np.isnan(y)] >= 0).all()
+    # the window given twice: the same numbers in both places
+    assert (w.start[2], w.end[2]) == (w.start[5], w.end[5]) and sr.same(got['q'][:, :, 2], got['q'][:, :, 5])
+    # the public call on observed rows: the same path with y_win = window_totals(y_obs)
+    y_rows = _y_rows(draws, yhat)
+    r = fc.predict_windows(*_args(c), w, LEVELS, y_obs=y_rows, **_kw(c, n_samples))
+    want = wr.score(draws, fc.window_totals(y_rows, w), LEVELS, w.start, w.end)
+    assert sr.same(r.q, got['q']) and sr.same(r.total, got['total']) and sr.same(r.y, fc.window_totals(y_rows, w))
+    for k in ('pit', 'crps', 'pinball') + SER:
+        assert sr.same(getattr(r, k), want[k]), k
+    assert np.isnan(r.y[:, 0]).all() and (r.n_obs[:-1] > 0).all() and r.n_obs[-1] == 0
+    f = r.frame(0)
+    assert list(f.columns) == (['period_start', 'period_end', 'n_rows', 'yhat', 'y'] + fc.quantile_columns(LEVELS)
+                               + ['pit', 'crps'] + fc.quantile_columns(LEVELS, 'pinball_q'))
+    assert len(f) == K and sr.same(f['yhat_q97.5'].to_numpy(), r.q[0, 4]) and sr.same(f['yhat'].to_numpy(), r.total[0])
+
+
+@pytest.mark.parametrize('n_samples', [3, 257, 4096])
+def test_crps_against_the_exact_value(env, general, n_samples):
+    """|crps - exact| <= 2^-53 (4 mean|v - y| + (log2(NSP) + 2) exact) on the window sums of the returned draws (the
+    bound the header derives for tsf_score_actuals, whose expressions these are)"""
+    fc, _lib = env
+    c, w, sums, y, got = general('iv65', n_samples)
+    for n, k in [(0, 0), (0, 1), (0, 2), (0, 4), (0, 6), (1, 0), (1, 7), (1, 10), (2, 2), (2, 8)]:
+        assert not np.isnan(y[n, k])
+        exact = sr.crps_exact(sums[n, k], y[n, k])
+        assert abs(Fraction(float(got['crps'][n, k])) - exact) <= sr.crps_bound(sums[n, k], y[n, k], exact), (n, k)
+
+
+# ---- 4. independence of the batch and of the scratch chunks ----------------------------------------------------------
+
+@pytest.mark.parametrize('name', ['iv65', 'iv129'])
+def test_each_series_alone(env, general, name):
+    fc, _lib = env
+    c, w, sums, y, full = general(name, 257)
+    for n in range(c.N):
+        one = _call(fc, c, w, y, ('yhat',) + ALL, 257, sl=slice(n, n + 1))
+        for k in ('yhat',) + ALL:
+            assert sr.same(one[k], full[k][n:n + 1]), (n, k)
+
+
+def test_windows_over_two_chunks(env):
+    """72 series x 960 rows x 1000 samples: one sample buffer, 7.7 MB per series, 69 series per 512 MB chunk, so the call
+    runs two chunks; series 64 .. 72 (both chunks) against a call on them alone, the aggregates included; one series
+    entirely unobserved"""
+    fc, _lib = env
+    c = fcs.make('h960')
+    rng = np.random.default_rng(5)
+    rep = 24
+    c.N = c.N * rep
+    ncp = c.spec.n_changepoints
+    c.theta = np.tile(c.theta, (rep, 1))
+    c.theta[:, 3 + ncp:] *= rng.uniform(0.5, 1.5, (c.N, 1))
+    c.theta[:, 2] += rng.normal(0, 0.3, c.N)
+    c.y_scale = np.tile(c.y_scale, rep) * rng.uniform(0.5, 2.0, c.N)
+    c.floor = np.tile(c.floor, rep)
+    assert c.N == 72 and c.H == 960
+    keys = np.arange(c.N, dtype=np.int64) ^ 0x3333
+    blocks = 7 * np.arange(137)
+    w = fc.Windows(np.concatenate([[0, 100, 959], blocks]), np.concatenate([[960, 107, 960], blocks + 7]))
+    assert len(w) == 140 and w.end[-1] == 959
+    yhat = fc.predict(*_args(c), floor=c.floor)
+    y_rows = yhat * (1.0 + 0.2 * rng.normal(size=yhat.shape))
+    y_rows[rng.uniform(size=y_rows.shape) < 0.01] = np.nan
+    y_rows[70] = np.nan
+    y = fc.window_totals(y_rows, w)
+    assert np.isnan(y[:, 0]).all() and not np.isnan(y[:70, 3:]).all(axis=1).any()
+    lv = [0.1, 0.5, 0.9]
+    full = _call(fc, c, w, y, ('yhat',) + ALL, 1000, levels=lv, keys=keys)
+    sl = slice(64, 72)
+    part = _call(fc, c, w, y, ('yhat',) + ALL, 1000, levels=lv, sl=sl, keys=keys)
+    for k in ('yhat',) + ALL:
+        assert sr.same(full[k][sl], part[k]), k
+    # the aggregates alone: their per-window inputs live in the scratch behind the chunk, yhat is not asked for
+    agg = _call(fc, c, w, y, SER, 1000, levels=lv, keys=keys)
+    assert set(agg) == set(SER)
+    for k in SER:
+        assert sr.same(agg[k], full[k]), k
+    assert sr.same(full['yhat'], yhat) and sr.same(full['total'], wr.totals(yhat, w.start, w.end))
+    assert full['n_obs'][70] == 0 and np.isnan(full['mean_crps'][70]) and np.isnan(full['coverage'][70]).all()
+    assert np.isnan(full['mean_pinball'][70]).all() and (full['n_obs'][:70] > 0).all()
+    want = sr.series(y, full['crps'], full['q'], full['pinball'])
+    for k in SER:
+        assert sr.same(full[k], want[k]), k
+    # the one-row window and the whole range against the per-row entries on the same keys
+    pq = fc.predict_quantiles(*_args(c), lv, floor=c.floor, series_key=keys, uncertainty_samples=1000, seed=SEED,
+                              cumulative=True)
+    assert sr.same(full['q'][:, :, 2], pq.q[:, :, 959]) and sr.same(full['q'][:, :, 0], pq.cum_q[:, :, 959])
+    assert sr.same(full['q'][:, :, 3], pq.cum_q[:, :, 6])
+
+
+# ---- 5. any subset of the outputs -------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize('name', ['iv65', 'iv129'])
+def test_any_subset_of_the_outputs(env, general, name):
+    fc, _lib = env
+    c, w, sums, y, full = general(name, 257)
+    every = ('yhat',) + ALL
+    subsets = [(k,) for k in every] + [SER, ROW, ('n_obs', 'coverage'), ('mean_pinball', 'q'), ('mean_crps', 'pinball'),
+                                       ('crps', 'coverage', 'total'), ('pit', 'mean_pinball', 'mean_crps'),
+                                       ('yhat', 'total'), ('total', 'mean_crps')]
+    for want in subsets:
+        r = _call(fc, c, w, y, want, 257)
+        assert set(r) == set(want)
+        for k in r:
+            assert sr.same(r[k], full[k]), (want, k)
+    # no observed totals: the outputs that need none
+    for want in (('q',), ('yhat', 'total', 'q'), ('total',), ('yhat',)):
+        r = _call(fc, c, w, None, want, 257)
+        assert set(r) == set(want)
+        for k in r:
+            assert sr.same(r[k], full[k]), (want, k)
+    # no levels: the outputs that need none
+    r = _call(fc, c, w, y, ('pit', 'crps', 'n_obs', 'mean_crps', 'total'), 257, levels=[])
+    for k in r:
+        assert sr.same(r[k], full[k]), k
+    p = fc.predict_windows(*_args(c), w, [], y_obs=None, **_kw(c, 257))
+    assert p.q is None and p.pit is None and sr.same(p.total, full['total']) and sr.same(p.yhat, full['yhat'])
+
+
+# ---- 6. roll-ups ---------------------------------------------------------------------------------------------------------
+
+def _members(name, N, seed, key0):
+    """case `name` repeated to N series with perturbed parameters -> dict of the arguments of Rollup.add"""
+    c = fcs.make(name)
+    rng = np.random.default_rng(seed)
+    rep = -(-N // c.N)
+    ncp = c.spec.n_changepoints
+    theta = np.tile(c.theta, (rep, 1))[:N].copy()
+    theta[:, 3 + ncp:] *= rng.uniform(0.5, 1.5, (N, 1))
+    theta[:, 2] += rng.normal(0, 0.3, N)
+    return dict(spec=c.spec, theta=theta, y_scale=np.tile(c.y_scale, rep)[:N] * rng.uniform(0.5, 2.0, N),
+                grid=c.grid[np.arange(N) % len(c.grid)].copy(), floor=np.tile(c.floor, rep)[:N].copy(),
+                cap=None if c.cap is None else np.tile(c.cap, rep)[:N].copy(),
+                series_key=np.arange(N, dtype=np.int64) * 7919 + key0), c
+
+
+def _add(roll, m, group, extra=None):
+    roll.add(m['spec'], m['theta'], m['y_scale'], m['grid'], group, m['series_key'], floor=m['floor'], cap=m['cap'],
+             extra_future=extra)
+
+
+def _check_rollup(roll, w, y_rows, lv=LEVELS):
+    """Rollup.windows against the restatement on the handle's own summed draws"""
+    from time_series_spark_amd import forecaster as fc
+    acc = roll.samples()
+    before = roll.quantiles(lv, cumulative=True)
+    r = roll.windows(w, lv, y_obs=y_rows)
+    y = fc.window_totals(y_rows, w)
+    want = wr.score(acc, y, lv, w.start, w.end)
+    assert sr.same(r.yhat, before.yhat) and sr.same(r.total, wr.totals(before.yhat, w.start, w.end)) and sr.same(r.y, y)
+    for k in ROW + SER:
+        assert sr.same(getattr(r, k), want[k]), k
+    # reading windows changes nothing: the accumulators and the quantiles afterwards, bit for bit
+    after = roll.quantiles(lv, cumulative=True)
+    assert sr.same(roll.samples(), acc) and sr.same(after.q, before.q) and sr.same(after.cum_q, before.cum_q)
+    assert sr.same(after.yhat, before.yhat) and np.array_equal(after.count, before.count)
+    return r, before
+
+
+@pytest.mark.parametrize('n_samples', [3, 257, 1000])
+def test_rollup_windows(env, n_samples):
+    """two specs in one handle (iv129's and iv65's members on one calendar), a read between the two adds, a group of one
+    series, an empty group"""
+    fc, _lib = env
+    a, ca = _members('iv129', 40, seed=11, key0=3)
+    b, cb = _members('iv65', 21, seed=12, key0=10 ** 7)
+    H = 30
+    cal = np.ascontiguousarray(np.sort(cb.fut[0])[:H])
+    extra = np.ascontiguousarray(ca.extra[:, :H])
+    ga = np.arange(40, dtype=np.int64) % 4
+    ga[39] = 4                                              # series 39 alone in group 4; group 5 stays empty
+    gb = np.arange(21, dtype=np.int64) % 3
+    w = fc.Windows([0, 0, 7, 5, H - 1, 7, 20, 3], [H, 7, 14, 25, H, 14, 21, 5])
+    rng = np.random.default_rng(3)
+    with fc.Rollup(cal, 6, uncertainty_samples=n_samples, seed=SEED) as roll:
+        _add(roll, a, ga, extra)
+        y_rows = roll.quantiles([0.5]).yhat * (1.0 + 0.05 * rng.normal(size=(6, H)))
+        y_rows[1, 8] = np.nan
+        y_rows[3] = np.nan
+        r1, q1 = _check_rollup(roll, w, y_rows)                # between the two adds
+        assert q1.count.tolist() == [10, 10, 10, 9, 1, 0]
+        # the group of one is the series
+        one = fc.predict_windows(a['spec'], a['theta'][39:], a['y_scale'][39:], a['grid'][39:], cal, w, LEVELS,
+                                 y_obs=y_rows[4:5], floor=a['floor'][39:], extra_future=extra,
+                                 series_key=a['series_key'][39:], uncertainty_samples=n_samples, seed=SEED)
+        for k in ('yhat', 'total') + ROW + SER:
+            assert sr.same(getattr(r1, k)[4:5], getattr(one, k)), k
+        # the empty group: +0.0 everywhere, scored like any other distribution
+        assert sr.same(r1.q[5], np.zeros((len(LEVELS), len(w)))) and sr.same(r1.total[5], np.zeros(len(w)))
+        assert r1.n_obs.tolist() == [8, 4, 8, 0, 8, 8] and np.isnan(r1.mean_crps[3])
+        _add(roll, b, gb)
+        r2, q2 = _check_rollup(roll, w, y_rows)
+        assert q2.count.tolist() == [17, 17, 17, 9, 1, 0]
+        assert sr.same(r2.q[3:], r1.q[3:]) and not sr.same(r2.q[:3], r1.q[:3])
+        # quantiles only, and one-row / prefix windows against the handle's own quantiles
+        rows = np.arange(H)
+        rq = roll.windows(fc.row_windows(H, 1), LEVELS)
+        assert rq.pit is None and sr.same(rq.q, q2.q) and sr.same(rq.total, q2.yhat)
+        assert sr.same(roll.windows(fc.Windows(0 * rows, rows + 1), LEVELS).q, q2.cum_q)
+        sub = roll._windows_call(w, fc.window_totals(y_rows, w), LEVELS, ('coverage', 'mean_crps'))
+        assert set(sub) == {'coverage', 'mean_crps'}
+        assert sr.same(sub['coverage'], r2.coverage) and sr.same(sub['mean_crps'], r2.mean_crps)
+        with pytest.raises(ValueError, match='behind'):
+            roll.windows(fc.row_windows(H + 1, 7), LEVELS)
+        with pytest.raises(ValueError, match='y_obs must be'):
+            roll.windows(w, LEVELS, y_obs=y_rows[:5])
+
+
+# ---- 7. the _dev entry ---------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize('keyed', [True, False])
+@pytest.mark.parametrize('name', ['iv65', 'iv129'])
+def test_predict_windows_dev(env, name, keyed):
+    """every input and output in device memory (torch tensors), on a caller stream that is not the default one: the
+    host entry's bits (the windows and the levels are host data in both)"""
+    fc, _lib = env
+    L, ctx = _lib.load(), fc.get_context()
+    c = fcs.make(name)
+    cs = c.spec.to_c()
+    n_samples, lv = 3, np.array([0.1, 0.9])
+    Q = len(lv)
+    w = _general_windows(fc, c.H)
+    K = len(w)
+    yhat = fc.predict(*_args(c), floor=c.floor, cap=c.cap, extra_future=c.extra)
+    y = fc.window_totals(yhat * (1.0 + 0.1 * np.random.default_rng(4).normal(size=yhat.shape)), w)
+    y[0, 2] = np.nan
+    f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)        # noqa: E731
+    host = dict(theta=f64(c.theta), y_scale=f64(c.y_scale),
+                grid=np.ascontiguousarray(c.grid, dtype=_lib.GRID_DTYPE).view(np.uint8),
+                fut=np.ascontiguousarray(c.fut, dtype=np.int64), floor=f64(c.floor), cap=f64(c.cap), extra=f64(c.extra),
+                key=_keys(c) if keyed else None, y=y)
+    dev = {k: None if v is None else torch.from_numpy(v).cuda() for k, v in host.items()}
+
+    def ptr(a):
+        return None if a is None else (a.data_ptr() if hasattr(a, 'data_ptr') else a.ctypes.data)
+
+    def head(a):
+        return [ctx.handle, ctypes.byref(cs), c.N, c.H, ptr(a['theta']), ptr(a['y_scale']), ptr(a['grid']), len(c.grid),
+                ptr(a['fut']), int(c.shared), ptr(a['floor']), ptr(a['cap']), ptr(a['extra']), ptr(a['key']), n_samples,
+                SEED, K, w.start.ctypes.data, w.end.ctypes.data, ptr(a['y']), Q, lv.ctypes.data]
+    out_h = {'yhat': np.zeros((c.N, c.H)), 'n_obs': np.zeros(c.N, np.int32), 'mean_crps': np.zeros(c.N)}
+    out_h.update({k: np.zeros((c.N, K)) for k in ('total', 'pit', 'crps')})
+    out_h.update({k: np.zeros((c.N, Q, K)) for k in ('q', 'pinball')})
+    out_h.update({k: np.zeros((c.N, Q)) for k in ('mean_pinball', 'coverage')})
+    out_d = {k: torch.from_numpy(v).cuda().fill_(-7 if v.dtype.kind == 'i' else float('nan')) for k, v in out_h.items()}
+    ho = _lib.TsfWindowOut(**{k: ptr(v) for k, v in out_h.items()})
+    do = _lib.TsfWindowOut(**{k: ptr(v) for k, v in out_d.items()})
+    ctx.check(L.tsf_predict_windows(*(head(host) + [ctypes.byref(ho)])))
+    torch.cuda.synchronize()                        # the device inputs and output fills are on the default stream
+    st = torch.cuda.Stream()
+    assert st.cuda_stream != 0
+    ctx.check(L.tsf_predict_windows_dev(*(head(dev) + [ctypes.byref(do), ctypes.c_void_p(st.cuda_stream)])))
+    st.synchronize()
+    for k, h in out_h.items():
+        got = out_d[k].cpu().numpy()
+        assert got.dtype == h.dtype and sr.same(got, h), k
+    assert sr.same(out_h['yhat'], yhat) and out_h['n_obs'].tolist() == [K - 1] + [K] * (c.N - 1)
+    assert not np.isnan(out_h['q']).any() and np.isnan(out_h['pit'][0, 2])
+
+
+# ---- 8. refusals ---------------------------------------------------------------------------------------------------------
+
+def test_refusals(env):
+    """each of these is refused (< 0, a message) before anything is launched, and the context stays usable"""
+    fc, _lib = env
+    L = _lib.load()
+    ctx = fc.get_context()
+    c = fcs.make('iv129')
+    N, H = c.N, c.H
+    cs = c.spec.to_c()
+    theta, ys = np.ascontiguousarray(c.theta), np.ascontiguousarray(c.y_scale)
+    fut, ex = np.ascontiguousarray(c.fut, dtype=np.int64), np.ascontiguousarray(c.extra)
+    KMAX = _lib.MAX_WINDOWS
+    bufs = {k: np.zeros((N, 65, KMAX + 1)) for k in ('q', 'pinball')}
+    bufs.update({k: np.zeros((N, KMAX + 1)) for k in ('total', 'pit', 'crps')})
+    bufs.update(yhat=np.zeros((N, H)), n_obs=np.zeros(N, np.int32), mean_crps=np.zeros(N), mean_pinball=np.zeros((N, 65)),
+                coverage=np.zeros((N, 65)))
+    y_ok = np.full((N, KMAX + 1), 1.0)
+
+    def call(levels, start=(0, 7), end=(7, H), n_samples=10, want=('pit', 'q'), grid=c.grid, n_q=None, y=y_ok, out=True,
+             K=None, windows=True):
+        levels = np.ascontiguousarray(levels, dtype=np.float64)
+        grid = np.ascontiguousarray(grid)
+        start, end = np.ascontiguousarray(start, dtype=np.int32), np.ascontiguousarray(end, dtype=np.int32)
+        o = _lib.TsfWindowOut(**{k: bufs[k].ctypes.data for k in want})
+        y_k = None if y is None else np.ascontiguousarray(y[:, :len(start)])        # [N][K]
+        return L.tsf_predict_windows(ctx.handle, ctypes.byref(cs), N, H, theta.ctypes.data, ys.ctypes.data, grid.ctypes.data,
+                                     len(grid), fut.ctypes.data, 1, None, None, ex.ctypes.data, None, n_samples, 0,
+                                     len(start) if K is None else K, start.ctypes.data if windows else None,
+                                     end.ctypes.data, None if y is None else y_k.ctypes.data,
+                                     len(levels) if n_q is None else n_q, levels.ctypes.data,
+                                     ctypes.byref(o) if out else None)
+
+    ok = [0.1, 0.9]
+    assert call(ok) == 0 and call(ok, want=('yhat',) + ALL) == 0 and call([], want=('pit',)) == 0
+    assert call([], want=('n_obs',)) == 0 and call([], want=('yhat',), y=None) == 0 and call(ok, want=('q',), y=None) == 0
+    assert call(np.linspace(0, 1, 64), want=ALL) == 0
+    assert call(ok, start=np.zeros(KMAX), end=np.ones(KMAX)) == 0                   # the most windows there may be
+    inf = y_ok.copy()
+    inf[1, 0] = np.inf
+    bad_grid = c.grid.copy()
+    bad_grid['S'][1] = -1
+    for kw, why in ((dict(levels=ok, out=False), 'NULL output'),
+                    (dict(levels=ok, K=0), r'K must be'),
+                    (dict(levels=ok, start=np.zeros(KMAX + 1), end=np.ones(KMAX + 1)), r'K must be'),
+                    (dict(levels=ok, windows=False), 'NULL win_start'),
+                    (dict(levels=ok, start=(0, 9), end=(7, 9)), r'window 1 = \[9, 9\)'),
+                    (dict(levels=ok, start=(0, 9), end=(7, 8)), r'window 1 = \[9, 8\)'),
+                    (dict(levels=ok, start=(0, 9), end=(H + 1, 12)), r'window 0 = \[0, %d\)' % (H + 1)),
+                    (dict(levels=ok, start=(0, -1), end=(7, 5)), r'window 1 = \[-1, 5\)'),
+                    (dict(levels=ok, want=('pit', 'q'), y=None), 'NULL y_win'),
+                    (dict(levels=ok, want=('n_obs',), y=None), 'NULL y_win'),
+                    (dict(levels=ok, want=('q', 'coverage'), y=None), 'NULL y_win'),
+                    (dict(levels=ok, y=inf), r'y_win\[1\]\[0\] is infinite'),
+                    (dict(levels=ok, y=-inf), r'y_win\[1\]\[0\] is infinite'),
+                    (dict(levels=[0.5, -0.1]), r'quantiles\[1\]'),
+                    (dict(levels=[0.1, 0.2, float('nan')]), r'quantiles\[2\]'),
+                    (dict(levels=np.linspace(0, 1, 65)), 'n_q'),
+                    (dict(levels=ok, n_q=-1), 'n_q'),
+                    (dict(levels=[], want=('q',)), 'n_q = 0'),
+                    (dict(levels=[], want=('crps', 'coverage')), 'n_q = 0'),
+                    (dict(levels=ok, n_samples=1), 'n_samples'),
+                    (dict(levels=ok, n_samples=4097), 'n_samples'),
+                    (dict(levels=ok, want=()), 'nothing requested'),
+                    (dict(levels=ok, grid=bad_grid), r'grid\[1\]')):
+        rc = call(**kw)
+        assert rc < 0, why
+        assert re.search(why, L.tsf_last_error(ctx.handle).decode()), (why, L.tsf_last_error(ctx.handle))
+        assert call(ok) == 0, why                               # a good call on the same context succeeds
+    w = fc.Windows([0, 7], [7, H])
+    with pytest.raises(_lib.TsfError, match='n_samples'):
+        fc.predict_windows(*_args(c), w, ok, extra_future=c.extra, uncertainty_samples=4097)
+    # the same call as before the refusals, the same bits
+    r = fc.predict_windows(*_args(c), w, ok, extra_future=c.extra, uncertainty_samples=10)
+    assert call(ok) == 0 and sr.same(r.q, bufs['q'].reshape(-1)[:N * 2 * 2].reshape(N, 2, 2))
+    # the roll-up entry: the same checks, and the handle stays usable
+    with fc.Rollup(fut, 2, uncertainty_samples=10, seed=0) as roll:
+        roll.add(c.spec, c.theta, c.y_scale, c.grid, np.arange(N, dtype=np.int64), _keys(c), extra_future=c.extra)
+        good = roll.windows(w, ok)
+
+        def rcall(start, end, want=('q',), y=None, levels=ok):
+            start, end = np.ascontiguousarray(start, dtype=np.int32), np.ascontiguousarray(end, dtype=np.int32)
+            lv = np.ascontiguousarray(levels, dtype=np.float64)
+            o = _lib.TsfWindowOut(**{k: bufs[k].ctypes.data for k in want})
+            return L.tsf_rollup_windows(roll._handle(), len(start), start.ctypes.data, end.ctypes.data,
+                                        None if y is None else np.ascontiguousarray(y).ctypes.data, len(lv),
+                                        lv.ctypes.data, ctypes.byref(o))
+        for kw, why in ((dict(start=[], end=[]), 'K must be'), (dict(start=[3], end=[3]), r'window 0 = \[3, 3\)'),
+                        (dict(start=[0], end=[H + 1]), 'window 0'), (dict(start=[0], end=[H], want=('crps',)), 'NULL y_win'),
+                        (dict(start=[0], end=[H], want=('crps',), y=[[np.inf], [1.0]]), r'y_win\[0\]\[0\] is infinite'),
+                        (dict(start=[0], end=[H], levels=[1.5]), r'quantiles\[0\]'),
+                        (dict(start=[0], end=[H], want=()), 'nothing requested')):
+            assert rcall(**kw) < 0, why
+            assert re.search(why, L.tsf_last_error(ctx.handle).decode()), (why, L.tsf_last_error(ctx.handle))
+        assert sr.same(roll.windows(w, ok).q, good.q)
+
+
+# ---- 9. plain C ------------------------------------------------------------------------------------------------------------
+
+def test_abi_windows_plain_c(env, tmp_path):
+    """tests/c/abi_windows.c drives tsf_predict_windows and tsf_rollup_windows from plain C99 and writes what they return"""
+    fc, _lib = env
+    c = fcs.make('iv129')
+    d = str(tmp_path)
+    w = fc.period_windows(c.fut, 'D')                           # the hourly calendar's days
+    K = len(w)
+    assert 6 <= K <= 7 and w.n_rows.sum() == c.H
+    yhat = fc.predict(*_args(c), extra_future=c.extra)
+    y_rows = yhat * (1.0 + 0.1 * np.random.default_rng(2).normal(size=yhat.shape))
+    y_rows[0, 30] = np.nan
+    y = fc.window_totals(y_rows, w)
+    g_rows = y_rows[:1] + y_rows[1:]
+    g_rows[0, 30] = yhat[:, 30].sum()
+    gy = fc.window_totals(g_rows, w)
+    keys = _keys(c)
+    np.ascontiguousarray(c.theta).tofile(d + '/theta.f64')
+    np.ascontiguousarray(c.y_scale).tofile(d + '/ys.f64')
+    np.ascontiguousarray(c.grid).tofile(d + '/grid.bin')
+    np.ascontiguousarray(c.fut, dtype=np.int64).tofile(d + '/fut.i64')
+    np.ascontiguousarray(c.extra).tofile(d + '/extra.f64')
+    keys.tofile(d + '/key.i64')
+    w.start.tofile(d + '/w0.i32')
+    w.end.tofile(d + '/w1.i32')
+    y.tofile(d + '/ywin.f64')
+    gy.tofile(d + '/gwin.f64')
+    exe = d + '/abi_windows'
+    lib_dir = os.path.dirname(_lib.LIB_PATH)
+    root = helpers.ROOT
+    subprocess.check_call(['gcc', '-std=c99', '-pedantic', '-Wall', '-Wextra', '-Werror', '-I', os.path.join(root, 'include'),
+                           os.path.join(root, 'tests', 'c', 'abi_windows.c'), '-o', exe, '-L', lib_dir, '-ltsf_amd',
+                           '-Wl,-rpath,' + lib_dir])
+    subprocess.check_call([exe, str(c.N), str(c.H), str(K), d])
+    got = np.fromfile(d + '/out.f64')
+    lv = [0.1, 0.5, 0.9]
+    s = fc.predict_windows(*_args(c), w, lv, y_obs=y_rows, extra_future=c.extra, series_key=keys, uncertainty_samples=50,
+                           seed=5)
+    with fc.Rollup(c.fut, 1, uncertainty_samples=50, seed=5) as roll:
+        roll.add(c.spec, c.theta, c.y_scale, c.grid, np.zeros(c.N, np.int64), keys, extra_future=c.extra)
+        g = roll.windows(w, lv, y_obs=g_rows)
+
+    def flat(r):
+        return [r.yhat.ravel(), r.total.ravel(), r.pit.ravel(), r.crps.ravel(), r.q.ravel(), r.pinball.ravel(), r.mean_crps,
+                r.mean_pinball.ravel(), r.coverage.ravel(), r.n_obs.astype(np.float64)]
+    want = np.concatenate(flat(s) + flat(g))
+    assert got.shape == want.shape and sr.same(got, want)
+    assert s.n_obs.tolist() == [K - 1, K] and g.n_obs.tolist() == [K]
+
+
+# ---- 10. the scorer --------------------------------------------------------------------------------------------------------
+
+def test_scorer_period_totals(env, tmp_path, monkeypatch):
+    """forecast.period_totals: the frame's rows are fc.predict_windows on the same models, calendar, keys and seed, bit
+    for bit; ProphetScorer.score writes it under io.period_forecasts, and the ordinary forecast output is byte for byte
+    the one of a run without the key"""
+    fc, _lib = env
+    from time_series_spark_amd import panel as pk, synth
+    from time_series_spark_amd.jobs import prophet_modeler as pm, prophet_scorer as ps
+    H, S = 24, 300
+    ds, y = synth.make_panel(6, 800, 'linear', seed=4)
+    # series_id 8 and 9 with three dim_ids each; three series of 400 daily rows, three of 800; dim 1 ends three days early
+    frames = [pd.DataFrame({'series_id': 8 + n // 3, 'dim_id': n, 'ds': pd.to_datetime(ds[-T:]), 'y': y[n, -T:]})
+              for n, T in enumerate([400, 800, 400, 800, 400, 800])]
+    frames[1] = frames[1].iloc[:-3]
+    mcfg = {'model': {'floor': 0, 'cap_multiplier': 1.1, 'prophet': {'growth': 'linear', 'seasonality_mode': 'additive'}}}
+    models = pm.model_panel(mcfg)(pd.concat(frames, ignore_index=True))
+    buckets = list(pk.load_models(models['model'].tolist()))
+    assert len(buckets) == 2                                   # the auto-seasonalities differ with the span
+    lv = [0.1, 0.5, 0.9]
+    base = {'periods': H, 'frequency': 'D', 'uncertainty_samples': S, 'seed': 1}
+    sids, dids = models['series_id'].to_numpy(), models['dim_id'].to_numpy()
+    names = ['yhat_q10', 'yhat_q50', 'yhat_q90']
+
+    def expect(n, windows_of):
+        """model row n by fc.predict_windows on it alone"""
+        spec_dict, idx, rec = [b for b in buckets if n in b[1]][0]
+        j = list(idx).index(n)
+        spec = fc.ModelSpec.from_dict(spec_dict)
+        theta = np.zeros((1, spec.theta_stride))
+        theta[:, :rec['theta'].shape[1]] = rec['theta'][j:j + 1]
+        fut = pk.future_dates(rec['last_ds_ns'][j:j + 1], H, 'D')[0]
+        grid = pk.grid_from_records(rec)
+        key = (sids[n:n + 1].astype(np.int64) << 32) ^ (dids[n:n + 1].astype(np.int64) & 0xffffffff)
+        return fc.predict_windows(spec, theta, rec['y_scale'][j:j + 1], grid if len(grid) == 1 else grid[j:j + 1], fut,
+                                  windows_of(fut), lv, floor=models['floor'].to_numpy(np.float64)[n:n + 1],
+                                  cap=models['cap'].to_numpy(np.float64)[n:n + 1], series_key=key, uncertainty_samples=S,
+                                  seed=1).frame(0)
+
+    for pt, windows_of in (({'freq': 'W', 'quantiles': lv}, lambda fut: fc.period_windows(fut, 'W')),
+                           ({'rows': 7, 'quantiles': lv}, lambda fut: fc.row_windows(H, 7))):
+        cfg = {'forecast': dict(base, period_totals=pt)}
+        got = ps.period_panel(cfg)(models)
+        assert list(got.columns) == ['series_id', 'dim_id'] + ps.period_columns(lv)
+        assert got['series_id'].dtype == np.int32 and got['dim_id'].dtype == np.int32
+        assert got['period_start'].dtype == np.dtype('datetime64[ns]') and got['yhat'].dtype == np.float64
+        at = 0
+        for n in range(len(models)):                            # the model frame's order, every model's own periods
+            f = expect(n, windows_of)
+            rows = got.iloc[at:at + len(f)]
+            at += len(f)
+            assert (rows['series_id'] == sids[n]).all() and (rows['dim_id'] == dids[n]).all()
+            assert np.array_equal(rows['period_start'].to_numpy(), f['period_start'].to_numpy())
+            assert np.array_equal(rows['period_end'].to_numpy(), f['period_end'].to_numpy())
+            assert rows['n_rows'].tolist() == f['n_rows'].tolist() and rows['n_rows'].sum() == H
+            for k in ['yhat'] + names:
+                assert sr.same(rows[k].to_numpy(), f[k].to_numpy()), (n, k)
+            assert (np.diff(rows[names].to_numpy(), axis=1) >= 0).all()
+        assert at == len(got)
+    # dim 1's calendar starts three days before the others': its weeks are cut elsewhere
+    assert got[got['dim_id'] == 1]['period_start'].iloc[0] != got[got['dim_id'] == 0]['period_start'].iloc[0]
+
+    # ProphetScorer.score, with and without the key (the time stamp of the run pinned: it is a column of the forecasts)
+    class Fixed(real_datetime):
+        @classmethod
+        def now(cls, tz=None):
+            return real_datetime(2024, 5, 6, 7, 8, 9, tzinfo=tz)
+    monkeypatch.setattr(ps, 'datetime', Fixed)
+    mdir = str(tmp_path / 'models')
+    pm.ProphetModeler({'io': {'models': mdir}}).persist_models(models)
+    cfg = {'forecast': dict(base, period_totals={'freq': 'W', 'quantiles': lv})}
+    want = ps.period_panel(cfg)(models)
+    f0, f1, pdir = (str(tmp_path / k) for k in ('forecasts0', 'forecasts1', 'periods'))
+    ps.ProphetScorer.score(None, {'forecast': dict(base), 'io': {'models': mdir, 'forecasts': f0, 'period_forecasts': pdir}})
+    assert not os.path.exists(pdir)
+    ps.ProphetScorer.score(None, dict(cfg, io={'models': mdir, 'forecasts': f1, 'period_forecasts': pdir}))
+    assert sorted(os.listdir(f0)) == sorted(os.listdir(f1)) and os.listdir(f0)
+    for part in os.listdir(f0):
+        assert open(os.path.join(f0, part), 'rb').read() == open(os.path.join(f1, part), 'rb').read(), part
+    back = pd.read_csv(os.path.join(pdir, 'part-00000.csv'), float_precision='round_trip')
+    assert list(back.columns) == list(want.columns) and len(back) == len(want)
+    assert sr.same(back[['yhat'] + names].to_numpy(np.float64), want[['yhat'] + names].to_numpy(np.float64))
+    assert back['period_start'].iloc[0].endswith('Z') and back['n_rows'].tolist() == want['n_rows'].tolist()
+    assert np.array_equal(pd.to_datetime(back['period_end']).dt.tz_localize(None).to_numpy().astype('datetime64[ns]'),
+                          want['period_end'].to_numpy())
+    with pytest.raises(ValueError):
+        ps.period_panel({'forecast': dict(base, period_totals={'freq': 'W', 'quantiles': [0.1, 1.2]})})(models)

@@ -19,6 +19,7 @@ MAX_K = 64
 MAX_P = 128
 MAX_COMP = 128
 MAX_QUANT = 64
+MAX_WINDOWS = 4096
 
 GROWTH_LINEAR, GROWTH_LOGISTIC = 0, 1
 MODE_ADDITIVE, MODE_MULTIPLICATIVE = 0, 1
@@ -116,6 +117,13 @@ class TsfRollupOut(ctypes.Structure):
                 ('samples', ctypes.c_void_p)]
 
 
+class TsfWindowOut(ctypes.Structure):
+    """tsf_window_out (include/tsf.h)."""
+    _fields_ = [('yhat', ctypes.c_void_p), ('total', ctypes.c_void_p), ('q', ctypes.c_void_p), ('pit', ctypes.c_void_p),
+                ('crps', ctypes.c_void_p), ('pinball', ctypes.c_void_p), ('n_obs', ctypes.c_void_p),
+                ('mean_crps', ctypes.c_void_p), ('mean_pinball', ctypes.c_void_p), ('coverage', ctypes.c_void_p)]
+
+
 class TsfReconcileOut(ctypes.Structure):
     """tsf_reconcile_out (include/tsf.h)."""
     _fields_ = [('yhat', ctypes.c_void_p), ('q', ctypes.c_void_p), ('cum_q', ctypes.c_void_p), ('samples', ctypes.c_void_p)]
@@ -188,6 +196,7 @@ EXPORTS = ['tsf_create', 'tsf_destroy', 'tsf_last_error', 'tsf_device_count', 't
            'tsf_predict_quantiles', 'tsf_predict_quantiles_dev',
            'tsf_score_out_size', 'tsf_score_actuals', 'tsf_score_actuals_dev',
            'tsf_rollup_create', 'tsf_rollup_add', 'tsf_rollup_quantiles', 'tsf_rollup_free',
+           'tsf_window_out_size', 'tsf_predict_windows', 'tsf_predict_windows_dev', 'tsf_rollup_windows',
            'tsf_reconcile_shares', 'tsf_reconcile_out_size', 'tsf_rollup_set_totals', 'tsf_rollup_reconcile', 'tsf_rollup_reconciled_totals',
            'tsf_eval', 'tsf_eval_quadratic', 'tsf_design', 'tsf_selftest_math',
            'tsf_set_option', 'tsf_get_option', 'tsf_set_cost_hints', 'tsf_set_profiling', 'tsf_profile_read', 'tsf_last_fit_kernel_ms', 'tsf_last_fit_route',
@@ -286,6 +295,10 @@ def load():
     L.tsf_rollup_quantiles.argtypes = [vp, i32, vp, ctypes.POINTER(TsfRollupOut)]
     L.tsf_rollup_free.argtypes = [vp]
     L.tsf_rollup_free.restype = None
+    L.tsf_predict_windows.argtypes = [vp, psp, i64, i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, i32, u64, i32, vp, vp, vp,
+                                      i32, vp, ctypes.POINTER(TsfWindowOut)]
+    L.tsf_predict_windows_dev.argtypes = L.tsf_predict_windows.argtypes + [vp]
+    L.tsf_rollup_windows.argtypes = [vp, i32, vp, vp, vp, i32, vp, ctypes.POINTER(TsfWindowOut)]
     L.tsf_reconcile_shares.argtypes = [i64, vp, vp, i64, vp, vp, vp]
     L.tsf_rollup_set_totals.argtypes = L.tsf_rollup_add.argtypes
     L.tsf_rollup_reconcile.argtypes = L.tsf_rollup_add.argtypes + [vp, i32, vp, ctypes.POINTER(TsfReconcileOut)]
@@ -368,6 +381,8 @@ def load():
         raise TsfError('tsf_grid_info layout mismatch between _lib.py and libtsf_amd.so')
     if L.tsf_score_out_size() != ctypes.sizeof(TsfScoreOut):
         raise TsfError('tsf_score_out layout mismatch between _lib.py and libtsf_amd.so')
+    if L.tsf_window_out_size() != ctypes.sizeof(TsfWindowOut):
+        raise TsfError('tsf_window_out layout mismatch between _lib.py and libtsf_amd.so')
     if L.tsf_reconcile_out_size() != ctypes.sizeof(TsfReconcileOut):
         raise TsfError('tsf_reconcile_out layout mismatch between _lib.py and libtsf_amd.so')
     if (L.tsf_screen_args_size() != ctypes.sizeof(TsfScreenArgs) or L.tsf_screen_out_size() != ctypes.sizeof(TsfScreenOut)

@@ -23,6 +23,7 @@
 #include "tsf_aux_kernels.h"
 #include "tsf_interval_kernels.h"
 #include "tsf_score_kernels.h"
+#include "tsf_window_kernels.h"
 #include "tsf_rollup_kernels.h"
 #include "tsf_reconcile_kernels.h"
 #include "tsf_component_kernels.h"
@@ -1828,12 +1829,9 @@ extern "C" int tsf_predict_components(tsf_ctx *ctx, const tsf_spec *spec, int64_
 
 // ---- forecast quantiles, cumulative quantiles, predictive samples ----------------------------------------
 
-// What both quantile entries check before anything is launched: the sample count, the levels (host data in both, like
-// the spec) and that the call asks for something.
-static int check_quantile_args(tsf_ctx *ctx, int32_t n_samples, int32_t n_q, const double *quantiles,
-                               const tsf_quantile_out *out)
+// The sample count and the levels of the quantile, score and window entries (host data in every variant, like the spec).
+static int check_samples_and_levels(tsf_ctx *ctx, int32_t n_samples, int32_t n_q, const double *quantiles)
 {
-    if (!out || !out->yhat) return fail(ctx, "NULL output (tsf_quantile_out and its yhat are required)");
     if (n_samples < 2 || n_samples > 4096) return fail(ctx, "n_samples must be in [2, 4096]");
     if (n_q < 0 || n_q > TSF_MAX_QUANT) return fail(ctx, "n_q must be in [0, TSF_MAX_QUANT]");
     if (n_q > 0 && !quantiles) return fail(ctx, "NULL quantiles");
@@ -1843,6 +1841,16 @@ static int check_quantile_args(tsf_ctx *ctx, int32_t n_samples, int32_t n_q, con
             snprintf(msg, sizeof(msg), "quantiles[%d] = %g: a level must be finite and in [0, 1]", (int)i, quantiles[i]);
             return fail(ctx, msg);
         }
+    return 0;
+}
+
+// What both quantile entries check before anything is launched: the sample count, the levels (host data in both, like
+// the spec) and that the call asks for something.
+static int check_quantile_args(tsf_ctx *ctx, int32_t n_samples, int32_t n_q, const double *quantiles,
+                               const tsf_quantile_out *out)
+{
+    if (!out || !out->yhat) return fail(ctx, "NULL output (tsf_quantile_out and its yhat are required)");
+    if (int rc = check_samples_and_levels(ctx, n_samples, n_q, quantiles)) return rc;
     const bool want_q = out->q || out->cum_q || out->trend_q, want_s = out->samples || out->trend_samples;
     if (!want_q && !want_s) return fail(ctx, "nothing requested: q, cum_q, trend_q, samples and trend_samples are all NULL");
     if (n_q == 0 && want_q) return fail(ctx, "n_q = 0 with a quantile output requested");
@@ -1952,15 +1960,7 @@ static int check_score_args(tsf_ctx *ctx, int32_t n_samples, int32_t n_q, const 
 {
     if (!out || !out->yhat) return fail(ctx, "NULL output (tsf_score_out and its yhat are required)");
     if (!y_obs) return fail(ctx, "NULL y_obs");
-    if (n_samples < 2 || n_samples > 4096) return fail(ctx, "n_samples must be in [2, 4096]");
-    if (n_q < 0 || n_q > TSF_MAX_QUANT) return fail(ctx, "n_q must be in [0, TSF_MAX_QUANT]");
-    if (n_q > 0 && !quantiles) return fail(ctx, "NULL quantiles");
-    for (int32_t i = 0; i < n_q; ++i)
-        if (!(quantiles[i] >= 0.0 && quantiles[i] <= 1.0)) {       // (NaN fails both comparisons)
-            char msg[120];
-            snprintf(msg, sizeof(msg), "quantiles[%d] = %g: a level must be finite and in [0, 1]", (int)i, quantiles[i]);
-            return fail(ctx, msg);
-        }
+    if (int rc = check_samples_and_levels(ctx, n_samples, n_q, quantiles)) return rc;
     const bool want_q = out->q || out->pinball || out->mean_pinball || out->coverage;
     if (!want_q && !out->pit && !out->crps && !out->n_obs && !out->mean_crps)
         return fail(ctx, "nothing requested: every output of tsf_score_out beyond yhat is NULL");
@@ -2398,6 +2398,276 @@ extern "C" int tsf_rollup_quantiles(tsf_rollup *r, int32_t n_q, const double *qu
     if (out->cum_q) HIP_TRY(ctx, hipMemcpy(out->cum_q, d_cq.p, nqh, hipMemcpyDeviceToHost));
     if (out->samples) HIP_TRY(ctx, hipMemcpy(out->samples, r->acc, 8 * gh * S, hipMemcpyDeviceToHost));
     return 0;
+}
+
+// ---- totals over row windows: quantiles and scores of calendar-period totals ---------------------------------
+
+extern "C" int tsf_window_out_size(void) { return (int)sizeof(tsf_window_out); }
+
+// The windows of a call (host data, like the levels) and the observed window totals (device memory behind the entries).
+struct WindowCall {
+    int32_t K;
+    const int32_t *win_start, *win_end;
+    const double *y_win;
+};
+
+// the outputs that are read from the sorted window sums: they need the draws (of a roll-up: the accumulators)
+static bool window_wants_draws(const tsf_window_out &o)
+{
+    return o.q || o.pit || o.crps || o.pinball || o.mean_crps || o.mean_pinball || o.coverage;
+}
+
+// What the three window entries check before anything is copied or launched: tsf_predict_quantiles' checks of the sample
+// count and the levels, the windows against H (they index the sample buffer), and what the outputs need.
+static int check_window_args(tsf_ctx *ctx, int32_t H, int32_t n_samples, int32_t n_q, const double *quantiles,
+                             const WindowCall &w, const tsf_window_out *out)
+{
+    if (!out) return fail(ctx, "NULL output (tsf_window_out is required)");
+    if (int rc = check_samples_and_levels(ctx, n_samples, n_q, quantiles)) return rc;
+    if (w.K < 1 || w.K > TSF_MAX_WINDOWS) return fail(ctx, "K must be in [1, TSF_MAX_WINDOWS]");
+    if (!w.win_start || !w.win_end) return fail(ctx, "NULL win_start or win_end");
+    for (int32_t k = 0; k < w.K; ++k)
+        if (w.win_start[k] < 0 || w.win_start[k] >= w.win_end[k] || w.win_end[k] > H) {
+            char msg[160];
+            snprintf(msg, sizeof(msg), "window %d = [%d, %d): a window needs 0 <= win_start < win_end <= H = %d", (int)k,
+                     (int)w.win_start[k], (int)w.win_end[k], (int)H);
+            return fail(ctx, msg);
+        }
+    const bool want_q = out->q || out->pinball || out->mean_pinball || out->coverage;
+    const bool want_score = out->pit || out->crps || out->pinball || out->n_obs || out->mean_crps || out->mean_pinball ||
+                            out->coverage;
+    if (!out->yhat && !out->total && !want_q && !want_score)
+        return fail(ctx, "nothing requested: every output of tsf_window_out is NULL");
+    if (n_q == 0 && want_q) return fail(ctx, "n_q = 0 with q, pinball, mean_pinball or coverage requested");
+    if (want_score && !w.y_win) return fail(ctx, "NULL y_win with a score output requested");
+    return 0;
+}
+
+// the host-pointer entries: an observed total is finite or NaN
+static int check_y_win(tsf_ctx *ctx, const double *y_win, int64_t N, int32_t K)
+{
+    const size_t nk = (size_t)N * K;
+    for (size_t i = 0; y_win && i < nk; ++i)
+        if (std::isinf(y_win[i])) {
+            char msg[120];
+            snprintf(msg, sizeof(msg), "y_win[%lld][%d] is infinite: an observed total must be finite (NaN = not observed)",
+                     (long long)(i / K), (int)(i % K));
+            return fail(ctx, msg);
+        }
+    return 0;
+}
+
+// window_score_kernel's arguments for the whole call, with what lies in the context's sample scratch behind its first
+// `base` bytes (the chunk draw_chunks carves from it: the block is sized for both here, so draw_chunks never
+// reallocates under them): the per-window arrays the aggregates read where the caller did not ask for them, yhat where
+// it is needed and not asked for, and the windows themselves (copied from the caller's host arrays before this
+// returns, as forecast_prologue's copy of the spec is).  Every pointer of `o` and w.y_win are device pointers.
+static int window_prepare(tsf_ctx *ctx, size_t base, int64_t N, int32_t H, int32_t n_samples, const QuantileCall &c,
+                          const WindowCall &w, const tsf_window_out &o, bool need_yhat, hipStream_t st, WindowArgs *a,
+                          double **yhat)
+{
+    const size_t nk = (size_t)N * w.K, nqk = nk * (size_t)c.n_q;
+    const size_t extra = (o.mean_crps && !o.crps ? nk : 0) + (o.mean_pinball && !o.pinball ? nqk : 0) +
+                         (o.coverage && !o.q ? nqk : 0) + (need_yhat && !o.yhat ? (size_t)N * H : 0);
+    if (int rc = ensure_iv_ws(ctx, base + 8 * extra + 8 * (size_t)w.K)) return rc;
+    double *d_next = (double *)((char *)ctx->iv_ws + base);
+    memset(a, 0, sizeof(*a));
+    a->y = w.y_win; a->pit = o.pit; a->crps = o.crps; a->q = o.q; a->pinball = o.pinball;
+    a->H = H; a->K = w.K; a->NS = n_samples; a->n_q = c.n_q;
+    for (int32_t i = 0; i < c.n_q; ++i) a->level[i] = c.quantiles[i];
+    if (o.mean_crps && !o.crps) { a->crps = d_next; d_next += nk; }
+    if (o.mean_pinball && !o.pinball) { a->pinball = d_next; d_next += nqk; }
+    if (o.coverage && !o.q) { a->q = d_next; d_next += nqk; }
+    *yhat = o.yhat;
+    if (need_yhat && !o.yhat) { *yhat = d_next; d_next += (size_t)N * H; }
+    int32_t *d_w = (int32_t *)d_next;
+    HIP_TRY(ctx, hipMemcpyAsync(d_w, w.win_start, 4 * (size_t)w.K, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_w + w.K, w.win_end, 4 * (size_t)w.K, hipMemcpyHostToDevice, st));
+    a->w0 = d_w; a->w1 = d_w + w.K;
+    return 0;
+}
+
+// window_score_kernel over the n series (groups) whose samples start at src, the first of them series n0 of the call;
+// a range of series per launch (the grid is series * K)
+static int launch_window_scores(tsf_ctx *ctx, WindowArgs a, const double *src, int64_t n0, int64_t n, hipStream_t st)
+{
+    const int NSP = sort_width(a.NS);
+    const int64_t range = std::max<int64_t>(1, ((int64_t)1 << 30) / a.K);
+    for (int64_t i0 = 0; i0 < n; i0 += range) {
+        const int64_t nc = std::min(range, n - i0);
+        a.src = src + (size_t)i0 * a.H * a.NS; a.n0 = n0 + i0;
+        hipLaunchKernelGGL(window_score_kernel, dim3((unsigned)(nc * a.K)), dim3(256), sizeof(double) * NSP, st, a, NSP);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return 0;
+}
+
+// what follows the window scores: the point totals from yhat, the per-series means by score_series_kernel with the
+// windows in the place of the rows
+static int window_finish(tsf_ctx *ctx, const WindowArgs &a, const double *yhat, int64_t N, const tsf_window_out &o,
+                         hipStream_t st)
+{
+    if (o.total) {
+        const int64_t threads = N * a.K;
+        hipLaunchKernelGGL(window_total_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, yhat, a.w0, a.w1,
+                           o.total, N, a.H, a.K);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    if (o.n_obs || o.mean_crps || o.mean_pinball || o.coverage) {
+        ScoreSeriesArgs s;
+        memset(&s, 0, sizeof(s));
+        s.y = a.y; s.crps = a.crps; s.q = a.q; s.pinball = a.pinball;
+        s.n_obs = o.n_obs; s.mean_crps = o.mean_crps; s.mean_pinball = o.mean_pinball; s.coverage = o.coverage;
+        s.N = N; s.H = a.K; s.n_q = a.n_q;
+        const int64_t threads = N * (1 + a.n_q);
+        hipLaunchKernelGGL(score_series_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, s);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return 0;
+}
+
+// The work of both tsf_predict_windows entries on device-resident inputs.
+static int predict_windows_run(tsf_ctx *ctx, const tsf_spec *spec, const ForecastIn &f, const QuantileCall &c,
+                               const WindowCall &w, const tsf_window_out &o, hipStream_t st)
+{
+    const int64_t N = f.N;
+    const int32_t H = f.H, n_samples = c.n_samples;
+    const bool draws = window_wants_draws(o), need_yhat = draws || o.yhat || o.total;
+    const size_t base = draws ? draw_scratch_bytes(draw_chunk_series(N, H, n_samples, 1), H, n_samples, 1) : 0;
+    WindowArgs a;
+    double *yhat = nullptr;
+    if (int rc = window_prepare(ctx, base, N, H, n_samples, c, w, o, need_yhat, st, &a, &yhat)) return rc;
+    if (draws) {
+        auto after = [&](int64_t n0, int64_t nc, const DrawBufs &b) -> int {
+            return launch_window_scores(ctx, a, b.samp, n0, nc, st);
+        };
+        const DrawSpec d = {n_samples, c.seed, false, false, yhat, nullptr};
+        if (int rc = draw_chunks(ctx, spec, f, d, st, after)) return rc;
+    } else if (need_yhat) {
+        if (int rc = tsf_predict_dev(ctx, spec, N, H, f.theta, f.y_scale, f.grid, f.n_grids, f.ds_future, f.shared_future,
+                                     f.floor_, f.cap, f.extra_future, yhat, nullptr, st))
+            return rc;
+    }
+    return window_finish(ctx, a, yhat, N, o, st);
+}
+
+extern "C" int tsf_predict_windows_dev(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H, const double *theta,
+                                       const double *y_scale, const tsf_grid_info *grid, int32_t n_grids,
+                                       const int64_t *ds_future, int32_t shared_future, const double *floor_,
+                                       const double *cap, const double *extra_future, const int64_t *series_key,
+                                       int32_t n_samples, uint64_t seed, int32_t K, const int32_t *win_start,
+                                       const int32_t *win_end, const double *y_win, int32_t n_q, const double *quantiles,
+                                       tsf_window_out *out, void *stream)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const ForecastIn f = {N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap, extra_future, series_key};
+    if (int rc = check_forecast_in(ctx, f, spec != nullptr)) return rc;
+    const WindowCall w = {K, win_start, win_end, y_win};
+    if (int rc = check_window_args(ctx, H, n_samples, n_q, quantiles, w, out)) return rc;
+    return predict_windows_run(ctx, spec, f, {n_samples, seed, n_q, quantiles}, w, *out, (hipStream_t)stream);
+}
+
+// The outputs of a host-pointer window entry on the device (pooled buffers that live in the entry's scope) and their
+// way back.  yhat_dev: the entry has yhat on the device already (the roll-up's ysum) and no buffer is taken for it.
+struct WindowDevOut {
+    DevBuf y, yh, tot, q, pit, crps, pb, no, mc, mp, cv;
+    tsf_window_out o;
+    size_t nh, nk, nqk, nq, n4;
+
+    int alloc(tsf_ctx *ctx, const tsf_window_out &h, const double *y_win, int64_t N, int32_t H, int32_t K, int32_t n_q,
+              double *yhat_dev, const double **d_y_win)
+    {
+        nh = 8 * (size_t)N * H; nk = 8 * (size_t)N * K; nqk = nk * (size_t)n_q; nq = 8 * (size_t)N * n_q; n4 = 4 * (size_t)N;
+        memset(&o, 0, sizeof(o));
+        *d_y_win = nullptr;
+        if (y_win) {
+            HIP_TRY(ctx, y.alloc(nk));
+            HIP_TRY(ctx, hipMemcpy(y.p, y_win, nk, hipMemcpyHostToDevice));
+            *d_y_win = y.as<double>();
+        }
+        if (h.yhat) {
+            if (yhat_dev) o.yhat = yhat_dev;
+            else { HIP_TRY(ctx, yh.alloc(nh)); o.yhat = yh.as<double>(); }
+        }
+        if (h.total) { HIP_TRY(ctx, tot.alloc(nk)); o.total = tot.as<double>(); }
+        if (h.q) { HIP_TRY(ctx, q.alloc(nqk)); o.q = q.as<double>(); }
+        if (h.pit) { HIP_TRY(ctx, pit.alloc(nk)); o.pit = pit.as<double>(); }
+        if (h.crps) { HIP_TRY(ctx, crps.alloc(nk)); o.crps = crps.as<double>(); }
+        if (h.pinball) { HIP_TRY(ctx, pb.alloc(nqk)); o.pinball = pb.as<double>(); }
+        if (h.n_obs) { HIP_TRY(ctx, no.alloc(n4)); o.n_obs = no.as<int32_t>(); }
+        if (h.mean_crps) { HIP_TRY(ctx, mc.alloc(8 * (size_t)N)); o.mean_crps = mc.as<double>(); }
+        if (h.mean_pinball) { HIP_TRY(ctx, mp.alloc(nq)); o.mean_pinball = mp.as<double>(); }
+        if (h.coverage) { HIP_TRY(ctx, cv.alloc(nq)); o.coverage = cv.as<double>(); }
+        return 0;
+    }
+
+    int fetch(tsf_ctx *ctx, const tsf_window_out &h, int64_t N)
+    {
+        if (h.yhat) HIP_TRY(ctx, hipMemcpy(h.yhat, o.yhat, nh, hipMemcpyDeviceToHost));
+        if (h.total) HIP_TRY(ctx, hipMemcpy(h.total, o.total, nk, hipMemcpyDeviceToHost));
+        if (h.q) HIP_TRY(ctx, hipMemcpy(h.q, o.q, nqk, hipMemcpyDeviceToHost));
+        if (h.pit) HIP_TRY(ctx, hipMemcpy(h.pit, o.pit, nk, hipMemcpyDeviceToHost));
+        if (h.crps) HIP_TRY(ctx, hipMemcpy(h.crps, o.crps, nk, hipMemcpyDeviceToHost));
+        if (h.pinball) HIP_TRY(ctx, hipMemcpy(h.pinball, o.pinball, nqk, hipMemcpyDeviceToHost));
+        if (h.n_obs) HIP_TRY(ctx, hipMemcpy(h.n_obs, o.n_obs, n4, hipMemcpyDeviceToHost));
+        if (h.mean_crps) HIP_TRY(ctx, hipMemcpy(h.mean_crps, o.mean_crps, 8 * (size_t)N, hipMemcpyDeviceToHost));
+        if (h.mean_pinball) HIP_TRY(ctx, hipMemcpy(h.mean_pinball, o.mean_pinball, nq, hipMemcpyDeviceToHost));
+        if (h.coverage) HIP_TRY(ctx, hipMemcpy(h.coverage, o.coverage, nq, hipMemcpyDeviceToHost));
+        return 0;
+    }
+};
+
+extern "C" int tsf_predict_windows(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H, const double *theta,
+                                   const double *y_scale, const tsf_grid_info *grid, int32_t n_grids,
+                                   const int64_t *ds_future, int32_t shared_future, const double *floor_, const double *cap,
+                                   const double *extra_future, const int64_t *series_key, int32_t n_samples, uint64_t seed,
+                                   int32_t K, const int32_t *win_start, const int32_t *win_end, const double *y_win,
+                                   int32_t n_q, const double *quantiles, tsf_window_out *out)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const ForecastIn h = {N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap, extra_future, series_key};
+    if (int rc = check_forecast_in(ctx, h, spec != nullptr)) return rc;
+    if (int rc = check_grids(ctx, spec, grid, n_grids)) return rc;
+    const WindowCall hw = {K, win_start, win_end, y_win};
+    if (int rc = check_window_args(ctx, H, n_samples, n_q, quantiles, hw, out)) return rc;
+    if (spec->n_extra > 0 && !extra_future) return fail(ctx, "extra_future is NULL");     // (ahead of the scan of y_win)
+    if (int rc = check_y_win(ctx, y_win, N, K)) return rc;
+    ForecastUpload up;
+    if (int rc = up.upload(ctx, spec, h)) return rc;
+    WindowDevOut d;
+    WindowCall w = hw;
+    if (int rc = d.alloc(ctx, *out, y_win, N, H, K, n_q, nullptr, &w.y_win)) return rc;
+    if (int rc = predict_windows_run(ctx, spec, up.dev, {n_samples, seed, n_q, quantiles}, w, d.o, nullptr)) return rc;
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    return d.fetch(ctx, *out, N);
+}
+
+extern "C" int tsf_rollup_windows(tsf_rollup *r, int32_t K, const int32_t *win_start, const int32_t *win_end,
+                                  const double *y_win, int32_t n_q, const double *quantiles, tsf_window_out *out)
+{
+    if (!r) return -1;
+    tsf_ctx *ctx = r->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (r->poisoned) return fail(ctx, ROLLUP_POISONED);
+    const int32_t H = r->H, S = r->S;
+    const int64_t G = r->G;
+    const WindowCall hw = {K, win_start, win_end, y_win};
+    if (int rc = check_window_args(ctx, H, S, n_q, quantiles, hw, out)) return rc;
+    if (int rc = check_y_win(ctx, y_win, G, K)) return rc;
+    // the accumulators are read in place, a group in the place of a series; yhat is the handle's ysum
+    WindowDevOut d;
+    WindowCall w = hw;
+    if (int rc = d.alloc(ctx, *out, y_win, G, H, K, n_q, r->ysum, &w.y_win)) return rc;
+    WindowArgs a;
+    double *yhat = nullptr;
+    if (int rc = window_prepare(ctx, 0, G, H, S, {S, r->seed, n_q, quantiles}, w, d.o, false, nullptr, &a, &yhat)) return rc;
+    if (window_wants_draws(d.o))
+        if (int rc = launch_window_scores(ctx, a, r->acc, 0, G, nullptr)) return rc;
+    if (int rc = window_finish(ctx, a, r->ysum, G, d.o, nullptr)) return rc;
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    return d.fetch(ctx, *out, G);
 }
 
 // ---- reconciliation: member forecasts and fitted totals made coherent ---------------------------------------

@@ -149,13 +149,12 @@ __global__ __launch_bounds__(256) void interval_sample_kernel(IntervalArgs a)
     }
 }
 
-// The sort of the three per-row kernels (here and tsf_score_kernels.h): the NS values of one row into LDS, padded to
-// NSP (a power of two) with +inf, then a bitonic network of compare-exchanges, ascending; ends behind a barrier.
-// Exchanges move values and round nothing, so the sorted row is a function of the row's multiset alone.
-__device__ __forceinline__ void iv_load_sort(double *v, const double *src, int NS, int NSP)
+// The sort of the per-row kernels (here, tsf_score_kernels.h and tsf_window_kernels.h): NSP values in LDS (a power of
+// two; the padding behind the real ones is +inf) through a bitonic network of compare-exchanges, ascending; it starts
+// from values every thread can see (a barrier behind the load) and ends behind a barrier.  Exchanges move values and
+// round nothing, so the sorted row is a function of the row's multiset alone.
+__device__ __forceinline__ void iv_sort_network(double *v, int NSP)
 {
-    for (int i = threadIdx.x; i < NSP; i += blockDim.x) v[i] = (i < NS) ? src[i] : __builtin_huge_val();
-    __syncthreads();
     for (int k = 2; k <= NSP; k <<= 1)
         for (int j = k >> 1; j > 0; j >>= 1) {
             for (int i = threadIdx.x; i < NSP; i += blockDim.x) {
@@ -168,6 +167,14 @@ __device__ __forceinline__ void iv_load_sort(double *v, const double *src, int N
             }
             __syncthreads();
         }
+}
+
+// The NS values of one row into LDS, padded to NSP with +inf, then the network.
+__device__ __forceinline__ void iv_load_sort(double *v, const double *src, int NS, int NSP)
+{
+    for (int i = threadIdx.x; i < NSP; i += blockDim.x) v[i] = (i < NS) ? src[i] : __builtin_huge_val();
+    __syncthreads();
+    iv_sort_network(v, NSP);
 }
 
 // NSP: NS rounded up to a power of two (<= 4096), the padding sorts to the end as +inf

@@ -24,39 +24,35 @@ struct ScoreArgs {
     double level[TSF_MAX_QUANT];
 };
 
-// NSP: NS rounded up to a power of two (<= 4096); LDS: NSP doubles (<= 32 KB, five workgroups of four waves per CU),
-// as quantile_kernel.  y is one value per workgroup, so every branch on it is uniform and every barrier is reached by
-// all 256 threads or by none.
-__global__ __launch_bounds__(256) void score_kernel(ScoreArgs a, int NSP)
+// What score_kernel (and window_score_kernel, tsf_window_kernels.h) reads from one sorted row v[0 .. NS) in LDS (NSP
+// doubles, the padding +inf) and the row's observed value y (NaN: not observed): the levels by quantile_kernel's
+// expression and their pinball losses into q[i * stride] / pinball[i * stride], the PIT from two binary searches, the
+// sample CRPS regrouped to non-negative terms and summed by a fixed halving tree in the same LDS (the sorted row is
+// overwritten).  A null output is not wanted.  y is one value per workgroup, so every branch on it is uniform and every
+// barrier is reached by all threads of the workgroup or by none.
+__device__ __forceinline__ void score_sorted_row(double *v, int NS, int NSP, double y, const double *level, int n_q,
+                                                 double *q, double *pinball, size_t stride, double *pit_out,
+                                                 double *crps_out)
 {
-    extern __shared__ __align__(16) unsigned char iv_smem[];
-    double *v = reinterpret_cast<double *>(iv_smem);
-    const int64_t nl = blockIdx.x / a.H;
-    const int h = (int)(blockIdx.x - nl * a.H);
-    const int NS = a.NS;
-    iv_load_sort(v, a.src + ((size_t)nl * a.H + h) * NS, NS, NSP);
-    const size_t row = (size_t)(a.n0 + nl) * a.H + h;
-    const double y = a.y[row];
     const bool observed = y == y;
     const double NaN = __builtin_nan("");
-    if (a.q || a.pinball)
-        for (int q = threadIdx.x; q < a.n_q; q += blockDim.x) {
+    if (q || pinball)
+        for (int i = threadIdx.x; i < n_q; i += blockDim.x) {
             // quantile_kernel's expression
-            const double pos = a.level[q] * (double)(NS - 1);
+            const double pos = level[i] * (double)(NS - 1);
             int lo = (int)__builtin_floor(pos);
             if (lo > NS - 1) lo = NS - 1;
             const int hi = lo + 1 < NS ? lo + 1 : NS - 1;
             const double val = v[lo] + (v[hi] - v[lo]) * (pos - (double)lo);
-            const size_t at = ((size_t)(a.n0 + nl) * a.n_q + q) * a.H + h;
-            if (a.q) a.q[at] = val;
-            if (a.pinball) {
+            if (q) q[(size_t)i * stride] = val;
+            if (pinball) {
                 const double e = y - val;
-                a.pinball[at] = !observed ? NaN : (e >= 0.0 ? a.level[q] * e : (a.level[q] - 1.0) * e);
+                pinball[(size_t)i * stride] = !observed ? NaN : (e >= 0.0 ? level[i] * e : (level[i] - 1.0) * e);
             }
         }
     // the PIT from exact counts over the NS real entries: lt = #{v < y}, le = #{v <= y} (the last thread: another wave
     // than the one that reads the levels)
-    if (a.pit && threadIdx.x == blockDim.x - 1) {
+    if (pit_out && threadIdx.x == blockDim.x - 1) {
         double pit = NaN;
         if (observed) {
             int lo = 0, hi = NS;
@@ -67,11 +63,11 @@ __global__ __launch_bounds__(256) void score_kernel(ScoreArgs a, int NSP)
             const int eq = lo - lt;
             pit = ((double)lt + 0.5 * (double)eq) / (double)NS;
         }
-        a.pit[row] = pit;
+        *pit_out = pit;
     }
-    if (!a.crps) return;
+    if (!crps_out) return;
     if (!observed) {
-        if (threadIdx.x == 0) a.crps[row] = NaN;
+        if (threadIdx.x == 0) *crps_out = NaN;
         return;
     }
     __syncthreads();            // every read of the sorted row is done: it is overwritten in place
@@ -91,7 +87,23 @@ __global__ __launch_bounds__(256) void score_kernel(ScoreArgs a, int NSP)
         for (int i = threadIdx.x; i < s; i += blockDim.x) v[i] = v[i] + v[i + s];
         __syncthreads();
     }
-    if (threadIdx.x == 0) a.crps[row] = v[0] / (double)NS;
+    if (threadIdx.x == 0) *crps_out = v[0] / (double)NS;
+}
+
+// NSP: NS rounded up to a power of two (<= 4096); LDS: NSP doubles (<= 32 KB, five workgroups of four waves per CU),
+// as quantile_kernel.
+__global__ __launch_bounds__(256) void score_kernel(ScoreArgs a, int NSP)
+{
+    extern __shared__ __align__(16) unsigned char iv_smem[];
+    double *v = reinterpret_cast<double *>(iv_smem);
+    const int64_t nl = blockIdx.x / a.H;
+    const int h = (int)(blockIdx.x - nl * a.H);
+    const int NS = a.NS;
+    iv_load_sort(v, a.src + ((size_t)nl * a.H + h) * NS, NS, NSP);
+    const size_t row = (size_t)(a.n0 + nl) * a.H + h;
+    const size_t at = (size_t)(a.n0 + nl) * a.n_q * a.H + h;       // level 0 of the row; level i: + i * H
+    score_sorted_row(v, NS, NSP, a.y[row], a.level, a.n_q, a.q ? a.q + at : nullptr, a.pinball ? a.pinball + at : nullptr,
+                     (size_t)a.H, a.pit ? a.pit + row : nullptr, a.crps ? a.crps + row : nullptr);
 }
 
 struct ScoreSeriesArgs {

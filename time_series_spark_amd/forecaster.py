@@ -827,10 +827,9 @@ class Scores(object):
             return (self.pit < alpha / 2.0) | (self.pit > 1.0 - alpha / 2.0)
 
 
-def _score_actuals_call(spec, theta, y_scale, grid, ds_ns, y_obs, floor, cap, extra_future, series_key,
-                        uncertainty_samples, seed, levels, want, ctx):
-    """One tsf_score_actuals call -> dict of the outputs named in `want` (and yhat).  Every argument-shape error is
-    raised before the library is loaded."""
+def _checked_forecast_inputs(spec, theta, y_scale, grid, ds_ns, floor, cap, extra_future, series_key):
+    """_forecast_inputs with every shape checked here: (theta, N, y_scale, grid, ds, shared, H, floor, cap, ex, key), a
+    ValueError for any argument of the wrong shape.  The library is not touched."""
     theta = np.ascontiguousarray(theta, dtype=np.float64)
     if theta.ndim != 2 or theta.shape[1] != spec.theta_stride:
         raise ValueError('theta must be [N][%d]' % spec.theta_stride)
@@ -846,11 +845,6 @@ def _score_actuals_call(spec, theta, y_scale, grid, ds_ns, y_obs, floor, cap, ex
     H = ds_ns.shape[-1]
     if ds_ns.ndim not in (1, 2) or H < 1 or (not shared and ds_ns.shape != (N, H)):
         raise ValueError('ds must be [H] or [N][H], H >= 1')
-    y_obs = np.ascontiguousarray(y_obs, dtype=np.float64)
-    if y_obs.shape != (N, H):
-        raise ValueError('y_obs must be [N][H] = %r (got %r)' % ((N, H), y_obs.shape))
-    if np.isinf(y_obs).any():
-        raise ValueError('y_obs holds an infinite value: an observed value must be finite (NaN = not observed)')
     floor = _opt_f64(floor, N, 'floor')
     cap = _opt_f64(cap, N, 'cap')
     ex = None
@@ -864,6 +858,20 @@ def _score_actuals_call(spec, theta, y_scale, grid, ds_ns, y_obs, floor, cap, ex
     key = None if series_key is None else np.ascontiguousarray(series_key, dtype=np.int64)
     if key is not None and key.shape != (N,):
         raise ValueError('series_key must be [N]')
+    return theta, N, y_scale, grid, ds_ns, shared, H, floor, cap, ex, key
+
+
+def _score_actuals_call(spec, theta, y_scale, grid, ds_ns, y_obs, floor, cap, extra_future, series_key,
+                        uncertainty_samples, seed, levels, want, ctx):
+    """One tsf_score_actuals call -> dict of the outputs named in `want` (and yhat).  Every argument-shape error is
+    raised before the library is loaded."""
+    theta, N, y_scale, grid, ds_ns, shared, H, floor, cap, ex, key = _checked_forecast_inputs(
+        spec, theta, y_scale, grid, ds_ns, floor, cap, extra_future, series_key)
+    y_obs = np.ascontiguousarray(y_obs, dtype=np.float64)
+    if y_obs.shape != (N, H):
+        raise ValueError('y_obs must be [N][H] = %r (got %r)' % ((N, H), y_obs.shape))
+    if np.isinf(y_obs).any():
+        raise ValueError('y_obs holds an infinite value: an observed value must be finite (NaN = not observed)')
     levels = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
     quantile_columns(levels)            # (ValueError for a bad level, two levels of one name, too many)
     Q, S = len(levels), int(uncertainty_samples)
@@ -903,6 +911,251 @@ def score_actuals(spec, theta, y_scale, grid, ds_ns, y_obs, quantiles=(), floor=
     r = _score_actuals_call(spec, theta, y_scale, grid, ds_ns, y_obs, floor, cap, extra_future, series_key,
                             uncertainty_samples, seed, levels, want, ctx)
     return Scores(r.pop('y'), r.pop('yhat'), levels, **r)
+
+
+# ---- totals over row windows: quantiles and scores of calendar-period totals ------------------------
+# "P10 / P50 / P90 of next week's total, of each calendar month, of every rolling 7-row block" (include/tsf.h "totals
+# over row windows"): every draw's rows summed over each window on the device, the sums sorted, and where the rows'
+# observed values are given, the observed totals scored against them.  The library sees row indices; which rows make a
+# week or a month is decided here, from a calendar (period_windows) or by counting rows (row_windows).
+
+PERIOD_FREQS = ('D', 'W', 'M', 'Q', 'Y')
+
+
+class Windows(object):
+    """K row windows: start, end [K] int32 (row indices, end exclusive, 0 <= start < end) and label_ns [K] int64 or None
+    (the first timestamp of each window where they were formed from a calendar).  Windows may overlap, repeat and come
+    in any order.  n_rows [K]: the rows in each window -- period_windows does not guess which end periods are complete,
+    this is there for the caller to judge."""
+
+    def __init__(self, start, end, label_ns=None):
+        start, end = np.asarray(start), np.asarray(end)
+        if start.ndim != 1 or start.shape != end.shape or start.dtype.kind not in 'iu' or end.dtype.kind not in 'iu':
+            raise ValueError('windows: start and end must be equally long 1-d integer arrays')
+        if not 1 <= len(start) <= _lib.MAX_WINDOWS:
+            raise ValueError('windows: between 1 and %d windows (got %d)' % (_lib.MAX_WINDOWS, len(start)))
+        if (start < 0).any() or (start >= end).any() or end.max() > 2 ** 31 - 1:
+            raise ValueError('windows: every window needs 0 <= start < end')
+        self.start = np.ascontiguousarray(start, dtype=np.int32)
+        self.end = np.ascontiguousarray(end, dtype=np.int32)
+        self.label_ns = None if label_ns is None else np.ascontiguousarray(label_ns, dtype=np.int64)
+        if self.label_ns is not None and self.label_ns.shape != self.start.shape:
+            raise ValueError('windows: label_ns must be as long as start')
+
+    def __len__(self):
+        return len(self.start)
+
+    @property
+    def n_rows(self):
+        return self.end - self.start
+
+    def check(self, H):
+        """ValueError where a window ends behind row H"""
+        if int(self.end.max()) > H:
+            raise ValueError('windows: a window ends at row %d, behind the %d forecast rows' % (int(self.end.max()), H))
+        return self
+
+
+def row_windows(H, width, step=None):
+    """Windows by counting rows of an [H] forecast.  Without step: consecutive blocks of `width` rows, the last one
+    shorter where width does not divide H.  With step: rolling windows of `width` rows starting every `step` rows, the
+    complete ones only."""
+    H, width = int(H), int(width)
+    if H < 1 or width < 1:
+        raise ValueError('row_windows: H and width must be >= 1')
+    if step is None:
+        start = np.arange(0, H, width)
+        return Windows(start, np.minimum(start + width, H))
+    if int(step) < 1 or width > H:
+        raise ValueError('row_windows: step must be >= 1 and width <= H')
+    start = np.arange(0, H - width + 1, int(step))
+    return Windows(start, start + width)
+
+
+def _period_index(ds_ns, freq):
+    """the calendar period of every timestamp as an integer that grows with time: days, Monday-based weeks, months,
+    quarters or years since 1970"""
+    days = np.floor_divide(ds_ns, DAY_NS)
+    if freq == 'D':
+        return days
+    if freq == 'W':
+        return np.floor_divide(days + 3, 7)             # 1970-01-01 was a Thursday: the Monday before is day -3
+    t = ds_ns.view('datetime64[ns]')
+    if freq == 'Y':
+        return t.astype('datetime64[Y]').astype(np.int64)
+    months = t.astype('datetime64[M]').astype(np.int64)
+    return months if freq == 'M' else np.floor_divide(months, 3)
+
+
+def period_windows(ds_ns, freq):
+    """Windows of calendar periods over one shared calendar ds_ns [H] (int64 ns, non-decreasing): freq 'D' | 'W' | 'M' |
+    'Q' | 'Y', weeks starting on Monday as pandas' default to_period('W').  A window is a maximal run of consecutive
+    rows in one period; label_ns is its first timestamp.  The first and the last period may be incomplete: n_rows says
+    how many rows each has.  ValueError for a calendar that is not 1-d (per-series calendars: form row windows per
+    series) or decreases somewhere."""
+    if freq not in PERIOD_FREQS:
+        raise ValueError('freq must be one of %s' % (PERIOD_FREQS,))
+    ds = np.asarray(ds_ns)
+    if ds.dtype.kind == 'M':
+        ds = ds.astype('datetime64[ns]').view(np.int64)
+    ds = np.ascontiguousarray(ds, dtype=np.int64)
+    if ds.ndim != 1 or len(ds) < 1:
+        raise ValueError('period_windows: ds must be one shared calendar [H], H >= 1')
+    if (np.diff(ds) < 0).any():
+        raise ValueError('period_windows: ds must be non-decreasing')
+    p = _period_index(ds, freq)
+    start = np.concatenate([[0], np.flatnonzero(np.diff(p)) + 1])
+    return Windows(start, np.concatenate([start[1:], [len(ds)]]), ds[start])
+
+
+def window_totals(y, windows):
+    """y [N][H] -> [N][K]: the total of every window, added one row at a time in row order from the window's first row
+    (the library's order of adds); NaN where any row of the window is NaN."""
+    y = np.asarray(y, dtype=np.float64)
+    if y.ndim != 2:
+        raise ValueError('window_totals: y must be [N][H]')
+    windows.check(y.shape[1])
+    out = np.empty((y.shape[0], len(windows)))
+    for k, (a, b) in enumerate(zip(windows.start, windows.end)):
+        c = y[:, a].copy()
+        for h in range(a + 1, b):
+            c = c + y[:, h]
+        out[:, k] = c
+    return out
+
+
+WINDOW_FIELDS = ('total', 'q', 'pit', 'crps', 'pinball', 'n_obs', 'mean_crps', 'mean_pinball', 'coverage')
+_WINDOW_SCORE_FIELDS = ('pit', 'crps', 'pinball', 'n_obs', 'mean_crps', 'mean_pinball', 'coverage')
+
+
+class WindowQuantiles(object):
+    """What predict_windows and Rollup.windows return (include/tsf.h tsf_window_out): windows (K of them); ds (the
+    calendar [H] or [N][H]); yhat [N][H]; total [N][K] (the sum of yhat over each window); quantiles [Q] (the levels as
+    given); q [N][Q][K] or None without levels.  With observed values: y [N][K] (the observed totals, NaN = not
+    observed), pit, crps [N][K], pinball [N][Q][K], n_obs [N] (int32), mean_crps [N], mean_pinball, coverage [N][Q];
+    None otherwise.  For a roll-up N is the number of groups."""
+
+    def __init__(self, windows, ds, yhat, quantiles, total=None, q=None, y=None, pit=None, crps=None, pinball=None,
+                 n_obs=None, mean_crps=None, mean_pinball=None, coverage=None):
+        self.windows, self.ds, self.yhat, self.quantiles, self.total, self.q, self.y = windows, ds, yhat, quantiles, total, q, y
+        self.pit, self.crps, self.pinball = pit, crps, pinball
+        self.n_obs, self.mean_crps, self.mean_pinball, self.coverage = n_obs, mean_crps, mean_pinball, coverage
+
+    def frame(self, n):
+        """Series (group) n as a DataFrame, one row per window: period_start, period_end (the timestamps of the window's
+        first and last row), n_rows, yhat (the window's total), y, yhat_q<..> per level, pit, crps, pinball_q<..> per
+        level; the columns of what was not computed are left out (names: quantile_columns)."""
+        import pandas as pd
+        w = self.windows
+        ds = self.ds if self.ds.ndim == 1 else self.ds[n]
+        first = ds[w.start] if w.label_ns is None else w.label_ns
+        cols = {'period_start': first.view('datetime64[ns]'), 'period_end': ds[w.end - 1].view('datetime64[ns]'),
+                'n_rows': w.n_rows, 'yhat': self.total[n]}
+        if self.y is not None:
+            cols['y'] = self.y[n]
+        if self.q is not None:
+            for i, name in enumerate(quantile_columns(self.quantiles)):
+                cols[name] = self.q[n, i]
+        for k in ('pit', 'crps'):
+            if getattr(self, k) is not None:
+                cols[k] = getattr(self, k)[n]
+        if self.pinball is not None:
+            for i, name in enumerate(quantile_columns(self.quantiles, 'pinball_q')):
+                cols[name] = self.pinball[n, i]
+        return pd.DataFrame(cols, columns=list(cols))
+
+
+def _window_call_args(windows, H, N, y_win, levels, want):
+    """What the two window calls check of their own arguments before the library is loaded -> (levels, y_win, res):
+    the outputs named in `want` allocated."""
+    if not isinstance(windows, Windows):
+        raise ValueError('windows must be a Windows (row_windows, period_windows)')
+    windows.check(H)
+    K = len(windows)
+    levels = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
+    quantile_columns(levels)            # (ValueError for a bad level, two levels of one name, too many)
+    Q = len(levels)
+    unknown = set(want) - set(WINDOW_FIELDS + ('yhat',))
+    if unknown:
+        raise ValueError('unknown outputs %s' % sorted(unknown))
+    if not want:
+        raise ValueError('no output wanted')
+    if not Q and set(want) & set(_SCORE_LEVEL_FIELDS):
+        raise ValueError('q, pinball, mean_pinball and coverage need quantile levels')
+    if y_win is None:
+        if set(want) & set(_WINDOW_SCORE_FIELDS):
+            raise ValueError('pit, crps, pinball and the per-series means need observed values')
+    else:
+        y_win = np.ascontiguousarray(y_win, dtype=np.float64)
+        if y_win.shape != (N, K):
+            raise ValueError('y_win must be [N][K] = %r (got %r)' % ((N, K), y_win.shape))
+        if np.isinf(y_win).any():
+            raise ValueError('an observed window total is infinite: it must be finite (NaN = not observed)')
+    shapes = {'yhat': (N, H), 'total': (N, K), 'q': (N, Q, K), 'pit': (N, K), 'crps': (N, K), 'pinball': (N, Q, K),
+              'mean_crps': (N,), 'mean_pinball': (N, Q), 'coverage': (N, Q)}
+    res = {k: np.zeros(N, np.int32) if k == 'n_obs' else np.zeros(shapes[k]) for k in want}
+    return levels, y_win, res
+
+
+def _predict_windows_call(spec, theta, y_scale, grid, ds_ns, windows, y_win, floor, cap, extra_future, series_key,
+                          uncertainty_samples, seed, levels, want, ctx):
+    """One tsf_predict_windows call -> dict of the outputs named in `want` (any of 'yhat' and WINDOW_FIELDS).  y_win
+    [N][K] or None.  Every argument-shape error is raised before the library is loaded."""
+    theta, N, y_scale, grid, ds_ns, shared, H, floor, cap, ex, key = _checked_forecast_inputs(
+        spec, theta, y_scale, grid, ds_ns, floor, cap, extra_future, series_key)
+    levels, y_win, res = _window_call_args(windows, H, N, y_win, levels, want)
+    Q, S = len(levels), int(uncertainty_samples)
+    ctx = ctx or get_context()
+    L = _lib.load()
+    cs = spec.to_c()
+    out = _lib.TsfWindowOut(**{k: v.ctypes.data for k, v in res.items()})
+    rc = L.tsf_predict_windows(ctx.handle, ctypes.byref(cs), N, H, theta.ctypes.data, y_scale.ctypes.data,
+                               grid.ctypes.data, len(grid), ds_ns.ctypes.data, int(shared), _lib._ptr(floor),
+                               _lib._ptr(cap), _lib._ptr(ex), _lib._ptr(key), S, int(seed), len(windows),
+                               windows.start.ctypes.data, windows.end.ctypes.data, _lib._ptr(y_win), Q,
+                               levels.ctypes.data if Q else None, ctypes.byref(out))
+    ctx.check(rc)
+    return res
+
+
+def _window_want(levels, scored):
+    """the outputs of the public window calls: everything the levels and the observed values allow"""
+    want = ['yhat', 'total'] + (['q'] if len(levels) else [])
+    if scored:
+        want += ['pit', 'crps', 'n_obs', 'mean_crps'] + (['pinball', 'mean_pinball', 'coverage'] if len(levels) else [])
+    return want
+
+
+def _observed_totals(y_obs, N, H, windows):
+    """y_obs [N][H] (NaN = not observed) -> the observed window totals [N][K]; None for None"""
+    if y_obs is None:
+        return None
+    y_obs = np.asarray(y_obs, dtype=np.float64)
+    if y_obs.shape != (N, H):
+        raise ValueError('y_obs must be [N][H] = %r (got %r)' % ((N, H), y_obs.shape))
+    if np.isinf(y_obs).any():
+        raise ValueError('y_obs holds an infinite value: an observed value must be finite (NaN = not observed)')
+    return window_totals(y_obs, windows)
+
+
+def predict_windows(spec, theta, y_scale, grid, ds_future_ns, windows, quantiles, y_obs=None, floor=None, cap=None,
+                    extra_future=None, series_key=None, uncertainty_samples=1000, seed=0, ctx=None):
+    """Quantiles of the TOTAL over each of `windows` (row_windows, period_windows) of the simulated futures of every
+    series -> WindowQuantiles (include/tsf.h tsf_predict_windows): yhat [N][H], total [N][K] (the sum of yhat over the
+    window), q [N][Q][K] at the levels `quantiles`.  With y_obs [N][H], the values observed on the forecast rows (NaN =
+    not observed; a window with such a row is not scored), the observed totals are scored against the distribution of the
+    window total: pit, crps, pinball per window, n_obs, mean_crps, mean_pinball, coverage per series.  The draws are
+    predict_quantiles' (same series_key, samples, seed): one-row windows give its q bit for bit, windows from row 0
+    its cum_q."""
+    levels = np.array(quantiles, dtype=np.float64).reshape(-1)
+    theta = np.asarray(theta)
+    ds = np.ascontiguousarray(ds_future_ns, dtype=np.int64)
+    if not isinstance(windows, Windows):
+        raise ValueError('windows must be a Windows (row_windows, period_windows)')
+    y_win = _observed_totals(y_obs, theta.shape[0], ds.shape[-1] if ds.ndim else 0, windows)
+    r = _predict_windows_call(spec, theta, y_scale, grid, ds, windows, y_win, floor, cap, extra_future, series_key,
+                              uncertainty_samples, seed, levels, _window_want(levels, y_win is not None), ctx)
+    return WindowQuantiles(windows, ds, r.pop('yhat'), levels, y=y_win, **r)
 
 
 # ---- group roll-ups: predictive quantiles of sums over series --------------------------------------
@@ -1074,6 +1327,30 @@ class Rollup(object):
     def samples(self):
         """-> [G][H][S]: the summed draws themselves (sample s of a group: the sum of sample s of its members)."""
         return self._read([], ['samples'])['samples']
+
+    def _windows_call(self, windows, y_win, levels, want):
+        """One tsf_rollup_windows call -> dict of the outputs named in `want` (any of 'yhat' and WINDOW_FIELDS); y_win
+        [G][K] or None.  Every argument-shape error is raised before the library is called."""
+        h = self._handle()
+        levels, y_win, res = _window_call_args(windows, self.H, self.G, y_win, levels, want)
+        Q = len(levels)
+        out = _lib.TsfWindowOut(**{k: v.ctypes.data for k, v in res.items()})
+        self._ctx.check(_lib.load().tsf_rollup_windows(h, len(windows), windows.start.ctypes.data, windows.end.ctypes.data,
+                                                       _lib._ptr(y_win), Q, levels.ctypes.data if Q else None,
+                                                       ctypes.byref(out)))
+        return res
+
+    def windows(self, windows, quantiles, y_obs=None):
+        """-> WindowQuantiles of the group totals over each of `windows` (row_windows, period_windows of the roll-up's
+        calendar) from what has been added so far, a group in the place of a series; with y_obs [G][H], the observed
+        group totals per row (NaN = not observed), scored as predict_windows scores a series.  The accumulators are not
+        modified."""
+        levels = np.array(quantiles, dtype=np.float64).reshape(-1)
+        if not isinstance(windows, Windows):
+            raise ValueError('windows must be a Windows (row_windows, period_windows)')
+        y_win = _observed_totals(y_obs, self.G, self.H, windows)
+        r = self._windows_call(windows, y_win, levels, _window_want(levels, y_win is not None))
+        return WindowQuantiles(windows, self.ds_future_ns, r.pop('yhat'), levels, y=y_win, **r)
 
     # -- reconciliation (include/tsf.h "reconciliation") --
 

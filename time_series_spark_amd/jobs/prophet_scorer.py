@@ -298,6 +298,94 @@ def rollup_panel(config):
     return rollup_panel_fn
 
 
+PERIOD_KEYS = ('freq', 'rows', 'quantiles')
+
+
+def period_settings(config):
+    """forecast.period_totals of a scorer configuration -> {'freq', 'rows', 'quantiles'} (one of freq / rows is None),
+    or None without the key.  ValueError for an unknown key, for both or neither of freq and rows, for a freq outside
+    fc.PERIOD_FREQS, rows < 1 and a bad or empty level list.  (`forecast.periods` is the number of rows to forecast.)"""
+    pt = (config.get('forecast') or {}).get('period_totals')
+    if not pt:
+        return None
+    unknown = set(pt) - set(PERIOD_KEYS)
+    if unknown:
+        raise ValueError('forecast.period_totals: unknown keys %s' % sorted(unknown))
+    freq, rows = pt.get('freq'), pt.get('rows')
+    if (freq is None) == (rows is None):
+        raise ValueError('forecast.period_totals: give freq (one of %s) or rows, not both' % (fc.PERIOD_FREQS,))
+    if freq is not None and freq not in fc.PERIOD_FREQS:
+        raise ValueError('forecast.period_totals.freq must be one of %s' % (fc.PERIOD_FREQS,))
+    if rows is not None and int(rows) < 1:
+        raise ValueError('forecast.period_totals.rows must be >= 1')
+    levels = list(pt.get('quantiles') or [])
+    if not fc.quantile_columns(levels):
+        raise ValueError('forecast.period_totals.quantiles: at least one level')
+    return {'freq': freq, 'rows': None if rows is None else int(rows), 'quantiles': levels}
+
+
+def period_columns(levels):
+    """the columns of the period frame behind the model's key columns"""
+    return ['period_start', 'period_end', 'n_rows', 'yhat'] + fc.quantile_columns(levels)
+
+
+def period_panel(config):
+    """forecast.period_totals: {freq: D | W | M | Q | Y, quantiles: [...]} (or rows: n in place of freq: blocks of n
+    forecast rows) -- the predictive distribution of every model's TOTAL over each calendar period of its forecast rows
+    (fc.predict_windows, include/tsf.h "totals over row windows"): the model frame -> one frame of one row per model
+    and period, in the order of the model frame, with columns series_id, dim_id int32, period_start, period_end (the
+    dates of the period's first and last forecast row), n_rows (the first and the last period may be incomplete),
+    yhat float64 (the sum of the period's point forecasts, not truncated), then yhat_q<..> per level.  Same
+    uncertainty_samples, seed and series key (series_id << 32) ^ dim_id as forecast.quantiles.  Models whose forecast
+    calendars differ get the periods of their own calendar: one call per distinct calendar of a spec bucket."""
+
+    def period_panel_fn(pdf):
+        fcfg = config['forecast']
+        st = period_settings(config)
+        levels = st['quantiles']
+        names = fc.quantile_columns(levels)
+        frequency = fcfg['frequency']
+        if frequency == 'W':
+            frequency = pd.offsets.Week()
+        periods = int(fcfg['periods'])
+        sids, dids = pdf['series_id'].to_numpy(), pdf['dim_id'].to_numpy()
+        floors, caps = pdf['floor'].to_numpy(dtype=np.float64), pdf['cap'].to_numpy(dtype=np.float64)
+        blobs = [None if (b is None or isinstance(b, float)) else b for b in pdf['model'].tolist()]
+        parts = []              # (row of the model frame, its K rows as a dict of columns)
+        for spec_dict, idx, rec in pk.load_models(blobs):
+            spec = fc.ModelSpec.from_dict(spec_dict)
+            theta = np.zeros((len(idx), spec.theta_stride))
+            theta[:, :rec['theta'].shape[1]] = rec['theta']
+            grid = pk.grid_from_records(rec)
+            fut = pk.future_dates(rec['last_ds_ns'], periods, frequency)
+            ex = _future_extra(spec, fut)
+            cals, which = np.unique(fut, axis=0, return_inverse=True)
+            which = which.reshape(-1)
+            for c, cal in enumerate(cals):
+                sel = np.flatnonzero(which == c)
+                cal = np.ascontiguousarray(cal)
+                w = fc.period_windows(cal, st['freq']) if st['freq'] else fc.row_windows(periods, st['rows'])
+                r = fc.predict_windows(
+                    spec, theta[sel], rec['y_scale'][sel], grid if len(grid) == 1 else grid[sel], cal, w, levels,
+                    floor=floors[idx][sel], cap=caps[idx][sel],
+                    extra_future=None if ex is None else np.ascontiguousarray(ex[sel[0]]),
+                    series_key=(sids[idx][sel].astype(np.int64) << 32) ^ (dids[idx][sel].astype(np.int64) & 0xffffffff),
+                    uncertainty_samples=int(fcfg.get('uncertainty_samples', 1000)), seed=int(fcfg.get('seed', 0)))
+                for j, n in enumerate(sel):
+                    parts.append((int(idx[n]), r.frame(j)))
+        if not parts:
+            return pd.DataFrame(columns=['series_id', 'dim_id'] + period_columns(levels))
+        parts.sort(key=lambda p: p[0])
+        out = pd.concat([f for _, f in parts], ignore_index=True)
+        rows = np.repeat([i for i, _ in parts], [len(f) for _, f in parts])
+        out.insert(0, 'dim_id', dids[rows].astype('int32'))
+        out.insert(0, 'series_id', sids[rows].astype('int32'))
+        assert list(out.columns) == ['series_id', 'dim_id'] + period_columns(levels) and names
+        return out
+
+    return period_panel_fn
+
+
 def forecast_time_series(config):
     """Forecast using trained time series model (series_id, dim_id) -- prophet_scorer.py:18."""
     batched = forecast_panel(config)
@@ -372,17 +460,26 @@ class ProphetScorer:
             pacsv.write_csv(pa.table(cols), f,
                             write_options=pacsv.WriteOptions(include_header=False, quoting_style='none'))
 
-    def write_rollup(self, rollup_df):
-        """The roll-up frame as one CSV with a header under io.rollup_forecasts (timestamps as write_forecasts writes
-        them; the float64 columns with repr's digits, so they read back bit for bit)."""
+    def _write_frame(self, path, df, time_columns):
+        """A frame as one CSV with a header under `path` (timestamps as write_forecasts writes them; the float64 columns
+        with repr's digits, so they read back bit for bit)."""
         import shutil
-        path = self.config['io']['rollup_forecasts']
         if os.path.isdir(path):
             shutil.rmtree(path)
         os.makedirs(path, exist_ok=True)
-        out = rollup_df.copy()
-        out['ds'] = [t + 'Z' for t in np.datetime_as_string(out['ds'].values.astype('datetime64[ns]'), unit='ms')]
+        out = df.copy()
+        for c in time_columns:
+            out[c] = [t + 'Z' for t in np.datetime_as_string(out[c].values.astype('datetime64[ns]'), unit='ms')]
         out.to_csv(os.path.join(path, 'part-00000.csv'), index=False)
+
+    def write_rollup(self, rollup_df):
+        """The roll-up frame as one CSV with a header under io.rollup_forecasts (_write_frame)."""
+        self._write_frame(self.config['io']['rollup_forecasts'], rollup_df, ['ds'])
+
+    def write_periods(self, period_df):
+        """The period frame (period_panel) as one CSV with a header under io.period_forecasts, written as write_rollup
+        writes."""
+        self._write_frame(self.config['io']['period_forecasts'], period_df, ['period_start', 'period_end'])
 
     def _clear_forecasts(self):
         """-> function that waits until the previous run's files are gone (pipeline.clear_directory)"""
@@ -455,7 +552,8 @@ class ProphetScorer:
         the converted frame -- 900 000 rows of Python date strings for 10 000 series -- is never built.  Returns None, as
         the reference does.
         With forecast.rollup and io.rollup_forecasts both set, the roll-up frame (rollup_panel) is written as CSV there
-        after the forecasts: a second pass over the whole model frame, not pipelined with the first."""
+        after the forecasts: a second pass over the whole model frame, not pipelined with the first.  With
+        forecast.period_totals and io.period_forecasts both set, the period frame (period_panel) is written likewise."""
         from .. import pipeline
         scorer = ProphetScorer(config)
         created = datetime.now(timezone.utc).replace(microsecond=0).isoformat()
@@ -488,3 +586,5 @@ class ProphetScorer:
                                              'ds': np.zeros(0, np.int64), 'yhat': np.zeros(0, np.int32)}, created)
         if (scorer.config.get('forecast') or {}).get('rollup') and scorer.config['io'].get('rollup_forecasts'):
             scorer.write_rollup(rollup_panel(scorer.config)(scorer.read_model_dataframe()))
+        if period_settings(scorer.config) and scorer.config['io'].get('period_forecasts'):
+            scorer.write_periods(period_panel(scorer.config)(scorer.read_model_dataframe()))
