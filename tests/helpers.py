@@ -158,6 +158,37 @@ def make_case(name, N=6, seed=21):
     return spec, ds, y, floor, cap, extra, fut, extra_future
 
 
+# All five L-BFGS tolerances zero: every fit goes on to rounding level, where its line search fails (LSFAIL;
+# tests/test_gpu_quad_termination.py test_line_search_restarts_empty_the_ring) -- one of the three endings after which
+# fbprophet's optimiser rule (include/tsf.h, algorithm AUTO) fits once more with Newton.
+ZERO_TOL = dict(tol_obj=0.0, tol_rel_obj=0.0, tol_grad=0.0, tol_rel_grad=0.0, tol_param=0.0)
+
+
+def retry_statuses(_lib):
+    """the L-BFGS endings pystan raises RuntimeError on: algorithm AUTO retries them with Newton"""
+    return (_lib.ST_LSFAIL, _lib.ST_INIT_NONFINITE, _lib.ST_EVAL_LIMIT)
+
+
+def explicit_algorithm(spec, algorithm):
+    """spec with its `algorithm` replaced (the by-hand side of an AUTO call fits with ALGO_LBFGS / ALGO_NEWTON specs)"""
+    from time_series_spark_amd import forecaster as fc
+    d = {k: v for k, v in spec.to_dict().items() if k != 'lbfgs'}
+    opts = {k: v for k, v in spec.lbfgs.items() if k != 'algorithm'}
+    return fc.ModelSpec(algorithm=algorithm, **d, **opts)
+
+
+def retry_panel():
+    """(offsets, ds, y, spec keywords) of the ragged panel on which algorithm AUTO with ZERO_TOL takes every branch of
+    the rule: series of 200, 200, 150 and 90 daily rows of synth.make_panel(4, 200, 'linear', seed=411), weekly order 3 --
+    an L-BFGS group whose fits end in LSFAIL (retried with Newton) beside a Newton group (fewer than 100 rows)."""
+    from time_series_spark_amd import synth
+    ds, y = synth.make_panel(4, 200, 'linear', seed=411)
+    lens = [200, 200, 150, 90]
+    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    return (off, np.concatenate([ds[:m] for m in lens]).astype(np.int64), np.concatenate([y[n, :m] for n, m in enumerate(lens)]),
+            dict(growth='linear', seasonalities=[dict(WEEKLY)]))
+
+
 def pack_reference(sid, did, ds_ns, y):
     """numpy statement of the packing order contract (include/tsf.h, tsf_pack_rows): NaN-y rows
     dropped, stable lexsort by (series_id, dim_id, ds).  Checker for the native packer."""

@@ -404,6 +404,11 @@ def test_calibrate_refuses_another_horizon(env, panels):
         rc = L.tsf_calibrate(ctx.handle, ctypes.byref(cs), N, T, None, p['ds'].ctypes.data, y.ctypes.data, _lib.Y_F64, None,
                              None, None, ctypes.byref(ca), None, ns, 0.8, 0, ctypes.byref(a), ctypes.byref(tab), None)
         assert (rc == 0) == ok, (cal_h, mode, rc)
+    # an algorithm outside the enum is refused up front, by tsf_calibrate and by tsf_cross_validate (one path)
+    bad = fc.ModelSpec(algorithm=7, **{k: v for k, v in spec.to_dict().items() if k != 'lbfgs'})
+    for call in (lambda: fc.calibrate(bad, p['ds'], y, HZ, [0.8], **CV), lambda: fc.cross_validate(bad, p['ds'], y, HZ, **CV)):
+        with pytest.raises(_lib.TsfError, match='bad algorithm'):
+            call()
 
 
 # ---- 5. plain C ----------------------------------------------------------------------------------------------------------------

@@ -265,6 +265,26 @@ def test_folds_cross_100_rows_newton_per_fold(env):
     _assert_metrics(_lib, cv, 0.1)
 
 
+def test_auto_retries_failed_line_searches_with_newton(env):
+    """algorithm AUTO with every tolerance zero on helpers.retry_panel (2 - 3 folds per series): the L-BFGS folds end in
+    a failed line search and are fitted once more with Newton, beside the folds of fewer than 100 rows that go to Newton
+    at once -- all three launches of the rule in one call.  The precondition is asserted on the by-hand L-BFGS fits."""
+    fc, _lib = env
+    off, ds, y, kw = helpers.retry_panel()
+    spec = fc.ModelSpec(algorithm=_lib.ALGO_AUTO, **kw, **helpers.ZERO_TOL)
+    cv = fc.cross_validate(spec, ds, y, 7 * DAY, offsets=off, period=56 * DAY, initial=25 * DAY)
+    assert list(cv.n_folds) == [3, 3, 3, 2] and (cv.status == 0).all()
+    launches = fc.last_cv_grids()[1]
+    lb = cv.hist_rows >= 100
+    assert lb.sum() == 5 and (~lb).sum() == 6
+    first, _, _, _ = _by_hand(fc, _lib, helpers.explicit_algorithm(spec, _lib.ALGO_LBFGS), cv, ds, y, off)
+    retried = np.isin(first['status'][lb], helpers.retry_statuses(_lib))
+    print('L-BFGS statuses of the folds of >= 100 rows:', first['status'][lb])
+    assert retried.any() and launches == 3                                  # the L-BFGS, the retry and the Newton launch
+    res, yh, lo, hi = _by_hand(fc, _lib, spec, cv, ds, y, off)
+    _assert_same_folds(cv, res, yh, lo, hi)
+
+
 def test_abi_cv_plain_c(env, tmp_path):
     """tests/c/abi_cv.c drives tsf_cross_validate from plain C99 and writes what the binding returns."""
     fc, _lib = env

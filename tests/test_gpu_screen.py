@@ -267,6 +267,88 @@ def test_fit_screened_is_fit_screen_cut_refit(env, fitted, kind, ragged):
     _check_composition(fc, c, spec, args, sf)
 
 
+def _fit_by_rule(fc, _lib, spec, rows, fit_group, one_grid=False):
+    """fbprophet's optimiser rule for algorithm AUTO done by hand over series of `rows` rows each, with explicit
+    ALGO_LBFGS / ALGO_NEWTON specs: L-BFGS from 100 rows on, Newton once more where it ended the way pystan raises on,
+    Newton below 100 rows.  fit_group(spec, indices) -> FitResult over the indices.  Returns the FitResult over all
+    series (one_grid: an aligned panel's single grid) and the L-BFGS statuses of the series of >= 100 rows."""
+    rows = np.asarray(rows)
+    idx = np.arange(len(rows))
+    got = {}
+
+    def put(sp, sel):
+        if len(sel) == 0:
+            return np.zeros(0, np.int32)
+        f = fit_group(sp, sel)
+        for k in ('theta', 'y_scale', 'fval', 'status', 'n_iter', 'n_eval', 'grid'):
+            v = getattr(f, k)
+            if k == 'grid' and one_grid:
+                got[k] = v
+                continue
+            got.setdefault(k, np.zeros((len(rows),) + v.shape[1:], v.dtype))[sel] = v
+        return f.status.copy()
+    sp_l, sp_n = helpers.explicit_algorithm(spec, _lib.ALGO_LBFGS), helpers.explicit_algorithm(spec, _lib.ALGO_NEWTON)
+    lb = idx[rows >= 100]
+    st = put(sp_l, lb)
+    put(sp_n, lb[np.isin(st, helpers.retry_statuses(_lib))])
+    put(sp_n, idx[rows < 100])
+    return fc.FitResult(spec, *[got[k] for k in ('theta', 'y_scale', 'fval', 'status', 'n_iter', 'n_eval', 'grid')]), st
+
+
+@pytest.mark.parametrize('zero_tol', [False, True], ids=['default_tol', 'zero_tol'])
+@pytest.mark.parametrize('ragged', [False, True], ids=['aligned', 'ragged'])
+def test_fit_screened_auto_is_the_rule_by_hand(env, ragged, zero_tol):
+    """algorithm AUTO: the first fit and the refit of the cut series are fbprophet's rule per series -- on the aligned
+    120-row panel everything is L-BFGS; the ragged panel has a spiked series of 80 rows besides, so both optimiser groups
+    occur in the first fit and in the refit; with every tolerance zero L-BFGS ends in a failed line search and the
+    Newton retry is taken (asserted on the by-hand L-BFGS statuses)."""
+    fc, _lib = env
+    c = sc.make('lin120', n_clean_extra=2)
+    spec = fc.ModelSpec(algorithm=_lib.ALGO_AUTO, **c.spec_kw, **(helpers.ZERO_TOL if zero_tol else {}))
+    if ragged:
+        off, ds, y = sc.ragged(c)
+        short = int(np.flatnonzero((c.rows < 70).sum(axis=1) >= 1)[0])        # a spike within its first 70 rows
+        off, ds, y = np.append(off, off[-1] + 80), np.concatenate([ds, c.ds[:80]]), np.concatenate([y, c.y[short, :80]])
+        args = dict(ds_ns=ds, y=y, offsets=off, floor=None, cap=None)
+        rows = np.diff(off)
+
+        def fit_first(sp, sel):
+            o2 = np.concatenate([[0], np.cumsum(rows[sel])]).astype(np.int64)
+            pick = np.concatenate([np.arange(off[n], off[n + 1]) for n in sel])
+            return fc.fit_ragged(sp, o2, ds[pick], y[pick])
+    else:
+        args = dict(ds_ns=c.ds, y=c.y, offsets=None, floor=None, cap=None)
+        rows = np.full(c.N, c.T)
+
+        def fit_first(sp, sel):
+            return fc.fit_aligned(sp, c.ds, c.y[sel])
+    N = len(rows)
+    every = np.arange(N)
+    sf = fc.fit_screened(spec, args['ds_ns'], args['y'], offsets=args['offsets'], **sc.SCREEN)
+    first, st_first = _fit_by_rule(fc, _lib, spec, rows, fit_first, one_grid=not ragged)
+    print('first fit: L-BFGS statuses', st_first)
+    assert ((rows < 100).any() and (rows >= 100).any()) == ragged
+    retry = helpers.retry_statuses(_lib)
+    assert np.isin(st_first, retry).any() or not zero_tol
+    _same_fit(sf.first, every, first, every, 'first')
+    assert sr.same(sf.first.fval, first.fval) and sr.same(sf.first.n_eval, first.n_eval)
+    assert len(sf.first.grid) == len(first.grid) and len(sf.fit.grid) == N
+    s = fc.screen(spec, first, args['ds_ns'], args['y'], offsets=args['offsets'], **sc.SCREEN)
+    for k in FIELDS:
+        assert sr.same(getattr(sf.screen, k), getattr(s, k)), k
+    flagged, clean = np.flatnonzero(s.n_new > 0), np.flatnonzero(s.n_new == 0)
+    assert len(flagged) >= sc.N_SPIKED and len(clean) >= 1
+    assert np.array_equal(sf.rounds, (s.n_new > 0).astype(np.int32))
+    _same_fit(sf.fit, clean, first, clean, 'never flagged')
+    kept = (rows - s.n_flagged)[flagged]
+    assert ((kept < 100).any() and (kept >= 100).any()) == ragged
+    by_hand, st_refit = _fit_by_rule(fc, _lib, spec, kept, lambda sp, sel: _refit_by_hand(fc, sp, args, s.flag, flagged[sel]))
+    print('refit: L-BFGS statuses', st_refit)
+    assert np.isin(st_refit, retry).any() or not zero_tol
+    _same_fit(sf.fit, flagged, by_hand, np.arange(len(flagged)), 'flagged')
+    assert sr.same(sf.fit.fval[flagged], by_hand.fval) and sr.same(sf.fit.n_eval[flagged], by_hand.n_eval)
+
+
 @pytest.mark.parametrize('ragged', [False, True], ids=['aligned', 'ragged'])
 def test_fit_screened_with_an_extra_column_and_int32_y(env, ragged):
     fc, _lib = env
@@ -384,6 +466,8 @@ def test_refusals_leave_the_context_usable(env):
         sout, _ = fc._alloc_screen(c.y, c.N)
         ctx.check(L.tsf_fit_screened(ctx.handle, ctypes.byref(cs), c.N, c.T, None, c.ds.ctypes.data, c.y.ctypes.data, _lib.Y_F64,
                                      None, None, None, 1e-8, ctypes.byref(a), ctypes.byref(_lib.TsfFitScreenedOut(fout, None, sout, None))))
+    with pytest.raises(_lib.TsfError, match='bad algorithm'):           # outside the enum: refused up front
+        fc.fit_screened(fc.ModelSpec(algorithm=7, **c.spec_kw), c.ds, c.y, **sc.SCREEN)
     assert fc.fit_screened(spec, c.ds, c.y, **sc.SCREEN).screen.n_new.sum() >= sc.N_SPIKED * sc.N_SPIKES
 
 

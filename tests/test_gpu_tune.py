@@ -140,6 +140,25 @@ def test_reference_model_ragged_auto(env):
     _refit_by_hand(fc, _lib, r, ds, y, off, floor, cap)
 
 
+def test_auto_retries_failed_line_searches_with_newton(env):
+    """algorithm AUTO with every tolerance zero on helpers.retry_panel: L-BFGS ends in a failed line search, so the
+    candidates' folds and the refit take the rule's Newton retry beside its Newton group (the 90-row series, the short
+    folds).  The precondition is asserted on an L-BFGS fit of the refit done by hand."""
+    fc, _lib = env
+    off, ds, y, kw = helpers.retry_panel()
+    spec = fc.ModelSpec(algorithm=_lib.ALGO_AUTO, **kw, **helpers.ZERO_TOL)
+    cvkw = dict(offsets=off, period=56 * DAY, initial=25 * DAY)
+    r = fc.tune(spec, ds, y, 7 * DAY, grid={'changepoint_prior_scale': [0.05, 0.5]}, **cvkw)
+    assert len(r.candidates) == 2 and (r.status == 0).all() and (r.best >= 0).all()
+    cvs = [fc.cross_validate(c, ds, y, 7 * DAY, rolling_window=1.0, **cvkw) for c in r.candidates]
+    _assert_scores_are_cv(fc, r, cvs, {'rmse': r})
+    first = [fc.fit_ragged(helpers.explicit_algorithm(r.spec_of(n), _lib.ALGO_LBFGS), np.array([0, off[n + 1] - off[n]], np.int64),
+                           ds[off[n]:off[n + 1]], y[off[n]:off[n + 1]]).status[0] for n in range(3)]
+    print('L-BFGS statuses of the refit series of >= 100 rows:', first)
+    assert np.isin(first, helpers.retry_statuses(_lib)).any()
+    _refit_by_hand(fc, _lib, r, ds, y, off)
+
+
 def test_edge_series_in_one_panel(env):
     """Among OK series: one with less data than the horizon (plan status for every candidate, base refit), a constant one
     (every candidate ties: candidate 0), and one with zeros in its holdout rows under mape (no score: TSF_TUNE_NO_SCORE,
@@ -253,6 +272,9 @@ def test_bad_arguments(env):
                                                                 changepoint_prior_scale=0.0)])
     with pytest.raises(ValueError):
         fc.tune(spec, ds, y, 30 * DAY, candidates=[spec] * (_lib.TUNE_MAX_CAND + 1))
+    with pytest.raises(_lib.TsfError, match='bad algorithm'):           # outside the enum: refused up front
+        bad = fc.ModelSpec(growth='linear', seasonalities=SEAS[1:], algorithm=7)
+        fc.tune(bad, ds, y, 30 * DAY, candidates=[bad])
 
 
 def test_abi_tune_plain_c(env, tmp_path):

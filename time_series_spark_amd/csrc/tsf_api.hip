@@ -201,6 +201,12 @@ static int pick_KP(int K, int n_cp, int mixed)
     return 64;
 }
 
+// (also asked by the panel jobs before they upload anything: they apply the optimiser rule to `algorithm` themselves)
+static int check_algorithm(tsf_ctx *ctx, const tsf_spec *s)
+{
+    return s->algorithm < TSF_ALGO_LBFGS || s->algorithm > TSF_ALGO_AUTO ? fail(ctx, "bad algorithm") : 0;
+}
+
 static int build_devspec(tsf_ctx *ctx, const tsf_spec *s, DevSpec *d, int *mode_out)
 {
     if (!s) return fail(ctx, "spec is NULL");
@@ -217,7 +223,7 @@ static int build_devspec(tsf_ctx *ctx, const tsf_spec *s, DevSpec *d, int *mode_
     if (!(s->changepoint_prior_scale > 0.0)) return fail(ctx, "changepoint_prior_scale must be > 0");
     if (s->history < 1 || s->history > MAXH) return fail(ctx, "history must be in [1,8]");
     if (s->eval_form < TSF_EVAL_AUTO || s->eval_form > TSF_EVAL_QUADRATIC) return fail(ctx, "bad eval_form");
-    if (s->algorithm < TSF_ALGO_LBFGS || s->algorithm > TSF_ALGO_AUTO) return fail(ctx, "bad algorithm");
+    if (int rc = check_algorithm(ctx, s)) return rc;
     if (s->residual_kernel < TSF_RK_AUTO || s->residual_kernel > TSF_RK_COOP) return fail(ctx, "bad residual_kernel");
     if (s->converge != TSF_CONVERGE_STAN && s->converge != TSF_CONVERGE_MAP) return fail(ctx, "bad converge");
     if (s->converge == TSF_CONVERGE_MAP && (s->map_max_iter < 1 || !(s->map_tol > 0.0))) return fail(ctx, "map_max_iter must be >= 1 and map_tol > 0");
@@ -916,10 +922,74 @@ struct DevBuf {
         }
         return hipMalloc(&p, bytes);
     }
-    template <class T> T *as() { return (T *)p; }
+    // alloc + the n bytes at the host pointer src copied in
+    hipError_t put(const void *src, size_t n)
+    {
+        const hipError_t e = alloc(n);
+        return e != hipSuccess ? e : hipMemcpy(p, src, n, hipMemcpyHostToDevice);
+    }
+    template <class T> T *as() const { return (T *)p; }
 };
 
 size_t ysize(int dt) { return dt == TSF_Y_F64 ? 8 : 4; }
+
+// What a DevFitOut holds when alloc returns: the pool does not clear its buffers, and what no launch writes the caller
+// reads, so each site names the contents it relies on.
+enum FitOutInit {
+    FIT_OUT_RAW,        // nothing: a launch writes every element before it is read (every fold of a plan is fitted)
+    FIT_OUT_LAUNCH,     // status, n_iter, n_eval and the grids zero: the outputs of one fit launch (run_fit)
+    FIT_OUT_UNFITTED    // everything zero, status TSF_ST_TOO_FEW: a destination no launch may reach (a series without rows)
+};
+
+// The device side of a tsf_fit_out over n series: a fit launch's outputs, or the destination the launches of a panel job
+// scatter to.  The one place a tsf_fit_out of device pointers is put together (view) and copied back (download).
+struct DevFitOut {
+    DevBuf theta, y_scale, fval, status, n_iter, n_eval, grid;
+    size_t n = 0, stride = 0;
+
+    int alloc(tsf_ctx *ctx, int64_t n_series, int theta_stride, int64_t n_grids, FitOutInit init)
+    {
+        n = (size_t)n_series; stride = (size_t)theta_stride;
+        const size_t grid_bytes = sizeof(tsf_grid_info) * (size_t)n_grids;
+        HIP_TRY(ctx, theta.alloc(8 * n * stride)); HIP_TRY(ctx, y_scale.alloc(8 * n)); HIP_TRY(ctx, fval.alloc(8 * n));
+        HIP_TRY(ctx, status.alloc(4 * n)); HIP_TRY(ctx, n_iter.alloc(4 * n)); HIP_TRY(ctx, n_eval.alloc(4 * n));
+        HIP_TRY(ctx, grid.alloc(grid_bytes));
+        if (init == FIT_OUT_RAW) return 0;
+        if (init == FIT_OUT_UNFITTED) {
+            HIP_TRY(ctx, hipMemset(theta.p, 0, 8 * n * stride)); HIP_TRY(ctx, hipMemset(y_scale.p, 0, 8 * n));
+            HIP_TRY(ctx, hipMemset(fval.p, 0, 8 * n));
+        } else {
+            HIP_TRY(ctx, hipMemset(status.p, 0, 4 * n));
+        }
+        HIP_TRY(ctx, hipMemset(n_iter.p, 0, 4 * n)); HIP_TRY(ctx, hipMemset(n_eval.p, 0, 4 * n));
+        HIP_TRY(ctx, hipMemset(grid.p, 0, grid_bytes));
+        if (init == FIT_OUT_UNFITTED) {
+            const std::vector<int32_t> st(n, TSF_ST_TOO_FEW);
+            HIP_TRY(ctx, hipMemcpy(status.p, st.data(), 4 * n, hipMemcpyHostToDevice));
+        }
+        return 0;
+    }
+    tsf_fit_out view() const
+    {
+        tsf_fit_out o;
+        o.theta = theta.as<double>(); o.y_scale = y_scale.as<double>(); o.fval = fval.as<double>();
+        o.status = status.as<int32_t>(); o.n_iter = n_iter.as<int32_t>(); o.n_eval = n_eval.as<int32_t>();
+        o.grid = grid.as<tsf_grid_info>();
+        return o;
+    }
+    // to the host arrays of `out`, the first n_grids grids (an aligned fit has one)
+    int download(tsf_ctx *ctx, const tsf_fit_out &out, int64_t n_grids) const
+    {
+        HIP_TRY(ctx, hipMemcpy(out.theta, theta.p, 8 * n * stride, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out.y_scale, y_scale.p, 8 * n, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out.fval, fval.p, 8 * n, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out.status, status.p, 4 * n, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out.n_iter, n_iter.p, 4 * n, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out.n_eval, n_eval.p, 4 * n, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out.grid, grid.p, sizeof(tsf_grid_info) * (size_t)n_grids, hipMemcpyDeviceToHost));
+        return 0;
+    }
+};
 }  // namespace
 
 // Which of N timestamp vectors -- vector n = ds[start[n] .. start[n] + len[n]) -- are IDENTICAL (hash of the bytes, then
@@ -1008,6 +1078,26 @@ static void calendar_start_order(const std::vector<int32_t> &gof, int64_t n_dist
         for (int x = 0; x < 8; ++x) { const int64_t k = (int64_t)x * seg + i; if (k < N) ord[(size_t)q++] = byg[(size_t)k]; }
 }
 
+// The shared-calendar tables of a ragged launch over gof.size() series on the classes of calendar_classes: gof (the
+// class of every series), the rows (first, count) of each class's first member reps[k] in the launch's panel (off: its
+// offsets) and the start order.  *n_distinct = the number of classes, or 0 -- nothing uploaded, a grid per series --
+// where no two series share a calendar.  The one producer of FitCall::grid_of / grid_rows / grid_order.
+static int upload_calendar_tables(tsf_ctx *ctx, const std::vector<int32_t> &gof, const std::vector<int64_t> &reps,
+                                  const int64_t *off, DevBuf *d_gof, DevBuf *d_grows, DevBuf *d_gord, int64_t *n_distinct)
+{
+    *n_distinct = 0;
+    if (reps.size() >= gof.size()) return 0;
+    std::vector<int64_t> grows;
+    for (int64_t r : reps) { grows.push_back(off[r]); grows.push_back(off[r + 1] - off[r]); }
+    std::vector<int32_t> ord;
+    calendar_start_order(gof, (int64_t)reps.size(), &ord);
+    HIP_TRY(ctx, d_gof->put(gof.data(), 4 * gof.size()));
+    HIP_TRY(ctx, d_grows->put(grows.data(), 8 * grows.size()));
+    HIP_TRY(ctx, d_gord->put(ord.data(), 4 * ord.size()));
+    *n_distinct = (int64_t)reps.size();
+    return 0;
+}
+
 static int fit_host_one(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int aligned, int32_t T,
                         const int64_t *offsets, const int64_t *ds, const void *y, int32_t y_dtype,
                         const double *floor_, const double *cap, const double *extra,
@@ -1043,42 +1133,23 @@ static int fit_host_one(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int align
     auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t_start = host_timing ? now() : 0.0;
     double t_h2d = 0.0, t_fit = 0.0;
-    DevBuf d_ds, d_y, d_off, d_floor, d_cap, d_extra, d_theta, d_ys, d_f, d_st, d_it, d_ev, d_grid, d_thin, d_grad, d_thref;
-    HIP_TRY(ctx, d_ds.alloc(8 * n_ds));
-    HIP_TRY(ctx, d_y.alloc(ysize(y_dtype) * total));
-    HIP_TRY(ctx, hipMemcpy(d_ds.p, ds, 8 * n_ds, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(d_y.p, y, ysize(y_dtype) * total, hipMemcpyHostToDevice));
-    if (!aligned) {
-        HIP_TRY(ctx, d_off.alloc(8 * (N + 1)));
-        HIP_TRY(ctx, hipMemcpy(d_off.p, offsets, 8 * (N + 1), hipMemcpyHostToDevice));
-    }
-    if (floor_) { HIP_TRY(ctx, d_floor.alloc(8 * N)); HIP_TRY(ctx, hipMemcpy(d_floor.p, floor_, 8 * N, hipMemcpyHostToDevice)); }
-    if (cap) { HIP_TRY(ctx, d_cap.alloc(8 * N)); HIP_TRY(ctx, hipMemcpy(d_cap.p, cap, 8 * N, hipMemcpyHostToDevice)); }
+    DevBuf d_ds, d_y, d_off, d_floor, d_cap, d_extra, d_thin, d_grad, d_thref;
+    HIP_TRY(ctx, d_ds.put(ds, 8 * n_ds));
+    HIP_TRY(ctx, d_y.put(y, ysize(y_dtype) * total));
+    if (!aligned) HIP_TRY(ctx, d_off.put(offsets, 8 * (N + 1)));
+    if (floor_) HIP_TRY(ctx, d_floor.put(floor_, 8 * N));
+    if (cap) HIP_TRY(ctx, d_cap.put(cap, 8 * N));
     if (spec->n_extra > 0) {
         if (!extra) return fail(ctx, "extra columns declared but extra is NULL");
-        const size_t nb = 8 * (size_t)spec->n_extra * n_ds;
-        HIP_TRY(ctx, d_extra.alloc(nb));
-        HIP_TRY(ctx, hipMemcpy(d_extra.p, extra, nb, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, d_extra.put(extra, 8 * (size_t)spec->n_extra * n_ds));
     }
-    HIP_TRY(ctx, d_theta.alloc(8 * (size_t)N * stride));
-    HIP_TRY(ctx, d_ys.alloc(8 * N)); HIP_TRY(ctx, d_f.alloc(8 * N));
-    HIP_TRY(ctx, d_st.alloc(4 * N)); HIP_TRY(ctx, d_it.alloc(4 * N)); HIP_TRY(ctx, d_ev.alloc(4 * N));
-    HIP_TRY(ctx, d_grid.alloc(sizeof(tsf_grid_info) * n_grids));
-    HIP_TRY(ctx, hipMemset(d_st.p, 0, 4 * N)); HIP_TRY(ctx, hipMemset(d_it.p, 0, 4 * N));
-    HIP_TRY(ctx, hipMemset(d_ev.p, 0, 4 * N));
-    HIP_TRY(ctx, hipMemset(d_grid.p, 0, sizeof(tsf_grid_info) * n_grids));
-    tsf_fit_out dout;
-    dout.theta = d_theta.as<double>(); dout.y_scale = d_ys.as<double>(); dout.fval = d_f.as<double>();
-    dout.status = d_st.as<int32_t>(); dout.n_iter = d_it.as<int32_t>(); dout.n_eval = d_ev.as<int32_t>();
-    dout.grid = d_grid.as<tsf_grid_info>();
+    DevFitOut fo;
+    if (int rc = fo.alloc(ctx, N, stride, n_grids, FIT_OUT_LAUNCH)) return rc;
+    tsf_fit_out dout = fo.view();
     if (theta_in) {
-        HIP_TRY(ctx, d_thin.alloc(8 * (size_t)N * stride));
-        HIP_TRY(ctx, hipMemcpy(d_thin.p, theta_in, 8 * (size_t)N * stride, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, d_thin.put(theta_in, 8 * (size_t)N * stride));
         HIP_TRY(ctx, d_grad.alloc(8 * (size_t)N * stride));
-        if (theta_ref) {
-            HIP_TRY(ctx, d_thref.alloc(8 * (size_t)N * stride));
-            HIP_TRY(ctx, hipMemcpy(d_thref.p, theta_ref, 8 * (size_t)N * stride, hipMemcpyHostToDevice));
-        }
+        if (theta_ref) HIP_TRY(ctx, d_thref.put(theta_ref, 8 * (size_t)N * stride));
     }
     // ragged panel: do all timestamps lie on one lattice base + u*step (the usual case: one
     // sampling grid, different start dates / lengths)?  Then the design rows are computed once
@@ -1105,29 +1176,12 @@ static int fit_host_one(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int align
     // columns are per row, not per timestamp).  TSF_GRID_SHARE=0 turns it off (tests compare both).
     DevBuf d_gof, d_grows, d_gord;
     int64_t n_distinct = 0;
-    {
-        if (!aligned && !theta_in && spec->n_extra == 0 && N >= 2 && ctx->opt[TSF_OPT_GRID_SHARE] != 0) {
-            std::vector<int64_t> vstart((size_t)N), vlen((size_t)N), reps;
-            for (int64_t n = 0; n < N; ++n) { vstart[(size_t)n] = offsets[n]; vlen[(size_t)n] = offsets[n + 1] - offsets[n]; }
-            std::vector<int32_t> gof;
-            calendar_classes(ds, vstart.data(), vlen.data(), N, &gof, &reps);
-            std::vector<int64_t> grows;
-            for (int64_t r : reps) { grows.push_back(offsets[r]); grows.push_back(offsets[r + 1] - offsets[r]); }
-            n_distinct = (int64_t)(grows.size() / 2);
-            if (n_distinct < N) {
-                HIP_TRY(ctx, d_gof.alloc(4 * (size_t)N));
-                HIP_TRY(ctx, d_grows.alloc(8 * grows.size()));
-                HIP_TRY(ctx, hipMemcpy(d_gof.p, gof.data(), 4 * (size_t)N, hipMemcpyHostToDevice));
-                HIP_TRY(ctx, hipMemcpy(d_grows.p, grows.data(), 8 * grows.size(), hipMemcpyHostToDevice));
-                // the order in which the launch starts the series (calendar_start_order)
-                std::vector<int32_t> ord;
-                calendar_start_order(gof, n_distinct, &ord);
-                HIP_TRY(ctx, d_gord.alloc(4 * (size_t)N));
-                HIP_TRY(ctx, hipMemcpy(d_gord.p, ord.data(), 4 * (size_t)N, hipMemcpyHostToDevice));
-            } else {
-                n_distinct = 0;
-            }
-        }
+    if (!aligned && !theta_in && spec->n_extra == 0 && N >= 2 && ctx->opt[TSF_OPT_GRID_SHARE] != 0) {
+        std::vector<int64_t> vstart((size_t)N), vlen((size_t)N), reps;
+        for (int64_t n = 0; n < N; ++n) { vstart[(size_t)n] = offsets[n]; vlen[(size_t)n] = offsets[n + 1] - offsets[n]; }
+        std::vector<int32_t> gof;
+        calendar_classes(ds, vstart.data(), vlen.data(), N, &gof, &reps);
+        if (int rc = upload_calendar_tables(ctx, gof, reps, offsets, &d_gof, &d_grows, &d_gord, &n_distinct)) return rc;
     }
     if (host_timing) t_h2d = now();
     FitCall c = {};
@@ -1146,17 +1200,12 @@ static int fit_host_one(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int align
     HIP_TRY(ctx, hipDeviceSynchronize());
     if (host_timing) t_fit = now();
     if (theta_in) {
-        HIP_TRY(ctx, hipMemcpy(f_out, d_f.p, 8 * N, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(f_out, fo.fval.p, 8 * N, hipMemcpyDeviceToHost));
         HIP_TRY(ctx, hipMemcpy(grad_out, d_grad.p, 8 * (size_t)N * stride, hipMemcpyDeviceToHost));
         return 0;
     }
-    HIP_TRY(ctx, hipMemcpy(out->theta, d_theta.p, 8 * (size_t)N * stride, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(out->y_scale, d_ys.p, 8 * N, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(out->fval, d_f.p, 8 * N, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(out->status, d_st.p, 4 * N, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(out->n_iter, d_it.p, 4 * N, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(out->n_eval, d_ev.p, 4 * N, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(out->grid, d_grid.p, sizeof(tsf_grid_info) * n_grids, hipMemcpyDeviceToHost));
+    rc = fo.download(ctx, *out, n_grids);
+    if (rc) return rc;
     if (host_timing)
         fprintf(stderr, "[host-timing] N %lld: alloc + H2D + clears %.3f ms, fit (launch .. device idle) %.3f ms, D2H %.3f ms\n",
                 (long long)N, t_h2d - t_start, t_fit - t_h2d, now() - t_fit);
@@ -1397,8 +1446,7 @@ struct ForecastUpload {
     {
         *d = nullptr;
         if (!src) return 0;
-        HIP_TRY(ctx, b->alloc(bytes));
-        HIP_TRY(ctx, hipMemcpy(b->p, src, bytes, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, b->put(src, bytes));
         *d = b->as<T>();
         return 0;
     }
@@ -3109,14 +3157,24 @@ extern "C" int tsf_last_cv_grids(const tsf_ctx *ctx, int64_t *n_grids, int32_t *
 }
 
 namespace {
+// The caller's panel as the host entries of the panel jobs receive it (host pointers).
+struct PanelIn {
+    int64_t N; int32_t T; const int64_t *offsets, *ds; const void *y; int32_t y_dtype; const double *floor_, *cap, *extra;
+};
+
+struct CvHoldout {              // the holdout rows of every fold as one padded future panel [F][Hmax]
+    DevBuf d_fds, d_fex, d_fkey, d_ffl, d_fcap;
+};
+
+struct CvMetrics {              // cv_metrics_kernel's tables, scratch and outputs
+    DevBuf d_foff, d_roff, d_moff, d_fcut, d_frow0, d_hs, d_ts, d_pre, d_yo, d_loo, d_hio, d_mh, d_mm, d_sst;
+    CvMetricArgs ma;
+};
+
 // What a cross-validation call derives once from its arguments: the plan, the fold tables, the caller's panel on the
-// device (cv_upload) and the fold fit outputs in plan order.
-struct CvCall {
+// device (cv_upload), the fold fit outputs in plan order, the holdout rows, their forecasts [F][Hmax] and the metrics.
+struct CvCall : PanelIn {
     bool aligned = false;
-    int64_t N = 0;
-    int32_t T = 0;
-    const int64_t *offsets = nullptr, *ds = nullptr;      // the caller's (host)
-    int32_t y_dtype = 0;
     size_t ysz = 8;
     int n_extra = 0, stride = 0;
     bool has_floor = false, has_cap = false;
@@ -3131,8 +3189,10 @@ struct CvCall {
     int32_t Hmax = 1, C = 0;
     DevBuf d_ds, d_y, d_off, d_ex, d_fl, d_cap, d_key, d_fser, d_fc, d_fhist, d_fhold;
     CvPanel pn;
-    DevBuf d_th, d_ys, d_fv, d_st, d_it, d_ev, d_gr;
-    tsf_fit_out dfo;
+    DevFitOut fit;
+    CvHoldout hold;
+    DevBuf d_yh, d_lo, d_hi;
+    CvMetrics met;
 };
 
 // Views of the caller's series that cv_expand_kernel cuts: view v = rows [0, hist[v]) of series series[v].  The folds
@@ -3150,30 +3210,32 @@ struct CvViews {
 // The panel of one fit launch: views gf[0 .. G), cut on the device, and their calendar classes.
 struct CvGroup {
     std::vector<int32_t> gf;
+    std::vector<int64_t> goff;          // [G + 1] row offsets of the members in the launch's panel
     int64_t G = 0, rows = 0, n_distinct = 0;
     int32_t maxT = 0;
     DevBuf d_gf, d_goff, d_gds, d_gy, d_gex, d_gfl, d_gcap, d_gof, d_grows, d_gord;
     DevBuf d_gkeep;             // [grids of the launch] CvViews::keep per grid (setup_grid_kernel grid_keep), where given
 };
 
-struct CvHoldout {              // the holdout rows of every fold as one padded future panel [F][Hmax]
-    DevBuf d_fds, d_fex, d_fkey, d_ffl, d_fcap;
-};
-
-struct CvMetrics {              // cv_metrics_kernel's tables, scratch and outputs
-    DevBuf d_foff, d_roff, d_moff, d_fcut, d_frow0, d_hs, d_ts, d_pre, d_yo, d_loo, d_hio, d_mh, d_mm, d_sst;
-    CvMetricArgs ma;
-};
 }  // namespace
 
-// the plan and the fold tables (host only)
-static void cv_plan_call(int64_t N, int32_t T, const int64_t *offsets, const int64_t *ds, const tsf_cv_args &a,
-                         const tsf_spec *spec, int32_t y_dtype, const double *floor_, const double *cap, CvCall *S)
+// the caller's panel and its shape (what cv_upload and every launch over the panel read of a CvCall)
+static void cv_call_shape(const PanelIn &p, const tsf_spec *spec, CvCall *S)
 {
-    S->aligned = offsets == nullptr;
-    S->N = N; S->T = T; S->offsets = offsets; S->ds = ds; S->y_dtype = y_dtype; S->ysz = ysize(y_dtype);
+    static_cast<PanelIn &>(*S) = p;
+    S->aligned = p.offsets == nullptr;
+    S->ysz = ysize(p.y_dtype);
     S->n_extra = spec->n_extra; S->stride = tsf_theta_stride(spec);
-    S->has_floor = floor_ != nullptr; S->has_cap = cap != nullptr;
+    S->has_floor = p.floor_ != nullptr; S->has_cap = p.cap != nullptr;
+}
+
+// the plan and the fold tables (host only)
+static void cv_plan_call(const PanelIn &p, const tsf_cv_args &a, const tsf_spec *spec, CvCall *S)
+{
+    const int64_t N = p.N, *offsets = p.offsets, *ds = p.ds;
+    const int32_t T = p.T;
+    const double *floor_ = p.floor_, *cap = p.cap;
+    cv_call_shape(p, spec, S);
     tsf_cv::panel_plan(N, T, offsets, ds, a, &S->plan, &S->pst, &S->pnh, &S->pnm);
     S->fold_off.assign((size_t)N + 1, 0); S->rows_off.assign((size_t)N + 1, 0); S->m_off.assign((size_t)N + 1, 0);
     for (int64_t n = 0; n < N; ++n) {
@@ -3211,48 +3273,30 @@ static void cv_plan_call(int64_t N, int32_t T, const int64_t *offsets, const int
 }
 
 // the caller's panel, once; the fold tables; the fold outputs in plan order
-static int cv_upload(tsf_ctx *ctx, const void *y, const double *floor_, const double *cap, const double *extra,
-                     const int64_t *series_key, CvCall *S)
+static int cv_upload(tsf_ctx *ctx, const int64_t *series_key, CvCall *S)
 {
     const int64_t N = S->N, F = S->F, T = S->T;
     const int64_t n_ds = S->aligned ? T : S->offsets[N];
     const int64_t n_y = S->aligned ? N * T : S->offsets[N];
-    HIP_TRY(ctx, S->d_ds.alloc(8 * (size_t)n_ds));
-    HIP_TRY(ctx, hipMemcpy(S->d_ds.p, S->ds, 8 * (size_t)n_ds, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, S->d_y.alloc(S->ysz * (size_t)n_y));
-    HIP_TRY(ctx, hipMemcpy(S->d_y.p, y, S->ysz * (size_t)n_y, hipMemcpyHostToDevice));
-    if (!S->aligned) {
-        HIP_TRY(ctx, S->d_off.alloc(8 * ((size_t)N + 1)));
-        HIP_TRY(ctx, hipMemcpy(S->d_off.p, S->offsets, 8 * ((size_t)N + 1), hipMemcpyHostToDevice));
-    }
-    if (S->n_extra > 0) {
-        HIP_TRY(ctx, S->d_ex.alloc(8 * (size_t)S->n_extra * n_ds));
-        HIP_TRY(ctx, hipMemcpy(S->d_ex.p, extra, 8 * (size_t)S->n_extra * n_ds, hipMemcpyHostToDevice));
-    }
-    if (floor_) { HIP_TRY(ctx, S->d_fl.alloc(8 * (size_t)N)); HIP_TRY(ctx, hipMemcpy(S->d_fl.p, floor_, 8 * (size_t)N, hipMemcpyHostToDevice)); }
-    if (cap) { HIP_TRY(ctx, S->d_cap.alloc(8 * (size_t)N)); HIP_TRY(ctx, hipMemcpy(S->d_cap.p, cap, 8 * (size_t)N, hipMemcpyHostToDevice)); }
-    if (series_key) { HIP_TRY(ctx, S->d_key.alloc(8 * (size_t)N)); HIP_TRY(ctx, hipMemcpy(S->d_key.p, series_key, 8 * (size_t)N, hipMemcpyHostToDevice)); }
+    HIP_TRY(ctx, S->d_ds.put(S->ds, 8 * (size_t)n_ds));
+    HIP_TRY(ctx, S->d_y.put(S->y, S->ysz * (size_t)n_y));
+    if (!S->aligned) HIP_TRY(ctx, S->d_off.put(S->offsets, 8 * ((size_t)N + 1)));
+    if (S->n_extra > 0) HIP_TRY(ctx, S->d_ex.put(S->extra, 8 * (size_t)S->n_extra * n_ds));
+    if (S->floor_) HIP_TRY(ctx, S->d_fl.put(S->floor_, 8 * (size_t)N));
+    if (S->cap) HIP_TRY(ctx, S->d_cap.put(S->cap, 8 * (size_t)N));
+    if (series_key) HIP_TRY(ctx, S->d_key.put(series_key, 8 * (size_t)N));
     if (F > 0) {                        // (tsf_tune uploads a panel without folds for its refit)
-        HIP_TRY(ctx, S->d_fser.alloc(4 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(S->d_fser.p, S->f_series.data(), 4 * (size_t)F, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, S->d_fc.alloc(4 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(S->d_fc.p, S->f_c.data(), 4 * (size_t)F, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, S->d_fhist.alloc(8 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(S->d_fhist.p, S->f_hist.data(), 8 * (size_t)F, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, S->d_fhold.alloc(8 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(S->d_fhold.p, S->f_hold.data(), 8 * (size_t)F, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, S->d_fser.put(S->f_series.data(), 4 * (size_t)F));
+        HIP_TRY(ctx, S->d_fc.put(S->f_c.data(), 4 * (size_t)F));
+        HIP_TRY(ctx, S->d_fhist.put(S->f_hist.data(), 8 * (size_t)F));
+        HIP_TRY(ctx, S->d_fhold.put(S->f_hold.data(), 8 * (size_t)F));
     }
     CvPanel &pn = S->pn;
     pn.ds = S->d_ds.as<int64_t>(); pn.y = S->d_y.p; pn.extra = S->n_extra > 0 ? S->d_ex.as<double>() : nullptr;
     pn.src_off = S->aligned ? nullptr : S->d_off.as<int64_t>(); pn.T = S->aligned ? T : 0;
     pn.src_total = S->aligned ? 0 : S->offsets[N];
     pn.ysz = (int)S->ysz; pn.n_extra = S->n_extra;
-    const int stride = S->stride;
-    HIP_TRY(ctx, S->d_th.alloc(8 * (size_t)F * stride)); HIP_TRY(ctx, S->d_ys.alloc(8 * (size_t)F));
-    HIP_TRY(ctx, S->d_fv.alloc(8 * (size_t)F)); HIP_TRY(ctx, S->d_st.alloc(4 * (size_t)F));
-    HIP_TRY(ctx, S->d_it.alloc(4 * (size_t)F)); HIP_TRY(ctx, S->d_ev.alloc(4 * (size_t)F));
-    HIP_TRY(ctx, S->d_gr.alloc(sizeof(tsf_grid_info) * (size_t)F));
-    tsf_fit_out &dfo = S->dfo;
-    dfo.theta = S->d_th.as<double>(); dfo.y_scale = S->d_ys.as<double>(); dfo.fval = S->d_fv.as<double>();
-    dfo.status = S->d_st.as<int32_t>(); dfo.n_iter = S->d_it.as<int32_t>(); dfo.n_eval = S->d_ev.as<int32_t>();
-    dfo.grid = S->d_gr.as<tsf_grid_info>();
-    return 0;
+    return S->fit.alloc(ctx, F, S->stride, F, FIT_OUT_RAW);
 }
 
 static CvViews cv_fold_views(CvCall &S)
@@ -3261,28 +3305,38 @@ static CvViews cv_fold_views(CvCall &S)
                    S.f_keep.empty() ? nullptr : S.f_keep.data()};
 }
 
-// the panel of one fit launch over the views gf (cv_expand_kernel) and its calendar classes (same rule as
-// fit_host_one: ragged, no explicit columns, two views or more)
+// the layout of a launch's panel over the members gf, member g with n_rows[gf[g]] rows: the list and the row offsets on
+// the device, the panel's buffers allocated (for cv_expand_kernel or screen_compact_kernel to fill)
+static int cv_group_layout(tsf_ctx *ctx, const CvCall &S, const std::vector<int32_t> &gf, const int64_t *n_rows, CvGroup *E)
+{
+    const size_t G = gf.size();
+    E->G = (int64_t)G;
+    E->gf = gf;
+    E->goff.assign(G + 1, 0);
+    for (size_t g = 0; g < G; ++g) {
+        const int64_t h = n_rows[(size_t)gf[g]];
+        E->goff[g + 1] = E->goff[g] + h;
+        if (h > E->maxT) E->maxT = (int32_t)h;
+    }
+    const size_t rows = (size_t)(E->rows = E->goff[G]);
+    if (G == 0) return 0;
+    HIP_TRY(ctx, E->d_gf.put(gf.data(), 4 * G));
+    HIP_TRY(ctx, E->d_goff.put(E->goff.data(), 8 * (G + 1)));
+    HIP_TRY(ctx, E->d_gds.alloc(8 * rows)); HIP_TRY(ctx, E->d_gy.alloc(S.ysz * rows));
+    if (S.n_extra > 0) HIP_TRY(ctx, E->d_gex.alloc(8 * (size_t)S.n_extra * rows));
+    if (S.has_floor) HIP_TRY(ctx, E->d_gfl.alloc(8 * G));
+    if (S.has_cap) HIP_TRY(ctx, E->d_gcap.alloc(8 * G));
+    return 0;
+}
+
+// the panel of one fit launch over the views gf (cv_expand_kernel) and its calendar classes (fit_host_one's rule:
+// ragged, no explicit columns, two views or more; the tables through upload_calendar_tables as there)
 static int cv_expand(tsf_ctx *ctx, CvCall &S, const CvViews &V, const std::vector<int32_t> &gf, CvGroup *E)
 {
-    const int64_t G = E->G = (int64_t)gf.size();
-    E->gf = gf;
+    if (int rc = cv_group_layout(ctx, S, gf, V.hist, E)) return rc;
+    const int64_t G = E->G, rows = E->rows;
+    const std::vector<int64_t> &goff = E->goff;
     if (G == 0) return 0;
-    std::vector<int64_t> goff((size_t)G + 1, 0);
-    int32_t maxT = 0;
-    for (int64_t g = 0; g < G; ++g) {
-        const int64_t h = V.hist[(size_t)gf[(size_t)g]];
-        goff[(size_t)g + 1] = goff[(size_t)g] + h;
-        if (h > maxT) maxT = (int32_t)h;
-    }
-    const int64_t rows = E->rows = goff[(size_t)G];
-    E->maxT = maxT;
-    HIP_TRY(ctx, E->d_gf.alloc(4 * (size_t)G)); HIP_TRY(ctx, hipMemcpy(E->d_gf.p, gf.data(), 4 * (size_t)G, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, E->d_goff.alloc(8 * ((size_t)G + 1))); HIP_TRY(ctx, hipMemcpy(E->d_goff.p, goff.data(), 8 * ((size_t)G + 1), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, E->d_gds.alloc(8 * (size_t)rows)); HIP_TRY(ctx, E->d_gy.alloc(S.ysz * (size_t)rows));
-    if (S.n_extra > 0) HIP_TRY(ctx, E->d_gex.alloc(8 * (size_t)S.n_extra * rows));
-    if (S.has_floor) HIP_TRY(ctx, E->d_gfl.alloc(8 * (size_t)G));
-    if (S.has_cap) HIP_TRY(ctx, E->d_gcap.alloc(8 * (size_t)G));
     hipLaunchKernelGGL(cv_expand_kernel, dim3((unsigned)(G < 65535 ? G : 65535)), dim3(256), 0, nullptr, S.pn, G,
                        E->d_gf.as<int32_t>(), V.d_series, E->d_goff.as<int64_t>(), rows,
                        S.has_floor ? S.d_fl.as<double>() : nullptr, S.has_cap ? S.d_cap.as<double>() : nullptr,
@@ -3321,28 +3375,18 @@ static int cv_expand(tsf_ctx *ctx, CvCall &S, const CvViews &V, const std::vecto
             }
             reps.swap(reps2);
         }
-        n_distinct = (int64_t)reps.size();
-        if (n_distinct < G) {
-            std::vector<int64_t> grows;
-            for (int64_t r : reps) { grows.push_back(goff[(size_t)r]); grows.push_back(goff[(size_t)r + 1] - goff[(size_t)r]); }
-            std::vector<int32_t> ord;
-            calendar_start_order(gof, n_distinct, &ord);
-            HIP_TRY(ctx, E->d_gof.alloc(4 * (size_t)G)); HIP_TRY(ctx, hipMemcpy(E->d_gof.p, gof.data(), 4 * (size_t)G, hipMemcpyHostToDevice));
-            HIP_TRY(ctx, E->d_grows.alloc(8 * grows.size())); HIP_TRY(ctx, hipMemcpy(E->d_grows.p, grows.data(), 8 * grows.size(), hipMemcpyHostToDevice));
-            HIP_TRY(ctx, E->d_gord.alloc(4 * (size_t)G)); HIP_TRY(ctx, hipMemcpy(E->d_gord.p, ord.data(), 4 * (size_t)G, hipMemcpyHostToDevice));
-            if (V.keep) {
-                std::vector<int32_t> kp;
-                for (int64_t r : reps) kp.push_back(V.keep[(size_t)gf[(size_t)r]]);
-                HIP_TRY(ctx, E->d_gkeep.alloc(4 * kp.size())); HIP_TRY(ctx, hipMemcpy(E->d_gkeep.p, kp.data(), 4 * kp.size(), hipMemcpyHostToDevice));
-            }
-        } else {
-            n_distinct = 0;
+        if (int rc = upload_calendar_tables(ctx, gof, reps, goff.data(), &E->d_gof, &E->d_grows, &E->d_gord, &n_distinct))
+            return rc;
+        if (V.keep && n_distinct > 0) {
+            std::vector<int32_t> kp;
+            for (int64_t r : reps) kp.push_back(V.keep[(size_t)gf[(size_t)r]]);
+            HIP_TRY(ctx, E->d_gkeep.put(kp.data(), 4 * kp.size()));
         }
     }
     if (V.keep && n_distinct == 0) {        // a grid per view
         std::vector<int32_t> kp((size_t)G);
         for (int64_t g = 0; g < G; ++g) kp[(size_t)g] = V.keep[(size_t)gf[(size_t)g]];
-        HIP_TRY(ctx, E->d_gkeep.alloc(4 * (size_t)G)); HIP_TRY(ctx, hipMemcpy(E->d_gkeep.p, kp.data(), 4 * (size_t)G, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, E->d_gkeep.put(kp.data(), 4 * (size_t)G));
     }
     E->n_distinct = n_distinct;
     return 0;
@@ -3355,16 +3399,9 @@ static int cv_fit(tsf_ctx *ctx, CvCall &S, CvGroup &E, const tsf_spec &gs, const
     const int64_t G = E.G;
     if (G == 0) return 0;
     const int stride = S.stride;
-    DevBuf g_th, g_ys, g_fv, g_st, g_it, g_ev, g_gr;
-    HIP_TRY(ctx, g_th.alloc(8 * (size_t)G * stride)); HIP_TRY(ctx, g_ys.alloc(8 * (size_t)G)); HIP_TRY(ctx, g_fv.alloc(8 * (size_t)G));
-    HIP_TRY(ctx, g_st.alloc(4 * (size_t)G)); HIP_TRY(ctx, g_it.alloc(4 * (size_t)G)); HIP_TRY(ctx, g_ev.alloc(4 * (size_t)G));
-    HIP_TRY(ctx, g_gr.alloc(sizeof(tsf_grid_info) * (size_t)G));
-    HIP_TRY(ctx, hipMemset(g_st.p, 0, 4 * (size_t)G)); HIP_TRY(ctx, hipMemset(g_it.p, 0, 4 * (size_t)G));
-    HIP_TRY(ctx, hipMemset(g_ev.p, 0, 4 * (size_t)G)); HIP_TRY(ctx, hipMemset(g_gr.p, 0, sizeof(tsf_grid_info) * (size_t)G));
-    tsf_fit_out go;
-    go.theta = g_th.as<double>(); go.y_scale = g_ys.as<double>(); go.fval = g_fv.as<double>();
-    go.status = g_st.as<int32_t>(); go.n_iter = g_it.as<int32_t>(); go.n_eval = g_ev.as<int32_t>();
-    go.grid = g_gr.as<tsf_grid_info>();
+    DevFitOut launch;
+    if (int rc = launch.alloc(ctx, G, stride, G, FIT_OUT_LAUNCH)) return rc;
+    tsf_fit_out go = launch.view();
     const int64_t nd = E.n_distinct;
     FitCall c = {};
     c.N = G; c.offsets = E.d_goff.as<int64_t>(); c.total_rows = E.rows; c.max_T = E.maxT;
@@ -3385,19 +3422,29 @@ static int cv_fit(tsf_ctx *ctx, CvCall &S, CvGroup &E, const tsf_spec &gs, const
     return 0;
 }
 
-// the folds with history below fbprophet's Newton threshold (algorithm AUTO), or all folds on the spec's optimiser
-static void cv_optimiser_groups(const CvCall &S, const tsf_spec *spec, std::vector<int32_t> *g_lbfgs,
-                                std::vector<int32_t> *g_newton)
+// ---- fbprophet's optimiser rule (include/tsf.h, TSF_ALGO_AUTO) ---------------------------------------------------
+// Newton for a history of fewer than TSF_NEWTON_BELOW_T rows, L-BFGS otherwise, Newton once more where L-BFGS ended
+// the way pystan raises RuntimeError on -- for models Newton takes (at most TSF_MAX_P parameters).  TSF_ALGO_LBFGS /
+// TSF_ALGO_NEWTON: every member on that optimiser, nothing retried.  The one implementation, for the folds of a
+// cross-validation, calibration or tuning and the series of tsf_tune's refit and of tsf_fit_screened's rounds.
+struct OptimiserGroups { std::vector<int32_t> lbfgs, newton; };
+enum RuleLaunch { RULE_LBFGS, RULE_RETRY, RULE_NEWTON };        // the launches of the rule, in their order
+
+static bool newton_takes(const tsf_spec &s) { return 3 + s.n_changepoints + tsf_spec_K(&s) <= TSF_MAX_P; }
+// the n members members[i] (null: 0 .. n - 1) split by their row counts rows[member]
+static OptimiserGroups optimiser_groups(const tsf_spec &spec, const int32_t *members, size_t n, const int64_t *rows)
 {
-    const bool auto_algo = spec->algorithm == TSF_ALGO_AUTO;
-    const bool newton_ok = 3 + spec->n_changepoints + tsf_spec_K(spec) <= TSF_MAX_P;
-    for (int64_t f = 0; f < S.F; ++f) {
-        const bool nw = auto_algo ? (newton_ok && S.f_hist[(size_t)f] < TSF_NEWTON_BELOW_T) : spec->algorithm == TSF_ALGO_NEWTON;
-        (nw ? *g_newton : *g_lbfgs).push_back((int32_t)f);
+    OptimiserGroups g;
+    const bool auto_algo = spec.algorithm == TSF_ALGO_AUTO, newton_ok = newton_takes(spec);
+    for (size_t i = 0; i < n; ++i) {
+        const int32_t m = members ? members[i] : (int32_t)i;
+        const bool nw = auto_algo ? (newton_ok && rows[m] < TSF_NEWTON_BELOW_T) : spec.algorithm == TSF_ALGO_NEWTON;
+        (nw ? g.newton : g.lbfgs).push_back(m);
     }
+    return g;
 }
 
-// the views of `sel` whose L-BFGS fit (status in `st`, indexed by view) ended the way pystan raises RuntimeError on
+// the members of `sel` whose L-BFGS fit (status in `st`, indexed by member) ended the way pystan raises RuntimeError on
 static std::vector<int32_t> newton_retry(const std::vector<int32_t> &sel, const std::vector<int32_t> &st)
 {
     std::vector<int32_t> retry;
@@ -3408,6 +3455,28 @@ static std::vector<int32_t> newton_retry(const std::vector<int32_t> &sel, const 
     return retry;
 }
 
+// The rule's launches through fit_group(the launch's spec, its members, which launch): the L-BFGS group, those of it
+// to retry (by the statuses the first launch left in dst, indexed by member), the Newton group; an empty list launches
+// nothing.  `which` lets tsf_tune, which cuts the two groups' panels once for all candidates, tell them from a retry.
+template <class FitGroup>
+static int fit_by_rule(tsf_ctx *ctx, const tsf_spec &spec, const OptimiserGroups &g, const DevFitOut &dst, FitGroup fit_group)
+{
+    tsf_spec sp_l = spec, sp_n = spec;
+    sp_l.algorithm = TSF_ALGO_LBFGS;
+    sp_n.algorithm = TSF_ALGO_NEWTON;
+    if (!g.lbfgs.empty()) {
+        if (int rc = fit_group(sp_l, g.lbfgs, RULE_LBFGS)) return rc;
+        if (spec.algorithm == TSF_ALGO_AUTO && newton_takes(spec)) {
+            std::vector<int32_t> st(dst.n);
+            HIP_TRY(ctx, hipMemcpy(st.data(), dst.status.p, 4 * dst.n, hipMemcpyDeviceToHost));
+            const std::vector<int32_t> retry = newton_retry(g.lbfgs, st);
+            if (!retry.empty())
+                if (int rc = fit_group(sp_n, retry, RULE_RETRY)) return rc;
+        }
+    }
+    return g.newton.empty() ? 0 : fit_group(sp_n, g.newton, RULE_NEWTON);
+}
+
 static int cv_holdout(tsf_ctx *ctx, CvCall &S, const int64_t *series_key, CvHoldout *H)
 {
     const int64_t F = S.F;
@@ -3415,8 +3484,8 @@ static int cv_holdout(tsf_ctx *ctx, CvCall &S, const int64_t *series_key, CvHold
     HIP_TRY(ctx, H->d_fds.alloc(8 * (size_t)F * Hmax));
     if (S.n_extra > 0) HIP_TRY(ctx, H->d_fex.alloc(8 * (size_t)F * S.n_extra * Hmax));
     HIP_TRY(ctx, H->d_fkey.alloc(8 * (size_t)F));
-    if (S.has_floor) { HIP_TRY(ctx, H->d_ffl.alloc(8 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(H->d_ffl.p, S.f_floor.data(), 8 * (size_t)F, hipMemcpyHostToDevice)); }
-    if (S.has_cap) { HIP_TRY(ctx, H->d_fcap.alloc(8 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(H->d_fcap.p, S.f_cap.data(), 8 * (size_t)F, hipMemcpyHostToDevice)); }
+    if (S.has_floor) HIP_TRY(ctx, H->d_ffl.put(S.f_floor.data(), 8 * (size_t)F));
+    if (S.has_cap) HIP_TRY(ctx, H->d_fcap.put(S.f_cap.data(), 8 * (size_t)F));
     hipLaunchKernelGGL(cv_holdout_kernel, dim3((unsigned)(F < 65535 ? F : 65535)), dim3(128), 0, nullptr, S.pn, F, Hmax,
                        S.d_fser.as<int32_t>(), S.d_fc.as<int32_t>(), S.d_fhist.as<int64_t>(), S.d_fhold.as<int64_t>(),
                        series_key ? S.d_key.as<int64_t>() : nullptr, H->d_fds.as<int64_t>(),
@@ -3431,22 +3500,22 @@ static int cv_metrics_setup(tsf_ctx *ctx, CvCall &S, const double *yhat, const d
 {
     const int64_t N = S.N, F = S.F, R = S.R, M = S.M;
     const bool iv = lo != nullptr;
-    HIP_TRY(ctx, X->d_foff.alloc(8 * ((size_t)N + 1))); HIP_TRY(ctx, hipMemcpy(X->d_foff.p, S.fold_off.data(), 8 * ((size_t)N + 1), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, X->d_roff.alloc(8 * ((size_t)N + 1))); HIP_TRY(ctx, hipMemcpy(X->d_roff.p, S.rows_off.data(), 8 * ((size_t)N + 1), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, X->d_moff.alloc(8 * ((size_t)N + 1))); HIP_TRY(ctx, hipMemcpy(X->d_moff.p, S.m_off.data(), 8 * ((size_t)N + 1), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, X->d_fcut.alloc(8 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(X->d_fcut.p, S.f_cut.data(), 8 * (size_t)F, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, X->d_frow0.alloc(8 * (size_t)F)); HIP_TRY(ctx, hipMemcpy(X->d_frow0.p, S.f_row0.data(), 8 * (size_t)F, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, X->d_foff.put(S.fold_off.data(), 8 * ((size_t)N + 1)));
+    HIP_TRY(ctx, X->d_roff.put(S.rows_off.data(), 8 * ((size_t)N + 1)));
+    HIP_TRY(ctx, X->d_moff.put(S.m_off.data(), 8 * ((size_t)N + 1)));
+    HIP_TRY(ctx, X->d_fcut.put(S.f_cut.data(), 8 * (size_t)F));
+    HIP_TRY(ctx, X->d_frow0.put(S.f_row0.data(), 8 * (size_t)F));
     HIP_TRY(ctx, X->d_hs.alloc(8 * (size_t)R)); HIP_TRY(ctx, X->d_ts.alloc(8 * 4 * (size_t)R)); HIP_TRY(ctx, X->d_pre.alloc(8 * 4 * (size_t)(R + 64 * N)));
     HIP_TRY(ctx, X->d_yo.alloc(8 * (size_t)R));
     if (iv) { HIP_TRY(ctx, X->d_loo.alloc(8 * (size_t)R)); HIP_TRY(ctx, X->d_hio.alloc(8 * (size_t)R)); }
     HIP_TRY(ctx, X->d_mh.alloc(8 * (size_t)M)); HIP_TRY(ctx, X->d_mm.alloc(8 * 5 * (size_t)M));
-    HIP_TRY(ctx, X->d_sst.alloc(4 * (size_t)N)); HIP_TRY(ctx, hipMemcpy(X->d_sst.p, S.pst.data(), 4 * (size_t)N, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, X->d_sst.put(S.pst.data(), 4 * (size_t)N));
     CvMetricArgs &ma = X->ma;
     memset(&ma, 0, sizeof(ma));
     ma.p = S.pn; ma.y_dtype = S.y_dtype; ma.N = N; ma.Hmax = S.Hmax;
     ma.fold_off = X->d_foff.as<int64_t>(); ma.rows_off = X->d_roff.as<int64_t>(); ma.m_off = X->d_moff.as<int64_t>();
     ma.cutoff = X->d_fcut.as<int64_t>(); ma.fold_hist = S.d_fhist.as<int64_t>(); ma.fold_hold = S.d_fhold.as<int64_t>();
-    ma.fold_row0 = X->d_frow0.as<int64_t>(); ma.fit_status = S.dfo.status;
+    ma.fold_row0 = X->d_frow0.as<int64_t>(); ma.fit_status = S.fit.status.as<int32_t>();
     ma.yhat = yhat; ma.lo = lo; ma.hi = hi;
     ma.rolling_window = rolling_window;
     ma.h_s = X->d_hs.as<int64_t>(); ma.t_s = X->d_ts.as<double>(); ma.pre = X->d_pre.as<double>(); ma.R = R;
@@ -3462,145 +3531,162 @@ static int calib_run(tsf_ctx *ctx, int64_t N, const int64_t *d_off, const int64_
                      const tsf_calib_table &o, hipStream_t st);
 static int calib_no_table(const tsf_calib_args &a, int64_t N, const tsf_calib_table &t);
 
-// tsf_cross_validate (cal == nullptr: out required) and tsf_calibrate (cal and tab given, checked by the caller: the rule
-// runs on the device's holdout rows behind the metrics, and out may be null: then only the table crosses back)
-static int cross_validate_run(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t T, const int64_t *offsets,
-                              const int64_t *ds, const void *y, int32_t y_dtype, const double *floor_,
-                              const double *cap, const double *extra, const tsf_cv_args *args,
-                              const int64_t *series_key, int32_t n_samples, double interval_width, uint64_t seed,
-                              tsf_cv_out *out, const tsf_calib_args *cal, const tsf_calib_table *tab)
+// what every panel job asks of its panel (max_N: tsf_fit_screened's lists index the series in 32 bits)
+static int check_panel_in(tsf_ctx *ctx, const tsf_spec *spec, const PanelIn &p, int64_t max_N = INT64_MAX)
 {
-    if (!spec || !ds || !y || (!cal && !out) || (out && !out->series_status)) return fail(ctx, "NULL input");
-    if (y_dtype < TSF_Y_F64 || y_dtype > TSF_Y_I32) return fail(ctx, "bad y_dtype");
-    tsf_cv_args a;
-    if (tsf_cv::resolve_args(args, &a)) return fail(ctx, "bad cross-validation arguments (horizon_ns > 0, rolling_window in [0, 1])");
-    if (tsf_cv::check_panel(N, T, offsets, ds))
+    if (p.N > max_N || tsf_cv::check_panel(p.N, p.T, p.offsets, p.ds))
         return fail(ctx, "bad panel (aligned: offsets NULL, 1 <= T <= TSF_MAX_T; ragged: T = 0, offsets[0] = 0, ascending)");
-    if (spec->n_extra > 0 && !extra) return fail(ctx, "extra columns declared but extra is NULL");
-    if (spec->growth == TSF_GROWTH_LOGISTIC && !cap) return fail(ctx, "logistic growth needs cap");
+    if (spec->n_extra > 0 && !p.extra) return fail(ctx, "extra columns declared but extra is NULL");
+    if (spec->growth == TSF_GROWTH_LOGISTIC && !p.cap) return fail(ctx, "logistic growth needs cap");
+    return 0;
+}
+
+// ---- the steps of cross_validate_run -----------------------------------------------------------------------------
+
+// the arguments, before the plan: *a = the cross-validation arguments with their defaults filled in
+static int cv_check_args(tsf_ctx *ctx, const tsf_spec *spec, const PanelIn &p, const tsf_cv_args *args, int32_t n_samples,
+                         double interval_width, const tsf_cv_out *out, const tsf_calib_args *cal, tsf_cv_args *a)
+{
+    if (!spec || !p.ds || !p.y || (!cal && !out) || (out && !out->series_status)) return fail(ctx, "NULL input");
+    if (p.y_dtype < TSF_Y_F64 || p.y_dtype > TSF_Y_I32) return fail(ctx, "bad y_dtype");
+    if (tsf_cv::resolve_args(args, a)) return fail(ctx, "bad cross-validation arguments (horizon_ns > 0, rolling_window in [0, 1])");
+    if (int rc = check_panel_in(ctx, spec, p)) return rc;
     const bool iv = n_samples > 0;
     if (iv && (n_samples < 2 || n_samples > 4096)) return fail(ctx, "n_samples must be 0 or in [2, 4096]");
     if (iv && !(interval_width > 0.0 && interval_width < 1.0)) return fail(ctx, "interval_width must be in (0, 1)");
     if (cal) {
-        if (cal->horizon_ns != a.horizon_ns) return fail(ctx, "tsf_calib_args.horizon_ns must equal the cross-validation's horizon");
+        if (cal->horizon_ns != a->horizon_ns) return fail(ctx, "tsf_calib_args.horizon_ns must equal the cross-validation's horizon");
         if (cal->mode == TSF_CALIB_CQR && !(cal->n_levels == 1 && iv && cal->levels[0] == interval_width))
             return fail(ctx, "TSF_CALIB_CQR needs n_levels == 1, n_samples > 0 and levels[0] == interval_width");
     }
+    return check_algorithm(ctx, spec);
+}
+
+// every fold fitted by the optimiser rule, one launch per group over its fold panel, the outputs in S.fit
+static int cv_fit_folds(tsf_ctx *ctx, CvCall &S, const tsf_spec &spec)
+{
+    const CvViews folds = cv_fold_views(S);
+    const tsf_fit_out dst = S.fit.view();
+    return fit_by_rule(ctx, spec, optimiser_groups(spec, nullptr, (size_t)S.F, S.f_hist.data()), S.fit,
+                       [&](const tsf_spec &gs, const std::vector<int32_t> &gf, RuleLaunch) -> int {
+                           CvGroup E;
+                           if (int rc = cv_expand(ctx, S, folds, gf, &E)) return rc;
+                           return cv_fit(ctx, S, E, gs, dst, &ctx->cv_grids, &ctx->cv_launches);
+                       });
+}
+
+// the holdout rows of every fold predicted in one call (n_samples > 0: with intervals), then the metrics per series
+static int cv_forecast_and_score(tsf_ctx *ctx, CvCall &S, const tsf_spec *spec, const int64_t *series_key, int32_t n_samples,
+                                 double interval_width, uint64_t seed, double rolling_window)
+{
+    const int64_t F = S.F;
+    const int32_t Hmax = S.Hmax;
+    const bool iv = n_samples > 0;
+    const tsf_fit_out fit = S.fit.view();
+    HIP_TRY(ctx, S.d_yh.alloc(8 * (size_t)F * Hmax));
+    if (iv) { HIP_TRY(ctx, S.d_lo.alloc(8 * (size_t)F * Hmax)); HIP_TRY(ctx, S.d_hi.alloc(8 * (size_t)F * Hmax)); }
+    if (int rc = cv_holdout(ctx, S, series_key, &S.hold)) return rc;
+    const CvHoldout &H = S.hold;
+    const double *pfl = S.has_floor ? H.d_ffl.as<double>() : nullptr, *pcap = S.has_cap ? H.d_fcap.as<double>() : nullptr;
+    const double *pex = spec->n_extra > 0 ? H.d_fex.as<double>() : nullptr;
+    const int rc = iv ? tsf_predict_intervals_dev(ctx, spec, F, Hmax, fit.theta, fit.y_scale, fit.grid, (int32_t)F,
+                                                  H.d_fds.as<int64_t>(), 0, pfl, pcap, pex, H.d_fkey.as<int64_t>(), n_samples,
+                                                  interval_width, seed, S.d_yh.as<double>(), S.d_lo.as<double>(),
+                                                  S.d_hi.as<double>(), nullptr)
+                      : tsf_predict_dev(ctx, spec, F, Hmax, fit.theta, fit.y_scale, fit.grid, (int32_t)F, H.d_fds.as<int64_t>(),
+                                        0, pfl, pcap, pex, S.d_yh.as<double>(), nullptr, nullptr);
+    if (rc) return rc;
+    if (int rc2 = cv_metrics_setup(ctx, S, S.d_yh.as<double>(), iv ? S.d_lo.as<double>() : nullptr,
+                                   iv ? S.d_hi.as<double>() : nullptr, rolling_window, &S.met))
+        return rc2;
+    hipLaunchKernelGGL(cv_metrics_kernel, dim3((unsigned)S.N), dim3(64), 0, nullptr, S.met.ma);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+// tsf_calibrate's tail: the rule on the device's own holdout rows -- horizon and y per row, then the table; only it
+// crosses back
+static int cv_calibration_tail(tsf_ctx *ctx, const CvCall &S, bool iv, const tsf_calib_args &cal, const tsf_calib_table &tab)
+{
+    const CvMetrics &X = S.met;
+    const int64_t N = S.N, R = S.R;
+    const int cells = (cal.n_buckets + 1) * cal.n_levels;
+    DevBuf d_rh, d_ry, d_q, d_n, d_cst;
+    HIP_TRY(ctx, d_rh.alloc(8 * (size_t)R)); HIP_TRY(ctx, d_ry.alloc(8 * (size_t)R));
+    HIP_TRY(ctx, d_q.alloc(8 * (size_t)N * cells)); HIP_TRY(ctx, d_n.alloc(4 * (size_t)N * cells)); HIP_TRY(ctx, d_cst.alloc(4 * (size_t)N));
+    hipLaunchKernelGGL(calib_cv_rows_kernel, dim3((unsigned)(N < 65535 ? N : 65535)), dim3(256), 0, nullptr, X.ma,
+                       d_rh.as<int64_t>(), d_ry.as<double>());
+    HIP_TRY(ctx, hipGetLastError());
+    const tsf_calib_table dt{d_q.as<double>(), d_n.as<int32_t>(), d_cst.as<int32_t>()};
+    if (int rc = calib_run(ctx, N, X.d_roff.as<int64_t>(), S.rows_off.data(), d_rh.as<int64_t>(), d_ry.as<double>(),
+                           X.d_yo.as<double>(), iv ? X.d_loo.as<double>() : nullptr, iv ? X.d_hio.as<double>() : nullptr,
+                           cal, dt, nullptr))
+        return rc;
+    hipLaunchKernelGGL(calib_mask_kernel, dim3((unsigned)(N < 65535 ? N : 65535)), dim3(256), 0, nullptr, N, cells,
+                       X.d_sst.as<int32_t>(), dt.q, dt.n, dt.status);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    HIP_TRY(ctx, hipMemcpy(tab.q, d_q.p, 8 * (size_t)N * cells, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(tab.n, d_n.p, 4 * (size_t)N * cells, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(tab.status, d_cst.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the fold fits, the holdout forecasts, the metric rows and the series statuses to the caller's arrays
+static int cv_download(tsf_ctx *ctx, const CvCall &S, bool iv, const tsf_cv_out &out)
+{
+    const CvMetrics &X = S.met;
+    const size_t N = (size_t)S.N, R = (size_t)S.R, M = (size_t)S.M;
+    if (int rc = S.fit.download(ctx, out.fit, S.F)) return rc;
+    HIP_TRY(ctx, hipMemcpy(out.yhat, X.d_yo.p, 8 * R, hipMemcpyDeviceToHost));
+    if (iv) {
+        HIP_TRY(ctx, hipMemcpy(out.yhat_lower, X.d_loo.p, 8 * R, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out.yhat_upper, X.d_hio.p, 8 * R, hipMemcpyDeviceToHost));
+    }
+    if (M > 0) {
+        const double *mm = X.d_mm.as<double>();
+        HIP_TRY(ctx, hipMemcpy(out.horizon_ns, X.d_mh.p, 8 * M, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out.mse, mm, 8 * M, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out.rmse, mm + M, 8 * M, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out.mae, mm + 2 * M, 8 * M, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out.mape, mm + 3 * M, 8 * M, hipMemcpyDeviceToHost));
+        if (iv) HIP_TRY(ctx, hipMemcpy(out.coverage, mm + 4 * M, 8 * M, hipMemcpyDeviceToHost));
+    }
+    HIP_TRY(ctx, hipMemcpy(out.series_status, X.d_sst.p, 4 * N, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// tsf_cross_validate (cal == nullptr: out required) and tsf_calibrate (cal and tab given, checked by the caller: the rule
+// runs on the device's holdout rows behind the metrics, and out may be null: then only the table crosses back)
+static int cross_validate_run(tsf_ctx *ctx, const tsf_spec *spec, const PanelIn &p, const tsf_cv_args *args,
+                              const int64_t *series_key, int32_t n_samples, double interval_width, uint64_t seed,
+                              tsf_cv_out *out, const tsf_calib_args *cal, const tsf_calib_table *tab)
+{
+    tsf_cv_args a;
+    if (int rc = cv_check_args(ctx, spec, p, args, n_samples, interval_width, out, cal, &a)) return rc;
+    const bool iv = n_samples > 0;
     ctx->order_n = 0;                   // (pending cost hints were meant for a fit call)
     ctx->cv_grids = 0;
     ctx->cv_launches = 0;
     CvCall S;
-    cv_plan_call(N, T, offsets, ds, a, spec, y_dtype, floor_, cap, &S);
-    const int64_t F = S.F, R = S.R, M = S.M;
-    if (out) memcpy(out->series_status, S.pst.data(), sizeof(int32_t) * (size_t)N);
-    if (F == 0) return cal ? calib_no_table(*cal, N, *tab) : 0;
+    cv_plan_call(p, a, spec, &S);
+    if (out) memcpy(out->series_status, S.pst.data(), sizeof(int32_t) * (size_t)p.N);
+    if (S.F == 0) return cal ? calib_no_table(*cal, p.N, *tab) : 0;
     if (out) {
-        const tsf_fit_out &fo = out->fit;
-        if (!fo.theta || !fo.y_scale || !fo.fval || !fo.status || !fo.n_iter || !fo.n_eval || !fo.grid)
-            return fail(ctx, "tsf_cv_out.fit has NULL members");
+        if (!fit_out_complete(out->fit)) return fail(ctx, "tsf_cv_out.fit has NULL members");
         if (!out->yhat || !out->horizon_ns || !out->mse || !out->rmse || !out->mae || !out->mape ||
             (iv && (!out->yhat_lower || !out->yhat_upper || !out->coverage)))
             return fail(ctx, "tsf_cv_out has NULL members");
     }
-    if (int rc = cv_upload(ctx, y, floor_, cap, extra, series_key, &S)) return rc;
-    const int stride = S.stride;
-    const int32_t Hmax = S.Hmax;
-    const tsf_fit_out &dfo = S.dfo;
-    const CvViews folds = cv_fold_views(S);
-    // one fit launch over the folds gf (plan indices)
-    auto fit_group = [&](const tsf_spec &gs, const std::vector<int32_t> &gf) -> int {
-        CvGroup E;
-        if (int rc = cv_expand(ctx, S, folds, gf, &E)) return rc;
-        return cv_fit(ctx, S, E, gs, dfo, &ctx->cv_grids, &ctx->cv_launches);
-    };
-    // fbprophet's optimiser choice per fold (include/tsf.h)
-    tsf_spec sp_l = *spec, sp_n = *spec;
-    sp_l.algorithm = TSF_ALGO_LBFGS;
-    sp_n.algorithm = TSF_ALGO_NEWTON;
-    const bool auto_algo = spec->algorithm == TSF_ALGO_AUTO;
-    const bool newton_ok = 3 + spec->n_changepoints + tsf_spec_K(spec) <= TSF_MAX_P;
-    std::vector<int32_t> g_newton, g_lbfgs;
-    cv_optimiser_groups(S, spec, &g_lbfgs, &g_newton);
-    if (int rc = fit_group(sp_l, g_lbfgs)) return rc;
-    if (auto_algo && newton_ok && !g_lbfgs.empty()) {
-        std::vector<int32_t> st((size_t)F);
-        HIP_TRY(ctx, hipMemcpy(st.data(), S.d_st.p, 4 * (size_t)F, hipMemcpyDeviceToHost));
-        if (int rc = fit_group(sp_n, newton_retry(g_lbfgs, st))) return rc;
-    }
-    if (int rc = fit_group(sp_n, g_newton)) return rc;
-    // the holdout rows of every fold, predicted in one call
-    CvHoldout H;
-    DevBuf d_yh, d_lo, d_hi;
-    HIP_TRY(ctx, d_yh.alloc(8 * (size_t)F * Hmax));
-    if (iv) { HIP_TRY(ctx, d_lo.alloc(8 * (size_t)F * Hmax)); HIP_TRY(ctx, d_hi.alloc(8 * (size_t)F * Hmax)); }
-    if (int rc = cv_holdout(ctx, S, series_key, &H)) return rc;
-    {
-        const double *pfl = floor_ ? H.d_ffl.as<double>() : nullptr, *pcap = cap ? H.d_fcap.as<double>() : nullptr;
-        const double *pex = spec->n_extra > 0 ? H.d_fex.as<double>() : nullptr;
-        const int rc = iv ? tsf_predict_intervals_dev(ctx, spec, F, Hmax, dfo.theta, dfo.y_scale, dfo.grid, (int32_t)F,
-                                                      H.d_fds.as<int64_t>(), 0, pfl, pcap, pex, H.d_fkey.as<int64_t>(), n_samples,
-                                                      interval_width, seed, d_yh.as<double>(), d_lo.as<double>(),
-                                                      d_hi.as<double>(), nullptr)
-                          : tsf_predict_dev(ctx, spec, F, Hmax, dfo.theta, dfo.y_scale, dfo.grid, (int32_t)F, H.d_fds.as<int64_t>(),
-                                            0, pfl, pcap, pex, d_yh.as<double>(), nullptr, nullptr);
-        if (rc) return rc;
-    }
-    // metrics per series
-    CvMetrics X;
-    if (int rc = cv_metrics_setup(ctx, S, d_yh.as<double>(), iv ? d_lo.as<double>() : nullptr, iv ? d_hi.as<double>() : nullptr,
-                                  a.rolling_window, &X))
-        return rc;
-    hipLaunchKernelGGL(cv_metrics_kernel, dim3((unsigned)N), dim3(64), 0, nullptr, X.ma);
-    HIP_TRY(ctx, hipGetLastError());
+    if (int rc = cv_upload(ctx, series_key, &S)) return rc;
+    if (int rc = cv_fit_folds(ctx, S, *spec)) return rc;
+    if (int rc = cv_forecast_and_score(ctx, S, spec, series_key, n_samples, interval_width, seed, a.rolling_window)) return rc;
     if (cal) {
-        // the rule on the device's own holdout rows: horizon and y per row, then the table; only it crosses back
-        const int cells = (cal->n_buckets + 1) * cal->n_levels;
-        DevBuf d_rh, d_ry, d_q, d_n, d_cst;
-        HIP_TRY(ctx, d_rh.alloc(8 * (size_t)R)); HIP_TRY(ctx, d_ry.alloc(8 * (size_t)R));
-        HIP_TRY(ctx, d_q.alloc(8 * (size_t)N * cells)); HIP_TRY(ctx, d_n.alloc(4 * (size_t)N * cells)); HIP_TRY(ctx, d_cst.alloc(4 * (size_t)N));
-        hipLaunchKernelGGL(calib_cv_rows_kernel, dim3((unsigned)(N < 65535 ? N : 65535)), dim3(256), 0, nullptr, X.ma,
-                           d_rh.as<int64_t>(), d_ry.as<double>());
-        HIP_TRY(ctx, hipGetLastError());
-        const tsf_calib_table dt{d_q.as<double>(), d_n.as<int32_t>(), d_cst.as<int32_t>()};
-        if (int rc = calib_run(ctx, N, X.d_roff.as<int64_t>(), S.rows_off.data(), d_rh.as<int64_t>(), d_ry.as<double>(),
-                               X.d_yo.as<double>(), iv ? X.d_loo.as<double>() : nullptr, iv ? X.d_hio.as<double>() : nullptr,
-                               *cal, dt, nullptr))
-            return rc;
-        hipLaunchKernelGGL(calib_mask_kernel, dim3((unsigned)(N < 65535 ? N : 65535)), dim3(256), 0, nullptr, N, cells,
-                           X.d_sst.as<int32_t>(), dt.q, dt.n, dt.status);
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipDeviceSynchronize());
-        HIP_TRY(ctx, hipMemcpy(tab->q, d_q.p, 8 * (size_t)N * cells, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(tab->n, d_n.p, 4 * (size_t)N * cells, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(tab->status, d_cst.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+        if (int rc = cv_calibration_tail(ctx, S, iv, *cal, *tab)) return rc;
         if (!out) return 0;
     }
     HIP_TRY(ctx, hipDeviceSynchronize());
-    // outputs
-    const tsf_fit_out &fo = out->fit;
-    HIP_TRY(ctx, hipMemcpy(fo.theta, S.d_th.p, 8 * (size_t)F * stride, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(fo.y_scale, S.d_ys.p, 8 * (size_t)F, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(fo.fval, S.d_fv.p, 8 * (size_t)F, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(fo.status, S.d_st.p, 4 * (size_t)F, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(fo.n_iter, S.d_it.p, 4 * (size_t)F, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(fo.n_eval, S.d_ev.p, 4 * (size_t)F, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(fo.grid, S.d_gr.p, sizeof(tsf_grid_info) * (size_t)F, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(out->yhat, X.d_yo.p, 8 * (size_t)R, hipMemcpyDeviceToHost));
-    if (iv) {
-        HIP_TRY(ctx, hipMemcpy(out->yhat_lower, X.d_loo.p, 8 * (size_t)R, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(out->yhat_upper, X.d_hio.p, 8 * (size_t)R, hipMemcpyDeviceToHost));
-    }
-    if (M > 0) {
-        const double *mm = X.d_mm.as<double>();
-        HIP_TRY(ctx, hipMemcpy(out->horizon_ns, X.d_mh.p, 8 * (size_t)M, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(out->mse, mm, 8 * (size_t)M, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(out->rmse, mm + M, 8 * (size_t)M, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(out->mae, mm + 2 * M, 8 * (size_t)M, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(out->mape, mm + 3 * M, 8 * (size_t)M, hipMemcpyDeviceToHost));
-        if (iv) HIP_TRY(ctx, hipMemcpy(out->coverage, mm + 4 * M, 8 * (size_t)M, hipMemcpyDeviceToHost));
-    }
-    HIP_TRY(ctx, hipMemcpy(out->series_status, X.d_sst.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
-    return 0;
+    return cv_download(ctx, S, iv, *out);
 }
 
 extern "C" int tsf_cross_validate(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t T, const int64_t *offsets,
@@ -3611,9 +3697,33 @@ extern "C" int tsf_cross_validate(tsf_ctx *ctx, const tsf_spec *spec, int64_t N,
 {
     if (!ctx) return -1;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return cross_validate_run(ctx, spec, N, T, offsets, ds, y, y_dtype, floor_, cap, extra, args, series_key, n_samples,
-                              interval_width, seed, out, nullptr, nullptr);
+    return cross_validate_run(ctx, spec, PanelIn{N, T, offsets, ds, y, y_dtype, floor_, cap, extra}, args, series_key,
+                              n_samples, interval_width, seed, out, nullptr, nullptr);
 }
+
+// The identity views of an uploaded panel -- view n = every row of series n -- for the launches that fit whole
+// histories (tsf_tune's refit, tsf_fit_screened's first fit).
+struct WholeViews {
+    std::vector<int32_t> ident;
+    std::vector<int64_t> len;           // rows per series
+    int64_t max_len = 0;
+    DevBuf d_ident;                     // (ragged panels: cv_expand_kernel reads it; an aligned panel is gathered by rows)
+
+    int build(tsf_ctx *ctx, const CvCall &S)
+    {
+        const size_t N = (size_t)S.N;
+        ident.resize(N);
+        len.resize(N);
+        for (size_t n = 0; n < N; ++n) {
+            ident[n] = (int32_t)n;
+            len[n] = S.aligned ? S.T : S.offsets[n + 1] - S.offsets[n];
+            if (len[n] > max_len) max_len = len[n];
+        }
+        if (!S.aligned) HIP_TRY(ctx, d_ident.put(ident.data(), 4 * N));
+        return 0;
+    }
+    CvViews views() const { return CvViews{d_ident.as<int32_t>(), ident.data(), len.data(), nullptr, 0, nullptr}; }
+};
 
 // One fit launch over the whole histories of the series sel of an uploaded panel with spec gs, its outputs put at the
 // series' positions of dst (tsf_tune's refit, tsf_fit_screened's first fit): aligned, the series' rows gathered into a
@@ -3631,8 +3741,8 @@ static int fit_whole_group(tsf_ctx *ctx, CvCall &S, const CvViews &whole, const 
     }
     const int32_t T = S.T;
     const int stride = S.stride;
-    DevBuf d_sel, d_gy, d_gfl, d_gcap, g_th, g_ys, g_fv, g_st, g_it, g_ev, g_gr;
-    HIP_TRY(ctx, d_sel.alloc(4 * (size_t)G)); HIP_TRY(ctx, hipMemcpy(d_sel.p, sel.data(), 4 * (size_t)G, hipMemcpyHostToDevice));
+    DevBuf d_sel, d_gy, d_gfl, d_gcap;
+    HIP_TRY(ctx, d_sel.put(sel.data(), 4 * (size_t)G));
     HIP_TRY(ctx, d_gy.alloc(S.ysz * (size_t)G * T));
     if (S.has_floor) HIP_TRY(ctx, d_gfl.alloc(8 * (size_t)G));
     if (S.has_cap) HIP_TRY(ctx, d_gcap.alloc(8 * (size_t)G));
@@ -3640,15 +3750,9 @@ static int fit_whole_group(tsf_ctx *ctx, CvCall &S, const CvViews &whole, const 
                        d_sel.as<int32_t>(), S.has_floor ? S.d_fl.as<double>() : nullptr, S.has_cap ? S.d_cap.as<double>() : nullptr,
                        d_gy.p, S.has_floor ? d_gfl.as<double>() : nullptr, S.has_cap ? d_gcap.as<double>() : nullptr);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, g_th.alloc(8 * (size_t)G * stride)); HIP_TRY(ctx, g_ys.alloc(8 * (size_t)G)); HIP_TRY(ctx, g_fv.alloc(8 * (size_t)G));
-    HIP_TRY(ctx, g_st.alloc(4 * (size_t)G)); HIP_TRY(ctx, g_it.alloc(4 * (size_t)G)); HIP_TRY(ctx, g_ev.alloc(4 * (size_t)G));
-    HIP_TRY(ctx, g_gr.alloc(sizeof(tsf_grid_info)));
-    HIP_TRY(ctx, hipMemset(g_st.p, 0, 4 * (size_t)G)); HIP_TRY(ctx, hipMemset(g_it.p, 0, 4 * (size_t)G));
-    HIP_TRY(ctx, hipMemset(g_ev.p, 0, 4 * (size_t)G)); HIP_TRY(ctx, hipMemset(g_gr.p, 0, sizeof(tsf_grid_info)));
-    tsf_fit_out go;
-    go.theta = g_th.as<double>(); go.y_scale = g_ys.as<double>(); go.fval = g_fv.as<double>();
-    go.status = g_st.as<int32_t>(); go.n_iter = g_it.as<int32_t>(); go.n_eval = g_ev.as<int32_t>();
-    go.grid = g_gr.as<tsf_grid_info>();
+    DevFitOut launch;
+    if (int rc = launch.alloc(ctx, G, stride, 1, FIT_OUT_LAUNCH)) return rc;
+    tsf_fit_out go = launch.view();
     FitCall c = {};
     c.N = G; c.aligned = 1; c.T = T; c.max_T = T;
     c.ds = S.d_ds.as<int64_t>(); c.y = d_gy.p; c.y_dtype = S.y_dtype;
@@ -3706,6 +3810,133 @@ static bool prior_scales_ok(const tsf_spec &s)
     return true;
 }
 
+// ---- the steps of tsf_tune ------------------------------------------------------------------------------------------
+
+// *a = the cross-validation arguments with their defaults filled in and one metric row per series
+static int tune_check_args(tsf_ctx *ctx, const tsf_spec *base, const tsf_spec *cand, int32_t C, const PanelIn &p,
+                           const tsf_cv_args *cv, int32_t metric, int32_t refit, const tsf_tune_out *out, tsf_cv_args *a)
+{
+    if (!base || !cand || !p.ds || !p.y || !out || !out->score || !out->cand_status || !out->best || !out->series_status)
+        return fail(ctx, "NULL input");
+    if (C < 1 || C > TSF_TUNE_MAX_CAND) return fail(ctx, "C must be in [1, TSF_TUNE_MAX_CAND]");
+    if (metric < TSF_TUNE_MSE || metric > TSF_TUNE_MAPE) return fail(ctx, "bad metric (TSF_TUNE_MSE .. TSF_TUNE_MAPE)");
+    if (refit != 0 && refit != 1) return fail(ctx, "refit must be 0 or 1");
+    if (p.y_dtype < TSF_Y_F64 || p.y_dtype > TSF_Y_I32) return fail(ctx, "bad y_dtype");
+    if (!cv) return fail(ctx, "cv is NULL");
+    tsf_cv_args cv1 = *cv;
+    cv1.rolling_window = 1.0;           // one metric row per series, over all its holdout rows
+    if (tsf_cv::resolve_args(&cv1, a)) return fail(ctx, "bad cross-validation arguments (horizon_ns > 0)");
+    if (int rc = check_panel_in(ctx, base, p)) return rc;
+    if (!prior_scales_ok(*base)) return fail(ctx, "base: prior scales must be finite and > 0");
+    for (int32_t c = 0; c < C; ++c) {
+        if (!same_but_prior_scales(*base, cand[c]))
+            return fail(ctx, "a candidate differs from base in more than its prior scales");
+        if (!prior_scales_ok(cand[c])) return fail(ctx, "a candidate's prior scales must be finite and > 0");
+    }
+    if (refit && !fit_out_complete(out->fit)) return fail(ctx, "tsf_tune_out.fit has NULL members");
+    return check_algorithm(ctx, base);      // (the candidates' is base's)
+}
+
+struct TuneScores {             // [N][C] scores and statuses, the plan's statuses, the choice and the series statuses
+    DevBuf d_score, d_cst, d_pst, d_best, d_sstat;
+};
+
+// every candidate cross-validated: shared by all of them the holdout rows, the metric tables and the fold panel of
+// the rule's L-BFGS and Newton group; per candidate the fits, one predict, the metrics and its column of the scores
+static int tune_score_candidates(tsf_ctx *ctx, CvCall &S, const tsf_spec *base, const tsf_spec *cand, int32_t C, int32_t metric,
+                                 double rolling_window, TuneScores *B)
+{
+    const int64_t N = S.N, F = S.F;
+    if (F == 0) {                       // no series has a fold: every score NaN, every status the plan's
+        const size_t NC = (size_t)N * C;
+        std::vector<double> sc(NC, std::nan(""));
+        std::vector<int32_t> cs(NC);
+        for (size_t i = 0; i < NC; ++i) cs[i] = S.pst[i / C];
+        HIP_TRY(ctx, hipMemcpy(B->d_score.p, sc.data(), 8 * NC, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(B->d_cst.p, cs.data(), 4 * NC, hipMemcpyHostToDevice));
+        return 0;
+    }
+    int64_t grids = 0;                  // (not reported)
+    CvHoldout &H = S.hold;
+    CvMetrics &X = S.met;
+    HIP_TRY(ctx, S.d_yh.alloc(8 * (size_t)F * S.Hmax));
+    if (int rc = cv_holdout(ctx, S, nullptr, &H)) return rc;
+    if (int rc = cv_metrics_setup(ctx, S, S.d_yh.as<double>(), nullptr, nullptr, rolling_window, &X)) return rc;
+    const double *mval = X.d_mm.as<double>() + (size_t)metric * S.M;
+    const CvViews folds = cv_fold_views(S);
+    const tsf_fit_out fit = S.fit.view();
+    const OptimiserGroups g = optimiser_groups(*base, nullptr, (size_t)F, S.f_hist.data());
+    CvGroup E_l, E_n;
+    if (int rc = cv_expand(ctx, S, folds, g.lbfgs, &E_l)) return rc;
+    if (int rc = cv_expand(ctx, S, folds, g.newton, &E_n)) return rc;
+    ctx->tune_expand += (E_l.G > 0) + (E_n.G > 0);
+    auto fit_group = [&](const tsf_spec &gs, const std::vector<int32_t> &gf, RuleLaunch which) -> int {
+        if (which != RULE_RETRY) return cv_fit(ctx, S, which == RULE_LBFGS ? E_l : E_n, gs, fit, &grids, &ctx->tune_fits);
+        CvGroup E_r;
+        if (int rc = cv_expand(ctx, S, folds, gf, &E_r)) return rc;
+        ctx->tune_expand += 1;
+        return cv_fit(ctx, S, E_r, gs, fit, &grids, &ctx->tune_fits);
+    };
+    const double *pfl = S.has_floor ? H.d_ffl.as<double>() : nullptr, *pcap = S.has_cap ? H.d_fcap.as<double>() : nullptr;
+    const double *pex = S.n_extra > 0 ? H.d_fex.as<double>() : nullptr;
+    for (int32_t c = 0; c < C; ++c) {
+        if (int rc = fit_by_rule(ctx, cand[c], g, S.fit, fit_group)) return rc;
+        if (int rc = tsf_predict_dev(ctx, &cand[c], F, S.Hmax, fit.theta, fit.y_scale, fit.grid, (int32_t)F,
+                                     H.d_fds.as<int64_t>(), 0, pfl, pcap, pex, S.d_yh.as<double>(), nullptr, nullptr))
+            return rc;
+        HIP_TRY(ctx, hipMemcpy(X.d_sst.p, S.pst.data(), 4 * (size_t)N, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(cv_metrics_kernel, dim3((unsigned)N), dim3(64), 0, nullptr, X.ma);
+        HIP_TRY(ctx, hipGetLastError());
+        hipLaunchKernelGGL(tune_score_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, nullptr, N, C, c, mval,
+                           X.d_moff.as<int64_t>(), X.d_sst.as<int32_t>(), B->d_score.as<double>(), B->d_cst.as<int32_t>());
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return 0;
+}
+
+// the choice per series, then scores, statuses and choices to the caller
+static int tune_select(tsf_ctx *ctx, int64_t N, int32_t C, const TuneScores &B, const tsf_tune_out &out)
+{
+    const size_t NC = (size_t)N * C;
+    hipLaunchKernelGGL(tune_select_kernel, dim3((unsigned)((N + TUNE_SELECT_WAVES - 1) / TUNE_SELECT_WAVES)),
+                       dim3(TUNE_SELECT_WAVES * 64), 0, nullptr, N, C, B.d_score.as<double>(), B.d_pst.as<int32_t>(),
+                       B.d_best.as<int32_t>(), B.d_sstat.as<int32_t>());
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    HIP_TRY(ctx, hipMemcpy(out.score, B.d_score.p, 8 * NC, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(out.cand_status, B.d_cst.p, 4 * NC, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(out.best, B.d_best.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(out.series_status, B.d_sstat.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// every series fitted on its whole history with its choice best[n] (base for -1): per choice the rule's launches
+static int tune_refit(tsf_ctx *ctx, CvCall &S, const tsf_spec *base, const tsf_spec *cand, int32_t C, const int32_t *best,
+                      const tsf_fit_out &out)
+{
+    const int64_t N = S.N, n_grids = S.aligned ? 1 : N;
+    int64_t grids = 0;                  // (not reported)
+    DevFitOut refit;
+    if (int rc = refit.alloc(ctx, N, S.stride, n_grids, FIT_OUT_UNFITTED)) return rc;
+    const tsf_fit_out dst = refit.view();
+    WholeViews W;
+    if (int rc = W.build(ctx, S)) return rc;
+    const CvViews whole = W.views();
+    auto fit_group = [&](const tsf_spec &gs, const std::vector<int32_t> &sel, RuleLaunch) -> int {
+        return fit_whole_group(ctx, S, whole, gs, sel, dst, &grids, &ctx->tune_fits);
+    };
+    for (int32_t b = -1; b < C; ++b) {
+        const tsf_spec &gs = b < 0 ? *base : cand[b];
+        std::vector<int32_t> members;
+        for (int64_t n = 0; n < N; ++n)
+            if (best[n] == b && W.len[(size_t)n] > 0) members.push_back((int32_t)n);
+        const OptimiserGroups g = optimiser_groups(gs, members.data(), members.size(), W.len.data());
+        if (int rc = fit_by_rule(ctx, gs, g, refit, fit_group)) return rc;
+    }
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    return refit.download(ctx, out, n_grids);
+}
+
 extern "C" int tsf_tune(tsf_ctx *ctx, const tsf_spec *base, const tsf_spec *cand, int32_t C, int64_t N, int32_t T,
                         const int64_t *offsets, const int64_t *ds, const void *y, int32_t y_dtype, const double *floor_,
                         const double *cap, const double *extra, const tsf_cv_args *cv, int32_t metric, int32_t refit,
@@ -3713,162 +3944,23 @@ extern "C" int tsf_tune(tsf_ctx *ctx, const tsf_spec *base, const tsf_spec *cand
 {
     if (!ctx) return -1;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!base || !cand || !ds || !y || !out || !out->score || !out->cand_status || !out->best || !out->series_status)
-        return fail(ctx, "NULL input");
-    if (C < 1 || C > TSF_TUNE_MAX_CAND) return fail(ctx, "C must be in [1, TSF_TUNE_MAX_CAND]");
-    if (metric < TSF_TUNE_MSE || metric > TSF_TUNE_MAPE) return fail(ctx, "bad metric (TSF_TUNE_MSE .. TSF_TUNE_MAPE)");
-    if (refit != 0 && refit != 1) return fail(ctx, "refit must be 0 or 1");
-    if (y_dtype < TSF_Y_F64 || y_dtype > TSF_Y_I32) return fail(ctx, "bad y_dtype");
+    const PanelIn p{N, T, offsets, ds, y, y_dtype, floor_, cap, extra};
     tsf_cv_args a;
-    if (!cv) return fail(ctx, "cv is NULL");
-    tsf_cv_args cv1 = *cv;
-    cv1.rolling_window = 1.0;           // one metric row per series, over all its holdout rows
-    if (tsf_cv::resolve_args(&cv1, &a)) return fail(ctx, "bad cross-validation arguments (horizon_ns > 0)");
-    if (tsf_cv::check_panel(N, T, offsets, ds))
-        return fail(ctx, "bad panel (aligned: offsets NULL, 1 <= T <= TSF_MAX_T; ragged: T = 0, offsets[0] = 0, ascending)");
-    if (base->n_extra > 0 && !extra) return fail(ctx, "extra columns declared but extra is NULL");
-    if (base->growth == TSF_GROWTH_LOGISTIC && !cap) return fail(ctx, "logistic growth needs cap");
-    if (!prior_scales_ok(*base)) return fail(ctx, "base: prior scales must be finite and > 0");
-    for (int32_t c = 0; c < C; ++c) {
-        if (!same_but_prior_scales(*base, cand[c]))
-            return fail(ctx, "a candidate differs from base in more than its prior scales");
-        if (!prior_scales_ok(cand[c])) return fail(ctx, "a candidate's prior scales must be finite and > 0");
-    }
-    const tsf_fit_out &fo = out->fit;
-    if (refit && (!fo.theta || !fo.y_scale || !fo.fval || !fo.status || !fo.n_iter || !fo.n_eval || !fo.grid))
-        return fail(ctx, "tsf_tune_out.fit has NULL members");
+    if (int rc = tune_check_args(ctx, base, cand, C, p, cv, metric, refit, out, &a)) return rc;
     ctx->order_n = 0;                   // (pending cost hints were meant for a fit call)
     ctx->tune_expand = 0;
     ctx->tune_fits = 0;
     CvCall S;
-    cv_plan_call(N, T, offsets, ds, a, base, y_dtype, floor_, cap, &S);
-    const int64_t F = S.F, M = S.M, NC = N * (int64_t)C;
-    if (int rc = cv_upload(ctx, y, floor_, cap, extra, nullptr, &S)) return rc;
-    const int stride = S.stride;
-    int64_t grids = 0;                  // (not reported)
-    DevBuf d_score, d_cst, d_pst, d_best, d_sstat;
-    HIP_TRY(ctx, d_score.alloc(8 * (size_t)NC)); HIP_TRY(ctx, d_cst.alloc(4 * (size_t)NC));
-    HIP_TRY(ctx, d_pst.alloc(4 * (size_t)N)); HIP_TRY(ctx, hipMemcpy(d_pst.p, S.pst.data(), 4 * (size_t)N, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_best.alloc(4 * (size_t)N)); HIP_TRY(ctx, d_sstat.alloc(4 * (size_t)N));
-    if (F == 0) {                       // no series has a fold: every score NaN, every status the plan's
-        std::vector<double> sc((size_t)NC, std::nan(""));
-        std::vector<int32_t> cs((size_t)NC);
-        for (int64_t i = 0; i < NC; ++i) cs[(size_t)i] = S.pst[(size_t)(i / C)];
-        HIP_TRY(ctx, hipMemcpy(d_score.p, sc.data(), 8 * (size_t)NC, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(d_cst.p, cs.data(), 4 * (size_t)NC, hipMemcpyHostToDevice));
-    } else {
-        // shared by every candidate: the holdout rows, the metric tables, the fold panel of each optimiser group
-        CvHoldout H;
-        DevBuf d_yh;
-        HIP_TRY(ctx, d_yh.alloc(8 * (size_t)F * S.Hmax));
-        if (int rc = cv_holdout(ctx, S, nullptr, &H)) return rc;
-        CvMetrics X;
-        if (int rc = cv_metrics_setup(ctx, S, d_yh.as<double>(), nullptr, nullptr, a.rolling_window, &X)) return rc;
-        const double *mval = X.d_mm.as<double>() + (size_t)metric * M;
-        const CvViews folds = cv_fold_views(S);
-        std::vector<int32_t> g_newton, g_lbfgs;
-        cv_optimiser_groups(S, base, &g_lbfgs, &g_newton);
-        CvGroup E_l, E_n;
-        if (int rc = cv_expand(ctx, S, folds, g_lbfgs, &E_l)) return rc;
-        if (int rc = cv_expand(ctx, S, folds, g_newton, &E_n)) return rc;
-        ctx->tune_expand += (E_l.G > 0) + (E_n.G > 0);
-        const bool auto_algo = base->algorithm == TSF_ALGO_AUTO;
-        const bool newton_ok = 3 + base->n_changepoints + tsf_spec_K(base) <= TSF_MAX_P;
-        std::vector<int32_t> st((size_t)F);
-        for (int32_t c = 0; c < C; ++c) {
-            tsf_spec sp_l = cand[c], sp_n = cand[c];
-            sp_l.algorithm = TSF_ALGO_LBFGS;
-            sp_n.algorithm = TSF_ALGO_NEWTON;
-            if (int rc = cv_fit(ctx, S, E_l, sp_l, S.dfo, &grids, &ctx->tune_fits)) return rc;
-            if (auto_algo && newton_ok && E_l.G > 0) {
-                HIP_TRY(ctx, hipMemcpy(st.data(), S.d_st.p, 4 * (size_t)F, hipMemcpyDeviceToHost));
-                CvGroup E_r;
-                if (int rc = cv_expand(ctx, S, folds, newton_retry(g_lbfgs, st), &E_r)) return rc;
-                ctx->tune_expand += E_r.G > 0;
-                if (int rc = cv_fit(ctx, S, E_r, sp_n, S.dfo, &grids, &ctx->tune_fits)) return rc;
-            }
-            if (int rc = cv_fit(ctx, S, E_n, sp_n, S.dfo, &grids, &ctx->tune_fits)) return rc;
-            const double *pfl = floor_ ? H.d_ffl.as<double>() : nullptr, *pcap = cap ? H.d_fcap.as<double>() : nullptr;
-            const double *pex = base->n_extra > 0 ? H.d_fex.as<double>() : nullptr;
-            if (int rc = tsf_predict_dev(ctx, &cand[c], F, S.Hmax, S.dfo.theta, S.dfo.y_scale, S.dfo.grid, (int32_t)F,
-                                         H.d_fds.as<int64_t>(), 0, pfl, pcap, pex, d_yh.as<double>(), nullptr, nullptr))
-                return rc;
-            HIP_TRY(ctx, hipMemcpy(X.d_sst.p, S.pst.data(), 4 * (size_t)N, hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(cv_metrics_kernel, dim3((unsigned)N), dim3(64), 0, nullptr, X.ma);
-            HIP_TRY(ctx, hipGetLastError());
-            hipLaunchKernelGGL(tune_score_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, nullptr, N, C, c, mval,
-                               X.d_moff.as<int64_t>(), X.d_sst.as<int32_t>(), d_score.as<double>(), d_cst.as<int32_t>());
-            HIP_TRY(ctx, hipGetLastError());
-        }
-    }
-    hipLaunchKernelGGL(tune_select_kernel, dim3((unsigned)((N + TUNE_SELECT_WAVES - 1) / TUNE_SELECT_WAVES)),
-                       dim3(TUNE_SELECT_WAVES * 64), 0, nullptr, N, C, d_score.as<double>(), d_pst.as<int32_t>(),
-                       d_best.as<int32_t>(), d_sstat.as<int32_t>());
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    HIP_TRY(ctx, hipMemcpy(out->score, d_score.p, 8 * (size_t)NC, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(out->cand_status, d_cst.p, 4 * (size_t)NC, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(out->best, d_best.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(out->series_status, d_sstat.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
-    if (!refit) return 0;
-    // ---- refit: one group per distinct choice (base for best = -1), per optimiser
-    const bool aligned = S.aligned;
-    const int64_t n_grids = aligned ? 1 : N;
-    DevBuf r_th, r_ys, r_fv, r_st, r_it, r_ev, r_gr;
-    HIP_TRY(ctx, r_th.alloc(8 * (size_t)N * stride)); HIP_TRY(ctx, r_ys.alloc(8 * (size_t)N)); HIP_TRY(ctx, r_fv.alloc(8 * (size_t)N));
-    HIP_TRY(ctx, r_st.alloc(4 * (size_t)N)); HIP_TRY(ctx, r_it.alloc(4 * (size_t)N)); HIP_TRY(ctx, r_ev.alloc(4 * (size_t)N));
-    HIP_TRY(ctx, r_gr.alloc(sizeof(tsf_grid_info) * (size_t)n_grids));
-    HIP_TRY(ctx, hipMemset(r_th.p, 0, 8 * (size_t)N * stride)); HIP_TRY(ctx, hipMemset(r_ys.p, 0, 8 * (size_t)N));
-    HIP_TRY(ctx, hipMemset(r_fv.p, 0, 8 * (size_t)N)); HIP_TRY(ctx, hipMemset(r_it.p, 0, 4 * (size_t)N));
-    HIP_TRY(ctx, hipMemset(r_ev.p, 0, 4 * (size_t)N)); HIP_TRY(ctx, hipMemset(r_gr.p, 0, sizeof(tsf_grid_info) * (size_t)n_grids));
-    std::vector<int32_t> rst((size_t)N, TSF_ST_TOO_FEW);      // (a ragged series without rows is not fitted)
-    HIP_TRY(ctx, hipMemcpy(r_st.p, rst.data(), 4 * (size_t)N, hipMemcpyHostToDevice));
-    tsf_fit_out rfo;
-    rfo.theta = r_th.as<double>(); rfo.y_scale = r_ys.as<double>(); rfo.fval = r_fv.as<double>();
-    rfo.status = r_st.as<int32_t>(); rfo.n_iter = r_it.as<int32_t>(); rfo.n_eval = r_ev.as<int32_t>();
-    rfo.grid = r_gr.as<tsf_grid_info>();
-    std::vector<int32_t> ident((size_t)N);
-    std::vector<int64_t> len((size_t)N);
-    for (int64_t n = 0; n < N; ++n) { ident[(size_t)n] = (int32_t)n; len[(size_t)n] = aligned ? T : offsets[n + 1] - offsets[n]; }
-    DevBuf d_ident;
-    if (!aligned) { HIP_TRY(ctx, d_ident.alloc(4 * (size_t)N)); HIP_TRY(ctx, hipMemcpy(d_ident.p, ident.data(), 4 * (size_t)N, hipMemcpyHostToDevice)); }
-    const CvViews whole{d_ident.as<int32_t>(), ident.data(), len.data(), nullptr, 0, nullptr};
-    auto refit_group = [&](const tsf_spec &gs, const std::vector<int32_t> &sel) -> int {
-        return fit_whole_group(ctx, S, whole, gs, sel, rfo, &grids, &ctx->tune_fits);
-    };
-    std::vector<int32_t> rstat((size_t)N);
-    for (int32_t b = -1; b < C; ++b) {
-        const tsf_spec &gs = b < 0 ? *base : cand[b];
-        const bool auto_g = gs.algorithm == TSF_ALGO_AUTO;
-        const bool newton_ok = 3 + gs.n_changepoints + tsf_spec_K(&gs) <= TSF_MAX_P;
-        std::vector<int32_t> g_lb, g_nw;      // (not AUTO: every series of the choice in g_lb, on gs's own optimiser)
-        for (int64_t n = 0; n < N; ++n) {
-            if (out->best[n] != b || len[(size_t)n] == 0) continue;
-            (auto_g && newton_ok && len[(size_t)n] < TSF_NEWTON_BELOW_T ? g_nw : g_lb).push_back((int32_t)n);
-        }
-        if (!auto_g) {
-            if (int rc = refit_group(gs, g_lb)) return rc;
-            continue;
-        }
-        tsf_spec sp_l = gs, sp_n = gs;
-        sp_l.algorithm = TSF_ALGO_LBFGS;
-        sp_n.algorithm = TSF_ALGO_NEWTON;
-        if (int rc = refit_group(sp_l, g_lb)) return rc;
-        if (newton_ok && !g_lb.empty()) {
-            HIP_TRY(ctx, hipMemcpy(rstat.data(), r_st.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
-            if (int rc = refit_group(sp_n, newton_retry(g_lb, rstat))) return rc;
-        }
-        if (int rc = refit_group(sp_n, g_nw)) return rc;
-    }
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    HIP_TRY(ctx, hipMemcpy(fo.theta, r_th.p, 8 * (size_t)N * stride, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(fo.y_scale, r_ys.p, 8 * (size_t)N, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(fo.fval, r_fv.p, 8 * (size_t)N, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(fo.status, r_st.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(fo.n_iter, r_it.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(fo.n_eval, r_ev.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(fo.grid, r_gr.p, sizeof(tsf_grid_info) * (size_t)n_grids, hipMemcpyDeviceToHost));
-    return 0;
+    cv_plan_call(p, a, base, &S);
+    if (int rc = cv_upload(ctx, nullptr, &S)) return rc;
+    const size_t NC = (size_t)N * C;
+    TuneScores B;
+    HIP_TRY(ctx, B.d_score.alloc(8 * NC)); HIP_TRY(ctx, B.d_cst.alloc(4 * NC));
+    HIP_TRY(ctx, B.d_pst.put(S.pst.data(), 4 * (size_t)N));
+    HIP_TRY(ctx, B.d_best.alloc(4 * (size_t)N)); HIP_TRY(ctx, B.d_sstat.alloc(4 * (size_t)N));
+    if (int rc = tune_score_candidates(ctx, S, base, cand, C, metric, a.rolling_window, &B)) return rc;
+    if (int rc = tune_select(ctx, N, C, B, *out)) return rc;
+    return refit ? tune_refit(ctx, S, base, cand, C, out->best, out->fit) : 0;
 }
 
 // ---- outlier screening (include/tsf.h) ----------------------------------------------------------------------
@@ -4036,6 +4128,175 @@ extern "C" int tsf_screen_rows(tsf_ctx *ctx, int64_t N, int32_t T, const int64_t
     return 0;
 }
 
+// ---- the steps of tsf_fit_screened ------------------------------------------------------------------------------
+
+static int screened_check_args(tsf_ctx *ctx, const tsf_spec *spec, const PanelIn &p, double scale_floor_rel,
+                               const tsf_screen_args *args, const tsf_fit_screened_out *out)
+{
+    if (!spec || !p.ds || !p.y || !out) return fail(ctx, "NULL input");
+    if (int rc = check_screen_args(ctx, args, &out->screen)) return rc;
+    if (p.y_dtype < TSF_Y_F64 || p.y_dtype > TSF_Y_I32) return fail(ctx, "bad y_dtype");
+    if (int rc = check_panel_in(ctx, spec, p, INT32_MAX)) return rc;
+    if (!(scale_floor_rel >= 0.0) || !std::isfinite(scale_floor_rel)) return fail(ctx, "scale_floor_rel must be finite and >= 0");
+    if (!fit_out_complete(out->fit)) return fail(ctx, "tsf_fit_screened_out.fit has NULL members");
+    if (out->first && !fit_out_complete(*out->first)) return fail(ctx, "tsf_fit_screened_out.first has NULL members");
+    return check_algorithm(ctx, spec);
+}
+
+// What the rounds of a tsf_fit_screened call work on: the panel, the current fit of every series (a grid per series
+// from the first round on), the history as a future panel, the screening outputs and the host's counts.
+struct ScreenedRun {
+    CvCall S;
+    DevFitOut fit;
+    WholeViews W;
+    int64_t grids = 0;                  // (not reported)
+    int32_t launches = 0;
+    int32_t H = 0;                      // columns of the history panel: T, or the longest series' rows
+    DevBuf d_hds, d_hex, d_fit, d_ms, d_flag, d_res, d_cen, d_sc, d_nn, d_nf, d_sst;
+    tsf_screen_out so;
+    std::vector<int32_t> h_new, h_flagged, rounds, active;
+    std::vector<int64_t> kept;          // rows without a flag, of the series cut so far
+};
+
+// round 0: every series with rows fitted on its whole history by the optimiser rule, as tsf_tune's refit fits base;
+// *first (where asked for) receives it, then the one grid of an aligned panel is spread to a grid per series
+static int screened_first_fit(tsf_ctx *ctx, ScreenedRun &R, const tsf_spec *spec, const tsf_fit_out *first)
+{
+    CvCall &S = R.S;
+    const int64_t N = S.N;
+    if (int rc = R.fit.alloc(ctx, N, S.stride, N, FIT_OUT_UNFITTED)) return rc;
+    if (int rc = R.W.build(ctx, S)) return rc;
+    const tsf_fit_out dst = R.fit.view();
+    const CvViews whole = R.W.views();
+    std::vector<int32_t> members;
+    for (int64_t n = 0; n < N; ++n) if (R.W.len[(size_t)n] > 0) members.push_back((int32_t)n);
+    if (int rc = fit_by_rule(ctx, *spec, optimiser_groups(*spec, members.data(), members.size(), R.W.len.data()), R.fit,
+                             [&](const tsf_spec &gs, const std::vector<int32_t> &sel, RuleLaunch) -> int {
+                                 return fit_whole_group(ctx, S, whole, gs, sel, dst, &R.grids, &R.launches);
+                             }))
+        return rc;
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    if (first)
+        if (int rc = R.fit.download(ctx, *first, S.aligned ? 1 : N)) return rc;
+    if (S.aligned && N > 1) {
+        const int64_t words = (N - 1) * (int64_t)(sizeof(tsf_grid_info) / 8);
+        hipLaunchKernelGGL(screen_grid_fill_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, nullptr, N, dst.grid);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return 0;
+}
+
+// the buffers of the rounds: the history as a future panel (ragged: padded to H columns), the fitted values, the flags
+// (none yet) and the screening outputs the caller asked for
+static int screened_rounds_setup(tsf_ctx *ctx, ScreenedRun &R, const tsf_screen_out &want)
+{
+    CvCall &S = R.S;
+    const int64_t N = S.N;
+    const int32_t H = R.H = S.aligned ? S.T : (int32_t)R.W.max_len;
+    const size_t rows = S.aligned ? (size_t)N * S.T : (size_t)S.offsets[N];
+    if (!S.aligned) {
+        HIP_TRY(ctx, R.d_hds.alloc(8 * (size_t)N * H));
+        if (S.n_extra > 0) HIP_TRY(ctx, R.d_hex.alloc(8 * (size_t)N * S.n_extra * H));
+        hipLaunchKernelGGL(screen_history_kernel, dim3((unsigned)(N < 65535 ? N : 65535)), dim3(256), 0, nullptr, S.pn, N, H,
+                           R.d_hds.as<int64_t>(), S.n_extra > 0 ? R.d_hex.as<double>() : nullptr);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, R.d_fit.alloc(8 * (size_t)N * H)); HIP_TRY(ctx, R.d_ms.alloc(8 * (size_t)N));
+    HIP_TRY(ctx, R.d_flag.alloc(rows)); HIP_TRY(ctx, hipMemset(R.d_flag.p, 0, rows ? rows : 1));
+    HIP_TRY(ctx, R.d_nn.alloc(4 * (size_t)N)); HIP_TRY(ctx, R.d_nf.alloc(4 * (size_t)N)); HIP_TRY(ctx, R.d_sst.alloc(4 * (size_t)N));
+    tsf_screen_out &so = R.so;
+    memset(&so, 0, sizeof(so));
+    so.flag = R.d_flag.as<uint8_t>(); so.n_new = R.d_nn.as<int32_t>(); so.n_flagged = R.d_nf.as<int32_t>();
+    so.status = R.d_sst.as<int32_t>();
+    if (want.resid) { HIP_TRY(ctx, R.d_res.alloc(8 * rows)); so.resid = R.d_res.as<double>(); }
+    if (want.center) { HIP_TRY(ctx, R.d_cen.alloc(8 * (size_t)N)); so.center = R.d_cen.as<double>(); }
+    if (want.scale) { HIP_TRY(ctx, R.d_sc.alloc(8 * (size_t)N)); so.scale = R.d_sc.as<double>(); }
+    R.h_new.resize((size_t)N); R.h_flagged.resize((size_t)N); R.rounds.assign((size_t)N, 0); R.kept.resize((size_t)N);
+    return 0;
+}
+
+// the rows without a flag of the series sel as one ragged panel, fitted with gs, the results at the series' positions
+static int screened_refit_cut(tsf_ctx *ctx, ScreenedRun &R, const tsf_spec &gs, const std::vector<int32_t> &sel)
+{
+    CvCall &S = R.S;
+    CvGroup E;
+    if (int rc = cv_group_layout(ctx, S, sel, R.kept.data(), &E)) return rc;
+    const int64_t G = E.G;
+    hipLaunchKernelGGL(screen_compact_kernel, dim3((unsigned)(G < 65535 ? G : 65535)), dim3(256), 0, nullptr, S.pn, G,
+                       E.d_gf.as<int32_t>(), R.d_flag.as<uint8_t>(), E.d_goff.as<int64_t>(), E.rows,
+                       S.has_floor ? S.d_fl.as<double>() : nullptr, S.has_cap ? S.d_cap.as<double>() : nullptr,
+                       E.d_gds.as<int64_t>(), E.d_gy.p, S.n_extra > 0 ? E.d_gex.as<double>() : nullptr,
+                       S.has_floor ? E.d_gfl.as<double>() : nullptr, S.has_cap ? E.d_gcap.as<double>() : nullptr);
+    HIP_TRY(ctx, hipGetLastError());
+    return cv_fit(ctx, S, E, gs, R.fit.view(), &R.grids, &R.launches);
+}
+
+// round p >= 1: predict over the history, the screening rule on the series still active, the flag counts back, and the
+// series with new flags cut and fitted again by the optimiser rule on the rows they keep.  *done: no series was cut.
+static int screened_round(tsf_ctx *ctx, ScreenedRun &R, const tsf_spec *spec, double scale_floor_rel,
+                          const tsf_screen_args &args, int32_t p, bool *done)
+{
+    CvCall &S = R.S;
+    const int64_t N = S.N;
+    const int32_t H = R.H;
+    const bool aligned = S.aligned;
+    const tsf_fit_out fit = R.fit.view();
+    if (int rc = tsf_predict_dev(ctx, spec, N, H, fit.theta, fit.y_scale, fit.grid, (int32_t)N,
+                                 aligned ? S.d_ds.as<int64_t>() : R.d_hds.as<int64_t>(), aligned ? 1 : 0,
+                                 S.has_floor ? S.d_fl.as<double>() : nullptr, S.has_cap ? S.d_cap.as<double>() : nullptr,
+                                 S.n_extra > 0 ? (aligned ? S.d_ex.as<double>() : R.d_hex.as<double>()) : nullptr,
+                                 R.d_fit.as<double>(), nullptr, nullptr))
+        return rc;
+    hipLaunchKernelGGL(screen_mask_failed_kernel, dim3((unsigned)(N < 65535 ? N : 65535)), dim3(256), 0, nullptr, N,
+                       (int64_t)H, fit.status, R.d_fit.as<double>());
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(screen_scale_floor_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, nullptr, N,
+                       scale_floor_rel, fit.y_scale, R.d_ms.as<double>());
+    HIP_TRY(ctx, hipGetLastError());
+    // (excluded and flag are one array: a thread reads a row's byte before it writes it, and no other thread does)
+    if (int rc = screen_run(ctx, N, S.T, S.d_off.as<int64_t>(), S.offsets, S.d_y.p, S.y_dtype, R.d_fit.as<double>(), H,
+                            R.d_flag.as<uint8_t>(), R.d_ms.as<double>(), args, R.so, p == 1 ? nullptr : R.active.data(),
+                            (int64_t)R.active.size(), nullptr))
+        return rc;
+    HIP_TRY(ctx, hipMemcpy(R.h_new.data(), R.d_nn.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(R.h_flagged.data(), R.d_nf.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+    std::vector<int32_t> cutl;
+    for (int64_t i = 0; i < (p == 1 ? N : (int64_t)R.active.size()); ++i) {
+        const int32_t n = p == 1 ? (int32_t)i : R.active[(size_t)i];
+        if (R.h_new[(size_t)n] <= 0) continue;
+        cutl.push_back(n);
+        R.rounds[(size_t)n] += 1;
+        R.kept[(size_t)n] = R.W.len[(size_t)n] - R.h_flagged[(size_t)n];
+    }
+    *done = cutl.empty();
+    if (*done) return 0;
+    if (int rc = fit_by_rule(ctx, *spec, optimiser_groups(*spec, cutl.data(), cutl.size(), R.kept.data()), R.fit,
+                             [&](const tsf_spec &gs, const std::vector<int32_t> &sel, RuleLaunch) -> int {
+                                 return screened_refit_cut(ctx, R, gs, sel);
+                             }))
+        return rc;
+    R.active.swap(cutl);
+    return 0;
+}
+
+// the last fit of every series, the screening outputs and the rounds to the caller
+static int screened_download(tsf_ctx *ctx, const ScreenedRun &R, const tsf_fit_screened_out &out)
+{
+    const CvCall &S = R.S;
+    const size_t N = (size_t)S.N, rows = S.aligned ? N * S.T : (size_t)S.offsets[N];
+    if (int rc = R.fit.download(ctx, out.fit, S.N)) return rc;
+    const tsf_screen_out &ho = out.screen;
+    if (rows) HIP_TRY(ctx, hipMemcpy(ho.flag, R.d_flag.p, rows, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(ho.status, R.d_sst.p, 4 * N, hipMemcpyDeviceToHost));
+    if (ho.resid && rows) HIP_TRY(ctx, hipMemcpy(ho.resid, R.d_res.p, 8 * rows, hipMemcpyDeviceToHost));
+    if (ho.center) HIP_TRY(ctx, hipMemcpy(ho.center, R.d_cen.p, 8 * N, hipMemcpyDeviceToHost));
+    if (ho.scale) HIP_TRY(ctx, hipMemcpy(ho.scale, R.d_sc.p, 8 * N, hipMemcpyDeviceToHost));
+    if (ho.n_new) HIP_TRY(ctx, hipMemcpy(ho.n_new, R.d_nn.p, 4 * N, hipMemcpyDeviceToHost));
+    if (ho.n_flagged) HIP_TRY(ctx, hipMemcpy(ho.n_flagged, R.d_nf.p, 4 * N, hipMemcpyDeviceToHost));
+    if (out.rounds) memcpy(out.rounds, R.rounds.data(), 4 * N);
+    return 0;
+}
+
 extern "C" int tsf_fit_screened(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t T, const int64_t *offsets,
                                 const int64_t *ds, const void *y, int32_t y_dtype, const double *floor_, const double *cap,
                                 const double *extra, double scale_floor_rel, const tsf_screen_args *args,
@@ -4043,194 +4304,20 @@ extern "C" int tsf_fit_screened(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, i
 {
     if (!ctx) return -1;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!spec || !ds || !y || !out) return fail(ctx, "NULL input");
-    if (int rc = check_screen_args(ctx, args, &out->screen)) return rc;
-    if (y_dtype < TSF_Y_F64 || y_dtype > TSF_Y_I32) return fail(ctx, "bad y_dtype");
-    if (N > (int64_t)INT32_MAX || tsf_cv::check_panel(N, T, offsets, ds))
-        return fail(ctx, "bad panel (aligned: offsets NULL, 1 <= T <= TSF_MAX_T; ragged: T = 0, offsets[0] = 0, ascending)");
-    if (spec->n_extra > 0 && !extra) return fail(ctx, "extra columns declared but extra is NULL");
-    if (spec->growth == TSF_GROWTH_LOGISTIC && !cap) return fail(ctx, "logistic growth needs cap");
-    if (!(scale_floor_rel >= 0.0) || !std::isfinite(scale_floor_rel)) return fail(ctx, "scale_floor_rel must be finite and >= 0");
-    if (!fit_out_complete(out->fit)) return fail(ctx, "tsf_fit_screened_out.fit has NULL members");
-    if (out->first && !fit_out_complete(*out->first)) return fail(ctx, "tsf_fit_screened_out.first has NULL members");
+    const PanelIn p{N, T, offsets, ds, y, y_dtype, floor_, cap, extra};
+    if (int rc = screened_check_args(ctx, spec, p, scale_floor_rel, args, out)) return rc;
     ctx->order_n = 0;                   // (pending cost hints were meant for a fit call)
-    const bool aligned = offsets == nullptr;
-    CvCall S;
-    S.aligned = aligned; S.N = N; S.T = T; S.offsets = offsets; S.ds = ds; S.y_dtype = y_dtype; S.ysz = ysize(y_dtype);
-    S.n_extra = spec->n_extra; S.stride = tsf_theta_stride(spec);
-    S.has_floor = floor_ != nullptr; S.has_cap = cap != nullptr;
-    std::vector<int32_t> ident((size_t)N);
-    std::vector<int64_t> len((size_t)N);
-    int64_t Tmax = 0;
-    for (int64_t n = 0; n < N; ++n) {
-        ident[(size_t)n] = (int32_t)n;
-        len[(size_t)n] = aligned ? T : offsets[n + 1] - offsets[n];
-        if (len[(size_t)n] > Tmax) Tmax = len[(size_t)n];
-    }
-    if (Tmax < 1) return fail(ctx, "no rows");
-    if (int rc = cv_upload(ctx, y, floor_, cap, extra, nullptr, &S)) return rc;
-    const int stride = S.stride;
-    const size_t rows = aligned ? (size_t)N * T : (size_t)offsets[N];
-    int64_t grids = 0;                  // (not reported)
-    int32_t launches = 0;
-    // ---- round 0: the first fit, as tsf_tune's refit of base
-    DevBuf r_th, r_ys, r_fv, r_st, r_it, r_ev, r_gr;
-    HIP_TRY(ctx, r_th.alloc(8 * (size_t)N * stride)); HIP_TRY(ctx, r_ys.alloc(8 * (size_t)N)); HIP_TRY(ctx, r_fv.alloc(8 * (size_t)N));
-    HIP_TRY(ctx, r_st.alloc(4 * (size_t)N)); HIP_TRY(ctx, r_it.alloc(4 * (size_t)N)); HIP_TRY(ctx, r_ev.alloc(4 * (size_t)N));
-    HIP_TRY(ctx, r_gr.alloc(sizeof(tsf_grid_info) * (size_t)N));
-    HIP_TRY(ctx, hipMemset(r_th.p, 0, 8 * (size_t)N * stride)); HIP_TRY(ctx, hipMemset(r_ys.p, 0, 8 * (size_t)N));
-    HIP_TRY(ctx, hipMemset(r_fv.p, 0, 8 * (size_t)N)); HIP_TRY(ctx, hipMemset(r_it.p, 0, 4 * (size_t)N));
-    HIP_TRY(ctx, hipMemset(r_ev.p, 0, 4 * (size_t)N)); HIP_TRY(ctx, hipMemset(r_gr.p, 0, sizeof(tsf_grid_info) * (size_t)N));
-    std::vector<int32_t> rstat((size_t)N, TSF_ST_TOO_FEW);    // (a ragged series without rows is not fitted)
-    HIP_TRY(ctx, hipMemcpy(r_st.p, rstat.data(), 4 * (size_t)N, hipMemcpyHostToDevice));
-    tsf_fit_out rfo;
-    rfo.theta = r_th.as<double>(); rfo.y_scale = r_ys.as<double>(); rfo.fval = r_fv.as<double>();
-    rfo.status = r_st.as<int32_t>(); rfo.n_iter = r_it.as<int32_t>(); rfo.n_eval = r_ev.as<int32_t>();
-    rfo.grid = r_gr.as<tsf_grid_info>();
-    DevBuf d_ident;
-    if (!aligned) { HIP_TRY(ctx, d_ident.alloc(4 * (size_t)N)); HIP_TRY(ctx, hipMemcpy(d_ident.p, ident.data(), 4 * (size_t)N, hipMemcpyHostToDevice)); }
-    const CvViews whole{d_ident.as<int32_t>(), ident.data(), len.data(), nullptr, 0, nullptr};
-    // fbprophet's optimiser rule per series of `members` on its row count n_rows[series] (tsf_tune's refit): one launch
-    // per optimiser, Newton once more where L-BFGS ended the way pystan raises on
-    const bool auto_g = spec->algorithm == TSF_ALGO_AUTO;
-    const bool newton_ok = 3 + spec->n_changepoints + tsf_spec_K(spec) <= TSF_MAX_P;
-    tsf_spec sp_l = *spec, sp_n = *spec;
-    sp_l.algorithm = TSF_ALGO_LBFGS;
-    sp_n.algorithm = TSF_ALGO_NEWTON;
-    auto by_rule = [&](const std::vector<int32_t> &members, const std::vector<int64_t> &n_rows, auto fit_group) -> int {
-        if (!auto_g) return fit_group(*spec, members);
-        std::vector<int32_t> g_lb, g_nw;
-        for (int32_t n : members) (newton_ok && n_rows[(size_t)n] < TSF_NEWTON_BELOW_T ? g_nw : g_lb).push_back(n);
-        if (int rc = fit_group(sp_l, g_lb)) return rc;
-        if (newton_ok && !g_lb.empty()) {
-            HIP_TRY(ctx, hipMemcpy(rstat.data(), r_st.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
-            if (int rc = fit_group(sp_n, newton_retry(g_lb, rstat))) return rc;
-        }
-        return fit_group(sp_n, g_nw);
-    };
-    {
-        std::vector<int32_t> members;
-        for (int64_t n = 0; n < N; ++n) if (len[(size_t)n] > 0) members.push_back((int32_t)n);
-        if (int rc = by_rule(members, len, [&](const tsf_spec &gs, const std::vector<int32_t> &sel) -> int {
-                return fit_whole_group(ctx, S, whole, gs, sel, rfo, &grids, &launches);
-            }))
-            return rc;
-    }
+    if (offsets && offsets[N] == 0) return fail(ctx, "no rows");
+    ScreenedRun R;
+    cv_call_shape(p, spec, &R.S);
+    if (int rc = cv_upload(ctx, nullptr, &R.S)) return rc;
+    if (int rc = screened_first_fit(ctx, R, spec, out->first)) return rc;
+    if (int rc = screened_rounds_setup(ctx, R, out->screen)) return rc;
+    bool done = false;
+    for (int32_t p = 1; p <= args->max_passes && !done; ++p)
+        if (int rc = screened_round(ctx, R, spec, scale_floor_rel, *args, p, &done)) return rc;
     HIP_TRY(ctx, hipDeviceSynchronize());
-    if (out->first) {
-        const tsf_fit_out &f1 = *out->first;
-        HIP_TRY(ctx, hipMemcpy(f1.theta, r_th.p, 8 * (size_t)N * stride, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(f1.y_scale, r_ys.p, 8 * (size_t)N, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(f1.fval, r_fv.p, 8 * (size_t)N, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(f1.status, r_st.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(f1.n_iter, r_it.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(f1.n_eval, r_ev.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(f1.grid, r_gr.p, sizeof(tsf_grid_info) * (size_t)(aligned ? 1 : N), hipMemcpyDeviceToHost));
-    }
-    if (aligned && N > 1) {             // from here on a grid per series
-        const int64_t words = (N - 1) * (int64_t)(sizeof(tsf_grid_info) / 8);
-        hipLaunchKernelGGL(screen_grid_fill_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, nullptr, N, rfo.grid);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    // ---- the rounds
-    const int32_t H = aligned ? T : (int32_t)Tmax;
-    DevBuf d_hds, d_hex, d_fit, d_ms, d_flag, d_res, d_cen, d_sc, d_nn, d_nf, d_sst;
-    if (!aligned) {
-        HIP_TRY(ctx, d_hds.alloc(8 * (size_t)N * H));
-        if (S.n_extra > 0) HIP_TRY(ctx, d_hex.alloc(8 * (size_t)N * S.n_extra * H));
-        hipLaunchKernelGGL(screen_history_kernel, dim3((unsigned)(N < 65535 ? N : 65535)), dim3(256), 0, nullptr, S.pn, N, H,
-                           d_hds.as<int64_t>(), S.n_extra > 0 ? d_hex.as<double>() : nullptr);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    HIP_TRY(ctx, d_fit.alloc(8 * (size_t)N * H)); HIP_TRY(ctx, d_ms.alloc(8 * (size_t)N));
-    HIP_TRY(ctx, d_flag.alloc(rows)); HIP_TRY(ctx, hipMemset(d_flag.p, 0, rows ? rows : 1));
-    HIP_TRY(ctx, d_nn.alloc(4 * (size_t)N)); HIP_TRY(ctx, d_nf.alloc(4 * (size_t)N)); HIP_TRY(ctx, d_sst.alloc(4 * (size_t)N));
-    tsf_screen_out so;
-    memset(&so, 0, sizeof(so));
-    so.flag = d_flag.as<uint8_t>(); so.n_new = d_nn.as<int32_t>(); so.n_flagged = d_nf.as<int32_t>(); so.status = d_sst.as<int32_t>();
-    if (out->screen.resid) { HIP_TRY(ctx, d_res.alloc(8 * rows)); so.resid = d_res.as<double>(); }
-    if (out->screen.center) { HIP_TRY(ctx, d_cen.alloc(8 * (size_t)N)); so.center = d_cen.as<double>(); }
-    if (out->screen.scale) { HIP_TRY(ctx, d_sc.alloc(8 * (size_t)N)); so.scale = d_sc.as<double>(); }
-    std::vector<int32_t> h_new((size_t)N), h_flagged((size_t)N), rounds((size_t)N, 0), active;
-    std::vector<int64_t> kept((size_t)N);
-    // the rows without a flag of the series sel as one ragged panel, fitted with gs, the results at the series' positions
-    auto refit_cut = [&](const tsf_spec &gs, const std::vector<int32_t> &sel) -> int {
-        CvGroup E;
-        const int64_t G = E.G = (int64_t)sel.size();
-        if (G == 0) return 0;
-        E.gf = sel;
-        std::vector<int64_t> goff((size_t)G + 1, 0);
-        for (int64_t g = 0; g < G; ++g) {
-            const int64_t h = kept[(size_t)sel[(size_t)g]];
-            goff[(size_t)g + 1] = goff[(size_t)g] + h;
-            if (h > E.maxT) E.maxT = (int32_t)h;
-        }
-        const int64_t total = E.rows = goff[(size_t)G];
-        HIP_TRY(ctx, E.d_gf.alloc(4 * (size_t)G)); HIP_TRY(ctx, hipMemcpy(E.d_gf.p, sel.data(), 4 * (size_t)G, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, E.d_goff.alloc(8 * ((size_t)G + 1))); HIP_TRY(ctx, hipMemcpy(E.d_goff.p, goff.data(), 8 * ((size_t)G + 1), hipMemcpyHostToDevice));
-        HIP_TRY(ctx, E.d_gds.alloc(8 * (size_t)total)); HIP_TRY(ctx, E.d_gy.alloc(S.ysz * (size_t)total));
-        if (S.n_extra > 0) HIP_TRY(ctx, E.d_gex.alloc(8 * (size_t)S.n_extra * total));
-        if (S.has_floor) HIP_TRY(ctx, E.d_gfl.alloc(8 * (size_t)G));
-        if (S.has_cap) HIP_TRY(ctx, E.d_gcap.alloc(8 * (size_t)G));
-        hipLaunchKernelGGL(screen_compact_kernel, dim3((unsigned)(G < 65535 ? G : 65535)), dim3(256), 0, nullptr, S.pn, G,
-                           E.d_gf.as<int32_t>(), d_flag.as<uint8_t>(), E.d_goff.as<int64_t>(), total,
-                           S.has_floor ? S.d_fl.as<double>() : nullptr, S.has_cap ? S.d_cap.as<double>() : nullptr,
-                           E.d_gds.as<int64_t>(), E.d_gy.p, S.n_extra > 0 ? E.d_gex.as<double>() : nullptr,
-                           S.has_floor ? E.d_gfl.as<double>() : nullptr, S.has_cap ? E.d_gcap.as<double>() : nullptr);
-        HIP_TRY(ctx, hipGetLastError());
-        return cv_fit(ctx, S, E, gs, rfo, &grids, &launches);
-    };
-    for (int32_t p = 1; p <= args->max_passes; ++p) {
-        if (int rc = tsf_predict_dev(ctx, spec, N, H, rfo.theta, rfo.y_scale, rfo.grid, (int32_t)N,
-                                     aligned ? S.d_ds.as<int64_t>() : d_hds.as<int64_t>(), aligned ? 1 : 0,
-                                     floor_ ? S.d_fl.as<double>() : nullptr, cap ? S.d_cap.as<double>() : nullptr,
-                                     S.n_extra > 0 ? (aligned ? S.d_ex.as<double>() : d_hex.as<double>()) : nullptr,
-                                     d_fit.as<double>(), nullptr, nullptr))
-            return rc;
-        hipLaunchKernelGGL(screen_mask_failed_kernel, dim3((unsigned)(N < 65535 ? N : 65535)), dim3(256), 0, nullptr, N,
-                           (int64_t)H, rfo.status, d_fit.as<double>());
-        HIP_TRY(ctx, hipGetLastError());
-        hipLaunchKernelGGL(screen_scale_floor_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, nullptr, N,
-                           scale_floor_rel, rfo.y_scale, d_ms.as<double>());
-        HIP_TRY(ctx, hipGetLastError());
-        // (excluded and flag are one array: a thread reads a row's byte before it writes it, and no other thread does)
-        if (int rc = screen_run(ctx, N, T, S.d_off.as<int64_t>(), offsets, S.d_y.p, y_dtype, d_fit.as<double>(), H,
-                                d_flag.as<uint8_t>(), d_ms.as<double>(), *args, so, p == 1 ? nullptr : active.data(),
-                                (int64_t)active.size(), nullptr))
-            return rc;
-        HIP_TRY(ctx, hipMemcpy(h_new.data(), d_nn.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(h_flagged.data(), d_nf.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
-        std::vector<int32_t> cutl;
-        for (int64_t i = 0; i < (p == 1 ? N : (int64_t)active.size()); ++i) {
-            const int32_t n = p == 1 ? (int32_t)i : active[(size_t)i];
-            if (h_new[(size_t)n] <= 0) continue;
-            cutl.push_back(n);
-            rounds[(size_t)n] += 1;
-            kept[(size_t)n] = len[(size_t)n] - h_flagged[(size_t)n];
-        }
-        if (cutl.empty()) break;
-        if (int rc = by_rule(cutl, kept, refit_cut)) return rc;
-        active.swap(cutl);
-    }
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    const tsf_fit_out &fo = out->fit;
-    HIP_TRY(ctx, hipMemcpy(fo.theta, r_th.p, 8 * (size_t)N * stride, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(fo.y_scale, r_ys.p, 8 * (size_t)N, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(fo.fval, r_fv.p, 8 * (size_t)N, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(fo.status, r_st.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(fo.n_iter, r_it.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(fo.n_eval, r_ev.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(fo.grid, r_gr.p, sizeof(tsf_grid_info) * (size_t)N, hipMemcpyDeviceToHost));
-    const tsf_screen_out &ho = out->screen;
-    if (rows) HIP_TRY(ctx, hipMemcpy(ho.flag, d_flag.p, rows, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(ho.status, d_sst.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
-    if (ho.resid && rows) HIP_TRY(ctx, hipMemcpy(ho.resid, d_res.p, 8 * rows, hipMemcpyDeviceToHost));
-    if (ho.center) HIP_TRY(ctx, hipMemcpy(ho.center, d_cen.p, 8 * (size_t)N, hipMemcpyDeviceToHost));
-    if (ho.scale) HIP_TRY(ctx, hipMemcpy(ho.scale, d_sc.p, 8 * (size_t)N, hipMemcpyDeviceToHost));
-    if (ho.n_new) HIP_TRY(ctx, hipMemcpy(ho.n_new, d_nn.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
-    if (ho.n_flagged) HIP_TRY(ctx, hipMemcpy(ho.n_flagged, d_nf.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
-    if (out->rounds) memcpy(out->rounds, rounds.data(), 4 * (size_t)N);
-    return 0;
+    return screened_download(ctx, R, *out);
 }
 
 // ---- conformal interval calibration (include/tsf.h) ---------------------------------------------------------
@@ -4487,6 +4574,6 @@ extern "C" int tsf_calibrate(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int3
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (int rc = check_calib_args(ctx, calib)) return rc;
     if (int rc = check_calib_table(ctx, table)) return rc;
-    return cross_validate_run(ctx, spec, N, T, offsets, ds, y, y_dtype, floor_, cap, extra, args, series_key, n_samples,
-                              interval_width, seed, cv_out, calib, table);
+    return cross_validate_run(ctx, spec, PanelIn{N, T, offsets, ds, y, y_dtype, floor_, cap, extra}, args, series_key,
+                              n_samples, interval_width, seed, cv_out, calib, table);
 }
