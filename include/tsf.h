@@ -473,8 +473,11 @@ int tsf_score_actuals_dev(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t
  * pinned is the contract below, against tsf_predict_quantiles' draws).  Host pointers only, like tsf_cross_validate.
  * Timing: tools/bench_rollup.py; the first MI355X run is in DESIGN.md 5f.
  *
- * Meaning: the members are taken as independent given their fits (each series is fitted alone and draws from its own
- * stream); where the members' errors are positively correlated in reality, the roll-up's spread is too narrow.
+ * Meaning: by default the members are taken as independent given their fits (each series is fitted alone and draws
+ * from its own stream); where the members' errors are positively correlated in reality, such a roll-up's spread is too
+ * narrow.  The remedy is opt-in: tsf_residual_corr estimates each group's residual correlation from the fits' own history
+ * and tsf_rollup_set_noise_corr makes the adds draw the members' observation noise with it ("correlated group roll-ups"
+ * below, with its limits).  A handle without a correlation set is what it always was, bit for bit.
  *
  * Rows: every member is forecast on the roll-up's own ds_future[H], one shared calendar; row h of a group is the sum
  * over its members at row index h.  extra_future is [n_extra][H] with shared_extra set, else [N][n_extra][H].  A
@@ -610,6 +613,88 @@ int tsf_rollup_reconcile(tsf_rollup *r, const tsf_spec *spec, int64_t N, const d
                          const double *quantiles, tsf_reconcile_out *out);
 int tsf_rollup_reconciled_totals(tsf_rollup *r, const double *share_total /* [G] */, int32_t n_q, const double *quantiles,
                                  tsf_rollup_out *out);
+
+/* ---- correlated group roll-ups: a shared noise factor per group ----------------------------------------
+ * The members of a total share weather, promotions and outages, so their forecast errors move together, and the P90
+ * of a total of m independent members is too narrow by a factor that grows like sqrt(1 + (m - 1) rho): more than 3 x at
+ * m = 100 and rho = 0.1.  Two pieces, both opt-in: an estimator of each group's residual correlation from the fits' own
+ * history, and an add route that draws the members' observation noise with that correlation.  Reference interface
+ * replaced: none (neither the reference nor fbprophet has such a function); parity unpinned (what is pinned is the
+ * contract below: the estimator bit for bit against a numpy restatement, tests/corr_ref.py, and the add against the
+ * independent add plus the restated factor term).  Timing: tools/bench_rollup_corr.py; DESIGN.md 5l.
+ *
+ * Limits, stated plainly.  One factor with equal loading per group: every pair of members of a group gets the same
+ * rho.  Contemporaneous correlation only: the factor is independent from row to row.  rho is estimated in sample, on
+ * the residuals of the fits' own history.  Only the observation noise is correlated: the sampled trend changes of the
+ * members stay independent.  A negative estimate is clipped to 0.  A series rolled up under two groupings (two handles)
+ * gets two unrelated factors.  Reconciling correlated draws is out of scope (see the refusals).
+ *
+ * tsf_residual_corr.  Aligned panels only (co-movement is row by row): y [N][T] in y_dtype; fitted [N][T] double --
+ * tsf_predict of each fit on its own history dates, as tsf_fit_screened forms it; group [N], each value in [0, G), or -1
+ * for a series that takes no part; args (NULL: the defaults) {rho_max = 0.95, min_rows = 8}.  Outputs per group: rho,
+ * status (required), rho_raw, n_pairs, n_used (NULL: not wanted); per series: scale (NULL: not wanted).  Host pointers
+ * in the host variant; in _dev y, fitted and every output are device pointers, while group, args and the tsf_corr_out
+ * struct itself are HOST memory (the members' lists are built on the host), and the call synchronises the stream before
+ * it returns.
+ * Contract, in plain double operations with one rounding each (no fused multiply-add, no atomics; a group's result
+ * depends on nothing else in the batch):
+ *   Per series i: row t is present where r = (double)y - fitted is finite; n_i = the present rows, ss_i = sum of r * r
+ *   over them.  n_i < min_rows or ss_i == 0: the series is unused and scale[i] = NaN.  Otherwise
+ *   scale[i] = sqrt(ss_i / (double)n_i) and e_it = r_it / scale[i].
+ *   Per group g and row t: over the used members present at t, in ascending series index, u = u + e, q = q + e * e,
+ *   k += 1 (from +0.0, +0.0, 0); c_t = u * u - q (the sum of e_i e_j over the ordered pairs) and p_t = k (k - 1), an int64.
+ *   Per group: A = sum of c_t, P = sum of p_t (an integer: exact), rho_raw = A / (double)P,
+ *   rho = fmin(fmax(rho_raw, 0), rho_max), n_pairs = P / 2, n_used = the used members.  P == 0 (a singleton, an empty
+ *   group, members that never overlap): rho_raw = NaN, rho = +0.0, status TSF_CORR_NO_PAIRS; otherwise TSF_CORR_OK.
+ *   The two sums over t (ss_i, A): 64 partials from +0.0, partial l adds rows l, l + 64, ... in ascending order (an absent
+ *   row adds +0.0); the partials are combined by the xor butterfly v[l] = v[l] + v[l ^ d] for d = 1, 2, 4, 8, 16, 32.
+ * Refusals (< 0 with a message, before any launch; the context stays usable): a NULL out, out->rho or out->status; NULL
+ *   y, fitted or group with N > 0; a group value outside [-1, G); rho_max outside [0, 1]; min_rows < 2; a bad y_dtype;
+ *   T < 1; G < 1.  N == 0 is a legal no-op that reports every group TSF_CORR_NO_PAIRS.
+ *
+ * tsf_rollup_set_noise_corr.  rho [G], each finite and in [0, 1]; group_key [G] (NULL: the group index), the key of each
+ * group's factor stream.  Legal only on a handle nothing has been added to.  It stores a_g = sqrt(1 - rho_g) - 1 and
+ * b_g = sqrt(rho_g), formed on the host in double (IEEE sqrt), and the keys.  From then on tsf_rollup_add (same
+ * signature, checks, chunking and ownership: one accumulator cell, its members added in list order by plain double adds)
+ * adds, for a member i of a group with rho_g > 0, at row index h and sample s,
+ *   v = v + (x_i + ((a_g * z_i + b_g * w) * sn_i)),    sn_i = exp(theta_i[2]) * y_scale_i  (the library's deterministic exp)
+ * where x_i is the member's draw (tsf_predict_quantiles' sample), z_i the standard normal the draw's noise was made from
+ * -- Box-Muller sqrt(-2 log u1) cos(2 pi u2) on the stream keyed (seed, series_key[i], s, stream 1) at counters 2h,
+ * 2h + 1 -- regenerated, not stored, and w the same expression on the group's stream keyed (seed, group_key[g], s,
+ * stream 2) at the same counters, formed once per cell.  The member's noise becomes
+ * (sqrt(1 - rho) z_i + sqrt(rho) w) sigma y_scale: its own marginal law is unchanged, any two members of a group have
+ * noise correlation rho at the same row and sample, and different rows, samples and groups stay independent.  A group
+ * with rho_g == 0 takes the independent expression v = v + x_i exactly, so its bits are those of a handle without a
+ * correlation; ysum and count are carried as always.  The result still depends neither on the chunking nor on what else
+ * a call contains.  tsf_rollup_quantiles and tsf_rollup_windows read the accumulators and need nothing new.
+ * Refusals (< 0 with a message; the accumulators are untouched and the handle and the context stay usable):
+ *   set_noise_corr after any add or set_totals, on a poisoned handle, with a NULL rho, or with a rho that is not finite
+ *   or outside [0, 1]; tsf_rollup_set_totals, tsf_rollup_reconcile and tsf_rollup_reconciled_totals on a handle with a
+ *   correlation set.
+ * Out of scope: ragged panels; several factors or unequal loadings; correlated trend changes; lagged correlation; the
+ * job configurations (the scorer has models and no history). */
+enum { TSF_CORR_OK = 0, TSF_CORR_NO_PAIRS = -50 };
+typedef struct {
+    double rho_max;         /* the estimate is clipped to [0, rho_max]; default 0.95 */
+    int32_t min_rows;       /* a series with fewer present rows is unused; default 8 */
+    int32_t reserved_;      /* 0 */
+} tsf_corr_args;
+typedef struct {
+    double *rho;            /* [G] required: the clipped estimate, what tsf_rollup_set_noise_corr takes */
+    double *rho_raw;        /* [G] the estimate before clipping (NaN without pairs); NULL: not wanted */
+    int64_t *n_pairs;       /* [G] member pairs summed over the rows; NULL: not wanted */
+    int32_t *n_used;        /* [G] the group's used members; NULL: not wanted */
+    int32_t *status;        /* [G] required: TSF_CORR_* */
+    double *scale;          /* [N] each series' residual root mean square (NaN: unused); NULL: not wanted */
+} tsf_corr_out;
+int tsf_corr_args_size(void);       /* sizeof(tsf_corr_args), sizeof(tsf_corr_out): the self-checks of a binding */
+int tsf_corr_out_size(void);
+int tsf_residual_corr(tsf_ctx *ctx, int64_t N, int32_t T, const void *y, int32_t y_dtype, const double *fitted,
+                      const int64_t *group /* [N], each in [-1, G) */, int64_t G, const tsf_corr_args *args /* NULL = defaults */,
+                      tsf_corr_out *out);
+int tsf_residual_corr_dev(tsf_ctx *ctx, int64_t N, int32_t T, const void *y, int32_t y_dtype, const double *fitted,
+                          const int64_t *group, int64_t G, const tsf_corr_args *args, tsf_corr_out *out, void *stream);
+int tsf_rollup_set_noise_corr(tsf_rollup *r, const double *rho /* [G] */, const int64_t *group_key /* [G], NULL = g */);
 
 /* ---- totals over row windows: quantiles and scores of calendar-period totals ----------------------------
  * "P10 / P50 / P90 of next week's total, of each calendar month, of every rolling 7-row block", for a series and for

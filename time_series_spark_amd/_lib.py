@@ -165,6 +165,17 @@ class TsfCalibTable(ctypes.Structure):
     _fields_ = [('q', ctypes.c_void_p), ('n', ctypes.c_void_p), ('status', ctypes.c_void_p)]
 
 
+class TsfCorrArgs(ctypes.Structure):
+    """tsf_corr_args (include/tsf.h)."""
+    _fields_ = [('rho_max', ctypes.c_double), ('min_rows', ctypes.c_int32), ('reserved_', ctypes.c_int32)]
+
+
+class TsfCorrOut(ctypes.Structure):
+    """tsf_corr_out (include/tsf.h)."""
+    _fields_ = [('rho', ctypes.c_void_p), ('rho_raw', ctypes.c_void_p), ('n_pairs', ctypes.c_void_p),
+                ('n_used', ctypes.c_void_p), ('status', ctypes.c_void_p), ('scale', ctypes.c_void_p)]
+
+
 class TsfFitShape(ctypes.Structure):
     """tsf_fit_shape (include/tsf_dev.h)."""
     _fields_ = [('N', ctypes.c_int64), ('n_distinct', ctypes.c_int64), ('lat_step', ctypes.c_int64), ('lat_U', ctypes.c_int64),
@@ -198,6 +209,7 @@ EXPORTS = ['tsf_create', 'tsf_destroy', 'tsf_last_error', 'tsf_device_count', 't
            'tsf_rollup_create', 'tsf_rollup_add', 'tsf_rollup_quantiles', 'tsf_rollup_free',
            'tsf_window_out_size', 'tsf_predict_windows', 'tsf_predict_windows_dev', 'tsf_rollup_windows',
            'tsf_reconcile_shares', 'tsf_reconcile_out_size', 'tsf_rollup_set_totals', 'tsf_rollup_reconcile', 'tsf_rollup_reconciled_totals',
+           'tsf_corr_args_size', 'tsf_corr_out_size', 'tsf_residual_corr', 'tsf_residual_corr_dev', 'tsf_rollup_set_noise_corr',
            'tsf_eval', 'tsf_eval_quadratic', 'tsf_design', 'tsf_selftest_math',
            'tsf_set_option', 'tsf_get_option', 'tsf_set_cost_hints', 'tsf_set_profiling', 'tsf_profile_read', 'tsf_last_fit_kernel_ms', 'tsf_last_fit_route',
            'tsf_fit_plan', 'tsf_fit_plan_info_size', 'tsf_fit_plan_error', 'tsf_last_fit_plan',
@@ -226,6 +238,8 @@ CALIB_ABS, CALIB_CQR = 0, 1
 CALIB_MODES = {'abs': CALIB_ABS, 'cqr': CALIB_CQR}
 CALIB_OK, CALIB_NO_SCORES, CALIB_TOO_LONG = 0, -40, -41
 CALIB_MAX_ROWS, CALIB_MAX_LEVELS, CALIB_MAX_BUCKETS = 16384, 16, 64
+# TSF_CORR_* (include/tsf.h): per-group outcome of the residual-correlation estimator
+CORR_OK, CORR_NO_PAIRS = 0, -50
 
 # TSF_ROUTE_* / TSF_CALL_* / TSF_PLAN_* (include/tsf_dev.h): a fit plan's route, the kind of call, why a call has no plan
 ROUTE_NEWTON, ROUTE_NEWTON_QUAD, ROUTE_QUAD_EVAL, ROUTE_QUAD_LBFGS, ROUTE_MFMA, ROUTE_WAVE = range(6)
@@ -303,6 +317,9 @@ def load():
     L.tsf_rollup_set_totals.argtypes = L.tsf_rollup_add.argtypes
     L.tsf_rollup_reconcile.argtypes = L.tsf_rollup_add.argtypes + [vp, i32, vp, ctypes.POINTER(TsfReconcileOut)]
     L.tsf_rollup_reconciled_totals.argtypes = [vp, vp, i32, vp, ctypes.POINTER(TsfRollupOut)]
+    L.tsf_residual_corr.argtypes = [vp, i64, i32, vp, i32, vp, vp, i64, ctypes.POINTER(TsfCorrArgs), ctypes.POINTER(TsfCorrOut)]
+    L.tsf_residual_corr_dev.argtypes = L.tsf_residual_corr.argtypes + [vp]
+    L.tsf_rollup_set_noise_corr.argtypes = [vp, vp, vp]
     L.tsf_eval.argtypes = [vp, psp, i64, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     L.tsf_eval_quadratic.argtypes = [vp, psp, i64, i32, vp, vp, i32, vp, vp, vp, vp, vp]
     L.tsf_design.argtypes = [vp, psp, i32, vp, vp, vp, vp, vp]
@@ -390,6 +407,8 @@ def load():
         raise TsfError('tsf_screen_args / tsf_screen_out layout mismatch between _lib.py and libtsf_amd.so')
     if L.tsf_calib_args_size() != ctypes.sizeof(TsfCalibArgs) or L.tsf_calib_table_size() != ctypes.sizeof(TsfCalibTable):
         raise TsfError('tsf_calib_args / tsf_calib_table layout mismatch between _lib.py and libtsf_amd.so')
+    if L.tsf_corr_args_size() != ctypes.sizeof(TsfCorrArgs) or L.tsf_corr_out_size() != ctypes.sizeof(TsfCorrOut):
+        raise TsfError('tsf_corr_args / tsf_corr_out layout mismatch between _lib.py and libtsf_amd.so')
     if L.tsf_fit_plan_info_size() != ctypes.sizeof(TsfFitPlanInfo):
         raise TsfError('tsf_fit_plan_info layout mismatch between _lib.py and libtsf_amd.so')
     _lib = L

@@ -35,6 +35,7 @@
 #include "tsf_tune_kernels.h"
 #include "tsf_screen_kernels.h"
 #include "tsf_calib_kernels.h"
+#include "tsf_corr_kernels.h"
 #include "tsf_cv_plan.h"
 #include "tsf_fit_plan.h"
 
@@ -2163,6 +2164,13 @@ struct tsf_rollup {
     double *ytop;                   // [G][H]
     int32_t *d_has_top;             // [G] device copy of has_top
     std::vector<int32_t> has_top;   // [G] the group has a total (host; empty until the first set_totals)
+    // correlated noise (tsf_rollup_set_noise_corr): allocated by that call and not before
+    bool corr;                      // a correlation is set: adds go through rollup_add_corr_kernel
+    bool added;                     // an add of N > 0 series has reached the accumulators
+    double *d_corr_ab;              // [2][G] a = sqrt(1 - rho) - 1, then b = sqrt(rho)
+    int64_t *d_group_key;           // [G]
+    std::vector<double> corr_a, corr_b;     // the host copies
+    std::vector<int64_t> group_key;
 };
 
 static void rollup_release(tsf_rollup *r)
@@ -2173,6 +2181,8 @@ static void rollup_release(tsf_rollup *r)
     if (r->top) (void)hipFree(r->top);
     if (r->ytop) (void)hipFree(r->ytop);
     if (r->d_has_top) (void)hipFree(r->d_has_top);
+    if (r->d_corr_ab) (void)hipFree(r->d_corr_ab);
+    if (r->d_group_key) (void)hipFree(r->d_group_key);
     delete r;
 }
 
@@ -2191,6 +2201,7 @@ extern "C" int tsf_rollup_create(tsf_ctx *ctx, int64_t G, int32_t H, const int64
     r->ctx = ctx; r->G = G; r->H = H; r->S = n_samples; r->seed = seed;
     r->d_ds = nullptr; r->acc = nullptr; r->ysum = nullptr; r->poisoned = false;
     r->top = nullptr; r->ytop = nullptr; r->d_has_top = nullptr;
+    r->corr = false; r->added = false; r->d_corr_ab = nullptr; r->d_group_key = nullptr;
     const size_t gh = (size_t)G * H;
     hipError_t e = hipMalloc((void **)&r->d_ds, 8 * (size_t)H);
     if (e == hipSuccess) e = hipMalloc((void **)&r->acc, 8 * gh * n_samples);
@@ -2320,7 +2331,9 @@ struct RollupSeries {
 };
 
 // The work of tsf_rollup_add (into acc / ysum) and of tsf_rollup_set_totals (into top / ytop) once the call is
-// checked: the series' draws added to the cells of their groups by rollup_add_kernel.
+// checked: the series' draws added to the cells of their groups by rollup_add_kernel -- on a handle with a noise
+// correlation set (tsf_rollup_add only: set_totals is refused there) by rollup_add_corr_kernel, after one
+// rollup_noise_scale_kernel over the call's series.
 static int rollup_accumulate(tsf_rollup *r, const tsf_spec *spec, int64_t N, const double *theta, const double *y_scale,
                              const tsf_grid_info *grid, int32_t n_grids, const double *floor_, const double *cap,
                              const double *extra_future, int32_t shared_extra, const int64_t *series_key,
@@ -2338,8 +2351,9 @@ static int rollup_accumulate(tsf_rollup *r, const tsf_spec *spec, int64_t N, con
     RollupSeries in;
     if (int rc = in.upload(r, spec, N, theta, y_scale, grid, n_grids, floor_, cap, extra_future, shared_extra, series_key))
         return rc;
-    DevBuf d_yh, d_csr;
+    DevBuf d_yh, d_csr, d_sn;
     HIP_TRY(ctx, d_yh.alloc(8 * (size_t)N * H));
+    if (r->corr) HIP_TRY(ctx, d_sn.alloc(8 * (size_t)N));
     const size_t n_t = P.touched.size(), n_f = P.first.size();
     HIP_TRY(ctx, d_csr.alloc(4 * (n_t + n_f + (size_t)N)));
     int32_t *d_touched = d_csr.as<int32_t>(), *d_first = d_touched + n_t, *d_member = d_first + n_f;
@@ -2351,14 +2365,25 @@ static int rollup_accumulate(tsf_rollup *r, const tsf_spec *spec, int64_t N, con
     RollupAddArgs ra;
     memset(&ra, 0, sizeof(ra));
     ra.acc = acc; ra.ysum = ysum; ra.H = H; ra.NS = S;
+    if (r->corr) {
+        hipLaunchKernelGGL(rollup_noise_scale_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, nullptr, in.up.dev.theta,
+                           tsf_theta_stride(spec), in.up.dev.y_scale, N, d_sn.as<double>());
+        HIP_TRY(ctx, hipGetLastError());
+    }
     auto after = [&](int64_t n0, int64_t nc, const DrawBufs &b) -> int {
         const size_t c = (size_t)(n0 / chunk);
         const size_t n_touched = (c + 1 < P.t0.size() ? P.t0[c + 1] : n_t) - P.t0[c];
         ra.samples = b.samp; ra.yhat = d_yh.as<double>() + (size_t)n0 * H;
         ra.touched = d_touched + P.t0[c]; ra.first = d_first + P.f0[c]; ra.member = d_member + n0;
         (void)nc;
-        hipLaunchKernelGGL(rollup_add_kernel, dim3((unsigned)(n_touched * (size_t)H), (unsigned)((S + 255) / 256)), dim3(256), 0,
-                           nullptr, ra);
+        const dim3 grid((unsigned)(n_touched * (size_t)H), (unsigned)((S + 255) / 256));
+        if (r->corr) {
+            const RollupCorrArgs rc = {ra, r->d_corr_ab, r->d_corr_ab + r->G, r->d_group_key, d_sn.as<double>() + n0,
+                                       in.up.dev.series_key + n0, r->seed};
+            hipLaunchKernelGGL(rollup_add_corr_kernel, grid, dim3(256), 0, nullptr, rc);
+        } else {
+            hipLaunchKernelGGL(rollup_add_kernel, grid, dim3(256), 0, nullptr, ra);
+        }
         HIP_TRY(ctx, hipGetLastError());
         return 0;
     };
@@ -2387,6 +2412,187 @@ extern "C" int tsf_rollup_add(tsf_rollup *r, const tsf_spec *spec, int64_t N, co
                                    series_key, group, r->acc, r->ysum))
         return rc;
     for (int64_t n = 0; n < N; ++n) r->count[(size_t)group[n]] += 1;
+    r->added = true;
+    return 0;
+}
+
+// ---- correlated group roll-ups: the residual correlation of a group, and the add that draws with it -------------
+
+extern "C" int tsf_corr_args_size(void) { return (int)sizeof(tsf_corr_args); }
+extern "C" int tsf_corr_out_size(void) { return (int)sizeof(tsf_corr_out); }
+
+// What both estimator entries check before anything is launched; group and args are host memory in both.  *a: the
+// arguments in force (the defaults where args is NULL).
+static int check_corr_call(tsf_ctx *ctx, int64_t N, int32_t T, const void *y, int32_t y_dtype, const double *fitted,
+                           const int64_t *group, int64_t G, const tsf_corr_args *args, const tsf_corr_out *out,
+                           tsf_corr_args *a)
+{
+    if (N < 0 || N > (int64_t)INT32_MAX) return fail(ctx, "N must be in [0, 2^31 - 1]");
+    if (G < 1 || G > (int64_t)INT32_MAX) return fail(ctx, "G must be in [1, 2^31 - 1]");
+    if (T < 1) return fail(ctx, "T must be >= 1 (aligned panels only)");
+    if (!out || !out->rho || !out->status) return fail(ctx, "NULL output (tsf_corr_out, its rho and its status are required)");
+    a->rho_max = 0.95; a->min_rows = 8;
+    if (args) *a = *args;
+    if (!(a->rho_max >= 0.0 && a->rho_max <= 1.0)) return fail(ctx, "rho_max must be in [0, 1]");
+    if (a->min_rows < 2) return fail(ctx, "min_rows must be >= 2");
+    if (y_dtype < TSF_Y_F64 || y_dtype > TSF_Y_I32) return fail(ctx, "bad y_dtype");
+    if (N > 0 && (!y || !fitted || !group)) return fail(ctx, "NULL input (y, fitted and group are required)");
+    for (int64_t n = 0; n < N; ++n)
+        if (group[n] < -1 || group[n] >= G) {
+            char msg[120];
+            snprintf(msg, sizeof(msg), "group[%lld] = %lld: outside [-1, G = %lld)", (long long)n, (long long)group[n],
+                     (long long)G);
+            return fail(ctx, msg);
+        }
+    const int64_t row_blocks = ((int64_t)T + 255) / 256;
+    if (G * row_blocks > (int64_t)INT32_MAX) return fail(ctx, "G * ceil(T / 256) must be < 2^31");
+    return 0;
+}
+
+// The estimator on device-resident y and fitted; o: device pointers (rho and status required).  The members' CSR is
+// built here, on the host, from the host's group (sorted by group, then by series index, as rollup_plan sorts).  Ends
+// with a synchronisation of the stream: its scratch goes back to the pool.
+static int corr_run(tsf_ctx *ctx, int64_t N, int32_t T, const void *d_y, int32_t y_dtype, const double *d_fit,
+                    const int64_t *group, int64_t G, const tsf_corr_args &a, const tsf_corr_out &o, hipStream_t st)
+{
+    std::vector<int32_t> csr;
+    try {
+        csr.assign((size_t)G + 1 + (size_t)N, 0);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, "tsf_residual_corr: out of host memory");
+    }
+    int32_t *first = csr.data(), *member = first + G + 1;
+    for (int64_t n = 0; n < N; ++n)
+        if (group[n] >= 0) first[group[n] + 1] += 1;
+    for (int64_t g = 0; g < G; ++g) first[g + 1] += first[g];
+    {
+        std::vector<int32_t> at(first, first + G);
+        for (int64_t n = 0; n < N; ++n)
+            if (group[n] >= 0) member[at[(size_t)group[n]]++] = (int32_t)n;    // ascending n within a group
+    }
+    const size_t nt = (size_t)N * T, gt = (size_t)G * T;
+    DevBuf d_csr, d_scale, d_e, d_c, d_p;
+    HIP_TRY(ctx, d_csr.alloc(4 * csr.size()));
+    HIP_TRY(ctx, hipMemcpy(d_csr.p, csr.data(), 4 * csr.size(), hipMemcpyHostToDevice));
+    double *scale = o.scale;
+    if (!scale) { HIP_TRY(ctx, d_scale.alloc(8 * (size_t)N)); scale = d_scale.as<double>(); }
+    HIP_TRY(ctx, d_e.alloc(8 * nt));
+    HIP_TRY(ctx, d_c.alloc(8 * gt));
+    HIP_TRY(ctx, d_p.alloc(8 * gt));
+    const int32_t *d_first = d_csr.as<int32_t>(), *d_member = d_first + G + 1;
+    if (N > 0) {
+        const CorrScaleArgs s = {d_y, d_fit, N, T, y_dtype, a.min_rows, scale, d_e.as<double>()};
+        hipLaunchKernelGGL(corr_scale_kernel, dim3((unsigned)((N + CORR_WAVES - 1) / CORR_WAVES)), dim3(CORR_WAVES * 64), 0, st, s);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    const int32_t row_blocks = (T + 255) / 256;
+    const CorrRowsArgs w = {d_e.as<double>(), d_first, d_member, T, row_blocks, d_c.as<double>(), d_p.as<int64_t>()};
+    hipLaunchKernelGGL(corr_rows_kernel, dim3((unsigned)(G * row_blocks)), dim3(256), 0, st, w);
+    HIP_TRY(ctx, hipGetLastError());
+    const CorrGroupArgs k = {d_c.as<double>(), d_p.as<int64_t>(), scale, d_first, d_member, G, T, a.rho_max,
+                             o.rho, o.rho_raw, o.n_pairs, o.n_used, o.status};
+    hipLaunchKernelGGL(corr_group_kernel, dim3((unsigned)((G + CORR_WAVES - 1) / CORR_WAVES)), dim3(CORR_WAVES * 64), 0, st, k,
+                       (int)TSF_CORR_OK, (int)TSF_CORR_NO_PAIRS);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int tsf_residual_corr_dev(tsf_ctx *ctx, int64_t N, int32_t T, const void *y, int32_t y_dtype, const double *fitted,
+                                     const int64_t *group, int64_t G, const tsf_corr_args *args, tsf_corr_out *out,
+                                     void *stream)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    tsf_corr_args a;
+    if (int rc = check_corr_call(ctx, N, T, y, y_dtype, fitted, group, G, args, out, &a)) return rc;
+    return corr_run(ctx, N, T, y, y_dtype, fitted, group, G, a, *out, (hipStream_t)stream);
+}
+
+extern "C" int tsf_residual_corr(tsf_ctx *ctx, int64_t N, int32_t T, const void *y, int32_t y_dtype, const double *fitted,
+                                 const int64_t *group, int64_t G, const tsf_corr_args *args, tsf_corr_out *out)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    tsf_corr_args a;
+    if (int rc = check_corr_call(ctx, N, T, y, y_dtype, fitted, group, G, args, out, &a)) return rc;
+    const size_t nt = (size_t)N * T, ysz = ysize(y_dtype), g = (size_t)G, n = (size_t)N;
+    DevBuf d_y, d_fit, d_rho, d_raw, d_np, d_nu, d_st, d_sc;
+    HIP_TRY(ctx, d_y.alloc(ysz * nt));
+    HIP_TRY(ctx, d_fit.alloc(8 * nt));
+    if (nt) {
+        HIP_TRY(ctx, hipMemcpy(d_y.p, y, ysz * nt, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(d_fit.p, fitted, 8 * nt, hipMemcpyHostToDevice));
+    }
+    tsf_corr_out o;
+    memset(&o, 0, sizeof(o));
+    HIP_TRY(ctx, d_rho.alloc(8 * g)); o.rho = d_rho.as<double>();
+    HIP_TRY(ctx, d_st.alloc(4 * g)); o.status = d_st.as<int32_t>();
+    if (out->rho_raw) { HIP_TRY(ctx, d_raw.alloc(8 * g)); o.rho_raw = d_raw.as<double>(); }
+    if (out->n_pairs) { HIP_TRY(ctx, d_np.alloc(8 * g)); o.n_pairs = d_np.as<int64_t>(); }
+    if (out->n_used) { HIP_TRY(ctx, d_nu.alloc(4 * g)); o.n_used = d_nu.as<int32_t>(); }
+    if (out->scale) { HIP_TRY(ctx, d_sc.alloc(8 * n)); o.scale = d_sc.as<double>(); }
+    if (int rc = corr_run(ctx, N, T, d_y.p, y_dtype, d_fit.as<double>(), group, G, a, o, nullptr)) return rc;
+    HIP_TRY(ctx, hipMemcpy(out->rho, d_rho.p, 8 * g, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(out->status, d_st.p, 4 * g, hipMemcpyDeviceToHost));
+    if (out->rho_raw) HIP_TRY(ctx, hipMemcpy(out->rho_raw, d_raw.p, 8 * g, hipMemcpyDeviceToHost));
+    if (out->n_pairs) HIP_TRY(ctx, hipMemcpy(out->n_pairs, d_np.p, 8 * g, hipMemcpyDeviceToHost));
+    if (out->n_used) HIP_TRY(ctx, hipMemcpy(out->n_used, d_nu.p, 4 * g, hipMemcpyDeviceToHost));
+    if (out->scale && n) HIP_TRY(ctx, hipMemcpy(out->scale, d_sc.p, 8 * n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+static const char *const ROLLUP_CORR_NO_RECONCILE =
+    "the roll-up has a noise correlation set (tsf_rollup_set_noise_corr): reconciling correlated draws is not supported";
+
+extern "C" int tsf_rollup_set_noise_corr(tsf_rollup *r, const double *rho, const int64_t *group_key)
+{
+    if (!r) return -1;
+    tsf_ctx *ctx = r->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (r->poisoned) return fail(ctx, ROLLUP_POISONED);
+    if (r->added || r->top)
+        return fail(ctx, "tsf_rollup_set_noise_corr after a tsf_rollup_add or tsf_rollup_set_totals: a correlation is set on an "
+                         "empty roll-up");
+    if (!rho) return fail(ctx, "NULL rho");
+    const size_t G = (size_t)r->G;
+    for (size_t g = 0; g < G; ++g)
+        if (!(rho[g] >= 0.0 && rho[g] <= 1.0)) {
+            char msg[120];
+            snprintf(msg, sizeof(msg), "rho[%lld] = %g: a correlation must be finite and in [0, 1]", (long long)g, rho[g]);
+            return fail(ctx, msg);
+        }
+    std::vector<double> ab;
+    std::vector<int64_t> key;
+    try {
+        ab.resize(2 * G);
+        key.resize(G);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, "tsf_rollup_set_noise_corr: out of host memory");
+    }
+    for (size_t g = 0; g < G; ++g) {
+        ab[g] = std::sqrt(1.0 - rho[g]) - 1.0;
+        ab[G + g] = std::sqrt(rho[g]);
+        key[g] = group_key ? group_key[g] : (int64_t)g;
+    }
+    double *d_ab = r->d_corr_ab;
+    int64_t *d_key = r->d_group_key;
+    hipError_t e = hipSuccess;
+    if (!d_ab) e = hipMalloc((void **)&d_ab, 16 * G);
+    if (e == hipSuccess && !d_key) e = hipMalloc((void **)&d_key, 8 * G);
+    if (e == hipSuccess) e = hipMemcpy(d_ab, ab.data(), 16 * G, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_key, key.data(), 8 * G, hipMemcpyHostToDevice);
+    r->d_corr_ab = d_ab; r->d_group_key = d_key;            // (the handle owns whatever was allocated)
+    if (e != hipSuccess) {
+        ctx->err = std::string("tsf_rollup_set_noise_corr: ") + hipGetErrorString(e);
+        (void)hipGetLastError();
+        if (r->corr) r->poisoned = true;        // (an earlier table may be half overwritten)
+        return -2;
+    }
+    r->corr_a.assign(ab.begin(), ab.begin() + (std::ptrdiff_t)G);
+    r->corr_b.assign(ab.begin() + (std::ptrdiff_t)G, ab.end());
+    r->group_key.swap(key);
+    r->corr = true;
     return 0;
 }
 
@@ -2755,6 +2961,7 @@ extern "C" int tsf_rollup_set_totals(tsf_rollup *r, const tsf_spec *spec, int64_
     tsf_ctx *ctx = r->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (r->poisoned) return fail(ctx, ROLLUP_POISONED);
+    if (r->corr) return fail(ctx, ROLLUP_CORR_NO_RECONCILE);
     if (Gt < 0) return fail(ctx, "N must be >= 0");
     if (Gt == 0) return 0;
     if (int rc = rollup_check_series(r, spec, Gt, theta, y_scale, grid, n_grids, cap, extra_future, series_key, group))
@@ -2830,6 +3037,7 @@ extern "C" int tsf_rollup_reconcile(tsf_rollup *r, const tsf_spec *spec, int64_t
     tsf_ctx *ctx = r->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (r->poisoned) return fail(ctx, ROLLUP_POISONED);
+    if (r->corr) return fail(ctx, ROLLUP_CORR_NO_RECONCILE);
     if (N < 0) return fail(ctx, "N must be >= 0");
     if (N == 0) return 0;
     if (!r->top) return fail(ctx, "tsf_rollup_reconcile before any tsf_rollup_set_totals: the roll-up has no total");
@@ -2914,6 +3122,7 @@ extern "C" int tsf_rollup_reconciled_totals(tsf_rollup *r, const double *share_t
     tsf_ctx *ctx = r->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (r->poisoned) return fail(ctx, ROLLUP_POISONED);
+    if (r->corr) return fail(ctx, ROLLUP_CORR_NO_RECONCILE);
     if (!r->top)
         return fail(ctx, "tsf_rollup_reconciled_totals before any tsf_rollup_set_totals: the roll-up has no total");
     if (!share_total) return fail(ctx, "NULL share_total");

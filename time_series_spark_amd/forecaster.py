@@ -1160,8 +1160,9 @@ def predict_windows(spec, theta, y_scale, grid, ds_future_ns, windows, quantiles
 
 # ---- group roll-ups: predictive quantiles of sums over series --------------------------------------
 # The distribution of a total over several series (include/tsf.h "group roll-ups"): the members' draws summed sample by
-# sample on the device, across specs and calls, then sorted.  Members are taken as independent given their fits: where
-# their errors are positively correlated in reality the spread is too narrow.
+# sample on the device, across specs and calls, then sorted.  By default members are taken as independent given their
+# fits: where their errors are positively correlated in reality the spread is too narrow.  residual_correlation
+# estimates each group's correlation from the fits' history and Rollup(noise_corr=) draws with it.
 
 def rollup_groups(labels):
     """Group labels -> (unique_sorted_labels, dense_index int64 [N]): the `group` argument of Rollup.add.  labels: one
@@ -1206,6 +1207,94 @@ class RollupQuantiles(object):
         return pd.DataFrame(cols, columns=list(cols))
 
 
+class NoiseCorrelation(object):
+    """What residual_correlation returns: per group rho [G] (clipped to [0, rho_max]: what Rollup(noise_corr=) takes),
+    rho_raw [G] (NaN without pairs), n_pairs [G] int64, n_used [G] int32, status [G] (_lib.CORR_*); per series scale [N]
+    (the residual root mean square; NaN: the series is unused)."""
+
+    def __init__(self, rho, rho_raw, n_pairs, n_used, status, scale):
+        self.rho, self.rho_raw, self.n_pairs, self.n_used, self.status, self.scale = rho, rho_raw, n_pairs, n_used, status, scale
+
+    def frame(self, labels=None):
+        """One row per group: group (the dense index, or `labels` [G]: rollup_groups' unique labels), rho, rho_raw,
+        n_pairs, n_used, status."""
+        import pandas as pd
+        G = len(self.rho)
+        group = np.arange(G, dtype=np.int64) if labels is None else np.asarray(labels)
+        if group.shape[0] != G:
+            raise ValueError('labels must be [n_groups]')
+        cols = {'group': list(group) if group.ndim > 1 else group, 'rho': self.rho, 'rho_raw': self.rho_raw,
+                'n_pairs': self.n_pairs, 'n_used': self.n_used, 'status': self.status}
+        return pd.DataFrame(cols, columns=list(cols))
+
+
+def _corr_args(rho_max, min_rows):
+    """tsf_corr_args, refused here as the library refuses them (before it is loaded)."""
+    if not 0.0 <= rho_max <= 1.0:
+        raise ValueError('rho_max must be in [0, 1]')
+    if int(min_rows) != min_rows or min_rows < 2:
+        raise ValueError('min_rows must be an integer >= 2')
+    a = _lib.TsfCorrArgs()
+    a.rho_max, a.min_rows, a.reserved_ = float(rho_max), int(min_rows), 0
+    return a
+
+
+def residual_correlation(y, fitted, group, n_groups, rho_max=0.95, min_rows=8, ctx=None):
+    """The residual correlation of each group (include/tsf.h tsf_residual_corr) of an aligned panel: y [N][T] (float64 /
+    float32 / int32), fitted [N][T] (each fit's forecast of its own history: fitted_history), group [N] dense indices in
+    [0, n_groups) or -1 for a series that takes no part.  Per series the residuals are standardised by their root mean
+    square over the finite rows; per group rho_raw is the mean of e_i e_j over the member pairs and rows where both are
+    present, rho its clip to [0, rho_max].  Returns a NoiseCorrelation."""
+    y = np.ascontiguousarray(y)
+    if y.ndim != 2 or y.shape[1] < 1:
+        raise ValueError('y must be [N][T], T >= 1 (aligned panels only)')
+    N, T = y.shape
+    fitted = np.ascontiguousarray(fitted, dtype=np.float64)
+    if fitted.shape != y.shape:
+        raise ValueError('fitted must have the shape of y')
+    G = int(n_groups)
+    if G < 1:
+        raise ValueError('n_groups must be >= 1')
+    group = np.ascontiguousarray(group, dtype=np.int64)
+    if group.shape != (N,):
+        raise ValueError('group must be [N]')
+    if N and (group.min() < -1 or group.max() >= G):
+        raise ValueError('group values must be in [-1, %d)' % G)
+    code = _lib.y_dtype_code(y)
+    a = _corr_args(rho_max, min_rows)
+    ctx = ctx or get_context()
+    rho, raw, scale = np.zeros(G), np.zeros(G), np.zeros(N)
+    n_pairs, n_used, status = np.zeros(G, np.int64), np.zeros(G, np.int32), np.zeros(G, np.int32)
+    out = _lib.TsfCorrOut(rho.ctypes.data, raw.ctypes.data, n_pairs.ctypes.data, n_used.ctypes.data, status.ctypes.data,
+                          scale.ctypes.data)
+    ctx.check(_lib.load().tsf_residual_corr(ctx.handle, N, T, y.ctypes.data, code, fitted.ctypes.data, group.ctypes.data, G,
+                                            ctypes.byref(a), ctypes.byref(out)))
+    return NoiseCorrelation(rho, raw, n_pairs, n_used, status, scale)
+
+
+def fit_residual_correlation(spec, res, ds_ns, y, group, n_groups, floor=None, cap=None, extra=None, rho_max=0.95,
+                             min_rows=8, ctx=None):
+    """residual_correlation of an aligned panel's fits `res` (fit_aligned's FitResult of this panel): fitted is predict on
+    the history's own dates ds_ns [T] (fitted_history)."""
+    fitted = fitted_history(spec, res, ds_ns, None, floor, cap, extra, ctx=ctx)
+    return residual_correlation(y, fitted, group, n_groups, rho_max=rho_max, min_rows=min_rows, ctx=ctx)
+
+
+def _noise_corr_args(noise_corr, group_key, G):
+    """(rho [G], group_key [G] or None) of Rollup(noise_corr=, group_key=); every error is a ValueError raised here."""
+    rho = noise_corr.rho if isinstance(noise_corr, NoiseCorrelation) else noise_corr
+    rho = np.ascontiguousarray(rho, dtype=np.float64)
+    if rho.shape != (G,):
+        raise ValueError('noise_corr must be [n_groups] (or a NoiseCorrelation of n_groups groups)')
+    if not (np.isfinite(rho).all() and rho.min() >= 0.0 and rho.max() <= 1.0):
+        raise ValueError('noise_corr values must be finite and in [0, 1]')
+    if group_key is not None:
+        group_key = np.ascontiguousarray(group_key, dtype=np.int64)
+        if group_key.shape != (G,):
+            raise ValueError('group_key must be [n_groups]')
+    return rho, group_key
+
+
 def _rollup_add_args(spec, theta, y_scale, grid, group, series_key, floor, cap, extra_future, G, H):
     """The arguments of one Rollup.add as the library takes them; every shape error is a ValueError raised here, before
     the library is touched."""
@@ -1246,9 +1335,12 @@ class Rollup(object):
     add (once per spec, any number of calls) and read by quantiles / samples at any time.  A context manager; close()
     frees the device memory (before its context is closed).  Shape and level errors raise ValueError before the library
     is touched.  Where the totals are fitted directly as well: set_totals, then reconcile (the members) and
-    reconciled_totals (include/tsf.h "reconciliation")."""
+    reconciled_totals (include/tsf.h "reconciliation").  noise_corr: rho [n_groups] in [0, 1] or a NoiseCorrelation
+    (residual_correlation) -- the members' observation noise is then drawn with that correlation within each group
+    (include/tsf.h "correlated group roll-ups"; group_key [n_groups]: the keys of the groups' factor streams, default the
+    group index); such a roll-up cannot be reconciled.  None: the members are independent, as always."""
 
-    def __init__(self, ds_future_ns, n_groups, uncertainty_samples=1000, seed=0, ctx=None):
+    def __init__(self, ds_future_ns, n_groups, uncertainty_samples=1000, seed=0, ctx=None, noise_corr=None, group_key=None):
         self._h = None
         ds = np.ascontiguousarray(ds_future_ns, dtype=np.int64)
         if ds.ndim != 1 or ds.shape[0] < 1:
@@ -1259,11 +1351,22 @@ class Rollup(object):
             raise ValueError('uncertainty_samples must be in [2, 4096]')
         self.ds_future_ns, self.G, self.H, self.S = ds, int(n_groups), ds.shape[0], int(uncertainty_samples)
         self.seed = int(seed)
+        if noise_corr is None and group_key is not None:
+            raise ValueError('group_key without noise_corr')
+        corr = None if noise_corr is None else _noise_corr_args(noise_corr, group_key, self.G)
         self._ctx = ctx or get_context()
         h = ctypes.c_void_p()
         self._ctx.check(_lib.load().tsf_rollup_create(self._ctx.handle, self.G, self.H, ds.ctypes.data, self.S, self.seed,
                                                       ctypes.byref(h)))
         self._h = h
+        if corr is not None:
+            self.set_noise_corr(*corr)
+
+    def set_noise_corr(self, rho, group_key=None):
+        """tsf_rollup_set_noise_corr: rho [n_groups] in [0, 1] (or a NoiseCorrelation), before anything is added."""
+        h = self._handle()
+        rho, group_key = _noise_corr_args(rho, group_key, self.G)
+        self._ctx.check(_lib.load().tsf_rollup_set_noise_corr(h, rho.ctypes.data, _lib._ptr(group_key)))
 
     def _handle(self):
         if not self._h:
@@ -1538,9 +1641,10 @@ def predict_reconciled(spec, theta, y_scale, grid, ds_future_ns, labels, quantil
 
 
 def predict_rollup(spec, theta, y_scale, grid, ds_future_ns, labels, quantiles, series_key, floor=None, cap=None,
-                   extra_future=None, uncertainty_samples=1000, seed=0, cumulative=False, ctx=None):
+                   extra_future=None, uncertainty_samples=1000, seed=0, cumulative=False, ctx=None, noise_corr=None,
+                   group_key=None):
     """The one-spec convenience: rollup_groups(labels), one Rollup.add, quantiles, close ->
-    (unique_labels, RollupQuantiles)."""
+    (unique_labels, RollupQuantiles).  noise_corr, group_key: as in Rollup, per unique label in sorted order."""
     quantile_columns(quantiles)
     if len(np.asarray(quantiles).reshape(-1)) == 0:
         raise ValueError('at least one quantile level')
@@ -1551,7 +1655,8 @@ def predict_rollup(spec, theta, y_scale, grid, ds_future_ns, labels, quantiles, 
     if ds.ndim != 1 or ds.shape[0] < 1:
         raise ValueError('ds_future must be [H], H >= 1: a roll-up has one calendar')
     _rollup_add_args(spec, theta, y_scale, grid, group, series_key, floor, cap, extra_future, len(uniq), ds.shape[0])
-    with Rollup(ds_future_ns, len(uniq), uncertainty_samples=uncertainty_samples, seed=seed, ctx=ctx) as r:
+    with Rollup(ds_future_ns, len(uniq), uncertainty_samples=uncertainty_samples, seed=seed, ctx=ctx, noise_corr=noise_corr,
+                group_key=group_key) as r:
         r.add(spec, theta, y_scale, grid, group, series_key, floor=floor, cap=cap, extra_future=extra_future)
         return uniq, r.quantiles(quantiles, cumulative=cumulative)
 
