@@ -104,6 +104,18 @@ def test_rule_ignores_row_order_and_the_rest_of_the_batch(env, rows, mode):
         assert cr.same(one.q[0], base.q[n]) and cr.same(one.n[0], base.n[n]) and one.status[0] == base.status[n]
 
 
+@pytest.mark.parametrize('mode', ['abs', 'cqr'])
+def test_rule_without_rows(env, mode):
+    """row_off[N] = 0: three series, no out-of-sample row -- nothing is copied in, every cell is empty"""
+    fc, _lib = env
+    none = np.zeros((2, 0))
+    got = fc.calibrate_rows(np.zeros(4, np.int64), np.zeros(0, np.int64), np.zeros(0), np.zeros(0), [0.8, 0.95], mode=mode,
+                            lower=none if mode == 'cqr' else None, upper=none if mode == 'cqr' else None, horizon=20 * DAY,
+                            n_buckets=4, min_scores=3)
+    assert got.q.shape == (3, 5, 2) and np.isnan(got.q).all() and not got.n.any()
+    assert list(got.status) == [_lib.CALIB_NO_SCORES] * 3 and _lib.CALIB_NO_SCORES == -40
+
+
 def test_rule_longest_series(env):
     """TSF_CALIB_MAX_ROWS rows and one row more than half of it: the launch class whose LDS goes beyond the default"""
     fc, _lib = env

@@ -88,6 +88,15 @@ def test_estimator_bit_for_bit(env, dtype, T):
     assert list(got.frame().columns) == ['group', 'rho', 'rho_raw', 'n_pairs', 'n_used', 'status']
 
 
+def test_estimator_without_series(env):
+    """N = 0: nothing is copied in, every group is without pairs, and scale has no element to copy back"""
+    fc, _lib = env
+    got = fc.residual_correlation(np.zeros((0, 40)), np.zeros((0, 40)), np.zeros(0, np.int64), 3)
+    assert list(got.status) == [_lib.CORR_NO_PAIRS] * 3 and _lib.CORR_NO_PAIRS == -50
+    assert list(got.rho) == [0.0] * 3 and np.isnan(got.rho_raw).all()
+    assert list(got.n_pairs) == [0] * 3 and list(got.n_used) == [0] * 3 and got.scale.shape == (0,)
+
+
 def test_estimator_dev_variant_agrees(env):
     """tsf_residual_corr_dev on device pointers (plain hipMalloc blocks; group on the host) == the host variant"""
     fc, _lib = env

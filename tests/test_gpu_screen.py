@@ -107,6 +107,16 @@ def test_rule_ragged_lengths_together(env, dtype):
     assert list(got.status[[3, 7]]) == [_lib.SCREEN_TOO_FEW] * 2 and got.n_new.sum() > 0
 
 
+def test_rule_ragged_panel_without_rows(env):
+    """offsets all zero: three series, no row at all -- nothing is copied either way, every series too short"""
+    fc, _lib = env
+    got = fc.screen_rows(np.zeros(0), np.zeros(0), offsets=np.zeros(4, np.int64), threshold=3.0, max_share=0.1, min_rows=5)
+    assert got.flag.shape == (0,) and got.resid.shape == (0,)
+    assert list(got.status) == [_lib.SCREEN_TOO_FEW] * 3 and _lib.SCREEN_TOO_FEW == -30
+    assert np.isnan(got.center).all() and np.isnan(got.scale).all()
+    assert list(got.n_new) == [0, 0, 0] and list(got.n_flagged) == [0, 0, 0]
+
+
 def test_rule_longest_series_and_too_long(env):
     fc, _lib = env
     lengths = [_lib.SCREEN_MAX_ROWS, _lib.SCREEN_MAX_ROWS + 1, 100]

@@ -402,6 +402,9 @@ def test_rollup_windows(env, n_samples):
         sub = roll._windows_call(w, fc.window_totals(y_rows, w), LEVELS, ('coverage', 'mean_crps'))
         assert set(sub) == {'coverage', 'mean_crps'}
         assert sr.same(sub['coverage'], r2.coverage) and sr.same(sub['mean_crps'], r2.mean_crps)
+        # yhat alone: the handle's own sums, copied out with no buffer and no launch of the call's own
+        alone = roll._windows_call(w, None, [], ('yhat',))
+        assert set(alone) == {'yhat'} and sr.same(alone['yhat'], q2.yhat)
         with pytest.raises(ValueError, match='behind'):
             roll.windows(fc.row_windows(H + 1, 7), LEVELS)
         with pytest.raises(ValueError, match='y_obs must be'):

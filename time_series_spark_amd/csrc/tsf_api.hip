@@ -12,7 +12,9 @@
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -898,6 +900,9 @@ struct DevBuf {
     void *p = nullptr;
     size_t bytes = 0;
     int device = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;            // (the destructor hands p to the pool: one owner)
+    DevBuf &operator=(const DevBuf &) = delete;
     ~DevBuf()
     {
         if (!p) return;
@@ -923,14 +928,80 @@ struct DevBuf {
         }
         return hipMalloc(&p, bytes);
     }
-    // alloc + the n bytes at the host pointer src copied in
+    // alloc + the n bytes at the host pointer src copied in (n = 0: the buffer alone, nothing is copied)
     hipError_t put(const void *src, size_t n)
     {
         const hipError_t e = alloc(n);
-        return e != hipSuccess ? e : hipMemcpy(p, src, n, hipMemcpyHostToDevice);
+        return e != hipSuccess || n == 0 ? e : hipMemcpy(p, src, n, hipMemcpyHostToDevice);
     }
     template <class T> T *as() const { return (T *)p; }
 };
+
+// The optional outputs of a host entry on the device and their way back: per output one `want` (the host pointer and its
+// size, said once), then one `fetch` behind the entry's synchronisation.  It lives in the entry's scope: the buffers go
+// back to the pool when it does.  (A deque: it never moves the DevBufs it holds.)
+struct HostOuts {
+    struct Pair { void *host; const void *dev; size_t bytes; };
+    std::deque<DevBuf> bufs;
+    std::vector<Pair> pairs;
+    hipError_t err = hipSuccess;        // the first failed allocation: every later want is null, ready and fetch report it
+
+    // a pooled device buffer of `bytes` for the output the caller wants at `host`; null, and no buffer, where host is null
+    template <class T> T *want(T *host, size_t bytes)
+    {
+        if (!host || err != hipSuccess) return nullptr;
+        bufs.emplace_back();
+        if ((err = bufs.back().alloc(bytes)) != hipSuccess) return nullptr;
+        return adopt(host, bufs.back().as<T>(), bytes);
+    }
+    // an output that is on the device already: dev is copied to host with the others
+    template <class T> T *adopt(T *host, T *dev, size_t bytes)
+    {
+        if (!host) return nullptr;
+        pairs.push_back({host, dev, bytes});
+        return dev;
+    }
+    // after the last want, before anything is launched
+    int ready(tsf_ctx *ctx) const
+    {
+        if (err == hipSuccess) return 0;
+        ctx->err = std::string("HostOuts::want: ") + hipGetErrorString(err);
+        return -2;
+    }
+    // every output asked for, in the order asked for, to its host pointer
+    int fetch(tsf_ctx *ctx) const
+    {
+        if (int rc = ready(ctx)) return rc;
+        for (const Pair &o : pairs)
+            if (o.bytes) HIP_TRY(ctx, hipMemcpy(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost));
+        return 0;
+    }
+};
+
+// Device memory a handle owns for its lifetime: plain hipMalloc / hipFree of the exact size (not the pool, whose
+// power-of-two classes would nearly double a large buffer), zero-filled where asked.  Reads as the pointer it holds.
+template <class T>
+struct OwnedDev {
+    T *p = nullptr;
+    OwnedDev() = default;
+    OwnedDev(const OwnedDev &) = delete;
+    OwnedDev &operator=(const OwnedDev &) = delete;
+    ~OwnedDev() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t n, bool zero = false)
+    {
+        const hipError_t e = hipMalloc((void **)&p, sizeof(T) * n);
+        return e != hipSuccess || !zero ? e : hipMemset(p, 0, sizeof(T) * n);
+    }
+    void swap(OwnedDev &o) { std::swap(p, o.p); }
+    operator T *() const { return p; }
+};
+
+// the first HIP error of a sequence of calls ends the function that holds them with that error
+#define HIP_OK(expr)                                                                         \
+    do {                                                                                     \
+        const hipError_t e_ = (expr);                                                        \
+        if (e_ != hipSuccess) return e_;                                                     \
+    } while (0)
 
 size_t ysize(int dt) { return dt == TSF_Y_F64 ? 8 : 4; }
 
@@ -1729,17 +1800,15 @@ extern "C" int tsf_predict_intervals(tsf_ctx *ctx, const tsf_spec *spec, int64_t
     if (int rc = up.upload(ctx, spec, h)) return rc;
     const ForecastIn &d = up.dev;
     const size_t nh = 8 * (size_t)N * H;
-    DevBuf d_yh, d_lo, d_hi;
-    HIP_TRY(ctx, d_yh.alloc(nh)); HIP_TRY(ctx, d_lo.alloc(nh)); HIP_TRY(ctx, d_hi.alloc(nh));
+    HostOuts outs;
+    double *d_yh = outs.want(yhat, nh), *d_lo = outs.want(yhat_lower, nh), *d_hi = outs.want(yhat_upper, nh);
+    if (int rc = outs.ready(ctx)) return rc;
     int rc = tsf_predict_intervals_dev(ctx, spec, N, H, d.theta, d.y_scale, d.grid, n_grids, d.ds_future, shared_future,
                                        d.floor_, d.cap, d.extra_future, d.series_key, n_samples, interval_width, seed,
-                                       d_yh.as<double>(), d_lo.as<double>(), d_hi.as<double>(), nullptr);
+                                       d_yh, d_lo, d_hi, nullptr);
     if (rc) return rc;
     HIP_TRY(ctx, hipDeviceSynchronize());
-    HIP_TRY(ctx, hipMemcpy(yhat, d_yh.p, nh, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(yhat_lower, d_lo.p, nh, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(yhat_upper, d_hi.p, nh, hipMemcpyDeviceToHost));
-    return 0;
+    return outs.fetch(ctx);
 }
 
 // ---- forecast components ------------------------------------------------------------------------------
@@ -1851,29 +1920,20 @@ extern "C" int tsf_predict_components(tsf_ctx *ctx, const tsf_spec *spec, int64_
     ForecastUpload up;
     if (int rc = up.upload(ctx, spec, h)) return rc;
     const ForecastIn &d = up.dev;
-    DevBuf d_yh, d_tr, d_co, d_lo, d_hi, d_tlo, d_thi;
+    // (comp without components and the interval outputs without samples are not outputs of the call: no buffer, no copy)
+    HostOuts outs;
     const size_t nh = 8 * (size_t)N * H;
-    HIP_TRY(ctx, d_yh.alloc(nh)); HIP_TRY(ctx, d_tr.alloc(nh));
-    if (n_comp > 0) HIP_TRY(ctx, d_co.alloc(nh * n_comp));
-    if (iv) { HIP_TRY(ctx, d_lo.alloc(nh)); HIP_TRY(ctx, d_hi.alloc(nh)); HIP_TRY(ctx, d_tlo.alloc(nh)); HIP_TRY(ctx, d_thi.alloc(nh)); }
+    double *d_yh = outs.want(yhat, nh), *d_tr = outs.want(trend, nh);
+    double *d_co = n_comp > 0 ? outs.want(comp, nh * n_comp) : nullptr;
+    double *d_lo = iv ? outs.want(yhat_lower, nh) : nullptr, *d_hi = iv ? outs.want(yhat_upper, nh) : nullptr;
+    double *d_tlo = iv ? outs.want(trend_lower, nh) : nullptr, *d_thi = iv ? outs.want(trend_upper, nh) : nullptr;
+    if (int rc = outs.ready(ctx)) return rc;
     int rc = tsf_predict_components_dev(ctx, spec, N, H, d.theta, d.y_scale, d.grid, n_grids, d.ds_future, shared_future,
                                         d.floor_, d.cap, d.extra_future, n_comp, comp_cols, comp_scaled, d.series_key,
-                                        n_samples, interval_width, seed, d_yh.as<double>(), d_tr.as<double>(),
-                                        n_comp > 0 ? d_co.as<double>() : nullptr,
-                                        iv ? d_lo.as<double>() : nullptr, iv ? d_hi.as<double>() : nullptr,
-                                        iv ? d_tlo.as<double>() : nullptr, iv ? d_thi.as<double>() : nullptr, nullptr);
+                                        n_samples, interval_width, seed, d_yh, d_tr, d_co, d_lo, d_hi, d_tlo, d_thi, nullptr);
     if (rc) return rc;
     HIP_TRY(ctx, hipDeviceSynchronize());
-    HIP_TRY(ctx, hipMemcpy(yhat, d_yh.p, nh, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(trend, d_tr.p, nh, hipMemcpyDeviceToHost));
-    if (n_comp > 0) HIP_TRY(ctx, hipMemcpy(comp, d_co.p, nh * n_comp, hipMemcpyDeviceToHost));
-    if (iv) {
-        HIP_TRY(ctx, hipMemcpy(yhat_lower, d_lo.p, nh, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(yhat_upper, d_hi.p, nh, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(trend_lower, d_tlo.p, nh, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(trend_upper, d_thi.p, nh, hipMemcpyDeviceToHost));
-    }
-    return 0;
+    return outs.fetch(ctx);
 }
 
 // ---- forecast quantiles, cumulative quantiles, predictive samples ----------------------------------------
@@ -1915,6 +1975,29 @@ struct QuantileCall {
     const double *quantiles;
 };
 
+// quantile_kernel with the levels of one call: the n_q quantiles of each of `count` * H rows of S sorted draws at src
+// (series or groups, the first of them number n0 of the call) into dst [..][n_q][H].  The one launch site of the kernel:
+// the forecast's chunks and the roll-up's group ranges.
+struct QuantilePass {
+    QuantileArgs q;
+    int NSP;
+
+    QuantilePass(int32_t H, int32_t S, int32_t n_q, const double *quantiles) : NSP(sort_width(S))
+    {
+        memset(&q, 0, sizeof(q));
+        q.H = H; q.NS = S; q.n_q = n_q;
+        for (int32_t i = 0; i < n_q; ++i) q.level[i] = quantiles[i];
+    }
+    int launch(tsf_ctx *ctx, const double *src, double *dst, int64_t n0, int64_t count, hipStream_t st) const
+    {
+        QuantileArgs a = q;
+        a.src = src; a.dst = dst; a.n0 = n0;
+        hipLaunchKernelGGL(quantile_kernel, dim3((unsigned)(count * a.H)), dim3(256), sizeof(double) * NSP, st, a, NSP);
+        HIP_TRY(ctx, hipGetLastError());
+        return 0;
+    }
+};
+
 // The work of both quantile entries on device-resident inputs.  The quantile outputs of `o` are device pointers; its
 // two sample outputs are copied out of the chunk's scratch in stream order with `kind` (device to device for the _dev
 // entry, device to host for the host entry, which therefore never holds N * H * n_samples values on the device).
@@ -1922,19 +2005,12 @@ static int predict_quantiles_run(tsf_ctx *ctx, const tsf_spec *spec, const Forec
                                  const tsf_quantile_out &o, hipMemcpyKind kind, hipStream_t st)
 {
     const int32_t H = f.H, n_samples = c.n_samples;
-    const int NSP = sort_width(n_samples);
-    QuantileArgs q;
-    memset(&q, 0, sizeof(q));
-    q.H = H; q.NS = n_samples; q.n_q = c.n_q;
-    for (int32_t i = 0; i < c.n_q; ++i) q.level[i] = c.quantiles[i];
+    const QuantilePass qp(H, n_samples, c.n_q, c.quantiles);
     auto after = [&](int64_t n0, int64_t nc, const DrawBufs &b) -> int {
         const struct { const double *src; double *dst; } sorts[3] = {{b.samp, o.q}, {b.cum, o.cum_q}, {b.trend, o.trend_q}};
-        for (const auto &so : sorts) {
-            if (!so.dst) continue;
-            q.src = so.src; q.dst = so.dst; q.n0 = n0;
-            hipLaunchKernelGGL(quantile_kernel, dim3((unsigned)(nc * H)), dim3(256), sizeof(double) * NSP, st, q, NSP);
-            HIP_TRY(ctx, hipGetLastError());
-        }
+        for (const auto &so : sorts)
+            if (so.dst)
+                if (int rc = qp.launch(ctx, so.src, so.dst, n0, nc, st)) return rc;
         // the raw draws leave the scratch before the next chunk overwrites it (stream order)
         const size_t off = (size_t)n0 * H * n_samples, nb = 8 * (size_t)nc * H * n_samples;
         if (o.samples) HIP_TRY(ctx, hipMemcpyAsync(o.samples + off, b.samp, nb, kind, st));
@@ -1976,26 +2052,17 @@ extern "C" int tsf_predict_quantiles(tsf_ctx *ctx, const tsf_spec *spec, int64_t
     if (int rc = check_quantile_args(ctx, n_samples, n_q, quantiles, out)) return rc;
     ForecastUpload up;
     if (int rc = up.upload(ctx, spec, h)) return rc;
-    DevBuf d_yh, d_q, d_cq, d_tq;
+    HostOuts outs;
     const size_t nh = 8 * (size_t)N * H, nqh = nh * (size_t)n_q;
-    HIP_TRY(ctx, d_yh.alloc(nh));
-    if (out->q) HIP_TRY(ctx, d_q.alloc(nqh));
-    if (out->cum_q) HIP_TRY(ctx, d_cq.alloc(nqh));
-    if (out->trend_q) HIP_TRY(ctx, d_tq.alloc(nqh));
     tsf_quantile_out o;
-    o.yhat = d_yh.as<double>();
-    o.q = out->q ? d_q.as<double>() : nullptr;
-    o.cum_q = out->cum_q ? d_cq.as<double>() : nullptr;
-    o.trend_q = out->trend_q ? d_tq.as<double>() : nullptr;
+    o.yhat = outs.want(out->yhat, nh);
+    o.q = outs.want(out->q, nqh); o.cum_q = outs.want(out->cum_q, nqh); o.trend_q = outs.want(out->trend_q, nqh);
     o.samples = out->samples; o.trend_samples = out->trend_samples;      // host: filled chunk by chunk
+    if (int rc = outs.ready(ctx)) return rc;
     int rc = predict_quantiles_run(ctx, spec, up.dev, {n_samples, seed, n_q, quantiles}, o, hipMemcpyDeviceToHost, nullptr);
     if (rc) return rc;
     HIP_TRY(ctx, hipDeviceSynchronize());
-    HIP_TRY(ctx, hipMemcpy(out->yhat, d_yh.p, nh, hipMemcpyDeviceToHost));
-    if (out->q) HIP_TRY(ctx, hipMemcpy(out->q, d_q.p, nqh, hipMemcpyDeviceToHost));
-    if (out->cum_q) HIP_TRY(ctx, hipMemcpy(out->cum_q, d_cq.p, nqh, hipMemcpyDeviceToHost));
-    if (out->trend_q) HIP_TRY(ctx, hipMemcpy(out->trend_q, d_tq.p, nqh, hipMemcpyDeviceToHost));
-    return 0;
+    return outs.fetch(ctx);
 }
 
 // ---- scoring observed values against the predictive distribution -------------------------------------------
@@ -2115,75 +2182,69 @@ extern "C" int tsf_score_actuals(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, 
         }
     ForecastUpload up;
     if (int rc = up.upload(ctx, spec, h)) return rc;
-    DevBuf d_y, d_yh, d_pit, d_crps, d_q, d_pb, d_no, d_mc, d_mp, d_cv;
+    DevBuf d_y;
+    HostOuts outs;
     const size_t nh = 8 * nhn, nqh = nh * (size_t)n_q, nq = 8 * (size_t)N * n_q;
-    HIP_TRY(ctx, d_y.alloc(nh));
-    HIP_TRY(ctx, hipMemcpy(d_y.p, y_obs, nh, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_yh.alloc(nh));
+    HIP_TRY(ctx, d_y.put(y_obs, nh));
     tsf_score_out o;
     memset(&o, 0, sizeof(o));
-    o.yhat = d_yh.as<double>();
-    if (out->pit) { HIP_TRY(ctx, d_pit.alloc(nh)); o.pit = d_pit.as<double>(); }
-    if (out->crps) { HIP_TRY(ctx, d_crps.alloc(nh)); o.crps = d_crps.as<double>(); }
-    if (out->q) { HIP_TRY(ctx, d_q.alloc(nqh)); o.q = d_q.as<double>(); }
-    if (out->pinball) { HIP_TRY(ctx, d_pb.alloc(nqh)); o.pinball = d_pb.as<double>(); }
-    if (out->n_obs) { HIP_TRY(ctx, d_no.alloc(4 * (size_t)N)); o.n_obs = d_no.as<int32_t>(); }
-    if (out->mean_crps) { HIP_TRY(ctx, d_mc.alloc(8 * (size_t)N)); o.mean_crps = d_mc.as<double>(); }
-    if (out->mean_pinball) { HIP_TRY(ctx, d_mp.alloc(nq)); o.mean_pinball = d_mp.as<double>(); }
-    if (out->coverage) { HIP_TRY(ctx, d_cv.alloc(nq)); o.coverage = d_cv.as<double>(); }
+    o.yhat = outs.want(out->yhat, nh);
+    o.pit = outs.want(out->pit, nh); o.crps = outs.want(out->crps, nh);
+    o.q = outs.want(out->q, nqh); o.pinball = outs.want(out->pinball, nqh);
+    o.n_obs = outs.want(out->n_obs, 4 * (size_t)N); o.mean_crps = outs.want(out->mean_crps, 8 * (size_t)N);
+    o.mean_pinball = outs.want(out->mean_pinball, nq); o.coverage = outs.want(out->coverage, nq);
+    if (int rc = outs.ready(ctx)) return rc;
     int rc = score_actuals_run(ctx, spec, up.dev, {n_samples, seed, n_q, quantiles}, d_y.as<double>(), o, nullptr);
     if (rc) return rc;
     HIP_TRY(ctx, hipDeviceSynchronize());
-    HIP_TRY(ctx, hipMemcpy(out->yhat, d_yh.p, nh, hipMemcpyDeviceToHost));
-    if (out->pit) HIP_TRY(ctx, hipMemcpy(out->pit, d_pit.p, nh, hipMemcpyDeviceToHost));
-    if (out->crps) HIP_TRY(ctx, hipMemcpy(out->crps, d_crps.p, nh, hipMemcpyDeviceToHost));
-    if (out->q) HIP_TRY(ctx, hipMemcpy(out->q, d_q.p, nqh, hipMemcpyDeviceToHost));
-    if (out->pinball) HIP_TRY(ctx, hipMemcpy(out->pinball, d_pb.p, nqh, hipMemcpyDeviceToHost));
-    if (out->n_obs) HIP_TRY(ctx, hipMemcpy(out->n_obs, d_no.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
-    if (out->mean_crps) HIP_TRY(ctx, hipMemcpy(out->mean_crps, d_mc.p, 8 * (size_t)N, hipMemcpyDeviceToHost));
-    if (out->mean_pinball) HIP_TRY(ctx, hipMemcpy(out->mean_pinball, d_mp.p, nq, hipMemcpyDeviceToHost));
-    if (out->coverage) HIP_TRY(ctx, hipMemcpy(out->coverage, d_cv.p, nq, hipMemcpyDeviceToHost));
-    return 0;
+    return outs.fetch(ctx);
 }
 
 // ---- group roll-ups: predictive quantiles of sums over series ---------------------------------------------
 
 // The accumulators of one roll-up (include/tsf.h): owned by the handle, not carved from the context's scratch.
 struct tsf_rollup {
-    tsf_ctx *ctx;
-    int64_t G;
-    int32_t H, S;
-    uint64_t seed;
-    int64_t *d_ds;                  // [H] the roll-up's calendar
-    double *acc;                    // [G][H][S]
-    double *ysum;                   // [G][H]
+    tsf_ctx *ctx = nullptr;
+    int64_t G = 0;
+    int32_t H = 0, S = 0;
+    uint64_t seed = 0;
+    OwnedDev<int64_t> d_ds;         // [H] the roll-up's calendar
+    OwnedDev<double> acc;           // [G][H][S]
+    OwnedDev<double> ysum;          // [G][H]
     std::vector<int64_t> count;     // [G] members added so far (host)
-    bool poisoned;                  // a HIP failure in the middle of an add: the accumulators may be half-added
+    bool poisoned = false;          // a HIP failure in the middle of an add: the accumulators may be half-added
     // reconciliation (tsf_rollup_set_totals): allocated by its first call and not before
-    double *top;                    // [G][H][S] the draws of the groups' directly fitted totals
-    double *ytop;                   // [G][H]
-    int32_t *d_has_top;             // [G] device copy of has_top
+    OwnedDev<double> top;           // [G][H][S] the draws of the groups' directly fitted totals
+    OwnedDev<double> ytop;          // [G][H]
+    OwnedDev<int32_t> d_has_top;    // [G] device copy of has_top
     std::vector<int32_t> has_top;   // [G] the group has a total (host; empty until the first set_totals)
     // correlated noise (tsf_rollup_set_noise_corr): allocated by that call and not before
-    bool corr;                      // a correlation is set: adds go through rollup_add_corr_kernel
-    bool added;                     // an add of N > 0 series has reached the accumulators
-    double *d_corr_ab;              // [2][G] a = sqrt(1 - rho) - 1, then b = sqrt(rho)
-    int64_t *d_group_key;           // [G]
+    bool corr = false;              // a correlation is set: adds go through rollup_add_corr_kernel
+    bool added = false;             // an add of N > 0 series has reached the accumulators
+    OwnedDev<double> d_corr_ab;     // [2][G] a = sqrt(1 - rho) - 1, then b = sqrt(rho)
+    OwnedDev<int64_t> d_group_key;  // [G]
     std::vector<double> corr_a, corr_b;     // the host copies
     std::vector<int64_t> group_key;
 };
 
-static void rollup_release(tsf_rollup *r)
+// A HIP failure of a roll-up's own allocations and copies: the message of the entry, -2, and the error read so that it
+// is not sticky (an allocation failure is not, once read: the context stays usable).
+static int rollup_hip_fail(tsf_ctx *ctx, const char *entry, hipError_t e)
 {
-    if (r->d_ds) (void)hipFree(r->d_ds);
-    if (r->acc) (void)hipFree(r->acc);
-    if (r->ysum) (void)hipFree(r->ysum);
-    if (r->top) (void)hipFree(r->top);
-    if (r->ytop) (void)hipFree(r->ytop);
-    if (r->d_has_top) (void)hipFree(r->d_has_top);
-    if (r->d_corr_ab) (void)hipFree(r->d_corr_ab);
-    if (r->d_group_key) (void)hipFree(r->d_group_key);
-    delete r;
+    ctx->err = std::string(entry) + ": " + hipGetErrorString(e);
+    (void)hipGetLastError();
+    return -2;
+}
+
+// the accumulators of a new roll-up: the calendar sent, +0.0 everywhere else
+static hipError_t rollup_alloc(tsf_rollup *r, const int64_t *ds_future)
+{
+    const size_t gh = (size_t)r->G * r->H;
+    HIP_OK(r->d_ds.alloc((size_t)r->H));
+    HIP_OK(r->acc.alloc(gh * r->S, true));
+    HIP_OK(r->ysum.alloc(gh, true));
+    HIP_OK(hipMemcpy(r->d_ds, ds_future, 8 * (size_t)r->H, hipMemcpyHostToDevice));
+    return hipDeviceSynchronize();
 }
 
 extern "C" int tsf_rollup_create(tsf_ctx *ctx, int64_t G, int32_t H, const int64_t *ds_future, int32_t n_samples,
@@ -2197,32 +2258,17 @@ extern "C" int tsf_rollup_create(tsf_ctx *ctx, int64_t G, int32_t H, const int64
     if (H < 1) return fail(ctx, "H must be >= 1");
     if (n_samples < 2 || n_samples > 4096) return fail(ctx, "n_samples must be in [2, 4096]");
     if (!ds_future) return fail(ctx, "NULL ds_future");
-    tsf_rollup *r = new tsf_rollup();
+    // (a return before the release frees the handle and, through its members, whatever it had allocated)
+    std::unique_ptr<tsf_rollup> r(new tsf_rollup());
     r->ctx = ctx; r->G = G; r->H = H; r->S = n_samples; r->seed = seed;
-    r->d_ds = nullptr; r->acc = nullptr; r->ysum = nullptr; r->poisoned = false;
-    r->top = nullptr; r->ytop = nullptr; r->d_has_top = nullptr;
-    r->corr = false; r->added = false; r->d_corr_ab = nullptr; r->d_group_key = nullptr;
-    const size_t gh = (size_t)G * H;
-    hipError_t e = hipMalloc((void **)&r->d_ds, 8 * (size_t)H);
-    if (e == hipSuccess) e = hipMalloc((void **)&r->acc, 8 * gh * n_samples);
-    if (e == hipSuccess) e = hipMalloc((void **)&r->ysum, 8 * gh);
-    if (e == hipSuccess) e = hipMemcpy(r->d_ds, ds_future, 8 * (size_t)H, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(r->acc, 0, 8 * gh * n_samples);       // +0.0
-    if (e == hipSuccess) e = hipMemset(r->ysum, 0, 8 * gh);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        ctx->err = std::string("tsf_rollup_create: ") + hipGetErrorString(e);
-        (void)hipGetLastError();        // (an allocation failure is not sticky once read: the context stays usable)
-        rollup_release(r);
-        return -2;
-    }
+    const hipError_t e = rollup_alloc(r.get(), ds_future);
+    if (e != hipSuccess) return rollup_hip_fail(ctx, "tsf_rollup_create", e);
     try {
         r->count.assign((size_t)G, 0);
     } catch (const std::bad_alloc &) {
-        rollup_release(r);
         return fail(ctx, "tsf_rollup_create: out of host memory");
     }
-    *out = r;
+    *out = r.release();
     return 0;
 }
 
@@ -2230,7 +2276,24 @@ extern "C" void tsf_rollup_free(tsf_rollup *r)
 {
     if (!r) return;
     hipSetDevice(r->ctx->device);
-    rollup_release(r);
+    delete r;
+}
+
+static const char *const ROLLUP_POISONED =
+    "the roll-up is poisoned: an earlier tsf_rollup_add or tsf_rollup_set_totals failed in the middle";
+static const char *const ROLLUP_CORR_NO_RECONCILE =
+    "the roll-up has a noise correlation set (tsf_rollup_set_noise_corr): reconciling correlated draws is not supported";
+
+// How every entry on a handle opens: the handle is there (-1 without one), its device is current, no earlier call left
+// it half-written; no_corr: and it has no noise correlation set (the reconciliation entries).  Then ctx = r->ctx.
+static int rollup_enter(tsf_rollup *r, bool no_corr = false)
+{
+    if (!r) return -1;
+    tsf_ctx *ctx = r->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (r->poisoned) return fail(ctx, ROLLUP_POISONED);
+    if (no_corr && r->corr) return fail(ctx, ROLLUP_CORR_NO_RECONCILE);
+    return 0;
 }
 
 // The small CSR of one add call, per scratch chunk [n0, n0 + nc): the groups the chunk touches (ascending) and, per
@@ -2261,9 +2324,6 @@ static void rollup_plan(const int64_t *group, int64_t N, int64_t chunk, RollupPl
         P->first.push_back((int32_t)nc);
     }
 }
-
-static const char *const ROLLUP_POISONED =
-    "the roll-up is poisoned: an earlier tsf_rollup_add or tsf_rollup_set_totals failed in the middle";
 
 // What tsf_rollup_add, tsf_rollup_set_totals and tsf_rollup_reconcile check of their series before anything is copied
 // or launched (the handle is not poisoned, N > 0).
@@ -2321,8 +2381,7 @@ struct RollupSeries {
             }
             HIP_TRY(ctx, hipMemcpy(ds_rep.data(), r->d_ds, 8 * (size_t)H, hipMemcpyDeviceToHost));
             for (int64_t n = 1; n < N; ++n) memcpy(&ds_rep[(size_t)n * H], ds_rep.data(), 8 * (size_t)H);
-            HIP_TRY(ctx, d_ds.alloc(8 * (size_t)N * H));
-            HIP_TRY(ctx, hipMemcpy(d_ds.p, ds_rep.data(), 8 * (size_t)N * H, hipMemcpyHostToDevice));
+            HIP_TRY(ctx, d_ds.put(ds_rep.data(), 8 * (size_t)N * H));
             ds_dev = d_ds.as<int64_t>();
         }
         const ForecastIn h = {N, H, theta, y_scale, grid, n_grids, ds_dev, shared, floor_, cap, extra_future, series_key};
@@ -2400,10 +2459,8 @@ extern "C" int tsf_rollup_add(tsf_rollup *r, const tsf_spec *spec, int64_t N, co
                               const double *extra_future, int32_t shared_extra, const int64_t *series_key,
                               const int64_t *group)
 {
-    if (!r) return -1;
+    if (int rc = rollup_enter(r)) return rc;
     tsf_ctx *ctx = r->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (r->poisoned) return fail(ctx, ROLLUP_POISONED);
     if (N < 0) return fail(ctx, "N must be >= 0");
     if (N == 0) return 0;
     if (int rc = rollup_check_series(r, spec, N, theta, y_scale, grid, n_grids, cap, extra_future, series_key, group))
@@ -2517,40 +2574,25 @@ extern "C" int tsf_residual_corr(tsf_ctx *ctx, int64_t N, int32_t T, const void 
     tsf_corr_args a;
     if (int rc = check_corr_call(ctx, N, T, y, y_dtype, fitted, group, G, args, out, &a)) return rc;
     const size_t nt = (size_t)N * T, ysz = ysize(y_dtype), g = (size_t)G, n = (size_t)N;
-    DevBuf d_y, d_fit, d_rho, d_raw, d_np, d_nu, d_st, d_sc;
-    HIP_TRY(ctx, d_y.alloc(ysz * nt));
-    HIP_TRY(ctx, d_fit.alloc(8 * nt));
-    if (nt) {
-        HIP_TRY(ctx, hipMemcpy(d_y.p, y, ysz * nt, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(d_fit.p, fitted, 8 * nt, hipMemcpyHostToDevice));
-    }
+    DevBuf d_y, d_fit;
+    HostOuts outs;
+    HIP_TRY(ctx, d_y.put(y, ysz * nt));
+    HIP_TRY(ctx, d_fit.put(fitted, 8 * nt));
     tsf_corr_out o;
     memset(&o, 0, sizeof(o));
-    HIP_TRY(ctx, d_rho.alloc(8 * g)); o.rho = d_rho.as<double>();
-    HIP_TRY(ctx, d_st.alloc(4 * g)); o.status = d_st.as<int32_t>();
-    if (out->rho_raw) { HIP_TRY(ctx, d_raw.alloc(8 * g)); o.rho_raw = d_raw.as<double>(); }
-    if (out->n_pairs) { HIP_TRY(ctx, d_np.alloc(8 * g)); o.n_pairs = d_np.as<int64_t>(); }
-    if (out->n_used) { HIP_TRY(ctx, d_nu.alloc(4 * g)); o.n_used = d_nu.as<int32_t>(); }
-    if (out->scale) { HIP_TRY(ctx, d_sc.alloc(8 * n)); o.scale = d_sc.as<double>(); }
+    o.rho = outs.want(out->rho, 8 * g); o.status = outs.want(out->status, 4 * g);
+    o.rho_raw = outs.want(out->rho_raw, 8 * g); o.n_pairs = outs.want(out->n_pairs, 8 * g);
+    o.n_used = outs.want(out->n_used, 4 * g); o.scale = outs.want(out->scale, 8 * n);
+    if (int rc = outs.ready(ctx)) return rc;
+    // (corr_run ends with a synchronisation of its stream)
     if (int rc = corr_run(ctx, N, T, d_y.p, y_dtype, d_fit.as<double>(), group, G, a, o, nullptr)) return rc;
-    HIP_TRY(ctx, hipMemcpy(out->rho, d_rho.p, 8 * g, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(out->status, d_st.p, 4 * g, hipMemcpyDeviceToHost));
-    if (out->rho_raw) HIP_TRY(ctx, hipMemcpy(out->rho_raw, d_raw.p, 8 * g, hipMemcpyDeviceToHost));
-    if (out->n_pairs) HIP_TRY(ctx, hipMemcpy(out->n_pairs, d_np.p, 8 * g, hipMemcpyDeviceToHost));
-    if (out->n_used) HIP_TRY(ctx, hipMemcpy(out->n_used, d_nu.p, 4 * g, hipMemcpyDeviceToHost));
-    if (out->scale && n) HIP_TRY(ctx, hipMemcpy(out->scale, d_sc.p, 8 * n, hipMemcpyDeviceToHost));
-    return 0;
+    return outs.fetch(ctx);
 }
-
-static const char *const ROLLUP_CORR_NO_RECONCILE =
-    "the roll-up has a noise correlation set (tsf_rollup_set_noise_corr): reconciling correlated draws is not supported";
 
 extern "C" int tsf_rollup_set_noise_corr(tsf_rollup *r, const double *rho, const int64_t *group_key)
 {
-    if (!r) return -1;
+    if (int rc = rollup_enter(r)) return rc;
     tsf_ctx *ctx = r->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (r->poisoned) return fail(ctx, ROLLUP_POISONED);
     if (r->added || r->top)
         return fail(ctx, "tsf_rollup_set_noise_corr after a tsf_rollup_add or tsf_rollup_set_totals: a correlation is set on an "
                          "empty roll-up");
@@ -2575,19 +2617,16 @@ extern "C" int tsf_rollup_set_noise_corr(tsf_rollup *r, const double *rho, const
         ab[G + g] = std::sqrt(rho[g]);
         key[g] = group_key ? group_key[g] : (int64_t)g;
     }
-    double *d_ab = r->d_corr_ab;
-    int64_t *d_key = r->d_group_key;
-    hipError_t e = hipSuccess;
-    if (!d_ab) e = hipMalloc((void **)&d_ab, 16 * G);
-    if (e == hipSuccess && !d_key) e = hipMalloc((void **)&d_key, 8 * G);
-    if (e == hipSuccess) e = hipMemcpy(d_ab, ab.data(), 16 * G, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_key, key.data(), 8 * G, hipMemcpyHostToDevice);
-    r->d_corr_ab = d_ab; r->d_group_key = d_key;            // (the handle owns whatever was allocated)
+    // (the tables are the handle's from their allocation on, whatever fails behind it)
+    const hipError_t e = [&]() -> hipError_t {
+        if (!r->d_corr_ab) HIP_OK(r->d_corr_ab.alloc(2 * G));
+        if (!r->d_group_key) HIP_OK(r->d_group_key.alloc(G));
+        HIP_OK(hipMemcpy(r->d_corr_ab, ab.data(), 16 * G, hipMemcpyHostToDevice));
+        return hipMemcpy(r->d_group_key, key.data(), 8 * G, hipMemcpyHostToDevice);
+    }();
     if (e != hipSuccess) {
-        ctx->err = std::string("tsf_rollup_set_noise_corr: ") + hipGetErrorString(e);
-        (void)hipGetLastError();
         if (r->corr) r->poisoned = true;        // (an earlier table may be half overwritten)
-        return -2;
+        return rollup_hip_fail(ctx, "tsf_rollup_set_noise_corr", e);
     }
     r->corr_a.assign(ab.begin(), ab.begin() + (std::ptrdiff_t)G);
     r->corr_b.assign(ab.begin() + (std::ptrdiff_t)G, ab.end());
@@ -2596,62 +2635,80 @@ extern "C" int tsf_rollup_set_noise_corr(tsf_rollup *r, const double *rho, const
     return 0;
 }
 
-extern "C" int tsf_rollup_quantiles(tsf_rollup *r, int32_t n_q, const double *quantiles, tsf_rollup_out *out)
+// What a read of a roll-up checks of its outputs and levels (those of a tsf_rollup_out or a tsf_reconcile_out):
+// tsf_predict_quantiles' checks, with the handle's sample count.
+static int check_rollup_read(tsf_rollup *r, int32_t n_q, const double *quantiles, double *yhat, double *q, double *cum_q,
+                             double *samples)
 {
-    if (!r) return -1;
+    tsf_quantile_out chk;
+    memset(&chk, 0, sizeof(chk));
+    chk.yhat = yhat; chk.q = q; chk.cum_q = cum_q; chk.samples = samples;
+    return check_quantile_args(r->ctx, r->S, n_q, quantiles, &chk);
+}
+
+// The read of every group's cells behind tsf_rollup_quantiles and tsf_rollup_reconciled_totals (which has put yhat into
+// `outs`), a range of groups at a time.  Without `total` the cells are the accumulators: q is sorted from them in place,
+// a range being what quantile_kernel's grid (groups * H) takes, and the samples are the accumulators themselves.  With
+// it, reconcile_total_kernel first writes a range's cells into the context's scratch (its out and g0 are set here): q is
+// sorted from there, and the samples leave the scratch range by range in stream order.  In both, the running sums of a
+// range for cum_q lie in the scratch as well, and a range is what keeps the scratch within its 512 MB.
+static int rollup_read(tsf_rollup *r, int32_t n_q, const double *quantiles, const tsf_rollup_out &out,
+                       ReconcileTotalArgs *total, HostOuts &outs)
+{
     tsf_ctx *ctx = r->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (r->poisoned) return fail(ctx, ROLLUP_POISONED);
-    if (!out) return fail(ctx, "NULL output (tsf_rollup_out and its yhat are required)");
-    {
-        tsf_quantile_out chk;
-        memset(&chk, 0, sizeof(chk));
-        chk.yhat = out->yhat; chk.q = out->q; chk.cum_q = out->cum_q; chk.samples = out->samples;
-        if (int rc = check_quantile_args(ctx, r->S, n_q, quantiles, &chk)) return rc;
-    }
     const int32_t H = r->H, S = r->S;
     const int64_t G = r->G;
     const size_t hs = (size_t)H * S, gh = (size_t)G * H, nqh = 8 * gh * (size_t)n_q;
-    const int NSP = sort_width(S);
-    QuantileArgs q;
-    memset(&q, 0, sizeof(q));
-    q.H = H; q.NS = S; q.n_q = n_q;
-    for (int32_t i = 0; i < n_q; ++i) q.level[i] = quantiles[i];
-    DevBuf d_q, d_cq;
-    if (out->q) {
-        // quantile_kernel reads the accumulator in place, a range of groups per launch (its grid is groups * H)
-        HIP_TRY(ctx, d_q.alloc(nqh));
+    const QuantilePass qp(H, S, n_q, quantiles);
+    double *d_q = outs.want(out.q, nqh), *d_cq = outs.want(out.cum_q, nqh);
+    if (!total) outs.adopt(out.samples, r->acc.p, 8 * gh * S);
+    if (int rc = outs.ready(ctx)) return rc;
+    if (d_q && !total) {
         const int64_t range = std::max<int64_t>(1, ((int64_t)1 << 30) / H);
-        for (int64_t g0 = 0; g0 < G; g0 += range) {
-            const int64_t gc = std::min(range, G - g0);
-            q.src = r->acc + (size_t)g0 * hs; q.dst = d_q.as<double>(); q.n0 = g0;
-            hipLaunchKernelGGL(quantile_kernel, dim3((unsigned)(gc * H)), dim3(256), sizeof(double) * NSP, nullptr, q, NSP);
-            HIP_TRY(ctx, hipGetLastError());
-        }
+        for (int64_t g0 = 0; g0 < G; g0 += range)
+            if (int rc = qp.launch(ctx, r->acc + (size_t)g0 * hs, d_q, g0, std::min(range, G - g0), nullptr)) return rc;
     }
-    if (out->cum_q) {
-        // the running sums of a range of groups in the context's scratch (within its 512 MB), sorted from there
-        HIP_TRY(ctx, d_cq.alloc(nqh));
-        const int64_t range = std::max<int64_t>(1, std::min<int64_t>(G, (int64_t)(((size_t)512 << 20) / (8 * hs))));
-        if (int rc = ensure_iv_ws(ctx, 8 * (size_t)range * hs)) return rc;
-        double *d_c = (double *)ctx->iv_ws;
+    const size_t n_buf = (total ? 1 : 0) + (d_cq ? 1 : 0);      // per range in the scratch: the cells, their running sums
+    if (n_buf) {
+        const int64_t range = std::max<int64_t>(1, std::min<int64_t>(G, (int64_t)(((size_t)512 << 20) / (8 * hs * n_buf))));
+        if (int rc = ensure_iv_ws(ctx, 8 * (size_t)range * hs * n_buf)) return rc;
+        double *d_x = (double *)ctx->iv_ws, *d_c = total ? d_x + (size_t)range * hs : d_x;
         for (int64_t g0 = 0; g0 < G; g0 += range) {
             const int64_t gc = std::min(range, G - g0);
-            hipLaunchKernelGGL(rollup_cumsum_kernel, dim3((unsigned)((gc * S + 255) / 256)), dim3(256), 0, nullptr,
-                               r->acc + (size_t)g0 * hs, d_c, gc, H, S);
-            HIP_TRY(ctx, hipGetLastError());
-            q.src = d_c; q.dst = d_cq.as<double>(); q.n0 = g0;
-            hipLaunchKernelGGL(quantile_kernel, dim3((unsigned)(gc * H)), dim3(256), sizeof(double) * NSP, nullptr, q, NSP);
-            HIP_TRY(ctx, hipGetLastError());
+            const double *cells = total ? d_x : r->acc + (size_t)g0 * hs;
+            if (total) {
+                total->out = d_x; total->g0 = g0;
+                hipLaunchKernelGGL(reconcile_total_kernel, dim3((unsigned)(gc * H), (unsigned)((S + 255) / 256)), dim3(256), 0,
+                                   nullptr, *total);
+                HIP_TRY(ctx, hipGetLastError());
+                if (d_q)
+                    if (int rc = qp.launch(ctx, d_x, d_q, g0, gc, nullptr)) return rc;
+            }
+            if (d_cq) {
+                hipLaunchKernelGGL(rollup_cumsum_kernel, dim3((unsigned)((gc * S + 255) / 256)), dim3(256), 0, nullptr,
+                                   cells, d_c, gc, H, S);
+                HIP_TRY(ctx, hipGetLastError());
+                if (int rc = qp.launch(ctx, d_c, d_cq, g0, gc, nullptr)) return rc;
+            }
+            if (total && out.samples)
+                HIP_TRY(ctx, hipMemcpyAsync(out.samples + (size_t)g0 * hs, d_x, 8 * (size_t)gc * hs, hipMemcpyDeviceToHost,
+                                            nullptr));
         }
     }
     HIP_TRY(ctx, hipDeviceSynchronize());
-    HIP_TRY(ctx, hipMemcpy(out->yhat, r->ysum, 8 * gh, hipMemcpyDeviceToHost));
-    if (out->count) memcpy(out->count, r->count.data(), 8 * (size_t)G);
-    if (out->q) HIP_TRY(ctx, hipMemcpy(out->q, d_q.p, nqh, hipMemcpyDeviceToHost));
-    if (out->cum_q) HIP_TRY(ctx, hipMemcpy(out->cum_q, d_cq.p, nqh, hipMemcpyDeviceToHost));
-    if (out->samples) HIP_TRY(ctx, hipMemcpy(out->samples, r->acc, 8 * gh * S, hipMemcpyDeviceToHost));
-    return 0;
+    if (out.count) memcpy(out.count, r->count.data(), 8 * (size_t)G);
+    return outs.fetch(ctx);
+}
+
+extern "C" int tsf_rollup_quantiles(tsf_rollup *r, int32_t n_q, const double *quantiles, tsf_rollup_out *out)
+{
+    if (int rc = rollup_enter(r)) return rc;
+    tsf_ctx *ctx = r->ctx;
+    if (!out) return fail(ctx, "NULL output (tsf_rollup_out and its yhat are required)");
+    if (int rc = check_rollup_read(r, n_q, quantiles, out->yhat, out->q, out->cum_q, out->samples)) return rc;
+    HostOuts outs;
+    outs.adopt(out->yhat, r->ysum.p, 8 * (size_t)r->G * r->H);
+    return rollup_read(r, n_q, quantiles, *out, nullptr, outs);
 }
 
 // ---- totals over row windows: quantiles and scores of calendar-period totals ---------------------------------
@@ -2822,55 +2879,21 @@ extern "C" int tsf_predict_windows_dev(tsf_ctx *ctx, const tsf_spec *spec, int64
     return predict_windows_run(ctx, spec, f, {n_samples, seed, n_q, quantiles}, w, *out, (hipStream_t)stream);
 }
 
-// The outputs of a host-pointer window entry on the device (pooled buffers that live in the entry's scope) and their
-// way back.  yhat_dev: the entry has yhat on the device already (the roll-up's ysum) and no buffer is taken for it.
-struct WindowDevOut {
-    DevBuf y, yh, tot, q, pit, crps, pb, no, mc, mp, cv;
+// The outputs of a host-pointer window entry over N series (groups) on the device: each field `h` asks for, at its size.
+// yhat_dev: the entry has yhat on the device already (the roll-up's ysum) and no buffer is taken for it.
+static tsf_window_out window_dev_outs(HostOuts &outs, const tsf_window_out &h, int64_t N, int32_t H, int32_t K, int32_t n_q,
+                                      double *yhat_dev)
+{
+    const size_t nh = 8 * (size_t)N * H, nk = 8 * (size_t)N * K, nqk = nk * (size_t)n_q, nq = 8 * (size_t)N * n_q;
     tsf_window_out o;
-    size_t nh, nk, nqk, nq, n4;
-
-    int alloc(tsf_ctx *ctx, const tsf_window_out &h, const double *y_win, int64_t N, int32_t H, int32_t K, int32_t n_q,
-              double *yhat_dev, const double **d_y_win)
-    {
-        nh = 8 * (size_t)N * H; nk = 8 * (size_t)N * K; nqk = nk * (size_t)n_q; nq = 8 * (size_t)N * n_q; n4 = 4 * (size_t)N;
-        memset(&o, 0, sizeof(o));
-        *d_y_win = nullptr;
-        if (y_win) {
-            HIP_TRY(ctx, y.alloc(nk));
-            HIP_TRY(ctx, hipMemcpy(y.p, y_win, nk, hipMemcpyHostToDevice));
-            *d_y_win = y.as<double>();
-        }
-        if (h.yhat) {
-            if (yhat_dev) o.yhat = yhat_dev;
-            else { HIP_TRY(ctx, yh.alloc(nh)); o.yhat = yh.as<double>(); }
-        }
-        if (h.total) { HIP_TRY(ctx, tot.alloc(nk)); o.total = tot.as<double>(); }
-        if (h.q) { HIP_TRY(ctx, q.alloc(nqk)); o.q = q.as<double>(); }
-        if (h.pit) { HIP_TRY(ctx, pit.alloc(nk)); o.pit = pit.as<double>(); }
-        if (h.crps) { HIP_TRY(ctx, crps.alloc(nk)); o.crps = crps.as<double>(); }
-        if (h.pinball) { HIP_TRY(ctx, pb.alloc(nqk)); o.pinball = pb.as<double>(); }
-        if (h.n_obs) { HIP_TRY(ctx, no.alloc(n4)); o.n_obs = no.as<int32_t>(); }
-        if (h.mean_crps) { HIP_TRY(ctx, mc.alloc(8 * (size_t)N)); o.mean_crps = mc.as<double>(); }
-        if (h.mean_pinball) { HIP_TRY(ctx, mp.alloc(nq)); o.mean_pinball = mp.as<double>(); }
-        if (h.coverage) { HIP_TRY(ctx, cv.alloc(nq)); o.coverage = cv.as<double>(); }
-        return 0;
-    }
-
-    int fetch(tsf_ctx *ctx, const tsf_window_out &h, int64_t N)
-    {
-        if (h.yhat) HIP_TRY(ctx, hipMemcpy(h.yhat, o.yhat, nh, hipMemcpyDeviceToHost));
-        if (h.total) HIP_TRY(ctx, hipMemcpy(h.total, o.total, nk, hipMemcpyDeviceToHost));
-        if (h.q) HIP_TRY(ctx, hipMemcpy(h.q, o.q, nqk, hipMemcpyDeviceToHost));
-        if (h.pit) HIP_TRY(ctx, hipMemcpy(h.pit, o.pit, nk, hipMemcpyDeviceToHost));
-        if (h.crps) HIP_TRY(ctx, hipMemcpy(h.crps, o.crps, nk, hipMemcpyDeviceToHost));
-        if (h.pinball) HIP_TRY(ctx, hipMemcpy(h.pinball, o.pinball, nqk, hipMemcpyDeviceToHost));
-        if (h.n_obs) HIP_TRY(ctx, hipMemcpy(h.n_obs, o.n_obs, n4, hipMemcpyDeviceToHost));
-        if (h.mean_crps) HIP_TRY(ctx, hipMemcpy(h.mean_crps, o.mean_crps, 8 * (size_t)N, hipMemcpyDeviceToHost));
-        if (h.mean_pinball) HIP_TRY(ctx, hipMemcpy(h.mean_pinball, o.mean_pinball, nq, hipMemcpyDeviceToHost));
-        if (h.coverage) HIP_TRY(ctx, hipMemcpy(h.coverage, o.coverage, nq, hipMemcpyDeviceToHost));
-        return 0;
-    }
-};
+    memset(&o, 0, sizeof(o));
+    o.yhat = yhat_dev ? outs.adopt(h.yhat, yhat_dev, nh) : outs.want(h.yhat, nh);
+    o.total = outs.want(h.total, nk); o.q = outs.want(h.q, nqk);
+    o.pit = outs.want(h.pit, nk); o.crps = outs.want(h.crps, nk); o.pinball = outs.want(h.pinball, nqk);
+    o.n_obs = outs.want(h.n_obs, 4 * (size_t)N); o.mean_crps = outs.want(h.mean_crps, 8 * (size_t)N);
+    o.mean_pinball = outs.want(h.mean_pinball, nq); o.coverage = outs.want(h.coverage, nq);
+    return o;
+}
 
 extern "C" int tsf_predict_windows(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H, const double *theta,
                                    const double *y_scale, const tsf_grid_info *grid, int32_t n_grids,
@@ -2890,38 +2913,42 @@ extern "C" int tsf_predict_windows(tsf_ctx *ctx, const tsf_spec *spec, int64_t N
     if (int rc = check_y_win(ctx, y_win, N, K)) return rc;
     ForecastUpload up;
     if (int rc = up.upload(ctx, spec, h)) return rc;
-    WindowDevOut d;
+    DevBuf d_y;
+    HostOuts outs;
     WindowCall w = hw;
-    if (int rc = d.alloc(ctx, *out, y_win, N, H, K, n_q, nullptr, &w.y_win)) return rc;
-    if (int rc = predict_windows_run(ctx, spec, up.dev, {n_samples, seed, n_q, quantiles}, w, d.o, nullptr)) return rc;
+    if (y_win) { HIP_TRY(ctx, d_y.put(y_win, 8 * (size_t)N * K)); w.y_win = d_y.as<double>(); }
+    const tsf_window_out o = window_dev_outs(outs, *out, N, H, K, n_q, nullptr);
+    if (int rc = outs.ready(ctx)) return rc;
+    if (int rc = predict_windows_run(ctx, spec, up.dev, {n_samples, seed, n_q, quantiles}, w, o, nullptr)) return rc;
     HIP_TRY(ctx, hipDeviceSynchronize());
-    return d.fetch(ctx, *out, N);
+    return outs.fetch(ctx);
 }
 
 extern "C" int tsf_rollup_windows(tsf_rollup *r, int32_t K, const int32_t *win_start, const int32_t *win_end,
                                   const double *y_win, int32_t n_q, const double *quantiles, tsf_window_out *out)
 {
-    if (!r) return -1;
+    if (int rc = rollup_enter(r)) return rc;
     tsf_ctx *ctx = r->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (r->poisoned) return fail(ctx, ROLLUP_POISONED);
     const int32_t H = r->H, S = r->S;
     const int64_t G = r->G;
     const WindowCall hw = {K, win_start, win_end, y_win};
     if (int rc = check_window_args(ctx, H, S, n_q, quantiles, hw, out)) return rc;
     if (int rc = check_y_win(ctx, y_win, G, K)) return rc;
     // the accumulators are read in place, a group in the place of a series; yhat is the handle's ysum
-    WindowDevOut d;
+    DevBuf d_y;
+    HostOuts outs;
     WindowCall w = hw;
-    if (int rc = d.alloc(ctx, *out, y_win, G, H, K, n_q, r->ysum, &w.y_win)) return rc;
+    if (y_win) { HIP_TRY(ctx, d_y.put(y_win, 8 * (size_t)G * K)); w.y_win = d_y.as<double>(); }
+    const tsf_window_out o = window_dev_outs(outs, *out, G, H, K, n_q, r->ysum);
+    if (int rc = outs.ready(ctx)) return rc;
     WindowArgs a;
     double *yhat = nullptr;
-    if (int rc = window_prepare(ctx, 0, G, H, S, {S, r->seed, n_q, quantiles}, w, d.o, false, nullptr, &a, &yhat)) return rc;
-    if (window_wants_draws(d.o))
+    if (int rc = window_prepare(ctx, 0, G, H, S, {S, r->seed, n_q, quantiles}, w, o, false, nullptr, &a, &yhat)) return rc;
+    if (window_wants_draws(o))
         if (int rc = launch_window_scores(ctx, a, r->acc, 0, G, nullptr)) return rc;
-    if (int rc = window_finish(ctx, a, r->ysum, G, d.o, nullptr)) return rc;
+    if (int rc = window_finish(ctx, a, r->ysum, G, o, nullptr)) return rc;
     HIP_TRY(ctx, hipDeviceSynchronize());
-    return d.fetch(ctx, *out, G);
+    return outs.fetch(ctx);
 }
 
 // ---- reconciliation: member forecasts and fitted totals made coherent ---------------------------------------
@@ -2957,11 +2984,8 @@ extern "C" int tsf_rollup_set_totals(tsf_rollup *r, const tsf_spec *spec, int64_
                                      const double *floor_, const double *cap, const double *extra_future,
                                      int32_t shared_extra, const int64_t *series_key, const int64_t *group)
 {
-    if (!r) return -1;
+    if (int rc = rollup_enter(r, true)) return rc;
     tsf_ctx *ctx = r->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (r->poisoned) return fail(ctx, ROLLUP_POISONED);
-    if (r->corr) return fail(ctx, ROLLUP_CORR_NO_RECONCILE);
     if (Gt < 0) return fail(ctx, "N must be >= 0");
     if (Gt == 0) return 0;
     if (int rc = rollup_check_series(r, spec, Gt, theta, y_scale, grid, n_grids, cap, extra_future, series_key, group))
@@ -2985,24 +3009,17 @@ extern "C" int tsf_rollup_set_totals(tsf_rollup *r, const tsf_spec *spec, int64_
     const size_t gh = (size_t)r->G * r->H;
     if (!r->top) {
         // the second accumulator: +0.0 everywhere, so that the add below leaves the draws themselves in it
-        double *top = nullptr, *ytop = nullptr;
-        int32_t *d_has = nullptr;
-        hipError_t e = hipMalloc((void **)&top, 8 * gh * r->S);
-        if (e == hipSuccess) e = hipMalloc((void **)&ytop, 8 * gh);
-        if (e == hipSuccess) e = hipMalloc((void **)&d_has, 4 * (size_t)r->G);
-        if (e == hipSuccess) e = hipMemset(top, 0, 8 * gh * r->S);
-        if (e == hipSuccess) e = hipMemset(ytop, 0, 8 * gh);
-        if (e == hipSuccess) e = hipMemset(d_has, 0, 4 * (size_t)r->G);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e != hipSuccess) {
-            ctx->err = std::string("tsf_rollup_set_totals: ") + hipGetErrorString(e);
-            (void)hipGetLastError();
-            if (top) (void)hipFree(top);
-            if (ytop) (void)hipFree(ytop);
-            if (d_has) (void)hipFree(d_has);
-            return -2;
-        }
-        r->top = top; r->ytop = ytop; r->d_has_top = d_has;
+        // (the three become the handle's together or not at all: a failure frees what the locals hold)
+        OwnedDev<double> top, ytop;
+        OwnedDev<int32_t> d_has;
+        const hipError_t e = [&]() -> hipError_t {
+            HIP_OK(top.alloc(gh * r->S, true));
+            HIP_OK(ytop.alloc(gh, true));
+            HIP_OK(d_has.alloc((size_t)r->G, true));
+            return hipDeviceSynchronize();
+        }();
+        if (e != hipSuccess) return rollup_hip_fail(ctx, "tsf_rollup_set_totals", e);
+        r->top.swap(top); r->ytop.swap(ytop); r->d_has_top.swap(d_has);
     }
     if (int rc = rollup_accumulate(r, spec, Gt, theta, y_scale, grid, n_grids, floor_, cap, extra_future, shared_extra,
                                    series_key, group, r->top, r->ytop))
@@ -3033,11 +3050,8 @@ extern "C" int tsf_rollup_reconcile(tsf_rollup *r, const tsf_spec *spec, int64_t
                                     int32_t shared_extra, const int64_t *series_key, const int64_t *group,
                                     const double *share, int32_t n_q, const double *quantiles, tsf_reconcile_out *out)
 {
-    if (!r) return -1;
+    if (int rc = rollup_enter(r, true)) return rc;
     tsf_ctx *ctx = r->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (r->poisoned) return fail(ctx, ROLLUP_POISONED);
-    if (r->corr) return fail(ctx, ROLLUP_CORR_NO_RECONCILE);
     if (N < 0) return fail(ctx, "N must be >= 0");
     if (N == 0) return 0;
     if (!r->top) return fail(ctx, "tsf_rollup_reconcile before any tsf_rollup_set_totals: the roll-up has no total");
@@ -3046,14 +3060,8 @@ extern "C" int tsf_rollup_reconcile(tsf_rollup *r, const tsf_spec *spec, int64_t
     if (!share) return fail(ctx, "NULL share");
     if (int rc = check_shares(ctx, "share", share, N)) return rc;
     if (!out) return fail(ctx, "NULL output (tsf_reconcile_out and its yhat are required)");
-    {
-        tsf_quantile_out chk;
-        memset(&chk, 0, sizeof(chk));
-        chk.yhat = out->yhat; chk.q = out->q; chk.cum_q = out->cum_q; chk.samples = out->samples;
-        if (int rc = check_quantile_args(ctx, r->S, n_q, quantiles, &chk)) return rc;
-    }
+    if (int rc = check_rollup_read(r, n_q, quantiles, out->yhat, out->q, out->cum_q, out->samples)) return rc;
     const int32_t H = r->H, S = r->S;
-    const int NSP = sort_width(S);
     std::vector<int32_t> g32;
     try {
         g32.resize((size_t)N);
@@ -3066,23 +3074,18 @@ extern "C" int tsf_rollup_reconcile(tsf_rollup *r, const tsf_spec *spec, int64_t
         return rc;
     // the shares and the groups of the whole call, sent once ahead of the first launch
     const size_t nh = 8 * (size_t)N * H, nqh = nh * (size_t)n_q;
-    DevBuf d_yh, d_q, d_cq, d_share, d_group;
-    HIP_TRY(ctx, d_yh.alloc(nh));
-    if (out->q) HIP_TRY(ctx, d_q.alloc(nqh));
-    if (out->cum_q) HIP_TRY(ctx, d_cq.alloc(nqh));
-    HIP_TRY(ctx, d_share.alloc(8 * (size_t)N));
-    HIP_TRY(ctx, d_group.alloc(4 * (size_t)N));
-    HIP_TRY(ctx, hipMemcpy(d_share.p, share, 8 * (size_t)N, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(d_group.p, g32.data(), 4 * (size_t)N, hipMemcpyHostToDevice));
+    HostOuts outs;
+    DevBuf d_share, d_group;
+    double *d_yh = outs.want(out->yhat, nh), *d_q = outs.want(out->q, nqh), *d_cq = outs.want(out->cum_q, nqh);
+    if (int rc = outs.ready(ctx)) return rc;
+    HIP_TRY(ctx, d_share.put(share, 8 * (size_t)N));
+    HIP_TRY(ctx, d_group.put(g32.data(), 4 * (size_t)N));
     ReconcileMemberArgs m;
     memset(&m, 0, sizeof(m));
     m.acc = r->acc; m.top = r->top; m.ysum = r->ysum; m.ytop = r->ytop; m.has_top = r->d_has_top; m.H = H; m.NS = S;
-    QuantileArgs q;
-    memset(&q, 0, sizeof(q));
-    q.H = H; q.NS = S; q.n_q = n_q;
-    for (int32_t i = 0; i < n_q; ++i) q.level[i] = quantiles[i];
+    const QuantilePass qp(H, S, n_q, quantiles);
     auto after = [&](int64_t n0, int64_t nc, const DrawBufs &b) -> int {
-        m.samp = b.samp; m.yhat = d_yh.as<double>() + (size_t)n0 * H;
+        m.samp = b.samp; m.yhat = d_yh + (size_t)n0 * H;
         m.group = d_group.as<int32_t>() + n0; m.share = d_share.as<double>() + n0;
         hipLaunchKernelGGL(reconcile_member_kernel, dim3((unsigned)(nc * H), (unsigned)((S + 255) / 256)), dim3(256), 0,
                            nullptr, m);
@@ -3093,100 +3096,42 @@ extern "C" int tsf_rollup_reconcile(tsf_rollup *r, const tsf_spec *spec, int64_t
                                b.samp, b.cum, nc, H, S);
             HIP_TRY(ctx, hipGetLastError());
         }
-        const struct { const double *src; double *dst; } sorts[2] = {{b.samp, d_q.as<double>()}, {b.cum, d_cq.as<double>()}};
-        for (const auto &so : sorts) {
-            if (!so.dst) continue;
-            q.src = so.src; q.dst = so.dst; q.n0 = n0;
-            hipLaunchKernelGGL(quantile_kernel, dim3((unsigned)(nc * H)), dim3(256), sizeof(double) * NSP, nullptr, q, NSP);
-            HIP_TRY(ctx, hipGetLastError());
-        }
+        const struct { const double *src; double *dst; } sorts[2] = {{b.samp, d_q}, {b.cum, d_cq}};
+        for (const auto &so : sorts)
+            if (so.dst)
+                if (int rc = qp.launch(ctx, so.src, so.dst, n0, nc, nullptr)) return rc;
         // the reconciled draws leave the scratch before the next chunk overwrites it (stream order)
         if (out->samples)
             HIP_TRY(ctx, hipMemcpyAsync(out->samples + (size_t)n0 * H * S, b.samp, 8 * (size_t)nc * H * S,
                                         hipMemcpyDeviceToHost, nullptr));
         return 0;
     };
-    const DrawSpec d = {S, r->seed, out->cum_q != nullptr, false, d_yh.as<double>(), nullptr};
+    const DrawSpec d = {S, r->seed, out->cum_q != nullptr, false, d_yh, nullptr};
     if (int rc = draw_chunks(ctx, spec, in.up.dev, d, nullptr, after)) return rc;
     HIP_TRY(ctx, hipDeviceSynchronize());
-    HIP_TRY(ctx, hipMemcpy(out->yhat, d_yh.p, nh, hipMemcpyDeviceToHost));
-    if (out->q) HIP_TRY(ctx, hipMemcpy(out->q, d_q.p, nqh, hipMemcpyDeviceToHost));
-    if (out->cum_q) HIP_TRY(ctx, hipMemcpy(out->cum_q, d_cq.p, nqh, hipMemcpyDeviceToHost));
-    return 0;
+    return outs.fetch(ctx);
 }
 
 extern "C" int tsf_rollup_reconciled_totals(tsf_rollup *r, const double *share_total, int32_t n_q,
                                             const double *quantiles, tsf_rollup_out *out)
 {
-    if (!r) return -1;
+    if (int rc = rollup_enter(r, true)) return rc;
     tsf_ctx *ctx = r->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (r->poisoned) return fail(ctx, ROLLUP_POISONED);
-    if (r->corr) return fail(ctx, ROLLUP_CORR_NO_RECONCILE);
     if (!r->top)
         return fail(ctx, "tsf_rollup_reconciled_totals before any tsf_rollup_set_totals: the roll-up has no total");
     if (!share_total) return fail(ctx, "NULL share_total");
     if (int rc = check_shares(ctx, "share_total", share_total, r->G)) return rc;
     if (!out) return fail(ctx, "NULL output (tsf_rollup_out and its yhat are required)");
-    {
-        tsf_quantile_out chk;
-        memset(&chk, 0, sizeof(chk));
-        chk.yhat = out->yhat; chk.q = out->q; chk.cum_q = out->cum_q; chk.samples = out->samples;
-        if (int rc = check_quantile_args(ctx, r->S, n_q, quantiles, &chk)) return rc;
-    }
-    const int32_t H = r->H, S = r->S;
-    const int64_t G = r->G;
-    const size_t hs = (size_t)H * S, gh = (size_t)G * H, nqh = 8 * gh * (size_t)n_q;
-    const int NSP = sort_width(S);
-    DevBuf d_share, d_yh, d_q, d_cq;
-    HIP_TRY(ctx, d_share.alloc(8 * (size_t)G));
-    HIP_TRY(ctx, d_yh.alloc(8 * gh));
-    if (out->q) HIP_TRY(ctx, d_q.alloc(nqh));
-    if (out->cum_q) HIP_TRY(ctx, d_cq.alloc(nqh));
-    HIP_TRY(ctx, hipMemcpy(d_share.p, share_total, 8 * (size_t)G, hipMemcpyHostToDevice));
-    // a range of groups at a time in the context's scratch (within its 512 MB): the reconciled cells, and behind them
-    // their running sums where wanted
-    const size_t n_buf = out->cum_q ? 2 : 1;
-    const int64_t range = std::max<int64_t>(1, std::min<int64_t>(G, (int64_t)(((size_t)512 << 20) / (8 * hs * n_buf))));
-    if (int rc = ensure_iv_ws(ctx, 8 * (size_t)range * hs * n_buf)) return rc;
-    double *d_x = (double *)ctx->iv_ws, *d_c = d_x + (size_t)range * hs;
+    if (int rc = check_rollup_read(r, n_q, quantiles, out->yhat, out->q, out->cum_q, out->samples)) return rc;
+    DevBuf d_share;
+    HostOuts outs;
+    HIP_TRY(ctx, d_share.put(share_total, 8 * (size_t)r->G));
+    // rollup_read's ranges of groups, each reconciled into the scratch first
     ReconcileTotalArgs t;
     memset(&t, 0, sizeof(t));
     t.acc = r->acc; t.top = r->top; t.ysum = r->ysum; t.ytop = r->ytop; t.has_top = r->d_has_top;
-    t.share = d_share.as<double>(); t.out = d_x; t.yout = d_yh.as<double>(); t.H = H; t.NS = S;
-    QuantileArgs q;
-    memset(&q, 0, sizeof(q));
-    q.H = H; q.NS = S; q.n_q = n_q;
-    for (int32_t i = 0; i < n_q; ++i) q.level[i] = quantiles[i];
-    for (int64_t g0 = 0; g0 < G; g0 += range) {
-        const int64_t gc = std::min(range, G - g0);
-        t.g0 = g0;
-        hipLaunchKernelGGL(reconcile_total_kernel, dim3((unsigned)(gc * H), (unsigned)((S + 255) / 256)), dim3(256), 0,
-                           nullptr, t);
-        HIP_TRY(ctx, hipGetLastError());
-        if (out->q) {
-            q.src = d_x; q.dst = d_q.as<double>(); q.n0 = g0;
-            hipLaunchKernelGGL(quantile_kernel, dim3((unsigned)(gc * H)), dim3(256), sizeof(double) * NSP, nullptr, q, NSP);
-            HIP_TRY(ctx, hipGetLastError());
-        }
-        if (out->cum_q) {
-            hipLaunchKernelGGL(rollup_cumsum_kernel, dim3((unsigned)((gc * S + 255) / 256)), dim3(256), 0, nullptr,
-                               d_x, d_c, gc, H, S);
-            HIP_TRY(ctx, hipGetLastError());
-            q.src = d_c; q.dst = d_cq.as<double>(); q.n0 = g0;
-            hipLaunchKernelGGL(quantile_kernel, dim3((unsigned)(gc * H)), dim3(256), sizeof(double) * NSP, nullptr, q, NSP);
-            HIP_TRY(ctx, hipGetLastError());
-        }
-        if (out->samples)
-            HIP_TRY(ctx, hipMemcpyAsync(out->samples + (size_t)g0 * hs, d_x, 8 * (size_t)gc * hs, hipMemcpyDeviceToHost,
-                                        nullptr));
-    }
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    HIP_TRY(ctx, hipMemcpy(out->yhat, d_yh.p, 8 * gh, hipMemcpyDeviceToHost));
-    if (out->count) memcpy(out->count, r->count.data(), 8 * (size_t)G);
-    if (out->q) HIP_TRY(ctx, hipMemcpy(out->q, d_q.p, nqh, hipMemcpyDeviceToHost));
-    if (out->cum_q) HIP_TRY(ctx, hipMemcpy(out->cum_q, d_cq.p, nqh, hipMemcpyDeviceToHost));
-    return 0;
+    t.share = d_share.as<double>(); t.yout = outs.want(out->yhat, 8 * (size_t)r->G * r->H); t.H = r->H; t.NS = r->S;
+    return rollup_read(r, n_q, quantiles, *out, &t, outs);
 }
 
 // ---- diagnostics --------------------------------------------------------------------------------
@@ -4304,37 +4249,25 @@ extern "C" int tsf_screen_rows(tsf_ctx *ctx, int64_t N, int32_t T, const int64_t
     if (N == 0) return 0;
     if (int rc = check_screen_panel(ctx, N, T, offsets)) return rc;
     const size_t rows = offsets ? (size_t)offsets[N] : (size_t)N * T, ysz = ysize(y_dtype);
-    DevBuf d_off, d_y, d_fit, d_ex, d_ms, d_flag, d_res, d_cen, d_sc, d_nn, d_nf, d_st;
-    if (offsets) {
-        HIP_TRY(ctx, d_off.alloc(8 * ((size_t)N + 1)));
-        HIP_TRY(ctx, hipMemcpy(d_off.p, offsets, 8 * ((size_t)N + 1), hipMemcpyHostToDevice));
-    }
-    HIP_TRY(ctx, d_y.alloc(ysz * rows)); HIP_TRY(ctx, hipMemcpy(d_y.p, y, ysz * rows, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_fit.alloc(8 * rows)); HIP_TRY(ctx, hipMemcpy(d_fit.p, fitted, 8 * rows, hipMemcpyHostToDevice));
-    if (excluded) { HIP_TRY(ctx, d_ex.alloc(rows)); HIP_TRY(ctx, hipMemcpy(d_ex.p, excluded, rows, hipMemcpyHostToDevice)); }
-    if (min_scale) { HIP_TRY(ctx, d_ms.alloc(8 * (size_t)N)); HIP_TRY(ctx, hipMemcpy(d_ms.p, min_scale, 8 * (size_t)N, hipMemcpyHostToDevice)); }
+    DevBuf d_off, d_y, d_fit, d_ex, d_ms;
+    HostOuts outs;
+    if (offsets) HIP_TRY(ctx, d_off.put(offsets, 8 * ((size_t)N + 1)));
+    HIP_TRY(ctx, d_y.put(y, ysz * rows));
+    HIP_TRY(ctx, d_fit.put(fitted, 8 * rows));
+    if (excluded) HIP_TRY(ctx, d_ex.put(excluded, rows));
+    if (min_scale) HIP_TRY(ctx, d_ms.put(min_scale, 8 * (size_t)N));
     tsf_screen_out o;
     memset(&o, 0, sizeof(o));
-    HIP_TRY(ctx, d_flag.alloc(rows)); o.flag = d_flag.as<uint8_t>();
-    HIP_TRY(ctx, d_st.alloc(4 * (size_t)N)); o.status = d_st.as<int32_t>();
-    if (out->resid) { HIP_TRY(ctx, d_res.alloc(8 * rows)); o.resid = d_res.as<double>(); }
-    if (out->center) { HIP_TRY(ctx, d_cen.alloc(8 * (size_t)N)); o.center = d_cen.as<double>(); }
-    if (out->scale) { HIP_TRY(ctx, d_sc.alloc(8 * (size_t)N)); o.scale = d_sc.as<double>(); }
-    if (out->n_new) { HIP_TRY(ctx, d_nn.alloc(4 * (size_t)N)); o.n_new = d_nn.as<int32_t>(); }
-    if (out->n_flagged) { HIP_TRY(ctx, d_nf.alloc(4 * (size_t)N)); o.n_flagged = d_nf.as<int32_t>(); }
+    o.flag = outs.want(out->flag, rows); o.status = outs.want(out->status, 4 * (size_t)N);
+    o.resid = outs.want(out->resid, 8 * rows);
+    o.center = outs.want(out->center, 8 * (size_t)N); o.scale = outs.want(out->scale, 8 * (size_t)N);
+    o.n_new = outs.want(out->n_new, 4 * (size_t)N); o.n_flagged = outs.want(out->n_flagged, 4 * (size_t)N);
+    if (int rc = outs.ready(ctx)) return rc;
     if (int rc = screen_run(ctx, N, T, d_off.as<int64_t>(), offsets, d_y.p, y_dtype, d_fit.as<double>(), 0,
-                            excluded ? d_ex.as<uint8_t>() : nullptr, min_scale ? d_ms.as<double>() : nullptr, *args, o,
-                            nullptr, 0, nullptr))
+                            d_ex.as<uint8_t>(), d_ms.as<double>(), *args, o, nullptr, 0, nullptr))
         return rc;
     HIP_TRY(ctx, hipDeviceSynchronize());
-    if (rows) HIP_TRY(ctx, hipMemcpy(out->flag, d_flag.p, rows, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(out->status, d_st.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
-    if (out->resid && rows) HIP_TRY(ctx, hipMemcpy(out->resid, d_res.p, 8 * rows, hipMemcpyDeviceToHost));
-    if (out->center) HIP_TRY(ctx, hipMemcpy(out->center, d_cen.p, 8 * (size_t)N, hipMemcpyDeviceToHost));
-    if (out->scale) HIP_TRY(ctx, hipMemcpy(out->scale, d_sc.p, 8 * (size_t)N, hipMemcpyDeviceToHost));
-    if (out->n_new) HIP_TRY(ctx, hipMemcpy(out->n_new, d_nn.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
-    if (out->n_flagged) HIP_TRY(ctx, hipMemcpy(out->n_flagged, d_nf.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
-    return 0;
+    return outs.fetch(ctx);
 }
 
 // ---- the steps of tsf_fit_screened ------------------------------------------------------------------------------
@@ -4670,31 +4603,19 @@ extern "C" int tsf_calibrate_rows(tsf_ctx *ctx, int64_t N, const int64_t *row_of
     if (int rc = check_calib_rows(ctx, N, row_off)) return rc;
     const size_t R = (size_t)row_off[N], L = (size_t)args->n_levels, cells = (size_t)(args->n_buckets + 1) * L;
     const bool cqr = args->mode == TSF_CALIB_CQR;
-    DevBuf d_off, d_h, d_y, d_yh, d_lo, d_hi, d_q, d_n, d_st;
-    HIP_TRY(ctx, d_off.alloc(8 * ((size_t)N + 1))); HIP_TRY(ctx, hipMemcpy(d_off.p, row_off, 8 * ((size_t)N + 1), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_h.alloc(8 * R)); HIP_TRY(ctx, d_y.alloc(8 * R)); HIP_TRY(ctx, d_yh.alloc(8 * R));
-    if (R) {
-        HIP_TRY(ctx, hipMemcpy(d_h.p, horizon_ns, 8 * R, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(d_y.p, y, 8 * R, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(d_yh.p, yhat, 8 * R, hipMemcpyHostToDevice));
-    }
-    if (cqr) {
-        HIP_TRY(ctx, d_lo.alloc(8 * L * R)); HIP_TRY(ctx, d_hi.alloc(8 * L * R));
-        if (R) {
-            HIP_TRY(ctx, hipMemcpy(d_lo.p, lower, 8 * L * R, hipMemcpyHostToDevice));
-            HIP_TRY(ctx, hipMemcpy(d_hi.p, upper, 8 * L * R, hipMemcpyHostToDevice));
-        }
-    }
-    HIP_TRY(ctx, d_q.alloc(8 * (size_t)N * cells)); HIP_TRY(ctx, d_n.alloc(4 * (size_t)N * cells)); HIP_TRY(ctx, d_st.alloc(4 * (size_t)N));
-    const tsf_calib_table dt{d_q.as<double>(), d_n.as<int32_t>(), d_st.as<int32_t>()};
+    DevBuf d_off, d_h, d_y, d_yh, d_lo, d_hi;
+    HostOuts outs;
+    HIP_TRY(ctx, d_off.put(row_off, 8 * ((size_t)N + 1)));
+    HIP_TRY(ctx, d_h.put(horizon_ns, 8 * R)); HIP_TRY(ctx, d_y.put(y, 8 * R)); HIP_TRY(ctx, d_yh.put(yhat, 8 * R));
+    if (cqr) { HIP_TRY(ctx, d_lo.put(lower, 8 * L * R)); HIP_TRY(ctx, d_hi.put(upper, 8 * L * R)); }
+    const tsf_calib_table dt{outs.want(table->q, 8 * (size_t)N * cells), outs.want(table->n, 4 * (size_t)N * cells),
+                             outs.want(table->status, 4 * (size_t)N)};
+    if (int rc = outs.ready(ctx)) return rc;
     if (int rc = calib_run(ctx, N, d_off.as<int64_t>(), row_off, d_h.as<int64_t>(), d_y.as<double>(), d_yh.as<double>(),
-                           cqr ? d_lo.as<double>() : nullptr, cqr ? d_hi.as<double>() : nullptr, *args, dt, nullptr))
+                           d_lo.as<double>(), d_hi.as<double>(), *args, dt, nullptr))
         return rc;
     HIP_TRY(ctx, hipDeviceSynchronize());
-    HIP_TRY(ctx, hipMemcpy(table->q, d_q.p, 8 * (size_t)N * cells, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(table->n, d_n.p, 4 * (size_t)N * cells, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(table->status, d_st.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
-    return 0;
+    return outs.fetch(ctx);
 }
 
 static int check_calib_apply_call(tsf_ctx *ctx, int64_t N, int32_t H, const double *yhat, const double *lower,
@@ -4750,27 +4671,23 @@ extern "C" int tsf_apply_calibration(tsf_ctx *ctx, int64_t N, int32_t H, const d
     const size_t NH = (size_t)N * H, L = (size_t)args->n_levels, cells = (size_t)(args->n_buckets + 1) * L;
     const size_t n_ds = shared_future ? (size_t)H : NH;
     const bool cqr = args->mode == TSF_CALIB_CQR;
-    DevBuf d_yh, d_lw, d_up, d_ds, d_or, d_q, d_n, d_lo, d_hi, d_cell;
-    HIP_TRY(ctx, d_yh.alloc(8 * NH)); HIP_TRY(ctx, hipMemcpy(d_yh.p, yhat, 8 * NH, hipMemcpyHostToDevice));
-    if (cqr) {
-        HIP_TRY(ctx, d_lw.alloc(8 * L * NH)); HIP_TRY(ctx, hipMemcpy(d_lw.p, lower, 8 * L * NH, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, d_up.alloc(8 * L * NH)); HIP_TRY(ctx, hipMemcpy(d_up.p, upper, 8 * L * NH, hipMemcpyHostToDevice));
-    }
-    HIP_TRY(ctx, d_ds.alloc(8 * n_ds)); HIP_TRY(ctx, hipMemcpy(d_ds.p, ds_future, 8 * n_ds, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_or.alloc(8 * (size_t)N)); HIP_TRY(ctx, hipMemcpy(d_or.p, origin_ns, 8 * (size_t)N, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_q.alloc(8 * (size_t)N * cells)); HIP_TRY(ctx, hipMemcpy(d_q.p, q, 8 * (size_t)N * cells, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_n.alloc(4 * (size_t)N * cells)); HIP_TRY(ctx, hipMemcpy(d_n.p, n, 4 * (size_t)N * cells, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, d_lo.alloc(8 * L * NH)); HIP_TRY(ctx, d_hi.alloc(8 * L * NH));
-    if (cell) HIP_TRY(ctx, d_cell.alloc(L * NH));
-    if (int rc = calib_apply_run(ctx, N, H, d_yh.as<double>(), cqr ? d_lw.as<double>() : nullptr, cqr ? d_up.as<double>() : nullptr,
-                                 d_ds.as<int64_t>(), shared_future, d_or.as<int64_t>(), d_q.as<double>(), d_n.as<int32_t>(), *args,
-                                 d_lo.as<double>(), d_hi.as<double>(), cell ? d_cell.as<int8_t>() : nullptr, nullptr))
+    DevBuf d_yh, d_lw, d_up, d_ds, d_or, d_q, d_n;
+    HostOuts outs;
+    HIP_TRY(ctx, d_yh.put(yhat, 8 * NH));
+    if (cqr) { HIP_TRY(ctx, d_lw.put(lower, 8 * L * NH)); HIP_TRY(ctx, d_up.put(upper, 8 * L * NH)); }
+    HIP_TRY(ctx, d_ds.put(ds_future, 8 * n_ds));
+    HIP_TRY(ctx, d_or.put(origin_ns, 8 * (size_t)N));
+    HIP_TRY(ctx, d_q.put(q, 8 * (size_t)N * cells));
+    HIP_TRY(ctx, d_n.put(n, 4 * (size_t)N * cells));
+    double *d_lo = outs.want(lo, 8 * L * NH), *d_hi = outs.want(hi, 8 * L * NH);
+    int8_t *d_cell = outs.want(cell, L * NH);
+    if (int rc = outs.ready(ctx)) return rc;
+    if (int rc = calib_apply_run(ctx, N, H, d_yh.as<double>(), d_lw.as<double>(), d_up.as<double>(), d_ds.as<int64_t>(),
+                                 shared_future, d_or.as<int64_t>(), d_q.as<double>(), d_n.as<int32_t>(), *args, d_lo, d_hi,
+                                 d_cell, nullptr))
         return rc;
     HIP_TRY(ctx, hipDeviceSynchronize());
-    HIP_TRY(ctx, hipMemcpy(lo, d_lo.p, 8 * L * NH, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(hi, d_hi.p, 8 * L * NH, hipMemcpyDeviceToHost));
-    if (cell) HIP_TRY(ctx, hipMemcpy(cell, d_cell.p, L * NH, hipMemcpyDeviceToHost));
-    return 0;
+    return outs.fetch(ctx);
 }
 
 extern "C" int tsf_calibrate(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t T, const int64_t *offsets,

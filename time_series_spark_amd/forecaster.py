@@ -1330,6 +1330,15 @@ def _rollup_add_args(spec, theta, y_scale, grid, group, series_key, floor, cap, 
     return N, theta, y_scale, grid, group, key, floor, cap, ex, shared
 
 
+def _rollup_c_args(spec, args):
+    """What tsf_rollup_add, tsf_rollup_set_totals and tsf_rollup_reconcile take behind the handle, from
+    _rollup_add_args' tuple (whose arrays the caller keeps alive over the call)."""
+    N, theta, y_scale, grid, group, key, floor, cap, ex, shared = args
+    cs = spec.to_c()
+    return (ctypes.byref(cs), N, theta.ctypes.data, y_scale.ctypes.data, grid.ctypes.data, len(grid), _lib._ptr(floor),
+            _lib._ptr(cap), _lib._ptr(ex), shared, key.ctypes.data, group.ctypes.data)
+
+
 class Rollup(object):
     """One tsf_rollup: n_groups accumulators of uncertainty_samples summed draws per row of ds_future_ns [H], filled by
     add (once per spec, any number of calls) and read by quantiles / samples at any time.  A context manager; close()
@@ -1395,24 +1404,24 @@ class Rollup(object):
         (required: the streams of two add calls must differ; the scorer's is (series_id << 32) ^ dim_id).  extra_future:
         [n_extra][H] shared by the series, or [N][n_extra][H]."""
         h = self._handle()
-        N, theta, y_scale, grid, group, key, floor, cap, ex, shared = _rollup_add_args(
-            spec, theta, y_scale, grid, group, series_key, floor, cap, extra_future, self.G, self.H)
-        cs = spec.to_c()
-        self._ctx.check(_lib.load().tsf_rollup_add(h, ctypes.byref(cs), N, theta.ctypes.data, y_scale.ctypes.data,
-                                                   grid.ctypes.data, len(grid), _lib._ptr(floor), _lib._ptr(cap),
-                                                   _lib._ptr(ex), shared, key.ctypes.data, group.ctypes.data))
+        args = _rollup_add_args(spec, theta, y_scale, grid, group, series_key, floor, cap, extra_future, self.G, self.H)
+        self._ctx.check(_lib.load().tsf_rollup_add(h, *_rollup_c_args(spec, args)))
 
-    def _read(self, levels, want):
-        h = self._handle()
-        levels = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
-        Q = len(levels)
+    def _group_outs(self, Q, want):
+        """-> (dict of a tsf_rollup_out's arrays: yhat, count and those of q, cum_q, samples named in `want`; the struct)"""
         res = {'yhat': np.zeros((self.G, self.H)), 'count': np.zeros(self.G, dtype=np.int64)}
         for k in ('q', 'cum_q'):
             if k in want:
                 res[k] = np.zeros((self.G, Q, self.H))
         if 'samples' in want:
             res['samples'] = np.zeros((self.G, self.H, self.S))
-        out = _lib.TsfRollupOut(**{k: v.ctypes.data for k, v in res.items()})
+        return res, _lib.TsfRollupOut(**{k: v.ctypes.data for k, v in res.items()})
+
+    def _read(self, levels, want):
+        h = self._handle()
+        levels = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
+        Q = len(levels)
+        res, out = self._group_outs(Q, want)
         self._ctx.check(_lib.load().tsf_rollup_quantiles(h, Q, levels.ctypes.data if Q else None, ctypes.byref(out)))
         return res
 
@@ -1462,14 +1471,11 @@ class Rollup(object):
         all calls).  Forecast on the roll-up's calendar like the members of add; series_key [Gt] is required and must
         differ from every member's key (a shared key is a shared stream)."""
         h = self._handle()
-        N, theta, y_scale, grid, group, key, floor, cap, ex, shared = _rollup_add_args(
-            spec, theta, y_scale, grid, group, series_key, floor, cap, extra_future, self.G, self.H)
+        args = _rollup_add_args(spec, theta, y_scale, grid, group, series_key, floor, cap, extra_future, self.G, self.H)
+        N, group = args[0], args[4]
         if len(np.unique(group)) != N:
             raise ValueError('group: a group appears twice (one total per group)')
-        cs = spec.to_c()
-        self._ctx.check(_lib.load().tsf_rollup_set_totals(h, ctypes.byref(cs), N, theta.ctypes.data, y_scale.ctypes.data,
-                                                          grid.ctypes.data, len(grid), _lib._ptr(floor), _lib._ptr(cap),
-                                                          _lib._ptr(ex), shared, key.ctypes.data, group.ctypes.data))
+        self._ctx.check(_lib.load().tsf_rollup_set_totals(h, *_rollup_c_args(spec, args)))
 
     def reconcile(self, spec, theta, y_scale, grid, group, series_key, share, quantiles=(), cumulative=False,
                   samples=False, floor=None, cap=None, extra_future=None):
@@ -1478,8 +1484,8 @@ class Rollup(object):
         Quantiles: yhat [N][H], q and cum_q [N][Q][H] at the levels `quantiles`; .samples [N][H][S] where asked for).
         share [N] in [0, 1] (reconcile_shares); a group without a total leaves its members as they are."""
         h = self._handle()
-        N, theta, y_scale, grid, group, key, floor, cap, ex, shared = _rollup_add_args(
-            spec, theta, y_scale, grid, group, series_key, floor, cap, extra_future, self.G, self.H)
+        args = _rollup_add_args(spec, theta, y_scale, grid, group, series_key, floor, cap, extra_future, self.G, self.H)
+        N = args[0]
         share = np.ascontiguousarray(share, dtype=np.float64)
         if share.shape != (N,):
             raise ValueError('share must be [N]')
@@ -1498,11 +1504,8 @@ class Rollup(object):
         if samples:
             res['samples'] = np.zeros((N, self.H, self.S))
         out = _lib.TsfReconcileOut(**{k: v.ctypes.data for k, v in res.items()})
-        cs = spec.to_c()
-        self._ctx.check(_lib.load().tsf_rollup_reconcile(
-            h, ctypes.byref(cs), N, theta.ctypes.data, y_scale.ctypes.data, grid.ctypes.data, len(grid), _lib._ptr(floor),
-            _lib._ptr(cap), _lib._ptr(ex), shared, key.ctypes.data, group.ctypes.data, share.ctypes.data, Q,
-            levels.ctypes.data if Q else None, ctypes.byref(out)))
+        self._ctx.check(_lib.load().tsf_rollup_reconcile(h, *_rollup_c_args(spec, args), share.ctypes.data, Q,
+                                                         levels.ctypes.data if Q else None, ctypes.byref(out)))
         return Reconciled(res['yhat'], levels, res.get('q'), res.get('cum_q'), res.get('samples'))
 
     def reconciled_totals(self, share_total, levels, cumulative=False, samples=False):
@@ -1519,12 +1522,7 @@ class Rollup(object):
         Q = len(levels)
         if Q == 0:
             raise ValueError('at least one quantile level')
-        res = {'yhat': np.zeros((self.G, self.H)), 'count': np.zeros(self.G, dtype=np.int64), 'q': np.zeros((self.G, Q, self.H))}
-        if cumulative:
-            res['cum_q'] = np.zeros((self.G, Q, self.H))
-        if samples:
-            res['samples'] = np.zeros((self.G, self.H, self.S))
-        out = _lib.TsfRollupOut(**{k: v.ctypes.data for k, v in res.items()})
+        res, out = self._group_outs(Q, ['q'] + (['cum_q'] if cumulative else []) + (['samples'] if samples else []))
         self._ctx.check(_lib.load().tsf_rollup_reconciled_totals(h, mu.ctypes.data, Q, levels.ctypes.data, ctypes.byref(out)))
         r = RollupQuantiles(res['yhat'], res['count'], levels, res['q'], res.get('cum_q'))
         return (r, res['samples']) if samples else r
