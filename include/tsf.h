@@ -696,6 +696,54 @@ int tsf_residual_corr_dev(tsf_ctx *ctx, int64_t N, int32_t T, const void *y, int
                           const int64_t *group, int64_t G, const tsf_corr_args *args, tsf_corr_out *out, void *stream);
 int tsf_rollup_set_noise_corr(tsf_rollup *r, const double *rho /* [G] */, const int64_t *group_key /* [G], NULL = g */);
 
+/* ---- conditional seasonalities ---------------------------------------------------------------------
+ * Replaces the `condition_name=` argument of fbprophet 0.5's `Prophet.add_seasonality(name, period, fourier_order,
+ * prior_scale, mode, condition_name)`: a seasonality that applies only on the rows where a boolean column of the frame
+ * is true -- a weekly pattern that differs in and out of season, a daily pattern that differs on weekdays and
+ * weekends.  fbprophet builds the seasonality's Fourier columns and sets them to 0 on the rows where the column is
+ * false (make_all_seasonality_features: `features[~df[condition_name]] = 0`).  The reference job never adds one
+ * (prophet_modeler.py:65 takes the constructor's defaults); it is here because users of the model expect it.
+ *
+ * Here a conditional seasonality is LOWERED to explicit design columns: 2 * order entries of tsf_spec's extra columns
+ * per seasonality (prior scale and mode per column), whose values this entry builds from the timestamps and the
+ * condition rows.  No fit, predict or sampling kernel knows about conditions: every entry point that takes `extra` /
+ * `extra_future` follows.  For seasonality s (period p, order m, condition row c) the entry writes 2 * m columns
+ * [sin 1, cos 1, sin 2, cos 2, ...], seasonalities in the order of the struct, column j of the whole at
+ * cols + j * col_stride:
+ *   - row i with cond[c][i] != 0: the value the fit's own tables hold for an unconditional seasonality of that period
+ *     and order at timestamp ds[i] -- bit for bit (the same statements: the first harmonic from the library's sincos
+ *     at 2 pi t / p, t in days since the epoch, the others by the recurrence u[h+1] = 2 cos u[h] - u[h-1]);
+ *   - row i with cond[c][i] == 0: +0.0.
+ * A value is a function of (ds[i], p, harmonic, cond[c][i]) alone: not of the panel's first timestamp, of `rows` or of
+ * where the row stands, so the columns of a sub-range of rows are the sub-range of the columns (cross-validation folds,
+ * future rows).  cols may point INTO the caller's extra block -- col_stride is its row length -- beside the holiday and
+ * regressor columns; nothing but the rows [0, rows) of the sum of 2 * order columns is written.
+ *   - cs is host memory in both variants (as tsf_spec); ds / cond / cols are host pointers in the plain variant, device
+ *     pointers in _dev, which is asynchronous on `stream`.
+ *   - rows = 0 is a legal no-op.
+ *   - API misuse (return < 0, text through tsf_last_error, before any launch; the context stays usable): col_stride <
+ *     rows; n outside [1, TSF_MAX_SEAS]; a period that is not finite and > 0; an order < 1, or orders whose columns
+ *     exceed TSF_MAX_EXTRA; a condition index outside [0, n_cond).
+ * Deviation, on purpose: fbprophet keeps a conditional seasonality's columns among the seasonal columns, in the order
+ * the seasonalities were added; here they stand among the extra columns, behind the holidays and the caller's
+ * regressors.  The posterior is the same function of the same columns; the optimiser's trajectory -- and with it the
+ * last bits of a Stan-rule fit -- depends on the column order, as it does for every fit of this library.  A model with
+ * such columns has explicit columns, so its fits leave the lattice tables and the in-register harmonic expansion, as a
+ * model with holidays does.
+ * These semantics are restated from recall of fbprophet 0.5; parity with fbprophet itself is unpinned, as everywhere
+ * in this library. */
+typedef struct {
+    int32_t n;                          /* conditional seasonalities, 1 .. TSF_MAX_SEAS */
+    double  period[TSF_MAX_SEAS];       /* days, finite, > 0 */
+    int32_t order[TSF_MAX_SEAS];        /* >= 1; sum of 2*order <= TSF_MAX_EXTRA */
+    int32_t cond[TSF_MAX_SEAS];         /* index of its condition row, in [0, n_cond) */
+} tsf_cond_seas;
+int tsf_cond_columns(tsf_ctx *ctx, const tsf_cond_seas *cs, int64_t rows, const int64_t *ds,
+                     int32_t n_cond, const uint8_t *cond /* [n_cond][rows], non-zero = true */,
+                     double *cols /* [sum 2*order][col_stride] */, int64_t col_stride);
+int tsf_cond_columns_dev(tsf_ctx *ctx, const tsf_cond_seas *cs, int64_t rows, const int64_t *ds,
+                         int32_t n_cond, const uint8_t *cond, double *cols, int64_t col_stride, void *stream);
+
 /* ---- totals over row windows: quantiles and scores of calendar-period totals ----------------------------
  * "P10 / P50 / P90 of next week's total, of each calendar month, of every rolling 7-row block", for a series and for
  * a roll-up's group total, and how an observed total scores against it.  cum_q answers this only for windows that start

@@ -176,6 +176,12 @@ class TsfCorrOut(ctypes.Structure):
                 ('n_used', ctypes.c_void_p), ('status', ctypes.c_void_p), ('scale', ctypes.c_void_p)]
 
 
+class TsfCondSeas(ctypes.Structure):
+    """tsf_cond_seas (include/tsf.h)."""
+    _fields_ = [('n', ctypes.c_int32), ('period', ctypes.c_double * MAX_SEAS), ('order', ctypes.c_int32 * MAX_SEAS),
+                ('cond', ctypes.c_int32 * MAX_SEAS)]
+
+
 class TsfFitShape(ctypes.Structure):
     """tsf_fit_shape (include/tsf_dev.h)."""
     _fields_ = [('N', ctypes.c_int64), ('n_distinct', ctypes.c_int64), ('lat_step', ctypes.c_int64), ('lat_U', ctypes.c_int64),
@@ -210,6 +216,7 @@ EXPORTS = ['tsf_create', 'tsf_destroy', 'tsf_last_error', 'tsf_device_count', 't
            'tsf_window_out_size', 'tsf_predict_windows', 'tsf_predict_windows_dev', 'tsf_rollup_windows',
            'tsf_reconcile_shares', 'tsf_reconcile_out_size', 'tsf_rollup_set_totals', 'tsf_rollup_reconcile', 'tsf_rollup_reconciled_totals',
            'tsf_corr_args_size', 'tsf_corr_out_size', 'tsf_residual_corr', 'tsf_residual_corr_dev', 'tsf_rollup_set_noise_corr',
+           'tsf_cond_columns', 'tsf_cond_columns_dev',
            'tsf_eval', 'tsf_eval_quadratic', 'tsf_design', 'tsf_selftest_math',
            'tsf_set_option', 'tsf_get_option', 'tsf_set_cost_hints', 'tsf_set_profiling', 'tsf_profile_read', 'tsf_last_fit_kernel_ms', 'tsf_last_fit_route',
            'tsf_fit_plan', 'tsf_fit_plan_info_size', 'tsf_fit_plan_error', 'tsf_last_fit_plan',
@@ -320,6 +327,8 @@ def load():
     L.tsf_residual_corr.argtypes = [vp, i64, i32, vp, i32, vp, vp, i64, ctypes.POINTER(TsfCorrArgs), ctypes.POINTER(TsfCorrOut)]
     L.tsf_residual_corr_dev.argtypes = L.tsf_residual_corr.argtypes + [vp]
     L.tsf_rollup_set_noise_corr.argtypes = [vp, vp, vp]
+    L.tsf_cond_columns.argtypes = [vp, ctypes.POINTER(TsfCondSeas), i64, vp, i32, vp, vp, i64]
+    L.tsf_cond_columns_dev.argtypes = L.tsf_cond_columns.argtypes + [vp]
     L.tsf_eval.argtypes = [vp, psp, i64, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     L.tsf_eval_quadratic.argtypes = [vp, psp, i64, i32, vp, vp, i32, vp, vp, vp, vp, vp]
     L.tsf_design.argtypes = [vp, psp, i32, vp, vp, vp, vp, vp]

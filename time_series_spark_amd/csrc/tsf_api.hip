@@ -38,6 +38,7 @@
 #include "tsf_screen_kernels.h"
 #include "tsf_calib_kernels.h"
 #include "tsf_corr_kernels.h"
+#include "tsf_cond_kernels.h"
 #include "tsf_cv_plan.h"
 #include "tsf_fit_plan.h"
 
@@ -2470,6 +2471,86 @@ extern "C" int tsf_rollup_add(tsf_rollup *r, const tsf_spec *spec, int64_t N, co
         return rc;
     for (int64_t n = 0; n < N; ++n) r->count[(size_t)group[n]] += 1;
     r->added = true;
+    return 0;
+}
+
+// ---- conditional seasonalities: their design columns ----------------------------------------------------------
+
+// What both entries check before anything is launched (cs is host memory in both); *a: the kernel's arguments but for
+// its three pointers, *C: the number of columns.
+static int check_cond_call(tsf_ctx *ctx, const tsf_cond_seas *cs, int64_t rows, const int64_t *ds, int32_t n_cond,
+                           const uint8_t *cond, const double *cols, int64_t col_stride, CondArgs *a, int *C)
+{
+    if (!cs) return fail(ctx, "NULL tsf_cond_seas");
+    if (rows < 0) return fail(ctx, "rows must be >= 0");
+    if (col_stride < rows) return fail(ctx, "col_stride must be >= rows");
+    if (cs->n < 1 || cs->n > TSF_MAX_SEAS) return fail(ctx, "tsf_cond_seas.n must be in [1, TSF_MAX_SEAS]");
+    if (n_cond < 1) return fail(ctx, "n_cond must be >= 1");
+    memset(a, 0, sizeof(*a));
+    int col = 0;
+    char msg[120];
+    for (int s = 0; s < cs->n; ++s) {
+        if (!(std::isfinite(cs->period[s]) && cs->period[s] > 0.0)) {
+            snprintf(msg, sizeof(msg), "period[%d] = %g: a period must be finite and > 0", s, cs->period[s]);
+            return fail(ctx, msg);
+        }
+        if (cs->order[s] < 1 || cs->order[s] > TSF_MAX_EXTRA / 2) {
+            snprintf(msg, sizeof(msg), "order[%d] = %d: an order must be in [1, TSF_MAX_EXTRA / 2]", s, (int)cs->order[s]);
+            return fail(ctx, msg);
+        }
+        if (cs->cond[s] < 0 || cs->cond[s] >= n_cond) {
+            snprintf(msg, sizeof(msg), "cond[%d] = %d: outside [0, n_cond = %d)", s, (int)cs->cond[s], (int)n_cond);
+            return fail(ctx, msg);
+        }
+        a->period[s] = cs->period[s]; a->order[s] = cs->order[s]; a->cond_row[s] = cs->cond[s]; a->col0[s] = col;
+        col += 2 * cs->order[s];
+        if (col > TSF_MAX_EXTRA) return fail(ctx, "the orders give more than TSF_MAX_EXTRA columns (sum of 2 * order)");
+    }
+    if (rows > 0 && (!ds || !cond || !cols)) return fail(ctx, "NULL input (ds, cond and cols are required)");
+    a->n = cs->n; a->rows = rows; a->col_stride = col_stride;
+    *C = col;
+    return 0;
+}
+
+static int cond_launch(tsf_ctx *ctx, CondArgs a, const int64_t *d_ds, const uint8_t *d_cond, double *d_cols, hipStream_t st)
+{
+    a.ds = d_ds; a.cond = d_cond; a.cols = d_cols;
+    const int64_t blocks = std::min<int64_t>((a.rows + COND_BLOCK - 1) / COND_BLOCK, 65536);    // (a grid-stride loop)
+    hipLaunchKernelGGL(cond_columns_kernel, dim3((unsigned)blocks, (unsigned)a.n), dim3(COND_BLOCK), 0, st, a);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+extern "C" int tsf_cond_columns_dev(tsf_ctx *ctx, const tsf_cond_seas *cs, int64_t rows, const int64_t *ds, int32_t n_cond,
+                                    const uint8_t *cond, double *cols, int64_t col_stride, void *stream)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    CondArgs a;
+    int C = 0;
+    if (int rc = check_cond_call(ctx, cs, rows, ds, n_cond, cond, cols, col_stride, &a, &C)) return rc;
+    if (rows == 0) return 0;
+    return cond_launch(ctx, a, ds, cond, cols, (hipStream_t)stream);
+}
+
+extern "C" int tsf_cond_columns(tsf_ctx *ctx, const tsf_cond_seas *cs, int64_t rows, const int64_t *ds, int32_t n_cond,
+                                const uint8_t *cond, double *cols, int64_t col_stride)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    CondArgs a;
+    int C = 0;
+    if (int rc = check_cond_call(ctx, cs, rows, ds, n_cond, cond, cols, col_stride, &a, &C)) return rc;
+    if (rows == 0) return 0;
+    const size_t r = (size_t)rows;
+    DevBuf d_ds, d_cond, d_cols;
+    HIP_TRY(ctx, d_ds.put(ds, 8 * r));
+    HIP_TRY(ctx, d_cond.put(cond, (size_t)n_cond * r));
+    HIP_TRY(ctx, d_cols.alloc(8 * (size_t)C * r));
+    a.col_stride = rows;            // (the device copy is dense; the caller's stride is applied on the way back)
+    if (int rc = cond_launch(ctx, a, d_ds.as<int64_t>(), d_cond.as<uint8_t>(), d_cols.as<double>(), nullptr)) return rc;
+    // rows of `rows` doubles into rows of `col_stride`: what lies behind a column's rows at the caller's is not touched
+    HIP_TRY(ctx, hipMemcpy2D(cols, 8 * (size_t)col_stride, d_cols.p, 8 * r, 8 * r, (size_t)C, hipMemcpyDeviceToHost));
     return 0;
 }
 

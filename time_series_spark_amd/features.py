@@ -15,6 +15,9 @@ Prophet.setup_dataframe; reached by the reference through Prophet(...).fit(pdf),
   * the columns follow the model's seasonality_mode;
   * a regressor is standardised with the mean / sample std (ddof = 1) of its TRAINING values unless
     it has fewer than two distinct values, or standardize='auto' and its values are exactly {0, 1}.
+Conditions of conditional seasonalities (add_seasonality(condition_name=...)) that are functions of the date are
+evaluated here too (condition_mask): fbprophet reads a boolean column of the frame; a date rule needs no array and
+travels with the model.  The columns themselves are built on the device (forecaster.conditional_extra).
 """
 import numpy as np
 import pandas as pd
@@ -110,6 +113,61 @@ def holiday_matrix(ds_ns, days_per_column):
     for i, d in enumerate(days_per_column):
         out[i] = np.isin(day, d)
     return out
+
+
+CONDITION_RULE_KEYS = ('weekdays', 'months', 'ranges', 'negate')
+
+
+def normalize_condition_rule(rule):
+    """A date rule of ModelSpec(conditions={name: rule}) in its JSON-able form: {'weekdays': [0..6, Monday = 0],
+    'months': [1..12], 'ranges': [[start, end), ...] as ISO strings with nanoseconds, 'negate': bool}, each key only
+    where given.  ValueError on an unknown key or a value out of range."""
+    if not isinstance(rule, dict):
+        raise ValueError('a condition rule must be a dict over %s' % (CONDITION_RULE_KEYS,))
+    unknown = sorted(set(rule) - set(CONDITION_RULE_KEYS))
+    if unknown:
+        raise ValueError('unknown condition rule keys %s (known: %s)' % (unknown, CONDITION_RULE_KEYS))
+    out = {}
+    if rule.get('weekdays') is not None:
+        out['weekdays'] = [int(w) for w in rule['weekdays']]
+        if any(w < 0 or w > 6 for w in out['weekdays']):
+            raise ValueError('condition rule: weekdays must be in 0..6 (Monday = 0)')
+    if rule.get('months') is not None:
+        out['months'] = [int(m) for m in rule['months']]
+        if any(m < 1 or m > 12 for m in out['months']):
+            raise ValueError('condition rule: months must be in 1..12')
+    if rule.get('ranges') is not None:
+        out['ranges'] = []
+        for r in rule['ranges']:
+            if len(r) != 2:
+                raise ValueError('condition rule: a range is [start, end)')
+            a, b = (np.datetime64(pd.Timestamp(v).to_datetime64(), 'ns') for v in r)
+            out['ranges'].append([str(a), str(b)])
+    if rule.get('negate') is not None:
+        out['negate'] = bool(rule['negate'])
+    return out
+
+
+def condition_mask(rule, ds_ns):
+    """bool [...shape of ds_ns]: where the date rule holds.  weekdays / months are those of date(ds) in UTC (_day_number's
+    day arithmetic: floor, also before 1970); a row is in `ranges` if start <= ds < end for one of them (on the
+    timestamps themselves); the keys combine by AND; negate inverts the result."""
+    rule = normalize_condition_rule(rule)
+    ds_ns = np.asarray(ds_ns, dtype=np.int64)
+    day = _day_number(ds_ns)
+    m = np.ones(day.shape, dtype=bool)
+    if 'weekdays' in rule:
+        m &= np.isin(np.mod(day + 3, 7), rule['weekdays'])         # (1970-01-01 was a Thursday: weekday 3)
+    if 'months' in rule:
+        month = np.mod(day.astype('datetime64[D]').astype('datetime64[M]').astype(np.int64), 12) + 1
+        m &= np.isin(month, rule['months'])
+    if 'ranges' in rule:
+        inside = np.zeros(day.shape, dtype=bool)
+        for a, b in rule['ranges']:
+            lo, hi = (int(np.datetime64(v, 'ns').astype(np.int64)) for v in (a, b))
+            inside |= (ds_ns >= lo) & (ds_ns < hi)
+        m &= inside
+    return ~m if rule.get('negate') else m
 
 
 def standardize_regressor(train_values, standardize='auto'):

@@ -28,12 +28,20 @@ class ModelSpec(object):
     is a ValueError (fbprophet would fit two identical trend columns), ``n_changepoints`` becomes its length and
     ``changepoint_range`` is ignored.  A series whose history does not span every date comes back with status
     ST_CHANGEPOINT.  (Semantics restated from recall of fbprophet 0.5: include/tsf.h.)
+    A seasonality dict may carry ``condition_name`` -- fbprophet's ``add_seasonality(..., condition_name=...)``: the
+    seasonality applies only on the rows where the boolean condition of that name is true.  Such seasonalities are kept
+    in ``conditional`` (not in ``seasonalities``) and lowered to ``2 * fourier_order`` explicit columns at the end of
+    ``extra`` (include/tsf.h "conditional seasonalities"; fbprophet keeps them among the seasonal columns instead: same
+    posterior, another column order); ``conditional_extra`` builds the values of all of ``extra`` for any entry point.
+    conditions: optional {condition name: date rule} -- a dict with any of ``weekdays`` (Monday = 0), ``months``
+    (1..12), ``ranges`` ([start, end) dates) and ``negate``, combined by AND (features.condition_mask) -- for conditions
+    that are functions of the date: they need no array and travel with the model (to_dict / the model blobs).
     """
 
     def __init__(self, growth='linear', seasonality_mode='additive', n_changepoints=25,
                  changepoint_range=0.8, changepoint_prior_scale=0.05,
                  seasonality_prior_scale=10.0, holidays_prior_scale=10.0,
-                 seasonalities=None, extra=None, holidays=None, changepoints=None, **lbfgs):
+                 seasonalities=None, extra=None, holidays=None, changepoints=None, conditions=None, **lbfgs):
         if growth not in ('linear', 'logistic'):
             raise ValueError("Parameter 'growth' should be 'linear' or 'logistic'.")
         if seasonality_mode not in ('additive', 'multiplicative'):
@@ -48,8 +56,17 @@ class ModelSpec(object):
         self.changepoint_prior_scale = float(changepoint_prior_scale)
         self.seasonality_prior_scale = float(seasonality_prior_scale)
         self.holidays_prior_scale = float(holidays_prior_scale)
-        self.seasonalities = [dict(s) for s in (seasonalities or [])]
+        given = [dict(s) for s in (seasonalities or [])]
+        self.seasonalities = [s for s in given if s.get('condition_name') is None]
         self.extra = [dict(e) for e in (extra or [])]
+        # conditional seasonalities (condition_name): out of `seasonalities`, lowered to explicit columns behind the
+        # caller's own (_lower_conditional); _given_conditional: which entries of the original list they were
+        self.conditional = [s for s in given if s.get('condition_name') is not None]
+        self._given_conditional = [s.get('condition_name') is not None for s in given]
+        self.conditions = {}
+        if conditions:
+            from . import features
+            self.conditions = {str(k): features.normalize_condition_rule(v) for k, v in dict(conditions).items()}
         # normalised holidays (features.normalize_holidays) whose indicator columns are the FIRST
         # len(features.holiday_columns(holidays)[0]) entries of `extra`: carried so that the scorer
         # can rebuild the columns for future dates (fbprophet keeps the holidays frame in the model)
@@ -60,6 +77,60 @@ class ModelSpec(object):
                          'tol_grad', 'tol_rel_grad', 'tol_param', 'eval_form', 'recenter_every',
                          'recenter_ratio', 'algorithm', 'residual_kernel', 'coop_after', 'converge', 'map_max_iter', 'map_tol'):
                 raise TypeError('unknown optimiser option %r' % k)
+        if self.conditional:
+            self._lower_conditional()
+
+    def _lower_conditional(self):
+        """Every conditional seasonality becomes 2 * fourier_order entries at the end of `extra` -- behind the holiday
+        columns, which stay first, and the caller's regressors --, named '<seasonality>_delim_<j>' (j = 1 .. 2 * order:
+        sin 1, cos 1, sin 2, ...), with the SEASONALITY's prior scale and mode (its own, else seasonality_prior_scale /
+        seasonality_mode -- not holidays_prior_scale, the default of other extra columns) and a 'seasonality' key that
+        names it: component_columns gathers the columns under that name.  fbprophet's validate_column_name, restated,
+        on the seasonality's name and on condition_name: no '_delim_', no reserved name, no name used twice."""
+        from . import features
+        hol = {str(h['holiday']) for h in features.normalize_holidays(self.holidays)} if self.holidays else set()
+        reg = {str(e.get('name')) for e in self.extra}
+        seas = [str(s.get('name')) for s in self.seasonalities + self.conditional]
+
+        def check(name, own_seasonality=False):
+            if '_delim_' in name:
+                raise ValueError('Name cannot contain "_delim_"')
+            if name in features.RESERVED_NAMES and not (own_seasonality and name in ('daily', 'weekly', 'yearly')):
+                raise ValueError('Name "{}" is reserved.'.format(name))
+            if name in hol:
+                raise ValueError('Name "{}" already used for a holiday.'.format(name))
+            if seas.count(name) > int(own_seasonality):
+                raise ValueError('Name "{}" already used for a seasonality.'.format(name))
+            if name in reg:
+                raise ValueError('Name "{}" already used for an added regressor.'.format(name))
+
+        for s in self.conditional:
+            if s.get('name') is None:
+                raise ValueError('a conditional seasonality needs a name')
+            # (a user seasonality may be called 'weekly': it then stands in for the automatic one, auto_from_stats)
+            check(str(s['name']), own_seasonality=True)
+            if not isinstance(s['condition_name'], str):
+                raise ValueError('condition_name must be a string')
+            check(s['condition_name'])
+            order, period = int(s['fourier_order']), float(s['period'])
+            if order < 1:
+                raise ValueError('Fourier Order must be > 0')
+            if not (np.isfinite(period) and period > 0):
+                raise ValueError('period must be finite and > 0')
+            scale = float(s.get('prior_scale', self.seasonality_prior_scale))
+            if not scale > 0:
+                raise ValueError('Prior scale must be > 0')
+            mode = s.get('mode', self.seasonality_mode)
+            if mode not in ('additive', 'multiplicative'):
+                raise ValueError("mode must be 'additive' or 'multiplicative'")
+            for j in range(2 * order):
+                self.extra.append({'name': '%s_delim_%d' % (s['name'], j + 1), 'prior_scale': scale, 'mode': mode,
+                                   'seasonality': str(s['name'])})
+
+    @property
+    def n_user_extra(self):
+        """The extra columns whose values the caller supplies: all but the lowered conditional seasonalities'."""
+        return sum(1 for e in self.extra if 'seasonality' not in e)
 
     # -- fbprophet set_auto_seasonalities on a timestamp vector --------------------------------
     @staticmethod
@@ -153,13 +224,27 @@ class ModelSpec(object):
             setattr(s, k, v)
         return s
 
+    def _given_seasonalities(self):
+        """The seasonalities as the caller gave them: the conditional ones, with their condition_name, where they stood."""
+        if not self.conditional:
+            return self.seasonalities
+        plain, cond = iter(self.seasonalities), iter(self.conditional)
+        if len(self._given_conditional) != len(self.seasonalities) + len(self.conditional):    # (a list edited since)
+            return self.seasonalities + self.conditional
+        return [next(cond) if c else next(plain) for c in self._given_conditional]
+
     def to_dict(self):
+        """The ORIGINAL form: `seasonalities` holds the conditional ones too, `extra` the caller's columns only, so
+        from_dict lowers them again (to the same to_c struct)."""
         return {'growth': self.growth, 'seasonality_mode': self.seasonality_mode,
                 'n_changepoints': self.n_changepoints, 'changepoint_range': self.changepoint_range,
                 'changepoint_prior_scale': self.changepoint_prior_scale,
                 'seasonality_prior_scale': self.seasonality_prior_scale,
                 'holidays_prior_scale': self.holidays_prior_scale,
-                'seasonalities': self.seasonalities, 'extra': self.extra, 'lbfgs': self.lbfgs,
+                'seasonalities': self._given_seasonalities(),
+                'extra': [e for e in self.extra if 'seasonality' not in e] if self.conditional else self.extra,
+                'lbfgs': self.lbfgs,
+                **({'conditions': self.conditions} if self.conditions else {}),
                 **({'holidays': self.holidays} if self.holidays else {}),
                 # ISO strings with nanoseconds: JSON (the model blobs' prefix) and YAML keep them exactly
                 **({'changepoints': [str(np.datetime64(int(v), 'ns')) for v in self.changepoints]}
@@ -458,6 +543,93 @@ def fit_ragged(spec, offsets, ds_ns, y, floor=None, cap=None, extra=None, ctx=No
     return FitResult(spec, *arrs)
 
 
+# ---- conditional seasonalities: the one construction path of their columns ---------------------------
+
+def _condition_rows(spec, shape, ds_ns, conditions):
+    """uint8 [n_cond][...shape] and the condition row of each conditional seasonality: a condition given as an array
+    wins, else the spec's date rule of that name; fbprophet's two messages where neither exists / a value is no
+    boolean (setup_dataframe)."""
+    from . import features
+    names = []
+    for s in spec.conditional:
+        if s['condition_name'] not in names:
+            names.append(s['condition_name'])
+    conditions = conditions or {}
+    rows = np.zeros((len(names),) + shape, dtype=np.uint8)
+    for r, name in enumerate(names):
+        if name in conditions:
+            v = np.asarray(conditions[name])
+            if v.shape != shape:
+                raise ValueError("condition %r must have the shape of ds %r" % (name, shape))
+            if v.dtype != np.bool_:
+                try:                                                # (NaN, 2, 'yes', None: no boolean)
+                    f = np.asarray(v, dtype=np.float64) if v.dtype.kind not in 'USMm' else None
+                    ok = f is not None and bool(((f == 0) | (f == 1)).all())
+                except (TypeError, ValueError):
+                    ok = False
+                if not ok:
+                    raise ValueError("Found non-boolean in column %r" % name)
+                v = v.astype(bool)
+            rows[r] = v
+        elif name in spec.conditions:
+            rows[r] = features.condition_mask(spec.conditions[name], ds_ns)
+        else:
+            raise ValueError("Condition %r missing from dataframe" % name)
+    return rows, [names.index(s['condition_name']) for s in spec.conditional]
+
+
+def conditional_extra(spec, ds_ns, conditions=None, extra=None, offsets=None, ctx=None):
+    """The full `extra` array of `spec` -- the caller's columns in front, the columns of the conditional seasonalities
+    behind them (include/tsf.h tsf_cond_columns) -- for any entry point that takes `extra` / `extra_future`.
+
+    ds_ns [T] (an aligned panel's or a shared future's timestamps), conditions {name: bool [T]}, extra [n_user_extra][T]
+    -> [n_extra][T]; ds_ns ragged [rows] with offsets (fit_ragged's layout; a column value depends on its own row
+    alone, so the offsets are only checked) -> [n_extra][rows]; ds_ns [N][H], conditions [N][H] each, extra
+    [N][n_user_extra][H] -> [N][n_extra][H], predict's per-series future layout.  A condition not given falls back on the
+    spec's date rule of that name (ModelSpec(conditions=...)).  A spec without conditional seasonalities: `extra` as
+    given.  One upload of ds and the masks, one launch, one download."""
+    if not spec.conditional:
+        return extra
+    ds_ns = np.ascontiguousarray(ds_ns, dtype=np.int64)
+    if ds_ns.ndim not in (1, 2):
+        raise ValueError('ds must be [T], ragged [rows] or [N][H]')
+    if offsets is not None:
+        offsets = np.asarray(offsets, dtype=np.int64)
+        if ds_ns.ndim != 1 or len(offsets) < 1 or offsets[-1] != ds_ns.shape[0]:
+            raise ValueError('ds must be 1-D with offsets[-1] rows')
+    nu, ne = spec.n_user_extra, len(spec.extra)
+    C = ne - nu
+    ex = None
+    if nu:
+        ex = np.asarray(extra, dtype=np.float64)
+        want = (nu,) + ds_ns.shape if ds_ns.ndim == 1 else (ds_ns.shape[0], nu, ds_ns.shape[1])
+        if ex.shape != want:
+            raise ValueError('extra must be %r: the caller\'s %d columns' % (want, nu))
+    cond, which = _condition_rows(spec, ds_ns.shape, ds_ns, conditions)
+    cs = _lib.TsfCondSeas()
+    if len(spec.conditional) > _lib.MAX_SEAS or ne > _lib.MAX_EXTRA:
+        raise ValueError('too many seasonalities (max %d) or extra columns (max %d)' % (_lib.MAX_SEAS, _lib.MAX_EXTRA))
+    cs.n = len(spec.conditional)
+    for i, s in enumerate(spec.conditional):
+        cs.period[i], cs.order[i], cs.cond[i] = float(s['period']), int(s['fourier_order']), which[i]
+    rows = ds_ns.size
+    flat = ds_ns.ndim == 1
+    out = np.empty((ne, rows)) if flat else np.empty((ds_ns.shape[0], ne, ds_ns.shape[1]))
+    cols = out[nu:] if flat else np.empty((C, rows))       # (flat: written in place, at the stride of the whole block)
+    cond = np.ascontiguousarray(cond.reshape(len(cond), rows))
+    ctx = ctx or get_context()
+    ctx.check(_lib.load().tsf_cond_columns(ctx.handle, ctypes.byref(cs), rows, ds_ns.ctypes.data, cond.shape[0],
+                                           cond.ctypes.data, cols.ctypes.data, rows))
+    if flat:
+        if nu:
+            out[:nu] = ex
+    else:
+        if nu:
+            out[:, :nu] = ex
+        out[:, nu:] = cols.reshape(C, ds_ns.shape[0], ds_ns.shape[1]).transpose(1, 0, 2)
+    return out
+
+
 def predict(spec, theta, y_scale, grid, ds_future_ns, floor=None, cap=None, extra_future=None,
             want_int=False, ctx=None, devices=None):
     """yhat [N][H] (float64) and, if want_int, the reference's int-truncated + floor-clamped
@@ -534,7 +706,9 @@ def component_columns(spec):
     original design column j; scaled: the component is additive (times y_scale).  Components: one per seasonality; one
     per holiday (the name before '_delim_' of the leading extra columns features.holiday_columns(spec.holidays) names)
     and 'holidays'; one per other extra column (a regressor) except the 'zeros' placeholder, and
-    'extra_regressors_additive' / '_multiplicative' where non-empty; 'additive_terms' and 'multiplicative_terms'."""
+    'extra_regressors_additive' / '_multiplicative' where non-empty; 'additive_terms' and 'multiplicative_terms'.
+    The extra columns of a conditional seasonality (their 'seasonality' key) form one component of its name, counted
+    in its mode's total like any seasonality, not among the regressors."""
     from . import features
     ADD, MUL = 'additive', 'multiplicative'
     masks, modes = {}, {}
@@ -559,6 +733,8 @@ def component_columns(spec):
         if e < n_hol:
             put(ex['name'].split('_delim_')[0], bit, mode)
             hol |= bit
+        elif 'seasonality' in ex:             # a lowered conditional seasonality's column: a seasonality, not a regressor
+            put(ex['seasonality'], bit, mode)
         elif ex['name'] == 'zeros':           # fbprophet's placeholder column: in its mode's total, no component of its own
             total[mode] |= bit
         else:
@@ -2036,7 +2212,8 @@ def _n_holiday_columns(spec):
 
 def tune_candidates(spec, grid):
     """The candidates of a grid over TUNE_AXES (dict axis -> list of scales): itertools.product of the axes in
-    TUNE_AXES order, the first varying slowest.  seasonality_prior_scale replaces the prior scale of every seasonality;
+    TUNE_AXES order, the first varying slowest.  seasonality_prior_scale replaces the prior scale of every seasonality,
+    the conditional ones (and so their columns of `extra`) included;
     holidays_prior_scale that of the holiday columns of `extra` (the first len(features.holiday_columns(spec.holidays)
     [0]) entries) -- regressors keep their own scale.  -> (candidates [ModelSpec], params {axis: float64 [C]})."""
     import itertools
@@ -2046,7 +2223,7 @@ def tune_candidates(spec, grid):
     if unknown:
         raise ValueError('unknown grid axes %s (tunable: %s)' % (unknown, TUNE_AXES))
     n_hol = _n_holiday_columns(spec)
-    if 'seasonality_prior_scale' in grid and not spec.seasonalities:
+    if 'seasonality_prior_scale' in grid and not (spec.seasonalities or spec.conditional):
         raise ValueError('grid over seasonality_prior_scale, but the model has no seasonality')
     if 'holidays_prior_scale' in grid and n_hol == 0:
         raise ValueError('grid over holidays_prior_scale, but the model has no holidays')
@@ -2061,9 +2238,11 @@ def tune_candidates(spec, grid):
         values.append(v)
     cands, params = [], {k: [] for k in axes}
     for combo in itertools.product(*values):
+        # (the original form: the conditional seasonalities among `seasonalities`, lowered again by from_dict with the
+        # candidate's scale -- copying spec.extra would lower them twice)
         d = spec.to_dict()
-        d['seasonalities'] = [dict(s) for s in spec.seasonalities]
-        d['extra'] = [dict(e) for e in spec.extra]
+        d['seasonalities'] = [dict(s) for s in d['seasonalities']]
+        d['extra'] = [dict(e) for e in d['extra']]
         for e in d['extra'][n_hol:]:          # (a regressor without its own scale would follow holidays_prior_scale)
             e.setdefault('prior_scale', spec.holidays_prior_scale)
         for k, v in zip(axes, combo):
@@ -2084,8 +2263,13 @@ def _effective_scales(spec, cands):
     """{axis: [C]} the scale each candidate gives the axis's columns (the first such column; NaN where it has none)."""
     n_hol = _n_holiday_columns(spec)
     cs = [c.to_c() for c in cands]
+
+    def seas_scale(cand, c):        # (all seasonalities conditional: the first of their columns)
+        if c.n_seas:
+            return c.seas_prior_scale[0]
+        return c.extra_prior_scale[cand.n_user_extra] if cand.conditional else np.nan
     return {'changepoint_prior_scale': np.array([c.changepoint_prior_scale for c in cs]),
-            'seasonality_prior_scale': np.array([c.seas_prior_scale[0] if c.n_seas else np.nan for c in cs]),
+            'seasonality_prior_scale': np.array([seas_scale(cand, c) for cand, c in zip(cands, cs)]),
             'holidays_prior_scale': np.array([c.extra_prior_scale[0] if n_hol else np.nan for c in cs])}
 
 

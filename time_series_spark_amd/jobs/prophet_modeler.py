@@ -146,10 +146,33 @@ def _empty_models():
     return pd.DataFrame(columns=MODEL_OUTPUT_COLUMNS)
 
 
+def check_conditions(kw):
+    """model.prophet.seasonalities entries may carry condition_name (fbprophet's add_seasonality(condition_name=...));
+    the condition is then a date rule under model.prophet.conditions (features.condition_mask): the reference's input
+    schema (series_id, dim_id, ds, y) has no column to take a condition from, so a name without a rule is an error of
+    the configuration."""
+    rules = kw.get('conditions') or {}
+    for s in kw.get('seasonalities') or ():
+        name = s.get('condition_name')
+        if name is not None and name not in rules:
+            raise ValueError("model.prophet.seasonalities: condition_name %r has no rule under model.prophet.conditions"
+                             % (name,))
+    for rule in rules.values():
+        features.normalize_condition_rule(rule)
+
+
+def bucket_extra(spec, seas, ds, hol_days, hol_extra):
+    """The `extra` array of a bucket's rows ds: the holiday indicators (or fbprophet's zero column of a model without
+    any seasonality), then the columns of the spec's conditional seasonalities from its date rules."""
+    ex = features.holiday_matrix(ds, hol_days) if hol_extra else (np.zeros((1, len(ds))) if not seas else None)
+    return fc.conditional_extra(spec, ds, extra=ex)
+
+
 def bucket_models(panel, kw):
     """The models fbprophet would build for the series of a PackedPanel: series are bucketed by the seasonality set
     fbprophet's 'auto' rules give their own history (each Prophet object decides alone).  Returns (buckets, holidays,
     holiday days, holiday columns); buckets = [(seasonalities, members (sorted), model dict for ModelSpec)]."""
+    check_conditions(kw)
     span, min_dt, _ = pk.per_series_stats(panel)
     mode = kw.get('seasonality_mode', 'additive')
     growth = kw.get('growth', 'linear')
@@ -188,6 +211,8 @@ def bucket_models(panel, kw):
                          extra=[{'name': 'zeros', 'prior_scale': 1.0, 'mode': 'additive'}])
         else:
             model = dict(growth=growth, seasonality_mode=mode, seasonalities=seas)
+        if any(s.get('condition_name') is not None for s in seas):
+            model['conditions'] = kw.get('conditions')        # (the rules travel with the model: ModelSpec.to_dict)
         buckets.append((seas, members, model))
     return buckets, hol, hol_days, hol_extra
 
@@ -287,8 +312,7 @@ def fit_packed(panel, floor, cap, kw, devices=None, cost=None, lap=None, screen=
             T = int(panel.lengths[gm[0]])
             a0 = panel.offsets[gm[0]]
             y2d = pk.rows_2d(panel.y, panel.offsets, gm, T)
-            ex = features.holiday_matrix(panel.ds_ns[a0:a0 + T], hol_days) if hol_extra else (
-                np.zeros((1, T)) if not seas else None)
+            ex = bucket_extra(spec, seas, panel.ds_ns[a0:a0 + T], hol_days, hol_extra)
             calls.append((gm, fit_call(
                 spec, gm, panel.ds_ns[a0:a0 + T], y2d, None,
                 None if floor is None else np.asarray(floor)[gm],
@@ -306,8 +330,7 @@ def fit_packed(panel, floor, cap, kw, devices=None, cost=None, lap=None, screen=
             else:
                 idx = np.repeat(panel.offsets[rest] - off[:-1], lens) + np.arange(off[-1], dtype=np.int64)
                 ds_r, y_r = panel.ds_ns[idx], panel.y[idx]
-            ex = features.holiday_matrix(ds_r, hol_days) if hol_extra else (
-                np.zeros((1, len(ds_r))) if not seas else None)
+            ex = bucket_extra(spec, seas, ds_r, hol_days, hol_extra)
             calls.append((rest, fit_call(
                 spec, rest, ds_r, y_r, off,
                 None if floor is None else np.asarray(floor)[rest],

@@ -34,7 +34,8 @@ def _future_extra(spec, fut):
         return None
     # holiday columns for the future dates (fbprophet rebuilds them from the holidays
     # frame it keeps in the model); any other explicit column has no future values in
-    # the reference's scorer (its future frame holds ds, floor, cap only): zeros
+    # the reference's scorer (its future frame holds ds, floor, cap only): zeros; the columns of a conditional
+    # seasonality are rebuilt from the future dates like the holidays'
     ex = np.zeros((fut.shape[0], len(spec.extra), fut.shape[1]))
     if spec.holidays:
         names, _scales, days = features.holiday_columns(features.normalize_holidays(spec.holidays))
@@ -44,7 +45,8 @@ def _future_extra(spec, fut):
             raise ValueError('model blob: the holiday columns rebuilt from `holidays` do not match '
                              'the leading entries of `extra`')
         ex[:, :len(names), :] = np.moveaxis(features.holiday_matrix(fut, days), 0, 1)
-    return ex
+    # the columns of conditional seasonalities, from the date rules the blob carries (ModelSpec.conditions)
+    return fc.conditional_extra(spec, fut, extra=ex[:, :spec.n_user_extra, :])
 
 
 def forecast_arrays(config):

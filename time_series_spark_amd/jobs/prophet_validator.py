@@ -46,7 +46,7 @@ import time
 import numpy as np
 import pandas as pd
 
-from .. import _lib, features, forecaster as fc, panel as pk
+from .. import _lib, forecaster as fc, panel as pk
 from . import prophet_modeler as pm
 
 CV_STATUS_NAMES = {_lib.CV_LESS_THAN_HORIZON: 'Less data than horizon.',
@@ -154,7 +154,7 @@ def _buckets(config, panel):
         off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
         idx = np.repeat(panel.offsets[members] - off[:-1], lens) + np.arange(off[-1], dtype=np.int64)
         ds_r, y_r = panel.ds_ns[idx], panel.y[idx]
-        ex = features.holiday_matrix(ds_r, hol_days) if hol_extra else (np.zeros((1, len(ds_r))) if not seas else None)
+        ex = pm.bucket_extra(spec, seas, ds_r, hol_days, hol_extra)
         yield spec, members, off, ds_r, y_r, ex, cap[members]
 
 
@@ -247,7 +247,7 @@ def tune_panel(config, panel):
     out = []
     for spec, members, off, ds_r, y_r, ex, cap_m in _buckets(config, panel):
         g = dict(grid)
-        if not spec.seasonalities:
+        if not (spec.seasonalities or spec.conditional):
             g.pop('seasonality_prior_scale', None)
         if not spec.holidays:
             g.pop('holidays_prior_scale', None)
