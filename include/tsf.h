@@ -696,6 +696,94 @@ int tsf_residual_corr_dev(tsf_ctx *ctx, int64_t N, int32_t T, const void *y, int
                           const int64_t *group, int64_t G, const tsf_corr_args *args, tsf_corr_out *out, void *stream);
 int tsf_rollup_set_noise_corr(tsf_rollup *r, const double *rho /* [G] */, const int64_t *group_key /* [G], NULL = g */);
 
+/* ---- serially correlated observation noise: AR(1) per series ---------------------------------------
+ * The observation noise of the draws is independent from row to row; the residuals of a real fit are not (a promotion,
+ * a cold spell, an outage lasts several rows), and with lag-one autocorrelation phi the spread of a total over n rows
+ * is too narrow by a factor that tends to sqrt((1 + phi) / (1 - phi)): 2.0 at phi = 0.6, 1.36 at phi = 0.3.  This is the
+ * time-direction twin of the correlated roll-ups above.  Two pieces, both opt-in: an estimator of each series' residual
+ * autocorrelation from the fit's own history, and a one-shot context setting that makes the next drawing entry chain the
+ * noise of each sample's rows.  Reference interface replaced: none (neither the reference nor fbprophet has such a
+ * function); parity unpinned (what is pinned is the contract below: the estimator bit for bit against a numpy
+ * restatement, tests/ar_ref.py, and the chain against the independent draw's own normals).  Timing:
+ * tools/bench_noise_ar.py; DESIGN.md 5o.  Without a setting every entry is what it always was, bit for bit.
+ *
+ * Limits, stated plainly.  Lag one ROW, not one unit of time: a Friday-to-Monday pair counts as lag one, rows are taken
+ * as equally spaced (in the history for the estimate, in the future for the draw).  phi is estimated in sample, on
+ * residuals that a flexible fit shrinks and may push negative.  A negative estimate is clipped to 0 (phi_raw is there
+ * for the caller who wants it).  Uncentred: the residuals' mean is taken as 0.  The estimator is biased towards 0 by a
+ * term of order phi / T: with A = sum r_t r_{t-1} / np, B = ss / n and a Gaussian AR(1) of unit variance,
+ * Cov(A, B) ~ 4 phi / (T (1 - phi^2)) and Var(B) ~ 2 (1 + phi^2) / (T (1 - phi^2)), so the ratio's second-order
+ * expansion E[A / B] ~ phi - Cov(A, B) + phi Var(B) gives E[phi_raw] ~ phi - 2 phi / T; what the fit's own parameters
+ * remove from the residuals comes on top and is not derived here.  Only the observation noise is chained: the sampled
+ * trend changes are what they were.  One phi per series: no higher lags, no seasonal lag.
+ *
+ * tsf_residual_autocorr.  Panel: aligned (offsets NULL: y, fitted are [N][T]) or ragged (T ignored; series n owns rows
+ * offsets[n] .. offsets[n + 1], as tsf_screen_rows takes them).  y in y_dtype; fitted double -- tsf_predict of each fit
+ * on its own history dates; args (NULL: the defaults) {phi_max = 0.95, min_pairs = 8}.  Outputs per series: phi, status
+ * (required), phi_raw, n_pairs, scale (NULL: not wanted).  Host pointers in the host variant; in _dev y, fitted and
+ * every output are device pointers, while offsets, args and the tsf_ar_out struct itself are HOST memory, and the call
+ * synchronises the stream before it returns.
+ * Contract, in plain double operations with one rounding each (no fused multiply-add, no atomics; a series' result
+ * depends on nothing else in the batch):
+ *   Row t of a series is present where r_t = (double)y_t - fitted_t is finite; n = the present rows, ss = sum of
+ *   r_t * r_t over them.  A pair is a row t >= 1 of the series with t and t - 1 both present; np = the pairs,
+ *   C = sum of r_t * r_{t-1} over them.
+ *   phi_raw = (C / (double)np) / (ss / (double)n),  phi = fmin(fmax(phi_raw, 0), phi_max),
+ *   scale = sqrt(ss / (double)n), n_pairs = np.
+ *   np < min_pairs or ss == 0: phi_raw = NaN, phi = +0.0, status TSF_AR_NO_PAIRS; otherwise TSF_AR_OK.  scale is NaN
+ *   only where n == 0 or ss == 0.
+ *   The two sums (ss, C): 64 partials from +0.0, partial l adds rows (for C: pairs, by their row t) l, l + 64, ... of the
+ *   series in ascending order (an absent row or pair adds +0.0); the partials are combined by the xor butterfly
+ *   v[l] = v[l] + v[l ^ d] for d = 1, 2, 4, 8, 16, 32.
+ * Refusals (< 0 with a message, before any launch; the context stays usable): a NULL out, out->phi or out->status; NULL
+ *   y or fitted with N > 0; a bad y_dtype; phi_max outside [0, 1); min_pairs < 1; T < 1 on an aligned call; offsets
+ *   that do not start at 0 or decrease.  N == 0 is a legal no-op.
+ *
+ * tsf_set_noise_ar.  phi: HOST [n], each finite with |phi| < 1 (a negative value is legal here: the estimator never
+ * returns one, a caller may); NULL or n == 0 clears.  The setting is consumed by the NEXT drawing entry on this context
+ * and is gone afterwards whatever that call returns.  It stores c = sqrt(1 - phi * phi) beside each phi, formed on the
+ * host in double (IEEE sqrt).  The entries that take it, with their _dev forms: tsf_predict_intervals,
+ * tsf_predict_quantiles, tsf_score_actuals, tsf_predict_windows, and tsf_rollup_add on a handle without a noise
+ * correlation; phi[i] belongs to series i of that call, and a call with N != n fails with a message (it is never
+ * silently ignored: this is a statistical setting, not a scheduling hint).  The pairs cross to the device from host
+ * memory, so a _dev entry that takes a setting synchronises its stream once, before its first launch.  In such a call
+ * the standard normal z_h that the draw of series i, sample s, row h makes from its noise stream (counters 2h, 2h + 1:
+ * untouched) is replaced by e_h:
+ *   e_0 = z_0;   e_h = phi * e_{h-1} + c * z_h   (two products and one add, each rounded),
+ * in the caller's row order, never restarted -- not where unsorted future rows restart the trend sweep either, the rule
+ * of the running sum -- and the sample is trend * (1 + mult) + add + (e_h * sigma) * y_scale as always.  A series with
+ * phi == 0 takes the independent expression exactly (a select, not 0 * e + 1 * z), so its bits are those of a call
+ * without a setting.  The start is stationary, so each row's marginal law is unchanged (per-row quantiles and intervals
+ * keep their law), rows i, j of one sample correlate phi^|i - j|, and samples, series and the sampled trend stay
+ * independent; sample s still depends on nothing but (seed, series key, s, phi).  Every consumer of the draws inherits
+ * the chain: the running sums, the window totals, the scores, the roll-up's accumulators.
+ * Every other entry that draws refuses (< 0 with a message, before any launch) while a setting is pending, and clears
+ * it: tsf_predict_components, tsf_cross_validate and tsf_calibrate, tsf_rollup_set_totals, tsf_rollup_reconcile, and
+ * tsf_rollup_add on a handle with tsf_rollup_set_noise_corr (that route regenerates z from the counters and would
+ * disagree with the chain).  Entries that do not draw (fits, tsf_predict, the roll-up's reads) leave the setting alone.
+ * Out of scope: the job configurations and the model blob (the scorer has models and no history). */
+enum { TSF_AR_OK = 0, TSF_AR_NO_PAIRS = -51 };
+typedef struct {
+    double phi_max;         /* the estimate is clipped to [0, phi_max]; default 0.95; in [0, 1) */
+    int32_t min_pairs;      /* a series with fewer pairs gets phi = 0 and TSF_AR_NO_PAIRS; default 8 */
+    int32_t reserved_;      /* 0 */
+} tsf_ar_args;
+typedef struct {
+    double *phi;            /* [N] required: the clipped estimate, what tsf_set_noise_ar takes */
+    double *phi_raw;        /* [N] the estimate before clipping (NaN without pairs); NULL: not wanted */
+    int64_t *n_pairs;       /* [N] the pairs of the series; NULL: not wanted */
+    double *scale;          /* [N] the residual root mean square; NULL: not wanted */
+    int32_t *status;        /* [N] required: TSF_AR_* */
+} tsf_ar_out;
+int tsf_ar_args_size(void);         /* sizeof(tsf_ar_args), sizeof(tsf_ar_out): the self-checks of a binding */
+int tsf_ar_out_size(void);
+int tsf_residual_autocorr(tsf_ctx *ctx, int64_t N, int32_t T, const int64_t *offsets /* NULL = aligned [N][T] */, const void *y,
+                          int32_t y_dtype, const double *fitted, const tsf_ar_args *args /* NULL = defaults */,
+                          tsf_ar_out *out);
+int tsf_residual_autocorr_dev(tsf_ctx *ctx, int64_t N, int32_t T, const int64_t *offsets /* host */, const void *y,
+                              int32_t y_dtype, const double *fitted, const tsf_ar_args *args, tsf_ar_out *out, void *stream);
+int tsf_set_noise_ar(tsf_ctx *ctx, const double *phi /* host [n] */, int64_t n);
+
 /* ---- conditional seasonalities ---------------------------------------------------------------------
  * Replaces the `condition_name=` argument of fbprophet 0.5's `Prophet.add_seasonality(name, period, fourier_order,
  * prior_scale, mode, condition_name)`: a seasonality that applies only on the rows where a boolean column of the frame

@@ -176,6 +176,17 @@ class TsfCorrOut(ctypes.Structure):
                 ('n_used', ctypes.c_void_p), ('status', ctypes.c_void_p), ('scale', ctypes.c_void_p)]
 
 
+class TsfArArgs(ctypes.Structure):
+    """tsf_ar_args (include/tsf.h)."""
+    _fields_ = [('phi_max', ctypes.c_double), ('min_pairs', ctypes.c_int32), ('reserved_', ctypes.c_int32)]
+
+
+class TsfArOut(ctypes.Structure):
+    """tsf_ar_out (include/tsf.h)."""
+    _fields_ = [('phi', ctypes.c_void_p), ('phi_raw', ctypes.c_void_p), ('n_pairs', ctypes.c_void_p),
+                ('scale', ctypes.c_void_p), ('status', ctypes.c_void_p)]
+
+
 class TsfCondSeas(ctypes.Structure):
     """tsf_cond_seas (include/tsf.h)."""
     _fields_ = [('n', ctypes.c_int32), ('period', ctypes.c_double * MAX_SEAS), ('order', ctypes.c_int32 * MAX_SEAS),
@@ -216,6 +227,7 @@ EXPORTS = ['tsf_create', 'tsf_destroy', 'tsf_last_error', 'tsf_device_count', 't
            'tsf_window_out_size', 'tsf_predict_windows', 'tsf_predict_windows_dev', 'tsf_rollup_windows',
            'tsf_reconcile_shares', 'tsf_reconcile_out_size', 'tsf_rollup_set_totals', 'tsf_rollup_reconcile', 'tsf_rollup_reconciled_totals',
            'tsf_corr_args_size', 'tsf_corr_out_size', 'tsf_residual_corr', 'tsf_residual_corr_dev', 'tsf_rollup_set_noise_corr',
+           'tsf_ar_args_size', 'tsf_ar_out_size', 'tsf_residual_autocorr', 'tsf_residual_autocorr_dev', 'tsf_set_noise_ar',
            'tsf_cond_columns', 'tsf_cond_columns_dev',
            'tsf_eval', 'tsf_eval_quadratic', 'tsf_design', 'tsf_selftest_math',
            'tsf_set_option', 'tsf_get_option', 'tsf_set_cost_hints', 'tsf_set_profiling', 'tsf_profile_read', 'tsf_last_fit_kernel_ms', 'tsf_last_fit_route',
@@ -247,6 +259,8 @@ CALIB_OK, CALIB_NO_SCORES, CALIB_TOO_LONG = 0, -40, -41
 CALIB_MAX_ROWS, CALIB_MAX_LEVELS, CALIB_MAX_BUCKETS = 16384, 16, 64
 # TSF_CORR_* (include/tsf.h): per-group outcome of the residual-correlation estimator
 CORR_OK, CORR_NO_PAIRS = 0, -50
+# TSF_AR_* (include/tsf.h): per-series outcome of the residual-autocorrelation estimator
+AR_OK, AR_NO_PAIRS = 0, -51
 
 # TSF_ROUTE_* / TSF_CALL_* / TSF_PLAN_* (include/tsf_dev.h): a fit plan's route, the kind of call, why a call has no plan
 ROUTE_NEWTON, ROUTE_NEWTON_QUAD, ROUTE_QUAD_EVAL, ROUTE_QUAD_LBFGS, ROUTE_MFMA, ROUTE_WAVE = range(6)
@@ -327,6 +341,9 @@ def load():
     L.tsf_residual_corr.argtypes = [vp, i64, i32, vp, i32, vp, vp, i64, ctypes.POINTER(TsfCorrArgs), ctypes.POINTER(TsfCorrOut)]
     L.tsf_residual_corr_dev.argtypes = L.tsf_residual_corr.argtypes + [vp]
     L.tsf_rollup_set_noise_corr.argtypes = [vp, vp, vp]
+    L.tsf_residual_autocorr.argtypes = [vp, i64, i32, vp, vp, i32, vp, ctypes.POINTER(TsfArArgs), ctypes.POINTER(TsfArOut)]
+    L.tsf_residual_autocorr_dev.argtypes = L.tsf_residual_autocorr.argtypes + [vp]
+    L.tsf_set_noise_ar.argtypes = [vp, vp, i64]
     L.tsf_cond_columns.argtypes = [vp, ctypes.POINTER(TsfCondSeas), i64, vp, i32, vp, vp, i64]
     L.tsf_cond_columns_dev.argtypes = L.tsf_cond_columns.argtypes + [vp]
     L.tsf_eval.argtypes = [vp, psp, i64, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
@@ -418,6 +435,8 @@ def load():
         raise TsfError('tsf_calib_args / tsf_calib_table layout mismatch between _lib.py and libtsf_amd.so')
     if L.tsf_corr_args_size() != ctypes.sizeof(TsfCorrArgs) or L.tsf_corr_out_size() != ctypes.sizeof(TsfCorrOut):
         raise TsfError('tsf_corr_args / tsf_corr_out layout mismatch between _lib.py and libtsf_amd.so')
+    if L.tsf_ar_args_size() != ctypes.sizeof(TsfArArgs) or L.tsf_ar_out_size() != ctypes.sizeof(TsfArOut):
+        raise TsfError('tsf_ar_args / tsf_ar_out layout mismatch between _lib.py and libtsf_amd.so')
     if L.tsf_fit_plan_info_size() != ctypes.sizeof(TsfFitPlanInfo):
         raise TsfError('tsf_fit_plan_info layout mismatch between _lib.py and libtsf_amd.so')
     _lib = L

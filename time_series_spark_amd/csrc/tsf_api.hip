@@ -38,6 +38,7 @@
 #include "tsf_screen_kernels.h"
 #include "tsf_calib_kernels.h"
 #include "tsf_corr_kernels.h"
+#include "tsf_ar_kernels.h"
 #include "tsf_cond_kernels.h"
 #include "tsf_cv_plan.h"
 #include "tsf_fit_plan.h"
@@ -77,6 +78,9 @@ struct tsf_ctx {
     int32_t cv_launches;
     int32_t tune_expand;    // tsf_last_tune_counts: fold panels cut / fit launches of the last tsf_tune call
     int32_t tune_fits;
+    std::vector<double> ar_pending;   // tsf_set_noise_ar: the pending (phi, c) pairs, [n][2]; empty: none pending
+    double *ar_dev;         // the pairs of the draw that took them, on the device (grown on demand)
+    size_t ar_dev_bytes;
 };
 
 #define HIP_TRY(ctx, expr)                                                                   \
@@ -114,6 +118,7 @@ extern "C" int tsf_create(int device_id, tsf_ctx **out)
     c->nb_ws = nullptr; c->nb_ws_bytes = 0;
     c->iv_ws = nullptr; c->iv_ws_bytes = 0;
     c->comp_tab = nullptr;
+    c->ar_dev = nullptr; c->ar_dev_bytes = 0;
     c->order_dev[0] = c->order_dev[1] = nullptr; c->order_cap[0] = c->order_cap[1] = 0; c->order_next = 0; c->order_n = 0;
     c->order_ev[0] = c->order_ev[1] = nullptr; c->order_busy[0] = c->order_busy[1] = 0;
     c->profiling = 0; c->ev_created = 0; c->ev_count = 0;
@@ -145,6 +150,7 @@ extern "C" void tsf_destroy(tsf_ctx *ctx)
     if (ctx->nb_ws) hipFree(ctx->nb_ws);
     if (ctx->iv_ws) hipFree(ctx->iv_ws);
     if (ctx->comp_tab) hipFree(ctx->comp_tab);
+    if (ctx->ar_dev) hipFree(ctx->ar_dev);
     for (int b = 0; b < 2; ++b) { if (ctx->order_dev[b]) hipFree(ctx->order_dev[b]); if (ctx->order_ev[b]) hipEventDestroy(ctx->order_ev[b]); }
     if (ctx->ev_created)
         for (int i = 0; i < TSF_PROFILE_RING; ++i) { hipEventDestroy(ctx->ev0[i]); hipEventDestroy(ctx->ev1[i]); }
@@ -1668,7 +1674,60 @@ struct DrawSpec {
     uint64_t seed;
     bool want_cum, want_trend;
     double *yhat, *trend_out;
+    bool takes_ar;          // the entry takes a pending tsf_set_noise_ar; false: it refuses while one is pending
 };
+
+// The one-shot rule of tsf_set_noise_ar.  An entry that draws holds a NoiseArOnce from its first line, so the setting
+// is gone when the entry returns, whatever it returns; draw_chunks takes the setting or refuses it by DrawSpec's flag,
+// and the drawing entries that reach draw_chunks through another public entry refuse it themselves (refuse_noise_ar).
+struct NoiseArOnce {
+    tsf_ctx *ctx;
+    explicit NoiseArOnce(tsf_ctx *c) : ctx(c) {}
+    ~NoiseArOnce() { if (ctx) ctx->ar_pending.clear(); }
+    NoiseArOnce(const NoiseArOnce &) = delete;
+    NoiseArOnce &operator=(const NoiseArOnce &) = delete;
+};
+
+static int refuse_noise_ar(tsf_ctx *ctx, const char *who)
+{
+    if (ctx->ar_pending.empty()) return 0;
+    ctx->ar_pending.clear();
+    ctx->err = std::string(who) + ": a tsf_set_noise_ar setting is pending and this entry does not take it (the setting is cleared)";
+    return -1;
+}
+
+// a pending setting is for N series, or the call fails (and the setting is cleared)
+static int check_noise_ar_count(tsf_ctx *ctx, int64_t N)
+{
+    const int64_t n = (int64_t)(ctx->ar_pending.size() / 2);
+    if (n == 0 || n == N) return 0;
+    ctx->ar_pending.clear();
+    char msg[160];
+    snprintf(msg, sizeof(msg), "tsf_set_noise_ar was given %lld series and this call has N = %lld (the setting is cleared)",
+             (long long)n, (long long)N);
+    return fail(ctx, msg);
+}
+
+// The pending pairs onto the device for a draw of N series on st; *dev: the pairs, or null where nothing is pending.
+static int take_noise_ar(tsf_ctx *ctx, int64_t N, hipStream_t st, const double **dev)
+{
+    *dev = nullptr;
+    if (int rc = check_noise_ar_count(ctx, N)) return rc;
+    if (ctx->ar_pending.empty()) return 0;
+    std::vector<double> pairs;
+    pairs.swap(ctx->ar_pending);
+    const size_t need = 8 * pairs.size();
+    // (an earlier draw on this stream may still read the buffer)
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (ctx->ar_dev_bytes < need) {
+        if (ctx->ar_dev) { HIP_TRY(ctx, hipFree(ctx->ar_dev)); ctx->ar_dev = nullptr; ctx->ar_dev_bytes = 0; }
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->ar_dev, need));
+        ctx->ar_dev_bytes = need;
+    }
+    HIP_TRY(ctx, hipMemcpy(ctx->ar_dev, pairs.data(), need, hipMemcpyHostToDevice));
+    *dev = ctx->ar_dev;
+    return 0;
+}
 
 // series per chunk: n_buf sample buffers and the three per-row pieces of a chunk within 512 MB
 static int64_t draw_chunk_series(int64_t N, int32_t H, int32_t n_samples, size_t n_buf)
@@ -1698,6 +1757,10 @@ template <class After>
 static int draw_chunks(tsf_ctx *ctx, const tsf_spec *spec, const ForecastIn &f, const DrawSpec &d, hipStream_t st,
                        After &&after)
 {
+    if (!d.takes_ar)
+        if (int rc = refuse_noise_ar(ctx, "this drawing entry")) return rc;
+    const double *d_ar = nullptr;
+    if (int rc = take_noise_ar(ctx, f.N, st, &d_ar)) return rc;
     DevSpec hs;
     if (int rc = forecast_prologue(ctx, spec, f, st, &hs)) return rc;
     const int64_t N = f.N;
@@ -1720,6 +1783,7 @@ static int draw_chunks(tsf_ctx *ctx, const tsf_spec *spec, const ForecastIn &f, 
     a.theta = f.theta; a.y_scale = f.y_scale; a.grid = f.grid; a.floor_ = f.floor_; a.cap = f.cap;
     a.series_key = f.series_key; a.seed = d.seed;
     a.samples = d_samp; a.trend_samples = d_tsamp; a.cum_samples = d_cum;
+    a.noise_ar = d_ar;
     const DrawBufs bufs = {d_samp, d_cum, d_tsamp};
     bool tab_ready = false;
     for (int64_t n0 = 0; n0 < N; n0 += chunk) {
@@ -1728,8 +1792,9 @@ static int draw_chunks(tsf_ctx *ctx, const tsf_spec *spec, const ForecastIn &f, 
         if (int prc = launch_predict(ctx, hs, p, n0, nc, &tab_ready, st)) return prc;
         a.n0 = n0; a.n_chunk = nc;
         a.t = d_t - (size_t)n0 * H; a.xa = d_xa - (size_t)n0 * H; a.opm = d_opm - (size_t)n0 * H;
-        hipLaunchKernelGGL(interval_sample_kernel, dim3((unsigned)nc, (unsigned)((n_samples + 255) / 256)),
-                           dim3(256), 0, st, a);
+        const dim3 sgrid((unsigned)nc, (unsigned)((n_samples + 255) / 256));
+        if (d_ar) hipLaunchKernelGGL(interval_sample_kernel<true>, sgrid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(interval_sample_kernel<false>, sgrid, dim3(256), 0, st, a);
         HIP_TRY(ctx, hipGetLastError());
         if (int arc = after(n0, nc, bufs)) return arc;
     }
@@ -1770,6 +1835,7 @@ extern "C" int tsf_predict_intervals_dev(tsf_ctx *ctx, const tsf_spec *spec, int
                                          double *yhat, double *yhat_lower, double *yhat_upper, void *stream)
 {
     if (!ctx) return -1;
+    NoiseArOnce ar_once(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const ForecastIn f = {N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap, extra_future, series_key};
     if (int rc = check_forecast_in(ctx, f, spec && yhat && yhat_lower && yhat_upper)) return rc;
@@ -1777,7 +1843,7 @@ extern "C" int tsf_predict_intervals_dev(tsf_ctx *ctx, const tsf_spec *spec, int
     if (!(interval_width > 0.0 && interval_width < 1.0)) return fail(ctx, "interval_width must be in (0, 1)");
     hipStream_t st = (hipStream_t)stream;
     const Percentiles pc = {H, n_samples, interval_width, st};
-    const DrawSpec d = {n_samples, seed, false, false, yhat, nullptr};
+    const DrawSpec d = {n_samples, seed, false, false, yhat, nullptr, true};
     return draw_chunks(ctx, spec, f, d, st, [&](int64_t n0, int64_t nc, const DrawBufs &b) -> int {
         return pc.launch(ctx, b.samp, n0, nc, yhat_lower, yhat_upper);
     });
@@ -1793,6 +1859,7 @@ extern "C" int tsf_predict_intervals(tsf_ctx *ctx, const tsf_spec *spec, int64_t
                                      double *yhat, double *yhat_lower, double *yhat_upper)
 {
     if (!ctx) return -1;
+    NoiseArOnce ar_once(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const ForecastIn h = {N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap, extra_future, series_key};
     if (int rc = check_forecast_in(ctx, h, spec && yhat && yhat_lower && yhat_upper)) return rc;
@@ -1848,6 +1915,9 @@ extern "C" int tsf_predict_components_dev(tsf_ctx *ctx, const tsf_spec *spec, in
                                           double *trend_upper, void *stream)
 {
     if (!ctx) return -1;
+    NoiseArOnce ar_once(n_samples != 0 ? ctx : nullptr);        // (without samples the entry draws nothing)
+    if (n_samples != 0)
+        if (int rc = refuse_noise_ar(ctx, "tsf_predict_components")) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const ForecastIn f = {N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap, extra_future, series_key};
     if (int rc = check_forecast_in(ctx, f, spec && yhat && trend)) return rc;
@@ -1874,7 +1944,7 @@ extern "C" int tsf_predict_components_dev(tsf_ctx *ctx, const tsf_spec *spec, in
     } else {
         // a second sample buffer (the sampled trend), and the percentiles of both
         const Percentiles pc = {H, n_samples, interval_width, st};
-        const DrawSpec d = {n_samples, seed, false, true, yhat, trend};
+        const DrawSpec d = {n_samples, seed, false, true, yhat, trend, false};
         int rc = draw_chunks(ctx, spec, f, d, st, [&](int64_t n0, int64_t nc, const DrawBufs &b) -> int {
             if (int prc = pc.launch(ctx, b.samp, n0, nc, yhat_lower, yhat_upper)) return prc;
             return pc.launch(ctx, b.trend, n0, nc, trend_lower, trend_upper);
@@ -1908,6 +1978,9 @@ extern "C" int tsf_predict_components(tsf_ctx *ctx, const tsf_spec *spec, int64_
                                       double *yhat_lower, double *yhat_upper, double *trend_lower, double *trend_upper)
 {
     if (!ctx) return -1;
+    NoiseArOnce ar_once(n_samples != 0 ? ctx : nullptr);        // (without samples the entry draws nothing)
+    if (n_samples != 0)
+        if (int rc = refuse_noise_ar(ctx, "tsf_predict_components")) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const bool iv = n_samples != 0;
     // (the keys matter to the draws only)
@@ -2018,7 +2091,7 @@ static int predict_quantiles_run(tsf_ctx *ctx, const tsf_spec *spec, const Forec
         if (o.trend_samples) HIP_TRY(ctx, hipMemcpyAsync(o.trend_samples + off, b.trend, nb, kind, st));
         return 0;
     };
-    const DrawSpec d = {n_samples, c.seed, o.cum_q != nullptr, o.trend_q || o.trend_samples, o.yhat, nullptr};
+    const DrawSpec d = {n_samples, c.seed, o.cum_q != nullptr, o.trend_q || o.trend_samples, o.yhat, nullptr, true};
     return draw_chunks(ctx, spec, f, d, st, after);
 }
 
@@ -2030,6 +2103,7 @@ extern "C" int tsf_predict_quantiles_dev(tsf_ctx *ctx, const tsf_spec *spec, int
                                          const double *quantiles, tsf_quantile_out *out, void *stream)
 {
     if (!ctx) return -1;
+    NoiseArOnce ar_once(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const ForecastIn f = {N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap, extra_future, series_key};
     if (int rc = check_forecast_in(ctx, f, spec != nullptr)) return rc;
@@ -2046,6 +2120,7 @@ extern "C" int tsf_predict_quantiles(tsf_ctx *ctx, const tsf_spec *spec, int64_t
                                      const double *quantiles, tsf_quantile_out *out)
 {
     if (!ctx) return -1;
+    NoiseArOnce ar_once(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const ForecastIn h = {N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap, extra_future, series_key};
     if (int rc = check_forecast_in(ctx, h, spec != nullptr)) return rc;
@@ -2118,7 +2193,7 @@ static int score_actuals_run(tsf_ctx *ctx, const tsf_spec *spec, const ForecastI
             HIP_TRY(ctx, hipGetLastError());
             return 0;
         };
-        const DrawSpec d = {n_samples, c.seed, false, false, o.yhat, nullptr};
+        const DrawSpec d = {n_samples, c.seed, false, false, o.yhat, nullptr, true};
         if (int rc = draw_chunks(ctx, spec, f, d, st, after)) return rc;
     } else {
         // n_obs alone: no draw is needed, only yhat
@@ -2147,6 +2222,7 @@ extern "C" int tsf_score_actuals_dev(tsf_ctx *ctx, const tsf_spec *spec, int64_t
                                      const double *quantiles, tsf_score_out *out, void *stream)
 {
     if (!ctx) return -1;
+    NoiseArOnce ar_once(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (N < 0 || H <= 0) return fail(ctx, "N must be >= 0 and H > 0");
     if (int rc = check_score_args(ctx, n_samples, n_q, quantiles, y_obs, out)) return rc;
@@ -2163,6 +2239,7 @@ extern "C" int tsf_score_actuals(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, 
                                  const double *y_obs, int32_t n_q, const double *quantiles, tsf_score_out *out)
 {
     if (!ctx) return -1;
+    NoiseArOnce ar_once(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (N < 0 || H <= 0) return fail(ctx, "N must be >= 0 and H > 0");
     const ForecastIn h = {N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap, extra_future, series_key};
@@ -2447,7 +2524,7 @@ static int rollup_accumulate(tsf_rollup *r, const tsf_spec *spec, int64_t N, con
         HIP_TRY(ctx, hipGetLastError());
         return 0;
     };
-    const DrawSpec d = {S, r->seed, false, false, d_yh.as<double>(), nullptr};
+    const DrawSpec d = {S, r->seed, false, false, d_yh.as<double>(), nullptr, acc == r->acc && !r->corr};
     int rc = draw_chunks(ctx, spec, in.up.dev, d, nullptr, after);
     if (rc) return rc;
     HIP_TRY(ctx, hipDeviceSynchronize());
@@ -2460,9 +2537,14 @@ extern "C" int tsf_rollup_add(tsf_rollup *r, const tsf_spec *spec, int64_t N, co
                               const double *extra_future, int32_t shared_extra, const int64_t *series_key,
                               const int64_t *group)
 {
+    NoiseArOnce ar_once(r ? r->ctx : nullptr);
     if (int rc = rollup_enter(r)) return rc;
     tsf_ctx *ctx = r->ctx;
+    // (before anything is launched: a refusal leaves the accumulators untouched and the handle usable)
+    if (r->corr)
+        if (int rc = refuse_noise_ar(ctx, "tsf_rollup_add on a handle with a noise correlation")) return rc;
     if (N < 0) return fail(ctx, "N must be >= 0");
+    if (int rc = check_noise_ar_count(ctx, N)) return rc;
     if (N == 0) return 0;
     if (int rc = rollup_check_series(r, spec, N, theta, y_scale, grid, n_grids, cap, extra_future, series_key, group))
         return rc;
@@ -2668,6 +2750,109 @@ extern "C" int tsf_residual_corr(tsf_ctx *ctx, int64_t N, int32_t T, const void 
     // (corr_run ends with a synchronisation of its stream)
     if (int rc = corr_run(ctx, N, T, d_y.p, y_dtype, d_fit.as<double>(), group, G, a, o, nullptr)) return rc;
     return outs.fetch(ctx);
+}
+
+// ---- serially correlated observation noise: the estimator of a series' residual autocorrelation, and the setting ----
+
+extern "C" int tsf_ar_args_size(void) { return (int)sizeof(tsf_ar_args); }
+extern "C" int tsf_ar_out_size(void) { return (int)sizeof(tsf_ar_out); }
+
+// What both estimator entries check before anything is launched; offsets and args are host memory in both.  *a: the
+// arguments in force (the defaults where args is NULL).
+static int check_ar_call(tsf_ctx *ctx, int64_t N, int32_t T, const int64_t *offsets, const void *y, int32_t y_dtype,
+                         const double *fitted, const tsf_ar_args *args, const tsf_ar_out *out, tsf_ar_args *a)
+{
+    if (N < 0 || N > (int64_t)INT32_MAX) return fail(ctx, "N must be in [0, 2^31 - 1]");
+    if (!out || !out->phi || !out->status) return fail(ctx, "NULL output (tsf_ar_out, its phi and its status are required)");
+    a->phi_max = 0.95; a->min_pairs = 8; a->reserved_ = 0;
+    if (args) *a = *args;
+    if (!(a->phi_max >= 0.0 && a->phi_max < 1.0)) return fail(ctx, "phi_max must be in [0, 1)");
+    if (a->min_pairs < 1) return fail(ctx, "min_pairs must be >= 1");
+    if (y_dtype < TSF_Y_F64 || y_dtype > TSF_Y_I32) return fail(ctx, "bad y_dtype");
+    if (N > 0 && (!y || !fitted)) return fail(ctx, "NULL input (y and fitted are required)");
+    if (!offsets) return T >= 1 ? 0 : fail(ctx, "bad panel (aligned: T >= 1)");
+    if (offsets[0] != 0) return fail(ctx, "bad panel (ragged: offsets[0] = 0)");
+    for (int64_t n = 0; n < N; ++n)
+        if (offsets[n + 1] < offsets[n]) return fail(ctx, "bad panel (ragged: offsets ascending)");
+    return 0;
+}
+
+// The estimator on device-resident y and fitted; d_off: the offsets on the device (null aligned); o: device pointers.
+static int ar_run(tsf_ctx *ctx, int64_t N, int32_t T, const int64_t *d_off, const void *d_y, int32_t y_dtype,
+                  const double *d_fit, const tsf_ar_args &a, const tsf_ar_out &o, hipStream_t st)
+{
+    if (N == 0) return 0;
+    const ArArgs k = {d_y, d_fit, d_off, N, T, y_dtype, a.min_pairs, a.phi_max, o.phi, o.phi_raw, o.n_pairs, o.scale, o.status};
+    hipLaunchKernelGGL(ar_series_kernel, dim3((unsigned)((N + AR_WAVES - 1) / AR_WAVES)), dim3(AR_WAVES * 64), 0, st, k,
+                       (int)TSF_AR_OK, (int)TSF_AR_NO_PAIRS);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+extern "C" int tsf_residual_autocorr_dev(tsf_ctx *ctx, int64_t N, int32_t T, const int64_t *offsets, const void *y,
+                                         int32_t y_dtype, const double *fitted, const tsf_ar_args *args, tsf_ar_out *out,
+                                         void *stream)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    tsf_ar_args a;
+    if (int rc = check_ar_call(ctx, N, T, offsets, y, y_dtype, fitted, args, out, &a)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf d_off;
+    if (offsets && N > 0) HIP_TRY(ctx, d_off.put(offsets, 8 * ((size_t)N + 1)));
+    if (int rc = ar_run(ctx, N, T, offsets ? d_off.as<int64_t>() : nullptr, y, y_dtype, fitted, a, *out, st)) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(st));         // (the offsets go back to the pool)
+    return 0;
+}
+
+extern "C" int tsf_residual_autocorr(tsf_ctx *ctx, int64_t N, int32_t T, const int64_t *offsets, const void *y,
+                                     int32_t y_dtype, const double *fitted, const tsf_ar_args *args, tsf_ar_out *out)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    tsf_ar_args a;
+    if (int rc = check_ar_call(ctx, N, T, offsets, y, y_dtype, fitted, args, out, &a)) return rc;
+    if (N == 0) return 0;
+    const size_t rows = offsets ? (size_t)offsets[N] : (size_t)N * T, n = (size_t)N;
+    DevBuf d_off, d_y, d_fit;
+    HostOuts outs;
+    if (offsets) HIP_TRY(ctx, d_off.put(offsets, 8 * (n + 1)));
+    HIP_TRY(ctx, d_y.put(y, ysize(y_dtype) * rows));
+    HIP_TRY(ctx, d_fit.put(fitted, 8 * rows));
+    tsf_ar_out o;
+    memset(&o, 0, sizeof(o));
+    o.phi = outs.want(out->phi, 8 * n); o.status = outs.want(out->status, 4 * n);
+    o.phi_raw = outs.want(out->phi_raw, 8 * n); o.n_pairs = outs.want(out->n_pairs, 8 * n);
+    o.scale = outs.want(out->scale, 8 * n);
+    if (int rc = outs.ready(ctx)) return rc;
+    if (int rc = ar_run(ctx, N, T, offsets ? d_off.as<int64_t>() : nullptr, d_y.p, y_dtype, d_fit.as<double>(), a, o, nullptr))
+        return rc;
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    return outs.fetch(ctx);
+}
+
+extern "C" int tsf_set_noise_ar(tsf_ctx *ctx, const double *phi, int64_t n)
+{
+    if (!ctx) return -1;
+    ctx->ar_pending.clear();
+    if (!phi || n <= 0) return 0;
+    for (int64_t i = 0; i < n; ++i)
+        if (!(std::fabs(phi[i]) < 1.0)) {            // (NaN fails the comparison)
+            char msg[120];
+            snprintf(msg, sizeof(msg), "phi[%lld] = %g: an autocorrelation must be finite with |phi| < 1", (long long)i, phi[i]);
+            return fail(ctx, msg);
+        }
+    try {
+        ctx->ar_pending.resize(2 * (size_t)n);
+    } catch (const std::bad_alloc &) {
+        ctx->ar_pending.clear();
+        return fail(ctx, "tsf_set_noise_ar: out of host memory");
+    }
+    for (int64_t i = 0; i < n; ++i) {
+        ctx->ar_pending[2 * (size_t)i] = phi[i];
+        ctx->ar_pending[2 * (size_t)i + 1] = std::sqrt(1.0 - phi[i] * phi[i]);
+    }
+    return 0;
 }
 
 extern "C" int tsf_rollup_set_noise_corr(tsf_rollup *r, const double *rho, const int64_t *group_key)
@@ -2933,7 +3118,7 @@ static int predict_windows_run(tsf_ctx *ctx, const tsf_spec *spec, const Forecas
         auto after = [&](int64_t n0, int64_t nc, const DrawBufs &b) -> int {
             return launch_window_scores(ctx, a, b.samp, n0, nc, st);
         };
-        const DrawSpec d = {n_samples, c.seed, false, false, yhat, nullptr};
+        const DrawSpec d = {n_samples, c.seed, false, false, yhat, nullptr, true};
         if (int rc = draw_chunks(ctx, spec, f, d, st, after)) return rc;
     } else if (need_yhat) {
         if (int rc = tsf_predict_dev(ctx, spec, N, H, f.theta, f.y_scale, f.grid, f.n_grids, f.ds_future, f.shared_future,
@@ -2952,6 +3137,7 @@ extern "C" int tsf_predict_windows_dev(tsf_ctx *ctx, const tsf_spec *spec, int64
                                        tsf_window_out *out, void *stream)
 {
     if (!ctx) return -1;
+    NoiseArOnce ar_once(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const ForecastIn f = {N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap, extra_future, series_key};
     if (int rc = check_forecast_in(ctx, f, spec != nullptr)) return rc;
@@ -2984,6 +3170,7 @@ extern "C" int tsf_predict_windows(tsf_ctx *ctx, const tsf_spec *spec, int64_t N
                                    int32_t n_q, const double *quantiles, tsf_window_out *out)
 {
     if (!ctx) return -1;
+    NoiseArOnce ar_once(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const ForecastIn h = {N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap, extra_future, series_key};
     if (int rc = check_forecast_in(ctx, h, spec != nullptr)) return rc;
@@ -3065,8 +3252,10 @@ extern "C" int tsf_rollup_set_totals(tsf_rollup *r, const tsf_spec *spec, int64_
                                      const double *floor_, const double *cap, const double *extra_future,
                                      int32_t shared_extra, const int64_t *series_key, const int64_t *group)
 {
+    NoiseArOnce ar_once(r ? r->ctx : nullptr);
     if (int rc = rollup_enter(r, true)) return rc;
     tsf_ctx *ctx = r->ctx;
+    if (int rc = refuse_noise_ar(ctx, "tsf_rollup_set_totals")) return rc;
     if (Gt < 0) return fail(ctx, "N must be >= 0");
     if (Gt == 0) return 0;
     if (int rc = rollup_check_series(r, spec, Gt, theta, y_scale, grid, n_grids, cap, extra_future, series_key, group))
@@ -3131,8 +3320,10 @@ extern "C" int tsf_rollup_reconcile(tsf_rollup *r, const tsf_spec *spec, int64_t
                                     int32_t shared_extra, const int64_t *series_key, const int64_t *group,
                                     const double *share, int32_t n_q, const double *quantiles, tsf_reconcile_out *out)
 {
+    NoiseArOnce ar_once(r ? r->ctx : nullptr);
     if (int rc = rollup_enter(r, true)) return rc;
     tsf_ctx *ctx = r->ctx;
+    if (int rc = refuse_noise_ar(ctx, "tsf_rollup_reconcile")) return rc;
     if (N < 0) return fail(ctx, "N must be >= 0");
     if (N == 0) return 0;
     if (!r->top) return fail(ctx, "tsf_rollup_reconcile before any tsf_rollup_set_totals: the roll-up has no total");
@@ -3187,7 +3378,7 @@ extern "C" int tsf_rollup_reconcile(tsf_rollup *r, const tsf_spec *spec, int64_t
                                         hipMemcpyDeviceToHost, nullptr));
         return 0;
     };
-    const DrawSpec d = {S, r->seed, out->cum_q != nullptr, false, d_yh, nullptr};
+    const DrawSpec d = {S, r->seed, out->cum_q != nullptr, false, d_yh, nullptr, false};
     if (int rc = draw_chunks(ctx, spec, in.up.dev, d, nullptr, after)) return rc;
     HIP_TRY(ctx, hipDeviceSynchronize());
     return outs.fetch(ctx);
@@ -3897,6 +4088,10 @@ static int cross_validate_run(tsf_ctx *ctx, const tsf_spec *spec, const PanelIn 
                               const int64_t *series_key, int32_t n_samples, double interval_width, uint64_t seed,
                               tsf_cv_out *out, const tsf_calib_args *cal, const tsf_calib_table *tab)
 {
+    // with intervals the folds' holdout rows are drawn (through tsf_predict_intervals_dev, which would take the setting)
+    NoiseArOnce ar_once(n_samples > 0 ? ctx : nullptr);
+    if (n_samples > 0)
+        if (int rc = refuse_noise_ar(ctx, "cross-validation / calibration with intervals")) return rc;
     tsf_cv_args a;
     if (int rc = cv_check_args(ctx, spec, p, args, n_samples, interval_width, out, cal, &a)) return rc;
     const bool iv = n_samples > 0;

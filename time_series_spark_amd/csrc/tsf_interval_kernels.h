@@ -7,12 +7,15 @@
 // sample, stream), deterministic transcendentals, the sampled changepoint times generated already
 // sorted.  These kernels consume the same streams in the same order: bit-identical to the oracle.
 //   interval_sample_kernel      one thread per (series, sample): sweeps the future rows, writes
-//                               samples[series][row][sample] (and, where asked, the sampled trend alike)
+//                               samples[series][row][sample] (and, where asked, the sampled trend alike); its
+//                               <true> instance chains the noise of a sample's rows (tsf_set_noise_ar), which is
+//                               this library's own and not the oracle's: tests/ar_ref.py restates it
 //   interval_percentile_kernel  one workgroup per (series, row): bitonic sort of the samples in LDS,
 //                               the two percentiles by linear interpolation (np.nanpercentile)
 //   quantile_kernel             the same sort once per (series, row), then any number of levels from the sorted
 //                               row (tsf_predict_quantiles: one launch per sample buffer -- yhat, running sum, trend)
-// Non-template __global__ functions: include from exactly one translation unit (tsf_api.hip).
+// Non-template __global__ functions (and one template that only tsf_api.hip instantiates): include from exactly one
+// translation unit (tsf_api.hip).
 #pragma once
 #include "tsf_common.h"
 
@@ -68,8 +71,12 @@ struct IntervalArgs {
     double *trend_samples;      // optional [n_chunk][H][NS]: each sample's trend before noise (tsf_predict_components)
     double *lower, *upper;      // [N][H]
     double *cum_samples;        // optional [n_chunk][H][NS]: each sample's running sum over rows 0..h (tsf_predict_quantiles)
+    const double *noise_ar;     // optional [N][2]: each series' (phi, sqrt(1 - phi^2)) of tsf_set_noise_ar (the AR instance only)
 };
 
+// AR: the instance that chains the observation noise of a sample's rows (tsf_set_noise_ar); the other instance is the
+// independent draw, whose code knows nothing of the chain.
+template <bool AR>
 __global__ __launch_bounds__(256) void interval_sample_kernel(IntervalArgs a)
 {
     const int64_t nl = blockIdx.x, n = a.n0 + nl;
@@ -101,6 +108,10 @@ __global__ __launch_bounds__(256) void interval_sample_kernel(IntervalArgs a)
     uint64_t ctr = 0;
     double *out = a.samples + (size_t)nl * H * a.NS + s;
     double csum = 0.0;          // the running sum of this sample's rows, in the caller's row order (never restarted)
+    // the noise chain of this sample's rows, in the caller's row order (never restarted either): e_0 = z_0 (the
+    // stationary start), e_h = phi e_{h-1} + c z_h, two products and one add, each rounded
+    double ar_phi = 0.0, ar_c = 0.0, ar_e = 0.0;
+    if (AR) { ar_phi = a.noise_ar[2 * (size_t)n]; ar_c = a.noise_ar[2 * (size_t)n + 1]; }
     for (int h = 0; h < H; ++h) {
         const double th_ = t[h];
         if (h == 0 || th_ < t_last) {       // (re)start the sweep: the stream is replayed from 0
@@ -138,7 +149,12 @@ __global__ __launch_bounds__(256) void interval_sample_kernel(IntervalArgs a)
         const double u1 = iv_u01(knz, 2 * (uint64_t)h), u2 = iv_u01(knz, 2 * (uint64_t)h + 1);
         double sn, cs;
         dm_sincos(6.283185307179586 * u2, sn, cs);
-        const double z = __builtin_sqrt(-2.0 * dm_log(u1)) * cs;
+        double z = __builtin_sqrt(-2.0 * dm_log(u1)) * cs;
+        if (AR) {
+            // (a select, not 0 * e + 1 * z: a series with phi == 0 keeps the independent draw's bits)
+            if (h > 0 && ar_phi != 0.0) z = ar_phi * ar_e + ar_c * z;
+            ar_e = z;
+        }
         const double val = trend * opm[h] + xa[h] + (z * sigma) * ys;
         out[(size_t)h * a.NS] = val;
         if (a.cum_samples) {

@@ -671,18 +671,20 @@ def predict(spec, theta, y_scale, grid, ds_future_ns, floor=None, cap=None, extr
 
 
 def predict_intervals(spec, theta, y_scale, grid, ds_future_ns, floor=None, cap=None, extra_future=None,
-                      series_key=None, uncertainty_samples=1000, interval_width=0.8, seed=0, ctx=None):
+                      series_key=None, uncertainty_samples=1000, interval_width=0.8, seed=0, ctx=None, noise_ar=None):
     """(yhat, yhat_lower, yhat_upper), each [N][H]: fbprophet's predict_uncertainty -- which the
     reference computes inside model.predict (prophet_scorer.py:70) and drops (:86) -- with a seeded
     counter-based generator (include/tsf.h tsf_predict_intervals).  series_key [N] int64: what the
     random streams are keyed by (e.g. a hash of (series_id, dim_id)), so that a series gets the same
-    interval whatever batch it is in; default: its index in this call."""
+    interval whatever batch it is in; default: its index in this call.  noise_ar: see residual_autocorrelation."""
     ctx = ctx or get_context()
     L = _lib.load()
     theta, N, y_scale, grid, ds_future_ns, shared, H, floor, cap, ex, key = _forecast_inputs(
         spec, theta, y_scale, grid, ds_future_ns, floor, cap, extra_future, series_key)
+    phi = _noise_ar_phi(noise_ar, N, ds_future_ns)
     cs = spec.to_c()
     yhat, lo, hi = np.zeros((N, H)), np.zeros((N, H)), np.zeros((N, H))
+    _set_noise_ar(ctx, phi)
     rc = L.tsf_predict_intervals(ctx.handle, ctypes.byref(cs), N, H, theta.ctypes.data, y_scale.ctypes.data,
                                  grid.ctypes.data, len(grid), ds_future_ns.ctypes.data, int(shared),
                                  _lib._ptr(floor), _lib._ptr(cap), _lib._ptr(ex), _lib._ptr(key),
@@ -897,12 +899,13 @@ class Quantiles(object):
 
 
 def _predict_quantiles_call(spec, theta, y_scale, grid, ds_future_ns, floor, cap, extra_future, series_key,
-                            uncertainty_samples, seed, levels, want, ctx):
+                            uncertainty_samples, seed, levels, want, ctx, noise_ar=None):
     """One tsf_predict_quantiles call -> dict of the outputs named in `want` (and yhat)."""
     ctx = ctx or get_context()
     L = _lib.load()
     theta, N, y_scale, grid, ds_future_ns, shared, H, floor, cap, ex, key = _forecast_inputs(
         spec, theta, y_scale, grid, ds_future_ns, floor, cap, extra_future, series_key)
+    phi = _noise_ar_phi(noise_ar, N, ds_future_ns)
     cs = spec.to_c()
     levels = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
     Q, S = len(levels), int(uncertainty_samples)
@@ -916,6 +919,7 @@ def _predict_quantiles_call(spec, theta, y_scale, grid, ds_future_ns, floor, cap
                 raise ValueError('uncertainty_samples must be in [2, 4096]')
             res[k] = np.zeros((N, H, S))
     out = _lib.TsfQuantileOut(**{k: v.ctypes.data for k, v in res.items()})
+    _set_noise_ar(ctx, phi)
     rc = L.tsf_predict_quantiles(ctx.handle, ctypes.byref(cs), N, H, theta.ctypes.data, y_scale.ctypes.data,
                                  grid.ctypes.data, len(grid), ds_future_ns.ctypes.data, int(shared),
                                  _lib._ptr(floor), _lib._ptr(cap), _lib._ptr(ex), _lib._ptr(key), S, int(seed),
@@ -925,26 +929,29 @@ def _predict_quantiles_call(spec, theta, y_scale, grid, ds_future_ns, floor, cap
 
 
 def predict_quantiles(spec, theta, y_scale, grid, ds_future_ns, quantiles, floor=None, cap=None, extra_future=None,
-                      series_key=None, uncertainty_samples=1000, seed=0, cumulative=False, trend=False, ctx=None):
+                      series_key=None, uncertainty_samples=1000, seed=0, cumulative=False, trend=False, ctx=None,
+                      noise_ar=None):
     """Quantiles of the simulated futures of every series -> Quantiles (include/tsf.h tsf_predict_quantiles): q [N][Q][H]
     per future row at the levels `quantiles` (in [0, 1]; 0.5 the median); with cumulative, cum_q: the same levels of each
     sample's running sum over the future rows (row h: the total of rows 0..h, e.g. demand over a lead time); with trend,
     trend_q: of the sampled trend.  The draws are predict_intervals' (same series_key, samples, seed): levels
-    (1 - w) / 2, (1 + w) / 2 give its yhat_lower / yhat_upper at width w bit for bit; yhat is predict's."""
+    (1 - w) / 2, (1 + w) / 2 give its yhat_lower / yhat_upper at width w bit for bit; yhat is predict's.  noise_ar: phi
+    [N] or a NoiseAR (residual_autocorrelation) -- the observation noise of each sample's rows is then an AR(1) chain
+    (include/tsf.h "serially correlated observation noise"): q keeps its law, cum_q widens as a real total's spread does."""
     want = ['q'] + (['cum_q'] if cumulative else []) + (['trend_q'] if trend else [])
     levels = np.array(quantiles, dtype=np.float64).reshape(-1)
     r = _predict_quantiles_call(spec, theta, y_scale, grid, ds_future_ns, floor, cap, extra_future, series_key,
-                                uncertainty_samples, seed, levels, want, ctx)
+                                uncertainty_samples, seed, levels, want, ctx, noise_ar=noise_ar)
     return Quantiles(r['yhat'], levels, r['q'], r.get('cum_q'), r.get('trend_q'))
 
 
 def predictive_samples(spec, theta, y_scale, grid, ds_future_ns, floor=None, cap=None, extra_future=None,
-                       series_key=None, uncertainty_samples=1000, seed=0, ctx=None):
+                       series_key=None, uncertainty_samples=1000, seed=0, ctx=None, noise_ar=None):
     """fbprophet 0.5's Prophet.predictive_samples for a panel: {'yhat': [N][H][S], 'trend': [N][H][S]}, the raw draws
     behind predict_intervals / predict_quantiles (sample s at index s, whatever S is; the trend before the observation
     noise).  For one series [n] is fbprophet's (H, S) layout.  N * H * S * 16 bytes of host memory."""
     r = _predict_quantiles_call(spec, theta, y_scale, grid, ds_future_ns, floor, cap, extra_future, series_key,
-                                uncertainty_samples, seed, [], ['samples', 'trend_samples'], ctx)
+                                uncertainty_samples, seed, [], ['samples', 'trend_samples'], ctx, noise_ar=noise_ar)
     return {'yhat': r['samples'], 'trend': r['trend_samples']}
 
 
@@ -1038,7 +1045,7 @@ def _checked_forecast_inputs(spec, theta, y_scale, grid, ds_ns, floor, cap, extr
 
 
 def _score_actuals_call(spec, theta, y_scale, grid, ds_ns, y_obs, floor, cap, extra_future, series_key,
-                        uncertainty_samples, seed, levels, want, ctx):
+                        uncertainty_samples, seed, levels, want, ctx, noise_ar=None):
     """One tsf_score_actuals call -> dict of the outputs named in `want` (and yhat).  Every argument-shape error is
     raised before the library is loaded."""
     theta, N, y_scale, grid, ds_ns, shared, H, floor, cap, ex, key = _checked_forecast_inputs(
@@ -1048,6 +1055,7 @@ def _score_actuals_call(spec, theta, y_scale, grid, ds_ns, y_obs, floor, cap, ex
         raise ValueError('y_obs must be [N][H] = %r (got %r)' % ((N, H), y_obs.shape))
     if np.isinf(y_obs).any():
         raise ValueError('y_obs holds an infinite value: an observed value must be finite (NaN = not observed)')
+    phi = _noise_ar_phi(noise_ar, N, ds_ns)
     levels = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
     quantile_columns(levels)            # (ValueError for a bad level, two levels of one name, too many)
     Q, S = len(levels), int(uncertainty_samples)
@@ -1065,6 +1073,7 @@ def _score_actuals_call(spec, theta, y_scale, grid, ds_ns, y_obs, floor, cap, ex
     L = _lib.load()
     cs = spec.to_c()
     out = _lib.TsfScoreOut(**{k: v.ctypes.data for k, v in res.items()})
+    _set_noise_ar(ctx, phi)
     rc = L.tsf_score_actuals(ctx.handle, ctypes.byref(cs), N, H, theta.ctypes.data, y_scale.ctypes.data,
                              grid.ctypes.data, len(grid), ds_ns.ctypes.data, int(shared), _lib._ptr(floor),
                              _lib._ptr(cap), _lib._ptr(ex), _lib._ptr(key), S, int(seed), y_obs.ctypes.data, Q,
@@ -1075,17 +1084,18 @@ def _score_actuals_call(spec, theta, y_scale, grid, ds_ns, y_obs, floor, cap, ex
 
 
 def score_actuals(spec, theta, y_scale, grid, ds_ns, y_obs, quantiles=(), floor=None, cap=None, extra_future=None,
-                  series_key=None, uncertainty_samples=1000, seed=0, ctx=None):
+                  series_key=None, uncertainty_samples=1000, seed=0, ctx=None, noise_ar=None):
     """Observed values scored against the predictive distribution of every series -> Scores (include/tsf.h
     tsf_score_actuals).  ds_ns [H] or [N][H]: the rows that were forecast; y_obs [N][H]: what was observed on them, NaN =
     not observed.  Per row: pit (the probability integral transform: uniform where the distribution is calibrated, in
     steps of 0.5 / uncertainty_samples), crps (the sample CRPS, in the units of y, lower is better) and, with levels
     `quantiles`, q and pinball; per series: n_obs, mean_crps, mean_pinball, coverage (the share of observed rows at or
-    below each quantile).  The draws are predict_quantiles' (same series_key, samples, seed): q is its q bit for bit."""
+    below each quantile).  The draws are predict_quantiles' (same series_key, samples, seed, noise_ar): q is its q bit
+    for bit."""
     levels = np.array(quantiles, dtype=np.float64).reshape(-1)
     want = ['pit', 'crps', 'n_obs', 'mean_crps'] + (list(_SCORE_LEVEL_FIELDS) if len(levels) else [])
     r = _score_actuals_call(spec, theta, y_scale, grid, ds_ns, y_obs, floor, cap, extra_future, series_key,
-                            uncertainty_samples, seed, levels, want, ctx)
+                            uncertainty_samples, seed, levels, want, ctx, noise_ar=noise_ar)
     return Scores(r.pop('y'), r.pop('yhat'), levels, **r)
 
 
@@ -1274,17 +1284,19 @@ def _window_call_args(windows, H, N, y_win, levels, want):
 
 
 def _predict_windows_call(spec, theta, y_scale, grid, ds_ns, windows, y_win, floor, cap, extra_future, series_key,
-                          uncertainty_samples, seed, levels, want, ctx):
+                          uncertainty_samples, seed, levels, want, ctx, noise_ar=None):
     """One tsf_predict_windows call -> dict of the outputs named in `want` (any of 'yhat' and WINDOW_FIELDS).  y_win
     [N][K] or None.  Every argument-shape error is raised before the library is loaded."""
     theta, N, y_scale, grid, ds_ns, shared, H, floor, cap, ex, key = _checked_forecast_inputs(
         spec, theta, y_scale, grid, ds_ns, floor, cap, extra_future, series_key)
     levels, y_win, res = _window_call_args(windows, H, N, y_win, levels, want)
+    phi = _noise_ar_phi(noise_ar, N, ds_ns)
     Q, S = len(levels), int(uncertainty_samples)
     ctx = ctx or get_context()
     L = _lib.load()
     cs = spec.to_c()
     out = _lib.TsfWindowOut(**{k: v.ctypes.data for k, v in res.items()})
+    _set_noise_ar(ctx, phi)
     rc = L.tsf_predict_windows(ctx.handle, ctypes.byref(cs), N, H, theta.ctypes.data, y_scale.ctypes.data,
                                grid.ctypes.data, len(grid), ds_ns.ctypes.data, int(shared), _lib._ptr(floor),
                                _lib._ptr(cap), _lib._ptr(ex), _lib._ptr(key), S, int(seed), len(windows),
@@ -1315,14 +1327,15 @@ def _observed_totals(y_obs, N, H, windows):
 
 
 def predict_windows(spec, theta, y_scale, grid, ds_future_ns, windows, quantiles, y_obs=None, floor=None, cap=None,
-                    extra_future=None, series_key=None, uncertainty_samples=1000, seed=0, ctx=None):
+                    extra_future=None, series_key=None, uncertainty_samples=1000, seed=0, ctx=None, noise_ar=None):
     """Quantiles of the TOTAL over each of `windows` (row_windows, period_windows) of the simulated futures of every
     series -> WindowQuantiles (include/tsf.h tsf_predict_windows): yhat [N][H], total [N][K] (the sum of yhat over the
     window), q [N][Q][K] at the levels `quantiles`.  With y_obs [N][H], the values observed on the forecast rows (NaN =
     not observed; a window with such a row is not scored), the observed totals are scored against the distribution of the
     window total: pit, crps, pinball per window, n_obs, mean_crps, mean_pinball, coverage per series.  The draws are
-    predict_quantiles' (same series_key, samples, seed): one-row windows give its q bit for bit, windows from row 0
-    its cum_q."""
+    predict_quantiles' (same series_key, samples, seed, noise_ar): one-row windows give its q bit for bit, windows from
+    row 0 its cum_q.  noise_ar (residual_autocorrelation): the remedy where a window total's interval is too narrow
+    because the residuals of neighbouring rows move together."""
     levels = np.array(quantiles, dtype=np.float64).reshape(-1)
     theta = np.asarray(theta)
     ds = np.ascontiguousarray(ds_future_ns, dtype=np.int64)
@@ -1330,8 +1343,98 @@ def predict_windows(spec, theta, y_scale, grid, ds_future_ns, windows, quantiles
         raise ValueError('windows must be a Windows (row_windows, period_windows)')
     y_win = _observed_totals(y_obs, theta.shape[0], ds.shape[-1] if ds.ndim else 0, windows)
     r = _predict_windows_call(spec, theta, y_scale, grid, ds, windows, y_win, floor, cap, extra_future, series_key,
-                              uncertainty_samples, seed, levels, _window_want(levels, y_win is not None), ctx)
+                              uncertainty_samples, seed, levels, _window_want(levels, y_win is not None), ctx,
+                              noise_ar=noise_ar)
     return WindowQuantiles(windows, ds, r.pop('yhat'), levels, y=y_win, **r)
+
+
+# ---- serially correlated observation noise: AR(1) per series -----------------------------------------
+# The residuals of neighbouring rows of a real fit move together, and the draws' noise is independent from row to row,
+# so the spread of a total over several rows (cum_q, a window, a roll-up's running sum) is too narrow (include/tsf.h
+# "serially correlated observation noise").  residual_autocorrelation estimates each series' lag-one ROW autocorrelation
+# from the fit's own history; noise_ar= on the drawing calls makes every sample's noise an AR(1) chain along its rows.
+
+class NoiseAR(object):
+    """What residual_autocorrelation returns, per series: phi [N] (clipped to [0, phi_max]: what noise_ar= takes),
+    phi_raw [N] (NaN without pairs), n_pairs [N] int64, scale [N] (the residual root mean square), status [N]
+    (_lib.AR_*)."""
+
+    def __init__(self, phi, phi_raw, n_pairs, scale, status):
+        self.phi, self.phi_raw, self.n_pairs, self.scale, self.status = phi, phi_raw, n_pairs, scale, status
+
+    def frame(self, keys=None):
+        """One row per series: series (the index, or `keys` [N]), phi, phi_raw, n_pairs, scale, status."""
+        import pandas as pd
+        N = len(self.phi)
+        series = np.arange(N, dtype=np.int64) if keys is None else np.asarray(keys)
+        if series.shape[0] != N:
+            raise ValueError('keys must be [N]')
+        cols = {'series': list(series) if series.ndim > 1 else series, 'phi': self.phi, 'phi_raw': self.phi_raw,
+                'n_pairs': self.n_pairs, 'scale': self.scale, 'status': self.status}
+        return pd.DataFrame(cols, columns=list(cols))
+
+
+def _ar_args(phi_max, min_pairs):
+    """tsf_ar_args, refused here as the library refuses them (before it is loaded)."""
+    if not 0.0 <= phi_max < 1.0:
+        raise ValueError('phi_max must be in [0, 1)')
+    if int(min_pairs) != min_pairs or min_pairs < 1:
+        raise ValueError('min_pairs must be an integer >= 1')
+    a = _lib.TsfArArgs()
+    a.phi_max, a.min_pairs, a.reserved_ = float(phi_max), int(min_pairs), 0
+    return a
+
+
+def residual_autocorrelation(y, fitted, offsets=None, phi_max=0.95, min_pairs=8, ctx=None):
+    """The lag-one residual autocorrelation of each series (include/tsf.h tsf_residual_autocorr): y [N][T], or 1-D with
+    offsets [N+1] (float64 / float32 / int32); fitted: y's shape (each fit's forecast of its own history:
+    fitted_history).  Lag one ROW, not one unit of time; uncentred; estimated in sample; phi_raw = (the mean of
+    r_t r_{t-1} over the pairs of neighbouring finite rows) / (the mean of r_t^2), phi its clip to [0, phi_max].  Returns
+    a NoiseAR."""
+    fitted = np.ascontiguousarray(fitted, dtype=np.float64)
+    y, offsets, N, T = _screen_panel(y, offsets, (fitted,), ('fitted',))
+    if offsets is None and T < 1:
+        raise ValueError('aligned panel: y must be [N][T], T >= 1')
+    code = _lib.y_dtype_code(y)
+    a = _ar_args(phi_max, min_pairs)
+    ctx = ctx or get_context()
+    phi, raw, scale = np.zeros(N), np.zeros(N), np.zeros(N)
+    n_pairs, status = np.zeros(N, np.int64), np.zeros(N, np.int32)
+    out = _lib.TsfArOut(phi.ctypes.data, raw.ctypes.data, n_pairs.ctypes.data, scale.ctypes.data, status.ctypes.data)
+    ctx.check(_lib.load().tsf_residual_autocorr(ctx.handle, N, T, _lib._ptr(offsets),
+                                                y.ctypes.data, code, fitted.ctypes.data, ctypes.byref(a), ctypes.byref(out)))
+    return NoiseAR(phi, raw, n_pairs, scale, status)
+
+
+def fit_residual_autocorrelation(spec, res, ds_ns, y, offsets=None, floor=None, cap=None, extra=None, phi_max=0.95,
+                                 min_pairs=8, ctx=None):
+    """residual_autocorrelation of a panel's fits `res` (the FitResult of this panel): fitted is predict on the
+    history's own dates (fitted_history), aligned ds_ns [T] or ragged with offsets."""
+    fitted = fitted_history(spec, res, ds_ns, offsets, floor, cap, extra, ctx=ctx)
+    return residual_autocorrelation(y, fitted, offsets, phi_max=phi_max, min_pairs=min_pairs, ctx=ctx)
+
+
+def _noise_ar_phi(noise_ar, N, ds_future_ns):
+    """phi [N] of a noise_ar= keyword (an array or a NoiseAR), or None; every error is a ValueError raised here.  The
+    chain runs in row order, so with it the future rows of every series must be strictly increasing."""
+    if noise_ar is None:
+        return None
+    phi = noise_ar.phi if isinstance(noise_ar, NoiseAR) else noise_ar
+    phi = np.ascontiguousarray(phi, dtype=np.float64)
+    if phi.shape != (N,):
+        raise ValueError('noise_ar must be [N] (or a NoiseAR of N series)')
+    if not (np.isfinite(phi).all() and (np.abs(phi) < 1.0).all()):
+        raise ValueError('noise_ar values must be finite with |phi| < 1')
+    ds = np.asarray(ds_future_ns, dtype=np.int64)
+    if ds.ndim and ds.shape[-1] > 1 and not (np.diff(ds, axis=-1) > 0).all():
+        raise ValueError('noise_ar needs strictly increasing future rows per series: the chain is row-ordered')
+    return phi
+
+
+def _set_noise_ar(ctx, phi):
+    """tsf_set_noise_ar for the library call that follows at once (the setting is consumed by it); None: nothing."""
+    if phi is not None:
+        ctx.check(_lib.load().tsf_set_noise_ar(ctx.handle, phi.ctypes.data, len(phi)))
 
 
 # ---- group roll-ups: predictive quantiles of sums over series --------------------------------------
@@ -1539,6 +1642,7 @@ class Rollup(object):
         if noise_corr is None and group_key is not None:
             raise ValueError('group_key without noise_corr')
         corr = None if noise_corr is None else _noise_corr_args(noise_corr, group_key, self.G)
+        self._has_corr = False
         self._ctx = ctx or get_context()
         h = ctypes.c_void_p()
         self._ctx.check(_lib.load().tsf_rollup_create(self._ctx.handle, self.G, self.H, ds.ctypes.data, self.S, self.seed,
@@ -1552,6 +1656,7 @@ class Rollup(object):
         h = self._handle()
         rho, group_key = _noise_corr_args(rho, group_key, self.G)
         self._ctx.check(_lib.load().tsf_rollup_set_noise_corr(h, rho.ctypes.data, _lib._ptr(group_key)))
+        self._has_corr = True
 
     def _handle(self):
         if not self._h:
@@ -1575,12 +1680,16 @@ class Rollup(object):
         except Exception:
             pass
 
-    def add(self, spec, theta, y_scale, grid, group, series_key, floor=None, cap=None, extra_future=None):
+    def add(self, spec, theta, y_scale, grid, group, series_key, floor=None, cap=None, extra_future=None, noise_ar=None):
         """Adds N series of one spec: group [N] (dense indices in [0, n_groups): rollup_groups), series_key [N]
         (required: the streams of two add calls must differ; the scorer's is (series_id << 32) ^ dim_id).  extra_future:
-        [n_extra][H] shared by the series, or [N][n_extra][H]."""
+        [n_extra][H] shared by the series, or [N][n_extra][H].  noise_ar: phi [N] or a NoiseAR -- these members' draws
+        chain their observation noise along the rows (residual_autocorrelation); not on a roll-up with noise_corr."""
         h = self._handle()
         args = _rollup_add_args(spec, theta, y_scale, grid, group, series_key, floor, cap, extra_future, self.G, self.H)
+        if noise_ar is not None and self._has_corr:
+            raise ValueError('noise_ar on a roll-up with noise_corr: the correlated add regenerates the independent noise')
+        _set_noise_ar(self._ctx, _noise_ar_phi(noise_ar, args[0], self.ds_future_ns))
         self._ctx.check(_lib.load().tsf_rollup_add(h, *_rollup_c_args(spec, args)))
 
     def _group_outs(self, Q, want):
@@ -1816,9 +1925,12 @@ def predict_reconciled(spec, theta, y_scale, grid, ds_future_ns, labels, quantil
 
 def predict_rollup(spec, theta, y_scale, grid, ds_future_ns, labels, quantiles, series_key, floor=None, cap=None,
                    extra_future=None, uncertainty_samples=1000, seed=0, cumulative=False, ctx=None, noise_corr=None,
-                   group_key=None):
+                   group_key=None, noise_ar=None):
     """The one-spec convenience: rollup_groups(labels), one Rollup.add, quantiles, close ->
-    (unique_labels, RollupQuantiles).  noise_corr, group_key: as in Rollup, per unique label in sorted order."""
+    (unique_labels, RollupQuantiles).  noise_corr, group_key: as in Rollup, per unique label in sorted order; noise_ar:
+    as in Rollup.add (not together with noise_corr)."""
+    if noise_ar is not None and noise_corr is not None:
+        raise ValueError('noise_ar together with noise_corr: the correlated add regenerates the independent noise')
     quantile_columns(quantiles)
     if len(np.asarray(quantiles).reshape(-1)) == 0:
         raise ValueError('at least one quantile level')
@@ -1831,7 +1943,8 @@ def predict_rollup(spec, theta, y_scale, grid, ds_future_ns, labels, quantiles, 
     _rollup_add_args(spec, theta, y_scale, grid, group, series_key, floor, cap, extra_future, len(uniq), ds.shape[0])
     with Rollup(ds_future_ns, len(uniq), uncertainty_samples=uncertainty_samples, seed=seed, ctx=ctx, noise_corr=noise_corr,
                 group_key=group_key) as r:
-        r.add(spec, theta, y_scale, grid, group, series_key, floor=floor, cap=cap, extra_future=extra_future)
+        r.add(spec, theta, y_scale, grid, group, series_key, floor=floor, cap=cap, extra_future=extra_future,
+              noise_ar=noise_ar)
         return uniq, r.quantiles(quantiles, cumulative=cumulative)
 
 
