@@ -1262,7 +1262,11 @@ int tsf_set_cost_hints(tsf_ctx *ctx, const int32_t *cost, int64_t n);
  *                   offsets [n_series+1], ds_out / y_out [n_rows], and per series
  *                   span = last ds - first ds, min_dt = smallest positive spacing (-1 if none),
  *                   y_max -- the inputs of fbprophet's set_auto_seasonalities and of
- *                   cap = max(y) * cap_multiplier (prophet_modeler.py:59-60).
+ *                   cap = max(y) * cap_multiplier (prophet_modeler.py:59-60).  span and every spacing are
+ *                   differences of ascending int64 values, taken exactly and SATURATED at INT64_MAX (a series
+ *                   that holds NaT = INT64_MIN beside a real date spans more than int64 holds; any series
+ *                   without NaT and under 292 years long is unaffected).  y_max is the first of the largest
+ *                   values.  ds_out may be the ds array given to tsf_pack_rows (in place).
  *   tsf_pack_flags  what tsf_pack_fetch's pass over the packed rows saw (valid after it): *aligned = 1 when every
  *                   series is observed on the first series' timestamp vector (one shared calendar: the panel can go
  *                   to tsf_fit_aligned as [n_series][T] without another look at ds); *has_inf = 1 when a y is
@@ -1315,6 +1319,26 @@ int tsf_model_blobs(int64_t N, const void *prefix, int32_t prefix_len, int32_t n
  *   quantity    integer (the reference's schema) or decimal; an empty field is a null and
  *               comes out as NaN (the packer drops it as fbprophet drops y.isnull() rows)
  *   rows come out in file order, files in the order given.
+ *   The fine print (what tests/csv_ref.py restates):
+ *   lines       end at '\n'; an unterminated last line counts.  Trailing '\r' and ' ' are cut off a line first; a
+ *               line then empty is BLANK: skipped, not malformed, but it counts in line numbers.
+ *   fields      split at ',' (quotes do not protect a comma); the layout's last column takes the rest of the line, so
+ *               a line with MORE fields than the layout fails in that column unless it is 'x'.  Every converted
+ *               field is first trimmed: blanks and tabs at both ends, '\r' at the end, then ONE pair of double
+ *               quotes around what is left (nothing inside the quotes is trimmed again, except for quantity).
+ *   integers    (series_id, dim_id) an optional '+' or '-' and 1 to 18 digits: a lone sign, an empty field and 19
+ *               digits or more do not convert.
+ *   start_time  exactly the pattern above: 4-digit year, 2-digit month / day / hour / minute / second, the fraction
+ *               only after seconds, at least one digit; digits after the ninth are dropped (truncation).  The date
+ *               must exist (proleptic Gregorian; Feb 29 in leap years only), hour <= 23 (no hour 24), minute and
+ *               second <= 59.  A timestamp that int64 nanoseconds cannot hold -- outside
+ *               1677-09-21T00:12:43.145224193 .. 2262-04-11T23:47:16.854775807; INT64_MIN is pandas' NaT and is
+ *               never produced -- DOES NOT CONVERT (round 13: it used to wrap into a valid-looking value; pandas
+ *               raises OutOfBoundsDatetime there; 0001-01-01 and 9999-12-31 are common sentinels).
+ *   quantity    trimmed; empty (also `""`) = null = NaN; else an integer as above (trimmed once more) -> that value
+ *               as a double; else whatever C's strtod takes IN FULL in the C locale (leading white space, decimal or
+ *               hexadecimal floating literal, "nan") -- a NUL byte or anything else left over fails the field, and
+ *               so does an infinite result ("inf", 1e999); underflow gives 0.
  *   A trailing '?' in layout ("dtq?") = Spark's default CSV mode PERMISSIVE: a line that does not
  *   match the schema (a field that does not convert, too few fields) is not an error.  Spark 2.4 turns
  *   it into a row of nulls (every column, dim_id included); a null y is dropped by the fit, and a null

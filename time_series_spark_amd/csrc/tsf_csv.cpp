@@ -258,8 +258,16 @@ bool parse_timestamp(const char *a, const char *b, int64_t *out) {
     static const int mdays[12] = {31, 29, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31};
     if (D > mdays[M - 1]) return false;
     if (M == 2 && D == 29 && !((Y % 4 == 0 && Y % 100 != 0) || Y % 400 == 0)) return false;
-    int64_t days = days_from_civil(Y, (unsigned)M, (unsigned)D);
-    *out = ((days * 24 + h) * 60 + mi) * 60 * 1000000000ll + s * 1000000000ll + frac;
+    // int64 ns hold 1677-09-21T00:12:43.145224193 (INT64_MIN + 1; INT64_MIN is pandas' NaT and is never produced) ..
+    // 2262-04-11T23:47:16.854775807; a date outside does not convert (0001-01-01, 9999-12-31: it used to wrap into a
+    // good-looking ds).  Days against the two boundary days, then the time of day: nothing here can overflow.
+    constexpr int64_t DAY = 86400000000000ll, DAY_LO = -106752, DAY_HI = 106751;
+    constexpr int64_t TOD_LO = 763145224193ll, TOD_HI = 85636854775807ll;
+    const int64_t days = days_from_civil(Y, (unsigned)M, (unsigned)D);
+    const int64_t tod = ((h * 60 + mi) * 60 + s) * 1000000000ll + frac;
+    if (days < DAY_LO || days > DAY_HI) return false;
+    if ((days == DAY_LO && tod < TOD_LO) || (days == DAY_HI && tod > TOD_HI)) return false;
+    *out = days < 0 ? (days + 1) * DAY + (tod - DAY) : days * DAY + tod;
     return true;
 }
 
@@ -297,7 +305,8 @@ bool parse_quantity(const char *a, const char *b, double *out) {
     std::string tmp(a, b);
     char *end = nullptr;
     double v = std::strtod(tmp.c_str(), &end);
-    if (end == tmp.c_str() || *end != '\0' || std::isinf(v)) return false;
+    // (the whole field, not the part before a NUL byte in it: "1.5\0junk" used to pass as 1.5)
+    if (end == tmp.c_str() || end != tmp.c_str() + tmp.size() || std::isinf(v)) return false;
     *out = v;
     return true;
 }

@@ -97,6 +97,13 @@ struct Pair {
     double y;
 };
 
+// b - a for a <= b (rows of a packed series ascend), taken in unsigned 64 bits and saturated at INT64_MAX: a series
+// that holds NaT (INT64_MIN) beside a real date spans more than int64 holds, and the signed difference overflowed
+inline int64_t sat_diff(int64_t b, int64_t a) {
+    const uint64_t d = (uint64_t)b - (uint64_t)a;
+    return d > (uint64_t)std::numeric_limits<int64_t>::max() ? std::numeric_limits<int64_t>::max() : (int64_t)d;
+}
+
 }  // namespace
 
 struct tsf_pack {
@@ -383,7 +390,7 @@ int tsf_pack_fetch(tsf_pack *p, int64_t *key_series_id, int64_t *key_dim_id, int
                     if (!(v >= -2147483648.0 && v <= 2147483647.0 && v == (double)(int32_t)v)) whole = false;
                     if (r == a) first = d;
                     else {
-                        int64_t dt = d - prev;
+                        int64_t dt = sat_diff(d, prev);
                         if (dt > 0 && (md < 0 || dt < md)) md = dt;
                     }
                     prev = d;
@@ -392,7 +399,7 @@ int tsf_pack_fetch(tsf_pack *p, int64_t *key_series_id, int64_t *key_dim_id, int
                 if (!same) not_aligned.store(1, std::memory_order_relaxed);
                 if (!fin) any_inf.store(1, std::memory_order_relaxed);
                 if (!whole) not_integral.store(1, std::memory_order_relaxed);
-                if (span) span[s] = prev - first;
+                if (span) span[s] = sat_diff(prev, first);
                 if (min_dt) min_dt[s] = md;
                 if (y_max) y_max[s] = ym;
             }
