@@ -590,7 +590,8 @@ void tsf_rollup_free(tsf_rollup *r);        /* before tsf_destroy of its context
  * before any set_totals (not silent zeros); a share outside [0, 1] or NaN; a bad n_q or level; an output set that
  * wants none of q / cum_q / samples.  N == 0 (Gt == 0) is a legal no-op.
  *
- * Out of scope: hierarchies deeper than two levels; non-diagonal covariance (MinT-shrink); per-row weights; the job
+ * Hierarchies deeper than two levels: "tree reconciliation", below.
+ * Out of scope: non-diagonal covariance (MinT-shrink); per-row weights; the job
  * configuration of the modeler and the scorer; _dev variants; more than one GPU. */
 int tsf_reconcile_shares(int64_t N, const int64_t *group, const double *w /* [N], NULL = all 1.0 */, int64_t G,
                          const double *v /* [G]; NaN = the group has no total */, double *share /* [N] lambda */,
@@ -613,6 +614,105 @@ int tsf_rollup_reconcile(tsf_rollup *r, const tsf_spec *spec, int64_t N, const d
                          const double *quantiles, tsf_reconcile_out *out);
 int tsf_rollup_reconciled_totals(tsf_rollup *r, const double *share_total /* [G] */, int32_t n_q, const double *quantiles,
                                  tsf_rollup_out *out);
+
+/* ---- tree reconciliation: hierarchies deeper than two levels ---------------------------------------------
+ * The reconciliation above stops at members and one total per group.  Real hierarchies go on: (series, dim) -> series
+ * -> region -> everything, each level with directly fitted totals of its own.  For a tree with diagonal weights the
+ * weighted least squares projection onto the coherent subspace is one sweep up and one sweep down over the sample
+ * buffers the roll-up already holds -- streaming kernels, nothing dense, nothing through the host.
+ * Reference interface replaced: none (none of this is Prophet's); parity unpinned (what is pinned is the contract
+ * below, against tsf_predict_quantiles' draws and the roll-up's accumulators).  Host pointers only, like tsf_rollup_*.
+ * Timing: tools/bench_tree.py; DESIGN.md 5p.
+ *
+ * Levels.  Level 0: the members.  Level 1: the roll-up's G groups.  Levels 2 .. L (L - 1 = n_upper <=
+ * TSF_TREE_MAX_LEVELS): n_nodes[k] nodes at level k + 2; every node below the top level has one parent in the level
+ * above; the top level may hold several nodes (a forest).  Arrays "over the nodes" are flat, level 1 first:
+ * [G + n_nodes[0] + ... + n_nodes[n_upper - 1]] = [M].  `parent` is flat over the nodes below the top: parent[g] of
+ * group g in [0, n_nodes[0]), then the parents of the level-2 nodes in [0, n_nodes[1]), and so on: [M - n_nodes[n_upper - 1]].
+ *
+ * Problem.  Members have variances w_i; a node n of level >= 1 may have a directly fitted total t_n with variance v_n.
+ * Minimise sum_i (x_i - b_i)^2 / w_i + sum_n (t_n - c_n)^2 / v_n, c_n the sum of the b_i below node n.
+ *
+ * tsf_reconcile_tree_shares (host only: no context, no device).  group [N] in [0, G); w [N] (NULL: all 1.0); v [M]
+ * (NaN: the node has no total).  In plain double operations, every sum from +0.0 in ascending index:
+ *   level 1:  E_g = W_g = sum of w_i over the group;  share[i] = w_i / W_g
+ *   any level, v_n not NaN and E_n > 0:  mu_n = E_n / (v_n + E_n),  e_n = (E_n * v_n) / (v_n + E_n)
+ *   otherwise:                           mu_n = +0.0,               e_n = E_n
+ *   the level above:  E_p = sum of e_c over the children c of p;  kappa_c = e_c / E_p, +0.0 where E_p == 0
+ *   the top level:    kappa = +0.0 (it has no parent)
+ * e_n is the variance left in node n after its own total and everything below it are blended in; kappa_c is child c's
+ * share of what its parent moves by.  A node with no member below it has E = 0, so mu = e = kappa = +0.0, and a total
+ * given for it is ignored (as tsf_reconcile_shares treats a group without members).  Returns -1 for a group or parent
+ * out of range, a weight or v that is not finite and positive (NaN v excepted), n_upper outside
+ * [0, TSF_TREE_MAX_LEVELS], n_nodes < 1, G < 1.  Weight policies are the caller's, on top of this.
+ *
+ * tsf_rollup_set_tree declares levels 2 .. L above the handle's groups (n_upper >= 1) and allocates what the solve
+ * keeps: per group cell one double (delta), per node cell of an upper level two (the bottom-up sum A and c).  A roll-up
+ * that never calls it costs what it did.  Refused: a second call; a handle with a noise correlation; a parent out of
+ * range; n_nodes[k] * H or G * H >= 2^31.
+ *
+ * tsf_rollup_set_node_totals forecasts the directly fitted totals of nodes of one level in [2, L] exactly as
+ * tsf_rollup_set_totals does for level 1 (which stays the entry for level 1): tsf_rollup_add's arguments, checks and
+ * draws ((seed, series_key[n], sample)), series n into node[n] of that level; t = +0.0 + draw, yt = +0.0 + yhat.  The
+ * level's buffer is allocated by the first call for it.  At most one total per node over all calls; a node that
+ * appears twice in one call is refused before any launch.  Keys distinct from every other key of the hierarchy are the
+ * caller's business.  A HIP failure in the middle poisons the handle, as for add.
+ *
+ * tsf_rollup_solve_tree runs the two sweeps with mu [M] and kappa [M] (each finite and in [0, 1]).  Per cell
+ * (node, row, sample), in plain double operations (no fused multiply-add), one writer per cell, no atomics:
+ *   up, level 1:   A = acc
+ *   up, above:     A_p = sum of m_c over the children c of p, from +0.0 in ascending child index
+ *   every level:   m_n = A_n + mu_n * (t_n - A_n) where node n was given a total (set_totals / set_node_totals),
+ *                  m_n = A_n where it was not (whatever mu_n says)
+ *   down, top:     c_n = m_n
+ *   down, below:   c_n = m_n + kappa_n * (c_p - A_p), p the parent of n
+ *   kept:          delta_g = c_g - acc_g per group cell; c_n per cell of the levels above
+ * The point forecast goes through the same recursion on ysum / ytop / the node totals' yhat.  Neither accumulator is
+ * modified.  A later tsf_rollup_add, tsf_rollup_set_totals or tsf_rollup_set_node_totals invalidates the solve: the two
+ * reads below are refused until it has run again.  It may be repeated with other shares.
+ *
+ * tsf_rollup_reconcile_tree is the members' second pass: tsf_rollup_reconcile's arguments, rules and outputs with
+ *   sample' = sample + share[n] * delta[g][h][s],  yhat' = yhat + share[n] * ydelta[g][h]    (a multiply, an add)
+ * and share [N] from tsf_reconcile_tree_shares.  The draws are the ones that were added (same keys, the handle's seed);
+ * the result depends neither on the scratch chunks nor on what else is in the call nor on the outputs requested.
+ * Without any total anywhere every delta is +0.0 and the call returns tsf_predict_quantiles' outputs bit for bit.
+ * With one upper level and no upper totals the solution is the two-level one above in exact arithmetic, not in bits
+ * (that one multiplies w_i / (v + W) by (t - acc) in one step).
+ *
+ * tsf_rollup_tree_totals reads the reconciled nodes node0 .. node0 + n_nodes of one level in [1, L]: at level 1 the
+ * cells acc + delta (one add), above it c itself; yhat the same from the point forecasts; the outputs are
+ * tsf_rollup_quantiles' outputs over those cells, sized by n_nodes (count: the members added below each node).  Nodes
+ * are processed in ranges through the context's scratch; nothing the handle holds is modified.
+ *
+ * Refusals (< 0 with a message, before any launch; the handle and the context stay usable): any of these before
+ * set_tree (shares excepted); a level outside its range; a node out of range or given a total twice; reconcile_tree or
+ * tree_totals before solve_tree or after a later add / set_totals / set_node_totals; a share, mu or kappa outside
+ * [0, 1] or NaN; tsf_rollup_add's refusals for set_node_totals and reconcile_tree; a bad n_q or level of a quantile; an
+ * output set that wants none of q / cum_q / samples; every entry on a handle with a noise correlation.  N == 0,
+ * Gt == 0 and n_nodes == 0 are legal no-ops.
+ *
+ * Limits: diagonal weights (no MinT-shrink); one weight per node, not per row; roll-ups with a noise correlation are
+ * not reconciled; one calendar, as with any roll-up; windows of the reconciled draws, the job configuration of the
+ * modeler and the scorer, _dev variants and more than one GPU are out of scope. */
+#define TSF_TREE_MAX_LEVELS 4
+int tsf_reconcile_tree_shares(int64_t N, const int64_t *group, const double *w /* [N], NULL = all 1.0 */, int64_t G,
+                              int32_t n_upper, const int64_t *n_nodes /* [n_upper] */, const int64_t *parent,
+                              const double *v /* [M]; NaN = the node has no total */, double *share /* [N] */,
+                              double *mu /* [M] */, double *e /* [M] */, double *kappa /* [M] */);
+int tsf_rollup_set_tree(tsf_rollup *r, int32_t n_upper, const int64_t *n_nodes /* [n_upper] */, const int64_t *parent);
+int tsf_rollup_set_node_totals(tsf_rollup *r, int32_t level, const tsf_spec *spec, int64_t Gt, const double *theta,
+                               const double *y_scale, const tsf_grid_info *grid, int32_t n_grids, const double *floor,
+                               const double *cap, const double *extra_future, int32_t shared_extra,
+                               const int64_t *series_key /* [Gt], required */,
+                               const int64_t *node /* [Gt], the node of `level` each total series belongs to */);
+int tsf_rollup_solve_tree(tsf_rollup *r, const double *mu /* [M] */, const double *kappa /* [M] */);
+int tsf_rollup_reconcile_tree(tsf_rollup *r, const tsf_spec *spec, int64_t N, const double *theta, const double *y_scale,
+                              const tsf_grid_info *grid, int32_t n_grids, const double *floor, const double *cap,
+                              const double *extra_future, int32_t shared_extra, const int64_t *series_key /* [N], required */,
+                              const int64_t *group /* [N] */, const double *share /* [N] */, int32_t n_q,
+                              const double *quantiles, tsf_reconcile_out *out);
+int tsf_rollup_tree_totals(tsf_rollup *r, int32_t level, int64_t node0, int64_t n_nodes, int32_t n_q,
+                           const double *quantiles, tsf_rollup_out *out);
 
 /* ---- correlated group roll-ups: a shared noise factor per group ----------------------------------------
  * The members of a total share weather, promotions and outages, so their forecast errors move together, and the P90

@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('TSF_LIB_PATH') or os.path.join(_HERE, 'libtsf_amd.so')   # override: A/B runs of two builds
 
 MAX_SEAS = 8
+TREE_MAX_LEVELS = 4         # TSF_TREE_MAX_LEVELS: levels above the groups of a roll-up's tree
 MAX_EXTRA = 64
 MAX_S = 60
 MAX_K = 64
@@ -226,6 +227,8 @@ EXPORTS = ['tsf_create', 'tsf_destroy', 'tsf_last_error', 'tsf_device_count', 't
            'tsf_rollup_create', 'tsf_rollup_add', 'tsf_rollup_quantiles', 'tsf_rollup_free',
            'tsf_window_out_size', 'tsf_predict_windows', 'tsf_predict_windows_dev', 'tsf_rollup_windows',
            'tsf_reconcile_shares', 'tsf_reconcile_out_size', 'tsf_rollup_set_totals', 'tsf_rollup_reconcile', 'tsf_rollup_reconciled_totals',
+           'tsf_reconcile_tree_shares', 'tsf_rollup_set_tree', 'tsf_rollup_set_node_totals', 'tsf_rollup_solve_tree',
+           'tsf_rollup_reconcile_tree', 'tsf_rollup_tree_totals',
            'tsf_corr_args_size', 'tsf_corr_out_size', 'tsf_residual_corr', 'tsf_residual_corr_dev', 'tsf_rollup_set_noise_corr',
            'tsf_ar_args_size', 'tsf_ar_out_size', 'tsf_residual_autocorr', 'tsf_residual_autocorr_dev', 'tsf_set_noise_ar',
            'tsf_cond_columns', 'tsf_cond_columns_dev',
@@ -338,6 +341,12 @@ def load():
     L.tsf_rollup_set_totals.argtypes = L.tsf_rollup_add.argtypes
     L.tsf_rollup_reconcile.argtypes = L.tsf_rollup_add.argtypes + [vp, i32, vp, ctypes.POINTER(TsfReconcileOut)]
     L.tsf_rollup_reconciled_totals.argtypes = [vp, vp, i32, vp, ctypes.POINTER(TsfRollupOut)]
+    L.tsf_reconcile_tree_shares.argtypes = [i64, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.tsf_rollup_set_tree.argtypes = [vp, i32, vp, vp]
+    L.tsf_rollup_set_node_totals.argtypes = [vp, i32] + L.tsf_rollup_add.argtypes[1:]
+    L.tsf_rollup_solve_tree.argtypes = [vp, vp, vp]
+    L.tsf_rollup_reconcile_tree.argtypes = L.tsf_rollup_reconcile.argtypes
+    L.tsf_rollup_tree_totals.argtypes = [vp, i32, i64, i64, i32, vp, ctypes.POINTER(TsfRollupOut)]
     L.tsf_residual_corr.argtypes = [vp, i64, i32, vp, i32, vp, vp, i64, ctypes.POINTER(TsfCorrArgs), ctypes.POINTER(TsfCorrOut)]
     L.tsf_residual_corr_dev.argtypes = L.tsf_residual_corr.argtypes + [vp]
     L.tsf_rollup_set_noise_corr.argtypes = [vp, vp, vp]

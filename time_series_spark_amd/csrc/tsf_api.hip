@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -28,6 +29,7 @@
 #include "tsf_window_kernels.h"
 #include "tsf_rollup_kernels.h"
 #include "tsf_reconcile_kernels.h"
+#include "tsf_tree_kernels.h"
 #include "tsf_component_kernels.h"
 #include "tsf_fit_kernels.h"
 #include "tsf_quad_kernels.h"
@@ -2280,6 +2282,27 @@ extern "C" int tsf_score_actuals(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, 
 
 // ---- group roll-ups: predictive quantiles of sums over series ---------------------------------------------
 
+// One level above the groups in a roll-up's tree (include/tsf.h "tree reconciliation"), n nodes.
+struct TreeLevel {
+    int64_t n = 0;
+    OwnedDev<double> A, C;          // [n][H][S] the bottom-up sum of the children's m; m, then c
+    OwnedDev<double> yA, yC;        // [n][H]
+    OwnedDev<double> T, yT;         // the draws and yhat of the nodes' fitted totals: the first tsf_rollup_set_node_totals
+    OwnedDev<int32_t> d_has;        // [n] device copy of has (with T)
+    std::vector<int32_t> has;       // [n] the node has a total (host; empty until then)
+    OwnedDev<int32_t> d_first, d_child, d_parent;   // [n + 1], [n_below]: each node's children, ascending; [n_below] parents
+    std::vector<int64_t> parent;    // [n_below] the parent of each node of the level below (host)
+};
+
+// The levels above a roll-up's groups and what tsf_rollup_solve_tree leaves for the two reads.
+struct RollupTree {
+    std::deque<TreeLevel> up;       // levels 2 .. L
+    int64_t M = 0;                  // nodes of all levels, the groups included: the length of mu and kappa
+    OwnedDev<double> delta, ydelta; // [G][H][S], [G][H]: m of level 1, then c - acc
+    OwnedDev<double> d_mk;          // [2][M] mu, then kappa, of the last solve
+    bool solved = false;            // the sweeps have run and nothing was added since
+};
+
 // The accumulators of one roll-up (include/tsf.h): owned by the handle, not carved from the context's scratch.
 struct tsf_rollup {
     tsf_ctx *ctx = nullptr;
@@ -2303,6 +2326,8 @@ struct tsf_rollup {
     OwnedDev<int64_t> d_group_key;  // [G]
     std::vector<double> corr_a, corr_b;     // the host copies
     std::vector<int64_t> group_key;
+    // tree reconciliation (tsf_rollup_set_tree): allocated by that call and not before
+    std::unique_ptr<RollupTree> tree;
 };
 
 // A HIP failure of a roll-up's own allocations and copies: the message of the entry, -2, and the error read so that it
@@ -2407,9 +2432,10 @@ static void rollup_plan(const int64_t *group, int64_t N, int64_t chunk, RollupPl
 // or launched (the handle is not poisoned, N > 0).
 static int rollup_check_series(tsf_rollup *r, const tsf_spec *spec, int64_t N, const double *theta, const double *y_scale,
                                const tsf_grid_info *grid, int32_t n_grids, const double *cap, const double *extra_future,
-                               const int64_t *series_key, const int64_t *group)
+                               const int64_t *series_key, const int64_t *group, int64_t G = -1 /* the handle's */)
 {
     tsf_ctx *ctx = r->ctx;
+    if (G < 0) G = r->G;
     if (N > 2147483647) return fail(ctx, "N must be < 2^31 per call");
     if (!spec || !theta || !y_scale || !grid) return fail(ctx, "NULL input");
     if (!series_key)
@@ -2417,10 +2443,10 @@ static int rollup_check_series(tsf_rollup *r, const tsf_spec *spec, int64_t N, c
     if (!group) return fail(ctx, "NULL group");
     if (n_grids != 1 && n_grids != N) return fail(ctx, "n_grids must be 1 or N");
     for (int64_t n = 0; n < N; ++n)
-        if (group[n] < 0 || group[n] >= r->G) {
+        if (group[n] < 0 || group[n] >= G) {
             char msg[120];
             snprintf(msg, sizeof(msg), "group[%lld] = %lld: outside [0, G = %lld)", (long long)n, (long long)group[n],
-                     (long long)r->G);
+                     (long long)G);
             return fail(ctx, msg);
         }
     if (int rc = check_grids(ctx, spec, grid, n_grids)) return rc;
@@ -2553,6 +2579,7 @@ extern "C" int tsf_rollup_add(tsf_rollup *r, const tsf_spec *spec, int64_t N, co
         return rc;
     for (int64_t n = 0; n < N; ++n) r->count[(size_t)group[n]] += 1;
     r->added = true;
+    if (r->tree) r->tree->solved = false;
     return 0;
 }
 
@@ -2918,35 +2945,36 @@ static int check_rollup_read(tsf_rollup *r, int32_t n_q, const double *quantiles
 // it, reconcile_total_kernel first writes a range's cells into the context's scratch (its out and g0 are set here): q is
 // sorted from there, and the samples leave the scratch range by range in stream order.  In both, the running sums of a
 // range for cum_q lie in the scratch as well, and a range is what keeps the scratch within its 512 MB.
-static int rollup_read(tsf_rollup *r, int32_t n_q, const double *quantiles, const tsf_rollup_out &out,
-                       ReconcileTotalArgs *total, HostOuts &outs)
+//
+// cells_read is that read over any G cells [G][H][S] the handle holds (`acc`: the accumulators, or a level of a solved
+// tree); `make` (null: the cells are `acc` itself) launches what writes the cells g0 .. g0 + gc into the scratch at dst.
+using CellMaker = std::function<int(double *dst, int64_t g0, int64_t gc)>;
+
+static int cells_read(tsf_rollup *r, const double *acc, int64_t G, int32_t n_q, const double *quantiles,
+                      const tsf_rollup_out &out, const CellMaker *make, HostOuts &outs)
 {
     tsf_ctx *ctx = r->ctx;
     const int32_t H = r->H, S = r->S;
-    const int64_t G = r->G;
     const size_t hs = (size_t)H * S, gh = (size_t)G * H, nqh = 8 * gh * (size_t)n_q;
     const QuantilePass qp(H, S, n_q, quantiles);
     double *d_q = outs.want(out.q, nqh), *d_cq = outs.want(out.cum_q, nqh);
-    if (!total) outs.adopt(out.samples, r->acc.p, 8 * gh * S);
+    if (!make) outs.adopt(out.samples, const_cast<double *>(acc), 8 * gh * S);
     if (int rc = outs.ready(ctx)) return rc;
-    if (d_q && !total) {
+    if (d_q && !make) {
         const int64_t range = std::max<int64_t>(1, ((int64_t)1 << 30) / H);
         for (int64_t g0 = 0; g0 < G; g0 += range)
-            if (int rc = qp.launch(ctx, r->acc + (size_t)g0 * hs, d_q, g0, std::min(range, G - g0), nullptr)) return rc;
+            if (int rc = qp.launch(ctx, acc + (size_t)g0 * hs, d_q, g0, std::min(range, G - g0), nullptr)) return rc;
     }
-    const size_t n_buf = (total ? 1 : 0) + (d_cq ? 1 : 0);      // per range in the scratch: the cells, their running sums
+    const size_t n_buf = (make ? 1 : 0) + (d_cq ? 1 : 0);       // per range in the scratch: the cells, their running sums
     if (n_buf) {
         const int64_t range = std::max<int64_t>(1, std::min<int64_t>(G, (int64_t)(((size_t)512 << 20) / (8 * hs * n_buf))));
         if (int rc = ensure_iv_ws(ctx, 8 * (size_t)range * hs * n_buf)) return rc;
-        double *d_x = (double *)ctx->iv_ws, *d_c = total ? d_x + (size_t)range * hs : d_x;
+        double *d_x = (double *)ctx->iv_ws, *d_c = make ? d_x + (size_t)range * hs : d_x;
         for (int64_t g0 = 0; g0 < G; g0 += range) {
             const int64_t gc = std::min(range, G - g0);
-            const double *cells = total ? d_x : r->acc + (size_t)g0 * hs;
-            if (total) {
-                total->out = d_x; total->g0 = g0;
-                hipLaunchKernelGGL(reconcile_total_kernel, dim3((unsigned)(gc * H), (unsigned)((S + 255) / 256)), dim3(256), 0,
-                                   nullptr, *total);
-                HIP_TRY(ctx, hipGetLastError());
+            const double *cells = make ? d_x : acc + (size_t)g0 * hs;
+            if (make) {
+                if (int rc = (*make)(d_x, g0, gc)) return rc;
                 if (d_q)
                     if (int rc = qp.launch(ctx, d_x, d_q, g0, gc, nullptr)) return rc;
             }
@@ -2956,14 +2984,30 @@ static int rollup_read(tsf_rollup *r, int32_t n_q, const double *quantiles, cons
                 HIP_TRY(ctx, hipGetLastError());
                 if (int rc = qp.launch(ctx, d_c, d_cq, g0, gc, nullptr)) return rc;
             }
-            if (total && out.samples)
+            if (make && out.samples)
                 HIP_TRY(ctx, hipMemcpyAsync(out.samples + (size_t)g0 * hs, d_x, 8 * (size_t)gc * hs, hipMemcpyDeviceToHost,
                                             nullptr));
         }
     }
     HIP_TRY(ctx, hipDeviceSynchronize());
-    if (out.count) memcpy(out.count, r->count.data(), 8 * (size_t)G);
     return outs.fetch(ctx);
+}
+
+static int rollup_read(tsf_rollup *r, int32_t n_q, const double *quantiles, const tsf_rollup_out &out,
+                       ReconcileTotalArgs *total, HostOuts &outs)
+{
+    tsf_ctx *ctx = r->ctx;
+    const int32_t H = r->H, S = r->S;
+    const CellMaker make = [&](double *dst, int64_t g0, int64_t gc) -> int {
+        total->out = dst; total->g0 = g0;
+        hipLaunchKernelGGL(reconcile_total_kernel, dim3((unsigned)(gc * H), (unsigned)((S + 255) / 256)), dim3(256), 0,
+                           nullptr, *total);
+        HIP_TRY(ctx, hipGetLastError());
+        return 0;
+    };
+    if (int rc = cells_read(r, r->acc, r->G, n_q, quantiles, out, total ? &make : nullptr, outs)) return rc;
+    if (out.count) memcpy(out.count, r->count.data(), 8 * (size_t)r->G);
+    return 0;
 }
 
 extern "C" int tsf_rollup_quantiles(tsf_rollup *r, int32_t n_q, const double *quantiles, tsf_rollup_out *out)
@@ -3299,6 +3343,7 @@ extern "C" int tsf_rollup_set_totals(tsf_rollup *r, const tsf_spec *spec, int64_
     HIP_TRY(ctx, hipMemcpy(r->d_has_top, has.data(), 4 * (size_t)r->G, hipMemcpyHostToDevice));
     r->poisoned = false;
     r->has_top.swap(has);
+    if (r->tree) r->tree->solved = false;
     return 0;
 }
 
@@ -3314,19 +3359,19 @@ static int check_shares(tsf_ctx *ctx, const char *name, const double *share, int
     return 0;
 }
 
-extern "C" int tsf_rollup_reconcile(tsf_rollup *r, const tsf_spec *spec, int64_t N, const double *theta,
-                                    const double *y_scale, const tsf_grid_info *grid, int32_t n_grids,
-                                    const double *floor_, const double *cap, const double *extra_future,
-                                    int32_t shared_extra, const int64_t *series_key, const int64_t *group,
-                                    const double *share, int32_t n_q, const double *quantiles, tsf_reconcile_out *out)
+// The second pass over the members behind tsf_rollup_reconcile and tsf_rollup_reconcile_tree, once the entry has
+// checked its handle: the call's checks, the members drawn again chunk by chunk, `pass` launched on each chunk's sample
+// buffer and point forecast in place (its arguments: samp, yhat, group and share of the chunk, the chunk's series count),
+// then the running sums, the sorts and the copies out.
+using MemberPass = std::function<void(double *samp, double *yhat, const int32_t *group, const double *share, int64_t nc)>;
+
+static int reconcile_members(tsf_rollup *r, const char *entry, const tsf_spec *spec, int64_t N, const double *theta,
+                             const double *y_scale, const tsf_grid_info *grid, int32_t n_grids, const double *floor_,
+                             const double *cap, const double *extra_future, int32_t shared_extra,
+                             const int64_t *series_key, const int64_t *group, const double *share, int32_t n_q,
+                             const double *quantiles, tsf_reconcile_out *out, const MemberPass &pass)
 {
-    NoiseArOnce ar_once(r ? r->ctx : nullptr);
-    if (int rc = rollup_enter(r, true)) return rc;
     tsf_ctx *ctx = r->ctx;
-    if (int rc = refuse_noise_ar(ctx, "tsf_rollup_reconcile")) return rc;
-    if (N < 0) return fail(ctx, "N must be >= 0");
-    if (N == 0) return 0;
-    if (!r->top) return fail(ctx, "tsf_rollup_reconcile before any tsf_rollup_set_totals: the roll-up has no total");
     if (int rc = rollup_check_series(r, spec, N, theta, y_scale, grid, n_grids, cap, extra_future, series_key, group))
         return rc;
     if (!share) return fail(ctx, "NULL share");
@@ -3338,7 +3383,7 @@ extern "C" int tsf_rollup_reconcile(tsf_rollup *r, const tsf_spec *spec, int64_t
     try {
         g32.resize((size_t)N);
     } catch (const std::bad_alloc &) {
-        return fail(ctx, "tsf_rollup_reconcile: out of host memory");
+        return fail(ctx, (std::string(entry) + ": out of host memory").c_str());
     }
     for (int64_t n = 0; n < N; ++n) g32[(size_t)n] = (int32_t)group[n];
     RollupSeries in;
@@ -3352,15 +3397,9 @@ extern "C" int tsf_rollup_reconcile(tsf_rollup *r, const tsf_spec *spec, int64_t
     if (int rc = outs.ready(ctx)) return rc;
     HIP_TRY(ctx, d_share.put(share, 8 * (size_t)N));
     HIP_TRY(ctx, d_group.put(g32.data(), 4 * (size_t)N));
-    ReconcileMemberArgs m;
-    memset(&m, 0, sizeof(m));
-    m.acc = r->acc; m.top = r->top; m.ysum = r->ysum; m.ytop = r->ytop; m.has_top = r->d_has_top; m.H = H; m.NS = S;
     const QuantilePass qp(H, S, n_q, quantiles);
     auto after = [&](int64_t n0, int64_t nc, const DrawBufs &b) -> int {
-        m.samp = b.samp; m.yhat = d_yh + (size_t)n0 * H;
-        m.group = d_group.as<int32_t>() + n0; m.share = d_share.as<double>() + n0;
-        hipLaunchKernelGGL(reconcile_member_kernel, dim3((unsigned)(nc * H), (unsigned)((S + 255) / 256)), dim3(256), 0,
-                           nullptr, m);
+        pass(b.samp, d_yh + (size_t)n0 * H, d_group.as<int32_t>() + n0, d_share.as<double>() + n0, nc);
         HIP_TRY(ctx, hipGetLastError());
         if (out->cum_q) {
             // the running sums of the reconciled draws over the ones interval_sample_kernel left in the second buffer
@@ -3384,6 +3423,32 @@ extern "C" int tsf_rollup_reconcile(tsf_rollup *r, const tsf_spec *spec, int64_t
     return outs.fetch(ctx);
 }
 
+extern "C" int tsf_rollup_reconcile(tsf_rollup *r, const tsf_spec *spec, int64_t N, const double *theta,
+                                    const double *y_scale, const tsf_grid_info *grid, int32_t n_grids,
+                                    const double *floor_, const double *cap, const double *extra_future,
+                                    int32_t shared_extra, const int64_t *series_key, const int64_t *group,
+                                    const double *share, int32_t n_q, const double *quantiles, tsf_reconcile_out *out)
+{
+    NoiseArOnce ar_once(r ? r->ctx : nullptr);
+    if (int rc = rollup_enter(r, true)) return rc;
+    tsf_ctx *ctx = r->ctx;
+    if (int rc = refuse_noise_ar(ctx, "tsf_rollup_reconcile")) return rc;
+    if (N < 0) return fail(ctx, "N must be >= 0");
+    if (N == 0) return 0;
+    if (!r->top) return fail(ctx, "tsf_rollup_reconcile before any tsf_rollup_set_totals: the roll-up has no total");
+    const int32_t H = r->H, S = r->S;
+    ReconcileMemberArgs m;
+    memset(&m, 0, sizeof(m));
+    m.acc = r->acc; m.top = r->top; m.ysum = r->ysum; m.ytop = r->ytop; m.has_top = r->d_has_top; m.H = H; m.NS = S;
+    const MemberPass pass = [&](double *samp, double *yhat, const int32_t *g, const double *sh, int64_t nc) {
+        m.samp = samp; m.yhat = yhat; m.group = g; m.share = sh;
+        hipLaunchKernelGGL(reconcile_member_kernel, dim3((unsigned)(nc * H), (unsigned)((S + 255) / 256)), dim3(256), 0,
+                           nullptr, m);
+    };
+    return reconcile_members(r, "tsf_rollup_reconcile", spec, N, theta, y_scale, grid, n_grids, floor_, cap, extra_future,
+                             shared_extra, series_key, group, share, n_q, quantiles, out, pass);
+}
+
 extern "C" int tsf_rollup_reconciled_totals(tsf_rollup *r, const double *share_total, int32_t n_q,
                                             const double *quantiles, tsf_rollup_out *out)
 {
@@ -3404,6 +3469,354 @@ extern "C" int tsf_rollup_reconciled_totals(tsf_rollup *r, const double *share_t
     t.acc = r->acc; t.top = r->top; t.ysum = r->ysum; t.ytop = r->ytop; t.has_top = r->d_has_top;
     t.share = d_share.as<double>(); t.yout = outs.want(out->yhat, 8 * (size_t)r->G * r->H); t.H = r->H; t.NS = r->S;
     return rollup_read(r, n_q, quantiles, *out, &t, outs);
+}
+
+// ---- tree reconciliation: levels above the groups ------------------------------------------------------------
+
+extern "C" int tsf_reconcile_tree_shares(int64_t N, const int64_t *group, const double *w, int64_t G, int32_t n_upper,
+                                         const int64_t *n_nodes, const int64_t *parent, const double *v, double *share,
+                                         double *mu, double *e, double *kappa)
+{
+    if (N < 0 || G < 1 || n_upper < 0 || n_upper > TSF_TREE_MAX_LEVELS) return -1;
+    if ((N > 0 && (!group || !share)) || !v || !mu || !e || !kappa || (n_upper > 0 && (!n_nodes || !parent))) return -1;
+    int64_t M = G, below = G, n_par = 0;
+    for (int32_t k = 0; k < n_upper; ++k) {
+        if (n_nodes[k] < 1) return -1;
+        for (int64_t c = 0; c < below; ++c)
+            if (parent[n_par + c] < 0 || parent[n_par + c] >= n_nodes[k]) return -1;
+        n_par += below; below = n_nodes[k]; M += below;
+    }
+    for (int64_t n = 0; n < N; ++n) {
+        if (group[n] < 0 || group[n] >= G) return -1;
+        if (w && !(w[n] > 0.0 && std::isfinite(w[n]))) return -1;
+    }
+    for (int64_t i = 0; i < M; ++i)
+        if (!std::isnan(v[i]) && !(v[i] > 0.0 && std::isfinite(v[i]))) return -1;
+    // E of a level in kappa's slots of that level until its own kappa is known
+    double *E = kappa;
+    for (int64_t g = 0; g < G; ++g) E[g] = 0.0;
+    for (int64_t n = 0; n < N; ++n) E[group[n]] = E[group[n]] + (w ? w[n] : 1.0);
+    for (int64_t n = 0; n < N; ++n) share[n] = (w ? w[n] : 1.0) / E[group[n]];
+    int64_t off = 0;
+    below = G; n_par = 0;
+    for (int32_t k = 0; k <= n_upper; ++k) {
+        for (int64_t i = off; i < off + below; ++i) {
+            const double En = E[i];
+            if (!std::isnan(v[i]) && En > 0.0) {
+                mu[i] = En / (v[i] + En);
+                e[i] = (En * v[i]) / (v[i] + En);
+            } else {
+                mu[i] = 0.0;
+                e[i] = En;
+            }
+        }
+        if (k == n_upper) {
+            for (int64_t i = off; i < off + below; ++i) kappa[i] = 0.0;        // the top level has no parent
+            break;
+        }
+        const int64_t up = off + below, n_up = n_nodes[k];
+        for (int64_t p = 0; p < n_up; ++p) E[up + p] = 0.0;
+        for (int64_t c = 0; c < below; ++c) E[up + parent[n_par + c]] = E[up + parent[n_par + c]] + e[off + c];
+        for (int64_t c = 0; c < below; ++c) {
+            const double Ep = E[up + parent[n_par + c]];
+            kappa[off + c] = Ep == 0.0 ? 0.0 : e[off + c] / Ep;
+        }
+        n_par += below; off = up; below = n_up;
+    }
+    return 0;
+}
+
+static const char *const TREE_NOT_SET = "before tsf_rollup_set_tree: the roll-up has no tree";
+
+extern "C" int tsf_rollup_set_tree(tsf_rollup *r, int32_t n_upper, const int64_t *n_nodes, const int64_t *parent)
+{
+    if (int rc = rollup_enter(r, true)) return rc;
+    tsf_ctx *ctx = r->ctx;
+    if (r->tree) return fail(ctx, "tsf_rollup_set_tree: the roll-up has a tree already (one tree per roll-up)");
+    if (n_upper < 1 || n_upper > TSF_TREE_MAX_LEVELS) return fail(ctx, "n_upper must be in [1, TSF_TREE_MAX_LEVELS]");
+    if (!n_nodes || !parent) return fail(ctx, "NULL n_nodes or parent");
+    const int32_t H = r->H, S = r->S;
+    const int64_t cell_max = 2147483647 / H;                    // a launch has nodes * H blocks
+    if (r->G > cell_max) return fail(ctx, "tsf_rollup_set_tree: G * H must be < 2^31");
+    {
+        int64_t below = r->G, n_par = 0;
+        for (int32_t k = 0; k < n_upper; ++k) {
+            if (n_nodes[k] < 1 || n_nodes[k] > cell_max) {
+                char msg[120];
+                snprintf(msg, sizeof(msg), "n_nodes[%d] = %lld: must be >= 1 and n_nodes * H < 2^31", k, (long long)n_nodes[k]);
+                return fail(ctx, msg);
+            }
+            for (int64_t c = 0; c < below; ++c)
+                if (parent[n_par + c] < 0 || parent[n_par + c] >= n_nodes[k]) {
+                    char msg[160];
+                    snprintf(msg, sizeof(msg), "parent[%lld] = %lld (node %lld of level %d): outside [0, %lld)",
+                             (long long)(n_par + c), (long long)parent[n_par + c], (long long)c, k + 1, (long long)n_nodes[k]);
+                    return fail(ctx, msg);
+                }
+            n_par += below; below = n_nodes[k];
+        }
+    }
+    std::unique_ptr<RollupTree> t;
+    std::vector<std::vector<int32_t>> first, child, par32;
+    try {
+        t.reset(new RollupTree());
+        int64_t below = r->G, n_par = 0;
+        t->M = r->G;
+        for (int32_t k = 0; k < n_upper; ++k) {
+            t->up.emplace_back();
+            TreeLevel &lv = t->up.back();
+            lv.n = n_nodes[k];
+            lv.parent.assign(parent + n_par, parent + n_par + below);
+            // the children of each node in ascending child index: a counting sort
+            first.emplace_back((size_t)lv.n + 1, 0);
+            child.emplace_back((size_t)below);
+            par32.emplace_back((size_t)below);
+            std::vector<int32_t> &f = first.back();
+            for (int64_t c = 0; c < below; ++c) f[(size_t)lv.parent[(size_t)c] + 1] += 1;
+            for (int64_t p = 0; p < lv.n; ++p) f[(size_t)p + 1] += f[(size_t)p];
+            std::vector<int32_t> at(f.begin(), f.end() - 1);
+            for (int64_t c = 0; c < below; ++c) {
+                child.back()[(size_t)at[(size_t)lv.parent[(size_t)c]]++] = (int32_t)c;
+                par32.back()[(size_t)c] = (int32_t)lv.parent[(size_t)c];
+            }
+            n_par += below; below = lv.n; t->M += lv.n;
+        }
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, "tsf_rollup_set_tree: out of host memory");
+    }
+    const hipError_t err = [&]() -> hipError_t {
+        const size_t hs = (size_t)H * S;
+        HIP_OK(t->delta.alloc((size_t)r->G * hs));
+        HIP_OK(t->ydelta.alloc((size_t)r->G * H));
+        HIP_OK(t->d_mk.alloc(2 * (size_t)t->M));
+        for (size_t k = 0; k < t->up.size(); ++k) {
+            TreeLevel &lv = t->up[k];
+            const size_t n = (size_t)lv.n, nb = child[k].size();
+            HIP_OK(lv.A.alloc(n * hs)); HIP_OK(lv.C.alloc(n * hs));
+            HIP_OK(lv.yA.alloc(n * H)); HIP_OK(lv.yC.alloc(n * H));
+            HIP_OK(lv.d_first.alloc(n + 1)); HIP_OK(lv.d_child.alloc(nb)); HIP_OK(lv.d_parent.alloc(nb));
+            HIP_OK(hipMemcpy(lv.d_first, first[k].data(), 4 * (n + 1), hipMemcpyHostToDevice));
+            HIP_OK(hipMemcpy(lv.d_child, child[k].data(), 4 * nb, hipMemcpyHostToDevice));
+            HIP_OK(hipMemcpy(lv.d_parent, par32[k].data(), 4 * nb, hipMemcpyHostToDevice));
+        }
+        return hipDeviceSynchronize();
+    }();
+    if (err != hipSuccess) return rollup_hip_fail(ctx, "tsf_rollup_set_tree", err);
+    r->tree.swap(t);
+    return 0;
+}
+
+// level (1 = the groups) -> the level above the groups it names, or a refusal
+static int tree_level(tsf_rollup *r, const char *entry, int32_t level, int32_t lowest, TreeLevel **lv)
+{
+    tsf_ctx *ctx = r->ctx;
+    if (!r->tree) return fail(ctx, (std::string(entry) + " " + TREE_NOT_SET).c_str());
+    const int32_t L = 1 + (int32_t)r->tree->up.size();
+    if (level < lowest || level > L) {
+        char msg[200];
+        snprintf(msg, sizeof(msg), "%s: level = %d: outside [%d, %d]%s", entry, level, lowest, L,
+                 level == 1 ? " (tsf_rollup_set_totals is the entry for level 1)" : "");
+        return fail(ctx, msg);
+    }
+    *lv = level >= 2 ? &r->tree->up[(size_t)level - 2] : nullptr;
+    return 0;
+}
+
+extern "C" int tsf_rollup_set_node_totals(tsf_rollup *r, int32_t level, const tsf_spec *spec, int64_t Gt,
+                                          const double *theta, const double *y_scale, const tsf_grid_info *grid,
+                                          int32_t n_grids, const double *floor_, const double *cap,
+                                          const double *extra_future, int32_t shared_extra, const int64_t *series_key,
+                                          const int64_t *node)
+{
+    NoiseArOnce ar_once(r ? r->ctx : nullptr);
+    if (int rc = rollup_enter(r, true)) return rc;
+    tsf_ctx *ctx = r->ctx;
+    if (int rc = refuse_noise_ar(ctx, "tsf_rollup_set_node_totals")) return rc;
+    TreeLevel *lv = nullptr;
+    if (int rc = tree_level(r, "tsf_rollup_set_node_totals", level, 2, &lv)) return rc;
+    if (Gt < 0) return fail(ctx, "N must be >= 0");
+    if (Gt == 0) return 0;
+    if (int rc = rollup_check_series(r, spec, Gt, theta, y_scale, grid, n_grids, cap, extra_future, series_key, node, lv->n))
+        return rc;
+    std::vector<int32_t> has;
+    try {
+        has = lv->has;
+        has.resize((size_t)lv->n, 0);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, "tsf_rollup_set_node_totals: out of host memory");
+    }
+    for (int64_t n = 0; n < Gt; ++n) {
+        if (has[(size_t)node[n]]) {
+            char msg[160];
+            snprintf(msg, sizeof(msg), "node[%lld] = %lld: the node has a total already (one total per node)",
+                     (long long)n, (long long)node[n]);
+            return fail(ctx, msg);
+        }
+        has[(size_t)node[n]] = 1;
+    }
+    if (!lv->T) {
+        // +0.0 everywhere, so that the add below leaves the draws themselves (together or not at all, as in set_totals)
+        OwnedDev<double> T, yT;
+        OwnedDev<int32_t> d_has;
+        const hipError_t e = [&]() -> hipError_t {
+            HIP_OK(T.alloc((size_t)lv->n * r->H * r->S, true));
+            HIP_OK(yT.alloc((size_t)lv->n * r->H, true));
+            HIP_OK(d_has.alloc((size_t)lv->n, true));
+            return hipDeviceSynchronize();
+        }();
+        if (e != hipSuccess) return rollup_hip_fail(ctx, "tsf_rollup_set_node_totals", e);
+        lv->T.swap(T); lv->yT.swap(yT); lv->d_has.swap(d_has);
+    }
+    r->tree->solved = false;
+    if (int rc = rollup_accumulate(r, spec, Gt, theta, y_scale, grid, n_grids, floor_, cap, extra_future, shared_extra,
+                                   series_key, node, lv->T, lv->yT))
+        return rc;
+    r->poisoned = true;
+    HIP_TRY(ctx, hipMemcpy(lv->d_has, has.data(), 4 * (size_t)lv->n, hipMemcpyHostToDevice));
+    r->poisoned = false;
+    lv->has.swap(has);
+    return 0;
+}
+
+extern "C" int tsf_rollup_solve_tree(tsf_rollup *r, const double *mu, const double *kappa)
+{
+    if (int rc = rollup_enter(r, true)) return rc;
+    tsf_ctx *ctx = r->ctx;
+    if (!r->tree) return fail(ctx, (std::string("tsf_rollup_solve_tree ") + TREE_NOT_SET).c_str());
+    RollupTree &t = *r->tree;
+    if (!mu || !kappa) return fail(ctx, "NULL mu or kappa");
+    if (int rc = check_shares(ctx, "mu", mu, t.M)) return rc;
+    if (int rc = check_shares(ctx, "kappa", kappa, t.M)) return rc;
+    t.solved = false;
+    HIP_TRY(ctx, hipMemcpy(t.d_mk, mu, 8 * (size_t)t.M, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(t.d_mk + t.M, kappa, 8 * (size_t)t.M, hipMemcpyHostToDevice));
+    const int32_t H = r->H, S = r->S;
+    const unsigned by = (unsigned)((S + 255) / 256);
+    const double *d_mu = t.d_mk, *d_kappa = t.d_mk + t.M;
+    // up: the groups' blend, then per level the gather of the level below and the blend with the level's own totals
+    TreeBlendArgs b;
+    memset(&b, 0, sizeof(b));
+    b.H = H; b.NS = S;
+    b.A = r->acc; b.t = r->top; b.m = t.delta; b.yA = r->ysum; b.yt = r->ytop; b.ym = t.ydelta;
+    b.has = r->top ? r->d_has_top.p : nullptr; b.mu = d_mu;
+    hipLaunchKernelGGL(tree_blend_kernel, dim3((unsigned)(r->G * H), by), dim3(256), 0, nullptr, b);
+    HIP_TRY(ctx, hipGetLastError());
+    const double *m = t.delta, *ym = t.ydelta;
+    int64_t off = r->G;
+    for (TreeLevel &lv : t.up) {
+        const TreeGatherArgs g = {m, lv.A, ym, lv.yA, lv.d_first, lv.d_child, H, S};
+        hipLaunchKernelGGL(tree_gather_kernel, dim3((unsigned)(lv.n * H), by), dim3(256), 0, nullptr, g);
+        HIP_TRY(ctx, hipGetLastError());
+        b.A = lv.A; b.t = lv.T; b.m = lv.C; b.yA = lv.yA; b.yt = lv.yT; b.ym = lv.yC;
+        b.has = lv.T ? lv.d_has.p : nullptr; b.mu = d_mu + off;
+        hipLaunchKernelGGL(tree_blend_kernel, dim3((unsigned)(lv.n * H), by), dim3(256), 0, nullptr, b);
+        HIP_TRY(ctx, hipGetLastError());
+        m = lv.C; ym = lv.yC; off += lv.n;
+    }
+    // down: the top level's c is its m; every level below takes its share of what its parent moved by
+    for (size_t k = t.up.size(); k-- > 0;) {
+        TreeLevel &lv = t.up[k];
+        off -= lv.n;                                            // (now the first node of level k + 2)
+        const bool groups = k == 0;
+        const int64_t n = groups ? r->G : t.up[k - 1].n;
+        TreePushArgs p;
+        memset(&p, 0, sizeof(p));
+        p.H = H; p.NS = S;
+        p.m = groups ? t.delta.p : t.up[k - 1].C.p; p.ym = groups ? t.ydelta.p : t.up[k - 1].yC.p;
+        p.cp = lv.C; p.Ap = lv.A; p.ycp = lv.yC; p.yAp = lv.yA;
+        p.acc = groups ? r->acc.p : nullptr; p.yacc = groups ? r->ysum.p : nullptr;
+        p.parent = lv.d_parent; p.kappa = d_kappa + (off - n);
+        hipLaunchKernelGGL(tree_push_kernel, dim3((unsigned)(n * H), by), dim3(256), 0, nullptr, p);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    t.solved = true;
+    return 0;
+}
+
+static const char *const TREE_NOT_SOLVED =
+    "the tree is not solved: tsf_rollup_solve_tree has not run since the last add, set_totals or set_node_totals";
+
+extern "C" int tsf_rollup_reconcile_tree(tsf_rollup *r, const tsf_spec *spec, int64_t N, const double *theta,
+                                         const double *y_scale, const tsf_grid_info *grid, int32_t n_grids,
+                                         const double *floor_, const double *cap, const double *extra_future,
+                                         int32_t shared_extra, const int64_t *series_key, const int64_t *group,
+                                         const double *share, int32_t n_q, const double *quantiles, tsf_reconcile_out *out)
+{
+    NoiseArOnce ar_once(r ? r->ctx : nullptr);
+    if (int rc = rollup_enter(r, true)) return rc;
+    tsf_ctx *ctx = r->ctx;
+    if (int rc = refuse_noise_ar(ctx, "tsf_rollup_reconcile_tree")) return rc;
+    if (N < 0) return fail(ctx, "N must be >= 0");
+    if (N == 0) return 0;
+    if (!r->tree) return fail(ctx, (std::string("tsf_rollup_reconcile_tree ") + TREE_NOT_SET).c_str());
+    if (!r->tree->solved) return fail(ctx, (std::string("tsf_rollup_reconcile_tree: ") + TREE_NOT_SOLVED).c_str());
+    const int32_t H = r->H, S = r->S;
+    TreeMemberArgs m;
+    memset(&m, 0, sizeof(m));
+    m.delta = r->tree->delta; m.ydelta = r->tree->ydelta; m.H = H; m.NS = S;
+    const MemberPass pass = [&](double *samp, double *yhat, const int32_t *g, const double *sh, int64_t nc) {
+        m.samp = samp; m.yhat = yhat; m.group = g; m.share = sh;
+        hipLaunchKernelGGL(tree_member_kernel, dim3((unsigned)(nc * H), (unsigned)((S + 255) / 256)), dim3(256), 0, nullptr, m);
+    };
+    return reconcile_members(r, "tsf_rollup_reconcile_tree", spec, N, theta, y_scale, grid, n_grids, floor_, cap,
+                             extra_future, shared_extra, series_key, group, share, n_q, quantiles, out, pass);
+}
+
+extern "C" int tsf_rollup_tree_totals(tsf_rollup *r, int32_t level, int64_t node0, int64_t n_nodes, int32_t n_q,
+                                      const double *quantiles, tsf_rollup_out *out)
+{
+    if (int rc = rollup_enter(r, true)) return rc;
+    tsf_ctx *ctx = r->ctx;
+    TreeLevel *lv = nullptr;
+    if (int rc = tree_level(r, "tsf_rollup_tree_totals", level, 1, &lv)) return rc;
+    RollupTree &t = *r->tree;
+    if (!t.solved) return fail(ctx, (std::string("tsf_rollup_tree_totals: ") + TREE_NOT_SOLVED).c_str());
+    const int64_t n_level = lv ? lv->n : r->G;
+    if (node0 < 0 || n_nodes < 0 || node0 > n_level || n_nodes > n_level - node0) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "nodes [%lld, %lld + %lld): outside the level's [0, %lld)", (long long)node0,
+                 (long long)node0, (long long)n_nodes, (long long)n_level);
+        return fail(ctx, msg);
+    }
+    if (!out) return fail(ctx, "NULL output (tsf_rollup_out and its yhat are required)");
+    if (int rc = check_rollup_read(r, n_q, quantiles, out->yhat, out->q, out->cum_q, out->samples)) return rc;
+    if (n_nodes == 0) return 0;
+    const int32_t H = r->H, S = r->S;
+    const size_t hs = (size_t)H * S;
+    if (out->count) {
+        // the members added below each node: the groups' counts summed up the levels
+        try {
+            std::vector<int64_t> cnt(r->count), up;
+            for (int32_t k = 2; k <= level; ++k) {
+                const TreeLevel &l = t.up[(size_t)k - 2];
+                up.assign((size_t)l.n, 0);
+                for (size_t c = 0; c < cnt.size(); ++c) up[(size_t)l.parent[c]] += cnt[c];
+                cnt.swap(up);
+            }
+            memcpy(out->count, cnt.data() + node0, 8 * (size_t)n_nodes);
+        } catch (const std::bad_alloc &) {
+            return fail(ctx, "tsf_rollup_tree_totals: out of host memory");
+        }
+    }
+    HostOuts outs;
+    if (lv) {
+        // a level above the groups: c itself is kept
+        outs.adopt(out->yhat, lv->yC + (size_t)node0 * H, 8 * (size_t)n_nodes * H);
+        return cells_read(r, lv->C + (size_t)node0 * hs, n_nodes, n_q, quantiles, *out, nullptr, outs);
+    }
+    // the groups: acc + (c - acc), range by range into the scratch
+    TreeTotalArgs a;
+    memset(&a, 0, sizeof(a));
+    a.acc = r->acc; a.delta = t.delta; a.ysum = r->ysum; a.ydelta = t.ydelta; a.H = H; a.NS = S;
+    double *d_yh = outs.want(out->yhat, 8 * (size_t)n_nodes * H);
+    const CellMaker make = [&](double *dst, int64_t g0, int64_t gc) -> int {
+        a.out = dst; a.yout = d_yh + (size_t)g0 * H; a.g0 = node0 + g0;
+        hipLaunchKernelGGL(tree_total_kernel, dim3((unsigned)(gc * H), (unsigned)((S + 255) / 256)), dim3(256), 0, nullptr, a);
+        HIP_TRY(ctx, hipGetLastError());
+        return 0;
+    };
+    return cells_read(r, nullptr, n_nodes, n_q, quantiles, *out, &make, outs);
 }
 
 // ---- diagnostics --------------------------------------------------------------------------------

@@ -1623,7 +1623,8 @@ class Rollup(object):
     add (once per spec, any number of calls) and read by quantiles / samples at any time.  A context manager; close()
     frees the device memory (before its context is closed).  Shape and level errors raise ValueError before the library
     is touched.  Where the totals are fitted directly as well: set_totals, then reconcile (the members) and
-    reconciled_totals (include/tsf.h "reconciliation").  noise_corr: rho [n_groups] in [0, 1] or a NoiseCorrelation
+    reconciled_totals (include/tsf.h "reconciliation"); with levels above the groups: set_tree, set_node_totals,
+    solve_tree, then reconcile_tree and tree_totals (include/tsf.h "tree reconciliation").  noise_corr: rho [n_groups] in [0, 1] or a NoiseCorrelation
     (residual_correlation) -- the members' observation noise is then drawn with that correlation within each group
     (include/tsf.h "correlated group roll-ups"; group_key [n_groups]: the keys of the groups' factor streams, default the
     group index); such a roll-up cannot be reconciled.  None: the members are independent, as always."""
@@ -1643,6 +1644,7 @@ class Rollup(object):
             raise ValueError('group_key without noise_corr')
         corr = None if noise_corr is None else _noise_corr_args(noise_corr, group_key, self.G)
         self._has_corr = False
+        self._tree_set = None
         self._ctx = ctx or get_context()
         h = ctypes.c_void_p()
         self._ctx.check(_lib.load().tsf_rollup_create(self._ctx.handle, self.G, self.H, ds.ctypes.data, self.S, self.seed,
@@ -1692,14 +1694,16 @@ class Rollup(object):
         _set_noise_ar(self._ctx, _noise_ar_phi(noise_ar, args[0], self.ds_future_ns))
         self._ctx.check(_lib.load().tsf_rollup_add(h, *_rollup_c_args(spec, args)))
 
-    def _group_outs(self, Q, want):
-        """-> (dict of a tsf_rollup_out's arrays: yhat, count and those of q, cum_q, samples named in `want`; the struct)"""
-        res = {'yhat': np.zeros((self.G, self.H)), 'count': np.zeros(self.G, dtype=np.int64)}
+    def _group_outs(self, Q, want, n=None):
+        """-> (dict of a tsf_rollup_out's arrays: yhat, count and those of q, cum_q, samples named in `want`; the struct);
+        n: the number of groups or nodes read (None: n_groups)"""
+        n = self.G if n is None else n
+        res = {'yhat': np.zeros((n, self.H)), 'count': np.zeros(n, dtype=np.int64)}
         for k in ('q', 'cum_q'):
             if k in want:
-                res[k] = np.zeros((self.G, Q, self.H))
+                res[k] = np.zeros((n, Q, self.H))
         if 'samples' in want:
-            res['samples'] = np.zeros((self.G, self.H, self.S))
+            res['samples'] = np.zeros((n, self.H, self.S))
         return res, _lib.TsfRollupOut(**{k: v.ctypes.data for k, v in res.items()})
 
     def _read(self, levels, want):
@@ -1768,6 +1772,12 @@ class Rollup(object):
         set_totals: draw' = draw + share[n] * (total's draw - sum of the group's member draws) -> Reconciled (a
         Quantiles: yhat [N][H], q and cum_q [N][Q][H] at the levels `quantiles`; .samples [N][H][S] where asked for).
         share [N] in [0, 1] (reconcile_shares); a group without a total leaves its members as they are."""
+        return self._second_pass('tsf_rollup_reconcile', spec, theta, y_scale, grid, group, series_key, share, quantiles,
+                                 cumulative, samples, floor, cap, extra_future)
+
+    def _second_pass(self, entry, spec, theta, y_scale, grid, group, series_key, share, quantiles, cumulative, samples,
+                     floor, cap, extra_future):
+        """reconcile and reconcile_tree: the checks, the outputs and the call of `entry`, which take the same arguments"""
         h = self._handle()
         args = _rollup_add_args(spec, theta, y_scale, grid, group, series_key, floor, cap, extra_future, self.G, self.H)
         N = args[0]
@@ -1789,8 +1799,8 @@ class Rollup(object):
         if samples:
             res['samples'] = np.zeros((N, self.H, self.S))
         out = _lib.TsfReconcileOut(**{k: v.ctypes.data for k, v in res.items()})
-        self._ctx.check(_lib.load().tsf_rollup_reconcile(h, *_rollup_c_args(spec, args), share.ctypes.data, Q,
-                                                         levels.ctypes.data if Q else None, ctypes.byref(out)))
+        self._ctx.check(getattr(_lib.load(), entry)(h, *_rollup_c_args(spec, args), share.ctypes.data, Q,
+                                                    levels.ctypes.data if Q else None, ctypes.byref(out)))
         return Reconciled(res['yhat'], levels, res.get('q'), res.get('cum_q'), res.get('samples'))
 
     def reconciled_totals(self, share_total, levels, cumulative=False, samples=False):
@@ -1809,6 +1819,92 @@ class Rollup(object):
             raise ValueError('at least one quantile level')
         res, out = self._group_outs(Q, ['q'] + (['cum_q'] if cumulative else []) + (['samples'] if samples else []))
         self._ctx.check(_lib.load().tsf_rollup_reconciled_totals(h, mu.ctypes.data, Q, levels.ctypes.data, ctypes.byref(out)))
+        r = RollupQuantiles(res['yhat'], res['count'], levels, res['q'], res.get('cum_q'))
+        return (r, res['samples']) if samples else r
+
+    # -- tree reconciliation (include/tsf.h "tree reconciliation") --
+
+    def _tree(self):
+        if self._tree_set is None:
+            raise ValueError('the roll-up has no tree: set_tree first')
+        return self._tree_set
+
+    def set_tree(self, tree):
+        """Declares the levels above the groups: a RollupTree (rollup_tree) whose level 1 is this roll-up's n_groups.
+        Once per roll-up; not on a roll-up with noise_corr."""
+        h = self._handle()
+        if not isinstance(tree, RollupTree):
+            raise ValueError('tree must be a RollupTree (rollup_tree)')
+        if self._tree_set is not None:
+            raise ValueError('the roll-up has a tree already')
+        if self._has_corr:
+            raise ValueError('a tree on a roll-up with noise_corr: correlated draws are not reconciled')
+        if tree.n_nodes[0] != self.G:
+            raise ValueError('the tree has %d groups, the roll-up %d' % (tree.n_nodes[0], self.G))
+        if tree.n_levels < 2:
+            raise ValueError('a tree needs at least one level above the groups')
+        n_nodes = np.ascontiguousarray(tree.n_nodes[1:], dtype=np.int64)
+        parent = np.ascontiguousarray(np.concatenate(tree.parent), dtype=np.int64)
+        self._ctx.check(_lib.load().tsf_rollup_set_tree(h, len(n_nodes), n_nodes.ctypes.data, parent.ctypes.data))
+        self._tree_set = tree
+
+    def set_node_totals(self, level, spec, theta, y_scale, grid, node, series_key, floor=None, cap=None,
+                        extra_future=None):
+        """The directly fitted totals of nodes of one level in [2, L] (level 1: set_totals): series n is the total of
+        node[n] of that level (at most one total per node, over all calls); series_key [Gt] is required and must differ
+        from every other key of the hierarchy."""
+        h = self._handle()
+        tree = self._tree()
+        if not 2 <= int(level) <= tree.n_levels:
+            raise ValueError('level must be in [2, %d] (level 1: set_totals)' % tree.n_levels)
+        args = _rollup_add_args(spec, theta, y_scale, grid, node, series_key, floor, cap, extra_future,
+                                tree.n_nodes[int(level) - 1], self.H)
+        if len(np.unique(args[4])) != args[0]:
+            raise ValueError('node: a node appears twice (one total per node)')
+        self._ctx.check(_lib.load().tsf_rollup_set_node_totals(h, int(level), *_rollup_c_args(spec, args)))
+
+    def solve_tree(self, shares):
+        """The two sweeps over what has been added, with a TreeShares (reconcile_tree_shares) of this tree, after every
+        add, set_totals and set_node_totals.  Any of those afterwards invalidates it."""
+        h = self._handle()
+        tree = self._tree()
+        if not isinstance(shares, TreeShares):
+            raise ValueError('shares must be a TreeShares (reconcile_tree_shares)')
+        mu, kappa = np.concatenate(shares.mu), np.concatenate(shares.kappa)
+        if [len(a) for a in shares.mu] != list(tree.n_nodes) or [len(a) for a in shares.kappa] != list(tree.n_nodes):
+            raise ValueError('shares: not of this tree (nodes per level differ)')
+        for a in (mu, kappa):
+            if not (np.isfinite(a).all() and a.min() >= 0.0 and a.max() <= 1.0):
+                raise ValueError('mu and kappa values must be finite and in [0, 1]')
+        self._ctx.check(_lib.load().tsf_rollup_solve_tree(h, mu.ctypes.data, kappa.ctypes.data))
+
+    def reconcile_tree(self, spec, theta, y_scale, grid, group, series_key, share, quantiles=(), cumulative=False,
+                       samples=False, floor=None, cap=None, extra_future=None):
+        """The second pass over members that were added, after solve_tree: draw' = draw + share[n] * (c - acc) of the
+        member's group -> Reconciled, with reconcile's arguments and outputs.  share [N]: TreeShares.share."""
+        self._handle()
+        self._tree()
+        return self._second_pass('tsf_rollup_reconcile_tree', spec, theta, y_scale, grid, group, series_key, share,
+                                 quantiles, cumulative, samples, floor, cap, extra_future)
+
+    def tree_totals(self, level, levels, cumulative=False, samples=False, nodes=None):
+        """-> RollupQuantiles of the reconciled nodes of one level in [1, L] (count: the members added below each node);
+        with samples, (RollupQuantiles, [n][H][S]).  nodes: (first, count), a range of the level's nodes (None: all)."""
+        h = self._handle()
+        tree = self._tree()
+        if not 1 <= int(level) <= tree.n_levels:
+            raise ValueError('level must be in [1, %d]' % tree.n_levels)
+        n_level = tree.n_nodes[int(level) - 1]
+        n0, n = (0, n_level) if nodes is None else (int(nodes[0]), int(nodes[1]))
+        if n0 < 0 or n < 1 or n0 + n > n_level:
+            raise ValueError('nodes: (first, count) within the level\'s %d nodes, count >= 1' % n_level)
+        quantile_columns(levels)
+        levels = np.array(levels, dtype=np.float64).reshape(-1)
+        Q = len(levels)
+        if Q == 0:
+            raise ValueError('at least one quantile level')
+        res, out = self._group_outs(Q, ['q'] + (['cum_q'] if cumulative else []) + (['samples'] if samples else []), n)
+        self._ctx.check(_lib.load().tsf_rollup_tree_totals(h, int(level), n0, n, Q, levels.ctypes.data, ctypes.byref(out)))
         r = RollupQuantiles(res['yhat'], res['count'], levels, res['q'], res.get('cum_q'))
         return (r, res['samples']) if samples else r
 
@@ -1884,6 +1980,122 @@ def aggregate_aligned(y, group, n_groups):
         g = int(group[n])
         tot[g] = tot[g] + y[n]
     return tot
+
+
+class RollupTree(object):
+    """The levels of a hierarchy above its members, host only (include/tsf.h "tree reconciliation"): group [N] (each
+    member's node of level 1, dense in [0, n_nodes[0])), n_nodes [L] (nodes per level 1 .. L), parent (L - 1 int64
+    arrays: parent[k][c] is the node of level k + 2 above node c of level k + 1), labels (the unique labels per level,
+    or None).  A node needs no child and a group no member: such a node is empty and stays 0.  Every error is a
+    ValueError."""
+
+    def __init__(self, group, n_nodes, parent, labels=None):
+        self.group = np.ascontiguousarray(group, dtype=np.int64)
+        self.n_nodes = [int(n) for n in n_nodes]
+        self.parent = [np.ascontiguousarray(p, dtype=np.int64) for p in parent]
+        self.labels = labels
+        if self.group.ndim != 1:
+            raise ValueError('group must be [N]')
+        if not 1 <= len(self.n_nodes) <= 1 + _lib.TREE_MAX_LEVELS:
+            raise ValueError('a tree has 1 to %d levels of nodes' % (1 + _lib.TREE_MAX_LEVELS))
+        if min(self.n_nodes) < 1:
+            raise ValueError('every level needs at least one node')
+        if len(self.parent) != len(self.n_nodes) - 1:
+            raise ValueError('parent: one array per level below the top')
+        if len(self.group) and (self.group.min() < 0 or self.group.max() >= self.n_nodes[0]):
+            raise ValueError('group values must be in [0, %d)' % self.n_nodes[0])
+        for k, p in enumerate(self.parent):
+            if p.shape != (self.n_nodes[k],):
+                raise ValueError('parent[%d] must be [%d]: one parent per node of level %d' % (k, self.n_nodes[k], k + 1))
+            if p.min() < 0 or p.max() >= self.n_nodes[k + 1]:
+                raise ValueError('parent[%d] values must be in [0, %d)' % (k, self.n_nodes[k + 1]))
+
+    @property
+    def n_levels(self):
+        return len(self.n_nodes)
+
+    def member_counts(self):
+        """-> per level, the number of members below each node (int64 [n_nodes[k]])"""
+        cnt = [np.bincount(self.group, minlength=self.n_nodes[0]).astype(np.int64)]
+        for k, p in enumerate(self.parent):
+            cnt.append(np.bincount(p, weights=cnt[-1], minlength=self.n_nodes[k + 1]).astype(np.int64))
+        return cnt
+
+
+def rollup_tree(level_labels):
+    """One label array [N] per level (each member's group label, that group's parent label, and so on upwards; each an
+    integer array or a tuple of them, as in rollup_groups) -> RollupTree with dense indices per level and the unique
+    labels.  A label with two different parents is a ValueError.  Pure numpy."""
+    if not isinstance(level_labels, (list, tuple)) or len(level_labels) < 1:
+        raise ValueError('level_labels: a list of label arrays, one per level')
+    uniq, idx = [], []
+    for lab in level_labels:
+        u, i = rollup_groups(lab)
+        if idx and len(i) != len(idx[0]):
+            raise ValueError('level_labels: the label arrays differ in length')
+        uniq.append(u)
+        idx.append(i)
+    if len(idx[0]) == 0:
+        raise ValueError('level_labels: no members')
+    parent = []
+    for k in range(1, len(idx)):
+        p = np.full(len(uniq[k - 1]), -1, dtype=np.int64)
+        p[idx[k - 1]] = idx[k]
+        if not np.array_equal(p[idx[k - 1]], idx[k]):
+            raise ValueError('level %d: a label has two different parents' % k)
+        parent.append(p)
+    return RollupTree(idx[0], [len(u) for u in uniq], parent, labels=uniq)
+
+
+class TreeShares(object):
+    """What reconcile_tree_shares returns: share [N] (Rollup.reconcile_tree) and, as one array per level 1 .. L, mu, e
+    and kappa (Rollup.solve_tree takes the object)."""
+
+    def __init__(self, share, mu, e, kappa):
+        self.share, self.mu, self.e, self.kappa = share, mu, e, kappa
+
+
+def reconcile_tree_shares(tree, weight=None, node_weight='struct'):
+    """Weights -> TreeShares: a thin binding of tsf_reconcile_tree_shares (host only).  weight [N]: the members' forecast
+    error variances (None: all 1).  node_weight: the variances of the nodes' fitted totals -- 'ols' (all 1), 'struct'
+    (the number of members below the node; a node without members gets none) or one array per level 1 .. L (NaN: the
+    node has no total)."""
+    if not isinstance(tree, RollupTree):
+        raise ValueError('tree must be a RollupTree (rollup_tree)')
+    N = len(tree.group)
+    w = None
+    if weight is not None:
+        w = np.ascontiguousarray(weight, dtype=np.float64)
+        if w.shape != (N,):
+            raise ValueError('weight must be [N]')
+        if not (np.isfinite(w).all() and (w > 0).all()):
+            raise ValueError('weight values must be finite and positive')
+    if isinstance(node_weight, str):
+        if node_weight == 'ols':
+            v = [np.ones(n) for n in tree.n_nodes]
+        elif node_weight == 'struct':
+            v = [np.where(c > 0, c, np.nan).astype(np.float64) for c in tree.member_counts()]
+        else:
+            raise ValueError("node_weight must be 'ols', 'struct' or one array per level")
+    else:
+        v = [np.ascontiguousarray(a, dtype=np.float64) for a in node_weight]
+        if [a.shape for a in v] != [(n,) for n in tree.n_nodes]:
+            raise ValueError('node_weight: one array [n_nodes] per level')
+    v = np.concatenate(v)
+    if not ((np.isfinite(v) & (v > 0)) | np.isnan(v)).all():
+        raise ValueError('node_weight values must be finite and positive (NaN: no total)')
+    M = len(v)
+    n_nodes = np.ascontiguousarray(tree.n_nodes[1:], dtype=np.int64)
+    parent = np.ascontiguousarray(np.concatenate(tree.parent + [np.zeros(0, dtype=np.int64)]), dtype=np.int64)
+    share, mu, e, kappa = np.zeros(N), np.zeros(M), np.zeros(M), np.zeros(M)
+    rc = _lib.load().tsf_reconcile_tree_shares(N, tree.group.ctypes.data if N else None, _lib._ptr(w) if N else None,
+                                               tree.n_nodes[0], len(n_nodes), n_nodes.ctypes.data, parent.ctypes.data,
+                                               v.ctypes.data, share.ctypes.data if N else None, mu.ctypes.data,
+                                               e.ctypes.data, kappa.ctypes.data)
+    if rc != 0:
+        raise _lib.TsfError('tsf_reconcile_tree_shares refused its arguments (%d)' % rc)
+    cuts = np.cumsum(tree.n_nodes)[:-1]
+    return TreeShares(share, np.split(mu, cuts), np.split(e, cuts), np.split(kappa, cuts))
 
 
 def predict_reconciled(spec, theta, y_scale, grid, ds_future_ns, labels, quantiles, series_key, total_theta,
