@@ -714,6 +714,95 @@ int tsf_rollup_reconcile_tree(tsf_rollup *r, const tsf_spec *spec, int64_t N, co
 int tsf_rollup_tree_totals(tsf_rollup *r, int32_t level, int64_t node0, int64_t n_nodes, int32_t n_q,
                            const double *quantiles, tsf_rollup_out *out);
 
+/* ---- temporal reconciliation: daily forecasts and directly fitted period totals made coherent ---------------
+ * The reconciliations above work across series.  This one works along time, inside one series: the H rows of a forecast
+ * are the members, the forecast of a second model fitted on the period totals of the same history (its weekly or monthly
+ * sums) is the total, and each row window [win_start[k], win_end[k]) is a group.  The sum of seven noisy days has a
+ * better signal than any one of them, so the period model sees level and yearly pattern better; the daily model alone
+ * knows the pattern inside the period.  Without this a caller who fits both has two answers for "next week's total".
+ * The method is "reconciliation"'s projection (weighted least squares, diagonal weights, two levels), applied to each
+ * sample's path on the device: the reconciled rows of a window sum to the reconciled period total, and the quantiles of
+ * both are quantiles of coherent draws.
+ * Reference interface replaced: none (neither the reference nor fbprophet has such a function); parity unpinned (what is
+ * pinned is the contract below, against tsf_predict, tsf_predict_quantiles and tsf_predict_windows).  Host pointers only.
+ * Timing: tools/bench_temporal.py; DESIGN.md 5q.
+ *
+ * tsf_temporal_shares (host only: no context, no device) is tsf_reconcile_shares' rule per window.  w [N][H] (NULL: all
+ * 1.0) and v [N][K] are the caller's estimates of the error variance of every row's forecast and of every period
+ * forecast; a NaN v marks a window that is not reconciled for that series.  Per series and window
+ *   W = the sum of w[n][h] over the window's rows, from +0.0 by plain double adds in ascending row order,
+ *   share[n][h] = w[n][h] / (v[n][k] + W),   share_total[n][k] = W / (v[n][k] + W)       (each one add and one divide).
+ * A window with a NaN v gets +0.0 in its share cells and NaN in share_total; a row in no window gets share +0.0.
+ * Returns -1 for K outside [1, TSF_MAX_WINDOWS], a window that is not 0 <= win_start < win_end <= H, two windows that
+ * share a row, and a w or v that is not finite and positive (NaN v excepted).
+ *
+ * tsf_predict_temporal.  The first block of arguments is the daily model and means what it means in
+ * tsf_predict_quantiles; the second block is the period model on its K rows ds_period (one row per window, in the order
+ * of the windows), with a spec, grids, floor, cap, extra columns and keys of its own.  noise_ar, noise_ar_p [N]: each
+ * model's AR(1) coefficients, phi in [0, 1), or NULL for independent noise.  They are arguments of this call: a pending
+ * tsf_set_noise_ar setting is neither taken nor cleared.  share [N][H] and share_total [N][K] as tsf_temporal_shares
+ * writes them.  The tsf_temporal_out struct, the levels, the windows and the shares are host memory.
+ *
+ * Contract, in plain double operations (no fused multiply-add).  x[h][s] are the daily draws: tsf_predict_quantiles'
+ * samples for (spec, series_key[n], seed, n_samples) with tsf_set_noise_ar(noise_ar) where it is given; t[k][s] are the
+ * period model's draws, the same statement for (spec_p, period_key[n], noise_ar_p) on the K rows ds_period; y and yp are
+ * tsf_predict's point forecasts of the two models.  Window k = [a, b) is active for series n where share_total[n][k] is
+ * not NaN.
+ *   sum      = x[a][s];  sum = sum + x[h][s] for h = a + 1 .. b - 1           (tsf_predict_windows' window sum)
+ *   d        = t[k][s] - sum where the window is active, +0.0 where it is not
+ *   x'[h][s] = x[h][s] + share[n][h] * d        for the rows of the window; a row in no window is left as it is
+ *   win'[k][s] = sum + share_total[n][k] * d    (the NaN of an inactive window read as +0.0: win' = sum)
+ *   ysum = y[a]; ysum = ysum + y[h] ...;  dy = yp[k] - ysum (+0.0 where inactive)
+ *   yhat'[h] = y[h] + share[n][h] * dy,   total[k] = ysum + share_total[n][k] * dy
+ *   q is tsf_predict_quantiles' expression over the ascending sort of x'[h][.]; cum_q the same over the running sums
+ *   c[0] = x'[0], c[h] = c[h-1] + x'[h]; win_q the same over win'[k][.].
+ * So with every share +0.0 and every share_total +0.0 or NaN, yhat, q, cum_q and samples are tsf_predict_quantiles' bit
+ * for bit and total and win_q are tsf_predict_windows' (for every value the draws produce: -0.0 would become +0.0).
+ * The sum of share[n][h] over a window equals share_total[n][k] (to rounding), so the reconciled rows of an active window
+ * sum to its reconciled total up to rounding.  The two streams are independent where the keys differ, so with weights
+ * equal to the true variances a reconciled total has variance v W / (v + W) and a reconciled row w - w^2 / (v + W).
+ * The result depends neither on how the call is cut into scratch chunks (512 MB: the daily sample buffer, a second one
+ * with cum_q, and the period buffer), nor on which outputs are wanted, nor on what other series are in the call.  No
+ * floating-point atomics.  Behaviour for non-finite draws is unspecified.
+ *
+ * Refusals (< 0 with a message, before any launch; the context stays usable): everything tsf_predict_windows refuses
+ * for its model, its windows (against H) and its levels, and the same for the period model (against K rows); two
+ * windows that share a row (tsf_predict_windows allows them; here a row would get two corrections); a NULL share or
+ * share_total, a share outside [0, 1] or NaN, a share_total outside [0, 1] and not NaN; a NULL series_key or
+ * period_key; a phi outside [0, 1); K outside [1, TSF_MAX_WINDOWS]; a NULL out or out->yhat; an output set that wants
+ * nothing but yhat and total; n_q = 0 with q, cum_q or win_q wanted.  N == 0 is a legal no-op.
+ * Not detected, the caller's business: a period_key equal to a series_key (the two streams are then shared and the
+ * independence above is gone); a ds_period that does not describe the windows.
+ *
+ * Out of scope: more than two temporal levels (weeks do not nest in months); overlapping windows; cross-temporal
+ * reconciliation (a roll-up whose members are temporally reconciled); non-diagonal weights; estimating the weights (w
+ * and v are the caller's variances); the job configurations; _dev variants; more than one GPU. */
+int tsf_temporal_shares(int64_t N, int32_t H, int32_t K, const int32_t *win_start, const int32_t *win_end /* [K] */,
+                        const double *w /* [N][H], NULL = all 1.0 */, const double *v /* [N][K]; NaN = not reconciled */,
+                        double *share /* [N][H] */, double *share_total /* [N][K] */);
+typedef struct {
+    double *yhat;           /* [N][H]        required: the reconciled point forecast */
+    double *q;              /* [N][n_q][H]   per-row quantiles of the reconciled draws; NULL: not wanted (all below likewise) */
+    double *cum_q;          /* [N][n_q][H]   quantiles of each reconciled sample's running sum over rows 0..h */
+    double *total;          /* [N][K]        the reconciled point forecast of every window's total */
+    double *win_q;          /* [N][n_q][K]   quantiles of the reconciled window totals */
+    double *samples;        /* [N][H][n_samples] the reconciled draws */
+    double *win_samples;    /* [N][K][n_samples] the reconciled window totals of every sample */
+} tsf_temporal_out;
+int tsf_temporal_out_size(void);    /* sizeof(tsf_temporal_out): the self-check of a binding */
+int tsf_predict_temporal(tsf_ctx *ctx,
+                         const tsf_spec *spec, int64_t N, int32_t H, const double *theta, const double *y_scale,
+                         const tsf_grid_info *grid, int32_t n_grids, const int64_t *ds_future /* [H] or [N][H] */,
+                         int32_t shared_future, const double *floor, const double *cap, const double *extra_future,
+                         const int64_t *series_key /* [N], required */, const double *noise_ar /* [N] phi or NULL */,
+                         const tsf_spec *spec_p, int32_t K, const double *theta_p, const double *y_scale_p,
+                         const tsf_grid_info *grid_p, int32_t n_grids_p, const int64_t *ds_period /* [K] or [N][K] */,
+                         int32_t shared_period, const double *floor_p, const double *cap_p, const double *extra_period,
+                         const int64_t *period_key /* [N], required */, const double *noise_ar_p /* [N] phi or NULL */,
+                         int32_t n_samples, uint64_t seed, const int32_t *win_start, const int32_t *win_end /* [K] */,
+                         const double *share /* [N][H] */, const double *share_total /* [N][K] */, int32_t n_q,
+                         const double *quantiles, tsf_temporal_out *out);
+
 /* ---- correlated group roll-ups: a shared noise factor per group ----------------------------------------
  * The members of a total share weather, promotions and outages, so their forecast errors move together, and the P90
  * of a total of m independent members is too narrow by a factor that grows like sqrt(1 + (m - 1) rho): more than 3 x at

@@ -130,6 +130,12 @@ class TsfReconcileOut(ctypes.Structure):
     _fields_ = [('yhat', ctypes.c_void_p), ('q', ctypes.c_void_p), ('cum_q', ctypes.c_void_p), ('samples', ctypes.c_void_p)]
 
 
+class TsfTemporalOut(ctypes.Structure):
+    """tsf_temporal_out (include/tsf.h)."""
+    _fields_ = [('yhat', ctypes.c_void_p), ('q', ctypes.c_void_p), ('cum_q', ctypes.c_void_p), ('total', ctypes.c_void_p),
+                ('win_q', ctypes.c_void_p), ('samples', ctypes.c_void_p), ('win_samples', ctypes.c_void_p)]
+
+
 class TsfTuneOut(ctypes.Structure):
     """tsf_tune_out (include/tsf.h)."""
     _fields_ = [('score', ctypes.c_void_p), ('cand_status', ctypes.c_void_p), ('best', ctypes.c_void_p),
@@ -229,6 +235,7 @@ EXPORTS = ['tsf_create', 'tsf_destroy', 'tsf_last_error', 'tsf_device_count', 't
            'tsf_reconcile_shares', 'tsf_reconcile_out_size', 'tsf_rollup_set_totals', 'tsf_rollup_reconcile', 'tsf_rollup_reconciled_totals',
            'tsf_reconcile_tree_shares', 'tsf_rollup_set_tree', 'tsf_rollup_set_node_totals', 'tsf_rollup_solve_tree',
            'tsf_rollup_reconcile_tree', 'tsf_rollup_tree_totals',
+           'tsf_temporal_shares', 'tsf_temporal_out_size', 'tsf_predict_temporal',
            'tsf_corr_args_size', 'tsf_corr_out_size', 'tsf_residual_corr', 'tsf_residual_corr_dev', 'tsf_rollup_set_noise_corr',
            'tsf_ar_args_size', 'tsf_ar_out_size', 'tsf_residual_autocorr', 'tsf_residual_autocorr_dev', 'tsf_set_noise_ar',
            'tsf_cond_columns', 'tsf_cond_columns_dev',
@@ -347,6 +354,10 @@ def load():
     L.tsf_rollup_solve_tree.argtypes = [vp, vp, vp]
     L.tsf_rollup_reconcile_tree.argtypes = L.tsf_rollup_reconcile.argtypes
     L.tsf_rollup_tree_totals.argtypes = [vp, i32, i64, i64, i32, vp, ctypes.POINTER(TsfRollupOut)]
+    L.tsf_temporal_shares.argtypes = [i64, i32, i32, vp, vp, vp, vp, vp, vp]
+    model = [psp, i64, i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]        # (the period model's: K without N)
+    L.tsf_predict_temporal.argtypes = [vp] + model + model[:1] + model[2:] + [i32, u64, vp, vp, vp, vp, i32, vp,
+                                                                               ctypes.POINTER(TsfTemporalOut)]
     L.tsf_residual_corr.argtypes = [vp, i64, i32, vp, i32, vp, vp, i64, ctypes.POINTER(TsfCorrArgs), ctypes.POINTER(TsfCorrOut)]
     L.tsf_residual_corr_dev.argtypes = L.tsf_residual_corr.argtypes + [vp]
     L.tsf_rollup_set_noise_corr.argtypes = [vp, vp, vp]
@@ -437,6 +448,8 @@ def load():
         raise TsfError('tsf_window_out layout mismatch between _lib.py and libtsf_amd.so')
     if L.tsf_reconcile_out_size() != ctypes.sizeof(TsfReconcileOut):
         raise TsfError('tsf_reconcile_out layout mismatch between _lib.py and libtsf_amd.so')
+    if L.tsf_temporal_out_size() != ctypes.sizeof(TsfTemporalOut):
+        raise TsfError('tsf_temporal_out layout mismatch between _lib.py and libtsf_amd.so')
     if (L.tsf_screen_args_size() != ctypes.sizeof(TsfScreenArgs) or L.tsf_screen_out_size() != ctypes.sizeof(TsfScreenOut)
             or L.tsf_fit_screened_out_size() != ctypes.sizeof(TsfFitScreenedOut)):
         raise TsfError('tsf_screen_args / tsf_screen_out layout mismatch between _lib.py and libtsf_amd.so')

@@ -30,6 +30,7 @@
 #include "tsf_rollup_kernels.h"
 #include "tsf_reconcile_kernels.h"
 #include "tsf_tree_kernels.h"
+#include "tsf_temporal_kernels.h"
 #include "tsf_component_kernels.h"
 #include "tsf_fit_kernels.h"
 #include "tsf_quad_kernels.h"
@@ -1533,14 +1534,20 @@ struct ForecastUpload {
     }
 };
 
-// What every forecast starts with on the device: the spec built and checked against the inputs, then sent to the
-// context's copy in stream order.
-static int forecast_prologue(tsf_ctx *ctx, const tsf_spec *spec, const ForecastIn &f, hipStream_t st, DevSpec *hs)
+// The spec built and checked against the forecast's inputs (host work alone).
+static int forecast_spec(tsf_ctx *ctx, const tsf_spec *spec, const ForecastIn &f, DevSpec *hs)
 {
     int mode = 0;
     if (int rc = build_devspec(ctx, spec, hs, &mode)) return rc;
     if (hs->n_extra > 0 && !f.extra_future) return fail(ctx, "extra_future is NULL");
     if (hs->growth == TSF_GROWTH_LOGISTIC && !f.cap) return fail(ctx, "logistic growth needs cap");
+    return 0;
+}
+
+// What every forecast starts with on the device: forecast_spec, then the spec sent to the context's copy in stream order.
+static int forecast_prologue(tsf_ctx *ctx, const tsf_spec *spec, const ForecastIn &f, hipStream_t st, DevSpec *hs)
+{
+    if (int rc = forecast_spec(ctx, spec, f, hs)) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_spec, hs, sizeof(*hs), hipMemcpyHostToDevice, st));
     return 0;
 }
@@ -1755,6 +1762,56 @@ static int sort_width(int32_t n_samples)
     return NSP;
 }
 
+// One model's draw of a call: what is set up once (the spec, the launch arguments over the chunk's scratch) and what runs
+// per chunk (launch_predict for yhat and the three per-row pieces, then interval_sample_kernel).  draw_chunks runs one of
+// them over the context's scratch; tsf_predict_temporal runs two side by side, each chunk's daily and period draws.
+struct ModelDraw {
+    DevSpec hs;
+    PredictArgs p;
+    IntervalArgs a;
+    double *d_t, *d_xa, *d_opm;
+    bool tab_ready;
+
+    // the launch arguments: pieces [3][chunk][H] and the sample buffers `b` of a chunk; d_ar: the series' (phi, c) pairs
+    // on the device or null.  Nothing is launched.
+    void bind(const tsf_ctx *ctx, const tsf_spec *spec, const ForecastIn &f, const DrawSpec &d, const double *d_ar,
+              double *pieces, size_t nh, const DrawBufs &b)
+    {
+        d_t = pieces; d_xa = d_t + nh; d_opm = d_xa + nh;
+        p = predict_args(ctx, spec, f, d.yhat);
+        p.trend_out = d.trend_out;
+        p.t_out = d_t; p.xa_out = d_xa; p.opm_out = d_opm;
+        memset(&a, 0, sizeof(a));
+        a.sp = ctx->d_spec; a.H = f.H; a.theta_stride = tsf_theta_stride(spec); a.n_grids = f.n_grids; a.NS = d.n_samples;
+        a.theta = f.theta; a.y_scale = f.y_scale; a.grid = f.grid; a.floor_ = f.floor_; a.cap = f.cap;
+        a.series_key = f.series_key; a.seed = d.seed;
+        a.samples = b.samp; a.trend_samples = b.trend; a.cum_samples = b.cum;
+        a.noise_ar = d_ar;
+        tab_ready = false;
+    }
+    // the context's device spec (and with it a shared future grid's design table) made this model's, in stream order
+    int send_spec(tsf_ctx *ctx, hipStream_t st)
+    {
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_spec, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
+        tab_ready = false;
+        return 0;
+    }
+    // the series [n0, n0 + nc) of the call drawn into the chunk's scratch
+    int chunk(tsf_ctx *ctx, int64_t n0, int64_t nc, hipStream_t st)
+    {
+        // the point forecast of the chunk and its per-row pieces (chunk-local scratch: rows of series n0 + i at [i][H])
+        if (int prc = launch_predict(ctx, hs, p, n0, nc, &tab_ready, st)) return prc;
+        const int H = a.H;
+        a.n0 = n0; a.n_chunk = nc;
+        a.t = d_t - (size_t)n0 * H; a.xa = d_xa - (size_t)n0 * H; a.opm = d_opm - (size_t)n0 * H;
+        const dim3 sgrid((unsigned)nc, (unsigned)((a.NS + 255) / 256));
+        if (a.noise_ar) hipLaunchKernelGGL(interval_sample_kernel<true>, sgrid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(interval_sample_kernel<false>, sgrid, dim3(256), 0, st, a);
+        HIP_TRY(ctx, hipGetLastError());
+        return 0;
+    }
+};
+
 template <class After>
 static int draw_chunks(tsf_ctx *ctx, const tsf_spec *spec, const ForecastIn &f, const DrawSpec &d, hipStream_t st,
                        After &&after)
@@ -1763,41 +1820,25 @@ static int draw_chunks(tsf_ctx *ctx, const tsf_spec *spec, const ForecastIn &f, 
         if (int rc = refuse_noise_ar(ctx, "this drawing entry")) return rc;
     const double *d_ar = nullptr;
     if (int rc = take_noise_ar(ctx, f.N, st, &d_ar)) return rc;
-    DevSpec hs;
-    if (int rc = forecast_prologue(ctx, spec, f, st, &hs)) return rc;
+    ModelDraw m;
+    if (int rc = forecast_spec(ctx, spec, f, &m.hs)) return rc;
+    if (int rc = m.send_spec(ctx, st)) return rc;
     const int64_t N = f.N;
     const int32_t H = f.H, n_samples = d.n_samples;
     const size_t n_buf = 1 + (size_t)d.want_cum + (size_t)d.want_trend;
     const int64_t chunk = draw_chunk_series(N, H, n_samples, n_buf);
     const size_t nh = (size_t)chunk * H;
     if (int rc = ensure_iv_ws(ctx, draw_scratch_bytes(chunk, H, n_samples, n_buf))) return rc;
-    double *d_t = (double *)ctx->iv_ws, *d_xa = d_t + nh, *d_opm = d_xa + nh, *d_samp = d_opm + nh;
+    double *d_samp = (double *)ctx->iv_ws + 3 * nh;
     double *d_next = d_samp + nh * n_samples;
     double *d_cum = nullptr, *d_tsamp = nullptr;
     if (d.want_cum) { d_cum = d_next; d_next += nh * n_samples; }
     if (d.want_trend) d_tsamp = d_next;
-    PredictArgs p = predict_args(ctx, spec, f, d.yhat);
-    p.trend_out = d.trend_out;
-    p.t_out = d_t; p.xa_out = d_xa; p.opm_out = d_opm;
-    IntervalArgs a;
-    memset(&a, 0, sizeof(a));
-    a.sp = ctx->d_spec; a.H = H; a.theta_stride = tsf_theta_stride(spec); a.n_grids = f.n_grids; a.NS = n_samples;
-    a.theta = f.theta; a.y_scale = f.y_scale; a.grid = f.grid; a.floor_ = f.floor_; a.cap = f.cap;
-    a.series_key = f.series_key; a.seed = d.seed;
-    a.samples = d_samp; a.trend_samples = d_tsamp; a.cum_samples = d_cum;
-    a.noise_ar = d_ar;
     const DrawBufs bufs = {d_samp, d_cum, d_tsamp};
-    bool tab_ready = false;
+    m.bind(ctx, spec, f, d, d_ar, (double *)ctx->iv_ws, nh, bufs);
     for (int64_t n0 = 0; n0 < N; n0 += chunk) {
         const int64_t nc = (N - n0 < chunk) ? N - n0 : chunk;
-        // the point forecast of the chunk and its per-row pieces (chunk-local scratch: rows of series n0 + i at [i][H])
-        if (int prc = launch_predict(ctx, hs, p, n0, nc, &tab_ready, st)) return prc;
-        a.n0 = n0; a.n_chunk = nc;
-        a.t = d_t - (size_t)n0 * H; a.xa = d_xa - (size_t)n0 * H; a.opm = d_opm - (size_t)n0 * H;
-        const dim3 sgrid((unsigned)nc, (unsigned)((n_samples + 255) / 256));
-        if (d_ar) hipLaunchKernelGGL(interval_sample_kernel<true>, sgrid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(interval_sample_kernel<false>, sgrid, dim3(256), 0, st, a);
-        HIP_TRY(ctx, hipGetLastError());
+        if (int rc = m.chunk(ctx, n0, nc, st)) return rc;
         if (int arc = after(n0, nc, bufs)) return arc;
     }
     return 0;
@@ -3038,13 +3079,9 @@ static bool window_wants_draws(const tsf_window_out &o)
     return o.q || o.pit || o.crps || o.pinball || o.mean_crps || o.mean_pinball || o.coverage;
 }
 
-// What the three window entries check before anything is copied or launched: tsf_predict_quantiles' checks of the sample
-// count and the levels, the windows against H (they index the sample buffer), and what the outputs need.
-static int check_window_args(tsf_ctx *ctx, int32_t H, int32_t n_samples, int32_t n_q, const double *quantiles,
-                             const WindowCall &w, const tsf_window_out *out)
+// the windows of a call against H: they index the sample buffer
+static int check_windows(tsf_ctx *ctx, int32_t H, const WindowCall &w)
 {
-    if (!out) return fail(ctx, "NULL output (tsf_window_out is required)");
-    if (int rc = check_samples_and_levels(ctx, n_samples, n_q, quantiles)) return rc;
     if (w.K < 1 || w.K > TSF_MAX_WINDOWS) return fail(ctx, "K must be in [1, TSF_MAX_WINDOWS]");
     if (!w.win_start || !w.win_end) return fail(ctx, "NULL win_start or win_end");
     for (int32_t k = 0; k < w.K; ++k)
@@ -3054,6 +3091,17 @@ static int check_window_args(tsf_ctx *ctx, int32_t H, int32_t n_samples, int32_t
                      (int)w.win_start[k], (int)w.win_end[k], (int)H);
             return fail(ctx, msg);
         }
+    return 0;
+}
+
+// What the three window entries check before anything is copied or launched: tsf_predict_quantiles' checks of the sample
+// count and the levels, the windows against H, and what the outputs need.
+static int check_window_args(tsf_ctx *ctx, int32_t H, int32_t n_samples, int32_t n_q, const double *quantiles,
+                             const WindowCall &w, const tsf_window_out *out)
+{
+    if (!out) return fail(ctx, "NULL output (tsf_window_out is required)");
+    if (int rc = check_samples_and_levels(ctx, n_samples, n_q, quantiles)) return rc;
+    if (int rc = check_windows(ctx, H, w)) return rc;
     const bool want_q = out->q || out->pinball || out->mean_pinball || out->coverage;
     const bool want_score = out->pit || out->crps || out->pinball || out->n_obs || out->mean_crps || out->mean_pinball ||
                             out->coverage;
@@ -3817,6 +3865,231 @@ extern "C" int tsf_rollup_tree_totals(tsf_rollup *r, int32_t level, int64_t node
         return 0;
     };
     return cells_read(r, nullptr, n_nodes, n_q, quantiles, *out, &make, outs);
+}
+
+// ---- temporal reconciliation: daily forecasts and fitted period totals made coherent ------------------------
+
+extern "C" int tsf_temporal_out_size(void) { return (int)sizeof(tsf_temporal_out); }
+
+// No row in two windows (the windows have passed check_windows).  ctx may be null (tsf_temporal_shares has none).
+static int check_disjoint_windows(tsf_ctx *ctx, int32_t H, const WindowCall &w)
+{
+    std::vector<int32_t> owner((size_t)H, -1);
+    for (int32_t k = 0; k < w.K; ++k)
+        for (int32_t h = w.win_start[k]; h < w.win_end[k]; ++h) {
+            if (owner[(size_t)h] >= 0) {
+                char msg[160];
+                snprintf(msg, sizeof(msg), "windows %d and %d overlap at row %d: a row would get two corrections",
+                         (int)owner[(size_t)h], (int)k, (int)h);
+                return fail(ctx, msg);
+            }
+            owner[(size_t)h] = k;
+        }
+    return 0;
+}
+
+extern "C" int tsf_temporal_shares(int64_t N, int32_t H, int32_t K, const int32_t *win_start, const int32_t *win_end,
+                                   const double *w, const double *v, double *share, double *share_total)
+{
+    if (N < 0 || H < 1 || (N > 0 && (!v || !share || !share_total))) return -1;
+    const WindowCall wc = {K, win_start, win_end, nullptr};
+    try {
+        if (check_windows(nullptr, H, wc) || check_disjoint_windows(nullptr, H, wc)) return -1;
+    } catch (const std::bad_alloc &) {
+        return -1;
+    }
+    const size_t nh = (size_t)N * H, nk = (size_t)N * K;
+    for (size_t i = 0; w && i < nh; ++i)
+        if (!(w[i] > 0.0 && std::isfinite(w[i]))) return -1;
+    for (size_t i = 0; i < nk; ++i)
+        if (!std::isnan(v[i]) && !(v[i] > 0.0 && std::isfinite(v[i]))) return -1;
+    for (int64_t n = 0; n < N; ++n) {
+        const double *wn = w ? w + (size_t)n * H : nullptr;
+        double *sh = share + (size_t)n * H;
+        for (int32_t h = 0; h < H; ++h) sh[h] = 0.0;
+        for (int32_t k = 0; k < K; ++k) {
+            const double vk = v[(size_t)n * K + k];
+            double *mu = share_total + (size_t)n * K + k;
+            if (std::isnan(vk)) { *mu = vk; continue; }
+            double W = 0.0;
+            for (int32_t h = win_start[k]; h < win_end[k]; ++h) W = W + (wn ? wn[h] : 1.0);
+            const double D = vk + W;
+            for (int32_t h = win_start[k]; h < win_end[k]; ++h) sh[h] = (wn ? wn[h] : 1.0) / D;
+            *mu = W / D;
+        }
+    }
+    return 0;
+}
+
+// phi [N] in [0, 1) -> the (phi, sqrt(1 - phi^2)) pairs interval_sample_kernel<true> reads (tsf_set_noise_ar's)
+static int noise_ar_pairs(tsf_ctx *ctx, const char *name, const double *phi, int64_t N, std::vector<double> *pairs)
+{
+    pairs->clear();
+    if (!phi) return 0;
+    for (int64_t i = 0; i < N; ++i)
+        if (!(phi[i] >= 0.0 && phi[i] < 1.0)) {                     // (NaN fails both comparisons)
+            char msg[120];
+            snprintf(msg, sizeof(msg), "%s[%lld] = %g: an autocorrelation must be in [0, 1)", name, (long long)i, phi[i]);
+            return fail(ctx, msg);
+        }
+    pairs->resize(2 * (size_t)N);
+    for (int64_t i = 0; i < N; ++i) {
+        (*pairs)[2 * (size_t)i] = phi[i];
+        (*pairs)[2 * (size_t)i + 1] = std::sqrt(1.0 - phi[i] * phi[i]);
+    }
+    return 0;
+}
+
+// series per chunk of tsf_predict_temporal: the daily model's n_buf sample buffers [H][n_samples], the period model's
+// one [K][n_samples] and the three per-row pieces of both within 512 MB
+static int64_t temporal_chunk_series(int64_t N, int32_t H, int32_t K, int32_t n_samples, size_t n_buf)
+{
+    const size_t per_series = 8 * ((size_t)H * (3 + n_buf * (size_t)n_samples) + (size_t)K * (3 + (size_t)n_samples));
+    int64_t chunk = (int64_t)(((size_t)512 << 20) / per_series);
+    if (chunk < 1) chunk = 1;
+    if (chunk > N) chunk = N;
+    return chunk;
+}
+
+// What tsf_predict_temporal refuses of its own arguments (the forecasts' inputs are checked by the entry), before
+// anything is copied or launched.
+static int check_temporal_args(tsf_ctx *ctx, int64_t N, int32_t H, int32_t K, int32_t n_samples, const int32_t *win_start,
+                               const int32_t *win_end, const double *share, const double *share_total, int32_t n_q,
+                               const double *quantiles, const tsf_temporal_out *out)
+{
+    if (!out || !out->yhat) return fail(ctx, "NULL output (tsf_temporal_out and its yhat are required)");
+    if (int rc = check_samples_and_levels(ctx, n_samples, n_q, quantiles)) return rc;
+    const WindowCall wc = {K, win_start, win_end, nullptr};
+    if (int rc = check_windows(ctx, H, wc)) return rc;
+    if (int rc = check_disjoint_windows(ctx, H, wc)) return rc;
+    if (!share || !share_total) return fail(ctx, "NULL share or share_total");
+    if (int rc = check_shares(ctx, "share", share, N * H)) return rc;
+    const size_t nk = (size_t)N * K;
+    for (size_t i = 0; i < nk; ++i)
+        if (!std::isnan(share_total[i]) && !(share_total[i] >= 0.0 && share_total[i] <= 1.0)) {
+            char msg[160];
+            snprintf(msg, sizeof(msg), "share_total[%lld][%d] = %g: a share must be in [0, 1] (NaN: the window is not reconciled)",
+                     (long long)(i / K), (int)(i % K), share_total[i]);
+            return fail(ctx, msg);
+        }
+    const bool want_q = out->q || out->cum_q || out->win_q;
+    if (!want_q && !out->samples && !out->win_samples)
+        return fail(ctx, "nothing requested but yhat and total: q, cum_q, win_q, samples and win_samples are all NULL");
+    if (n_q == 0 && want_q) return fail(ctx, "n_q = 0 with a quantile output requested");
+    return 0;
+}
+
+extern "C" int tsf_predict_temporal(tsf_ctx *ctx,
+                                    const tsf_spec *spec, int64_t N, int32_t H, const double *theta, const double *y_scale,
+                                    const tsf_grid_info *grid, int32_t n_grids, const int64_t *ds_future,
+                                    int32_t shared_future, const double *floor_, const double *cap,
+                                    const double *extra_future, const int64_t *series_key, const double *noise_ar,
+                                    const tsf_spec *spec_p, int32_t K, const double *theta_p, const double *y_scale_p,
+                                    const tsf_grid_info *grid_p, int32_t n_grids_p, const int64_t *ds_period,
+                                    int32_t shared_period, const double *floor_p, const double *cap_p,
+                                    const double *extra_period, const int64_t *period_key, const double *noise_ar_p,
+                                    int32_t n_samples, uint64_t seed, const int32_t *win_start, const int32_t *win_end,
+                                    const double *share, const double *share_total, int32_t n_q, const double *quantiles,
+                                    tsf_temporal_out *out)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (N < 0) return fail(ctx, "N must be >= 0");
+    if (N == 0) return 0;
+    if (K < 1 || K > TSF_MAX_WINDOWS) return fail(ctx, "K must be in [1, TSF_MAX_WINDOWS]");
+    const ForecastIn h = {N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap, extra_future, series_key};
+    const ForecastIn hp = {N, K, theta_p, y_scale_p, grid_p, n_grids_p, ds_period, shared_period, floor_p, cap_p, extra_period,
+                           period_key};
+    if (int rc = check_forecast_in(ctx, h, spec != nullptr)) return rc;
+    if (int rc = check_forecast_in(ctx, hp, spec_p != nullptr)) return rc;
+    if (!series_key || !period_key)
+        return fail(ctx, "series_key and period_key are required: the index-in-call default would give both models the same streams");
+    if (int rc = check_grids(ctx, spec, grid, n_grids)) return rc;
+    if (int rc = check_grids(ctx, spec_p, grid_p, n_grids_p)) return rc;
+    ModelDraw day, per;
+    std::vector<double> ar, ar_p;
+    try {
+        if (int rc = check_temporal_args(ctx, N, H, K, n_samples, win_start, win_end, share, share_total, n_q, quantiles, out))
+            return rc;
+        if (int rc = noise_ar_pairs(ctx, "noise_ar", noise_ar, N, &ar)) return rc;
+        if (int rc = noise_ar_pairs(ctx, "noise_ar_p", noise_ar_p, N, &ar_p)) return rc;
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, "tsf_predict_temporal: out of host memory");
+    }
+    if (int rc = forecast_spec(ctx, spec, h, &day.hs)) return rc;
+    if (int rc = forecast_spec(ctx, spec_p, hp, &per.hs)) return rc;
+
+    // both models' inputs, the shares, the windows and the AR pairs onto the device; the [N][.]-sized outputs there
+    ForecastUpload up, up_p;
+    if (int rc = up.upload(ctx, spec, h)) return rc;
+    if (int rc = up_p.upload(ctx, spec_p, hp)) return rc;
+    const size_t nh = (size_t)N * H, nk = (size_t)N * K;
+    DevBuf d_share, d_mu, d_win, d_ar, d_ar_p, d_yp;
+    HIP_TRY(ctx, d_share.put(share, 8 * nh));
+    HIP_TRY(ctx, d_mu.put(share_total, 8 * nk));
+    HIP_TRY(ctx, d_win.alloc(8 * (size_t)K));
+    int32_t *d_w0 = d_win.as<int32_t>(), *d_w1 = d_w0 + K;
+    HIP_TRY(ctx, hipMemcpy(d_w0, win_start, 4 * (size_t)K, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(d_w1, win_end, 4 * (size_t)K, hipMemcpyHostToDevice));
+    if (!ar.empty()) HIP_TRY(ctx, d_ar.put(ar.data(), 8 * ar.size()));
+    if (!ar_p.empty()) HIP_TRY(ctx, d_ar_p.put(ar_p.data(), 8 * ar_p.size()));
+    HIP_TRY(ctx, d_yp.alloc(8 * nk));
+    HostOuts outs;
+    double *d_yh = outs.want(out->yhat, 8 * nh);
+    double *d_q = outs.want(out->q, 8 * nh * (size_t)n_q), *d_cq = outs.want(out->cum_q, 8 * nh * (size_t)n_q);
+    double *d_tot = outs.want(out->total, 8 * nk), *d_wq = outs.want(out->win_q, 8 * nk * (size_t)n_q);
+    if (int rc = outs.ready(ctx)) return rc;
+
+    // the chunk's scratch: the per-row pieces of both models, the daily buffer, the running sums with cum_q, the period buffer
+    const size_t NS = (size_t)n_samples, n_buf = out->cum_q ? 2 : 1;
+    const int64_t chunk = temporal_chunk_series(N, H, K, n_samples, n_buf);
+    const size_t ch = (size_t)chunk * H, ck = (size_t)chunk * K;
+    if (int rc = ensure_iv_ws(ctx, 8 * (ch * (3 + n_buf * NS) + ck * (3 + NS)))) return rc;
+    double *d_pieces = (double *)ctx->iv_ws, *d_pieces_p = d_pieces + 3 * ch;
+    double *d_samp = d_pieces_p + 3 * ck, *d_cum = out->cum_q ? d_samp + ch * NS : nullptr;
+    double *d_psamp = d_samp + n_buf * ch * NS;
+    hipStream_t st = nullptr;
+    const DrawSpec dd = {n_samples, seed, false, false, d_yh, nullptr, false};
+    const DrawSpec dp = {n_samples, seed, false, false, d_yp.as<double>(), nullptr, false};
+    day.bind(ctx, spec, up.dev, dd, ar.empty() ? nullptr : d_ar.as<double>(), d_pieces, ch, {d_samp, nullptr, nullptr});
+    per.bind(ctx, spec_p, up_p.dev, dp, ar_p.empty() ? nullptr : d_ar_p.as<double>(), d_pieces_p, ck, {d_psamp, nullptr, nullptr});
+    const QuantilePass qp(H, n_samples, n_q, quantiles), qpw(K, n_samples, n_q, quantiles);
+    TemporalArgs t;
+    memset(&t, 0, sizeof(t));
+    t.samp = d_samp; t.win = d_psamp; t.w0 = d_w0; t.w1 = d_w1; t.H = H; t.K = K; t.NS = n_samples;
+    for (int64_t n0 = 0; n0 < N; n0 += chunk) {
+        const int64_t nc = std::min(chunk, N - n0);
+        // (the context has one device spec and one future design table: each model's are sent ahead of its draw)
+        if (int rc = day.send_spec(ctx, st)) return rc;
+        if (int rc = day.chunk(ctx, n0, nc, st)) return rc;
+        if (int rc = per.send_spec(ctx, st)) return rc;
+        if (int rc = per.chunk(ctx, n0, nc, st)) return rc;
+        t.share = d_share.as<double>() + (size_t)n0 * H; t.share_total = d_mu.as<double>() + (size_t)n0 * K;
+        hipLaunchKernelGGL(temporal_reconcile_kernel, dim3((unsigned)(nc * K), (unsigned)((n_samples + 255) / 256)), dim3(256),
+                           0, st, t);
+        HIP_TRY(ctx, hipGetLastError());
+        if (d_cum) {
+            hipLaunchKernelGGL(rollup_cumsum_kernel, dim3((unsigned)((nc * n_samples + 255) / 256)), dim3(256), 0, st, d_samp,
+                               d_cum, nc, H, n_samples);
+            HIP_TRY(ctx, hipGetLastError());
+        }
+        if (d_q) if (int rc = qp.launch(ctx, d_samp, d_q, n0, nc, st)) return rc;
+        if (d_cq) if (int rc = qp.launch(ctx, d_cum, d_cq, n0, nc, st)) return rc;
+        if (d_wq) if (int rc = qpw.launch(ctx, d_psamp, d_wq, n0, nc, st)) return rc;
+        // the reconciled draws leave the scratch before the next chunk overwrites it (stream order)
+        if (out->samples)
+            HIP_TRY(ctx, hipMemcpyAsync(out->samples + (size_t)n0 * H * NS, d_samp, 8 * (size_t)nc * H * NS,
+                                        hipMemcpyDeviceToHost, st));
+        if (out->win_samples)
+            HIP_TRY(ctx, hipMemcpyAsync(out->win_samples + (size_t)n0 * K * NS, d_psamp, 8 * (size_t)nc * K * NS,
+                                        hipMemcpyDeviceToHost, st));
+    }
+    // the point forecasts of the whole call: yhat rewritten in place, total where wanted
+    hipLaunchKernelGGL(temporal_point_kernel, dim3((unsigned)((N * K + 255) / 256)), dim3(256), 0, st, d_yh,
+                       d_yp.as<double>(), d_w0, d_w1, d_share.as<double>(), d_mu.as<double>(), d_tot, N, H, K);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    return outs.fetch(ctx);
 }
 
 // ---- diagnostics --------------------------------------------------------------------------------

@@ -2160,6 +2160,224 @@ def predict_rollup(spec, theta, y_scale, grid, ds_future_ns, labels, quantiles, 
         return uniq, r.quantiles(quantiles, cumulative=cumulative)
 
 
+# ---- temporal reconciliation: daily forecasts and directly fitted period totals --------------------------------
+# Reconciliation along time inside each series (include/tsf.h "temporal reconciliation"): the rows of a daily forecast are
+# the members, the forecast of a model fitted on the weekly or monthly totals of the same history is the total, each
+# window of rows is a group.  period_history makes the histories to fit the period model on, temporal_shares the shares,
+# predict_temporal the coherent forecast of both.
+
+def _most_frequent_rows(windows):
+    """the row count most windows have (the larger one on a tie): what a complete period of the calendar holds"""
+    rows, counts = np.unique(windows.n_rows, return_counts=True)
+    return int(rows[np.flatnonzero(counts == counts.max())[-1]])
+
+
+def period_history(ds_ns, y, freq, full_rows=None):
+    """The history's totals over the calendar periods `freq` (period_windows) -> (ds_period [Tk], y_period [N][Tk],
+    windows): the panel to fit the period model on.  ds_ns [T] one shared calendar, y [N][T].  A period is kept only where
+    it has full_rows rows (None: the row count most periods have), so an incomplete first or last period and a period
+    with a missing day are left out rather than fitted as a low total; ds_period is each kept window's first timestamp,
+    windows the kept Windows over the T rows.  The totals are window_totals' (NaN where a row is NaN).  Host numpy."""
+    w = period_windows(ds_ns, freq)
+    y = np.asarray(y, dtype=np.float64)
+    if y.ndim != 2 or y.shape[1] != int(w.end.max()):
+        raise ValueError('period_history: y must be [N][T] on the calendar ds [T]')
+    full = _most_frequent_rows(w) if full_rows is None else int(full_rows)
+    keep = np.flatnonzero(w.n_rows == full)
+    if len(keep) == 0:
+        raise ValueError('period_history: no period has %d rows' % full)
+    kept = Windows(w.start[keep], w.end[keep], w.label_ns[keep])
+    return kept.label_ns.copy(), window_totals(y, kept), kept
+
+
+class TemporalShares(object):
+    """What temporal_shares returns: windows (K of them), share [N][H], share_total [N][K] (NaN: the window is not
+    reconciled for that series)."""
+
+    def __init__(self, windows, share, share_total):
+        self.windows, self.share, self.share_total = windows, share, share_total
+
+
+def _disjoint(windows, H):
+    """ValueError where two windows share a row"""
+    windows.check(H)
+    cover = np.zeros(H + 1, dtype=np.int64)
+    np.add.at(cover, windows.start, 1)
+    np.add.at(cover, windows.end, -1)
+    if (np.cumsum(cover) > 1).any():
+        raise ValueError('windows: two windows share a row (temporal reconciliation needs disjoint windows)')
+
+
+def temporal_shares(windows, N, H, weight=None, period_weight='struct', active=None):
+    """Weights -> TemporalShares for predict_temporal: a thin binding of tsf_temporal_shares (host only).  weight: the
+    forecast error variances of the rows, [H] or [N][H] (None: all 1).  period_weight: the period forecasts' -- 'struct'
+    (the window's row count: a period total is as uncertain as its rows together), 'ols' (all 1) or an array [K] or
+    [N][K].  active [K] or [N][K] bool: the windows to reconcile (None: those with the row count most windows have, so
+    that a partial first or last week of the horizon is left as it is).  share = w / (v + W), share_total = W / (v + W),
+    W the window's sum of w; a window that is not active gets share 0 and share_total NaN."""
+    if not isinstance(windows, Windows):
+        raise ValueError('windows must be a Windows (row_windows, period_windows)')
+    N, H, K = int(N), int(H), len(windows)
+    if N < 0 or H < 1:
+        raise ValueError('N must be >= 0 and H >= 1')
+    _disjoint(windows, H)
+    w = None
+    if weight is not None:
+        w = np.asarray(weight, dtype=np.float64)
+        if w.shape not in ((H,), (N, H)):
+            raise ValueError('weight must be [H] or [N][H]')
+        if not (np.isfinite(w).all() and (w > 0).all()):
+            raise ValueError('weight values must be finite and positive')
+        w = np.ascontiguousarray(np.broadcast_to(w, (N, H)))
+    if isinstance(period_weight, str):
+        if period_weight == 'struct':
+            v = windows.n_rows.astype(np.float64)
+        elif period_weight == 'ols':
+            v = np.ones(K)
+        else:
+            raise ValueError("period_weight must be 'struct', 'ols' or an array [K] or [N][K]")
+    else:
+        v = np.asarray(period_weight, dtype=np.float64)
+        if v.shape not in ((K,), (N, K)):
+            raise ValueError('period_weight must be [K] or [N][K]')
+        if not ((np.isfinite(v) & (v > 0)) | np.isnan(v)).all():
+            raise ValueError('period_weight values must be finite and positive (NaN: the window is not reconciled)')
+    v = np.array(np.broadcast_to(v, (N, K)), dtype=np.float64, order='C')
+    if active is None:
+        act = windows.n_rows == _most_frequent_rows(windows)
+    else:
+        act = np.asarray(active)
+        if act.dtype != np.bool_ or act.shape not in ((K,), (N, K)):
+            raise ValueError('active must be bool [K] or [N][K]')
+    v[~np.broadcast_to(act, (N, K))] = np.nan
+    share, share_total = np.zeros((N, H)), np.zeros((N, K))
+    rc = _lib.load().tsf_temporal_shares(N, H, K, windows.start.ctypes.data, windows.end.ctypes.data, _lib._ptr(w),
+                                         v.ctypes.data if N else None, share.ctypes.data if N else None,
+                                         share_total.ctypes.data if N else None)
+    if rc != 0:
+        raise _lib.TsfError('tsf_temporal_shares refused its arguments (%d)' % rc)
+    return TemporalShares(windows, share, share_total)
+
+
+TEMPORAL_FIELDS = ('q', 'cum_q', 'total', 'win_q', 'samples', 'win_samples')
+
+
+class TemporalQuantiles(Quantiles):
+    """What predict_temporal returns: a Quantiles of the reconciled rows (yhat [N][H]; quantiles [Q]; q, cum_q [N][Q][H]
+    or None) with ds (the daily calendar), windows (K of them), total [N][K] (the reconciled point forecast of every
+    window's total), win_q [N][Q][K] (the quantiles of the reconciled window totals), and samples [N][H][S], win_samples
+    [N][K][S] or None."""
+
+    def __init__(self, windows, ds, yhat, quantiles, q, cum_q=None, total=None, win_q=None, samples=None, win_samples=None):
+        Quantiles.__init__(self, yhat, quantiles, q, cum_q)
+        self.windows, self.ds, self.total, self.win_q = windows, ds, total, win_q
+        self.samples, self.win_samples = samples, win_samples
+
+    def frame(self, n):
+        """The rows of series n in Quantiles.frame's layout: ds, yhat, yhat_q<..>, yhat_cum_q<..>."""
+        return Quantiles.frame(self, n, self.ds if self.ds.ndim == 1 else self.ds[n])
+
+    def window_frame(self, n):
+        """The periods of series n in WindowQuantiles.frame's layout, one row per window."""
+        return WindowQuantiles(self.windows, self.ds, self.yhat, self.quantiles, total=self.total, q=self.win_q).frame(n)
+
+
+def _temporal_phi(noise_ar, N, ds_ns, name):
+    """_noise_ar_phi with the temporal entry's range: phi in [0, 1)"""
+    phi = _noise_ar_phi(noise_ar, N, ds_ns)
+    if phi is not None and (phi < 0).any():
+        raise ValueError('%s values must be in [0, 1)' % name)
+    return phi
+
+
+def _predict_temporal_call(spec, theta, y_scale, grid, ds_ns, windows, period_spec, period_theta, period_y_scale,
+                           period_grid, ds_period_ns, shares, levels, series_key, period_key, want, floor=None, cap=None,
+                           extra_future=None, period_floor=None, period_cap=None, period_extra_future=None, noise_ar=None,
+                           period_noise_ar=None, uncertainty_samples=1000, seed=0, ctx=None):
+    """One tsf_predict_temporal call -> dict of yhat and the outputs named in `want` (TEMPORAL_FIELDS).  Every
+    argument-shape error is raised before the library is loaded."""
+    theta, N, y_scale, grid, ds_ns, shared, H, floor, cap, ex, key = _checked_forecast_inputs(
+        spec, theta, y_scale, grid, ds_ns, floor, cap, extra_future, series_key)
+    if not isinstance(windows, Windows):
+        raise ValueError('windows must be a Windows (row_windows, period_windows)')
+    _disjoint(windows, H)
+    K = len(windows)
+    ptheta, Np, py_scale, pgrid, ds_p, pshared, Hp, pfloor, pcap, pex, pkey = _checked_forecast_inputs(
+        period_spec, period_theta, period_y_scale, period_grid, ds_period_ns, period_floor, period_cap,
+        period_extra_future, period_key)
+    if Np != N:
+        raise ValueError('period_theta must be [N][stride]: one period model per series')
+    if Hp != K:
+        raise ValueError('ds_period must be [K] or [N][K]: one row per window (K = %d, got %d)' % (K, Hp))
+    if key is None or pkey is None:
+        raise ValueError('series_key and period_key are required')
+    if not isinstance(shares, TemporalShares):
+        raise ValueError('shares must be a TemporalShares (temporal_shares)')
+    share = np.ascontiguousarray(shares.share, dtype=np.float64)
+    share_total = np.ascontiguousarray(shares.share_total, dtype=np.float64)
+    if share.shape != (N, H) or share_total.shape != (N, K):
+        raise ValueError('shares must hold share [N][H] = %r and share_total [N][K] = %r' % ((N, H), (N, K)))
+    levels = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
+    quantile_columns(levels)            # (ValueError for a bad level, two levels of one name, too many)
+    Q, S = len(levels), int(uncertainty_samples)
+    unknown = set(want) - set(TEMPORAL_FIELDS)
+    if unknown:
+        raise ValueError('unknown outputs %s' % sorted(unknown))
+    if not set(want) - {'total'}:
+        raise ValueError('no output wanted but yhat and total')
+    if not Q and set(want) & {'q', 'cum_q', 'win_q'}:
+        raise ValueError('q, cum_q and win_q need quantile levels')
+    if not 2 <= S <= 4096:
+        raise ValueError('uncertainty_samples must be in [2, 4096]')
+    phi = _temporal_phi(noise_ar, N, ds_ns, 'noise_ar')
+    pphi = _temporal_phi(period_noise_ar, N, ds_p, 'period_noise_ar')
+    shapes = {'q': (N, Q, H), 'cum_q': (N, Q, H), 'total': (N, K), 'win_q': (N, Q, K), 'samples': (N, H, S),
+              'win_samples': (N, K, S)}
+    res = {'yhat': np.zeros((N, H))}
+    res.update((k, np.zeros(shapes[k])) for k in want)
+    ctx = ctx or get_context()
+    L = _lib.load()
+    cs, cps = spec.to_c(), period_spec.to_c()
+    out = _lib.TsfTemporalOut(**{k: v.ctypes.data for k, v in res.items()})
+    rc = L.tsf_predict_temporal(
+        ctx.handle,
+        ctypes.byref(cs), N, H, theta.ctypes.data, y_scale.ctypes.data, grid.ctypes.data, len(grid), ds_ns.ctypes.data,
+        int(shared), _lib._ptr(floor), _lib._ptr(cap), _lib._ptr(ex), key.ctypes.data, _lib._ptr(phi),
+        ctypes.byref(cps), K, ptheta.ctypes.data, py_scale.ctypes.data, pgrid.ctypes.data, len(pgrid), ds_p.ctypes.data,
+        int(pshared), _lib._ptr(pfloor), _lib._ptr(pcap), _lib._ptr(pex), pkey.ctypes.data, _lib._ptr(pphi),
+        S, int(seed), windows.start.ctypes.data, windows.end.ctypes.data, share.ctypes.data, share_total.ctypes.data, Q,
+        levels.ctypes.data if Q else None, ctypes.byref(out))
+    ctx.check(rc)
+    return res
+
+
+def predict_temporal(spec, theta, y_scale, grid, ds_future_ns, windows, period_spec, period_theta, period_y_scale,
+                     period_grid, ds_period_ns, shares, quantiles, series_key, period_key, cumulative=False, samples=False,
+                     floor=None, cap=None, extra_future=None, period_floor=None, period_cap=None,
+                     period_extra_future=None, noise_ar=None, period_noise_ar=None, uncertainty_samples=1000, seed=0,
+                     ctx=None):
+    """The daily forecast of every series and the forecast of its period model made coherent -> TemporalQuantiles
+    (include/tsf.h tsf_predict_temporal).  The first five arguments are the daily model as in predict_quantiles; windows
+    (period_windows(ds_future_ns, 'W'), ...) are disjoint row windows of its H rows; period_spec ... ds_period_ns are the
+    model fitted on the period totals (period_history) and its K future rows, one per window (windows.label_ns);
+    shares: temporal_shares(windows, N, H, ...).  Sample by sample the incoherence d = period draw - the window's sum of
+    daily draws is shared out: row + share * d, total + share_total * d, so the reconciled rows of a window sum to the
+    reconciled total, and q, cum_q (with cumulative) and win_q are quantiles of coherent draws.  series_key and
+    period_key [N] are both required and should not share a value (the two models' streams would be shared).  With
+    samples, the reconciled draws [N][H][S] and window totals [N][K][S] are returned as well."""
+    levels = np.array(quantiles, dtype=np.float64).reshape(-1)
+    if len(levels) == 0:
+        raise ValueError('at least one quantile level')
+    want = ['q', 'total', 'win_q'] + (['cum_q'] if cumulative else []) + (['samples', 'win_samples'] if samples else [])
+    r = _predict_temporal_call(spec, theta, y_scale, grid, ds_future_ns, windows, period_spec, period_theta, period_y_scale,
+                               period_grid, ds_period_ns, shares, levels, series_key, period_key, want, floor=floor,
+                               cap=cap, extra_future=extra_future, period_floor=period_floor, period_cap=period_cap,
+                               period_extra_future=period_extra_future, noise_ar=noise_ar,
+                               period_noise_ar=period_noise_ar, uncertainty_samples=uncertainty_samples, seed=seed, ctx=ctx)
+    return TemporalQuantiles(windows, np.ascontiguousarray(ds_future_ns, dtype=np.int64), r['yhat'], levels, r['q'],
+                             r.get('cum_q'), r['total'], r['win_q'], r.get('samples'), r.get('win_samples'))
+
+
 # ---- diagnostics used by the parity tests -----------------------------------------------------
 
 def eval_aligned(spec, ds_ns, y, theta, floor=None, cap=None, extra=None, ctx=None):
