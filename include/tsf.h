@@ -1241,6 +1241,63 @@ int tsf_tune(tsf_ctx *ctx, const tsf_spec *base, const tsf_spec *cand, int32_t C
              const double *cap, const double *extra, const tsf_cv_args *cv, int32_t metric, int32_t refit,
              tsf_tune_out *out);
 
+/* ---- model-structure selection by cross-validation ---------------------------------------------
+ * tsf_tune's recipe over candidates that differ in STRUCTURE: Prophet's documented hyperparameter search lists
+ * seasonality_mode among the parameters to tune and changepoint_range as worth trying, and a panel raises the same
+ * question for growth, the number of changepoints and the seasonality set.  One call scores every candidate for every
+ * series, chooses per series, and refits each series with its choice.  tsf_tune and its contract are unchanged.
+ *
+ * Candidates: cand[0 .. C), 1 <= C <= TSF_TUNE_MAX_CAND; there is no base spec.  They may differ in growth,
+ *   n_changepoints, changepoint_range, changepoints_specified and the dates, the whole seasonality set (n_seas, periods,
+ *   orders, modes, prior scales), extra_mode, extra_prior_scale and changepoint_prior_scale.  They must agree in n_extra
+ *   (the call has one `extra` array, and its columns are every candidate's) and in every optimiser field (max_iter,
+ *   history, init_alpha, tol_*, eval_form, recenter_*, algorithm, residual_kernel, coop_after, converge, map_max_iter,
+ *   map_tol).  A logistic candidate without cap is refused, as is a prior scale that is not finite and > 0 and any spec
+ *   a fit call would refuse.  Every refusal happens before any launch and leaves the context usable.
+ * Score: score[n][c] / cand_status[n][c] = what tsf_cross_validate returns for cand[c] with rolling_window = 1 on the
+ *   same panel, floor, cap, extra and cutoffs -- the single metric row and the series status, bit for bit (NaN where the
+ *   series has no metric row).  metric: TSF_TUNE_MSE .. TSF_TUNE_MAPE; cv->rolling_window is ignored; no intervals.  The
+ *   plan reads no spec field and is made once; a candidate with specified changepoints keeps per fold the leading
+ *   dates <= the cutoff, its own table.
+ * Choice: m = the least finite score of the row; best[n] = the lowest c with a finite score and
+ *   score[n][c] <= m * (1.0 + tolerance) -- one add, one multiply, no fused multiply-add.  tolerance finite and >= 0;
+ *   tolerance = 0 is tsf_tune's first-minimum rule exactly.  Order the candidates from simple to complex and the choice
+ *   is the simplest one within the tolerance of the best: a model does not win on selection noise.  series_status[n]
+ *   as tsf_tune's: the plan's status where it is not TSF_CV_OK (best -1), TSF_TUNE_NO_SCORE where no candidate has a
+ *   finite score (best -1), else TSF_CV_OK.  chosen[n] = best[n], or `fallback` (in [0, C)) where best[n] is -1: the
+ *   candidate the refit uses.
+ * Refit (refit = 1): every series fitted on its whole history with cand[chosen[n]], the optimiser rule applied per
+ *   series as in tsf_tune's refit.  The series' row of every fit output is what tsf_fit_aligned / tsf_fit_ragged gives
+ *   for that series with that spec, bit for bit.  theta rows have stride_max = tsf_select_stride(cand, C) doubles: the
+ *   first tsf_theta_stride(&cand[chosen[n]]) are the fit's, the rest +0.0.  grid, aligned panel: [C], grid[c] candidate
+ *   c's grid where at least one series with rows was refitted with it, all zero bytes otherwise; ragged panel: [N].  A
+ *   series without rows is left as tsf_tune's refit leaves it (status TSF_ST_TOO_FEW, everything else zero).
+ *   refit = 0: out->fit is not touched.
+ * Work shared by the candidates: the panel crosses to the device once; the holdout rows and the metric tables are made
+ *   once; the fold panel of each optimiser group is cut once per distinct grouping of the folds (with equal algorithm
+ *   the grouping differs only between candidates Newton takes, at most TSF_MAX_P parameters, and those it does not;
+ *   candidates with specified changepoints share a panel where they carry the same dates); the fold fit
+ *   outputs are allocated once at stride_max and read at each candidate's own stride.  tsf_last_tune_counts reports
+ *   the call's fold panels and fit launches, as for tsf_tune.
+ * Input as tsf_tune (host pointers).  Outputs (host): score / cand_status [N][C], best / chosen / series_status [N],
+ *   fit (refit = 1).  Pending cost hints are discarded.  tsf_select_stride returns -1 for cand NULL, C < 1 or an n_seas
+ *   out of range.  Timing: tools/bench_select.py; DESIGN.md 5r.
+ * Reference interface replaced: none. */
+typedef struct {
+    double *score;            /* [N][C] */
+    int32_t *cand_status;     /* [N][C] */
+    int32_t *best;            /* [N]  the rule's choice, -1: none */
+    int32_t *chosen;          /* [N]  best, or `fallback` where best is -1: the candidate the refit uses */
+    int32_t *series_status;   /* [N]  as tsf_tune's */
+    tsf_fit_out fit;          /* refit = 1: theta [N][stride_max], the others [N]; grid [C] aligned / [N] ragged */
+} tsf_select_out;
+int tsf_select_out_size(void);
+int tsf_select_stride(const tsf_spec *cand, int32_t C);   /* stride_max = max over c of tsf_theta_stride(&cand[c]) */
+int tsf_select(tsf_ctx *ctx, const tsf_spec *cand, int32_t C, int64_t N, int32_t T, const int64_t *offsets,
+               const int64_t *ds, const void *y, int32_t y_dtype, const double *floor, const double *cap,
+               const double *extra, const tsf_cv_args *cv, int32_t metric, double tolerance, int32_t fallback,
+               int32_t refit, tsf_select_out *out);
+
 /* ---- outlier screening: robust residual flags and refit ------------------------------------------------
  * One bad row -- a double-counted day, an outage, a unit mix-up -- bends the trend and the seasonality of its whole
  * series, and Prophet's documented remedy is to remove the rows and fit again.  tsf_screen_rows is that decision for

@@ -142,6 +142,12 @@ class TsfTuneOut(ctypes.Structure):
                 ('series_status', ctypes.c_void_p), ('fit', TsfFitOut)]
 
 
+class TsfSelectOut(ctypes.Structure):
+    """tsf_select_out (include/tsf.h)."""
+    _fields_ = [('score', ctypes.c_void_p), ('cand_status', ctypes.c_void_p), ('best', ctypes.c_void_p),
+                ('chosen', ctypes.c_void_p), ('series_status', ctypes.c_void_p), ('fit', TsfFitOut)]
+
+
 class TsfScreenArgs(ctypes.Structure):
     """tsf_screen_args (include/tsf.h)."""
     _fields_ = [('threshold', ctypes.c_double), ('max_share', ctypes.c_double), ('min_rows', ctypes.c_int32),
@@ -243,6 +249,7 @@ EXPORTS = ['tsf_create', 'tsf_destroy', 'tsf_last_error', 'tsf_device_count', 't
            'tsf_set_option', 'tsf_get_option', 'tsf_set_cost_hints', 'tsf_set_profiling', 'tsf_profile_read', 'tsf_last_fit_kernel_ms', 'tsf_last_fit_route',
            'tsf_fit_plan', 'tsf_fit_plan_info_size', 'tsf_fit_plan_error', 'tsf_last_fit_plan',
            'tsf_cv_plan', 'tsf_cross_validate', 'tsf_last_cv_grids', 'tsf_tune', 'tsf_last_tune_counts',
+           'tsf_select_out_size', 'tsf_select_stride', 'tsf_select',
            'tsf_screen_args_size', 'tsf_screen_out_size', 'tsf_fit_screened_out_size', 'tsf_screen_rows', 'tsf_screen_rows_dev',
            'tsf_fit_screened',
            'tsf_calib_args_size', 'tsf_calib_table_size', 'tsf_calibrate_rows', 'tsf_calibrate_rows_dev',
@@ -389,6 +396,9 @@ def load():
     L.tsf_tune.argtypes = [vp, psp, psp, i32, i64, i32, vp, vp, vp, i32, vp, vp, vp, ctypes.POINTER(TsfCvArgs), i32, i32,
                            ctypes.POINTER(TsfTuneOut)]
     L.tsf_last_tune_counts.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.tsf_select_stride.argtypes = [psp, i32]
+    L.tsf_select.argtypes = [vp, psp, i32, i64, i32, vp, vp, vp, i32, vp, vp, vp, ctypes.POINTER(TsfCvArgs), i32,
+                             ctypes.c_double, i32, i32, ctypes.POINTER(TsfSelectOut)]
     L.tsf_screen_rows.argtypes = [vp, i64, i32, vp, vp, i32, vp, vp, vp, ctypes.POINTER(TsfScreenArgs),
                                   ctypes.POINTER(TsfScreenOut)]
     L.tsf_screen_rows_dev.argtypes = L.tsf_screen_rows.argtypes + [vp]
@@ -459,6 +469,8 @@ def load():
         raise TsfError('tsf_corr_args / tsf_corr_out layout mismatch between _lib.py and libtsf_amd.so')
     if L.tsf_ar_args_size() != ctypes.sizeof(TsfArArgs) or L.tsf_ar_out_size() != ctypes.sizeof(TsfArOut):
         raise TsfError('tsf_ar_args / tsf_ar_out layout mismatch between _lib.py and libtsf_amd.so')
+    if L.tsf_select_out_size() != ctypes.sizeof(TsfSelectOut):
+        raise TsfError('tsf_select_out layout mismatch between _lib.py and libtsf_amd.so')
     if L.tsf_fit_plan_info_size() != ctypes.sizeof(TsfFitPlanInfo):
         raise TsfError('tsf_fit_plan_info layout mismatch between _lib.py and libtsf_amd.so')
     _lib = L

@@ -38,6 +38,7 @@
 #include "tsf_launch.h"
 #include "tsf_cv_kernels.h"
 #include "tsf_tune_kernels.h"
+#include "tsf_select_kernels.h"
 #include "tsf_screen_kernels.h"
 #include "tsf_calib_kernels.h"
 #include "tsf_corr_kernels.h"
@@ -4341,6 +4342,21 @@ static void cv_call_shape(const PanelIn &p, const tsf_spec *spec, CvCall *S)
     S->has_floor = p.floor_ != nullptr; S->has_cap = p.cap != nullptr;
 }
 
+// specified changepoints: per fold (cutoffs f_cut) the leading dates <= its cutoff -- what prophet_copy(m, cutoff) keeps,
+// changepoints[changepoints <= cutoff], a prefix of the sorted list; empty for a spec without specified dates
+static std::vector<int32_t> cv_fold_keep(const tsf_spec &spec, const std::vector<int64_t> &f_cut)
+{
+    std::vector<int32_t> keep;
+    if (!(spec.changepoints_specified == 1 && spec.n_changepoints >= 0 && spec.n_changepoints <= TSF_MAX_S)) return keep;
+    keep.resize(f_cut.size());
+    for (size_t f = 0; f < f_cut.size(); ++f) {
+        int32_t k = 0;
+        while (k < spec.n_changepoints && spec.changepoint_ns[k] <= f_cut[f]) ++k;
+        keep[f] = k;
+    }
+    return keep;
+}
+
 // the plan and the fold tables (host only)
 static void cv_plan_call(const PanelIn &p, const tsf_cv_args &a, const tsf_spec *spec, CvCall *S)
 {
@@ -4360,8 +4376,6 @@ static void cv_plan_call(const PanelIn &p, const tsf_cv_args &a, const tsf_spec 
     S->f_series.resize((size_t)F); S->f_c.resize((size_t)F);
     S->f_cut.resize((size_t)F); S->f_hist.resize((size_t)F); S->f_hold.resize((size_t)F); S->f_row0.resize((size_t)F);
     S->f_floor.resize(floor_ ? (size_t)F : 0); S->f_cap.resize(cap ? (size_t)F : 0);
-    const bool cp_spec = spec->changepoints_specified == 1 && spec->n_changepoints >= 0 && spec->n_changepoints <= TSF_MAX_S;
-    S->f_keep.resize(cp_spec ? (size_t)F : 0);
     for (int64_t n = 0; n < N; ++n) {
         int64_t r = S->rows_off[(size_t)n];
         for (size_t c = 0; c < S->plan[(size_t)n].size(); ++c) {
@@ -4371,17 +4385,12 @@ static void cv_plan_call(const PanelIn &p, const tsf_cv_args &a, const tsf_spec 
             S->f_cut[(size_t)f] = x.cutoff; S->f_hist[(size_t)f] = x.hist; S->f_hold[(size_t)f] = x.hold; S->f_row0[(size_t)f] = r;
             if (floor_) S->f_floor[(size_t)f] = floor_[n];
             if (cap) S->f_cap[(size_t)f] = cap[n];
-            if (cp_spec) {
-                // what prophet_copy(m, cutoff) keeps: changepoints[changepoints <= cutoff], a prefix of the sorted list
-                int32_t k = 0;
-                while (k < spec->n_changepoints && spec->changepoint_ns[k] <= x.cutoff) ++k;
-                S->f_keep[(size_t)f] = k;
-            }
             r += x.hold;
             if (x.hold > S->Hmax) S->Hmax = (int32_t)x.hold;
         }
         if ((int32_t)S->plan[(size_t)n].size() > S->C) S->C = (int32_t)S->plan[(size_t)n].size();
     }
+    S->f_keep = cv_fold_keep(*spec, S->f_cut);
 }
 
 // the caller's panel, once; the fold tables; the fold outputs in plan order
@@ -4894,6 +4903,17 @@ extern "C" int tsf_last_tune_counts(const tsf_ctx *ctx, int32_t *expand_launches
     return 0;
 }
 
+// every optimiser field of a and b equal (what tsf_select asks of its candidates beside n_extra)
+static bool same_optimiser(const tsf_spec &a, const tsf_spec &b)
+{
+    return a.max_iter == b.max_iter && a.history == b.history && a.init_alpha == b.init_alpha && a.tol_obj == b.tol_obj &&
+           a.tol_rel_obj == b.tol_rel_obj && a.tol_grad == b.tol_grad && a.tol_rel_grad == b.tol_rel_grad &&
+           a.tol_param == b.tol_param && a.eval_form == b.eval_form && a.recenter_every == b.recenter_every &&
+           a.recenter_ratio == b.recenter_ratio && a.algorithm == b.algorithm && a.residual_kernel == b.residual_kernel &&
+           a.coop_after == b.coop_after && a.converge == b.converge && a.map_max_iter == b.map_max_iter &&
+           a.map_tol == b.map_tol;
+}
+
 // every field of a and b equal except the prior scales (the columns' entries only)
 static bool same_but_prior_scales(const tsf_spec &a, const tsf_spec &b)
 {
@@ -4909,12 +4929,7 @@ static bool same_but_prior_scales(const tsf_spec &a, const tsf_spec &b)
             return false;
     for (int i = 0; i < a.n_extra; ++i)
         if (a.extra_mode[i] != b.extra_mode[i]) return false;
-    return a.max_iter == b.max_iter && a.history == b.history && a.init_alpha == b.init_alpha && a.tol_obj == b.tol_obj &&
-           a.tol_rel_obj == b.tol_rel_obj && a.tol_grad == b.tol_grad && a.tol_rel_grad == b.tol_rel_grad &&
-           a.tol_param == b.tol_param && a.eval_form == b.eval_form && a.recenter_every == b.recenter_every &&
-           a.recenter_ratio == b.recenter_ratio && a.algorithm == b.algorithm && a.residual_kernel == b.residual_kernel &&
-           a.coop_after == b.coop_after && a.converge == b.converge && a.map_max_iter == b.map_max_iter &&
-           a.map_tol == b.map_tol;
+    return same_optimiser(a, b);
 }
 
 static bool prior_scales_ok(const tsf_spec &s)
@@ -4957,9 +4972,19 @@ struct TuneScores {             // [N][C] scores and statuses, the plan's status
     DevBuf d_score, d_cst, d_pst, d_best, d_sstat;
 };
 
-// every candidate cross-validated: shared by all of them the holdout rows, the metric tables and the fold panel of
-// the rule's L-BFGS and Newton group; per candidate the fits, one predict, the metrics and its column of the scores
-static int tune_score_candidates(tsf_ctx *ctx, CvCall &S, const tsf_spec *base, const tsf_spec *cand, int32_t C, int32_t metric,
+// The fold panels of the rule's L-BFGS and Newton group, cut once for every candidate that groups the folds alike.
+struct FoldPanels {
+    bool cut = false;
+    OptimiserGroups g;
+    CvGroup E_l, E_n;
+};
+
+// every candidate cross-validated: shared by all of them the holdout rows and the metric tables; shared by those that
+// group the folds alike (tsf_tune: all; tsf_select: by newton_takes under TSF_ALGO_AUTO and by their specified
+// changepoints) the fold panel of the rule's L-BFGS and Newton group; per candidate the fits, one
+// predict, the metrics and its column of the scores.  S.fit holds rows of the widest candidate's stride; each
+// candidate's launches write and its predict reads them at its own (S.stride follows the candidate).
+static int tune_score_candidates(tsf_ctx *ctx, CvCall &S, const tsf_spec *cand, int32_t C, int32_t metric,
                                  double rolling_window, TuneScores *B)
 {
     const int64_t N = S.N, F = S.F;
@@ -4979,24 +5004,44 @@ static int tune_score_candidates(tsf_ctx *ctx, CvCall &S, const tsf_spec *base, 
     if (int rc = cv_holdout(ctx, S, nullptr, &H)) return rc;
     if (int rc = cv_metrics_setup(ctx, S, S.d_yh.as<double>(), nullptr, nullptr, rolling_window, &X)) return rc;
     const double *mval = X.d_mm.as<double>() + (size_t)metric * S.M;
-    const CvViews folds = cv_fold_views(S);
     const tsf_fit_out fit = S.fit.view();
-    const OptimiserGroups g = optimiser_groups(*base, nullptr, (size_t)F, S.f_hist.data());
-    CvGroup E_l, E_n;
-    if (int rc = cv_expand(ctx, S, folds, g.lbfgs, &E_l)) return rc;
-    if (int rc = cv_expand(ctx, S, folds, g.newton, &E_n)) return rc;
-    ctx->tune_expand += (E_l.G > 0) + (E_n.G > 0);
-    auto fit_group = [&](const tsf_spec &gs, const std::vector<int32_t> &gf, RuleLaunch which) -> int {
-        if (which != RULE_RETRY) return cv_fit(ctx, S, which == RULE_LBFGS ? E_l : E_n, gs, fit, &grids, &ctx->tune_fits);
-        CvGroup E_r;
-        if (int rc = cv_expand(ctx, S, folds, gf, &E_r)) return rc;
-        ctx->tune_expand += 1;
-        return cv_fit(ctx, S, E_r, gs, fit, &grids, &ctx->tune_fits);
+    // what the fold panels of a candidate depend on: bit 0, the rule hands its short folds to Newton; bit 1 and the
+    // list, its specified changepoints (the table kept per fold, cv_fold_keep, follows from them)
+    using PanelKey = std::pair<int, std::vector<int64_t>>;
+    auto key_of = [](const tsf_spec &s) {
+        PanelKey k(s.algorithm == TSF_ALGO_AUTO && newton_takes(s) ? 1 : 0, {});
+        if (s.changepoints_specified == 1 && s.n_changepoints >= 0 && s.n_changepoints <= TSF_MAX_S) {
+            k.first |= 2;
+            k.second.assign(s.changepoint_ns, s.changepoint_ns + s.n_changepoints);
+        }
+        return k;
     };
+    std::map<PanelKey, FoldPanels> panels;
+    std::map<PanelKey, int32_t> users;          // candidates still to come per key: a panel is freed after its last
+    for (int32_t c = 0; c < C; ++c) ++users[key_of(cand[c])];
     const double *pfl = S.has_floor ? H.d_ffl.as<double>() : nullptr, *pcap = S.has_cap ? H.d_fcap.as<double>() : nullptr;
     const double *pex = S.n_extra > 0 ? H.d_fex.as<double>() : nullptr;
     for (int32_t c = 0; c < C; ++c) {
-        if (int rc = fit_by_rule(ctx, cand[c], g, S.fit, fit_group)) return rc;
+        S.stride = tsf_theta_stride(&cand[c]);
+        S.f_keep = cv_fold_keep(cand[c], S.f_cut);
+        const CvViews folds = cv_fold_views(S);
+        const PanelKey key = key_of(cand[c]);
+        FoldPanels &P = panels[key];
+        if (!P.cut) {
+            P.g = optimiser_groups(cand[c], nullptr, (size_t)F, S.f_hist.data());
+            if (int rc = cv_expand(ctx, S, folds, P.g.lbfgs, &P.E_l)) return rc;
+            if (int rc = cv_expand(ctx, S, folds, P.g.newton, &P.E_n)) return rc;
+            ctx->tune_expand += (P.E_l.G > 0) + (P.E_n.G > 0);
+            P.cut = true;
+        }
+        auto fit_group = [&](const tsf_spec &gs, const std::vector<int32_t> &gf, RuleLaunch which) -> int {
+            if (which != RULE_RETRY) return cv_fit(ctx, S, which == RULE_LBFGS ? P.E_l : P.E_n, gs, fit, &grids, &ctx->tune_fits);
+            CvGroup E_r;
+            if (int rc = cv_expand(ctx, S, folds, gf, &E_r)) return rc;
+            ctx->tune_expand += 1;
+            return cv_fit(ctx, S, E_r, gs, fit, &grids, &ctx->tune_fits);
+        };
+        if (int rc = fit_by_rule(ctx, cand[c], P.g, S.fit, fit_group)) return rc;
         if (int rc = tsf_predict_dev(ctx, &cand[c], F, S.Hmax, fit.theta, fit.y_scale, fit.grid, (int32_t)F,
                                      H.d_fds.as<int64_t>(), 0, pfl, pcap, pex, S.d_yh.as<double>(), nullptr, nullptr))
             return rc;
@@ -5006,6 +5051,7 @@ static int tune_score_candidates(tsf_ctx *ctx, CvCall &S, const tsf_spec *base, 
         hipLaunchKernelGGL(tune_score_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, nullptr, N, C, c, mval,
                            X.d_moff.as<int64_t>(), X.d_sst.as<int32_t>(), B->d_score.as<double>(), B->d_cst.as<int32_t>());
         HIP_TRY(ctx, hipGetLastError());
+        if (--users[key] == 0) panels.erase(key);       // (its fit launches are over: cv_fit synchronises)
     }
     return 0;
 }
@@ -5074,9 +5120,147 @@ extern "C" int tsf_tune(tsf_ctx *ctx, const tsf_spec *base, const tsf_spec *cand
     HIP_TRY(ctx, B.d_score.alloc(8 * NC)); HIP_TRY(ctx, B.d_cst.alloc(4 * NC));
     HIP_TRY(ctx, B.d_pst.put(S.pst.data(), 4 * (size_t)N));
     HIP_TRY(ctx, B.d_best.alloc(4 * (size_t)N)); HIP_TRY(ctx, B.d_sstat.alloc(4 * (size_t)N));
-    if (int rc = tune_score_candidates(ctx, S, base, cand, C, metric, a.rolling_window, &B)) return rc;
+    if (int rc = tune_score_candidates(ctx, S, cand, C, metric, a.rolling_window, &B)) return rc;
     if (int rc = tune_select(ctx, N, C, B, *out)) return rc;
     return refit ? tune_refit(ctx, S, base, cand, C, out->best, out->fit) : 0;
+}
+
+// ---- model-structure selection (include/tsf.h) ----------------------------------------------------------------------
+// tsf_tune's steps over candidates of different structure: the plan reads no spec field and is made once;
+// tune_score_candidates takes each candidate's theta stride, its table of specified changepoints kept per fold and its
+// grouping of the folds; the choice is select_choose_kernel's; the refit fits each choice's series into outputs of that
+// candidate's own stride (fit_whole_group, as tsf_tune's refit) and select_scatter_kernel pads them.
+
+extern "C" int tsf_select_out_size(void) { return (int)sizeof(tsf_select_out); }
+
+extern "C" int tsf_select_stride(const tsf_spec *cand, int32_t C)
+{
+    if (!cand || C < 1) return -1;
+    int stride_max = 0;
+    for (int32_t c = 0; c < C; ++c) {
+        if (cand[c].n_seas < 0 || cand[c].n_seas > TSF_MAX_SEAS) return -1;
+        const int s = tsf_theta_stride(&cand[c]);
+        if (s > stride_max) stride_max = s;
+    }
+    return stride_max;
+}
+
+// *a = the cross-validation arguments with their defaults filled in and one metric row per series
+static int select_check_args(tsf_ctx *ctx, const tsf_spec *cand, int32_t C, const PanelIn &p, const tsf_cv_args *cv,
+                             int32_t metric, double tolerance, int32_t fallback, int32_t refit, const tsf_select_out *out,
+                             tsf_cv_args *a)
+{
+    if (!cand || !p.ds || !p.y || !out || !out->score || !out->cand_status || !out->best || !out->chosen || !out->series_status)
+        return fail(ctx, "NULL input");
+    if (C < 1 || C > TSF_TUNE_MAX_CAND) return fail(ctx, "C must be in [1, TSF_TUNE_MAX_CAND]");
+    if (metric < TSF_TUNE_MSE || metric > TSF_TUNE_MAPE) return fail(ctx, "bad metric (TSF_TUNE_MSE .. TSF_TUNE_MAPE)");
+    if (refit != 0 && refit != 1) return fail(ctx, "refit must be 0 or 1");
+    if (!(std::isfinite(tolerance) && tolerance >= 0.0)) return fail(ctx, "tolerance must be finite and >= 0");
+    if (fallback < 0 || fallback >= C) return fail(ctx, "fallback must be in [0, C)");
+    if (p.y_dtype < TSF_Y_F64 || p.y_dtype > TSF_Y_I32) return fail(ctx, "bad y_dtype");
+    if (!cv) return fail(ctx, "cv is NULL");
+    tsf_cv_args cv1 = *cv;
+    cv1.rolling_window = 1.0;           // one metric row per series, over all its holdout rows
+    if (tsf_cv::resolve_args(&cv1, a)) return fail(ctx, "bad cross-validation arguments (horizon_ns > 0)");
+    for (int32_t c = 0; c < C; ++c) {
+        DevSpec d;
+        int mode;
+        if (int rc = build_devspec(ctx, &cand[c], &d, &mode)) return rc;       // (every range a launch would refuse)
+        if (cand[c].n_extra != cand[0].n_extra)
+            return fail(ctx, "the candidates must agree in n_extra (the call has one extra array)");
+        if (!same_optimiser(cand[0], cand[c])) return fail(ctx, "the candidates must agree in every optimiser field");
+        if (!prior_scales_ok(cand[c])) return fail(ctx, "a candidate's prior scales must be finite and > 0");
+        if (cand[c].growth == TSF_GROWTH_LOGISTIC && !p.cap) return fail(ctx, "logistic growth needs cap");
+    }
+    if (int rc = check_panel_in(ctx, &cand[0], p)) return rc;
+    if (refit && !fit_out_complete(out->fit)) return fail(ctx, "tsf_select_out.fit has NULL members");
+    return 0;
+}
+
+// the choice per series, then scores, statuses and choices to the caller
+static int select_choose(tsf_ctx *ctx, int64_t N, int32_t C, double tolerance, int32_t fallback, const TuneScores &B,
+                         const tsf_select_out &out)
+{
+    const size_t NC = (size_t)N * C;
+    DevBuf d_chosen;
+    HIP_TRY(ctx, d_chosen.alloc(4 * (size_t)N));
+    hipLaunchKernelGGL(select_choose_kernel, dim3((unsigned)((N + TUNE_SELECT_WAVES - 1) / TUNE_SELECT_WAVES)),
+                       dim3(TUNE_SELECT_WAVES * 64), 0, nullptr, N, C, tolerance, fallback, B.d_score.as<double>(),
+                       B.d_pst.as<int32_t>(), B.d_best.as<int32_t>(), d_chosen.as<int32_t>(), B.d_sstat.as<int32_t>());
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    HIP_TRY(ctx, hipMemcpy(out.score, B.d_score.p, 8 * NC, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(out.cand_status, B.d_cst.p, 4 * NC, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(out.best, B.d_best.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(out.chosen, d_chosen.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(out.series_status, B.d_sstat.p, 4 * (size_t)N, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// every series fitted on its whole history with cand[chosen[n]]: per candidate the rule's launches into outputs of its
+// own stride, then its members' rows padded into the call's (theta rows of stride_max; aligned: grid[c] the candidate's)
+static int select_refit(tsf_ctx *ctx, CvCall &S, const tsf_spec *cand, int32_t C, int stride_max, const int32_t *chosen,
+                        const tsf_fit_out &out)
+{
+    const int64_t N = S.N, n_grids = S.aligned ? C : N;
+    int64_t grids = 0;                  // (not reported)
+    DevFitOut padded;
+    if (int rc = padded.alloc(ctx, N, stride_max, n_grids, FIT_OUT_UNFITTED)) return rc;
+    WholeViews W;
+    if (int rc = W.build(ctx, S)) return rc;
+    const CvViews whole = W.views();
+    for (int32_t c = 0; c < C; ++c) {
+        const tsf_spec &gs = cand[c];
+        std::vector<int32_t> members;
+        for (int64_t n = 0; n < N; ++n)
+            if (chosen[n] == c && W.len[(size_t)n] > 0) members.push_back((int32_t)n);
+        if (members.empty()) continue;
+        S.stride = tsf_theta_stride(&gs);
+        DevFitOut own;                  // (only the members' rows and the grids of their launches are read)
+        if (int rc = own.alloc(ctx, N, S.stride, S.aligned ? 1 : N, FIT_OUT_LAUNCH)) return rc;
+        const tsf_fit_out dst = own.view();
+        auto fit_group = [&](const tsf_spec &ls, const std::vector<int32_t> &sel, RuleLaunch) -> int {
+            return fit_whole_group(ctx, S, whole, ls, sel, dst, &grids, &ctx->tune_fits);
+        };
+        const OptimiserGroups g = optimiser_groups(gs, members.data(), members.size(), W.len.data());
+        if (int rc = fit_by_rule(ctx, gs, g, own, fit_group)) return rc;
+        DevBuf d_mem;
+        HIP_TRY(ctx, d_mem.put(members.data(), 4 * members.size()));
+        hipLaunchKernelGGL(select_scatter_kernel, dim3((unsigned)members.size()), dim3(64), 0, nullptr, (int64_t)members.size(),
+                           d_mem.as<int32_t>(), S.stride, stride_max, S.aligned ? c : -1, dst, padded.view());
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipDeviceSynchronize());       // (this candidate's buffers go back to the pool)
+    }
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    return padded.download(ctx, out, n_grids);
+}
+
+extern "C" int tsf_select(tsf_ctx *ctx, const tsf_spec *cand, int32_t C, int64_t N, int32_t T, const int64_t *offsets,
+                          const int64_t *ds, const void *y, int32_t y_dtype, const double *floor_, const double *cap,
+                          const double *extra, const tsf_cv_args *cv, int32_t metric, double tolerance, int32_t fallback,
+                          int32_t refit, tsf_select_out *out)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const PanelIn p{N, T, offsets, ds, y, y_dtype, floor_, cap, extra};
+    tsf_cv_args a;
+    if (int rc = select_check_args(ctx, cand, C, p, cv, metric, tolerance, fallback, refit, out, &a)) return rc;
+    ctx->order_n = 0;                   // (pending cost hints were meant for a fit call)
+    ctx->tune_expand = 0;
+    ctx->tune_fits = 0;
+    const int stride_max = tsf_select_stride(cand, C);
+    CvCall S;
+    cv_plan_call(p, a, &cand[0], &S);   // (of the spec: n_extra, every candidate's; the rest is set per candidate)
+    S.stride = stride_max;              // (the fold fit outputs, allocated once)
+    if (int rc = cv_upload(ctx, nullptr, &S)) return rc;
+    const size_t NC = (size_t)N * C;
+    TuneScores B;
+    HIP_TRY(ctx, B.d_score.alloc(8 * NC)); HIP_TRY(ctx, B.d_cst.alloc(4 * NC));
+    HIP_TRY(ctx, B.d_pst.put(S.pst.data(), 4 * (size_t)N));
+    HIP_TRY(ctx, B.d_best.alloc(4 * (size_t)N)); HIP_TRY(ctx, B.d_sstat.alloc(4 * (size_t)N));
+    if (int rc = tune_score_candidates(ctx, S, cand, C, metric, a.rolling_window, &B)) return rc;
+    if (int rc = select_choose(ctx, N, C, tolerance, fallback, B, *out)) return rc;
+    return refit ? select_refit(ctx, S, cand, C, stride_max, out->chosen, out->fit) : 0;
 }
 
 // ---- outlier screening (include/tsf.h) ----------------------------------------------------------------------

@@ -2929,6 +2929,221 @@ def last_tune_counts(ctx=None):
     return int(e.value), int(f.value)
 
 
+# ---- model-structure selection (include/tsf.h tsf_select) ---------------------------------------------------
+
+SELECT_AXES = TUNE_AXES + ('seasonality_mode', 'growth', 'changepoint_range', 'n_changepoints')
+
+
+def select_candidates(spec, grid):
+    """The candidates of a grid over SELECT_AXES (dict axis -> list of values): itertools.product of the axes in
+    SELECT_AXES order, the first varying slowest.  The prior-scale axes as tune_candidates; seasonality_mode sets the
+    mode of every seasonality (the conditional ones included) and of the holiday columns of `extra` -- regressors keep
+    theirs; growth, changepoint_range and n_changepoints replace the spec's (growth 'logistic' is allowed here: a
+    missing cap is reported by the call).  -> (candidates [ModelSpec], params {axis: array [C]})."""
+    import itertools
+    if not isinstance(grid, dict) or not grid:
+        raise ValueError('grid must be a non-empty dict over %s' % (SELECT_AXES,))
+    unknown = sorted(set(grid) - set(SELECT_AXES))
+    if unknown:
+        raise ValueError('unknown grid axes %s (selectable: %s)' % (unknown, SELECT_AXES))
+    n_hol = _n_holiday_columns(spec)
+    if 'seasonality_prior_scale' in grid and not (spec.seasonalities or spec.conditional):
+        raise ValueError('grid over seasonality_prior_scale, but the model has no seasonality')
+    if 'holidays_prior_scale' in grid and n_hol == 0:
+        raise ValueError('grid over holidays_prior_scale, but the model has no holidays')
+    if 'n_changepoints' in grid and spec.specified_changepoints:
+        raise ValueError('grid over n_changepoints, but the changepoint dates are specified')
+    axes = [k for k in SELECT_AXES if k in grid]
+    values = []
+    for k in axes:
+        v = list(np.asarray(grid[k]).ravel().tolist())
+        if not v:
+            raise ValueError('grid axis %s is empty' % k)
+        if k in TUNE_AXES and not all(np.isfinite(x) and x > 0 for x in np.asarray(v, dtype=np.float64)):
+            raise ValueError('grid axis %s: prior scales must be finite and > 0' % k)
+        if k == 'n_changepoints' and not all(float(x) == int(x) and 0 <= int(x) <= _lib.MAX_S for x in v):
+            raise ValueError('grid axis n_changepoints: integers in [0, %d]' % _lib.MAX_S)
+        values.append(v)
+    cands, params = [], {k: [] for k in axes}
+    for combo in itertools.product(*values):
+        d = spec.to_dict()                      # (the original form, as tune_candidates)
+        d['seasonalities'] = [dict(s) for s in d['seasonalities']]
+        d['extra'] = [dict(e) for e in d['extra']]
+        for e in d['extra'][n_hol:]:            # (a regressor without its own would follow the axes)
+            e.setdefault('prior_scale', spec.holidays_prior_scale)
+            e.setdefault('mode', spec.seasonality_mode)
+        for k, v in zip(axes, combo):
+            v = int(v) if k == 'n_changepoints' else (str(v) if k in ('seasonality_mode', 'growth') else float(v))
+            d[k] = v
+            params[k].append(v)
+            if k == 'seasonality_prior_scale':
+                for s in d['seasonalities']:
+                    s['prior_scale'] = v
+            elif k == 'holidays_prior_scale':
+                for e in d['extra'][:n_hol]:
+                    e['prior_scale'] = v
+            elif k == 'seasonality_mode':
+                for s in d['seasonalities']:
+                    s['mode'] = v
+                for e in d['extra'][:n_hol]:
+                    e['mode'] = v
+        cands.append(ModelSpec.from_dict(d))    # (a bad growth / mode / range is ModelSpec's ValueError)
+    return cands, {k: np.array(v) for k, v in params.items()}
+
+
+def _select_axis_values(cands):
+    """{axis: [C]} what each candidate carries for SELECT_AXES, and the names of its seasonalities."""
+    d = {k: np.array([getattr(c, k) for c in cands]) for k in SELECT_AXES}
+    d['seasonalities'] = np.array([','.join(str(s.get('name')) for s in c.seasonalities + c.conditional) for c in cands],
+                                  dtype=object)
+    return d
+
+
+class SelectResult(object):
+    """What select_model returns (include/tsf.h tsf_select).
+
+    candidates [C] (ModelSpec), metric; score / cand_status [N][C]; best [N] (-1: the rule made no choice), chosen [N]
+    (best, or the fallback: the candidate of the refit), status [N] (the plan's TSF_CV_* or TUNE_NO_SCORE); fit: the
+    refit as the library returns it (None without) -- theta rows padded to the widest candidate's stride, grid [C] on an
+    aligned panel (aligned = True) or [N]; groups() cuts it into one FitResult per candidate."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def spec_of(self, n):
+        """The ModelSpec series n is refitted with."""
+        return self.candidates[int(self.chosen[n])]
+
+    def groups(self):
+        """[(c, idx, FitResult)] for every candidate c some series was refitted with: idx the series (ascending), the
+        FitResult their fits with theta cut to the candidate's stride and the candidate's grid(s) -- what every predict
+        entry takes with candidates[c]."""
+        if self.fit is None:
+            raise ValueError('select_model ran without refit')
+        out = []
+        f = self.fit
+        for c in np.unique(self.chosen):
+            c = int(c)
+            idx = np.flatnonzero(self.chosen == c)
+            sp = self.candidates[c]
+            grid = f.grid[c:c + 1] if self.aligned else f.grid[idx]
+            out.append((c, idx, FitResult(sp, np.ascontiguousarray(f.theta[idx, :sp.theta_stride]), f.y_scale[idx],
+                                          f.fval[idx], f.status[idx], f.n_iter[idx], f.n_eval[idx], grid)))
+        return out
+
+    def predict(self, ds_future_ns, floor=None, cap=None, extra_future=None, ctx=None):
+        """yhat [N][H]: one predict per group with its candidate, placed by series.  ds_future_ns [H] or [N][H];
+        floor / cap [N]; extra_future as predict's ([n_extra][H] shared, [N][n_extra][H] per series).  A series of a
+        ragged panel that no fit reached (too few rows: its grid is empty, and predict refuses such a grid) is NaN."""
+        N = len(self.chosen)
+        fut = np.asarray(ds_future_ns, dtype=np.int64)
+        fl, cp = _opt_f64(floor, N, 'floor'), _opt_f64(cap, N, 'cap')
+        ex = None if extra_future is None else np.asarray(extra_future, dtype=np.float64)
+        yhat = np.full((N, fut.shape[-1]), np.nan)
+        for c, idx, f in self.groups():
+            ok = np.arange(len(idx)) if self.aligned else np.flatnonzero(f.grid['t_scale_ns'] > 0)
+            if ok.size == 0:
+                continue
+            sel = idx[ok]
+            yhat[sel] = predict(f.spec, f.theta[ok], f.y_scale[ok], f.grid if self.aligned else f.grid[ok],
+                                fut if fut.ndim == 1 else fut[sel], None if fl is None else fl[sel],
+                                None if cp is None else cp[sel], ex if (ex is None or fut.ndim == 1) else ex[sel], ctx=ctx)
+        return yhat
+
+    def frame(self):
+        """One row per series: series, candidate (the refit's), status, one column per axis of SELECT_AXES (and the
+        seasonality names) that varies among the candidates, metric and the score of the choice (NaN without one)."""
+        import pandas as pd
+        N = len(self.chosen)
+        d = {'series': np.arange(N, dtype=np.int64), 'candidate': self.chosen.astype(np.int64),
+             'status': self.status.astype(np.int64)}
+        for k, v in _select_axis_values(self.candidates).items():
+            if len(set(v.tolist())) > 1:
+                d[k] = v[self.chosen]
+        d['metric'] = np.full(N, self.metric, dtype=object)
+        d['score'] = self.score[np.arange(N), self.chosen]
+        return pd.DataFrame(d)
+
+
+def select_model(candidates, ds_ns, y, horizon, period=None, initial=None, offsets=None, floor=None, cap=None, extra=None,
+                 metric='rmse', tolerance=0.0, fallback=0, refit=True, ctx=None, devices=None):
+    """Choose the model structure per series by cross-validation in one call (include/tsf.h tsf_select): every candidate
+    cross-validated as cross_validate(rolling_window=1) scores it, per series the lowest-numbered candidate within
+    `tolerance` of the best score (order the candidates from simple to complex), and (refit) every series fitted on its
+    full history with its choice -- `fallback` where it has none.  candidates: ModelSpecs that agree in their extra
+    columns and optimiser options (select_candidates builds a grid of them).  Input as cross_validate.  devices: several
+    GPUs, split by series.  Returns a SelectResult."""
+    cands = list(candidates)
+    C = len(cands)
+    if C > _lib.TUNE_MAX_CAND:
+        raise ValueError('at most %d candidates' % _lib.TUNE_MAX_CAND)
+    if metric not in _lib.TUNE_METRICS:
+        raise ValueError('metric must be one of %s' % sorted(_lib.TUNE_METRICS))
+    ds_ns, y, offsets, N, T = _cv_panel(ds_ns, y, offsets)
+    fl = _opt_f64(floor, N, 'floor')
+    cp = _opt_f64(cap, N, 'cap')
+    aligned = offsets is None
+
+    def result(score, cst, best, chosen, sst, fit):
+        return SelectResult(candidates=cands, metric=metric, tolerance=float(tolerance), score=score, cand_status=cst,
+                            best=best, chosen=chosen, status=sst, fit=fit, aligned=aligned)
+    devs = None if ctx is not None else resolve_devices(devices)
+    if devs and N >= 2 * MIN_SERIES_PER_DEVICE:
+        parts = min(len(devs), N // MIN_SERIES_PER_DEVICE)
+        lens = np.full(N, T, np.int64) if aligned else np.diff(offsets)
+        cuts = _cuts(lens, parts)
+        ex = None if extra is None else np.asarray(extra)
+
+        def one(c, a, b):
+            kw = dict(metric=metric, tolerance=tolerance, fallback=fallback, refit=refit, ctx=c)
+            if aligned:
+                return select_model(cands, ds_ns, y[a:b], horizon, period, initial, None, None if fl is None else fl[a:b],
+                                    None if cp is None else cp[a:b], extra, **kw)
+            r0, r1 = int(offsets[a]), int(offsets[b])
+            return select_model(cands, ds_ns[r0:r1], y[r0:r1], horizon, period, initial, offsets[a:b + 1] - r0,
+                                None if fl is None else fl[a:b], None if cp is None else cp[a:b],
+                                None if ex is None else ex[:, r0:r1], **kw)
+        blocks = [(c, int(a), int(b)) for c, a, b in zip(_contexts(devs[:parts]), cuts[:-1], cuts[1:]) if b > a]
+        pr = _run_blocks(one, blocks)
+        cat = lambda k: np.concatenate([getattr(p, k) for p in pr])     # noqa: E731
+        fit = None
+        if refit:
+            fit = _merge_fits(None, [p.fit for p in pr], shared_grid=aligned)
+            if aligned:                 # grid[c]: from the first block that refitted a series with candidate c
+                fit.grid = fit.grid.copy()
+                for c in range(C):
+                    for p in pr:
+                        if any(p.fit.grid[c:c + 1].tobytes()):
+                            fit.grid[c] = p.fit.grid[c]
+                            break
+        return result(cat('score'), cat('cand_status'), cat('best'), cat('chosen'), cat('status'), fit)
+    ctx = ctx or get_context()
+    L = _lib.load()
+    n_extra = len(cands[0].extra) if cands else 0
+    ex = None
+    if n_extra:
+        ex = np.ascontiguousarray(extra, dtype=np.float64)
+        if ex.shape != (n_extra, len(ds_ns)):
+            raise ValueError('extra must be [n_extra][len(ds)]')
+    carr = (_lib.TsfSpec * max(C, 1))(*[c.to_c() for c in cands])
+    stride_max = max([c.theta_stride for c in cands] + [1])
+    if C >= 1 and L.tsf_select_stride(carr, C) != stride_max:
+        raise _lib.TsfError('tsf_select_stride disagrees with ModelSpec.theta_stride')
+    score = np.zeros((N, max(C, 1)))
+    cst = np.zeros((N, max(C, 1)), np.int32)
+    best = np.zeros(N, np.int32)
+    chosen = np.zeros(N, np.int32)
+    sst = np.zeros(N, np.int32)
+    fout, farrs = _alloc_out(N, stride_max, C if aligned else N) if refit else (_lib.TsfFitOut(), None)
+    out = _lib.TsfSelectOut(score.ctypes.data, cst.ctypes.data, best.ctypes.data, chosen.ctypes.data, sst.ctypes.data, fout)
+    a = _cv_args(horizon, period, initial, 1.0)
+    rc = L.tsf_select(ctx.handle, carr, C, N, T, _lib._ptr(offsets), ds_ns.ctypes.data, y.ctypes.data,
+                      _lib.y_dtype_code(y), _lib._ptr(fl), _lib._ptr(cp), _lib._ptr(ex), ctypes.byref(a),
+                      _lib.TUNE_METRICS[metric], float(tolerance), int(fallback), int(bool(refit)), ctypes.byref(out))
+    ctx.check(rc)
+    return result(score, cst, best, chosen, sst, FitResult(None, *farrs) if refit else None)
+
+
 # ---- outlier screening: robust residual flags and refit (include/tsf.h) --------------------------------------
 
 class Screen(object):
