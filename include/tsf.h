@@ -973,6 +973,88 @@ int tsf_residual_autocorr_dev(tsf_ctx *ctx, int64_t N, int32_t T, const int64_t 
                               int32_t y_dtype, const double *fitted, const tsf_ar_args *args, tsf_ar_out *out, void *stream);
 int tsf_set_noise_ar(tsf_ctx *ctx, const double *phi /* host [n] */, int64_t n);
 
+/* ---- serially correlated observation noise: the conditioned start ------------------------------------
+ * The chain above starts every sample at the stationary law, e_0 = z_0: right for a forecast that begins far from the
+ * data.  A forecast that begins at the row behind the history does not: the fit has just seen the last residual.  If the
+ * last present row stood r above the fit (y units) and the residuals are an AR(1) with autocorrelation phi and marginal
+ * deviation sigma y_scale, then the noise of the row `steps` rows behind it has mean phi^steps r and variance
+ * (1 - phi^(2 steps)) sigma^2 y_scale^2, and the rows after it follow the same recursion as always.  With p0 = phi^steps:
+ * the noise of future row h has mean m_h = p0 phi^h r and variance (1 - (p0 phi^h)^2) sigma^2 y_scale^2, rows i <= j have
+ * noise covariance phi^(j - i) times row i's variance, and as h grows everything tends to the stationary chain.  The
+ * point forecast gains the correction of a regression with AR(1) errors (yhat + m_h: it removes the share p0^2 of the
+ * first row's squared error, 36 % at phi = 0.6 and steps = 1), the near rows' intervals narrow by sqrt(1 - p0^2), and
+ * totals, running sums, roll-ups and scores inherit both, being functions of the same draws.  Three pieces, all opt-in;
+ * reference interface replaced: none; parity unpinned (pinned: the contract below, restated in numpy in
+ * tests/ar_start_ref.py).  Timing: tools/bench_noise_ar_start.py; DESIGN.md 5s.  Without the new setting every entry is
+ * what it was, bit for bit -- the stationary chain included.
+ *
+ * tsf_residual_last.  The panel arguments of tsf_residual_autocorr (aligned, or ragged by offsets; y in y_dtype, fitted
+ * double).  Outputs per series, all three required: last_resid = r_t = (double)y_t - fitted_t of the last present
+ * (finite) row t; last_gap (int32) = the rows of the series behind that row, 0 where the final row is present; status
+ * TSF_AR_OK, or TSF_AR_NO_ROW for a series without a present row (an empty one too), whose last_resid is +0.0 and whose
+ * last_gap is its row count.  Host pointers in the host variant; in _dev y, fitted and the three outputs are device
+ * pointers, offsets and the tsf_ar_last_out struct itself are HOST memory, and the call synchronises the stream before
+ * it returns.  One launch, one wave per series, which reads the series from its end in blocks of 64 rows and stops at the
+ * first block with a present row.  Refusals: those of tsf_residual_autocorr (but for its args), a NULL last_resid,
+ * last_gap or status, and a ragged series of more than 2^31 - 1 rows; N == 0 is a legal no-op.
+ * tsf_residual_autocorr_last (host pointers only) is both calls on one copy of the panel: the copy-in of y and fitted is
+ * most of either, and a caller of the conditioned start wants both.  Its outputs are those of the two entries, bit for
+ * bit, and its refusals the union of theirs.
+ *
+ * tsf_set_noise_ar_start.  resid: HOST [n], y units, each finite; steps: HOST [n], each >= 1: last_gap plus the number
+ * of rows from the end of the history to the first future row (normally the next row: 1) -- lag one ROW, as above.  Legal
+ * only while a tsf_set_noise_ar setting for the same n is pending: without one, or with another n, it is refused (< 0,
+ * a message) and the pending setting is cleared; a bad resid or steps is refused likewise and clears it too (a
+ * statistical setting is never half applied).  NULL resid or steps, or n == 0, clears the start only.  A later
+ * tsf_set_noise_ar clears the start.  Both settings are consumed together by the next drawing entry, under the one-shot
+ * rule above.  It stores per series, formed on the host in plain double operations with one rounding each (no fused
+ * multiply-add):
+ *   p0 = phi multiplied by itself steps - 1 more times (the loop stops at the first zero, whose sign it keeps);
+ *   c0 = sqrt(1 - p0 * p0);   m0 = resid * p0
+ * in an array [n][3] of its own beside the (phi, c) pairs, which are what they were.
+ *
+ * tsf_noise_ar_mean (host only, no context, nothing launched; < 0 for a bad argument: n < 0, H < 0, a NULL array that is
+ * needed, |phi| >= 1 or not finite, a non-finite resid, steps < 1).  The conditional mean in y units, [n][H]:
+ *   mean[i][0] = m0 = resid[i] * p0;   mean[i][h] = phi[i] * mean[i][h - 1]   (one product each).
+ *
+ * The conditioned draw.  In a call that holds both settings, series i is drawn with m_h = tsf_noise_ar_mean's values and
+ * z_h the same counter-based normals as always (counters 2h, 2h + 1 of the noise stream, untouched):
+ *   e_0 = c0 * z_0;   e_h = phi * e_(h-1) + c * z_h   (the expression above);
+ *   sample = trend * (1 + mult) + (add + m_h) + (e_h * sigma) * y_scale;   yhat' = yhat + m_h   (one add).
+ * The mean travels in the additive piece: a kernel of its own (ar_start_shift_kernel, one thread per series and row) runs
+ * behind the point forecast's kernel and in front of the sample kernel; it forms m_h by the recursion above and adds it to
+ * the chunk's additive term (add * y_scale, already rounded: `add` above) and to yhat, one add each.  The order of the adds in
+ * a sample is therefore (trend * (1 + mult) + (add + m_h)) + noise.  The sample kernel's third instance differs from the
+ * chained one in e_0 alone.  A series with phi == 0 takes the independent expression exactly (a select), and neither its
+ * additive term nor its yhat is touched, whatever resid is.  The sampled trend and trend_out are unchanged; ysum of a
+ * roll-up accumulates the shifted yhat.  Sample s depends on nothing but (seed, series key, s, phi, resid, steps).
+ * The entries that take the start are exactly those that take tsf_set_noise_ar; those that refuse a pending setting
+ * refuse as before and clear both.
+ *
+ * Limits.  tsf_predict_temporal takes its phi as arguments, not through the setting, and keeps the stationary start (its
+ * signature is published).  No conditioning inside tsf_cross_validate, tsf_calibrate, tsf_tune and tsf_select: the folds
+ * would need each fold's fitted history; none on roll-ups with a noise correlation; no higher lags; the chain
+ * runs on rows, not on the calendar; the job configurations and the model blob are untouched; no devices= split; no
+ * existing signature or struct changes (tsf_ar_out is what it was). */
+enum { TSF_AR_NO_ROW = -52 };       /* beside TSF_AR_OK: a series without a present row */
+typedef struct {
+    double *last_resid;     /* [N] required: the last present row's residual, y units (+0.0 without one) */
+    int32_t *last_gap;      /* [N] required: the rows of the series behind that row */
+    int32_t *status;        /* [N] required: TSF_AR_OK or TSF_AR_NO_ROW */
+} tsf_ar_last_out;
+int tsf_ar_last_out_size(void);     /* sizeof(tsf_ar_last_out): the self-check of a binding */
+int tsf_residual_last(tsf_ctx *ctx, int64_t N, int32_t T, const int64_t *offsets /* NULL = aligned [N][T] */, const void *y,
+                      int32_t y_dtype, const double *fitted, tsf_ar_last_out *out);
+int tsf_residual_last_dev(tsf_ctx *ctx, int64_t N, int32_t T, const int64_t *offsets /* host */, const void *y,
+                          int32_t y_dtype, const double *fitted, tsf_ar_last_out *out, void *stream);
+/* tsf_residual_autocorr and tsf_residual_last on one copy of the panel (host pointers): both results, each bit for bit */
+int tsf_residual_autocorr_last(tsf_ctx *ctx, int64_t N, int32_t T, const int64_t *offsets, const void *y, int32_t y_dtype,
+                               const double *fitted, const tsf_ar_args *args, tsf_ar_out *out, tsf_ar_last_out *last);
+int tsf_set_noise_ar_start(tsf_ctx *ctx, const double *resid /* host [n], y units */, const int32_t *steps /* host [n], >= 1 */,
+                           int64_t n);
+int tsf_noise_ar_mean(int64_t n, const double *phi, const double *resid, const int32_t *steps, int32_t H,
+                      double *mean /* [n][H] */);
+
 /* ---- conditional seasonalities ---------------------------------------------------------------------
  * Replaces the `condition_name=` argument of fbprophet 0.5's `Prophet.add_seasonality(name, period, fourier_order,
  * prior_scale, mode, condition_name)`: a seasonality that applies only on the rows where a boolean column of the frame

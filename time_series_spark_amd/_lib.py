@@ -200,6 +200,11 @@ class TsfArOut(ctypes.Structure):
                 ('scale', ctypes.c_void_p), ('status', ctypes.c_void_p)]
 
 
+class TsfArLastOut(ctypes.Structure):
+    """tsf_ar_last_out (include/tsf.h)."""
+    _fields_ = [('last_resid', ctypes.c_void_p), ('last_gap', ctypes.c_void_p), ('status', ctypes.c_void_p)]
+
+
 class TsfCondSeas(ctypes.Structure):
     """tsf_cond_seas (include/tsf.h)."""
     _fields_ = [('n', ctypes.c_int32), ('period', ctypes.c_double * MAX_SEAS), ('order', ctypes.c_int32 * MAX_SEAS),
@@ -244,6 +249,8 @@ EXPORTS = ['tsf_create', 'tsf_destroy', 'tsf_last_error', 'tsf_device_count', 't
            'tsf_temporal_shares', 'tsf_temporal_out_size', 'tsf_predict_temporal',
            'tsf_corr_args_size', 'tsf_corr_out_size', 'tsf_residual_corr', 'tsf_residual_corr_dev', 'tsf_rollup_set_noise_corr',
            'tsf_ar_args_size', 'tsf_ar_out_size', 'tsf_residual_autocorr', 'tsf_residual_autocorr_dev', 'tsf_set_noise_ar',
+           'tsf_ar_last_out_size', 'tsf_residual_last', 'tsf_residual_last_dev', 'tsf_residual_autocorr_last',
+           'tsf_set_noise_ar_start', 'tsf_noise_ar_mean',
            'tsf_cond_columns', 'tsf_cond_columns_dev',
            'tsf_eval', 'tsf_eval_quadratic', 'tsf_design', 'tsf_selftest_math',
            'tsf_set_option', 'tsf_get_option', 'tsf_set_cost_hints', 'tsf_set_profiling', 'tsf_profile_read', 'tsf_last_fit_kernel_ms', 'tsf_last_fit_route',
@@ -278,6 +285,7 @@ CALIB_MAX_ROWS, CALIB_MAX_LEVELS, CALIB_MAX_BUCKETS = 16384, 16, 64
 CORR_OK, CORR_NO_PAIRS = 0, -50
 # TSF_AR_* (include/tsf.h): per-series outcome of the residual-autocorrelation estimator
 AR_OK, AR_NO_PAIRS = 0, -51
+AR_NO_ROW = -52                 # tsf_residual_last: a series without a present row
 
 # TSF_ROUTE_* / TSF_CALL_* / TSF_PLAN_* (include/tsf_dev.h): a fit plan's route, the kind of call, why a call has no plan
 ROUTE_NEWTON, ROUTE_NEWTON_QUAD, ROUTE_QUAD_EVAL, ROUTE_QUAD_LBFGS, ROUTE_MFMA, ROUTE_WAVE = range(6)
@@ -371,6 +379,11 @@ def load():
     L.tsf_residual_autocorr.argtypes = [vp, i64, i32, vp, vp, i32, vp, ctypes.POINTER(TsfArArgs), ctypes.POINTER(TsfArOut)]
     L.tsf_residual_autocorr_dev.argtypes = L.tsf_residual_autocorr.argtypes + [vp]
     L.tsf_set_noise_ar.argtypes = [vp, vp, i64]
+    L.tsf_residual_last.argtypes = [vp, i64, i32, vp, vp, i32, vp, ctypes.POINTER(TsfArLastOut)]
+    L.tsf_residual_last_dev.argtypes = L.tsf_residual_last.argtypes + [vp]
+    L.tsf_residual_autocorr_last.argtypes = L.tsf_residual_autocorr.argtypes + [ctypes.POINTER(TsfArLastOut)]
+    L.tsf_set_noise_ar_start.argtypes = [vp, vp, vp, i64]
+    L.tsf_noise_ar_mean.argtypes = [i64, vp, vp, vp, i32, vp]
     L.tsf_cond_columns.argtypes = [vp, ctypes.POINTER(TsfCondSeas), i64, vp, i32, vp, vp, i64]
     L.tsf_cond_columns_dev.argtypes = L.tsf_cond_columns.argtypes + [vp]
     L.tsf_eval.argtypes = [vp, psp, i64, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
@@ -469,6 +482,8 @@ def load():
         raise TsfError('tsf_corr_args / tsf_corr_out layout mismatch between _lib.py and libtsf_amd.so')
     if L.tsf_ar_args_size() != ctypes.sizeof(TsfArArgs) or L.tsf_ar_out_size() != ctypes.sizeof(TsfArOut):
         raise TsfError('tsf_ar_args / tsf_ar_out layout mismatch between _lib.py and libtsf_amd.so')
+    if L.tsf_ar_last_out_size() != ctypes.sizeof(TsfArLastOut):
+        raise TsfError('tsf_ar_last_out layout mismatch between _lib.py and libtsf_amd.so')
     if L.tsf_select_out_size() != ctypes.sizeof(TsfSelectOut):
         raise TsfError('tsf_select_out layout mismatch between _lib.py and libtsf_amd.so')
     if L.tsf_fit_plan_info_size() != ctypes.sizeof(TsfFitPlanInfo):

@@ -83,7 +83,8 @@ struct tsf_ctx {
     int32_t tune_expand;    // tsf_last_tune_counts: fold panels cut / fit launches of the last tsf_tune call
     int32_t tune_fits;
     std::vector<double> ar_pending;   // tsf_set_noise_ar: the pending (phi, c) pairs, [n][2]; empty: none pending
-    double *ar_dev;         // the pairs of the draw that took them, on the device (grown on demand)
+    std::vector<double> ar_start_pending;   // tsf_set_noise_ar_start: the pending (p0, c0, m0), [n][3], beside ar_pending
+    double *ar_dev;         // the pairs of the draw that took them, on the device (grown on demand); behind them its starts
     size_t ar_dev_bytes;
 };
 
@@ -1693,7 +1694,7 @@ struct DrawSpec {
 struct NoiseArOnce {
     tsf_ctx *ctx;
     explicit NoiseArOnce(tsf_ctx *c) : ctx(c) {}
-    ~NoiseArOnce() { if (ctx) ctx->ar_pending.clear(); }
+    ~NoiseArOnce() { if (ctx) { ctx->ar_pending.clear(); ctx->ar_start_pending.clear(); } }
     NoiseArOnce(const NoiseArOnce &) = delete;
     NoiseArOnce &operator=(const NoiseArOnce &) = delete;
 };
@@ -1702,6 +1703,7 @@ static int refuse_noise_ar(tsf_ctx *ctx, const char *who)
 {
     if (ctx->ar_pending.empty()) return 0;
     ctx->ar_pending.clear();
+    ctx->ar_start_pending.clear();
     ctx->err = std::string(who) + ": a tsf_set_noise_ar setting is pending and this entry does not take it (the setting is cleared)";
     return -1;
 }
@@ -1712,21 +1714,26 @@ static int check_noise_ar_count(tsf_ctx *ctx, int64_t N)
     const int64_t n = (int64_t)(ctx->ar_pending.size() / 2);
     if (n == 0 || n == N) return 0;
     ctx->ar_pending.clear();
+    ctx->ar_start_pending.clear();
     char msg[160];
     snprintf(msg, sizeof(msg), "tsf_set_noise_ar was given %lld series and this call has N = %lld (the setting is cleared)",
              (long long)n, (long long)N);
     return fail(ctx, msg);
 }
 
-// The pending pairs onto the device for a draw of N series on st; *dev: the pairs, or null where nothing is pending.
-static int take_noise_ar(tsf_ctx *ctx, int64_t N, hipStream_t st, const double **dev)
+// The pending pairs onto the device for a draw of N series on st; *dev: the pairs, or null where nothing is pending;
+// *dev_start: the (p0, c0, m0) of a pending conditioned start (tsf_set_noise_ar_start: only ever beside pairs of the same
+// count), behind the pairs in the same block, or null.
+static int take_noise_ar(tsf_ctx *ctx, int64_t N, hipStream_t st, const double **dev, const double **dev_start)
 {
     *dev = nullptr;
+    *dev_start = nullptr;
     if (int rc = check_noise_ar_count(ctx, N)) return rc;
     if (ctx->ar_pending.empty()) return 0;
-    std::vector<double> pairs;
+    std::vector<double> pairs, start;
     pairs.swap(ctx->ar_pending);
-    const size_t need = 8 * pairs.size();
+    start.swap(ctx->ar_start_pending);
+    const size_t need = 8 * (pairs.size() + start.size());
     // (an earlier draw on this stream may still read the buffer)
     HIP_TRY(ctx, hipStreamSynchronize(st));
     if (ctx->ar_dev_bytes < need) {
@@ -1734,8 +1741,12 @@ static int take_noise_ar(tsf_ctx *ctx, int64_t N, hipStream_t st, const double *
         HIP_TRY(ctx, hipMalloc((void **)&ctx->ar_dev, need));
         ctx->ar_dev_bytes = need;
     }
-    HIP_TRY(ctx, hipMemcpy(ctx->ar_dev, pairs.data(), need, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->ar_dev, pairs.data(), 8 * pairs.size(), hipMemcpyHostToDevice));
     *dev = ctx->ar_dev;
+    if (!start.empty()) {
+        HIP_TRY(ctx, hipMemcpy(ctx->ar_dev + pairs.size(), start.data(), 8 * start.size(), hipMemcpyHostToDevice));
+        *dev_start = ctx->ar_dev + pairs.size();
+    }
     return 0;
 }
 
@@ -1774,9 +1785,10 @@ struct ModelDraw {
     bool tab_ready;
 
     // the launch arguments: pieces [3][chunk][H] and the sample buffers `b` of a chunk; d_ar: the series' (phi, c) pairs
-    // on the device or null.  Nothing is launched.
+    // on the device or null; d_start: beside d_ar, the series' (p0, c0, m0) of a conditioned start, or null.  Nothing is
+    // launched.
     void bind(const tsf_ctx *ctx, const tsf_spec *spec, const ForecastIn &f, const DrawSpec &d, const double *d_ar,
-              double *pieces, size_t nh, const DrawBufs &b)
+              double *pieces, size_t nh, const DrawBufs &b, const double *d_start = nullptr)
     {
         d_t = pieces; d_xa = d_t + nh; d_opm = d_xa + nh;
         p = predict_args(ctx, spec, f, d.yhat);
@@ -1788,6 +1800,7 @@ struct ModelDraw {
         a.series_key = f.series_key; a.seed = d.seed;
         a.samples = b.samp; a.trend_samples = b.trend; a.cum_samples = b.cum;
         a.noise_ar = d_ar;
+        a.ar_start = d_ar ? d_start : nullptr;
         tab_ready = false;
     }
     // the context's device spec (and with it a shared future grid's design table) made this model's, in stream order
@@ -1806,7 +1819,14 @@ struct ModelDraw {
         a.n0 = n0; a.n_chunk = nc;
         a.t = d_t - (size_t)n0 * H; a.xa = d_xa - (size_t)n0 * H; a.opm = d_opm - (size_t)n0 * H;
         const dim3 sgrid((unsigned)nc, (unsigned)((a.NS + 255) / 256));
-        if (a.noise_ar) hipLaunchKernelGGL(interval_sample_kernel<true>, sgrid, dim3(256), 0, st, a);
+        if (a.ar_start) {
+            // the conditioned start: its mean into the chunk's additive piece and into yhat (p.yhat: the call's [N][H]),
+            // behind predict_kernel in stream order; then the instance whose chain starts at e_0 = c0 z_0
+            const ArStartArgs sa = {a.noise_ar, a.ar_start, d_xa, p.yhat, n0, nc, H};
+            hipLaunchKernelGGL(ar_start_shift_kernel, dim3((unsigned)((nc * H + 255) / 256)), dim3(256), 0, st, sa);
+            hipLaunchKernelGGL((interval_sample_kernel<true, true>), sgrid, dim3(256), 0, st, a);
+        }
+        else if (a.noise_ar) hipLaunchKernelGGL(interval_sample_kernel<true>, sgrid, dim3(256), 0, st, a);
         else hipLaunchKernelGGL(interval_sample_kernel<false>, sgrid, dim3(256), 0, st, a);
         HIP_TRY(ctx, hipGetLastError());
         return 0;
@@ -1819,8 +1839,8 @@ static int draw_chunks(tsf_ctx *ctx, const tsf_spec *spec, const ForecastIn &f, 
 {
     if (!d.takes_ar)
         if (int rc = refuse_noise_ar(ctx, "this drawing entry")) return rc;
-    const double *d_ar = nullptr;
-    if (int rc = take_noise_ar(ctx, f.N, st, &d_ar)) return rc;
+    const double *d_ar = nullptr, *d_start = nullptr;
+    if (int rc = take_noise_ar(ctx, f.N, st, &d_ar, &d_start)) return rc;
     ModelDraw m;
     if (int rc = forecast_spec(ctx, spec, f, &m.hs)) return rc;
     if (int rc = m.send_spec(ctx, st)) return rc;
@@ -1836,7 +1856,7 @@ static int draw_chunks(tsf_ctx *ctx, const tsf_spec *spec, const ForecastIn &f, 
     if (d.want_cum) { d_cum = d_next; d_next += nh * n_samples; }
     if (d.want_trend) d_tsamp = d_next;
     const DrawBufs bufs = {d_samp, d_cum, d_tsamp};
-    m.bind(ctx, spec, f, d, d_ar, (double *)ctx->iv_ws, nh, bufs);
+    m.bind(ctx, spec, f, d, d_ar, (double *)ctx->iv_ws, nh, bufs, d_start);
     for (int64_t n0 = 0; n0 < N; n0 += chunk) {
         const int64_t nc = (N - n0 < chunk) ? N - n0 : chunk;
         if (int rc = m.chunk(ctx, n0, nc, st)) return rc;
@@ -2900,9 +2920,186 @@ extern "C" int tsf_residual_autocorr(tsf_ctx *ctx, int64_t N, int32_t T, const i
     return outs.fetch(ctx);
 }
 
+// ---- the conditioned start of the chain: the residuals' state at the end of the history, the setting, the mean ----
+
+extern "C" int tsf_ar_last_out_size(void) { return (int)sizeof(tsf_ar_last_out); }
+
+// What both tsf_residual_last entries check before anything is launched (tsf_residual_autocorr's refusals, and a ragged
+// series whose row count does not fit last_gap); offsets and out are host memory in both.
+static int check_ar_last_call(tsf_ctx *ctx, int64_t N, int32_t T, const int64_t *offsets, const void *y, int32_t y_dtype,
+                              const double *fitted, const tsf_ar_last_out *out)
+{
+    if (N < 0 || N > (int64_t)INT32_MAX) return fail(ctx, "N must be in [0, 2^31 - 1]");
+    if (!out || !out->last_resid || !out->last_gap || !out->status)
+        return fail(ctx, "NULL output (tsf_ar_last_out, its last_resid, last_gap and status are required)");
+    if (y_dtype < TSF_Y_F64 || y_dtype > TSF_Y_I32) return fail(ctx, "bad y_dtype");
+    if (N > 0 && (!y || !fitted)) return fail(ctx, "NULL input (y and fitted are required)");
+    if (!offsets) return T >= 1 ? 0 : fail(ctx, "bad panel (aligned: T >= 1)");
+    if (offsets[0] != 0) return fail(ctx, "bad panel (ragged: offsets[0] = 0)");
+    for (int64_t n = 0; n < N; ++n) {
+        if (offsets[n + 1] < offsets[n]) return fail(ctx, "bad panel (ragged: offsets ascending)");
+        if (offsets[n + 1] - offsets[n] > (int64_t)INT32_MAX) return fail(ctx, "bad panel (ragged: a series has more than 2^31 - 1 rows)");
+    }
+    return 0;
+}
+
+static int ar_last_run(tsf_ctx *ctx, int64_t N, int32_t T, const int64_t *d_off, const void *d_y, int32_t y_dtype,
+                       const double *d_fit, const tsf_ar_last_out &o, hipStream_t st)
+{
+    if (N == 0) return 0;
+    const ArLastArgs k = {d_y, d_fit, d_off, N, T, y_dtype, o.last_resid, o.last_gap, o.status};
+    hipLaunchKernelGGL(ar_last_kernel, dim3((unsigned)((N + AR_WAVES - 1) / AR_WAVES)), dim3(AR_WAVES * 64), 0, st, k,
+                       (int)TSF_AR_OK, (int)TSF_AR_NO_ROW);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+extern "C" int tsf_residual_last_dev(tsf_ctx *ctx, int64_t N, int32_t T, const int64_t *offsets, const void *y,
+                                     int32_t y_dtype, const double *fitted, tsf_ar_last_out *out, void *stream)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rc = check_ar_last_call(ctx, N, T, offsets, y, y_dtype, fitted, out)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf d_off;
+    if (offsets && N > 0) HIP_TRY(ctx, d_off.put(offsets, 8 * ((size_t)N + 1)));
+    if (int rc = ar_last_run(ctx, N, T, offsets ? d_off.as<int64_t>() : nullptr, y, y_dtype, fitted, *out, st)) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(st));         // (the offsets go back to the pool)
+    return 0;
+}
+
+extern "C" int tsf_residual_last(tsf_ctx *ctx, int64_t N, int32_t T, const int64_t *offsets, const void *y,
+                                 int32_t y_dtype, const double *fitted, tsf_ar_last_out *out)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rc = check_ar_last_call(ctx, N, T, offsets, y, y_dtype, fitted, out)) return rc;
+    if (N == 0) return 0;
+    const size_t rows = offsets ? (size_t)offsets[N] : (size_t)N * T, n = (size_t)N;
+    DevBuf d_off, d_y, d_fit;
+    HostOuts outs;
+    if (offsets) HIP_TRY(ctx, d_off.put(offsets, 8 * (n + 1)));
+    HIP_TRY(ctx, d_y.put(y, ysize(y_dtype) * rows));
+    HIP_TRY(ctx, d_fit.put(fitted, 8 * rows));
+    tsf_ar_last_out o;
+    memset(&o, 0, sizeof(o));
+    o.last_resid = outs.want(out->last_resid, 8 * n); o.last_gap = outs.want(out->last_gap, 4 * n);
+    o.status = outs.want(out->status, 4 * n);
+    if (int rc = outs.ready(ctx)) return rc;
+    if (int rc = ar_last_run(ctx, N, T, offsets ? d_off.as<int64_t>() : nullptr, d_y.p, y_dtype, d_fit.as<double>(), o, nullptr))
+        return rc;
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    return outs.fetch(ctx);
+}
+
+// Both kernels on one copy of the panel: what tsf_residual_autocorr and tsf_residual_last return, each bit for bit, for
+// the caller who wants both (the copy-in of y and fitted is most of either call).
+extern "C" int tsf_residual_autocorr_last(tsf_ctx *ctx, int64_t N, int32_t T, const int64_t *offsets, const void *y,
+                                          int32_t y_dtype, const double *fitted, const tsf_ar_args *args, tsf_ar_out *out,
+                                          tsf_ar_last_out *last)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    tsf_ar_args a;
+    if (int rc = check_ar_call(ctx, N, T, offsets, y, y_dtype, fitted, args, out, &a)) return rc;
+    if (int rc = check_ar_last_call(ctx, N, T, offsets, y, y_dtype, fitted, last)) return rc;
+    if (N == 0) return 0;
+    const size_t rows = offsets ? (size_t)offsets[N] : (size_t)N * T, n = (size_t)N;
+    DevBuf d_off, d_y, d_fit;
+    HostOuts outs;
+    if (offsets) HIP_TRY(ctx, d_off.put(offsets, 8 * (n + 1)));
+    HIP_TRY(ctx, d_y.put(y, ysize(y_dtype) * rows));
+    HIP_TRY(ctx, d_fit.put(fitted, 8 * rows));
+    tsf_ar_out o;
+    memset(&o, 0, sizeof(o));
+    o.phi = outs.want(out->phi, 8 * n); o.status = outs.want(out->status, 4 * n);
+    o.phi_raw = outs.want(out->phi_raw, 8 * n); o.n_pairs = outs.want(out->n_pairs, 8 * n);
+    o.scale = outs.want(out->scale, 8 * n);
+    tsf_ar_last_out l;
+    memset(&l, 0, sizeof(l));
+    l.last_resid = outs.want(last->last_resid, 8 * n); l.last_gap = outs.want(last->last_gap, 4 * n);
+    l.status = outs.want(last->status, 4 * n);
+    if (int rc = outs.ready(ctx)) return rc;
+    const int64_t *off = offsets ? d_off.as<int64_t>() : nullptr;
+    if (int rc = ar_run(ctx, N, T, off, d_y.p, y_dtype, d_fit.as<double>(), a, o, nullptr)) return rc;
+    if (int rc = ar_last_run(ctx, N, T, off, d_y.p, y_dtype, d_fit.as<double>(), l, nullptr)) return rc;
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    return outs.fetch(ctx);
+}
+
+// p0 = phi^steps: phi multiplied by itself steps - 1 more times, one rounding each.  The loop stops at the first zero (an
+// underflow, or phi == 0) and keeps that zero with its sign.
+static double ar_start_p0(double phi, int32_t steps)
+{
+    double p0 = phi;
+    for (int32_t k = 1; k < steps && p0 != 0.0; ++k) p0 = p0 * phi;
+    return p0;
+}
+
+extern "C" int tsf_set_noise_ar_start(tsf_ctx *ctx, const double *resid, const int32_t *steps, int64_t n)
+{
+    if (!ctx) return -1;
+    ctx->ar_start_pending.clear();
+    if (!resid || !steps || n <= 0) return 0;
+    char msg[200];
+    if (ctx->ar_pending.size() != 2 * (size_t)n) {
+        const long long pending = (long long)(ctx->ar_pending.size() / 2);
+        ctx->ar_pending.clear();
+        if (pending == 0)
+            return fail(ctx, "tsf_set_noise_ar_start: no tsf_set_noise_ar setting is pending (phi first, then the start)");
+        snprintf(msg, sizeof(msg), "tsf_set_noise_ar_start was given %lld series and the pending tsf_set_noise_ar setting has "
+                 "%lld (the setting is cleared)", (long long)n, pending);
+        return fail(ctx, msg);
+    }
+    for (int64_t i = 0; i < n; ++i) {
+        if (!std::isfinite(resid[i])) {
+            snprintf(msg, sizeof(msg), "resid[%lld] = %g: a residual must be finite (the setting is cleared)", (long long)i, resid[i]);
+            ctx->ar_pending.clear();
+            return fail(ctx, msg);
+        }
+        if (steps[i] < 1) {
+            snprintf(msg, sizeof(msg), "steps[%lld] = %d: the first future row lies at least one row behind the last residual "
+                     "(the setting is cleared)", (long long)i, (int)steps[i]);
+            ctx->ar_pending.clear();
+            return fail(ctx, msg);
+        }
+    }
+    try {
+        ctx->ar_start_pending.resize(3 * (size_t)n);
+    } catch (const std::bad_alloc &) {
+        ctx->ar_start_pending.clear();
+        ctx->ar_pending.clear();
+        return fail(ctx, "tsf_set_noise_ar_start: out of host memory");
+    }
+    for (int64_t i = 0; i < n; ++i) {
+        const double p0 = ar_start_p0(ctx->ar_pending[2 * (size_t)i], steps[i]);
+        ctx->ar_start_pending[3 * (size_t)i] = p0;
+        ctx->ar_start_pending[3 * (size_t)i + 1] = std::sqrt(1.0 - p0 * p0);
+        ctx->ar_start_pending[3 * (size_t)i + 2] = resid[i] * p0;
+    }
+    return 0;
+}
+
+extern "C" int tsf_noise_ar_mean(int64_t n, const double *phi, const double *resid, const int32_t *steps, int32_t H,
+                                 double *mean)
+{
+    if (n < 0 || H < 0 || (n > 0 && (!phi || !resid || !steps)) || (n > 0 && H > 0 && !mean)) return -1;
+    for (int64_t i = 0; i < n; ++i)
+        if (!(std::fabs(phi[i]) < 1.0) || !std::isfinite(resid[i]) || steps[i] < 1) return -1;
+    for (int64_t i = 0; i < n; ++i) {
+        double m = resid[i] * ar_start_p0(phi[i], steps[i]);
+        for (int32_t h = 0; h < H; ++h) {
+            mean[(size_t)i * H + h] = m;
+            m = phi[i] * m;
+        }
+    }
+    return 0;
+}
+
 extern "C" int tsf_set_noise_ar(tsf_ctx *ctx, const double *phi, int64_t n)
 {
     if (!ctx) return -1;
+    ctx->ar_start_pending.clear();
     ctx->ar_pending.clear();
     if (!phi || n <= 0) return 0;
     for (int64_t i = 0; i < n; ++i)

@@ -3,6 +3,8 @@
 //   ar_series_kernel    one wave per series: y and fitted are read once; the residual of row t - 1 comes from the
 //                       neighbouring lane (lane 0: from lane 63 of the sweep's step before), which is the value a
 //                       second read would form, bit for bit
+//   ar_last_kernel      one wave per series: the last present row's residual and the rows behind it (tsf_residual_last,
+//                       what the conditioned start of the chain is formed from); described at the kernel
 // The two sums over the rows (ss over the present rows, C over the pairs) have the library's shape: lane l adds rows
 // (pairs) l, l + 64, ... in ascending order from +0.0, the 64 partials are combined by the xor butterfly 1, 2, 4, 8,
 // 16, 32 (corr_wave_sum).  An absent row or pair adds +0.0, which changes no bit of a partial.
@@ -65,6 +67,49 @@ __global__ __launch_bounds__(AR_WAVES * 64) void ar_series_kernel(ArArgs a, int 
     if (a.phi_raw) a.phi_raw[n] = raw;
     if (a.n_pairs) a.n_pairs[n] = np;
     if (a.scale) a.scale[n] = (ss == 0.0) ? NaN : __builtin_sqrt(var);
+}
+
+// ar_last_kernel (tsf_residual_last): the residual of each series' last present row and the number of rows behind it.
+// One wave per series.  The wave walks the series from its end in blocks of 64 rows (the first block holds rows
+// len - 64 .. len - 1; a lane in front of row 0 holds an absent row), every lane forms its row's residual, and a ballot
+// over "finite" names the highest present row of the block; its value comes from that lane by a shuffle.  The loop ends
+// at the first block with a present row, so a series whose final row is present reads 64 rows.
+struct ArLastArgs {
+    const void *y;              // as ArArgs
+    const double *fitted;
+    const int64_t *offsets;     // [N + 1], or null = aligned [N][T]
+    int64_t N;
+    int32_t T, y_dtype;
+    double *last_resid;         // [N]
+    int32_t *last_gap, *status; // [N]
+};
+
+__global__ __launch_bounds__(AR_WAVES * 64) void ar_last_kernel(ArLastArgs a, int ok_status, int no_row_status)
+{
+    const int64_t n = (int64_t)blockIdx.x * AR_WAVES + (threadIdx.x >> 6);
+    if (n >= a.N) return;       // (a whole wave: no lane of it reaches the ballot)
+    const int lane = threadIdx.x & 63;
+    const int64_t r0 = a.offsets ? a.offsets[n] : n * a.T;
+    const int64_t len = a.offsets ? a.offsets[n + 1] - r0 : (int64_t)a.T;
+    double resid = 0.0;
+    int64_t gap = len;
+    int st = no_row_status;
+    for (int64_t top = len; top > 0; top -= 64) {           // (the bound is the wave's: every lane takes every step)
+        const int64_t t = top - 64 + lane;
+        const double r = (t >= 0) ? load_y(a.y, a.y_dtype, r0 + t) - a.fitted[r0 + t] : __builtin_nan("");
+        const unsigned long long present = __ballot(__builtin_isfinite(r));
+        if (present) {
+            const int hi = 63 - __builtin_clzll(present);
+            resid = __shfl(r, hi, 64);
+            gap = len - 1 - (top - 64 + hi);
+            st = ok_status;
+            break;
+        }
+    }
+    if (lane != 0) return;
+    a.last_resid[n] = resid;
+    a.last_gap[n] = (int32_t)gap;
+    a.status[n] = st;
 }
 
 }  // namespace tsf

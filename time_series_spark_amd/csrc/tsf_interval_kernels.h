@@ -9,7 +9,11 @@
 //   interval_sample_kernel      one thread per (series, sample): sweeps the future rows, writes
 //                               samples[series][row][sample] (and, where asked, the sampled trend alike); its
 //                               <true> instance chains the noise of a sample's rows (tsf_set_noise_ar), which is
-//                               this library's own and not the oracle's: tests/ar_ref.py restates it
+//                               this library's own and not the oracle's: tests/ar_ref.py restates it; its
+//                               <true, true> instance starts that chain conditioned on the history's last residual
+//                               (tsf_set_noise_ar_start; tests/ar_start_ref.py)
+//   ar_start_shift_kernel       one thread per (series, row): the conditioned start's mean added to the chunk's additive piece
+//                               and to yhat, behind predict_kernel and in front of the sample kernel
 //   interval_percentile_kernel  one workgroup per (series, row): bitonic sort of the samples in LDS,
 //                               the two percentiles by linear interpolation (np.nanpercentile)
 //   quantile_kernel             the same sort once per (series, row), then any number of levels from the sorted
@@ -72,11 +76,14 @@ struct IntervalArgs {
     double *lower, *upper;      // [N][H]
     double *cum_samples;        // optional [n_chunk][H][NS]: each sample's running sum over rows 0..h (tsf_predict_quantiles)
     const double *noise_ar;     // optional [N][2]: each series' (phi, sqrt(1 - phi^2)) of tsf_set_noise_ar (the AR instance only)
+    const double *ar_start;     // optional [N][3]: each series' (p0, c0, m0) of tsf_set_noise_ar_start (the START instance only)
 };
 
 // AR: the instance that chains the observation noise of a sample's rows (tsf_set_noise_ar); the other instance is the
-// independent draw, whose code knows nothing of the chain.
-template <bool AR>
+// independent draw, whose code knows nothing of the chain.  START (with AR): the chain starts conditioned on the
+// history's last residual, e_0 = c0 z_0; the conditional mean is not this kernel's business: ar_start_shift_kernel has
+// put it into xa (and yhat) before.
+template <bool AR, bool START = false>
 __global__ __launch_bounds__(256) void interval_sample_kernel(IntervalArgs a)
 {
     const int64_t nl = blockIdx.x, n = a.n0 + nl;
@@ -112,6 +119,8 @@ __global__ __launch_bounds__(256) void interval_sample_kernel(IntervalArgs a)
     // stationary start), e_h = phi e_{h-1} + c z_h, two products and one add, each rounded
     double ar_phi = 0.0, ar_c = 0.0, ar_e = 0.0;
     if (AR) { ar_phi = a.noise_ar[2 * (size_t)n]; ar_c = a.noise_ar[2 * (size_t)n + 1]; }
+    double ar_c0 = 1.0;
+    if (START) ar_c0 = a.ar_start[3 * (size_t)n + 1];
     for (int h = 0; h < H; ++h) {
         const double th_ = t[h];
         if (h == 0 || th_ < t_last) {       // (re)start the sweep: the stream is replayed from 0
@@ -152,6 +161,7 @@ __global__ __launch_bounds__(256) void interval_sample_kernel(IntervalArgs a)
         double z = __builtin_sqrt(-2.0 * dm_log(u1)) * cs;
         if (AR) {
             // (a select, not 0 * e + 1 * z: a series with phi == 0 keeps the independent draw's bits)
+            if (START && h == 0 && ar_phi != 0.0) z = ar_c0 * z;
             if (h > 0 && ar_phi != 0.0) z = ar_phi * ar_e + ar_c * z;
             ar_e = z;
         }
@@ -163,6 +173,36 @@ __global__ __launch_bounds__(256) void interval_sample_kernel(IntervalArgs a)
         }
         if (a.trend_samples) a.trend_samples[(size_t)nl * H * a.NS + s + (size_t)h * a.NS] = trend;
     }
+}
+
+// The conditional mean of the conditioned start, in y units: m_0 = m0, m_h = phi * m_(h-1) (one product each, what
+// tsf_noise_ar_mean forms), added to the additive piece xa [n_chunk][H] of the chunk (so every sample of the row is
+// trend * opm + (xa + m_h) + noise) and to yhat [N][H] of the call (yhat + m_h, one add).  A series with phi == 0 is not
+// touched.  One thread per (series, row) of the chunk: the thread of row h forms m_h by the h products of the recursion in
+// registers (the same roundings as a serial walk over the rows, without its chain of dependent memory round trips), so
+// neighbouring lanes touch neighbouring rows.
+struct ArStartArgs {
+    const double *noise_ar, *ar_start;      // [N][2], [N][3] of the call
+    double *xa;                             // [n_chunk][H] of the chunk
+    double *yhat;                           // [N][H] of the call
+    int64_t n0, n_chunk;
+    int H;
+};
+
+__global__ __launch_bounds__(256) void ar_start_shift_kernel(ArStartArgs a)
+{
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= a.n_chunk * a.H) return;
+    const int64_t i = g / a.H;
+    const int h = (int)(g - i * a.H);
+    const int64_t n = a.n0 + i;
+    const double phi = a.noise_ar[2 * (size_t)n];
+    if (phi == 0.0) return;
+    double m = a.ar_start[3 * (size_t)n + 2];
+    for (int k = 0; k < h; ++k) m = phi * m;
+    a.xa[g] = a.xa[g] + m;
+    double *yh = a.yhat + (size_t)n * a.H + h;
+    *yh = *yh + m;
 }
 
 // The sort of the per-row kernels (here, tsf_score_kernels.h and tsf_window_kernels.h): NSP values in LDS (a power of

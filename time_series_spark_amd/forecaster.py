@@ -631,9 +631,22 @@ def conditional_extra(spec, ds_ns, conditions=None, extra=None, offsets=None, ct
 
 
 def predict(spec, theta, y_scale, grid, ds_future_ns, floor=None, cap=None, extra_future=None,
-            want_int=False, ctx=None, devices=None):
+            want_int=False, ctx=None, devices=None, noise_ar=None):
     """yhat [N][H] (float64) and, if want_int, the reference's int-truncated + floor-clamped
-    column (prophet_scorer.py:73-84).  ds_future_ns: [H] (shared) or [N][H]."""
+    column (prophet_scorer.py:73-84).  ds_future_ns: [H] (shared) or [N][H].  noise_ar: a NoiseAR.conditioned() object
+    -- yhat plus the conditional mean of the AR(1) noise given the history's last residual (tsf_noise_ar_mean; one
+    numpy add, series with phi == 0 untouched): the corrected point forecast without a draw, the yhat of the drawing
+    calls with the same noise_ar."""
+    if noise_ar is not None:
+        start = _noise_ar_phi(noise_ar, len(np.asarray(theta)), ds_future_ns)
+        if not isinstance(start, _NoiseArArmed):
+            raise ValueError('predict takes noise_ar only as a NoiseAR.conditioned() object: a phi alone does not move yhat')
+        if want_int:
+            raise ValueError('noise_ar together with want_int: the integer column is the uncorrected forecast\'s')
+        yhat = predict(spec, theta, y_scale, grid, ds_future_ns, floor=floor, cap=cap, extra_future=extra_future,
+                       ctx=ctx, devices=devices)
+        mean = noise_ar_mean(start.phi, start.resid, start.steps, yhat.shape[1])
+        return np.where((start.phi != 0.0)[:, None], yhat + mean, yhat)
     devs = None if ctx is not None else resolve_devices(devices)
     if devs and len(theta) >= 2 * MIN_SERIES_PER_DEVICE:
         N = len(theta)
@@ -1357,13 +1370,33 @@ def predict_windows(spec, theta, y_scale, grid, ds_future_ns, windows, quantiles
 class NoiseAR(object):
     """What residual_autocorrelation returns, per series: phi [N] (clipped to [0, phi_max]: what noise_ar= takes),
     phi_raw [N] (NaN without pairs), n_pairs [N] int64, scale [N] (the residual root mean square), status [N]
-    (_lib.AR_*)."""
+    (_lib.AR_*); the residuals' state at the end of the history (residual_last): last_resid [N] (the last present row's
+    residual, y units), last_gap [N] int32 (the rows behind it), and, from fit_residual_autocorrelation, last_ds_ns [N]
+    int64 (the date of each series' final history row, present or not; the smallest int64 for an empty series).  The
+    last three are None on an object built without them."""
 
-    def __init__(self, phi, phi_raw, n_pairs, scale, status):
+    def __init__(self, phi, phi_raw, n_pairs, scale, status, last_resid=None, last_gap=None, last_ds_ns=None):
         self.phi, self.phi_raw, self.n_pairs, self.scale, self.status = phi, phi_raw, n_pairs, scale, status
+        self.last_resid, self.last_gap, self.last_ds_ns = last_resid, last_gap, last_ds_ns
 
-    def frame(self, keys=None):
-        """One row per series: series (the index, or `keys` [N]), phi, phi_raw, n_pairs, scale, status."""
+    def conditioned(self, lead=1):
+        """What noise_ar= takes for a chain that starts conditioned on the history's last residual (include/tsf.h
+        "the conditioned start"): phi, resid = last_resid and steps = last_gap + lead.  lead (an int or [N], >= 1): the
+        rows from the end of the history to the first future row -- 1 where the forecast begins at the next row."""
+        if self.last_resid is None or self.last_gap is None:
+            raise ValueError('this NoiseAR has no last_resid / last_gap (residual_last; residual_autocorrelation fills them)')
+        N = len(self.phi)
+        lead = np.asarray(lead)
+        if lead.ndim > 1 or (lead.ndim == 1 and lead.shape != (N,)) or not np.issubdtype(lead.dtype, np.integer):
+            raise ValueError('lead must be an int or [N] ints')
+        if (lead < 1).any():
+            raise ValueError('lead must be >= 1: the first future row lies behind the history')
+        steps = np.asarray(self.last_gap, dtype=np.int64) + lead
+        return NoiseARStart(self.phi, self.last_resid, steps, self.last_ds_ns)
+
+    def frame(self, keys=None, last=False):
+        """One row per series: series (the index, or `keys` [N]), phi, phi_raw, n_pairs, scale, status; with last=True
+        the columns last_resid, last_gap (and last_ds_ns where known) behind them."""
         import pandas as pd
         N = len(self.phi)
         series = np.arange(N, dtype=np.int64) if keys is None else np.asarray(keys)
@@ -1371,7 +1404,56 @@ class NoiseAR(object):
             raise ValueError('keys must be [N]')
         cols = {'series': list(series) if series.ndim > 1 else series, 'phi': self.phi, 'phi_raw': self.phi_raw,
                 'n_pairs': self.n_pairs, 'scale': self.scale, 'status': self.status}
+        if last:
+            if self.last_resid is None or self.last_gap is None:
+                raise ValueError('this NoiseAR has no last_resid / last_gap')
+            cols['last_resid'], cols['last_gap'] = self.last_resid, self.last_gap
+            if self.last_ds_ns is not None:
+                cols['last_ds_ns'] = self.last_ds_ns
         return pd.DataFrame(cols, columns=list(cols))
+
+
+class NoiseARStart(object):
+    """NoiseAR.conditioned(): phi [N], resid [N] (y units), steps [N] int32 (>= 1: rows from the last present history
+    row to the first future row), last_ds_ns [N] int64 or None -- what noise_ar= takes for the conditioned start."""
+
+    def __init__(self, phi, resid, steps, last_ds_ns=None):
+        self.phi = np.ascontiguousarray(phi, dtype=np.float64)
+        self.resid = np.ascontiguousarray(resid, dtype=np.float64)
+        steps = np.asarray(steps)
+        N = len(self.phi)
+        if self.phi.shape != (N,) or self.resid.shape != (N,) or steps.shape != (N,):
+            raise ValueError('phi, resid and steps must be [N]')
+        if not np.isfinite(self.resid).all():
+            raise ValueError('resid must be finite')
+        if not np.issubdtype(steps.dtype, np.integer) or (steps < 1).any() or (steps > np.iinfo(np.int32).max).any():
+            raise ValueError('steps must be integers in [1, 2^31 - 1]')
+        self.steps = np.ascontiguousarray(steps, dtype=np.int32)
+        self.last_ds_ns = None if last_ds_ns is None else np.ascontiguousarray(last_ds_ns, dtype=np.int64)
+        if self.last_ds_ns is not None and self.last_ds_ns.shape != (N,):
+            raise ValueError('last_ds_ns must be [N]')
+
+
+class _NoiseArArmed(object):
+    """a checked NoiseARStart on its way to the library (_noise_ar_phi -> _set_noise_ar)"""
+
+    def __init__(self, start):
+        self.phi, self.resid, self.steps = start.phi, start.resid, start.steps
+
+
+def noise_ar_mean(phi, resid, steps, H):
+    """The conditional mean [N][H] of the AR(1) noise in y units (include/tsf.h tsf_noise_ar_mean; host only):
+    mean[i][0] = resid[i] * phi[i]^steps[i], mean[i][h] = phi[i] * mean[i][h - 1]."""
+    phi = np.ascontiguousarray(phi, dtype=np.float64)
+    resid = np.ascontiguousarray(resid, dtype=np.float64)
+    steps = np.ascontiguousarray(steps, dtype=np.int32)
+    N = len(phi)
+    if phi.shape != (N,) or resid.shape != (N,) or steps.shape != (N,) or int(H) < 0:
+        raise ValueError('phi, resid and steps must be [N], H >= 0')
+    mean = np.zeros((N, int(H)))
+    if _lib.load().tsf_noise_ar_mean(N, _lib._ptr(phi), _lib._ptr(resid), _lib._ptr(steps), int(H), _lib._ptr(mean)) != 0:
+        raise ValueError('tsf_noise_ar_mean: |phi| < 1, finite resid and steps >= 1 are required')
+    return mean
 
 
 def _ar_args(phi_max, min_pairs):
@@ -1401,17 +1483,48 @@ def residual_autocorrelation(y, fitted, offsets=None, phi_max=0.95, min_pairs=8,
     phi, raw, scale = np.zeros(N), np.zeros(N), np.zeros(N)
     n_pairs, status = np.zeros(N, np.int64), np.zeros(N, np.int32)
     out = _lib.TsfArOut(phi.ctypes.data, raw.ctypes.data, n_pairs.ctypes.data, scale.ctypes.data, status.ctypes.data)
-    ctx.check(_lib.load().tsf_residual_autocorr(ctx.handle, N, T, _lib._ptr(offsets),
-                                                y.ctypes.data, code, fitted.ctypes.data, ctypes.byref(a), ctypes.byref(out)))
-    return NoiseAR(phi, raw, n_pairs, scale, status)
+    last_resid, last_gap, last_status = np.zeros(N), np.zeros(N, np.int32), np.zeros(N, np.int32)
+    last = _lib.TsfArLastOut(last_resid.ctypes.data, last_gap.ctypes.data, last_status.ctypes.data)
+    # (both kernels on one copy of the panel: tsf_residual_autocorr's outputs bit for bit, and tsf_residual_last's)
+    ctx.check(_lib.load().tsf_residual_autocorr_last(ctx.handle, N, T, _lib._ptr(offsets), y.ctypes.data, code,
+                                                     fitted.ctypes.data, ctypes.byref(a), ctypes.byref(out), ctypes.byref(last)))
+    return NoiseAR(phi, raw, n_pairs, scale, status, last_resid, last_gap)
+
+
+def residual_last(y, fitted, offsets=None, ctx=None):
+    """The residuals' state at the end of each series' history (include/tsf.h tsf_residual_last): y, fitted, offsets as
+    residual_autocorrelation takes them -> (last_resid [N], last_gap [N] int32, status [N] int32): the residual of the
+    last present (finite) row, the rows behind it, and _lib.AR_OK or _lib.AR_NO_ROW (then +0.0 and the row count)."""
+    fitted = np.ascontiguousarray(fitted, dtype=np.float64)
+    y, offsets, N, T = _screen_panel(y, offsets, (fitted,), ('fitted',))
+    if offsets is None and T < 1:
+        raise ValueError('aligned panel: y must be [N][T], T >= 1')
+    code = _lib.y_dtype_code(y)
+    ctx = ctx or get_context()
+    last_resid, last_gap, status = np.zeros(N), np.zeros(N, np.int32), np.zeros(N, np.int32)
+    out = _lib.TsfArLastOut(last_resid.ctypes.data, last_gap.ctypes.data, status.ctypes.data)
+    ctx.check(_lib.load().tsf_residual_last(ctx.handle, N, T, _lib._ptr(offsets), y.ctypes.data, code, fitted.ctypes.data,
+                                            ctypes.byref(out)))
+    return last_resid, last_gap, status
 
 
 def fit_residual_autocorrelation(spec, res, ds_ns, y, offsets=None, floor=None, cap=None, extra=None, phi_max=0.95,
                                  min_pairs=8, ctx=None):
     """residual_autocorrelation of a panel's fits `res` (the FitResult of this panel): fitted is predict on the
-    history's own dates (fitted_history), aligned ds_ns [T] or ragged with offsets."""
+    history's own dates (fitted_history), aligned ds_ns [T] or ragged with offsets.  last_resid and last_gap come from
+    the same fitted (one more launch), last_ds_ns from ds_ns: the date of each series' final history row."""
     fitted = fitted_history(spec, res, ds_ns, offsets, floor, cap, extra, ctx=ctx)
-    return residual_autocorrelation(y, fitted, offsets, phi_max=phi_max, min_pairs=min_pairs, ctx=ctx)
+    est = residual_autocorrelation(y, fitted, offsets, phi_max=phi_max, min_pairs=min_pairs, ctx=ctx)
+    ds = np.asarray(ds_ns, dtype=np.int64)
+    N = len(est.phi)
+    if offsets is None:
+        est.last_ds_ns = np.full(N, ds[-1], dtype=np.int64)
+    else:
+        off = np.asarray(offsets, dtype=np.int64)
+        est.last_ds_ns = np.full(N, np.iinfo(np.int64).min, dtype=np.int64)
+        some = off[1:] > off[:-1]
+        est.last_ds_ns[some] = ds[off[1:][some] - 1]
+    return est
 
 
 def _noise_ar_phi(noise_ar, N, ds_future_ns):
@@ -1419,6 +1532,15 @@ def _noise_ar_phi(noise_ar, N, ds_future_ns):
     chain runs in row order, so with it the future rows of every series must be strictly increasing."""
     if noise_ar is None:
         return None
+    if isinstance(noise_ar, NoiseARStart):
+        phi = _noise_ar_phi(noise_ar.phi, N, ds_future_ns)
+        if noise_ar.last_ds_ns is not None:
+            ds = np.asarray(ds_future_ns, dtype=np.int64)
+            first = ds[..., 0] if ds.ndim and ds.shape[-1] else None
+            if first is not None and (first <= noise_ar.last_ds_ns).any():
+                raise ValueError('a conditioned noise_ar needs future rows after the history: a first future row lies at or '
+                                 'before last_ds_ns')
+        return _NoiseArArmed(noise_ar)
     phi = noise_ar.phi if isinstance(noise_ar, NoiseAR) else noise_ar
     phi = np.ascontiguousarray(phi, dtype=np.float64)
     if phi.shape != (N,):
@@ -1433,7 +1555,11 @@ def _noise_ar_phi(noise_ar, N, ds_future_ns):
 
 def _set_noise_ar(ctx, phi):
     """tsf_set_noise_ar for the library call that follows at once (the setting is consumed by it); None: nothing."""
-    if phi is not None:
+    if isinstance(phi, _NoiseArArmed):
+        a = phi
+        ctx.check(_lib.load().tsf_set_noise_ar(ctx.handle, a.phi.ctypes.data, len(a.phi)))
+        ctx.check(_lib.load().tsf_set_noise_ar_start(ctx.handle, a.resid.ctypes.data, a.steps.ctypes.data, len(a.phi)))
+    elif phi is not None:
         ctx.check(_lib.load().tsf_set_noise_ar(ctx.handle, phi.ctypes.data, len(phi)))
 
 
@@ -2284,6 +2410,8 @@ class TemporalQuantiles(Quantiles):
 
 def _temporal_phi(noise_ar, N, ds_ns, name):
     """_noise_ar_phi with the temporal entry's range: phi in [0, 1)"""
+    if isinstance(noise_ar, NoiseARStart):
+        raise ValueError('%s: predict_temporal keeps the stationary start (a conditioned noise_ar is not taken)' % name)
     phi = _noise_ar_phi(noise_ar, N, ds_ns)
     if phi is not None and (phi < 0).any():
         raise ValueError('%s values must be in [0, 1)' % name)
@@ -2296,6 +2424,9 @@ def _predict_temporal_call(spec, theta, y_scale, grid, ds_ns, windows, period_sp
                            period_noise_ar=None, uncertainty_samples=1000, seed=0, ctx=None):
     """One tsf_predict_temporal call -> dict of yhat and the outputs named in `want` (TEMPORAL_FIELDS).  Every
     argument-shape error is raised before the library is loaded."""
+    for name, v in (('noise_ar', noise_ar), ('period_noise_ar', period_noise_ar)):
+        if isinstance(v, NoiseARStart):
+            raise ValueError('%s: predict_temporal keeps the stationary start (a conditioned noise_ar is not taken)' % name)
     theta, N, y_scale, grid, ds_ns, shared, H, floor, cap, ex, key = _checked_forecast_inputs(
         spec, theta, y_scale, grid, ds_ns, floor, cap, extra_future, series_key)
     if not isinstance(windows, Windows):
