@@ -1327,3 +1327,17 @@ def test_packer_takes_the_reference_schemas_own_types_in_place(built):
     f32.loc[3, 'y'] = np.nan
     q = pk.pack_long_frame(f32)
     assert q.lengths[0] == T - 1 and not q.aligned and q.y.dtype == np.float64
+
+
+def test_the_share_solvers_build_without_hip(tmp_path):
+    """csrc/tsf_shares.cpp is host-only code: a plain C++17 compiler builds it with no ROCm include path, the object
+    asks for no HIP symbol, and it defines the four solvers of include/tsf.h that need no device."""
+    import subprocess
+    obj = str(tmp_path / 'tsf_shares.o')
+    subprocess.check_call(['g++', '-std=c++17', '-ffp-contract=off', '-I', 'include', '-c',
+                           os.path.join('time_series_spark_amd', 'csrc', 'tsf_shares.cpp'), '-o', obj], cwd=helpers.ROOT)
+    syms = [ln.split() for ln in subprocess.check_output(['nm', obj]).decode().splitlines()]
+    undefined = [s[-1] for s in syms if s[0] == 'U']
+    assert not [u for u in undefined if u.startswith('hip')], undefined
+    defined = {s[-1] for s in syms if len(s) == 3 and s[1] == 'T'}
+    assert {'tsf_reconcile_shares', 'tsf_reconcile_tree_shares', 'tsf_temporal_shares', 'tsf_noise_ar_mean'} <= defined

@@ -46,6 +46,7 @@
 #include "tsf_cond_kernels.h"
 #include "tsf_cv_plan.h"
 #include "tsf_fit_plan.h"
+#include "tsf_shares.h"
 
 using namespace tsf;
 
@@ -2344,14 +2345,20 @@ extern "C" int tsf_score_actuals(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, 
 
 // ---- group roll-ups: predictive quantiles of sums over series ---------------------------------------------
 
+// The directly fitted totals of one level's n slots -- the groups (tsf_rollup_set_totals) or the nodes of a level above
+// them (tsf_rollup_set_node_totals): allocated by the level's first such call and not before.
+struct FittedTotals {
+    OwnedDev<double> T, yT;         // [n][H][S] the draws of the totals, [n][H] their yhat
+    OwnedDev<int32_t> d_has;        // [n] device copy of has (with T)
+    std::vector<int32_t> has;       // [n] the slot has a total (host; empty until then)
+};
+
 // One level above the groups in a roll-up's tree (include/tsf.h "tree reconciliation"), n nodes.
 struct TreeLevel {
     int64_t n = 0;
     OwnedDev<double> A, C;          // [n][H][S] the bottom-up sum of the children's m; m, then c
     OwnedDev<double> yA, yC;        // [n][H]
-    OwnedDev<double> T, yT;         // the draws and yhat of the nodes' fitted totals: the first tsf_rollup_set_node_totals
-    OwnedDev<int32_t> d_has;        // [n] device copy of has (with T)
-    std::vector<int32_t> has;       // [n] the node has a total (host; empty until then)
+    FittedTotals fit;               // the nodes' fitted totals
     OwnedDev<int32_t> d_first, d_child, d_parent;   // [n + 1], [n_below]: each node's children, ascending; [n_below] parents
     std::vector<int64_t> parent;    // [n_below] the parent of each node of the level below (host)
 };
@@ -2376,11 +2383,7 @@ struct tsf_rollup {
     OwnedDev<double> ysum;          // [G][H]
     std::vector<int64_t> count;     // [G] members added so far (host)
     bool poisoned = false;          // a HIP failure in the middle of an add: the accumulators may be half-added
-    // reconciliation (tsf_rollup_set_totals): allocated by its first call and not before
-    OwnedDev<double> top;           // [G][H][S] the draws of the groups' directly fitted totals
-    OwnedDev<double> ytop;          // [G][H]
-    OwnedDev<int32_t> d_has_top;    // [G] device copy of has_top
-    std::vector<int32_t> has_top;   // [G] the group has a total (host; empty until the first set_totals)
+    FittedTotals top;               // reconciliation: the groups' fitted totals
     // correlated noise (tsf_rollup_set_noise_corr): allocated by that call and not before
     bool corr = false;              // a correlation is set: adds go through rollup_add_corr_kernel
     bool added = false;             // an add of N > 0 series has reached the accumulators
@@ -2461,46 +2464,32 @@ static int rollup_enter(tsf_rollup *r, bool no_corr = false)
     return 0;
 }
 
-// The small CSR of one add call, per scratch chunk [n0, n0 + nc): the groups the chunk touches (ascending) and, per
-// such group, its chunk-local members in ascending order.  One int32 buffer: touched | first | member.
-struct RollupPlan {
-    std::vector<int32_t> touched, first, member;            // all chunks, one after another
-    std::vector<size_t> t0, f0;                             // per chunk: where its touched / first entries start
+// The series of one call on a roll-up as its entries receive them (host pointers): the models, their forecast inputs on
+// the handle's calendar, and the group (or node) of each.
+struct RollupCall {
+    const tsf_spec *spec;
+    int64_t N;
+    const double *theta, *y_scale;
+    const tsf_grid_info *grid;
+    int32_t n_grids;
+    const double *floor_, *cap, *extra_future;
+    int32_t shared_extra;
+    const int64_t *series_key, *group;
 };
-
-static void rollup_plan(const int64_t *group, int64_t N, int64_t chunk, RollupPlan *P)
-{
-    P->member.resize((size_t)N);
-    std::vector<std::pair<int64_t, int32_t>> order;
-    for (int64_t n0 = 0; n0 < N; n0 += chunk) {
-        const int64_t nc = (N - n0 < chunk) ? N - n0 : chunk;
-        order.clear();
-        for (int64_t i = 0; i < nc; ++i) order.push_back({group[n0 + i], (int32_t)i});
-        std::sort(order.begin(), order.end());              // by group, then by index in the call
-        P->t0.push_back(P->touched.size());
-        P->f0.push_back(P->first.size());
-        for (int64_t i = 0; i < nc; ++i) {
-            if (i == 0 || order[i].first != order[i - 1].first) {
-                P->touched.push_back((int32_t)order[i].first);
-                P->first.push_back((int32_t)i);
-            }
-            P->member[(size_t)(n0 + i)] = order[i].second;
-        }
-        P->first.push_back((int32_t)nc);
-    }
-}
 
 // What tsf_rollup_add, tsf_rollup_set_totals and tsf_rollup_reconcile check of their series before anything is copied
 // or launched (the handle is not poisoned, N > 0).
-static int rollup_check_series(tsf_rollup *r, const tsf_spec *spec, int64_t N, const double *theta, const double *y_scale,
-                               const tsf_grid_info *grid, int32_t n_grids, const double *cap, const double *extra_future,
-                               const int64_t *series_key, const int64_t *group, int64_t G = -1 /* the handle's */)
+static int rollup_check_series(tsf_rollup *r, const RollupCall &c, int64_t G = -1 /* the handle's */)
 {
     tsf_ctx *ctx = r->ctx;
+    const tsf_spec *spec = c.spec;
+    const int64_t N = c.N, *group = c.group;
+    const tsf_grid_info *grid = c.grid;
+    const int32_t n_grids = c.n_grids;
     if (G < 0) G = r->G;
     if (N > 2147483647) return fail(ctx, "N must be < 2^31 per call");
-    if (!spec || !theta || !y_scale || !grid) return fail(ctx, "NULL input");
-    if (!series_key)
+    if (!spec || !c.theta || !c.y_scale || !grid) return fail(ctx, "NULL input");
+    if (!c.series_key)
         return fail(ctx, "series_key is required: the index-in-call default would give two calls the same streams");
     if (!group) return fail(ctx, "NULL group");
     if (n_grids != 1 && n_grids != N) return fail(ctx, "n_grids must be 1 or N");
@@ -2517,8 +2506,8 @@ static int rollup_check_series(tsf_rollup *r, const tsf_spec *spec, int64_t N, c
         int mode = 0;
         if (int rc = build_devspec(ctx, spec, &hs, &mode)) return rc;
     }
-    if (spec->n_extra > 0 && !extra_future) return fail(ctx, "extra_future is NULL");
-    if (spec->growth == TSF_GROWTH_LOGISTIC && !cap) return fail(ctx, "logistic growth needs cap");
+    if (spec->n_extra > 0 && !c.extra_future) return fail(ctx, "extra_future is NULL");
+    if (spec->growth == TSF_GROWTH_LOGISTIC && !c.cap) return fail(ctx, "logistic growth needs cap");
     return 0;
 }
 
@@ -2529,13 +2518,12 @@ struct RollupSeries {
     DevBuf d_ds;
     ForecastUpload up;
 
-    int upload(tsf_rollup *r, const tsf_spec *spec, int64_t N, const double *theta, const double *y_scale,
-               const tsf_grid_info *grid, int32_t n_grids, const double *floor_, const double *cap,
-               const double *extra_future, int32_t shared_extra, const int64_t *series_key)
+    int upload(tsf_rollup *r, const RollupCall &c)
     {
         tsf_ctx *ctx = r->ctx;
         const int32_t H = r->H;
-        const int shared = (spec->n_extra == 0 || shared_extra) ? 1 : 0;
+        const int64_t N = c.N;
+        const int shared = (c.spec->n_extra == 0 || c.shared_extra) ? 1 : 0;
         // the calendar is the handle's, on the device already; the inputs beside it are uploaded
         const int64_t *ds_dev = r->d_ds;
         if (!shared) {
@@ -2550,8 +2538,9 @@ struct RollupSeries {
             HIP_TRY(ctx, d_ds.put(ds_rep.data(), 8 * (size_t)N * H));
             ds_dev = d_ds.as<int64_t>();
         }
-        const ForecastIn h = {N, H, theta, y_scale, grid, n_grids, ds_dev, shared, floor_, cap, extra_future, series_key};
-        return up.upload(ctx, spec, h, true);
+        const ForecastIn h = {N, H, c.theta, c.y_scale, c.grid, c.n_grids, ds_dev, shared, c.floor_, c.cap, c.extra_future,
+                              c.series_key};
+        return up.upload(ctx, c.spec, h, true);
     }
 };
 
@@ -2559,23 +2548,21 @@ struct RollupSeries {
 // checked: the series' draws added to the cells of their groups by rollup_add_kernel -- on a handle with a noise
 // correlation set (tsf_rollup_add only: set_totals is refused there) by rollup_add_corr_kernel, after one
 // rollup_noise_scale_kernel over the call's series.
-static int rollup_accumulate(tsf_rollup *r, const tsf_spec *spec, int64_t N, const double *theta, const double *y_scale,
-                             const tsf_grid_info *grid, int32_t n_grids, const double *floor_, const double *cap,
-                             const double *extra_future, int32_t shared_extra, const int64_t *series_key,
-                             const int64_t *group, double *acc, double *ysum)
+static int rollup_accumulate(tsf_rollup *r, const RollupCall &c, double *acc, double *ysum)
 {
     tsf_ctx *ctx = r->ctx;
+    const tsf_spec *spec = c.spec;
+    const int64_t N = c.N;
     const int32_t H = r->H, S = r->S;
     const int64_t chunk = draw_chunk_series(N, H, S, 1);       // draw_chunks' chunks: one sample buffer
     RollupPlan P;
     try {
-        rollup_plan(group, N, chunk, &P);
+        rollup_plan(c.group, N, chunk, &P);
     } catch (const std::bad_alloc &) {
         return fail(ctx, "tsf_rollup: out of host memory");
     }
     RollupSeries in;
-    if (int rc = in.upload(r, spec, N, theta, y_scale, grid, n_grids, floor_, cap, extra_future, shared_extra, series_key))
-        return rc;
+    if (int rc = in.upload(r, c)) return rc;
     DevBuf d_yh, d_csr, d_sn;
     HIP_TRY(ctx, d_yh.alloc(8 * (size_t)N * H));
     if (r->corr) HIP_TRY(ctx, d_sn.alloc(8 * (size_t)N));
@@ -2596,10 +2583,10 @@ static int rollup_accumulate(tsf_rollup *r, const tsf_spec *spec, int64_t N, con
         HIP_TRY(ctx, hipGetLastError());
     }
     auto after = [&](int64_t n0, int64_t nc, const DrawBufs &b) -> int {
-        const size_t c = (size_t)(n0 / chunk);
-        const size_t n_touched = (c + 1 < P.t0.size() ? P.t0[c + 1] : n_t) - P.t0[c];
+        const size_t k = (size_t)(n0 / chunk);
+        const size_t n_touched = (k + 1 < P.t0.size() ? P.t0[k + 1] : n_t) - P.t0[k];
         ra.samples = b.samp; ra.yhat = d_yh.as<double>() + (size_t)n0 * H;
-        ra.touched = d_touched + P.t0[c]; ra.first = d_first + P.f0[c]; ra.member = d_member + n0;
+        ra.touched = d_touched + P.t0[k]; ra.first = d_first + P.f0[k]; ra.member = d_member + n0;
         (void)nc;
         const dim3 grid((unsigned)(n_touched * (size_t)H), (unsigned)((S + 255) / 256));
         if (r->corr) {
@@ -2634,11 +2621,9 @@ extern "C" int tsf_rollup_add(tsf_rollup *r, const tsf_spec *spec, int64_t N, co
     if (N < 0) return fail(ctx, "N must be >= 0");
     if (int rc = check_noise_ar_count(ctx, N)) return rc;
     if (N == 0) return 0;
-    if (int rc = rollup_check_series(r, spec, N, theta, y_scale, grid, n_grids, cap, extra_future, series_key, group))
-        return rc;
-    if (int rc = rollup_accumulate(r, spec, N, theta, y_scale, grid, n_grids, floor_, cap, extra_future, shared_extra,
-                                   series_key, group, r->acc, r->ysum))
-        return rc;
+    const RollupCall c = {spec, N, theta, y_scale, grid, n_grids, floor_, cap, extra_future, shared_extra, series_key, group};
+    if (int rc = rollup_check_series(r, c)) return rc;
+    if (int rc = rollup_accumulate(r, c, r->acc, r->ysum)) return rc;
     for (int64_t n = 0; n < N; ++n) r->count[(size_t)group[n]] += 1;
     r->added = true;
     if (r->tree) r->tree->solved = false;
@@ -3027,15 +3012,6 @@ extern "C" int tsf_residual_autocorr_last(tsf_ctx *ctx, int64_t N, int32_t T, co
     return outs.fetch(ctx);
 }
 
-// p0 = phi^steps: phi multiplied by itself steps - 1 more times, one rounding each.  The loop stops at the first zero (an
-// underflow, or phi == 0) and keeps that zero with its sign.
-static double ar_start_p0(double phi, int32_t steps)
-{
-    double p0 = phi;
-    for (int32_t k = 1; k < steps && p0 != 0.0; ++k) p0 = p0 * phi;
-    return p0;
-}
-
 extern "C" int tsf_set_noise_ar_start(tsf_ctx *ctx, const double *resid, const int32_t *steps, int64_t n)
 {
     if (!ctx) return -1;
@@ -3080,22 +3056,6 @@ extern "C" int tsf_set_noise_ar_start(tsf_ctx *ctx, const double *resid, const i
     return 0;
 }
 
-extern "C" int tsf_noise_ar_mean(int64_t n, const double *phi, const double *resid, const int32_t *steps, int32_t H,
-                                 double *mean)
-{
-    if (n < 0 || H < 0 || (n > 0 && (!phi || !resid || !steps)) || (n > 0 && H > 0 && !mean)) return -1;
-    for (int64_t i = 0; i < n; ++i)
-        if (!(std::fabs(phi[i]) < 1.0) || !std::isfinite(resid[i]) || steps[i] < 1) return -1;
-    for (int64_t i = 0; i < n; ++i) {
-        double m = resid[i] * ar_start_p0(phi[i], steps[i]);
-        for (int32_t h = 0; h < H; ++h) {
-            mean[(size_t)i * H + h] = m;
-            m = phi[i] * m;
-        }
-    }
-    return 0;
-}
-
 extern "C" int tsf_set_noise_ar(tsf_ctx *ctx, const double *phi, int64_t n)
 {
     if (!ctx) return -1;
@@ -3125,7 +3085,7 @@ extern "C" int tsf_rollup_set_noise_corr(tsf_rollup *r, const double *rho, const
 {
     if (int rc = rollup_enter(r)) return rc;
     tsf_ctx *ctx = r->ctx;
-    if (r->added || r->top)
+    if (r->added || r->top.T)
         return fail(ctx, "tsf_rollup_set_noise_corr after a tsf_rollup_add or tsf_rollup_set_totals: a correlation is set on an "
                          "empty roll-up");
     if (!rho) return fail(ctx, "NULL rho");
@@ -3264,32 +3224,22 @@ extern "C" int tsf_rollup_quantiles(tsf_rollup *r, int32_t n_q, const double *qu
 
 extern "C" int tsf_window_out_size(void) { return (int)sizeof(tsf_window_out); }
 
-// The windows of a call (host data, like the levels) and the observed window totals (device memory behind the entries).
-struct WindowCall {
-    int32_t K;
-    const int32_t *win_start, *win_end;
-    const double *y_win;
-};
-
 // the outputs that are read from the sorted window sums: they need the draws (of a roll-up: the accumulators)
 static bool window_wants_draws(const tsf_window_out &o)
 {
     return o.q || o.pit || o.crps || o.pinball || o.mean_crps || o.mean_pinball || o.coverage;
 }
 
-// the windows of a call against H: they index the sample buffer
+// the window checks of tsf_shares.cpp (WindowCall: tsf_shares.h), their message left in the context
 static int check_windows(tsf_ctx *ctx, int32_t H, const WindowCall &w)
 {
-    if (w.K < 1 || w.K > TSF_MAX_WINDOWS) return fail(ctx, "K must be in [1, TSF_MAX_WINDOWS]");
-    if (!w.win_start || !w.win_end) return fail(ctx, "NULL win_start or win_end");
-    for (int32_t k = 0; k < w.K; ++k)
-        if (w.win_start[k] < 0 || w.win_start[k] >= w.win_end[k] || w.win_end[k] > H) {
-            char msg[160];
-            snprintf(msg, sizeof(msg), "window %d = [%d, %d): a window needs 0 <= win_start < win_end <= H = %d", (int)k,
-                     (int)w.win_start[k], (int)w.win_end[k], (int)H);
-            return fail(ctx, msg);
-        }
-    return 0;
+    char msg[WINDOW_MSG];
+    return check_windows(H, w, msg) ? fail(ctx, msg) : 0;
+}
+static int check_disjoint_windows(tsf_ctx *ctx, int32_t H, const WindowCall &w)
+{
+    char msg[WINDOW_MSG];
+    return check_disjoint_windows(H, w, msg) ? fail(ctx, msg) : 0;
 }
 
 // What the three window entries check before anything is copied or launched: tsf_predict_quantiles' checks of the sample
@@ -3513,27 +3463,59 @@ extern "C" int tsf_rollup_windows(tsf_rollup *r, int32_t K, const int32_t *win_s
 
 extern "C" int tsf_reconcile_out_size(void) { return (int)sizeof(tsf_reconcile_out); }
 
-extern "C" int tsf_reconcile_shares(int64_t N, const int64_t *group, const double *w, int64_t G, const double *v,
-                                    double *share, double *share_total)
+// (tsf_reconcile_shares, the host-only solver of the shares: tsf_shares.cpp)
+
+// The two steps of tsf_rollup_set_totals and tsf_rollup_set_node_totals once the call's series are checked, for the
+// totals c of a level of n slots (`noun`s: c.group names each total's slot) kept in *f.
+// Claim: a slot takes one total, ever -- *has = the level's flags with this call's set; the level's buffers are
+// allocated by its first call.  Nothing of the handle's has changed yet but that.
+static int fitted_totals_claim(tsf_rollup *r, const char *entry, const char *noun, FittedTotals *f, int64_t n,
+                               const RollupCall &c, std::vector<int32_t> *has_out)
 {
-    if (N < 0 || G < 0 || (N > 0 && (!group || !share)) || (G > 0 && (!v || !share_total))) return -1;
-    for (int64_t n = 0; n < N; ++n) {
-        if (group[n] < 0 || group[n] >= G) return -1;
-        if (w && !(w[n] > 0.0 && std::isfinite(w[n]))) return -1;
+    tsf_ctx *ctx = r->ctx;
+    std::vector<int32_t> &has = *has_out;
+    try {
+        has = f->has;
+        has.resize((size_t)n, 0);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, (std::string(entry) + ": out of host memory").c_str());
     }
-    for (int64_t g = 0; g < G; ++g)
-        if (!std::isnan(v[g]) && !(v[g] > 0.0 && std::isfinite(v[g]))) return -1;
-    // W_g in share_total, from +0.0 in ascending member index
-    for (int64_t g = 0; g < G; ++g) share_total[g] = 0.0;
-    for (int64_t n = 0; n < N; ++n) share_total[group[n]] = share_total[group[n]] + (w ? w[n] : 1.0);
-    for (int64_t n = 0; n < N; ++n) {
-        const int64_t g = group[n];
-        share[n] = std::isnan(v[g]) ? 0.0 : (w ? w[n] : 1.0) / (v[g] + share_total[g]);
+    for (int64_t i = 0; i < c.N; ++i) {
+        if (has[(size_t)c.group[i]]) {
+            char msg[160];
+            snprintf(msg, sizeof(msg), "%s[%lld] = %lld: the %s has a total already (one total per %s)", noun,
+                     (long long)i, (long long)c.group[i], noun, noun);
+            return fail(ctx, msg);
+        }
+        has[(size_t)c.group[i]] = 1;
     }
-    for (int64_t g = 0; g < G; ++g) {
-        const double W = share_total[g];
-        share_total[g] = (std::isnan(v[g]) || W == 0.0) ? 0.0 : W / (v[g] + W);
+    if (!f->T) {
+        // a second accumulator: +0.0 everywhere, so that the add below leaves the draws themselves in it
+        // (the three become the handle's together or not at all: a failure frees what the locals hold)
+        OwnedDev<double> T, yT;
+        OwnedDev<int32_t> d_has;
+        const hipError_t e = [&]() -> hipError_t {
+            HIP_OK(T.alloc((size_t)n * r->H * r->S, true));
+            HIP_OK(yT.alloc((size_t)n * r->H, true));
+            HIP_OK(d_has.alloc((size_t)n, true));
+            return hipDeviceSynchronize();
+        }();
+        if (e != hipSuccess) return rollup_hip_fail(ctx, entry, e);
+        f->T.swap(T); f->yT.swap(yT); f->d_has.swap(d_has);
     }
+    return 0;
+}
+
+// Draw: the totals' draws into the claimed slots, then the flags of the claim made the level's.
+static int fitted_totals_draw(tsf_rollup *r, FittedTotals *f, const RollupCall &c, std::vector<int32_t> &has)
+{
+    tsf_ctx *ctx = r->ctx;
+    if (int rc = rollup_accumulate(r, c, f->T, f->yT)) return rc;
+    // (a failure of this copy leaves the device's flags behind the draws in T: poisoned like a failed add)
+    r->poisoned = true;
+    HIP_TRY(ctx, hipMemcpy(f->d_has, has.data(), 4 * has.size(), hipMemcpyHostToDevice));
+    r->poisoned = false;
+    f->has.swap(has);
     return 0;
 }
 
@@ -3548,47 +3530,11 @@ extern "C" int tsf_rollup_set_totals(tsf_rollup *r, const tsf_spec *spec, int64_
     if (int rc = refuse_noise_ar(ctx, "tsf_rollup_set_totals")) return rc;
     if (Gt < 0) return fail(ctx, "N must be >= 0");
     if (Gt == 0) return 0;
-    if (int rc = rollup_check_series(r, spec, Gt, theta, y_scale, grid, n_grids, cap, extra_future, series_key, group))
-        return rc;
+    const RollupCall c = {spec, Gt, theta, y_scale, grid, n_grids, floor_, cap, extra_future, shared_extra, series_key, group};
+    if (int rc = rollup_check_series(r, c)) return rc;
     std::vector<int32_t> has;
-    try {
-        has = r->has_top;
-        has.resize((size_t)r->G, 0);
-    } catch (const std::bad_alloc &) {
-        return fail(ctx, "tsf_rollup_set_totals: out of host memory");
-    }
-    for (int64_t n = 0; n < Gt; ++n) {
-        if (has[(size_t)group[n]]) {
-            char msg[160];
-            snprintf(msg, sizeof(msg), "group[%lld] = %lld: the group has a total already (one total per group)",
-                     (long long)n, (long long)group[n]);
-            return fail(ctx, msg);
-        }
-        has[(size_t)group[n]] = 1;
-    }
-    const size_t gh = (size_t)r->G * r->H;
-    if (!r->top) {
-        // the second accumulator: +0.0 everywhere, so that the add below leaves the draws themselves in it
-        // (the three become the handle's together or not at all: a failure frees what the locals hold)
-        OwnedDev<double> top, ytop;
-        OwnedDev<int32_t> d_has;
-        const hipError_t e = [&]() -> hipError_t {
-            HIP_OK(top.alloc(gh * r->S, true));
-            HIP_OK(ytop.alloc(gh, true));
-            HIP_OK(d_has.alloc((size_t)r->G, true));
-            return hipDeviceSynchronize();
-        }();
-        if (e != hipSuccess) return rollup_hip_fail(ctx, "tsf_rollup_set_totals", e);
-        r->top.swap(top); r->ytop.swap(ytop); r->d_has_top.swap(d_has);
-    }
-    if (int rc = rollup_accumulate(r, spec, Gt, theta, y_scale, grid, n_grids, floor_, cap, extra_future, shared_extra,
-                                   series_key, group, r->top, r->ytop))
-        return rc;
-    // (a failure of this copy leaves the device's flags behind the draws in `top`: poisoned like a failed add)
-    r->poisoned = true;
-    HIP_TRY(ctx, hipMemcpy(r->d_has_top, has.data(), 4 * (size_t)r->G, hipMemcpyHostToDevice));
-    r->poisoned = false;
-    r->has_top.swap(has);
+    if (int rc = fitted_totals_claim(r, "tsf_rollup_set_totals", "group", &r->top, r->G, c, &has)) return rc;
+    if (int rc = fitted_totals_draw(r, &r->top, c, has)) return rc;
     if (r->tree) r->tree->solved = false;
     return 0;
 }
@@ -3611,15 +3557,13 @@ static int check_shares(tsf_ctx *ctx, const char *name, const double *share, int
 // then the running sums, the sorts and the copies out.
 using MemberPass = std::function<void(double *samp, double *yhat, const int32_t *group, const double *share, int64_t nc)>;
 
-static int reconcile_members(tsf_rollup *r, const char *entry, const tsf_spec *spec, int64_t N, const double *theta,
-                             const double *y_scale, const tsf_grid_info *grid, int32_t n_grids, const double *floor_,
-                             const double *cap, const double *extra_future, int32_t shared_extra,
-                             const int64_t *series_key, const int64_t *group, const double *share, int32_t n_q,
+static int reconcile_members(tsf_rollup *r, const char *entry, const RollupCall &c, const double *share, int32_t n_q,
                              const double *quantiles, tsf_reconcile_out *out, const MemberPass &pass)
 {
     tsf_ctx *ctx = r->ctx;
-    if (int rc = rollup_check_series(r, spec, N, theta, y_scale, grid, n_grids, cap, extra_future, series_key, group))
-        return rc;
+    const tsf_spec *spec = c.spec;
+    const int64_t N = c.N, *group = c.group;
+    if (int rc = rollup_check_series(r, c)) return rc;
     if (!share) return fail(ctx, "NULL share");
     if (int rc = check_shares(ctx, "share", share, N)) return rc;
     if (!out) return fail(ctx, "NULL output (tsf_reconcile_out and its yhat are required)");
@@ -3633,8 +3577,7 @@ static int reconcile_members(tsf_rollup *r, const char *entry, const tsf_spec *s
     }
     for (int64_t n = 0; n < N; ++n) g32[(size_t)n] = (int32_t)group[n];
     RollupSeries in;
-    if (int rc = in.upload(r, spec, N, theta, y_scale, grid, n_grids, floor_, cap, extra_future, shared_extra, series_key))
-        return rc;
+    if (int rc = in.upload(r, c)) return rc;
     // the shares and the groups of the whole call, sent once ahead of the first launch
     const size_t nh = 8 * (size_t)N * H, nqh = nh * (size_t)n_q;
     HostOuts outs;
@@ -3681,18 +3624,18 @@ extern "C" int tsf_rollup_reconcile(tsf_rollup *r, const tsf_spec *spec, int64_t
     if (int rc = refuse_noise_ar(ctx, "tsf_rollup_reconcile")) return rc;
     if (N < 0) return fail(ctx, "N must be >= 0");
     if (N == 0) return 0;
-    if (!r->top) return fail(ctx, "tsf_rollup_reconcile before any tsf_rollup_set_totals: the roll-up has no total");
+    if (!r->top.T) return fail(ctx, "tsf_rollup_reconcile before any tsf_rollup_set_totals: the roll-up has no total");
     const int32_t H = r->H, S = r->S;
     ReconcileMemberArgs m;
     memset(&m, 0, sizeof(m));
-    m.acc = r->acc; m.top = r->top; m.ysum = r->ysum; m.ytop = r->ytop; m.has_top = r->d_has_top; m.H = H; m.NS = S;
+    m.acc = r->acc; m.top = r->top.T; m.ysum = r->ysum; m.ytop = r->top.yT; m.has_top = r->top.d_has; m.H = H; m.NS = S;
     const MemberPass pass = [&](double *samp, double *yhat, const int32_t *g, const double *sh, int64_t nc) {
         m.samp = samp; m.yhat = yhat; m.group = g; m.share = sh;
         hipLaunchKernelGGL(reconcile_member_kernel, dim3((unsigned)(nc * H), (unsigned)((S + 255) / 256)), dim3(256), 0,
                            nullptr, m);
     };
-    return reconcile_members(r, "tsf_rollup_reconcile", spec, N, theta, y_scale, grid, n_grids, floor_, cap, extra_future,
-                             shared_extra, series_key, group, share, n_q, quantiles, out, pass);
+    const RollupCall c = {spec, N, theta, y_scale, grid, n_grids, floor_, cap, extra_future, shared_extra, series_key, group};
+    return reconcile_members(r, "tsf_rollup_reconcile", c, share, n_q, quantiles, out, pass);
 }
 
 extern "C" int tsf_rollup_reconciled_totals(tsf_rollup *r, const double *share_total, int32_t n_q,
@@ -3700,7 +3643,7 @@ extern "C" int tsf_rollup_reconciled_totals(tsf_rollup *r, const double *share_t
 {
     if (int rc = rollup_enter(r, true)) return rc;
     tsf_ctx *ctx = r->ctx;
-    if (!r->top)
+    if (!r->top.T)
         return fail(ctx, "tsf_rollup_reconciled_totals before any tsf_rollup_set_totals: the roll-up has no total");
     if (!share_total) return fail(ctx, "NULL share_total");
     if (int rc = check_shares(ctx, "share_total", share_total, r->G)) return rc;
@@ -3712,65 +3655,12 @@ extern "C" int tsf_rollup_reconciled_totals(tsf_rollup *r, const double *share_t
     // rollup_read's ranges of groups, each reconciled into the scratch first
     ReconcileTotalArgs t;
     memset(&t, 0, sizeof(t));
-    t.acc = r->acc; t.top = r->top; t.ysum = r->ysum; t.ytop = r->ytop; t.has_top = r->d_has_top;
+    t.acc = r->acc; t.top = r->top.T; t.ysum = r->ysum; t.ytop = r->top.yT; t.has_top = r->top.d_has;
     t.share = d_share.as<double>(); t.yout = outs.want(out->yhat, 8 * (size_t)r->G * r->H); t.H = r->H; t.NS = r->S;
     return rollup_read(r, n_q, quantiles, *out, &t, outs);
 }
 
 // ---- tree reconciliation: levels above the groups ------------------------------------------------------------
-
-extern "C" int tsf_reconcile_tree_shares(int64_t N, const int64_t *group, const double *w, int64_t G, int32_t n_upper,
-                                         const int64_t *n_nodes, const int64_t *parent, const double *v, double *share,
-                                         double *mu, double *e, double *kappa)
-{
-    if (N < 0 || G < 1 || n_upper < 0 || n_upper > TSF_TREE_MAX_LEVELS) return -1;
-    if ((N > 0 && (!group || !share)) || !v || !mu || !e || !kappa || (n_upper > 0 && (!n_nodes || !parent))) return -1;
-    int64_t M = G, below = G, n_par = 0;
-    for (int32_t k = 0; k < n_upper; ++k) {
-        if (n_nodes[k] < 1) return -1;
-        for (int64_t c = 0; c < below; ++c)
-            if (parent[n_par + c] < 0 || parent[n_par + c] >= n_nodes[k]) return -1;
-        n_par += below; below = n_nodes[k]; M += below;
-    }
-    for (int64_t n = 0; n < N; ++n) {
-        if (group[n] < 0 || group[n] >= G) return -1;
-        if (w && !(w[n] > 0.0 && std::isfinite(w[n]))) return -1;
-    }
-    for (int64_t i = 0; i < M; ++i)
-        if (!std::isnan(v[i]) && !(v[i] > 0.0 && std::isfinite(v[i]))) return -1;
-    // E of a level in kappa's slots of that level until its own kappa is known
-    double *E = kappa;
-    for (int64_t g = 0; g < G; ++g) E[g] = 0.0;
-    for (int64_t n = 0; n < N; ++n) E[group[n]] = E[group[n]] + (w ? w[n] : 1.0);
-    for (int64_t n = 0; n < N; ++n) share[n] = (w ? w[n] : 1.0) / E[group[n]];
-    int64_t off = 0;
-    below = G; n_par = 0;
-    for (int32_t k = 0; k <= n_upper; ++k) {
-        for (int64_t i = off; i < off + below; ++i) {
-            const double En = E[i];
-            if (!std::isnan(v[i]) && En > 0.0) {
-                mu[i] = En / (v[i] + En);
-                e[i] = (En * v[i]) / (v[i] + En);
-            } else {
-                mu[i] = 0.0;
-                e[i] = En;
-            }
-        }
-        if (k == n_upper) {
-            for (int64_t i = off; i < off + below; ++i) kappa[i] = 0.0;        // the top level has no parent
-            break;
-        }
-        const int64_t up = off + below, n_up = n_nodes[k];
-        for (int64_t p = 0; p < n_up; ++p) E[up + p] = 0.0;
-        for (int64_t c = 0; c < below; ++c) E[up + parent[n_par + c]] = E[up + parent[n_par + c]] + e[off + c];
-        for (int64_t c = 0; c < below; ++c) {
-            const double Ep = E[up + parent[n_par + c]];
-            kappa[off + c] = Ep == 0.0 ? 0.0 : e[off + c] / Ep;
-        }
-        n_par += below; off = up; below = n_up;
-    }
-    return 0;
-}
 
 static const char *const TREE_NOT_SET = "before tsf_rollup_set_tree: the roll-up has no tree";
 
@@ -3882,46 +3772,12 @@ extern "C" int tsf_rollup_set_node_totals(tsf_rollup *r, int32_t level, const ts
     if (int rc = tree_level(r, "tsf_rollup_set_node_totals", level, 2, &lv)) return rc;
     if (Gt < 0) return fail(ctx, "N must be >= 0");
     if (Gt == 0) return 0;
-    if (int rc = rollup_check_series(r, spec, Gt, theta, y_scale, grid, n_grids, cap, extra_future, series_key, node, lv->n))
-        return rc;
+    const RollupCall c = {spec, Gt, theta, y_scale, grid, n_grids, floor_, cap, extra_future, shared_extra, series_key, node};
+    if (int rc = rollup_check_series(r, c, lv->n)) return rc;
     std::vector<int32_t> has;
-    try {
-        has = lv->has;
-        has.resize((size_t)lv->n, 0);
-    } catch (const std::bad_alloc &) {
-        return fail(ctx, "tsf_rollup_set_node_totals: out of host memory");
-    }
-    for (int64_t n = 0; n < Gt; ++n) {
-        if (has[(size_t)node[n]]) {
-            char msg[160];
-            snprintf(msg, sizeof(msg), "node[%lld] = %lld: the node has a total already (one total per node)",
-                     (long long)n, (long long)node[n]);
-            return fail(ctx, msg);
-        }
-        has[(size_t)node[n]] = 1;
-    }
-    if (!lv->T) {
-        // +0.0 everywhere, so that the add below leaves the draws themselves (together or not at all, as in set_totals)
-        OwnedDev<double> T, yT;
-        OwnedDev<int32_t> d_has;
-        const hipError_t e = [&]() -> hipError_t {
-            HIP_OK(T.alloc((size_t)lv->n * r->H * r->S, true));
-            HIP_OK(yT.alloc((size_t)lv->n * r->H, true));
-            HIP_OK(d_has.alloc((size_t)lv->n, true));
-            return hipDeviceSynchronize();
-        }();
-        if (e != hipSuccess) return rollup_hip_fail(ctx, "tsf_rollup_set_node_totals", e);
-        lv->T.swap(T); lv->yT.swap(yT); lv->d_has.swap(d_has);
-    }
+    if (int rc = fitted_totals_claim(r, "tsf_rollup_set_node_totals", "node", &lv->fit, lv->n, c, &has)) return rc;
     r->tree->solved = false;
-    if (int rc = rollup_accumulate(r, spec, Gt, theta, y_scale, grid, n_grids, floor_, cap, extra_future, shared_extra,
-                                   series_key, node, lv->T, lv->yT))
-        return rc;
-    r->poisoned = true;
-    HIP_TRY(ctx, hipMemcpy(lv->d_has, has.data(), 4 * (size_t)lv->n, hipMemcpyHostToDevice));
-    r->poisoned = false;
-    lv->has.swap(has);
-    return 0;
+    return fitted_totals_draw(r, &lv->fit, c, has);
 }
 
 extern "C" int tsf_rollup_solve_tree(tsf_rollup *r, const double *mu, const double *kappa)
@@ -3943,8 +3799,8 @@ extern "C" int tsf_rollup_solve_tree(tsf_rollup *r, const double *mu, const doub
     TreeBlendArgs b;
     memset(&b, 0, sizeof(b));
     b.H = H; b.NS = S;
-    b.A = r->acc; b.t = r->top; b.m = t.delta; b.yA = r->ysum; b.yt = r->ytop; b.ym = t.ydelta;
-    b.has = r->top ? r->d_has_top.p : nullptr; b.mu = d_mu;
+    b.A = r->acc; b.t = r->top.T; b.m = t.delta; b.yA = r->ysum; b.yt = r->top.yT; b.ym = t.ydelta;
+    b.has = r->top.T ? r->top.d_has.p : nullptr; b.mu = d_mu;
     hipLaunchKernelGGL(tree_blend_kernel, dim3((unsigned)(r->G * H), by), dim3(256), 0, nullptr, b);
     HIP_TRY(ctx, hipGetLastError());
     const double *m = t.delta, *ym = t.ydelta;
@@ -3953,8 +3809,8 @@ extern "C" int tsf_rollup_solve_tree(tsf_rollup *r, const double *mu, const doub
         const TreeGatherArgs g = {m, lv.A, ym, lv.yA, lv.d_first, lv.d_child, H, S};
         hipLaunchKernelGGL(tree_gather_kernel, dim3((unsigned)(lv.n * H), by), dim3(256), 0, nullptr, g);
         HIP_TRY(ctx, hipGetLastError());
-        b.A = lv.A; b.t = lv.T; b.m = lv.C; b.yA = lv.yA; b.yt = lv.yT; b.ym = lv.yC;
-        b.has = lv.T ? lv.d_has.p : nullptr; b.mu = d_mu + off;
+        b.A = lv.A; b.t = lv.fit.T; b.m = lv.C; b.yA = lv.yA; b.yt = lv.fit.yT; b.ym = lv.yC;
+        b.has = lv.fit.T ? lv.fit.d_has.p : nullptr; b.mu = d_mu + off;
         hipLaunchKernelGGL(tree_blend_kernel, dim3((unsigned)(lv.n * H), by), dim3(256), 0, nullptr, b);
         HIP_TRY(ctx, hipGetLastError());
         m = lv.C; ym = lv.yC; off += lv.n;
@@ -4005,8 +3861,8 @@ extern "C" int tsf_rollup_reconcile_tree(tsf_rollup *r, const tsf_spec *spec, in
         m.samp = samp; m.yhat = yhat; m.group = g; m.share = sh;
         hipLaunchKernelGGL(tree_member_kernel, dim3((unsigned)(nc * H), (unsigned)((S + 255) / 256)), dim3(256), 0, nullptr, m);
     };
-    return reconcile_members(r, "tsf_rollup_reconcile_tree", spec, N, theta, y_scale, grid, n_grids, floor_, cap,
-                             extra_future, shared_extra, series_key, group, share, n_q, quantiles, out, pass);
+    const RollupCall c = {spec, N, theta, y_scale, grid, n_grids, floor_, cap, extra_future, shared_extra, series_key, group};
+    return reconcile_members(r, "tsf_rollup_reconcile_tree", c, share, n_q, quantiles, out, pass);
 }
 
 extern "C" int tsf_rollup_tree_totals(tsf_rollup *r, int32_t level, int64_t node0, int64_t n_nodes, int32_t n_q,
@@ -4068,56 +3924,6 @@ extern "C" int tsf_rollup_tree_totals(tsf_rollup *r, int32_t level, int64_t node
 // ---- temporal reconciliation: daily forecasts and fitted period totals made coherent ------------------------
 
 extern "C" int tsf_temporal_out_size(void) { return (int)sizeof(tsf_temporal_out); }
-
-// No row in two windows (the windows have passed check_windows).  ctx may be null (tsf_temporal_shares has none).
-static int check_disjoint_windows(tsf_ctx *ctx, int32_t H, const WindowCall &w)
-{
-    std::vector<int32_t> owner((size_t)H, -1);
-    for (int32_t k = 0; k < w.K; ++k)
-        for (int32_t h = w.win_start[k]; h < w.win_end[k]; ++h) {
-            if (owner[(size_t)h] >= 0) {
-                char msg[160];
-                snprintf(msg, sizeof(msg), "windows %d and %d overlap at row %d: a row would get two corrections",
-                         (int)owner[(size_t)h], (int)k, (int)h);
-                return fail(ctx, msg);
-            }
-            owner[(size_t)h] = k;
-        }
-    return 0;
-}
-
-extern "C" int tsf_temporal_shares(int64_t N, int32_t H, int32_t K, const int32_t *win_start, const int32_t *win_end,
-                                   const double *w, const double *v, double *share, double *share_total)
-{
-    if (N < 0 || H < 1 || (N > 0 && (!v || !share || !share_total))) return -1;
-    const WindowCall wc = {K, win_start, win_end, nullptr};
-    try {
-        if (check_windows(nullptr, H, wc) || check_disjoint_windows(nullptr, H, wc)) return -1;
-    } catch (const std::bad_alloc &) {
-        return -1;
-    }
-    const size_t nh = (size_t)N * H, nk = (size_t)N * K;
-    for (size_t i = 0; w && i < nh; ++i)
-        if (!(w[i] > 0.0 && std::isfinite(w[i]))) return -1;
-    for (size_t i = 0; i < nk; ++i)
-        if (!std::isnan(v[i]) && !(v[i] > 0.0 && std::isfinite(v[i]))) return -1;
-    for (int64_t n = 0; n < N; ++n) {
-        const double *wn = w ? w + (size_t)n * H : nullptr;
-        double *sh = share + (size_t)n * H;
-        for (int32_t h = 0; h < H; ++h) sh[h] = 0.0;
-        for (int32_t k = 0; k < K; ++k) {
-            const double vk = v[(size_t)n * K + k];
-            double *mu = share_total + (size_t)n * K + k;
-            if (std::isnan(vk)) { *mu = vk; continue; }
-            double W = 0.0;
-            for (int32_t h = win_start[k]; h < win_end[k]; ++h) W = W + (wn ? wn[h] : 1.0);
-            const double D = vk + W;
-            for (int32_t h = win_start[k]; h < win_end[k]; ++h) sh[h] = (wn ? wn[h] : 1.0) / D;
-            *mu = W / D;
-        }
-    }
-    return 0;
-}
 
 // phi [N] in [0, 1) -> the (phi, sqrt(1 - phi^2)) pairs interval_sample_kernel<true> reads (tsf_set_noise_ar's)
 static int noise_ar_pairs(tsf_ctx *ctx, const char *name, const double *phi, int64_t N, std::vector<double> *pairs)
