@@ -950,7 +950,8 @@ int tsf_rollup_set_noise_corr(tsf_rollup *r, const double *rho /* [G] */, const 
  * it: tsf_predict_components, tsf_cross_validate and tsf_calibrate, tsf_rollup_set_totals, tsf_rollup_reconcile, and
  * tsf_rollup_add on a handle with tsf_rollup_set_noise_corr (that route regenerates z from the counters and would
  * disagree with the chain).  Entries that do not draw (fits, tsf_predict, the roll-up's reads) leave the setting alone.
- * Out of scope: the job configurations and the model blob (the scorer has models and no history). */
+ * The jobs: the modeler writes each series' phi beside its models and the scorer draws with it (model.noise, io.noise,
+ * forecast.noise: "the noise state of a fitted panel" below).  Out of scope: the model blob. */
 enum { TSF_AR_OK = 0, TSF_AR_NO_PAIRS = -51 };
 typedef struct {
     double phi_max;         /* the estimate is clipped to [0, phi_max]; default 0.95; in [0, 1) */
@@ -1034,7 +1035,8 @@ int tsf_set_noise_ar(tsf_ctx *ctx, const double *phi /* host [n] */, int64_t n);
  * Limits.  tsf_predict_temporal takes its phi as arguments, not through the setting, and keeps the stationary start (its
  * signature is published).  No conditioning inside tsf_cross_validate, tsf_calibrate, tsf_tune and tsf_select: the folds
  * would need each fold's fitted history; none on roll-ups with a noise correlation; no higher lags; the chain
- * runs on rows, not on the calendar; the job configurations and the model blob are untouched; no devices= split; no
+ * runs on rows, not on the calendar; the model blob is untouched (the state travels in a table of its own: "the noise
+ * state of a fitted panel" below); no devices= split; no
  * existing signature or struct changes (tsf_ar_out is what it was). */
 enum { TSF_AR_NO_ROW = -52 };       /* beside TSF_AR_OK: a series without a present row */
 typedef struct {
@@ -1054,6 +1056,84 @@ int tsf_set_noise_ar_start(tsf_ctx *ctx, const double *resid /* host [n], y unit
                            int64_t n);
 int tsf_noise_ar_mean(int64_t n, const double *phi, const double *resid, const int32_t *steps, int32_t H,
                       double *mean /* [n][H] */);
+
+/* ---- serially correlated observation noise: the noise state of a fitted panel --------------------------
+ * What the conditioned start needs from a history -- phi, the last present row's residual and the rows behind it -- are
+ * five numbers per series, and the modeler holds the history at the moment it fits.  By hand they cost a forecast of the
+ * whole history ([rows] fitted values to the host and back) for the two estimator entries above to read.
+ * tsf_noise_state forms them in one launch from the panel and its fit, with no buffer of fitted values at any point;
+ * tsf_predict_conditioned is the corrected point forecast with the reference's integer column, for the caller who has the
+ * numbers and no history (the scorer job: DESIGN.md 5u).  Both opt-in; reference interface replaced: none; parity unpinned
+ * (pinned: the contract below, against tsf_predict, tsf_residual_autocorr, tsf_residual_last and tsf_noise_ar_mean).
+ * Timing: tools/bench_noise_state.py.
+ *
+ * tsf_noise_state.  The panel arguments of tsf_fit_aligned (offsets NULL: ds [T], y [N][T], extra [n_extra][T]) or
+ * tsf_fit_ragged (offsets [N + 1], T ignored: ds, y [total_rows], extra [n_extra][total_rows]), floor / cap [N] or NULL as
+ * there; a fit of that panel (theta [N][tsf_theta_stride(spec)], y_scale [N], grid [n_grids], n_grids = 1 or N, status
+ * [N]); excluded (uint8 in y's layout, 1 = the row is absent, as if y were NaN there) or NULL; args (NULL: the defaults
+ * of tsf_ar_args).  Outputs per series: every field of tsf_ar_out and of tsf_ar_last_out -- phi, status, last_resid,
+ * last_gap, last_status required; phi_raw, n_pairs, scale NULL where not wanted -- and last_ds_ns (NULL: not wanted): the
+ * date of the series' final row, present or not, INT64_MIN for an empty series.
+ * Contract: each output is bit for bit what tsf_predict on the series' own dates (with the same floor, cap and explicit
+ * columns), then tsf_residual_autocorr, then tsf_residual_last give, for every model tsf_predict takes; a series' result
+ * depends on nothing else in the batch.  A series whose fit status is negative has no fitted values (its grid may be the
+ * degenerate one of a series of fewer than two rows, which tsf_predict refuses): phi = +0.0, phi_raw and scale NaN,
+ * n_pairs 0, TSF_AR_NO_PAIRS, TSF_AR_NO_ROW, last_resid +0.0, last_gap = its row count.
+ * One launch (noise_state_kernel), one wave per series: lane l takes rows l, l + 64, ...; per row the fitted value by
+ * predict_kernel's per-series-date arithmetic, the residual, and the residual into ar_series_kernel's sums (the left
+ * neighbour by shuffle, a carry across 64-row steps).
+ * Host pointers in the host variant.  In _dev ds, y, floor, cap, extra, theta, y_scale, grid, status, excluded and every
+ * output are device pointers; spec, offsets, args and the tsf_noise_state_out struct itself are HOST memory, and the call
+ * synchronises the stream before it returns.
+ * Refusals (< 0 with a message, before any launch; the context stays usable): those of tsf_residual_autocorr and
+ * tsf_residual_last on the panel (N outside [0, 2^31 - 1], a NULL required output, a bad y_dtype or args, T < 1 aligned,
+ * offsets that do not start at 0 or decrease, a series of more than 2^31 - 1 rows); with N > 0 those of tsf_predict (a
+ * bad spec, NULL ds, y, theta, y_scale, grid or status, n_grids other than 1 or N, NULL extra with n_extra > 0, logistic
+ * growth without cap, and -- host variant -- a grid of a series with status >= 0 that tsf_predict refuses) and -- host
+ * variant -- an excluded value other than 0 / 1.  N == 0 is a legal no-op.
+ *
+ * tsf_predict_conditioned.  tsf_predict's arguments, then phi, resid, steps: HOST [N] in both variants, checked as
+ * tsf_set_noise_ar and tsf_set_noise_ar_start check them (phi finite with |phi| < 1, resid finite, steps >= 1).
+ *   yhat = tsf_predict's, plus tsf_noise_ar_mean's row values for the series with phi != 0 (one add per cell): the bits of
+ *   the yhat a drawing entry returns under the same conditioned start.
+ *   yhat_int (NULL: not wanted) = the reference's post-step on that corrected yhat: truncate toward zero, saturate to
+ *   int32, clamp to floor -- the expression of tsf_predict, one device function both kernels call.
+ *   A series with phi == 0 gets tsf_predict's two outputs bit for bit.
+ * predict_kernel, then conditioned_shift_kernel (one thread per series and row) on the same stream.  It reads no pending
+ * tsf_set_noise_ar setting and leaves one alone.  _dev: the forecast's arrays and both outputs are device pointers, and
+ * the call synchronises the stream before it returns (the (phi, m0) pairs cross from host memory). */
+typedef struct {
+    double *phi;            /* [N] required: tsf_ar_out's fields */
+    double *phi_raw;        /* [N] or NULL */
+    int64_t *n_pairs;       /* [N] or NULL */
+    double *scale;          /* [N] or NULL */
+    int32_t *status;        /* [N] required: TSF_AR_OK or TSF_AR_NO_PAIRS */
+    double *last_resid;     /* [N] required: tsf_ar_last_out's fields */
+    int32_t *last_gap;      /* [N] required */
+    int32_t *last_status;   /* [N] required: TSF_AR_OK or TSF_AR_NO_ROW */
+    int64_t *last_ds_ns;    /* [N] or NULL: the date of the final row, INT64_MIN for an empty series */
+} tsf_noise_state_out;
+int tsf_noise_state_out_size(void); /* sizeof(tsf_noise_state_out): the self-check of a binding */
+int tsf_noise_state(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t T, const int64_t *offsets /* NULL = aligned */,
+                    const int64_t *ds, const void *y, int32_t y_dtype, const double *floor, const double *cap,
+                    const double *extra, const double *theta, const double *y_scale, const tsf_grid_info *grid,
+                    int32_t n_grids, const int32_t *status, const uint8_t *excluded /* NULL = none */,
+                    const tsf_ar_args *args /* NULL = defaults */, tsf_noise_state_out *out);
+int tsf_noise_state_dev(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t T, const int64_t *offsets /* host */,
+                        const int64_t *ds, const void *y, int32_t y_dtype, const double *floor, const double *cap,
+                        const double *extra, const double *theta, const double *y_scale, const tsf_grid_info *grid,
+                        int32_t n_grids, const int32_t *status, const uint8_t *excluded, const tsf_ar_args *args,
+                        tsf_noise_state_out *out, void *stream);
+int tsf_predict_conditioned(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H, const double *theta,
+                            const double *y_scale, const tsf_grid_info *grid, int32_t n_grids, const int64_t *ds_future,
+                            int32_t shared_future, const double *floor, const double *cap, const double *extra_future,
+                            const double *phi /* host [N] */, const double *resid /* host [N] */,
+                            const int32_t *steps /* host [N] */, double *yhat, int32_t *yhat_int);
+int tsf_predict_conditioned_dev(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H, const double *theta,
+                                const double *y_scale, const tsf_grid_info *grid, int32_t n_grids, const int64_t *ds_future,
+                                int32_t shared_future, const double *floor, const double *cap, const double *extra_future,
+                                const double *phi, const double *resid, const int32_t *steps, double *yhat,
+                                int32_t *yhat_int, void *stream);
 
 /* ---- conditional seasonalities ---------------------------------------------------------------------
  * Replaces the `condition_name=` argument of fbprophet 0.5's `Prophet.add_seasonality(name, period, fourier_order,

@@ -205,6 +205,13 @@ class TsfArLastOut(ctypes.Structure):
     _fields_ = [('last_resid', ctypes.c_void_p), ('last_gap', ctypes.c_void_p), ('status', ctypes.c_void_p)]
 
 
+class TsfNoiseStateOut(ctypes.Structure):
+    """tsf_noise_state_out (include/tsf.h)."""
+    _fields_ = [('phi', ctypes.c_void_p), ('phi_raw', ctypes.c_void_p), ('n_pairs', ctypes.c_void_p),
+                ('scale', ctypes.c_void_p), ('status', ctypes.c_void_p), ('last_resid', ctypes.c_void_p),
+                ('last_gap', ctypes.c_void_p), ('last_status', ctypes.c_void_p), ('last_ds_ns', ctypes.c_void_p)]
+
+
 class TsfCondSeas(ctypes.Structure):
     """tsf_cond_seas (include/tsf.h)."""
     _fields_ = [('n', ctypes.c_int32), ('period', ctypes.c_double * MAX_SEAS), ('order', ctypes.c_int32 * MAX_SEAS),
@@ -251,6 +258,8 @@ EXPORTS = ['tsf_create', 'tsf_destroy', 'tsf_last_error', 'tsf_device_count', 't
            'tsf_ar_args_size', 'tsf_ar_out_size', 'tsf_residual_autocorr', 'tsf_residual_autocorr_dev', 'tsf_set_noise_ar',
            'tsf_ar_last_out_size', 'tsf_residual_last', 'tsf_residual_last_dev', 'tsf_residual_autocorr_last',
            'tsf_set_noise_ar_start', 'tsf_noise_ar_mean',
+           'tsf_noise_state_out_size', 'tsf_noise_state', 'tsf_noise_state_dev', 'tsf_predict_conditioned',
+           'tsf_predict_conditioned_dev',
            'tsf_cond_columns', 'tsf_cond_columns_dev',
            'tsf_eval', 'tsf_eval_quadratic', 'tsf_design', 'tsf_selftest_math',
            'tsf_set_option', 'tsf_get_option', 'tsf_set_cost_hints', 'tsf_set_profiling', 'tsf_profile_read', 'tsf_last_fit_kernel_ms', 'tsf_last_fit_route',
@@ -384,6 +393,11 @@ def load():
     L.tsf_residual_autocorr_last.argtypes = L.tsf_residual_autocorr.argtypes + [ctypes.POINTER(TsfArLastOut)]
     L.tsf_set_noise_ar_start.argtypes = [vp, vp, vp, i64]
     L.tsf_noise_ar_mean.argtypes = [i64, vp, vp, vp, i32, vp]
+    L.tsf_noise_state.argtypes = [vp, psp, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp,
+                                  ctypes.POINTER(TsfArArgs), ctypes.POINTER(TsfNoiseStateOut)]
+    L.tsf_noise_state_dev.argtypes = L.tsf_noise_state.argtypes + [vp]
+    L.tsf_predict_conditioned.argtypes = L.tsf_predict.argtypes[:13] + [vp, vp, vp, vp, vp]
+    L.tsf_predict_conditioned_dev.argtypes = L.tsf_predict_conditioned.argtypes + [vp]
     L.tsf_cond_columns.argtypes = [vp, ctypes.POINTER(TsfCondSeas), i64, vp, i32, vp, vp, i64]
     L.tsf_cond_columns_dev.argtypes = L.tsf_cond_columns.argtypes + [vp]
     L.tsf_eval.argtypes = [vp, psp, i64, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
@@ -484,6 +498,8 @@ def load():
         raise TsfError('tsf_ar_args / tsf_ar_out layout mismatch between _lib.py and libtsf_amd.so')
     if L.tsf_ar_last_out_size() != ctypes.sizeof(TsfArLastOut):
         raise TsfError('tsf_ar_last_out layout mismatch between _lib.py and libtsf_amd.so')
+    if L.tsf_noise_state_out_size() != ctypes.sizeof(TsfNoiseStateOut):
+        raise TsfError('tsf_noise_state_out layout mismatch between _lib.py and libtsf_amd.so')
     if L.tsf_select_out_size() != ctypes.sizeof(TsfSelectOut):
         raise TsfError('tsf_select_out layout mismatch between _lib.py and libtsf_amd.so')
     if L.tsf_fit_plan_info_size() != ctypes.sizeof(TsfFitPlanInfo):

@@ -52,7 +52,9 @@ def build_lib(force=False, verbose=False):
     os.makedirs(OBJ, exist_ok=True)
     srcs = sorted(glob.glob(os.path.join(CSRC, '*.hip')) + glob.glob(os.path.join(CSRC, '*.cpp')))
     hdr = _newest_header()
-    jobs = [(s, os.path.join(OBJ, os.path.splitext(os.path.basename(s))[0] + '.o')) for s in srcs]
+    if not force and os.path.exists(LIB) and os.path.getmtime(LIB) >= max([hdr] + [os.path.getmtime(s) for s in srcs]):
+        return LIB          # (newer than every source and header: up to date, whether or not the objects are still there)
+    jobs =[(s, os.path.join(OBJ, os.path.splitext(os.path.basename(s))[0] + '.o')) for s in srcs]
     changed = False
     with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, len(jobs))) as ex:
         for obj, did in ex.map(lambda j: _compile(j[0], j[1], hdr, force), jobs):

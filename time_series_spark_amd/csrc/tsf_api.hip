@@ -43,6 +43,7 @@
 #include "tsf_calib_kernels.h"
 #include "tsf_corr_kernels.h"
 #include "tsf_ar_kernels.h"
+#include "tsf_noise_state_kernels.h"
 #include "tsf_cond_kernels.h"
 #include "tsf_cv_plan.h"
 #include "tsf_fit_plan.h"
@@ -1457,10 +1458,15 @@ extern "C" int tsf_eval_quadratic(tsf_ctx *ctx, const tsf_spec *spec, int64_t N,
 // The grids a host-memory predict entry is handed are caller data (model blobs read back from storage):
 // checked before anything is copied or launched.  S beyond the spec's n_changepoints would read beta as
 // delta; beyond TSF_MAX_S the kernel's LDS segment tables overflow.
-static int check_grids(tsf_ctx *ctx, const tsf_spec *spec, const tsf_grid_info *grid, int32_t n_grids)
+// fit_status (tsf_noise_state: one per series, n_grids = 1 or their count N): the grid of a series whose status is
+// negative is not read by the kernel and not checked; a shared grid is checked where any series uses it.
+static int check_grids(tsf_ctx *ctx, const tsf_spec *spec, const tsf_grid_info *grid, int32_t n_grids,
+                       const int32_t *fit_status = nullptr, int64_t N = 0)
 {
+    if (fit_status && n_grids == 1 && std::none_of(fit_status, fit_status + N, [](int32_t s) { return s >= 0; })) return 0;
     for (int32_t g = 0; g < n_grids; ++g) {
         const tsf_grid_info &gi = grid[g];
+        if (fit_status && n_grids != 1 && fit_status[g] < 0) continue;
         const char *why = nullptr;
         if (gi.S < 0) why = "S < 0";
         else if (gi.S > spec->n_changepoints) why = "S > the spec's n_changepoints";
@@ -3010,6 +3016,232 @@ extern "C" int tsf_residual_autocorr_last(tsf_ctx *ctx, int64_t N, int32_t T, co
     if (int rc = ar_last_run(ctx, N, T, off, d_y.p, y_dtype, d_fit.as<double>(), l, nullptr)) return rc;
     HIP_TRY(ctx, hipDeviceSynchronize());
     return outs.fetch(ctx);
+}
+
+// ---- the noise state of a fitted panel in one pass, and the corrected point forecast (tsf_noise_state_kernels.h) ----
+
+extern "C" int tsf_noise_state_out_size(void) { return (int)sizeof(tsf_noise_state_out); }
+
+// A panel and its fit as tsf_noise_state takes them: host pointers in the host entry, device pointers behind it and in
+// the `_dev` entry (offsets: host in both).
+struct NoiseStateIn {
+    int64_t N;
+    int32_t T;
+    const int64_t *offsets, *ds;
+    const void *y;
+    int32_t y_dtype;
+    const double *floor_, *cap, *extra, *theta, *y_scale;
+    const tsf_grid_info *grid;
+    int32_t n_grids;
+    const int32_t *status;
+    const uint8_t *excluded;
+};
+
+// What both tsf_noise_state entries check before anything is launched and before anything is dereferenced but offsets:
+// the panel checks of the two estimator entries, then (N > 0) tsf_predict's on the fit.  *a: the arguments in force.
+static int check_noise_state_call(tsf_ctx *ctx, const tsf_spec *spec, const NoiseStateIn &in, const tsf_ar_args *args,
+                                  const tsf_noise_state_out *out, tsf_ar_args *a)
+{
+    if (!out) return fail(ctx, "NULL output (tsf_noise_state_out)");
+    // (the estimators' checks know y and fitted: y stands for both here, the fitted values are never materialised)
+    const void *panel = in.N > 0 ? in.y : nullptr;
+    const tsf_ar_out ar = {out->phi, out->phi_raw, out->n_pairs, out->scale, out->status};
+    if (int rc = check_ar_call(ctx, in.N, in.T, in.offsets, panel, in.y_dtype, (const double *)panel, args, &ar, a)) return rc;
+    const tsf_ar_last_out last = {out->last_resid, out->last_gap, out->last_status};
+    if (int rc = check_ar_last_call(ctx, in.N, in.T, in.offsets, panel, in.y_dtype, (const double *)panel, &last)) return rc;
+    if (in.N == 0) return 0;
+    if (!spec || !in.ds || !in.theta || !in.y_scale || !in.grid || !in.status)
+        return fail(ctx, "NULL input (spec, ds, theta, y_scale, grid and status are required)");
+    if (in.n_grids != 1 && in.n_grids != in.N) return fail(ctx, "n_grids must be 1 or N");
+    return 0;
+}
+
+// The launch on device-resident inputs; o: device pointers.  The spec goes to the context's copy in stream order first.
+static int noise_state_run(tsf_ctx *ctx, const tsf_spec *spec, const NoiseStateIn &d, const int64_t *d_off, int64_t rows,
+                           const tsf_ar_args &a, const tsf_noise_state_out &o, hipStream_t st)
+{
+    const ForecastIn f = {d.N, 1, d.theta, d.y_scale, d.grid, d.n_grids, d.ds, 0, d.floor_, d.cap, d.extra, nullptr};
+    DevSpec hs;
+    if (int rc = forecast_prologue(ctx, spec, f, st, &hs)) return rc;
+    NoiseStateArgs k;
+    memset(&k, 0, sizeof(k));
+    k.sp = ctx->d_spec; k.N = d.N; k.T = d.T; k.y_dtype = d.y_dtype; k.theta_stride = tsf_theta_stride(spec);
+    k.n_grids = d.n_grids; k.min_pairs = a.min_pairs; k.phi_max = a.phi_max;
+    k.offsets = d_off; k.ds = d.ds; k.y = d.y; k.excluded = d.excluded; k.floor_ = d.floor_; k.cap = d.cap;
+    k.extra = hs.n_extra > 0 ? d.extra : nullptr; k.extra_stride = d_off ? rows : (int64_t)d.T;
+    k.theta = d.theta; k.y_scale = d.y_scale; k.grid = d.grid; k.fit_status = d.status;
+    k.phi = o.phi; k.phi_raw = o.phi_raw; k.n_pairs = o.n_pairs; k.scale = o.scale; k.status = o.status;
+    k.last_resid = o.last_resid; k.last_gap = o.last_gap; k.last_status = o.last_status; k.last_ds_ns = o.last_ds_ns;
+    hipLaunchKernelGGL(noise_state_kernel, dim3((unsigned)((d.N + NS_WAVES - 1) / NS_WAVES)), dim3(NS_WAVES * 64), 0, st, k,
+                       (int)TSF_AR_OK, (int)TSF_AR_NO_PAIRS, (int)TSF_AR_NO_ROW);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+extern "C" int tsf_noise_state_dev(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t T, const int64_t *offsets,
+                                   const int64_t *ds, const void *y, int32_t y_dtype, const double *floor_,
+                                   const double *cap, const double *extra, const double *theta, const double *y_scale,
+                                   const tsf_grid_info *grid, int32_t n_grids, const int32_t *status,
+                                   const uint8_t *excluded, const tsf_ar_args *args, tsf_noise_state_out *out, void *stream)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const NoiseStateIn in = {N, T, offsets, ds, y, y_dtype, floor_, cap, extra, theta, y_scale, grid, n_grids, status, excluded};
+    tsf_ar_args a;
+    if (int rc = check_noise_state_call(ctx, spec, in, args, out, &a)) return rc;
+    if (N == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf d_off;
+    if (offsets) HIP_TRY(ctx, d_off.put(offsets, 8 * ((size_t)N + 1)));
+    if (int rc = noise_state_run(ctx, spec, in, offsets ? d_off.as<int64_t>() : nullptr, offsets ? offsets[N] : 0, a, *out, st))
+        return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(st));         // (the offsets go back to the pool)
+    return 0;
+}
+
+extern "C" int tsf_noise_state(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t T, const int64_t *offsets,
+                               const int64_t *ds, const void *y, int32_t y_dtype, const double *floor_, const double *cap,
+                               const double *extra, const double *theta, const double *y_scale, const tsf_grid_info *grid,
+                               int32_t n_grids, const int32_t *status, const uint8_t *excluded, const tsf_ar_args *args,
+                               tsf_noise_state_out *out)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const NoiseStateIn h = {N, T, offsets, ds, y, y_dtype, floor_, cap, extra, theta, y_scale, grid, n_grids, status, excluded};
+    tsf_ar_args a;
+    if (int rc = check_noise_state_call(ctx, spec, h, args, out, &a)) return rc;
+    if (N == 0) return 0;
+    const size_t n = (size_t)N, rows = offsets ? (size_t)offsets[N] : n * T, nds = offsets ? rows : (size_t)T;
+    {   // what only a host entry can see: the spec against the inputs, the grids the kernel will read, the marks
+        const ForecastIn f = {N, 1, theta, y_scale, grid, n_grids, ds, 0, floor_, cap, extra, nullptr};
+        DevSpec hs;
+        if (int rc = forecast_spec(ctx, spec, f, &hs)) return rc;
+        if (int rc = check_grids(ctx, spec, grid, n_grids, status, N)) return rc;
+        if (excluded)
+            for (size_t i = 0; i < rows; ++i)
+                if (excluded[i] > 1) return fail(ctx, "excluded holds a value other than 0 / 1");
+    }
+    NoiseStateIn d = h;
+    DevBuf d_off, d_ds, d_y, d_ex, d_fl, d_cap, d_x, d_th, d_ys, d_grid, d_st;
+    if (offsets) HIP_TRY(ctx, d_off.put(offsets, 8 * (n + 1)));
+    if (int rc = ForecastUpload::put(ctx, &d_ds, ds, 8 * nds, &d.ds)) return rc;
+    HIP_TRY(ctx, d_y.put(y, ysize(y_dtype) * rows));
+    d.y = d_y.p;
+    if (int rc = ForecastUpload::put(ctx, &d_ex, excluded, rows, &d.excluded)) return rc;
+    if (int rc = ForecastUpload::put(ctx, &d_fl, floor_, 8 * n, &d.floor_)) return rc;
+    if (int rc = ForecastUpload::put(ctx, &d_cap, cap, 8 * n, &d.cap)) return rc;
+    if (spec->n_extra == 0) d.extra = nullptr;
+    else if (int rc = ForecastUpload::put(ctx, &d_x, extra, 8 * (size_t)spec->n_extra * nds, &d.extra)) return rc;
+    if (int rc = ForecastUpload::put(ctx, &d_th, theta, 8 * n * tsf_theta_stride(spec), &d.theta)) return rc;
+    if (int rc = ForecastUpload::put(ctx, &d_ys, y_scale, 8 * n, &d.y_scale)) return rc;
+    if (int rc = ForecastUpload::put(ctx, &d_grid, grid, sizeof(tsf_grid_info) * (size_t)n_grids, &d.grid)) return rc;
+    if (int rc = ForecastUpload::put(ctx, &d_st, status, 4 * n, &d.status)) return rc;
+    HostOuts outs;
+    tsf_noise_state_out o;
+    memset(&o, 0, sizeof(o));
+    o.phi = outs.want(out->phi, 8 * n); o.status = outs.want(out->status, 4 * n);
+    o.phi_raw = outs.want(out->phi_raw, 8 * n); o.n_pairs = outs.want(out->n_pairs, 8 * n);
+    o.scale = outs.want(out->scale, 8 * n); o.last_resid = outs.want(out->last_resid, 8 * n);
+    o.last_gap = outs.want(out->last_gap, 4 * n); o.last_status = outs.want(out->last_status, 4 * n);
+    o.last_ds_ns = outs.want(out->last_ds_ns, 8 * n);
+    if (int rc = outs.ready(ctx)) return rc;
+    if (int rc = noise_state_run(ctx, spec, d, offsets ? d_off.as<int64_t>() : nullptr, (int64_t)rows, a, o, nullptr)) return rc;
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    return outs.fetch(ctx);
+}
+
+// phi, resid, steps of tsf_predict_conditioned (host memory in both variants), checked as tsf_set_noise_ar and
+// tsf_set_noise_ar_start check them; *pm: (phi, m0 = resid * phi^steps) per series, tsf_noise_ar_mean's first row.
+static int conditioned_pairs(tsf_ctx *ctx, int64_t N, const double *phi, const double *resid, const int32_t *steps,
+                             std::vector<double> *pm)
+{
+    if (!phi || !resid || !steps) return fail(ctx, "NULL input (phi, resid and steps are required)");
+    char msg[160];
+    for (int64_t i = 0; i < N; ++i) {
+        if (!(std::fabs(phi[i]) < 1.0)) {
+            snprintf(msg, sizeof(msg), "phi[%lld] = %g: each phi must be finite with |phi| < 1", (long long)i, phi[i]);
+            return fail(ctx, msg);
+        }
+        if (!std::isfinite(resid[i])) {
+            snprintf(msg, sizeof(msg), "resid[%lld] = %g: a residual must be finite", (long long)i, resid[i]);
+            return fail(ctx, msg);
+        }
+        if (steps[i] < 1) {
+            snprintf(msg, sizeof(msg), "steps[%lld] = %d: the first future row lies at least one row behind the last residual",
+                     (long long)i, (int)steps[i]);
+            return fail(ctx, msg);
+        }
+    }
+    try {
+        pm->resize(2 * (size_t)N);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, "tsf_predict_conditioned: out of host memory");
+    }
+    for (int64_t i = 0; i < N; ++i) {
+        (*pm)[2 * (size_t)i] = phi[i];
+        (*pm)[2 * (size_t)i + 1] = resid[i] * ar_start_p0(phi[i], steps[i]);
+    }
+    return 0;
+}
+
+extern "C" int tsf_predict_conditioned_dev(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H, const double *theta,
+                                           const double *y_scale, const tsf_grid_info *grid, int32_t n_grids,
+                                           const int64_t *ds_future, int32_t shared_future, const double *floor_,
+                                           const double *cap, const double *extra_future, const double *phi,
+                                           const double *resid, const int32_t *steps, double *yhat, int32_t *yhat_int,
+                                           void *stream)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const ForecastIn f = {N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap, extra_future, nullptr};
+    if (int rc = check_forecast_in(ctx, f, spec && yhat)) return rc;
+    std::vector<double> pm;
+    if (int rc = conditioned_pairs(ctx, N, phi, resid, steps, &pm)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    DevSpec hs;
+    if (int rc = forecast_prologue(ctx, spec, f, st, &hs)) return rc;
+    DevBuf d_pm;
+    HIP_TRY(ctx, d_pm.put(pm.data(), 8 * pm.size()));
+    PredictArgs a = predict_args(ctx, spec, f, yhat);
+    bool tab_ready = false;
+    if (int rc = launch_predict(ctx, hs, a, 0, N, &tab_ready, st)) return rc;
+    const ConditionedArgs c = {d_pm.as<double>(), floor_, yhat, yhat_int, N, H};
+    const int64_t cells = N * (int64_t)H;
+    hipLaunchKernelGGL(conditioned_shift_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, c);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(st));         // (the pairs go back to the pool)
+    return 0;
+}
+
+extern "C" int tsf_predict_conditioned(tsf_ctx *ctx, const tsf_spec *spec, int64_t N, int32_t H, const double *theta,
+                                       const double *y_scale, const tsf_grid_info *grid, int32_t n_grids,
+                                       const int64_t *ds_future, int32_t shared_future, const double *floor_,
+                                       const double *cap, const double *extra_future, const double *phi,
+                                       const double *resid, const int32_t *steps, double *yhat, int32_t *yhat_int)
+{
+    if (!ctx) return -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const ForecastIn h = {N, H, theta, y_scale, grid, n_grids, ds_future, shared_future, floor_, cap, extra_future, nullptr};
+    if (int rc = check_forecast_in(ctx, h, spec && yhat)) return rc;
+    if (int rc = check_grids(ctx, spec, grid, n_grids)) return rc;
+    {
+        std::vector<double> pm;     // (checked here too: a refusal comes before anything is copied)
+        if (int rc = conditioned_pairs(ctx, N, phi, resid, steps, &pm)) return rc;
+    }
+    ForecastUpload up;
+    if (int rc = up.upload(ctx, spec, h)) return rc;
+    const ForecastIn &d = up.dev;
+    DevBuf d_yh, d_yi;
+    HIP_TRY(ctx, d_yh.alloc(8 * (size_t)N * H));
+    if (yhat_int) HIP_TRY(ctx, d_yi.alloc(4 * (size_t)N * H));
+    if (int rc = tsf_predict_conditioned_dev(ctx, spec, N, H, d.theta, d.y_scale, d.grid, n_grids, d.ds_future, shared_future,
+                                             d.floor_, d.cap, d.extra_future, phi, resid, steps, d_yh.as<double>(),
+                                             yhat_int ? d_yi.as<int32_t>() : nullptr, nullptr))
+        return rc;
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    HIP_TRY(ctx, hipMemcpy(yhat, d_yh.p, 8 * (size_t)N * H, hipMemcpyDeviceToHost));
+    if (yhat_int) HIP_TRY(ctx, hipMemcpy(yhat_int, d_yi.p, 4 * (size_t)N * H, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 extern "C" int tsf_set_noise_ar_start(tsf_ctx *ctx, const double *resid, const int32_t *steps, int64_t n)

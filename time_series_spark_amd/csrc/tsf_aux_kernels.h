@@ -424,6 +424,18 @@ __global__ void future_design_kernel(const DevSpec *sp, int H, const int64_t *ds
 
 constexpr int PREDICT_WAVES = 4;        // series per workgroup
 
+// The reference's post-step on one forecast value (prophet_scorer.py:73 astype(int) truncates toward zero; :76-84 clamp
+// to floor): truncate, saturate to int32 (NaN: INT32_MIN), clamp to floor.  predict_kernel and conditioned_shift_kernel.
+__device__ __forceinline__ int32_t yhat_post_int(double yh, double fl_clamp)
+{
+    double tr = __builtin_trunc(yh);
+    if (!(tr >= -2147483648.0)) tr = -2147483648.0;
+    if (tr > 2147483647.0) tr = 2147483647.0;
+    int32_t iv = (int32_t)tr;
+    if ((double)iv < fl_clamp) iv = (int32_t)fl_clamp;
+    return iv;
+}
+
 __global__ __launch_bounds__(PREDICT_WAVES * 64) void predict_kernel(PredictArgs a)
 {
     __shared__ double seg_ks[PREDICT_WAVES][TSF_MAX_S + 4], seg_mc[PREDICT_WAVES][TSF_MAX_S + 4];
@@ -544,15 +556,7 @@ __global__ __launch_bounds__(PREDICT_WAVES * 64) void predict_kernel(PredictArgs
         a.yhat[gid] = yh;
         if (a.trend_out) a.trend_out[gid] = trend;
         if (a.t_out) { a.t_out[gid] = t; a.xa_out[gid] = xa * ys; a.opm_out[gid] = 1.0 + xm; }
-        if (a.yhat_int) {
-            // prophet_scorer.py:73 astype(int) truncates toward zero; :76-84 clamp to floor
-            double tr = __builtin_trunc(yh);
-            if (!(tr >= -2147483648.0)) tr = -2147483648.0;
-            if (tr > 2147483647.0) tr = 2147483647.0;
-            int32_t iv = (int32_t)tr;
-            if ((double)iv < fl_clamp) iv = (int32_t)fl_clamp;
-            a.yhat_int[gid] = iv;
-        }
+        if (a.yhat_int) a.yhat_int[gid] = yhat_post_int(yh, fl_clamp);
     }
 }
 

@@ -1412,6 +1412,20 @@ class NoiseAR(object):
                 cols['last_ds_ns'] = self.last_ds_ns
         return pd.DataFrame(cols, columns=list(cols))
 
+    @classmethod
+    def from_frame(cls, df):
+        """The inverse of frame(keys, last=True), bit for bit: a NoiseAR from the columns phi, phi_raw, n_pairs, scale,
+        status, last_resid, last_gap (and last_ds_ns where the frame has it), in the frame's row order.  The `series`
+        column is the caller's to join on."""
+        need = ('phi', 'phi_raw', 'n_pairs', 'scale', 'status', 'last_resid', 'last_gap')
+        missing = [c for c in need if c not in df.columns]
+        if missing:
+            raise ValueError('from_frame: the frame lacks %s (frame(keys, last=True) writes them)' % ', '.join(missing))
+        col = lambda name, dt: np.ascontiguousarray(df[name].to_numpy(), dtype=dt)       # noqa: E731
+        return cls(col('phi', np.float64), col('phi_raw', np.float64), col('n_pairs', np.int64), col('scale', np.float64),
+                   col('status', np.int32), col('last_resid', np.float64), col('last_gap', np.int32),
+                   col('last_ds_ns', np.int64) if 'last_ds_ns' in df.columns else None)
+
 
 class NoiseARStart(object):
     """NoiseAR.conditioned(): phi [N], resid [N] (y units), steps [N] int32 (>= 1: rows from the last present history
@@ -1525,6 +1539,103 @@ def fit_residual_autocorrelation(spec, res, ds_ns, y, offsets=None, floor=None, 
         some = off[1:] > off[:-1]
         est.last_ds_ns[some] = ds[off[1:][some] - 1]
     return est
+
+
+def fit_noise_state(spec, res, ds_ns, y, offsets=None, floor=None, cap=None, extra=None, excluded=None, phi_max=0.95,
+                    min_pairs=8, ctx=None):
+    """fit_residual_autocorrelation's NoiseAR, field by field and bit for bit, in one launch (include/tsf.h
+    tsf_noise_state): the panel as fit_aligned (ds_ns [T], y [N][T], extra [n_extra][T]) or, with offsets [N+1], as
+    fit_ragged took it, and its FitResult `res`.  The fitted values are formed row by row on the device and never
+    stored; nothing of the panel's size comes back.  excluded (uint8 / bool, y's shape; 1 = the row is absent, as if y
+    were NaN there): a screened fit summarised on the rows its final fit saw (ScreenedFit.screen.flag).  A series whose
+    fit status is negative has no fitted values: phi 0, AR_NO_PAIRS, no last row, last_gap = its row count."""
+    ex = None if excluded is None else np.ascontiguousarray(excluded, dtype=np.uint8)
+    y, offsets, N, T = _screen_panel(y, offsets, (ex,), ('excluded',))
+    if offsets is None and T < 1:
+        raise ValueError('aligned panel: y must be [N][T], T >= 1')
+    ds = np.ascontiguousarray(ds_ns, dtype=np.int64)
+    rows = T if offsets is None else y.shape[0]
+    if ds.shape != (rows,):
+        raise ValueError('ds must be [T] (aligned) or [total_rows] (ragged)')
+    a = _ar_args(phi_max, min_pairs)
+    theta = np.ascontiguousarray(res.theta, dtype=np.float64)
+    y_scale = np.ascontiguousarray(res.y_scale, dtype=np.float64)
+    grid = np.ascontiguousarray(res.grid, dtype=_lib.GRID_DTYPE)
+    status = np.ascontiguousarray(res.status, dtype=np.int32)
+    if theta.shape != (N, spec.theta_stride) or y_scale.shape != (N,) or status.shape != (N,) or len(grid) not in (1, N):
+        raise ValueError('res must be the FitResult of this panel: theta [N][stride], y_scale, status [N], grid [1] or [N]')
+    fl = _opt_f64(floor, N, 'floor')
+    cp = _opt_f64(cap, N, 'cap')
+    xt = None
+    if spec.extra:
+        xt = np.ascontiguousarray(extra, dtype=np.float64)
+        if xt.shape != (len(spec.extra), rows):
+            raise ValueError('extra must be [n_extra][len(ds)]')
+    ctx = ctx or get_context()
+    cs = spec.to_c()
+    phi, raw, scale, last_resid = np.zeros(N), np.zeros(N), np.zeros(N), np.zeros(N)
+    n_pairs, last_ds = np.zeros(N, np.int64), np.zeros(N, np.int64)
+    st, last_gap, last_status = np.zeros(N, np.int32), np.zeros(N, np.int32), np.zeros(N, np.int32)
+    out = _lib.TsfNoiseStateOut(phi.ctypes.data, raw.ctypes.data, n_pairs.ctypes.data, scale.ctypes.data, st.ctypes.data,
+                                last_resid.ctypes.data, last_gap.ctypes.data, last_status.ctypes.data, last_ds.ctypes.data)
+    ctx.check(_lib.load().tsf_noise_state(ctx.handle, ctypes.byref(cs), N, T, _lib._ptr(offsets), ds.ctypes.data,
+                                          y.ctypes.data, _lib.y_dtype_code(y), _lib._ptr(fl), _lib._ptr(cp), _lib._ptr(xt),
+                                          theta.ctypes.data, y_scale.ctypes.data, grid.ctypes.data, len(grid),
+                                          status.ctypes.data, _lib._ptr(ex), ctypes.byref(a), ctypes.byref(out)))
+    return NoiseAR(phi, raw, n_pairs, scale, st, last_resid, last_gap, last_ds)
+
+
+def predict_conditioned(spec, theta, y_scale, grid, ds_future_ns, start, floor=None, cap=None, extra_future=None,
+                        want_int=True, ctx=None):
+    """The corrected point forecast with its integer column (include/tsf.h tsf_predict_conditioned): start, a
+    NoiseAR.conditioned() object -> (yhat, yhat_int) with want_int, else yhat.  yhat has the bits of
+    predict(noise_ar=start); yhat_int is the reference's post-step (truncate, saturate, clamp to floor) on that
+    corrected value -- what predict refuses to give, its integer column being the uncorrected forecast's.  A series
+    with phi == 0 gets predict(want_int=True)'s two outputs."""
+    if not isinstance(start, NoiseARStart):
+        raise ValueError('start must be a NoiseAR.conditioned() object')
+    theta, N, y_scale, grid, ds, shared, H, floor, cap, ex, _ = _forecast_inputs(
+        spec, theta, y_scale, grid, ds_future_ns, floor, cap, extra_future)
+    if start.phi.shape != (N,):
+        raise ValueError('start must hold N series')
+    if not (np.isfinite(start.phi).all() and (np.abs(start.phi) < 1.0).all()):
+        raise ValueError('noise_ar values must be finite with |phi| < 1')
+    if start.last_ds_ns is not None and H and (ds[..., 0] <= start.last_ds_ns).any():
+        raise ValueError('a conditioned noise_ar needs future rows after the history: a first future row lies at or '
+                         'before last_ds_ns')
+    ctx = ctx or get_context()
+    cs = spec.to_c()
+    yhat = np.zeros((N, H))
+    yint = np.zeros((N, H), dtype=np.int32) if want_int else None
+    ctx.check(_lib.load().tsf_predict_conditioned(ctx.handle, ctypes.byref(cs), N, H, theta.ctypes.data, y_scale.ctypes.data,
+                                                  grid.ctypes.data, len(grid), ds.ctypes.data, int(shared), _lib._ptr(floor),
+                                                  _lib._ptr(cap), _lib._ptr(ex), start.phi.ctypes.data,
+                                                  start.resid.ctypes.data, start.steps.ctypes.data, yhat.ctypes.data,
+                                                  _lib._ptr(yint)))
+    return (yhat, yint) if want_int else yhat
+
+
+def noise_lead(last_ds_ns, row_step_ns, ds_future_ns):
+    """(lead [N] int64, ok [N] bool): the rows from the end of each history to its first future row -- what
+    NoiseAR.conditioned(lead=) takes -- where the future continues the history's row grid.  last_ds_ns, row_step_ns [N];
+    ds_future_ns [H] (shared) or [N][H].  ok: row_step_ns > 0, the series' future rows uniformly spaced by its
+    row_step_ns, and the first one a positive whole number of steps after last_ds_ns; lead is that number (0 where not
+    ok).  The chain runs on rows: a weekly forecast of a daily history is not ok.  Pure numpy."""
+    last = np.asarray(last_ds_ns, dtype=np.int64).reshape(-1)
+    step = np.asarray(row_step_ns, dtype=np.int64).reshape(-1)
+    N = len(last)
+    fut = np.asarray(ds_future_ns, dtype=np.int64)
+    if step.shape != (N,) or fut.ndim not in (1, 2) or fut.shape[-1] < 1 or (fut.ndim == 2 and fut.shape[0] != N):
+        raise ValueError('last_ds_ns, row_step_ns must be [N], ds_future [H] or [N][H] with H >= 1')
+    fut = np.broadcast_to(fut, (N, fut.shape[-1]))
+    ok = (step > 0) & (last != np.iinfo(np.int64).min)
+    ok &= (np.diff(fut, axis=1) == step[:, None]).all(axis=1)
+    first = fut[:, 0]
+    ok &= first > last                                      # (compared first: the difference below cannot wrap)
+    ahead = np.where(ok, first - np.where(ok, last, first), 0)
+    safe = np.where(ok, step, 1)
+    ok &= ahead % safe == 0
+    return np.where(ok, ahead // safe, 0).astype(np.int64), ok
 
 
 def _noise_ar_phi(noise_ar, N, ds_future_ns):

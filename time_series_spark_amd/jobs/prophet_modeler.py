@@ -247,7 +247,50 @@ def _empty_screened():
                          'center': np.zeros(0), 'scale': np.zeros(0)}, columns=SCREENED_COLUMNS)
 
 
-def fit_packed(panel, floor, cap, kw, devices=None, cost=None, lap=None, screen=None, removed=None):
+NOISE_DEFAULTS = {'phi_max': 0.95, 'min_pairs': 8}
+NOISE_FIELDS = ['phi', 'phi_raw', 'n_pairs', 'scale', 'status', 'last_resid', 'last_gap', 'last_ds_ns']
+NOISE_COLUMNS = ['series_id', 'dim_id'] + NOISE_FIELDS + ['row_step_ns']
+_NOISE_DTYPES = {'phi': np.float64, 'phi_raw': np.float64, 'n_pairs': np.int64, 'scale': np.float64, 'status': np.int32,
+                 'last_resid': np.float64, 'last_gap': np.int32, 'last_ds_ns': np.int64}
+
+
+def noise_settings(config):
+    """config['model']['noise'] (optional, not in the reference): the AR(1) noise state of every fit (fc.fit_noise_state:
+    each series' residual autocorrelation and the residual of its last present row, from the history the fit has just
+    seen), for the scorer's forecast.noise.  None without the section; else the keywords phi_max, min_pairs of
+    fc.fit_noise_state, defaults filled in (an empty mapping: the defaults).  An unknown key or a value the library
+    would refuse raises ValueError."""
+    model = config.get('model') or {}
+    if 'noise' not in model:
+        return None
+    sec = {} if model['noise'] is None else model['noise']
+    if not isinstance(sec, dict):
+        raise ValueError('model.noise must be a mapping (phi_max, min_pairs)')
+    unknown = sorted(set(sec) - set(NOISE_DEFAULTS))
+    if unknown:
+        raise ValueError('model.noise: unknown key(s) %s (known: %s)' % (unknown, sorted(NOISE_DEFAULTS)))
+    out = dict(NOISE_DEFAULTS, **sec)
+    out['phi_max'] = float(out['phi_max'])
+    fc._ar_args(out['phi_max'], out['min_pairs'])            # (ValueError)
+    out['min_pairs'] = int(out['min_pairs'])
+    return out
+
+
+def check_noise_io(config):
+    """io.noise is where model.noise's table goes: the one without the other is an error of the configuration."""
+    if (config.get('io') or {}).get('noise') and noise_settings(config) is None:
+        raise ValueError('io.noise needs model.noise')
+
+
+def _empty_noise():
+    cols = {'series_id': np.zeros(0, np.int32), 'dim_id': np.zeros(0, np.int32)}
+    cols.update((f, np.zeros(0, _NOISE_DTYPES[f])) for f in NOISE_FIELDS)
+    cols['row_step_ns'] = np.zeros(0, np.int64)
+    return pd.DataFrame(cols, columns=NOISE_COLUMNS)
+
+
+def fit_packed(panel, floor, cap, kw, devices=None, cost=None, lap=None, screen=None, removed=None, noise=None,
+               noise_out=None):
     """Fit every series of a PackedPanel.  Series are bucketed by the seasonality set
     fbprophet's 'auto' rules give their own history (each Prophet object decides alone), one
     kernel launch per bucket.  Returns (pieces, status, n_iter): pieces = [(members, buffer)] -- the blobs of one fit
@@ -257,7 +300,10 @@ def fit_packed(panel, floor, cap, kw, devices=None, cost=None, lap=None, screen=
     scheduling hints for the launches (tsf_set_cost_hints); results do not depend on them.
     screen: screen_settings(config) or None -- every fit call becomes fc.fit_screened with these keywords (same spec,
     same groups, same Newton retry on top); removed: a dict that then receives, per series with flagged rows,
-    (ds, y, resid, center, scale) of those rows (a later fit of the series supersedes an earlier one)."""
+    (ds, y, resid, center, scale) of those rows (a later fit of the series supersedes an earlier one).
+    noise: noise_settings(config) or None -- behind every fit call fc.fit_noise_state on the same arrays (with `screen`
+    the flagged rows as `excluded`); noise_out: a dict {field: [N] array} (NOISE_FIELDS) that receives each series'
+    state (a later fit of the series supersedes an earlier one)."""
     N = panel.N
     lap = lap or (lambda name: None)
     hint = (lambda mem: None) if cost is None else (lambda mem: np.asarray(cost)[mem])
@@ -277,11 +323,22 @@ def fit_packed(panel, floor, cap, kw, devices=None, cost=None, lap=None, screen=
     lap('specs')
 
     def fit_call(spec, mem, ds, y, off, fl, cp, ex):
-        """fit_aligned (off None: y [G][T]) / fit_ragged of the series mem -- or, with `screen`, fit_screened"""
+        """fit_plain, and with `noise` the noise state of its fits"""
+        res, flag = fit_plain(spec, mem, ds, y, off, fl, cp, ex)
+        if noise is not None:
+            est = fc.fit_noise_state(spec, res, ds, y, offsets=off, floor=fl, cap=cp, extra=ex, excluded=flag, **noise)
+            for f in NOISE_FIELDS:
+                noise_out[f][mem] = getattr(est, f)
+            lap('fit_noise_state %d' % len(mem))
+        return res
+
+    def fit_plain(spec, mem, ds, y, off, fl, cp, ex):
+        """fit_aligned (off None: y [G][T]) / fit_ragged of the series mem -- or, with `screen`, fit_screened;
+        -> (FitResult, the flagged rows in y's layout or None)"""
         if screen is None:
             if off is None:
-                return fc.fit_aligned(spec, ds, y, floor=fl, cap=cp, extra=ex, devices=devices, **_hint_kw(hint(mem)))
-            return fc.fit_ragged(spec, off, ds, y, floor=fl, cap=cp, extra=ex, devices=devices, **_hint_kw(hint(mem)))
+                return fc.fit_aligned(spec, ds, y, floor=fl, cap=cp, extra=ex, devices=devices, **_hint_kw(hint(mem))), None
+            return fc.fit_ragged(spec, off, ds, y, floor=fl, cap=cp, extra=ex, devices=devices, **_hint_kw(hint(mem))), None
         sf = fc.fit_screened(spec, ds, y, offsets=off, floor=fl, cap=cp, extra=ex, devices=devices, **screen)
         if removed is not None:
             sc = sf.screen
@@ -295,7 +352,7 @@ def fit_packed(panel, floor, cap, kw, devices=None, cost=None, lap=None, screen=
                     rows = int(off[g]) + np.flatnonzero(sc.flag[int(off[g]):int(off[g + 1])])
                     rec = (ds[rows], y[rows], sc.resid[rows])
                 removed[int(mem[g])] = rec + (float(sc.center[g]), float(sc.scale[g]))
-        return sf.fit
+        return sf.fit, sf.screen.flag
 
     def run(spec, sd, seas, members):
         """One optimiser over `members`: series that share a timestamp vector are fitted
@@ -519,14 +576,20 @@ def _model_packed(config, panel, n_rows, execution_time, previous=None, lap=None
     lap('checks + hints')
     screen = screen_settings(config)
     removed = {} if screen is not None else None
+    noise = noise_settings(config)
+    check_noise_io(config)
+    noise_out = None if noise is None else {f: np.zeros(panel.N, _NOISE_DTYPES[f]) for f in NOISE_FIELDS}
     pieces, status, n_iter = fit_packed(panel, floors, cap, kw, devices=config.get('devices'), cost=cost, lap=lap,
-                                        **({} if screen is None else {'screen': screen, 'removed': removed}))
+                                        **({} if screen is None else {'screen': screen, 'removed': removed}),
+                                        **({} if noise is None else {'noise': noise, 'noise_out': noise_out}))
     lap('fit_packed tail')
     sids = panel.keys['series_id'].to_numpy()
     dids = panel.keys['dim_id'].to_numpy()
     out = ModelBatch(sids, dids, floor, cap, pieces, status, n_iter)
     if removed is not None:
         out.screened = _screened_frame(sids, dids, removed)
+    if noise is not None:
+        out.noise = _noise_frame(sids, dids, out.keep, noise_out, pk.per_series_stats(panel)[1], panel.last_ds_all)
     for n in np.flatnonzero(out.piece_of < 0):
         # pystan RuntimeError -> the reference prints and drops the series (:81-85)
         print(f"Runtime error {_lib.STATUS_NAMES.get(int(status[n]), status[n])} for "
@@ -547,6 +610,27 @@ def _screened_frame(sids, dids, removed):
                          'ds': cat(0).astype('datetime64[ns]'), 'y': cat(1).astype(np.float64), 'resid': cat(2),
                          'center': rep([removed[n][3] for n in order]), 'scale': rep([removed[n][4] for n in order])},
                         columns=SCREENED_COLUMNS)
+
+
+def _noise_frame(sids, dids, keep, noise_out, min_dt, last_ds_all=None):
+    """model.noise's table (NOISE_COLUMNS): one row per fitted series, in model order; row_step_ns is the series'
+    smallest spacing (per_series_stats: -1 for a one-row series), what the scorer measures the forecast's lead in."""
+    cols = {'series_id': np.asarray(sids)[keep].astype(np.int32), 'dim_id': np.asarray(dids)[keep].astype(np.int32)}
+    cols.update((f, noise_out[f][keep]) for f in NOISE_FIELDS)
+    step = np.asarray(min_dt, dtype=np.int64)[keep]
+    if last_ds_all is not None:
+        # The model's history ends at its last date INCLUDING rows whose y is null (fit_packed: last_ds), which the packed
+        # panel does not hold: such trailing rows lie behind the last present row like any other absent row.  Where they
+        # are whole steps they join last_gap; where not, the series has no row grid the chain could run on (row_step -1).
+        tail = np.asarray(last_ds_all, dtype=np.int64)[keep] - cols['last_ds_ns']
+        more = tail > 0
+        whole = more & (step > 0) & (tail % np.where(step > 0, step, 1) == 0)
+        cols['last_gap'] = np.where(whole, cols['last_gap'] + tail // np.where(step > 0, step, 1),
+                                    cols['last_gap']).astype(np.int32)
+        step = np.where(more & ~whole, -1, step)
+        cols['last_ds_ns'] = np.where(more, cols['last_ds_ns'] + tail, cols['last_ds_ns'])
+    cols['row_step_ns'] = step
+    return pd.DataFrame(cols, columns=NOISE_COLUMNS)
 
 
 def model_panel(config):
@@ -936,6 +1020,22 @@ class ProphetModeler:
                 os.remove(os.path.join(path, f))
         out.to_parquet(os.path.join(path, 'part-00000.parquet'), index=False)
 
+    def persist_noise(self, batches):
+        """config['io']['noise'] (optional, with model.noise): the fits' AR(1) noise state, one row per model
+        (NOISE_COLUMNS), as one parquet part in that directory, mode='overwrite' like the models -- what the scorer's
+        forecast.noise.table reads."""
+        path = self.config['io'].get('noise')
+        if not path:
+            return
+        check_noise_io(self.config)
+        frames = [b.noise for b in batches if b is not None and getattr(b, 'noise', None) is not None]
+        out = pd.concat(frames, ignore_index=True) if frames else _empty_noise()
+        os.makedirs(path, exist_ok=True)
+        for f in os.listdir(path):
+            if f.endswith('.parquet'):
+                os.remove(os.path.join(path, f))
+        out.to_parquet(os.path.join(path, 'part-00000.parquet'), index=False)
+
     def _clear_models(self):
         """-> function that waits until the previous run's files are gone (pipeline.clear_directory)"""
         from ..pipeline import clear_directory
@@ -993,6 +1093,7 @@ class ProphetModeler:
         signature compatibility and may be None.  return_frame=False: return nothing, as the reference's does (the
         drivers; a chunked run then never builds the frame)."""
         scorer = ProphetModeler(config)
+        check_noise_io(config)              # (before anything is read or overwritten)
         # A re-run overwrites io.models (:123-125).  Before it does, what the previous run left there gives this run
         # its scheduling hints: the iteration count of every model, the one cheap predictor of how long each fit takes,
         # so that the launches start their longest fits first (the reference's model on 100 000 series: 1.00 -> 0.84 s
@@ -1022,6 +1123,7 @@ class ProphetModeler:
         # same rows as a frame for callers that want one
         batch = fit(*scorer.read_input_columns())
         scorer.persist_screened([batch])
+        scorer.persist_noise([batch])
         if batch is None:
             scorer.persist_models(_empty_models())
             return _empty_models() if return_frame else None
@@ -1056,6 +1158,7 @@ class ProphetModeler:
         if not cleared:
             self._clear_models()()
         self.persist_screened([b for _k, b, _part in done])
+        self.persist_noise([b for _k, b, _part in done])
         live = [(b, part) for _k, b, part in done if part is not None]
         if live:
             _write_cost_sidecar(self.config['io']['models'], [part for _b, part in live],

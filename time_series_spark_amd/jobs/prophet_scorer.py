@@ -49,6 +49,101 @@ def _future_extra(spec, fut):
     return fc.conditional_extra(spec, fut, extra=ex[:, :spec.n_user_extra, :])
 
 
+NOISE_KEYS = ('table', 'point')
+
+
+def noise_settings(config):
+    """forecast.noise of a scorer configuration (optional, not in the reference) -> {'table': path, 'point': bool}, or
+    None without the key.  table: the parquet the modeler's io.noise wrote (model.noise: each model's AR(1) noise state
+    at the end of its history); point (default true): the point forecast and the draws start conditioned on the last
+    residual -- false: the draws take the plain phi, the stationary chain, and yhat is what it was.  ValueError for an
+    unknown key, a missing table, and the combinations that cannot be honoured: forecast.calibration (its table was built
+    from uncorrected errors), forecast.components (that entry refuses the setting), more than one device."""
+    fcfg = config.get('forecast') or {}
+    if 'noise' not in fcfg or fcfg['noise'] is None:
+        return None
+    sec = fcfg['noise']
+    if not isinstance(sec, dict):
+        raise ValueError('forecast.noise must be a mapping (table, point)')
+    unknown = sorted(set(sec) - set(NOISE_KEYS))
+    if unknown:
+        raise ValueError('forecast.noise: unknown key(s) %s (known: %s)' % (unknown, sorted(NOISE_KEYS)))
+    if not sec.get('table'):
+        raise ValueError('forecast.noise.table: the path of the modeler\'s io.noise is required')
+    point = sec.get('point', True)
+    if not isinstance(point, (bool, np.bool_)):
+        raise ValueError('forecast.noise.point must be true or false')
+    if fcfg.get('calibration'):
+        raise ValueError('forecast.noise together with forecast.calibration: the calibration table was built from '
+                         'uncorrected errors')
+    if fcfg.get('components'):
+        raise ValueError('forecast.noise together with forecast.components: the components\' draws refuse the setting')
+    if fc.resolve_devices(config.get('devices')) is not None:
+        raise ValueError('forecast.noise on more than one device: the noise setting belongs to one context')
+    return {'table': str(sec['table']), 'point': bool(point)}
+
+
+class NoiseTable(object):
+    """forecast.noise.table, read once and joined on (series_id, dim_id) as the calibration table is: per frame of
+    models the noise_ar= of the library calls.  Models without a row, with status != 0 (no phi was estimated) or whose
+    future rows do not continue their history's row grid (fc.noise_lead: a weekly forecast of a daily history) are
+    scored exactly as without the key -- phi = 0, which every entry takes as the independent expression bit for bit --
+    counted, and reported in one printed line per call."""
+
+    def __init__(self, settings):
+        self.point = settings['point']
+        df = pd.read_parquet(settings['table'])
+        self.est = fc.NoiseAR.from_frame(df)
+        if self.est.last_ds_ns is None or 'row_step_ns' not in df.columns:
+            raise ValueError('forecast.noise.table: not a table of the modeler\'s io.noise (last_ds_ns, row_step_ns)')
+        self.row_step = df['row_step_ns'].to_numpy().astype(np.int64)
+        self.where = {k: i for i, k in enumerate(zip(df['series_id'].tolist(), df['dim_id'].tolist()))}
+        self.counts = np.zeros(5, np.int64)
+
+    def report(self):
+        """the one line of a call: how many of its models were scored as without the key, and why"""
+        c, self.counts = self.counts, np.zeros(5, np.int64)
+        print('forecast.noise: %d of %d models scored without it (%d without a table row, %d without an estimate, '
+              '%d whose forecast rows do not continue the history\'s)' % (c[1], c[0], c[2], c[3], c[4]))
+
+    def noise_ar(self, sids, dids, last_ds_ns, fut):
+        """-> what noise_ar= takes for these models (a NoiseARStart with `point`, else phi [n]), or None where no
+        model of the frame takes part; the counts go to report()."""
+        at = np.array([self.where.get(k, -1) for k in zip(np.asarray(sids).tolist(), np.asarray(dids).tolist())],
+                      dtype=np.int64)
+        have = at >= 0
+        row = np.maximum(at, 0)
+        est = self.est
+        stale = np.flatnonzero(have & (est.last_ds_ns[row] != np.asarray(last_ds_ns, dtype=np.int64)))
+        if len(stale):
+            j = int(stale[0])
+            raise ValueError('forecast.noise.table is stale: series_id %d, dim_id %d ends at %s in the table and at %s in '
+                             'its model' % (int(sids[j]), int(dids[j]),
+                                            np.int64(est.last_ds_ns[row[j]]).view('datetime64[ns]'),
+                                            np.int64(last_ds_ns[j]).view('datetime64[ns]')))
+        estimated = have & (est.status[row] == _lib.AR_OK)
+        lead, ok = fc.noise_lead(last_ds_ns, np.where(have, self.row_step[row], -1), fut)
+        use = estimated & ok
+        self.counts += np.array([len(use), int((~use).sum()), int((~have).sum()), int((have & ~estimated).sum()),
+                                 int((estimated & ~ok).sum())])
+        if not use.any():
+            return None
+        phi = np.where(use, est.phi[row], 0.0)
+        if not self.point:
+            return phi
+        steps = np.where(use, est.last_gap[row].astype(np.int64) + lead, 1)
+        return fc.NoiseARStart(phi, np.where(use, est.last_resid[row], 0.0), steps)
+
+
+def _noise_rows(noise_ar, sel):
+    """the series `sel` of a noise_ar= value"""
+    if noise_ar is None:
+        return None
+    if isinstance(noise_ar, fc.NoiseARStart):
+        return fc.NoiseARStart(noise_ar.phi[sel], noise_ar.resid[sel], noise_ar.steps[sel])
+    return noise_ar[sel]
+
+
 def forecast_arrays(config):
     """The predict UDF on columns that never were a DataFrame: (series_id, dim_id, floor, cap, models) -> dict of the
     forecast frame's columns (series_id, dim_id int32; ds int64 ns; yhat int32; yhat_lower / yhat_upper when
@@ -62,6 +157,8 @@ def forecast_arrays(config):
     (panel.model_column_buffer: a parquet column as it lies in memory, no Python object per series)."""
 
     table = []          # forecast.calibration, read at the first frame: [Calibration, {(series_id, dim_id): row}]
+    noise = noise_settings(config)          # (a refused combination fails here, before any launch)
+    noise_table = []    # forecast.noise.table, read at the first frame
 
     def calibration_of(sid, did):
         """the rows of the calibration table for these models as a Calibration of their own (no row: no cell)"""
@@ -108,12 +205,24 @@ def forecast_arrays(config):
             lap('future_dates')
             floor, cap = floors[idx], caps[idx]                          # :67-68
             ex = _future_extra(spec, fut)
+            nar = None
+            if noise is not None:
+                if not noise_table:
+                    noise_table.append(NoiseTable(noise))
+                nar = noise_table[0].noise_ar(sids[idx], dids[idx], rec['last_ds_ns'], fut)
+            nkw = {} if nar is None else {'noise_ar': nar}
             if len(fut) and (fut == fut[0]).all():
                 fut = np.ascontiguousarray(fut[0])           # one future grid for the batch: one shared design table on the device
-            yhat, yint = fc.predict(spec, theta, rec['y_scale'], grid, fut, floor=floor, cap=cap,
-                                    extra_future=ex if (ex is None or fut.ndim == 2) else np.ascontiguousarray(ex[0]),
-                                    want_int=True,      # :70-84
-                                    devices=config.get('devices'))
+            if isinstance(nar, fc.NoiseARStart):
+                # the corrected point forecast with its integer column (fc.predict refuses want_int beside noise_ar)
+                yhat, yint = fc.predict_conditioned(
+                    spec, theta, rec['y_scale'], grid, fut, nar, floor=floor, cap=cap,
+                    extra_future=ex if (ex is None or fut.ndim == 2) else np.ascontiguousarray(ex[0]))
+            else:
+                yhat, yint = fc.predict(spec, theta, rec['y_scale'], grid, fut, floor=floor, cap=cap,
+                                        extra_future=ex if (ex is None or fut.ndim == 2) else np.ascontiguousarray(ex[0]),
+                                        want_int=True,      # :70-84
+                                        devices=config.get('devices'))
             lap('predict')
             iv = comps = quant = calib = None
             fcfg = config.get('forecast') or {}
@@ -142,7 +251,7 @@ def forecast_arrays(config):
                     extra_future=ex if (ex is None or fut.ndim == 2) else np.ascontiguousarray(ex[0]),
                     series_key=(sids[idx].astype(np.int64) << 32) ^ (dids[idx].astype(np.int64) & 0xffffffff),
                     uncertainty_samples=int(fcfg.get('uncertainty_samples', 1000)), seed=int(fcfg.get('seed', 0)),
-                    cumulative=bool(fcfg.get('cumulative')))
+                    cumulative=bool(fcfg.get('cumulative')), **nkw)
             if fcfg.get('intervals') or fcfg.get('components'):
                 # not in the reference's output (it drops yhat_lower / yhat_upper and the components, :86): opt-in
                 # extra columns; the random streams are keyed by (series_id, dim_id), so a series gets the
@@ -160,7 +269,7 @@ def forecast_arrays(config):
                     if fcfg.get('intervals'):
                         iv = (comps.yhat_lower, comps.yhat_upper)
                 else:
-                    _, lo, hi = fc.predict_intervals(spec, theta, rec['y_scale'], grid, fut, **kw)
+                    _, lo, hi = fc.predict_intervals(spec, theta, rec['y_scale'], grid, fut, **kw, **nkw)
                     iv = (lo, hi)
             for j in np.flatnonzero((np.trunc(yhat) < floor[:, None]).any(axis=1)):
                 print(f"Negative forecast values found for series_id: {int(sids[idx[j]])}, "
@@ -169,6 +278,8 @@ def forecast_arrays(config):
                 fut = np.broadcast_to(fut, (len(idx), periods))
             pieces.append((idx, fut, yint, iv, comps, quant, calib))
             lap('negative check')
+        if noise_table:
+            noise_table[0].report()
         if not pieces:
             return None
 
@@ -260,6 +371,8 @@ def rollup_panel(config):
         blobs = [None if (b is None or isinstance(b, float)) else b for b in pdf['model'].tolist()]
         uniq, group = fc.rollup_groups(sids.astype(np.int64))
         roll = cal = None
+        noise = noise_settings(config)
+        noise_table = NoiseTable(noise) if noise is not None else None
         try:
             for spec_dict, idx, rec in pk.load_models(blobs):
                 spec = fc.ModelSpec.from_dict(spec_dict)
@@ -279,9 +392,13 @@ def rollup_panel(config):
                     roll = fc.Rollup(cal, len(uniq), uncertainty_samples=int(fcfg.get('uncertainty_samples', 1000)),
                                      seed=int(fcfg.get('seed', 0)))
                 ex = _future_extra(spec, fut[:1])                # (one calendar: one set of columns for the bucket)
+                nar = None if noise_table is None else noise_table.noise_ar(sids[idx], dids[idx], rec['last_ds_ns'], fut)
                 roll.add(spec, theta, rec['y_scale'], pk.grid_from_records(rec), group[idx],
                          (sids[idx].astype(np.int64) << 32) ^ (dids[idx].astype(np.int64) & 0xffffffff),
-                         floor=floors[idx], cap=caps[idx], extra_future=None if ex is None else ex[0])
+                         floor=floors[idx], cap=caps[idx], extra_future=None if ex is None else ex[0],
+                         **({} if nar is None else {'noise_ar': nar}))
+            if noise_table is not None:
+                noise_table.report()
             if roll is None:
                 return pd.DataFrame(columns=['series_id', 'ds', 'yhat', 'count'] + names + cum_names)
             r = roll.quantiles(levels, cumulative=cumulative)
@@ -354,6 +471,8 @@ def period_panel(config):
         floors, caps = pdf['floor'].to_numpy(dtype=np.float64), pdf['cap'].to_numpy(dtype=np.float64)
         blobs = [None if (b is None or isinstance(b, float)) else b for b in pdf['model'].tolist()]
         parts = []              # (row of the model frame, its K rows as a dict of columns)
+        noise = noise_settings(config)
+        noise_table = NoiseTable(noise) if noise is not None else None
         for spec_dict, idx, rec in pk.load_models(blobs):
             spec = fc.ModelSpec.from_dict(spec_dict)
             theta = np.zeros((len(idx), spec.theta_stride))
@@ -361,6 +480,7 @@ def period_panel(config):
             grid = pk.grid_from_records(rec)
             fut = pk.future_dates(rec['last_ds_ns'], periods, frequency)
             ex = _future_extra(spec, fut)
+            nar = None if noise_table is None else noise_table.noise_ar(sids[idx], dids[idx], rec['last_ds_ns'], fut)
             cals, which = np.unique(fut, axis=0, return_inverse=True)
             which = which.reshape(-1)
             for c, cal in enumerate(cals):
@@ -372,9 +492,12 @@ def period_panel(config):
                     floor=floors[idx][sel], cap=caps[idx][sel],
                     extra_future=None if ex is None else np.ascontiguousarray(ex[sel[0]]),
                     series_key=(sids[idx][sel].astype(np.int64) << 32) ^ (dids[idx][sel].astype(np.int64) & 0xffffffff),
-                    uncertainty_samples=int(fcfg.get('uncertainty_samples', 1000)), seed=int(fcfg.get('seed', 0)))
+                    uncertainty_samples=int(fcfg.get('uncertainty_samples', 1000)), seed=int(fcfg.get('seed', 0)),
+                    **({} if nar is None else {'noise_ar': _noise_rows(nar, sel)}))
                 for j, n in enumerate(sel):
                     parts.append((int(idx[n]), r.frame(j)))
+        if noise_table is not None:
+            noise_table.report()
         if not parts:
             return pd.DataFrame(columns=['series_id', 'dim_id'] + period_columns(levels))
         parts.sort(key=lambda p: p[0])
